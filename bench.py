@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py — frames/s of the YOLOv3 hot path (Darknet.forward + write_results) on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--res 608] [--batch 8]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--res 608] [--batch 8] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Both launch forms work: started plainly with ``--gpus N > 1`` (no WORLD_SIZE in the environment) this process starts N
@@ -13,10 +13,16 @@ N > 1, the fixed-capacity RCCL all-gather of the detections (shard.FixedGather).
 sharded (weak scaling: every rank runs its own ``--batch`` frames), no collective on the data path except that final
 gather.  Rank 0 prints ONE JSON line.
 
+A plain run sets up, warms up, times the K steps, writes the last step's outputs (``--dump-outputs DIR``) and prints the line
+with the headline figure.  ``--full`` adds everything else below (second and third timed runs, the instrumented roofline
+replay, the other workloads and the CPU baseline), after the headline's timed run and dump.
+
 What the numbers in the line are (all measured in this run, same plans, same inputs):
   value         K steps between barrier + device-synchronise pairs, ``--inflight`` batches in flight (default 2: steps
                 alternate over two plans on two HIP streams), ``write_results_async`` (device-side counts, no host sync)
-                on a third stream.  The throughput-serving schedule; the metric string says so.
+                on a third stream.  The throughput-serving schedule; the metric string says so.  ``ms_per_step`` = the
+                timed region / K.
+  --full only:
   single_stream one batch in flight: forward i+1 starts after forward i (write_results_async still on its own stream).
   dropin_api    the reference's calling sequence verbatim (detect.py:62-70): ``y = model(x)``;
                 ``write_results(y, 80, conf, nms)`` returning a new [D,8] tensor — one plan, one stream, the host
@@ -40,6 +46,7 @@ import time
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
+DUMP_BYTES = 64 * 10**6             # --dump-outputs: payload of all .npy files together
 PEAK_FP32_MFMA_TFLOPS = 157.3
 PEAK_F16_MFMA_TFLOPS = 2500.0        # dense f16/bf16 MFMA; the split kernel issues 3 products per algorithmic MAC
 HBM_PEAK_GBS = 8000.0
@@ -63,7 +70,7 @@ def parse_args(argv=None):
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--opt", action="append", default=[], metavar="NAME=INT",
                     help="plan option (rtod_plan_set_option) for A/B runs, e.g. --opt k_slices=0; recorded in config.plan_options")
-    ap.add_argument("--layers-out", default="", help="write the per-launch table (JSON) here")
+    ap.add_argument("--layers-out", default="", help="write the per-launch table (JSON) of the --full roofline replay here")
     ap.add_argument("--tiles", default="", metavar="FILE",
                     help="tile table (JSON): if FILE holds a table for this resolution / batch it is installed (rtod_plan_set_tiles: no autotune "
                          "launches, the same kernels in every process — profiled passes replay the timing pass); otherwise autotune runs and "
@@ -71,6 +78,11 @@ def parse_args(argv=None):
     ap.add_argument("--no-extras", action="store_true",
                     help="skip the extra workloads reported beside the headline (BASELINE configs[1]: YOLOv3 416x416 batch 8; configs[4]'s "
                          "shape: the YOLOv5s-style graph 640x640 batch 8, parity unpinned)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: single_stream, dropin_api, roofline (--layers-out), the extra "
+                         "workloads, as_run_bn and the CPU baseline (--no-roofline / --no-extras / --no-cpu-baseline drop parts of it)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last step returned as DIR/<name>.npy (see dump_outputs)")
     return ap.parse_args(argv)
 
 
@@ -109,6 +121,31 @@ def self_launch(args):
                     procs[q].terminate()                    # exact PIDs this process started
         time.sleep(0.05)
     return rc
+
+
+# ------------------------------------------------------------------------------------------ outputs of the timed path
+def dump_outputs(out_dir, y, det, counts, B):
+    """What a caller of the timed step received from the last one, as .npy files: predictions.npy = the forward's [B, N, 85]
+    float32 tensor, detections.npy = write_results' [D, 8] float32 rows (N > 1: gathered over the ranks), detection_counts.npy
+    = float64 [D, candidates, detections of image 0 .. B-1].  If the predictions do not fit in DUMP_BYTES beside the rest,
+    predictions.npy holds a fixed seeded sample of their rows ([k, 85]) and predictions_rows.npy (float64) the flat row
+    indices (b * N + n) of that sample."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"detections": np.zeros((0, 8), np.float32) if isinstance(det, int) else det.float().cpu().numpy(),
+              "detection_counts": counts[:2 + B].cpu().numpy().astype(np.float64)}
+    pred = y.float().cpu().numpy()
+    room = DUMP_BYTES - sum(a.nbytes for a in arrays.values()) - 4096      # .npy headers
+    if pred.nbytes <= room:
+        arrays["predictions"] = pred
+    else:
+        rows = pred.reshape(-1, pred.shape[-1])
+        k = min(rows.shape[0], room // (rows.shape[1] * 4 + 8))
+        idx = np.sort(np.random.default_rng(0).choice(rows.shape[0], size=k, replace=False))
+        arrays["predictions"] = rows[idx]
+        arrays["predictions_rows"] = idx.astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 # ------------------------------------------------------------------------------------------ model / baselines
@@ -506,33 +543,36 @@ def run_rank(args):
         json.dump(tabs, open(args.tiles, "w"))
     dt, (y, rows, counts) = timed_run(step, len(models))
     n_det, n_cand = [int(v) for v in counts[:2].tolist()]
-    gathered = None
+    gathered = g = None
     if gather is not None:
         g = gather.compact()                            # content check of the last step's gather (host side, untimed)
         gathered = 0 if isinstance(g, int) else int(g.size(0))
     overflow = any(m_.overflowed() for m_ in models)    # split-f16 range guard over everything run so far
+    if args.dump_outputs and rank == 0:                 # before --full: its runs overwrite the plans' outputs
+        dump_outputs(args.dump_outputs, y, g if gather is not None else rows[:min(n_det, CAP)], counts, B)
 
     def rate(dt_):
         return round(world * B * args.steps / dt_, 2), round(dt_ / args.steps * 1e3, 4)
 
-    single = None
-    if len(models) > 1:                                 # the strictly sequential figure beside the pipelined one
+    fps, ms_step = rate(dt)
+    single = dropin = None
+    if args.full and len(models) > 1:                   # the strictly sequential figure beside the pipelined one
         dt1, _ = timed_run(step, 1)
         v, ms = rate(dt1)
         single = {"value": v, "unit": "frames/s", "ms_per_step": ms,
                   "note": "one batch in flight (forward i+1 starts after forward i); write_results_async on a second stream"}
-    model.overflow_check = "write_results"
-    dtd, (_, det, _) = timed_run(step_dropin, 1)
-    model.overflow_check = "off"
-    v, ms = rate(dtd)
-    dropin = {"value": v, "unit": "frames/s", "ms_per_step": ms,
-              "detections_last_step": 0 if isinstance(det, int) else int(det.size(0)),
-              "note": "reference calling sequence: y = model(x); write_results(y, 80, conf, nms) -> new [D,8] tensor; one plan, "
-                      "one stream, write_results' host sync (and the split-f16 range check) inside every step"}
-    fps, ms_step = rate(dt)
+    if args.full:
+        model.overflow_check = "write_results"
+        dtd, (_, det, _) = timed_run(step_dropin, 1)
+        model.overflow_check = "off"
+        v, ms = rate(dtd)
+        dropin = {"value": v, "unit": "frames/s", "ms_per_step": ms,
+                  "detections_last_step": 0 if isinstance(det, int) else int(det.size(0)),
+                  "note": "reference calling sequence: y = model(x); write_results(y, 80, conf, nms) -> new [D,8] tensor; one plan, "
+                          "one stream, write_results' host sync (and the split-f16 range check) inside every step"}
 
     roof = None
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         roof, per_layer, groups = roofline_from_launches(model, x, max(1, min(args.steps, 10)))
         # HBM bytes per launch of that kernel: PMC counters need rocprofv3 around the process, so this run cannot measure them;
         # the figure comes from the committed passes of this same command with the tile table frozen (profiles/traffic.json,
@@ -552,14 +592,14 @@ def run_rank(args):
             json.dump({"per_launch": per_layer, "groups": groups}, open(args.layers_out, "w"), indent=1)
     n_inflight = len(models)
     other = None
-    if rank == 0 and world == 1 and not args.no_extras and R == 608 and B == 8:
+    if rank == 0 and world == 1 and args.full and not args.no_extras and R == 608 and B == 8:
         del extra, models[1:]                           # their arenas are not needed any more
         other = extra_workloads(dev, args)
     as_run = None
-    if rank == 0 and world == 1 and not args.no_extras and R == 608 and B == 8:
+    if rank == 0 and world == 1 and args.full and not args.no_extras and R == 608 and B == 8:
         as_run = as_run_bn_workload(dev, args)
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline(cfg_text, w, R, B, args.conf, args.nms)
 
     if rank == 0:
@@ -586,7 +626,8 @@ def run_rank(args):
             line["config"]["gathered_detections_last_step"] = gathered
         if single is not None:
             line["single_stream"] = single
-        line["dropin_api"] = dropin
+        if dropin is not None:
+            line["dropin_api"] = dropin
         if roof is not None:
             line["roofline"] = roof
         if other is not None:

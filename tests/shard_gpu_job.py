@@ -89,7 +89,7 @@ def main():
         with open(os.path.join(out, "bench.json"), "w") as fo, open(os.path.join(out, "bench.log"), "w") as fe:
             try:
                 r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--res", str(RES), "--batch", str(B), "--steps", str(STEPS),
-                                    "--warmup", "1", "--no-extras", "--no-cpu-baseline", "--no-roofline"], env=env, stdout=fo, stderr=fe, timeout=900)
+                                    "--warmup", "1", "--full", "--no-extras", "--no-cpu-baseline", "--no-roofline"], env=env, stdout=fo, stderr=fe, timeout=900)
                 status["stage2_rc"] = r.returncode
             except subprocess.TimeoutExpired:
                 status["stage2_rc"] = -9

@@ -1,9 +1,8 @@
 """Pin the CPU oracle (oracle/darknet_ref.py) against fixtures captured from the REAL reference.
 
-The fixtures under tests/golden/ were written by tests/golden/make_golden.py, which imports
-/root/reference (uguryagmur/RealTimeObjectDetection) in the build container.  These tests are CPU
-only and run everywhere; the ``reference``-marked ones additionally compare against the live
-reference when it is mounted.
+The fixtures under tests/golden/ were written by tests/golden/make_golden*.py, which import a
+checkout of the reference (uguryagmur/RealTimeObjectDetection).  These tests are CPU only and read
+nothing but those fixtures.
 """
 import json
 import os
@@ -13,7 +12,7 @@ import pytest
 import torch
 
 from realtimeobjectdetection_amd import cfgs, synth
-from realtimeobjectdetection_amd.cfg import parse_cfg_text, parse_cfg, build_ir
+from realtimeobjectdetection_amd.cfg import parse_cfg_text, build_ir
 from oracle import darknet_ref as O
 
 NETS = {"yolov3-tiny": cfgs.yolov3_tiny_cfg, "yolov3": cfgs.yolov3_cfg}
@@ -55,10 +54,10 @@ def test_rows_and_flops():
         assert abs(ir.conv_flops / 1e9 - gflop) < 5e-3 * gflop, ir.conv_flops / 1e9
 
 
-@pytest.mark.reference
 @pytest.mark.parametrize("net", list(NETS))
-def test_generated_cfg_equals_reference_cfg(net):
-    ref_blocks = parse_cfg(f"/root/reference/cfg/{net}.cfg")
+def test_generated_cfg_equals_reference_cfg(golden_dir, net):
+    """Against the reference's cfg files as parsed by parse_cfg (tests/golden/make_golden_refcheck.py: ref_cfg_blocks.json)."""
+    ref_blocks = json.load(open(os.path.join(golden_dir, "ref_cfg_blocks.json")))[net]
     gen_blocks = parse_cfg_text(NETS[net]())
     assert len(ref_blocks) == len(gen_blocks)
     used = {"convolutional": ("batch_normalize", "filters", "size", "stride", "pad", "activation"),
@@ -181,19 +180,14 @@ def test_oracle_iou_and_mask(golden_dir):
     assert int((cm[0, :, 4] != 0).sum()) == int(g["cm_nnz_rows"])
 
 
-# ---------------------------------------------------------------- live reference (build container)
-@pytest.mark.reference
-def test_oracle_vs_live_reference_write_results():
-    import sys, types
-    sys.dont_write_bytecode = True
-    sys.modules.setdefault("cv2", types.ModuleType("cv2"))
-    sys.path.insert(0, "/root/reference")
-    from src.util import write_results as ref_wr
+# ---------------------------------------------------------------- the reference's own write_results
+def test_oracle_vs_live_reference_write_results(golden_dir):
+    """The reference's write_results on these seeded predictions, stored by tests/golden/make_golden_refcheck.py."""
+    g = _load(golden_dir, "ref_write_results.npz")
     for seed, B, N, conf, thr in ((31, 2, 1500, 0.5, 0.4), (32, 1, 4000, 0.7, 0.6), (33, 3, 800, 0.3, 0.5)):
         p = synth.synth_predictions(B, N, 80, 416, seed=seed, obj_mu=-2.5)
-        a = ref_wr(torch.from_numpy(p.copy()), 80, conf, thr)
         b = O.write_results(torch.from_numpy(p), 80, conf, thr)
-        assert np.array_equal(a.numpy(), b.numpy())
+        assert np.array_equal(g["out_%d" % seed], b.numpy())
 
 
 # ---------------------------------------------------------------- small test networks (tests/golden/make_golden_mini.py)

@@ -11,10 +11,10 @@ T=$out/tiles.json
 cd /tmp 2>/dev/null; export TMPDIR=/tmp; cd - >/dev/null
 set -e
 rm -f $T   # never replay a tile table measured on an older build
-timeout -k 10 600 python bench.py --steps 20 --warmup 5 --tiles $T --layers-out $out/layers.json > $out/bench.log 2> $out/bench.err
-timeout -k 10 300 python bench.py --steps 20 --warmup 5 --res 416 --no-cpu-baseline --no-extras > $out/bench_416.log 2>> $out/bench.err
-timeout -k 10 300 python bench.py --steps 20 --warmup 5 --precision fp32 --no-cpu-baseline --no-extras > $out/bench_fp32.log 2>> $out/bench.err
-P="--no-cpu-baseline --no-roofline --no-extras --tiles $T"
+timeout -k 10 600 python bench.py --full --steps 20 --warmup 5 --tiles $T --layers-out $out/layers.json > $out/bench.log 2> $out/bench.err
+timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 --res 416 --no-cpu-baseline --no-extras > $out/bench_416.log 2>> $out/bench.err
+timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 --precision fp32 --no-cpu-baseline --no-extras > $out/bench_fp32.log 2>> $out/bench.err
+P="--full --no-cpu-baseline --no-roofline --no-extras --tiles $T"
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -- python bench.py --steps 20 --warmup 5 $P > $out/stats.log 2>&1
 timeout -k 10 400 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $out/fetch -- python bench.py --steps 3 --warmup 1 --inflight 1 $P > $out/fetch.log 2>&1
 timeout -k 10 400 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $out/write -- python bench.py --steps 3 --warmup 1 --inflight 1 $P > $out/write.log 2>&1
