@@ -84,7 +84,8 @@ int rtod_plan_get_launch(const rtod_plan* plan, int index, rtod_launch_info* out
 int rtod_plan_describe(const rtod_plan* plan, char* buf, size_t len, size_t* needed);
 const char* rtod_conv_variant_name(int variant);
 /* Demangled name of the kernel instantiation a launch runs (what rocprofv3 --kernel-trace prints): variant from
- * rtod_launch_info, epilogue 0 plain, 1 fused shortcut, 2 fused head decode, 3 / 4 = 0 / 1 with a fused pointwise conv. */
+ * rtod_launch_info, epilogue 0 plain, 1 fused shortcut, 2 fused head decode, 3 / 4 = 0 / 1 with a fused pointwise conv;
+ * + 8: the plain-f16 instance (precision 2) of epilogues 0-2. */
 int rtod_conv_kernel_name(int variant, int epilogue, char* buf, size_t len);
 /* Same for launch `index` of a plan (all context taken from the plan; "" for launches that are not convolution kernels). */
 int rtod_plan_launch_kernel_name(const rtod_plan* plan, int index, char* buf, size_t len);
@@ -94,6 +95,14 @@ int rtod_plan_launch_kernel_name(const rtod_plan* plan, int index, char* buf, si
  *      operands, error ~2x fp32 per layer), 16x the MFMA rate per product.  Activations live in
  *      HBM as f16 hi/lo planes (x8 pre-scaled): needs |activation| < 8188, every conv after the
  *      stem with Cin % 32 == 0, no stand-alone shortcut / copy / decode launch; otherwise RTOD_E_CFG.
+ *   2  plain f16 (opt-in speed mode, not the parity path): every activation stored once as RNE_f16(8x) in the hi plane
+ *      of mode 1's layout (the lo plane is never written or read), weights = mode 1's pre-scaled hi plane, ONE
+ *      v_mfma_f32_16x16x32_f16 per fragment pair with fp32 accumulation; epilogue (scale, bias, activation, fused
+ *      shortcut, saturating store + range flag) as mode 1.  Error ~1e-3 relative end to end (profiles/f16_floor.json),
+ *      same range |activation| < 8188, same cfg requirements (RTOD_E_CFG otherwise; also with bn_batch_stats).  Kernels:
+ *      the split stem, then the generic tiles, the bandd band / wide tiles and the 1x1 slab tiles in their f16
+ *      instances (no conv_band / ring / patch tile, no fused stem + layer 1, no hosted pointwise conv).
+ * Other modes: RTOD_E_ARG.
  * cfg grammar: the reference's (src/darknet.py:412-603) plus three extension keys for YOLOv5-style blocks (detect.py:255-285
  * fetches that model from the network; only its building blocks exist here): [convolutional] activation=silu,
  * [maxpool] symmetric=1 (-inf padding of (size-1)/2 per side), [upsample] mode=nearest, [yolo] decode=v5, [route] with up to
@@ -113,7 +122,7 @@ int rtod_plan_set_precision(rtod_plan* plan, int mode);
  *   "k_slices"          exact-fp32 plans: deep small-grid layers summed in K slices (conv_igemm_f32.hip); 0: one chain
  *   "k_slice_workgroups" ... one workgroup per slice when the grid is small; 0: always inside the workgroup (same bits)
  *   "force_f16s3_variant" / "force_f32_variant"   >= 0: one tile variant for every conv (tests, A/B runs)
- * Options that leave a cfg inexpressible in the split-f16 format return RTOD_E_CFG when precision is 1. */
+ * Options that leave a cfg inexpressible in the split-f16 format return RTOD_E_CFG when precision is 1 or 2. */
 int rtod_plan_set_option(rtod_plan* plan, const char* name, int value);
 /* Split-f16 plans store activations as f16 hi/lo planes of 8*x: |activation| must stay below 8188.  Producers
  * saturate at that range (never inf / NaN) and OR 1 into *flag_dev (caller-owned device int32, zero it yourself)

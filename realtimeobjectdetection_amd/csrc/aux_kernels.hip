@@ -86,7 +86,9 @@ __global__ void upsample2x_kernel(View in, View out, int B) {
 
 // split-format variant: 8 channels (16 B of each plane) per thread; interpolation is linear, so it runs
 // directly on hi+lo (the SPLIT_SCALE factor carries through) and the result is re-split.
+// F16 (plain-f16 plans, View::split == 2): hi planes only, the result rounded to f16 (RNE).
 typedef _Float16 f16x8a __attribute__((ext_vector_type(8)));
+template <bool F16>
 __global__ void upsample2x_split_kernel(View in, View out, int B) {
     const int C8 = in.C / 8;
     const int64_t total = (int64_t)B * out.H * out.W * C8;
@@ -106,9 +108,14 @@ __global__ void upsample2x_split_kernel(View in, View out, int B) {
         auto ld = [&](int y, int x, float* v) {
             const _Float16* q = ib + ((rb + y) * in.W + x) * 2 * in.ldc + in.coff + c;
             const f16x8a h = *reinterpret_cast<const f16x8a*>(q);
-            const f16x8a l = *reinterpret_cast<const f16x8a*>(q + in.ldc);
+            if constexpr (F16) {
 #pragma unroll
-            for (int e = 0; e < 8; ++e) v[e] = (float)h[e] + (float)l[e];
+                for (int e = 0; e < 8; ++e) v[e] = (float)h[e];
+            } else {
+                const f16x8a l = *reinterpret_cast<const f16x8a*>(q + in.ldc);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) v[e] = (float)h[e] + (float)l[e];
+            }
         };
         float v00[8], v01[8], v10[8], v11[8];
         ld(y0, x0, v00); ld(y0, x1, v01); ld(y1, x0, v10); ld(y1, x1, v11);
@@ -121,7 +128,7 @@ __global__ void upsample2x_split_kernel(View in, View out, int B) {
         }
         _Float16* q = ob + (((int64_t)b * out.H + oy) * out.W + ox) * 2 * out.ldc + out.coff + c;
         *reinterpret_cast<f16x8a*>(q) = rh;
-        *reinterpret_cast<f16x8a*>(q + out.ldc) = rl;
+        if constexpr (!F16) *reinterpret_cast<f16x8a*>(q + out.ldc) = rl;
     }
 }
 
@@ -133,7 +140,8 @@ int launch_upsample2x(const View& in, const View& out, int B, hipStream_t s) {
         if (!in.base || !out.base || in.C % 8 || in.ldc % 8 || in.coff % 8 || out.ldc % 8 || out.coff % 8 ||
             out.H != 2 * in.H || out.W != 2 * in.W || out.C != in.C) { set_error("upsample2x(split): bad views"); return RTOD_E_ARG; }
         const int64_t total = (int64_t)B * out.H * out.W * (in.C / 8);
-        hipLaunchKernelGGL(upsample2x_split_kernel, dim3(grid_for(total, 256)), dim3(256), 0, s, in, out, B);
+        if (in.split == 2) hipLaunchKernelGGL(upsample2x_split_kernel<true>, dim3(grid_for(total, 256)), dim3(256), 0, s, in, out, B);
+        else hipLaunchKernelGGL(upsample2x_split_kernel<false>, dim3(grid_for(total, 256)), dim3(256), 0, s, in, out, B);
         return hip_fail(hipGetLastError(), "upsample2x(split) launch");
     }
     if (!view_ok4(in) || !view_ok4(out) || out.H != 2 * in.H || out.W != 2 * in.W || out.C != in.C) {
@@ -222,6 +230,8 @@ __global__ void maxpool_kernel(View in, View out, int B, int size, int stride, i
 
 // split-format variant: the maximum is taken over hi + lo (exact in fp32: 22 significant bits) and the winning element's
 // (hi, lo) pair is stored as it stands — no re-split, no rounding.  8 channels (16 B of each plane) per thread.
+// F16 (plain-f16 plans): the maximum over the hi plane alone, hi stored.
+template <bool F16>
 __global__ void maxpool_split_kernel(View in, View out, int B, int size, int stride, int pad) {
     const int C8 = in.C / 8;
     const int64_t total = (int64_t)B * out.H * out.W * C8;
@@ -245,17 +255,18 @@ __global__ void maxpool_split_kernel(View in, View out, int B, int size, int str
                 if (pad) { if ((unsigned)ix >= (unsigned)in.W) continue; } else if (ix > in.W - 1) ix = in.W - 1;
                 const _Float16* q = ib + (((int64_t)b * in.H + iy) * in.W + ix) * 2 * in.ldc + in.coff + c;
                 const f16x8a h = *reinterpret_cast<const f16x8a*>(q);
-                const f16x8a l = *reinterpret_cast<const f16x8a*>(q + in.ldc);
+                f16x8a l = mh;
+                if constexpr (!F16) l = *reinterpret_cast<const f16x8a*>(q + in.ldc);
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
-                    const float v = (float)h[e] + (float)l[e];
+                    const float v = F16 ? (float)h[e] : (float)h[e] + (float)l[e];
                     if (v > m[e]) { m[e] = v; mh[e] = h[e]; ml[e] = l[e]; }
                 }
             }
         }
         _Float16* o = ob + (((int64_t)b * out.H + oy) * out.W + ox) * 2 * out.ldc + out.coff + c;
         *reinterpret_cast<f16x8a*>(o) = mh;
-        *reinterpret_cast<f16x8a*>(o + out.ldc) = ml;
+        if constexpr (!F16) *reinterpret_cast<f16x8a*>(o + out.ldc) = ml;
     }
 }
 
@@ -268,7 +279,8 @@ int launch_maxpool(const View& in, const View& out, int B, int size, int stride,
     if (in.split) {
         if (!in.base || !out.base || in.C % 8 || in.coff % 8 || out.coff % 8 || in.ldc % 8 || out.ldc % 8) { set_error("maxpool: bad split views"); return RTOD_E_ARG; }
         const int64_t total = (int64_t)B * out.H * out.W * (in.C / 8);
-        hipLaunchKernelGGL(maxpool_split_kernel, dim3(grid_for(total, 256)), dim3(256), 0, s, in, out, B, size, stride, pad);
+        if (in.split == 2) hipLaunchKernelGGL(maxpool_split_kernel<true>, dim3(grid_for(total, 256)), dim3(256), 0, s, in, out, B, size, stride, pad);
+        else hipLaunchKernelGGL(maxpool_split_kernel<false>, dim3(grid_for(total, 256)), dim3(256), 0, s, in, out, B, size, stride, pad);
         return hip_fail(hipGetLastError(), "maxpool_split launch");
     }
     if (!view_ok4(in) || !view_ok4(out)) { set_error("maxpool: bad views"); return RTOD_E_ARG; }
@@ -279,7 +291,7 @@ int launch_maxpool(const View& in, const View& out, int B, int size, int stride,
 
 // ---------------------------------------------------------------------------------------------
 // nearest x2 (cfg extension `[upsample] mode=nearest`; nn.Upsample(scale_factor=2, mode="nearest")): out(y, x) = in(y/2, x/2).
-// A pure copy in either activation format (split: both planes move unchanged).
+// A pure copy in either activation format (split: both planes move unchanged; plain f16: the hi plane).
 __global__ void upsample_nearest2x_kernel(View in, View out, int B) {
     const int per = in.split ? 8 : 4;                         // channels per thread: 16 bytes of a plane / of the fp32 pixel
     const int CV = in.C / per;
@@ -295,7 +307,7 @@ __global__ void upsample_nearest2x_kernel(View in, View out, int B) {
             const _Float16* q = reinterpret_cast<const _Float16*>(in.base) + ip * 2 * in.ldc + in.coff + c;
             _Float16* o = reinterpret_cast<_Float16*>(out.base) + op * 2 * out.ldc + out.coff + c;
             *reinterpret_cast<f16x8a*>(o) = *reinterpret_cast<const f16x8a*>(q);
-            *reinterpret_cast<f16x8a*>(o + out.ldc) = *reinterpret_cast<const f16x8a*>(q + in.ldc);
+            if (in.split == 1) *reinterpret_cast<f16x8a*>(o + out.ldc) = *reinterpret_cast<const f16x8a*>(q + in.ldc);
         } else {
             *reinterpret_cast<f32x4*>(out.base + out.coff + c + op * out.ldc) = *reinterpret_cast<const f32x4*>(in.base + in.coff + c + ip * in.ldc);
         }
@@ -542,7 +554,7 @@ __global__ void view_to_nchw_kernel(View in, int B, float* __restrict__ out) {
         const int64_t pix = ((int64_t)b * in.H + y) * in.W + x;
         if (in.split) {
             const _Float16* q = reinterpret_cast<const _Float16*>(in.base) + pix * 2 * in.ldc + in.coff + c;
-            out[t] = ((float)q[0] + (float)q[in.ldc]) * (1.0f / SPLIT_SCALE);
+            out[t] = (in.split == 2 ? (float)q[0] : (float)q[0] + (float)q[in.ldc]) * (1.0f / SPLIT_SCALE);     // 2: plain f16, hi plane only
         } else {
             out[t] = in.base[pix * in.ldc + in.coff + c];
         }

@@ -126,7 +126,8 @@ int rtod_plan_launch_kernel_name(const rtod_plan* plan, int index, char* buf, si
     plan->p.fill_launch_info(index, &li, plan->p.tuned.empty() ? plan->p.max_batch : plan->p.tuned.rbegin()->first);
     buf[0] = 0;
     if (li.kind != LK_CONV || li.flops_per_frame == 0) return RTOD_OK;                 // non-conv launch / conv hosted by the previous launch: empty name
-    const int epi = li.fused_decode ? 2 : (li.fused_pointwise ? (li.fused_residual ? 4 : 3) : (li.fused_residual ? 1 : 0));
+    int epi = li.fused_decode ? 2 : (li.fused_pointwise ? (li.fused_residual ? 4 : 3) : (li.fused_residual ? 1 : 0));
+    if (plan->p.precision == 2 && li.variant >= 100) epi |= EPI_F16;              // plain-f16 instance of the split kernels
     int n = -1;
     if (li.variant == 100 + STEM2_VARIANT) n = conv_stem2_kernel_name(li.fused_pointwise, buf, len);
     else return rtod_conv_kernel_name(li.variant, epi, buf, len);
@@ -136,9 +137,9 @@ int rtod_plan_launch_kernel_name(const rtod_plan* plan, int index, char* buf, si
 }
 
 int rtod_plan_set_precision(rtod_plan* plan, int mode) {
-    if (!plan || (mode != 0 && mode != 1)) { set_error("set_precision: mode must be 0 (fp32) or 1 (f16 split)"); return RTOD_E_ARG; }
+    if (!plan || mode < 0 || mode > 2) { set_error("set_precision: mode must be 0 (fp32), 1 (f16 split) or 2 (plain f16)"); return RTOD_E_ARG; }
     if (plan->p.d_weights) { set_error("set_precision: must be called before rtod_plan_load_weights"); return RTOD_E_STATE; }
-    if (mode == 1) { const int rc = plan->p.check_split_supported(); if (rc) return rc; }
+    if (mode >= 1) { const int rc = plan->p.check_split_supported(mode); if (rc) return rc; }
     plan->p.precision = mode;
     plan->p.layout_weights();
     return RTOD_OK;

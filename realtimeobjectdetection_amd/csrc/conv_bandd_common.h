@@ -15,11 +15,14 @@ static __device__ unsigned long long g_bandd_epi[BD_EPI_BLOCKS * 5];
 #define BD_ESTAMP(slot)
 #endif
 
+// an N outside the list is a compile error (it used to emit no wait at all)
 template <int N> __device__ __forceinline__ void bandd_wait_vmcnt() {
-    static_assert(N >= 0 && N <= 16, "vmcnt literal");
+    static_assert(N >= 0 && N <= 63, "vmcnt literal");
 #define RTOD_VMCNT_CASE(n) else if constexpr (N == n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory");
     if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    RTOD_VMCNT_CASE(2) RTOD_VMCNT_CASE(4) RTOD_VMCNT_CASE(5) RTOD_VMCNT_CASE(6) RTOD_VMCNT_CASE(8) RTOD_VMCNT_CASE(9) RTOD_VMCNT_CASE(10) RTOD_VMCNT_CASE(12) RTOD_VMCNT_CASE(16)
+    RTOD_VMCNT_CASE(2) RTOD_VMCNT_CASE(3) RTOD_VMCNT_CASE(4) RTOD_VMCNT_CASE(5) RTOD_VMCNT_CASE(6) RTOD_VMCNT_CASE(7) RTOD_VMCNT_CASE(8)
+    RTOD_VMCNT_CASE(9) RTOD_VMCNT_CASE(10) RTOD_VMCNT_CASE(12) RTOD_VMCNT_CASE(14) RTOD_VMCNT_CASE(16) RTOD_VMCNT_CASE(18)
+    else static_assert(N < 0, "add the vmcnt literal");
 #undef RTOD_VMCNT_CASE
 }
 
@@ -33,25 +36,17 @@ __device__ __forceinline__ void bandd_wait_vmcnt_folded(int n) {
     }
 }
 
-// wait for all but the NBASE + 2 n youngest operations, n (0 ... 5) wave-uniform: the band pieces issued after the awaited B set
-template <int NBASE> __device__ __forceinline__ void bandd_wait_vmcnt_plus(int n) {
-    static_assert(NBASE == 4 || NBASE == 8, "two B sets of 2 or 4 loads");
+// wait for all but the NBASE + PER n youngest operations, n (0 ... 5) wave-uniform: the band pieces issued after the awaited B set
+// (PER: loads per band piece, 2 = hi + lo, 1 = hi only in plain-f16 instances)
+template <int NBASE, int PER = 2> __device__ __forceinline__ void bandd_wait_vmcnt_plus(int n) {
+    static_assert(((NBASE == 4 || NBASE == 8) && PER == 2) || ((NBASE == 2 || NBASE == 4) && PER == 1), "two B sets of 1, 2 or 4 loads");
     asm volatile("" : "+s"(n));                                 // opaque: left visible, the loop-invariant n unswitches the whole chunk loop six ways
-    if constexpr (NBASE == 8) {
-        if (n == 0) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-        else if (n == 1) asm volatile("s_waitcnt vmcnt(10)" ::: "memory");
-        else if (n == 2) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-        else if (n == 3) asm volatile("s_waitcnt vmcnt(14)" ::: "memory");
-        else if (n == 4) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(18)" ::: "memory");
-    } else {
-        if (n == 0) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-        else if (n == 1) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-        else if (n == 2) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-        else if (n == 3) asm volatile("s_waitcnt vmcnt(10)" ::: "memory");
-        else if (n == 4) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(14)" ::: "memory");
-    }
+    if (n == 0) bandd_wait_vmcnt<NBASE>();
+    else if (n == 1) bandd_wait_vmcnt<NBASE + PER>();
+    else if (n == 2) bandd_wait_vmcnt<NBASE + 2 * PER>();
+    else if (n == 3) bandd_wait_vmcnt<NBASE + 3 * PER>();
+    else if (n == 4) bandd_wait_vmcnt<NBASE + 4 * PER>();
+    else bandd_wait_vmcnt<NBASE + 5 * PER>();
 }
 
 // raw buffer load with an instruction offset (the 16-column tile of the strip: j KiB), hidden from the compiler's waitcnt pass
@@ -78,16 +73,34 @@ __device__ __forceinline__ void bandd_dma_pair(const __amdgpu_buffer_rsrc_t rsrc
         : "memory", "scc");
 }
 
-template <int TN> __device__ __forceinline__ void bandd_tie(u32x4 (&q)[TN][2]) {
+// hi piece alone (plain-f16 instances)
+__device__ __forceinline__ void bandd_dma_hi(const __amdgpu_buffer_rsrc_t rsrc, unsigned voffset, unsigned soff_hi, unsigned lds_hi) {
+    unsigned keep;
+    asm volatile(
+        "s_mov_b32 %0, m0\n\t"
+        "s_mov_b32 m0, %4\n\t"
+        "s_nop 0\n\t"
+        "buffer_load_dwordx4 %1, %2, %3 offen lds\n\t"
+        "s_mov_b32 m0, %0"
+        : "=&s"(keep)
+        : "v"(voffset), "s"(rsrc), "s"(soff_hi), "s"(lds_hi)
+        : "memory", "scc");
+}
+
+// F16: only the hi registers [j][0] are loaded (plain-f16 instances)
+template <int TN, bool F16 = false> __device__ __forceinline__ void bandd_tie(u32x4 (&q)[TN][2]) {
     static_assert(TN >= 1 && TN <= 2, "strip width");
-    if constexpr (TN == 1) asm volatile("" : "+v"(q[0][0]), "+v"(q[0][1]) :: "memory");
+    if constexpr (F16 && TN == 1) asm volatile("" : "+v"(q[0][0]) :: "memory");
+    else if constexpr (F16) asm volatile("" : "+v"(q[0][0]), "+v"(q[1][0]) :: "memory");
+    else if constexpr (TN == 1) asm volatile("" : "+v"(q[0][0]), "+v"(q[0][1]) :: "memory");
     else asm volatile("" : "+v"(q[0][0]), "+v"(q[0][1]), "+v"(q[1][0]), "+v"(q[1][1]) :: "memory");
 }
 
 // ---- epilogue: scale / bias / activation, LDS transpose in passes of RG rows, split-format store (+ residual).
 // Arithmetic and expression shapes are those of conv_f16s3_epilogue (conv_f16s3_common.h): the same bits.  Unlike that
 // function a pass may cover a PART of a wave's rows (a wave owns all BM rows of its strip; the whole tile would need 64 KB).
-template <int BM, int BN, int WM, int WN, int NT, int RG, bool RES, int KG>
+// F16: plain-f16 output (hi plane of the shortcut operand read, hi plane stored).
+template <int BM, int BN, int WM, int WN, int NT, int RG, bool RES, int KG, bool F16 = false>
 __device__ __forceinline__ void bandd_epilogue(const ConvArgs& a, f32x4 (&acc)[WM / 16][WN / 16], unsigned char* smem, int bm, int bn, int tid,
                                                int wm, int wn, int lr, int lh, int M, int kg) {
     constexpr int TM = WM / 16, TN = WN / 16, MT = 16, NE = 4, TS = BN;
@@ -134,7 +147,7 @@ __device__ __forceinline__ void bandd_epilogue(const ConvArgs& a, f32x4 (&acc)[W
                 // rows past M / channels past Cout are never stored: their operand only has to come from a valid address
                 const _Float16* qq = (er + i * RSTEP < RG && m < M && ecol) ? q : rh0;      // (a pass's last item may be partial: RG GPR items over NT threads)
                 rq_h[p][i] = *reinterpret_cast<const f16x8*>(qq);
-                rq_l[p][i] = *reinterpret_cast<const f16x8*>(qq + a.res_ldc);
+                if constexpr (!F16) rq_l[p][i] = *reinterpret_cast<const f16x8*>(qq + a.res_ldc);
                 q += rstep;
             }
         }
@@ -199,16 +212,27 @@ __device__ __forceinline__ void bandd_epilogue(const ConvArgs& a, f32x4 (&acc)[W
             const f32x4 v0 = *reinterpret_cast<const f32x4*>(T + r * TS + ec8);
             const f32x4 v1 = *reinterpret_cast<const f32x4*>(T + r * TS + ec8 + 4);
             float v[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
-            if constexpr (RES) {
+            if constexpr (RES && F16) {
+                const f16x8 qh = rq_h[rg / RG][gi];
+#pragma unroll
+                for (int e = 0; e < 8; ++e) v[e] += (float)qh[e];
+            } else if constexpr (RES) {
                 const f16x8 qh = rq_h[rg / RG][gi], ql = rq_l[rg / RG][gi];
 #pragma unroll
                 for (int e = 0; e < 8; ++e) v[e] += (float)qh[e] + (float)ql[e];
             }
-            f16x8 ph, pl;
+            if constexpr (F16) {
+                f16x8 ph;
 #pragma unroll
-            for (int e = 0; e < 8; ++e) { _Float16 h, l; split_f16(v[e], h, l, amax); ph[e] = h; pl[e] = l; }
-            store_act16(oq, ph, false);
-            store_act16(oq + a.out_ldc, pl, false);
+                for (int e = 0; e < 8; ++e) ph[e] = f16_sat(v[e], amax);
+                store_act16(oq, ph, false);
+            } else {
+                f16x8 ph, pl;
+#pragma unroll
+                for (int e = 0; e < 8; ++e) { _Float16 h, l; split_f16(v[e], h, l, amax); ph[e] = h; pl[e] = l; }
+                store_act16(oq, ph, false);
+                store_act16(oq + a.out_ldc, pl, false);
+            }
         }
         BD_ESTAMP(3)
         if (rg + RG < BM) __syncthreads();

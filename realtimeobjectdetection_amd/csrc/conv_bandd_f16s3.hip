@@ -62,9 +62,12 @@ __host__ __device__ constexpr int bandd_rows(int bm, int w) { return (bm + 2 * w
 // BM x BN workgroup tile; NWM x NWN waves per K group, each wave a (BM/NWM) x (BN/NWN) strip (NWM = 1: no weight byte is
 // loaded twice in a workgroup).  DB: double-buffered band.  KG = 2: two wave groups on the even / odd channel chunks (own band
 // buffers), summed in the epilogue — the split-K layers of conv_band_f16s3.hip (conv_band_layer_kg), same summation order.
+// EPI | EPI_F16: plain-f16 instance.  The band image keeps its 2 KiB blocks (the lo halves are neither DMA'd nor read), the B sets
+// hold the hi fragments only, one MFMA per (A, B) pair; every counted wait scales with the loads that remain (NB, PER below).
 template <int BM, int BN, int NWM, int NWN, int MINW, int EPI, int BUFM, int KG, int MAXW>
 __global__ __launch_bounds__(NWM * NWN * 64 * KG, MINW)
 void conv_bandd_f16s3_kernel(const ConvArgs a, const int grid_m, const int grid_n) {
+    constexpr bool F16 = epi_f16(EPI);
     // BUFM: 0 one band buffer, replaced between two barriers at every chunk top (the load is exposed; other workgroups cover it);
     //       1 two band buffers, the next chunk's band loads under the current chunk.
     // (Round 4 also measured a ROLLING band — one buffer replaced in place in three parts as the taps release its rows, every load
@@ -76,7 +79,8 @@ void conv_bandd_f16s3_kernel(const ConvArgs a, const int grid_m, const int grid_
     static_assert(WM % 16 == 0 && WN % 16 == 0 && BM % NWM == 0 && BN % NWN == 0, "wave tile");
     constexpr int TM = WM / 16, TN = WN / 16;
     static_assert(TN <= 2, "strip width: 16 or 32 columns (instruction offsets, tie)");
-    constexpr int NB = 2 * TN;                                  // B loads of one step
+    constexpr int NB = (F16 ? 1 : 2) * TN;                      // B loads of one step
+    constexpr int PER = F16 ? 1 : 2;                            // loads of one band piece (hi + lo, or hi)
     constexpr int UNITS = 9 * TM;                               // (tap, 16-row tile) units of one channel chunk
     constexpr int NBLK_MAX = bandd_rows(BM, MAXW) / 16;
     constexpr int PPW = (NBLK_MAX + NW - 1) / NW;               // band blocks per wave, at most
@@ -149,7 +153,9 @@ void conv_bandd_f16s3_kernel(const ConvArgs a, const int grid_m, const int grid_
             const int r = r0 + k * NW * 16;
             const int q = m0 - W - 1 + r;
             const unsigned vo = (blk < blk_hi && r < NBv && (unsigned)q < (unsigned)M) ? (unsigned)q * PS + dma_cpart : OOB;
-            if (k < n) bandd_dma_pair(rs_a, vo, soff, lo_plane + soff, base + (unsigned)(blk < blk_hi ? blk * 2048 : zero_off));
+            const unsigned dst = base + (unsigned)(blk < blk_hi ? blk * 2048 : zero_off);
+            if constexpr (F16) { if (k < n) bandd_dma_hi(rs_a, vo, soff, dst); }
+            else if (k < n) bandd_dma_pair(rs_a, vo, soff, lo_plane + soff, dst);
         }
     };
     auto dma_band = [&](int cc, int buf) __attribute__((always_inline)) { dma_blocks(cc, buf, 0, NBLK, n_dma); };
@@ -165,10 +171,10 @@ void conv_bandd_f16s3_kernel(const ConvArgs a, const int grid_m, const int grid_
         const unsigned vo = ld_step < nsteps ? bvoff : OOB;
         const unsigned koff = (unsigned)((ld_cc * KG + kg) * 9 + ld_tap) * wchunk;
         q[0][0] = bandd_load_b<0>(rs_wh, vo, koff);
-        q[0][1] = bandd_load_b<0>(rs_wl, vo, koff);
+        if constexpr (!F16) q[0][1] = bandd_load_b<0>(rs_wl, vo, koff);
         if constexpr (TN == 2) {
             q[1][0] = bandd_load_b<1024>(rs_wh, vo, koff);
-            q[1][1] = bandd_load_b<1024>(rs_wl, vo, koff);
+            if constexpr (!F16) q[1][1] = bandd_load_b<1024>(rs_wl, vo, koff);
         }
         ++ld_step;
         if (++ld_tap == 9) { ld_tap = 0; ++ld_cc; }
@@ -231,7 +237,7 @@ void conv_bandd_f16s3_kernel(const ConvArgs a, const int grid_m, const int grid_
         int o;
         asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(o) : "v"(sel), "v"(x0), "s"(z));
         h = *reinterpret_cast<lds_f16x8*>((unsigned)(o + 2048 * i));
-        l = *reinterpret_cast<lds_f16x8*>((unsigned)(o + 2048 * i + 1024));
+        if constexpr (!F16) l = *reinterpret_cast<lds_f16x8*>((unsigned)(o + 2048 * i + 1024));
     };
 
     // ---- prologue: band chunk 0, B sets of steps 0 and 1
@@ -240,7 +246,7 @@ void conv_bandd_f16s3_kernel(const ConvArgs a, const int grid_m, const int grid_
     load_b(Bq[1]);
     if constexpr (DB) {                                         // band(0) landed (the chunk tops of the double-buffered loop wait for nothing)
         bandd_wait_vmcnt<0>();
-        bandd_tie<TN>(Bq[0]); bandd_tie<TN>(Bq[1]);
+        bandd_tie<TN, F16>(Bq[0]); bandd_tie<TN, F16>(Bq[1]);
         __builtin_amdgcn_sched_barrier(0);
     }
     __syncthreads();                                            // zero blocks written
@@ -270,7 +276,7 @@ void conv_bandd_f16s3_kernel(const ConvArgs a, const int grid_m, const int grid_
         int dma_behind = 0;                                     // band pairs issued between B(s + 1) and B(s + 2) of the current phase's first step
         if constexpr (!DB) {
             bandd_wait_vmcnt<0>();
-            bandd_tie<TN>(Bq[0]); bandd_tie<TN>(Bq[1]);
+            bandd_tie<TN, F16>(Bq[0]); bandd_tie<TN, F16>(Bq[1]);
         }
         __builtin_amdgcn_sched_barrier(0);
         __builtin_amdgcn_s_barrier();
@@ -285,16 +291,18 @@ void conv_bandd_f16s3_kernel(const ConvArgs a, const int grid_m, const int grid_
             if (i == 0) {                                       // step head: B set of step t + 2, wait for this step's
                 load_b(Bq[(t + 2) % 3]);
                 if constexpr (DB) {                             // younger than this step's set: the next two sets and, for t < 2, the band pieces
-                    if (t >= 2) bandd_wait_vmcnt<2 * NB>(); else bandd_wait_vmcnt_plus<2 * NB>(dma_behind);
-                    bandd_tie<TN>(Bq[t % 3]);
-                } else if (t >= 2) { bandd_wait_vmcnt<2 * NB>(); bandd_tie<TN>(Bq[t % 3]); }
+                    if (t >= 2) bandd_wait_vmcnt<2 * NB>(); else bandd_wait_vmcnt_plus<2 * NB, PER>(dma_behind);
+                    bandd_tie<TN, F16>(Bq[t % 3]);
+                } else if (t >= 2) { bandd_wait_vmcnt<2 * NB>(); bandd_tie<TN, F16>(Bq[t % 3]); }
                 __builtin_amdgcn_sched_barrier(0);
             }
             if (u + 2 < UNITS) read_unit((u + 2) / TM, (u + 2) % TM, bufoff, Ah[(u + 2) % 3], Al[(u + 2) % 3]);
             const f16x8 ah = Ah[u % 3], al = Al[u % 3];
 #pragma unroll
             for (int j = 0; j < TN; ++j) {
-                const f16x8 bh = __builtin_bit_cast(f16x8, Bq[t % 3][j][0]), bl = __builtin_bit_cast(f16x8, Bq[t % 3][j][1]);
+                const f16x8 bh = __builtin_bit_cast(f16x8, Bq[t % 3][j][0]);
+                if constexpr (F16) { acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh, acc[i][j], 0, 0, 0); continue; }
+                const f16x8 bl = __builtin_bit_cast(f16x8, Bq[t % 3][j][1]);
                 acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bh, acc[i][j], 0, 0, 0);
                 acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bl, acc[i][j], 0, 0, 0);
                 acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh, acc[i][j], 0, 0, 0);
@@ -305,12 +313,12 @@ void conv_bandd_f16s3_kernel(const ConvArgs a, const int grid_m, const int grid_
     }
     // drain: the two trailing (out-of-range) B sets' registers stay allocated until they have landed
     bandd_wait_vmcnt<0>();
-    bandd_tie<TN>(Bq[0]); bandd_tie<TN>(Bq[1]); bandd_tie<TN>(Bq[2]);
+    bandd_tie<TN, F16>(Bq[0]); bandd_tie<TN, F16>(Bq[1]); bandd_tie<TN, F16>(Bq[2]);
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_setprio(0);
     BD_STAMP(3)
 
-    bandd_epilogue<BM, BN, WM, WN, NT * KG, RG, EPI == EPI_SPLIT_RES, KG>(a, acc, smem, bm, bn, (int)threadIdx.x, wm, wn, lr, lh, M, kg);
+    bandd_epilogue<BM, BN, WM, WN, NT * KG, RG, epi_kind(EPI) == EPI_SPLIT_RES, KG, F16>(a, acc, smem, bm, bn, (int)threadIdx.x, wm, wn, lr, lh, M, kg);
 #ifdef RTOD_TIMELINE
     BD_STAMP(4)
     if (threadIdx.x == 0 && blockIdx.x < BD_TL_BLOCKS) {
@@ -336,18 +344,19 @@ static int launch_bandd(const ConvArgs& a, hipStream_t s) {
     const int epi_bytes = RG * BN * 4;
     const int lds = main_bytes > epi_bytes ? main_bytes : epi_bytes;
     if (lds > 160 * 1024) { set_error("launch_conv_bandd: %d bytes of LDS", lds); return RTOD_E_ARG; }
-    auto k_res = conv_bandd_f16s3_kernel<BM, BN, NWM, NWN, MINW, EPI_SPLIT_RES, BUFM, KG, MAXW>;
-    auto k_plain = conv_bandd_f16s3_kernel<BM, BN, NWM, NWN, MINW, EPI_SPLIT, BUFM, KG, MAXW>;
-    static std::atomic<unsigned long long> attr_done{0};       // per instantiation, one bit per device; > 64 KiB of dynamic LDS needs the opt-in
+    const int fe = a.f16 ? EPI_F16 : 0;
+    auto k_res = fe ? conv_bandd_f16s3_kernel<BM, BN, NWM, NWN, MINW, EPI_SPLIT_RES | EPI_F16, BUFM, KG, MAXW> : conv_bandd_f16s3_kernel<BM, BN, NWM, NWN, MINW, EPI_SPLIT_RES, BUFM, KG, MAXW>;
+    auto k_plain = fe ? conv_bandd_f16s3_kernel<BM, BN, NWM, NWN, MINW, EPI_SPLIT | EPI_F16, BUFM, KG, MAXW> : conv_bandd_f16s3_kernel<BM, BN, NWM, NWN, MINW, EPI_SPLIT, BUFM, KG, MAXW>;
+    static std::atomic<unsigned long long> attr_done[2] = {{0}, {0}};   // per instantiation (f16s3, f16), one bit per device; > 64 KiB of dynamic LDS needs the opt-in
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) return hip_fail(hipGetLastError(), "conv_bandd_f16s3 hipGetDevice");
-    if (!((attr_done.load(std::memory_order_acquire) >> (dev & 63)) & 1ull)) {
+    if (!((attr_done[fe ? 1 : 0].load(std::memory_order_acquire) >> (dev & 63)) & 1ull)) {
         const int cap = KG * (DB ? 2 : 1) * (bandd_rows(BM, MAXW) / 16 + 1) * 2048;
         const int mx = std::min(cap > epi_bytes ? cap : epi_bytes, 160 * 1024);    // (a launch that needs more is refused above)
         if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_res), hipFuncAttributeMaxDynamicSharedMemorySize, mx) != hipSuccess ||
             hipFuncSetAttribute(reinterpret_cast<const void*>(k_plain), hipFuncAttributeMaxDynamicSharedMemorySize, mx) != hipSuccess)
             return hip_fail(hipGetLastError(), "conv_bandd_f16s3 LDS attribute");
-        attr_done.fetch_or(1ull << (dev & 63), std::memory_order_release);
+        attr_done[fe ? 1 : 0].fetch_or(1ull << (dev & 63), std::memory_order_release);
     }
     if (a.res) hipLaunchKernelGGL(k_res, dim3(gm * gn), dim3(NT), lds, s, ax, gm, gn);
     else hipLaunchKernelGGL(k_plain, dim3(gm * gn), dim3(NT), lds, s, ax, gm, gn);
@@ -437,7 +446,7 @@ int conv_bandd_kernel_name(int idx, int epi, char* buf, size_t len) {
 }
 
 int launch_conv_bandd_f16s3(const ConvArgs& a, int idx, hipStream_t s) {
-    if (!a.in || !a.w_hi || !a.w_lo || !a.bias || !a.inv_scale || !a.out) { set_error("launch_conv_bandd: null pointer"); return RTOD_E_ARG; }
+    if (!a.in || !a.w_hi || (!a.w_lo && !a.f16) || !a.bias || !a.inv_scale || !a.out) { set_error("launch_conv_bandd: null pointer"); return RTOD_E_ARG; }
     if (a.kh != 3 || a.stride != 1 || a.pad != 1 || a.Cin % 32 || a.Wi > BANDD_WIDE_W || a.kw != 3 || a.Ho != a.Hi || a.Wo != a.Wi || a.dec.enabled || a.pw_wh) {
         set_error("launch_conv_bandd: unsupported shape (k=%d s=%d pad=%d Cin=%d W=%d)", a.kh, a.stride, a.pad, a.Cin, a.Wi); return RTOD_E_ARG;
     }

@@ -13,6 +13,12 @@ constexpr int HBK = 32;                  // K elements per LDS stage (64 bytes p
 constexpr unsigned OOB = 0x80000000u;    // voffset beyond any buffer (< 2 GiB enforced on the host)
 
 enum { EPI_SPLIT = 0, EPI_SPLIT_RES = 1, EPI_DECODE = 2, EPI_SPLIT_PW = 3, EPI_SPLIT_RES_PW = 4 };
+// Plain-f16 instances (precision mode 2, "f16"): EPI | EPI_F16 as the kernels' EPI template argument.  The main loop drops the lo
+// loads / LDS panels and two of the three MFMAs (one ah*bh product per fragment pair); the epilogue reads the hi plane of a
+// shortcut operand only and stores the hi plane only (the lo halves of an f16 plan's arena are never written or read).
+// Kept inside EPI so that the f16s3 instances keep their names (rocprofv3, bench.py).  EPI_F16 itself: rtod_internal.h.
+__host__ __device__ constexpr bool epi_f16(int epi) { return (epi & EPI_F16) != 0; }
+__host__ __device__ constexpr int epi_kind(int epi) { return epi & ~EPI_F16; }
 constexpr int PW_MAX_COUT = 64, PW_MAX_K = 64;    // measured: hosts with 128 output channels gain nothing over the stand-alone 1x1 kernel
 
 __device__ __forceinline__ float h_sigmoid(float v) { return 1.0f / (1.0f + expf(-v)); }
@@ -160,13 +166,15 @@ constexpr int epi_row_group(int bm, int wm, int rg_max) {
 // PRE: the caller hands over bias[n] / inv_scale[n] of its WN / 16 column groups in registers (conv_ring_f16s3.hip loads them at
 // the start of a tile: a compiler-visible global load inside the epilogue would be waited for with vmcnt(0), which also
 // drains the LDS-DMA ring that is prefetching the next tile).
-template <int BM, int BN, int WM, int WN, int NT, int EPI, int SMEM_BYTES, int KG = 1, bool PRE = false>
+// F16: plain-f16 output (precision mode 2): hi plane of the shortcut operand, hi plane stored (no hosted pointwise conv).
+template <int BM, int BN, int WM, int WN, int NT, int EPI, int SMEM_BYTES, int KG = 1, bool PRE = false, bool F16 = false>
 __device__ __forceinline__ void conv_f16s3_epilogue(const ConvArgs& a, f32x4 (&acc)[WM / 16][WN / 16], unsigned char* smem,
                                                     int bm, int bn, int tid, int wm, int wn, int lr, int lh, int M, int kg = 0,
                                                     const float* pre_bias = nullptr, const float* pre_inv = nullptr) {
     constexpr int MT = 16, TM = WM / MT, TN = WN / MT, NE = 4;
     constexpr bool PW = EPI == EPI_SPLIT_PW || EPI == EPI_SPLIT_RES_PW;
     constexpr bool RES = EPI == EPI_SPLIT_RES || EPI == EPI_SPLIT_RES_PW;
+    static_assert(!(F16 && PW), "plain-f16 plans host no pointwise conv");
     // fused pointwise conv: the transpose tile doubles as the A operand of the second GEMM (row stride + 4 floats: the
     // 16 rows x 16 bytes of a fragment read then cover all 64 banks), and a second tile T2 takes its result
     constexpr int TS = PW ? BN + 4 : BN;
@@ -178,6 +186,7 @@ __device__ __forceinline__ void conv_f16s3_epilogue(const ConvArgs& a, f32x4 (&a
     constexpr int RG_MAX = SMEM_BYTES / ((TS + (PW ? T2S : 0)) * 4);
     constexpr int RG = epi_row_group(BM, WM, RG_MAX);                     // rows per pass: multiple of WM dividing BM
     static_assert(RG >= WM && BM % RG == 0, "epilogue row group");
+    static_assert(RG * (TS + (PW ? T2S : 0)) * 4 <= SMEM_BYTES, "epilogue tile exceeds the kernel's LDS");
     float* T = reinterpret_cast<float*>(smem);
     const int hw = a.Ho * a.Wo;
 #ifdef RTOD_DIAG
@@ -241,9 +250,12 @@ __device__ __forceinline__ void conv_f16s3_epilogue(const ConvArgs& a, f32x4 (&a
                 // unconditional loads from a clamped address, selected afterwards: written as `ok ? *q : 0` each load became a
                 // branch with its own s_waitcnt vmcnt(0) — NG pairs of memory latencies in a row at the head of every epilogue
                 const _Float16* q = rh0 + (int64_t)(ok ? m : 0) * 2 * a.res_ldc + (ok ? c8 : 0);
-                const f16x8 th = *reinterpret_cast<const f16x8*>(q), tl = *reinterpret_cast<const f16x8*>(q + a.res_ldc);
+                const f16x8 th = *reinterpret_cast<const f16x8*>(q);
                 rq_h[i] = ok ? th : f16x8{0, 0, 0, 0, 0, 0, 0, 0};
-                rq_l[i] = ok ? tl : f16x8{0, 0, 0, 0, 0, 0, 0, 0};
+                if constexpr (!F16) {
+                    const f16x8 tl = *reinterpret_cast<const f16x8*>(q + a.res_ldc);
+                    rq_l[i] = ok ? tl : f16x8{0, 0, 0, 0, 0, 0, 0, 0};
+                }
             }
         }
         if constexpr (KG == 2) {
@@ -349,7 +361,11 @@ __device__ __forceinline__ void conv_f16s3_epilogue(const ConvArgs& a, f32x4 (&a
                 const f32x4 v0 = *reinterpret_cast<const f32x4*>(T + r * TS + c8);
                 const f32x4 v1 = *reinterpret_cast<const f32x4*>(T + r * TS + c8 + 4);
                 float v[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
-                if constexpr (RES) {
+                if constexpr (RES && F16) {
+                    const f16x8 qh = rq_h[gi];
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) v[e] += (float)qh[e];
+                } else if constexpr (RES) {
                     const f16x8 qh = rq_h[gi], ql = rq_l[gi];
 #pragma unroll
                     for (int e = 0; e < 8; ++e) v[e] += (float)qh[e] + (float)ql[e];
@@ -358,12 +374,19 @@ __device__ __forceinline__ void conv_f16s3_epilogue(const ConvArgs& a, f32x4 (&a
                         *reinterpret_cast<f32x4*>(T + r * TS + c8 + 4) = f32x4{v[4], v[5], v[6], v[7]};
                     }
                 }
-                f16x8 ph, pl;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) { _Float16 h, l; split_f16(v[e], h, l, amax); ph[e] = h; pl[e] = l; }
                 _Float16* q = oh + (int64_t)m * 2 * a.out_ldc + c8;
-                store_act16(q, ph, st_plain);
-                store_act16(q + a.out_ldc, pl, st_plain);
+                if constexpr (F16) {
+                    f16x8 ph;
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) ph[e] = f16_sat(v[e], amax);
+                    store_act16(q, ph, st_plain);
+                } else {
+                    f16x8 ph, pl;
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) { _Float16 h, l; split_f16(v[e], h, l, amax); ph[e] = h; pl[e] = l; }
+                    store_act16(q, ph, st_plain);
+                    store_act16(q + a.out_ldc, pl, st_plain);
+                }
             }
             if constexpr (PW) {
                 // ---- fused 1x1 conv: out2[RG x pw_cout] = act[RG x pw_k] * W2^T, same three-product split arithmetic.

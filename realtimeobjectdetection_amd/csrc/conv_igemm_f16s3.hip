@@ -48,9 +48,11 @@ struct StageRegs {
 // BM x BN workgroup tile, NWM x NWN waves of (BM/NWM) x (BN/NWN), both multiples of 16.  MINW = waves per SIMD the
 // register budget must admit (2nd __launch_bounds__ argument): wave tiles of 32x64 / 48x32 or smaller are built for
 // 4 waves/SIMD — tools/ubench_tiles.hip: occupancy buys more MFMA utilisation than a larger wave tile.
+// EPI | EPI_F16: plain-f16 instance (hi planes only: half the loads and LDS panels, one MFMA per fragment pair).
 template <int BM, int BN, int NWM, int NWN, int MINW, int EPI>
 __global__ __launch_bounds__(NWM * NWN * 64, MINW)
 void conv_igemm_f16s3_kernel(const ConvArgs a, const int grid_m, const int grid_n) {
+    constexpr bool F16 = epi_f16(EPI);
     constexpr int WM = BM / NWM, WN = BN / NWN;
     constexpr int NT = NWM * NWN * 64;
     static_assert(WM % 16 == 0 && WN % 16 == 0 && BM % NWM == 0 && BN % NWN == 0, "wave tile");
@@ -62,9 +64,12 @@ void conv_igemm_f16s3_kernel(const ConvArgs a, const int grid_m, const int grid_
     // slice: its loads are issued out of range (the vmcnt count per stage stays constant) and its LDS
     // writes are skipped
     constexpr int PANEL_A = BM * 64, PANEL_B = BN * 64;        // bytes
-    constexpr int STAGE = 2 * PANEL_A + 2 * PANEL_B;
+    constexpr int STAGE = (F16 ? 1 : 2) * (PANEL_A + PANEL_B);     // [A hi][A lo][B hi][B lo], f16: [A hi][B hi]
+    constexpr int PANEL_B0 = (F16 ? 1 : 2) * PANEL_A;                  // offset of the B hi panel
+    // the epilogue's transpose tile needs at least one WM-row pass of BN fp32 (f16 128x256: 64 KiB against 48 KiB of stages)
+    constexpr int SMEM = 2 * STAGE > WM * BN * 4 ? 2 * STAGE : WM * BN * 4;
 
-    __shared__ __attribute__((aligned(16))) unsigned char smem[2 * STAGE];
+    __shared__ __attribute__((aligned(16))) unsigned char smem[SMEM];
 
     const int nwg = grid_m * grid_n;
     int bid = blockIdx.x;
@@ -123,27 +128,35 @@ void conv_igemm_f16s3_kernel(const ConvArgs a, const int grid_m, const int grid_
             const bool ok = live && (unsigned)(iy0[i] + ld_ky) < (unsigned)a.Hi && (unsigned)(ix0[i] + ld_kx) < (unsigned)a.Wi;
             const unsigned vo = ok ? pbase[i] + tap_off : OOB;
             S.ah[i] = asm_buffer_load_b128(rs_a, vo, 0u);
-            S.al[i] = asm_buffer_load_b128(rs_a, vo, lo_plane);
+            if constexpr (!F16) S.al[i] = asm_buffer_load_b128(rs_a, vo, lo_plane);
         }
         const unsigned koff = (unsigned)ld_kc * wchunk;
 #pragma unroll
         for (int i = 0; i < B_SLOTS; ++i) {
             const unsigned wo = live ? wbase[i] : OOB;
             S.bh[i] = asm_buffer_load_b128(rs_wh, wo, koff);
-            S.bl[i] = asm_buffer_load_b128(rs_wl, wo, koff);
+            if constexpr (!F16) S.bl[i] = asm_buffer_load_b128(rs_wl, wo, koff);
         }
         // advance the cursor (scalar).  K order = (32-channel chunk outer, tap inner), the same order as the
         // band kernel and the packed weights, so every tile variant / kernel sums each output identically
         ++ld_kc;
         if (++ld_kx == a.kw) { ld_kx = 0; if (++ld_ky == a.kh) { ld_ky = 0; ld_c0 += HBK; } }
     };
-    constexpr int LOADS_PER_STAGE = 2 * A_SLOTS + 2 * B_SLOTS;
+    constexpr int LOADS_PER_STAGE = (F16 ? 1 : 2) * (A_SLOTS + B_SLOTS);
     static_assert(LOADS_PER_STAGE <= 8, "vmcnt literals below");
     // wait until at most `LOADS_PER_STAGE` loads (the younger stage set) are outstanding: the older set S
     // has landed.  Every register of S is an in/out operand so no use can be scheduled above the wait.
     auto wait_stage = [&](StageRegs<A_SLOTS, B_SLOTS>& S) {
         static_assert(A_SLOTS >= 1 && A_SLOTS <= 2 && B_SLOTS >= 1 && B_SLOTS <= 2, "stage shape");
-        if constexpr (A_SLOTS == 2 && B_SLOTS == 2)
+        if constexpr (F16 && A_SLOTS == 2 && B_SLOTS == 2)
+            asm volatile("s_waitcnt vmcnt(4)" : "+v"(S.ah[0]), "+v"(S.ah[1]), "+v"(S.bh[0]), "+v"(S.bh[1]) :: "memory");
+        else if constexpr (F16 && A_SLOTS == 2 && B_SLOTS == 1)
+            asm volatile("s_waitcnt vmcnt(3)" : "+v"(S.ah[0]), "+v"(S.ah[1]), "+v"(S.bh[0]) :: "memory");
+        else if constexpr (F16 && A_SLOTS == 1 && B_SLOTS == 2)
+            asm volatile("s_waitcnt vmcnt(3)" : "+v"(S.ah[0]), "+v"(S.bh[0]), "+v"(S.bh[1]) :: "memory");
+        else if constexpr (F16)
+            asm volatile("s_waitcnt vmcnt(2)" : "+v"(S.ah[0]), "+v"(S.bh[0]) :: "memory");
+        else if constexpr (A_SLOTS == 2 && B_SLOTS == 2)
             asm volatile("s_waitcnt vmcnt(8)" : "+v"(S.ah[0]), "+v"(S.al[0]), "+v"(S.ah[1]), "+v"(S.al[1]),
                          "+v"(S.bh[0]), "+v"(S.bl[0]), "+v"(S.bh[1]), "+v"(S.bl[1]) :: "memory");
         else if constexpr (A_SLOTS == 2 && B_SLOTS == 1)
@@ -165,15 +178,15 @@ void conv_igemm_f16s3_kernel(const ConvArgs a, const int grid_m, const int grid_
             const int o = (row0 + i * RPP) * 64 + wr_swz;
             if ((i + 1) * RPP <= BM || row0 + i * RPP < BM) {
                 *reinterpret_cast<u32x4*>(st + o) = S.ah[i];
-                *reinterpret_cast<u32x4*>(st + PANEL_A + o) = S.al[i];
+                if constexpr (!F16) *reinterpret_cast<u32x4*>(st + PANEL_A + o) = S.al[i];
             }
         }
 #pragma unroll
         for (int i = 0; i < B_SLOTS; ++i) {
             const int o = (row0 + i * RPP) * 64 + wr_swz;
             if ((i + 1) * RPP <= BN || row0 + i * RPP < BN) {
-                *reinterpret_cast<u32x4*>(st + 2 * PANEL_A + o) = S.bh[i];
-                *reinterpret_cast<u32x4*>(st + 2 * PANEL_A + PANEL_B + o) = S.bl[i];
+                *reinterpret_cast<u32x4*>(st + PANEL_B0 + o) = S.bh[i];
+                if constexpr (!F16) *reinterpret_cast<u32x4*>(st + PANEL_B0 + PANEL_B + o) = S.bl[i];
             }
         }
     };
@@ -190,7 +203,7 @@ void conv_igemm_f16s3_kernel(const ConvArgs a, const int grid_m, const int grid_
     const int wm = wave / NWN, wn = wave - wm * NWN;
     const int lr = lane & 15, lh = lane >> 4;
     const int co = (lh ^ ((lr >> 1) & 3)) << 4;                  // WM, WN % 16 == 0: the row's swizzle is the lane's
-    const int a_row = (wm * WM + lr) * 64 + co, b_row = 2 * PANEL_A + (wn * WN + lr) * 64 + co;
+    const int a_row = (wm * WM + lr) * 64 + co, b_row = PANEL_B0 + (wn * WN + lr) * 64 + co;
 
     // the A fragments of the K-chunk are read into registers first, then the next chunk's LDS writes and the
     // global loads of the chunk after are issued, and only then the MFMA block runs (B fragments read per
@@ -202,7 +215,7 @@ void conv_igemm_f16s3_kernel(const ConvArgs a, const int grid_m, const int grid_
 #pragma unroll
         for (int i = 0; i < TM; ++i) {
             ah[i] = *reinterpret_cast<const f16x8*>(st + i * 16 * 64);
-            al[i] = *reinterpret_cast<const f16x8*>(st + PANEL_A + i * 16 * 64);
+            if constexpr (!F16) al[i] = *reinterpret_cast<const f16x8*>(st + PANEL_A + i * 16 * 64);
         }
     };
     auto compute = [&](int buf) {
@@ -211,12 +224,13 @@ void conv_igemm_f16s3_kernel(const ConvArgs a, const int grid_m, const int grid_
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
             bh[j] = *reinterpret_cast<const f16x8*>(st + j * 16 * 64);
-            bl[j] = *reinterpret_cast<const f16x8*>(st + PANEL_B + j * 16 * 64);
+            if constexpr (!F16) bl[j] = *reinterpret_cast<const f16x8*>(st + PANEL_B + j * 16 * 64);
         }
 #pragma unroll
         for (int j = 0; j < TN; ++j)
 #pragma unroll
             for (int i = 0; i < TM; ++i) {
+                if constexpr (F16) { acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[i], bh[j], acc[i][j], 0, 0, 0); continue; }
                 acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[i], bh[j], acc[i][j], 0, 0, 0);
                 acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[i], bl[j], acc[i][j], 0, 0, 0);
                 acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[i], bh[j], acc[i][j], 0, 0, 0);
@@ -277,7 +291,7 @@ void conv_igemm_f16s3_kernel(const ConvArgs a, const int grid_m, const int grid_
 #ifdef RTOD_DIAG
     if (a.dbg & 4) return;                            // timing experiment: no epilogue
 #endif
-    conv_f16s3_epilogue<BM, BN, WM, WN, NT, EPI, 2 * STAGE>(a, acc, smem, bm, bn, tid, wm, wn, lr, lh, M);
+    conv_f16s3_epilogue<BM, BN, WM, WN, NT, epi_kind(EPI), SMEM, 1, false, F16>(a, acc, smem, bm, bn, tid, wm, wn, lr, lh, M);
 #ifdef RTOD_STAMPS
     RTOD_GSTAMP(6)                                    // 6: epilogue
     if ((threadIdx.x & 63) == 0 && blockIdx.x < GSTAMP_BLOCKS) {
@@ -320,7 +334,14 @@ static int launch_h(const ConvArgs& a, hipStream_t s) {
     auto k_plain = conv_igemm_f16s3_kernel<BM, BN, NWM, NWN, MINW, EPI_SPLIT>;
     auto k_res_pw = conv_igemm_f16s3_kernel<BM, BN, NWM, NWN, MINW, EPI_SPLIT_RES_PW>;
     auto k_pw = conv_igemm_f16s3_kernel<BM, BN, NWM, NWN, MINW, EPI_SPLIT_PW>;
-    if (a.pw_wh) {
+    if (a.f16) {
+        if (a.pw_wh) { set_error("conv_igemm_f16s3: plain-f16 launch with a fused pointwise conv"); return RTOD_E_ARG; }
+        auto f_dec = conv_igemm_f16s3_kernel<BM, BN, NWM, NWN, MINW, EPI_DECODE | EPI_F16>;
+        auto f_res = conv_igemm_f16s3_kernel<BM, BN, NWM, NWN, MINW, EPI_SPLIT_RES | EPI_F16>;
+        auto f_plain = conv_igemm_f16s3_kernel<BM, BN, NWM, NWN, MINW, EPI_SPLIT | EPI_F16>;
+        hipLaunchKernelGGL(a.dec.enabled ? f_dec : a.res ? f_res : f_plain, dim3(gm * gn), dim3(NT), 0, s, a, gm, gn);
+    }
+    else if (a.pw_wh) {
         if (gn != 1 || a.dec.enabled) { set_error("conv_igemm_f16s3: fused pointwise conv needs Cout <= BN (%d > %d) and no decode", a.Cout, BN); return RTOD_E_ARG; }
         if (a.res) hipLaunchKernelGGL(k_res_pw, dim3(gm), dim3(NT), 0, s, a, gm, gn);
         else hipLaunchKernelGGL(k_pw, dim3(gm), dim3(NT), 0, s, a, gm, gn);
@@ -352,7 +373,7 @@ static int launch_h(const ConvArgs& a, hipStream_t s) {
 
 int launch_conv_f16s3(const ConvArgs& a_in, int variant, hipStream_t s) {
     ConvArgs a = a_in;
-    if (!a.in || !a.w_hi || !a.w_lo || !a.bias || !a.inv_scale || !a.out) { set_error("launch_conv_f16s3: null pointer"); return RTOD_E_ARG; }
+    if (!a.in || !a.w_hi || (!a.w_lo && !a.f16) || !a.bias || !a.inv_scale || !a.out) { set_error("launch_conv_f16s3: null pointer"); return RTOD_E_ARG; }
     if (a.Cin % HBK || a.in_ldc % 8 || a.in_coff % 8 || a.Kpad % HBK || a.K != a.Kpad || a.K != a.kh * a.kw * a.Cin) {
         set_error("launch_conv_f16s3: needs Cin %% 32 == 0 and 8-channel aligned views (Cin=%d ldc=%ld coff=%d K=%d Kpad=%d)", a.Cin, (long)a.in_ldc, a.in_coff, a.K, a.Kpad);
         return RTOD_E_ARG;

@@ -52,6 +52,7 @@ template <int N> __device__ __forceinline__ void pwd_wait_vmcnt() {
     static_assert(N >= 0 && N <= 63, "vmcnt literal");
 #define RTOD_VMCNT_CASE(n) else if constexpr (N == n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory");
     if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    RTOD_VMCNT_CASE(4) RTOD_VMCNT_CASE(5) RTOD_VMCNT_CASE(6) RTOD_VMCNT_CASE(7) RTOD_VMCNT_CASE(9) RTOD_VMCNT_CASE(11)
     RTOD_VMCNT_CASE(8) RTOD_VMCNT_CASE(10) RTOD_VMCNT_CASE(12) RTOD_VMCNT_CASE(14) RTOD_VMCNT_CASE(16) RTOD_VMCNT_CASE(18) RTOD_VMCNT_CASE(20)
     RTOD_VMCNT_CASE(22) RTOD_VMCNT_CASE(24) RTOD_VMCNT_CASE(26) RTOD_VMCNT_CASE(28) RTOD_VMCNT_CASE(30) RTOD_VMCNT_CASE(32) RTOD_VMCNT_CASE(36)
     RTOD_VMCNT_CASE(40) RTOD_VMCNT_CASE(44) RTOD_VMCNT_CASE(48)
@@ -60,9 +61,13 @@ template <int N> __device__ __forceinline__ void pwd_wait_vmcnt() {
 }
 
 // BM x (32 NW) workgroup tile, NW waves, each a BM x 32 strip; NST slabs of 64 channels in the LDS ring.
+// EPI | EPI_F16: plain-f16 instance (slab blocks keep their 4 KiB layout, the lo pieces are neither DMA'd nor read; hi B fragments only,
+// one MFMA per pair; the counted waits scale with LB / LP below).
 template <int BM, int NW, int NST, int MINW, int EPI>
 __global__ __launch_bounds__(NW * 64, MINW)
 void conv_pwd_f16s3_kernel(const ConvArgs a, const int grid_m, const int grid_n) {
+    constexpr bool F16 = epi_f16(EPI);
+    constexpr int LB = F16 ? 2 : 4, LP = F16 ? 1 : 2;          // loads of one B set / of one slab piece
     constexpr int BN = NW * 32, NT = NW * 64, TM = BM / 16, TN = 2;
     constexpr int SLAB = BM * 256;                              // bytes of one slab: BM rows x 64 channels x (hi + lo)
     constexpr int NP = BM / 8;                                  // 8-row groups (hi + lo DMA pairs) of a slab
@@ -71,9 +76,9 @@ void conv_pwd_f16s3_kernel(const ConvArgs a, const int grid_m, const int grid_n)
     static_assert(BM % 16 == 0 && NPP >= 1 && NPP <= 8, "slab pieces per wave");
     static_assert(NST >= 2 && NST <= 4, "ring depth");
     constexpr int RG = BM * BN * 4 <= 32768 ? BM : (BM / 2) * BN * 4 <= 32768 ? BM / 2 : BM / 4;   // epilogue rows per pass (<= 32 KB of fp32)
-    constexpr int WAIT_B = 8 + 2 * NPP;                         // younger than the awaited B set: one B set, one slab, one B set
-    constexpr int WAIT_SLAB = 8 + (NST - 2) * (2 * NPP + 8);    // younger than slab j at the top of iteration j (j >= NST - 1)
-    constexpr int WAIT_SLAB_PRO = 8 + (NST - 2) * 2 * NPP;      // ... for the slabs issued by the prologue (a lower bound of what is younger)
+    constexpr int WAIT_B = 2 * LB + LP * NPP;                   // younger than the awaited B set: one B set, one slab, one B set
+    constexpr int WAIT_SLAB = 2 * LB + (NST - 2) * (LP * NPP + 2 * LB);   // younger than slab j at the top of iteration j (j >= NST - 1)
+    constexpr int WAIT_SLAB_PRO = 2 * LB + (NST - 2) * LP * NPP;          // ... for the slabs issued by the prologue (a lower bound of what is younger)
 
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int nwg = grid_m * grid_n;
@@ -113,8 +118,9 @@ void conv_pwd_f16s3_kernel(const ConvArgs a, const int grid_m, const int grid_n)
 #pragma unroll
         for (int k = 0; k < NPP; ++k) {
             const int p = wave + k * NW;
-            pwd_dma_pair(rs_a, live ? dma_vo[k] : OOB, soff, lo_plane + soff,
-                         p < NP ? base + (unsigned)((p >> 1) * 4096 + (p & 1) * 1024) : lds0 + (unsigned)(NST * SLAB));
+            const unsigned dst = p < NP ? base + (unsigned)((p >> 1) * 4096 + (p & 1) * 1024) : lds0 + (unsigned)(NST * SLAB);
+            if constexpr (F16) bandd_dma_hi(rs_a, live ? dma_vo[k] : OOB, soff, dst);
+            else pwd_dma_pair(rs_a, live ? dma_vo[k] : OOB, soff, lo_plane + soff, dst);
         }
     };
     // ---- B fragments: lane (lr, lh) <- weight row n0 + 16 j + lr, 16-byte chunk lh of the step's panel; four register sets (t % 4)
@@ -128,9 +134,9 @@ void conv_pwd_f16s3_kernel(const ConvArgs a, const int grid_m, const int grid_n)
         const unsigned vo = t < nsteps ? bvoff : OOB;
         const unsigned koff = (unsigned)t * wchunk;
         q[0][0] = bandd_load_b<0>(rs_wh, vo, koff);
-        q[0][1] = bandd_load_b<0>(rs_wl, vo, koff);
+        if constexpr (!F16) q[0][1] = bandd_load_b<0>(rs_wl, vo, koff);
         q[1][0] = bandd_load_b<1024>(rs_wh, vo, koff);
-        q[1][1] = bandd_load_b<1024>(rs_wl, vo, koff);
+        if constexpr (!F16) q[1][1] = bandd_load_b<1024>(rs_wl, vo, koff);
     };
 
     f32x4 acc[TM][TN];
@@ -150,7 +156,7 @@ void conv_pwd_f16s3_kernel(const ConvArgs a, const int grid_m, const int grid_n)
     auto read_unit = [&](int q, int i, int slotoff, f16x8& h, f16x8& l) __attribute__((always_inline)) {
         const int o = (q ? xq1 : xq0) + slotoff;
         h = *reinterpret_cast<lds_f16x8*>((unsigned)(o + 4096 * i));
-        l = *reinterpret_cast<lds_f16x8*>((unsigned)(o + 4096 * i + 2048));
+        if constexpr (!F16) l = *reinterpret_cast<lds_f16x8*>((unsigned)(o + 4096 * i + 2048));
     };
 
     // ---- prologue: slabs 0 .. NST-2, B sets of steps 0 and 1
@@ -178,14 +184,16 @@ void conv_pwd_f16s3_kernel(const ConvArgs a, const int grid_m, const int grid_n)
             if (i == 0) {                                       // step head: B set of step t + 2, wait for this step's
                 if (q == 0) load_b(2 * j + 2, Bq[(2 * par + 2) % 4]); else load_b(2 * j + 3, Bq[(2 * par + 3) % 4]);
                 pwd_wait_vmcnt<WAIT_B>();
-                if (q == 0) bandd_tie<TN>(Bq[2 * par]); else bandd_tie<TN>(Bq[2 * par + 1]);
+                if (q == 0) bandd_tie<TN, F16>(Bq[2 * par]); else bandd_tie<TN, F16>(Bq[2 * par + 1]);
                 __builtin_amdgcn_sched_barrier(0);
             }
             if (u + 2 < 2 * TM) read_unit((u + 2) / TM, (u + 2) % TM, slotoff, Ah[(u + 2) % 3], Al[(u + 2) % 3]);
             const f16x8 ah = Ah[u % 3], al = Al[u % 3];
 #pragma unroll
             for (int jn = 0; jn < TN; ++jn) {
-                const f16x8 bh = __builtin_bit_cast(f16x8, Bq[2 * par + q][jn][0]), bl = __builtin_bit_cast(f16x8, Bq[2 * par + q][jn][1]);
+                const f16x8 bh = __builtin_bit_cast(f16x8, Bq[2 * par + q][jn][0]);
+                if constexpr (F16) { acc[i][jn] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh, acc[i][jn], 0, 0, 0); continue; }
+                const f16x8 bl = __builtin_bit_cast(f16x8, Bq[2 * par + q][jn][1]);
                 acc[i][jn] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bh, acc[i][jn], 0, 0, 0);
                 acc[i][jn] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bl, acc[i][jn], 0, 0, 0);
                 acc[i][jn] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh, acc[i][jn], 0, 0, 0);
@@ -200,11 +208,11 @@ void conv_pwd_f16s3_kernel(const ConvArgs a, const int grid_m, const int grid_n)
     }
     // drain: trailing (out-of-range) B sets and slab pieces have landed before the ring becomes the transpose tile
     pwd_wait_vmcnt<0>();
-    bandd_tie<TN>(Bq[0]); bandd_tie<TN>(Bq[1]); bandd_tie<TN>(Bq[2]); bandd_tie<TN>(Bq[3]);
+    bandd_tie<TN, F16>(Bq[0]); bandd_tie<TN, F16>(Bq[1]); bandd_tie<TN, F16>(Bq[2]); bandd_tie<TN, F16>(Bq[3]);
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_setprio(0);
 
-    bandd_epilogue<BM, BN, BM, 32, NT, RG, EPI == EPI_SPLIT_RES, 1>(a, acc, smem, bm, bn, tid, 0, wn, lr, lh, M, 0);
+    bandd_epilogue<BM, BN, BM, 32, NT, RG, epi_kind(EPI) == EPI_SPLIT_RES, 1, F16>(a, acc, smem, bm, bn, tid, 0, wn, lr, lh, M, 0);
 }
 
 template <int BM, int NW, int NST, int MINW>
@@ -218,17 +226,18 @@ static int launch_pwd(const ConvArgs& a, hipStream_t s) {
     constexpr int ring_bytes = NST * BM * 256 + ((BM / 8) % NW ? 4096 : 0), epi_bytes = RG * BN * 4;
     constexpr int lds = ring_bytes > epi_bytes ? ring_bytes : epi_bytes;
     static_assert(lds <= 160 * 1024, "LDS");
-    auto k_res = conv_pwd_f16s3_kernel<BM, NW, NST, MINW, EPI_SPLIT_RES>;
-    auto k_plain = conv_pwd_f16s3_kernel<BM, NW, NST, MINW, EPI_SPLIT>;
-    if constexpr (lds > 64 * 1024) {                            // > 64 KiB of dynamic LDS needs the opt-in, once per device
-        static std::atomic<unsigned long long> attr_done{0};
+    const int fe = a.f16 ? 1 : 0;
+    auto k_res = fe ? conv_pwd_f16s3_kernel<BM, NW, NST, MINW, EPI_SPLIT_RES | EPI_F16> : conv_pwd_f16s3_kernel<BM, NW, NST, MINW, EPI_SPLIT_RES>;
+    auto k_plain = fe ? conv_pwd_f16s3_kernel<BM, NW, NST, MINW, EPI_SPLIT | EPI_F16> : conv_pwd_f16s3_kernel<BM, NW, NST, MINW, EPI_SPLIT>;
+    if constexpr (lds > 64 * 1024) {                            // > 64 KiB of dynamic LDS needs the opt-in, once per device and instantiation
+        static std::atomic<unsigned long long> attr_done[2] = {{0}, {0}};
         int dev = 0;
         if (hipGetDevice(&dev) != hipSuccess) return hip_fail(hipGetLastError(), "conv_pwd_f16s3 hipGetDevice");
-        if (!((attr_done.load(std::memory_order_acquire) >> (dev & 63)) & 1ull)) {
+        if (!((attr_done[fe].load(std::memory_order_acquire) >> (dev & 63)) & 1ull)) {
             if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_res), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess ||
                 hipFuncSetAttribute(reinterpret_cast<const void*>(k_plain), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
                 return hip_fail(hipGetLastError(), "conv_pwd_f16s3 LDS attribute");
-            attr_done.fetch_or(1ull << (dev & 63), std::memory_order_release);
+            attr_done[fe].fetch_or(1ull << (dev & 63), std::memory_order_release);
         }
     }
     if (a.res) hipLaunchKernelGGL(k_res, dim3(gm * gn), dim3(NT), lds, s, ax, gm, gn);
@@ -257,7 +266,7 @@ int conv_pwd_kernel_name(int idx, int epi, char* buf, size_t len) {
 }
 
 int launch_conv_pwd_f16s3(const ConvArgs& a, int idx, hipStream_t s) {
-    if (!a.in || !a.w_hi || !a.w_lo || !a.bias || !a.inv_scale || !a.out) { set_error("launch_conv_pwd: null pointer"); return RTOD_E_ARG; }
+    if (!a.in || !a.w_hi || (!a.w_lo && !a.f16) || !a.bias || !a.inv_scale || !a.out) { set_error("launch_conv_pwd: null pointer"); return RTOD_E_ARG; }
     if (!conv_pwd_supported(a.kh, a.stride, a.pad, a.Cin) || a.kw != 1 || a.Ho != a.Hi || a.Wo != a.Wi || a.dec.enabled || a.pw_wh) {
         set_error("launch_conv_pwd: unsupported shape (k=%d s=%d pad=%d Cin=%d)", a.kh, a.stride, a.pad, a.Cin); return RTOD_E_ARG;
     }

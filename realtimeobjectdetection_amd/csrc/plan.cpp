@@ -314,7 +314,7 @@ int Plan::set_option(const char* name, int value) {
     if (flag) *flag = value != 0; else *num = value;
     reset_planning();
     int rc = plan_buffers();
-    if (!rc && precision == 1) rc = check_split_supported();
+    if (!rc && precision >= 1) rc = check_split_supported(precision);
     if (rc) {                                                  // refuse: the plan stays as it was (the error message is kept)
         const std::string msg = last_error_string();
         if (flag) *flag = old_flag; else *num = old_num;
@@ -510,29 +510,29 @@ int Plan::plan_buffers() {
 }
 
 bool Plan::uses_split(const Layer& L, int cin_p) const {
-    return precision == 1 && L.index > 0;      // layer 0 stays on an exact-fp32 kernel and writes the split format
+    return precision >= 1 && L.index > 0;      // layer 0 stays on an exact-fp32 kernel and writes the split format
 }
 
-int Plan::check_split_supported() const {
-
-    if (opt_bn_batch_stats) { set_error("precision f16s3 unsupported with bn_batch_stats (batch-statistics BatchNorm runs on the exact-fp32 kernels)"); return RTOD_E_CFG; }
-    // precision 1 keeps every activation in the split f16 format: every conv but the stem must read
+int Plan::check_split_supported(int mode) const {
+    const char* pn = mode == 2 ? "f16" : "f16s3";
+    if (opt_bn_batch_stats) { set_error("precision %s unsupported with bn_batch_stats (batch-statistics BatchNorm runs on the exact-fp32 kernels)", pn); return RTOD_E_CFG; }
+    // precisions 1 and 2 keep every activation in the split f16 layout: every conv but the stem must read
     // 32-channel K-chunks, every shortcut / head must ride a conv epilogue, concats must be zero-copy
     for (const auto& l : launches) {
         if (l.kind == LK_ADD || l.kind == LK_COPY || l.kind == LK_DECODE) {       // (max-pool and both upsamples have split-format kernels)
-            set_error("precision f16s3 unsupported for this cfg (layer %d needs a stand-alone %s kernel); use fp32", l.layer,
+            set_error("precision %s unsupported for this cfg (layer %d needs a stand-alone %s kernel); use fp32", pn, l.layer,
                       l.kind == LK_ADD ? "add" : l.kind == LK_COPY ? "copy" : "decode");
             return RTOD_E_CFG;
         }
         if (l.kind == LK_CONV && l.layer > 0) {
             const Layer& L = layers[l.layer];
             if (L.cin % 32 || L.cout % 8 * (l.out_layer != -2)) {
-                set_error("precision f16s3 unsupported for this cfg (layer %d: Cin=%d Cout=%d); use fp32", l.layer, L.cin, L.cout);
+                set_error("precision %s unsupported for this cfg (layer %d: Cin=%d Cout=%d); use fp32", pn, l.layer, L.cin, L.cout);
                 return RTOD_E_CFG;
             }
         }
     }
-    for (const auto& b : bufs) if (b.C % 8 && &b != &bufs[input_buf]) { set_error("precision f16s3: a buffer has %d channels (not a multiple of 8)", b.C); return RTOD_E_CFG; }
+    for (const auto& b : bufs) if (b.C % 8 && &b != &bufs[input_buf]) { set_error("precision %s: a buffer has %d channels (not a multiple of 8)", pn, b.C); return RTOD_E_CFG; }
     return RTOD_OK;
 }
 
@@ -547,7 +547,7 @@ void Plan::layout_weights() {
         const Layer& L = layers[pc.layer];
         pc.split = uses_split(L, pc.cin_p);
         const int64_t panel = (int64_t)pc.Npad * pc.Kpad;
-        if (pc.stem && precision == 1) {                              // split stem: [Cout][32] f16 hi, lo, inv_scale
+        if (pc.stem && precision >= 1) {                              // split stem: [Cout][32] f16 hi, lo, inv_scale (its hi output is plain f16's format too)
             pc.split = true;
             pc.w_off = packed_floats; packed_floats += 16 * (int64_t)L.cout;
             pc.wl_off = packed_floats; packed_floats += 16 * (int64_t)L.cout;
@@ -611,7 +611,7 @@ View Plan::view_of(int layer) const {
     const Layer& L = layers[resolve_alias(layers, layer)];
     if (L.buf < 0) return v;
     const Buffer& b = bufs[L.buf];
-    v.split = precision == 1 ? 1 : 0;
+    v.split = precision;                   // 0 fp32, 1 split hi + lo, 2 the split layout with the hi plane alone
     v.base = d_arena ? d_arena + b.offset : nullptr;
     v.ldc = b.C; v.coff = L.coff; v.C = L.cout; v.H = L.hout; v.W = L.wout;
     return v;
@@ -757,7 +757,10 @@ int Plan::load_weights(const float* w, size_t n) {
     if (!d_weights) RTOD_HIP(hipMalloc((void**)&d_weights, sizeof(float) * (size_t)packed_floats));
     if (!d_arena) {
         RTOD_HIP(hipMalloc((void**)&d_arena, sizeof(float) * (size_t)arena_floats));
-        RTOD_HIP(hipMemset(d_arena, 0, sizeof(float) * (size_t)arena_floats));
+        // plain-f16 plans: every half of the arena starts as an f16 NaN, so a kernel that wrongly reads a lo plane (never
+        // written in that mode) turns the results NaN, deterministically, instead of picking up stale but plausible values
+        if (precision == 2) RTOD_HIP(hipMemsetD16((hipDeviceptr_t)d_arena, 0x7E00, 2 * (size_t)arena_floats));
+        else RTOD_HIP(hipMemset(d_arena, 0, sizeof(float) * (size_t)arena_floats));
     }
     if (opt_bn_batch_stats && !d_bn_stats && bn_stats_doubles > 0) {
         RTOD_HIP(hipMalloc((void**)&d_bn_stats, sizeof(double) * (size_t)bn_stats_doubles));
@@ -804,7 +807,25 @@ int Plan::f32_slice_mode(const Launch& l, int batch, int variant) const {
     return (opt_k_slice_workgroups && d_scratch && tiles < 512 && S * M * pc.Npad <= scratch_floats) ? 2 : 1;
 }
 
+// Plain-f16 plans (precision 2) run the families that have an f16 instance: the generic tiles (conv_igemm_f16s3.hip), the bandd
+// tiles (the band layers, and the wide slab tile of the other 3x3 stride-1 layers) and the 1x1 slab tiles (conv_pwd_f16s3.hip).
+// conv_band / ring / patch / the fused stem + layer 1 and the hosted pointwise epilogues are never candidates there.
+static bool variant_has_f16(int v) {
+    return (v >= 0 && v < HV_COUNT) || (v >= BAND_VARIANT_BASE + BAND_LDS_MODES && v < BAND_VARIANT_BASE + BAND_MODES) ||
+           (v >= PWD_VARIANT_BASE && v < PWD_VARIANT_BASE + PWD_MODES);
+}
+// band-family mode of a band layer: valid for its shape and, in plain-f16 plans, a bandd tile
+static bool band_mode_ok(int precision, int mode, const Layer& L) {
+    return conv_band_mode_valid(mode, L.cin, L.hin, L.win) && (precision != 2 || mode >= BAND_LDS_MODES);
+}
+static int band_default_mode(int precision, const Layer& L) {
+    if (precision != 2) return conv_band_default_mode(L.cin, L.hin, L.win);
+    for (int m = BAND_LDS_MODES; m < BAND_MODES; ++m) if (conv_band_mode_valid(m, L.cin, L.hin, L.win)) return m;
+    return BAND_LDS_MODES;
+}
+
 int Plan::launch_split_variant(ConvArgs& a, const PackedConv& pc, int v, hipStream_t s) const {
+    if (precision == 2 && !variant_has_f16(v)) { set_error("variant %d has no plain-f16 instance", v); return RTOD_E_STATE; }
     if (v >= PATCH_VARIANT_BASE) {
         if (pc.band) { set_error("patch variant requested for a band layer"); return RTOD_E_STATE; }
         return launch_conv_patch_f16s3(a, v - PATCH_VARIANT_BASE, s);
@@ -838,6 +859,7 @@ int Plan::build_conv_args(const Launch& l, int batch, float* out, ConvArgs& a) c
         a.w_hi = reinterpret_cast<const _Float16*>(d_weights + pc.w_off);
         a.w_lo = reinterpret_cast<const _Float16*>(d_weights + pc.wl_off);
         a.inv_scale = d_weights + pc.s_off;
+        a.f16 = precision == 2 ? 1 : 0;
     }
     a.kh = a.kw = L.size; a.stride = L.stride; a.pad = L.pad;
     a.Ho = L.hout; a.Wo = L.wout; a.Cout = L.cout; a.leaky = L.act;
@@ -884,8 +906,10 @@ int Plan::tune_launch(size_t li, ConvArgs& a, int batch, hipStream_t s) {
     const Layer& L = layers[l.layer];
     const bool pw = a.pw_wh != nullptr;
     // shape + everything else the candidate set depends on (a second plan with other kernel-selection options must not inherit tiles)
+    // (the precision too: an f16 plan must not inherit an f16s3 plan's tile, or the reverse)
     const std::vector<int> key = {L.cin, L.cout, L.size, L.stride, L.hout, L.wout, l.in2_layer >= 0, l.out_layer == -2, pw ? a.pw_cout : 0,
-                                  convs[l.conv_slot].band ? 1 : 0, opt_ring_kernel ? 1 : 0, opt_patch_kernel ? 1 : 0, opt_pwd_kernel ? 1 : 0, L.act};
+                                  convs[l.conv_slot].band ? 1 : 0, opt_ring_kernel ? 1 : 0, opt_patch_kernel ? 1 : 0, opt_pwd_kernel ? 1 : 0, L.act,
+                                  precision};
     auto it = tune_cache.find(key);
     if (it != tune_cache.end()) { tuning[li] = it->second; return RTOD_OK; }
     // process-wide memo (device, batch, shape): a second plan of the same network (bench.py keeps two batches in flight)
@@ -900,7 +924,7 @@ int Plan::tune_launch(size_t li, ConvArgs& a, int batch, hipStream_t s) {
     RTOD_HIP(hipEventCreate(&e0)); RTOD_HIP(hipEventCreate(&e1));
     std::vector<int> cand;
     if (convs[l.conv_slot].band) {                                                    // band layers: band tiles only (see rtod_internal.h)
-        for (int m = 0; m < BAND_MODES; ++m) if (conv_band_mode_valid(m, L.cin, L.hin, L.win)) cand.push_back(BAND_VARIANT_BASE + m);
+        for (int m = 0; m < BAND_MODES; ++m) if (band_mode_ok(precision, m, L)) cand.push_back(BAND_VARIANT_BASE + m);
     } else {
         for (int v = 0; v < HV_COUNT; ++v) {
             const ConvVariantInfo& vi = conv_f16s3_variant_info(v);
@@ -909,7 +933,7 @@ int Plan::tune_launch(size_t li, ConvArgs& a, int batch, hipStream_t s) {
             cand.push_back(v);
         }
         // (SiLU layers: only the kernels with the LDS-transposed epilogue carry that activation — generic and band tiles)
-        if (!pw && L.act <= 1 && opt_patch_kernel && conv_patch_supported(L.size, L.stride, L.pad, L.cin, L.cout) && L.hout == L.hin && l.out_layer != -2)
+        if (precision == 1 && !pw && L.act <= 1 && opt_patch_kernel && conv_patch_supported(L.size, L.stride, L.pad, L.cin, L.cout) && L.hout == L.hin && l.out_layer != -2)
             for (int m = 0; m < PATCH_MODES; ++m) {
                 if (conv_patch_mode_info(m).bn > L.cout && conv_patch_mode_info(m).bn > 64) continue;
                 if (!conv_patch_mode_valid(m, L.cin, L.cout)) continue;
@@ -922,7 +946,7 @@ int Plan::tune_launch(size_t li, ConvArgs& a, int batch, hipStream_t s) {
                 if (conv_pwd_mode_info(m).bn > 128 && conv_pwd_mode_info(m).bn > (L.cout + 127) / 128 * 128) continue;   // tile wider than the layer
                 cand.push_back(PWD_VARIANT_BASE + m);
             }
-        if (!pw && L.act <= 1 && opt_ring_kernel)
+        if (precision == 1 && !pw && L.act <= 1 && opt_ring_kernel)
             for (int m = 0; m < RING_MODES; ++m) {
                 const ConvVariantInfo& vi = conv_ring_mode_info(m);
                 if (vi.bn > 2 * ((L.cout + 63) / 64 * 64) && vi.bn > 64) continue;
@@ -974,7 +998,7 @@ int Plan::tune_launch(size_t li, ConvArgs& a, int batch, hipStream_t s) {
 
 int Plan::set_tiles(int batch, const int* variants, int count) {
     if (!variants || count != (int)launches.size() || batch <= 0 || batch > max_batch) { set_error("set_tiles: %d entries for %d launches, batch %d", count, (int)launches.size(), batch); return RTOD_E_ARG; }
-    if (precision != 1) { set_error("set_tiles: split-f16 plans only"); return RTOD_E_STATE; }
+    if (precision < 1) { set_error("set_tiles: split-f16 / f16 plans only"); return RTOD_E_STATE; }
     for (int i = 0; i < count; ++i) {
         const int v = variants[i];
         const Launch& l = launches[i];
@@ -983,7 +1007,8 @@ int Plan::set_tiles(int batch, const int* variants, int count) {
         const Layer& L = layers[l.layer];
         const bool band = convs[l.conv_slot].band, hosts_pw = l.pw_guest >= 0 && pw_active();
         bool ok;
-        if (band) ok = v >= BAND_VARIANT_BASE && v < BAND_VARIANT_BASE + BAND_MODES && conv_band_mode_valid(v - BAND_VARIANT_BASE, L.cin, L.hin, L.win);
+        if (precision == 2 && !variant_has_f16(v)) ok = false;
+        else if (band) ok = v >= BAND_VARIANT_BASE && v < BAND_VARIANT_BASE + BAND_MODES && band_mode_ok(precision, v - BAND_VARIANT_BASE, L);
         else if (v >= PATCH_VARIANT_BASE) ok = v < PATCH_VARIANT_BASE + PATCH_MODES && !hosts_pw && l.out_layer != -2 && L.act <= 1 && L.hout == L.hin &&
                                                conv_patch_supported(L.size, L.stride, L.pad, L.cin, L.cout) && conv_patch_mode_valid(v - PATCH_VARIANT_BASE, L.cin, L.cout);
         else if (v >= PWD_VARIANT_BASE) ok = v < PWD_VARIANT_BASE + PWD_MODES && pwd_candidate(l, L);
@@ -1001,11 +1026,11 @@ int Plan::variant_for(const Launch& l, int batch) const {
     if (opt_force_f16s3_variant >= 0) {                      // >= BAND_VARIANT_BASE: tile of the band layers, below: of the others
         const int v = opt_force_f16s3_variant;
         const Layer& FL = layers[l.layer];
-        if (band) return conv_band_mode_valid(v - BAND_VARIANT_BASE, FL.cin, FL.hin, FL.win) ? v : BAND_VARIANT_BASE + conv_band_default_mode(FL.cin, FL.hin, FL.win);
+        if (band) return band_mode_ok(precision, v - BAND_VARIANT_BASE, FL) ? v : BAND_VARIANT_BASE + band_default_mode(precision, FL);
         if (v == BAND_VARIANT_BASE + BANDD_WIDE_MODE) { if (bandd_wide_candidate(l, FL)) return v; }
         else if (v >= PWD_VARIANT_BASE && v < PWD_VARIANT_BASE + PWD_MODES) { if (pwd_candidate(l, FL)) return v; }
-        else if (v >= RING_VARIANT_BASE && v < RING_VARIANT_BASE + RING_MODES && !(l.pw_guest >= 0 && pw_active()) && FL.act <= 1) return v;
-        if (v >= PATCH_VARIANT_BASE && v < PATCH_VARIANT_BASE + PATCH_MODES && !(l.pw_guest >= 0 && pw_active()) && l.out_layer != -2 && FL.act <= 1 &&
+        else if (precision == 1 && v >= RING_VARIANT_BASE && v < RING_VARIANT_BASE + RING_MODES && !(l.pw_guest >= 0 && pw_active()) && FL.act <= 1) return v;
+        if (precision == 1 && v >= PATCH_VARIANT_BASE && v < PATCH_VARIANT_BASE + PATCH_MODES && !(l.pw_guest >= 0 && pw_active()) && l.out_layer != -2 && FL.act <= 1 &&
             conv_patch_supported(FL.size, FL.stride, FL.pad, FL.cin, FL.cout) && FL.hout == FL.hin && conv_patch_mode_valid(v - PATCH_VARIANT_BASE, FL.cin, FL.cout)) return v;
         const int g = choose_variant_f16s3(layers[l.layer], batch);
         if (l.pw_guest >= 0 && pw_active() && conv_f16s3_variant_info(g).bn < layers[l.layer].cout) return HV_128x128_8W;
@@ -1014,7 +1039,7 @@ int Plan::variant_for(const Launch& l, int batch) const {
     auto it = tuned.find(batch);
     const size_t idx = &l - &launches[0];
     if (it != tuned.end() && idx < it->second.size() && it->second[idx] >= 0) return it->second[idx];
-    if (band) return BAND_VARIANT_BASE + conv_band_default_mode(layers[l.layer].cin, layers[l.layer].hin, layers[l.layer].win);
+    if (band) return BAND_VARIANT_BASE + band_default_mode(precision, layers[l.layer]);
     const int v = choose_variant_f16s3(layers[l.layer], batch);
     // host of a fused pointwise conv: one N tile must cover every output channel
     if (l.pw_guest >= 0 && pw_active() && conv_f16s3_variant_info(v).bn < layers[l.layer].cout) return HV_128x128_8W;
@@ -1053,7 +1078,7 @@ int Plan::forward(const float* x, int batch, float* out, hipStream_t s, float* l
     if (batch < 1 || batch > max_batch) { set_error("forward: batch %d outside 1..%d", batch, max_batch); return RTOD_E_ARG; }
     RTOD_HIP(hipSetDevice(device));
     // rtod_plan_autotune only: rtod_forward never measures, never synchronises (safe under stream capture)
-    const bool tune_now = tune && precision == 1 && opt_force_f16s3_variant < 0;
+    const bool tune_now = tune && precision >= 1 && opt_force_f16s3_variant < 0;
     if (tune_now) { tuning.assign(launches.size(), -1); tune_cache.clear(); }
     const size_t nl = launches.size();
     if (launch_ms && events.size() < 2 * nl) {

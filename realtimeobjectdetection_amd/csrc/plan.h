@@ -92,7 +92,7 @@ struct Plan {
     int64_t scratch_floats = 0;
     bool weights_loaded = false;
     int train_decode = 0;
-    int precision = 0;         // 0 = exact fp32 MFMA, 1 = f16 hi/lo split (3 products)
+    int precision = 0;         // 0 = exact fp32 MFMA, 1 = f16 hi/lo split (3 products), 2 = plain f16 (hi plane only, 1 product)
     bool keep_all = false;     // debug: no arena reuse, every layer output stays readable after forward
     // plan options (rtod_plan_set_option, before rtod_plan_load_weights).  Explicit per-plan state: the library reads no
     // environment variable.
@@ -121,7 +121,7 @@ struct Plan {
     void assign_arena();
     void layout_weights();
     bool uses_split(const Layer& L, int cin_p) const;
-    int check_split_supported() const;
+    int check_split_supported(int mode) const;   // mode 1 (f16s3) or 2 (f16): same layout requirements
     int load_weights(const float* w, size_t n);
     int forward(const float* x, int batch, float* out, hipStream_t s, float* launch_ms, bool tune = false);
     int set_option(const char* name, int value);

@@ -27,7 +27,8 @@ int hip_fail(hipError_t e, const char* what);
 
 // NHWC view of an activation: element (b,y,x,c) at base[((b*H + y)*W + x)*ldc + coff + c]
 struct View {
-    int split = 0;     // 0: fp32 NHWC; 1: split f16 hi/lo planes per pixel (conv_igemm_f16s3.hip), same bytes
+    int split = 0;     // 0: fp32 NHWC; 1: split f16 hi/lo planes per pixel (conv_igemm_f16s3.hip), same bytes;
+                       // 2: the same layout, hi plane only (plain f16, precision mode 2: the lo plane is never written or read)
     float* base = nullptr;
     int64_t ldc = 0;   // floats between consecutive pixels (>= C: concat buffers are wider)
     int coff = 0;      // first channel of this view inside the pixel
@@ -76,6 +77,7 @@ struct ConvArgs {
     int32_t* ovf = nullptr;                     // split-format producers: device word that gets 1 OR-ed in when an activation saturates the f16 range
     int xcd_by_n = 0;                           // split kernels: workgroup -> XCD by output-channel tile instead of by pixel tile (see launch_band)
     int out_split = 0;                          // exact-fp32 kernel only: write the output in the split format
+    int f16 = 0;                                // split kernels: 1 = plain-f16 instance (precision mode 2: hi planes only, one MFMA per fragment pair)
     // exact-fp32 kernel only: K slices (conv_igemm_f32.hip).  slice_chunks > 0: the K sum is formed slice by slice (a property of
     // the layer); partial != nullptr: one workgroup per slice, raw sums to this scratch ([slices][M][Npad] floats), then a reduction
     int slice_chunks = 0;
@@ -106,6 +108,11 @@ __device__ __forceinline__ void split_f16(float v, _Float16& h, _Float16& l, flo
     h = (_Float16)vc;
     l = (_Float16)(vc - (float)h);
 }
+// Plain-f16 store (precision mode 2): the hi half of split_f16, alone — RNE_f16 of the saturated value, same overflow sentinel.
+__device__ __forceinline__ _Float16 f16_sat(float v, float& amax) {
+    amax = fmaxf(amax, fabsf(v));
+    return (_Float16)__builtin_amdgcn_fmed3f(v, -F16_MAX, F16_MAX);
+}
 // Activation of a conv epilogue: 0 linear, 1 leaky(0.1) (src/darknet.py:497-501), 2 SiLU x * sigmoid(x) (cfg extension).
 // Exact-fp32 kernels and the stems; the split-f16 epilogues have their own form (conv_f16s3_common.h: silu_scaled behind a
 // uniform branch around the loops of the LDS-transposed epilogue).
@@ -118,6 +125,9 @@ __device__ __forceinline__ void split_overflow_report(int32_t* flag, float amax)
     if (flag && !(amax <= F16_MAX)) atomicOr(flag, 1);        // also true for NaN
 }
 #endif
+
+// epilogue-code flag of the plain-f16 kernel instances (precision mode 2): EPI | EPI_F16 (conv_f16s3_common.h)
+constexpr int EPI_F16 = 8;
 
 enum ConvVariant { CV_128x128 = 0, CV_128x64 = 1, CV_64x64 = 2, CV_128x32 = 3, CV_COUNT };
 struct ConvVariantInfo { int bm, bn; const char* name; };

@@ -33,7 +33,7 @@ from . import _ffi
 from .cfg import parse_cfg, build_ir
 
 
-_OVERFLOW_MSG = ("Darknet (precision f16s3): an activation reached the split-f16 range limit (|x| >= 8188) and was saturated; "
+_OVERFLOW_MSG = ("Darknet (precision f16s3 / f16): an activation reached the split-f16 range limit (|x| >= 8188) and was saturated; "
                  "the results of that forward are not valid. Use precision='fp32' (exact MFMA kernels) for these weights.")
 
 
@@ -107,7 +107,9 @@ class Darknet(nn.Module):
         self.bn_running_stats_in_train = False
         self._warned_batch_bn = False
         self.update_running_stats = True   # training-mode forward updates running_mean / running_var / num_batches_tracked like torch does
-        self.precision = os.environ.get("RTOD_PRECISION", "auto")   # "fp32" (exact MFMA) | "f16s3" (split f16, 3 products) | "auto"
+        # "fp32" (exact MFMA) | "f16s3" (split f16, 3 products) | "auto" (f16s3 where the cfg allows it, else fp32) |
+        # "f16" (opt-in plain f16, one product: faster, ~1e-3 relative error; never chosen by "auto")
+        self.precision = os.environ.get("RTOD_PRECISION", "auto")
         self.keep_all_layers = False      # debug: no activation-arena reuse (read_layer after forward)
         self.autotune = True              # split-f16 plans: measure the tile variants once per batch size (rtod_plan_autotune)
         self.options = {}                 # rtod_plan_set_option name -> int (fusion / kernel-selection switches, tests and A/B runs)
@@ -262,16 +264,17 @@ class Darknet(nn.Module):
             device = torch.cuda.current_device()
         device = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
         inp_dim = int(self.net_info["height"])
-        if self.precision not in ("fp32", "f16s3", "auto"):
-            raise ValueError("Darknet.precision must be 'fp32', 'f16s3' or 'auto'")
+        if self.precision not in ("fp32", "f16s3", "f16", "auto"):
+            raise ValueError("Darknet.precision must be 'fp32', 'f16s3', 'f16' or 'auto'")
         # BatchNorm semantics follow the module's mode like nn.BatchNorm2d: eval() = running statistics, folded into the convs
         # (the fast path, frame-independent); training mode = the statistics of the batch — what the reference's callers
         # actually run, since they never call .eval() (detect.py:185-194).  That mode is a parity path on the
         # exact-fp32 kernels (conv -> per-channel statistics -> normalise), several times slower and batch-dependent.
         batch_bn = bool(self.training and not self.bn_running_stats_in_train)
-        if batch_bn and self.precision == "f16s3":
+        if batch_bn and self.precision in ("f16s3", "f16"):
             raise RuntimeError("Darknet is in training mode (batch-statistics BatchNorm, like the reference without .eval()): that "
-                               "path runs on the exact-fp32 kernels only; call .eval() for the split-f16 kernels or set precision='auto'")
+                               "path runs on the exact-fp32 kernels only; call .eval() for the %s kernels or set precision='auto'"
+                               % ("split-f16" if self.precision == "f16s3" else "plain-f16"))
         if batch_bn and not self._warned_batch_bn:
             warnings.warn("Darknet is in training mode: BatchNorm uses the statistics of the batch, as the reference does when its "
                           "callers skip .eval() (slow parity path, results depend on the batch); call .eval() for the fast, "
@@ -299,6 +302,9 @@ class Darknet(nn.Module):
             # Cin % 32 != 0 such as yolov3-tiny do not), else the exact-fp32 MFMA kernels.  Both are HIP paths.
             if self.precision == "fp32" or batch_bn:
                 self.active_precision = "fp32"
+            elif self.precision == "f16":                        # opt-in only: "auto" never picks it
+                _ffi.check(lib.rtod_plan_set_precision(self._plan, 2))
+                self.active_precision = "f16"
             else:
                 rc = lib.rtod_plan_set_precision(self._plan, 1)
                 if rc == 0:
@@ -382,7 +388,7 @@ class Darknet(nn.Module):
         with torch.cuda.device(x.device):
             _ffi.check(lib.rtod_plan_set_train_decode(self._plan, 1 if self.TRAIN else 0))
             if _launch_ms is None:
-                if self.autotune and self.active_precision == "f16s3" and B not in self._tuned:
+                if self.autotune and self.active_precision in ("f16s3", "f16") and B not in self._tuned:
                     # first forward of a batch size: measures the tile variants (synchronises); rtod_forward itself never does
                     _ffi.check(lib.rtod_plan_autotune(self._plan, C.c_void_p(x.data_ptr()), B, C.c_void_p(out.data_ptr()), stream))
                     self._tuned.add(B)
@@ -399,7 +405,7 @@ class Darknet(nn.Module):
                 anchors.extend(m[0].anchors)
                 self.num_classes = int(blk["classes"])
         self.anchors = anchors
-        if self.active_precision == "f16s3" and self.overflow_check != "off":
+        if self.active_precision in ("f16s3", "f16") and self.overflow_check != "off":
             if self.overflow_check == "forward":
                 if self.overflowed():
                     if self.precision != "auto":

@@ -25,8 +25,9 @@ from .util import load_classes, prep_image, rescale_boxes, write_results
 class Darknetv3Detector:
     def __init__(self, images: str, destination: str, cfg_path: str, weights_path: str, resolution: int,
                  confidence: float, nms_thresh: float, CUDA: bool = True, TORCH: bool = False, batch_size: int = 8,
-                 names_path: str = None, draw: bool = True):
+                 names_path: str = None, draw: bool = True, precision: str = None):
         self.images = images
+        self.precision = precision                # None: Darknet's default (RTOD_PRECISION or "auto"); "f16": opt-in plain f16
         self.batch_size = int(batch_size)
         self.confidence = float(confidence)
         self.nms_thresh = float(nms_thresh)
@@ -51,6 +52,8 @@ class Darknetv3Detector:
             model.load_state_dict(torch.load(self.weights_path, map_location="cpu", weights_only=True))
         else:
             model.load_weights(self.weights_path)
+        if self.precision is not None:
+            model.precision = self.precision
         return model.eval()
 
     @staticmethod
