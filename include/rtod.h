@@ -77,6 +77,14 @@ int rtod_device_count(int* out);
  * device memory is touched until rtod_plan_load_weights. */
 int rtod_plan_create(const char* cfg_text, size_t len, int height, int width, int max_batch,
                      int device, rtod_plan** out);
+/* (new; opt-in) Same for a rectangular input [*,3,height,width] (height != width allowed; the reference only defines the square
+ * network, whose strides all derive from net_info['height']).  Every [yolo] head's grid GH x GW must have one integer stride
+ * on both axes, height / GH == width / GW (and height // (height // GH) == GH, likewise for width), else RTOD_E_CFG naming the
+ * layer.  Head rows keep the reference's order with G*G split into GH*GW: row r = (gy * GW + gx) * A + a, GH*GW*A rows per head.
+ * With height == width the plan (describe JSON, launches, tiles, output) is identical to rtod_plan_create's.  Option
+ * "bn_batch_stats" is refused (RTOD_E_ARG) on a plan with height != width. */
+int rtod_plan_create_rect(const char* cfg_text, size_t len, int height, int width, int max_batch,
+                          int device, rtod_plan** out);
 int rtod_plan_destroy(rtod_plan* plan);
 int rtod_plan_get_info(const rtod_plan* plan, rtod_plan_info* out);
 int rtod_plan_get_launch(const rtod_plan* plan, int index, rtod_launch_info* out);
@@ -199,6 +207,13 @@ int rtod_bbox_iou(const float* box1_dev, const float* boxes_dev, int k, int row_
  * default mode) -> out_dev float32 [3,inp_dim,inp_dim]: aspect-preserving bicubic resize, grey 128 padding,
  * /255.  cv2 is unavailable offline, so parity with cv2.INTER_CUBIC is unpinned (see preprocess.hip). */
 int rtod_prep_image(const uint8_t* img_dev, int height, int width, int bgr, int inp_dim, float* out_dev, void* stream);
+/* (new) Batched, rectangular-target prep_image: frames_dev uint8 [batch,height,width,3] (HWC frames of one camera size,
+ * contiguous) -> out_dev float32 [batch,3,out_h,out_w] in one launch.  Geometry exactly letterbox_image(img, (out_w, out_h))
+ * (util.py:360-370: s = min(out_w / width, out_h / height) in double, new size int(dim * s), offsets (out - new) // 2);
+ * interpolation, grey 128 fill, channel swap and /255 as rtod_prep_image (batch 1 with out_h == out_w == inp_dim gives its
+ * bits).  Enqueues only. */
+int rtod_prep_frames(const uint8_t* frames_dev, int batch, int height, int width, int bgr, int out_h, int out_w,
+                     float* out_dev, void* stream);
 
 /* replaces write_results                                     src/util.py:242-346
  * pred_dev [batch,n,5+num_class].  Writes detections rows [img,x1,y1,x2,y2,obj,score,cls] to

@@ -38,6 +38,7 @@ SIGNATURES = {
     "rtod_last_error": (C.c_int, [C.c_char_p, C.c_size_t]),
     "rtod_device_count": (C.c_int, [C.POINTER(C.c_int)]),
     "rtod_plan_create": (C.c_int, [C.c_char_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    "rtod_plan_create_rect": (C.c_int, [C.c_char_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "rtod_plan_destroy": (C.c_int, [C.c_void_p]),
     "rtod_plan_get_info": (C.c_int, [C.c_void_p, C.POINTER(PlanInfo)]),
     "rtod_plan_get_launch": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(LaunchInfo)]),
@@ -64,6 +65,7 @@ SIGNATURES = {
     "rtod_confidence_mask": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_float, C.c_void_p, C.c_void_p]),
     "rtod_bbox_iou": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "rtod_prep_image": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "rtod_prep_frames": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "rtod_write_results_workspace": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
     "rtod_nms_class_offset": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "rtod_write_results": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),

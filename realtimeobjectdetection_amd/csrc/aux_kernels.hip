@@ -570,20 +570,20 @@ int launch_view_to_nchw(const View& in, int B, float* out, hipStream_t s) {
 
 // ---------------------------------------------------------------------------------------------
 // stand-alone head decode = predict_transform (src/util.py:175-239) over a strided raw tensor.
-// out row r = (gy*G + gx)*A + a, attribute c  <->  raw channel a*attrs + c at cell (gy, gx).
+// out row r = (gy*GW + gx)*A + a, attribute c  <->  raw channel a*attrs + c at cell (gy, gx).
 __device__ __forceinline__ float sigm(float v) { return 1.0f / (1.0f + expf(-v)); }
 
 __global__ void decode_kernel(const float* __restrict__ raw, int64_t sb, int64_t sc, int64_t sy, int64_t sx,
                               int B, DecodeArgs d, float* __restrict__ out) {
     const int AC = d.n_anchors * d.attrs;
-    const int64_t per_img = (int64_t)d.G * d.G * AC;
+    const int64_t per_img = (int64_t)d.GH * d.GW * AC;
     const int64_t total = (int64_t)B * per_img;
     for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
         const int64_t b = t / per_img;
         const int64_t r = t - b * per_img;
         const int cell = (int)(r / AC);
         const int n = (int)(r - (int64_t)cell * AC);
-        const int gy = cell / d.G, gx = cell - gy * d.G;
+        const int gy = cell / d.GW, gx = cell - gy * d.GW;
         const int a = n / d.attrs, c = n - a * d.attrs;
         float v = raw[b * sb + (int64_t)n * sc + (int64_t)gy * sy + (int64_t)gx * sx];
         if (c >= 4) v = sigm(v);
@@ -600,8 +600,8 @@ __global__ void decode_kernel(const float* __restrict__ raw, int64_t sb, int64_t
 
 int launch_decode(const float* raw, int64_t sb, int64_t sc, int64_t sy, int64_t sx, int B,
                   const DecodeArgs& d, float* out, hipStream_t s) {
-    if (!raw || !out || d.G <= 0 || d.attrs < 5 || d.n_anchors < 1 || d.n_anchors > 4) { set_error("decode: bad args"); return RTOD_E_ARG; }
-    const int64_t total = (int64_t)B * d.G * d.G * d.n_anchors * d.attrs;
+    if (!raw || !out || d.GH <= 0 || d.GW <= 0 || d.attrs < 5 || d.n_anchors < 1 || d.n_anchors > 4) { set_error("decode: bad args"); return RTOD_E_ARG; }
+    const int64_t total = (int64_t)B * d.GH * d.GW * d.n_anchors * d.attrs;
     hipLaunchKernelGGL(decode_kernel, dim3(grid_for(total, 256)), dim3(256), 0, s, raw, sb, sc, sy, sx, B, d, out);
     return hip_fail(hipGetLastError(), "decode launch");
 }

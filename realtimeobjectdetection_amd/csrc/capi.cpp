@@ -37,12 +37,7 @@ int rtod_device_count(int* out) {
     return RTOD_OK;
 }
 
-int rtod_plan_create(const char* cfg_text, size_t len, int height, int width, int max_batch, int device, rtod_plan** out) {
-    RTOD_GUARD_BEGIN
-    if (!cfg_text || !out) { set_error("plan_create: null pointer"); return RTOD_E_ARG; }
-    *out = nullptr;
-    if (height < 1 || width < 1 || max_batch < 1 || device < 0) { set_error("plan_create: bad geometry %dx%d batch %d device %d", height, width, max_batch, device); return RTOD_E_ARG; }
-    if (height != width) { set_error("plan_create: only square inputs are supported (the reference derives every stride from net_info['height'])"); return RTOD_E_ARG; }
+static int plan_create(const char* cfg_text, size_t len, int height, int width, int max_batch, int device, rtod_plan** out) {
     rtod_plan* h = new rtod_plan();
     h->p.height = height; h->p.width = width; h->p.max_batch = max_batch; h->p.device = device;
     int rc = h->p.parse(std::string(cfg_text, len));
@@ -51,6 +46,24 @@ int rtod_plan_create(const char* cfg_text, size_t len, int height, int width, in
     if (rc) { delete h; return rc; }
     *out = h;
     return RTOD_OK;
+}
+
+int rtod_plan_create(const char* cfg_text, size_t len, int height, int width, int max_batch, int device, rtod_plan** out) {
+    RTOD_GUARD_BEGIN
+    if (!cfg_text || !out) { set_error("plan_create: null pointer"); return RTOD_E_ARG; }
+    *out = nullptr;
+    if (height < 1 || width < 1 || max_batch < 1 || device < 0) { set_error("plan_create: bad geometry %dx%d batch %d device %d", height, width, max_batch, device); return RTOD_E_ARG; }
+    if (height != width) { set_error("plan_create: only square inputs are supported (the reference derives every stride from net_info['height']); use rtod_plan_create_rect"); return RTOD_E_ARG; }
+    return plan_create(cfg_text, len, height, width, max_batch, device, out);
+    RTOD_GUARD_END
+}
+
+int rtod_plan_create_rect(const char* cfg_text, size_t len, int height, int width, int max_batch, int device, rtod_plan** out) {
+    RTOD_GUARD_BEGIN
+    if (!cfg_text || !out) { set_error("plan_create_rect: null pointer"); return RTOD_E_ARG; }
+    *out = nullptr;
+    if (height < 1 || width < 1 || max_batch < 1 || device < 0) { set_error("plan_create_rect: bad geometry %dx%d batch %d device %d", height, width, max_batch, device); return RTOD_E_ARG; }
+    return plan_create(cfg_text, len, height, width, max_batch, device, out);
     RTOD_GUARD_END
 }
 
@@ -286,7 +299,7 @@ int rtod_predict_transform(const float* raw_dev, int batch, int attrs, int grid,
     if (batch < 1 || attrs < 5 || grid < 1 || n_anchors < 1 || n_anchors > 4 || inp_dim < grid) { set_error("predict_transform: bad shape"); return RTOD_E_ARG; }
     const int stride = inp_dim / grid;                 // util.py:194
     if (inp_dim / stride != grid) { set_error("predict_transform: grid %d inconsistent with inp_dim %d (util.py:195 would mis-shape)", grid, inp_dim); return RTOD_E_ARG; }
-    DecodeArgs d; d.enabled = 1; d.G = grid; d.attrs = attrs; d.n_anchors = n_anchors; d.train = train ? 1 : 0; d.stride = (float)stride;
+    DecodeArgs d; d.enabled = 1; d.GH = grid; d.GW = grid; d.attrs = attrs; d.n_anchors = n_anchors; d.train = train ? 1 : 0; d.stride = (float)stride;
     for (int a = 0; a < n_anchors; ++a) {
         d.aw[a] = (float)((double)anchors_wh[2 * a] / (double)stride);
         d.ah[a] = (float)((double)anchors_wh[2 * a + 1] / (double)stride);
@@ -308,6 +321,12 @@ int rtod_bbox_iou(const float* box1_dev, const float* boxes_dev, int k, int row_
 int rtod_prep_image(const uint8_t* img_dev, int height, int width, int bgr, int inp_dim, float* out_dev, void* stream) {
     RTOD_GUARD_BEGIN
     return launch_prep_image(img_dev, height, width, bgr, inp_dim, out_dev, (hipStream_t)stream);
+    RTOD_GUARD_END
+}
+
+int rtod_prep_frames(const uint8_t* frames_dev, int batch, int height, int width, int bgr, int out_h, int out_w, float* out_dev, void* stream) {
+    RTOD_GUARD_BEGIN
+    return launch_prep_frames(frames_dev, batch, height, width, bgr, out_h, out_w, out_dev, (hipStream_t)stream);
     RTOD_GUARD_END
 }
 

@@ -311,7 +311,7 @@ __device__ __forceinline__ void conv_f16s3_epilogue(const ConvArgs& a, f32x4 (&a
                 int m = bm * BM + rg + r0;
                 const int b = m / hw;
                 int cell = m - b * hw;
-                int gy = cell / a.dec.G, gx = cell - gy * a.dec.G;
+                int gy = cell / a.dec.GW, gx = cell - gy * a.dec.GW;
                 // The loop is VALU-bound (1 600 instructions per thread per 128-row tile with libm expf, an IEEE divide and
                 // 64-bit index arithmetic per element: the decode epilogue was 58 % of the 76x76 head kernel): hardware
                 // exp2 / rcp (1 ulp; the result has to meet 1e-4) and a running output pointer.
@@ -326,8 +326,8 @@ __device__ __forceinline__ void conv_f16s3_epilogue(const ConvArgs& a, f32x4 (&a
                         else if (c < 4) { const float t2 = sg * 2.0f; o = (t2 * t2) * anc; }
                         *op = o;
                         op += row_step; cell += RSTEP; gx += RSTEP;
-                        while (gx >= a.dec.G) { gx -= a.dec.G; ++gy; }
-                        while (cell >= hw) { cell -= hw; gy -= a.dec.G; op += img_fix; }
+                        while (gx >= a.dec.GW) { gx -= a.dec.GW; ++gy; }
+                        while (cell >= hw) { cell -= hw; gy -= a.dec.GH; op += img_fix; }
                     }
                 } else
                 for (int r = r0; r < RG && m < M; r += RSTEP, m += RSTEP) {
@@ -344,8 +344,8 @@ __device__ __forceinline__ void conv_f16s3_epilogue(const ConvArgs& a, f32x4 (&a
                     }
                     *op = o;
                     op += row_step; cell += RSTEP; gx += RSTEP;
-                    while (gx >= a.dec.G) { gx -= a.dec.G; ++gy; }
-                    while (cell >= hw) { cell -= hw; gy -= a.dec.G; op += img_fix; }   // G*G < RSTEP: a step may cross several images
+                    while (gx >= a.dec.GW) { gx -= a.dec.GW; ++gy; }
+                    while (cell >= hw) { cell -= hw; gy -= a.dec.GH; op += img_fix; }   // GH*GW < RSTEP: a step may cross several images
                 }
             }
         } else {

@@ -67,7 +67,7 @@ __device__ __forceinline__ void conv_f32_store(const ConvArgs& a, int m, int n, 
     if (a.res) v += a.res[(int64_t)m * a.res_ldc + a.res_coff + n];
     if (a.dec.enabled) {
         const int b = m / hw, cell = m - b * hw;
-        const int gy = cell / a.dec.G, gx = cell - gy * a.dec.G;
+        const int gy = cell / a.dec.GW, gx = cell - gy * a.dec.GW;
         v = decode_value(a.dec, v, n, gx, gy);
         a.out[(int64_t)b * a.dec.img_stride + a.dec.head_off + (int64_t)cell * a.Cout + n] = v;
     } else if (a.out_split) {

@@ -250,10 +250,17 @@ int Plan::resolve_shapes() {
             case LT_YOLO: {
                 if (i < 1) { set_error("cfg: yolo as first layer"); return RTOD_E_CFG; }
                 const int A = (int)L.anchors.size();
-                if (ph != pw) { set_error("cfg: layer %d: non-square head %dx%d unsupported (reference assumes square)", i, ph, pw); return RTOD_E_CFG; }
                 if (pc != A * (5 + L.classes)) { set_error("cfg: layer %d: head has %d channels, expected %d", i, pc, A * (5 + L.classes)); return RTOD_E_CFG; }
-                if (height % ph) { /* stride = inp_dim // G, G' = inp_dim // stride (util.py:194-195) must equal G */ }
-                if (height / (height / ph) != ph) { set_error("cfg: layer %d: grid %d does not divide input %d", i, ph, height); return RTOD_E_CFG; }
+                // stride = inp_dim // G, G' = inp_dim // stride (util.py:194-195) must equal G — per axis, and the decode has one stride:
+                // a rectangular input needs height // GH == width // GW (square inputs: the reference's own condition)
+                if (ph > height || pw > width || height / (height / ph) != ph || width / (width / pw) != pw) {
+                    set_error("cfg: layer %d: grid %dx%d does not divide input %dx%d", i, ph, pw, height, width); return RTOD_E_CFG;
+                }
+                if (height / ph != width / pw) {
+                    set_error("cfg: layer %d: head grid %dx%d has stride %d along y but %d along x for input %dx%d (one integer stride on both axes is required)",
+                              i, ph, pw, height / ph, width / pw, height, width);
+                    return RTOD_E_CFG;
+                }
                 if (attrs && attrs != 5 + L.classes) { set_error("cfg: heads with different class counts"); return RTOD_E_CFG; }
                 attrs = 5 + L.classes;
                 L.cout = pc; L.hout = ph; L.wout = pw;
@@ -299,7 +306,11 @@ int Plan::set_option(const char* name, int value) {
     else if (k == "pwd_kernel") flag = &opt_pwd_kernel;
     else if (k == "stem2_kernel") flag = &opt_stem2_kernel;
     else if (k == "k_slices") flag = &opt_k_slices;
-    else if (k == "bn_batch_stats") flag = &opt_bn_batch_stats;
+    else if (k == "bn_batch_stats") {
+        // batch-statistics BatchNorm is the reference's own (square) training-mode path: not offered on a rectangular plan
+        if (value && height != width) { set_error("set_option: bn_batch_stats is not supported on a rectangular plan (%dx%d)", height, width); return RTOD_E_ARG; }
+        flag = &opt_bn_batch_stats;
+    }
     else if (k == "k_slice_workgroups") flag = &opt_k_slice_workgroups;
     else if (k == "patch_kernel") flag = &opt_patch_kernel;
     else if (k == "stem_kernel") flag = &opt_stem_kernel;
@@ -414,8 +425,8 @@ int Plan::plan_buffers() {
                     if (F.type == LT_SHORTCUT) { l.out_layer = F.index; l.in2_layer = F.srcs[1]; }
                     else {
                         l.out_layer = -2;
-                        DecodeArgs d; d.enabled = 1; d.G = F.hout; d.attrs = 5 + F.classes; d.n_anchors = (int)F.anchors.size();
-                        const int stride = height / F.hout;
+                        DecodeArgs d; d.enabled = 1; d.GH = F.hout; d.GW = F.wout; d.attrs = 5 + F.classes; d.n_anchors = (int)F.anchors.size();
+                        const int stride = height / F.hout;                 // == width / F.wout (resolve_shapes)
                         d.stride = (float)stride;
                         for (size_t a = 0; a < F.anchors.size(); ++a) {
                             d.aw[a] = (float)((double)F.anchors[a].first / (double)stride);     // Python float divide -> FloatTensor (util.py:213-216)
@@ -447,8 +458,8 @@ int Plan::plan_buffers() {
             case LT_YOLO:
                 if (!L.fused_away) {
                     l.kind = LK_DECODE; l.in_layer = i - 1; l.out_layer = -2;
-                    DecodeArgs d; d.enabled = 1; d.G = L.hout; d.attrs = 5 + L.classes; d.n_anchors = (int)L.anchors.size();
-                    const int stride = height / L.hout;
+                    DecodeArgs d; d.enabled = 1; d.GH = L.hout; d.GW = L.wout; d.attrs = 5 + L.classes; d.n_anchors = (int)L.anchors.size();
+                    const int stride = height / L.hout;                     // == width / L.wout (resolve_shapes)
                     d.stride = (float)stride;
                     for (size_t a = 0; a < L.anchors.size(); ++a) {
                         d.aw[a] = (float)((double)L.anchors[a].first / (double)stride);
@@ -906,10 +917,11 @@ int Plan::tune_launch(size_t li, ConvArgs& a, int batch, hipStream_t s) {
     const Layer& L = layers[l.layer];
     const bool pw = a.pw_wh != nullptr;
     // shape + everything else the candidate set depends on (a second plan with other kernel-selection options must not inherit tiles)
-    // (the precision too: an f16 plan must not inherit an f16s3 plan's tile, or the reverse)
+    // (the precision too: an f16 plan must not inherit an f16s3 plan's tile, or the reverse; and the input geometry hin / win / pad:
+    // two layers with the same output shape but another input extent or padding are other problems, e.g. across rectangular plans)
     const std::vector<int> key = {L.cin, L.cout, L.size, L.stride, L.hout, L.wout, l.in2_layer >= 0, l.out_layer == -2, pw ? a.pw_cout : 0,
                                   convs[l.conv_slot].band ? 1 : 0, opt_ring_kernel ? 1 : 0, opt_patch_kernel ? 1 : 0, opt_pwd_kernel ? 1 : 0, L.act,
-                                  precision};
+                                  precision, L.hin, L.win, L.pad};
     auto it = tune_cache.find(key);
     if (it != tune_cache.end()) { tuning[li] = it->second; return RTOD_OK; }
     // process-wide memo (device, batch, shape): a second plan of the same network (bench.py keeps two batches in flight)

@@ -39,13 +39,13 @@ struct View {
 // stand-alone kernel.
 struct DecodeArgs {
     int enabled = 0;
-    int G = 0;               // grid size
+    int GH = 0, GW = 0;      // grid rows / columns (square plans: GH == GW == G); rows r = (gy * GW + gx) * A + a
     int attrs = 0;           // 5 + classes
     int n_anchors = 0;
     int train = 0;           // TRAIN=True: sigmoids only
     int v5 = 0;              // cfg extension `[yolo] decode=v5` (YOLOv5-style heads): xy = (2 s - 0.5 + g) * stride, wh = (2 s)^2 * anchor
                              // (aw / ah then hold the anchors in PIXELS), everything else sigmoid; not reference behaviour
-    float stride = 0.f;      // inp_dim // G
+    float stride = 0.f;      // inp_dim // G: one integer stride, the same along both axes (checked at plan build)
     float aw[4] = {0, 0, 0, 0};   // fp32(anchor_w / stride)
     float ah[4] = {0, 0, 0, 0};
     int64_t img_stride = 0;  // total_rows * attrs
@@ -204,6 +204,7 @@ int launch_conv_stem(const float* x_nchw, const float* w, const float* bias, con
 int launch_conv_stem_split(const float* x_nchw, const _Float16* wh, const _Float16* wl, const float* inv_scale, const float* bias,
                            const View& out, int B, int H, int W, int Ho, int Wo, int stride, int Cout, int leaky, int32_t* ovf, hipStream_t s);
 int launch_prep_image(const unsigned char* img, int h, int w, int bgr, int inp_dim, float* out, hipStream_t s);
+int launch_prep_frames(const unsigned char* frames, int batch, int h, int w, int bgr, int out_h, int out_w, float* out, hipStream_t s);
 int launch_pack_input(const float* x_nchw, int B, int C, int H, int W, float* out_nhwc, int Cp, hipStream_t s);
 int launch_upsample2x(const View& in, const View& out, int B, hipStream_t s);
 int launch_add(const View& a, const View& b, const View& out, int B, hipStream_t s);

@@ -2,7 +2,7 @@
 
 Drop-in surface (reference: src/darknet.py:138-603, SURVEY.md §8 b): ``Darknet(cfg_file_path, CUDA)``,
 ``.blocks`` / ``.net_info`` (mutable; callers set ``net_info["height"]``) / ``.module_list`` /
-``.header`` / ``.seen`` / ``.CUDA`` / ``.TRAIN``, ``get_blocks()``, ``get_module_list()``,
+``.header`` / ``.seen`` / ``.CUDA`` / ``.TRAIN``, (extension) ``.input_width`` for rectangular inputs, ``get_blocks()``, ``get_module_list()``,
 ``load_weights(path)``, ``load_state_dict`` with the reference's key names
 (``module_list.{i}.conv_{i}.weight`` ...), ``forward(x) -> [B,N,5+C]``, ``train_mode()``, and after
 the first forward ``.anchors`` / ``.num_classes``.
@@ -111,6 +111,9 @@ class Darknet(nn.Module):
         # "f16" (opt-in plain f16, one product: faster, ~1e-3 relative error; never chosen by "auto")
         self.precision = os.environ.get("RTOD_PRECISION", "auto")
         self.keep_all_layers = False      # debug: no activation-arena reuse (read_layer after forward)
+        # None: square input net_info["height"] x net_info["height"] (the reference's calling sequence).  An int: opt-in rectangular
+        # input [B,3,net_info["height"],input_width] (rtod_plan_create_rect; every head needs one integer stride on both axes)
+        self.input_width = None
         self.autotune = True              # split-f16 plans: measure the tile variants once per batch size (rtod_plan_autotune)
         self.options = {}                 # rtod_plan_set_option name -> int (fusion / kernel-selection switches, tests and A/B runs)
         # split-f16 range guard (|activation| < 8188): producers saturate and raise a device flag.  "write_results": the flag
@@ -264,6 +267,7 @@ class Darknet(nn.Module):
             device = torch.cuda.current_device()
         device = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
         inp_dim = int(self.net_info["height"])
+        width = inp_dim if self.input_width is None else int(self.input_width)
         if self.precision not in ("fp32", "f16s3", "f16", "auto"):
             raise ValueError("Darknet.precision must be 'fp32', 'f16s3', 'f16' or 'auto'")
         # BatchNorm semantics follow the module's mode like nn.BatchNorm2d: eval() = running statistics, folded into the convs
@@ -275,6 +279,9 @@ class Darknet(nn.Module):
             raise RuntimeError("Darknet is in training mode (batch-statistics BatchNorm, like the reference without .eval()): that "
                                "path runs on the exact-fp32 kernels only; call .eval() for the %s kernels or set precision='auto'"
                                % ("split-f16" if self.precision == "f16s3" else "plain-f16"))
+        if batch_bn and self.input_width is not None and width != inp_dim:
+            raise RuntimeError("Darknet is in training mode (batch-statistics BatchNorm, the reference's square path): a rectangular "
+                               "input (input_width=%d, height %d) runs in eval mode only; call .eval()" % (width, inp_dim))
         if batch_bn and not self._warned_batch_bn:
             warnings.warn("Darknet is in training mode: BatchNorm uses the statistics of the batch, as the reference does when its "
                           "callers skip .eval() (slow parity path, results depend on the batch); call .eval() for the fast, "
@@ -283,12 +290,16 @@ class Darknet(nn.Module):
         opts = dict(self.options)
         if batch_bn:
             opts["bn_batch_stats"] = 1
-        key = (inp_dim, int(max_batch), device.index, bool(self.keep_all_layers), "fp32" if batch_bn else self.precision, tuple(sorted(opts.items())))
+        key = (inp_dim, int(max_batch), device.index, bool(self.keep_all_layers), "fp32" if batch_bn else self.precision, tuple(sorted(opts.items())),
+               self.input_width is not None, width)
         if self._plan is None or self._plan_key != key:
             self._destroy_plan()
             h = C.c_void_p()
             txt = self._cfg_text.encode()
-            _ffi.check(lib.rtod_plan_create(txt, len(txt), inp_dim, inp_dim, int(max_batch), device.index, C.byref(h)))
+            if self.input_width is None:
+                _ffi.check(lib.rtod_plan_create(txt, len(txt), inp_dim, inp_dim, int(max_batch), device.index, C.byref(h)))
+            else:
+                _ffi.check(lib.rtod_plan_create_rect(txt, len(txt), inp_dim, width, int(max_batch), device.index, C.byref(h)))
             self._plan, self._plan_key = h, key
             self._tuned = set()
             if self.keep_all_layers:
@@ -371,6 +382,11 @@ class Darknet(nn.Module):
         if x.dtype != torch.float32 or x.dim() != 4 or x.size(1) != 3:
             raise ValueError("Darknet.forward: expected float32 [B,3,H,W], got %s %s" % (x.dtype, tuple(x.shape)))
         inp_dim = int(self.net_info["height"])
+        if self.input_width is not None:
+            if x.size(2) != inp_dim or x.size(3) != int(self.input_width):
+                raise ValueError("Darknet.forward: input is %dx%d (HxW) but the model expects net_info['height'] x input_width = %dx%d"
+                                 % (x.size(2), x.size(3), inp_dim, int(self.input_width)))
+            return inp_dim
         if x.size(2) != inp_dim or x.size(3) != inp_dim:
             raise ValueError("Darknet.forward: input is %dx%d but net_info['height'] = %d (set it like detect.py:47 does)"
                              % (x.size(2), x.size(3), inp_dim))

@@ -9,6 +9,10 @@ coordinates like the reference stores them) and ``det_<cfg>_<image>`` outputs.  
 nothing only because of that), a trailing partial batch is processed, the box rescale uses the actual
 resolution instead of the constant 416, the model runs in ``.eval()`` mode, images are read and
 drawn with PIL (OpenCV is not a dependency), preprocessing runs on the GPU (``util.prep_image``).
+
+Extension: ``resolution`` may be a ``[width, height]`` pair (both multiples of 32 and greater than 32): the network then
+runs a rectangular input (``Darknet.input_width``), a batch of equal-sized frames is letterboxed in one launch
+(``util.prep_frames``) and boxes are rescaled per axis.  An int is the reference's square resolution, unchanged.
 """
 import json
 import os
@@ -19,11 +23,25 @@ import numpy as np
 import torch
 
 from .darknet import Darknet
-from .util import load_classes, prep_image, rescale_boxes, write_results
+from .util import load_classes, prep_frames, prep_image, rescale_boxes, write_results
+
+
+def parse_resolution(resolution):
+    """int -> (r, r, False), checked where the reference checks it (the asserts of __call__); ``[width, height]`` ->
+    (width, height, True), each side a multiple of 32 and greater than 32 (the reference's two asserts, detect.py:51-52, per axis)."""
+    if not isinstance(resolution, (tuple, list)):
+        return int(resolution), int(resolution), False
+    if len(resolution) != 2:
+        raise ValueError("resolution: expected an int or a [width, height] pair, got %r" % (resolution,))
+    w, h = int(resolution[0]), int(resolution[1])
+    for v in (w, h):
+        if v % 32 or v <= 32:
+            raise ValueError("resolution %r: every side must be a multiple of 32 and greater than 32" % (resolution,))
+    return w, h, True
 
 
 class Darknetv3Detector:
-    def __init__(self, images: str, destination: str, cfg_path: str, weights_path: str, resolution: int,
+    def __init__(self, images: str, destination: str, cfg_path: str, weights_path: str, resolution,
                  confidence: float, nms_thresh: float, CUDA: bool = True, TORCH: bool = False, batch_size: int = 8,
                  names_path: str = None, draw: bool = True, precision: str = None):
         self.images = images
@@ -34,7 +52,8 @@ class Darknetv3Detector:
         self.destination = destination
         self.cfg_path = cfg_path
         self.weights_path = weights_path
-        self.reso = int(resolution)
+        self.reso_w, self.reso_h, self.rect = parse_resolution(resolution)
+        self.reso = (self.reso_w, self.reso_h) if self.rect else self.reso_h
         self.CUDA = CUDA
         self.TORCH = TORCH
         self.draw = draw
@@ -75,10 +94,13 @@ class Darknetv3Detector:
     def __call__(self, *args, **kwargs):
         model = self.configure_darknet()
         os.makedirs(self.destination, exist_ok=True)
-        model.net_info["height"] = self.reso
+        model.net_info["height"] = self.reso_h
+        if self.rect:
+            model.input_width = self.reso_w
         self.inp_dim = int(model.net_info["height"])
         assert self.inp_dim % 32 == 0
         assert self.inp_dim > 32
+        canvas = (self.reso_w, self.reso_h) if self.rect else self.inp_dim     # rescale_boxes / prep_image convention
         paths, names = self.read_directory(self.images)
         print("Number of Images= ", len(paths))
         for start_idx in range(0, len(paths), self.batch_size):
@@ -87,7 +109,10 @@ class Darknetv3Detector:
             loaded = [self._load_rgb(p) for p in b_paths]
             im_dims = torch.tensor([(im.shape[1], im.shape[0]) for im in loaded], dtype=torch.float32)
             t0 = time.time()
-            x = torch.cat([prep_image(im, self.inp_dim, mode="RGB") for im in loaded], 0)
+            if self.rect and len({im.shape for im in loaded}) == 1:
+                x = prep_frames(np.stack(loaded), canvas, mode="RGB")          # one launch for the batch
+            else:
+                x = torch.cat([prep_image(im, canvas, mode="RGB") for im in loaded], 0)
             with torch.no_grad():
                 prediction = write_results(model(x), self.num_classes, self.confidence, self.nms_thresh)
             torch.cuda.synchronize()
@@ -105,7 +130,7 @@ class Darknetv3Detector:
                 self.metrics[name] = 0 if rows is None or rows.size(0) == 0 else rows.tolist()
                 self.timings[name] = dt / len(b_names)
             if self.draw and not isinstance(prediction, int):
-                boxes = rescale_boxes(prediction, im_dims, self.inp_dim).cpu()
+                boxes = rescale_boxes(prediction, im_dims, canvas).cpu()
                 for j, (name, im) in enumerate(zip(b_names, loaded)):
                     self._draw_and_save(im, boxes[boxes[:, 0] == j], name)
             elif self.draw:

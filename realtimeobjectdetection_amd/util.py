@@ -7,6 +7,7 @@ Same names, argument meaning and return conventions as the reference (SURVEY.md 
   -> float32 ``[D,8]`` tensor on prediction's device, or the Python int ``0``
 * ``confidence_mask(tensor, confidence)``                                              src/util.py:106-117
 * ``bbox_iou(box1, box2)``                                                             src/util.py:120-153
+* ``prep_image`` / ``rescale_boxes`` (int or ``(width, height)`` canvas), ``prep_frames`` (batched, new)    src/util.py:349-397
 
 All tensors must be CUDA (ROCm) float32 tensors; there is no CPU fallback.
 """
@@ -44,15 +45,37 @@ def load_classes(names_file_path: str = None) -> list:
     return out
 
 
+def _canvas(inp_dim):
+    """``inp_dim`` -> (width, height): an int is the reference's square canvas, a pair is ``letterbox_image``'s (w, h)."""
+    if isinstance(inp_dim, (tuple, list)):
+        if len(inp_dim) != 2:
+            raise ValueError("inp_dim: expected an int or a (width, height) pair, got %r" % (inp_dim,))
+        return int(inp_dim[0]), int(inp_dim[1])
+    return int(inp_dim), int(inp_dim)
+
+
+def letterbox_geometry(img_w: int, img_h: int, size) -> tuple:
+    """``(new_w, new_h, off_x, off_y)`` of ``letterbox_image(img, (w, h))`` (reference: src/util.py:360-370: Python float
+    ``min``, ``int()`` truncation, ``// 2`` offsets) for a canvas ``size`` = int or (width, height): what the prep kernels place
+    and what ``rescale_boxes`` undoes.  Host arithmetic only."""
+    w, h = _canvas(size)
+    s = min(w / img_w, h / img_h)
+    new_w, new_h = int(img_w * s), int(img_h * s)
+    return new_w, new_h, (w - new_w) // 2, (h - new_h) // 2
+
+
 def prep_image(img, inp_dim, mode="BGR", device=None) -> torch.Tensor:
     """uint8 HWC image (numpy or torch) -> float32 ``[1,3,inp_dim,inp_dim]`` network input on the GPU
     (reference: src/util.py:375-397 + letterbox_image 349-372).  Only the uint8 pixels cross PCIe; resize,
     padding, channel swap and /255 run in a HIP kernel.  ``mode='BGR'`` (OpenCV order, the reference's default)
-    is swapped to RGB.  Parity with cv2.INTER_CUBIC is unpinned (OpenCV is not available offline)."""
+    is swapped to RGB.  Parity with cv2.INTER_CUBIC is unpinned (OpenCV is not available offline).
+    ``inp_dim`` may also be a ``(width, height)`` pair (letterbox_image's convention): ``[1,3,height,width]``."""
     assert mode == "BGR" or mode == "RGB"
     t = torch.as_tensor(img)
     if t.dtype != torch.uint8 or t.dim() != 3 or t.size(2) != 3:
         raise ValueError("prep_image: expected uint8 [H,W,3], got %s %s" % (t.dtype, tuple(t.shape)))
+    if isinstance(inp_dim, (tuple, list)):
+        return prep_frames(t.unsqueeze(0), inp_dim, mode=mode, device=device)
     if device is None:
         device = t.device if t.is_cuda else torch.device("cuda", torch.cuda.current_device())
     t = t.to(device).contiguous()
@@ -63,15 +86,42 @@ def prep_image(img, inp_dim, mode="BGR", device=None) -> torch.Tensor:
     return out
 
 
-def rescale_boxes(output: torch.Tensor, im_dim_list: torch.Tensor, inp_dim: int) -> torch.Tensor:
+def prep_frames(frames, size, mode="BGR", device=None) -> torch.Tensor:
+    """uint8 ``[B,H,W,3]`` frames of one camera size (numpy or torch) -> float32 ``[B,3,height,width]`` on the GPU in one
+    kernel launch, ``size = (width, height)`` or an int for a square canvas: ``prep_image`` of every frame, letterboxed
+    exactly like ``letterbox_image(img, (width, height))`` (rtod_prep_frames)."""
+    assert mode == "BGR" or mode == "RGB"
+    w, h = _canvas(size)
+    t = torch.as_tensor(frames)
+    if t.dtype != torch.uint8 or t.dim() != 4 or t.size(3) != 3 or t.size(0) < 1:
+        raise ValueError("prep_frames: expected uint8 [B,H,W,3], got %s %s" % (t.dtype, tuple(t.shape)))
+    if device is None:
+        device = t.device if t.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    t = t.to(device).contiguous()
+    out = torch.empty((t.size(0), 3, h, w), dtype=torch.float32, device=t.device)
+    with torch.cuda.device(t.device):
+        _ffi.check(_ffi.lib().rtod_prep_frames(C.c_void_p(t.data_ptr()), t.size(0), t.size(1), t.size(2), 1 if mode == "BGR" else 0,
+                                               h, w, C.c_void_p(out.data_ptr()), _stream(t.device)))
+    return out
+
+
+def rescale_boxes(output: torch.Tensor, im_dim_list: torch.Tensor, inp_dim) -> torch.Tensor:
     """Undo the letterbox on detection rows ``[img,x1,y1,x2,y2,...]`` and clamp to the image
     (reference: detect.py:120-136, which hard-codes 416 for the scale; here the actual ``inp_dim``).
-    ``im_dim_list``: ``[n_images, 2]`` = (width, height) per image.  Returns a new tensor."""
+    ``im_dim_list``: ``[n_images, 2]`` = (width, height) per image.  ``inp_dim``: int, or the ``(width, height)`` of a
+    rectangular canvas (offsets ``(w - s*img_w)/2`` and ``(h - s*img_h)/2`` per axis).  Returns a new tensor."""
     out = output.clone()
+    cw, ch = _canvas(inp_dim)
     dims = im_dim_list.to(out.device, torch.float32)[out[:, 0].long()]
-    scale = torch.min(float(inp_dim) / dims, 1)[0].view(-1, 1)
-    out[:, [1, 3]] -= (inp_dim - scale * dims[:, 0].view(-1, 1)) / 2
-    out[:, [2, 4]] -= (inp_dim - scale * dims[:, 1].view(-1, 1)) / 2
+    if cw == ch and not isinstance(inp_dim, (tuple, list)):
+        scale = torch.min(float(inp_dim) / dims, 1)[0].view(-1, 1)
+        out[:, [1, 3]] -= (inp_dim - scale * dims[:, 0].view(-1, 1)) / 2
+        out[:, [2, 4]] -= (inp_dim - scale * dims[:, 1].view(-1, 1)) / 2
+    else:
+        canvas = torch.tensor([cw, ch], dtype=torch.float32, device=out.device)
+        scale = torch.min(canvas / dims, 1)[0].view(-1, 1)
+        out[:, [1, 3]] -= (cw - scale * dims[:, 0].view(-1, 1)) / 2
+        out[:, [2, 4]] -= (ch - scale * dims[:, 1].view(-1, 1)) / 2
     out[:, 1:5] /= scale
     out[:, [1, 3]] = torch.minimum(torch.clamp(out[:, [1, 3]], min=0.0), dims[:, 0].view(-1, 1))
     out[:, [2, 4]] = torch.minimum(torch.clamp(out[:, [2, 4]], min=0.0), dims[:, 1].view(-1, 1))
