@@ -31,28 +31,10 @@
 //
 // Limits: stride 1, pad 1, 3x3, Cin % 32 == 0, W <= 94.
 #include "conv_f16s3_common.h"
-#include <atomic>
 #include <cstdio>
 #include <cstdlib>
 
 namespace rtod {
-
-template <int N> __device__ __forceinline__ void wait_vmcnt() {
-    static_assert(N >= 0 && N <= 30 && N % 2 == 0, "vmcnt literal");
-#define RTOD_VMCNT_CASE(n) else if constexpr (N == n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory");
-    if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    RTOD_VMCNT_CASE(2) RTOD_VMCNT_CASE(4) RTOD_VMCNT_CASE(6) RTOD_VMCNT_CASE(8) RTOD_VMCNT_CASE(10) RTOD_VMCNT_CASE(12) RTOD_VMCNT_CASE(14)
-    RTOD_VMCNT_CASE(16) RTOD_VMCNT_CASE(18) RTOD_VMCNT_CASE(20) RTOD_VMCNT_CASE(22) RTOD_VMCNT_CASE(24) RTOD_VMCNT_CASE(26) RTOD_VMCNT_CASE(28) RTOD_VMCNT_CASE(30)
-#undef RTOD_VMCNT_CASE
-}
-template <typename T, int N> __device__ __forceinline__ void tie_regs(T (&r)[N]) {   // pins later uses below a preceding wait
-    static_assert(N >= 1 && N <= 5, "tie_regs");
-    if constexpr (N == 1) asm volatile("" : "+v"(r[0]) :: "memory");
-    else if constexpr (N == 2) asm volatile("" : "+v"(r[0]), "+v"(r[1]) :: "memory");
-    else if constexpr (N == 3) asm volatile("" : "+v"(r[0]), "+v"(r[1]), "+v"(r[2]) :: "memory");
-    else if constexpr (N == 4) asm volatile("" : "+v"(r[0]), "+v"(r[1]), "+v"(r[2]), "+v"(r[3]) :: "memory");
-    else asm volatile("" : "+v"(r[0]), "+v"(r[1]), "+v"(r[2]), "+v"(r[3]), "+v"(r[4]) :: "memory");
-}
 
 __device__ __forceinline__ int band_swz(int row) { return (row >> 1) & 3; }
 
@@ -136,10 +118,8 @@ void conv_band_f16s3_kernel(const ConvArgs a, const int grid_m, const int grid_n
 
     const int nwg = grid_m * grid_n;
     int bid = blockIdx.x;
-    if (!a.xcd_by_n) {                                         // XCD x (= blockIdx % 8) takes a contiguous range of pixel tiles
-        const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-    }                                                          // else: grid_n % 8 == 0, bn = bid % grid_n -> XCD = bn % 8
+    if (!a.xcd_by_n) bid = xcd_remap(bid, nwg);                // XCD x (= blockIdx % 8) takes a contiguous range of pixel tiles
+                                                               // else: grid_n % 8 == 0, bn = bid % grid_n -> XCD = bn % 8
     const int bm = bid / grid_n, bn = bid - bm * grid_n;
 
     const int tid = KG == 1 ? (int)threadIdx.x : (int)threadIdx.x - kg * NT;   // thread index within the K group
@@ -167,9 +147,9 @@ void conv_band_f16s3_kernel(const ConvArgs a, const int grid_m, const int grid_n
         wbase[i] = (row0 + i * RPP < BN) ? (unsigned)((bn * BN + (BAND_TR ? tr_chan_of_row(row0 + i * RPP) : row0 + i * RPP)) * 32 + c16 * 8) * 2u : OOB;
     const unsigned wchunk = (unsigned)a.Npad * (HBK * 2);        // bytes of one (chunk, tap) panel of a weight plane ([chunk][Npad][32])
 
-    const __amdgpu_buffer_rsrc_t rs_a = __builtin_amdgcn_make_buffer_rsrc((void*)a.in, 0, a.in_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_wh = __builtin_amdgcn_make_buffer_rsrc((void*)a.w_hi, 0, a.w_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_wl = __builtin_amdgcn_make_buffer_rsrc((void*)a.w_lo, 0, a.w_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_a = buffer_rsrc(a.in, a.in_bytes);
+    const __amdgpu_buffer_rsrc_t rs_wh = buffer_rsrc(a.w_hi, a.w_bytes);
+    const __amdgpu_buffer_rsrc_t rs_wl = buffer_rsrc(a.w_lo, a.w_bytes);
 
     const int n_cc = a.Cin / 32 / KG;                          // channel chunks of this group: kg, kg + KG, ...
     const int nsteps = 9 * n_cc;
@@ -210,8 +190,8 @@ void conv_band_f16s3_kernel(const ConvArgs a, const int grid_m, const int grid_n
 #pragma unroll
         for (int i = 0; i < B_SLOTS; ++i) {
             const unsigned wo = live ? wbase[i] : OOB;
-            S.bh[i] = asm_buffer_load_b128(rs_wh, wo, koff);
-            S.bl[i] = asm_buffer_load_b128(rs_wl, wo, koff);
+            S.bh[i] = buffer_load_b128(rs_wh, wo, koff);
+            S.bl[i] = buffer_load_b128(rs_wl, wo, koff);
         }
         ++ld_step;
         if (++ld_tap == 9) { ld_tap = 0; ++ld_cc; }
@@ -222,8 +202,8 @@ void conv_band_f16s3_kernel(const ConvArgs a, const int grid_m, const int grid_n
 #pragma unroll
         for (int j = 0; j < BAND_SLOTS; ++j) {
             const unsigned vo = live ? bvo[j] : OOB;
-            BRh[j] = asm_buffer_load_b128(rs_a, vo, soff);
-            BRl[j] = asm_buffer_load_b128(rs_a, vo, lo_plane + soff);
+            BRh[j] = buffer_load_b128(rs_a, vo, soff);
+            BRl[j] = buffer_load_b128(rs_a, vo, lo_plane + soff);
         }
     };
     // vmcnt bookkeeping (in-order completion).  Steady-state issue pattern: [B set x][B set y] and, right after a
@@ -235,14 +215,14 @@ void conv_band_f16s3_kernel(const ConvArgs a, const int grid_m, const int grid_n
     // loads cost, 14-21 % of these kernels in the timing-only builds of tools/run_abl.sh, is throughput, not latency.)
     int band_age = 0;                                          // steps since the last band prefetch was issued
     auto wait_b = [&](BStage& S) {
-        if (band_age < 2) wait_vmcnt<B_LOADS + BAND_LOADS>(); else wait_vmcnt<B_LOADS>();
-        tie_regs(S.bh); tie_regs(S.bl);
+        if (band_age < 2) vmcnt<B_LOADS + BAND_LOADS>(); else vmcnt<B_LOADS>();
+        tie(S.bh); tie(S.bl);
         ++band_age;
         __builtin_amdgcn_sched_barrier(0);
     };
     auto wait_band = [&]() {                                   // everything issued so far except the two B sets
-        wait_vmcnt<2 * B_LOADS>();
-        tie_regs(BRh); tie_regs(BRl);
+        vmcnt<2 * B_LOADS>();
+        tie(BRh); tie(BRl);
         __builtin_amdgcn_sched_barrier(0);
     };
     const int wr_swz = (c16 ^ band_swz(row0)) << 4;            // RPP % 8 == 0: the same for every pass
@@ -403,8 +383,8 @@ void conv_band_f16s3_kernel(const ConvArgs a, const int grid_m, const int grid_n
         if (t + 1 < nsteps) step(1, S0);
     }
     // drain: the trailing loads' destination registers must stay allocated until they have landed (see conv_igemm_f16s3.hip)
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    tie_regs(S0.bh); tie_regs(S0.bl); tie_regs(S1.bh); tie_regs(S1.bl); tie_regs(BRh); tie_regs(BRl);
+    vmcnt<0>();
+    tie(S0.bh); tie(S0.bl); tie(S1.bh); tie(S1.bl); tie(BRh); tie(BRl);
     __builtin_amdgcn_sched_barrier(0);
     __syncthreads();
     RTOD_STAMP(6)                                              // 6: drain
@@ -454,17 +434,9 @@ static int launch_band(const ConvArgs& a, hipStream_t s) {
     const int lds = main_bytes > band_epi_bytes(BM, BN) ? main_bytes : band_epi_bytes(BM, BN);
     auto k_res = conv_band_f16s3_kernel<BM, BN, NWM, NWN, MINW, EPI_SPLIT_RES, KG>;
     auto k_plain = conv_band_f16s3_kernel<BM, BN, NWM, NWN, MINW, EPI_SPLIT, KG>;
-    static std::atomic<unsigned long long> attr_done{0};       // per instantiation, one bit per device; > 64 KiB of dynamic LDS needs the opt-in
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return hip_fail(hipGetLastError(), "conv_band_f16s3 hipGetDevice");
-    if (!((attr_done.load(std::memory_order_acquire) >> (dev & 63)) & 1ull)) {       // idempotent: a second thread may repeat the calls
-        const int cap = KG * (4 * BN * 64 + 2 * (band_rows(BM, BAND_MAX_W) + 1) * 64);
-        const int mx = cap > band_epi_bytes(BM, BN) ? cap : band_epi_bytes(BM, BN);
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_res), hipFuncAttributeMaxDynamicSharedMemorySize, mx) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void*>(k_plain), hipFuncAttributeMaxDynamicSharedMemorySize, mx) != hipSuccess)
-            return hip_fail(hipGetLastError(), "conv_band_f16s3 LDS attribute");
-        attr_done.fetch_or(1ull << (dev & 63), std::memory_order_release);
-    }
+    static std::atomic<unsigned long long> attr_done{0};
+    const int cap = KG * (4 * BN * 64 + 2 * (band_rows(BM, BAND_MAX_W) + 1) * 64);
+    if (int rc = lds_opt_in(attr_done, cap > band_epi_bytes(BM, BN) ? cap : band_epi_bytes(BM, BN), "conv_band_f16s3", k_res, k_plain)) return rc;
     if (a.res) hipLaunchKernelGGL(k_res, dim3(gm * gn), dim3(NWM * NWN * 64 * KG), lds, s, ax, gm, gn);
     else hipLaunchKernelGGL(k_plain, dim3(gm * gn), dim3(NWM * NWN * 64 * KG), lds, s, ax, gm, gn);
 #ifdef RTOD_TIMELINE
@@ -571,13 +543,11 @@ const ConvVariantInfo& conv_band_mode_info(int mode) {
 int launch_conv_band_f16s3(const ConvArgs& a_in, int mode, hipStream_t s) {
     if (mode >= BAND_LDS_MODES && mode < BAND_MODES) return launch_conv_bandd_f16s3(a_in, mode - BAND_LDS_MODES, s);
     ConvArgs a = a_in;
-    if (!a.in || !a.w_hi || !a.w_lo || !a.bias || !a.inv_scale || !a.out) { set_error("launch_conv_band: null pointer"); return RTOD_E_ARG; }
+    if (int rc = check_split_conv_args(a, "launch_conv_band", false)) return rc;
     if (!conv_band_supported(a.kh, a.stride, a.pad, a.Cin, a.Wi) || a.kw != 3 || a.Ho != a.Hi || a.Wo != a.Wi || a.dec.enabled) {
         set_error("launch_conv_band: unsupported shape (k=%d s=%d pad=%d Cin=%d W=%d)", a.kh, a.stride, a.pad, a.Cin, a.Wi); return RTOD_E_ARG;
     }
     if (a.in_ldc % 8 || a.in_coff % 8 || a.K != a.Kpad || a.K != 9 * a.Cin) { set_error("launch_conv_band: bad view / K"); return RTOD_E_ARG; }
-    if (a.in_bytes == 0 || a.in_bytes >= OOB || a.w_bytes == 0 || a.w_bytes >= OOB) { set_error("launch_conv_band: buffer extents"); return RTOD_E_ARG; }
-    if ((uint64_t)a.B * a.Hi * a.Wi * a.in_ldc * 4ull > (uint64_t)a.in_bytes) { set_error("launch_conv_band: input view exceeds its buffer"); return RTOD_E_ARG; }
 #ifdef RTOD_DIAG
     static const int dbg_zero = getenv("RTOD_DBG_ZERO") ? atoi(getenv("RTOD_DBG_ZERO")) : 0;   // diagnostic build only
     if (dbg_zero & 1) a.in_bytes = 1;

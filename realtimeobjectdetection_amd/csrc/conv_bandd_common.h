@@ -1,5 +1,5 @@
 // Pieces shared by the kernels that load their weight fragments straight from global memory (conv_bandd_f16s3.hip: 3x3 band;
-// conv_pwd_f16s3.hip: 1x1): counted vmcnt waits, the raw fragment load, register ties, and the epilogue in row passes.
+// conv_pwd_f16s3.hip: 1x1): the wait behind a wave-uniform number of band pieces, and the epilogue in row passes.
 #pragma once
 #include "conv_f16s3_common.h"
 
@@ -15,85 +15,17 @@ static __device__ unsigned long long g_bandd_epi[BD_EPI_BLOCKS * 5];
 #define BD_ESTAMP(slot)
 #endif
 
-// an N outside the list is a compile error (it used to emit no wait at all)
-template <int N> __device__ __forceinline__ void bandd_wait_vmcnt() {
-    static_assert(N >= 0 && N <= 63, "vmcnt literal");
-#define RTOD_VMCNT_CASE(n) else if constexpr (N == n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory");
-    if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    RTOD_VMCNT_CASE(2) RTOD_VMCNT_CASE(3) RTOD_VMCNT_CASE(4) RTOD_VMCNT_CASE(5) RTOD_VMCNT_CASE(6) RTOD_VMCNT_CASE(7) RTOD_VMCNT_CASE(8)
-    RTOD_VMCNT_CASE(9) RTOD_VMCNT_CASE(10) RTOD_VMCNT_CASE(12) RTOD_VMCNT_CASE(14) RTOD_VMCNT_CASE(16) RTOD_VMCNT_CASE(18)
-    else static_assert(N < 0, "add the vmcnt literal");
-#undef RTOD_VMCNT_CASE
-}
-
-// the same with a count that is a constant only after unrolling (a loop variable of a fully unrolled loop): the switch folds
-__device__ __forceinline__ void bandd_wait_vmcnt_folded(int n) {
-    switch (n) {
-#define RTOD_VMCNT_CASE(k) case k: asm volatile("s_waitcnt vmcnt(" #k ")" ::: "memory"); break;
-        RTOD_VMCNT_CASE(4) RTOD_VMCNT_CASE(5) RTOD_VMCNT_CASE(6) RTOD_VMCNT_CASE(8) RTOD_VMCNT_CASE(9) RTOD_VMCNT_CASE(10)
-#undef RTOD_VMCNT_CASE
-        default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;          // (never taken: stricter, still correct)
-    }
-}
-
 // wait for all but the NBASE + PER n youngest operations, n (0 ... 5) wave-uniform: the band pieces issued after the awaited B set
 // (PER: loads per band piece, 2 = hi + lo, 1 = hi only in plain-f16 instances)
 template <int NBASE, int PER = 2> __device__ __forceinline__ void bandd_wait_vmcnt_plus(int n) {
     static_assert(((NBASE == 4 || NBASE == 8) && PER == 2) || ((NBASE == 2 || NBASE == 4) && PER == 1), "two B sets of 1, 2 or 4 loads");
     asm volatile("" : "+s"(n));                                 // opaque: left visible, the loop-invariant n unswitches the whole chunk loop six ways
-    if (n == 0) bandd_wait_vmcnt<NBASE>();
-    else if (n == 1) bandd_wait_vmcnt<NBASE + PER>();
-    else if (n == 2) bandd_wait_vmcnt<NBASE + 2 * PER>();
-    else if (n == 3) bandd_wait_vmcnt<NBASE + 3 * PER>();
-    else if (n == 4) bandd_wait_vmcnt<NBASE + 4 * PER>();
-    else bandd_wait_vmcnt<NBASE + 5 * PER>();
-}
-
-// raw buffer load with an instruction offset (the 16-column tile of the strip: j KiB), hidden from the compiler's waitcnt pass
-template <int OFF> __device__ __forceinline__ u32x4 bandd_load_b(const __amdgpu_buffer_rsrc_t rsrc, unsigned voffset, unsigned soffset) {
-    u32x4 v;
-    asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen offset:%4" : "=v"(v) : "v"(voffset), "s"(rsrc), "s"(soffset), "n"(OFF) : "memory");
-    return v;
-}
-
-// hi and lo piece of one 16-row band block: lane l's 16 bytes land at lds + 16 l (M0 written in the statement that uses it)
-__device__ __forceinline__ void bandd_dma_pair(const __amdgpu_buffer_rsrc_t rsrc, unsigned voffset, unsigned soff_hi, unsigned soff_lo, unsigned lds_hi) {
-    unsigned keep;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %5\n\t"
-        "s_nop 0\n\t"
-        "buffer_load_dwordx4 %1, %2, %3 offen lds\n\t"
-        "s_add_u32 m0, %5, 0x400\n\t"
-        "s_nop 0\n\t"
-        "buffer_load_dwordx4 %1, %2, %4 offen lds\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(voffset), "s"(rsrc), "s"(soff_hi), "s"(soff_lo), "s"(lds_hi)
-        : "memory", "scc");
-}
-
-// hi piece alone (plain-f16 instances)
-__device__ __forceinline__ void bandd_dma_hi(const __amdgpu_buffer_rsrc_t rsrc, unsigned voffset, unsigned soff_hi, unsigned lds_hi) {
-    unsigned keep;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %4\n\t"
-        "s_nop 0\n\t"
-        "buffer_load_dwordx4 %1, %2, %3 offen lds\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(voffset), "s"(rsrc), "s"(soff_hi), "s"(lds_hi)
-        : "memory", "scc");
-}
-
-// F16: only the hi registers [j][0] are loaded (plain-f16 instances)
-template <int TN, bool F16 = false> __device__ __forceinline__ void bandd_tie(u32x4 (&q)[TN][2]) {
-    static_assert(TN >= 1 && TN <= 2, "strip width");
-    if constexpr (F16 && TN == 1) asm volatile("" : "+v"(q[0][0]) :: "memory");
-    else if constexpr (F16) asm volatile("" : "+v"(q[0][0]), "+v"(q[1][0]) :: "memory");
-    else if constexpr (TN == 1) asm volatile("" : "+v"(q[0][0]), "+v"(q[0][1]) :: "memory");
-    else asm volatile("" : "+v"(q[0][0]), "+v"(q[0][1]), "+v"(q[1][0]), "+v"(q[1][1]) :: "memory");
+    if (n == 0) vmcnt<NBASE>();
+    else if (n == 1) vmcnt<NBASE + PER>();
+    else if (n == 2) vmcnt<NBASE + 2 * PER>();
+    else if (n == 3) vmcnt<NBASE + 3 * PER>();
+    else if (n == 4) vmcnt<NBASE + 4 * PER>();
+    else vmcnt<NBASE + 5 * PER>();
 }
 
 // ---- epilogue: scale / bias / activation, LDS transpose in passes of RG rows, split-format store (+ residual).

@@ -36,7 +36,6 @@
 // Single-buffered band (76x76: three workgroups per CU leave 53 KB each): barrier, DMA, vmcnt(0), barrier at every chunk top;
 // the other two workgroups' waves on the SIMD cover the exposed load.
 #include "conv_bandd_common.h"
-#include <atomic>
 #include <cstdio>
 #include <cstdlib>
 #include <map>
@@ -101,10 +100,7 @@ void conv_bandd_f16s3_kernel(const ConvArgs a, const int grid_m, const int grid_
 
     const int nwg = grid_m * grid_n;
     int bid = blockIdx.x;
-    if (!a.xcd_by_n) {                                          // XCD x (= blockIdx % 8) takes a contiguous range of tiles
-        const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-    }
+    if (!a.xcd_by_n) bid = xcd_remap(bid, nwg);                 // XCD x (= blockIdx % 8) takes a contiguous range of tiles
     const int bm = bid / grid_n, bn = bid - bm * grid_n;
 
     const int tid = KG == 1 ? (int)threadIdx.x : (int)threadIdx.x - kg * NT;
@@ -130,9 +126,9 @@ void conv_bandd_f16s3_kernel(const ConvArgs a, const int grid_m, const int grid_
     // ---- band DMA: block = wave + k NW; lane -> row lane >> 2 of the block, position lane & 3 <- source chunk (lane & 3) ^ swizzle(row)
     // (per-block source offsets are recomputed at every chunk top from two registers: held in registers across the main loop they
     //  were the first thing the allocator spilled)
-    const __amdgpu_buffer_rsrc_t rs_a = __builtin_amdgcn_make_buffer_rsrc((void*)a.in, 0, a.in_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_wh = __builtin_amdgcn_make_buffer_rsrc((void*)a.w_hi, 0, a.w_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_wl = __builtin_amdgcn_make_buffer_rsrc((void*)a.w_lo, 0, a.w_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_a = buffer_rsrc(a.in, a.in_bytes);
+    const __amdgpu_buffer_rsrc_t rs_wh = buffer_rsrc(a.w_hi, a.w_bytes);
+    const __amdgpu_buffer_rsrc_t rs_wl = buffer_rsrc(a.w_lo, a.w_bytes);
     const unsigned lds0 = (unsigned)(size_t)smem;
     // Every wave issues the SAME number of pieces, n_dma = ceil(NBLK / NW) pairs (the counted waits of the steps behind a DMA
     // need it): a wave whose block index runs past the band writes zeros (out-of-range source) into the zero block instead.
@@ -154,8 +150,8 @@ void conv_bandd_f16s3_kernel(const ConvArgs a, const int grid_m, const int grid_
             const int q = m0 - W - 1 + r;
             const unsigned vo = (blk < blk_hi && r < NBv && (unsigned)q < (unsigned)M) ? (unsigned)q * PS + dma_cpart : OOB;
             const unsigned dst = base + (unsigned)(blk < blk_hi ? blk * 2048 : zero_off);
-            if constexpr (F16) { if (k < n) bandd_dma_hi(rs_a, vo, soff, dst); }
-            else if (k < n) bandd_dma_pair(rs_a, vo, soff, lo_plane + soff, dst);
+            if constexpr (F16) { if (k < n) lds_dma(rs_a, vo, soff, dst); }
+            else if (k < n) lds_dma_pair<0x400>(rs_a, vo, soff, lo_plane + soff, dst);     // hi and lo piece of one 16-row band block
         }
     };
     auto dma_band = [&](int cc, int buf) __attribute__((always_inline)) { dma_blocks(cc, buf, 0, NBLK, n_dma); };
@@ -170,11 +166,11 @@ void conv_bandd_f16s3_kernel(const ConvArgs a, const int grid_m, const int grid_
     auto load_b = [&](u32x4 (&q)[TN][2]) __attribute__((always_inline)) {
         const unsigned vo = ld_step < nsteps ? bvoff : OOB;
         const unsigned koff = (unsigned)((ld_cc * KG + kg) * 9 + ld_tap) * wchunk;
-        q[0][0] = bandd_load_b<0>(rs_wh, vo, koff);
-        if constexpr (!F16) q[0][1] = bandd_load_b<0>(rs_wl, vo, koff);
-        if constexpr (TN == 2) {
-            q[1][0] = bandd_load_b<1024>(rs_wh, vo, koff);
-            if constexpr (!F16) q[1][1] = bandd_load_b<1024>(rs_wl, vo, koff);
+        q[0][0] = buffer_load_b128(rs_wh, vo, koff);
+        if constexpr (!F16) q[0][1] = buffer_load_b128(rs_wl, vo, koff);
+        if constexpr (TN == 2) {                                // the strip's second 16-column tile: 1 KiB further (instruction offset)
+            q[1][0] = buffer_load_b128<1024>(rs_wh, vo, koff);
+            if constexpr (!F16) q[1][1] = buffer_load_b128<1024>(rs_wl, vo, koff);
         }
         ++ld_step;
         if (++ld_tap == 9) { ld_tap = 0; ++ld_cc; }
@@ -245,8 +241,8 @@ void conv_bandd_f16s3_kernel(const ConvArgs a, const int grid_m, const int grid_
     load_b(Bq[0]);
     load_b(Bq[1]);
     if constexpr (DB) {                                         // band(0) landed (the chunk tops of the double-buffered loop wait for nothing)
-        bandd_wait_vmcnt<0>();
-        bandd_tie<TN, F16>(Bq[0]); bandd_tie<TN, F16>(Bq[1]);
+        vmcnt<0>();
+        tie_bset<F16>(Bq[0]); tie_bset<F16>(Bq[1]);
         __builtin_amdgcn_sched_barrier(0);
     }
     __syncthreads();                                            // zero blocks written
@@ -275,8 +271,8 @@ void conv_bandd_f16s3_kernel(const ConvArgs a, const int grid_m, const int grid_
         // chunk waited for: landed.  Nothing is waited for here: the B sets of the next two steps stay in flight across the barrier.
         int dma_behind = 0;                                     // band pairs issued between B(s + 1) and B(s + 2) of the current phase's first step
         if constexpr (!DB) {
-            bandd_wait_vmcnt<0>();
-            bandd_tie<TN, F16>(Bq[0]); bandd_tie<TN, F16>(Bq[1]);
+            vmcnt<0>();
+            tie_bset<F16>(Bq[0]); tie_bset<F16>(Bq[1]);
         }
         __builtin_amdgcn_sched_barrier(0);
         __builtin_amdgcn_s_barrier();
@@ -291,9 +287,9 @@ void conv_bandd_f16s3_kernel(const ConvArgs a, const int grid_m, const int grid_
             if (i == 0) {                                       // step head: B set of step t + 2, wait for this step's
                 load_b(Bq[(t + 2) % 3]);
                 if constexpr (DB) {                             // younger than this step's set: the next two sets and, for t < 2, the band pieces
-                    if (t >= 2) bandd_wait_vmcnt<2 * NB>(); else bandd_wait_vmcnt_plus<2 * NB, PER>(dma_behind);
-                    bandd_tie<TN, F16>(Bq[t % 3]);
-                } else if (t >= 2) { bandd_wait_vmcnt<2 * NB>(); bandd_tie<TN, F16>(Bq[t % 3]); }
+                    if (t >= 2) vmcnt<2 * NB>(); else bandd_wait_vmcnt_plus<2 * NB, PER>(dma_behind);
+                    tie_bset<F16>(Bq[t % 3]);
+                } else if (t >= 2) { vmcnt<2 * NB>(); tie_bset<F16>(Bq[t % 3]); }
                 __builtin_amdgcn_sched_barrier(0);
             }
             if (u + 2 < UNITS) read_unit((u + 2) / TM, (u + 2) % TM, bufoff, Ah[(u + 2) % 3], Al[(u + 2) % 3]);
@@ -312,8 +308,8 @@ void conv_bandd_f16s3_kernel(const ConvArgs a, const int grid_m, const int grid_
         BD_STAMP(2)
     }
     // drain: the two trailing (out-of-range) B sets' registers stay allocated until they have landed
-    bandd_wait_vmcnt<0>();
-    bandd_tie<TN, F16>(Bq[0]); bandd_tie<TN, F16>(Bq[1]); bandd_tie<TN, F16>(Bq[2]);
+    vmcnt<0>();
+    tie_bset<F16>(Bq[0]); tie_bset<F16>(Bq[1]); tie_bset<F16>(Bq[2]);
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_setprio(0);
     BD_STAMP(3)
@@ -347,17 +343,10 @@ static int launch_bandd(const ConvArgs& a, hipStream_t s) {
     const int fe = a.f16 ? EPI_F16 : 0;
     auto k_res = fe ? conv_bandd_f16s3_kernel<BM, BN, NWM, NWN, MINW, EPI_SPLIT_RES | EPI_F16, BUFM, KG, MAXW> : conv_bandd_f16s3_kernel<BM, BN, NWM, NWN, MINW, EPI_SPLIT_RES, BUFM, KG, MAXW>;
     auto k_plain = fe ? conv_bandd_f16s3_kernel<BM, BN, NWM, NWN, MINW, EPI_SPLIT | EPI_F16, BUFM, KG, MAXW> : conv_bandd_f16s3_kernel<BM, BN, NWM, NWN, MINW, EPI_SPLIT, BUFM, KG, MAXW>;
-    static std::atomic<unsigned long long> attr_done[2] = {{0}, {0}};   // per instantiation (f16s3, f16), one bit per device; > 64 KiB of dynamic LDS needs the opt-in
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return hip_fail(hipGetLastError(), "conv_bandd_f16s3 hipGetDevice");
-    if (!((attr_done[fe ? 1 : 0].load(std::memory_order_acquire) >> (dev & 63)) & 1ull)) {
-        const int cap = KG * (DB ? 2 : 1) * (bandd_rows(BM, MAXW) / 16 + 1) * 2048;
-        const int mx = std::min(cap > epi_bytes ? cap : epi_bytes, 160 * 1024);    // (a launch that needs more is refused above)
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_res), hipFuncAttributeMaxDynamicSharedMemorySize, mx) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void*>(k_plain), hipFuncAttributeMaxDynamicSharedMemorySize, mx) != hipSuccess)
-            return hip_fail(hipGetLastError(), "conv_bandd_f16s3 LDS attribute");
-        attr_done[fe ? 1 : 0].fetch_or(1ull << (dev & 63), std::memory_order_release);
-    }
+    static std::atomic<unsigned long long> attr_done[2] = {{0}, {0}};   // per instantiation: f16s3, f16
+    const int cap = KG * (DB ? 2 : 1) * (bandd_rows(BM, MAXW) / 16 + 1) * 2048;
+    const int mx = std::min(cap > epi_bytes ? cap : epi_bytes, 160 * 1024);        // (a launch that needs more is refused above)
+    if (int rc = lds_opt_in(attr_done[fe ? 1 : 0], mx, "conv_bandd_f16s3", k_res, k_plain)) return rc;
     if (a.res) hipLaunchKernelGGL(k_res, dim3(gm * gn), dim3(NT), lds, s, ax, gm, gn);
     else hipLaunchKernelGGL(k_plain, dim3(gm * gn), dim3(NT), lds, s, ax, gm, gn);
 #ifdef RTOD_TIMELINE
@@ -446,13 +435,11 @@ int conv_bandd_kernel_name(int idx, int epi, char* buf, size_t len) {
 }
 
 int launch_conv_bandd_f16s3(const ConvArgs& a, int idx, hipStream_t s) {
-    if (!a.in || !a.w_hi || (!a.w_lo && !a.f16) || !a.bias || !a.inv_scale || !a.out) { set_error("launch_conv_bandd: null pointer"); return RTOD_E_ARG; }
+    if (int rc = check_split_conv_args(a, "launch_conv_bandd", true)) return rc;
     if (a.kh != 3 || a.stride != 1 || a.pad != 1 || a.Cin % 32 || a.Wi > BANDD_WIDE_W || a.kw != 3 || a.Ho != a.Hi || a.Wo != a.Wi || a.dec.enabled || a.pw_wh) {
         set_error("launch_conv_bandd: unsupported shape (k=%d s=%d pad=%d Cin=%d W=%d)", a.kh, a.stride, a.pad, a.Cin, a.Wi); return RTOD_E_ARG;
     }
     if (a.in_ldc % 8 || a.in_coff % 8 || a.K != a.Kpad || a.K != 9 * a.Cin || a.Npad % 128) { set_error("launch_conv_bandd: bad view / K"); return RTOD_E_ARG; }
-    if (a.in_bytes == 0 || a.in_bytes >= OOB || a.w_bytes == 0 || a.w_bytes >= OOB) { set_error("launch_conv_bandd: buffer extents"); return RTOD_E_ARG; }
-    if ((uint64_t)a.B * a.Hi * a.Wi * a.in_ldc * 4ull > (uint64_t)a.in_bytes) { set_error("launch_conv_bandd: input view exceeds its buffer"); return RTOD_E_ARG; }
     switch (idx) {
 #define RTOD_X_CASE(i, bm, bn, nwm, nwn, minw, db, kg, maxw, sfx) case i: if (a.Wi > maxw) break; return launch_bandd<bm, bn, nwm, nwn, minw, db, kg, maxw>(a, s);
         RTOD_BANDD_TILES(RTOD_X_CASE)

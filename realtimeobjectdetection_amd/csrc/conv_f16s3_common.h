@@ -1,4 +1,6 @@
-// Shared pieces of the split-precision f16 convolution kernels (conv_igemm_f16s3.hip, conv_band_f16s3.hip).
+// Shared pieces of the split-precision f16 convolution kernels (conv_igemm_f16s3, conv_band_f16s3, conv_bandd_f16s3, conv_pwd_f16s3,
+// conv_ring_f16s3, conv_patch_f16s3, conv_stem2_f16s3): the inline-asm memory primitives, the launchers' common argument checks,
+// the epilogues.
 #pragma once
 #include "rtod_internal.h"
 #include <type_traits>
@@ -11,6 +13,120 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int HBK = 32;                  // K elements per LDS stage (64 bytes per panel row)
 constexpr unsigned OOB = 0x80000000u;    // voffset beyond any buffer (< 2 GiB enforced on the host)
+
+// ---- Memory primitives of the main loops.  Their loads are issued through inline asm, so hipcc's s_waitcnt insertion does not
+// see them: the loops keep loads in flight across barriers and retire them with hand-counted waits (cdna guide 5.7).  Why they
+// are written exactly this way: DESIGN.md section 4, "Two GPU memory-access faults of round 2".
+
+// Wait until at most N of this wave's vector-memory operations are outstanding (loads, stores and LDS-DMA count together and
+// retire in issue order).
+template <int N> __device__ __forceinline__ void vmcnt() {
+    static_assert(0 <= N && N <= 63, "vmcnt range");
+    asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory");
+}
+
+// 16-byte raw buffer load, OFF = instruction offset in bytes.  Its destination may be used only after the counted wait that
+// retires it and a tie (below) that names it.
+template <int OFF = 0> __device__ __forceinline__ u32x4 buffer_load_b128(const __amdgpu_buffer_rsrc_t rsrc, unsigned voffset, unsigned soffset) {
+    u32x4 v;
+    asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen offset:%4" : "=v"(v) : "v"(voffset), "s"(rsrc), "s"(soffset), "n"(OFF) : "memory");
+    return v;
+}
+
+// Register ties.  To the compiler an asm load writes its destination when the statement ends: once the last read is
+// scheduled, the register is dead and may be reused (or register-only code hoisted above a wait: "memory" orders memory
+// operations only) while the load is still in flight — a late load then overwrites a live value (fault 1).
+// Rule: after the wait that retires a load, one empty statement names every register that load may still write as in/out.
+// The registers then stay allocated until the data has landed, and no use is scheduled above the wait.
+template <typename T> __device__ __forceinline__ void tie(T& a) { asm volatile("" : "+v"(a) :: "memory"); }
+template <typename T> __device__ __forceinline__ void tie(T& a, T& b) { asm volatile("" : "+v"(a), "+v"(b) :: "memory"); }
+template <typename T> __device__ __forceinline__ void tie(T& a, T& b, T& c) { asm volatile("" : "+v"(a), "+v"(b), "+v"(c) :: "memory"); }
+template <typename T> __device__ __forceinline__ void tie(T& a, T& b, T& c, T& d) {
+    asm volatile("" : "+v"(a), "+v"(b), "+v"(c), "+v"(d) :: "memory");
+}
+template <typename T> __device__ __forceinline__ void tie(T& a, T& b, T& c, T& d, T& e) {
+    asm volatile("" : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(e) :: "memory");
+}
+// every element of a register array, in one statement
+template <typename T, int N> __device__ __forceinline__ void tie(T (&r)[N]) {
+    static_assert(N >= 1 && N <= 5, "tie: 1 to 5 registers");
+    if constexpr (N == 1) tie(r[0]);
+    else if constexpr (N == 2) tie(r[0], r[1]);
+    else if constexpr (N == 3) tie(r[0], r[1], r[2]);
+    else if constexpr (N == 4) tie(r[0], r[1], r[2], r[3]);
+    else tie(r[0], r[1], r[2], r[3], r[4]);
+}
+// a B set of the strip kernels (conv_bandd_common.h): [strip tile][hi, lo]; plain-f16 instances load the hi registers only
+template <bool F16, int TN> __device__ __forceinline__ void tie_bset(u32x4 (&q)[TN][2]) {
+    static_assert(TN >= 1 && TN <= 2, "strip width");
+    if constexpr (F16 && TN == 1) tie(q[0][0]);
+    else if constexpr (F16) tie(q[0][0], q[1][0]);
+    else if constexpr (TN == 1) tie(q[0][0], q[0][1]);
+    else tie(q[0][0], q[0][1], q[1][0], q[1][1]);
+}
+
+// LDS-DMA: `buffer_load_dwordx4 ... offen lds` writes lane l's 16 bytes at LDS byte address M0 + 16 l (a voffset past the
+// descriptor's extent writes zeros).  The compiler neither tracks nor preserves M0 around asm, so M0 is saved, written in the
+// statement that uses it, and restored; s_nop 0 separates the SALU write of M0 from the DMA that reads it.
+// Two pieces with their own descriptors and LDS addresses (the hi and lo plane of the same rows).
+__device__ __forceinline__ void lds_dma_pair(const __amdgpu_buffer_rsrc_t rsrc_hi, const __amdgpu_buffer_rsrc_t rsrc_lo, unsigned voffset,
+                                             unsigned soff_hi, unsigned soff_lo, unsigned lds_hi, unsigned lds_lo) {
+    unsigned keep;
+    asm volatile(
+        "s_mov_b32 %0, m0\n\t"
+        "s_mov_b32 m0, %6\n\t"
+        "s_nop 0\n\t"
+        "buffer_load_dwordx4 %1, %2, %4 offen lds\n\t"
+        "s_mov_b32 m0, %7\n\t"
+        "s_nop 0\n\t"
+        "buffer_load_dwordx4 %1, %3, %5 offen lds\n\t"
+        "s_mov_b32 m0, %0"
+        : "=&s"(keep)
+        : "v"(voffset), "s"(rsrc_hi), "s"(rsrc_lo), "s"(soff_hi), "s"(soff_lo), "s"(lds_hi), "s"(lds_lo)
+        : "memory");
+}
+// Two pieces from one descriptor, the lo piece LO_STEP bytes behind the hi piece in LDS.
+template <int LO_STEP>
+__device__ __forceinline__ void lds_dma_pair(const __amdgpu_buffer_rsrc_t rsrc, unsigned voffset, unsigned soff_hi, unsigned soff_lo, unsigned lds_hi) {
+    unsigned keep;
+    asm volatile(
+        "s_mov_b32 %0, m0\n\t"
+        "s_mov_b32 m0, %5\n\t"
+        "s_nop 0\n\t"
+        "buffer_load_dwordx4 %1, %2, %3 offen lds\n\t"
+        "s_add_u32 m0, %5, %6\n\t"
+        "s_nop 0\n\t"
+        "buffer_load_dwordx4 %1, %2, %4 offen lds\n\t"
+        "s_mov_b32 m0, %0"
+        : "=&s"(keep)
+        : "v"(voffset), "s"(rsrc), "s"(soff_hi), "s"(soff_lo), "s"(lds_hi), "n"(LO_STEP)
+        : "memory", "scc");
+}
+// One piece (the hi plane alone: plain-f16 instances).
+__device__ __forceinline__ void lds_dma(const __amdgpu_buffer_rsrc_t rsrc, unsigned voffset, unsigned soff, unsigned lds) {
+    unsigned keep;
+    asm volatile(
+        "s_mov_b32 %0, m0\n\t"
+        "s_mov_b32 m0, %4\n\t"
+        "s_nop 0\n\t"
+        "buffer_load_dwordx4 %1, %2, %3 offen lds\n\t"
+        "s_mov_b32 m0, %0"
+        : "=&s"(keep)
+        : "v"(voffset), "s"(rsrc), "s"(soff), "s"(lds)
+        : "memory", "scc");
+}
+
+// ---- Host: the argument checks every split launcher shares; `who` (the launcher's name) starts every error text.  The operands are
+// present (a plain-f16 launch may omit the lo weight plane where `f16_ok`: the families with f16 instances), both buffers are
+// non-empty and below OOB (so that a voffset of OOB is out of range), and the input view lies inside its buffer.
+inline int check_split_conv_args(const ConvArgs& a, const char* who, bool f16_ok) {
+    if (!a.in || !a.w_hi || (!a.w_lo && !(f16_ok && a.f16)) || !a.bias || !a.inv_scale || !a.out) { set_error("%s: null pointer", who); return RTOD_E_ARG; }
+    if (a.in_bytes == 0 || a.in_bytes >= OOB || a.w_bytes == 0 || a.w_bytes >= OOB) {
+        set_error("%s: buffer of %u / %u bytes outside (0, 2 GiB)", who, a.in_bytes, a.w_bytes); return RTOD_E_ARG;
+    }
+    if ((uint64_t)a.B * a.Hi * a.Wi * a.in_ldc * 4ull > (uint64_t)a.in_bytes) { set_error("%s: input view exceeds its buffer", who); return RTOD_E_ARG; }
+    return RTOD_OK;
+}
 
 enum { EPI_SPLIT = 0, EPI_SPLIT_RES = 1, EPI_DECODE = 2, EPI_SPLIT_PW = 3, EPI_SPLIT_RES_PW = 4 };
 // Plain-f16 instances (precision mode 2, "f16"): EPI | EPI_F16 as the kernels' EPI template argument.  The main loop drops the lo
@@ -35,16 +151,6 @@ __device__ __forceinline__ float h_decode(const DecodeArgs& d, float v, int n, i
     if (d.train) return v;
     const float anc = (c == 2) ? d.aw[a] : d.ah[a];
     return (expf(v) * anc) * d.stride;
-}
-
-// Raw buffer load issued through inline asm so that hipcc's s_waitcnt insertion does not see it: the
-// main loop keeps two K-chunks of loads in flight across barriers and waits with hand-counted
-// vmcnt(N) (cdna guide 5.7: loads hidden from the compiler need their own counted wait, and every
-// destination must be named by the wait statement before its first use).
-__device__ __forceinline__ u32x4 asm_buffer_load_b128(const __amdgpu_buffer_rsrc_t rsrc, unsigned voffset, unsigned soffset) {
-    u32x4 v;
-    asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen" : "=v"(v) : "v"(voffset), "s"(rsrc), "s"(soffset) : "memory");
-    return v;
 }
 
 // 16-byte activation store, sc1 (write-through): a layer's output is read by the NEXT kernel, on all XCDs, so it has

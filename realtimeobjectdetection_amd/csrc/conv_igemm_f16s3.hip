@@ -73,10 +73,7 @@ void conv_igemm_f16s3_kernel(const ConvArgs a, const int grid_m, const int grid_
 
     const int nwg = grid_m * grid_n;
     int bid = blockIdx.x;
-    {   // XCD-aware remap (bijective): blocks sharing an A row-panel run on one XCD / L2
-        const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-    }
+    bid = xcd_remap(bid, nwg);                                   // blocks sharing an A row-panel run on one XCD / L2
     const int bm = bid / grid_n, bn = bid - bm * grid_n;
 
     const int tid = threadIdx.x;
@@ -109,9 +106,9 @@ void conv_igemm_f16s3_kernel(const ConvArgs a, const int grid_m, const int grid_
         wbase[i] = (row0 + i * RPP < BN) ? (unsigned)((bn * BN + row0 + i * RPP) * 32 + c16 * 8) * 2u : OOB;
     const unsigned wchunk = (unsigned)a.Npad * (HBK * 2);        // bytes of one K-chunk panel of a weight plane
 
-    const __amdgpu_buffer_rsrc_t rs_a = __builtin_amdgcn_make_buffer_rsrc((void*)a.in, 0, a.in_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_wh = __builtin_amdgcn_make_buffer_rsrc((void*)a.w_hi, 0, a.w_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_wl = __builtin_amdgcn_make_buffer_rsrc((void*)a.w_lo, 0, a.w_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_a = buffer_rsrc(a.in, a.in_bytes);
+    const __amdgpu_buffer_rsrc_t rs_wh = buffer_rsrc(a.w_hi, a.w_bytes);
+    const __amdgpu_buffer_rsrc_t rs_wl = buffer_rsrc(a.w_lo, a.w_bytes);
 
     // wave-uniform K-chunk cursor: tap (ky,kx) and first channel c0 of the chunk to be LOADED next
     int ld_kc = 0, ld_c0 = 0, ld_ky = 0, ld_kx = 0;
@@ -127,15 +124,15 @@ void conv_igemm_f16s3_kernel(const ConvArgs a, const int grid_m, const int grid_
         for (int i = 0; i < A_SLOTS; ++i) {
             const bool ok = live && (unsigned)(iy0[i] + ld_ky) < (unsigned)a.Hi && (unsigned)(ix0[i] + ld_kx) < (unsigned)a.Wi;
             const unsigned vo = ok ? pbase[i] + tap_off : OOB;
-            S.ah[i] = asm_buffer_load_b128(rs_a, vo, 0u);
-            if constexpr (!F16) S.al[i] = asm_buffer_load_b128(rs_a, vo, lo_plane);
+            S.ah[i] = buffer_load_b128(rs_a, vo, 0u);
+            if constexpr (!F16) S.al[i] = buffer_load_b128(rs_a, vo, lo_plane);
         }
         const unsigned koff = (unsigned)ld_kc * wchunk;
 #pragma unroll
         for (int i = 0; i < B_SLOTS; ++i) {
             const unsigned wo = live ? wbase[i] : OOB;
-            S.bh[i] = asm_buffer_load_b128(rs_wh, wo, koff);
-            if constexpr (!F16) S.bl[i] = asm_buffer_load_b128(rs_wl, wo, koff);
+            S.bh[i] = buffer_load_b128(rs_wh, wo, koff);
+            if constexpr (!F16) S.bl[i] = buffer_load_b128(rs_wl, wo, koff);
         }
         // advance the cursor (scalar).  K order = (32-channel chunk outer, tap inner), the same order as the
         // band kernel and the packed weights, so every tile variant / kernel sums each output identically
@@ -283,7 +280,7 @@ void conv_igemm_f16s3_kernel(const ConvArgs a, const int grid_m, const int grid_
     // orders memory operations only) may be allocated into them — a load landing afterwards then zeroes a live pointer
     // (observed: 'Memory access fault on address (nil)' once the epilogue's code changed).  wait_stage names every
     // register of a set as in/out, so both sets stay allocated until the loads have landed.
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    vmcnt<0>();
     wait_stage(S0);
     wait_stage(S1);
     RTOD_GSTAMP(5)                                    // 5: drain
@@ -373,7 +370,7 @@ static int launch_h(const ConvArgs& a, hipStream_t s) {
 
 int launch_conv_f16s3(const ConvArgs& a_in, int variant, hipStream_t s) {
     ConvArgs a = a_in;
-    if (!a.in || !a.w_hi || (!a.w_lo && !a.f16) || !a.bias || !a.inv_scale || !a.out) { set_error("launch_conv_f16s3: null pointer"); return RTOD_E_ARG; }
+    if (int rc = check_split_conv_args(a, "launch_conv_f16s3", true)) return rc;
     if (a.Cin % HBK || a.in_ldc % 8 || a.in_coff % 8 || a.Kpad % HBK || a.K != a.Kpad || a.K != a.kh * a.kw * a.Cin) {
         set_error("launch_conv_f16s3: needs Cin %% 32 == 0 and 8-channel aligned views (Cin=%d ldc=%ld coff=%d K=%d Kpad=%d)", a.Cin, (long)a.in_ldc, a.in_coff, a.K, a.Kpad);
         return RTOD_E_ARG;
@@ -384,10 +381,6 @@ int launch_conv_f16s3(const ConvArgs& a_in, int variant, hipStream_t s) {
                     (a.pw_cout != 16 && a.pw_cout != 32 && a.pw_cout != 64) || a.pw_out_ldc % 8 || a.pw_out_coff % 8)) {
         set_error("launch_conv_f16s3: bad fused pointwise conv (k=%d cout=%d, conv Cout=%d)", a.pw_k, a.pw_cout, a.Cout); return RTOD_E_ARG;
     }
-    if (a.in_bytes == 0 || a.in_bytes >= OOB || a.w_bytes == 0 || a.w_bytes >= OOB) {
-        set_error("launch_conv_f16s3: buffer of %u / %u bytes outside (0, 2 GiB)", a.in_bytes, a.w_bytes); return RTOD_E_ARG;
-    }
-    if ((uint64_t)a.B * a.Hi * a.Wi * a.in_ldc * 4ull > (uint64_t)a.in_bytes) { set_error("launch_conv_f16s3: input view exceeds its buffer"); return RTOD_E_ARG; }
 #ifdef RTOD_DIAG
     // diagnostic build only: timing experiments (cdna guide 7: zero-record descriptors drop the loads of one operand, results are garbage)
     static const int dbg_zero = getenv("RTOD_DBG_ZERO") ? atoi(getenv("RTOD_DBG_ZERO")) : 0;

@@ -105,10 +105,7 @@ void conv_igemm_f32_kernel(const ConvArgs a, const int grid_m, const int grid_n)
     int bid = blockIdx.x;
     int slice = 0;
     if constexpr (MODE == 2) { slice = bid / nwg; bid -= slice * nwg; }
-    {
-        const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-    }
+    bid = xcd_remap(bid, nwg);
     const int bm = bid / grid_n, bn = bid - bm * grid_n;
 
     const int tid = threadIdx.x;

@@ -14,39 +14,9 @@
 // tile boundaries (conv_ring_f16s3.hip's scheme), the epilogue works straight from the accumulators (transposed product,
 // conv_f16s3_common.h) with no barrier, so tile t+1's loads and first steps overlap tile t's stores.
 #include "conv_f16s3_common.h"
-#include <atomic>
 #include <cstdio>
 
 namespace rtod {
-
-template <int N> __device__ __forceinline__ void patch_wait_vmcnt() {
-    static_assert(N >= 0 && N <= 20, "vmcnt literal");
-#define RTOD_VMCNT_CASE(n) else if constexpr (N == n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory");
-    if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    RTOD_VMCNT_CASE(1) RTOD_VMCNT_CASE(2) RTOD_VMCNT_CASE(3) RTOD_VMCNT_CASE(4) RTOD_VMCNT_CASE(5) RTOD_VMCNT_CASE(6)
-    RTOD_VMCNT_CASE(7) RTOD_VMCNT_CASE(8) RTOD_VMCNT_CASE(9) RTOD_VMCNT_CASE(10) RTOD_VMCNT_CASE(11) RTOD_VMCNT_CASE(12)
-    RTOD_VMCNT_CASE(13) RTOD_VMCNT_CASE(14) RTOD_VMCNT_CASE(15) RTOD_VMCNT_CASE(16) RTOD_VMCNT_CASE(17) RTOD_VMCNT_CASE(18)
-    RTOD_VMCNT_CASE(19) RTOD_VMCNT_CASE(20)
-#undef RTOD_VMCNT_CASE
-}
-
-// two LDS-DMA pieces with one per-lane source offset (conv_ring_f16s3.hip: dma_pair)
-__device__ __forceinline__ void patch_dma_pair(const __amdgpu_buffer_rsrc_t rsrc_hi, const __amdgpu_buffer_rsrc_t rsrc_lo, unsigned voffset,
-                                               unsigned soff_hi, unsigned soff_lo, unsigned lds_hi, unsigned lds_lo) {
-    unsigned keep;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %6\n\t"
-        "s_nop 0\n\t"
-        "buffer_load_dwordx4 %1, %2, %4 offen lds\n\t"
-        "s_mov_b32 m0, %7\n\t"
-        "s_nop 0\n\t"
-        "buffer_load_dwordx4 %1, %3, %5 offen lds\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(voffset), "s"(rsrc_hi), "s"(rsrc_lo), "s"(soff_hi), "s"(soff_lo), "s"(lds_hi), "s"(lds_lo)
-        : "memory");
-}
 
 constexpr int PT_TH = 8, PT_TW = 16, PT_BM = PT_TH * PT_TW;            // output tile: 8 rows x 16 columns
 constexpr int PT_PR = PT_TH + 2, PT_PC = PT_TW + 2, PT_PE = PT_PR * PT_PC;   // stride-1 patch: 10 x 18 = 180 input pixels
@@ -76,15 +46,14 @@ void conv_patch_f16s3_kernel(const ConvArgs a, const int tiles_x, const int tile
     const unsigned PS = (unsigned)a.in_ldc * 4u, lo_plane = (unsigned)a.in_ldc * 2u;
     const int ncc = a.Cin / 32;
     const unsigned wchunk = (unsigned)a.Npad * (HBK * 2);
-    const __amdgpu_buffer_rsrc_t rs_a = __builtin_amdgcn_make_buffer_rsrc((void*)a.in, 0, a.in_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_wh = __builtin_amdgcn_make_buffer_rsrc((void*)a.w_hi, 0, a.w_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_wl = __builtin_amdgcn_make_buffer_rsrc((void*)a.w_lo, 0, a.w_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_a = buffer_rsrc(a.in, a.in_bytes);
+    const __amdgpu_buffer_rsrc_t rs_wh = buffer_rsrc(a.w_hi, a.w_bytes);
+    const __amdgpu_buffer_rsrc_t rs_wl = buffer_rsrc(a.w_lo, a.w_bytes);
     const unsigned lds0 = (unsigned)(size_t)smem;
 
     // tile index -> (image, tile row, tile column, channel tile); XCD-aware remap as in conv_ring_f16s3.hip
     auto tile_of = [&](int t, int& b, int& y0, int& x0, int& bn) __attribute__((always_inline)) {
-        const int q = n_tiles >> 3, r = n_tiles & 7, xcd = t & 7;
-        int u = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (t >> 3);
+        int u = xcd_remap(t, n_tiles);
         bn = u % grid_n; u /= grid_n;
         x0 = (u % tiles_x) * PT_TW; u /= tiles_x;
         y0 = (u % tiles_y) * PT_TH; b = u / tiles_y;
@@ -127,7 +96,7 @@ void conv_patch_f16s3_kernel(const ConvArgs a, const int tiles_x, const int tile
 #pragma unroll
         for (int j = 0; j < B_PER; ++j) {
             const unsigned l = sbase + (unsigned)blk_b[j] * 1024u;
-            patch_dma_pair(rs_wh, rs_wl, wrow[j], koff, koff, l, l + PANEL_B);
+            lds_dma_pair(rs_wh, rs_wl, wrow[j], koff, koff, l, l + PANEL_B);
         }
         if (++ld_tap == 9) { ld_tap = 0; if (++ld_cc == ncc) { ld_tile += gridDim.x; wload_enter_tile(); } }
     };
@@ -142,7 +111,7 @@ void conv_patch_f16s3_kernel(const ConvArgs a, const int tiles_x, const int tile
             const bool ok = pt < n_tiles && (unsigned)iy < (unsigned)a.Hi && (unsigned)ix < (unsigned)a.Wi;
             const unsigned vo = ok ? (unsigned)((b * a.Hi + iy) * a.Wi + ix) * PS + (unsigned)a.in_coff * 2u + pchunk[j] : OOB;
             const unsigned l = lds0 + (unsigned)pbuf * PATCH + (unsigned)pc_piece[j] * 1024u;
-            patch_dma_pair(rs_a, rs_a, vo, soff, soff + lo_plane, l, l + PT_PLANE);
+            lds_dma_pair(rs_a, rs_a, vo, soff, soff + lo_plane, l, l + PT_PLANE);
         }
     };
 
@@ -178,8 +147,8 @@ void conv_patch_f16s3_kernel(const ConvArgs a, const int tiles_x, const int tile
             for (int tap = 0; tap < 9; ++tap) {
                 // this wave's pieces of the current weight stage (and, being older, of the current patch) have landed; younger:
                 // STAGES-2 weight stages and, for the STAGES-1 steps after a patch prefetch was issued, that patch
-                if (tap >= 1 && tap <= STAGES - 1) patch_wait_vmcnt<(STAGES - 2) * LB + LP>();
-                else patch_wait_vmcnt<(STAGES - 2) * LB>();
+                if (tap >= 1 && tap <= STAGES - 1) vmcnt<(STAGES - 2) * LB + LP>();
+                else vmcnt<(STAGES - 2) * LB>();
                 __builtin_amdgcn_s_barrier();                    // ... and everybody's; the previous step's slot / the other patch buffer are free
                 wload_issue(slot == 0 ? STAGES - 1 : slot - 1);  // the weight stage STAGES-1 steps ahead
                 if (tap == 0) {                                  // next chunk's patch (of the next tile after the last chunk) into the other buffer
@@ -223,7 +192,7 @@ void conv_patch_f16s3_kernel(const ConvArgs a, const int tiles_x, const int tile
         }
         conv_f16s3_epilogue_regs<WM, WN, EPI == EPI_SPLIT_RES>(a, acc, nullptr, mrow, bn * BN + wn * WN, tid, lh);
     }
-    patch_wait_vmcnt<0>();                                       // trailing (out-of-range) pieces: nothing may be in flight at exit
+    vmcnt<0>();                                                  // trailing (out-of-range) pieces: nothing may be in flight at exit
 }
 
 // ---- Weights-resident variant (mode PATCH_WRES_MODE): Cin = 32, Cout = 64 (YOLOv3's layer 3, 304x304 at 608x608).
@@ -247,12 +216,11 @@ void conv_patch_wres_f16s3_kernel(const ConvArgs a, const int tiles_x, const int
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
     const int n_tiles = a.B * tiles_y * tiles_x;
     const unsigned PS = (unsigned)a.in_ldc * 4u, lo_plane = (unsigned)a.in_ldc * 2u;
-    const __amdgpu_buffer_rsrc_t rs_a = __builtin_amdgcn_make_buffer_rsrc((void*)a.in, 0, a.in_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_a = buffer_rsrc(a.in, a.in_bytes);
     const unsigned lds0 = (unsigned)(size_t)smem;
 
     auto tile_of = [&](int t, int& b, int& y0, int& x0) __attribute__((always_inline)) {
-        const int q = n_tiles >> 3, r = n_tiles & 7, xcd = t & 7;
-        int u = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (t >> 3);
+        int u = xcd_remap(t, n_tiles);
         x0 = (u % tiles_x) * PT_TW; u /= tiles_x;
         y0 = (u % tiles_y) * PT_TH; b = u / tiles_y;
     };
@@ -260,8 +228,8 @@ void conv_patch_wres_f16s3_kernel(const ConvArgs a, const int tiles_x, const int
     // ---- once: the nine taps' weights -> LDS (rows in the transposed product's channel order, chunk swizzle on the source side)
     const int lrow = lane >> 2;
     {
-        const __amdgpu_buffer_rsrc_t rs_wh = __builtin_amdgcn_make_buffer_rsrc((void*)a.w_hi, 0, a.w_bytes, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rs_wl = __builtin_amdgcn_make_buffer_rsrc((void*)a.w_lo, 0, a.w_bytes, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rs_wh = buffer_rsrc(a.w_hi, a.w_bytes);
+        const __amdgpu_buffer_rsrc_t rs_wl = buffer_rsrc(a.w_lo, a.w_bytes);
         for (int p = wave; p < 9 * 4; p += NW) {                         // (tap, 16-row block): one hi + one lo piece each
             const int tap = p >> 2, rb = p & 3;
             const int rho = rb * 16 + lrow;
@@ -269,7 +237,7 @@ void conv_patch_wres_f16s3_kernel(const ConvArgs a, const int tiles_x, const int
             const unsigned vo = (unsigned)(tr_chan_of_row(rho) * 32 + ch * 8) * 2u;      // planes are [chunk*9 + tap][Npad][32], Cin = 32: chunk 0
             const unsigned koff = (unsigned)tap * (unsigned)a.Npad * 64u;
             const unsigned l = lds0 + 2u * PATCH + (unsigned)(tap * 64 * 64 + rb * 1024);
-            patch_dma_pair(rs_wh, rs_wl, vo, koff, koff, l, l + PW_W1);
+            lds_dma_pair(rs_wh, rs_wl, vo, koff, koff, l, l + PW_W1);
         }
     }
     // ---- patch loader (as above, one chunk)
@@ -292,7 +260,7 @@ void conv_patch_wres_f16s3_kernel(const ConvArgs a, const int tiles_x, const int
             const bool ok = pt < n_tiles && (unsigned)iy < (unsigned)a.Hi && (unsigned)ix < (unsigned)a.Wi;
             const unsigned vo = ok ? (unsigned)((b * a.Hi + iy) * a.Wi + ix) * PS + (unsigned)a.in_coff * 2u + pchunk[j] : OOB;
             const unsigned l = lds0 + (unsigned)pbuf * PATCH + (unsigned)pc_piece[j] * 1024u;
-            patch_dma_pair(rs_a, rs_a, vo, 0u, lo_plane, l, l + PT_PLANE);
+            lds_dma_pair(rs_a, rs_a, vo, 0u, lo_plane, l, l + PT_PLANE);
         }
     };
 
@@ -305,7 +273,7 @@ void conv_patch_wres_f16s3_kernel(const ConvArgs a, const int tiles_x, const int
     for (int i = 0; i < TM; ++i) a_base[i] = (wm * TM + i) * PT_PC + lr;
 
     patch_issue(blockIdx.x, 0);
-    patch_wait_vmcnt<0>();                                               // weights and the first patch: this wave's pieces
+    vmcnt<0>();                                                          // weights and the first patch: this wave's pieces
     int pbuf = 0;
     for (int tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
         int tb, y0, x0;
@@ -351,7 +319,7 @@ void conv_patch_wres_f16s3_kernel(const ConvArgs a, const int tiles_x, const int
                 }
             __builtin_amdgcn_sched_barrier(0);
         }
-        patch_wait_vmcnt<0>();                                           // this wave's pieces of the next patch (issued nine taps ago) and older stores
+        vmcnt<0>();                                                      // this wave's pieces of the next patch (issued nine taps ago) and older stores
         int mrow[TM];
 #pragma unroll
         for (int i = 0; i < TM; ++i) {
@@ -361,7 +329,7 @@ void conv_patch_wres_f16s3_kernel(const ConvArgs a, const int tiles_x, const int
         conv_f16s3_epilogue_regs<WM, WN, EPI == EPI_SPLIT_RES>(a, acc, nullptr, mrow, wn * WN, tid, lh);
         pbuf ^= 1;
     }
-    patch_wait_vmcnt<0>();
+    vmcnt<0>();
 }
 
 bool conv_patch_supported(int ksize, int stride, int pad, int cin, int cout) {
@@ -396,9 +364,8 @@ static int launch_patch(const ConvArgs& a, hipStream_t s) {
     constexpr int NT = NWM * NWN * 64;
     const int tiles_x = (a.Wo + PT_TW - 1) / PT_TW, tiles_y = (a.Ho + PT_TH - 1) / PT_TH, gn = (a.Cout + BN - 1) / BN;
     const int lds = 4 * PT_PLANE + STAGES * 2 * BN * 64;
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-        return hip_fail(hipGetLastError(), "conv_patch_f16s3 device query");
+    const int cus = device_cu_count();
+    if (cus <= 0) return hip_fail(hipGetLastError(), "conv_patch_f16s3 device query");
     const int by_lds = (160 * 1024) / lds, by_waves = (MINW * 4) / (NWM * NWN) > 0 ? (MINW * 4) / (NWM * NWN) : 1;
     const int per_cu = by_lds < by_waves ? by_lds : by_waves;
     const int64_t tiles = (int64_t)a.B * tiles_x * tiles_y * gn;
@@ -407,43 +374,30 @@ static int launch_patch(const ConvArgs& a, hipStream_t s) {
     auto k_res = conv_patch_f16s3_kernel<BN, NWM, NWN, STAGES, MINW, EPI_SPLIT_RES>;
     auto k_plain = conv_patch_f16s3_kernel<BN, NWM, NWN, STAGES, MINW, EPI_SPLIT>;
     static std::atomic<unsigned long long> attr_done{0};
-    if (!((attr_done.load(std::memory_order_acquire) >> (dev & 63)) & 1ull)) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_res), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void*>(k_plain), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-            return hip_fail(hipGetLastError(), "conv_patch_f16s3 LDS attribute");
-        attr_done.fetch_or(1ull << (dev & 63), std::memory_order_release);
-    }
+    if (int rc = lds_opt_in(attr_done, 160 * 1024, "conv_patch_f16s3", k_res, k_plain)) return rc;
     if (a.res) hipLaunchKernelGGL(k_res, dim3(grid), dim3(NT), lds, s, a, tiles_x, tiles_y, gn);
     else hipLaunchKernelGGL(k_plain, dim3(grid), dim3(NT), lds, s, a, tiles_x, tiles_y, gn);
     return hip_fail(hipGetLastError(), "conv_patch_f16s3 launch");
 }
 
 int launch_conv_patch_f16s3(const ConvArgs& a, int mode, hipStream_t s) {
-    if (!a.in || !a.w_hi || !a.w_lo || !a.bias || !a.inv_scale || !a.out) { set_error("launch_conv_patch: null pointer"); return RTOD_E_ARG; }
+    if (int rc = check_split_conv_args(a, "launch_conv_patch", false)) return rc;
     if (!conv_patch_supported(a.kh, a.stride, a.pad, a.Cin, a.Cout) || a.kw != 3 || a.Ho != a.Hi || a.Wo != a.Wi || a.dec.enabled || a.pw_wh) {
         set_error("launch_conv_patch: unsupported layer (k=%d s=%d pad=%d Cin=%d)", a.kh, a.stride, a.pad, a.Cin); return RTOD_E_ARG;
     }
     if (a.in_ldc % 8 || a.in_coff % 8 || a.out_ldc % 8 || a.out_coff % 8 || a.K != a.Kpad || a.K != 9 * a.Cin) { set_error("launch_conv_patch: bad view / K"); return RTOD_E_ARG; }
-    if (a.in_bytes == 0 || a.in_bytes >= OOB || a.w_bytes == 0 || a.w_bytes >= OOB) { set_error("launch_conv_patch: buffer extents"); return RTOD_E_ARG; }
-    if ((uint64_t)a.B * a.Hi * a.Wi * a.in_ldc * 4ull > (uint64_t)a.in_bytes) { set_error("launch_conv_patch: input view exceeds its buffer"); return RTOD_E_ARG; }
     if (mode == PATCH_WRES_MODE) {
         if (a.Cin != 32 || a.Cout != 64 || a.Npad < 64) { set_error("launch_conv_patch: the weights-resident tile needs Cin = 32, Cout = 64"); return RTOD_E_ARG; }
         const int tiles_x = (a.Wo + PT_TW - 1) / PT_TW, tiles_y = (a.Ho + PT_TH - 1) / PT_TH;
-        int dev = 0, cus = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-            return hip_fail(hipGetLastError(), "conv_patch_f16s3 device query");
+        const int cus = device_cu_count();
+        if (cus <= 0) return hip_fail(hipGetLastError(), "conv_patch_f16s3 device query");
         const int64_t tiles = (int64_t)a.B * tiles_x * tiles_y;
         if (tiles >= (1ll << 30)) { set_error("launch_conv_patch: too many tiles"); return RTOD_E_ARG; }
         const int grid = (int)(tiles < cus ? tiles : cus);
         auto k_res = conv_patch_wres_f16s3_kernel<EPI_SPLIT_RES>;
         auto k_plain = conv_patch_wres_f16s3_kernel<EPI_SPLIT>;
         static std::atomic<unsigned long long> attr_done{0};
-        if (!((attr_done.load(std::memory_order_acquire) >> (dev & 63)) & 1ull)) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_res), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-                hipFuncSetAttribute(reinterpret_cast<const void*>(k_plain), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-                return hip_fail(hipGetLastError(), "conv_patch_f16s3 LDS attribute");
-            attr_done.fetch_or(1ull << (dev & 63), std::memory_order_release);
-        }
+        if (int rc = lds_opt_in(attr_done, 160 * 1024, "conv_patch_f16s3", k_res, k_plain)) return rc;
         static_assert(PW_LDS <= 160 * 1024, "LDS budget");
         if (a.res) hipLaunchKernelGGL(k_res, dim3(grid), dim3(512), PW_LDS, s, a, tiles_x, tiles_y);
         else hipLaunchKernelGGL(k_plain, dim3(grid), dim3(512), PW_LDS, s, a, tiles_x, tiles_y);

@@ -27,38 +27,8 @@
 // slab (pieces past the end of K have an out-of-range source and write zeros into a slot nobody reads), so the B wait is always
 // vmcnt(8 + 2 NPP), and it implies that this wave's pieces of slab j+1 have landed by the end of iteration j.
 #include "conv_bandd_common.h"
-#include <atomic>
 
 namespace rtod {
-
-// hi and lo piece of one 8-row group: lane l's 16 bytes land at lds + 16 l; the lo piece sits 2 KiB behind the hi piece
-__device__ __forceinline__ void pwd_dma_pair(const __amdgpu_buffer_rsrc_t rsrc, unsigned voffset, unsigned soff_hi, unsigned soff_lo, unsigned lds_hi) {
-    unsigned keep;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %5\n\t"
-        "s_nop 0\n\t"
-        "buffer_load_dwordx4 %1, %2, %3 offen lds\n\t"
-        "s_add_u32 m0, %5, 0x800\n\t"
-        "s_nop 0\n\t"
-        "buffer_load_dwordx4 %1, %2, %4 offen lds\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(voffset), "s"(rsrc), "s"(soff_hi), "s"(soff_lo), "s"(lds_hi)
-        : "memory", "scc");
-}
-
-template <int N> __device__ __forceinline__ void pwd_wait_vmcnt() {
-    static_assert(N >= 0 && N <= 63, "vmcnt literal");
-#define RTOD_VMCNT_CASE(n) else if constexpr (N == n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory");
-    if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    RTOD_VMCNT_CASE(4) RTOD_VMCNT_CASE(5) RTOD_VMCNT_CASE(6) RTOD_VMCNT_CASE(7) RTOD_VMCNT_CASE(9) RTOD_VMCNT_CASE(11)
-    RTOD_VMCNT_CASE(8) RTOD_VMCNT_CASE(10) RTOD_VMCNT_CASE(12) RTOD_VMCNT_CASE(14) RTOD_VMCNT_CASE(16) RTOD_VMCNT_CASE(18) RTOD_VMCNT_CASE(20)
-    RTOD_VMCNT_CASE(22) RTOD_VMCNT_CASE(24) RTOD_VMCNT_CASE(26) RTOD_VMCNT_CASE(28) RTOD_VMCNT_CASE(30) RTOD_VMCNT_CASE(32) RTOD_VMCNT_CASE(36)
-    RTOD_VMCNT_CASE(40) RTOD_VMCNT_CASE(44) RTOD_VMCNT_CASE(48)
-    else static_assert(N < 0, "add the vmcnt literal");
-#undef RTOD_VMCNT_CASE
-}
 
 // BM x (32 NW) workgroup tile, NW waves, each a BM x 32 strip; NST slabs of 64 channels in the LDS ring.
 // EPI | EPI_F16: plain-f16 instance (slab blocks keep their 4 KiB layout, the lo pieces are neither DMA'd nor read; hi B fragments only,
@@ -83,10 +53,7 @@ void conv_pwd_f16s3_kernel(const ConvArgs a, const int grid_m, const int grid_n)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int nwg = grid_m * grid_n;
     int bid = blockIdx.x;
-    if (!a.xcd_by_n) {                                          // XCD x (= blockIdx % 8) takes a contiguous range of tiles
-        const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-    }
+    if (!a.xcd_by_n) bid = xcd_remap(bid, nwg);                 // XCD x (= blockIdx % 8) takes a contiguous range of tiles
     const int bm = bid / grid_n, bn = bid - bm * grid_n;
     const int tid = (int)threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
@@ -96,9 +63,9 @@ void conv_pwd_f16s3_kernel(const ConvArgs a, const int grid_m, const int grid_n)
     const unsigned PS = (unsigned)a.in_ldc * 4u;                // bytes of one pixel (hi plane + lo plane)
     const unsigned lo_plane = (unsigned)a.in_ldc * 2u;
 
-    const __amdgpu_buffer_rsrc_t rs_a = __builtin_amdgcn_make_buffer_rsrc((void*)a.in, 0, a.in_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_wh = __builtin_amdgcn_make_buffer_rsrc((void*)a.w_hi, 0, a.w_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_wl = __builtin_amdgcn_make_buffer_rsrc((void*)a.w_lo, 0, a.w_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_a = buffer_rsrc(a.in, a.in_bytes);
+    const __amdgpu_buffer_rsrc_t rs_wh = buffer_rsrc(a.w_hi, a.w_bytes);
+    const __amdgpu_buffer_rsrc_t rs_wl = buffer_rsrc(a.w_lo, a.w_bytes);
     const unsigned lds0 = (unsigned)(size_t)smem;
     const int NS = a.Cin / 64;                                  // slabs
 
@@ -119,8 +86,8 @@ void conv_pwd_f16s3_kernel(const ConvArgs a, const int grid_m, const int grid_n)
         for (int k = 0; k < NPP; ++k) {
             const int p = wave + k * NW;
             const unsigned dst = p < NP ? base + (unsigned)((p >> 1) * 4096 + (p & 1) * 1024) : lds0 + (unsigned)(NST * SLAB);
-            if constexpr (F16) bandd_dma_hi(rs_a, live ? dma_vo[k] : OOB, soff, dst);
-            else pwd_dma_pair(rs_a, live ? dma_vo[k] : OOB, soff, lo_plane + soff, dst);
+            if constexpr (F16) lds_dma(rs_a, live ? dma_vo[k] : OOB, soff, dst);
+            else lds_dma_pair<0x800>(rs_a, live ? dma_vo[k] : OOB, soff, lo_plane + soff, dst);     // the lo piece sits 2 KiB behind the hi piece
         }
     };
     // ---- B fragments: lane (lr, lh) <- weight row n0 + 16 j + lr, 16-byte chunk lh of the step's panel; four register sets (t % 4)
@@ -133,10 +100,10 @@ void conv_pwd_f16s3_kernel(const ConvArgs a, const int grid_m, const int grid_n)
     auto load_b = [&](int t, u32x4 (&q)[TN][2]) __attribute__((always_inline)) {
         const unsigned vo = t < nsteps ? bvoff : OOB;
         const unsigned koff = (unsigned)t * wchunk;
-        q[0][0] = bandd_load_b<0>(rs_wh, vo, koff);
-        if constexpr (!F16) q[0][1] = bandd_load_b<0>(rs_wl, vo, koff);
-        q[1][0] = bandd_load_b<1024>(rs_wh, vo, koff);
-        if constexpr (!F16) q[1][1] = bandd_load_b<1024>(rs_wl, vo, koff);
+        q[0][0] = buffer_load_b128(rs_wh, vo, koff);
+        if constexpr (!F16) q[0][1] = buffer_load_b128(rs_wl, vo, koff);
+        q[1][0] = buffer_load_b128<1024>(rs_wh, vo, koff);
+        if constexpr (!F16) q[1][1] = buffer_load_b128<1024>(rs_wl, vo, koff);
     };
 
     f32x4 acc[TM][TN];
@@ -170,7 +137,7 @@ void conv_pwd_f16s3_kernel(const ConvArgs a, const int grid_m, const int grid_n)
     auto slab_body = [&](int j, auto par_c) __attribute__((always_inline)) {
         constexpr int par = decltype(par_c)::value;
         asm volatile("" : "+v"(xq0), "+v"(xq1));                // not loop-invariant: the unit addresses are recomputed per slab, not held in registers
-        if (j < NST - 1) pwd_wait_vmcnt<WAIT_SLAB_PRO>(); else pwd_wait_vmcnt<WAIT_SLAB>();
+        if (j < NST - 1) vmcnt<WAIT_SLAB_PRO>(); else vmcnt<WAIT_SLAB>();
         __builtin_amdgcn_sched_barrier(0);
         __builtin_amdgcn_s_barrier();                           // slab j complete in every wave's view; slab j - 1 released
         dma_slab(j + NST - 1);
@@ -183,8 +150,8 @@ void conv_pwd_f16s3_kernel(const ConvArgs a, const int grid_m, const int grid_n)
             const int q = u / TM, i = u % TM;
             if (i == 0) {                                       // step head: B set of step t + 2, wait for this step's
                 if (q == 0) load_b(2 * j + 2, Bq[(2 * par + 2) % 4]); else load_b(2 * j + 3, Bq[(2 * par + 3) % 4]);
-                pwd_wait_vmcnt<WAIT_B>();
-                if (q == 0) bandd_tie<TN, F16>(Bq[2 * par]); else bandd_tie<TN, F16>(Bq[2 * par + 1]);
+                vmcnt<WAIT_B>();
+                if (q == 0) tie_bset<F16>(Bq[2 * par]); else tie_bset<F16>(Bq[2 * par + 1]);
                 __builtin_amdgcn_sched_barrier(0);
             }
             if (u + 2 < 2 * TM) read_unit((u + 2) / TM, (u + 2) % TM, slotoff, Ah[(u + 2) % 3], Al[(u + 2) % 3]);
@@ -207,8 +174,8 @@ void conv_pwd_f16s3_kernel(const ConvArgs a, const int grid_m, const int grid_n)
         if (j + 1 < NS) slab_body(j + 1, std::integral_constant<int, 1>{});
     }
     // drain: trailing (out-of-range) B sets and slab pieces have landed before the ring becomes the transpose tile
-    pwd_wait_vmcnt<0>();
-    bandd_tie<TN, F16>(Bq[0]); bandd_tie<TN, F16>(Bq[1]); bandd_tie<TN, F16>(Bq[2]); bandd_tie<TN, F16>(Bq[3]);
+    vmcnt<0>();
+    tie_bset<F16>(Bq[0]); tie_bset<F16>(Bq[1]); tie_bset<F16>(Bq[2]); tie_bset<F16>(Bq[3]);
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_setprio(0);
 
@@ -231,14 +198,7 @@ static int launch_pwd(const ConvArgs& a, hipStream_t s) {
     auto k_plain = fe ? conv_pwd_f16s3_kernel<BM, NW, NST, MINW, EPI_SPLIT | EPI_F16> : conv_pwd_f16s3_kernel<BM, NW, NST, MINW, EPI_SPLIT>;
     if constexpr (lds > 64 * 1024) {                            // > 64 KiB of dynamic LDS needs the opt-in, once per device and instantiation
         static std::atomic<unsigned long long> attr_done[2] = {{0}, {0}};
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess) return hip_fail(hipGetLastError(), "conv_pwd_f16s3 hipGetDevice");
-        if (!((attr_done[fe].load(std::memory_order_acquire) >> (dev & 63)) & 1ull)) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_res), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess ||
-                hipFuncSetAttribute(reinterpret_cast<const void*>(k_plain), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
-                return hip_fail(hipGetLastError(), "conv_pwd_f16s3 LDS attribute");
-            attr_done[fe].fetch_or(1ull << (dev & 63), std::memory_order_release);
-        }
+        if (int rc = lds_opt_in(attr_done[fe], lds, "conv_pwd_f16s3", k_res, k_plain)) return rc;
     }
     if (a.res) hipLaunchKernelGGL(k_res, dim3(gm * gn), dim3(NT), lds, s, ax, gm, gn);
     else hipLaunchKernelGGL(k_plain, dim3(gm * gn), dim3(NT), lds, s, ax, gm, gn);
@@ -266,13 +226,11 @@ int conv_pwd_kernel_name(int idx, int epi, char* buf, size_t len) {
 }
 
 int launch_conv_pwd_f16s3(const ConvArgs& a, int idx, hipStream_t s) {
-    if (!a.in || !a.w_hi || (!a.w_lo && !a.f16) || !a.bias || !a.inv_scale || !a.out) { set_error("launch_conv_pwd: null pointer"); return RTOD_E_ARG; }
+    if (int rc = check_split_conv_args(a, "launch_conv_pwd", true)) return rc;
     if (!conv_pwd_supported(a.kh, a.stride, a.pad, a.Cin) || a.kw != 1 || a.Ho != a.Hi || a.Wo != a.Wi || a.dec.enabled || a.pw_wh) {
         set_error("launch_conv_pwd: unsupported shape (k=%d s=%d pad=%d Cin=%d)", a.kh, a.stride, a.pad, a.Cin); return RTOD_E_ARG;
     }
     if (a.in_ldc % 8 || a.in_coff % 8 || a.K != a.Kpad || a.K != a.Cin || a.Npad % 128) { set_error("launch_conv_pwd: bad view / K"); return RTOD_E_ARG; }
-    if (a.in_bytes == 0 || a.in_bytes >= OOB || a.w_bytes == 0 || a.w_bytes >= OOB) { set_error("launch_conv_pwd: buffer extents"); return RTOD_E_ARG; }
-    if ((uint64_t)a.B * a.Hi * a.Wi * a.in_ldc * 4ull > (uint64_t)a.in_bytes) { set_error("launch_conv_pwd: input view exceeds its buffer"); return RTOD_E_ARG; }
     switch (idx) {
 #define RTOD_X_CASE(i, bm, nw, nst, minw) case i: return launch_pwd<bm, nw, nst, minw>(a, s);
         RTOD_PWD_TILES(RTOD_X_CASE)

@@ -33,44 +33,10 @@
 // shorten these kernels: rocprofv3's per-dispatch trace shows ~4.5 us of every launch is dispatch + drain (a one-workgroup
 // kernel that writes 28 bytes takes 4.8 us there) and the weights of every layer arrive cold from HBM.
 #include "conv_f16s3_common.h"
-#include <atomic>
 #include <cstdio>
 #include <cstdlib>
 
 namespace rtod {
-
-// this wave's vector-memory operations except the N youngest have completed (loads, stores and LDS-DMA count together,
-// in issue order)
-template <int N> __device__ __forceinline__ void ring_wait_vmcnt() {
-    static_assert(N >= 0 && N <= 24, "vmcnt literal");
-#define RTOD_VMCNT_CASE(n) else if constexpr (N == n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory");
-    if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    RTOD_VMCNT_CASE(1) RTOD_VMCNT_CASE(2) RTOD_VMCNT_CASE(3) RTOD_VMCNT_CASE(4) RTOD_VMCNT_CASE(5) RTOD_VMCNT_CASE(6)
-    RTOD_VMCNT_CASE(7) RTOD_VMCNT_CASE(8) RTOD_VMCNT_CASE(9) RTOD_VMCNT_CASE(10) RTOD_VMCNT_CASE(11) RTOD_VMCNT_CASE(12)
-    RTOD_VMCNT_CASE(13) RTOD_VMCNT_CASE(14) RTOD_VMCNT_CASE(15) RTOD_VMCNT_CASE(16) RTOD_VMCNT_CASE(17) RTOD_VMCNT_CASE(18)
-    RTOD_VMCNT_CASE(19) RTOD_VMCNT_CASE(20) RTOD_VMCNT_CASE(21) RTOD_VMCNT_CASE(22) RTOD_VMCNT_CASE(23) RTOD_VMCNT_CASE(24)
-#undef RTOD_VMCNT_CASE
-}
-
-// Two LDS-DMA pieces (the hi and the lo plane of the same 16 rows): lane l's 16 bytes land at lds + 16*l.  M0 carries the
-// LDS byte address and is written in the statement that uses it (the compiler does not preserve M0 around asm; cdna guide
-// 5.7); s_nop 0: SALU write of M0 -> LDS-DMA read of M0.  voffset >= the descriptor's extent writes zeros.
-__device__ __forceinline__ void dma_pair(const __amdgpu_buffer_rsrc_t rsrc_hi, const __amdgpu_buffer_rsrc_t rsrc_lo, unsigned voffset,
-                                         unsigned soff_hi, unsigned soff_lo, unsigned lds_hi, unsigned lds_lo) {
-    unsigned keep;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %6\n\t"
-        "s_nop 0\n\t"
-        "buffer_load_dwordx4 %1, %2, %4 offen lds\n\t"
-        "s_mov_b32 m0, %7\n\t"
-        "s_nop 0\n\t"
-        "buffer_load_dwordx4 %1, %3, %5 offen lds\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(voffset), "s"(rsrc_hi), "s"(rsrc_lo), "s"(soff_hi), "s"(soff_lo), "s"(lds_hi), "s"(lds_lo)
-        : "memory");
-}
 
 // BM x BN workgroup tile, NWM x NWN waves of (BM/NWM) x (BN/NWN).  STAGES ring slots of one k32 step each.
 // LDS: [STAGES][A hi BM x 64 B | A lo | B hi BN x 64 B | B lo].  The epilogue's transpose tile is the ring slot the last
@@ -116,16 +82,15 @@ void conv_ring_f16s3_kernel(const ConvArgs a, const int grid_m, const int grid_n
     const int nk = a.Kpad / HBK;
     const int hw = a.Ho * a.Wo;
 
-    const __amdgpu_buffer_rsrc_t rs_a = __builtin_amdgcn_make_buffer_rsrc((void*)a.in, 0, a.in_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_wh = __builtin_amdgcn_make_buffer_rsrc((void*)a.w_hi, 0, a.w_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_wl = __builtin_amdgcn_make_buffer_rsrc((void*)a.w_lo, 0, a.w_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_a = buffer_rsrc(a.in, a.in_bytes);
+    const __amdgpu_buffer_rsrc_t rs_wh = buffer_rsrc(a.w_hi, a.w_bytes);
+    const __amdgpu_buffer_rsrc_t rs_wl = buffer_rsrc(a.w_lo, a.w_bytes);
     const unsigned lds0 = (unsigned)(size_t)smem;                // LDS byte address of the ring
 
     // tile sequence of this workgroup: t = blockIdx.x, + gridDim.x, ...; XCD-aware bijective remap of the tile index
     // (workgroups b and b + 8 share an XCD / L2: XCD x takes a contiguous range of tiles, neighbours share A row panels)
     auto tile_of = [&](int t, int& bm, int& bn) __attribute__((always_inline)) {
-        const int q = n_tiles >> 3, r = n_tiles & 7, xcd = t & 7;
-        const int u = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (t >> 3);
+        const int u = xcd_remap(t, n_tiles);
         bm = u / grid_n; bn = u - bm * grid_n;
     };
 
@@ -175,12 +140,12 @@ void conv_ring_f16s3_kernel(const ConvArgs a, const int grid_m, const int grid_n
             const bool ok = (unsigned)(iy0[j] + ld_ky) < (unsigned)a.Hi && (unsigned)(ix0[j] + ld_kx) < (unsigned)a.Wi;
             const unsigned vo = ok ? pa[j] + tap_off : OOB;
             const unsigned l = sbase + (unsigned)blk_a[j] * 1024u;
-            dma_pair(rs_a, rs_a, vo, 0u, lo_plane, l, l + PANEL_A);
+            lds_dma_pair(rs_a, rs_a, vo, 0u, lo_plane, l, l + PANEL_A);
         }
 #pragma unroll
         for (int j = 0; j < B_PER; ++j) {
             const unsigned l = sbase + 2u * PANEL_A + (unsigned)blk_b[j] * 1024u;
-            dma_pair(rs_wh, rs_wl, pw_[j], koff, koff, l, l + PANEL_B);           // hi and lo weight planes: two allocations
+            lds_dma_pair(rs_wh, rs_wl, pw_[j], koff, koff, l, l + PANEL_B);           // hi and lo weight planes: two allocations
         }
         ++ld_kc;
         if (++ld_kx == a.kw) { ld_kx = 0; if (++ld_ky == a.kh) { ld_ky = 0; ld_c0 += HBK; } }
@@ -225,7 +190,7 @@ void conv_ring_f16s3_kernel(const ConvArgs a, const int grid_m, const int grid_n
 
 #pragma unroll 1
         for (int kc = 0; kc < nk; ++kc) {
-            ring_wait_vmcnt<(STAGES - 2) * LPW>();               // this wave's pieces of the current step have landed (the younger STAGES-2 stages may stay in flight)
+            vmcnt<(STAGES - 2) * LPW>();                         // this wave's pieces of the current step have landed (the younger STAGES-2 stages may stay in flight)
             __builtin_amdgcn_s_barrier();                        // ... and everybody's; the previous step's slot is free
             {
                 const int prev = slot == 0 ? STAGES - 1 : slot - 1;
@@ -277,7 +242,7 @@ void conv_ring_f16s3_kernel(const ConvArgs a, const int grid_m, const int grid_n
             __builtin_amdgcn_s_barrier();                        // transpose reads done before the slot is handed back to the loader
         }
     }
-    ring_wait_vmcnt<0>();                                        // trailing (out-of-range) pieces: nothing may be in flight at exit
+    vmcnt<0>();                                                  // trailing (out-of-range) pieces: nothing may be in flight at exit
 #ifdef RTOD_TIMELINE
     __syncthreads();
     if (threadIdx.x == 0 && blockIdx.x < RING_TL_BLOCKS) { g_ring_tl[blockIdx.x * 2] = tl_start_; g_ring_tl[blockIdx.x * 2 + 1] = __builtin_amdgcn_s_memrealtime(); }
@@ -311,24 +276,16 @@ static int launch_ring(const ConvArgs& a, hipStream_t s) {
     const bool pw = a.pw_wh != nullptr;
     const int lds = STAGES * (2 * BM * 64 + 2 * BN * 64);
     if (lds > 160 * 1024) { set_error("conv_ring_f16s3: %d bytes of LDS", lds); return RTOD_E_ARG; }
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-        return hip_fail(hipGetLastError(), "conv_ring_f16s3 device query");
+    const int cus = device_cu_count();
+    if (cus <= 0) return hip_fail(hipGetLastError(), "conv_ring_f16s3 device query");
     const int slots = cus * ((160 * 1024) / lds < WPC ? (160 * 1024) / lds : WPC);
     const int tiles = gm * gn;
     const int grid = tiles < slots ? tiles : slots;
     auto k_dec = conv_ring_f16s3_kernel<BM, BN, NWM, NWN, STAGES, MINW, EPI_DECODE>;
     auto k_res = conv_ring_f16s3_kernel<BM, BN, NWM, NWN, STAGES, MINW, EPI_SPLIT_RES>;
     auto k_plain = conv_ring_f16s3_kernel<BM, BN, NWM, NWN, STAGES, MINW, EPI_SPLIT>;
-    static std::atomic<unsigned long long> attr_done{0};       // per instantiation, one bit per device: > 64 KiB of dynamic LDS needs the opt-in
-    if (!((attr_done.load(std::memory_order_acquire) >> (dev & 63)) & 1ull)) {
-        const int mx = 160 * 1024;
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_dec), hipFuncAttributeMaxDynamicSharedMemorySize, mx) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void*>(k_res), hipFuncAttributeMaxDynamicSharedMemorySize, mx) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void*>(k_plain), hipFuncAttributeMaxDynamicSharedMemorySize, mx) != hipSuccess)
-            return hip_fail(hipGetLastError(), "conv_ring_f16s3 LDS attribute");
-        attr_done.fetch_or(1ull << (dev & 63), std::memory_order_release);
-    }
+    static std::atomic<unsigned long long> attr_done{0};
+    if (int rc = lds_opt_in(attr_done, 160 * 1024, "conv_ring_f16s3", k_dec, k_res, k_plain)) return rc;
     if (pw) { set_error("conv_ring_f16s3: fused pointwise epilogue not built for this kernel"); return RTOD_E_ARG; }
     if (a.dec.enabled) hipLaunchKernelGGL(k_dec, dim3(grid), dim3(NT), lds, s, a, gm, gn);
     else if (a.res) hipLaunchKernelGGL(k_res, dim3(grid), dim3(NT), lds, s, a, gm, gn);
@@ -355,14 +312,12 @@ static int launch_ring(const ConvArgs& a, hipStream_t s) {
 
 int launch_conv_ring_f16s3(const ConvArgs& a_in, int mode, hipStream_t s) {
     ConvArgs a = a_in;
-    if (!a.in || !a.w_hi || !a.w_lo || !a.bias || !a.inv_scale || !a.out) { set_error("launch_conv_ring: null pointer"); return RTOD_E_ARG; }
+    if (int rc = check_split_conv_args(a, "launch_conv_ring", false)) return rc;
     if (a.Cin % HBK || a.in_ldc % 8 || a.in_coff % 8 || a.Kpad % HBK || a.K != a.Kpad || a.K != a.kh * a.kw * a.Cin) {
         set_error("launch_conv_ring: needs Cin %% 32 == 0 and 8-channel aligned views (Cin=%d ldc=%ld coff=%d K=%d Kpad=%d)", a.Cin, (long)a.in_ldc, a.in_coff, a.K, a.Kpad);
         return RTOD_E_ARG;
     }
     if (a.B <= 0 || a.Ho <= 0 || a.Wo <= 0 || a.Cout <= 0) { set_error("launch_conv_ring: empty shape"); return RTOD_E_ARG; }
-    if (a.in_bytes == 0 || a.in_bytes >= OOB || a.w_bytes == 0 || a.w_bytes >= OOB) { set_error("launch_conv_ring: buffer extents"); return RTOD_E_ARG; }
-    if ((uint64_t)a.B * a.Hi * a.Wi * a.in_ldc * 4ull > (uint64_t)a.in_bytes) { set_error("launch_conv_ring: input view exceeds its buffer"); return RTOD_E_ARG; }
 #ifdef RTOD_DIAG
     // diagnostic build only: zero-extent descriptors drop the loads of one operand (DMA pieces then write zeros), bit 4 the epilogue
     static const int dbg_zero = getenv("RTOD_DBG_ZERO") ? atoi(getenv("RTOD_DBG_ZERO")) : 0;

@@ -151,7 +151,7 @@ void conv_stem_split_kernel(const StemSplitArgs a) {
     const int64_t plane = (int64_t)a.H * a.W;
     const int hw = a.Ho * a.Wo;
     float* Tw = T[wave];
-    const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc((void*)a.x, 0, a.x_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_x = buffer_rsrc(a.x, a.x_bytes);
     int koff[8], need[8];
     float amax = 0.f;
 #pragma unroll

@@ -32,7 +32,6 @@
 // Arithmetic, K order and rounding points are those of the stand-alone kernels (conv_stem.hip, conv_igemm_f16s3.hip with
 // EPI_SPLIT_PW): the outputs are bit-identical to the unfused plan's.
 #include "conv_f16s3_common.h"
-#include <atomic>
 #include <cstdio>
 #include <cstdlib>
 
@@ -76,23 +75,6 @@ struct Stem2Args {
     int dbg;                                          // RTOD_DIAG builds only: phase ablation bits (timing experiments)
 };
 
-__device__ __forceinline__ void s2_dma_pair(const __amdgpu_buffer_rsrc_t rsrc_hi, const __amdgpu_buffer_rsrc_t rsrc_lo, unsigned voffset,
-                                            unsigned soff, unsigned lds_hi, unsigned lds_lo) {
-    unsigned keep;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %5\n\t"
-        "s_nop 0\n\t"
-        "buffer_load_dwordx4 %1, %2, %4 offen lds\n\t"
-        "s_mov_b32 m0, %6\n\t"
-        "s_nop 0\n\t"
-        "buffer_load_dwordx4 %1, %3, %4 offen lds\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(voffset), "s"(rsrc_hi), "s"(rsrc_lo), "s"(soff), "s"(lds_hi), "s"(lds_lo)
-        : "memory");
-}
-
 template <bool PW>
 __global__ __launch_bounds__(S2_NT, 2)
 void conv_stem2_f16s3_kernel(const Stem2Args a) {
@@ -115,8 +97,8 @@ void conv_stem2_f16s3_kernel(const Stem2Args a) {
 
     // ---- once per workgroup: layer 1's weights -> LDS, scale / bias tables
     {
-        const __amdgpu_buffer_rsrc_t rs_wh = __builtin_amdgcn_make_buffer_rsrc((void*)c.w_hi, 0, c.w_bytes, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rs_wl = __builtin_amdgcn_make_buffer_rsrc((void*)c.w_lo, 0, c.w_bytes, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rs_wh = buffer_rsrc(c.w_hi, c.w_bytes);
+        const __amdgpu_buffer_rsrc_t rs_wl = buffer_rsrc(c.w_lo, c.w_bytes);
         const unsigned lds0 = (unsigned)(size_t)w1;
         const int lrow = lane >> 2;
         for (int p = wave; p < 9 * 4; p += S2_WAVES) {                  // (tap, 16-row block): one hi + one lo piece each
@@ -125,13 +107,14 @@ void conv_stem2_f16s3_kernel(const Stem2Args a) {
             const int ch = (lane & 3) ^ ((rho >> 1) & 3);
             const unsigned vo = (unsigned)(tr_chan_of_row(rho) * 32 + ch * 8) * 2u;      // planes are [chunk*9 + tap][Npad][32], Cin = 32: chunk 0
             const unsigned l = lds0 + (unsigned)(tap * 64 * 64 + rb * 1024);
-            s2_dma_pair(rs_wh, rs_wl, vo, (unsigned)tap * (unsigned)c.Npad * 64u, l, l + S2_W1);
+            const unsigned koff = (unsigned)tap * (unsigned)c.Npad * 64u;
+            lds_dma_pair(rs_wh, rs_wl, vo, koff, koff, l, l + S2_W1);
         }
         for (int i = tid; i < 64; i += S2_NT) { tab[i] = c.inv_scale[i] * SPLIT_SCALE; tab[64 + i] = c.bias[i] * SPLIT_SCALE; }
         if constexpr (PW)
             for (int i = tid; i < 32; i += S2_NT) { tab[128 + i] = c.pw_inv_scale[i] * SPLIT_SCALE; tab[160 + i] = c.pw_bias[i] * SPLIT_SCALE; }
         for (int i = tid; i < (S2_ZERO + 3) / 4; i += S2_NT) reinterpret_cast<unsigned*>(zreg)[i] = 0u;
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        vmcnt<0>();
     }
 
     // ---- stem constants of this lane: weight fragments (rows in the transposed product's channel order), scale, bias
@@ -194,7 +177,7 @@ void conv_stem2_f16s3_kernel(const Stem2Args a) {
         in_y[r] = i < S2_IN ? iy : -(1 << 20);
         in_x[r] = ix;
     }
-    const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc((void*)a.x, 0, a.x_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_x = buffer_rsrc(a.x, a.x_bytes);
     const int w_lane = lr * 64 + ((lh ^ ((lr >> 1) & 3)) << 4);         // fragment address inside a 16-row weight block
     float amax = 0.f;
 #ifdef RTOD_DIAG
@@ -500,20 +483,14 @@ int launch_conv_stem2_f16s3(const float* x, int B, int H, int W, const _Float16*
     if (const char* e = getenv("RTOD_S2_DBG")) a.dbg = atoi(e);
 #endif
     a.tiles_x = (c1.Wo + S2_TW - 1) / S2_TW; a.tiles_y = (c1.Ho + S2_TH - 1) / S2_TH;
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-        return hip_fail(hipGetLastError(), "conv_stem2 device query");
+    const int cus = device_cu_count();
+    if (cus <= 0) return hip_fail(hipGetLastError(), "conv_stem2 device query");
     const int64_t pairs = ((int64_t)B * a.tiles_x * a.tiles_y + 1) / 2;      // one tile per wave half
     const int grid = (int)(pairs < cus ? pairs : cus);
     auto k_pw = conv_stem2_f16s3_kernel<true>;
     auto k_plain = conv_stem2_f16s3_kernel<false>;
     static std::atomic<unsigned long long> attr_done{0};
-    if (!((attr_done.load(std::memory_order_acquire) >> (dev & 63)) & 1ull)) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_pw), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void*>(k_plain), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-            return hip_fail(hipGetLastError(), "conv_stem2 LDS attribute");
-        attr_done.fetch_or(1ull << (dev & 63), std::memory_order_release);
-    }
+    if (int rc = lds_opt_in(attr_done, 160 * 1024, "conv_stem2", k_pw, k_plain)) return rc;
     static_assert(S2_LDS <= 160 * 1024, "LDS budget");
     if (pw) hipLaunchKernelGGL(k_pw, dim3(grid), dim3(S2_NT), S2_LDS, s, a);
     else hipLaunchKernelGGL(k_plain, dim3(grid), dim3(S2_NT), S2_LDS, s, a);

@@ -24,7 +24,6 @@
 //
 // Ties in objectness (undefined in the reference, torch.sort is unstable) resolve to the lower row.
 #include "rtod_internal.h"
-#include <atomic>
 
 namespace rtod {
 
@@ -610,17 +609,10 @@ void nms_emit_kernel(int B, int n, NmsWs w, float* __restrict__ out, int cap, in
     }
 }
 
-// > 64 KiB of dynamic LDS needs the opt-in, once per device (idempotent: a second thread may repeat the calls)
+// > 64 KiB of dynamic LDS needs the opt-in, once per device (both entry points share it)
 static int nms_lds_opt_in() {
     static std::atomic<unsigned long long> done{0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return hip_fail(hipGetLastError(), "write_results hipGetDevice");
-    if ((done.load(std::memory_order_acquire) >> (dev & 63)) & 1ull) return RTOD_OK;
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(nms_sort_suppress_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, NMS_LDS_BYTES) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(nms_sort_suppress_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, NMS_LDS_BYTES) != hipSuccess)
-        return hip_fail(hipGetLastError(), "write_results LDS attribute");
-    done.fetch_or(1ull << (dev & 63), std::memory_order_release);
-    return RTOD_OK;
+    return lds_opt_in(done, NMS_LDS_BYTES, "write_results", nms_sort_suppress_kernel<false>, nms_sort_suppress_kernel<true>);
 }
 
 int launch_write_results(const float* pred, int batch, int n, int num_class, float conf, float nms,

@@ -7,6 +7,7 @@
 #define RTOD_DIAG 1
 #endif
 #include <algorithm>
+#include <atomic>
 #include <cstdint>
 #include <cstdio>
 #include <string>
@@ -24,6 +25,27 @@ int hip_fail(hipError_t e, const char* what);
         hipError_t _e = (expr);                                     \
         if (_e != hipSuccess) return ::rtod::hip_fail(_e, #expr);   \
     } while (0)
+
+// More than 64 KiB of dynamic LDS needs a per-kernel opt-in, made once per device: `done` is the calling instantiation's own
+// static word, one bit per device.  Idempotent: two threads may both make the calls.  Error texts start with `who`.
+template <typename... Kernel>
+int lds_opt_in(std::atomic<unsigned long long>& done, int bytes, const char* who, Kernel... kernels) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return hip_fail(hipGetLastError(), (std::string(who) + " hipGetDevice").c_str());
+    if ((done.load(std::memory_order_acquire) >> (dev & 63)) & 1ull) return RTOD_OK;
+    for (const void* k : {reinterpret_cast<const void*>(kernels)...})
+        if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess)
+            return hip_fail(hipGetLastError(), (std::string(who) + " LDS attribute").c_str());
+    done.fetch_or(1ull << (dev & 63), std::memory_order_release);
+    return RTOD_OK;
+}
+
+// compute units of the current device (persistent grids are sized by it); 0 if the query fails
+inline int device_cu_count() {
+    int dev = 0, cus = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
+    return cus;
+}
 
 // NHWC view of an activation: element (b,y,x,c) at base[((b*H + y)*W + x)*ldc + coff + c]
 struct View {
@@ -123,6 +145,18 @@ __device__ __forceinline__ float apply_act(float v, int act) {
 }
 __device__ __forceinline__ void split_overflow_report(int32_t* flag, float amax) {
     if (flag && !(amax <= F16_MAX)) atomicOr(flag, 1);        // also true for NaN
+}
+// Raw buffer descriptor of `bytes` bytes at p: stride 0, descriptor word 3 = 0x00020000 (32-bit data format).  A buffer load
+// at voffset >= bytes returns zeros and an LDS-DMA piece writes zeros: the kernels send padding and tail lanes out of range.
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t buffer_rsrc(const void* p, unsigned bytes) {
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, bytes, 0x00020000);
+}
+// XCD-aware bijective remap of a workgroup or tile index id in [0, n): the dispatcher deals consecutive indices round-robin
+// over the 8 XCDs, and XCD x = id % 8 takes the x-th contiguous range of the result, so neighbouring tiles (which share an
+// operand panel) share one L2.
+__device__ __forceinline__ int xcd_remap(int id, int n) {
+    const int q = n >> 3, r = n & 7, xcd = id & 7;
+    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (id >> 3);
 }
 #endif
 
