@@ -102,14 +102,15 @@ int rtod_plan_launch_kernel_name(const rtod_plan* plan, int index, char* buf, si
  *   1  split-precision f16 MFMA: a*w ~= ah*wh + ah*wl + al*wh with fp32 accumulation (22-bit
  *      operands, error ~2x fp32 per layer), 16x the MFMA rate per product.  Activations live in
  *      HBM as f16 hi/lo planes (x8 pre-scaled): needs |activation| < 8188, every conv after the
- *      stem with Cin % 32 == 0, no stand-alone shortcut / copy / decode launch; otherwise RTOD_E_CFG.
+ *      stem with Cin % 32 == 0 (or, with option "narrow_cin", Cin == 16: conv_c16_f16s3.hip), no stand-alone
+ *      shortcut / copy / decode launch; otherwise RTOD_E_CFG.
  *   2  plain f16 (opt-in speed mode, not the parity path): every activation stored once as RNE_f16(8x) in the hi plane
  *      of mode 1's layout (the lo plane is never written or read), weights = mode 1's pre-scaled hi plane, ONE
  *      v_mfma_f32_16x16x32_f16 per fragment pair with fp32 accumulation; epilogue (scale, bias, activation, fused
  *      shortcut, saturating store + range flag) as mode 1.  Error ~1e-3 relative end to end (profiles/f16_floor.json),
  *      same range |activation| < 8188, same cfg requirements (RTOD_E_CFG otherwise; also with bn_batch_stats).  Kernels:
- *      the split stem, then the generic tiles, the bandd band / wide tiles and the 1x1 slab tiles in their f16
- *      instances (no conv_band / ring / patch tile, no fused stem + layer 1, no hosted pointwise conv).
+ *      the split stem, then the generic tiles, the bandd band / wide tiles, the 1x1 slab tiles and the narrow (Cin == 16)
+ *      tiles in their f16 instances (no conv_band / ring / patch tile, no fused stem + layer 1, no hosted pointwise conv).
  * Other modes: RTOD_E_ARG.
  * cfg grammar: the reference's (src/darknet.py:412-603) plus three extension keys for YOLOv5-style blocks (detect.py:255-285
  * fetches that model from the network; only its building blocks exist here): [convolutional] activation=silu,
@@ -129,8 +130,13 @@ int rtod_plan_set_precision(rtod_plan* plan, int mode);
  *   "bn_batch_stats"    (default 0) exact-fp32 plans: BatchNorm on batch statistics instead of the folded running statistics
  *   "k_slices"          exact-fp32 plans: deep small-grid layers summed in K slices (conv_igemm_f32.hip); 0: one chain
  *   "k_slice_workgroups" ... one workgroup per slice when the grid is small; 0: always inside the workgroup (same bits)
+ *   "narrow_cin"        (default 0) precisions 1 / 2 accept convs after layer 0 that read exactly 16 channels (YOLOv3-tiny's
+ *                       layer 2, any cfg with a 16-filter stem): they run on their own tile family (conv_c16_f16s3.hip, variant
+ *                       ids 140 ..., K order tap-major over the 16 channels).  Other Cin % 32 != 0 (48, 80, ...) stay refused.
+ *                       Plans without such a layer, and exact-fp32 plans, are unchanged by it
  *   "force_f16s3_variant" / "force_f32_variant"   >= 0: one tile variant for every conv (tests, A/B runs)
- * Options that leave a cfg inexpressible in the split-f16 format return RTOD_E_CFG when precision is 1 or 2. */
+ * Options that leave a cfg inexpressible in the split-f16 format return RTOD_E_CFG when precision is 1 or 2 (so does setting
+ * "narrow_cin" back to 0 on a plan that needs it); the plan then stays as it was. */
 int rtod_plan_set_option(rtod_plan* plan, const char* name, int value);
 /* Split-f16 plans store activations as f16 hi/lo planes of 8*x: |activation| must stay below 8188.  Producers
  * saturate at that range (never inf / NaN) and OR 1 into *flag_dev (caller-owned device int32, zero it yourself)

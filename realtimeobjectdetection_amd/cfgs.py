@@ -132,6 +132,27 @@ def mini_fallback_cfg(height=64, width=64, classes=3) -> str:
     return "\n".join(L) + "\n"
 
 
+def narrow_mini_cfg(height=64, width=64, classes=3) -> str:
+    """Small test network for the 16-input-channel convolutions (plan option narrow_cin): a 16-filter stem like YOLOv3-tiny's,
+    then a Cin = 16 conv of each kind (3x3 stride 1 / stride 2, 1x1, one reading the stem out of a concat buffer, one with a
+    fused shortcut, a head with fused decode; 16, 32 and 24 output channels) among ordinary 32-channel layers and a max-pool.
+    One head at stride 8."""
+    nout = 3 * (5 + classes)
+    L = _net(height, width)
+    L += _conv(16, 3, 1)                               # 0: 16-filter stem (exact-fp32 conv), lives in route 5's buffer at channel 16
+    L += _conv(16, 3, 1)                               # 1: Cin 16, 3x3 s1 p1, reads the view ldc 32 / coff 16
+    L += _conv(16, 1, 1)                               # 2: Cin 16, 1x1
+    L += _conv(16, 3, 1) + _shortcut(-3)               # 3, 4: Cin 16 with the shortcut (layer 1) in its epilogue, writes ldc 32 / coff 0
+    L += _route(-1, -5)                                # 5: layers 4 and 0, 32 @ H x W, zero-copy (a source of 0 would mean "this layer")
+    L += _conv(32, 3, 2)                               # 6: ordinary 32-channel layer, 32 @ H/2
+    L += _maxpool(2, 2)                                # 7: 32 @ H/4
+    L += _conv(16, 1, 1)                               # 8: 32 -> 16
+    L += _conv(32, 3, 2)                               # 9: Cin 16, 3x3 s2, 32 @ H/8 (followed by a 1x1: must not host it)
+    L += _conv(16, 1, 1)                               # 10: 32 -> 16
+    L += _conv(nout, 1, 1, bn=False, act="linear") + _yolo((0, 1, 2), _ANCHORS_V3, 9, classes)   # 11, 12: Cin 16 head, fused decode
+    return "\n".join(L) + "\n"
+
+
 def v5_style_mini_cfg(height=128, width=128, classes=80, act="silu") -> str:
     """YOLOv5-style building blocks in the (extended) cfg grammar — NOT a reference network.  The reference's YOLOv5 path is a
     torch.hub fetch (detect.py:255-285) whose model source does not exist offline, so no YOLOv5 graph can be pinned; this cfg

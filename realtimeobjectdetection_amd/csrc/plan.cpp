@@ -318,6 +318,7 @@ int Plan::set_option(const char* name, int value) {
     else if (k == "fuse_shortcut") flag = &opt_fuse_shortcut;
     else if (k == "fuse_decode") flag = &opt_fuse_decode;
     else if (k == "zero_copy_concat") flag = &opt_zero_copy_concat;
+    else if (k == "narrow_cin") flag = &opt_narrow_cin;
     else if (k == "force_f16s3_variant") num = &opt_force_f16s3_variant;
     else if (k == "force_f32_variant") num = &opt_force_f32_variant;
     else { set_error("set_option: unknown option '%s'", name); return RTOD_E_ARG; }
@@ -483,6 +484,7 @@ int Plan::plan_buffers() {
         if (g.in_layer != h.out_layer || G.size != 1 || G.stride != 1 || G.pad != 0 || G.cin != H.cout) continue;
         if (H.cout % 32 || H.cout > 64 || (G.cout != 16 && G.cout != 32 && G.cout != 64) || G.fused_into >= 0) continue;   // PW_MAX_K
         if (conv_band_supported(H.size, H.stride, H.pad, H.cin, H.win) && H.hout == H.hin) continue;   // band kernel: no pointwise epilogue
+        if (opt_narrow_cin && h.layer > 0 && conv_c16_supported(H.cin)) continue;                     // narrow family (conv_c16_f16s3.hip): no pointwise epilogue
         h.pw_guest = (int)i + 1; g.pw_host = (int)i;
     }
     // stem + layer 1 fusion candidate: launch 0 is the stem kernel, launch 1 the conv of layer 1 reading only it, nothing else reads layer 0
@@ -528,7 +530,7 @@ int Plan::check_split_supported(int mode) const {
     const char* pn = mode == 2 ? "f16" : "f16s3";
     if (opt_bn_batch_stats) { set_error("precision %s unsupported with bn_batch_stats (batch-statistics BatchNorm runs on the exact-fp32 kernels)", pn); return RTOD_E_CFG; }
     // precisions 1 and 2 keep every activation in the split f16 layout: every conv but the stem must read
-    // 32-channel K-chunks, every shortcut / head must ride a conv epilogue, concats must be zero-copy
+    // 32-channel K-chunks (or, with option narrow_cin, exactly 16 channels), every shortcut / head must ride a conv epilogue, concats must be zero-copy
     for (const auto& l : launches) {
         if (l.kind == LK_ADD || l.kind == LK_COPY || l.kind == LK_DECODE) {       // (max-pool and both upsamples have split-format kernels)
             set_error("precision %s unsupported for this cfg (layer %d needs a stand-alone %s kernel); use fp32", pn, l.layer,
@@ -537,7 +539,8 @@ int Plan::check_split_supported(int mode) const {
         }
         if (l.kind == LK_CONV && l.layer > 0) {
             const Layer& L = layers[l.layer];
-            if (L.cin % 32 || L.cout % 8 * (l.out_layer != -2)) {
+            const bool cin_ok = L.cin % 32 == 0 || (opt_narrow_cin && conv_c16_supported(L.cin));      // narrow family: conv_c16_f16s3.hip
+            if (!cin_ok || L.cout % 8 * (l.out_layer != -2)) {
                 set_error("precision %s unsupported for this cfg (layer %d: Cin=%d Cout=%d); use fp32", pn, l.layer, L.cin, L.cout);
                 return RTOD_E_CFG;
             }
@@ -557,6 +560,7 @@ void Plan::layout_weights() {
     for (auto& pc : convs) {
         const Layer& L = layers[pc.layer];
         pc.split = uses_split(L, pc.cin_p);
+        pc.narrow = false;
         const int64_t panel = (int64_t)pc.Npad * pc.Kpad;
         if (pc.stem && precision >= 1) {                              // split stem: [Cout][32] f16 hi, lo, inv_scale (its hi output is plain f16's format too)
             pc.split = true;
@@ -569,8 +573,9 @@ void Plan::layout_weights() {
             pc.w_off = packed_floats; packed_floats += panel / 2;       // f16 hi plane
             pc.wl_off = packed_floats; packed_floats += panel / 2;      // f16 lo plane
             pc.s_off = packed_floats; packed_floats += pc.Npad;
+            pc.narrow = opt_narrow_cin && conv_c16_supported(L.cin);
             pc.band = conv_band_supported(L.size, L.stride, L.pad, L.cin, L.win) && L.hout == L.hin &&
-                      !(L.fused_into >= 0 && layers[L.fused_into].type == LT_YOLO) && opt_band_kernel;
+                      !(L.fused_into >= 0 && layers[L.fused_into].type == LT_YOLO) && opt_band_kernel && !pc.narrow;
         } else {
             pc.w_off = packed_floats; packed_floats += panel;
             // deep small-grid layers (13x13 ... 52x52 stages, K >= 256): the K sum is formed in slices of 9 chunks (one 3x3 tap
@@ -759,7 +764,11 @@ int Plan::load_weights(const float* w, size_t n) {
                             const uint16_t l = f32_to_f16_rn(vs - f16_to_f32(h));
                             // K order of the split kernels: k = ((c/32)*k*k + tap)*32 + c%32 (channel chunk outer, tap inner);
                             // planes are K-chunk major, [chunk][Npad][32]: the rows of one stage are contiguous
-                            const int64_t idx = ((int64_t)((c / 32) * k * k + (ky * k + kx)) * pc.Npad + o) * 32 + (c % 32);
+                            // narrow layers (conv_c16_f16s3.hip): tap-major over the 16 channels, k = tap * 16 + c, so chunk j holds
+                            // taps 2j and 2j + 1 (the unused half of the last chunk of an odd tap count stays zero in both planes)
+                            const int tap = ky * k + kx;
+                            const int64_t idx = pc.narrow ? ((int64_t)(tap / 2) * pc.Npad + o) * 32 + (tap % 2) * 16 + c
+                                                          : ((int64_t)((c / 32) * k * k + tap) * pc.Npad + o) * 32 + (c % 32);
                             wh[idx] = h; wl[idx] = l;
                         }
             }
@@ -820,10 +829,12 @@ int Plan::f32_slice_mode(const Launch& l, int batch, int variant) const {
 
 // Plain-f16 plans (precision 2) run the families that have an f16 instance: the generic tiles (conv_igemm_f16s3.hip), the bandd
 // tiles (the band layers, and the wide slab tile of the other 3x3 stride-1 layers) and the 1x1 slab tiles (conv_pwd_f16s3.hip).
+// The narrow family (conv_c16_f16s3.hip) has both.
 // conv_band / ring / patch / the fused stem + layer 1 and the hosted pointwise epilogues are never candidates there.
+static bool c16_variant(int v) { return v >= C16_VARIANT_BASE && v < C16_VARIANT_BASE + C16_MODES; }
 static bool variant_has_f16(int v) {
     return (v >= 0 && v < HV_COUNT) || (v >= BAND_VARIANT_BASE + BAND_LDS_MODES && v < BAND_VARIANT_BASE + BAND_MODES) ||
-           (v >= PWD_VARIANT_BASE && v < PWD_VARIANT_BASE + PWD_MODES);
+           (v >= PWD_VARIANT_BASE && v < PWD_VARIANT_BASE + PWD_MODES) || c16_variant(v);
 }
 // band-family mode of a band layer: valid for its shape and, in plain-f16 plans, a bandd tile
 static bool band_mode_ok(int precision, int mode, const Layer& L) {
@@ -837,6 +848,11 @@ static int band_default_mode(int precision, const Layer& L) {
 
 int Plan::launch_split_variant(ConvArgs& a, const PackedConv& pc, int v, hipStream_t s) const {
     if (precision == 2 && !variant_has_f16(v)) { set_error("variant %d has no plain-f16 instance", v); return RTOD_E_STATE; }
+    if (pc.narrow != c16_variant(v)) {      // its own K order and packed weights: a narrow layer runs narrow tiles only, and no other layer does
+        set_error(pc.narrow ? "variant %d requested for a narrow (Cin = 16) layer" : "narrow variant %d requested for a layer without tap-major weights", v);
+        return RTOD_E_STATE;
+    }
+    if (pc.narrow) return launch_conv_c16_f16s3(a, v - C16_VARIANT_BASE, s);
     if (v >= PATCH_VARIANT_BASE) {
         if (pc.band) { set_error("patch variant requested for a band layer"); return RTOD_E_STATE; }
         return launch_conv_patch_f16s3(a, v - PATCH_VARIANT_BASE, s);
@@ -935,7 +951,9 @@ int Plan::tune_launch(size_t li, ConvArgs& a, int batch, hipStream_t s) {
     hipEvent_t e0, e1;
     RTOD_HIP(hipEventCreate(&e0)); RTOD_HIP(hipEventCreate(&e1));
     std::vector<int> cand;
-    if (convs[l.conv_slot].band) {                                                    // band layers: band tiles only (see rtod_internal.h)
+    if (convs[l.conv_slot].narrow) {                                                  // narrow layers: their own tiles only (the key carries cin)
+        for (int m = 0; m < C16_MODES; ++m) cand.push_back(C16_VARIANT_BASE + m);
+    } else if (convs[l.conv_slot].band) {                                             // band layers: band tiles only (see rtod_internal.h)
         for (int m = 0; m < BAND_MODES; ++m) if (band_mode_ok(precision, m, L)) cand.push_back(BAND_VARIANT_BASE + m);
     } else {
         for (int v = 0; v < HV_COUNT; ++v) {
@@ -1020,6 +1038,7 @@ int Plan::set_tiles(int batch, const int* variants, int count) {
         const bool band = convs[l.conv_slot].band, hosts_pw = l.pw_guest >= 0 && pw_active();
         bool ok;
         if (precision == 2 && !variant_has_f16(v)) ok = false;
+        else if (convs[l.conv_slot].narrow || c16_variant(v)) ok = convs[l.conv_slot].narrow && c16_variant(v);
         else if (band) ok = v >= BAND_VARIANT_BASE && v < BAND_VARIANT_BASE + BAND_MODES && band_mode_ok(precision, v - BAND_VARIANT_BASE, L);
         else if (v >= PATCH_VARIANT_BASE) ok = v < PATCH_VARIANT_BASE + PATCH_MODES && !hosts_pw && l.out_layer != -2 && L.act <= 1 && L.hout == L.hin &&
                                                conv_patch_supported(L.size, L.stride, L.pad, L.cin, L.cout) && conv_patch_mode_valid(v - PATCH_VARIANT_BASE, L.cin, L.cout);
@@ -1035,6 +1054,17 @@ int Plan::set_tiles(int batch, const int* variants, int count) {
 
 int Plan::variant_for(const Launch& l, int batch) const {
     const bool band = convs[l.conv_slot].band;
+    if (convs[l.conv_slot].narrow) {                         // a narrow layer always gets a narrow tile: forced, tuned, or the closed-form default
+        const Layer& NL = layers[l.layer];
+        if (opt_force_f16s3_variant >= 0) {
+            if (c16_variant(opt_force_f16s3_variant)) return opt_force_f16s3_variant;
+        } else {
+            auto nt = tuned.find(batch);
+            const size_t ni = &l - &launches[0];
+            if (nt != tuned.end() && ni < nt->second.size() && c16_variant(nt->second[ni])) return nt->second[ni];
+        }
+        return C16_VARIANT_BASE + conv_c16_default_mode(NL.cout, (int64_t)batch * NL.hout * NL.wout);
+    }
     if (opt_force_f16s3_variant >= 0) {                      // >= BAND_VARIANT_BASE: tile of the band layers, below: of the others
         const int v = opt_force_f16s3_variant;
         const Layer& FL = layers[l.layer];
@@ -1061,14 +1091,14 @@ int Plan::variant_for(const Launch& l, int batch) const {
 bool Plan::pw_active() const { return precision == 1 && opt_fuse_pointwise; }
 // 3x3 stride-1 layer too wide for the band family's LDS budget at three workgroups per CU but not for its one-buffer tile
 bool Plan::bandd_wide_candidate(const Launch& l, const Layer& L) const {
-    if (!opt_band_kernel || l.conv_slot < 0 || convs[l.conv_slot].band || !convs[l.conv_slot].split) return false;
+    if (!opt_band_kernel || l.conv_slot < 0 || convs[l.conv_slot].band || convs[l.conv_slot].narrow || !convs[l.conv_slot].split) return false;
     if (l.out_layer == -2 || (l.pw_guest >= 0 && pw_active())) return false;
     const PackedConv& pc = convs[l.conv_slot];
     return conv_bandd_wide_supported(L.size, L.stride, L.pad, pc.cin_p, L.win) && L.hout == L.hin && L.wout == L.win && pc.Npad % 128 == 0 && pc.K == pc.Kpad;
 }
 // plain 1x1 layer the slab tiles of conv_pwd_f16s3.hip can run: no fused head decode, no hosted pointwise conv, whole 64-channel slabs
 bool Plan::pwd_candidate(const Launch& l, const Layer& L) const {
-    if (!opt_pwd_kernel || l.conv_slot < 0 || convs[l.conv_slot].band || !convs[l.conv_slot].split) return false;
+    if (!opt_pwd_kernel || l.conv_slot < 0 || convs[l.conv_slot].band || convs[l.conv_slot].narrow || !convs[l.conv_slot].split) return false;
     if (l.out_layer == -2 || (l.pw_guest >= 0 && pw_active())) return false;
     return conv_pwd_supported(L.size, L.stride, L.pad, convs[l.conv_slot].cin_p) && L.hout == L.hin && L.wout == L.win;
 }

@@ -65,6 +65,7 @@ struct PackedConv {
     bool stem = false;                // conv_stem.hip: weights [28][Cout] fp32, or (split) [Cout][32] f16 hi / lo planes + inv_scale
     bool split = false;               // f16 hi/lo planes (conv_igemm_f16s3) instead of an fp32 panel
     bool band = false;                // eligible for conv_band_f16s3 (3x3 s1 p1, band fits LDS)
+    bool narrow = false;              // split, Cin == 16 (option narrow_cin): tap-major K order, runs on conv_c16_f16s3 only
     int64_t wl_off = 0, s_off = 0;    // split: w_off = hi plane, wl_off = lo plane (float units), s_off = inv_scale
     int64_t stats_off = -1;           // batch-statistics BatchNorm plans: this layer's [Npad] mean, [Npad] variance in Plan::d_bn_stats (doubles)
     int64_t bn_off = 0;               // batch-statistics BatchNorm plans: [Npad] beta, [Npad] gamma (the conv itself is packed unfolded)
@@ -109,6 +110,7 @@ struct Plan {
     bool opt_fuse_shortcut = true;    // shortcut in the producing conv's epilogue (else stand-alone add kernel)
     bool opt_fuse_decode = true;      // head decode in the head conv's epilogue (else stand-alone decode kernel)
     bool opt_zero_copy_concat = true; // route producers write straight into the concat buffer (else copy kernels)
+    bool opt_narrow_cin = false;      // precisions 1 / 2 accept convs after layer 0 that read exactly 16 channels (conv_c16_f16s3.hip)
     int opt_force_f16s3_variant = -1; // >= 0: tile variant for every split-f16 conv (>= BAND_VARIANT_BASE: band layers)
     int opt_force_f32_variant = -1;   // >= 0: tile variant for every exact-fp32 conv
     int32_t* overflow_flag = nullptr; // caller-owned device word: split-f16 producers OR 1 into it when a value saturates

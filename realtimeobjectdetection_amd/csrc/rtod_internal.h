@@ -233,6 +233,17 @@ const ConvVariantInfo& conv_patch_mode_info(int mode);
 int conv_patch_kernel_name(int mode, int epi, char* buf, size_t len);
 int launch_conv_patch_f16s3(const ConvArgs& a, int mode, hipStream_t s);
 
+// Convolutions that read 16 input channels (conv_c16_f16s3.hip; plan option "narrow_cin"): K order tap-major over 16 channels
+// (k = tap * 16 + c, a 32-wide K-chunk holds two taps), its own packed weights, so a narrow layer ALWAYS runs on this family and
+// no other layer does.  All tiles are bit-identical; f16s3 and plain-f16 instances, epilogues 0 / 1 / 2.
+constexpr int C16_MODES = 4;
+constexpr int C16_VARIANT_BASE = 140;      // variant ids in [140, 140 + C16_MODES): C16_VARIANT_BASE + mode
+constexpr bool conv_c16_supported(int cin) { return cin == 16; }
+const ConvVariantInfo& conv_c16_mode_info(int mode);
+int conv_c16_default_mode(int cout, int64_t m);                               // m = batch * Ho * Wo
+int conv_c16_kernel_name(int mode, int epi, char* buf, size_t len);
+int launch_conv_c16_f16s3(const ConvArgs& a, int mode, hipStream_t s);
+
 int launch_conv_stem(const float* x_nchw, const float* w, const float* bias, const View& out, int B, int H, int W,
                      int Ho, int Wo, int stride, int Cout, int leaky, hipStream_t s);
 int launch_conv_stem_split(const float* x_nchw, const _Float16* wh, const _Float16* wl, const float* inv_scale, const float* bias,

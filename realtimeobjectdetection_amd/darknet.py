@@ -309,8 +309,9 @@ class Darknet(nn.Module):
             if self._ovf is None or self._ovf.device != device:
                 self._ovf = torch.zeros(1, dtype=torch.int32, device=device)
             _ffi.check(lib.rtod_plan_set_overflow_flag(self._plan, C.c_void_p(self._ovf.data_ptr())))
-            # "auto": the split-f16 kernels when the cfg supports them (yolov3 does; cfgs with maxpool or
-            # Cin % 32 != 0 such as yolov3-tiny do not), else the exact-fp32 MFMA kernels.  Both are HIP paths.
+            # "auto": the split-f16 kernels when the cfg supports them (yolov3 does; a cfg with a conv after layer 0 whose
+            # Cin % 32 != 0 does not — yolov3-tiny's 16-channel layer 2 does with options = {"narrow_cin": 1}, already set
+            # above), else the exact-fp32 MFMA kernels.  Both are HIP paths.
             if self.precision == "fp32" or batch_bn:
                 self.active_precision = "fp32"
             elif self.precision == "f16":                        # opt-in only: "auto" never picks it

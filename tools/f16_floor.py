@@ -1,6 +1,6 @@
 """CPU floor of the plain-f16 precision mode (precision 2): the f16 emulation of tests/f16_emulation.py (f16 weights, f16 stored
-activations, float32 accumulation on torch CPU) against the fp32 oracle, yolov3 at 416 b2 and 608 b1 with the synthetic weights
-and frames of the golden fixtures.  Per materialised layer: max |emu - ref| / max(1, max |ref|) and rms-relative; on the output:
+activations, float32 accumulation on torch CPU) against the fp32 oracle, yolov3 at 416 b2 and 608 b1 and yolov3-tiny at 416 b1 and
+608 b2 with the synthetic weights and frames of the golden fixtures.  Per materialised layer: max |emu - ref| / max(1, max |ref|) and rms-relative; on the output:
 p99.9 / max of |emu - ref| / max(1, |ref|).  The GPU gates of tests/test_f16_gpu.py are derived from this file.
 Usage: python tools/f16_floor.py [profiles/f16_floor.json]"""
 import json
@@ -17,7 +17,7 @@ from realtimeobjectdetection_amd import cfgs, synth  # noqa: E402
 from oracle import darknet_ref as O  # noqa: E402
 from f16_emulation import F16Emulation, layer_distance, output_distance  # noqa: E402
 
-CASES = [("yolov3", 416, 2), ("yolov3", 608, 1)]
+CASES = [("yolov3", 416, 2), ("yolov3", 608, 1), ("yolov3-tiny", 416, 1), ("yolov3-tiny", 608, 2)]   # tiny: f16 needs option narrow_cin
 SEED = synth.FRAME_SEED   # the frames of tests/golden/fwd_* (synth.synth_frames default)
 
 
