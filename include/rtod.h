@@ -134,6 +134,14 @@ int rtod_plan_set_precision(rtod_plan* plan, int mode);
  *                       layer 2, any cfg with a 16-filter stem): they run on their own tile family (conv_c16_f16s3.hip, variant
  *                       ids 140 ..., K order tap-major over the 16 channels).  Other Cin % 32 != 0 (48, 80, ...) stay refused.
  *                       Plans without such a layer, and exact-fp32 plans, are unchanged by it
+ *   "stem_pool"         (default 0) precisions 1 / 2: a layer 0 that is 3x3 / stride 1 / pad 1 with Cin 3 and 16 filters (YOLOv3-tiny's;
+ *                       BatchNorm folded or absent, any activation) runs on the split-f16 stem of conv_stem16_f16s3.hip, which
+ *                       reads the NCHW input directly (no pack launch, no exact-fp32 conv).  Exact-fp32 plans and plans whose
+ *                       layer 0 does not match are unchanged by it.  Precision and option may be set in either order
+ *   "fuse_stem_pool"    (default 1) with "stem_pool": where layer 1 is a [maxpool] size 2 / stride 2 (not symmetric) that alone
+ *                       reads layer 0, layer 0's H and W are even and keep_all_layers is off, the pool runs in the stem's kernel:
+ *                       layer 0 is never stored (describe: "fused_into": 1), the pool's launch entry stays in the list and
+ *                       enqueues nothing.  Bit-identical to the stand-alone stem + max-pool kernel; 0: always stand-alone
  *   "force_f16s3_variant" / "force_f32_variant"   >= 0: one tile variant for every conv (tests, A/B runs)
  * Options that leave a cfg inexpressible in the split-f16 format return RTOD_E_CFG when precision is 1 or 2 (so does setting
  * "narrow_cin" back to 0 on a plan that needs it); the plan then stays as it was. */

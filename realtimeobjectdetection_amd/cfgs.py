@@ -153,6 +153,20 @@ def narrow_mini_cfg(height=64, width=64, classes=3) -> str:
     return "\n".join(L) + "\n"
 
 
+def stem_pool_mini_cfg(height=64, width=64, classes=3) -> str:
+    """Small test network for the 16-filter split-f16 stem with its fused max-pool (plan options narrow_cin + stem_pool): it
+    starts like YOLOv3-tiny (16-filter stem, 2x2 / stride-2 max-pool read by nothing else), then a Cin = 16 conv, an ordinary
+    32-channel conv and a head.  One head at stride 8; 40x56 is a legal rectangular shape (5x7 grid)."""
+    nout = 3 * (5 + classes)
+    L = _net(height, width)
+    L += _conv(16, 3, 1)                               # 0: 16-filter stem, 16 @ H x W
+    L += _maxpool(2, 2)                                # 1: 16 @ H/2 (fused into the stem's kernel)
+    L += _conv(32, 3, 2)                               # 2: Cin 16, 32 @ H/4
+    L += _conv(32, 3, 2)                               # 3: ordinary 32-channel layer, 32 @ H/8
+    L += _conv(nout, 1, 1, bn=False, act="linear") + _yolo((0, 1, 2), _ANCHORS_V3, 9, classes)   # 4, 5: head, fused decode
+    return "\n".join(L) + "\n"
+
+
 def v5_style_mini_cfg(height=128, width=128, classes=80, act="silu") -> str:
     """YOLOv5-style building blocks in the (extended) cfg grammar — NOT a reference network.  The reference's YOLOv5 path is a
     torch.hub fetch (detect.py:255-285) whose model source does not exist offline, so no YOLOv5 graph can be pinned; this cfg

@@ -319,6 +319,8 @@ int Plan::set_option(const char* name, int value) {
     else if (k == "fuse_decode") flag = &opt_fuse_decode;
     else if (k == "zero_copy_concat") flag = &opt_zero_copy_concat;
     else if (k == "narrow_cin") flag = &opt_narrow_cin;
+    else if (k == "stem_pool") flag = &opt_stem_pool;
+    else if (k == "fuse_stem_pool") flag = &opt_fuse_stem_pool;
     else if (k == "force_f16s3_variant") num = &opt_force_f16s3_variant;
     else if (k == "force_f32_variant") num = &opt_force_f32_variant;
     else { set_error("set_option: unknown option '%s'", name); return RTOD_E_ARG; }
@@ -330,6 +332,24 @@ int Plan::set_option(const char* name, int value) {
     if (rc) {                                                  // refuse: the plan stays as it was (the error message is kept)
         const std::string msg = last_error_string();
         if (flag) *flag = old_flag; else *num = old_num;
+        reset_planning();
+        (void)plan_buffers();
+        set_error("%s", msg.c_str());
+    }
+    return rc;
+}
+
+// The launch list depends on the precision (option stem_pool), so a precision change plans again: option-then-precision and
+// precision-then-option give the same plan.  Refused: the plan stays as it was.
+int Plan::set_precision(int mode) {
+    const int old = precision;
+    precision = mode;
+    reset_planning();
+    int rc = plan_buffers();
+    if (!rc && mode >= 1) rc = check_split_supported(mode);
+    if (rc) {
+        const std::string msg = last_error_string();
+        precision = old;
         reset_planning();
         (void)plan_buffers();
         set_error("%s", msg.c_str());
@@ -414,7 +434,10 @@ int Plan::plan_buffers() {
     // dedicated stem kernel (reads NCHW directly) when layer 0 is a plain 3x3 / pad 1 conv with 32 or 64 filters
     const bool use_stem = layers[0].size == 3 && layers[0].pad == 1 && layers[0].cin == 3 && layers[0].cout % 32 == 0 &&
                           layers[0].cout <= 64 && layers[0].fused_into < 0 && opt_stem_kernel && !(opt_bn_batch_stats && layers[0].bn);
-    if (!use_stem) { Launch l; l.kind = LK_PACK; l.layer = 0; launches.push_back(l); }
+    // option stem_pool (split-f16 / f16 plans): a 16-filter layer 0 on the split stem of conv_stem16_f16s3.hip, BatchNorm folded or absent
+    const bool use_stem16 = opt_stem_pool && precision >= 1 && layers[0].fused_into < 0 &&
+                            conv_stem16_supported(layers[0].size, layers[0].stride, layers[0].pad, layers[0].cin, layers[0].cout, layers[0].act);
+    if (!use_stem && !use_stem16) { Launch l; l.kind = LK_PACK; l.layer = 0; launches.push_back(l); }
     for (auto& L : layers) {
         const int i = L.index;
         Launch l; l.layer = i;
@@ -440,7 +463,7 @@ int Plan::plan_buffers() {
                     }
                 }
                 PackedConv pc; pc.layer = i; pc.cin_p = (i == 0) ? 4 : L.cin;
-                if (i == 0 && use_stem) { pc.stem = true; l.kind = LK_STEM; }
+                if (i == 0 && (use_stem || use_stem16)) { pc.stem = true; pc.stem16 = use_stem16; l.kind = LK_STEM; }
                 if (pc.cin_p % 4) { set_error("layer %d: %d input channels not a multiple of 4", i, pc.cin_p); return RTOD_E_CFG; }
                 pc.K = L.size * L.size * pc.cin_p; pc.Kpad = (pc.K + 31) / 32 * 32; pc.Npad = (L.cout + 127) / 128 * 128;
                 l.conv_slot = (int)convs.size();
@@ -497,6 +520,10 @@ int Plan::plan_buffers() {
         stem2_pattern = L0.bn && L1.bn && L0.act <= 1 && L1.act <= 1 && (launches[1].pw_guest < 0 || layers[launches[launches[1].pw_guest].layer].act <= 1) && conv_stem2_supported(L0.size, L0.stride, L0.pad, L0.cin, L0.cout, L1.size, L1.stride, L1.pad, L1.cout, pwc) &&
                         (pwc == 0 || pwc == 32);
     }
+    // 16-filter stem + max-pool fusion candidate: layer 1 is a plain 2x2 / stride-2 pool over an even map and the only reader of layer 0
+    stem_pool_pattern = use_stem16 && opt_fuse_stem_pool && n > 1 && layers[1].type == LT_MAXPOOL && layers[1].size == 2 && layers[1].stride == 2 &&
+                        layers[1].pool_pad == 0 && cons[0].size() == 1 && layers[0].hout % 2 == 0 && layers[0].wout % 2 == 0 &&
+                        launches.size() >= 2 && launches[0].kind == LK_STEM && launches[1].kind == LK_MAXPOOL && launches[1].layer == 1;
     // liveness per buffer over launch time (= layer index of the launch)
     const int NB = (int)bufs.size();
     for (auto& b : bufs) { b.first = 1 << 30; b.last = -1; }
@@ -505,7 +532,11 @@ int Plan::plan_buffers() {
     for (const auto& l : launches) {
         const int t = l.layer;
         if (l.kind == LK_PACK) { touch(input_buf, 0); continue; }
-        if (l.kind == LK_STEM) { touch(buf_of_layer(l.out_layer), t); continue; }
+        if (l.kind == LK_STEM) {
+            touch(buf_of_layer(l.out_layer), t);
+            if (stem_pool_pattern) touch(buf_of_layer(1), t);                            // written by the stem's kernel when fused
+            continue;
+        }
         touch(buf_of_layer(l.in_layer), t);
         if (l.in2_layer >= 0) touch(buf_of_layer(l.in2_layer), t);
         if (l.kind == LK_COPY) touch(l.out_buf, t);
@@ -1102,6 +1133,7 @@ bool Plan::pwd_candidate(const Launch& l, const Layer& L) const {
     if (l.out_layer == -2 || (l.pw_guest >= 0 && pw_active())) return false;
     return conv_pwd_supported(L.size, L.stride, L.pad, convs[l.conv_slot].cin_p) && L.hout == L.hin && L.wout == L.win;
 }
+bool Plan::stem_pool_fused() const { return precision >= 1 && stem_pool_pattern && !keep_all && convs[launches[0].conv_slot].stem16; }
 bool Plan::stem2_active() const { return precision == 1 && opt_stem2_kernel && stem2_pattern && !keep_all && convs[launches[0].conv_slot].split; }
 
 int Plan::choose_variant_f16s3(const Layer& L, int batch) const {
@@ -1176,7 +1208,13 @@ int Plan::forward(const float* x, int batch, float* out, hipStream_t s, float* l
                 const Layer& L = layers[l.layer];
                 const PackedConv& pc = convs[l.conv_slot];
                 const View o = view_of(l.out_layer);
-                if (pc.split)
+                if (pc.stem16) {                                        // 16 filters: stand-alone, or with layer 1's max-pool (writes layer 1's view)
+                    if (!pc.split) { set_error("forward: the 16-filter stem needs a split-f16 / f16 plan"); return RTOD_E_STATE; }
+                    const bool pool = stem_pool_fused();
+                    rc = launch_conv_stem16_f16s3(x, reinterpret_cast<const _Float16*>(d_weights + pc.w_off), reinterpret_cast<const _Float16*>(d_weights + pc.wl_off),
+                                                  d_weights + pc.s_off, d_weights + pc.b_off, pool ? view_of(1) : o, batch, height, width, L.act, pool ? 1 : 0, overflow_flag, s);
+                }
+                else if (pc.split)
                     rc = launch_conv_stem_split(x, reinterpret_cast<const _Float16*>(d_weights + pc.w_off), reinterpret_cast<const _Float16*>(d_weights + pc.wl_off),
                                                 d_weights + pc.s_off, d_weights + pc.b_off, o, batch, height, width, L.hout, L.wout,
                                                 L.stride, L.cout, L.act, overflow_flag, s);
@@ -1189,7 +1227,9 @@ int Plan::forward(const float* x, int batch, float* out, hipStream_t s, float* l
                 rc = layers[l.layer].nearest ? launch_upsample_nearest2x(view_of(l.in_layer), view_of(l.out_layer), batch, s)
                                              : launch_upsample2x(view_of(l.in_layer), view_of(l.out_layer), batch, s);
                 break;
-            case LK_MAXPOOL: rc = launch_maxpool(view_of(l.in_layer), view_of(l.out_layer), batch, layers[l.layer].size, layers[l.layer].stride, layers[l.layer].pool_pad, s); break;
+            case LK_MAXPOOL:
+                if (li == 1 && stem_pool_fused()) break;                // computed inside the stem's kernel
+                rc = launch_maxpool(view_of(l.in_layer), view_of(l.out_layer), batch, layers[l.layer].size, layers[l.layer].stride, layers[l.layer].pool_pad, s); break;
             case LK_ADD: rc = launch_add(view_of(l.in_layer), view_of(l.in2_layer), view_of(l.out_layer), batch, s); break;
             case LK_COPY: {
                 const View in = view_of(l.in_layer);
@@ -1229,8 +1269,11 @@ void Plan::fill_launch_info(int idx, rtod_launch_info* o, int batch) const {
         case LK_STEM:
             if (stem2_active()) { o->bytes_per_frame = 0; break; }                   // accounted on layer 1's launch
             o->flops_per_frame = 2ll * L.hout * L.wout * L.cout * L.cin * L.size * L.size;
-            o->bytes_per_frame = in_b + out_b;
+            o->bytes_per_frame = in_b + (stem_pool_fused() ? out_b / 4 : out_b);  // fused 2x2 pool: the pooled map is what is written
             o->weight_bytes = ((int64_t)L.cout * L.cin * L.size * L.size + L.cout) * 4;
+            break;
+        case LK_MAXPOOL:
+            o->bytes_per_frame = (idx == 1 && stem_pool_fused()) ? 0 : in_b + out_b;   // fused: accounted on the stem's launch
             break;
         case LK_CONV:
             if (l.pw_host >= 0 && pw_active()) { o->bytes_per_frame = 0; break; }    // accounted on the host conv's launch
@@ -1276,7 +1319,7 @@ std::string Plan::describe() const {
         os << "],\"anchors\":[";
         for (size_t a = 0; a < L.anchors.size(); ++a) os << (a ? "," : "") << "[" << L.anchors[a].first << "," << L.anchors[a].second << "]";
         os << "],\"classes\":" << L.classes << ",\"row_offset\":" << L.row_offset << ",\"rows\":" << L.rows << ",\"w_off\":" << L.w_off
-           << ",\"fused_into\":" << ((i == 0 && stem2_active()) ? 1 : L.fused_into) << ",\"fused_away\":" << (L.fused_away ? "true" : "false") << ",\"alias_of\":" << L.alias_of
+           << ",\"fused_into\":" << ((i == 0 && (stem2_active() || stem_pool_fused())) ? 1 : L.fused_into) << ",\"fused_away\":" << (L.fused_away ? "true" : "false") << ",\"alias_of\":" << L.alias_of
            << ",\"buf\":" << L.buf << ",\"coff\":" << L.coff << "}";
     }
     os << "],\"bufs\":[";

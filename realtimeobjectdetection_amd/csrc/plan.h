@@ -62,6 +62,7 @@ struct PackedConv {
     int layer = 0;
     int cin_p = 0, K = 0, Kpad = 0, Npad = 0;
     int64_t w_off = 0, b_off = 0;     // float offsets into the device weight arena
+    bool stem16 = false;              // stem on conv_stem16_f16s3.hip (option stem_pool: 16 filters, split packing of `stem`)
     bool stem = false;                // conv_stem.hip: weights [28][Cout] fp32, or (split) [Cout][32] f16 hi / lo planes + inv_scale
     bool split = false;               // f16 hi/lo planes (conv_igemm_f16s3) instead of an fp32 panel
     bool band = false;                // eligible for conv_band_f16s3 (3x3 s1 p1, band fits LDS)
@@ -111,6 +112,8 @@ struct Plan {
     bool opt_fuse_decode = true;      // head decode in the head conv's epilogue (else stand-alone decode kernel)
     bool opt_zero_copy_concat = true; // route producers write straight into the concat buffer (else copy kernels)
     bool opt_narrow_cin = false;      // precisions 1 / 2 accept convs after layer 0 that read exactly 16 channels (conv_c16_f16s3.hip)
+    bool opt_stem_pool = false;       // precisions 1 / 2: a 3x3 / stride 1 / 16-filter layer 0 runs the split-f16 stem of conv_stem16_f16s3.hip (no pack launch)
+    bool opt_fuse_stem_pool = true;   // ... with the 2x2 / stride-2 max-pool that follows it in the same kernel where the plan allows it (off: A/B and tests)
     int opt_force_f16s3_variant = -1; // >= 0: tile variant for every split-f16 conv (>= BAND_VARIANT_BASE: band layers)
     int opt_force_f32_variant = -1;   // >= 0: tile variant for every exact-fp32 conv
     int32_t* overflow_flag = nullptr; // caller-owned device word: split-f16 producers OR 1 into it when a value saturates
@@ -127,6 +130,7 @@ struct Plan {
     int load_weights(const float* w, size_t n);
     int forward(const float* x, int batch, float* out, hipStream_t s, float* launch_ms, bool tune = false);
     int set_option(const char* name, int value);
+    int set_precision(int mode);              // re-plans: the launch list depends on the precision (option stem_pool)
     int set_tiles(int batch, const int* variants, int count);   // install a tile table (validated per launch)
     void reset_planning();
     View view_of(int layer) const;            // resolves aliases; base == nullptr if not materialised
@@ -144,6 +148,8 @@ struct Plan {
     bool bandd_wide_candidate(const Launch& l, const Layer& L) const;                     // fused pointwise convs in use (precision 1, option fuse_pointwise)
     bool stem2_pattern = false;                 // launches 0 / 1 are a stem and the stride-2 conv conv_stem2_f16s3 fuses (set by plan_buffers)
     bool stem2_active() const;                  // ... and the plan runs them fused (split-f16 precision, option stem2_kernel)
+    bool stem_pool_pattern = false;             // launch 0 is the 16-filter stem and launch 1 the 2x2 / stride-2 max-pool that alone reads it (set by plan_buffers)
+    bool stem_pool_fused() const;               // ... and the plan runs them as one kernel (not under keep_all_layers)
     std::map<int, std::vector<int>> tuned;     // batch -> per-launch split-f16 tile variant (-1: heuristic)
     std::string describe() const;
     void fill_launch_info(int idx, rtod_launch_info* o, int batch) const;

@@ -248,6 +248,11 @@ int launch_conv_stem(const float* x_nchw, const float* w, const float* bias, con
                      int Ho, int Wo, int stride, int Cout, int leaky, hipStream_t s);
 int launch_conv_stem_split(const float* x_nchw, const _Float16* wh, const _Float16* wl, const float* inv_scale, const float* bias,
                            const View& out, int B, int H, int W, int Ho, int Wo, int stride, int Cout, int leaky, int32_t* ovf, hipStream_t s);
+// 16-filter stem in the split-f16 arithmetic, stand-alone or with the following 2x2 / stride-2 max-pool fused (conv_stem16_f16s3.hip;
+// plan option "stem_pool").  pool == 1: `out` is the pool's view (H/2 x W/2); bit-identical to pool == 0 followed by launch_maxpool.
+bool conv_stem16_supported(int ksize, int stride, int pad, int cin, int cout, int act);
+int launch_conv_stem16_f16s3(const float* x_nchw, const _Float16* wh, const _Float16* wl, const float* inv_scale, const float* bias,
+                             const View& out, int B, int H, int W, int act, int pool, int32_t* ovf, hipStream_t s);
 int launch_prep_image(const unsigned char* img, int h, int w, int bgr, int inp_dim, float* out, hipStream_t s);
 int launch_prep_frames(const unsigned char* frames, int batch, int h, int w, int bgr, int out_h, int out_w, float* out, hipStream_t s);
 int launch_pack_input(const float* x_nchw, int B, int C, int H, int W, float* out_nhwc, int Cp, hipStream_t s);

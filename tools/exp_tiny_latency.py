@@ -2,7 +2,8 @@
 """Latency datapoint for SURVEY.md §8(f) row 3: YOLOv3-tiny 416x416 batch 1 (BASELINE configs[0]), forward + write_results, one
 stream, HIP-event timed, then the per-launch table of one forward_timed.  Default: precision "auto" without options, which runs
 tiny on the exact-fp32 kernels; --narrow-cin sets the plan option narrow_cin, with which f16s3 / f16 (and auto -> f16s3) run it.
-python tools/exp_tiny_latency.py [--batch 1] [--res 416] [--precision {auto,fp32,f16s3,f16}] [--narrow-cin]"""
+--option NAME=VALUE sets any further plan option (repeatable), e.g. --narrow-cin --option stem_pool=1.
+python tools/exp_tiny_latency.py [--batch 1] [--res 416] [--precision {auto,fp32,f16s3,f16}] [--narrow-cin] [--option NAME=VALUE ...]"""
 import argparse, os, sys, tempfile
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -15,6 +16,7 @@ ap = argparse.ArgumentParser(); ap.add_argument("--batch", type=int, default=1);
 ap.add_argument("--iters", type=int, default=200)
 ap.add_argument("--precision", choices=["auto", "fp32", "f16s3", "f16"], default="auto")
 ap.add_argument("--narrow-cin", action="store_true", help="plan option narrow_cin: the Cin = 16 layer on conv_c16_f16s3 tiles (f16s3 / f16 need it)")
+ap.add_argument("--option", action="append", default=[], metavar="NAME=VALUE", help="plan option (rtod_plan_set_option), repeatable")
 args = ap.parse_args()
 cfg_text = cfgs.yolov3_tiny_cfg()
 ir = build_ir(parse_cfg_text(cfg_text), args.res)
@@ -24,6 +26,7 @@ with tempfile.TemporaryDirectory() as d:
     m.precision = args.precision
     if args.narrow_cin:
         m.options = {"narrow_cin": 1}
+    m.options.update({kv.split("=")[0]: int(kv.split("=")[1]) for kv in args.option})
     m.load_weights(synth.write_weights_file(os.path.join(d, "t.weights"), synth.synth_weights(ir)))
 x = torch.from_numpy(synth.synth_frames(args.batch, args.res)).cuda()
 print('stage: eager', flush=True)
@@ -57,7 +60,7 @@ for _ in range(args.iters):
 lat = (time.perf_counter() - t0) / args.iters * 1e3
 print({"graph_ms_per_batch": round(ms_graph, 4), "graph_frames_per_s": round(args.batch * 1000.0 / ms_graph, 1),
        "graph_latency_with_host_readback_ms": round(lat, 4), "launches": m._info.n_launches})
-print({"net": "yolov3-tiny", "res": args.res, "batch": args.batch, "precision": m.active_precision, "narrow_cin": int(args.narrow_cin), "ms_per_batch": round(ms, 4),
+print({"net": "yolov3-tiny", "res": args.res, "batch": args.batch, "precision": m.active_precision, "options": dict(m.options), "ms_per_batch": round(ms, 4),
        "frames_per_s": round(args.batch * 1000.0 / ms, 1), "gflop_per_frame": round(ir.conv_flops / 1e9, 3)})
 # per-launch table of one forward (a HIP-event pair around every launch: each time includes the launch gap it ends)
 from realtimeobjectdetection_amd import _ffi

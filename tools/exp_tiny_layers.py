@@ -1,17 +1,25 @@
 #!/usr/bin/env python
-"""Per-launch table of YOLOv3-tiny (exact-fp32 kernels):  python tools/exp_tiny_layers.py [batch] [res]"""
-import os, sys, tempfile
+"""Per-launch table of YOLOv3-tiny:  python tools/exp_tiny_layers.py [batch] [res] [--precision {auto,fp32,f16s3,f16}] [--option NAME=VALUE ...]
+Default: precision "auto" without options, which runs tiny on the exact-fp32 kernels.  --option sets a plan option
+(rtod_plan_set_option), e.g. --precision f16s3 --option narrow_cin=1 --option stem_pool=1."""
+import argparse, os, sys, tempfile
 sys.path.insert(0, os.getcwd())
 import numpy as np, torch
 from realtimeobjectdetection_amd import cfgs, synth, _ffi
 from realtimeobjectdetection_amd.cfg import parse_cfg_text, build_ir
 from realtimeobjectdetection_amd.darknet import Darknet
-B = int(sys.argv[1]) if len(sys.argv) > 1 else 1
-res = int(sys.argv[2]) if len(sys.argv) > 2 else 416
+ap = argparse.ArgumentParser()
+ap.add_argument("batch", nargs="?", type=int, default=1); ap.add_argument("res", nargs="?", type=int, default=416)
+ap.add_argument("--precision", choices=["auto", "fp32", "f16s3", "f16"], default="auto")
+ap.add_argument("--option", action="append", default=[], metavar="NAME=VALUE", help="plan option, repeatable")
+args = ap.parse_args()
+B, res = args.batch, args.res
 text = cfgs.yolov3_tiny_cfg(); ir = build_ir(parse_cfg_text(text), res)
 d = tempfile.mkdtemp()
 m = Darknet(cfgs.write_cfg(os.path.join(d, "t.cfg"), text), True).eval()
 m.net_info["height"] = res
+m.precision = args.precision
+m.options = {kv.split("=")[0]: int(kv.split("=")[1]) for kv in args.option}
 m.load_weight_stream(synth.synth_weights(ir))
 x = torch.from_numpy(synth.synth_frames(B, res)).cuda()
 with torch.no_grad():
@@ -24,4 +32,4 @@ tot /= 20
 for li, t in zip(m.launch_infos(), tot):
     print("L%-3d kind %d k%d s%d %4d->%4d @%3d  %.4f ms  %s" % (li.layer, li.kind, li.ksize, li.stride, li.cin, li.cout, li.hout, t,
           _ffi.lib().rtod_conv_variant_name(li.variant).decode() if li.kind == 0 else ""))
-print("sum %.4f ms" % tot.sum())
+print("sum %.4f ms  (precision %s, options %s)" % (tot.sum(), m.active_precision, m.options))
