@@ -129,7 +129,19 @@ int rtod_plan_set_precision(rtod_plan* plan, int mode);
  *   "stem2_kernel"      layers 0-2 of Darknet-53 in one kernel (conv_stem2_f16s3.hip, bit-identical); 0: stand-alone kernels
  *   "bn_batch_stats"    (default 0) exact-fp32 plans: BatchNorm on batch statistics instead of the folded running statistics
  *   "k_slices"          exact-fp32 plans: deep small-grid layers summed in K slices (conv_igemm_f32.hip); 0: one chain
- *   "k_slice_workgroups" ... one workgroup per slice when the grid is small; 0: always inside the workgroup (same bits)
+ *   "k_slice_workgroups" ... one workgroup per slice when the grid is small; 0: always inside the workgroup (same bits).
+ *                       Governs the K-sliced split-f16 tiles of "k_slices_split" in the same way
+ *   "k_slices_split"    (default 0) precisions 1 / 2, for single-frame latency: a conv is SLICED when its shape alone says so — after
+ *                       layer 0, Cin % 32 == 0 (not a "narrow_cin" layer), no fused head decode, neither host nor guest of a
+ *                       fused-pointwise candidate pair nor layer 1 of the fused stem pattern, hout * wout <= 2704 and at least 8
+ *                       K-chunks of 32.  Its K sum is formed in slices of 9 / 4 / 2 chunks (32+ / 16+ / 8+ chunks; the last slice
+ *                       may be shorter) in the generic K order, slice sums added in ascending order in fp32.  A sliced layer always
+ *                       runs the tile family of conv_ks_f16s3.hip (variant ids 150 + 2 * tile + schedule; schedule 0 walks the
+ *                       slices inside the workgroup, schedule 1 gives every (tile, slice) its own workgroup and reduces the panels:
+ *                       same bits), at every batch size, and is no band layer; rtod_plan_describe reports "k_slices": S on it.
+ *                       The summation order differs from the default plan's, so results differ from it in the last bits.
+ *                       At large batches the sliced 3x3 layers lose the band kernels: keep a second plan for throughput.
+ *                       Exact-fp32 plans accept the option and ignore it; plans without it are unchanged.  Either order with precision
  *   "narrow_cin"        (default 0) precisions 1 / 2 accept convs after layer 0 that read exactly 16 channels (YOLOv3-tiny's
  *                       layer 2, any cfg with a 16-filter stem): they run on their own tile family (conv_c16_f16s3.hip, variant
  *                       ids 140 ..., K order tap-major over the 16 channels).  Other Cin % 32 != 0 (48, 80, ...) stay refused.

@@ -167,6 +167,27 @@ def stem_pool_mini_cfg(height=64, width=64, classes=3) -> str:
     return "\n".join(L) + "\n"
 
 
+def kslice_mini_cfg(height=64, width=64, classes=3) -> str:
+    """Small test network for the K-sliced split-f16 convolutions (plan option k_slices_split).  Every map is at most 52x52 at the
+    test shapes, so the rule slices each conv with at least 8 K-chunks of 32 that has no fused head decode: slices of 2 chunks
+    (8 ... 15 chunks), 4 (16 ... 31) or 9 (32 and more).  One head at stride 8; 40x56 is a legal rectangular shape (5x7 grid)."""
+    nout = 3 * (5 + classes)
+    L = _net(height, width)
+    L += _conv(32, 3, 1)                               # 0: stem
+    L += _conv(32, 1, 1)                               # 1: 1 K-chunk: not sliced, stays on the generic tiles
+    L += _conv(64, 3, 2)                               # 2: 3x3 s2, 9 chunks -> 5 slices of 2, the last of one chunk; 64 @ H/2
+    L += _conv(64, 3, 1)                               # 3: 3x3 s1, 18 chunks -> 5 slices of 4, the last of 2 (a band layer without the option)
+    L += _conv(64, 3, 1) + _shortcut(-3)               # 4, 5: 3x3 s1 with the shortcut (layer 2) in its epilogue (a band layer without the option)
+    L += _conv(256, 3, 2)                              # 6: 18 chunks, 256 @ H/4
+    L += _conv(96, 1, 1, act="linear")                 # 7: 1x1, Cin 256: 8 chunks -> 4 slices of 2; linear; 96 filters (no multiple of a
+                                                       #    64- or 128-wide tile); writes channel 0 of route 8's buffer
+    L += _route(-1, -2)                                # 8: layers 7 and 6, 352 @ H/4, zero-copy
+    L += _conv(128, 3, 1)                              # 9: Cin 352: 99 chunks -> 11 slices of 9
+    L += _conv(256, 3, 2)                              # 10: 36 chunks -> 4 slices of 9; 256 @ H/8
+    L += _conv(nout, 1, 1, bn=False, act="linear") + _yolo((0, 1, 2), _ANCHORS_V3, 9, classes)   # 11, 12: 8 chunks, fused decode: not sliced
+    return "\n".join(L) + "\n"
+
+
 def v5_style_mini_cfg(height=128, width=128, classes=80, act="silu") -> str:
     """YOLOv5-style building blocks in the (extended) cfg grammar — NOT a reference network.  The reference's YOLOv5 path is a
     torch.hub fetch (detect.py:255-285) whose model source does not exist offline, so no YOLOv5 graph can be pinned; this cfg

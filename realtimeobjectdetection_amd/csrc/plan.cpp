@@ -312,6 +312,7 @@ int Plan::set_option(const char* name, int value) {
         flag = &opt_bn_batch_stats;
     }
     else if (k == "k_slice_workgroups") flag = &opt_k_slice_workgroups;
+    else if (k == "k_slices_split") flag = &opt_k_slices_split;
     else if (k == "patch_kernel") flag = &opt_patch_kernel;
     else if (k == "stem_kernel") flag = &opt_stem_kernel;
     else if (k == "band_kernel") flag = &opt_band_kernel;
@@ -581,8 +582,21 @@ int Plan::check_split_supported(int mode) const {
     return RTOD_OK;
 }
 
+// Option k_slices_split: slice length, in K-chunks of 32, of a split conv (0: not sliced).  The one place that holds the
+// thresholds and lengths; it sees the layer's shape alone (never the batch), so a frame's bits do not depend on the batch it
+// rides in.  The starting rule of the exact-fp32 kernel (pc.slice_chunks below): grids up to 52x52, K >= 256, slices of 9 / 4 / 2.
+static int split_slice_chunks(const Layer& L, int kpad) {
+    const int nkc = kpad / 32;
+    if (L.hout * L.wout > 2704 || nkc < 8) return 0;
+    return nkc >= 32 ? 9 : nkc >= 16 ? 4 : 2;
+}
+
 void Plan::layout_weights() {
     packed_floats = 0;
+    // sliced layers (option k_slices_split): split convs that are neither the stem nor narrow, carry no fused head decode, are
+    // neither host nor guest of a fused-pointwise candidate pair nor layer 1 of the fused stem pattern, and that the rule names
+    std::vector<const Launch*> launch_of(convs.size(), nullptr);
+    for (const auto& l : launches) if ((l.kind == LK_CONV || l.kind == LK_STEM) && l.conv_slot >= 0) launch_of[l.conv_slot] = &l;
     bn_stats_doubles = 0;
     for (auto& pc : convs) {
         pc.stats_off = -1;
@@ -605,8 +619,13 @@ void Plan::layout_weights() {
             pc.wl_off = packed_floats; packed_floats += panel / 2;      // f16 lo plane
             pc.s_off = packed_floats; packed_floats += pc.Npad;
             pc.narrow = opt_narrow_cin && conv_c16_supported(L.cin);
+            const Launch* ll = launch_of[&pc - &convs[0]];
+            pc.ks_chunks = 0;
+            if (opt_k_slices_split && ll && !pc.narrow && ll->out_layer != -2 && ll->pw_guest < 0 && ll->pw_host < 0 &&
+                !(stem2_pattern && pc.layer == 1) && pc.K == pc.Kpad && L.cin % 32 == 0)
+                pc.ks_chunks = split_slice_chunks(L, pc.Kpad);
             pc.band = conv_band_supported(L.size, L.stride, L.pad, L.cin, L.win) && L.hout == L.hin &&
-                      !(L.fused_into >= 0 && layers[L.fused_into].type == LT_YOLO) && opt_band_kernel && !pc.narrow;
+                      !(L.fused_into >= 0 && layers[L.fused_into].type == LT_YOLO) && opt_band_kernel && !pc.narrow && pc.ks_chunks == 0;
         } else {
             pc.w_off = packed_floats; packed_floats += panel;
             // deep small-grid layers (13x13 ... 52x52 stages, K >= 256): the K sum is formed in slices of 9 chunks (one 3x3 tap
@@ -823,9 +842,9 @@ int Plan::load_weights(const float* w, size_t n) {
     }
     if (!d_scratch) {
         bool any = false;
-        for (const auto& pc : convs) any = any || (!pc.split && !pc.stem && pc.slice_chunks > 0);
+        for (const auto& pc : convs) any = any || (!pc.split && !pc.stem && pc.slice_chunks > 0) || (pc.split && pc.ks_chunks > 0);
         if (any) {
-            scratch_floats = 8ll << 20;                                   // 32 MB: L2 / Infinity-Cache resident; larger panels run the in-workgroup schedule
+            scratch_floats = KS_SCRATCH_FLOATS;                                   // 32 MB: L2 / Infinity-Cache resident; larger panels run the in-workgroup schedule
             RTOD_HIP(hipMalloc((void**)&d_scratch, sizeof(float) * (size_t)scratch_floats));
         }
     }
@@ -863,8 +882,9 @@ int Plan::f32_slice_mode(const Launch& l, int batch, int variant) const {
 // The narrow family (conv_c16_f16s3.hip) has both.
 // conv_band / ring / patch / the fused stem + layer 1 and the hosted pointwise epilogues are never candidates there.
 static bool c16_variant(int v) { return v >= C16_VARIANT_BASE && v < C16_VARIANT_BASE + C16_MODES; }
+static bool ks_variant(int v) { return v >= KS_VARIANT_BASE && v < KS_VARIANT_BASE + KS_MODES; }
 static bool variant_has_f16(int v) {
-    return (v >= 0 && v < HV_COUNT) || (v >= BAND_VARIANT_BASE + BAND_LDS_MODES && v < BAND_VARIANT_BASE + BAND_MODES) ||
+    return ks_variant(v) || (v >= 0 && v < HV_COUNT) || (v >= BAND_VARIANT_BASE + BAND_LDS_MODES && v < BAND_VARIANT_BASE + BAND_MODES) ||
            (v >= PWD_VARIANT_BASE && v < PWD_VARIANT_BASE + PWD_MODES) || c16_variant(v);
 }
 // band-family mode of a band layer: valid for its shape and, in plain-f16 plans, a bandd tile
@@ -884,6 +904,16 @@ int Plan::launch_split_variant(ConvArgs& a, const PackedConv& pc, int v, hipStre
         return RTOD_E_STATE;
     }
     if (pc.narrow) return launch_conv_c16_f16s3(a, v - C16_VARIANT_BASE, s);
+    if ((pc.ks_chunks > 0) != ks_variant(v)) {   // its own summation order: a sliced layer runs the K-sliced tiles only, and no other layer does
+        set_error(pc.ks_chunks > 0 ? "variant %d requested for a K-sliced layer" : "K-sliced variant %d requested for a layer that is not sliced", v);
+        return RTOD_E_STATE;
+    }
+    if (pc.ks_chunks > 0) {
+        a.slice_chunks = pc.ks_chunks;
+        a.partial = nullptr; a.partial_floats = 0;
+        if ((v - KS_VARIANT_BASE) & 1) { a.partial = d_scratch; a.partial_floats = scratch_floats; }     // one workgroup per (tile, slice)
+        return launch_conv_ks_f16s3(a, v - KS_VARIANT_BASE, s);
+    }
     if (v >= PATCH_VARIANT_BASE) {
         if (pc.band) { set_error("patch variant requested for a band layer"); return RTOD_E_STATE; }
         return launch_conv_patch_f16s3(a, v - PATCH_VARIANT_BASE, s);
@@ -968,7 +998,7 @@ int Plan::tune_launch(size_t li, ConvArgs& a, int batch, hipStream_t s) {
     // two layers with the same output shape but another input extent or padding are other problems, e.g. across rectangular plans)
     const std::vector<int> key = {L.cin, L.cout, L.size, L.stride, L.hout, L.wout, l.in2_layer >= 0, l.out_layer == -2, pw ? a.pw_cout : 0,
                                   convs[l.conv_slot].band ? 1 : 0, opt_ring_kernel ? 1 : 0, opt_patch_kernel ? 1 : 0, opt_pwd_kernel ? 1 : 0, L.act,
-                                  precision, L.hin, L.win, L.pad};
+                                  precision, L.hin, L.win, L.pad, convs[l.conv_slot].ks_chunks, opt_k_slice_workgroups ? 1 : 0};
     auto it = tune_cache.find(key);
     if (it != tune_cache.end()) { tuning[li] = it->second; return RTOD_OK; }
     // process-wide memo (device, batch, shape): a second plan of the same network (bench.py keeps two batches in flight)
@@ -984,6 +1014,9 @@ int Plan::tune_launch(size_t li, ConvArgs& a, int batch, hipStream_t s) {
     std::vector<int> cand;
     if (convs[l.conv_slot].narrow) {                                                  // narrow layers: their own tiles only (the key carries cin)
         for (int m = 0; m < C16_MODES; ++m) cand.push_back(C16_VARIANT_BASE + m);
+    } else if (convs[l.conv_slot].ks_chunks > 0) {                                    // sliced layers: every tile x schedule of their family (bit-identical)
+        const bool b_ok = opt_k_slice_workgroups && ks_sched_b_fits(l, batch);
+        for (int m = 0; m < KS_MODES; ++m) if (!(m & 1) || b_ok) cand.push_back(KS_VARIANT_BASE + m);
     } else if (convs[l.conv_slot].band) {                                             // band layers: band tiles only (see rtod_internal.h)
         for (int m = 0; m < BAND_MODES; ++m) if (band_mode_ok(precision, m, L)) cand.push_back(BAND_VARIANT_BASE + m);
     } else {
@@ -1070,6 +1103,13 @@ int Plan::set_tiles(int batch, const int* variants, int count) {
         bool ok;
         if (precision == 2 && !variant_has_f16(v)) ok = false;
         else if (convs[l.conv_slot].narrow || c16_variant(v)) ok = convs[l.conv_slot].narrow && c16_variant(v);
+        else if (convs[l.conv_slot].ks_chunks > 0 || ks_variant(v)) {
+            ok = convs[l.conv_slot].ks_chunks > 0 && ks_variant(v);
+            if (ok && ((v - KS_VARIANT_BASE) & 1) && !ks_sched_b_fits(l, batch)) {
+                set_error("set_tiles: variant %d (one workgroup per K slice) of launch %d (layer %d) needs more slice scratch than the plan has at batch %d", v, i, l.layer, batch);
+                return RTOD_E_ARG;
+            }
+        }
         else if (band) ok = v >= BAND_VARIANT_BASE && v < BAND_VARIANT_BASE + BAND_MODES && band_mode_ok(precision, v - BAND_VARIANT_BASE, L);
         else if (v >= PATCH_VARIANT_BASE) ok = v < PATCH_VARIANT_BASE + PATCH_MODES && !hosts_pw && l.out_layer != -2 && L.act <= 1 && L.hout == L.hin &&
                                                conv_patch_supported(L.size, L.stride, L.pad, L.cin, L.cout) && conv_patch_mode_valid(v - PATCH_VARIANT_BASE, L.cin, L.cout);
@@ -1096,6 +1136,7 @@ int Plan::variant_for(const Launch& l, int batch) const {
         }
         return C16_VARIANT_BASE + conv_c16_default_mode(NL.cout, (int64_t)batch * NL.hout * NL.wout);
     }
+    if (convs[l.conv_slot].ks_chunks > 0) return ks_variant_for(l, batch);      // a sliced layer always gets a tile of its family
     if (opt_force_f16s3_variant >= 0) {                      // >= BAND_VARIANT_BASE: tile of the band layers, below: of the others
         const int v = opt_force_f16s3_variant;
         const Layer& FL = layers[l.layer];
@@ -1116,6 +1157,37 @@ int Plan::variant_for(const Launch& l, int batch) const {
     const int v = choose_variant_f16s3(layers[l.layer], batch);
     // host of a fused pointwise conv: one N tile must cover every output channel
     if (l.pw_guest >= 0 && pw_active() && conv_f16s3_variant_info(v).bn < layers[l.layer].cout) return HV_128x128_8W;
+    return v;
+}
+
+// Sliced split layers (option k_slices_split, conv_ks_f16s3.hip).  The slice panels [S][M][Npad] of schedule B fit the scratch:
+bool Plan::ks_sched_b_fits(const Launch& l, int batch) const {
+    const PackedConv& pc = convs[l.conv_slot];
+    if (pc.ks_chunks <= 0) return false;
+    const Layer& L = layers[l.layer];
+    const int64_t S = (pc.Kpad / 32 + pc.ks_chunks - 1) / pc.ks_chunks;
+    return S * batch * L.hout * L.wout * pc.Npad <= KS_SCRATCH_FLOATS;
+}
+// Tile + schedule: forced (a family id), tuned, or the default — the 64x64 tile, and like f32_slice_mode one workgroup per
+// (tile, slice) while the tile grid alone leaves the chip idle and the panels fit, else the slices inside the workgroup.
+// Option k_slice_workgroups = 0 and slice panels larger than the scratch (allocated with the weights of every plan that has a
+// sliced layer) turn every choice into schedule A of the same tile (the same bits).
+int Plan::ks_variant_for(const Launch& l, int batch) const {
+    const Layer& L = layers[l.layer];
+    const bool b_ok = opt_k_slice_workgroups && ks_sched_b_fits(l, batch);
+    int v = -1;
+    if (opt_force_f16s3_variant >= 0) { if (ks_variant(opt_force_f16s3_variant)) v = opt_force_f16s3_variant; }
+    else {
+        auto it = tuned.find(batch);
+        const size_t idx = &l - &launches[0];
+        if (it != tuned.end() && idx < it->second.size() && ks_variant(it->second[idx])) v = it->second[idx];
+    }
+    if (v < 0) {
+        const int64_t M = (int64_t)batch * L.hout * L.wout;
+        const int64_t tiles = ((M + 63) / 64) * ((L.cout + 63) / 64);
+        v = KS_VARIANT_BASE + (tiles < 512 ? 1 : 0);
+    }
+    if (!b_ok) v = KS_VARIANT_BASE + ((v - KS_VARIANT_BASE) & ~1);
     return v;
 }
 
@@ -1320,7 +1392,11 @@ std::string Plan::describe() const {
         for (size_t a = 0; a < L.anchors.size(); ++a) os << (a ? "," : "") << "[" << L.anchors[a].first << "," << L.anchors[a].second << "]";
         os << "],\"classes\":" << L.classes << ",\"row_offset\":" << L.row_offset << ",\"rows\":" << L.rows << ",\"w_off\":" << L.w_off
            << ",\"fused_into\":" << ((i == 0 && (stem2_active() || stem_pool_fused())) ? 1 : L.fused_into) << ",\"fused_away\":" << (L.fused_away ? "true" : "false") << ",\"alias_of\":" << L.alias_of
-           << ",\"buf\":" << L.buf << ",\"coff\":" << L.coff << "}";
+           << ",\"buf\":" << L.buf << ",\"coff\":" << L.coff;
+        if (L.type == LT_CONV)                                                       // sliced layers only (option k_slices_split)
+            for (const auto& pc : convs)
+                if (pc.layer == L.index && pc.split && pc.ks_chunks > 0) os << ",\"k_slices\":" << (pc.Kpad / 32 + pc.ks_chunks - 1) / pc.ks_chunks;
+        os << "}";
     }
     os << "],\"bufs\":[";
     for (size_t i = 0; i < bufs.size(); ++i) {

@@ -71,6 +71,7 @@ struct PackedConv {
     int64_t stats_off = -1;           // batch-statistics BatchNorm plans: this layer's [Npad] mean, [Npad] variance in Plan::d_bn_stats (doubles)
     int64_t bn_off = 0;               // batch-statistics BatchNorm plans: [Npad] beta, [Npad] gamma (the conv itself is packed unfolded)
     int slice_chunks = 0;             // exact-fp32 panels: K summed in slices of this many 32-wide chunks (0: one chain), conv_igemm_f32.hip
+    int ks_chunks = 0;                // split, option k_slices_split: sliced layer (slices of this many K-chunks), runs on conv_ks_f16s3 only; 0: not sliced
 };
 
 struct Plan {
@@ -90,7 +91,7 @@ struct Plan {
     int64_t bn_stats_doubles = 0;
     double* d_bn_partial = nullptr;   // per-range partial sums of the two-stage statistics kernel
     int64_t bn_partial_count = 0;
-    float* d_scratch = nullptr;       // exact-fp32 plans: slice panels of the one-workgroup-per-K-slice schedule
+    float* d_scratch = nullptr;       // slice panels of the one-workgroup-per-K-slice schedules (exact-fp32 plans; split plans with a sliced layer)
     int64_t scratch_floats = 0;
     bool weights_loaded = false;
     int train_decode = 0;
@@ -103,7 +104,8 @@ struct Plan {
     bool opt_band_kernel = true;      // LDS-band kernel for the 3x3 stride-1 layers it supports
     bool opt_bn_batch_stats = false;  // exact-fp32 plans: BatchNorm on the statistics of the batch (what the reference runs: no .eval()), not folded
     bool opt_k_slices = true;         // exact-fp32 kernels: deep small-grid layers summed in K slices (own workgroups when the grid is small)
-    bool opt_k_slice_workgroups = true;   // ... (off: always the in-workgroup schedule — same bits; A/B and tests)
+    bool opt_k_slice_workgroups = true;   // ... (off: always the in-workgroup schedule — same bits; A/B and tests).  Governs conv_ks_f16s3 too
+    bool opt_k_slices_split = false;  // precisions 1 / 2: deep small-grid convs summed in K slices on conv_ks_f16s3.hip (single-frame latency; opt-in)
     bool opt_stem2_kernel = true;     // stem + layer 1 (+ hosted 1x1) in one kernel when the cfg starts like Darknet-53 (split-f16 plans)
     bool opt_patch_kernel = true;     // 2-D patch tiles among the autotune candidates of the wide 3x3 stride-1 layers
     bool opt_ring_kernel = true;      // persistent LDS-DMA ring tiles among the autotune candidates of the other layers
@@ -143,6 +145,8 @@ struct Plan {
     int launch_split_variant(ConvArgs& a, const PackedConv& pc, int v, hipStream_t s) const;
     int variant_for(const Launch& l, int batch) const;
     int f32_slice_mode(const Launch& l, int batch, int variant) const;   // 0 plain, 1 slices inside the workgroup, 2 one workgroup per slice
+    bool ks_sched_b_fits(const Launch& l, int batch) const;              // sliced split layer: the slice panels of this batch fit the scratch
+    int ks_variant_for(const Launch& l, int batch) const;                // sliced split layer: forced, tuned or default tile + schedule
     bool pw_active() const;
     bool pwd_candidate(const Launch& l, const Layer& L) const;
     bool bandd_wide_candidate(const Launch& l, const Layer& L) const;                     // fused pointwise convs in use (precision 1, option fuse_pointwise)

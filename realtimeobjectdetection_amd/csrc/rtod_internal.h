@@ -100,7 +100,7 @@ struct ConvArgs {
     int xcd_by_n = 0;                           // split kernels: workgroup -> XCD by output-channel tile instead of by pixel tile (see launch_band)
     int out_split = 0;                          // exact-fp32 kernel only: write the output in the split format
     int f16 = 0;                                // split kernels: 1 = plain-f16 instance (precision mode 2: hi planes only, one MFMA per fragment pair)
-    // exact-fp32 kernel only: K slices (conv_igemm_f32.hip).  slice_chunks > 0: the K sum is formed slice by slice (a property of
+    // exact-fp32 kernel and the K-sliced split family (conv_ks_f16s3.hip): K slices (conv_igemm_f32.hip).  slice_chunks > 0: the K sum is formed slice by slice (a property of
     // the layer); partial != nullptr: one workgroup per slice, raw sums to this scratch ([slices][M][Npad] floats), then a reduction
     int slice_chunks = 0;
     float* partial = nullptr;
@@ -243,6 +243,20 @@ const ConvVariantInfo& conv_c16_mode_info(int mode);
 int conv_c16_default_mode(int cout, int64_t m);                               // m = batch * Ho * Wo
 int conv_c16_kernel_name(int mode, int epi, char* buf, size_t len);
 int launch_conv_c16_f16s3(const ConvArgs& a, int mode, hipStream_t s);
+
+// K-sliced generic tiles (conv_ks_f16s3.hip; plan option "k_slices_split"): the K sum of a deep small-grid layer formed in slices
+// of ConvArgs::slice_chunks K-chunks, added in ascending order.  That summation order differs from every other family's, so a
+// sliced layer ALWAYS runs on this family and no other layer does.  Mode = 2 * tile + schedule: schedule 0 walks the slices inside
+// the workgroup, schedule 1 gives every (tile, slice) its own workgroup (raw sums to ConvArgs::partial, then a reduction kernel,
+// both under one launch entry).  All modes are bit-identical; f16s3 and plain-f16 instances, epilogues 0 / 1.
+constexpr int KS_TILES = 3;
+constexpr int KS_MODES = 2 * KS_TILES;
+constexpr int KS_VARIANT_BASE = 150;       // variant ids in [150, 150 + KS_MODES): KS_VARIANT_BASE + mode
+constexpr int64_t KS_SCRATCH_FLOATS = 8ll << 20;   // Plan::d_scratch: 32 MB of slice panels (L2 / Infinity-Cache resident)
+const ConvVariantInfo& conv_ks_mode_info(int mode);
+int conv_ks_slices(const ConvArgs& a);                                        // K slices of a launch of this family
+int conv_ks_kernel_name(int mode, int epi, char* buf, size_t len);
+int launch_conv_ks_f16s3(const ConvArgs& a, int mode, hipStream_t s);
 
 int launch_conv_stem(const float* x_nchw, const float* w, const float* bias, const View& out, int B, int H, int W,
                      int Ho, int Wo, int stride, int Cout, int leaky, hipStream_t s);
