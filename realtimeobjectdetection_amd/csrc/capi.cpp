@@ -105,14 +105,8 @@ int rtod_plan_describe(const rtod_plan* plan, char* buf, size_t len, size_t* nee
 }
 
 const char* rtod_conv_variant_name(int variant) {
-    if (variant >= 100 + KS_VARIANT_BASE && variant < 100 + KS_VARIANT_BASE + KS_MODES) return conv_ks_mode_info(variant - 100 - KS_VARIANT_BASE).name;
-    if (variant >= 100 + C16_VARIANT_BASE && variant < 100 + C16_VARIANT_BASE + C16_MODES) return conv_c16_mode_info(variant - 100 - C16_VARIANT_BASE).name;
     if (variant == 100 + STEM2_VARIANT) return "conv_stem2_f16s3<2 x 4x16, stem + 3x3 s2 + 1x1>";
-    if (variant >= 100 + PATCH_VARIANT_BASE && variant < 100 + PATCH_VARIANT_BASE + PATCH_MODES) return conv_patch_mode_info(variant - 100 - PATCH_VARIANT_BASE).name;
-    if (variant >= 100 + PWD_VARIANT_BASE && variant < 100 + PWD_VARIANT_BASE + PWD_MODES) return conv_pwd_mode_info(variant - 100 - PWD_VARIANT_BASE).name;
-    if (variant >= 100 + RING_VARIANT_BASE && variant < 100 + RING_VARIANT_BASE + RING_MODES) return conv_ring_mode_info(variant - 100 - RING_VARIANT_BASE).name;
-    if (variant >= 100 + BAND_VARIANT_BASE && variant < 100 + BAND_VARIANT_BASE + BAND_MODES) return conv_band_mode_info(variant - 100 - BAND_VARIANT_BASE).name;
-    if (variant >= 100 && variant < 100 + HV_COUNT) return conv_f16s3_variant_info(variant - 100).name;
+    if (variant >= 100) { const TileRef t = family_of(variant - 100); return t ? t.fam->info(t.mode).name : ""; }   // split-f16 tiles: 100 + id
     if (variant < 0 || variant % 10 >= CV_COUNT || variant / 10 > 2) return "";
     static const char* const kSliced[2][CV_COUNT] = {
         {"conv_igemm_f32<128x128,w64x64,k-slices>", "conv_igemm_f32<128x64,w64x32,k-slices>", "conv_igemm_f32<64x64,w32x32,k-slices>", "conv_igemm_f32<128x32,w32x32,k-slices>"},
@@ -124,13 +118,7 @@ const char* rtod_conv_variant_name(int variant) {
 int rtod_conv_kernel_name(int variant, int epilogue, char* buf, size_t len) {
     if (!buf || len == 0) { set_error("conv_kernel_name: null buffer"); return RTOD_E_ARG; }
     int n = -1;
-    if (variant >= 100 + KS_VARIANT_BASE) n = conv_ks_kernel_name(variant - 100 - KS_VARIANT_BASE, epilogue, buf, len);
-    else if (variant >= 100 + C16_VARIANT_BASE) n = conv_c16_kernel_name(variant - 100 - C16_VARIANT_BASE, epilogue, buf, len);
-    else if (variant >= 100 + PATCH_VARIANT_BASE) n = conv_patch_kernel_name(variant - 100 - PATCH_VARIANT_BASE, epilogue, buf, len);
-    else if (variant >= 100 + PWD_VARIANT_BASE) n = conv_pwd_kernel_name(variant - 100 - PWD_VARIANT_BASE, epilogue, buf, len);
-    else if (variant >= 100 + RING_VARIANT_BASE) n = conv_ring_kernel_name(variant - 100 - RING_VARIANT_BASE, epilogue, buf, len);
-    else if (variant >= 100 + BAND_VARIANT_BASE) n = conv_band_kernel_name(variant - 100 - BAND_VARIANT_BASE, epilogue, buf, len);
-    else if (variant >= 100) n = conv_f16s3_kernel_name(variant - 100, epilogue, buf, len);
+    if (variant >= 100) { const TileRef t = family_of(variant - 100); if (t) n = t.fam->kernel_name(t.mode, epilogue, buf, len); }
     else n = conv_f32_kernel_name(variant, buf, len);
     if (n < 0 || (size_t)n >= len) { set_error("conv_kernel_name: unknown variant %d or buffer too small", variant); return RTOD_E_ARG; }
     return RTOD_OK;

@@ -327,12 +327,18 @@ int Plan::set_option(const char* name, int value) {
     else { set_error("set_option: unknown option '%s'", name); return RTOD_E_ARG; }
     const bool old_flag = flag ? *flag : false; const int old_num = num ? *num : 0;
     if (flag) *flag = value != 0; else *num = value;
+    return replan_or([&] { if (flag) *flag = old_flag; else *num = old_num; });
+}
+
+// Plans again after a change of an option or the precision.  Refused: `restore` undoes the change, the plan is rebuilt as it
+// was and the error message is kept.
+int Plan::replan_or(const std::function<void()>& restore) {
     reset_planning();
     int rc = plan_buffers();
     if (!rc && precision >= 1) rc = check_split_supported(precision);
-    if (rc) {                                                  // refuse: the plan stays as it was (the error message is kept)
+    if (rc) {
         const std::string msg = last_error_string();
-        if (flag) *flag = old_flag; else *num = old_num;
+        restore();
         reset_planning();
         (void)plan_buffers();
         set_error("%s", msg.c_str());
@@ -345,17 +351,22 @@ int Plan::set_option(const char* name, int value) {
 int Plan::set_precision(int mode) {
     const int old = precision;
     precision = mode;
-    reset_planning();
-    int rc = plan_buffers();
-    if (!rc && mode >= 1) rc = check_split_supported(mode);
-    if (rc) {
-        const std::string msg = last_error_string();
-        precision = old;
-        reset_planning();
-        (void)plan_buffers();
-        set_error("%s", msg.c_str());
+    return replan_or([&] { precision = old; });
+}
+
+// Decode arguments of yolo layer Y: for the head conv it is fused into, or for the stand-alone decode launch
+DecodeArgs Plan::decode_args(const Layer& Y) const {
+    DecodeArgs d; d.enabled = 1; d.GH = Y.hout; d.GW = Y.wout; d.attrs = 5 + Y.classes; d.n_anchors = (int)Y.anchors.size();
+    const int stride = height / Y.hout;                 // == width / Y.wout (resolve_shapes)
+    d.stride = (float)stride;
+    for (size_t a = 0; a < Y.anchors.size(); ++a) {
+        d.aw[a] = (float)((double)Y.anchors[a].first / (double)stride);     // Python float divide -> FloatTensor (util.py:213-216)
+        d.ah[a] = (float)((double)Y.anchors[a].second / (double)stride);
+        if (Y.decode_v5) { d.aw[a] = (float)Y.anchors[a].first; d.ah[a] = (float)Y.anchors[a].second; }   // pixels
     }
-    return rc;
+    d.v5 = Y.decode_v5 ? 1 : 0;
+    d.img_stride = (int64_t)total_rows * attrs; d.head_off = (int64_t)Y.row_offset * attrs;
+    return d;
 }
 
 int Plan::plan_buffers() {
@@ -448,20 +459,7 @@ int Plan::plan_buffers() {
                 if (L.fused_into >= 0) {
                     const Layer& F = layers[L.fused_into];
                     if (F.type == LT_SHORTCUT) { l.out_layer = F.index; l.in2_layer = F.srcs[1]; }
-                    else {
-                        l.out_layer = -2;
-                        DecodeArgs d; d.enabled = 1; d.GH = F.hout; d.GW = F.wout; d.attrs = 5 + F.classes; d.n_anchors = (int)F.anchors.size();
-                        const int stride = height / F.hout;                 // == width / F.wout (resolve_shapes)
-                        d.stride = (float)stride;
-                        for (size_t a = 0; a < F.anchors.size(); ++a) {
-                            d.aw[a] = (float)((double)F.anchors[a].first / (double)stride);     // Python float divide -> FloatTensor (util.py:213-216)
-                            d.ah[a] = (float)((double)F.anchors[a].second / (double)stride);
-                            if (F.decode_v5) { d.aw[a] = (float)F.anchors[a].first; d.ah[a] = (float)F.anchors[a].second; }   // pixels
-                        }
-                        d.v5 = F.decode_v5 ? 1 : 0;
-                        d.img_stride = (int64_t)total_rows * attrs; d.head_off = (int64_t)F.row_offset * attrs;
-                        l.dec = d;
-                    }
+                    else { l.out_layer = -2; l.dec = decode_args(F); }
                 }
                 PackedConv pc; pc.layer = i; pc.cin_p = (i == 0) ? 4 : L.cin;
                 if (i == 0 && (use_stem || use_stem16)) { pc.stem = true; pc.stem16 = use_stem16; l.kind = LK_STEM; }
@@ -482,18 +480,7 @@ int Plan::plan_buffers() {
                 break;
             case LT_YOLO:
                 if (!L.fused_away) {
-                    l.kind = LK_DECODE; l.in_layer = i - 1; l.out_layer = -2;
-                    DecodeArgs d; d.enabled = 1; d.GH = L.hout; d.GW = L.wout; d.attrs = 5 + L.classes; d.n_anchors = (int)L.anchors.size();
-                    const int stride = height / L.hout;                     // == width / L.wout (resolve_shapes)
-                    d.stride = (float)stride;
-                    for (size_t a = 0; a < L.anchors.size(); ++a) {
-                        d.aw[a] = (float)((double)L.anchors[a].first / (double)stride);
-                        d.ah[a] = (float)((double)L.anchors[a].second / (double)stride);
-                        if (L.decode_v5) { d.aw[a] = (float)L.anchors[a].first; d.ah[a] = (float)L.anchors[a].second; }
-                    }
-                    d.v5 = L.decode_v5 ? 1 : 0;
-                    d.img_stride = (int64_t)total_rows * attrs; d.head_off = (int64_t)L.row_offset * attrs;
-                    l.dec = d;
+                    l.kind = LK_DECODE; l.in_layer = i - 1; l.out_layer = -2; l.dec = decode_args(L);
                     launches.push_back(l);
                 }
                 break;
@@ -582,9 +569,12 @@ int Plan::check_split_supported(int mode) const {
     return RTOD_OK;
 }
 
-// Option k_slices_split: slice length, in K-chunks of 32, of a split conv (0: not sliced).  The one place that holds the
+// Slice length, in K-chunks of 32, of a conv whose K sum is formed in slices (0: not sliced): the exact-fp32 panels (option
+// k_slices) and the split convs of option k_slices_split; the callers apply their option.  The one place that holds the
 // thresholds and lengths; it sees the layer's shape alone (never the batch), so a frame's bits do not depend on the batch it
-// rides in.  The starting rule of the exact-fp32 kernel (pc.slice_chunks below): grids up to 52x52, K >= 256, slices of 9 / 4 / 2.
+// rides in.  Deep small-grid layers (13x13 ... 52x52 stages, K >= 256): slices of 9 chunks (one 3x3 tap row of 32 channels; the
+// value only has to be fixed per layer), so that a small batch can give every slice its own workgroup; shorter sums (K = 256 ...
+// 992: the head and route 1x1 convs of those stages) use slices of 4 / 2.
 static int split_slice_chunks(const Layer& L, int kpad) {
     const int nkc = kpad / 32;
     if (L.hout * L.wout > 2704 || nkc < 8) return 0;
@@ -628,12 +618,7 @@ void Plan::layout_weights() {
                       !(L.fused_into >= 0 && layers[L.fused_into].type == LT_YOLO) && opt_band_kernel && !pc.narrow && pc.ks_chunks == 0;
         } else {
             pc.w_off = packed_floats; packed_floats += panel;
-            // deep small-grid layers (13x13 ... 52x52 stages, K >= 256): the K sum is formed in slices of 9 chunks (one 3x3 tap
-            // row of 32 channels ... the value only has to be fixed per layer), so that a small batch can give every slice
-            // its own workgroup.  Decided by the layer's shape alone: the same bits at every batch size.
-            // Shorter sums (K = 256 ... 992: the head and route 1x1 convs of those stages) use shorter slices.
-            const int nkc = pc.Kpad / 32;
-            pc.slice_chunks = (!opt_k_slices || L.hout * L.wout > 2704 || nkc < 8) ? 0 : nkc >= 32 ? 9 : nkc >= 16 ? 4 : 2;
+            pc.slice_chunks = opt_k_slices ? split_slice_chunks(L, pc.Kpad) : 0;
         }
         pc.b_off = packed_floats; packed_floats += pc.Npad;
         if (opt_bn_batch_stats && L.bn) { pc.bn_off = packed_floats; packed_floats += 2 * (int64_t)pc.Npad; }
@@ -877,61 +862,122 @@ int Plan::f32_slice_mode(const Launch& l, int batch, int variant) const {
     return (opt_k_slice_workgroups && d_scratch && tiles < 512 && S * M * pc.Npad <= scratch_floats) ? 2 : 1;
 }
 
-// Plain-f16 plans (precision 2) run the families that have an f16 instance: the generic tiles (conv_igemm_f16s3.hip), the bandd
-// tiles (the band layers, and the wide slab tile of the other 3x3 stride-1 layers) and the 1x1 slab tiles (conv_pwd_f16s3.hip).
-// The narrow family (conv_c16_f16s3.hip) has both.
-// conv_band / ring / patch / the fused stem + layer 1 and the hosted pointwise epilogues are never candidates there.
-static bool c16_variant(int v) { return v >= C16_VARIANT_BASE && v < C16_VARIANT_BASE + C16_MODES; }
-static bool ks_variant(int v) { return v >= KS_VARIANT_BASE && v < KS_VARIANT_BASE + KS_MODES; }
-static bool variant_has_f16(int v) {
-    return ks_variant(v) || (v >= 0 && v < HV_COUNT) || (v >= BAND_VARIANT_BASE + BAND_LDS_MODES && v < BAND_VARIANT_BASE + BAND_MODES) ||
-           (v >= PWD_VARIANT_BASE && v < PWD_VARIANT_BASE + PWD_MODES) || c16_variant(v);
-}
-// band-family mode of a band layer: valid for its shape and, in plain-f16 plans, a bandd tile
-static bool band_mode_ok(int precision, int mode, const Layer& L) {
-    return conv_band_mode_valid(mode, L.cin, L.hin, L.win) && (precision != 2 || mode >= BAND_LDS_MODES);
-}
-static int band_default_mode(int precision, const Layer& L) {
-    if (precision != 2) return conv_band_default_mode(L.cin, L.hin, L.win);
-    for (int m = BAND_LDS_MODES; m < BAND_MODES; ++m) if (conv_band_mode_valid(m, L.cin, L.hin, L.win)) return m;
-    return BAND_LDS_MODES;
+// ------------------------------------------------------------------------------------- split-f16 tiles
+// Which tile a split-f16 conv launch runs is decided here and nowhere else: tile_legal (may it?), default_tile (the closed-form
+// choice), variant_for (forced / tuned / default), tile_candidates (what autotune times); ids resolve through family_of
+// (split_tiles.cpp).
+//
+// May launch `l` run tile `v` and give this layer's defined bits?  Does not depend on the batch; a one-workgroup-per-slice tile
+// whose panels do not fit the scratch is legal here: variant_for runs schedule A of the same tile (same bits), set_tiles refuses it.
+// Plain-f16 plans (precision 2) run the tiles that have an f16 instance (the f16 column of the family table): the generic, bandd
+// (band layers, and the wide tile of the other 3x3 stride-1 layers), 1x1 slab, narrow and K-sliced tiles; never conv_band / ring /
+// patch, and no hosted pointwise epilogue (pw_active).
+bool Plan::tile_legal(const Launch& l, int /*batch*/, int v) const {
+    const TileRef t = family_of(v);
+    if (!t || l.kind != LK_CONV || l.conv_slot < 0 || !convs[l.conv_slot].split) return false;
+    const PackedConv& pc = convs[l.conv_slot];
+    const Layer& L = layers[l.layer];
+    if (precision == 2 && !t.f16()) return false;
+    // own K order / packed weights / summation order: narrow, sliced and band layers run their family only, and no other layer does
+    if (pc.narrow || t.is(TF_C16)) return pc.narrow && t.is(TF_C16);
+    if (pc.ks_chunks > 0 || t.is(TF_KS)) return pc.ks_chunks > 0 && t.is(TF_KS);
+    if (pc.band) return t.is(TF_BAND) && conv_band_mode_valid(t.mode, L.cin, L.hin, L.win);
+    // the other layers: generic K order.  plain = no fused head decode, no hosted pointwise conv
+    const bool hosts_pw = l.pw_guest >= 0 && pw_active(), plain = l.out_layer != -2 && !hosts_pw, same_map = L.hout == L.hin && L.wout == L.win;
+    switch (t.fam->id) {
+        case TF_GENERIC: return !(hosts_pw && t.fam->info(t.mode).bn < L.cout);        // fused pointwise: one N tile must cover every output channel
+        // the one-buffer bandd tile: 3x3 stride-1 layers too wide for the band family's LDS budget at three workgroups per CU
+        case TF_BAND: return t.bandd_wide() && opt_band_kernel && plain && same_map && pc.Npad % 128 == 0 && pc.K == pc.Kpad &&
+                             conv_bandd_wide_supported(L.size, L.stride, L.pad, pc.cin_p, L.win);
+        // (SiLU layers: only the kernels with the LDS-transposed epilogue carry that activation: generic, band and slab tiles)
+        case TF_RING: return !hosts_pw && L.act <= 1;
+        case TF_PWD: return opt_pwd_kernel && plain && same_map && conv_pwd_supported(L.size, L.stride, L.pad, pc.cin_p);   // whole 64-channel slabs
+        case TF_PATCH: return plain && L.act <= 1 && L.hout == L.hin && conv_patch_supported(L.size, L.stride, L.pad, L.cin, L.cout) &&
+                              conv_patch_mode_valid(t.mode, L.cin, L.cout);
+    }
+    return false;
 }
 
+// The closed-form choice (no forced id, no tuned entry, or an illegal one)
+int Plan::default_tile(const Launch& l, int batch) const {
+    const PackedConv& pc = convs[l.conv_slot];
+    const Layer& L = layers[l.layer];
+    const int64_t M = (int64_t)batch * L.hout * L.wout;
+    if (pc.narrow) return tile_id(TF_C16, conv_c16_default_mode(L.cout, M));
+    // sliced: the 64x64 tile, and like f32_slice_mode one workgroup per (tile, slice) while the tile grid alone leaves the chip idle
+    if (pc.ks_chunks > 0) return tile_id(TF_KS, ((M + 63) / 64) * ((L.cout + 63) / 64) < 512 ? 1 : 0);
+    if (pc.band) {
+        if (precision != 2) return tile_id(TF_BAND, conv_band_default_mode(L.cin, L.hin, L.win));
+        const TileFamily& B = tile_family(TF_BAND);                                       // plain f16: the first legal (bandd) mode
+        for (int m = 0; m < B.modes; ++m) if (tile_legal(l, batch, B.base + m)) return B.base + m;
+        return B.base + B.f16_from;
+    }
+    const int64_t gn = (L.cout + 127) / 128;
+    const int g = L.cout <= 64 ? HV_128x64 : ((M + 127) / 128) * gn >= 512 ? HV_128x128 : ((M + 63) / 64) * gn >= 512 ? HV_64x128 : HV_64x64;
+    return tile_legal(l, batch, g) ? g : HV_128x128_8W;                                   // (host of a fused pointwise conv: one N tile)
+}
+
+// Forced id (the tuned table is then ignored), else the tuned entry of this batch; an illegal one silently gives the default.
+// Option k_slice_workgroups = 0 and slice panels larger than the scratch (allocated with the weights of every plan that has a
+// sliced layer) turn a one-workgroup-per-slice tile into schedule A of the same tile (the same bits).
+int Plan::variant_for(const Launch& l, int batch) const {
+    int want = opt_force_f16s3_variant;
+    if (want < 0) {
+        auto it = tuned.find(batch);
+        const size_t idx = &l - &launches[0];
+        if (it != tuned.end() && idx < it->second.size()) want = it->second[idx];
+    }
+    int v = want >= 0 && tile_legal(l, batch, want) ? want : default_tile(l, batch);
+    if (family_of(v).ks_sched_b() && !(opt_k_slice_workgroups && ks_sched_b_fits(l, batch))) --v;
+    return v;
+}
+
+// What autotune times for a launch, in screening order: the legal tiles minus those far wider than the layer, the families
+// switched off as candidates (options ring_kernel / patch_kernel) and the one-workgroup-per-slice tiles that cannot run as such.
+// Narrow, sliced and band layers: their own family in mode order.
+std::vector<int> Plan::tile_candidates(const Launch& l, int batch) const {
+    static const int kOrder[TF_COUNT] = {TF_GENERIC, TF_PATCH, TF_BAND, TF_PWD, TF_RING, TF_C16, TF_KS};
+    const int cout = layers[l.layer].cout;
+    const bool ks_b = opt_k_slice_workgroups && ks_sched_b_fits(l, batch);
+    std::vector<int> cand;
+    for (int f : kOrder) {
+        if ((f == TF_RING && !opt_ring_kernel) || (f == TF_PATCH && !opt_patch_kernel)) continue;
+        const TileFamily& F = tile_family(f);
+        for (int m = 0; m < F.modes; ++m) {
+            const int bn = F.info(m).bn;
+            const bool too_wide = f == TF_GENERIC || f == TF_RING ? bn > 64 && bn > 2 * ((cout + 63) / 64 * 64)
+                                : f == TF_PATCH ? bn > 64 && bn > cout
+                                : f == TF_PWD ? bn > 128 && bn > (cout + 127) / 128 * 128 : false;
+            if (too_wide || (family_of(F.base + m).ks_sched_b() && !ks_b) || !tile_legal(l, batch, F.base + m)) continue;
+            cand.push_back(F.base + m);
+        }
+    }
+    return cand;
+}
+
+// Refuses what would compute wrong results (tile_legal's family rules; the caller went through variant_for or tile_candidates)
 int Plan::launch_split_variant(ConvArgs& a, const PackedConv& pc, int v, hipStream_t s) const {
-    if (precision == 2 && !variant_has_f16(v)) { set_error("variant %d has no plain-f16 instance", v); return RTOD_E_STATE; }
-    if (pc.narrow != c16_variant(v)) {      // its own K order and packed weights: a narrow layer runs narrow tiles only, and no other layer does
+    const TileRef t = family_of(v);
+    if (!t) { set_error("variant %d is no split-f16 tile", v); return RTOD_E_STATE; }
+    if (precision == 2 && !t.f16()) { set_error("variant %d has no plain-f16 instance", v); return RTOD_E_STATE; }
+    if (pc.narrow != t.is(TF_C16)) {
         set_error(pc.narrow ? "variant %d requested for a narrow (Cin = 16) layer" : "narrow variant %d requested for a layer without tap-major weights", v);
         return RTOD_E_STATE;
     }
-    if (pc.narrow) return launch_conv_c16_f16s3(a, v - C16_VARIANT_BASE, s);
-    if ((pc.ks_chunks > 0) != ks_variant(v)) {   // its own summation order: a sliced layer runs the K-sliced tiles only, and no other layer does
+    if ((pc.ks_chunks > 0) != t.is(TF_KS)) {
         set_error(pc.ks_chunks > 0 ? "variant %d requested for a K-sliced layer" : "K-sliced variant %d requested for a layer that is not sliced", v);
         return RTOD_E_STATE;
     }
-    if (pc.ks_chunks > 0) {
+    if (pc.band != t.is(TF_BAND) && !(t.bandd_wide() && !pc.band)) {
+        set_error(pc.band ? "variant %d requested for a band layer" : "band variant %d requested for a layer without band weights", v);
+        return RTOD_E_STATE;
+    }
+    if (t.is(TF_KS)) {
         a.slice_chunks = pc.ks_chunks;
         a.partial = nullptr; a.partial_floats = 0;
-        if ((v - KS_VARIANT_BASE) & 1) { a.partial = d_scratch; a.partial_floats = scratch_floats; }     // one workgroup per (tile, slice)
-        return launch_conv_ks_f16s3(a, v - KS_VARIANT_BASE, s);
+        if (t.ks_sched_b()) { a.partial = d_scratch; a.partial_floats = scratch_floats; }     // one workgroup per (tile, slice)
     }
-    if (v >= PATCH_VARIANT_BASE) {
-        if (pc.band) { set_error("patch variant requested for a band layer"); return RTOD_E_STATE; }
-        return launch_conv_patch_f16s3(a, v - PATCH_VARIANT_BASE, s);
-    }
-    if (v >= PWD_VARIANT_BASE) {
-        if (pc.band) { set_error("pointwise variant requested for a band layer"); return RTOD_E_STATE; }
-        return launch_conv_pwd_f16s3(a, v - PWD_VARIANT_BASE, s);
-    }
-    if (v >= RING_VARIANT_BASE) {
-        if (pc.band) { set_error("ring variant requested for a band layer"); return RTOD_E_STATE; }
-        return launch_conv_ring_f16s3(a, v - RING_VARIANT_BASE, s);
-    }
-    if (v >= BAND_VARIANT_BASE) {
-        if (v == BAND_VARIANT_BASE + BANDD_WIDE_MODE && !pc.band) return launch_conv_bandd_f16s3(a, v - BAND_VARIANT_BASE - BAND_LDS_MODES, s);
-        if (!pc.band) { set_error("band variant requested for a layer without band weights"); return RTOD_E_STATE; }
-        return launch_conv_band_f16s3(a, v - BAND_VARIANT_BASE, s);
-    }
-    return launch_conv_f16s3(a, v, s);
+    return t.fam->launch(a, t.mode, s);
 }
 
 int Plan::build_conv_args(const Launch& l, int batch, float* out, ConvArgs& a) const {
@@ -1011,42 +1057,7 @@ int Plan::tune_launch(size_t li, ConvArgs& a, int batch, hipStream_t s) {
     }
     hipEvent_t e0, e1;
     RTOD_HIP(hipEventCreate(&e0)); RTOD_HIP(hipEventCreate(&e1));
-    std::vector<int> cand;
-    if (convs[l.conv_slot].narrow) {                                                  // narrow layers: their own tiles only (the key carries cin)
-        for (int m = 0; m < C16_MODES; ++m) cand.push_back(C16_VARIANT_BASE + m);
-    } else if (convs[l.conv_slot].ks_chunks > 0) {                                    // sliced layers: every tile x schedule of their family (bit-identical)
-        const bool b_ok = opt_k_slice_workgroups && ks_sched_b_fits(l, batch);
-        for (int m = 0; m < KS_MODES; ++m) if (!(m & 1) || b_ok) cand.push_back(KS_VARIANT_BASE + m);
-    } else if (convs[l.conv_slot].band) {                                             // band layers: band tiles only (see rtod_internal.h)
-        for (int m = 0; m < BAND_MODES; ++m) if (band_mode_ok(precision, m, L)) cand.push_back(BAND_VARIANT_BASE + m);
-    } else {
-        for (int v = 0; v < HV_COUNT; ++v) {
-            const ConvVariantInfo& vi = conv_f16s3_variant_info(v);
-            if (vi.bn > 2 * ((L.cout + 63) / 64 * 64) && vi.bn > 64) continue;       // tile far wider than the layer
-            if (pw && vi.bn < L.cout) continue;                                       // fused pointwise: one N tile
-            cand.push_back(v);
-        }
-        // (SiLU layers: only the kernels with the LDS-transposed epilogue carry that activation — generic and band tiles)
-        if (precision == 1 && !pw && L.act <= 1 && opt_patch_kernel && conv_patch_supported(L.size, L.stride, L.pad, L.cin, L.cout) && L.hout == L.hin && l.out_layer != -2)
-            for (int m = 0; m < PATCH_MODES; ++m) {
-                if (conv_patch_mode_info(m).bn > L.cout && conv_patch_mode_info(m).bn > 64) continue;
-                if (!conv_patch_mode_valid(m, L.cin, L.cout)) continue;
-                cand.push_back(PATCH_VARIANT_BASE + m);
-            }
-        // (the slab tiles use the epilogue of the band family, which carries all three activations)
-        if (bandd_wide_candidate(l, L)) cand.push_back(BAND_VARIANT_BASE + BANDD_WIDE_MODE);
-        if (pwd_candidate(l, L))
-            for (int m = 0; m < PWD_MODES; ++m) {
-                if (conv_pwd_mode_info(m).bn > 128 && conv_pwd_mode_info(m).bn > (L.cout + 127) / 128 * 128) continue;   // tile wider than the layer
-                cand.push_back(PWD_VARIANT_BASE + m);
-            }
-        if (precision == 1 && !pw && L.act <= 1 && opt_ring_kernel)
-            for (int m = 0; m < RING_MODES; ++m) {
-                const ConvVariantInfo& vi = conv_ring_mode_info(m);
-                if (vi.bn > 2 * ((L.cout + 63) / 64 * 64) && vi.bn > 64) continue;
-                cand.push_back(RING_VARIANT_BASE + m);
-            }
-    }
+    const std::vector<int> cand = tile_candidates(l, batch);
     int best_v = variant_for(l, batch);
     int rc = RTOD_OK;
     // min over `reps` timed groups of `per` back-to-back launches
@@ -1098,66 +1109,14 @@ int Plan::set_tiles(int batch, const int* variants, int count) {
         const Launch& l = launches[i];
         if (v < 0) continue;
         if (l.kind != LK_CONV || l.conv_slot < 0 || !convs[l.conv_slot].split) { set_error("set_tiles: launch %d is not a split-f16 convolution", i); return RTOD_E_ARG; }
-        const Layer& L = layers[l.layer];
-        const bool band = convs[l.conv_slot].band, hosts_pw = l.pw_guest >= 0 && pw_active();
-        bool ok;
-        if (precision == 2 && !variant_has_f16(v)) ok = false;
-        else if (convs[l.conv_slot].narrow || c16_variant(v)) ok = convs[l.conv_slot].narrow && c16_variant(v);
-        else if (convs[l.conv_slot].ks_chunks > 0 || ks_variant(v)) {
-            ok = convs[l.conv_slot].ks_chunks > 0 && ks_variant(v);
-            if (ok && ((v - KS_VARIANT_BASE) & 1) && !ks_sched_b_fits(l, batch)) {
-                set_error("set_tiles: variant %d (one workgroup per K slice) of launch %d (layer %d) needs more slice scratch than the plan has at batch %d", v, i, l.layer, batch);
-                return RTOD_E_ARG;
-            }
+        if (!tile_legal(l, batch, v)) { set_error("set_tiles: variant %d is not a valid tile of launch %d (layer %d)", v, i, l.layer); return RTOD_E_ARG; }
+        if (family_of(v).ks_sched_b() && !ks_sched_b_fits(l, batch)) {
+            set_error("set_tiles: variant %d (one workgroup per K slice) of launch %d (layer %d) needs more slice scratch than the plan has at batch %d", v, i, l.layer, batch);
+            return RTOD_E_ARG;
         }
-        else if (band) ok = v >= BAND_VARIANT_BASE && v < BAND_VARIANT_BASE + BAND_MODES && band_mode_ok(precision, v - BAND_VARIANT_BASE, L);
-        else if (v >= PATCH_VARIANT_BASE) ok = v < PATCH_VARIANT_BASE + PATCH_MODES && !hosts_pw && l.out_layer != -2 && L.act <= 1 && L.hout == L.hin &&
-                                               conv_patch_supported(L.size, L.stride, L.pad, L.cin, L.cout) && conv_patch_mode_valid(v - PATCH_VARIANT_BASE, L.cin, L.cout);
-        else if (v >= PWD_VARIANT_BASE) ok = v < PWD_VARIANT_BASE + PWD_MODES && pwd_candidate(l, L);
-        else if (v == BAND_VARIANT_BASE + BANDD_WIDE_MODE) ok = bandd_wide_candidate(l, L);
-        else if (v >= RING_VARIANT_BASE) ok = v < RING_VARIANT_BASE + RING_MODES && !hosts_pw && L.act <= 1;
-        else ok = v < HV_COUNT && !(hosts_pw && conv_f16s3_variant_info(v).bn < L.cout);
-        if (!ok) { set_error("set_tiles: variant %d is not a valid tile of launch %d (layer %d)", v, i, l.layer); return RTOD_E_ARG; }
     }
     tuned[batch] = std::vector<int>(variants, variants + count);
     return RTOD_OK;
-}
-
-int Plan::variant_for(const Launch& l, int batch) const {
-    const bool band = convs[l.conv_slot].band;
-    if (convs[l.conv_slot].narrow) {                         // a narrow layer always gets a narrow tile: forced, tuned, or the closed-form default
-        const Layer& NL = layers[l.layer];
-        if (opt_force_f16s3_variant >= 0) {
-            if (c16_variant(opt_force_f16s3_variant)) return opt_force_f16s3_variant;
-        } else {
-            auto nt = tuned.find(batch);
-            const size_t ni = &l - &launches[0];
-            if (nt != tuned.end() && ni < nt->second.size() && c16_variant(nt->second[ni])) return nt->second[ni];
-        }
-        return C16_VARIANT_BASE + conv_c16_default_mode(NL.cout, (int64_t)batch * NL.hout * NL.wout);
-    }
-    if (convs[l.conv_slot].ks_chunks > 0) return ks_variant_for(l, batch);      // a sliced layer always gets a tile of its family
-    if (opt_force_f16s3_variant >= 0) {                      // >= BAND_VARIANT_BASE: tile of the band layers, below: of the others
-        const int v = opt_force_f16s3_variant;
-        const Layer& FL = layers[l.layer];
-        if (band) return band_mode_ok(precision, v - BAND_VARIANT_BASE, FL) ? v : BAND_VARIANT_BASE + band_default_mode(precision, FL);
-        if (v == BAND_VARIANT_BASE + BANDD_WIDE_MODE) { if (bandd_wide_candidate(l, FL)) return v; }
-        else if (v >= PWD_VARIANT_BASE && v < PWD_VARIANT_BASE + PWD_MODES) { if (pwd_candidate(l, FL)) return v; }
-        else if (precision == 1 && v >= RING_VARIANT_BASE && v < RING_VARIANT_BASE + RING_MODES && !(l.pw_guest >= 0 && pw_active()) && FL.act <= 1) return v;
-        if (precision == 1 && v >= PATCH_VARIANT_BASE && v < PATCH_VARIANT_BASE + PATCH_MODES && !(l.pw_guest >= 0 && pw_active()) && l.out_layer != -2 && FL.act <= 1 &&
-            conv_patch_supported(FL.size, FL.stride, FL.pad, FL.cin, FL.cout) && FL.hout == FL.hin && conv_patch_mode_valid(v - PATCH_VARIANT_BASE, FL.cin, FL.cout)) return v;
-        const int g = choose_variant_f16s3(layers[l.layer], batch);
-        if (l.pw_guest >= 0 && pw_active() && conv_f16s3_variant_info(g).bn < layers[l.layer].cout) return HV_128x128_8W;
-        return g;
-    }
-    auto it = tuned.find(batch);
-    const size_t idx = &l - &launches[0];
-    if (it != tuned.end() && idx < it->second.size() && it->second[idx] >= 0) return it->second[idx];
-    if (band) return BAND_VARIANT_BASE + band_default_mode(precision, layers[l.layer]);
-    const int v = choose_variant_f16s3(layers[l.layer], batch);
-    // host of a fused pointwise conv: one N tile must cover every output channel
-    if (l.pw_guest >= 0 && pw_active() && conv_f16s3_variant_info(v).bn < layers[l.layer].cout) return HV_128x128_8W;
-    return v;
 }
 
 // Sliced split layers (option k_slices_split, conv_ks_f16s3.hip).  The slice panels [S][M][Npad] of schedule B fit the scratch:
@@ -1168,55 +1127,9 @@ bool Plan::ks_sched_b_fits(const Launch& l, int batch) const {
     const int64_t S = (pc.Kpad / 32 + pc.ks_chunks - 1) / pc.ks_chunks;
     return S * batch * L.hout * L.wout * pc.Npad <= KS_SCRATCH_FLOATS;
 }
-// Tile + schedule: forced (a family id), tuned, or the default — the 64x64 tile, and like f32_slice_mode one workgroup per
-// (tile, slice) while the tile grid alone leaves the chip idle and the panels fit, else the slices inside the workgroup.
-// Option k_slice_workgroups = 0 and slice panels larger than the scratch (allocated with the weights of every plan that has a
-// sliced layer) turn every choice into schedule A of the same tile (the same bits).
-int Plan::ks_variant_for(const Launch& l, int batch) const {
-    const Layer& L = layers[l.layer];
-    const bool b_ok = opt_k_slice_workgroups && ks_sched_b_fits(l, batch);
-    int v = -1;
-    if (opt_force_f16s3_variant >= 0) { if (ks_variant(opt_force_f16s3_variant)) v = opt_force_f16s3_variant; }
-    else {
-        auto it = tuned.find(batch);
-        const size_t idx = &l - &launches[0];
-        if (it != tuned.end() && idx < it->second.size() && ks_variant(it->second[idx])) v = it->second[idx];
-    }
-    if (v < 0) {
-        const int64_t M = (int64_t)batch * L.hout * L.wout;
-        const int64_t tiles = ((M + 63) / 64) * ((L.cout + 63) / 64);
-        v = KS_VARIANT_BASE + (tiles < 512 ? 1 : 0);
-    }
-    if (!b_ok) v = KS_VARIANT_BASE + ((v - KS_VARIANT_BASE) & ~1);
-    return v;
-}
-
 bool Plan::pw_active() const { return precision == 1 && opt_fuse_pointwise; }
-// 3x3 stride-1 layer too wide for the band family's LDS budget at three workgroups per CU but not for its one-buffer tile
-bool Plan::bandd_wide_candidate(const Launch& l, const Layer& L) const {
-    if (!opt_band_kernel || l.conv_slot < 0 || convs[l.conv_slot].band || convs[l.conv_slot].narrow || !convs[l.conv_slot].split) return false;
-    if (l.out_layer == -2 || (l.pw_guest >= 0 && pw_active())) return false;
-    const PackedConv& pc = convs[l.conv_slot];
-    return conv_bandd_wide_supported(L.size, L.stride, L.pad, pc.cin_p, L.win) && L.hout == L.hin && L.wout == L.win && pc.Npad % 128 == 0 && pc.K == pc.Kpad;
-}
-// plain 1x1 layer the slab tiles of conv_pwd_f16s3.hip can run: no fused head decode, no hosted pointwise conv, whole 64-channel slabs
-bool Plan::pwd_candidate(const Launch& l, const Layer& L) const {
-    if (!opt_pwd_kernel || l.conv_slot < 0 || convs[l.conv_slot].band || convs[l.conv_slot].narrow || !convs[l.conv_slot].split) return false;
-    if (l.out_layer == -2 || (l.pw_guest >= 0 && pw_active())) return false;
-    return conv_pwd_supported(L.size, L.stride, L.pad, convs[l.conv_slot].cin_p) && L.hout == L.hin && L.wout == L.win;
-}
 bool Plan::stem_pool_fused() const { return precision >= 1 && stem_pool_pattern && !keep_all && convs[launches[0].conv_slot].stem16; }
 bool Plan::stem2_active() const { return precision == 1 && opt_stem2_kernel && stem2_pattern && !keep_all && convs[launches[0].conv_slot].split; }
-
-int Plan::choose_variant_f16s3(const Layer& L, int batch) const {
-    if (opt_force_f16s3_variant >= 0 && opt_force_f16s3_variant < HV_COUNT) return opt_force_f16s3_variant;
-    if (L.cout <= 64) return HV_128x64;
-    const int64_t M = (int64_t)batch * L.hout * L.wout;
-    const int64_t gn = (L.cout + 127) / 128;
-    if (((M + 127) / 128) * gn >= 512) return HV_128x128;
-    if (((M + 63) / 64) * gn >= 512) return HV_64x128;
-    return HV_64x64;
-}
 
 int Plan::forward(const float* x, int batch, float* out, hipStream_t s, float* launch_ms, bool tune) {
     if (!weights_loaded) { set_error("forward: load_weights has not been called"); return RTOD_E_STATE; }

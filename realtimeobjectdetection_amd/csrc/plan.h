@@ -1,6 +1,7 @@
 // Static execution plan of a Darknet cfg on one GPU: layer IR, NHWC buffer arena with liveness
 // reuse, zero-copy route concat, fused shortcut / head-decode epilogues, packed weights, launch list.
 #pragma once
+#include <functional>
 #include <map>
 #include <string>
 #include <vector>
@@ -125,6 +126,8 @@ struct Plan {
     int parse(const std::string& cfg_text);
     int resolve_shapes();
     int plan_buffers();
+    DecodeArgs decode_args(const Layer& yolo) const;
+    int replan_or(const std::function<void()>& restore);   // re-plan after an option / precision change; refused: restore, re-plan, keep the message
     void assign_arena();
     void layout_weights();
     bool uses_split(const Layer& L, int cin_p) const;
@@ -137,19 +140,19 @@ struct Plan {
     void reset_planning();
     View view_of(int layer) const;            // resolves aliases; base == nullptr if not materialised
     int choose_variant(const Layer& L, int batch) const;
-    int choose_variant_f16s3(const Layer& L, int batch) const;
     int build_conv_args(const Launch& l, int batch, float* out, ConvArgs& a) const;
     int tune_launch(size_t li, ConvArgs& a, int batch, hipStream_t s);
     std::vector<int> tuning;                    // scratch of the tuning forward
     std::map<std::vector<int>, int> tune_cache;
+    // split-f16 tiles (ids: split_tiles.cpp): the rules live in these four, and launch_split_variant refuses by the same family facts
+    bool tile_legal(const Launch& l, int batch, int v) const;            // may this launch run tile v and give the layer's defined bits?
+    int default_tile(const Launch& l, int batch) const;                  // closed-form choice per kind of layer
+    int variant_for(const Launch& l, int batch) const;                   // forced or tuned id if legal, else the default
+    std::vector<int> tile_candidates(const Launch& l, int batch) const;  // what autotune times, in screening order
     int launch_split_variant(ConvArgs& a, const PackedConv& pc, int v, hipStream_t s) const;
-    int variant_for(const Launch& l, int batch) const;
     int f32_slice_mode(const Launch& l, int batch, int variant) const;   // 0 plain, 1 slices inside the workgroup, 2 one workgroup per slice
     bool ks_sched_b_fits(const Launch& l, int batch) const;              // sliced split layer: the slice panels of this batch fit the scratch
-    int ks_variant_for(const Launch& l, int batch) const;                // sliced split layer: forced, tuned or default tile + schedule
-    bool pw_active() const;
-    bool pwd_candidate(const Launch& l, const Layer& L) const;
-    bool bandd_wide_candidate(const Launch& l, const Layer& L) const;                     // fused pointwise convs in use (precision 1, option fuse_pointwise)
+    bool pw_active() const;                     // fused pointwise convs in use (precision 1, option fuse_pointwise)
     bool stem2_pattern = false;                 // launches 0 / 1 are a stem and the stride-2 conv conv_stem2_f16s3 fuses (set by plan_buffers)
     bool stem2_active() const;                  // ... and the plan runs them fused (split-f16 precision, option stem2_kernel)
     bool stem_pool_pattern = false;             // launch 0 is the 16-filter stem and launch 1 the 2x2 / stride-2 max-pool that alone reads it (set by plan_buffers)

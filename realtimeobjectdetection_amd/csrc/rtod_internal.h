@@ -174,6 +174,12 @@ enum ConvF16Variant { HV_128x128 = 0, HV_128x64 = 1, HV_64x64 = 2, HV_64x128 = 3
 const ConvVariantInfo& conv_f16s3_variant_info(int v);
 int conv_f16s3_kernel_name(int variant, int epi, char* buf, size_t len);      // demangled instantiation name (rocprofv3)
 int launch_conv_f16s3(const ConvArgs& a, int variant, hipStream_t s);
+// The split-f16 tile families.  A tile id is family base + mode; the constants below give each family's range and mode-level
+// facts.  split_tiles.cpp holds the one table of the ranges (TileFamily, family_of) and is, with this header, the only place
+// that compares an id against a base or a mode count.  Which tile a launch may run, runs by default and times in autotune is
+// decided in plan.cpp alone: Plan::tile_legal, Plan::default_tile, Plan::tile_candidates (variant_for / set_tiles /
+// tune_launch / launch_split_variant all go through them and family_of).  A new family: its constants here, one row there,
+// its rules in those three functions.
 // 3x3 stride-1 pad-1 convs with an LDS-resident input band (conv_band_f16s3.hip); weights in band K order
 bool conv_band_supported(int ksize, int stride, int pad, int cin, int w_in);
 // A layer the band kernel supports ALWAYS runs on it (its split-K layers sum in a different order than the generic kernel, and
@@ -182,7 +188,7 @@ constexpr int BANDD_MODES = 9;             // conv_bandd_f16s3.hip (round 4): we
 constexpr int BAND_LDS_MODES = 11;         // conv_band_f16s3.hip: 128x128/4x2 waves, 128x64/4x2, 192x128/4x2, 192x128/6x2, 96x128/2x4, 128x128/2x2, 64x128/2x4,
                                            // and with in-workgroup split-K (two wave groups): 96x128/2x4, 128x128/4x2, 64x128/2x4, 128x64/4x2 (13x13 grids)
 constexpr int BAND_MODES = BAND_LDS_MODES + BANDD_MODES;
-static_assert(50 + BAND_MODES <= 70, "band variant ids end where the ring kernel's begin");    // modes >= BAND_LDS_MODES: conv_bandd tile (mode - BAND_LDS_MODES)
+                                           // modes >= BAND_LDS_MODES: conv_bandd tile (mode - BAND_LDS_MODES)
 constexpr int BAND_K2_MODE0 = 7;
 const ConvVariantInfo& conv_bandd_mode_info(int idx);
 int conv_bandd_mode_kg(int idx);
@@ -257,6 +263,27 @@ const ConvVariantInfo& conv_ks_mode_info(int mode);
 int conv_ks_slices(const ConvArgs& a);                                        // K slices of a launch of this family
 int conv_ks_kernel_name(int mode, int epi, char* buf, size_t len);
 int launch_conv_ks_f16s3(const ConvArgs& a, int mode, hipStream_t s);
+
+// One row per id range (split_tiles.cpp), in ascending base order.  STEM2_VARIANT is a reported id only and has no row.
+enum TileFamilyId { TF_GENERIC = 0, TF_BAND, TF_RING, TF_PWD, TF_PATCH, TF_C16, TF_KS, TF_COUNT };
+struct TileFamily {
+    int id, base, modes;
+    int f16_from;                                                   // modes >= this have a plain-f16 instance (== modes: none has)
+    const ConvVariantInfo& (*info)(int mode);
+    int (*kernel_name)(int mode, int epi, char* buf, size_t len);
+    int (*launch)(const ConvArgs& a, int mode, hipStream_t s);
+};
+struct TileRef {                                                    // a tile id resolved: its family's row and the mode (fam == nullptr: no such tile)
+    const TileFamily* fam; int mode;
+    explicit operator bool() const { return fam != nullptr; }
+    bool is(int family) const { return fam && fam->id == family; }
+    bool f16() const { return fam && mode >= fam->f16_from; }
+    bool ks_sched_b() const { return is(TF_KS) && (mode & 1); }    // one workgroup per (tile, slice); id - 1 is schedule A of the same tile
+    bool bandd_wide() const { return is(TF_BAND) && mode == BANDD_WIDE_MODE; }
+};
+TileRef family_of(int v);
+const TileFamily& tile_family(int family);
+inline int tile_id(int family, int mode) { return tile_family(family).base + mode; }
 
 int launch_conv_stem(const float* x_nchw, const float* w, const float* bias, const View& out, int B, int H, int W,
                      int Ho, int Wo, int stride, int Cout, int leaky, hipStream_t s);
