@@ -128,6 +128,17 @@ int rtod_plan_set_precision(rtod_plan* plan, int mode);
  *   "patch_kernel"      2-D patch tiles among the autotune candidates of the wide 3x3 stride-1 layers (bit-identical)
  *   "stem2_kernel"      layers 0-2 of Darknet-53 in one kernel (conv_stem2_f16s3.hip, bit-identical); 0: stand-alone kernels
  *   "bn_batch_stats"    (default 0) exact-fp32 plans: BatchNorm on batch statistics instead of the folded running statistics
+ *   "bn_batch_split"    (default 0) with "bn_batch_stats": lets precision 1 (split f16) run that mode; without it the option is inert
+ *                       (same plan, same bits, in every precision).  Every BatchNorm conv after layer 0 runs a RAW-SUM instance of a
+ *                       generic, bandd or 1x1 slab tile (epilogue code 16 in rtod_conv_kernel_name: the fp32 convolution sums go to a
+ *                       dense scratch, "bn_raw_bytes" in rtod_plan_describe, allocated with the weights), then the statistics kernels
+ *                       of "bn_batch_stats", then a normalise kernel that applies the activation, adds the shortcut and writes the
+ *                       split format.  Layer 0 stays on the exact-fp32 kernel.  Convs without BatchNorm run as in an eval plan; no
+ *                       hosted pointwise conv, no fused stem.  Tiles: those with a raw-sum instance that the layer's family rules
+ *                       admit (rtod_plan_set_tiles refuses the others).  RTOD_E_CFG from rtod_plan_set_precision (or from the option
+ *                       call that completes the combination): precision 2; a BatchNorm conv with Cin == 16 (with or without
+ *                       "narrow_cin"); "k_slices_split" or "stem_pool" together with the mode.  Accepted before or after
+ *                       rtod_plan_set_precision.  rtod_plan_bn_batch_stats / rtod_plan_bn_update_running work as in fp32 plans
  *   "k_slices"          exact-fp32 plans: deep small-grid layers summed in K slices (conv_igemm_f32.hip); 0: one chain
  *   "k_slice_workgroups" ... one workgroup per slice when the grid is small; 0: always inside the workgroup (same bits).
  *                       Governs the K-sliced split-f16 tiles of "k_slices_split" in the same way

@@ -2,7 +2,7 @@
 // upsample, stand-alone shortcut add, max-pool, channel copy, NHWC->NCHW read-back, stand-alone head
 // decode, confidence mask, IoU.  All are HBM-bound elementwise work: one float4 (16 B) per lane
 // along the channel axis wherever the layout allows, grid capped at ~2048 blocks + grid stride.
-#include "rtod_internal.h"
+#include "conv_f16s3_common.h"
 #include <algorithm>
 
 namespace rtod {
@@ -509,6 +509,89 @@ int launch_bn_batch(const View& x, const View& y, const View* res, int B, double
     View r = res ? *res : x;
     hipLaunchKernelGGL(bn_apply_kernel, dim3(grid_for(total, 256)), dim3(256), 0, s, x, y, r, res ? 1 : 0, B, stats, sstride, bn, gstride, act);
     return hip_fail(hipGetLastError(), "bn_apply launch");
+}
+
+// Batch-statistics BatchNorm on a split-f16 plan (plan option bn_batch_split).  The conv's raw-sum instance (EPI_RAW) has written
+// the convolution sums as dense fp32 rows; the statistics kernels above read them through an fp32 view; this kernel normalises and
+// writes the split format.  One thread per 8 channels of a pixel: two 16-byte fp32 reads, one 16-byte read per plane of the shortcut
+// operand, one 16-byte store per plane.  y = act(raw * w_c + b_c) + (hi + lo) / 8 with w_c / b_c formed by the expressions of
+// bn_apply_kernel (WB: read from the constants bn_stats_final_kernel wrote, the same expressions); 8 y goes through split_f16.
+template <bool WB>
+__global__ void bn_apply_split_kernel(View x, View y, View res, int has_res, int B, const float* __restrict__ wb, const double* __restrict__ stats,
+                                      int sstride, const float* __restrict__ bn, int gstride, int act, int32_t* ovf) {
+    const int C8 = x.C / 8;
+    const int64_t total = (int64_t)B * x.H * x.W * C8;
+    const _Float16* rb = reinterpret_cast<const _Float16*>(res.base);
+    _Float16* yb = reinterpret_cast<_Float16*>(y.base);
+    float amax = 0.f;
+    for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
+        const int c = (int)(t % C8) * 8;
+        const int64_t p = t / C8;
+        const float* xp = x.base + x.coff + c + p * x.ldc;
+        const f32x4 v0 = *reinterpret_cast<const f32x4*>(xp), v1 = *reinterpret_cast<const f32x4*>(xp + 4);
+        float w[8], b[8];
+        if constexpr (WB) {
+            const f32x4 w0 = *reinterpret_cast<const f32x4*>(wb + c), w1 = *reinterpret_cast<const f32x4*>(wb + c + 4);
+            const f32x4 b0 = *reinterpret_cast<const f32x4*>(wb + sstride + c), b1 = *reinterpret_cast<const f32x4*>(wb + sstride + c + 4);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) { w[e] = e < 4 ? w0[e] : w1[e - 4]; b[e] = e < 4 ? b0[e] : b1[e - 4]; }
+        } else {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const double invstd = 1.0 / sqrt(stats[sstride + c + e] + 1e-5);
+                w[e] = (float)(invstd * (double)bn[gstride + c + e]);                                   // gamma / sqrt(var + eps)
+                b[e] = (float)((double)bn[c + e] - stats[c + e] * invstd * (double)bn[gstride + c + e]);
+            }
+        }
+        f16x8 qh = {0, 0, 0, 0, 0, 0, 0, 0}, ql = {0, 0, 0, 0, 0, 0, 0, 0};
+        if (has_res) {
+            const _Float16* q = rb + p * 2 * res.ldc + res.coff + c;
+            qh = *reinterpret_cast<const f16x8*>(q);
+            ql = *reinterpret_cast<const f16x8*>(q + res.ldc);
+        }
+        f16x8 ph, pl;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            float u = (e < 4 ? v0[e] : v1[e - 4]) * w[e] + b[e];
+            u = apply_act(u, act);
+            if (has_res) u += ((float)qh[e] + (float)ql[e]) * (1.0f / SPLIT_SCALE);
+            _Float16 h, l;
+            split_f16(u * SPLIT_SCALE, h, l, amax);
+            ph[e] = h; pl[e] = l;
+        }
+        _Float16* o = yb + p * 2 * y.ldc + y.coff + c;
+        store_act16(o, ph, false);
+        store_act16(o + y.ldc, pl, false);
+    }
+    split_overflow_report(ovf, amax);
+}
+
+static bool view_ok8_split(const View& v) { return v.base && v.split == 1 && v.C % 8 == 0 && v.ldc % 8 == 0 && v.coff % 8 == 0; }
+
+int launch_bn_batch_split(const View& raw, const View& y, const View* res, int B, double* stats, int sstride, const float* bn, int gstride, int act,
+                          double* partial, int64_t partial_doubles, int32_t* ovf, hipStream_t s) {
+    if (raw.split || !raw.base || raw.C % 8 || raw.ldc % 8 || raw.coff % 8) { set_error("bn_batch_split: bad raw-sum view"); return RTOD_E_ARG; }
+    if (!view_ok8_split(y) || raw.C != y.C || raw.H != y.H || raw.W != y.W || !stats || !bn || gstride < raw.C || sstride < raw.C || B < 1) { set_error("bn_batch_split: bad views"); return RTOD_E_ARG; }
+    if (res && (!view_ok8_split(*res) || res->C != raw.C || res->H != raw.H || res->W != raw.W)) { set_error("bn_batch_split: bad shortcut view"); return RTOD_E_ARG; }
+    const int C4 = raw.C / 4;
+    const int64_t npix = (int64_t)B * raw.H * raw.W;
+    const int64_t total = npix * (raw.C / 8);
+    const View r = res ? *res : y;
+    const int nparts = (int)std::min<int64_t>(BN_PARTS_MAX, std::max<int64_t>(1, npix / 128));
+    // the statistics path of launch_bn_batch: two stages where the channel count allows, else one workgroup per 4 channels
+    if (partial && (256 % C4 == 0 || C4 % 256 == 0) && (int64_t)nparts * 2 * sstride + sstride <= partial_doubles) {
+        hipLaunchKernelGGL(bn_stats_partial_kernel, dim3(nparts), dim3(256), 0, s, raw, B, partial, sstride, nparts);
+        if (hipGetLastError() != hipSuccess) return hip_fail(hipGetLastError(), "bn_stats_partial launch");
+        float* wb = reinterpret_cast<float*>(partial + (int64_t)nparts * 2 * sstride);
+        hipLaunchKernelGGL(bn_stats_final_kernel, dim3((raw.C + 15) / 16), dim3(256), 0, s, partial, sstride, nparts, raw.C, (double)npix, stats, sstride, bn, gstride, wb);
+        if (hipGetLastError() != hipSuccess) return hip_fail(hipGetLastError(), "bn_stats_final launch");
+        hipLaunchKernelGGL(bn_apply_split_kernel<true>, dim3(grid_for(total, 256)), dim3(256), 0, s, raw, y, r, res ? 1 : 0, B, wb, stats, sstride, bn, gstride, act, ovf);
+        return hip_fail(hipGetLastError(), "bn_apply_split launch");
+    }
+    hipLaunchKernelGGL(bn_stats_kernel, dim3(raw.C / 4), dim3(256), 0, s, raw, B, stats, sstride);
+    if (hipGetLastError() != hipSuccess) return hip_fail(hipGetLastError(), "bn_stats launch");
+    hipLaunchKernelGGL(bn_apply_split_kernel<false>, dim3(grid_for(total, 256)), dim3(256), 0, s, raw, y, r, res ? 1 : 0, B, (const float*)nullptr, stats, sstride, bn, gstride, act, ovf);
+    return hip_fail(hipGetLastError(), "bn_apply_split launch");
 }
 
 // Training-mode side effect of nn.BatchNorm2d on its buffers, for ALL BatchNorm layers of a plan in one launch (the host class

@@ -133,6 +133,7 @@ int rtod_plan_launch_kernel_name(const rtod_plan* plan, int index, char* buf, si
     if (li.kind != LK_CONV || li.flops_per_frame == 0) return RTOD_OK;                 // non-conv launch / conv hosted by the previous launch: empty name
     int epi = li.fused_decode ? 2 : (li.fused_pointwise ? (li.fused_residual ? 4 : 3) : (li.fused_residual ? 1 : 0));
     if (plan->p.precision == 2 && li.variant >= 100) epi |= EPI_F16;              // plain-f16 instance of the split kernels
+    if (plan->p.raw_launch(plan->p.launches[index]) && li.variant >= 100) epi = EPI_RAW;   // raw-sum instance (the shortcut rides the normalise kernel)
     int n = -1;
     if (li.variant == 100 + STEM2_VARIANT) n = conv_stem2_kernel_name(li.fused_pointwise, buf, len);
     else return rtod_conv_kernel_name(li.variant, epi, buf, len);

@@ -32,18 +32,21 @@ template <int NBASE, int PER = 2> __device__ __forceinline__ void bandd_wait_vmc
 // Arithmetic and expression shapes are those of conv_f16s3_epilogue (conv_f16s3_common.h): the same bits.  Unlike that
 // function a pass may cover a PART of a wave's rows (a wave owns all BM rows of its strip; the whole tile would need 64 KB).
 // F16: plain-f16 output (hi plane of the shortcut operand read, hi plane stored).
-template <int BM, int BN, int WM, int WN, int NT, int RG, bool RES, int KG, bool F16 = false>
+// RAW: raw-sum instance (epi_raw, conv_f16s3_common.h): acc * inv_scale[n] as fp32 rows of ConvArgs::raw_out; no bias load, no
+// shortcut operand (RES is false: its loads are not compiled), no split store.
+template <int BM, int BN, int WM, int WN, int NT, int RG, bool RES, int KG, bool F16 = false, bool RAW = false>
 __device__ __forceinline__ void bandd_epilogue(const ConvArgs& a, f32x4 (&acc)[WM / 16][WN / 16], unsigned char* smem, int bm, int bn, int tid,
                                                int wm, int wn, int lr, int lh, int M, int kg) {
     constexpr int TM = WM / 16, TN = WN / 16, MT = 16, NE = 4, TS = BN;
     static_assert(BM % RG == 0 && RG % 16 == 0, "epilogue pass");
+    static_assert(!RAW || (!RES && !F16), "raw-sum instances: no shortcut, no plain-f16 store");
 #ifdef RTOD_TIMELINE
     unsigned long long et_[5] = {0, 0, 0, 0, 0};
     unsigned long long eprev_ = __builtin_amdgcn_s_memtime();
 #endif
     float* T = reinterpret_cast<float*>(smem);
     float amax = 0.f;
-    const float escale = SPLIT_SCALE;
+    const float escale = RAW ? 1.0f : SPLIT_SCALE;
     constexpr int GPR = BN / 8;
     constexpr int NG = (RG * GPR + NT - 1) / NT;
     // every global load of the epilogue up front, for ALL passes: bias / scale of the wave's column tiles, then the residual
@@ -55,7 +58,7 @@ __device__ __forceinline__ void bandd_epilogue(const ConvArgs& a, f32x4 (&acc)[W
     for (int j = 0; j < TN; ++j) {
         const int n = bn * BN + wn * WN + j * MT + lr;
         const int nc = n < a.Cout ? n : 0;
-        const float b = a.bias[nc], iv = a.inv_scale[nc];
+        const float b = RAW ? 0.f : a.bias[nc], iv = a.inv_scale[nc];
         bias_j[j] = n < a.Cout ? b : 0.f; inv_j[j] = n < a.Cout ? iv : 0.f;
     }
     f16x8 rq_h[RES ? NP : 1][RES ? NG : 1], rq_l[RES ? NP : 1][RES ? NG : 1];
@@ -118,6 +121,7 @@ __device__ __forceinline__ void bandd_epilogue(const ConvArgs& a, f32x4 (&acc)[W
                                 const int rl = r0 - rg + e + 4 * lh;
                                 float s = acc[i][j][e];
                                 if constexpr (KG == 2) s += T[rl * TS + nl];
+                                if constexpr (RAW) { T[rl * TS + nl] = s * inv; continue; }       // the convolution sum: exact undo of the pre-scales
                                 float v = s * inv + bias;
                                 if constexpr (decltype(act)::value == 2) v = silu_scaled(v, 1.0f / escale);
                                 else if constexpr (decltype(act)::value == 1) v = __builtin_fmaxf(v, v * 0.1f);
@@ -126,7 +130,8 @@ __device__ __forceinline__ void bandd_epilogue(const ConvArgs& a, f32x4 (&acc)[W
                         }
                     }
                 };
-                if (a.leaky == 2) col(std::integral_constant<int, 2>{});
+                if constexpr (RAW) col(std::integral_constant<int, 0>{});
+                else if (a.leaky == 2) col(std::integral_constant<int, 2>{});
                 else if (a.leaky) col(std::integral_constant<int, 1>{});
                 else col(std::integral_constant<int, 0>{});
             }
@@ -143,6 +148,12 @@ __device__ __forceinline__ void bandd_epilogue(const ConvArgs& a, f32x4 (&acc)[W
             if (r >= RG || m >= M || !ecol) continue;
             const f32x4 v0 = *reinterpret_cast<const f32x4*>(T + r * TS + ec8);
             const f32x4 v1 = *reinterpret_cast<const f32x4*>(T + r * TS + ec8 + 4);
+            if constexpr (RAW) {                                         // 8 channels of row m of the dense [M][Npad] scratch
+                float* rp = a.raw_out + (int64_t)m * a.Npad + bn * BN + ec8;
+                *reinterpret_cast<f32x4*>(rp) = v0;
+                *reinterpret_cast<f32x4*>(rp + 4) = v1;
+                continue;
+            }
             float v[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
             if constexpr (RES && F16) {
                 const f16x8 qh = rq_h[rg / RG][gi];
@@ -173,7 +184,7 @@ __device__ __forceinline__ void bandd_epilogue(const ConvArgs& a, f32x4 (&acc)[W
 #ifdef RTOD_TIMELINE
     if (threadIdx.x == 0 && blockIdx.x < BD_EPI_BLOCKS) for (int i = 0; i < 5; ++i) g_bandd_epi[blockIdx.x * 5 + i] = et_[i];
 #endif
-    split_overflow_report(a.ovf, amax);
+    if constexpr (!RAW) split_overflow_report(a.ovf, amax);
 }
 
 }  // namespace rtod

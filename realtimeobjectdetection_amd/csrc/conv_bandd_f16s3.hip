@@ -63,6 +63,8 @@ __host__ __device__ constexpr int bandd_rows(int bm, int w) { return (bm + 2 * w
 // buffers), summed in the epilogue — the split-K layers of conv_band_f16s3.hip (conv_band_layer_kg), same summation order.
 // EPI | EPI_F16: plain-f16 instance.  The band image keeps its 2 KiB blocks (the lo halves are neither DMA'd nor read), the B sets
 // hold the hi fragments only, one MFMA per (A, B) pair; every counted wait scales with the loads that remain (NB, PER below).
+// EPI_SPLIT | EPI_RAW: raw-sum instance: the f16s3 main loop and its counted waits unchanged (the epilogue's loads are the compiler's,
+// behind the drain), fp32 sums to ConvArgs::raw_out.
 template <int BM, int BN, int NWM, int NWN, int MINW, int EPI, int BUFM, int KG, int MAXW>
 __global__ __launch_bounds__(NWM * NWN * 64 * KG, MINW)
 void conv_bandd_f16s3_kernel(const ConvArgs a, const int grid_m, const int grid_n) {
@@ -314,7 +316,7 @@ void conv_bandd_f16s3_kernel(const ConvArgs a, const int grid_m, const int grid_
     __builtin_amdgcn_s_setprio(0);
     BD_STAMP(3)
 
-    bandd_epilogue<BM, BN, WM, WN, NT * KG, RG, epi_kind(EPI) == EPI_SPLIT_RES, KG, F16>(a, acc, smem, bm, bn, (int)threadIdx.x, wm, wn, lr, lh, M, kg);
+    bandd_epilogue<BM, BN, WM, WN, NT * KG, RG, epi_kind(EPI) == EPI_SPLIT_RES, KG, F16, epi_raw(EPI)>(a, acc, smem, bm, bn, (int)threadIdx.x, wm, wn, lr, lh, M, kg);
 #ifdef RTOD_TIMELINE
     BD_STAMP(4)
     if (threadIdx.x == 0 && blockIdx.x < BD_TL_BLOCKS) {
@@ -343,9 +345,15 @@ static int launch_bandd(const ConvArgs& a, hipStream_t s) {
     const int fe = a.f16 ? EPI_F16 : 0;
     auto k_res = fe ? conv_bandd_f16s3_kernel<BM, BN, NWM, NWN, MINW, EPI_SPLIT_RES | EPI_F16, BUFM, KG, MAXW> : conv_bandd_f16s3_kernel<BM, BN, NWM, NWN, MINW, EPI_SPLIT_RES, BUFM, KG, MAXW>;
     auto k_plain = fe ? conv_bandd_f16s3_kernel<BM, BN, NWM, NWN, MINW, EPI_SPLIT | EPI_F16, BUFM, KG, MAXW> : conv_bandd_f16s3_kernel<BM, BN, NWM, NWN, MINW, EPI_SPLIT, BUFM, KG, MAXW>;
-    static std::atomic<unsigned long long> attr_done[2] = {{0}, {0}};   // per instantiation: f16s3, f16
+    auto k_raw = conv_bandd_f16s3_kernel<BM, BN, NWM, NWN, MINW, EPI_SPLIT | EPI_RAW, BUFM, KG, MAXW>;
+    static std::atomic<unsigned long long> attr_done[3] = {{0}, {0}, {0}};   // per instantiation: f16s3, f16, raw sums
     const int cap = KG * (DB ? 2 : 1) * (bandd_rows(BM, MAXW) / 16 + 1) * 2048;
     const int mx = std::min(cap > epi_bytes ? cap : epi_bytes, 160 * 1024);        // (a launch that needs more is refused above)
+    if (a.raw_out) {
+        if (int rc = lds_opt_in(attr_done[2], mx, "conv_bandd_f16s3", k_raw)) return rc;
+        hipLaunchKernelGGL(k_raw, dim3(gm * gn), dim3(NT), lds, s, ax, gm, gn);
+        return hip_fail(hipGetLastError(), "conv_bandd_f16s3 launch");
+    }
     if (int rc = lds_opt_in(attr_done[fe ? 1 : 0], mx, "conv_bandd_f16s3", k_res, k_plain)) return rc;
     if (a.res) hipLaunchKernelGGL(k_res, dim3(gm * gn), dim3(NT), lds, s, ax, gm, gn);
     else hipLaunchKernelGGL(k_plain, dim3(gm * gn), dim3(NT), lds, s, ax, gm, gn);
@@ -440,6 +448,7 @@ int launch_conv_bandd_f16s3(const ConvArgs& a, int idx, hipStream_t s) {
         set_error("launch_conv_bandd: unsupported shape (k=%d s=%d pad=%d Cin=%d W=%d)", a.kh, a.stride, a.pad, a.Cin, a.Wi); return RTOD_E_ARG;
     }
     if (a.in_ldc % 8 || a.in_coff % 8 || a.K != a.Kpad || a.K != 9 * a.Cin || a.Npad % 128) { set_error("launch_conv_bandd: bad view / K"); return RTOD_E_ARG; }
+    if (a.raw_out && (a.f16 || a.res)) { set_error("launch_conv_bandd: a raw-sum launch carries no shortcut and no plain-f16 store"); return RTOD_E_ARG; }
     switch (idx) {
 #define RTOD_X_CASE(i, bm, bn, nwm, nwn, minw, db, kg, maxw, sfx) case i: if (a.Wi > maxw) break; return launch_bandd<bm, bn, nwm, nwn, minw, db, kg, maxw>(a, s);
         RTOD_BANDD_TILES(RTOD_X_CASE)

@@ -134,7 +134,12 @@ enum { EPI_SPLIT = 0, EPI_SPLIT_RES = 1, EPI_DECODE = 2, EPI_SPLIT_PW = 3, EPI_S
 // shortcut operand only and stores the hi plane only (the lo halves of an f16 plan's arena are never written or read).
 // Kept inside EPI so that the f16s3 instances keep their names (rocprofv3, bench.py).  EPI_F16 itself: rtod_internal.h.
 __host__ __device__ constexpr bool epi_f16(int epi) { return (epi & EPI_F16) != 0; }
-__host__ __device__ constexpr int epi_kind(int epi) { return epi & ~EPI_F16; }
+// Raw-sum instances (plan option bn_batch_split): EPI_SPLIT | EPI_RAW.  Same main loop; the epilogue stores acc * inv_scale[n] — the
+// convolution sum itself: the pre-scales are powers of two — as dense fp32 rows [M][Npad] to ConvArgs::raw_out, after the same LDS
+// transpose: no SPLIT_SCALE, bias, activation or shortcut, no split store, no overflow sentinel.  The normalisation that follows
+// (aux_kernels.hip: bn_apply_split_kernel) writes the split format.
+__host__ __device__ constexpr bool epi_raw(int epi) { return (epi & EPI_RAW) != 0; }
+__host__ __device__ constexpr int epi_kind(int epi) { return epi & ~(EPI_F16 | EPI_RAW); }
 constexpr int PW_MAX_COUT = 64, PW_MAX_K = 64;    // measured: hosts with 128 output channels gain nothing over the stand-alone 1x1 kernel
 
 __device__ __forceinline__ float h_sigmoid(float v) { return 1.0f / (1.0f + expf(-v)); }
@@ -273,7 +278,8 @@ constexpr int epi_row_group(int bm, int wm, int rg_max) {
 // the start of a tile: a compiler-visible global load inside the epilogue would be waited for with vmcnt(0), which also
 // drains the LDS-DMA ring that is prefetching the next tile).
 // F16: plain-f16 output (precision mode 2): hi plane of the shortcut operand, hi plane stored (no hosted pointwise conv).
-template <int BM, int BN, int WM, int WN, int NT, int EPI, int SMEM_BYTES, int KG = 1, bool PRE = false, bool F16 = false>
+// RAW: raw-sum instance (epi_raw above): EPI_SPLIT only, never with F16.
+template <int BM, int BN, int WM, int WN, int NT, int EPI, int SMEM_BYTES, int KG = 1, bool PRE = false, bool F16 = false, bool RAW = false>
 __device__ __forceinline__ void conv_f16s3_epilogue(const ConvArgs& a, f32x4 (&acc)[WM / 16][WN / 16], unsigned char* smem,
                                                     int bm, int bn, int tid, int wm, int wn, int lr, int lh, int M, int kg = 0,
                                                     const float* pre_bias = nullptr, const float* pre_inv = nullptr) {
@@ -281,6 +287,7 @@ __device__ __forceinline__ void conv_f16s3_epilogue(const ConvArgs& a, f32x4 (&a
     constexpr bool PW = EPI == EPI_SPLIT_PW || EPI == EPI_SPLIT_RES_PW;
     constexpr bool RES = EPI == EPI_SPLIT_RES || EPI == EPI_SPLIT_RES_PW;
     static_assert(!(F16 && PW), "plain-f16 plans host no pointwise conv");
+    static_assert(!RAW || (EPI == EPI_SPLIT && !F16), "raw-sum instances: no shortcut, decode, hosted pointwise conv or plain-f16 store");
     // fused pointwise conv: the transpose tile doubles as the A operand of the second GEMM (row stride + 4 floats: the
     // 16 rows x 16 bytes of a fragment read then cover all 64 banks), and a second tile T2 takes its result
     constexpr int TS = PW ? BN + 4 : BN;
@@ -321,7 +328,7 @@ __device__ __forceinline__ void conv_f16s3_epilogue(const ConvArgs& a, f32x4 (&a
         }
         bias2 = a.pw_bias[n2] * SPLIT_SCALE; inv2 = a.pw_inv_scale[n2] * SPLIT_SCALE;
     }
-    const float escale = (EPI == EPI_DECODE) ? 1.0f : SPLIT_SCALE;   // (acc*inv + bias)*8 == acc*(8 inv) + 8 bias exactly
+    const float escale = (EPI == EPI_DECODE || RAW) ? 1.0f : SPLIT_SCALE;   // (acc*inv + bias)*8 == acc*(8 inv) + 8 bias exactly
     constexpr int GPR_ = BN / 8;                                          // 8-channel (16-byte) groups per row
     constexpr int NG = (RG * GPR_ + NT - 1) / NT;                         // groups per thread and pass
     // bias / scale of the wave's TN column groups: all loads first and ahead of the residual loads (vmcnt retires in order: the
@@ -389,6 +396,7 @@ __device__ __forceinline__ void conv_f16s3_epilogue(const ConvArgs& a, f32x4 (&a
                             const int rl = wm * WM - rg + i * MT + e + 4 * lh;
                             float s = acc[i][j][e];
                             if constexpr (KG == 2) s += T[rl * TS + nl];
+                            if constexpr (RAW) { T[rl * TS + nl] = s * inv; continue; }           // the convolution sum: exact undo of the pre-scales
                             float v = s * inv + bias;
                             if constexpr (decltype(act)::value == 2) v = silu_scaled(v, 1.0f / escale);
                             else if constexpr (decltype(act)::value == 1) v = __builtin_fmaxf(v, v * 0.1f);   // == v > 0 ? v : 0.1 v, bit for bit (signed zeros, infinities, NaN)
@@ -396,7 +404,8 @@ __device__ __forceinline__ void conv_f16s3_epilogue(const ConvArgs& a, f32x4 (&a
                         }
                 };
                 // uniform three-way branch around the loop: a per-value `if (a.leaky)` was a compare, a mask OR and a select per element
-                if (a.leaky == 2) col(std::integral_constant<int, 2>{});
+                if constexpr (RAW) col(std::integral_constant<int, 0>{});
+                else if (a.leaky == 2) col(std::integral_constant<int, 2>{});
                 else if (a.leaky) col(std::integral_constant<int, 1>{});
                 else col(std::integral_constant<int, 0>{});
             }
@@ -466,6 +475,12 @@ __device__ __forceinline__ void conv_f16s3_epilogue(const ConvArgs& a, f32x4 (&a
                 if (m >= M || bn * BN + c8 >= a.Cout) continue;
                 const f32x4 v0 = *reinterpret_cast<const f32x4*>(T + r * TS + c8);
                 const f32x4 v1 = *reinterpret_cast<const f32x4*>(T + r * TS + c8 + 4);
+                if constexpr (RAW) {                                      // 8 channels of row m of the dense [M][Npad] scratch (Cout <= Npad, both multiples of 8)
+                    float* rp = a.raw_out + (int64_t)m * a.Npad + bn * BN + c8;
+                    *reinterpret_cast<f32x4*>(rp) = v0;
+                    *reinterpret_cast<f32x4*>(rp + 4) = v1;
+                    continue;
+                }
                 float v[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
                 if constexpr (RES && F16) {
                     const f16x8 qh = rq_h[gi];
@@ -557,7 +572,7 @@ __device__ __forceinline__ void conv_f16s3_epilogue(const ConvArgs& a, f32x4 (&a
         }
         if (rg + RG < BM) __syncthreads();
     }
-    if constexpr (EPI != EPI_DECODE) split_overflow_report(a.ovf, amax);
+    if constexpr (EPI != EPI_DECODE && !RAW) split_overflow_report(a.ovf, amax);
 }
 
 }  // namespace rtod

@@ -49,6 +49,7 @@ struct StageRegs {
 // register budget must admit (2nd __launch_bounds__ argument): wave tiles of 32x64 / 48x32 or smaller are built for
 // 4 waves/SIMD — tools/ubench_tiles.hip: occupancy buys more MFMA utilisation than a larger wave tile.
 // EPI | EPI_F16: plain-f16 instance (hi planes only: half the loads and LDS panels, one MFMA per fragment pair).
+// EPI_SPLIT | EPI_RAW: raw-sum instance (the f16s3 main loop as it stands; the epilogue stores the fp32 sums to ConvArgs::raw_out).
 template <int BM, int BN, int NWM, int NWN, int MINW, int EPI>
 __global__ __launch_bounds__(NWM * NWN * 64, MINW)
 void conv_igemm_f16s3_kernel(const ConvArgs a, const int grid_m, const int grid_n) {
@@ -288,7 +289,7 @@ void conv_igemm_f16s3_kernel(const ConvArgs a, const int grid_m, const int grid_
 #ifdef RTOD_DIAG
     if (a.dbg & 4) return;                            // timing experiment: no epilogue
 #endif
-    conv_f16s3_epilogue<BM, BN, WM, WN, NT, epi_kind(EPI), SMEM, 1, false, F16>(a, acc, smem, bm, bn, tid, wm, wn, lr, lh, M);
+    conv_f16s3_epilogue<BM, BN, WM, WN, NT, epi_kind(EPI), SMEM, 1, false, F16, epi_raw(EPI)>(a, acc, smem, bm, bn, tid, wm, wn, lr, lh, M);
 #ifdef RTOD_STAMPS
     RTOD_GSTAMP(6)                                    // 6: epilogue
     if ((threadIdx.x & 63) == 0 && blockIdx.x < GSTAMP_BLOCKS) {
@@ -331,7 +332,12 @@ static int launch_h(const ConvArgs& a, hipStream_t s) {
     auto k_plain = conv_igemm_f16s3_kernel<BM, BN, NWM, NWN, MINW, EPI_SPLIT>;
     auto k_res_pw = conv_igemm_f16s3_kernel<BM, BN, NWM, NWN, MINW, EPI_SPLIT_RES_PW>;
     auto k_pw = conv_igemm_f16s3_kernel<BM, BN, NWM, NWN, MINW, EPI_SPLIT_PW>;
-    if (a.f16) {
+    if (a.raw_out) {
+        if (a.f16 || a.pw_wh || a.dec.enabled || a.res) { set_error("conv_igemm_f16s3: a raw-sum launch carries no shortcut, decode, hosted pointwise conv or plain-f16 store"); return RTOD_E_ARG; }
+        auto k_raw = conv_igemm_f16s3_kernel<BM, BN, NWM, NWN, MINW, EPI_SPLIT | EPI_RAW>;
+        hipLaunchKernelGGL(k_raw, dim3(gm * gn), dim3(NT), 0, s, a, gm, gn);
+    }
+    else if (a.f16) {
         if (a.pw_wh) { set_error("conv_igemm_f16s3: plain-f16 launch with a fused pointwise conv"); return RTOD_E_ARG; }
         auto f_dec = conv_igemm_f16s3_kernel<BM, BN, NWM, NWN, MINW, EPI_DECODE | EPI_F16>;
         auto f_res = conv_igemm_f16s3_kernel<BM, BN, NWM, NWN, MINW, EPI_SPLIT_RES | EPI_F16>;

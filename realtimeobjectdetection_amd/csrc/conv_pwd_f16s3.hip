@@ -33,6 +33,7 @@ namespace rtod {
 // BM x (32 NW) workgroup tile, NW waves, each a BM x 32 strip; NST slabs of 64 channels in the LDS ring.
 // EPI | EPI_F16: plain-f16 instance (slab blocks keep their 4 KiB layout, the lo pieces are neither DMA'd nor read; hi B fragments only,
 // one MFMA per pair; the counted waits scale with LB / LP below).
+// EPI_SPLIT | EPI_RAW: raw-sum instance: the f16s3 main loop and its counted waits unchanged, fp32 sums to ConvArgs::raw_out.
 template <int BM, int NW, int NST, int MINW, int EPI>
 __global__ __launch_bounds__(NW * 64, MINW)
 void conv_pwd_f16s3_kernel(const ConvArgs a, const int grid_m, const int grid_n) {
@@ -179,7 +180,7 @@ void conv_pwd_f16s3_kernel(const ConvArgs a, const int grid_m, const int grid_n)
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_setprio(0);
 
-    bandd_epilogue<BM, BN, BM, 32, NT, RG, epi_kind(EPI) == EPI_SPLIT_RES, 1, F16>(a, acc, smem, bm, bn, tid, 0, wn, lr, lh, M, 0);
+    bandd_epilogue<BM, BN, BM, 32, NT, RG, epi_kind(EPI) == EPI_SPLIT_RES, 1, F16, epi_raw(EPI)>(a, acc, smem, bm, bn, tid, 0, wn, lr, lh, M, 0);
 }
 
 template <int BM, int NW, int NST, int MINW>
@@ -196,9 +197,15 @@ static int launch_pwd(const ConvArgs& a, hipStream_t s) {
     const int fe = a.f16 ? 1 : 0;
     auto k_res = fe ? conv_pwd_f16s3_kernel<BM, NW, NST, MINW, EPI_SPLIT_RES | EPI_F16> : conv_pwd_f16s3_kernel<BM, NW, NST, MINW, EPI_SPLIT_RES>;
     auto k_plain = fe ? conv_pwd_f16s3_kernel<BM, NW, NST, MINW, EPI_SPLIT | EPI_F16> : conv_pwd_f16s3_kernel<BM, NW, NST, MINW, EPI_SPLIT>;
+    auto k_raw = conv_pwd_f16s3_kernel<BM, NW, NST, MINW, EPI_SPLIT | EPI_RAW>;
     if constexpr (lds > 64 * 1024) {                            // > 64 KiB of dynamic LDS needs the opt-in, once per device and instantiation
-        static std::atomic<unsigned long long> attr_done[2] = {{0}, {0}};
-        if (int rc = lds_opt_in(attr_done[fe], lds, "conv_pwd_f16s3", k_res, k_plain)) return rc;
+        static std::atomic<unsigned long long> attr_done[3] = {{0}, {0}, {0}};   // f16s3, f16, raw sums
+        if (a.raw_out) { if (int rc = lds_opt_in(attr_done[2], lds, "conv_pwd_f16s3", k_raw)) return rc; }
+        else if (int rc = lds_opt_in(attr_done[fe], lds, "conv_pwd_f16s3", k_res, k_plain)) return rc;
+    }
+    if (a.raw_out) {
+        hipLaunchKernelGGL(k_raw, dim3(gm * gn), dim3(NT), lds, s, ax, gm, gn);
+        return hip_fail(hipGetLastError(), "conv_pwd_f16s3 launch");
     }
     if (a.res) hipLaunchKernelGGL(k_res, dim3(gm * gn), dim3(NT), lds, s, ax, gm, gn);
     else hipLaunchKernelGGL(k_plain, dim3(gm * gn), dim3(NT), lds, s, ax, gm, gn);
@@ -231,6 +238,7 @@ int launch_conv_pwd_f16s3(const ConvArgs& a, int idx, hipStream_t s) {
         set_error("launch_conv_pwd: unsupported shape (k=%d s=%d pad=%d Cin=%d)", a.kh, a.stride, a.pad, a.Cin); return RTOD_E_ARG;
     }
     if (a.in_ldc % 8 || a.in_coff % 8 || a.K != a.Kpad || a.K != a.Cin || a.Npad % 128) { set_error("launch_conv_pwd: bad view / K"); return RTOD_E_ARG; }
+    if (a.raw_out && (a.f16 || a.res)) { set_error("launch_conv_pwd: a raw-sum launch carries no shortcut and no plain-f16 store"); return RTOD_E_ARG; }
     switch (idx) {
 #define RTOD_X_CASE(i, bm, nw, nst, minw) case i: return launch_pwd<bm, nw, nst, minw>(a, s);
         RTOD_PWD_TILES(RTOD_X_CASE)

@@ -45,6 +45,7 @@ Plan::~Plan() {
     if (d_scratch) (void)hipFree(d_scratch);
     if (d_bn_stats) (void)hipFree(d_bn_stats);
     if (d_bn_partial) (void)hipFree(d_bn_partial);
+    if (d_bn_raw) (void)hipFree(d_bn_raw);
     if (d_weights) (void)hipFree(d_weights);
 }
 
@@ -311,6 +312,7 @@ int Plan::set_option(const char* name, int value) {
         if (value && height != width) { set_error("set_option: bn_batch_stats is not supported on a rectangular plan (%dx%d)", height, width); return RTOD_E_ARG; }
         flag = &opt_bn_batch_stats;
     }
+    else if (k == "bn_batch_split") flag = &opt_bn_batch_split;
     else if (k == "k_slice_workgroups") flag = &opt_k_slice_workgroups;
     else if (k == "k_slices_split") flag = &opt_k_slices_split;
     else if (k == "patch_kernel") flag = &opt_patch_kernel;
@@ -547,7 +549,29 @@ bool Plan::uses_split(const Layer& L, int cin_p) const {
 
 int Plan::check_split_supported(int mode) const {
     const char* pn = mode == 2 ? "f16" : "f16s3";
-    if (opt_bn_batch_stats) { set_error("precision %s unsupported with bn_batch_stats (batch-statistics BatchNorm runs on the exact-fp32 kernels)", pn); return RTOD_E_CFG; }
+    if (opt_bn_batch_stats && !(opt_bn_batch_split && mode == 1)) {
+        set_error("precision %s unsupported with bn_batch_stats (batch-statistics BatchNorm runs on the exact-fp32 kernels%s)", pn,
+                  mode == 1 ? "; option bn_batch_split runs it on the split-f16 kernels" : "");
+        return RTOD_E_CFG;
+    }
+    if (opt_bn_batch_stats) {
+        // batch-statistics BatchNorm on the split kernels (option bn_batch_split): every BatchNorm conv after layer 0 needs a raw-sum
+        // instance — the generic, bandd and 1x1 slab tiles have one; the narrow, K-sliced and 16-filter stem kernels do not
+        if (opt_k_slices_split || opt_stem_pool) {
+            set_error("precision %s with bn_batch_stats + bn_batch_split: option %s is not supported in that mode (layer %d would run a kernel without a raw-sum instance)",
+                      pn, opt_k_slices_split ? "k_slices_split" : "stem_pool", opt_stem_pool ? 0 : 1);
+            return RTOD_E_CFG;
+        }
+        for (const auto& l : launches) {
+            if (l.kind != LK_CONV || l.layer == 0 || !layers[l.layer].bn) continue;
+            const Layer& L = layers[l.layer];
+            if (conv_c16_supported(L.cin)) {
+                set_error("precision %s with bn_batch_stats + bn_batch_split: layer %d is a narrow BatchNorm conv (Cin=%d: no raw-sum instance); use fp32", pn, l.layer, L.cin);
+                return RTOD_E_CFG;
+            }
+            if (l.out_layer == -2) { set_error("precision %s with bn_batch_stats + bn_batch_split: layer %d is a BatchNorm conv with a fused head decode; use fp32", pn, l.layer); return RTOD_E_CFG; }
+        }
+    }
     // precisions 1 and 2 keep every activation in the split f16 layout: every conv but the stem must read
     // 32-channel K-chunks (or, with option narrow_cin, exactly 16 channels), every shortcut / head must ride a conv epilogue, concats must be zero-copy
     for (const auto& l : launches) {
@@ -592,6 +616,12 @@ void Plan::layout_weights() {
         pc.stats_off = -1;
         if (opt_bn_batch_stats && layers[pc.layer].bn) { pc.stats_off = bn_stats_doubles; bn_stats_doubles += 2 * (int64_t)pc.Npad; }
     }
+    bn_raw_floats = 0;
+    if (bn_split_active())
+        for (const auto& pc : convs) {
+            const Layer& L = layers[pc.layer];
+            if (L.bn) bn_raw_floats = std::max(bn_raw_floats, (int64_t)max_batch * L.hout * L.wout * pc.Npad);
+        }
     for (auto& pc : convs) {
         const Layer& L = layers[pc.layer];
         pc.split = uses_split(L, pc.cin_p);
@@ -825,6 +855,7 @@ int Plan::load_weights(const float* w, size_t n) {
         bn_partial_count = (int64_t)bn_partial_doubles(maxn);
         RTOD_HIP(hipMalloc((void**)&d_bn_partial, sizeof(double) * (size_t)bn_partial_count));
     }
+    if (bn_raw_floats > 0 && !d_bn_raw) RTOD_HIP(hipMalloc((void**)&d_bn_raw, sizeof(float) * (size_t)bn_raw_floats));
     if (!d_scratch) {
         bool any = false;
         for (const auto& pc : convs) any = any || (!pc.split && !pc.stem && pc.slice_chunks > 0) || (pc.split && pc.ks_chunks > 0);
@@ -872,12 +903,15 @@ int Plan::f32_slice_mode(const Launch& l, int batch, int variant) const {
 // Plain-f16 plans (precision 2) run the tiles that have an f16 instance (the f16 column of the family table): the generic, bandd
 // (band layers, and the wide tile of the other 3x3 stride-1 layers), 1x1 slab, narrow and K-sliced tiles; never conv_band / ring /
 // patch, and no hosted pointwise epilogue (pw_active).
+// A BatchNorm conv of a batch-statistics split plan (raw_launch) runs the tiles with a raw-sum instance (the raw column) that its
+// family rules admit; for layers that are neither narrow nor sliced that is the set of a plain-f16 plan.
 bool Plan::tile_legal(const Launch& l, int /*batch*/, int v) const {
     const TileRef t = family_of(v);
     if (!t || l.kind != LK_CONV || l.conv_slot < 0 || !convs[l.conv_slot].split) return false;
     const PackedConv& pc = convs[l.conv_slot];
     const Layer& L = layers[l.layer];
     if (precision == 2 && !t.f16()) return false;
+    if (raw_launch(l) && !t.raw()) return false;
     // own K order / packed weights / summation order: narrow, sliced and band layers run their family only, and no other layer does
     if (pc.narrow || t.is(TF_C16)) return pc.narrow && t.is(TF_C16);
     if (pc.ks_chunks > 0 || t.is(TF_KS)) return pc.ks_chunks > 0 && t.is(TF_KS);
@@ -907,8 +941,8 @@ int Plan::default_tile(const Launch& l, int batch) const {
     // sliced: the 64x64 tile, and like f32_slice_mode one workgroup per (tile, slice) while the tile grid alone leaves the chip idle
     if (pc.ks_chunks > 0) return tile_id(TF_KS, ((M + 63) / 64) * ((L.cout + 63) / 64) < 512 ? 1 : 0);
     if (pc.band) {
-        if (precision != 2) return tile_id(TF_BAND, conv_band_default_mode(L.cin, L.hin, L.win));
-        const TileFamily& B = tile_family(TF_BAND);                                       // plain f16: the first legal (bandd) mode
+        if (precision != 2 && !raw_launch(l)) return tile_id(TF_BAND, conv_band_default_mode(L.cin, L.hin, L.win));
+        const TileFamily& B = tile_family(TF_BAND);                                       // plain f16, raw sums: the first legal (bandd) mode
         for (int m = 0; m < B.modes; ++m) if (tile_legal(l, batch, B.base + m)) return B.base + m;
         return B.base + B.f16_from;
     }
@@ -960,6 +994,7 @@ int Plan::launch_split_variant(ConvArgs& a, const PackedConv& pc, int v, hipStre
     const TileRef t = family_of(v);
     if (!t) { set_error("variant %d is no split-f16 tile", v); return RTOD_E_STATE; }
     if (precision == 2 && !t.f16()) { set_error("variant %d has no plain-f16 instance", v); return RTOD_E_STATE; }
+    if (a.raw_out && !t.raw()) { set_error("variant %d has no raw-sum instance", v); return RTOD_E_STATE; }
     if (pc.narrow != t.is(TF_C16)) {
         set_error(pc.narrow ? "variant %d requested for a narrow (Cin = 16) layer" : "narrow variant %d requested for a layer without tap-major weights", v);
         return RTOD_E_STATE;
@@ -1044,7 +1079,8 @@ int Plan::tune_launch(size_t li, ConvArgs& a, int batch, hipStream_t s) {
     // two layers with the same output shape but another input extent or padding are other problems, e.g. across rectangular plans)
     const std::vector<int> key = {L.cin, L.cout, L.size, L.stride, L.hout, L.wout, l.in2_layer >= 0, l.out_layer == -2, pw ? a.pw_cout : 0,
                                   convs[l.conv_slot].band ? 1 : 0, opt_ring_kernel ? 1 : 0, opt_patch_kernel ? 1 : 0, opt_pwd_kernel ? 1 : 0, L.act,
-                                  precision, L.hin, L.win, L.pad, convs[l.conv_slot].ks_chunks, opt_k_slice_workgroups ? 1 : 0};
+                                  precision, L.hin, L.win, L.pad, convs[l.conv_slot].ks_chunks, opt_k_slice_workgroups ? 1 : 0,
+                                  a.raw_out ? 1 : 0};      // (a raw-sum launch times other kernels over another candidate set: never an eval plan's id)
     auto it = tune_cache.find(key);
     if (it != tune_cache.end()) { tuning[li] = it->second; return RTOD_OK; }
     // process-wide memo (device, batch, shape): a second plan of the same network (bench.py keeps two batches in flight)
@@ -1127,9 +1163,18 @@ bool Plan::ks_sched_b_fits(const Launch& l, int batch) const {
     const int64_t S = (pc.Kpad / 32 + pc.ks_chunks - 1) / pc.ks_chunks;
     return S * batch * L.hout * L.wout * pc.Npad <= KS_SCRATCH_FLOATS;
 }
-bool Plan::pw_active() const { return precision == 1 && opt_fuse_pointwise; }
+// fp32 view over the raw-sum scratch for the conv of launch `l` at this batch: dense rows of Npad floats (base null: no scratch / too small)
+View Plan::bn_raw_view(const Launch& l, int batch) const {
+    View v;
+    const Layer& L = layers[l.layer];
+    const PackedConv& pc = convs[l.conv_slot];
+    if (!d_bn_raw || (int64_t)batch * L.hout * L.wout * pc.Npad > bn_raw_floats) return v;
+    v.base = d_bn_raw; v.ldc = pc.Npad; v.coff = 0; v.C = L.cout; v.H = L.hout; v.W = L.wout;
+    return v;
+}
+bool Plan::pw_active() const { return precision == 1 && opt_fuse_pointwise && !bn_split_active(); }
 bool Plan::stem_pool_fused() const { return precision >= 1 && stem_pool_pattern && !keep_all && convs[launches[0].conv_slot].stem16; }
-bool Plan::stem2_active() const { return precision == 1 && opt_stem2_kernel && stem2_pattern && !keep_all && convs[launches[0].conv_slot].split; }
+bool Plan::stem2_active() const { return precision == 1 && !bn_split_active() && opt_stem2_kernel && stem2_pattern && !keep_all && convs[launches[0].conv_slot].split; }
 
 int Plan::forward(const float* x, int batch, float* out, hipStream_t s, float* launch_ms, bool tune) {
     if (!weights_loaded) { set_error("forward: load_weights has not been called"); return RTOD_E_STATE; }
@@ -1166,12 +1211,22 @@ int Plan::forward(const float* x, int batch, float* out, hipStream_t s, float* l
                     a.slice_chunks = mode ? pc.slice_chunks : 0;
                     if (mode == 2) { a.partial = d_scratch; a.partial_floats = scratch_floats; }
                     if (opt_bn_batch_stats && L.bn) {            // raw conv, then statistics + normalise + activation + shortcut in place
-                        if (a.dec.enabled || a.out_split || !d_bn_stats || pc.stats_off < 0) { set_error("forward: layer %d: batch-statistics BatchNorm on an unsupported launch", l.layer); return RTOD_E_STATE; }
+                        if (a.dec.enabled || (a.out_split && !bn_split_active()) || !d_bn_stats || pc.stats_off < 0) { set_error("forward: layer %d: batch-statistics BatchNorm on an unsupported launch", l.layer); return RTOD_E_STATE; }
                         a.leaky = 0; a.res = nullptr;
-                        rc = launch_conv(a, v, s);
-                        if (rc) return rc;
                         const View o = view_of(l.out_layer);
                         View r; if (l.in2_layer >= 0) r = view_of(l.in2_layer);
+                        if (a.out_split) {                           // split plan (option bn_batch_split), layer 0: raw sums to the scratch, normalised into the split format
+                            const View rv = bn_raw_view(l, batch);
+                            if (!rv.base) { set_error("forward: layer %d: no raw-sum scratch", l.layer); return RTOD_E_STATE; }
+                            a.out = rv.base; a.out_ldc = rv.ldc; a.out_coff = 0; a.out_split = 0;
+                            rc = launch_conv(a, v, s);
+                            if (rc) return rc;
+                            rc = launch_bn_batch_split(rv, o, l.in2_layer >= 0 ? &r : nullptr, batch, d_bn_stats + pc.stats_off, pc.Npad, d_weights + pc.bn_off, pc.Npad, L.act,
+                                                       d_bn_partial, bn_partial_count, overflow_flag, s);
+                            break;
+                        }
+                        rc = launch_conv(a, v, s);
+                        if (rc) return rc;
                         rc = launch_bn_batch(o, o, l.in2_layer >= 0 ? &r : nullptr, batch, d_bn_stats + pc.stats_off, pc.Npad, d_weights + pc.bn_off, pc.Npad, L.act, d_bn_partial, bn_partial_count, s);
                     } else
                     rc = launch_conv(a, v, s);
@@ -1183,8 +1238,20 @@ int Plan::forward(const float* x, int batch, float* out, hipStream_t s, float* l
                                                  reinterpret_cast<const _Float16*>(d_weights + p0.wl_off), d_weights + p0.s_off, d_weights + p0.b_off,
                                                  layers[0].act, a, s);
                 } else {
+                    const bool raw = raw_launch(l);            // BatchNorm conv of a batch-statistics split plan: raw sums, statistics, normalise (+ activation + shortcut)
+                    View rv;
+                    if (raw) {
+                        rv = bn_raw_view(l, batch);
+                        if (!rv.base || a.dec.enabled || a.pw_wh || !d_bn_stats || pc.stats_off < 0) { set_error("forward: layer %d: batch-statistics BatchNorm on an unsupported launch", l.layer); return RTOD_E_STATE; }
+                        a.raw_out = rv.base; a.res = nullptr; a.leaky = 0;
+                    }
                     if (tune_now) { rc = tune_launch(li, a, batch, s); if (rc) return rc; }      // (never reached for the fused stem launch)
                     rc = launch_split_variant(a, pc, tune_now && tuning[li] >= 0 ? tuning[li] : variant_for(l, batch), s);
+                    if (!rc && raw) {
+                        View r; if (l.in2_layer >= 0) r = view_of(l.in2_layer);
+                        rc = launch_bn_batch_split(rv, view_of(l.out_layer), l.in2_layer >= 0 ? &r : nullptr, batch, d_bn_stats + pc.stats_off, pc.Npad, d_weights + pc.bn_off, pc.Npad,
+                                                   L.act, d_bn_partial, bn_partial_count, overflow_flag, s);
+                    }
                 }
                 break;
             }
@@ -1318,7 +1385,9 @@ std::string Plan::describe() const {
         os << "{\"C\":" << b.C << ",\"H\":" << b.H << ",\"W\":" << b.W << ",\"first\":" << b.first << ",\"last\":" << b.last << ",\"offset\":" << b.offset
            << ",\"floats_per_frame\":" << b.floats_per_frame << "}";
     }
-    os << "]}";
+    os << "]";
+    if (bn_split_active()) os << ",\"bn_batch_split\":true,\"bn_raw_bytes\":" << bn_raw_floats * 4;     // batch-statistics BatchNorm on the split kernels: its raw-sum scratch
+    os << "}";
     return os.str();
 }
 

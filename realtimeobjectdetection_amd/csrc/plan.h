@@ -92,6 +92,9 @@ struct Plan {
     int64_t bn_stats_doubles = 0;
     double* d_bn_partial = nullptr;   // per-range partial sums of the two-stage statistics kernel
     int64_t bn_partial_count = 0;
+    float* d_bn_raw = nullptr;        // option bn_batch_split: the raw sums of the BatchNorm conv that is running, dense fp32 rows [M][Npad] (never in place:
+                                      // an fp32 slice of a zero-copy concat pixel would overlap the other producers' hi / lo planes)
+    int64_t bn_raw_floats = 0;        // max over BatchNorm convs of max_batch * hout * wout * Npad (layout_weights); 0 unless bn_split_active()
     float* d_scratch = nullptr;       // slice panels of the one-workgroup-per-K-slice schedules (exact-fp32 plans; split plans with a sliced layer)
     int64_t scratch_floats = 0;
     bool weights_loaded = false;
@@ -104,6 +107,8 @@ struct Plan {
     bool opt_stem_kernel = true;      // dedicated NCHW-reading kernel for layer 0 (else pack + generic conv)
     bool opt_band_kernel = true;      // LDS-band kernel for the 3x3 stride-1 layers it supports
     bool opt_bn_batch_stats = false;  // exact-fp32 plans: BatchNorm on the statistics of the batch (what the reference runs: no .eval()), not folded
+    bool opt_bn_batch_split = false;  // ... on the split-f16 kernels (precision 1 only; inert without bn_batch_stats): raw-sum conv instances, statistics,
+                                      // a normalise kernel that writes the split format
     bool opt_k_slices = true;         // exact-fp32 kernels: deep small-grid layers summed in K slices (own workgroups when the grid is small)
     bool opt_k_slice_workgroups = true;   // ... (off: always the in-workgroup schedule — same bits; A/B and tests).  Governs conv_ks_f16s3 too
     bool opt_k_slices_split = false;  // precisions 1 / 2: deep small-grid convs summed in K slices on conv_ks_f16s3.hip (single-frame latency; opt-in)
@@ -152,6 +157,9 @@ struct Plan {
     int launch_split_variant(ConvArgs& a, const PackedConv& pc, int v, hipStream_t s) const;
     int f32_slice_mode(const Launch& l, int batch, int variant) const;   // 0 plain, 1 slices inside the workgroup, 2 one workgroup per slice
     bool ks_sched_b_fits(const Launch& l, int batch) const;              // sliced split layer: the slice panels of this batch fit the scratch
+    bool bn_split_active() const { return opt_bn_batch_stats && opt_bn_batch_split && precision == 1; }   // batch-statistics BatchNorm on the split kernels
+    bool raw_launch(const Launch& l) const { return bn_split_active() && l.kind == LK_CONV && layers[l.layer].bn; }   // a BatchNorm conv of such a plan: raw sums, then normalise
+    View bn_raw_view(const Launch& l, int batch) const;   // fp32 view over d_bn_raw for this launch's conv
     bool pw_active() const;                     // fused pointwise convs in use (precision 1, option fuse_pointwise)
     bool stem2_pattern = false;                 // launches 0 / 1 are a stem and the stride-2 conv conv_stem2_f16s3 fuses (set by plan_buffers)
     bool stem2_active() const;                  // ... and the plan runs them fused (split-f16 precision, option stem2_kernel)

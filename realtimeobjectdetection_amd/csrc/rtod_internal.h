@@ -100,6 +100,8 @@ struct ConvArgs {
     int xcd_by_n = 0;                           // split kernels: workgroup -> XCD by output-channel tile instead of by pixel tile (see launch_band)
     int out_split = 0;                          // exact-fp32 kernel only: write the output in the split format
     int f16 = 0;                                // split kernels: 1 = plain-f16 instance (precision mode 2: hi planes only, one MFMA per fragment pair)
+    float* raw_out = nullptr;                   // split kernels, raw-sum instances (EPI_RAW; plan option bn_batch_split): acc * inv_scale[n] as dense fp32 rows [M][Npad];
+                                                // no bias, activation, shortcut or split store (`out` is not written)
     // exact-fp32 kernel and the K-sliced split family (conv_ks_f16s3.hip): K slices (conv_igemm_f32.hip).  slice_chunks > 0: the K sum is formed slice by slice (a property of
     // the layer); partial != nullptr: one workgroup per slice, raw sums to this scratch ([slices][M][Npad] floats), then a reduction
     int slice_chunks = 0;
@@ -162,6 +164,9 @@ __device__ __forceinline__ int xcd_remap(int id, int n) {
 
 // epilogue-code flag of the plain-f16 kernel instances (precision mode 2): EPI | EPI_F16 (conv_f16s3_common.h)
 constexpr int EPI_F16 = 8;
+// epilogue-code flag of the raw-sum instances (batch-statistics BatchNorm on the split kernels, plan option bn_batch_split):
+// EPI_SPLIT | EPI_RAW.  Generic, bandd and 1x1 slab tiles only (the raw column of the family table)
+constexpr int EPI_RAW = 16;
 
 enum ConvVariant { CV_128x128 = 0, CV_128x64 = 1, CV_64x64 = 2, CV_128x32 = 3, CV_COUNT };
 struct ConvVariantInfo { int bm, bn; const char* name; };
@@ -269,6 +274,7 @@ enum TileFamilyId { TF_GENERIC = 0, TF_BAND, TF_RING, TF_PWD, TF_PATCH, TF_C16, 
 struct TileFamily {
     int id, base, modes;
     int f16_from;                                                   // modes >= this have a plain-f16 instance (== modes: none has)
+    int raw_from;                                                   // modes >= this have a raw-sum instance (EPI_RAW; == modes: none has)
     const ConvVariantInfo& (*info)(int mode);
     int (*kernel_name)(int mode, int epi, char* buf, size_t len);
     int (*launch)(const ConvArgs& a, int mode, hipStream_t s);
@@ -278,6 +284,7 @@ struct TileRef {                                                    // a tile id
     explicit operator bool() const { return fam != nullptr; }
     bool is(int family) const { return fam && fam->id == family; }
     bool f16() const { return fam && mode >= fam->f16_from; }
+    bool raw() const { return fam && mode >= fam->raw_from; }
     bool ks_sched_b() const { return is(TF_KS) && (mode & 1); }    // one workgroup per (tile, slice); id - 1 is schedule A of the same tile
     bool bandd_wide() const { return is(TF_BAND) && mode == BANDD_WIDE_MODE; }
 };
@@ -305,6 +312,11 @@ int launch_upsample_nearest2x(const View& in, const View& out, int B, hipStream_
 int launch_bn_batch(const View& x, const View& y, const View* res, int B, double* stats, int sstride, const float* bn, int gstride, int act,
                     double* partial, int64_t partial_doubles, hipStream_t s);    // partial: scratch of the two-stage statistics (bn_partial_doubles), or null
 size_t bn_partial_doubles(int max_channels);
+// the same on a split-f16 plan (plan option bn_batch_split): `raw` is the fp32 view of the conv's raw sums (dense scratch rows), the
+// statistics kernels above read it, bn_apply_split_kernel normalises, applies the activation, adds the shortcut operand of its split
+// view and stores the split format into `y` (ldc / coff honoured: concat slices)
+int launch_bn_batch_split(const View& raw, const View& y, const View* res, int B, double* stats, int sstride, const float* bn, int gstride, int act,
+                          double* partial, int64_t partial_doubles, int32_t* ovf, hipStream_t s);
 // running_mean / running_var update of every BatchNorm layer of a batch-statistics plan in one launch (aux_kernels.hip)
 struct BnUpdateEntry { float* running_mean; float* running_var; int64_t stats_off; double unbias; int sstride; int channels; };
 constexpr int BN_UPDATE_MAX = 32;                 // entries per launch (by-value kernel argument: 32 x 40 bytes)

@@ -274,8 +274,11 @@ class Darknet(nn.Module):
         # (the fast path, frame-independent); training mode = the statistics of the batch — what the reference's callers
         # actually run, since they never call .eval() (detect.py:185-194).  That mode is a parity path on the
         # exact-fp32 kernels (conv -> per-channel statistics -> normalise), several times slower and batch-dependent.
+        # options = {"bn_batch_split": 1} (opt-in) runs that mode on the split-f16 kernels where the cfg allows it: raw-sum conv
+        # instances, the same statistics kernels, a normalise kernel that writes the split format (precision "f16s3" / "auto").
         batch_bn = bool(self.training and not self.bn_running_stats_in_train)
-        if batch_bn and self.precision in ("f16s3", "f16"):
+        bn_split = bool(batch_bn and int(self.options.get("bn_batch_split", 0)))
+        if batch_bn and (self.precision == "f16" or (self.precision == "f16s3" and not bn_split)):
             raise RuntimeError("Darknet is in training mode (batch-statistics BatchNorm, like the reference without .eval()): that "
                                "path runs on the exact-fp32 kernels only; call .eval() for the %s kernels or set precision='auto'"
                                % ("split-f16" if self.precision == "f16s3" else "plain-f16"))
@@ -290,7 +293,7 @@ class Darknet(nn.Module):
         opts = dict(self.options)
         if batch_bn:
             opts["bn_batch_stats"] = 1
-        key = (inp_dim, int(max_batch), device.index, bool(self.keep_all_layers), "fp32" if batch_bn else self.precision, tuple(sorted(opts.items())),
+        key = (inp_dim, int(max_batch), device.index, bool(self.keep_all_layers), "fp32" if batch_bn and not bn_split else self.precision, tuple(sorted(opts.items())),
                self.input_width is not None, width)
         if self._plan is None or self._plan_key != key:
             self._destroy_plan()
@@ -312,7 +315,7 @@ class Darknet(nn.Module):
             # "auto": the split-f16 kernels when the cfg supports them (yolov3 does; a cfg with a conv after layer 0 whose
             # Cin % 32 != 0 does not — yolov3-tiny's 16-channel layer 2 does with options = {"narrow_cin": 1}, already set
             # above), else the exact-fp32 MFMA kernels.  Both are HIP paths.
-            if self.precision == "fp32" or batch_bn:
+            if self.precision == "fp32" or (batch_bn and not bn_split):
                 self.active_precision = "fp32"
             elif self.precision == "f16":                        # opt-in only: "auto" never picks it
                 _ffi.check(lib.rtod_plan_set_precision(self._plan, 2))
