@@ -137,8 +137,25 @@ int rtod_plan_set_precision(rtod_plan* plan, int mode);
  *                       hosted pointwise conv, no fused stem.  Tiles: those with a raw-sum instance that the layer's family rules
  *                       admit (rtod_plan_set_tiles refuses the others).  RTOD_E_CFG from rtod_plan_set_precision (or from the option
  *                       call that completes the combination): precision 2; a BatchNorm conv with Cin == 16 (with or without
- *                       "narrow_cin"); "k_slices_split" or "stem_pool" together with the mode.  Accepted before or after
+ *                       "narrow_cin"); "k_slices_split" or "stem_pool" together with the mode (see "bn_split_narrow").  Accepted before or after
  *                       rtod_plan_set_precision.  rtod_plan_bn_batch_stats / rtod_plan_bn_update_running work as in fp32 plans
+ *   "bn_split_narrow"   (default 0) read only when "bn_batch_stats", "bn_batch_split" and precision 1 are all in force (otherwise inert: same
+ *                       plan, same bits): that mode also for YOLOv3-tiny's kind of graph.  A BatchNorm conv with Cin == 16 is accepted
+ *                       (needs "narrow_cin") and runs a raw-sum instance of a narrow tile (ids 140 ..., epilogue code 16;
+ *                       rtod_plan_set_tiles accepts the narrow ids on it and refuses the others).  "stem_pool" is accepted together
+ *                       with the mode: a matching layer 0 with BatchNorm runs the raw-sum instance of the 16-filter split stem (NCHW
+ *                       input read directly, no pack launch, no exact-fp32 conv); a layer 0 that does not match stays on the
+ *                       exact-fp32 kernel.  Rows of the raw-sum scratch are Cout rounded up to 8 floats for those two kernels, Npad
+ *                       floats for the others; "bn_raw_bytes" is the maximum over the BatchNorm convs of max_batch * hout * wout *
+ *                       row * 4.  Still RTOD_E_CFG, the plan left as it was, in either call order: precision 2, "k_slices_split", a
+ *                       BatchNorm conv with a fused head decode
+ *   "fuse_bn_pool"      (default 1, read only when "bn_split_narrow" is in force) where a BatchNorm conv (raw-sum launch of any family,
+ *                       layer 0 on the exact-fp32 kernel too) without a fused shortcut is followed by a [maxpool] size 2 / stride 2
+ *                       (not symmetric) that alone reads it, its hout and wout are even and keep_all_layers is off, the normalise
+ *                       kernel also does the pool: the conv's full-resolution map is never stored (describe: "fused_into": <pool
+ *                       index>; rtod_plan_read_layer on the conv: RTOD_E_STATE), the pool's launch entry stays in the list and
+ *                       enqueues nothing.  Bit-identical to the stand-alone normalise + max-pool kernels, batch statistics and
+ *                       range flag included; 0: always stand-alone
  *   "k_slices"          exact-fp32 plans: deep small-grid layers summed in K slices (conv_igemm_f32.hip); 0: one chain
  *   "k_slice_workgroups" ... one workgroup per slice when the grid is small; 0: always inside the workgroup (same bits).
  *                       Governs the K-sliced split-f16 tiles of "k_slices_split" in the same way

@@ -167,6 +167,32 @@ def stem_pool_mini_cfg(height=64, width=64, classes=3) -> str:
     return "\n".join(L) + "\n"
 
 
+def bn_pool_mini_cfg(height=64, width=64, classes=3) -> str:
+    """Small tiny-like test network for batch-statistics BatchNorm on the narrow split-f16 kernels with the max-pool in the
+    normalise kernel (plan options narrow_cin + stem_pool + bn_batch_split + bn_split_narrow + fuse_bn_pool): a 16-filter stem, a
+    Cin = 16 conv and a 32-channel conv, each followed by a 2x2 / stride-2 max-pool that alone reads it (the third pooled map lands in
+    a zero-copy concat slice at channel 32, and its 96 filters put the statistics on the one-stage path); a 24-filter conv
+    (one-stage statistics, stand-alone normalise); a conv read by its 2x2 / stride-2 pool AND by a route; a conv followed by a
+    size-2 / stride-1 pool.  One head at stride 8; 64x64 and 40x40 (maps 40, 20, 10, 5: the last one odd) are legal shapes."""
+    nout = 3 * (5 + classes)
+    L = _net(height, width)
+    L += _conv(16, 3, 1) + _maxpool(2, 2)              # 0, 1: 16-filter stem, 16 @ H/2
+    L += _conv(32, 3, 1) + _maxpool(2, 2)              # 2, 3: Cin 16, 32 @ H/4
+    L += _conv(96, 3, 1) + _maxpool(2, 2)              # 4, 5: Cin 32, 96 filters (256 % 24 != 0); the pool writes channel 32 of route 7's buffer, 96 @ H/8
+    L += _conv(32, 1, 1)                               # 6: Cin 96, writes channel 0 of route 7's buffer
+    L += _route(-1, 5)                                 # 7: layers 6 and 5, 128 @ H/8, zero-copy
+    L += _conv(24, 1, 1)                               # 8: 24 filters (256 % 6 != 0): one-stage statistics; channel 8 of route 11's buffer
+    L += _route(-2)                                    # 9: layer 7 again
+    L += _conv(8, 1, 1)                                # 10: 8 filters, channel 0 of route 11's buffer
+    L += _route(-1, 8)                                 # 11: layers 10 and 8, 32 @ H/8
+    L += _conv(32, 3, 1)                               # 12: read by pool 13 and by route 14: never fused
+    L += _maxpool(2, 2)                                # 13: 32 @ H/16, read by nothing
+    L += _route(-2)                                    # 14: layer 12 again
+    L += _conv(32, 1, 1) + _maxpool(2, 1)              # 15, 16: a size-2 / stride-1 pool: never fused
+    L += _conv(nout, 1, 1, bn=False, act="linear") + _yolo((0, 1, 2), _ANCHORS_V3, 9, classes)   # 17, 18: head, fused decode
+    return "\n".join(L) + "\n"
+
+
 def kslice_mini_cfg(height=64, width=64, classes=3) -> str:
     """Small test network for the K-sliced split-f16 convolutions (plan option k_slices_split).  Every map is at most 52x52 at the
     test shapes, so the rule slices each conv with at least 8 K-chunks of 32 that has no fused head decode: slices of 2 chunks

@@ -566,16 +566,80 @@ __global__ void bn_apply_split_kernel(View x, View y, View res, int has_res, int
     split_overflow_report(ovf, amax);
 }
 
+// The same followed by the 2x2 / stride-2 max-pool that alone reads the conv (plan options bn_split_narrow + fuse_bn_pool): the
+// conv's full-resolution split map is never stored.  One thread per 8 channels of a POOLED pixel of `y` (the pool's view).  Every
+// window position, in (dy, dx) order, is normalised, activated and split exactly as bn_apply_split_kernel does it (amax over all
+// four: the range flag equals the stand-alone path's); the winner is chosen as maxpool_split_kernel chooses it — hi + lo compared in
+// fp32, a pair replaces the held one only when strictly greater — and its pair is stored as it stands.  Bit-identical to
+// bn_apply_split_kernel followed by maxpool_split_kernel.  x.H and x.W are even (y.H = x.H / 2, y.W = x.W / 2).
+template <bool WB>
+__global__ void bn_apply_split_pool_kernel(View x, View y, int B, const float* __restrict__ wb, const double* __restrict__ stats,
+                                           int sstride, const float* __restrict__ bn, int gstride, int act, int32_t* ovf) {
+    const int C8 = x.C / 8;
+    const int64_t total = (int64_t)B * y.H * y.W * C8;
+    _Float16* yb = reinterpret_cast<_Float16*>(y.base);
+    float amax = 0.f;
+    for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
+        const int c = (int)(t % C8) * 8;
+        int64_t p = t / C8;
+        const int ox = (int)(p % y.W); p /= y.W;
+        const int oy = (int)(p % y.H);
+        const int b = (int)(p / y.H);
+        float w[8], bb[8];
+        if constexpr (WB) {
+            const f32x4 w0 = *reinterpret_cast<const f32x4*>(wb + c), w1 = *reinterpret_cast<const f32x4*>(wb + c + 4);
+            const f32x4 b0 = *reinterpret_cast<const f32x4*>(wb + sstride + c), b1 = *reinterpret_cast<const f32x4*>(wb + sstride + c + 4);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) { w[e] = e < 4 ? w0[e] : w1[e - 4]; bb[e] = e < 4 ? b0[e] : b1[e - 4]; }
+        } else {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const double invstd = 1.0 / sqrt(stats[sstride + c + e] + 1e-5);
+                w[e] = (float)(invstd * (double)bn[gstride + c + e]);                                   // gamma / sqrt(var + eps)
+                bb[e] = (float)((double)bn[c + e] - stats[c + e] * invstd * (double)bn[gstride + c + e]);
+            }
+        }
+        // the four window rows first: eight 16-byte loads in flight
+        f32x4 v0[4], v1[4];
+#pragma unroll
+        for (int pos = 0; pos < 4; ++pos) {
+            const float* xp = x.base + x.coff + c + (((int64_t)b * x.H + 2 * oy + (pos >> 1)) * x.W + 2 * ox + (pos & 1)) * x.ldc;
+            v0[pos] = *reinterpret_cast<const f32x4*>(xp); v1[pos] = *reinterpret_cast<const f32x4*>(xp + 4);
+        }
+        float m[8];
+        f16x8 mh, ml;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) { m[e] = -INFINITY; mh[e] = (_Float16)0.f; ml[e] = (_Float16)0.f; }
+#pragma unroll
+        for (int pos = 0; pos < 4; ++pos)
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                float u = (e < 4 ? v0[pos][e] : v1[pos][e - 4]) * w[e] + bb[e];
+                u = apply_act(u, act);
+                _Float16 h, l;
+                split_f16(u * SPLIT_SCALE, h, l, amax);
+                const float s = (float)h + (float)l;
+                if (s > m[e]) { m[e] = s; mh[e] = h; ml[e] = l; }
+            }
+        _Float16* o = yb + (((int64_t)b * y.H + oy) * y.W + ox) * 2 * y.ldc + y.coff + c;
+        store_act16(o, mh, false);
+        store_act16(o + y.ldc, ml, false);
+    }
+    split_overflow_report(ovf, amax);
+}
+
 static bool view_ok8_split(const View& v) { return v.base && v.split == 1 && v.C % 8 == 0 && v.ldc % 8 == 0 && v.coff % 8 == 0; }
 
 int launch_bn_batch_split(const View& raw, const View& y, const View* res, int B, double* stats, int sstride, const float* bn, int gstride, int act,
-                          double* partial, int64_t partial_doubles, int32_t* ovf, hipStream_t s) {
+                          double* partial, int64_t partial_doubles, int32_t* ovf, hipStream_t s, int pool) {
     if (raw.split || !raw.base || raw.C % 8 || raw.ldc % 8 || raw.coff % 8) { set_error("bn_batch_split: bad raw-sum view"); return RTOD_E_ARG; }
-    if (!view_ok8_split(y) || raw.C != y.C || raw.H != y.H || raw.W != y.W || !stats || !bn || gstride < raw.C || sstride < raw.C || B < 1) { set_error("bn_batch_split: bad views"); return RTOD_E_ARG; }
+    if (pool && (res || raw.H % 2 || raw.W % 2)) { set_error("bn_batch_split: the fused 2x2 max-pool needs an even map and no shortcut"); return RTOD_E_ARG; }
+    const int yh = pool ? raw.H / 2 : raw.H, yw = pool ? raw.W / 2 : raw.W;
+    if (!view_ok8_split(y) || raw.C != y.C || yh != y.H || yw != y.W || !stats || !bn || gstride < raw.C || sstride < raw.C || B < 1) { set_error("bn_batch_split: bad views"); return RTOD_E_ARG; }
     if (res && (!view_ok8_split(*res) || res->C != raw.C || res->H != raw.H || res->W != raw.W)) { set_error("bn_batch_split: bad shortcut view"); return RTOD_E_ARG; }
     const int C4 = raw.C / 4;
     const int64_t npix = (int64_t)B * raw.H * raw.W;
-    const int64_t total = npix * (raw.C / 8);
+    const int64_t total = (int64_t)B * yh * yw * (raw.C / 8);      // threads of the normalise kernel: 8 channels of a written pixel
     const View r = res ? *res : y;
     const int nparts = (int)std::min<int64_t>(BN_PARTS_MAX, std::max<int64_t>(1, npix / 128));
     // the statistics path of launch_bn_batch: two stages where the channel count allows, else one workgroup per 4 channels
@@ -585,12 +649,14 @@ int launch_bn_batch_split(const View& raw, const View& y, const View* res, int B
         float* wb = reinterpret_cast<float*>(partial + (int64_t)nparts * 2 * sstride);
         hipLaunchKernelGGL(bn_stats_final_kernel, dim3((raw.C + 15) / 16), dim3(256), 0, s, partial, sstride, nparts, raw.C, (double)npix, stats, sstride, bn, gstride, wb);
         if (hipGetLastError() != hipSuccess) return hip_fail(hipGetLastError(), "bn_stats_final launch");
-        hipLaunchKernelGGL(bn_apply_split_kernel<true>, dim3(grid_for(total, 256)), dim3(256), 0, s, raw, y, r, res ? 1 : 0, B, wb, stats, sstride, bn, gstride, act, ovf);
+        if (pool) hipLaunchKernelGGL(bn_apply_split_pool_kernel<true>, dim3(grid_for(total, 256)), dim3(256), 0, s, raw, y, B, wb, stats, sstride, bn, gstride, act, ovf);
+        else hipLaunchKernelGGL(bn_apply_split_kernel<true>, dim3(grid_for(total, 256)), dim3(256), 0, s, raw, y, r, res ? 1 : 0, B, wb, stats, sstride, bn, gstride, act, ovf);
         return hip_fail(hipGetLastError(), "bn_apply_split launch");
     }
     hipLaunchKernelGGL(bn_stats_kernel, dim3(raw.C / 4), dim3(256), 0, s, raw, B, stats, sstride);
     if (hipGetLastError() != hipSuccess) return hip_fail(hipGetLastError(), "bn_stats launch");
-    hipLaunchKernelGGL(bn_apply_split_kernel<false>, dim3(grid_for(total, 256)), dim3(256), 0, s, raw, y, r, res ? 1 : 0, B, (const float*)nullptr, stats, sstride, bn, gstride, act, ovf);
+    if (pool) hipLaunchKernelGGL(bn_apply_split_pool_kernel<false>, dim3(grid_for(total, 256)), dim3(256), 0, s, raw, y, B, (const float*)nullptr, stats, sstride, bn, gstride, act, ovf);
+    else hipLaunchKernelGGL(bn_apply_split_kernel<false>, dim3(grid_for(total, 256)), dim3(256), 0, s, raw, y, r, res ? 1 : 0, B, (const float*)nullptr, stats, sstride, bn, gstride, act, ovf);
     return hip_fail(hipGetLastError(), "bn_apply_split launch");
 }
 

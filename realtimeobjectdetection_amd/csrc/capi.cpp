@@ -227,7 +227,7 @@ int rtod_plan_set_keep_all_layers(rtod_plan* plan, int keep) {
 int rtod_plan_layer_shape(const rtod_plan* plan, int layer, int* c, int* h, int* w) {
     if (!plan || layer < 0 || layer >= (int)plan->p.layers.size() || !c || !h || !w) { set_error("layer_shape: bad args"); return RTOD_E_ARG; }
     const View v = plan->p.view_of(layer);
-    if (v.C == 0 || (layer == 0 && plan->p.stem_pool_fused())) { set_error("layer %d is fused into its consumer and has no materialised output", layer); return RTOD_E_STATE; }
+    if (v.C == 0 || (layer == 0 && plan->p.stem_pool_fused()) || plan->p.bn_pool_fused(layer)) { set_error("layer %d is fused into its consumer and has no materialised output", layer); return RTOD_E_STATE; }
     *c = v.C; *h = v.H; *w = v.W;
     return RTOD_OK;
 }
@@ -237,7 +237,7 @@ int rtod_plan_read_layer(rtod_plan* plan, int layer, int batch, float* out_dev_n
     if (!plan || layer < 0 || layer >= (int)plan->p.layers.size()) { set_error("read_layer: bad args"); return RTOD_E_ARG; }
     if (batch < 1 || batch > plan->p.max_batch) { set_error("read_layer: bad batch"); return RTOD_E_ARG; }
     const View v = plan->p.view_of(layer);
-    if (!v.base || (layer == 0 && plan->p.stem_pool_fused())) { set_error("layer %d has no materialised output (fused) or weights not loaded", layer); return RTOD_E_STATE; }
+    if (!v.base || (layer == 0 && plan->p.stem_pool_fused()) || plan->p.bn_pool_fused(layer)) { set_error("layer %d has no materialised output (fused) or weights not loaded", layer); return RTOD_E_STATE; }
     return launch_view_to_nchw(v, batch, out_dev_nchw, (hipStream_t)stream);
     RTOD_GUARD_END
 }

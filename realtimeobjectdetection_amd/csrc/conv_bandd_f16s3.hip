@@ -449,6 +449,7 @@ int launch_conv_bandd_f16s3(const ConvArgs& a, int idx, hipStream_t s) {
     }
     if (a.in_ldc % 8 || a.in_coff % 8 || a.K != a.Kpad || a.K != 9 * a.Cin || a.Npad % 128) { set_error("launch_conv_bandd: bad view / K"); return RTOD_E_ARG; }
     if (a.raw_out && (a.f16 || a.res)) { set_error("launch_conv_bandd: a raw-sum launch carries no shortcut and no plain-f16 store"); return RTOD_E_ARG; }
+    if (a.raw_out && a.raw_ld != a.Npad) { set_error("launch_conv_bandd: raw-sum rows are Npad floats in this family (raw_ld %d, Npad %d)", a.raw_ld, a.Npad); return RTOD_E_ARG; }
     switch (idx) {
 #define RTOD_X_CASE(i, bm, bn, nwm, nwn, minw, db, kg, maxw, sfx) case i: if (a.Wi > maxw) break; return launch_bandd<bm, bn, nwm, nwn, minw, db, kg, maxw>(a, s);
         RTOD_BANDD_TILES(RTOD_X_CASE)

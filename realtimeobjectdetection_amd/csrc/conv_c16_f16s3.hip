@@ -25,6 +25,8 @@ struct C16StageRegs {
 };
 
 // BM x BN workgroup tile, NWM x NWN waves of (BM/NWM) x (BN/NWN); EPI | EPI_F16: plain-f16 instance (hi planes only).
+// EPI_SPLIT | EPI_RAW: raw-sum instance (plan option bn_split_narrow): the f16s3 main loop as it stands, the shared epilogue's RAW
+// branch stores the fp32 sums to ConvArgs::raw_out in rows of ConvArgs::raw_ld floats.
 template <int BM, int BN, int NWM, int NWN, int MINW, int EPI>
 __global__ __launch_bounds__(NWM * NWN * 64, MINW)
 void conv_c16_f16s3_kernel(const ConvArgs a, const int grid_m, const int grid_n) {
@@ -212,7 +214,7 @@ void conv_c16_f16s3_kernel(const ConvArgs a, const int grid_m, const int grid_n)
     wait_stage(S0);
     wait_stage(S1);
 
-    conv_f16s3_epilogue<BM, BN, WM, WN, NT, epi_kind(EPI), SMEM, 1, false, F16>(a, acc, smem, bm, bn, tid, wm, wn, lr, lh, M);
+    conv_f16s3_epilogue<BM, BN, WM, WN, NT, epi_kind(EPI), SMEM, 1, false, F16, epi_raw(EPI)>(a, acc, smem, bm, bn, tid, wm, wn, lr, lh, M);
 }
 
 // One list drives the tile table, the launch switch and the kernel names rocprofv3 prints:
@@ -256,7 +258,9 @@ static int launch_c16(const ConvArgs& a, hipStream_t s) {
     auto f_dec = conv_c16_f16s3_kernel<BM, BN, NWM, NWN, MINW, EPI_DECODE | EPI_F16>;
     auto f_res = conv_c16_f16s3_kernel<BM, BN, NWM, NWN, MINW, EPI_SPLIT_RES | EPI_F16>;
     auto f_plain = conv_c16_f16s3_kernel<BM, BN, NWM, NWN, MINW, EPI_SPLIT | EPI_F16>;
-    if (a.f16) hipLaunchKernelGGL(a.dec.enabled ? f_dec : a.res ? f_res : f_plain, dim3(gm * gn), dim3(NT), 0, s, a, gm, gn);
+    auto k_raw = conv_c16_f16s3_kernel<BM, BN, NWM, NWN, MINW, EPI_SPLIT | EPI_RAW>;
+    if (a.raw_out) hipLaunchKernelGGL(k_raw, dim3(gm * gn), dim3(NT), 0, s, a, gm, gn);
+    else if (a.f16) hipLaunchKernelGGL(a.dec.enabled ? f_dec : a.res ? f_res : f_plain, dim3(gm * gn), dim3(NT), 0, s, a, gm, gn);
     else hipLaunchKernelGGL(a.dec.enabled ? k_dec : a.res ? k_res : k_plain, dim3(gm * gn), dim3(NT), 0, s, a, gm, gn);
     return hip_fail(hipGetLastError(), "conv_c16_f16s3 launch");
 }
@@ -274,6 +278,7 @@ int launch_conv_c16_f16s3(const ConvArgs& a, int mode, hipStream_t s) {
     if (!a.dec.enabled && a.out_ldc <= 0) { set_error("launch_conv_c16_f16s3: bad output view"); return RTOD_E_ARG; }
     if (a.B <= 0 || a.Ho <= 0 || a.Wo <= 0 || a.Cout <= 0) { set_error("launch_conv_c16_f16s3: empty shape"); return RTOD_E_ARG; }
     if (a.pw_wh) { set_error("launch_conv_c16_f16s3: no hosted pointwise conv in this family"); return RTOD_E_ARG; }
+    if (a.raw_out && (a.f16 || a.res || a.dec.enabled)) { set_error("launch_conv_c16_f16s3: a raw-sum launch carries no shortcut, decode or plain-f16 store"); return RTOD_E_ARG; }
     switch (mode) {
 #define RTOD_X_CASE(id, bm, bn, nwm, nwn, minw) case id: return launch_c16<bm, bn, nwm, nwn, minw>(a, s);
         RTOD_C16_TILES(RTOD_X_CASE)

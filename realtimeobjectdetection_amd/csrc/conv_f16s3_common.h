@@ -125,6 +125,7 @@ inline int check_split_conv_args(const ConvArgs& a, const char* who, bool f16_ok
         set_error("%s: buffer of %u / %u bytes outside (0, 2 GiB)", who, a.in_bytes, a.w_bytes); return RTOD_E_ARG;
     }
     if ((uint64_t)a.B * a.Hi * a.Wi * a.in_ldc * 4ull > (uint64_t)a.in_bytes) { set_error("%s: input view exceeds its buffer", who); return RTOD_E_ARG; }
+    if (a.raw_out && (a.raw_ld % 4 || a.raw_ld < (a.Cout + 7) / 8 * 8)) { set_error("%s: raw-sum rows of %d floats for %d channels", who, a.raw_ld, a.Cout); return RTOD_E_ARG; }
     return RTOD_OK;
 }
 
@@ -135,7 +136,7 @@ enum { EPI_SPLIT = 0, EPI_SPLIT_RES = 1, EPI_DECODE = 2, EPI_SPLIT_PW = 3, EPI_S
 // Kept inside EPI so that the f16s3 instances keep their names (rocprofv3, bench.py).  EPI_F16 itself: rtod_internal.h.
 __host__ __device__ constexpr bool epi_f16(int epi) { return (epi & EPI_F16) != 0; }
 // Raw-sum instances (plan option bn_batch_split): EPI_SPLIT | EPI_RAW.  Same main loop; the epilogue stores acc * inv_scale[n] — the
-// convolution sum itself: the pre-scales are powers of two — as dense fp32 rows [M][Npad] to ConvArgs::raw_out, after the same LDS
+// convolution sum itself: the pre-scales are powers of two — as fp32 rows [M][ConvArgs::raw_ld] to ConvArgs::raw_out, after the same LDS
 // transpose: no SPLIT_SCALE, bias, activation or shortcut, no split store, no overflow sentinel.  The normalisation that follows
 // (aux_kernels.hip: bn_apply_split_kernel) writes the split format.
 __host__ __device__ constexpr bool epi_raw(int epi) { return (epi & EPI_RAW) != 0; }
@@ -475,8 +476,8 @@ __device__ __forceinline__ void conv_f16s3_epilogue(const ConvArgs& a, f32x4 (&a
                 if (m >= M || bn * BN + c8 >= a.Cout) continue;
                 const f32x4 v0 = *reinterpret_cast<const f32x4*>(T + r * TS + c8);
                 const f32x4 v1 = *reinterpret_cast<const f32x4*>(T + r * TS + c8 + 4);
-                if constexpr (RAW) {                                      // 8 channels of row m of the dense [M][Npad] scratch (Cout <= Npad, both multiples of 8)
-                    float* rp = a.raw_out + (int64_t)m * a.Npad + bn * BN + c8;
+                if constexpr (RAW) {                                      // 8 channels of row m of the [M][raw_ld] scratch (Cout rounded up to 8 <= raw_ld)
+                    float* rp = a.raw_out + (int64_t)m * a.raw_ld + bn * BN + c8;
                     *reinterpret_cast<f32x4*>(rp) = v0;
                     *reinterpret_cast<f32x4*>(rp + 4) = v1;
                     continue;

@@ -239,6 +239,7 @@ int launch_conv_pwd_f16s3(const ConvArgs& a, int idx, hipStream_t s) {
     }
     if (a.in_ldc % 8 || a.in_coff % 8 || a.K != a.Kpad || a.K != a.Cin || a.Npad % 128) { set_error("launch_conv_pwd: bad view / K"); return RTOD_E_ARG; }
     if (a.raw_out && (a.f16 || a.res)) { set_error("launch_conv_pwd: a raw-sum launch carries no shortcut and no plain-f16 store"); return RTOD_E_ARG; }
+    if (a.raw_out && a.raw_ld != a.Npad) { set_error("launch_conv_pwd: raw-sum rows are Npad floats in this family (raw_ld %d, Npad %d)", a.raw_ld, a.Npad); return RTOD_E_ARG; }
     switch (idx) {
 #define RTOD_X_CASE(i, bm, nw, nst, minw) case i: return launch_pwd<bm, nw, nst, minw>(a, s);
         RTOD_PWD_TILES(RTOD_X_CASE)

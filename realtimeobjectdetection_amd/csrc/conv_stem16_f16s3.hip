@@ -182,4 +182,121 @@ int launch_conv_stem16_f16s3(const float* x, const _Float16* wh, const _Float16*
     return hip_fail(hipGetLastError(), "conv_stem16 launch");
 }
 
+// ---------------------------------------------------------------------------------------------
+// Raw-sum instance of the non-pooling kernel (plan options bn_batch_split + bn_split_narrow + stem_pool): batch-statistics BatchNorm
+// on layer 0.  The weights are packed unfolded, so acc * inv_scale IS the convolution sum; it is stored as fp32 rows of `ld` floats —
+// no bias, no activation, no split store, no overflow sentinel: the normalise kernel that follows (aux_kernels.hip) writes the split
+// format.  A kernel of its own, so that conv_stem16_kernel's instances stay as they are compiled today; same gather, same three
+// products, same LDS transpose (one dword per (pixel, channel)), four 16-byte pieces of 4 channels per pixel.
+struct Stem16RawArgs {
+    const float* x; const _Float16* wh; const _Float16* wl; const float* inv_scale;
+    float* raw; int64_t ld;            // rows of `ld` floats (>= 16, multiple of 4), one per pixel
+    int B, H, W;
+    unsigned x_bytes;
+};
+
+__global__ __launch_bounds__(256)
+void conv_stem16_raw_kernel(const Stem16RawArgs a) {
+    constexpr int NT = STEM16_NT, TS = STEM16_TS;
+    constexpr int NP = NT * 16;                                        // pixels written per wave iteration
+    __shared__ __attribute__((aligned(16))) float T[4][NP * TS];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int lr = lane & 15, lh = lane >> 4;
+    const int hw = a.H * a.W;
+    const int M = a.B * hw;
+    float* Tw = T[wave];
+    const __amdgpu_buffer_rsrc_t rs_x = buffer_rsrc(a.x, a.x_bytes);
+    int koff[8], need[8];                                              // tap geometry of the lane's 8 k values (conv_stem16_kernel)
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        const int k = lh * 8 + e;                                  // 0..31, k = (ky*3+kx)*3 + c
+        const int tap = k / 3, c = k - tap * 3;
+        const int ky = tap / 3, kx = tap - ky * 3;
+        koff[e] = (c * hw + ky * a.W + kx) * 4;
+        need[e] = (ky == 0 ? 1 : 0) | (ky == 2 ? 2 : 0) | (kx == 0 ? 4 : 0) | (kx == 2 ? 8 : 0) | (k >= 27 ? 16 : 0) | 32;
+    }
+    const f16x8 bh = *reinterpret_cast<const f16x8*>(a.wh + lr * 32 + lh * 8);
+    const f16x8 bl = *reinterpret_cast<const f16x8*>(a.wl + lr * 32 + lh * 8);
+    const float inv = a.inv_scale[lr];
+
+    auto gather = [&](int tile, float (&av)[NT][8]) {
+#pragma unroll
+        for (int i = 0; i < NT; ++i) {
+            const int m = tile * NP + i * 16 + lr;
+            const bool mok = m < M;
+            const int mm = mok ? m : 0;
+            const int b = mm / hw, r = mm - b * hw;
+            const int oy = r / a.W, ox = r - oy * a.W;
+            const int iy0 = oy - 1, ix0 = ox - 1;
+            const int edge = (iy0 < 0 ? 1 : 0) | (iy0 + 2 >= a.H ? 2 : 0) | (ix0 < 0 ? 4 : 0) | (ix0 + 2 >= a.W ? 8 : 0) | 16 | (mok ? 0 : 32);
+            const int base = (b * 3 * hw + iy0 * a.W + ix0) * 4;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const unsigned vo = (need[e] & edge) ? 0x80000000u : (unsigned)(base + koff[e]);
+                av[i][e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_x, vo, 0, 0));
+            }
+        }
+    };
+
+    const int tstep = gridDim.x * 4;
+    int tile = blockIdx.x * 4 + wave;
+    float av[NT][8], an[NT][8];
+    if ((int64_t)tile * NP < M) gather(tile, av);
+    for (; (int64_t)tile * NP < M; tile += tstep) {
+        if ((int64_t)(tile + tstep) * NP < M) gather(tile + tstep, an);        // wave-uniform
+#pragma unroll
+        for (int i = 0; i < NT; ++i) {
+            f16x8 ah, al;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const float v = av[i][e] * SPLIT_SCALE;
+                const _Float16 h = (_Float16)v;
+                ah[e] = h; al[e] = (_Float16)(v - (float)h);
+            }
+            f32x4 c = {0.f, 0.f, 0.f, 0.f};
+            c = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bh, c, 0, 0, 0);
+            c = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bl, c, 0, 0, 0);
+            c = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh, c, 0, 0, 0);
+            // D: col = lane%16 (channel), row = 4*(lane/16) + e
+#pragma unroll
+            for (int e = 0; e < 4; ++e) Tw[(i * 16 + 4 * lh + e) * TS + lr] = c[e] * inv;
+        }
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");   // the wave's own LDS writes, then reads (in order)
+        __builtin_amdgcn_wave_barrier();
+        // NP pixels x 4 pieces of 16 bytes (channels 0-3, 4-7, 8-11, 12-15)
+#pragma unroll
+        for (int q = 0; q < NP * 4 / 64; ++q) {
+            const int g = lane + q * 64;
+            const int p = g >> 2, piece = g & 3;
+            const int mo = tile * NP + p;
+            const f32x4 d = *reinterpret_cast<const f32x4*>(Tw + p * TS + piece * 4);
+            if (mo < M) *reinterpret_cast<f32x4*>(a.raw + (int64_t)mo * a.ld + piece * 4) = d;
+        }
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int i = 0; i < NT; ++i)
+#pragma unroll
+            for (int e = 0; e < 8; ++e) av[i][e] = an[i][e];
+    }
+}
+
+// raw: fp32 view H x W over the raw-sum scratch, C = 16, coff 0, rows of raw.ldc floats
+int launch_conv_stem16_raw(const float* x, const _Float16* wh, const _Float16* wl, const float* inv_scale, const View& raw, int B, int H, int W, hipStream_t s) {
+    if (!x || !wh || !wl || !inv_scale || !raw.base) { set_error("conv_stem16(raw): null pointer"); return RTOD_E_ARG; }
+    if (B < 1 || H < 1 || W < 1) { set_error("conv_stem16(raw): bad geometry"); return RTOD_E_ARG; }
+    if (raw.split || raw.C != 16 || raw.H != H || raw.W != W || raw.ldc < 16 || raw.ldc % 4 || raw.coff != 0) { set_error("conv_stem16(raw): bad raw-sum view"); return RTOD_E_ARG; }
+    if ((int64_t)B * H * W >= (1ll << 31) || (int64_t)B * 3 * H * W * 4 >= (1ll << 31)) { set_error("conv_stem16(raw): input exceeds 2 GiB / int32 pixels"); return RTOD_E_ARG; }
+    Stem16RawArgs a;
+    a.x = x; a.wh = wh; a.wl = wl; a.inv_scale = inv_scale;
+    a.raw = raw.base; a.ld = raw.ldc;
+    a.B = B; a.H = H; a.W = W;
+    a.x_bytes = (unsigned)((int64_t)B * 3 * H * W * 4);
+    const int64_t tiles = ((int64_t)B * H * W + STEM16_NT * 16 - 1) / (STEM16_NT * 16);
+    int grid = (int)((tiles + 3) / 4);
+    if (grid > 2048) grid = 2048;                                      // larger maps: several tiles per wave, the next one's input in flight
+    hipLaunchKernelGGL(conv_stem16_raw_kernel, dim3(grid), dim3(256), 0, s, a);
+    return hip_fail(hipGetLastError(), "conv_stem16(raw) launch");
+}
+
 }  // namespace rtod

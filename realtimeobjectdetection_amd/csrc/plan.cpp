@@ -292,7 +292,7 @@ static int resolve_alias(const std::vector<Layer>& layers, int i) {
 }
 
 void Plan::reset_planning() {
-    for (auto& L : layers) { L.fused_into = -1; L.fused_away = false; L.buf = -1; L.coff = 0; L.alias_of = -1; }
+    for (auto& L : layers) { L.fused_into = -1; L.fused_away = false; L.buf = -1; L.coff = 0; L.alias_of = -1; L.bn_pool = -1; }
     bufs.clear(); launches.clear(); convs.clear(); input_buf = -1;
     tuned.clear(); tune_cache.clear(); tuning.clear();
 }
@@ -313,6 +313,8 @@ int Plan::set_option(const char* name, int value) {
         flag = &opt_bn_batch_stats;
     }
     else if (k == "bn_batch_split") flag = &opt_bn_batch_split;
+    else if (k == "bn_split_narrow") flag = &opt_bn_split_narrow;
+    else if (k == "fuse_bn_pool") flag = &opt_fuse_bn_pool;
     else if (k == "k_slice_workgroups") flag = &opt_k_slice_workgroups;
     else if (k == "k_slices_split") flag = &opt_k_slices_split;
     else if (k == "patch_kernel") flag = &opt_patch_kernel;
@@ -511,9 +513,21 @@ int Plan::plan_buffers() {
                         (pwc == 0 || pwc == 32);
     }
     // 16-filter stem + max-pool fusion candidate: layer 1 is a plain 2x2 / stride-2 pool over an even map and the only reader of layer 0
-    stem_pool_pattern = use_stem16 && opt_fuse_stem_pool && n > 1 && layers[1].type == LT_MAXPOOL && layers[1].size == 2 && layers[1].stride == 2 &&
+    // (a BatchNorm layer 0 of a batch-statistics split plan writes raw sums: its pool, if any, rides the normalise kernel — below)
+    stem_pool_pattern = use_stem16 && !(bn_split_active() && layers[0].bn) && opt_fuse_stem_pool && n > 1 && layers[1].type == LT_MAXPOOL && layers[1].size == 2 && layers[1].stride == 2 &&
                         layers[1].pool_pad == 0 && cons[0].size() == 1 && layers[0].hout % 2 == 0 && layers[0].wout % 2 == 0 &&
                         launches.size() >= 2 && launches[0].kind == LK_STEM && launches[1].kind == LK_MAXPOOL && launches[1].layer == 1;
+    // normalise + max-pool candidates (options bn_split_narrow + fuse_bn_pool): a BatchNorm conv without a fused shortcut / decode whose
+    // even map is read by a plain 2x2 / stride-2 pool alone.  Every BatchNorm conv of such a plan has a raw-sum launch.
+    // The conv keeps its own full-resolution buffer in the arena (as layer 0 does under stem_pool_pattern): keep_all_layers, which
+    // is set after planning and only re-assigns the arena, turns the pair back into the stand-alone form, which writes that buffer
+    if (bn_narrow_active() && opt_fuse_bn_pool)
+        for (int i = 0; i + 1 < n; ++i) {
+            Layer& L = layers[i]; const Layer& P = layers[i + 1];
+            if (L.type == LT_CONV && L.bn && L.fused_into < 0 && P.type == LT_MAXPOOL && P.size == 2 && P.stride == 2 && P.pool_pad == 0 &&
+                cons[i].size() == 1 && cons[i][0] == i + 1 && L.hout % 2 == 0 && L.wout % 2 == 0)
+                L.bn_pool = i + 1;
+        }
     // liveness per buffer over launch time (= layer index of the launch)
     const int NB = (int)bufs.size();
     for (auto& b : bufs) { b.first = 1 << 30; b.last = -1; }
@@ -525,8 +539,10 @@ int Plan::plan_buffers() {
         if (l.kind == LK_STEM) {
             touch(buf_of_layer(l.out_layer), t);
             if (stem_pool_pattern) touch(buf_of_layer(1), t);                            // written by the stem's kernel when fused
+            if (layers[l.layer].bn_pool >= 0) touch(buf_of_layer(layers[l.layer].bn_pool), t);   // ... by its normalise kernel
             continue;
         }
+        if (l.kind == LK_CONV && layers[l.layer].bn_pool >= 0) touch(buf_of_layer(layers[l.layer].bn_pool), t);   // written by the conv's normalise kernel when fused
         touch(buf_of_layer(l.in_layer), t);
         if (l.in2_layer >= 0) touch(buf_of_layer(l.in2_layer), t);
         if (l.kind == LK_COPY) touch(l.out_buf, t);
@@ -556,8 +572,9 @@ int Plan::check_split_supported(int mode) const {
     }
     if (opt_bn_batch_stats) {
         // batch-statistics BatchNorm on the split kernels (option bn_batch_split): every BatchNorm conv after layer 0 needs a raw-sum
-        // instance — the generic, bandd and 1x1 slab tiles have one; the narrow, K-sliced and 16-filter stem kernels do not
-        if (opt_k_slices_split || opt_stem_pool) {
+        // instance — the generic, bandd and 1x1 slab tiles have one; the K-sliced kernels do not; the narrow tiles and the 16-filter stem
+        // run theirs with option bn_split_narrow only
+        if (opt_k_slices_split || (opt_stem_pool && !opt_bn_split_narrow)) {
             set_error("precision %s with bn_batch_stats + bn_batch_split: option %s is not supported in that mode (layer %d would run a kernel without a raw-sum instance)",
                       pn, opt_k_slices_split ? "k_slices_split" : "stem_pool", opt_stem_pool ? 0 : 1);
             return RTOD_E_CFG;
@@ -565,7 +582,7 @@ int Plan::check_split_supported(int mode) const {
         for (const auto& l : launches) {
             if (l.kind != LK_CONV || l.layer == 0 || !layers[l.layer].bn) continue;
             const Layer& L = layers[l.layer];
-            if (conv_c16_supported(L.cin)) {
+            if (conv_c16_supported(L.cin) && !opt_bn_split_narrow) {
                 set_error("precision %s with bn_batch_stats + bn_batch_split: layer %d is a narrow BatchNorm conv (Cin=%d: no raw-sum instance); use fp32", pn, l.layer, L.cin);
                 return RTOD_E_CFG;
             }
@@ -616,12 +633,6 @@ void Plan::layout_weights() {
         pc.stats_off = -1;
         if (opt_bn_batch_stats && layers[pc.layer].bn) { pc.stats_off = bn_stats_doubles; bn_stats_doubles += 2 * (int64_t)pc.Npad; }
     }
-    bn_raw_floats = 0;
-    if (bn_split_active())
-        for (const auto& pc : convs) {
-            const Layer& L = layers[pc.layer];
-            if (L.bn) bn_raw_floats = std::max(bn_raw_floats, (int64_t)max_batch * L.hout * L.wout * pc.Npad);
-        }
     for (auto& pc : convs) {
         const Layer& L = layers[pc.layer];
         pc.split = uses_split(L, pc.cin_p);
@@ -654,6 +665,19 @@ void Plan::layout_weights() {
         if (opt_bn_batch_stats && L.bn) { pc.bn_off = packed_floats; packed_floats += 2 * (int64_t)pc.Npad; }
         packed_floats = (packed_floats + 63) / 64 * 64;
     }
+    bn_raw_floats = 0;                                                   // every layer with its own row stride
+    if (bn_split_active())
+        for (const auto& pc : convs) {
+            const Layer& L = layers[pc.layer];
+            if (L.bn) bn_raw_floats = std::max(bn_raw_floats, (int64_t)max_batch * L.hout * L.wout * raw_stride(pc));
+        }
+}
+
+// Rows of the raw-sum scratch: Npad floats apart for the tiles that had a raw-sum instance before option bn_split_narrow (and the
+// exact-fp32 layer 0), dense — Cout rounded up to 8 — for the narrow tiles and the 16-filter stem: their layers are the largest maps
+// with the fewest channels (16 filters at 416x416 would use 64 of every 512 bytes)
+int Plan::raw_stride(const PackedConv& pc) const {
+    return (pc.split && (pc.narrow || pc.stem16)) ? (layers[pc.layer].cout + 7) / 8 * 8 : pc.Npad;
 }
 
 void Plan::assign_arena() {
@@ -1163,17 +1187,18 @@ bool Plan::ks_sched_b_fits(const Launch& l, int batch) const {
     const int64_t S = (pc.Kpad / 32 + pc.ks_chunks - 1) / pc.ks_chunks;
     return S * batch * L.hout * L.wout * pc.Npad <= KS_SCRATCH_FLOATS;
 }
-// fp32 view over the raw-sum scratch for the conv of launch `l` at this batch: dense rows of Npad floats (base null: no scratch / too small)
+// fp32 view over the raw-sum scratch for the conv of launch `l` at this batch: rows of raw_stride floats (base null: no scratch / too small)
 View Plan::bn_raw_view(const Launch& l, int batch) const {
     View v;
     const Layer& L = layers[l.layer];
     const PackedConv& pc = convs[l.conv_slot];
-    if (!d_bn_raw || (int64_t)batch * L.hout * L.wout * pc.Npad > bn_raw_floats) return v;
-    v.base = d_bn_raw; v.ldc = pc.Npad; v.coff = 0; v.C = L.cout; v.H = L.hout; v.W = L.wout;
+    if (!d_bn_raw || (int64_t)batch * L.hout * L.wout * raw_stride(pc) > bn_raw_floats) return v;
+    v.base = d_bn_raw; v.ldc = raw_stride(pc); v.coff = 0; v.C = L.cout; v.H = L.hout; v.W = L.wout;
     return v;
 }
 bool Plan::pw_active() const { return precision == 1 && opt_fuse_pointwise && !bn_split_active(); }
 bool Plan::stem_pool_fused() const { return precision >= 1 && stem_pool_pattern && !keep_all && convs[launches[0].conv_slot].stem16; }
+bool Plan::bn_pool_fused(int layer) const { return bn_narrow_active() && opt_fuse_bn_pool && !keep_all && layers[layer].bn_pool >= 0; }
 bool Plan::stem2_active() const { return precision == 1 && !bn_split_active() && opt_stem2_kernel && stem2_pattern && !keep_all && convs[launches[0].conv_slot].split; }
 
 int Plan::forward(const float* x, int batch, float* out, hipStream_t s, float* launch_ms, bool tune) {
@@ -1221,8 +1246,9 @@ int Plan::forward(const float* x, int batch, float* out, hipStream_t s, float* l
                             a.out = rv.base; a.out_ldc = rv.ldc; a.out_coff = 0; a.out_split = 0;
                             rc = launch_conv(a, v, s);
                             if (rc) return rc;
-                            rc = launch_bn_batch_split(rv, o, l.in2_layer >= 0 ? &r : nullptr, batch, d_bn_stats + pc.stats_off, pc.Npad, d_weights + pc.bn_off, pc.Npad, L.act,
-                                                       d_bn_partial, bn_partial_count, overflow_flag, s);
+                            const bool pool = bn_pool_fused(l.layer);      // normalise + the max-pool that follows, into the pool's view
+                            rc = launch_bn_batch_split(rv, pool ? view_of(L.bn_pool) : o, l.in2_layer >= 0 ? &r : nullptr, batch, d_bn_stats + pc.stats_off, pc.Npad, d_weights + pc.bn_off, pc.Npad, L.act,
+                                                       d_bn_partial, bn_partial_count, overflow_flag, s, pool ? 1 : 0);
                             break;
                         }
                         rc = launch_conv(a, v, s);
@@ -1243,14 +1269,15 @@ int Plan::forward(const float* x, int batch, float* out, hipStream_t s, float* l
                     if (raw) {
                         rv = bn_raw_view(l, batch);
                         if (!rv.base || a.dec.enabled || a.pw_wh || !d_bn_stats || pc.stats_off < 0) { set_error("forward: layer %d: batch-statistics BatchNorm on an unsupported launch", l.layer); return RTOD_E_STATE; }
-                        a.raw_out = rv.base; a.res = nullptr; a.leaky = 0;
+                        a.raw_out = rv.base; a.raw_ld = (int)rv.ldc; a.res = nullptr; a.leaky = 0;
                     }
                     if (tune_now) { rc = tune_launch(li, a, batch, s); if (rc) return rc; }      // (never reached for the fused stem launch)
                     rc = launch_split_variant(a, pc, tune_now && tuning[li] >= 0 ? tuning[li] : variant_for(l, batch), s);
                     if (!rc && raw) {
                         View r; if (l.in2_layer >= 0) r = view_of(l.in2_layer);
-                        rc = launch_bn_batch_split(rv, view_of(l.out_layer), l.in2_layer >= 0 ? &r : nullptr, batch, d_bn_stats + pc.stats_off, pc.Npad, d_weights + pc.bn_off, pc.Npad,
-                                                   L.act, d_bn_partial, bn_partial_count, overflow_flag, s);
+                        const bool pool = bn_pool_fused(l.layer);
+                        rc = launch_bn_batch_split(rv, view_of(pool ? L.bn_pool : l.out_layer), l.in2_layer >= 0 ? &r : nullptr, batch, d_bn_stats + pc.stats_off, pc.Npad, d_weights + pc.bn_off, pc.Npad,
+                                                   L.act, d_bn_partial, bn_partial_count, overflow_flag, s, pool ? 1 : 0);
                     }
                 }
                 break;
@@ -1262,6 +1289,17 @@ int Plan::forward(const float* x, int batch, float* out, hipStream_t s, float* l
                 const View o = view_of(l.out_layer);
                 if (pc.stem16) {                                        // 16 filters: stand-alone, or with layer 1's max-pool (writes layer 1's view)
                     if (!pc.split) { set_error("forward: the 16-filter stem needs a split-f16 / f16 plan"); return RTOD_E_STATE; }
+                    if (bn_split_active() && L.bn) {                    // raw sums (unfolded weights), statistics, normalise (+ the max-pool that follows)
+                        const View rv = bn_raw_view(l, batch);
+                        if (!rv.base || !d_bn_stats || pc.stats_off < 0 || !opt_bn_split_narrow) { set_error("forward: layer %d: batch-statistics BatchNorm on an unsupported launch", l.layer); return RTOD_E_STATE; }
+                        rc = launch_conv_stem16_raw(x, reinterpret_cast<const _Float16*>(d_weights + pc.w_off), reinterpret_cast<const _Float16*>(d_weights + pc.wl_off),
+                                                    d_weights + pc.s_off, rv, batch, height, width, s);
+                        if (rc) return rc;
+                        const bool fuse = bn_pool_fused(l.layer);
+                        rc = launch_bn_batch_split(rv, fuse ? view_of(L.bn_pool) : o, nullptr, batch, d_bn_stats + pc.stats_off, pc.Npad, d_weights + pc.bn_off, pc.Npad, L.act,
+                                                   d_bn_partial, bn_partial_count, overflow_flag, s, fuse ? 1 : 0);
+                        break;
+                    }
                     const bool pool = stem_pool_fused();
                     rc = launch_conv_stem16_f16s3(x, reinterpret_cast<const _Float16*>(d_weights + pc.w_off), reinterpret_cast<const _Float16*>(d_weights + pc.wl_off),
                                                   d_weights + pc.s_off, d_weights + pc.b_off, pool ? view_of(1) : o, batch, height, width, L.act, pool ? 1 : 0, overflow_flag, s);
@@ -1281,6 +1319,7 @@ int Plan::forward(const float* x, int batch, float* out, hipStream_t s, float* l
                 break;
             case LK_MAXPOOL:
                 if (li == 1 && stem_pool_fused()) break;                // computed inside the stem's kernel
+                if (pool_fused_away(l.layer)) break;                    // ... inside the conv's normalise kernel
                 rc = launch_maxpool(view_of(l.in_layer), view_of(l.out_layer), batch, layers[l.layer].size, layers[l.layer].stride, layers[l.layer].pool_pad, s); break;
             case LK_ADD: rc = launch_add(view_of(l.in_layer), view_of(l.in2_layer), view_of(l.out_layer), batch, s); break;
             case LK_COPY: {
@@ -1321,11 +1360,11 @@ void Plan::fill_launch_info(int idx, rtod_launch_info* o, int batch) const {
         case LK_STEM:
             if (stem2_active()) { o->bytes_per_frame = 0; break; }                   // accounted on layer 1's launch
             o->flops_per_frame = 2ll * L.hout * L.wout * L.cout * L.cin * L.size * L.size;
-            o->bytes_per_frame = in_b + (stem_pool_fused() ? out_b / 4 : out_b);  // fused 2x2 pool: the pooled map is what is written
+            o->bytes_per_frame = in_b + (stem_pool_fused() || bn_pool_fused(l.layer) ? out_b / 4 : out_b);  // fused 2x2 pool: the pooled map is what is written
             o->weight_bytes = ((int64_t)L.cout * L.cin * L.size * L.size + L.cout) * 4;
             break;
         case LK_MAXPOOL:
-            o->bytes_per_frame = (idx == 1 && stem_pool_fused()) ? 0 : in_b + out_b;   // fused: accounted on the stem's launch
+            o->bytes_per_frame = (idx == 1 && stem_pool_fused()) || pool_fused_away(l.layer) ? 0 : in_b + out_b;   // fused: accounted on the stem's / conv's launch
             break;
         case LK_CONV:
             if (l.pw_host >= 0 && pw_active()) { o->bytes_per_frame = 0; break; }    // accounted on the host conv's launch
@@ -1333,7 +1372,7 @@ void Plan::fill_launch_info(int idx, rtod_launch_info* o, int batch) const {
             else { const int v = choose_variant(L, batch); o->variant = v + 10 * f32_slice_mode(l, batch, v); }   // tile + 10 * K-slice schedule
             o->flops_per_frame = 2ll * L.hout * L.wout * L.cout * L.cin * L.size * L.size;
             o->fused_residual = l.in2_layer >= 0; o->fused_decode = l.out_layer == -2;
-            o->bytes_per_frame = in_b + out_b + (l.in2_layer >= 0 ? out_b : 0);
+            o->bytes_per_frame = in_b + (bn_pool_fused(l.layer) ? out_b / 4 : out_b) + (l.in2_layer >= 0 ? out_b : 0);   // (fused 2x2 pool: the pooled map is what is written)
             o->weight_bytes = ((int64_t)L.cout * L.cin * L.size * L.size + L.cout) * 4;
             if (idx == 1 && stem2_active()) {                                        // fused stem: its FLOPs ride here, its output is never written
                 const Layer& S = layers[0];
@@ -1371,7 +1410,7 @@ std::string Plan::describe() const {
         os << "],\"anchors\":[";
         for (size_t a = 0; a < L.anchors.size(); ++a) os << (a ? "," : "") << "[" << L.anchors[a].first << "," << L.anchors[a].second << "]";
         os << "],\"classes\":" << L.classes << ",\"row_offset\":" << L.row_offset << ",\"rows\":" << L.rows << ",\"w_off\":" << L.w_off
-           << ",\"fused_into\":" << ((i == 0 && (stem2_active() || stem_pool_fused())) ? 1 : L.fused_into) << ",\"fused_away\":" << (L.fused_away ? "true" : "false") << ",\"alias_of\":" << L.alias_of
+           << ",\"fused_into\":" << ((i == 0 && (stem2_active() || stem_pool_fused())) ? 1 : bn_pool_fused((int)i) ? L.bn_pool : L.fused_into) << ",\"fused_away\":" << (L.fused_away ? "true" : "false") << ",\"alias_of\":" << L.alias_of
            << ",\"buf\":" << L.buf << ",\"coff\":" << L.coff;
         if (L.type == LT_CONV)                                                       // sliced layers only (option k_slices_split)
             for (const auto& pc : convs)

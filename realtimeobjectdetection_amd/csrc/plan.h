@@ -32,6 +32,8 @@ struct Layer {
     bool fused_away = false;  // shortcut / yolo executed inside the preceding conv's epilogue
     int buf = -1, coff = 0;   // materialised output: arena buffer id + channel offset (-1: none/alias)
     int alias_of = -1;        // single-source route / yolo: same view as that layer
+    int bn_pool = -1;         // BatchNorm conv of a batch-statistics split plan (options bn_split_narrow + fuse_bn_pool): index of the 2x2 / stride-2
+                              // max-pool that alone reads it and that its normalise kernel can run (Plan::bn_pool_fused decides at run time)
 };
 
 struct Buffer {
@@ -92,9 +94,9 @@ struct Plan {
     int64_t bn_stats_doubles = 0;
     double* d_bn_partial = nullptr;   // per-range partial sums of the two-stage statistics kernel
     int64_t bn_partial_count = 0;
-    float* d_bn_raw = nullptr;        // option bn_batch_split: the raw sums of the BatchNorm conv that is running, dense fp32 rows [M][Npad] (never in place:
+    float* d_bn_raw = nullptr;        // option bn_batch_split: the raw sums of the BatchNorm conv that is running, fp32 rows [M][raw_stride] (never in place:
                                       // an fp32 slice of a zero-copy concat pixel would overlap the other producers' hi / lo planes)
-    int64_t bn_raw_floats = 0;        // max over BatchNorm convs of max_batch * hout * wout * Npad (layout_weights); 0 unless bn_split_active()
+    int64_t bn_raw_floats = 0;        // max over BatchNorm convs of max_batch * hout * wout * raw_stride (layout_weights); 0 unless bn_split_active()
     float* d_scratch = nullptr;       // slice panels of the one-workgroup-per-K-slice schedules (exact-fp32 plans; split plans with a sliced layer)
     int64_t scratch_floats = 0;
     bool weights_loaded = false;
@@ -109,6 +111,8 @@ struct Plan {
     bool opt_bn_batch_stats = false;  // exact-fp32 plans: BatchNorm on the statistics of the batch (what the reference runs: no .eval()), not folded
     bool opt_bn_batch_split = false;  // ... on the split-f16 kernels (precision 1 only; inert without bn_batch_stats): raw-sum conv instances, statistics,
                                       // a normalise kernel that writes the split format
+    bool opt_bn_split_narrow = false; // ... (read only when that mode is in force) also on the narrow tiles and the 16-filter stem: YOLOv3-tiny's 16-channel layers
+    bool opt_fuse_bn_pool = true;     // ... with bn_split_narrow: the 2x2 / stride-2 max-pool that alone reads a BatchNorm conv runs in its normalise kernel
     bool opt_k_slices = true;         // exact-fp32 kernels: deep small-grid layers summed in K slices (own workgroups when the grid is small)
     bool opt_k_slice_workgroups = true;   // ... (off: always the in-workgroup schedule — same bits; A/B and tests).  Governs conv_ks_f16s3 too
     bool opt_k_slices_split = false;  // precisions 1 / 2: deep small-grid convs summed in K slices on conv_ks_f16s3.hip (single-frame latency; opt-in)
@@ -159,6 +163,10 @@ struct Plan {
     bool ks_sched_b_fits(const Launch& l, int batch) const;              // sliced split layer: the slice panels of this batch fit the scratch
     bool bn_split_active() const { return opt_bn_batch_stats && opt_bn_batch_split && precision == 1; }   // batch-statistics BatchNorm on the split kernels
     bool raw_launch(const Launch& l) const { return bn_split_active() && l.kind == LK_CONV && layers[l.layer].bn; }   // a BatchNorm conv of such a plan: raw sums, then normalise
+    bool bn_narrow_active() const { return bn_split_active() && opt_bn_split_narrow; }   // ... narrow tiles, 16-filter stem and fused pools included
+    int raw_stride(const PackedConv& pc) const;           // floats per row of the raw-sum scratch: Npad; narrow tiles and the 16-filter stem: Cout rounded up to 8
+    bool bn_pool_fused(int layer) const;                  // the BatchNorm conv `layer` is normalised and pooled by one kernel: its own map is never stored
+    bool pool_fused_away(int layer) const { return layer > 0 && layers[layer - 1].bn_pool == layer && bn_pool_fused(layer - 1); }   // max-pool `layer` runs in that kernel
     View bn_raw_view(const Launch& l, int batch) const;   // fp32 view over d_bn_raw for this launch's conv
     bool pw_active() const;                     // fused pointwise convs in use (precision 1, option fuse_pointwise)
     bool stem2_pattern = false;                 // launches 0 / 1 are a stem and the stride-2 conv conv_stem2_f16s3 fuses (set by plan_buffers)

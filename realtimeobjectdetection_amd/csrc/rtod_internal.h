@@ -100,8 +100,10 @@ struct ConvArgs {
     int xcd_by_n = 0;                           // split kernels: workgroup -> XCD by output-channel tile instead of by pixel tile (see launch_band)
     int out_split = 0;                          // exact-fp32 kernel only: write the output in the split format
     int f16 = 0;                                // split kernels: 1 = plain-f16 instance (precision mode 2: hi planes only, one MFMA per fragment pair)
-    float* raw_out = nullptr;                   // split kernels, raw-sum instances (EPI_RAW; plan option bn_batch_split): acc * inv_scale[n] as dense fp32 rows [M][Npad];
+    float* raw_out = nullptr;                   // split kernels, raw-sum instances (EPI_RAW; plan option bn_batch_split): acc * inv_scale[n] as fp32 rows [M][raw_ld];
                                                 // no bias, activation, shortcut or split store (`out` is not written)
+    int raw_ld = 0;                             // ... floats between consecutive rows of raw_out, read by the shared epilogue of the generic and narrow tiles: Npad, or (narrow
+                                                // tiles, plan option bn_split_narrow) Cout rounded up to 8.  The bandd and 1x1 slab instances write rows of Npad and refuse another value
     // exact-fp32 kernel and the K-sliced split family (conv_ks_f16s3.hip): K slices (conv_igemm_f32.hip).  slice_chunks > 0: the K sum is formed slice by slice (a property of
     // the layer); partial != nullptr: one workgroup per slice, raw sums to this scratch ([slices][M][Npad] floats), then a reduction
     int slice_chunks = 0;
@@ -165,7 +167,7 @@ __device__ __forceinline__ int xcd_remap(int id, int n) {
 // epilogue-code flag of the plain-f16 kernel instances (precision mode 2): EPI | EPI_F16 (conv_f16s3_common.h)
 constexpr int EPI_F16 = 8;
 // epilogue-code flag of the raw-sum instances (batch-statistics BatchNorm on the split kernels, plan option bn_batch_split):
-// EPI_SPLIT | EPI_RAW.  Generic, bandd and 1x1 slab tiles only (the raw column of the family table)
+// EPI_SPLIT | EPI_RAW.  Generic, bandd, 1x1 slab and narrow tiles (the raw column of the family table)
 constexpr int EPI_RAW = 16;
 
 enum ConvVariant { CV_128x128 = 0, CV_128x64 = 1, CV_64x64 = 2, CV_128x32 = 3, CV_COUNT };
@@ -246,7 +248,7 @@ int launch_conv_patch_f16s3(const ConvArgs& a, int mode, hipStream_t s);
 
 // Convolutions that read 16 input channels (conv_c16_f16s3.hip; plan option "narrow_cin"): K order tap-major over 16 channels
 // (k = tap * 16 + c, a 32-wide K-chunk holds two taps), its own packed weights, so a narrow layer ALWAYS runs on this family and
-// no other layer does.  All tiles are bit-identical; f16s3 and plain-f16 instances, epilogues 0 / 1 / 2.
+// no other layer does.  All tiles are bit-identical; f16s3 and plain-f16 instances, epilogues 0 / 1 / 2; raw-sum instances (epilogue 16).
 constexpr int C16_MODES = 4;
 constexpr int C16_VARIANT_BASE = 140;      // variant ids in [140, 140 + C16_MODES): C16_VARIANT_BASE + mode
 constexpr bool conv_c16_supported(int cin) { return cin == 16; }
@@ -301,6 +303,8 @@ int launch_conv_stem_split(const float* x_nchw, const _Float16* wh, const _Float
 bool conv_stem16_supported(int ksize, int stride, int pad, int cin, int cout, int act);
 int launch_conv_stem16_f16s3(const float* x_nchw, const _Float16* wh, const _Float16* wl, const float* inv_scale, const float* bias,
                              const View& out, int B, int H, int W, int act, int pool, int32_t* ovf, hipStream_t s);
+// ... its raw-sum instance (plan options bn_batch_split + bn_split_narrow + stem_pool): acc * inv_scale as fp32 rows of raw.ldc floats
+int launch_conv_stem16_raw(const float* x_nchw, const _Float16* wh, const _Float16* wl, const float* inv_scale, const View& raw, int B, int H, int W, hipStream_t s);
 int launch_prep_image(const unsigned char* img, int h, int w, int bgr, int inp_dim, float* out, hipStream_t s);
 int launch_prep_frames(const unsigned char* frames, int batch, int h, int w, int bgr, int out_h, int out_w, float* out, hipStream_t s);
 int launch_pack_input(const float* x_nchw, int B, int C, int H, int W, float* out_nhwc, int Cp, hipStream_t s);
@@ -316,7 +320,9 @@ size_t bn_partial_doubles(int max_channels);
 // statistics kernels above read it, bn_apply_split_kernel normalises, applies the activation, adds the shortcut operand of its split
 // view and stores the split format into `y` (ldc / coff honoured: concat slices)
 int launch_bn_batch_split(const View& raw, const View& y, const View* res, int B, double* stats, int sstride, const float* bn, int gstride, int act,
-                          double* partial, int64_t partial_doubles, int32_t* ovf, hipStream_t s);
+                          double* partial, int64_t partial_doubles, int32_t* ovf, hipStream_t s, int pool = 0);
+// pool == 1 (plan options bn_split_narrow + fuse_bn_pool): `y` is the view of the 2x2 / stride-2 max-pool that alone reads the conv
+// (raw.H / 2 x raw.W / 2, both even, no shortcut); bn_apply_split_pool_kernel normalises and pools, bit-identical to pool == 0 + launch_maxpool
 // running_mean / running_var update of every BatchNorm layer of a batch-statistics plan in one launch (aux_kernels.hip)
 struct BnUpdateEntry { float* running_mean; float* running_var; int64_t stats_off; double unbias; int sstride; int channels; };
 constexpr int BN_UPDATE_MAX = 32;                 // entries per launch (by-value kernel argument: 32 x 40 bytes)
