@@ -289,6 +289,43 @@ int rtod_nms_class_offset(const float* pred_dev, int batch, int n, int num_class
                           int max_det, float* out_dev, int cap, int32_t* counts_dev, void* workspace_dev, size_t workspace_bytes,
                           void* stream);
 
+/* ---- validator: detections scored against ground truth -------------------------------------
+ * replaces DarknetValidator.target_filter / pred_filter / compare_boxes / get_img_scores      test.py:62-151, 182-208
+ * (as committed the reference's compare_boxes raises TypeError: its two helpers are @staticmethods declared with a `self`
+ * parameter; the arithmetic restated here is what those helpers do when called directly).
+ * Largest numbers of KEPT predictions / KEPT targets per image the kernel matches (1024 / 256). */
+int rtod_score_detections_limits(int* max_pred_per_image, int* max_targets_per_image);
+/* Bytes of device workspace for a call with these arguments (1 <= max_targets_per_image <= the limit). */
+int rtod_score_detections_workspace(int batch, int cap, int max_targets_per_image, size_t* bytes);
+/* One launch for the whole batch, one workgroup per image.  Enqueues only (no allocation, no host synchronisation: legal under
+ * stream capture).  An image's results do not depend on the batch it rides in.  Per image b:
+ *   rows      det_dev rows [sum counts[2..2+b), + counts[2+b]) — the output of rtod_write_results / rtod_nms_class_offset;
+ *   kept predictions: column 7 is an integer in [0, num_class) whose bit is set in class_mask_host   (pred[i, -1] in permitted_classes)
+ *   kept targets: t[2] > min_box_size and t[3] > min_box_size (strict, fp32) and the FIRST arg-max of t[5:5+num_class] permitted;
+ *             box (cx - w/2, cy - h/2, cx + w/2, cy + h/2) in fp32                                   (xywh2xyxy, src/util.py:39-43)
+ *             (target_corners != 0: columns 0-3 already hold those corners, the output of target_filter; the size test then
+ *             reads columns 2 and 3 as they are, so pass min_box_size = -inf);
+ *   M[i][j]   bbox_iou(pred[i,1:5], box_j) if (double)iou > iou_threshold (strict) else 0             (iou.item() > threshold)
+ *   matching  at most P_f rounds, stop when max(M) == 0: first row holding the maximum, first column holding it in that row;
+ *             row and column are zeroed, tp += 1 (torch's first-occurrence max / argmax: ties between equal boxes resolve so)
+ *   scores_dev[b] = people_num = T_f, tp, fp = P_f - tp, fn = T_f - tp;  totals_dev[0..4) += the same (integer atomics; the caller
+ *             zeroes; may be NULL)
+ *   match_dev[r] (may be NULL), per detection row: -2 filtered out, -1 kept and unmatched (a false positive), else the matched
+ *             target's index in the image's unfiltered target list;  match_iou_dev[r] (may be NULL): M of the matched pair, else 0
+ *   status_dev[0] |= 1: counts[0] > cap (or counts that do not fit cap rows): every image's scores are -1, totals and match untouched;
+ *                 |= 2: an image has more kept predictions than the limit or more kept targets than max_targets_per_image:
+ *                       its scores are -1, the totals are untouched by it, its matching is not run (match_dev: -2 / -1 only).
+ * tgt_dev: [T_total][5+num_class] rows (cx, cy, w, h, obj, one-hot...), the images' targets concatenated; tgt_offsets_dev
+ * [batch+1] row offsets into it.  After the call the workspace holds every scored image's M: float
+ * [batch][max_targets_per_image][ld], entry (b, j, i) for kept target j and kept prediction i, ld = min(max(cap, 1), 1024)
+ * rounded up to 64.  RTOD_E_ARG (decided on the host, no device needed): a null pointer, batch < 1, cap < 0, num_class outside
+ * 1..4096, max_targets_per_image outside 1..limit, a workspace that is too small or not 16-byte aligned, iou_threshold NaN. */
+int rtod_score_detections(const float* det_dev, const int32_t* counts_dev, int cap, int batch,
+                          const float* tgt_dev, const int32_t* tgt_offsets_dev, int num_class,
+                          const uint32_t* class_mask_host, float min_box_size, double iou_threshold,
+                          int max_targets_per_image, int target_corners, int32_t* scores_dev, int32_t* totals_dev,
+                          int32_t* match_dev, float* match_iou_dev, int32_t* status_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -322,6 +322,34 @@ int rtod_prep_frames(const uint8_t* frames_dev, int batch, int height, int width
     RTOD_GUARD_END
 }
 
+int rtod_score_detections_limits(int* max_pred_per_image, int* max_targets_per_image) {
+    if (!max_pred_per_image || !max_targets_per_image) { set_error("score_detections_limits: null pointer"); return RTOD_E_ARG; }
+    score_limits(max_pred_per_image, max_targets_per_image);
+    return RTOD_OK;
+}
+
+int rtod_score_detections_workspace(int batch, int cap, int max_targets_per_image, size_t* bytes) {
+    int max_pred = 0, max_tgt = 0;
+    score_limits(&max_pred, &max_tgt);
+    if (!bytes || batch < 1 || cap < 0 || max_targets_per_image < 1 || max_targets_per_image > max_tgt) {
+        set_error("score_detections_workspace: bad args (batch=%d cap=%d max_targets_per_image=%d, limit %d)", batch, cap, max_targets_per_image, max_tgt);
+        return RTOD_E_ARG;
+    }
+    *bytes = score_workspace_bytes(batch, cap, max_targets_per_image);
+    return RTOD_OK;
+}
+
+int rtod_score_detections(const float* det_dev, const int32_t* counts_dev, int cap, int batch, const float* tgt_dev, const int32_t* tgt_offsets_dev,
+                          int num_class, const uint32_t* class_mask_host, float min_box_size, double iou_threshold, int max_targets_per_image, int target_corners,
+                          int32_t* scores_dev, int32_t* totals_dev, int32_t* match_dev, float* match_iou_dev, int32_t* status_dev,
+                          void* workspace_dev, size_t workspace_bytes, void* stream) {
+    RTOD_GUARD_BEGIN
+    return launch_score_detections(det_dev, counts_dev, cap, batch, tgt_dev, tgt_offsets_dev, num_class, class_mask_host, min_box_size,
+                                   iou_threshold, max_targets_per_image, target_corners, scores_dev, totals_dev, match_dev, match_iou_dev, status_dev,
+                                   workspace_dev, workspace_bytes, (hipStream_t)stream);
+    RTOD_GUARD_END
+}
+
 int rtod_write_results_workspace(int batch, int n, size_t* bytes) {
     if (!bytes || batch < 1 || n < 1) { set_error("write_results_workspace: bad args"); return RTOD_E_ARG; }
     *bytes = nms_workspace_bytes(batch, n);

@@ -24,10 +24,9 @@
 //
 // Ties in objectness (undefined in the reference, torch.sort is unstable) resolve to the lower row.
 #include "rtod_internal.h"
+#include "iou_ref.h"
 
 namespace rtod {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int NMS_LDS_CAP = 8192;      // keys that fit the LDS sort (64 KiB)
 constexpr int NMS_RANK_CAP = 2048;     // up to here the keys are sorted by counting (two per thread)
@@ -198,17 +197,7 @@ void nms_filter_kernel(const float* __restrict__ pred, int B, int n, int num_cla
 }
 
 // ------------------------------------------------------------------------------------------ K2
-__device__ __forceinline__ float iou_ref(const f32x4 a, const f32x4 b) {
-    // bbox_iou, src/util.py:138-151 — same operation order, fp32, one rounding per op
-    const float ix1 = fmaxf(a[0], b[0]), iy1 = fmaxf(a[1], b[1]);
-    const float ix2 = fminf(a[2], b[2]), iy2 = fminf(a[3], b[3]);
-    const float iw = fmaxf((ix2 - ix1) + 1.0f, 0.0f);
-    const float ih = fmaxf((iy2 - iy1) + 1.0f, 0.0f);
-    const float inter = iw * ih;
-    const float a1 = ((a[2] - a[0]) + 1.0f) * ((a[3] - a[1]) + 1.0f);
-    const float a2 = ((b[2] - b[0]) + 1.0f) * ((b[3] - b[1]) + 1.0f);
-    return inter / ((a1 + a2) - inter);
-}
+// iou_ref (bbox_iou, src/util.py:138-151): iou_ref.h
 
 // IoU of the class-offset batched NMS: boxes shifted by class * max_wh before the test (so that one NMS pass serves all
 // classes; the shift costs coordinate bits in fp32 and is therefore restated, not optimised away), no +1, no contraction.

@@ -342,4 +342,12 @@ int launch_write_results(const float* pred, int batch, int n, int num_class, flo
 int launch_nms_class_offset(const float* pred, int batch, int n, int num_class, float conf, float iou_thr, float max_wh, int max_det,
                             float* out, int cap, int32_t* counts, void* ws, size_t ws_bytes, hipStream_t s);
 
+// validator: detections of write_results scored against ground truth (match.hip)
+void score_limits(int* max_pred, int* max_tgt);
+size_t score_workspace_bytes(int batch, int cap, int max_targets);
+int launch_score_detections(const float* det, const int32_t* counts, int cap, int batch, const float* tgt, const int32_t* tgt_off,
+                            int num_class, const uint32_t* class_mask, float min_box_size, double iou_threshold, int max_targets, int target_corners,
+                            int32_t* scores, int32_t* totals, int32_t* match, float* match_iou, int32_t* status,
+                            void* ws, size_t ws_bytes, hipStream_t s);
+
 }  // namespace rtod
