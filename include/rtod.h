@@ -223,6 +223,13 @@ int rtod_forward_timed(rtod_plan* plan, const float* x_dev, int batch, float* ou
 /* replaces `with model.train_mode():`                       src/darknet.py:305-314
  * train != 0: heads apply only the sigmoids (TRAIN=True in predict_transform, util.py:211). */
 int rtod_plan_set_train_decode(rtod_plan* plan, int train);
+/* (new) Turns the output of a forward run with train != 0 into the eval decode IN PLACE: columns 0-3 of every head become
+ * (sigmoid + cell offset) * stride and exp(raw) * anchor / stride * stride, in the operation order and with the exponential of
+ * the kernel that decodes that head in this plan (libm expf in exact-fp32 plans, the hardware exponential of the split-f16 / f16
+ * head epilogue) — which is why the call is bound to a plan.  pred_dev [batch, N, 5+C] is then bit-identical to the output of a
+ * forward of the same input with train == 0: one forward serves both the loss and the detections.  Enqueues only.
+ * RTOD_E_CFG: a head with `decode=v5`. */
+int rtod_plan_finish_decode(rtod_plan* plan, float* pred_dev, int batch, void* stream);
 /* Debug/test: keep != 0 disables liveness-based arena reuse so that every layer's output is still
  * intact after a forward (for rtod_plan_read_layer).  Call before rtod_plan_load_weights. */
 int rtod_plan_set_keep_all_layers(rtod_plan* plan, int keep);
@@ -325,6 +332,55 @@ int rtod_score_detections(const float* det_dev, const int32_t* counts_dev, int c
                           const uint32_t* class_mask_host, float min_box_size, double iou_threshold,
                           int max_targets_per_image, int target_corners, int32_t* scores_dev, int32_t* totals_dev,
                           int32_t* match_dev, float* match_iou_dev, int32_t* status_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+
+/* ---- training loss, forward value only ---------------------------------------------------------
+ * replaces DarknetTrainer.target_creator / target_layer / anchor_fit    train.py:129-209
+ *          xywh2YOLO, bbox_iou_wh                                       src/util.py:48-75, 156-172
+ *          DarknetTrainer.darknet_loss                                  train.py:211-230
+ * One [yolo] head of the prediction tensor: grid_h x grid_w cells (separate: rtod_plan_create_rect), stride = input / grid,
+ * n_anchors (<= 8) anchors as (w, h) pairs in input pixels.  Rows of a head: (gy * grid_w + gx) * n_anchors + a; the heads follow
+ * one another in cfg order (at most 4). */
+typedef struct rtod_yolo_head {
+    int grid_h, grid_w, stride, n_anchors;
+    int anchors[16];
+} rtod_yolo_head;
+/* Bytes of device workspace of rtod_yolo_loss(batch, n_rows); the same workspace serves rtod_darknet_loss_dense with
+ * rows = batch * n_rows (that call needs 40 bytes per 1024 rows). */
+int rtod_yolo_loss_workspace(int batch, int n_rows, size_t* bytes);
+/* pred_dev [batch, n_rows, 5+num_class]: the TRAIN=True decode (rtod_plan_set_train_decode).  boxes_dev [sum T][5+num_class] rows
+ * (cx, cy, w, h, 1, one-hot...) in input pixels, the images' boxes concatenated; box_offsets_dev [batch+1] row offsets into it.
+ * Targets, the reference's behaviour as it is (per image and head):
+ *   a box is skipped unless box[5] == 1 (only class 0 passes) and w >= min_box_size and h >= min_box_size (fp32; 24 in the reference);
+ *   anchor = FIRST maximum over the head's anchors of the IoU of (w, h) with (anchor_w, anchor_w), in doubles (bbox_iou_wh reads
+ *   the anchor's width twice; its height takes no part);
+ *   x = cx / stride, gx = int(x), fx = x - gx in doubles, y likewise; row (gy * grid_w + gx) * n_anchors + anchor of the head;
+ *   target row = the box's row with columns 0-3 replaced by (float(fy), float(fx), tw, th) — the centre slots are swapped in the
+ *   reference — tw = float(log(double(w / float(anchor_w) + 1e-16f))) with the quotient and the sum in fp32, th likewise with the
+ *   anchor's height;  of two boxes of an image on one row the LATER one wins; mask = 1 on such rows.
+ *   (new) a box whose cell lies outside the grid (x or y negative, >= the grid, or NaN) is skipped for that head and
+ *   status_dev[0] |= 1 (the reference wraps into the next grid row or raises IndexError); status_dev[0] |= 2: box_offsets_dev not
+ *   ascending from >= 0 for an image, whose boxes are then ignored.  The caller zeroes status_dev.
+ * Loss (sums over the batch, p = pred, t = target, accumulated in double, terms added in this order):
+ *   loss_dev[1..5] = 5 sum_obj (p0-t0)^2 + (p1-t1)^2,  5 sum_obj (p2-t2)^2 + (p3-t3)^2,  sum_obj (p4-t4)^2,
+ *                    0.5 sum_noobj (p4-t4)^2,  sum_obj sum_c (p_{5+c} - t_{5+c})^2;   loss_dev[0] = their sum.
+ *   per_image_dev (may be NULL) [batch][6]: the same six numbers per image.  No floating-point atomics: workgroup partials are
+ *   combined in a fixed order, the result is bit-identical from call to call.  A row without object reads only p4.
+ * Optional outputs (NULL: not written): target_dev [batch, n_rows, 5+num_class] and mask_dev [batch, n_rows] (0 / 1), what
+ * target_creator returns; n_obj_dev [batch]: masked rows per image.  Enqueues only (memset nodes + kernels: legal under stream
+ * capture).  RTOD_E_ARG (decided on the host): a null pointer, batch / n_rows / num_class < 1, n_heads outside 1..4, a head with
+ * n_anchors outside 1..8 or a non-positive grid, stride or anchor, heads whose rows do not add up to n_rows, a workspace that is
+ * too small or not 8-byte aligned, min_box_size NaN. */
+int rtod_yolo_loss(const float* pred_dev, int batch, int n_rows, int num_class,
+                   const rtod_yolo_head* heads, int n_heads,
+                   const float* boxes_dev, const int32_t* box_offsets_dev, float min_box_size,
+                   double* loss_dev, double* per_image_dev, float* target_dev, uint8_t* mask_dev,
+                   int32_t* n_obj_dev, int32_t* status_dev, void* workspace, size_t workspace_bytes, void* stream);
+/* darknet_loss(pred, target, obj_mask) on caller-supplied dense tensors: pred_dev / target_dev [rows, attrs], mask_dev [rows]
+ * (non-zero = object), loss_dev [6] as above.  Same kernels and summation scheme as rtod_yolo_loss; workgroups take 1024
+ * consecutive rows of the flat tensor, so for a one-image tensor the six doubles equal rtod_yolo_loss's bit for bit, for several
+ * images they agree to the accuracy of a double sum.  RTOD_E_ARG: null pointer, rows < 1, attrs < 5, workspace. */
+int rtod_darknet_loss_dense(const float* pred_dev, const float* target_dev, const uint8_t* mask_dev,
+                            int64_t rows, int attrs, double* loss_dev, void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -32,6 +32,10 @@ class LaunchInfo(C.Structure):
                 ("bytes_per_frame", C.c_int64), ("weight_bytes", C.c_int64)]
 
 
+class YoloHead(C.Structure):
+    _fields_ = [("grid_h", C.c_int), ("grid_w", C.c_int), ("stride", C.c_int), ("n_anchors", C.c_int), ("anchors", C.c_int * 16)]
+
+
 # name -> (restype, argtypes): every symbol include/rtod.h declares
 SIGNATURES = {
     "rtod_version": (C.c_int, []),
@@ -56,6 +60,7 @@ SIGNATURES = {
     "rtod_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "rtod_forward_timed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]),
     "rtod_plan_set_train_decode": (C.c_int, [C.c_void_p, C.c_int]),
+    "rtod_plan_finish_decode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "rtod_plan_set_keep_all_layers": (C.c_int, [C.c_void_p, C.c_int]),
     "rtod_plan_layer_shape": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "rtod_plan_read_layer": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
@@ -73,6 +78,10 @@ SIGNATURES = {
     "rtod_score_detections_workspace": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
     "rtod_score_detections": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_uint32), C.c_float,
                                         C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "rtod_yolo_loss_workspace": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    "rtod_yolo_loss": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(YoloHead), C.c_int, C.c_void_p, C.c_void_p, C.c_float,
+                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "rtod_darknet_loss_dense": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
 }
 
 _lib = None

@@ -756,6 +756,38 @@ int launch_decode(const float* raw, int64_t sb, int64_t sc, int64_t sy, int64_t 
 }
 
 // ---------------------------------------------------------------------------------------------
+// TRAIN=True decode -> eval decode, in place, columns 0-3 of one head: what the decode above (and the conv epilogues) add when
+// train == 0, from the values they store when train != 0 — the sigmoid for x / y, the raw sum for w / h — in their operation
+// order.  hw_exp: the head was decoded by the split-f16 epilogue (conv_f16s3_common.h: __expf), else by libm expf.
+__global__ void finish_decode_kernel(float* __restrict__ out, int B, DecodeArgs d, int hw_exp) {
+    const int64_t rows = (int64_t)d.GH * d.GW * d.n_anchors;
+    const int64_t total = (int64_t)B * rows * 4;
+    for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t b = t / (rows * 4);
+        const int64_t q = t - b * rows * 4;
+        const int64_t r = q >> 2;
+        const int c = (int)(q & 3);
+        const int cell = (int)(r / d.n_anchors), a = (int)(r - (int64_t)cell * d.n_anchors);
+        const int gy = cell / d.GW, gx = cell - gy * d.GW;
+        float* p = out + b * d.img_stride + d.head_off + r * d.attrs + c;
+        float v = *p;
+        if (c < 2) v = (v + (float)(c == 0 ? gx : gy)) * d.stride;
+        else {
+            const float ex = hw_exp ? __expf(v) : expf(v);
+            v = (ex * (c == 2 ? d.aw[a] : d.ah[a])) * d.stride;
+        }
+        *p = v;
+    }
+}
+
+int launch_finish_decode(float* out, int B, const DecodeArgs& d, int hw_exp, hipStream_t s) {
+    if (!out || d.GH <= 0 || d.GW <= 0 || d.attrs < 5 || d.n_anchors < 1 || d.n_anchors > 4 || d.v5) { set_error("finish_decode: bad args"); return RTOD_E_ARG; }
+    const int64_t total = (int64_t)B * d.GH * d.GW * d.n_anchors * 4;
+    hipLaunchKernelGGL(finish_decode_kernel, dim3(grid_for(total, 256)), dim3(256), 0, s, out, B, d, hw_exp);
+    return hip_fail(hipGetLastError(), "finish_decode launch");
+}
+
+// ---------------------------------------------------------------------------------------------
 // confidence_mask (src/util.py:106-117): out = pred * float(pred[...,4] > conf)
 __global__ void confidence_mask_kernel(const float* __restrict__ pred, int64_t rows, int attrs, float conf, float* __restrict__ out) {
     const int64_t total = rows * attrs;

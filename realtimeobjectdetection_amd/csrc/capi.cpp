@@ -216,6 +216,13 @@ int rtod_plan_set_train_decode(rtod_plan* plan, int train) {
     return RTOD_OK;
 }
 
+int rtod_plan_finish_decode(rtod_plan* plan, float* pred_dev, int batch, void* stream) {
+    RTOD_GUARD_BEGIN
+    if (!plan) { set_error("finish_decode: null plan"); return RTOD_E_ARG; }
+    return plan->p.finish_decode(pred_dev, batch, (hipStream_t)stream);
+    RTOD_GUARD_END
+}
+
 int rtod_plan_set_keep_all_layers(rtod_plan* plan, int keep) {
     if (!plan) { set_error("set_keep_all_layers: null plan"); return RTOD_E_ARG; }
     if (plan->p.d_arena) { set_error("set_keep_all_layers: must be called before rtod_plan_load_weights"); return RTOD_E_STATE; }
@@ -347,6 +354,28 @@ int rtod_score_detections(const float* det_dev, const int32_t* counts_dev, int c
     return launch_score_detections(det_dev, counts_dev, cap, batch, tgt_dev, tgt_offsets_dev, num_class, class_mask_host, min_box_size,
                                    iou_threshold, max_targets_per_image, target_corners, scores_dev, totals_dev, match_dev, match_iou_dev, status_dev,
                                    workspace_dev, workspace_bytes, (hipStream_t)stream);
+    RTOD_GUARD_END
+}
+
+int rtod_yolo_loss_workspace(int batch, int n_rows, size_t* bytes) {
+    if (!bytes || batch < 1 || n_rows < 1 || (int64_t)batch * n_rows > INT32_MAX) { set_error("yolo_loss_workspace: bad args (batch=%d n_rows=%d)", batch, n_rows); return RTOD_E_ARG; }
+    *bytes = yolo_loss_workspace_bytes(batch, n_rows);
+    return RTOD_OK;
+}
+
+int rtod_yolo_loss(const float* pred_dev, int batch, int n_rows, int num_class, const rtod_yolo_head* heads, int n_heads,
+                   const float* boxes_dev, const int32_t* box_offsets_dev, float min_box_size, double* loss_dev, double* per_image_dev,
+                   float* target_dev, uint8_t* mask_dev, int32_t* n_obj_dev, int32_t* status_dev, void* workspace, size_t workspace_bytes, void* stream) {
+    RTOD_GUARD_BEGIN
+    return launch_yolo_loss(pred_dev, batch, n_rows, num_class, heads, n_heads, boxes_dev, box_offsets_dev, min_box_size, loss_dev, per_image_dev,
+                            target_dev, mask_dev, n_obj_dev, status_dev, workspace, workspace_bytes, (hipStream_t)stream);
+    RTOD_GUARD_END
+}
+
+int rtod_darknet_loss_dense(const float* pred_dev, const float* target_dev, const uint8_t* mask_dev, int64_t rows, int attrs, double* loss_dev,
+                            void* workspace, size_t workspace_bytes, void* stream) {
+    RTOD_GUARD_BEGIN
+    return launch_darknet_loss_dense(pred_dev, target_dev, mask_dev, rows, attrs, loss_dev, workspace, workspace_bytes, (hipStream_t)stream);
     RTOD_GUARD_END
 }
 

@@ -1201,6 +1201,21 @@ bool Plan::stem_pool_fused() const { return precision >= 1 && stem_pool_pattern 
 bool Plan::bn_pool_fused(int layer) const { return bn_narrow_active() && opt_fuse_bn_pool && !keep_all && layers[layer].bn_pool >= 0; }
 bool Plan::stem2_active() const { return precision == 1 && !bn_split_active() && opt_stem2_kernel && stem2_pattern && !keep_all && convs[launches[0].conv_slot].split; }
 
+// Every head of the plan, in the arithmetic of the kernel that decodes it in a forward: fused into a split-f16 / f16 conv the
+// epilogue of conv_f16s3_common.h (hardware exp2), otherwise the exact-fp32 conv epilogue or the stand-alone kernel (libm expf).
+int Plan::finish_decode(float* out, int batch, hipStream_t s) const {
+    if (!out) { set_error("finish_decode: null pointer"); return RTOD_E_ARG; }
+    if (batch < 1 || batch > max_batch) { set_error("finish_decode: batch %d outside 1..%d", batch, max_batch); return RTOD_E_ARG; }
+    for (const auto& l : launches)
+        if (l.out_layer == -2 && l.dec.v5) { set_error("finish_decode: layer %d decodes YOLOv5-style, which has no TRAIN=True form", l.layer); return RTOD_E_CFG; }
+    RTOD_HIP(hipSetDevice(device));
+    for (const auto& l : launches) {
+        if (l.out_layer != -2) continue;
+        if (int rc = launch_finish_decode(out, batch, l.dec, precision >= 1 && l.kind == LK_CONV ? 1 : 0, s)) return rc;
+    }
+    return RTOD_OK;
+}
+
 int Plan::forward(const float* x, int batch, float* out, hipStream_t s, float* launch_ms, bool tune) {
     if (!weights_loaded) { set_error("forward: load_weights has not been called"); return RTOD_E_STATE; }
     if (!x || !out) { set_error("forward: null pointer"); return RTOD_E_ARG; }

@@ -143,6 +143,7 @@ struct Plan {
     int check_split_supported(int mode) const;   // mode 1 (f16s3) or 2 (f16): same layout requirements
     int load_weights(const float* w, size_t n);
     int forward(const float* x, int batch, float* out, hipStream_t s, float* launch_ms, bool tune = false);
+    int finish_decode(float* out, int batch, hipStream_t s) const;   // TRAIN=True output -> eval decode in place (rtod_plan_finish_decode)
     int set_option(const char* name, int value);
     int set_precision(int mode);              // re-plans: the launch list depends on the precision (option stem_pool)
     int set_tiles(int batch, const int* variants, int count);   // install a tile table (validated per launch)

@@ -331,6 +331,7 @@ int launch_bn_update_running(const BnUpdateEntry* entries, int n, const double* 
 int launch_copy(const View& in, const View& out, int B, hipStream_t s);
 int launch_view_to_nchw(const View& in, int B, float* out_nchw, hipStream_t s);
 // strided decode: raw element (b, ch, y, x) at raw[b*sb + ch*sc + y*sy + x*sx]
+int launch_finish_decode(float* out, int B, const DecodeArgs& d, int hw_exp, hipStream_t s);
 int launch_decode(const float* raw, int64_t sb, int64_t sc, int64_t sy, int64_t sx, int B,
                   const DecodeArgs& d, float* out, hipStream_t s);
 int launch_confidence_mask(const float* pred, int64_t rows, int attrs, float conf, float* out, hipStream_t s);
@@ -349,5 +350,13 @@ int launch_score_detections(const float* det, const int32_t* counts, int cap, in
                             int num_class, const uint32_t* class_mask, float min_box_size, double iou_threshold, int max_targets, int target_corners,
                             int32_t* scores, int32_t* totals, int32_t* match, float* match_iou, int32_t* status,
                             void* ws, size_t ws_bytes, hipStream_t s);
+
+// training loss, forward value: targets from boxes + the five-term sum of squares (loss.hip)
+size_t yolo_loss_workspace_bytes(int batch, int n_rows);
+int launch_yolo_loss(const float* pred, int batch, int n_rows, int num_class, const rtod_yolo_head* heads, int n_heads,
+                     const float* boxes, const int32_t* box_off, float min_box_size, double* loss, double* per_image,
+                     float* target, uint8_t* mask, int32_t* n_obj, int32_t* status, void* ws, size_t ws_bytes, hipStream_t s);
+int launch_darknet_loss_dense(const float* pred, const float* target, const uint8_t* mask, int64_t rows, int attrs, double* loss,
+                              void* ws, size_t ws_bytes, hipStream_t s);
 
 }  // namespace rtod

@@ -544,3 +544,20 @@ class Darknet(nn.Module):
             yield
         finally:
             self.TRAIN = False
+
+    def finish_decode(self, prediction):
+        """Turn the output of a forward run under ``train_mode()`` into the eval decode, in place (rtod_plan_finish_decode): the
+        tensor is then bit-identical to ``forward`` of the same input outside ``train_mode()``, so one forward serves the loss
+        and the detections.  Uses the plan of the last forward; returns ``prediction``."""
+        if self._plan is None or self._info is None:
+            raise RuntimeError("Darknet.finish_decode: no forward has run yet")
+        p = prediction
+        if not isinstance(p, torch.Tensor) or not p.is_cuda:
+            raise RuntimeError("Darknet.finish_decode: expected a CUDA (ROCm) tensor; this build has no CPU path")
+        if p.dtype != torch.float32 or p.dim() != 3 or not p.is_contiguous() or tuple(p.shape[1:]) != (self._info.total_rows, self._info.attrs):
+            raise ValueError("Darknet.finish_decode: expected the contiguous float32 [B,%d,%d] output of forward, got %s %s"
+                             % (self._info.total_rows, self._info.attrs, p.dtype, tuple(p.shape)))
+        with torch.cuda.device(p.device):
+            stream = C.c_void_p(torch.cuda.current_stream(p.device).cuda_stream)
+            _ffi.check(_ffi.lib().rtod_plan_finish_decode(self._plan, C.c_void_p(p.data_ptr()), p.size(0), stream))
+        return p

@@ -1,0 +1,247 @@
+"""Host-side mirror of the loss side of the reference's trainer (``DarknetTrainer``, train.py:17-230) on librtod.so.
+
+Only the FORWARD VALUE of the loss exists here: targets from ground-truth boxes (``target_creator``) and the five-term sum of
+squares (``darknet_loss``), the last step of ``feed_forward_through_model`` (train.py:412-425).  Backward, the optimiser, epochs
+and data loaders are out of scope.  Same names and return conventions as the reference:
+
+* ``DarknetTrainer.anchor_fit(box, anchors)``, ``target_layer(bboxes, scale, anchors)``     host mirrors, train.py:167-209
+* ``DarknetTrainer.target_creator(bndbox) -> (target, mask)``                               train.py:129-149, one launch sequence
+* ``DarknetTrainer.darknet_loss(pred, target, obj_mask)`` (``criterion``)                   train.py:211-230, dense tensors
+* ``DarknetTrainer.loss_from_boxes(pred, bndbox) -> (loss, components)``                    both fused: no dense target is built
+* ``DarknetTrainer.forward_loss(frames_or_x, bndbox)``                                      forward under ``train_mode()`` + loss
+
+The reference's behaviour is kept as it is: only boxes whose class-0 slot is 1 and whose sides are at least
+``min_box_size`` (24) count, ``anchor_fit`` compares a box with a square of the anchor's WIDTH, target slot 0 holds the y fraction
+and slot 1 the x fraction, the later of two boxes on one (cell, anchor) wins.  Heads come from the model's cfg (grid = input /
+stride, anchors by mask, cfg order) instead of the reference's hard-coded 13 / 26 / 52; at 416 the two agree.  A box whose cell lies
+outside a head's grid is skipped there and sets bit 0 of ``status``.  Loss kernels need CUDA (ROCm) tensors; no CPU fallback.
+"""
+import ctypes as C
+import math
+
+import numpy as np
+import torch
+
+from . import _ffi
+from .cfg import build_ir
+from .util import _need_cuda, _stream, prep_frames
+
+_ws_cache = {}
+
+
+def _workspace(dev, batch, n_rows):
+    key = (dev.index, batch, n_rows)
+    ws = _ws_cache.get(key)
+    if ws is None:
+        nbytes = C.c_size_t()
+        _ffi.check(_ffi.lib().rtod_yolo_loss_workspace(batch, n_rows, C.byref(nbytes)))
+        if len(_ws_cache) > 16:
+            _ws_cache.clear()
+        ws = _ws_cache[key] = (torch.empty((nbytes.value + 7) // 8, dtype=torch.float64, device=dev), nbytes.value)
+    return ws
+
+
+def make_heads(heads):
+    """ctypes array of rtod_yolo_head from ``[(grid_h, grid_w, stride, [(w, h), ...]), ...]``."""
+    arr = (_ffi.YoloHead * max(len(heads), 1))()
+    for q, (gh, gw, stride, anchors) in zip(arr, heads):
+        if len(anchors) > 8:
+            raise ValueError("yolo_loss: a head has %d anchors, the kernel takes at most 8" % len(anchors))
+        q.grid_h, q.grid_w, q.stride, q.n_anchors = int(gh), int(gw), int(stride), len(anchors)
+        for a, (w, h) in enumerate(anchors):
+            q.anchors[2 * a], q.anchors[2 * a + 1] = int(w), int(h)
+    return arr
+
+
+def pack_boxes(bndbox, attrs, dev):
+    """Per-image box lists -> (boxes [sum T, attrs] float32, offsets int32 [B+1]) on ``dev``; nothing synchronises."""
+    offs, parts = [0], []
+    for t in bndbox:
+        t = None if t is None or isinstance(t, int) else torch.as_tensor(t, dtype=torch.float32)
+        n = 0
+        if t is not None and t.numel():
+            parts.append(t.reshape(-1, attrs))
+            n = parts[-1].size(0)
+        offs.append(offs[-1] + n)
+    if parts and all(p.is_cuda for p in parts):
+        boxes = torch.cat(parts).contiguous()
+    elif parts:
+        boxes = torch.cat([p.cpu() for p in parts]).contiguous().pin_memory().to(dev, non_blocking=True)
+    else:
+        boxes = torch.zeros((1, attrs), dtype=torch.float32, device=dev)
+    return boxes, torch.tensor(offs, dtype=torch.int32).pin_memory().to(dev, non_blocking=True)
+
+
+def yolo_loss_async(pred, bndbox, heads, num_class, min_box_size=24, dense=False, per_image=False, status=None):
+    """Enqueue rtod_yolo_loss for one batch; nothing synchronises.  ``pred`` [B,N,5+C] (TRAIN=True decode), ``bndbox`` one
+    ``[T_i, 5+C]`` tensor (or None / empty) per image, ``heads`` as for ``make_heads``.  Returns a dict of device tensors:
+    ``components`` float64 [6] (total, xy, wh, obj, noobj, cls), ``n_obj`` int32 [B], ``status`` int32 [1] (OR-ed into the caller's
+    if given), and with ``per_image`` float64 [B,6], with ``dense`` ``target`` float32 [B,N,5+C] and ``mask`` uint8 [B,N]."""
+    _need_cuda(pred, "yolo_loss")
+    attrs = 5 + int(num_class)
+    if pred.dim() != 3 or pred.size(2) != attrs or not pred.is_contiguous():
+        raise ValueError("yolo_loss: expected contiguous predictions [B,N,%d], got %s" % (attrs, tuple(pred.shape)))
+    B, N = pred.size(0), pred.size(1)
+    if len(bndbox) != B:
+        raise ValueError("yolo_loss: %d box lists for a batch of %d" % (len(bndbox), B))
+    dev = pred.device
+    boxes, offs = pack_boxes(bndbox, attrs, dev)
+    ws, nbytes = _workspace(dev, B, N)
+    out = {"components": torch.empty(6, dtype=torch.float64, device=dev), "n_obj": torch.empty(B, dtype=torch.int32, device=dev),
+           "status": status if status is not None else torch.zeros(1, dtype=torch.int32, device=dev)}
+    if per_image:
+        out["per_image"] = torch.empty((B, 6), dtype=torch.float64, device=dev)
+    if dense:
+        out["target"] = torch.empty((B, N, attrs), dtype=torch.float32, device=dev)
+        out["mask"] = torch.empty((B, N), dtype=torch.uint8, device=dev)
+    ptr = lambda k: C.c_void_p(out[k].data_ptr()) if k in out else None
+    with torch.cuda.device(dev):
+        _ffi.check(_ffi.lib().rtod_yolo_loss(
+            C.c_void_p(pred.data_ptr()), B, N, int(num_class), make_heads(heads), len(heads), C.c_void_p(boxes.data_ptr()), C.c_void_p(offs.data_ptr()),
+            float(min_box_size), ptr("components"), ptr("per_image"), ptr("target"), ptr("mask"), ptr("n_obj"), ptr("status"),
+            C.c_void_p(ws.data_ptr()), nbytes, _stream(dev)))
+    return out
+
+
+def model_heads(model, height=None, width=None):
+    """``[(grid_h, grid_w, stride, anchors)]`` of a Darknet's [yolo] layers in cfg order, and its number of classes."""
+    h = int(model.net_info["height"]) if height is None else int(height)
+    w = (int(model.input_width) if getattr(model, "input_width", None) is not None else h) if width is None else int(width)
+    heads, classes = [], None
+    for L in build_ir(model.blocks, h, w).layers:
+        if L.type != "yolo":
+            continue
+        if L.decode_v5:
+            raise ValueError("DarknetTrainer: a [yolo] layer with decode=v5 has no TRAIN=True decode; the reference's loss is not defined for it")
+        heads.append((L.hout, L.wout, h // L.hout, [tuple(a) for a in L.anchors]))
+        classes = L.classes
+    if not heads:
+        raise ValueError("DarknetTrainer: the cfg has no [yolo] layer")
+    return heads, classes
+
+
+class DarknetTrainer:
+    """The loss side of the reference's trainer around a built ``Darknet`` (no optimiser, no epochs, no data loaders).
+
+    Attributes (the reference's): darknet, resolution, num_classes, criterion, TINY, history.  New: ``heads`` (from the cfg),
+    ``min_box_size`` (the literal 24 of target_layer), ``status`` (device int32 [1]: bit 0 = a box's cell lay outside a grid and
+    was skipped; OR-ed by every call, read it when you synchronise anyway), ``last_components`` (device float64 [6] of the
+    last loss: total, xy, wh, obj, noobj, cls)."""
+
+    def __init__(self, model, resolution=None, num_classes=None):
+        self.darknet = model
+        if resolution is not None:
+            assert isinstance(resolution, int) and resolution % 32 == 0
+            model.net_info["height"] = resolution
+        self.resolution = int(model.net_info["height"])
+        self.heads, classes = model_heads(model)
+        self.num_classes = int(classes if num_classes is None else num_classes)
+        if self.num_classes != classes:
+            raise ValueError("DarknetTrainer: num_classes=%d but the cfg's [yolo] layers have %d" % (self.num_classes, classes))
+        self.TINY = len(self.heads) == 2
+        self.min_box_size = 24
+        self.criterion = self.darknet_loss
+        self.history = dict()
+        self.status = None
+        self.last_components = None
+
+    # ------------------------------------------------------------------ host mirrors (small and exact)
+    @staticmethod
+    def anchor_fit(box, anchors):
+        """Index of the best fitting anchor (train.py:196-209): first maximum of the IoU of the box's (w, h) with a square of
+        the anchor's width — bbox_iou_wh reads the anchor's width twice — in Python floats."""
+        w1, h1 = float(np.float32(box[2])), float(np.float32(box[3]))
+        best, best_iou = 0, None
+        for i, anchor in enumerate(anchors):
+            w2 = h2 = float(anchor[0])
+            inter = min(w1, w2) * min(h1, h2)
+            iou = inter / (w1 * h1 + w2 * h2 - inter)
+            if best_iou is None or iou > best_iou:
+                best, best_iou = i, iou
+        return best
+
+    def target_layer(self, bboxes, scale, anchors):
+        """Target and mask of one square head (train.py:167-193) on the host: float32 ``[scale*scale*A, 5+C]`` and ``[...]``."""
+        A = len(anchors)
+        output = torch.zeros((scale * scale * A, 5 + self.num_classes))
+        mask = torch.zeros(output.shape[:-1])
+        stride = self.resolution // scale
+        boxes = np.asarray(torch.as_tensor(bboxes, dtype=torch.float32).cpu().numpy(), np.float32).reshape(-1, 5 + self.num_classes)
+        for box in boxes:
+            if box[5] != 1 or box[2] < np.float32(self.min_box_size) or box[3] < np.float32(self.min_box_size):
+                continue
+            fit = self.anchor_fit(box, anchors)
+            x, y = float(box[0]) / stride, float(box[1]) / stride
+            if not (0.0 <= x < scale and 0.0 <= y < scale):
+                continue                                              # outside the grid: skipped (the reference wraps or raises)
+            gx, gy = int(x), int(y)
+            loc = (gy * scale + gx) * A + fit
+            row = box.copy()
+            row[0], row[1] = np.float32(y - gy), np.float32(x - gx)      # the reference's swapped centre slots
+            with np.errstate(divide="ignore"):
+                row[2] = np.float32(math.log(float(box[2] / np.float32(anchors[fit][0]) + np.float32(1e-16))))
+                row[3] = np.float32(math.log(float(box[3] / np.float32(anchors[fit][1]) + np.float32(1e-16))))
+            output[loc] = torch.from_numpy(row)
+            mask[loc] = 1
+        return output, mask
+
+    # ------------------------------------------------------------------ device paths
+    def _status(self, dev):
+        if self.status is None or self.status.device != dev:
+            self.status = torch.zeros(1, dtype=torch.int32, device=dev)
+        return self.status
+
+    def _device(self):
+        if not torch.cuda.is_available():
+            raise RuntimeError("DarknetTrainer: this build has no CPU path")
+        return torch.device("cuda", torch.cuda.current_device())
+
+    def target_creator(self, bndbox):
+        """``(target float32 [B,N,5+C], mask bool [B,N])`` as device tensors (train.py:129-149), written by the kernels."""
+        dev = next((t.device for t in bndbox if isinstance(t, torch.Tensor) and t.is_cuda), None) or self._device()
+        n = sum(gh * gw * len(a) for gh, gw, _, a in self.heads)
+        pred = torch.zeros((len(bndbox), n, 5 + self.num_classes), dtype=torch.float32, device=dev)
+        out = yolo_loss_async(pred, bndbox, self.heads, self.num_classes, self.min_box_size, dense=True, status=self._status(dev))
+        return out["target"], out["mask"].bool()
+
+    def darknet_loss(self, pred, target, obj_mask):
+        """The loss of dense tensors (train.py:211-230) as a 0-dim float32 device tensor; ``last_components`` holds the doubles."""
+        _need_cuda(pred, "darknet_loss")
+        _need_cuda(target, "darknet_loss")
+        if not isinstance(obj_mask, torch.Tensor) or not obj_mask.is_cuda:
+            raise RuntimeError("darknet_loss: expected a CUDA (ROCm) mask; this build has no CPU path")
+        if pred.shape != target.shape or pred.dim() < 2 or tuple(obj_mask.shape) != tuple(pred.shape[:-1]):
+            raise ValueError("darknet_loss: pred %s, target %s and obj_mask %s do not fit" % (tuple(pred.shape), tuple(target.shape), tuple(obj_mask.shape)))
+        pred, target = pred.contiguous(), target.contiguous()
+        mask = (obj_mask if obj_mask.dtype == torch.uint8 else obj_mask.bool().to(torch.uint8)).contiguous()
+        attrs = pred.size(-1)
+        rows = pred.numel() // attrs
+        dev = pred.device
+        ws, nbytes = _workspace(dev, 1, rows)
+        comp = torch.empty(6, dtype=torch.float64, device=dev)
+        with torch.cuda.device(dev):
+            _ffi.check(_ffi.lib().rtod_darknet_loss_dense(C.c_void_p(pred.data_ptr()), C.c_void_p(target.data_ptr()), C.c_void_p(mask.data_ptr()),
+                                                          rows, attrs, C.c_void_p(comp.data_ptr()), C.c_void_p(ws.data_ptr()), nbytes, _stream(dev)))
+        self.last_components = comp
+        return comp[0].float()
+
+    def loss_from_boxes(self, pred, bndbox):
+        """``(loss, components)`` of a TRAIN=True prediction tensor against per-image box lists, without a dense target: loss a
+        0-dim float32 device tensor, components the device float64 [6] (total, xy, wh, obj, noobj, cls).  Nothing synchronises."""
+        out = yolo_loss_async(pred, bndbox, self.heads, self.num_classes, self.min_box_size, status=self._status(pred.device))
+        self.last_components = out["components"]
+        return out["components"][0].float(), out["components"]
+
+    def forward_loss(self, frames_or_x, bndbox):
+        """Forward under ``train_mode()`` (float32 ``[B,3,H,W]`` inputs, or uint8 ``[B,H,W,3]`` RGB frames letterboxed on the
+        device), then ``loss_from_boxes``; returns the loss."""
+        x = torch.as_tensor(frames_or_x)
+        if x.dtype == torch.uint8:
+            h = int(self.darknet.net_info["height"])
+            w = int(self.darknet.input_width) if getattr(self.darknet, "input_width", None) is not None else h
+            x = prep_frames(x, (w, h), mode="RGB")
+        elif not x.is_cuda:
+            x = x.cuda()
+        with torch.no_grad(), self.darknet.train_mode():
+            pred = self.darknet(x)
+        return self.loss_from_boxes(pred, bndbox)[0]

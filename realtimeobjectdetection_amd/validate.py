@@ -320,12 +320,15 @@ class DarknetValidator:
         self.recall = (tp / (tp + fn)).clone()
         self.f_score = (2 / ((1 / self.recall) + (1 / self.precision))).clone()
 
-    def _run(self, model, batches, settings, img_scores):
+    def _run(self, model, batches, settings, img_scores, trainer=None):
         """Shared body of validate_model and sweep: per batch ONE forward, then per (confidence, nms) setting write_results +
-        scoring with that setting's device totals.  Host synchronisations: one at the end (img_scores: one per batch)."""
+        scoring with that setting's device totals.  Host synchronisations: one at the end (img_scores: one per batch).
+        ``trainer`` (validate_model(loss=True)): the forward runs under ``train_mode()``, the loss of the batch is added to a
+        device sum, and ``finish_decode`` turns the tensor into the eval decode before write_results."""
         from .darknet import take_pending_overflow, raise_overflow
         S = len(settings)
         totals = status_log = None
+        loss_sum, n_batches = None, 0
         pending, guard = [], None                                        # pending: (samples, targets, status tensor [S]) per batch
 
         def enqueue(x, targets, conf, nms, tot, st, cap=None):
@@ -360,7 +363,15 @@ class DarknetValidator:
 
         for names, samples, targets in batches:
             with torch.no_grad():
-                pred = model(self._network_input(model, samples))
+                if trainer is None:
+                    pred = model(self._network_input(model, samples))
+                else:
+                    with model.train_mode():
+                        pred = model(self._network_input(model, samples))
+                    comp = trainer.loss_from_boxes(pred, targets)[1]
+                    loss_sum = comp.clone() if loss_sum is None else loss_sum.add_(comp)
+                    n_batches += 1
+                    model.finish_decode(pred)
             m, flag = take_pending_overflow(pred)                        # split-f16 range guard, read at the synchronisation below
             if m is not None:
                 guard = (m, flag)
@@ -384,9 +395,13 @@ class DarknetValidator:
             return [[0, 0, 0, 0] for _ in settings]
         torch.cuda.current_stream(totals.device).synchronize()           # THE host synchronisation of a run
         settle(pending)
+        if trainer is not None:
+            self.loss_components = (loss_sum / n_batches).cpu()
+            self.loss = float(self.loss_components[0])
+            self.loss_status = int(trainer.status.item())
         return totals.cpu().tolist()
 
-    def validate_model(self, model, batches=None, CUDA=True, img_scores=False):
+    def validate_model(self, model, batches=None, CUDA=True, img_scores=False, loss=False):
         """Validate a detector against ground truth (reference: test.py:244-280).  ``batches``: any iterable of
         ``(names, samples, targets)`` at any batch size — ``samples`` float32 ``[B,3,H,W]`` network inputs or uint8 ``[B,H,W,3]``
         RGB frames, ``targets`` one ``[T_i, 5+C]`` centre-form tensor per image; default: the ``CocoTargets`` of the constructor.
@@ -395,17 +410,32 @@ class DarknetValidator:
         split-f16 range flag is honoured like ``write_results`` honours it, and a batch whose detections exceeded
         ``write_results_async``'s default capacity is redone at full capacity (its ``samples`` are kept until then).
         The frames of a batch are independent only with ``model.eval()``: in training mode BatchNorm runs on the statistics of
-        the batch (as in the reference, which never calls ``.eval()`` and therefore validates at batch 1)."""
+        the batch (as in the reference, which never calls ``.eval()`` and therefore validates at batch 1).
+        ``loss=True`` also evaluates the reference's training loss (train.DarknetTrainer.loss_from_boxes) of every batch against
+        its targets, still with ONE forward per batch: it runs under ``train_mode()``, the loss is added to a sum on the device,
+        ``Darknet.finish_decode`` turns the tensor into the eval decode in place (bit-identical to an eval forward), and
+        write_results and the scoring go on as before.  After the run ``loss`` is the mean loss per batch (a float, like the
+        reference's ``history['train_loss']``), ``loss_components`` the float64 [6] means (total, xy, wh, obj, noobj, cls) and
+        ``loss_status`` the trainer's status word (bit 0: a box lay outside a grid and was skipped).  ``loss=False`` launches
+        nothing new."""
         if not CUDA:
             raise RuntimeError("DarknetValidator.validate_model: this build has no CPU path (CUDA=False)")
         if batches is None:
             batches = self.dataset
-        people, tp, fp, fn = self._run(model, batches, [(self.confidence, self.nms_thresh)], img_scores)[0]
+        trainer = None
+        if loss:
+            from .train import DarknetTrainer
+            trainer = DarknetTrainer(model, num_classes=self.num_classes)
+            trainer.min_box_size = self.min_box_size
+            self.loss, self.loss_components, self.loss_status = float("nan"), None, 0
+        people, tp, fp, fn = self._run(model, batches, [(self.confidence, self.nms_thresh)], img_scores, trainer)[0]
         self.save_total_scores_(people, tp, fp, fn)
         self._finish()
         print("\tPrecision = ", self.precision)
         print("\tRecall = ", self.recall)
         print("\tF_Score = ", self.f_score)
+        if loss:
+            print("\tLoss = ", self.loss)
 
     def validate_json(self, pred_dict, targets_by_name=None, img_scores=True, batch_size=64, device=None):
         """The same from stored detections (reference: test.py:282-313): ``pred_dict`` maps an image name to its detection rows
