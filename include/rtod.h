@@ -90,6 +90,12 @@ int rtod_plan_get_info(const rtod_plan* plan, rtod_plan_info* out);
 int rtod_plan_get_launch(const rtod_plan* plan, int index, rtod_launch_info* out);
 /* JSON description of the resolved layer IR (tests compare it with the Python IR / reference). */
 int rtod_plan_describe(const rtod_plan* plan, char* buf, size_t len, size_t* needed);
+/* (new) The packed weight image rtod_plan_load_weights would upload for the plan's current options and precision, computed on
+ * the host: no device is touched, so it works without one and before or after rtod_plan_load_weights.  Same two-call shape as
+ * rtod_plan_describe: *needed_floats (if given) receives the image's size; with out == NULL nothing else happens; otherwise
+ * capacity_floats must cover it (RTOD_E_SIZE) and `w` / n_floats are the .weights payload as for rtod_plan_load_weights. */
+int rtod_plan_pack_weights(const rtod_plan* plan, const float* w, size_t n_floats, float* out, size_t capacity_floats,
+                           size_t* needed_floats);
 const char* rtod_conv_variant_name(int variant);
 /* Demangled name of the kernel instantiation a launch runs (what rocprofv3 --kernel-trace prints): variant from
  * rtod_launch_info, epilogue 0 plain, 1 fused shortcut, 2 fused head decode, 3 / 4 = 0 / 1 with a fused pointwise conv;

@@ -47,6 +47,7 @@ SIGNATURES = {
     "rtod_plan_get_info": (C.c_int, [C.c_void_p, C.POINTER(PlanInfo)]),
     "rtod_plan_get_launch": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(LaunchInfo)]),
     "rtod_plan_describe": (C.c_int, [C.c_void_p, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "rtod_plan_pack_weights": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "rtod_conv_variant_name": (C.c_char_p, [C.c_int]),
     "rtod_conv_kernel_name": (C.c_int, [C.c_int, C.c_int, C.c_char_p, C.c_size_t]),
     "rtod_plan_launch_kernel_name": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.c_size_t]),

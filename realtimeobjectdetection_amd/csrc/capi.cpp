@@ -104,6 +104,19 @@ int rtod_plan_describe(const rtod_plan* plan, char* buf, size_t len, size_t* nee
     RTOD_GUARD_END
 }
 
+int rtod_plan_pack_weights(const rtod_plan* plan, const float* w, size_t n_floats, float* out, size_t capacity_floats, size_t* needed_floats) {
+    RTOD_GUARD_BEGIN
+    if (!plan) { set_error("pack_weights: null plan"); return RTOD_E_ARG; }
+    if (needed_floats) *needed_floats = (size_t)plan->p.packed_floats;
+    if (!out) return RTOD_OK;
+    if (capacity_floats < (size_t)plan->p.packed_floats) { set_error("pack_weights: capacity %zu < %lld floats", capacity_floats, (long long)plan->p.packed_floats); return RTOD_E_SIZE; }
+    std::vector<float> packed;
+    if (int rc = plan->p.pack_weights(w, n_floats, packed)) return rc;
+    if (!packed.empty()) memcpy(out, packed.data(), sizeof(float) * packed.size());
+    return RTOD_OK;
+    RTOD_GUARD_END
+}
+
 const char* rtod_conv_variant_name(int variant) {
     if (variant == 100 + STEM2_VARIANT) return "conv_stem2_f16s3<2 x 4x16, stem + 3x3 s2 + 1x1>";
     if (variant >= 100) { const TileRef t = family_of(variant - 100); return t ? t.fam->info(t.mode).name : ""; }   // split-f16 tiles: 100 + id

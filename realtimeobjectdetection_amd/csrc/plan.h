@@ -18,8 +18,8 @@ struct Layer {
     int type = LT_CONV;
     int cin = 0, cout = 0, hin = 0, win = 0, hout = 0, wout = 0;
     int size = 0, stride = 1, pad = 0;
-    bool bn = false, leaky = false;
-    int act = 0;                  // 0 linear, 1 leaky(0.1), 2 SiLU (cfg extension); leaky == (act == 1)
+    bool bn = false;
+    int act = 0;                  // 0 linear, 1 leaky(0.1), 2 SiLU (cfg extension)
     bool nearest = false;         // upsample: mode=nearest (cfg extension; the reference builds bilinear)
     bool decode_v5 = false;       // yolo: decode=v5 (cfg extension: YOLOv5-style head arithmetic)
     int pool_pad = 0;             // maxpool: symmetric=1 -> (size-1)/2 of -inf padding per side (cfg extension)
@@ -77,6 +77,9 @@ struct PackedConv {
     int ks_chunks = 0;                // split, option k_slices_split: sliced layer (slices of this many K-chunks), runs on conv_ks_f16s3 only; 0: not sliced
 };
 
+// One struct, defined over five files by concern: plan_cfg.cpp (parse, resolve_shapes: no HIP call), plan_build.cpp (options, buffer
+// planning, weight layout, describe), plan_weights.cpp (pack_weights, load_weights), plan_tiles.cpp (which kernel variant a conv
+// launch runs, autotune), plan_forward.cpp (the launch list on a stream, launch records).
 struct Plan {
     int height = 0, width = 0, max_batch = 0, device = 0;
     std::map<std::string, std::string> net_info;
@@ -139,10 +142,18 @@ struct Plan {
     int replan_or(const std::function<void()>& restore);   // re-plan after an option / precision change; refused: restore, re-plan, keep the message
     void assign_arena();
     void layout_weights();
-    bool uses_split(const Layer& L, int cin_p) const;
+    bool uses_split(const Layer& L) const;
     int check_split_supported(int mode) const;   // mode 1 (f16s3) or 2 (f16): same layout requirements
+    int pack_weights(const float* w, size_t n, std::vector<float>& packed) const;   // the packed image, on the host (no HIP call)
     int load_weights(const float* w, size_t n);
     int forward(const float* x, int batch, float* out, hipStream_t s, float* launch_ms, bool tune = false);
+    // the launches of one LK_CONV / LK_STEM step of forward, in order
+    int run_conv(size_t li, const float* x, int batch, float* out, hipStream_t s, bool tune_now);
+    int run_conv_f32(const Launch& l, ConvArgs& a, int batch, hipStream_t s) const;
+    int run_conv_split(size_t li, ConvArgs& a, int batch, hipStream_t s, bool tune_now);
+    int run_stem(const Launch& l, const float* x, int batch, hipStream_t s) const;
+    int raw_bn_begin(const Launch& l, int batch, bool site_ok, View& raw) const;        // raw view of a batch-statistics BatchNorm step, checked once
+    int run_raw_bn(const Launch& l, const View& raw, int batch, hipStream_t s) const;   // ... its statistics + normalise (the only caller of launch_bn_batch_split)
     int finish_decode(float* out, int batch, hipStream_t s) const;   // TRAIN=True output -> eval decode in place (rtod_plan_finish_decode)
     int set_option(const char* name, int value);
     int set_precision(int mode);              // re-plans: the launch list depends on the precision (option stem_pool)
@@ -155,7 +166,7 @@ struct Plan {
     std::vector<int> tuning;                    // scratch of the tuning forward
     std::map<std::vector<int>, int> tune_cache;
     // split-f16 tiles (ids: split_tiles.cpp): the rules live in these four, and launch_split_variant refuses by the same family facts
-    bool tile_legal(const Launch& l, int batch, int v) const;            // may this launch run tile v and give the layer's defined bits?
+    bool tile_legal(const Launch& l, int v) const;            // may this launch run tile v and give the layer's defined bits?
     int default_tile(const Launch& l, int batch) const;                  // closed-form choice per kind of layer
     int variant_for(const Launch& l, int batch) const;                   // forced or tuned id if legal, else the default
     std::vector<int> tile_candidates(const Launch& l, int batch) const;  // what autotune times, in screening order

@@ -1,0 +1,168 @@
+// Packed weights: the .weights payload -> the image the kernels read (host), and its upload.  Weight stream order in the
+// reference: src/darknet.py:316-410.
+#include "plan.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+
+namespace rtod {
+
+static uint16_t f32_to_f16_rn(float f) {           // IEEE binary16, round to nearest even, host side
+    uint32_t x; memcpy(&x, &f, 4);
+    const uint32_t sign = (x >> 16) & 0x8000u;
+    x &= 0x7FFFFFFFu;
+    if (x >= 0x7F800000u) return (uint16_t)(sign | (x > 0x7F800000u ? 0x7E00u : 0x7C00u));
+    if (x >= 0x477FF000u) return (uint16_t)(sign | 0x7C00u);               // rounds to >= 65520 -> inf
+    if (x < 0x33000001u) return (uint16_t)sign;                             // < 2^-25 -> 0
+    int e = (int)(x >> 23) - 127;
+    uint32_t m = (x & 0x7FFFFFu) | 0x800000u;
+    int shift = (e < -14) ? (13 + (-14 - e)) : 13;                          // subnormal halves lose extra bits
+    uint32_t half_m = m >> shift;
+    const uint32_t rem = m & ((1u << shift) - 1), halfway = 1u << (shift - 1);
+    if (rem > halfway || (rem == halfway && (half_m & 1))) ++half_m;
+    uint32_t out;
+    if (e < -14) out = half_m;                                               // subnormal (may carry into normal)
+    else out = ((uint32_t)(e + 15) << 10) + (half_m - 0x400u);               // carry propagates into the exponent
+    return (uint16_t)(sign | out);
+}
+static float f16_to_f32(uint16_t h) {
+    const uint32_t sign = (uint32_t)(h & 0x8000u) << 16;
+    const int e = (h >> 10) & 0x1F; const uint32_t m = h & 0x3FFu;
+    float v;
+    if (e == 0) v = std::ldexp((float)m, -24);
+    else if (e == 31) v = m ? NAN : INFINITY;
+    else v = std::ldexp((float)(m | 0x400u), e - 25);
+    uint32_t x; memcpy(&x, &v, 4); x |= sign; memcpy(&v, &x, 4);
+    return v;
+}
+
+// Split layouts, per output channel: a power-of-two pre-scale 2^e puts max|w| in [2^12, 2^13), so that low parts of weights down to
+// 2^-16 of the channel maximum stay normal f16; e is held to -24 .. 40 and an all-zero channel keeps e = 0.  ps = 2^e multiplies
+// the folded weights, inv = 2^-e / ACT_SCALE_F16S3 is what the kernels' epilogues multiply the sums by.
+struct PreScale { double ps = 1.0; float inv = 0.f; };
+static PreScale channel_prescale(const float* w, int64_t n, double scale) {
+    double mx = 0.0;
+    for (int64_t q = 0; q < n; ++q) mx = std::max(mx, std::fabs((double)w[q] * scale));
+    int e = 0;
+    if (mx > 0.0) { int ex; std::frexp(mx, &ex); e = 13 - ex; }      // mx * 2^e in [2^12, 2^13)
+    e = std::max(-24, std::min(40, e));
+    PreScale s;
+    s.ps = std::ldexp(1.0, e);
+    s.inv = (float)(std::ldexp(1.0, -e) / (double)ACT_SCALE_F16S3);
+    return s;
+}
+static void split_hi_lo(float v, uint16_t& hi, uint16_t& lo) {
+    hi = f32_to_f16_rn(v);
+    lo = f32_to_f16_rn(v - f16_to_f32(hi));
+}
+
+// The image rtod_plan_load_weights uploads, for the plan's current options and precision.  Host only: no HIP call, no device state.
+int Plan::pack_weights(const float* w, size_t n, std::vector<float>& packed) const {
+    if (!w) { set_error("load_weights: null pointer"); return RTOD_E_ARG; }
+    if ((int64_t)n < n_weight_floats) {
+        set_error("load_weights: stream has %zu floats, network needs %lld", n, (long long)n_weight_floats);
+        return RTOD_E_SIZE;
+    }
+    packed.assign((size_t)packed_floats, 0.0f);
+    std::vector<double> scale;
+    for (const auto& pc : convs) {
+        const Layer& L = layers[pc.layer];
+        const float* p = w + L.w_off;
+        const int C = L.cout, cin = L.cin, k = L.size;
+        scale.assign(C, 1.0);
+        float* bias = packed.data() + pc.b_off;
+        if (L.bn && opt_bn_batch_stats) {
+            // batch-statistics mode: the conv stays unfolded (no bias), beta / gamma go to the normalisation kernel; the
+            // stream's running mean / variance are not used (the reference only updates them as a side effect)
+            float* bnp = packed.data() + pc.bn_off;
+            for (int o = 0; o < C; ++o) { bias[o] = 0.f; bnp[o] = p[o]; bnp[pc.Npad + o] = p[C + o]; }
+            p += 4 * C;
+        } else if (L.bn) {
+            const float *beta = p, *gamma = p + C, *mean = p + 2 * C, *var = p + 3 * C;
+            for (int o = 0; o < C; ++o) {
+                // eval BatchNorm (x - mean) / sqrt(var + 1e-5) * gamma + beta folded into the conv
+                const double s = (double)gamma[o] / std::sqrt((double)var[o] + 1e-5);
+                scale[o] = s;
+                bias[o] = (float)((double)beta[o] - (double)mean[o] * s);
+            }
+            p += 4 * C;
+        } else {
+            for (int o = 0; o < C; ++o) bias[o] = p[o];
+            p += C;
+        }
+        // One walk over the OIHW block.  Every weight is folded to fp32 first ((double) w * scale, rounded once); the four layouts
+        // differ in where it lands alone (element index: floats of the fp32 layouts, halves of the split planes):
+        //   fp32 stem    [28][Cout], k = (ky*3+kx)*3 + c (conv_stem.hip)
+        //   fp32 panel   [Cout][Kpad], k = tap * cin_p + c
+        //   split stem   [Cout][32] f16 hi / lo planes, k = (ky*3+kx)*3 + c, k >= 27 zero
+        //   split planes K-chunk major, [chunk][Npad][32]: the rows of one stage are contiguous.  K order of the split kernels:
+        //                k = ((c/32)*k*k + tap)*32 + c%32 (channel chunk outer, tap inner);
+        //                narrow layers (conv_c16_f16s3.hip): tap-major over the 16 channels, k = tap * 16 + c, so chunk j holds
+        //                taps 2j and 2j + 1 (the unused half of the last chunk of an odd tap count stays zero in both planes)
+        const int taps = k * k;
+        auto dst = [&](int o, int c, int tap) -> int64_t {
+            if (pc.stem) return pc.split ? o * 32 + tap * 3 + c : (int64_t)(tap * 3 + c) * C + o;
+            if (!pc.split) return (int64_t)o * pc.Kpad + tap * pc.cin_p + c;
+            return pc.narrow ? ((int64_t)(tap / 2) * pc.Npad + o) * 32 + (tap % 2) * 16 + c
+                             : ((int64_t)((c / 32) * taps + tap) * pc.Npad + o) * 32 + (c % 32);
+        };
+        float* wp = packed.data() + pc.w_off;
+        uint16_t* wh = reinterpret_cast<uint16_t*>(packed.data() + pc.w_off);
+        uint16_t* wl = reinterpret_cast<uint16_t*>(packed.data() + pc.wl_off);
+        float* inv = packed.data() + pc.s_off;
+        if (pc.split && !pc.stem) for (int o = 0; o < pc.Npad; ++o) inv[o] = 1.0f / ACT_SCALE_F16S3;      // padding channels
+        const int64_t per_o = (int64_t)cin * taps;
+        for (int o = 0; o < C; ++o) {
+            const float* po = p + o * per_o;
+            PreScale s;
+            if (pc.split) { s = channel_prescale(po, per_o, scale[o]); inv[o] = s.inv; }
+            for (int c = 0; c < cin; ++c)
+                for (int tap = 0; tap < taps; ++tap) {
+                    const float v = (float)((double)po[(int64_t)c * taps + tap] * scale[o]);      // the fp32 folded weight
+                    const int64_t idx = dst(o, c, tap);
+                    if (!pc.split) { wp[idx] = v; continue; }
+                    const float vs = (float)((double)v * s.ps);                                   // exact (power of two)
+                    split_hi_lo(vs, wh[idx], wl[idx]);
+                }
+        }
+    }
+    return RTOD_OK;
+}
+
+int Plan::load_weights(const float* w, size_t n) {
+    std::vector<float> packed;
+    if (int rc = pack_weights(w, n, packed)) return rc;
+    RTOD_HIP(hipSetDevice(device));
+    if (!d_weights) RTOD_HIP(hipMalloc((void**)&d_weights, sizeof(float) * (size_t)packed_floats));
+    if (!d_arena) {
+        RTOD_HIP(hipMalloc((void**)&d_arena, sizeof(float) * (size_t)arena_floats));
+        // plain-f16 plans: every half of the arena starts as an f16 NaN, so a kernel that wrongly reads a lo plane (never
+        // written in that mode) turns the results NaN, deterministically, instead of picking up stale but plausible values
+        if (precision == 2) RTOD_HIP(hipMemsetD16((hipDeviceptr_t)d_arena, 0x7E00, 2 * (size_t)arena_floats));
+        else RTOD_HIP(hipMemset(d_arena, 0, sizeof(float) * (size_t)arena_floats));
+    }
+    if (opt_bn_batch_stats && !d_bn_stats && bn_stats_doubles > 0) {
+        RTOD_HIP(hipMalloc((void**)&d_bn_stats, sizeof(double) * (size_t)bn_stats_doubles));
+        RTOD_HIP(hipMemset(d_bn_stats, 0, sizeof(double) * (size_t)bn_stats_doubles));
+        int maxn = 0;
+        for (const auto& pc : convs) if (pc.stats_off >= 0) maxn = std::max(maxn, pc.Npad);
+        bn_partial_count = (int64_t)bn_partial_doubles(maxn);
+        RTOD_HIP(hipMalloc((void**)&d_bn_partial, sizeof(double) * (size_t)bn_partial_count));
+    }
+    if (bn_raw_floats > 0 && !d_bn_raw) RTOD_HIP(hipMalloc((void**)&d_bn_raw, sizeof(float) * (size_t)bn_raw_floats));
+    if (!d_scratch) {
+        bool any = false;
+        for (const auto& pc : convs) any = any || (!pc.split && !pc.stem && pc.slice_chunks > 0) || (pc.split && pc.ks_chunks > 0);
+        if (any) {
+            scratch_floats = KS_SCRATCH_FLOATS;                                   // 32 MB: L2 / Infinity-Cache resident; larger panels run the in-workgroup schedule
+            RTOD_HIP(hipMalloc((void**)&d_scratch, sizeof(float) * (size_t)scratch_floats));
+        }
+    }
+    RTOD_HIP(hipMemcpy(d_weights, packed.data(), sizeof(float) * (size_t)packed_floats, hipMemcpyHostToDevice));
+    RTOD_HIP(hipDeviceSynchronize());
+    weights_loaded = true;
+    return RTOD_OK;
+}
+
+}  // namespace rtod

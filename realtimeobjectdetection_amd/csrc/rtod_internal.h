@@ -184,7 +184,7 @@ int launch_conv_f16s3(const ConvArgs& a, int variant, hipStream_t s);
 // The split-f16 tile families.  A tile id is family base + mode; the constants below give each family's range and mode-level
 // facts.  split_tiles.cpp holds the one table of the ranges (TileFamily, family_of) and is, with this header, the only place
 // that compares an id against a base or a mode count.  Which tile a launch may run, runs by default and times in autotune is
-// decided in plan.cpp alone: Plan::tile_legal, Plan::default_tile, Plan::tile_candidates (variant_for / set_tiles /
+// decided in plan_tiles.cpp alone: Plan::tile_legal, Plan::default_tile, Plan::tile_candidates (variant_for / set_tiles /
 // tune_launch / launch_split_variant all go through them and family_of).  A new family: its constants here, one row there,
 // its rules in those three functions.
 // 3x3 stride-1 pad-1 convs with an LDS-resident input band (conv_band_f16s3.hip); weights in band K order

@@ -1,5 +1,5 @@
 // The split-f16 tile families: one row per id range.  Everything that turns a tile id into a family, a mode, a name, a kernel
-// or a launch goes through family_of; the rules about which launch may run which tile are Plan::tile_legal's (plan.cpp).
+// or a launch goes through family_of; the rules about which launch may run which tile are Plan::tile_legal's (plan_tiles.cpp).
 #include "rtod_internal.h"
 
 namespace rtod {

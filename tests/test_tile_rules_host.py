@@ -1,4 +1,4 @@
-"""CPU gate of the split-f16 tile rules (csrc/split_tiles.cpp, Plan::tile_legal / default_tile / variant_for / set_tiles): the
+"""CPU gate of the split-f16 tile rules (csrc/split_tiles.cpp, csrc/plan_tiles.cpp: Plan::tile_legal / default_tile / variant_for / set_tiles): the
 whole matrix of forced ids 0 .. 169 and single-entry tile tables 0 .. 169, per launch, at batch 1 and 8, over every case of
 tools/dump_tile_rules.py (cfgs x option sets x precisions 1 / 2), must be what tests/golden/tile_rules.json recorded: one
 SHA-256 of the tool's printed text per case and the case's launch count.  On a mismatch run the tool for that case

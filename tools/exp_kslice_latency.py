@@ -5,7 +5,7 @@
     on      k_slices_split = 1                                  (deep small-grid convs on the K-sliced tiles of conv_ks_f16s3.hip)
 after autotune, timed in interleaved rounds: forward + write_results eager and replayed as one HIP graph (HIP events around
 `iters` batches, medians over the rounds), then the per-launch times (a HIP-event pair around every launch, averaged) of the
-layers the option slices, off against on, with grid, K and the number of slices: the rule in plan.cpp (split_slice_chunks)
+layers the option slices, off against on, with grid, K and the number of slices: the rule in plan_build.cpp (split_slice_chunks)
 keeps a class of layers only if it is faster than `off` at batch 1 by more than the printed noise floor.
     python tools/exp_kslice_latency.py [--nets yolov3:608,yolov3:416,tiny:416] [--batches 1,2,8] [--precisions f16s3,f16]
                                        [--rounds 5] [--iters 60]"""
