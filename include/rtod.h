@@ -188,6 +188,10 @@ int rtod_plan_set_precision(rtod_plan* plan, int mode);
  *                       reads layer 0, layer 0's H and W are even and keep_all_layers is off, the pool runs in the stem's kernel:
  *                       layer 0 is never stored (describe: "fused_into": 1), the pool's launch entry stays in the list and
  *                       enqueues nothing.  Bit-identical to the stand-alone stem + max-pool kernel; 0: always stand-alone
+ *   "keep_head_inputs"  (default 0) the buffer read by every conv in front of a [yolo] layer (the detection-head convs, decode fused or not)
+ *                       keeps its lifetime to the end of the forward, so rtod_plan_read_layer of that input layer is valid after a
+ *                       forward in every precision: the activations rtod_conv1x1_wgrad needs.  Liveness only: launches, tiles and
+ *                       output bits are those of the plan without the option; arena_bytes may grow
  *   "force_f16s3_variant" / "force_f32_variant"   >= 0: one tile variant for every conv (tests, A/B runs)
  * Options that leave a cfg inexpressible in the split-f16 format return RTOD_E_CFG when precision is 1 or 2 (so does setting
  * "narrow_cin" back to 0 on a plan that needs it); the plan then stays as it was. */
@@ -203,6 +207,17 @@ int rtod_plan_set_overflow_flag(rtod_plan* plan, int32_t* flag_dev);
  * conv.weight (OIHW).  Folds eval-mode BatchNorm (eps 1e-5) into the conv, packs K-major panels,
  * allocates device memory on first call and uploads.  Synchronises the device. */
 int rtod_plan_load_weights(rtod_plan* plan, const float* w, size_t n_floats);
+/* (new) The detection heads of a plan in cfg order: conv_layers[i] is the conv directly in front of the i-th [yolo] layer,
+ * input_layers[i] the layer whose output it reads (conv_layers[i] - 1; see option "keep_head_inputs").  Returns the number of
+ * heads (also when it exceeds capacity: then only capacity entries were written; capacity 0 with NULL arrays asks for the count). */
+int rtod_plan_head_layers(const rtod_plan* plan, int* conv_layers, int* input_layers, int capacity);
+/* (new) Replaces the weights of ONE conv without BatchNorm on a plan whose weights are loaded: weight_oihw_host [Cout,Cin,k,k] and
+ * bias_host [Cout] (host float32).  Only that conv's bias, weight planes and per-channel scales are packed again, by the very
+ * function rtod_plan_load_weights packs every conv with, and only those ranges are copied to the device: the plan then holds
+ * the bits a full rtod_plan_load_weights of the edited stream gives.  Synchronises the device.  RTOD_E_ARG: a null pointer, a
+ * layer that is not a convolution, a conv with BatchNorm, a conv that hosts or is hosted in a fused pointwise pair;
+ * RTOD_E_STATE: before rtod_plan_load_weights. */
+int rtod_plan_update_conv(rtod_plan* plan, int layer, const float* weight_oihw_host, const float* bias_host);
 
 /* replaces Darknet.forward                                   src/darknet.py:199-303
  * x_dev: [batch,3,H,W] NCHW float32; out_dev: [batch,N,5+C] (new contiguous tensor in the
@@ -387,6 +402,41 @@ int rtod_yolo_loss(const float* pred_dev, int batch, int n_rows, int num_class,
  * images they agree to the accuracy of a double sum.  RTOD_E_ARG: null pointer, rows < 1, attrs < 5, workspace. */
 int rtod_darknet_loss_dense(const float* pred_dev, const float* target_dev, const uint8_t* mask_dev,
                             int64_t rows, int attrs, double* loss_dev, void* workspace, size_t workspace_bytes, void* stream);
+
+
+/* ---- gradients of the detection-head convs --------------------------------------------------------
+ * Gradient of the loss above with respect to the RAW head maps z (the outputs of the convs in front of the [yolo] layers), what
+ * autograd gives through predict_transform(TRAIN=True) (src/util.py:175-239) and darknet_loss (train.py:211-230).  pred_dev is
+ * the TRAIN=True decode of those maps.  With p a prediction row, t its target row, w = (5, 5, 5, 5, 1, 1, ...):
+ *   object row     g_c = 2 w_c (p_c - t_c)                                  c = 0 .. 4 + num_class
+ *   no-object row  g_4 = p_4 (= 2 * 0.5 * (p_4 - 0)), every other g_c = 0
+ *   dz_c = g_c p_c (1 - p_c) for the sigmoid columns c in {0, 1, 4, 5, ...};  dz_c = g_c for c in {2, 3}
+ * float32, one rounding per operation, in that order; a value the formula makes exactly 0 is stored as +0.
+ * grad_raw_dev: the heads' maps concatenated, head h as [batch, A_h * attrs, GH_h, GW_h] NCHW (channel a * attrs + c at cell
+ * (gy, gx) <-> prediction row (gy * GW + gx) * A + a of that head) at float offset batch * sum_{h' < h} A * attrs * GH * GW;
+ * batch * n_rows * attrs floats in all, every one written (no need to zero).  grad_pred_dev (may be NULL): g, [batch, n_rows, attrs].
+ * loss_dev (may be NULL): the six doubles, bit-identical to rtod_yolo_loss on the same arguments.  n_obj_dev (may be NULL) and
+ * status_dev as there.  Targets, filters, the owner map and the status bits are exactly that call's; workspace:
+ * rtod_yolo_loss_workspace.  Enqueues only (legal under stream capture).  RTOD_E_ARG as rtod_yolo_loss (and a NULL grad_raw_dev),
+ * decided on the host. */
+int rtod_yolo_loss_grad(const float* pred_dev, int batch, int n_rows, int num_class,
+                        const rtod_yolo_head* heads, int n_heads,
+                        const float* boxes_dev, const int32_t* box_offsets_dev, float min_box_size,
+                        float* grad_raw_dev, float* grad_pred_dev, double* loss_dev,
+                        int32_t* n_obj_dev, int32_t* status_dev,
+                        void* workspace, size_t workspace_bytes, void* stream);
+/* Weight and bias gradient of a 1x1 convolution z = W x + b over dense NCHW maps:
+ *   dw_dev[o][c] = sum_{b,p} dz[b,o,p] * x[b,c,p]   ([cout, cin], overwritten);   db_dev[o] = sum_{b,p} dz[b,o,p]   (may be NULL)
+ * dz_dev [batch, cout, pixels], x_dev [batch, cin, pixels].  Exact-fp32 MFMA (v_mfma_f32_32x32x2_f32): every partial sum is an
+ * fmaf chain.  K = batch * pixels is summed in S contiguous slices, one workgroup per (64 x 64 tile of dW, slice), whose sums a
+ * second kernel adds in ascending slice order; no floating-point atomics, so results are bit-identical from call to call.
+ * Slice rule (K alone):  units = ceil(K / 8);  slice length L = 8 * ceil(units / 16);  S = ceil(K / L) <= 16.
+ * Workspace: 4 * S * (cout * cin + cout) bytes, 16-byte aligned.  Shapes: cout >= 1 (any), cin a multiple of 32, pixels >= 1 (rows
+ * of an image may start on any 4-byte boundary), batch * pixels < 2^31 - 64.  Enqueues only.  RTOD_E_ARG: a null pointer, a shape
+ * outside those, a workspace that is too small or misaligned. */
+int rtod_conv1x1_wgrad_workspace(int batch, int cout, int cin, int pixels, size_t* bytes);
+int rtod_conv1x1_wgrad(const float* dz_dev, const float* x_dev, int batch, int cout, int cin, int pixels,
+                       float* dw_dev, float* db_dev, void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

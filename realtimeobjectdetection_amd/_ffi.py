@@ -83,6 +83,15 @@ SIGNATURES = {
     "rtod_yolo_loss": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(YoloHead), C.c_int, C.c_void_p, C.c_void_p, C.c_float,
                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "rtod_darknet_loss_dense": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "rtod_yolo_loss_grad": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(YoloHead), C.c_int, C.c_void_p, C.c_void_p, C.c_float,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "rtod_plan_head_layers": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int]),
+    "rtod_plan_update_conv": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+}
+# ... and the entry points whose names hold a digit (the scan of the header for declared names reads lower-case letters and '_')
+SIGNATURES_DIGIT_NAMES = {
+    "rtod_conv1x1_wgrad_workspace": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    "rtod_conv1x1_wgrad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
 }
 
 _lib = None
@@ -103,7 +112,7 @@ def lib():
         if os.path.exists(bundled):
             C.CDLL(bundled, mode=C.RTLD_GLOBAL)
         l = C.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_DIGIT_NAMES.items()):
             fn = getattr(l, name)
             fn.restype = res
             fn.argtypes = args

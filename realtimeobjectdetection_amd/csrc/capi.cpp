@@ -392,6 +392,49 @@ int rtod_darknet_loss_dense(const float* pred_dev, const float* target_dev, cons
     RTOD_GUARD_END
 }
 
+int rtod_yolo_loss_grad(const float* pred_dev, int batch, int n_rows, int num_class, const rtod_yolo_head* heads, int n_heads,
+                        const float* boxes_dev, const int32_t* box_offsets_dev, float min_box_size, float* grad_raw_dev, float* grad_pred_dev,
+                        double* loss_dev, int32_t* n_obj_dev, int32_t* status_dev, void* workspace, size_t workspace_bytes, void* stream) {
+    RTOD_GUARD_BEGIN
+    return launch_yolo_loss_grad(pred_dev, batch, n_rows, num_class, heads, n_heads, boxes_dev, box_offsets_dev, min_box_size, grad_raw_dev,
+                                 grad_pred_dev, loss_dev, n_obj_dev, status_dev, workspace, workspace_bytes, (hipStream_t)stream);
+    RTOD_GUARD_END
+}
+
+int rtod_conv1x1_wgrad_workspace(int batch, int cout, int cin, int pixels, size_t* bytes) {
+    if (!bytes || batch < 1 || cout < 1 || cin < 32 || cin % 32 || pixels < 1 || (int64_t)batch * pixels > INT32_MAX - 64 || (int64_t)cout * cin > INT32_MAX) {
+        set_error("conv1x1_wgrad_workspace: bad args (batch=%d cout=%d cin=%d pixels=%d; cin must be a multiple of 32)", batch, cout, cin, pixels);
+        return RTOD_E_ARG;
+    }
+    *bytes = wgrad_workspace_bytes(batch, cout, cin, pixels);
+    return RTOD_OK;
+}
+
+int rtod_conv1x1_wgrad(const float* dz_dev, const float* x_dev, int batch, int cout, int cin, int pixels, float* dw_dev, float* db_dev,
+                       void* workspace, size_t workspace_bytes, void* stream) {
+    RTOD_GUARD_BEGIN
+    return launch_conv1x1_wgrad(dz_dev, x_dev, batch, cout, cin, pixels, dw_dev, db_dev, workspace, workspace_bytes, (hipStream_t)stream);
+    RTOD_GUARD_END
+}
+
+int rtod_plan_head_layers(const rtod_plan* plan, int* conv_layers, int* input_layers, int capacity) {
+    if (!plan || capacity < 0 || (capacity > 0 && (!conv_layers || !input_layers))) { set_error("plan_head_layers: bad args"); return RTOD_E_ARG; }
+    int n = 0;
+    for (const auto& L : plan->p.layers) {
+        if (!plan->p.feeds_yolo(L.index)) continue;
+        if (n < capacity) { conv_layers[n] = L.index; input_layers[n] = L.index - 1; }
+        ++n;
+    }
+    return n;
+}
+
+int rtod_plan_update_conv(rtod_plan* plan, int layer, const float* weight_oihw_host, const float* bias_host) {
+    RTOD_GUARD_BEGIN
+    if (!plan) { set_error("update_conv: null plan"); return RTOD_E_ARG; }
+    return plan->p.update_conv(layer, weight_oihw_host, bias_host);
+    RTOD_GUARD_END
+}
+
 int rtod_write_results_workspace(int batch, int n, size_t* bytes) {
     if (!bytes || batch < 1 || n < 1) { set_error("write_results_workspace: bad args"); return RTOD_E_ARG; }
     *bytes = nms_workspace_bytes(batch, n);

@@ -22,77 +22,17 @@
 //             so the six doubles are bit-identical from call to call
 //   dense     (optional) target [B,N,5+C] and mask [B,N] from the owner map: zero fill and scatter in one pass
 // rtod_darknet_loss_dense runs reduce + finalize on a caller's dense target / mask instead (darknet_loss's own signature).
-#include "rtod_internal.h"
+// The head table and the target arithmetic of one box live in loss_common.h: loss_grad.hip (the gradient) shares them and enters
+// the memset / assign / reduce / finalize sequence through enqueue_loss_core.
+#include "loss_common.h"
 
 namespace rtod {
-
-constexpr int LOSS_BLOCK = 256;
-constexpr int LOSS_WAVES = LOSS_BLOCK / 64;
-constexpr int LOSS_ROWS = 1024;                   // rows per workgroup of the reduce phase: 4 x 64 per wave
-constexpr int LOSS_MAX_HEADS = 4;
-constexpr int LOSS_MAX_ANCHORS = 8;
-
-struct LossHeads {
-    int n;
-    int gh[LOSS_MAX_HEADS], gw[LOSS_MAX_HEADS], stride[LOSS_MAX_HEADS], na[LOSS_MAX_HEADS];
-    int off[LOSS_MAX_HEADS + 1];                  // first row of each head; off[n] = N
-    int aw[LOSS_MAX_HEADS][LOSS_MAX_ANCHORS], ah[LOSS_MAX_HEADS][LOSS_MAX_ANCHORS];
-};
 
 static int64_t loss_blocks(int64_t rows) { return (rows + LOSS_ROWS - 1) / LOSS_ROWS; }
 
 size_t yolo_loss_workspace_bytes(int batch, int n_rows) {
     const size_t partials = sizeof(double) * 5 * (size_t)batch * (size_t)loss_blocks(n_rows);
     return (partials + sizeof(int32_t) * (size_t)batch * n_rows + 15) & ~(size_t)15;
-}
-
-// bbox_iou_wh (src/util.py:168-172) on Python doubles; the anchor's second side is its WIDTH again (wh2[0] read twice)
-__device__ __forceinline__ int anchor_fit(double w1, double h1, const int* aw, int na) {
-    int best = 0;
-    double bestv = 0.0;
-    for (int a = 0; a < na; ++a) {
-        const double w2 = (double)aw[a], h2 = w2;
-        const double inter = fmin(w1, w2) * fmin(h1, h2);
-        const double uni = (w1 * h1 + w2 * h2) - inter;
-        const double v = inter / uni;
-        if (a == 0 || v > bestv) { bestv = v; best = a; }           // list.index(max(...)): the first maximum
-    }
-    return best;
-}
-
-// xywh2YOLO's cell and centre fractions (src/util.py:67-72), doubles.  False: the cell lies outside the grid (also for NaN).
-__device__ __forceinline__ bool box_cell(float cx, float cy, int stride, int gw, int gh, int& gx, int& gy, double& fx, double& fy) {
-    const double x = (double)cx / (double)stride, y = (double)cy / (double)stride;
-    if (!(x >= 0.0 && x < (double)gw && y >= 0.0 && y < (double)gh)) return false;
-    gx = (int)x; gy = (int)y;
-    fx = x - (double)gx; fy = y - (double)gy;
-    return true;
-}
-
-// torch.log(box / anchor + 1e-16) on a float32 tensor (src/util.py:73-74): float32 quotient and sum, then the correctly rounded
-// logarithm of that float32 value
-__device__ __forceinline__ float log_ratio(float v, int anchor) {
-    const float q = v / (float)anchor + 1e-16f;
-    return (float)log((double)q);
-}
-
-// the head that holds row r of an image, and the anchor of that row
-__device__ __forceinline__ int head_of_row(const LossHeads& H, int r, int& a) {
-    int h = 0;
-    while (h + 1 < H.n && r >= H.off[h + 1]) ++h;
-    a = (r - H.off[h]) % H.na[h];
-    return h;
-}
-
-// columns 0-3 of the target row that box `bx` leaves on (head h, anchor a): (y fraction, x fraction, tw, th) — the centre slots
-// are swapped in the reference (train.py:187: the caller unpacks xywh2YOLO's (y_coor, x_coor, y, x, w, h) as w-first)
-__device__ __forceinline__ void target_xywh(const LossHeads& H, int h, int a, const float* bx, float t[4]) {
-    int gx = 0, gy = 0;
-    double fx = 0.0, fy = 0.0;
-    box_cell(bx[0], bx[1], H.stride[h], H.gw[h], H.gh[h], gx, gy, fx, fy);
-    t[0] = (float)fy; t[1] = (float)fx;
-    t[2] = log_ratio(bx[2], H.aw[h][a]);
-    t[3] = log_ratio(bx[3], H.ah[h][a]);
 }
 
 __global__ __launch_bounds__(LOSS_BLOCK)
@@ -246,7 +186,7 @@ void loss_dense_kernel(const int32_t* __restrict__ owner, const float* __restric
     }
 }
 
-static int make_heads(const rtod_yolo_head* heads, int n_heads, int n_rows, LossHeads& H, const char* who) {
+int make_heads(const rtod_yolo_head* heads, int n_heads, int n_rows, LossHeads& H, const char* who) {
     if (n_heads < 1 || n_heads > LOSS_MAX_HEADS) { set_error("%s: %d heads outside 1..%d", who, n_heads, LOSS_MAX_HEADS); return RTOD_E_ARG; }
     H.n = n_heads;
     int64_t off = 0;
@@ -275,6 +215,25 @@ static int make_heads(const rtod_yolo_head* heads, int n_heads, int n_rows, Loss
     return RTOD_OK;
 }
 
+int32_t* loss_owner_map(void* ws, int batch, int n_rows) {
+    return (int32_t*)((double*)ws + 5 * (int64_t)batch * loss_blocks(n_rows));
+}
+
+int enqueue_loss_core(const float* pred, int batch, int n_rows, int attrs, const LossHeads& H, const float* boxes, const int32_t* box_off,
+                      float min_box_size, double* loss, double* per_image, int32_t* n_obj, int32_t* status, void* ws, hipStream_t s) {
+    const int64_t nblk = loss_blocks(n_rows);
+    double* partials = (double*)ws;
+    int32_t* owner = loss_owner_map(ws, batch, n_rows);
+    RTOD_HIP(hipMemsetAsync(owner, 0xFF, sizeof(int32_t) * (size_t)batch * n_rows, s));
+    if (n_obj) RTOD_HIP(hipMemsetAsync(n_obj, 0, sizeof(int32_t) * (size_t)batch, s));
+    hipLaunchKernelGGL(loss_assign_kernel, dim3(batch), dim3(LOSS_BLOCK), 0, s, boxes, box_off, n_rows, attrs, H, min_box_size, owner, status);
+    if (loss || n_obj)
+        hipLaunchKernelGGL(loss_reduce_kernel<false>, dim3((unsigned)nblk, batch), dim3(LOSS_BLOCK), 0, s, pred, (int64_t)n_rows, attrs, owner, boxes, H,
+                           (const float*)nullptr, (const uint8_t*)nullptr, partials, n_obj);
+    if (loss) hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(64), 0, s, partials, batch, nblk, loss, per_image);
+    return hip_fail(hipGetLastError(), "yolo_loss launch");
+}
+
 int launch_yolo_loss(const float* pred, int batch, int n_rows, int num_class, const rtod_yolo_head* heads, int n_heads,
                      const float* boxes, const int32_t* box_off, float min_box_size, double* loss, double* per_image,
                      float* target, uint8_t* mask, int32_t* n_obj, int32_t* status, void* ws, size_t ws_bytes, hipStream_t s) {
@@ -287,15 +246,8 @@ int launch_yolo_loss(const float* pred, int batch, int n_rows, int num_class, co
     if (ws_bytes < yolo_loss_workspace_bytes(batch, n_rows)) { set_error("yolo_loss: workspace too small"); return RTOD_E_ARG; }
     if ((uintptr_t)ws & 7) { set_error("yolo_loss: workspace must be 8-byte aligned"); return RTOD_E_ARG; }
     const int attrs = 5 + num_class;
-    const int64_t nblk = loss_blocks(n_rows);
-    double* partials = (double*)ws;
-    int32_t* owner = (int32_t*)(partials + 5 * (int64_t)batch * nblk);
-    RTOD_HIP(hipMemsetAsync(owner, 0xFF, sizeof(int32_t) * (size_t)batch * n_rows, s));
-    if (n_obj) RTOD_HIP(hipMemsetAsync(n_obj, 0, sizeof(int32_t) * (size_t)batch, s));
-    hipLaunchKernelGGL(loss_assign_kernel, dim3(batch), dim3(LOSS_BLOCK), 0, s, boxes, box_off, n_rows, attrs, H, min_box_size, owner, status);
-    hipLaunchKernelGGL(loss_reduce_kernel<false>, dim3((unsigned)nblk, batch), dim3(LOSS_BLOCK), 0, s, pred, (int64_t)n_rows, attrs, owner, boxes, H,
-                       (const float*)nullptr, (const uint8_t*)nullptr, partials, n_obj);
-    hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(64), 0, s, partials, batch, nblk, loss, per_image);
+    if (int rc = enqueue_loss_core(pred, batch, n_rows, attrs, H, boxes, box_off, min_box_size, loss, per_image, n_obj, status, ws, s)) return rc;
+    const int32_t* owner = loss_owner_map(ws, batch, n_rows);
     if (target || mask) {
         const int64_t total = (int64_t)batch * n_rows * attrs;
         const int64_t blocks = std::min<int64_t>((total + LOSS_BLOCK - 1) / LOSS_BLOCK, 4096);

@@ -78,7 +78,7 @@ struct PackedConv {
 };
 
 // One struct, defined over five files by concern: plan_cfg.cpp (parse, resolve_shapes: no HIP call), plan_build.cpp (options, buffer
-// planning, weight layout, describe), plan_weights.cpp (pack_weights, load_weights), plan_tiles.cpp (which kernel variant a conv
+// planning, weight layout, describe), plan_weights.cpp (pack_conv, pack_weights, load_weights, update_conv), plan_tiles.cpp (which kernel variant a conv
 // launch runs, autotune), plan_forward.cpp (the launch list on a stream, launch records).
 struct Plan {
     int height = 0, width = 0, max_batch = 0, device = 0;
@@ -128,6 +128,8 @@ struct Plan {
     bool opt_zero_copy_concat = true; // route producers write straight into the concat buffer (else copy kernels)
     bool opt_narrow_cin = false;      // precisions 1 / 2 accept convs after layer 0 that read exactly 16 channels (conv_c16_f16s3.hip)
     bool opt_stem_pool = false;       // precisions 1 / 2: a 3x3 / stride 1 / 16-filter layer 0 runs the split-f16 stem of conv_stem16_f16s3.hip (no pack launch)
+    bool opt_keep_head_inputs = false; // the buffer every conv in front of a [yolo] layer reads stays live to the end of the forward (rtod_plan_read_layer after it:
+                                      // the activations of rtod_conv1x1_wgrad); liveness only: launches, tiles and output bits are unchanged
     bool opt_fuse_stem_pool = true;   // ... with the 2x2 / stride-2 max-pool that follows it in the same kernel where the plan allows it (off: A/B and tests)
     int opt_force_f16s3_variant = -1; // >= 0: tile variant for every split-f16 conv (>= BAND_VARIANT_BASE: band layers)
     int opt_force_f32_variant = -1;   // >= 0: tile variant for every exact-fp32 conv
@@ -145,7 +147,11 @@ struct Plan {
     bool uses_split(const Layer& L) const;
     int check_split_supported(int mode) const;   // mode 1 (f16s3) or 2 (f16): same layout requirements
     int pack_weights(const float* w, size_t n, std::vector<float>& packed) const;   // the packed image, on the host (no HIP call)
+    void pack_conv(const PackedConv& pc, const float* p, float* blk) const;         // one conv: its block of the stream -> its block of the image (blk = image + pc.w_off)
+    int64_t conv_block_floats(size_t slot) const;                                   // floats of that block: every range of the conv, padding to the next conv included
     int load_weights(const float* w, size_t n);
+    int update_conv(int layer, const float* weight_oihw, const float* bias);        // re-pack and upload one conv without BatchNorm (rtod_plan_update_conv)
+    bool feeds_yolo(int layer) const { return layers[layer].type == LT_CONV && layer + 1 < (int)layers.size() && layers[layer + 1].type == LT_YOLO; }
     int forward(const float* x, int batch, float* out, hipStream_t s, float* launch_ms, bool tune = false);
     // the launches of one LK_CONV / LK_STEM step of forward, in order
     int run_conv(size_t li, const float* x, int batch, float* out, hipStream_t s, bool tune_now);

@@ -62,7 +62,7 @@ int Plan::set_option(const char* name, int value) {
         {"k_slice_workgroups", &Plan::opt_k_slice_workgroups}, {"k_slices_split", &Plan::opt_k_slices_split}, {"patch_kernel", &Plan::opt_patch_kernel},
         {"stem_kernel", &Plan::opt_stem_kernel}, {"band_kernel", &Plan::opt_band_kernel}, {"fuse_shortcut", &Plan::opt_fuse_shortcut},
         {"fuse_decode", &Plan::opt_fuse_decode}, {"zero_copy_concat", &Plan::opt_zero_copy_concat}, {"narrow_cin", &Plan::opt_narrow_cin},
-        {"stem_pool", &Plan::opt_stem_pool}, {"fuse_stem_pool", &Plan::opt_fuse_stem_pool},
+        {"stem_pool", &Plan::opt_stem_pool}, {"fuse_stem_pool", &Plan::opt_fuse_stem_pool}, {"keep_head_inputs", &Plan::opt_keep_head_inputs},
     };
     const std::string k(name);
     bool* flag = nullptr; int* num = nullptr;
@@ -291,6 +291,11 @@ int Plan::plan_buffers() {
         else if (l.out_layer >= 0) touch(buf_of_layer(l.out_layer), t);
         if (l.pw_guest >= 0) touch(buf_of_layer(launches[l.pw_guest].out_layer), t);     // written by the host's epilogue when fused
     }
+    // option keep_head_inputs: what a head conv (the conv in front of a [yolo] layer, decode fused or not) reads stays intact to the
+    // end of the forward; nothing else about the plan depends on the option
+    if (opt_keep_head_inputs)
+        for (const auto& l : launches)
+            if (l.kind == LK_CONV && feeds_yolo(l.layer)) touch(buf_of_layer(l.in_layer), n);
     // a concat buffer is live from its first producer to its last consumer: touches above cover both
     for (int b = 0; b < NB; ++b) {
         if (bufs[b].last < 0) { bufs[b].first = bufs[b].last = 0; }      // never used (dead layer): still give it space

@@ -57,6 +57,76 @@ static void split_hi_lo(float v, uint16_t& hi, uint16_t& lo) {
     lo = f32_to_f16_rn(v - f16_to_f32(hi));
 }
 
+// One conv's block of the .weights payload (p: [bn.bias, bn.weight, running_mean, running_var] or [conv.bias], then conv.weight
+// OIHW) -> its block of the packed image (blk = image + pc.w_off, conv_block_floats floats, zero on entry: padding rows, padding
+// channels and the unused halves of narrow chunks stay zero).  The one place that folds, pre-scales and places a conv's weights:
+// pack_weights walks every conv through it, update_conv one.
+void Plan::pack_conv(const PackedConv& pc, const float* p, float* blk) const {
+    const Layer& L = layers[pc.layer];
+    const int C = L.cout, cin = L.cin, k = L.size;
+    std::vector<double> scale(C, 1.0);
+    float* bias = blk + (pc.b_off - pc.w_off);
+    if (L.bn && opt_bn_batch_stats) {
+        // batch-statistics mode: the conv stays unfolded (no bias), beta / gamma go to the normalisation kernel; the
+        // stream's running mean / variance are not used (the reference only updates them as a side effect)
+        float* bnp = blk + (pc.bn_off - pc.w_off);
+        for (int o = 0; o < C; ++o) { bias[o] = 0.f; bnp[o] = p[o]; bnp[pc.Npad + o] = p[C + o]; }
+        p += 4 * C;
+    } else if (L.bn) {
+        const float *beta = p, *gamma = p + C, *mean = p + 2 * C, *var = p + 3 * C;
+        for (int o = 0; o < C; ++o) {
+            // eval BatchNorm (x - mean) / sqrt(var + 1e-5) * gamma + beta folded into the conv
+            const double s = (double)gamma[o] / std::sqrt((double)var[o] + 1e-5);
+            scale[o] = s;
+            bias[o] = (float)((double)beta[o] - (double)mean[o] * s);
+        }
+        p += 4 * C;
+    } else {
+        for (int o = 0; o < C; ++o) bias[o] = p[o];
+        p += C;
+    }
+    // One walk over the OIHW block.  Every weight is folded to fp32 first ((double) w * scale, rounded once); the four layouts
+    // differ in where it lands alone (element index: floats of the fp32 layouts, halves of the split planes):
+    //   fp32 stem    [28][Cout], k = (ky*3+kx)*3 + c (conv_stem.hip)
+    //   fp32 panel   [Cout][Kpad], k = tap * cin_p + c
+    //   split stem   [Cout][32] f16 hi / lo planes, k = (ky*3+kx)*3 + c, k >= 27 zero
+    //   split planes K-chunk major, [chunk][Npad][32]: the rows of one stage are contiguous.  K order of the split kernels:
+    //                k = ((c/32)*k*k + tap)*32 + c%32 (channel chunk outer, tap inner);
+    //                narrow layers (conv_c16_f16s3.hip): tap-major over the 16 channels, k = tap * 16 + c, so chunk j holds
+    //                taps 2j and 2j + 1 (the unused half of the last chunk of an odd tap count stays zero in both planes)
+    const int taps = k * k;
+    auto dst = [&](int o, int c, int tap) -> int64_t {
+        if (pc.stem) return pc.split ? o * 32 + tap * 3 + c : (int64_t)(tap * 3 + c) * C + o;
+        if (!pc.split) return (int64_t)o * pc.Kpad + tap * pc.cin_p + c;
+        return pc.narrow ? ((int64_t)(tap / 2) * pc.Npad + o) * 32 + (tap % 2) * 16 + c
+                         : ((int64_t)((c / 32) * taps + tap) * pc.Npad + o) * 32 + (c % 32);
+    };
+    float* wp = blk;
+    uint16_t* wh = reinterpret_cast<uint16_t*>(blk);
+    uint16_t* wl = reinterpret_cast<uint16_t*>(blk + (pc.wl_off - pc.w_off));
+    float* inv = blk + (pc.s_off - pc.w_off);
+    if (pc.split && !pc.stem) for (int o = 0; o < pc.Npad; ++o) inv[o] = 1.0f / ACT_SCALE_F16S3;      // padding channels
+    const int64_t per_o = (int64_t)cin * taps;
+    for (int o = 0; o < C; ++o) {
+        const float* po = p + o * per_o;
+        PreScale s;
+        if (pc.split) { s = channel_prescale(po, per_o, scale[o]); inv[o] = s.inv; }
+        for (int c = 0; c < cin; ++c)
+            for (int tap = 0; tap < taps; ++tap) {
+                const float v = (float)((double)po[(int64_t)c * taps + tap] * scale[o]);      // the fp32 folded weight
+                const int64_t idx = dst(o, c, tap);
+                if (!pc.split) { wp[idx] = v; continue; }
+                const float vs = (float)((double)v * s.ps);                                   // exact (power of two)
+                split_hi_lo(vs, wh[idx], wl[idx]);
+            }
+    }
+}
+
+// layout_weights gives every conv one contiguous run of the image that starts at its w_off
+int64_t Plan::conv_block_floats(size_t slot) const {
+    return (slot + 1 < convs.size() ? convs[slot + 1].w_off : packed_floats) - convs[slot].w_off;
+}
+
 // The image rtod_plan_load_weights uploads, for the plan's current options and precision.  Host only: no HIP call, no device state.
 int Plan::pack_weights(const float* w, size_t n, std::vector<float>& packed) const {
     if (!w) { set_error("load_weights: null pointer"); return RTOD_E_ARG; }
@@ -65,68 +135,37 @@ int Plan::pack_weights(const float* w, size_t n, std::vector<float>& packed) con
         return RTOD_E_SIZE;
     }
     packed.assign((size_t)packed_floats, 0.0f);
-    std::vector<double> scale;
-    for (const auto& pc : convs) {
-        const Layer& L = layers[pc.layer];
-        const float* p = w + L.w_off;
-        const int C = L.cout, cin = L.cin, k = L.size;
-        scale.assign(C, 1.0);
-        float* bias = packed.data() + pc.b_off;
-        if (L.bn && opt_bn_batch_stats) {
-            // batch-statistics mode: the conv stays unfolded (no bias), beta / gamma go to the normalisation kernel; the
-            // stream's running mean / variance are not used (the reference only updates them as a side effect)
-            float* bnp = packed.data() + pc.bn_off;
-            for (int o = 0; o < C; ++o) { bias[o] = 0.f; bnp[o] = p[o]; bnp[pc.Npad + o] = p[C + o]; }
-            p += 4 * C;
-        } else if (L.bn) {
-            const float *beta = p, *gamma = p + C, *mean = p + 2 * C, *var = p + 3 * C;
-            for (int o = 0; o < C; ++o) {
-                // eval BatchNorm (x - mean) / sqrt(var + 1e-5) * gamma + beta folded into the conv
-                const double s = (double)gamma[o] / std::sqrt((double)var[o] + 1e-5);
-                scale[o] = s;
-                bias[o] = (float)((double)beta[o] - (double)mean[o] * s);
-            }
-            p += 4 * C;
-        } else {
-            for (int o = 0; o < C; ++o) bias[o] = p[o];
-            p += C;
-        }
-        // One walk over the OIHW block.  Every weight is folded to fp32 first ((double) w * scale, rounded once); the four layouts
-        // differ in where it lands alone (element index: floats of the fp32 layouts, halves of the split planes):
-        //   fp32 stem    [28][Cout], k = (ky*3+kx)*3 + c (conv_stem.hip)
-        //   fp32 panel   [Cout][Kpad], k = tap * cin_p + c
-        //   split stem   [Cout][32] f16 hi / lo planes, k = (ky*3+kx)*3 + c, k >= 27 zero
-        //   split planes K-chunk major, [chunk][Npad][32]: the rows of one stage are contiguous.  K order of the split kernels:
-        //                k = ((c/32)*k*k + tap)*32 + c%32 (channel chunk outer, tap inner);
-        //                narrow layers (conv_c16_f16s3.hip): tap-major over the 16 channels, k = tap * 16 + c, so chunk j holds
-        //                taps 2j and 2j + 1 (the unused half of the last chunk of an odd tap count stays zero in both planes)
-        const int taps = k * k;
-        auto dst = [&](int o, int c, int tap) -> int64_t {
-            if (pc.stem) return pc.split ? o * 32 + tap * 3 + c : (int64_t)(tap * 3 + c) * C + o;
-            if (!pc.split) return (int64_t)o * pc.Kpad + tap * pc.cin_p + c;
-            return pc.narrow ? ((int64_t)(tap / 2) * pc.Npad + o) * 32 + (tap % 2) * 16 + c
-                             : ((int64_t)((c / 32) * taps + tap) * pc.Npad + o) * 32 + (c % 32);
-        };
-        float* wp = packed.data() + pc.w_off;
-        uint16_t* wh = reinterpret_cast<uint16_t*>(packed.data() + pc.w_off);
-        uint16_t* wl = reinterpret_cast<uint16_t*>(packed.data() + pc.wl_off);
-        float* inv = packed.data() + pc.s_off;
-        if (pc.split && !pc.stem) for (int o = 0; o < pc.Npad; ++o) inv[o] = 1.0f / ACT_SCALE_F16S3;      // padding channels
-        const int64_t per_o = (int64_t)cin * taps;
-        for (int o = 0; o < C; ++o) {
-            const float* po = p + o * per_o;
-            PreScale s;
-            if (pc.split) { s = channel_prescale(po, per_o, scale[o]); inv[o] = s.inv; }
-            for (int c = 0; c < cin; ++c)
-                for (int tap = 0; tap < taps; ++tap) {
-                    const float v = (float)((double)po[(int64_t)c * taps + tap] * scale[o]);      // the fp32 folded weight
-                    const int64_t idx = dst(o, c, tap);
-                    if (!pc.split) { wp[idx] = v; continue; }
-                    const float vs = (float)((double)v * s.ps);                                   // exact (power of two)
-                    split_hi_lo(vs, wh[idx], wl[idx]);
-                }
-        }
+    for (const auto& pc : convs) pack_conv(pc, w + layers[pc.layer].w_off, packed.data() + pc.w_off);
+    return RTOD_OK;
+}
+
+// One conv without BatchNorm re-packed from (weight OIHW, bias) and its block alone copied to the device: the bits a full
+// load_weights of the edited stream gives, since both go through pack_conv.  Synchronises the device (a forward in flight may
+// still read the old block).
+int Plan::update_conv(int layer, const float* weight_oihw, const float* bias) {
+    if (!weight_oihw || !bias) { set_error("update_conv: null pointer"); return RTOD_E_ARG; }
+    if (layer < 0 || layer >= (int)layers.size() || layers[layer].type != LT_CONV) { set_error("update_conv: layer %d is not a convolution", layer); return RTOD_E_ARG; }
+    const Layer& L = layers[layer];
+    if (L.bn) { set_error("update_conv: layer %d has BatchNorm (only convs without it can be replaced)", layer); return RTOD_E_ARG; }
+    size_t slot = convs.size();
+    for (const auto& l : launches) {
+        if ((l.kind != LK_CONV && l.kind != LK_STEM) || l.layer != layer || l.conv_slot < 0) continue;
+        if (l.pw_guest >= 0 || l.pw_host >= 0) { set_error("update_conv: layer %d is part of a fused pointwise pair", layer); return RTOD_E_ARG; }
+        slot = (size_t)l.conv_slot;
     }
+    if (slot >= convs.size()) { set_error("update_conv: layer %d has no packed weights", layer); return RTOD_E_ARG; }
+    if (!weights_loaded || !d_weights) { set_error("update_conv: call rtod_plan_load_weights first"); return RTOD_E_STATE; }
+    const PackedConv& pc = convs[slot];
+    const int64_t nw = (int64_t)L.cout * L.cin * L.size * L.size;
+    std::vector<float> stream((size_t)(L.cout + nw));
+    memcpy(stream.data(), bias, sizeof(float) * (size_t)L.cout);
+    memcpy(stream.data() + L.cout, weight_oihw, sizeof(float) * (size_t)nw);
+    std::vector<float> blk((size_t)conv_block_floats(slot), 0.0f);
+    pack_conv(pc, stream.data(), blk.data());
+    RTOD_HIP(hipSetDevice(device));
+    RTOD_HIP(hipDeviceSynchronize());
+    RTOD_HIP(hipMemcpy(d_weights + pc.w_off, blk.data(), sizeof(float) * blk.size(), hipMemcpyHostToDevice));
+    RTOD_HIP(hipDeviceSynchronize());
     return RTOD_OK;
 }
 

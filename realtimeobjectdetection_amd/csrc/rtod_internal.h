@@ -358,5 +358,14 @@ int launch_yolo_loss(const float* pred, int batch, int n_rows, int num_class, co
                      float* target, uint8_t* mask, int32_t* n_obj, int32_t* status, void* ws, size_t ws_bytes, hipStream_t s);
 int launch_darknet_loss_dense(const float* pred, const float* target, const uint8_t* mask, int64_t rows, int attrs, double* loss,
                               void* ws, size_t ws_bytes, hipStream_t s);
+// ... its gradient with respect to the raw head maps (loss_grad.hip; same workspace)
+int launch_yolo_loss_grad(const float* pred, int batch, int n_rows, int num_class, const rtod_yolo_head* heads, int n_heads,
+                          const float* boxes, const int32_t* box_off, float min_box_size, float* grad_raw, float* grad_pred, double* loss,
+                          int32_t* n_obj, int32_t* status, void* ws, size_t ws_bytes, hipStream_t s);
+// weight / bias gradient of a 1x1 convolution on the exact-fp32 MFMA, K slices added in order (wgrad.hip)
+int64_t wgrad_slice_len(int64_t K);
+size_t wgrad_workspace_bytes(int batch, int cout, int cin, int pixels);
+int launch_conv1x1_wgrad(const float* dz, const float* x, int batch, int cout, int cin, int pixels, float* dw, float* db,
+                         void* ws, size_t ws_bytes, hipStream_t s);
 
 }  // namespace rtod

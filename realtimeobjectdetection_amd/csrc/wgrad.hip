@@ -1,0 +1,163 @@
+// Weight and bias gradient of a 1x1 convolution on the exact-fp32 MFMA (v_mfma_f32_32x32x2_f32), gfx950:
+//   dW[o][c] = sum_{b,p} dz[b,o,p] * x[b,c,p]        db[o] = sum_{b,p} dz[b,o,p]
+// dz [batch, cout, pixels] and x [batch, cin, pixels] are dense NCHW maps (the gradient of rtod_yolo_loss_grad for one head and
+// rtod_plan_read_layer of the head conv's input).  An NT GEMM: both operands are contiguous along the summed index
+// k = b * pixels + p inside an image, K = batch * pixels.
+//
+// GEMM view:  D[m][n] = sum_k A[m][k] * B[n][k],  m = o (MFMA rows), n = c (MFMA columns, on the lane: coalesced dW stores).
+// Workgroup: 4 waves, a 64 x 64 tile of dW, one 32 x 32 accumulator per wave.  K-chunks of 32 are staged through LDS as
+// [row][32 + 4] floats (conv_igemm_f32.hip's layout: one ds_read_b128 feeds four MFMAs; inside an 8-wide k group the lane halves
+// take k = {0..3} and {4..7}), and the next chunk's global loads are in flight during the MFMAs.  Global loads are 4-byte loads
+// with k on the lane: a row of an image starts on a 4-byte boundary only (pixels = 169), consecutive lanes read consecutive
+// addresses inside an image, and a chunk may cross an image boundary.
+// Rows past cout / cin and k past the slice are staged as zeros, which leave an fmaf chain unchanged.
+//
+// K slices.  The tile grid is small (4 x 16 tiles at most), so K is split into S contiguous slices, one workgroup per (tile,
+// slice); slice sums go to the workspace and wgrad_reduce_kernel adds them in ascending slice order.  No floating-point atomics:
+// the result is bit-identical from call to call.  The slice rule sees K alone (wgrad_slice_len, documented in rtod.h):
+//   units = ceil(K / 8);  slice length = 8 * ceil(units / 16);  S = ceil(K / slice length)  (<= 16)
+// Every accumulator is an fmaf chain over its slice in a fixed permutation of k; db is a plain fp32 sum over the slice in
+// ascending k, kept by the workgroups of the first column of tiles.
+#include "rtod_internal.h"
+
+namespace rtod {
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+constexpr int WG_BK = 32;               // k per LDS stage
+constexpr int WG_LD = WG_BK + 4;        // padded row (floats)
+constexpr int WG_T = 64;                // tile edge (rows of dz and rows of x per workgroup)
+constexpr int WG_MAX_SLICES = 16;
+
+int64_t wgrad_slice_len(int64_t K) {
+    const int64_t units = (K + 7) / 8;
+    return 8 * ((units + WG_MAX_SLICES - 1) / WG_MAX_SLICES);
+}
+static int64_t wgrad_slices(int64_t K) { const int64_t L = wgrad_slice_len(K); return (K + L - 1) / L; }
+
+size_t wgrad_workspace_bytes(int batch, int cout, int cin, int pixels) {
+    const int64_t S = wgrad_slices((int64_t)batch * pixels);
+    return sizeof(float) * (size_t)S * ((size_t)cout * cin + (size_t)cout);
+}
+
+// part: [S][cout][cin] slice sums of dW, then [S][cout] slice sums of db
+__global__ __launch_bounds__(256)
+void wgrad_slice_kernel(const float* __restrict__ dz, const float* __restrict__ x, int cout, int cin, int pixels, int K, int slice_len,
+                        int grid_m, int grid_n, float* __restrict__ part, float* __restrict__ part_db) {
+    __shared__ __attribute__((aligned(16))) float smem[2 * WG_T * WG_LD];
+    float* sA = smem;
+    float* sB = smem + WG_T * WG_LD;
+    const int tiles = grid_m * grid_n;
+    const int slice = blockIdx.x / tiles;
+    const int tile = blockIdx.x - slice * tiles;
+    const int bm = tile / grid_n, bn = tile - bm * grid_n;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int kk = tid & 31, row0 = tid >> 5;                     // this thread stages k = kk of rows row0, row0 + 8, ...
+    const int k0 = slice * slice_len;
+    const int k1 = min(k0 + slice_len, K);
+
+    f32x16 acc;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) acc[e] = 0.f;
+    float db = 0.f;
+    const int wm = wave >> 1, wn = wave & 1;
+    const int lr = lane & 31, lh = lane >> 5;
+    const float* pa = sA + (wm * 32 + lr) * WG_LD + lh * 4;
+    const float* pb = sB + (wn * 32 + lr) * WG_LD + lh * 4;
+
+    // one register stage, as in conv_igemm_f32.hip: chunk kc + 1 is fetched while chunk kc computes
+    float ra[WG_T / 8], rb[WG_T / 8];
+    auto gload = [&](int kc) {
+        const int k = kc + kk;
+        const bool kok = k < k1;
+        const int b = kok ? k / pixels : 0;
+        const int p = kok ? k - b * pixels : 0;
+#pragma unroll
+        for (int i = 0; i < WG_T / 8; ++i) {
+            const int o = bm * WG_T + row0 + i * 8, c = bn * WG_T + row0 + i * 8;
+            ra[i] = (kok && o < cout) ? dz[((int64_t)b * cout + o) * pixels + p] : 0.f;
+            rb[i] = (kok && c < cin) ? x[((int64_t)b * cin + c) * pixels + p] : 0.f;
+        }
+    };
+    gload(k0);
+    for (int kc = k0; kc < k1; kc += WG_BK) {
+        __syncthreads();                                          // the previous chunk's LDS reads are done
+#pragma unroll
+        for (int i = 0; i < WG_T / 8; ++i) {
+            sA[(row0 + i * 8) * WG_LD + kk] = ra[i];
+            sB[(row0 + i * 8) * WG_LD + kk] = rb[i];
+        }
+        __syncthreads();
+        if (kc + WG_BK < k1) gload(kc + WG_BK);                   // in flight while the MFMAs below run
+#pragma unroll
+        for (int q = 0; q < WG_BK / 8; ++q) {
+            const f32x4 fa = *reinterpret_cast<const f32x4*>(pa + q * 8);
+            const f32x4 fb = *reinterpret_cast<const f32x4*>(pb + q * 8);
+#pragma unroll
+            for (int s = 0; s < 4; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[s], fb[s], acc, 0, 0, 0);
+        }
+        if (part_db && bn == 0 && tid < WG_T) {                   // uniform per wave: wave 0 alone
+#pragma clang fp contract(off)
+            const float* r = sA + tid * WG_LD;
+            for (int j = 0; j < WG_BK; ++j) db = db + r[j];
+        }
+    }
+    // D: column = lane & 31 (c), row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5) (o)
+    const int c = bn * WG_T + wn * 32 + lr;
+    float* out = part + (int64_t)slice * cout * cin;
+    if (c < cin) {
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+            const int o = bm * WG_T + wm * 32 + (e & 3) + 8 * (e >> 2) + 4 * lh;
+            if (o < cout) out[(int64_t)o * cin + c] = acc[e];
+        }
+    }
+    if (part_db && bn == 0 && tid < WG_T) {
+        const int o = bm * WG_T + tid;
+        if (o < cout) part_db[(int64_t)slice * cout + o] = db;
+    }
+}
+
+// the slice sums added in ascending slice order: one thread per element of dW, then of db
+__global__ __launch_bounds__(256)
+void wgrad_reduce_kernel(const float* __restrict__ part, const float* __restrict__ part_db, int64_t n_dw, int cout, int slices,
+                         float* __restrict__ dw, float* __restrict__ db) {
+#pragma clang fp contract(off)
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n_dw) {
+        float v = part[i];
+        for (int s = 1; s < slices; ++s) v = v + part[(int64_t)s * n_dw + i];
+        dw[i] = v;
+    } else if (db && i < n_dw + cout) {
+        const int64_t o = i - n_dw;
+        float v = part_db[o];
+        for (int s = 1; s < slices; ++s) v = v + part_db[(int64_t)s * cout + o];
+        db[o] = v;
+    }
+}
+
+int launch_conv1x1_wgrad(const float* dz, const float* x, int batch, int cout, int cin, int pixels, float* dw, float* db,
+                         void* ws, size_t ws_bytes, hipStream_t s) {
+    if (!dz || !x || !dw || !ws) { set_error("conv1x1_wgrad: null pointer"); return RTOD_E_ARG; }
+    if (batch < 1 || cout < 1 || cin < 32 || cin % 32 || pixels < 1) {
+        set_error("conv1x1_wgrad: unsupported shape (batch=%d cout=%d cin=%d pixels=%d; cin must be a multiple of 32)", batch, cout, cin, pixels);
+        return RTOD_E_ARG;
+    }
+    const int64_t K = (int64_t)batch * pixels;
+    if (K > INT32_MAX - 64 || (int64_t)cout * cin > INT32_MAX) { set_error("conv1x1_wgrad: batch * pixels or cout * cin exceeds int32"); return RTOD_E_ARG; }
+    if (ws_bytes < wgrad_workspace_bytes(batch, cout, cin, pixels)) { set_error("conv1x1_wgrad: workspace too small"); return RTOD_E_ARG; }
+    if ((uintptr_t)ws & 15) { set_error("conv1x1_wgrad: workspace must be 16-byte aligned"); return RTOD_E_ARG; }
+    const int S = (int)wgrad_slices(K);
+    const int gm = (cout + WG_T - 1) / WG_T, gn = (cin + WG_T - 1) / WG_T;
+    if ((int64_t)gm * gn * S > INT32_MAX) { set_error("conv1x1_wgrad: grid too large"); return RTOD_E_ARG; }
+    float* part = (float*)ws;
+    float* part_db = part + (int64_t)S * cout * cin;
+    hipLaunchKernelGGL(wgrad_slice_kernel, dim3((unsigned)(gm * gn * S)), dim3(256), 0, s, dz, x, cout, cin, pixels, (int)K, (int)wgrad_slice_len(K),
+                       gm, gn, part, db ? part_db : (float*)nullptr);
+    const int64_t n = (int64_t)cout * cin + (db ? cout : 0);
+    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, part, part_db, (int64_t)cout * cin, cout, S, dw, db);
+    return hip_fail(hipGetLastError(), "conv1x1_wgrad launch");
+}
+
+}  // namespace rtod

@@ -246,6 +246,43 @@ class Darknet(nn.Module):
         """Call after mutating parameters in place so the next forward re-packs them."""
         self._weights_version += 1
 
+    # ------------------------------------------------------------------ detection heads
+    def head_layers(self) -> list:
+        """``[(conv_layer, input_layer)]`` of the detection heads in cfg order: the conv directly in front of every [yolo] block
+        and the layer whose output it reads (what ``read_layer`` returns after a forward with options ``keep_head_inputs``)."""
+        types = [b["type"] for b in self.blocks[1:]]
+        return [(i - 1, i - 2) for i, t in enumerate(types) if t == "yolo" and i > 0 and types[i - 1] == "convolutional"]
+
+    def update_conv(self, layer: int, weight, bias) -> None:
+        """Replace the weights of one conv without BatchNorm: ``weight`` [Cout,Cin,k,k] and ``bias`` [Cout] go into the module's
+        parameters and, when a plan with current weights is loaded, into that plan through rtod_plan_update_conv, which re-packs
+        this conv alone (the bits a full re-pack gives) — the next forward does not re-pack the network.  Synchronises."""
+        conv = bn = None
+        if 0 <= int(layer) < len(self.module_list):
+            for name, sub in self.module_list[int(layer)].named_children():
+                if name.startswith("conv_"):
+                    conv = sub
+                elif name.startswith("batch_norm_"):
+                    bn = sub
+        if conv is None or bn is not None:
+            raise ValueError("Darknet.update_conv: layer %d is not a convolution without BatchNorm" % int(layer))
+        w = torch.as_tensor(weight).detach().to(torch.float32)
+        b = torch.as_tensor(bias).detach().to(torch.float32)
+        if tuple(w.shape) != tuple(conv.weight.shape) or tuple(b.shape) != tuple(conv.bias.shape):
+            raise ValueError("Darknet.update_conv: layer %d takes weight %s and bias %s, got %s and %s"
+                             % (int(layer), tuple(conv.weight.shape), tuple(conv.bias.shape), tuple(w.shape), tuple(b.shape)))
+        with torch.no_grad():
+            conv.weight.copy_(w)
+            conv.bias.copy_(b)
+        batch_bn = bool(self.training and not self.bn_running_stats_in_train)
+        current = (self._weights_version, 0 if batch_bn else self._stats_version)
+        if self._plan is not None and self._plan_weights_version == current:
+            wh = np.ascontiguousarray(w.cpu().numpy())
+            bh = np.ascontiguousarray(b.cpu().numpy())
+            with torch.cuda.device(self._plan_key[2]):
+                _ffi.check(_ffi.lib().rtod_plan_update_conv(self._plan, int(layer), wh.ctypes.data_as(C.c_void_p), bh.ctypes.data_as(C.c_void_p)))
+        # the plan's weight version stays current: parameters and plan agree again (a plan that was stale before still re-packs)
+
     # ------------------------------------------------------------------ plan
     def _destroy_plan(self):
         if self._plan is not None:

@@ -1,14 +1,19 @@
 """Host-side mirror of the loss side of the reference's trainer (``DarknetTrainer``, train.py:17-230) on librtod.so.
 
-Only the FORWARD VALUE of the loss exists here: targets from ground-truth boxes (``target_creator``) and the five-term sum of
-squares (``darknet_loss``), the last step of ``feed_forward_through_model`` (train.py:412-425).  Backward, the optimiser, epochs
-and data loaders are out of scope.  Same names and return conventions as the reference:
+The FORWARD VALUE of the loss: targets from ground-truth boxes (``target_creator``) and the five-term sum of squares
+(``darknet_loss``), the last step of ``feed_forward_through_model`` (train.py:412-425); and the first layer of its backward pass:
+the gradient with respect to the raw head maps and from it ``dW``, ``db`` of the detection-head convs (the 1x1 convs without
+BatchNorm in front of the [yolo] blocks), with a plain SGD step on them — fine-tuning the heads with the backbone frozen.  Backward
+through the trunk, BatchNorm gradients, other optimisers, epochs and data loaders are out of scope.  Same names and
+return conventions as the reference:
 
 * ``DarknetTrainer.anchor_fit(box, anchors)``, ``target_layer(bboxes, scale, anchors)``     host mirrors, train.py:167-209
 * ``DarknetTrainer.target_creator(bndbox) -> (target, mask)``                               train.py:129-149, one launch sequence
 * ``DarknetTrainer.darknet_loss(pred, target, obj_mask)`` (``criterion``)                   train.py:211-230, dense tensors
 * ``DarknetTrainer.loss_from_boxes(pred, bndbox) -> (loss, components)``                    both fused: no dense target is built
 * ``DarknetTrainer.forward_loss(frames_or_x, bndbox)``                                      forward under ``train_mode()`` + loss
+* ``DarknetTrainer.head_gradients(frames_or_x, bndbox) -> (loss, {conv_layer: (dW, db)})``  (new) what ``loss.backward()`` leaves on the heads
+* ``DarknetTrainer.head_step(frames_or_x, bndbox, lr)``                                     (new) ``w -= lr * dW``, ``b -= lr * db`` on the heads
 
 The reference's behaviour is kept as it is: only boxes whose class-0 slot is 1 and whose sides are at least
 ``min_box_size`` (24) count, ``anchor_fit`` compares a box with a square of the anchor's WIDTH, target slot 0 holds the y fraction
@@ -103,6 +108,69 @@ def yolo_loss_async(pred, bndbox, heads, num_class, min_box_size=24, dense=False
     return out
 
 
+def yolo_loss_grad_async(pred, bndbox, heads, num_class, min_box_size=24, grad_pred=False, status=None):
+    """Enqueue rtod_yolo_loss_grad for one batch; nothing synchronises.  Arguments as ``yolo_loss_async``.  Returns a dict of
+    device tensors: ``grad_raw`` a list with one ``[B, A*attrs, GH, GW]`` view per head (the gradient with respect to the raw head
+    maps, views of one buffer ``grad_raw_flat``), ``components`` float64 [6] (bit-identical to ``yolo_loss_async``), ``n_obj``,
+    ``status``, and with ``grad_pred`` the gradient with respect to ``pred`` [B,N,5+C]."""
+    _need_cuda(pred, "yolo_loss_grad")
+    attrs = 5 + int(num_class)
+    if pred.dim() != 3 or pred.size(2) != attrs or not pred.is_contiguous():
+        raise ValueError("yolo_loss_grad: expected contiguous predictions [B,N,%d], got %s" % (attrs, tuple(pred.shape)))
+    B, N = pred.size(0), pred.size(1)
+    if len(bndbox) != B:
+        raise ValueError("yolo_loss_grad: %d box lists for a batch of %d" % (len(bndbox), B))
+    dev = pred.device
+    boxes, offs = pack_boxes(bndbox, attrs, dev)
+    ws, nbytes = _workspace(dev, B, N)
+    out = {"grad_raw_flat": torch.empty(B * N * attrs, dtype=torch.float32, device=dev), "components": torch.empty(6, dtype=torch.float64, device=dev),
+           "n_obj": torch.empty(B, dtype=torch.int32, device=dev), "status": status if status is not None else torch.zeros(1, dtype=torch.int32, device=dev)}
+    if grad_pred:
+        out["grad_pred"] = torch.empty((B, N, attrs), dtype=torch.float32, device=dev)
+    ptr = lambda k: C.c_void_p(out[k].data_ptr()) if k in out else None
+    with torch.cuda.device(dev):
+        _ffi.check(_ffi.lib().rtod_yolo_loss_grad(
+            C.c_void_p(pred.data_ptr()), B, N, int(num_class), make_heads(heads), len(heads), C.c_void_p(boxes.data_ptr()), C.c_void_p(offs.data_ptr()),
+            float(min_box_size), ptr("grad_raw_flat"), ptr("grad_pred"), ptr("components"), ptr("n_obj"), ptr("status"),
+            C.c_void_p(ws.data_ptr()), nbytes, _stream(dev)))
+    views, off = [], 0
+    for gh, gw, _, anchors in heads:                                  # head h at float offset B * sum of the earlier heads' A * attrs * GH * GW
+        n = B * len(anchors) * attrs * gh * gw
+        views.append(out["grad_raw_flat"][off:off + n].view(B, len(anchors) * attrs, gh, gw))
+        off += n
+    out["grad_raw"] = views
+    return out
+
+
+_wgrad_ws = {}
+
+
+def conv1x1_wgrad_async(dz, x, bias=True):
+    """Enqueue rtod_conv1x1_wgrad: ``dz`` [B,Cout,H,W] and ``x`` [B,Cin,H,W] (contiguous float32 device tensors, Cin a multiple
+    of 32) -> ``(dW [Cout,Cin,1,1], db [Cout] or None)``; nothing synchronises."""
+    _need_cuda(dz, "conv1x1_wgrad")
+    _need_cuda(x, "conv1x1_wgrad")
+    if dz.dim() != 4 or x.dim() != 4 or dz.size(0) != x.size(0) or tuple(dz.shape[2:]) != tuple(x.shape[2:]) or dz.dtype != torch.float32 or x.dtype != torch.float32:
+        raise ValueError("conv1x1_wgrad: expected float32 dz [B,Cout,H,W] and x [B,Cin,H,W], got %s and %s" % (tuple(dz.shape), tuple(x.shape)))
+    dz, x = dz.contiguous(), x.contiguous()
+    B, cout, cin, pixels = dz.size(0), dz.size(1), x.size(1), dz.size(2) * dz.size(3)
+    dev = dz.device
+    key = (dev.index, B, cout, cin, pixels)
+    ws = _wgrad_ws.get(key)
+    if ws is None:
+        nbytes = C.c_size_t()
+        _ffi.check(_ffi.lib().rtod_conv1x1_wgrad_workspace(B, cout, cin, pixels, C.byref(nbytes)))
+        if len(_wgrad_ws) > 16:
+            _wgrad_ws.clear()
+        ws = _wgrad_ws[key] = (torch.empty((nbytes.value + 7) // 8, dtype=torch.float64, device=dev), nbytes.value)
+    dw = torch.empty((cout, cin, 1, 1), dtype=torch.float32, device=dev)
+    db = torch.empty(cout, dtype=torch.float32, device=dev) if bias else None
+    with torch.cuda.device(dev):
+        _ffi.check(_ffi.lib().rtod_conv1x1_wgrad(C.c_void_p(dz.data_ptr()), C.c_void_p(x.data_ptr()), B, cout, cin, pixels, C.c_void_p(dw.data_ptr()),
+                                                 C.c_void_p(db.data_ptr()) if bias else None, C.c_void_p(ws[0].data_ptr()), ws[1], _stream(dev)))
+    return dw, db
+
+
 def model_heads(model, height=None, width=None):
     """``[(grid_h, grid_w, stride, anchors)]`` of a Darknet's [yolo] layers in cfg order, and its number of classes."""
     h = int(model.net_info["height"]) if height is None else int(height)
@@ -144,6 +212,7 @@ class DarknetTrainer:
         self.history = dict()
         self.status = None
         self.last_components = None
+        self._head_masters = None          # head_step: {conv_layer: [weight, bias]} float32 device masters of the head convs
 
     # ------------------------------------------------------------------ host mirrors (small and exact)
     @staticmethod
@@ -235,6 +304,10 @@ class DarknetTrainer:
     def forward_loss(self, frames_or_x, bndbox):
         """Forward under ``train_mode()`` (float32 ``[B,3,H,W]`` inputs, or uint8 ``[B,H,W,3]`` RGB frames letterboxed on the
         device), then ``loss_from_boxes``; returns the loss."""
+        return self.loss_from_boxes(self._forward_train(frames_or_x), bndbox)[0]
+
+    # ------------------------------------------------------------------ gradients of the detection-head convs
+    def _forward_train(self, frames_or_x):
         x = torch.as_tensor(frames_or_x)
         if x.dtype == torch.uint8:
             h = int(self.darknet.net_info["height"])
@@ -243,5 +316,45 @@ class DarknetTrainer:
         elif not x.is_cuda:
             x = x.cuda()
         with torch.no_grad(), self.darknet.train_mode():
-            pred = self.darknet(x)
-        return self.loss_from_boxes(pred, bndbox)[0]
+            return self.darknet(x)
+
+    def head_gradients(self, frames_or_x, bndbox):
+        """``(loss, {conv_layer: (dW [Cout,Cin,1,1], db [Cout])})``: what ``loss.backward()`` of the reference leaves on the
+        detection-head convs.  Forward under ``train_mode()`` (inputs as ``forward_loss``), rtod_yolo_loss_grad, then per head
+        ``read_layer`` of the conv's input and rtod_conv1x1_wgrad; all on the current stream, nothing synchronises.  The model's
+        ``options`` must hold ``keep_head_inputs`` (the head inputs are otherwise overwritten before the forward ends)."""
+        model = self.darknet
+        if not int(getattr(model, "options", {}).get("keep_head_inputs", 0)):
+            raise RuntimeError("DarknetTrainer.head_gradients: set model.options['keep_head_inputs'] = 1 before the first forward; "
+                               "without it the activations that feed the head convs do not survive the forward")
+        pred = self._forward_train(frames_or_x)
+        out = yolo_loss_grad_async(pred, bndbox, self.heads, self.num_classes, self.min_box_size, status=self._status(pred.device))
+        self.last_components = out["components"]
+        layers = model.head_layers()
+        if len(layers) != len(self.heads):
+            raise RuntimeError("DarknetTrainer.head_gradients: %d [yolo] layers but %d of them follow a convolution" % (len(self.heads), len(layers)))
+        grads = {}
+        for (conv_layer, input_layer), dz in zip(layers, out["grad_raw"]):
+            if input_layer < 0:
+                raise RuntimeError("DarknetTrainer.head_gradients: head conv %d reads the network input" % conv_layer)
+            grads[conv_layer] = conv1x1_wgrad_async(dz, model.read_layer(input_layer, pred.size(0)))
+        return out["components"][0].float(), grads
+
+    def head_step(self, frames_or_x, bndbox, lr):
+        """One plain SGD step on the detection-head convs, ``w -= lr * dW``, ``b -= lr * db``, on float32 device masters the
+        trainer keeps for them (taken from the model's parameters at the first call), followed by ``Darknet.update_conv``, which
+        re-packs those convs alone.  SYNCHRONISES the device (the updated weights pass through the host).  Returns the loss
+        from before the step (0-dim float32 device tensor)."""
+        loss, grads = self.head_gradients(frames_or_x, bndbox)
+        model = self.darknet
+        if self._head_masters is None:
+            self._head_masters = {}
+            for layer in grads:
+                conv = next(sub for name, sub in model.module_list[layer].named_children() if name.startswith("conv_"))
+                self._head_masters[layer] = [conv.weight.detach().to(loss.device, torch.float32).clone(), conv.bias.detach().to(loss.device, torch.float32).clone()]
+        for layer, (dw, db) in grads.items():
+            w, b = self._head_masters[layer]
+            w.sub_(dw * float(lr))
+            b.sub_(db * float(lr))
+            model.update_conv(layer, w, b)
+        return loss
