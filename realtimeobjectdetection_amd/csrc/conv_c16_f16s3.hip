@@ -1,12 +1,12 @@
 // Implicit-GEMM convolution for layers that read 16 input channels (option "narrow_cin": YOLOv3-tiny's layer 2, any cfg that
 // opens with a 16-filter stem), split-precision f16 MFMA (v_mfma_f32_16x16x32_f16), gfx950.
 //
-// Same data formats, LDS panels, MFMA sequence and epilogues as conv_igemm_f16s3.hip; what differs is the K order and with it
+// Same data formats and epilogues as conv_igemm_f16s3.hip, and the same main loop (conv_f16s3_staged.h); what differs is the K order and with it
 // the A-tile addressing.  A 32-wide K-chunk cannot be one tap of 32 channels here, so it is TWO taps of 16:
 //
 //   k = tap * 16 + c,  tap = ky * kw + kx          K-chunk j = taps 2j and 2j + 1;  K = 16 kh kw, Kpad = 160 (3x3) / 32 (1x1)
 //
-// (the packed weights of a narrow layer are laid out in this order: plan.cpp, load_weights).  A 64-byte panel row is four
+// (the packed weights of a narrow layer are laid out in this order: plan_weights.cpp, pack_conv).  A 64-byte panel row is four
 // 16-byte chunks; the thread that stages chunk c16 of a row loads channels 8 (c16 & 1) ... + 7 of tap 2j + (c16 >> 1).  The tap
 // and the padding predicate are therefore per LANE, not per wave: a row's two taps may straddle an image border (one in range,
 // one padding), and the second tap of the last chunk of an odd kh kw does not exist.  Both are sent out of range (the buffer load
@@ -14,15 +14,10 @@
 // plane, and 0 * inf would be NaN.
 // These layers have K <= 160 and few output channels: they are bandwidth- and launch-bound, so the tiles are few and simple
 // (no LDS-DMA, no hosted pointwise conv).  Every tile sums in the same order: results are bit-identical across tiles.
-#include "conv_f16s3_common.h"
+#include "conv_f16s3_staged.h"
 #include <cstdio>
 
 namespace rtod {
-
-template <int ASL, int BSL>
-struct C16StageRegs {
-    u32x4 ah[ASL], al[ASL], bh[BSL], bl[BSL];
-};
 
 // BM x BN workgroup tile, NWM x NWN waves of (BM/NWM) x (BN/NWN); EPI | EPI_F16: plain-f16 instance (hi planes only).
 // EPI_SPLIT | EPI_RAW: raw-sum instance (plan option bn_split_narrow): the f16s3 main loop as it stands, the shared epilogue's RAW
@@ -31,18 +26,9 @@ template <int BM, int BN, int NWM, int NWN, int MINW, int EPI>
 __global__ __launch_bounds__(NWM * NWN * 64, MINW)
 void conv_c16_f16s3_kernel(const ConvArgs a, const int grid_m, const int grid_n) {
     constexpr bool F16 = epi_f16(EPI);
-    constexpr int WM = BM / NWM, WN = BN / NWN;
-    constexpr int NT = NWM * NWN * 64;
-    static_assert(WM % 16 == 0 && WN % 16 == 0 && BM % NWM == 0 && BN % NWN == 0, "wave tile");
-    constexpr int TM = WM / 16, TN = WN / 16;
-    constexpr int RPP = NT / 4;                    // rows per pass: 4 x 16-B chunks per 64-B row
-    constexpr int A_SLOTS = (BM + RPP - 1) / RPP, B_SLOTS = (BN + RPP - 1) / RPP;
-    static_assert(RPP % 16 == 0, "predication per 16-row wave slice; swizzle period 8");
-    static_assert(A_SLOTS >= 1 && A_SLOTS <= 2 && B_SLOTS == 1, "stage shape (vmcnt literals below)");
-    constexpr int PANEL_A = BM * 64, PANEL_B = BN * 64;        // bytes
-    constexpr int STAGE = (F16 ? 1 : 2) * (PANEL_A + PANEL_B);     // [A hi][A lo][B hi][B lo], f16: [A hi][B hi]
-    constexpr int PANEL_B0 = (F16 ? 1 : 2) * PANEL_A;                  // offset of the B hi panel
-    constexpr int SMEM = 2 * STAGE > WM * BN * 4 ? 2 * STAGE : WM * BN * 4;   // the epilogue's transpose tile: one WM-row pass of BN fp32
+    using Tile = StagedTile<BM, BN, NWM, NWN, F16>;
+    constexpr int WM = Tile::WM, WN = Tile::WN, NT = Tile::NT, RPP = Tile::RPP, A_SLOTS = Tile::A_SLOTS, SMEM = Tile::SMEM;
+    static_assert(Tile::B_SLOTS == 1, "gload below loads one B row per thread");
 
     __shared__ __attribute__((aligned(16))) unsigned char smem[SMEM];
 
@@ -89,8 +75,7 @@ void conv_c16_f16s3_kernel(const ConvArgs a, const int grid_m, const int grid_n)
     if (ld_kx >= a.kw) { ld_kx -= a.kw; ++ld_ky; }               // kw == 1
     const int nk = a.Kpad / HBK;
 
-    C16StageRegs<A_SLOTS, 1> S0, S1;
-    auto gload = [&](C16StageRegs<A_SLOTS, 1>& S) {
+    auto gload = [&](typename Tile::Regs& S) {
         // chunks past the end of K (issued unconditionally: the loop stays branch-free and the vmcnt bookkeeping exact) and
         // taps past the last one (ld_ky >= kh) read out of range -> zeros
         const bool live = ld_kc < nk;
@@ -112,107 +97,16 @@ void conv_c16_f16s3_kernel(const ConvArgs a, const int grid_m, const int grid_n)
         if (ld_kx >= a.kw) { ld_kx -= a.kw; ++ld_ky; }
         if (ld_kx >= a.kw) { ld_kx -= a.kw; ++ld_ky; }
     };
-    // wait until at most one stage set's loads (the younger set) are outstanding: the older set S has landed.  Every register
-    // of S is an in/out operand so no use can be scheduled above the wait.
-    auto wait_stage = [&](C16StageRegs<A_SLOTS, 1>& S) {
-        if constexpr (F16 && A_SLOTS == 2)
-            asm volatile("s_waitcnt vmcnt(3)" : "+v"(S.ah[0]), "+v"(S.ah[1]), "+v"(S.bh[0]) :: "memory");
-        else if constexpr (F16)
-            asm volatile("s_waitcnt vmcnt(2)" : "+v"(S.ah[0]), "+v"(S.bh[0]) :: "memory");
-        else if constexpr (A_SLOTS == 2)
-            asm volatile("s_waitcnt vmcnt(6)" : "+v"(S.ah[0]), "+v"(S.al[0]), "+v"(S.ah[1]), "+v"(S.al[1]),
-                         "+v"(S.bh[0]), "+v"(S.bl[0]) :: "memory");
-        else
-            asm volatile("s_waitcnt vmcnt(4)" : "+v"(S.ah[0]), "+v"(S.al[0]), "+v"(S.bh[0]), "+v"(S.bl[0]) :: "memory");
-        __builtin_amdgcn_sched_barrier(0);
-    };
-    // LDS image: panel row r, 16-B chunk c at byte r*64 + ((c ^ ((r>>1)&3)) << 4)
-    const int wr_swz = (c16 ^ ((row0 >> 1) & 3)) << 4;           // RPP % 8 == 0 -> same swizzle for every slot
-    auto lds_write = [&](const C16StageRegs<A_SLOTS, 1>& S, int buf) {
-        unsigned char* st = smem + buf * STAGE;
-#pragma unroll
-        for (int i = 0; i < A_SLOTS; ++i) {
-            const int o = (row0 + i * RPP) * 64 + wr_swz;
-            if ((i + 1) * RPP <= BM || row0 + i * RPP < BM) {
-                *reinterpret_cast<u32x4*>(st + o) = S.ah[i];
-                if constexpr (!F16) *reinterpret_cast<u32x4*>(st + PANEL_A + o) = S.al[i];
-            }
-        }
-        if (RPP <= BN || row0 < BN) {
-            const int o = row0 * 64 + wr_swz;
-            *reinterpret_cast<u32x4*>(st + PANEL_B0 + o) = S.bh[0];
-            if constexpr (!F16) *reinterpret_cast<u32x4*>(st + PANEL_B0 + PANEL_B + o) = S.bl[0];
-        }
-    };
 
-    f32x4 acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) acc[i][j][e] = 0.f;
-
-    const int wave = tid >> 6, lane = tid & 63;
-    const int wm = wave / NWN, wn = wave - wm * NWN;
-    const int lr = lane & 15, lh = lane >> 4;
-    const int co = (lh ^ ((lr >> 1) & 3)) << 4;                  // WM, WN % 16 == 0: the row's swizzle is the lane's
-    const int a_row = (wm * WM + lr) * 64 + co, b_row = PANEL_B0 + (wn * WN + lr) * 64 + co;
-
-    // the generic MFMA step over the staged panels: three products for f16s3, one for plain f16, fp32 accumulate
-    auto compute = [&](int buf) {
-        const unsigned char* sa = smem + buf * STAGE + a_row;
-        const unsigned char* sb = smem + buf * STAGE + b_row;
-        f16x8 ah[TM], al[TM], bh[TN], bl[TN];
-#pragma unroll
-        for (int i = 0; i < TM; ++i) {
-            ah[i] = *reinterpret_cast<const f16x8*>(sa + i * 16 * 64);
-            if constexpr (!F16) al[i] = *reinterpret_cast<const f16x8*>(sa + PANEL_A + i * 16 * 64);
-        }
-#pragma unroll
-        for (int j = 0; j < TN; ++j) {
-            bh[j] = *reinterpret_cast<const f16x8*>(sb + j * 16 * 64);
-            if constexpr (!F16) bl[j] = *reinterpret_cast<const f16x8*>(sb + PANEL_B + j * 16 * 64);
-        }
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int i = 0; i < TM; ++i) {
-                if constexpr (F16) { acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[i], bh[j], acc[i][j], 0, 0, 0); continue; }
-                acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[i], bh[j], acc[i][j], 0, 0, 0);
-                acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[i], bl[j], acc[i][j], 0, 0, 0);
-                acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[i], bh[j], acc[i][j], 0, 0, 0);
-            }
-    };
-
-    // Two register stage sets keep two K-chunks of loads in flight, LDS is double-buffered, one barrier per K-chunk (the schedule
-    // of conv_igemm_f16s3.hip).  vmcnt bookkeeping: loads retire in issue order; at every wait the older stage set's loads are
-    // followed by exactly one younger set's.  Chunks >= nk are zero chunks; an odd nk costs one of them in MFMAs.
-    gload(S0);
-    gload(S1);
-    wait_stage(S0);
-    lds_write(S0, 0);
-    gload(S0);
-    __syncthreads();
-    for (int t = 0; t < nk; t += 2) {
-        wait_stage(S1);
-        lds_write(S1, 1);                             // chunk t+1
-        gload(S1);                                    // chunk t+3
-        __builtin_amdgcn_sched_barrier(0);
-        compute(0);                                   // chunk t
-        __syncthreads();
-        wait_stage(S0);
-        lds_write(S0, 0);                             // chunk t+2
-        gload(S0);                                    // chunk t+4
-        __builtin_amdgcn_sched_barrier(0);
-        compute(1);                                   // chunk t+1
-        __syncthreads();
+    f32x4 acc[Tile::TM][Tile::TN];
+    Tile::zero(acc);
+    // the shared pipeline over the whole K sum; in this family the A fragments are read with the B fragments, after the staging
+    constexpr bool A_AHEAD = false;
+#include "conv_f16s3_staged_defs.inc"
+    {
+        const int kc0 = 0, kc1 = nk;
+#include "conv_f16s3_staged_run.inc"
     }
-    // drain the trailing zero-chunk loads; wait_stage names every register of a set as in/out, so both sets stay allocated until
-    // the loads have landed (conv_f16s3_common.h, register ties)
-    vmcnt<0>();
-    wait_stage(S0);
-    wait_stage(S1);
 
     conv_f16s3_epilogue<BM, BN, WM, WN, NT, epi_kind(EPI), SMEM, 1, false, F16, epi_raw(EPI)>(a, acc, smem, bm, bn, tid, wm, wn, lr, lh, M);
 }

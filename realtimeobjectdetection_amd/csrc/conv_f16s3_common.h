@@ -246,7 +246,7 @@ __device__ __forceinline__ void conv_f16s3_epilogue_regs(const ConvArgs& a, f32x
                 const float s = e < 4 ? acc[i][2 * P][e] : acc[i][2 * P + 1][e - 4];
                 // (acc*inv + bias)*8 == acc*(8 inv) + 8 bias exactly (power of two)
                 float v = s * ((e < 4 ? iv0[e] : iv1[e - 4]) * SPLIT_SCALE) + (e < 4 ? bs0[e] : bs1[e - 4]) * SPLIT_SCALE;
-                if (a.leaky) v = v > 0.f ? v : v * 0.1f;              // linear / leaky only: SiLU layers run on the LDS-transposed epilogue (plan.cpp)
+                if (a.leaky) v = v > 0.f ? v : v * 0.1f;              // linear / leaky only: SiLU layers run on the LDS-transposed epilogue (plan_tiles.cpp)
                 if constexpr (RES) v += (float)rq_h[i][e] + (float)rq_l[i][e];
                 _Float16 h, l;
                 split_f16(v, h, l, amax);

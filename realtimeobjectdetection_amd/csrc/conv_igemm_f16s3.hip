@@ -17,15 +17,13 @@
 // in the epilogue through inv_scale[n].
 //
 // Main loop: BMxBNx32 per stage = one k32 step of 16x16x32 MFMAs (the shape the chip clocks highest on, and
-// whose 16-row granularity allows 48-row wave tiles: conv_band_f16s3.hip); LDS double-buffered, four
-// 64-byte-row f16 panels per stage with a 16-byte-chunk XOR swizzle (chunk ^= (row>>1)&3: conflict-free
-// ds_read_b128 for 16 rows x 4 chunks per read, tools/lds_bank_sim.py); two register stage sets keep two
-// K-chunks of global loads in flight; one barrier per K-chunk.
+// whose 16-row granularity allows 48-row wave tiles: conv_band_f16s3.hip), staged through LDS by the pipeline of
+// conv_f16s3_staged.h (shared with conv_c16_f16s3.hip and conv_ks_f16s3.hip); this file holds where a K-chunk is loaded from.
 // K order: k = ((c/32)*kh*kw + tap)*32 + c%32 (channel chunk outer, tap inner).
 // Addressing: the tap (ky,kx) and channel offset of a K-chunk are wave-uniform (Cin % 32 == 0) and
 // advanced in scalar registers; loads are raw buffer loads whose per-lane voffset is
 // pixel-origin + tap offset, forced out of range (-> zeros) for padding taps and rows >= M.
-#include "conv_f16s3_common.h"
+#include "conv_f16s3_staged.h"
 #include <cstdio>
 #include <cstdlib>
 
@@ -40,11 +38,6 @@ __device__ unsigned long long g_igemm_stamps[GSTAMP_BLOCKS * GSTAMP_WAVES * (GST
 #define RTOD_GSTAMP(i)
 #endif
 
-template <int ASL, int BSL>
-struct StageRegs {
-    u32x4 ah[ASL], al[ASL], bh[BSL], bl[BSL];
-};
-
 // BM x BN workgroup tile, NWM x NWN waves of (BM/NWM) x (BN/NWN), both multiples of 16.  MINW = waves per SIMD the
 // register budget must admit (2nd __launch_bounds__ argument): wave tiles of 32x64 / 48x32 or smaller are built for
 // 4 waves/SIMD — tools/ubench_tiles.hip: occupancy buys more MFMA utilisation than a larger wave tile.
@@ -54,21 +47,8 @@ template <int BM, int BN, int NWM, int NWN, int MINW, int EPI>
 __global__ __launch_bounds__(NWM * NWN * 64, MINW)
 void conv_igemm_f16s3_kernel(const ConvArgs a, const int grid_m, const int grid_n) {
     constexpr bool F16 = epi_f16(EPI);
-    constexpr int WM = BM / NWM, WN = BN / NWN;
-    constexpr int NT = NWM * NWN * 64;
-    static_assert(WM % 16 == 0 && WN % 16 == 0 && BM % NWM == 0 && BN % NWN == 0, "wave tile");
-    constexpr int TM = WM / 16, TN = WN / 16;
-    constexpr int RPP = NT / 4;                    // rows per pass: 4 x 16-B chunks per 64-B row
-    constexpr int A_SLOTS = (BM + RPP - 1) / RPP, B_SLOTS = (BN + RPP - 1) / RPP;
-    static_assert(RPP % 16 == 0, "predication per 16-row wave slice; swizzle period 8");
-    // a pass that runs past the panel (BM or BN not a multiple of RPP) is predicated per 16-row wave
-    // slice: its loads are issued out of range (the vmcnt count per stage stays constant) and its LDS
-    // writes are skipped
-    constexpr int PANEL_A = BM * 64, PANEL_B = BN * 64;        // bytes
-    constexpr int STAGE = (F16 ? 1 : 2) * (PANEL_A + PANEL_B);     // [A hi][A lo][B hi][B lo], f16: [A hi][B hi]
-    constexpr int PANEL_B0 = (F16 ? 1 : 2) * PANEL_A;                  // offset of the B hi panel
-    // the epilogue's transpose tile needs at least one WM-row pass of BN fp32 (f16 128x256: 64 KiB against 48 KiB of stages)
-    constexpr int SMEM = 2 * STAGE > WM * BN * 4 ? 2 * STAGE : WM * BN * 4;
+    using Tile = StagedTile<BM, BN, NWM, NWN, F16>;
+    constexpr int WM = Tile::WM, WN = Tile::WN, NT = Tile::NT, RPP = Tile::RPP, A_SLOTS = Tile::A_SLOTS, B_SLOTS = Tile::B_SLOTS, SMEM = Tile::SMEM;
 
     __shared__ __attribute__((aligned(16))) unsigned char smem[SMEM];
 
@@ -115,8 +95,7 @@ void conv_igemm_f16s3_kernel(const ConvArgs a, const int grid_m, const int grid_
     int ld_kc = 0, ld_c0 = 0, ld_ky = 0, ld_kx = 0;
     const int nk = a.Kpad / HBK;
 
-    StageRegs<A_SLOTS, B_SLOTS> S0, S1;
-    auto gload = [&](StageRegs<A_SLOTS, B_SLOTS>& S) {
+    auto gload = [&](typename Tile::Regs& S) {
         // chunks past the end of K (issued unconditionally to keep the loop branch-free, so that the
         // compiler's vmcnt bookkeeping stays exact) read out of range -> zeros
         const bool live = ld_kc < nk;
@@ -140,151 +119,22 @@ void conv_igemm_f16s3_kernel(const ConvArgs a, const int grid_m, const int grid_
         ++ld_kc;
         if (++ld_kx == a.kw) { ld_kx = 0; if (++ld_ky == a.kh) { ld_ky = 0; ld_c0 += HBK; } }
     };
-    constexpr int LOADS_PER_STAGE = (F16 ? 1 : 2) * (A_SLOTS + B_SLOTS);
-    static_assert(LOADS_PER_STAGE <= 8, "vmcnt literals below");
-    // wait until at most `LOADS_PER_STAGE` loads (the younger stage set) are outstanding: the older set S
-    // has landed.  Every register of S is an in/out operand so no use can be scheduled above the wait.
-    auto wait_stage = [&](StageRegs<A_SLOTS, B_SLOTS>& S) {
-        static_assert(A_SLOTS >= 1 && A_SLOTS <= 2 && B_SLOTS >= 1 && B_SLOTS <= 2, "stage shape");
-        if constexpr (F16 && A_SLOTS == 2 && B_SLOTS == 2)
-            asm volatile("s_waitcnt vmcnt(4)" : "+v"(S.ah[0]), "+v"(S.ah[1]), "+v"(S.bh[0]), "+v"(S.bh[1]) :: "memory");
-        else if constexpr (F16 && A_SLOTS == 2 && B_SLOTS == 1)
-            asm volatile("s_waitcnt vmcnt(3)" : "+v"(S.ah[0]), "+v"(S.ah[1]), "+v"(S.bh[0]) :: "memory");
-        else if constexpr (F16 && A_SLOTS == 1 && B_SLOTS == 2)
-            asm volatile("s_waitcnt vmcnt(3)" : "+v"(S.ah[0]), "+v"(S.bh[0]), "+v"(S.bh[1]) :: "memory");
-        else if constexpr (F16)
-            asm volatile("s_waitcnt vmcnt(2)" : "+v"(S.ah[0]), "+v"(S.bh[0]) :: "memory");
-        else if constexpr (A_SLOTS == 2 && B_SLOTS == 2)
-            asm volatile("s_waitcnt vmcnt(8)" : "+v"(S.ah[0]), "+v"(S.al[0]), "+v"(S.ah[1]), "+v"(S.al[1]),
-                         "+v"(S.bh[0]), "+v"(S.bl[0]), "+v"(S.bh[1]), "+v"(S.bl[1]) :: "memory");
-        else if constexpr (A_SLOTS == 2 && B_SLOTS == 1)
-            asm volatile("s_waitcnt vmcnt(6)" : "+v"(S.ah[0]), "+v"(S.al[0]), "+v"(S.ah[1]), "+v"(S.al[1]),
-                         "+v"(S.bh[0]), "+v"(S.bl[0]) :: "memory");
-        else if constexpr (A_SLOTS == 1 && B_SLOTS == 2)
-            asm volatile("s_waitcnt vmcnt(6)" : "+v"(S.ah[0]), "+v"(S.al[0]),
-                         "+v"(S.bh[0]), "+v"(S.bl[0]), "+v"(S.bh[1]), "+v"(S.bl[1]) :: "memory");
-        else
-            asm volatile("s_waitcnt vmcnt(4)" : "+v"(S.ah[0]), "+v"(S.al[0]), "+v"(S.bh[0]), "+v"(S.bl[0]) :: "memory");
-        __builtin_amdgcn_sched_barrier(0);
-    };
-    // LDS image: panel row r, 16-B chunk c at byte r*64 + ((c ^ ((r>>1)&3)) << 4)
-    const int wr_swz = (c16 ^ ((row0 >> 1) & 3)) << 4;           // RPP % 8 == 0 -> same swizzle for every slot
-    auto lds_write = [&](const StageRegs<A_SLOTS, B_SLOTS>& S, int buf) {
-        unsigned char* st = smem + buf * STAGE;
-#pragma unroll
-        for (int i = 0; i < A_SLOTS; ++i) {
-            const int o = (row0 + i * RPP) * 64 + wr_swz;
-            if ((i + 1) * RPP <= BM || row0 + i * RPP < BM) {
-                *reinterpret_cast<u32x4*>(st + o) = S.ah[i];
-                if constexpr (!F16) *reinterpret_cast<u32x4*>(st + PANEL_A + o) = S.al[i];
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < B_SLOTS; ++i) {
-            const int o = (row0 + i * RPP) * 64 + wr_swz;
-            if ((i + 1) * RPP <= BN || row0 + i * RPP < BN) {
-                *reinterpret_cast<u32x4*>(st + PANEL_B0 + o) = S.bh[i];
-                if constexpr (!F16) *reinterpret_cast<u32x4*>(st + PANEL_B0 + PANEL_B + o) = S.bl[i];
-            }
-        }
-    };
 
-    f32x4 acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) acc[i][j][e] = 0.f;
-
-    const int wave = tid >> 6, lane = tid & 63;
-    const int wm = wave / NWN, wn = wave - wm * NWN;
-    const int lr = lane & 15, lh = lane >> 4;
-    const int co = (lh ^ ((lr >> 1) & 3)) << 4;                  // WM, WN % 16 == 0: the row's swizzle is the lane's
-    const int a_row = (wm * WM + lr) * 64 + co, b_row = PANEL_B0 + (wn * WN + lr) * 64 + co;
-
-    // the A fragments of the K-chunk are read into registers first, then the next chunk's LDS writes and the
-    // global loads of the chunk after are issued, and only then the MFMA block runs (B fragments read per
-    // 16-column group just ahead of their MFMAs): the LDS write drain (~80 B/clk/CU through the VGPR path) and
-    // the load latency overlap with the matrix pipe instead of sitting between the MFMAs and the barrier.
-    f16x8 ah[TM], al[TM];
-    auto read_a = [&](int buf) {
-        const unsigned char* st = smem + buf * STAGE + a_row;
-#pragma unroll
-        for (int i = 0; i < TM; ++i) {
-            ah[i] = *reinterpret_cast<const f16x8*>(st + i * 16 * 64);
-            if constexpr (!F16) al[i] = *reinterpret_cast<const f16x8*>(st + PANEL_A + i * 16 * 64);
-        }
-    };
-    auto compute = [&](int buf) {
-        const unsigned char* st = smem + buf * STAGE + b_row;
-        f16x8 bh[TN], bl[TN];
-#pragma unroll
-        for (int j = 0; j < TN; ++j) {
-            bh[j] = *reinterpret_cast<const f16x8*>(st + j * 16 * 64);
-            if constexpr (!F16) bl[j] = *reinterpret_cast<const f16x8*>(st + PANEL_B + j * 16 * 64);
-        }
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int i = 0; i < TM; ++i) {
-                if constexpr (F16) { acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[i], bh[j], acc[i][j], 0, 0, 0); continue; }
-                acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[i], bh[j], acc[i][j], 0, 0, 0);
-                acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[i], bl[j], acc[i][j], 0, 0, 0);
-                acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[i], bh[j], acc[i][j], 0, 0, 0);
-            }
-    };
-
-    // prologue: chunks 0 and 1 in flight, chunk 0 staged, chunk 2 issued.  The steady state is
-    // branch-free: every half-iteration computes one chunk, stages the next and issues the load of the
-    // one after (chunks >= nk are zero chunks); an odd nk costs one zero chunk of MFMAs.
-    // vmcnt bookkeeping: loads complete in issue order; at every wait the older stage set has
-    // LOADS_PER_STAGE loads outstanding and the younger set LOADS_PER_STAGE more behind them.
+    f32x4 acc[Tile::TM][Tile::TN];
+    Tile::zero(acc);
 #ifdef RTOD_STAMPS
     unsigned long long ts_[GSTAMP_SLOTS] = {0, 0, 0, 0, 0, 0, 0, 0};
     unsigned long long tprev_ = __builtin_amdgcn_s_memtime();
     const unsigned long long tstart_ = tprev_;
 #endif
-    gload(S0);
-    gload(S1);
-    wait_stage(S0);
-    lds_write(S0, 0);
-    gload(S0);
-    __syncthreads();
-    RTOD_GSTAMP(0)                                    // 0: prologue
-    for (int t = 0; t < nk; t += 2) {
-        read_a(0);                                    // chunk t
-        wait_stage(S1);
-        RTOD_GSTAMP(1)                                // 1: A reads issued + wait for the staged set
-        lds_write(S1, 1);                             // chunk t+1
-        gload(S1);                                    // chunk t+3
-        __builtin_amdgcn_sched_barrier(0);
-        RTOD_GSTAMP(2)                                // 2: LDS writes + loads issued
-        compute(0);
-        RTOD_GSTAMP(3)                                // 3: B reads + MFMA issue
-        __syncthreads();
-        RTOD_GSTAMP(4)                                // 4: barrier
-        read_a(1);                                    // chunk t+1
-        wait_stage(S0);
-        RTOD_GSTAMP(1)
-        lds_write(S0, 0);                             // chunk t+2
-        gload(S0);                                    // chunk t+4
-        __builtin_amdgcn_sched_barrier(0);
-        RTOD_GSTAMP(2)
-        compute(1);
-        RTOD_GSTAMP(3)
-        __syncthreads();
-        RTOD_GSTAMP(4)
+    // the shared pipeline over the whole K sum, A fragments read ahead of the wait; its phases are stamped in a diagnostic build
+    constexpr bool A_AHEAD = true;
+#define RTOD_STAGED_PHASE(i) RTOD_GSTAMP(i)
+#include "conv_f16s3_staged_defs.inc"
+    {
+        const int kc0 = 0, kc1 = nk;
+#include "conv_f16s3_staged_run.inc"
     }
-    // Drain the trailing zero-chunk loads.  Their destination registers are dead to the compiler from the moment the
-    // last gload statement ends, and register-only epilogue code (address arithmetic, hoisted above this asm: "memory"
-    // orders memory operations only) may be allocated into them — a load landing afterwards then zeroes a live pointer
-    // (observed: 'Memory access fault on address (nil)' once the epilogue's code changed).  wait_stage names every
-    // register of a set as in/out, so both sets stay allocated until the loads have landed.
-    vmcnt<0>();
-    wait_stage(S0);
-    wait_stage(S1);
-    RTOD_GSTAMP(5)                                    // 5: drain
 
 #ifdef RTOD_DIAG
     if (a.dbg & 4) return;                            // timing experiment: no epilogue

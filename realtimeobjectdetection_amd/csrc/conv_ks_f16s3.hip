@@ -3,7 +3,7 @@
 //
 // At one or two frames the deep layers (13x13 ... 52x52 grids, K = 256 ... 9216) have a few dozen output tiles for 256 CUs and
 // each tile walks the whole K sum.  Here the K-chunks of 32 are cut into slices of `a.slice_chunks` chunks (a property of the
-// layer: plan.cpp, split_slice_chunks; the last slice may be shorter).  Every slice starts from zero accumulators and runs the
+// layer: plan_build.cpp, split_slice_chunks; the last slice may be shorter).  Every slice starts from zero accumulators and runs the
 // very same pipelined loop, and the slice sums are added in ascending slice order in fp32, starting from zero.  That order is
 // fixed by the layer alone, so two schedules give the same bits:
 //   schedule A (SCHED_B = false): the grid is the tiles; a workgroup walks slice after slice, total = total + slice at every
@@ -12,18 +12,13 @@
 //                                 a.partial [slice][M][Npad]; conv_ks_reduce_kernel then adds the panels in ascending order and
 //                                 applies the arithmetic of conv_f16s3_epilogue (conv_f16s3_common.h), restated below.
 // A sliced layer always runs this family, at every batch size (a frame's result must not depend on the batch it rides in);
-// autotune picks tile and schedule.  Same LDS staging, swizzle, buffer-load addressing, MFMA sequence and F16 flag as the
+// autotune picks tile and schedule.  The LDS staging, swizzle, MFMA sequence and schedule are the one copy of conv_f16s3_staged.h; same buffer-load addressing and F16 flag as the
 // generic tile; K order k = ((c/32)*kh*kw + tap)*32 + c%32, so the weights are the generic packing.
 // No fused head decode and no hosted pointwise conv in this family (the planner never slices such layers).
-#include "conv_f16s3_common.h"
+#include "conv_f16s3_staged.h"
 #include <cstdio>
 
 namespace rtod {
-
-template <int ASL, int BSL>
-struct KsStageRegs {
-    u32x4 ah[ASL], al[ASL], bh[BSL], bl[BSL];
-};
 
 // BM x BN workgroup tile, NWM x NWN waves; MINW = waves per SIMD the register budget must admit.  Schedule A keeps two
 // accumulator sets (slice + total): 64x64 keeps the generic tile's 4 waves per SIMD (112 VGPRs) and 64x128 its 3 (162 VGPRs); the
@@ -32,17 +27,9 @@ template <int BM, int BN, int NWM, int NWN, int MINW, int EPI, bool SCHED_B>
 __global__ __launch_bounds__(NWM * NWN * 64, MINW)
 void conv_ks_f16s3_kernel(const ConvArgs a, const int grid_m, const int grid_n) {
     constexpr bool F16 = epi_f16(EPI);
-    constexpr int WM = BM / NWM, WN = BN / NWN;
-    constexpr int NT = NWM * NWN * 64;
-    static_assert(WM % 16 == 0 && WN % 16 == 0 && BM % NWM == 0 && BN % NWN == 0, "wave tile");
-    constexpr int TM = WM / 16, TN = WN / 16;
-    constexpr int RPP = NT / 4;                    // rows per pass: 4 x 16-B chunks per 64-B row
-    constexpr int A_SLOTS = (BM + RPP - 1) / RPP, B_SLOTS = (BN + RPP - 1) / RPP;
-    static_assert(RPP % 16 == 0, "predication per 16-row wave slice; swizzle period 8");
-    constexpr int PANEL_A = BM * 64, PANEL_B = BN * 64;        // bytes
-    constexpr int STAGE = (F16 ? 1 : 2) * (PANEL_A + PANEL_B);     // [A hi][A lo][B hi][B lo], f16: [A hi][B hi]
-    constexpr int PANEL_B0 = (F16 ? 1 : 2) * PANEL_A;                  // offset of the B hi panel
-    constexpr int SMEM = 2 * STAGE > WM * BN * 4 ? 2 * STAGE : WM * BN * 4;   // stages, or one WM-row pass of the epilogue's transpose tile
+    using Tile = StagedTile<BM, BN, NWM, NWN, F16>;
+    constexpr int WM = Tile::WM, WN = Tile::WN, NT = Tile::NT, TM = Tile::TM, TN = Tile::TN, RPP = Tile::RPP;
+    constexpr int A_SLOTS = Tile::A_SLOTS, B_SLOTS = Tile::B_SLOTS, SMEM = Tile::SMEM;
 
     __shared__ __attribute__((aligned(16))) unsigned char smem[SMEM];
 
@@ -91,8 +78,7 @@ void conv_ks_f16s3_kernel(const ConvArgs a, const int grid_m, const int grid_n) 
     int ld_kc = 0, ld_c0 = 0, ld_ky = 0, ld_kx = 0, ld_end = 0;
     const int nk = a.Kpad / HBK;
 
-    KsStageRegs<A_SLOTS, B_SLOTS> S0, S1;
-    auto gload = [&](KsStageRegs<A_SLOTS, B_SLOTS>& S) {
+    auto gload = [&](typename Tile::Regs& S) {
         // chunks past the end of the slice (issued unconditionally: the loop stays branch-free and the vmcnt bookkeeping exact)
         // read out of range -> zeros
         const bool live = ld_kc < ld_end;
@@ -114,142 +100,24 @@ void conv_ks_f16s3_kernel(const ConvArgs a, const int grid_m, const int grid_n) 
         ++ld_kc;
         if (++ld_kx == a.kw) { ld_kx = 0; if (++ld_ky == a.kh) { ld_ky = 0; ld_c0 += HBK; } }
     };
-    constexpr int LOADS_PER_STAGE = (F16 ? 1 : 2) * (A_SLOTS + B_SLOTS);
-    static_assert(LOADS_PER_STAGE <= 8, "vmcnt literals below");
-    // wait until at most LOADS_PER_STAGE loads (the younger stage set) are outstanding: the older set S has landed.  Every
-    // register of S is an in/out operand so no use can be scheduled above the wait.
-    auto wait_stage = [&](KsStageRegs<A_SLOTS, B_SLOTS>& S) {
-        static_assert(A_SLOTS >= 1 && A_SLOTS <= 2 && B_SLOTS >= 1 && B_SLOTS <= 2, "stage shape");
-        if constexpr (F16 && A_SLOTS == 2 && B_SLOTS == 2)
-            asm volatile("s_waitcnt vmcnt(4)" : "+v"(S.ah[0]), "+v"(S.ah[1]), "+v"(S.bh[0]), "+v"(S.bh[1]) :: "memory");
-        else if constexpr (F16 && A_SLOTS == 2 && B_SLOTS == 1)
-            asm volatile("s_waitcnt vmcnt(3)" : "+v"(S.ah[0]), "+v"(S.ah[1]), "+v"(S.bh[0]) :: "memory");
-        else if constexpr (F16 && A_SLOTS == 1 && B_SLOTS == 2)
-            asm volatile("s_waitcnt vmcnt(3)" : "+v"(S.ah[0]), "+v"(S.bh[0]), "+v"(S.bh[1]) :: "memory");
-        else if constexpr (F16)
-            asm volatile("s_waitcnt vmcnt(2)" : "+v"(S.ah[0]), "+v"(S.bh[0]) :: "memory");
-        else if constexpr (A_SLOTS == 2 && B_SLOTS == 2)
-            asm volatile("s_waitcnt vmcnt(8)" : "+v"(S.ah[0]), "+v"(S.al[0]), "+v"(S.ah[1]), "+v"(S.al[1]),
-                         "+v"(S.bh[0]), "+v"(S.bl[0]), "+v"(S.bh[1]), "+v"(S.bl[1]) :: "memory");
-        else if constexpr (A_SLOTS == 2 && B_SLOTS == 1)
-            asm volatile("s_waitcnt vmcnt(6)" : "+v"(S.ah[0]), "+v"(S.al[0]), "+v"(S.ah[1]), "+v"(S.al[1]),
-                         "+v"(S.bh[0]), "+v"(S.bl[0]) :: "memory");
-        else if constexpr (A_SLOTS == 1 && B_SLOTS == 2)
-            asm volatile("s_waitcnt vmcnt(6)" : "+v"(S.ah[0]), "+v"(S.al[0]),
-                         "+v"(S.bh[0]), "+v"(S.bl[0]), "+v"(S.bh[1]), "+v"(S.bl[1]) :: "memory");
-        else
-            asm volatile("s_waitcnt vmcnt(4)" : "+v"(S.ah[0]), "+v"(S.al[0]), "+v"(S.bh[0]), "+v"(S.bl[0]) :: "memory");
-        __builtin_amdgcn_sched_barrier(0);
-    };
-    // LDS image: panel row r, 16-B chunk c at byte r*64 + ((c ^ ((r>>1)&3)) << 4)
-    const int wr_swz = (c16 ^ ((row0 >> 1) & 3)) << 4;           // RPP % 8 == 0 -> same swizzle for every slot
-    auto lds_write = [&](const KsStageRegs<A_SLOTS, B_SLOTS>& S, int buf) {
-        unsigned char* st = smem + buf * STAGE;
-#pragma unroll
-        for (int i = 0; i < A_SLOTS; ++i) {
-            const int o = (row0 + i * RPP) * 64 + wr_swz;
-            if ((i + 1) * RPP <= BM || row0 + i * RPP < BM) {
-                *reinterpret_cast<u32x4*>(st + o) = S.ah[i];
-                if constexpr (!F16) *reinterpret_cast<u32x4*>(st + PANEL_A + o) = S.al[i];
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < B_SLOTS; ++i) {
-            const int o = (row0 + i * RPP) * 64 + wr_swz;
-            if ((i + 1) * RPP <= BN || row0 + i * RPP < BN) {
-                *reinterpret_cast<u32x4*>(st + PANEL_B0 + o) = S.bh[i];
-                if constexpr (!F16) *reinterpret_cast<u32x4*>(st + PANEL_B0 + PANEL_B + o) = S.bl[i];
-            }
-        }
-    };
 
     f32x4 acc[TM][TN];                                           // the current slice
     f32x4 total[SCHED_B ? 1 : TM][SCHED_B ? 1 : TN];             // schedule A: sum of the finished slices
     (void)total;
-    if constexpr (!SCHED_B) {
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) total[i][j][e] = 0.f;
-    }
+    if constexpr (!SCHED_B) Tile::zero(total);
 
-    const int wave = tid >> 6, lane = tid & 63;
-    const int wm = wave / NWN, wn = wave - wm * NWN;
-    const int lr = lane & 15, lh = lane >> 4;
-    const int co = (lh ^ ((lr >> 1) & 3)) << 4;
-    const int a_row = (wm * WM + lr) * 64 + co, b_row = PANEL_B0 + (wn * WN + lr) * 64 + co;
+    constexpr bool A_AHEAD = true;                               // the generic tile's read order
+#include "conv_f16s3_staged_defs.inc"
 
-    f16x8 ah[TM], al[TM];
-    auto read_a = [&](int buf) {
-        const unsigned char* st = smem + buf * STAGE + a_row;
-#pragma unroll
-        for (int i = 0; i < TM; ++i) {
-            ah[i] = *reinterpret_cast<const f16x8*>(st + i * 16 * 64);
-            if constexpr (!F16) al[i] = *reinterpret_cast<const f16x8*>(st + PANEL_A + i * 16 * 64);
-        }
-    };
-    auto compute = [&](int buf) {
-        const unsigned char* st = smem + buf * STAGE + b_row;
-        f16x8 bh[TN], bl[TN];
-#pragma unroll
-        for (int j = 0; j < TN; ++j) {
-            bh[j] = *reinterpret_cast<const f16x8*>(st + j * 16 * 64);
-            if constexpr (!F16) bl[j] = *reinterpret_cast<const f16x8*>(st + PANEL_B + j * 16 * 64);
-        }
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int i = 0; i < TM; ++i) {
-                if constexpr (F16) { acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[i], bh[j], acc[i][j], 0, 0, 0); continue; }
-                acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[i], bh[j], acc[i][j], 0, 0, 0);
-                acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[i], bl[j], acc[i][j], 0, 0, 0);
-                acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[i], bh[j], acc[i][j], 0, 0, 0);
-            }
-    };
-
-    // One slice [kc0, kc1): zero accumulators, then the generic tile's pipeline (prologue: two chunks in flight, the first staged;
-    // steady state branch-free, one barrier per chunk; chunks >= kc1 are zero chunks, so an odd slice length costs one zero chunk of
-    // MFMAs, which leaves every accumulator bit as it is in both schedules alike).  It ends on a barrier with no load in flight,
-    // so the next slice may restage LDS at once.
+    // One slice [kc0, kc1): zero accumulators, the cursor seeded at kc0, then the shared pipeline (chunks >= kc1 are zero chunks, so
+    // an odd slice length costs one zero chunk of MFMAs, which leaves every accumulator bit as it is in both schedules alike).  It
+    // ends on a barrier with no load in flight, so the next slice may restage LDS at once.
     auto run_slice = [&](int kc0, int kc1) {
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) acc[i][j][e] = 0.f;
+        Tile::zero(acc);
         const int taps = a.kh * a.kw;
         const int cchunk = kc0 / taps, tap = kc0 - cchunk * taps;
         ld_kc = kc0; ld_end = kc1; ld_c0 = cchunk * HBK; ld_ky = tap / a.kw; ld_kx = tap - ld_ky * a.kw;
-        gload(S0);
-        gload(S1);
-        wait_stage(S0);
-        lds_write(S0, 0);
-        gload(S0);
-        __syncthreads();
-        for (int t = kc0; t < kc1; t += 2) {
-            read_a(0);                                    // chunk t
-            wait_stage(S1);
-            lds_write(S1, 1);                             // chunk t+1
-            gload(S1);                                    // chunk t+3
-            __builtin_amdgcn_sched_barrier(0);
-            compute(0);
-            __syncthreads();
-            read_a(1);                                    // chunk t+1
-            wait_stage(S0);
-            lds_write(S0, 0);                             // chunk t+2
-            gload(S0);                                    // chunk t+4
-            __builtin_amdgcn_sched_barrier(0);
-            compute(1);
-            __syncthreads();
-        }
-        // drain the trailing zero-chunk loads; wait_stage names every register of a set as in/out, so both sets stay allocated
-        // until the loads have landed (conv_f16s3_common.h, register ties)
-        vmcnt<0>();
-        wait_stage(S0);
-        wait_stage(S1);
+#include "conv_f16s3_staged_run.inc"
     };
 
     if constexpr (SCHED_B) {

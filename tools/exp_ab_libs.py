@@ -3,7 +3,9 @@
 Darknet per library, the same tile table installed in each (RTOD_TILES, saved by bench.py --tiles; without it each library autotunes),
 per-launch hipEvent timings taken in interleaved rounds — box, clock state and thermal drift are shared, which separate processes
 (tools/run_abn.sh: +-1...2 % between identical kernels) cannot offer.
-    python tools/exp_ab_libs.py out.json res batch libA.so libB.so ...     (names relative to realtimeobjectdetection_amd/)"""
+    python tools/exp_ab_libs.py out.json res batch libA.so libB.so ...     (names relative to realtimeobjectdetection_amd/)
+Environment: NET=yolov3 (default) | yolov3-tiny; OPTS=name=value,... plan options put into Darknet.options of every model (e.g.
+NET=yolov3-tiny OPTS=narrow_cin=1, or OPTS=k_slices_split=1: the 16-channel and the K-sliced families); ROUNDS; RTOD_TILES."""
 import collections, json, os, sys, tempfile
 sys.path.insert(0, os.getcwd())
 import numpy as np, torch
@@ -12,13 +14,15 @@ from realtimeobjectdetection_amd.cfg import parse_cfg_text, build_ir
 from realtimeobjectdetection_amd.darknet import Darknet
 out = sys.argv[1]; res = int(sys.argv[2]); B = int(sys.argv[3]); names = sys.argv[4:]
 ROUNDS = int(os.environ.get("ROUNDS", "24"))
+NET = os.environ.get("NET", "yolov3")
+OPTS = {k: int(v) for k, v in (kv.split("=") for kv in os.environ.get("OPTS", "").split(",") if kv)}
 here = os.path.dirname(os.path.abspath(_ffi.__file__))
 handles = {}
 for n in names:
     _ffi.LIB_PATH = os.path.join(here, n); _ffi._lib = None
     handles[n] = _ffi.lib()
 def use(n): _ffi._lib = handles[n]
-text = cfgs.yolov3_cfg(); ir = build_ir(parse_cfg_text(text), res)
+text = {"yolov3": cfgs.yolov3_cfg, "yolov3-tiny": cfgs.yolov3_tiny_cfg}[NET](); ir = build_ir(parse_cfg_text(text), res)
 w = synth.synth_weights(ir)
 x = torch.from_numpy(synth.synth_frames(B, res)).cuda()
 d = tempfile.mkdtemp()
@@ -31,6 +35,7 @@ for n in names:
     use(n)
     m = Darknet(cfgs.write_cfg(os.path.join(d, "m.cfg"), text), True).eval()
     m.net_info["height"] = res; m.precision = "f16s3"; m.overflow_check = "off"
+    m.options.update(OPTS)
     m.load_weight_stream(w)
     if table is not None:
         m.prepare(B); m.set_tiles(B, table)
