@@ -29,7 +29,8 @@ template <int NBASE, int PER = 2> __device__ __forceinline__ void bandd_wait_vmc
 }
 
 // ---- epilogue: scale / bias / activation, LDS transpose in passes of RG rows, split-format store (+ residual).
-// Arithmetic and expression shapes are those of conv_f16s3_epilogue (conv_f16s3_common.h): the same bits.  Unlike that
+// The arithmetic is conv_f16s3_epilogue's: the same bits (epi_col_params and the text of conv_f16s3_epi_transpose.inc are the one copy
+// both use; the finish-and-store statements are restated below).  Unlike that
 // function a pass may cover a PART of a wave's rows (a wave owns all BM rows of its strip; the whole tile would need 64 KB).
 // F16: plain-f16 output (hi plane of the shortcut operand read, hi plane stored).
 // RAW: raw-sum instance (epi_raw, conv_f16s3_common.h): acc * inv_scale[n] as fp32 rows of ConvArgs::raw_out; no bias load, no
@@ -37,7 +38,7 @@ template <int NBASE, int PER = 2> __device__ __forceinline__ void bandd_wait_vmc
 template <int BM, int BN, int WM, int WN, int NT, int RG, bool RES, int KG, bool F16 = false, bool RAW = false>
 __device__ __forceinline__ void bandd_epilogue(const ConvArgs& a, f32x4 (&acc)[WM / 16][WN / 16], unsigned char* smem, int bm, int bn, int tid,
                                                int wm, int wn, int lr, int lh, int M, int kg) {
-    constexpr int TM = WM / 16, TN = WN / 16, MT = 16, NE = 4, TS = BN;
+    constexpr int TM = WM / 16, TN = WN / 16, MT = 16, TS = BN;
     static_assert(BM % RG == 0 && RG % 16 == 0, "epilogue pass");
     static_assert(!RAW || (!RES && !F16), "raw-sum instances: no shortcut, no plain-f16 store");
 #ifdef RTOD_TIMELINE
@@ -55,12 +56,7 @@ __device__ __forceinline__ void bandd_epilogue(const ConvArgs& a, f32x4 (&acc)[W
     constexpr int NP = BM / RG;
     float bias_j[TN], inv_j[TN];
 #pragma unroll
-    for (int j = 0; j < TN; ++j) {
-        const int n = bn * BN + wn * WN + j * MT + lr;
-        const int nc = n < a.Cout ? n : 0;
-        const float b = RAW ? 0.f : a.bias[nc], iv = a.inv_scale[nc];
-        bias_j[j] = n < a.Cout ? b : 0.f; inv_j[j] = n < a.Cout ? iv : 0.f;
-    }
+    for (int j = 0; j < TN; ++j) epi_col_params<!RAW>(a, bn * BN + wn * WN + j * MT + lr, bias_j[j], inv_j[j]);
     f16x8 rq_h[RES ? NP : 1][RES ? NG : 1], rq_l[RES ? NP : 1][RES ? NG : 1];
     // Item (pass p, i) of a thread is row p RG + tid / GPR + i (NT / GPR), 8 channels at (tid % GPR) 8 when NT is a multiple of GPR
     // (every tile of this family): row and channel split ONCE, addresses advance by a constant — the per-item 64-bit multiplies of
@@ -91,51 +87,14 @@ __device__ __forceinline__ void bandd_epilogue(const ConvArgs& a, f32x4 (&acc)[W
     BD_ESTAMP(0)
 #pragma unroll
     for (int rg = 0; rg < BM; rg += RG) {
-        if constexpr (KG == 2) {                                         // K group 1 deposits its raw sums, group 0 adds its own
-            if (kg == 1) {
-#pragma unroll
-                for (int i = 0; i < TM; ++i) {
-                    const int r0 = wm * WM + i * MT;
-                    if (r0 >= rg && r0 < rg + RG) {
-#pragma unroll
-                        for (int j = 0; j < TN; ++j)
-#pragma unroll
-                            for (int e = 0; e < NE; ++e) T[(r0 - rg + e + 4 * lh) * TS + wn * WN + j * MT + lr] = acc[i][j][e];
-                    }
-                }
-            }
-            __syncthreads();
-        }
-        if (KG == 1 || kg == 0) {
-#pragma unroll
-            for (int j = 0; j < TN; ++j) {
-                const int nl = wn * WN + j * MT + lr;
-                const float bias = bias_j[j] * escale, inv = inv_j[j] * escale;
-                auto col = [&](auto act) {                                   // 0 linear, 1 leaky, 2 SiLU
-#pragma unroll
-                    for (int i = 0; i < TM; ++i) {
-                        const int r0 = wm * WM + i * MT;
-                        if (r0 >= rg && r0 < rg + RG) {                       // compile-time for one wave along M
-#pragma unroll
-                            for (int e = 0; e < NE; ++e) {
-                                const int rl = r0 - rg + e + 4 * lh;
-                                float s = acc[i][j][e];
-                                if constexpr (KG == 2) s += T[rl * TS + nl];
-                                if constexpr (RAW) { T[rl * TS + nl] = s * inv; continue; }       // the convolution sum: exact undo of the pre-scales
-                                float v = s * inv + bias;
-                                if constexpr (decltype(act)::value == 2) v = silu_scaled(v, 1.0f / escale);
-                                else if constexpr (decltype(act)::value == 1) v = __builtin_fmaxf(v, v * 0.1f);
-                                T[rl * TS + nl] = v;
-                            }
-                        }
-                    }
-                };
-                if constexpr (RAW) col(std::integral_constant<int, 0>{});
-                else if (a.leaky == 2) col(std::integral_constant<int, 2>{});
-                else if (a.leaky) col(std::integral_constant<int, 1>{});
-                else col(std::integral_constant<int, 0>{});
-            }
-        }
+        // a pass takes whole 16-row tiles, a part of the wave's: compile-time for one wave along M
+#define EPI_WAVE_IN_PASS true
+#define EPI_TILE_IN_PASS(i) (wm * WM + (i) * MT >= rg && wm * WM + (i) * MT < rg + RG)
+#define EPI_TILE_ROW(i) (wm * WM + (i) * MT - rg)
+#include "conv_f16s3_epi_transpose.inc"
+#undef EPI_WAVE_IN_PASS
+#undef EPI_TILE_IN_PASS
+#undef EPI_TILE_ROW
         BD_ESTAMP(1)
         __syncthreads();
         BD_ESTAMP(2)
@@ -154,6 +113,8 @@ __device__ __forceinline__ void bandd_epilogue(const ConvArgs& a, f32x4 (&acc)[W
                 *reinterpret_cast<f32x4*>(rp + 4) = v1;
                 continue;
             }
+            // shortcut add, split and store: the statements of epi_add_shortcut8 / epi_split8 / epi_store8 (conv_f16s3_common.h), NOT
+            // shared with them: called here, two shortcut instances (128- and 96-row bandd tiles) changed their VGPR count
             float v[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
             if constexpr (RES && F16) {
                 const f16x8 qh = rq_h[rg / RG][gi];

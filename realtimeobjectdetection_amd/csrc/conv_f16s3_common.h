@@ -1,6 +1,7 @@
-// Shared pieces of the split-precision f16 convolution kernels (conv_igemm_f16s3, conv_band_f16s3, conv_bandd_f16s3, conv_pwd_f16s3,
-// conv_ring_f16s3, conv_patch_f16s3, conv_stem2_f16s3): the inline-asm memory primitives, the launchers' common argument checks,
-// the epilogues.
+// Shared pieces of the split-precision f16 convolution kernels (conv_igemm_f16s3, conv_c16_f16s3, conv_ks_f16s3 through
+// conv_f16s3_staged.h; conv_band_f16s3, conv_ring_f16s3, conv_patch_f16s3, conv_stem2_f16s3; conv_bandd_f16s3, conv_pwd_f16s3 through
+// conv_bandd_common.h): the inline-asm memory primitives, the launchers' common argument checks, the epilogue arithmetic (epi_*),
+// the register epilogue and the LDS-transposed epilogue.
 #pragma once
 #include "rtod_internal.h"
 #include <type_traits>
@@ -175,6 +176,56 @@ __device__ __forceinline__ void store_act16(_Float16* p, const f16x8& v, bool pl
 // activations for every element: 2.5 % on the YOLOv3 forward, measured).
 __device__ __forceinline__ float silu_scaled(float v, float inv_domain) { return v * __builtin_amdgcn_rcpf(1.0f + __expf(-v * inv_domain)); }
 
+// ---- The epilogue arithmetic.  Every tile of a layer gives the same bits; these pieces and conv_f16s3_epi_transpose.inc (the
+// deposit / scale / activate text of the two LDS-transposed epilogues) are the copies the epilogues share.  The form follows the
+// code objects (profiles/experiments/epilogue_share_resource_usage.txt): where a call changed an instance's registers, the call
+// site keeps its own statements and says so (conv_f16s3_epilogue_regs, the store half of bandd_epilogue, the hosted 1x1's activation).
+
+// (a) bias[n] / inv_scale[n] of output channel n: loads from a clamped index, selected afterwards (the conditional form
+// `n < Cout ? bias[n] : 0` cost a branch and a full memory wait per value).  BIAS = false (raw-sum instances): no bias load.
+template <bool BIAS = true> __device__ __forceinline__ void epi_col_params(const ConvArgs& a, int n, float& bias, float& inv) {
+    const int nc = n < a.Cout ? n : 0;
+    const float b = BIAS ? a.bias[nc] : 0.f, iv = a.inv_scale[nc];
+    bias = n < a.Cout ? b : 0.f; inv = n < a.Cout ? iv : 0.f;
+}
+
+// (b) one value: s inv + bias in ONE rounding (inv and bias carry the format's scale, exact products by a power of two; spelled as
+// an fma so that no call site is free to fuse the bias product into the add instead), then ACT: 0 linear, 1 leaky, 2 SiLU.
+template <int ACT> __device__ __forceinline__ float epi_scale_act1(float s, float inv, float bias, float inv_domain) {
+    const float v = __builtin_fmaf(s, inv, bias);
+    if constexpr (ACT == 2) return silu_scaled(v, inv_domain);
+    else if constexpr (ACT == 1) return __builtin_fmaxf(v, v * 0.1f);           // == v > 0 ? v : 0.1 v, bit for bit (signed zeros, infinities, NaN)
+    else return v;
+}
+// f(integral_constant<int, ACT>) behind a uniform three-way branch on ConvArgs::leaky, AROUND the caller's loops (silu_scaled above)
+template <typename F> __device__ __forceinline__ void epi_by_activation(int leaky, F f) {
+    if (leaky == 2) f(std::integral_constant<int, 2>{});
+    else if (leaky) f(std::integral_constant<int, 1>{});
+    else f(std::integral_constant<int, 0>{});
+}
+
+// (d) eight finished values -> the stored format.  The shortcut operand: hi + lo of a split tensor, hi alone of a plain-f16 one.
+template <bool F16> __device__ __forceinline__ void epi_add_shortcut8(float (&v)[8], const f16x8& qh, const f16x8& ql) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        if constexpr (F16) v[e] += (float)qh[e];
+        else v[e] += (float)qh[e] + (float)ql[e];
+    }
+}
+// split_f16 (F16: f16_sat, pl untouched) of eight values with the overflow sentinel
+template <bool F16> __device__ __forceinline__ void epi_split8(const float (&v)[8], f16x8& ph, f16x8& pl, float& amax) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        if constexpr (F16) ph[e] = f16_sat(v[e], amax);
+        else { _Float16 h, l; split_f16(v[e], h, l, amax); ph[e] = h; pl[e] = l; }
+    }
+}
+// the hi plane at q, the lo plane ldc halves behind it (F16: the hi plane alone)
+template <bool F16> __device__ __forceinline__ void epi_store8(_Float16* q, int ldc, const f16x8& ph, const f16x8& pl, bool plain) {
+    store_act16(q, ph, plain);
+    if constexpr (!F16) store_act16(q + ldc, pl, plain);
+}
+
 // ---- transposed product (out^T = W * act^T): the MFMA's first operand is the weight fragment, the second the activation
 // fragment, so a lane's accumulator holds 4 consecutive output CHANNELS (rows 4*lh + e) of ONE pixel (column lr).  With the
 // weight rows of a 32-channel group interleaved over two 16-row tiles (tr_chan_of_row) the two tiles of a pair give the lane
@@ -240,6 +291,7 @@ __device__ __forceinline__ void conv_f16s3_epilogue_regs(const ConvArgs& a, f32x
 #pragma unroll
         for (int i = 0; i < TM; ++i) {
             const int m = mrow[i];
+            // (not shared with epi_split8 / epi_store8: built on them, 30 ring / patch instances changed their VGPR count, up to +13)
             f16x8 ph, pl;
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
@@ -284,7 +336,7 @@ template <int BM, int BN, int WM, int WN, int NT, int EPI, int SMEM_BYTES, int K
 __device__ __forceinline__ void conv_f16s3_epilogue(const ConvArgs& a, f32x4 (&acc)[WM / 16][WN / 16], unsigned char* smem,
                                                     int bm, int bn, int tid, int wm, int wn, int lr, int lh, int M, int kg = 0,
                                                     const float* pre_bias = nullptr, const float* pre_inv = nullptr) {
-    constexpr int MT = 16, TM = WM / MT, TN = WN / MT, NE = 4;
+    constexpr int MT = 16, TM = WM / MT, TN = WN / MT;
     constexpr bool PW = EPI == EPI_SPLIT_PW || EPI == EPI_SPLIT_RES_PW;
     constexpr bool RES = EPI == EPI_SPLIT_RES || EPI == EPI_SPLIT_RES_PW;
     static_assert(!(F16 && PW), "plain-f16 plans host no pointwise conv");
@@ -342,12 +394,7 @@ __device__ __forceinline__ void conv_f16s3_epilogue(const ConvArgs& a, f32x4 (&a
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
             if constexpr (PRE) { bias_j[j] = pre_bias[j]; inv_j[j] = pre_inv[j]; }
-            else {
-                const int n = bn * BN + wn * WN + j * MT + lr;
-                const int nc = n < a.Cout ? n : 0;
-                const float b = a.bias[nc], iv = a.inv_scale[nc];
-                bias_j[j] = n < a.Cout ? b : 0.f; inv_j[j] = n < a.Cout ? iv : 0.f;
-            }
+            else epi_col_params(a, bn * BN + wn * WN + j * MT + lr, bias_j[j], inv_j[j]);
         }
         // residual operands of this pass: issued ahead of the transpose so that their latency (HBM / L2, ~2 us when
         // waited for inside the store loop: in-kernel stamps showed the epilogue at 15 % of a 76x76 tile) overlaps the
@@ -372,45 +419,14 @@ __device__ __forceinline__ void conv_f16s3_epilogue(const ConvArgs& a, f32x4 (&a
                 }
             }
         }
-        if constexpr (KG == 2) {
-            if (kg == 1 && wm * WM >= rg && wm * WM < rg + RG) {
-#pragma unroll
-                for (int j = 0; j < TN; ++j)
-#pragma unroll
-                    for (int i = 0; i < TM; ++i)
-#pragma unroll
-                        for (int e = 0; e < NE; ++e)
-                            T[(wm * WM - rg + i * MT + e + 4 * lh) * TS + wn * WN + j * MT + lr] = acc[i][j][e];
-            }
-            __syncthreads();
-        }
-        if ((KG == 1 || kg == 0) && (RG == BM || (wm * WM >= rg && wm * WM < rg + RG))) {     // single pass, one K group: no branch
-#pragma unroll
-            for (int j = 0; j < TN; ++j) {
-                const int nl = wn * WN + j * MT + lr;
-                const float bias = bias_j[j] * escale, inv = inv_j[j] * escale;
-                auto col = [&](auto act) {                                   // 0 linear, 1 leaky, 2 SiLU
-#pragma unroll
-                    for (int i = 0; i < TM; ++i)
-#pragma unroll
-                        for (int e = 0; e < NE; ++e) {
-                            const int rl = wm * WM - rg + i * MT + e + 4 * lh;
-                            float s = acc[i][j][e];
-                            if constexpr (KG == 2) s += T[rl * TS + nl];
-                            if constexpr (RAW) { T[rl * TS + nl] = s * inv; continue; }           // the convolution sum: exact undo of the pre-scales
-                            float v = s * inv + bias;
-                            if constexpr (decltype(act)::value == 2) v = silu_scaled(v, 1.0f / escale);
-                            else if constexpr (decltype(act)::value == 1) v = __builtin_fmaxf(v, v * 0.1f);   // == v > 0 ? v : 0.1 v, bit for bit (signed zeros, infinities, NaN)
-                            T[rl * TS + nl] = v;
-                        }
-                };
-                // uniform three-way branch around the loop: a per-value `if (a.leaky)` was a compare, a mask OR and a select per element
-                if constexpr (RAW) col(std::integral_constant<int, 0>{});
-                else if (a.leaky == 2) col(std::integral_constant<int, 2>{});
-                else if (a.leaky) col(std::integral_constant<int, 1>{});
-                else col(std::integral_constant<int, 0>{});
-            }
-        }
+        // a wave's WM rows lie in one pass (RG is a multiple of WM); single pass: no branch
+#define EPI_WAVE_IN_PASS (RG == BM || (wm * WM >= rg && wm * WM < rg + RG))
+#define EPI_TILE_IN_PASS(i) true
+#define EPI_TILE_ROW(i) (wm * WM - rg + (i) * MT)
+#include "conv_f16s3_epi_transpose.inc"
+#undef EPI_WAVE_IN_PASS
+#undef EPI_TILE_IN_PASS
+#undef EPI_TILE_ROW
         __syncthreads();
         if constexpr (EPI == EPI_DECODE) {
             // thread <-> fixed channel n: anchor / attribute kind are per-thread constants; rows advance by NT/BN
@@ -483,32 +499,16 @@ __device__ __forceinline__ void conv_f16s3_epilogue(const ConvArgs& a, f32x4 (&a
                     continue;
                 }
                 float v[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
-                if constexpr (RES && F16) {
-                    const f16x8 qh = rq_h[gi];
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) v[e] += (float)qh[e];
-                } else if constexpr (RES) {
-                    const f16x8 qh = rq_h[gi], ql = rq_l[gi];
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) v[e] += (float)qh[e] + (float)ql[e];
+                if constexpr (RES) {
+                    epi_add_shortcut8<F16>(v, rq_h[gi], rq_l[gi]);
                     if constexpr (PW) {                                   // the second GEMM reads the sum
                         *reinterpret_cast<f32x4*>(T + r * TS + c8) = f32x4{v[0], v[1], v[2], v[3]};
                         *reinterpret_cast<f32x4*>(T + r * TS + c8 + 4) = f32x4{v[4], v[5], v[6], v[7]};
                     }
                 }
-                _Float16* q = oh + (int64_t)m * 2 * a.out_ldc + c8;
-                if constexpr (F16) {
-                    f16x8 ph;
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) ph[e] = f16_sat(v[e], amax);
-                    store_act16(q, ph, st_plain);
-                } else {
-                    f16x8 ph, pl;
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) { _Float16 h, l; split_f16(v[e], h, l, amax); ph[e] = h; pl[e] = l; }
-                    store_act16(q, ph, st_plain);
-                    store_act16(q + a.out_ldc, pl, st_plain);
-                }
+                f16x8 ph, pl;
+                epi_split8<F16>(v, ph, pl, amax);
+                epi_store8<F16>(oh + (int64_t)m * 2 * a.out_ldc + c8, a.out_ldc, ph, pl, st_plain);
             }
             if constexpr (PW) {
                 // ---- fused 1x1 conv: out2[RG x pw_cout] = act[RG x pw_k] * W2^T, same three-product split arithmetic.
@@ -562,12 +562,10 @@ __device__ __forceinline__ void conv_f16s3_epilogue(const ConvArgs& a, f32x4 (&a
                     if (m >= M) continue;
                     const f32x4 v0 = *reinterpret_cast<const f32x4*>(T2 + r * T2S + c8);
                     const f32x4 v1 = *reinterpret_cast<const f32x4*>(T2 + r * T2S + c8 + 4);
+                    const float v[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
                     f16x8 ph, pl;
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) { _Float16 h, l; split_f16(e < 4 ? v0[e] : v1[e - 4], h, l, amax); ph[e] = h; pl[e] = l; }
-                    _Float16* q = oh2 + (int64_t)m * 2 * a.pw_out_ldc + c8;
-                    store_act16(q, ph, st_plain);
-                    store_act16(q + a.pw_out_ldc, pl, st_plain);
+                    epi_split8<false>(v, ph, pl, amax);
+                    epi_store8<false>(oh2 + (int64_t)m * 2 * a.pw_out_ldc + c8, a.pw_out_ldc, ph, pl, st_plain);
                 }
             }
         }

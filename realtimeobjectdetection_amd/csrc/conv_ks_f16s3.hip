@@ -10,7 +10,7 @@
 //                                 slice end, then the common epilogue (plain or fused shortcut) runs on the total;
 //   schedule B (SCHED_B = true):  the grid is tiles x slices; a workgroup writes the raw fp32 accumulators of its slice to
 //                                 a.partial [slice][M][Npad]; conv_ks_reduce_kernel then adds the panels in ascending order and
-//                                 applies the arithmetic of conv_f16s3_epilogue (conv_f16s3_common.h), restated below.
+//                                 applies the arithmetic of conv_f16s3_epilogue (the epi_* pieces of conv_f16s3_common.h).
 // A sliced layer always runs this family, at every batch size (a frame's result must not depend on the batch it rides in);
 // autotune picks tile and schedule.  The LDS staging, swizzle, MFMA sequence and schedule are the one copy of conv_f16s3_staged.h; same buffer-load addressing and F16 flag as the
 // generic tile; K order k = ((c/32)*kh*kw + tap)*32 + c%32, so the weights are the generic packing.
@@ -182,40 +182,15 @@ void conv_ks_reduce_kernel(const ConvArgs a, const int n_slices, const int M) {
         const f32x4 iv0 = *reinterpret_cast<const f32x4*>(a.inv_scale + c8), iv1 = *reinterpret_cast<const f32x4*>(a.inv_scale + c8 + 4);
         const f32x4 bs0 = *reinterpret_cast<const f32x4*>(a.bias + c8), bs1 = *reinterpret_cast<const f32x4*>(a.bias + c8 + 4);
         float v[8];
-        auto act = [&](auto kind) {                              // 0 linear, 1 leaky, 2 SiLU
+        epi_by_activation(a.leaky, [&](auto act) {
 #pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const float bias = (e < 4 ? bs0[e] : bs1[e - 4]) * SPLIT_SCALE, inv = (e < 4 ? iv0[e] : iv1[e - 4]) * SPLIT_SCALE;
-                float x = __builtin_fmaf(s[e], inv, bias);     // the epilogue's `s * inv + bias` compiles to this fma (inv, bias: exact products by 8); spelled out,
-                                                               // since here the compiler is free to fuse the bias product into the add instead
-                if constexpr (decltype(kind)::value == 2) x = silu_scaled(x, 1.0f / SPLIT_SCALE);
-                else if constexpr (decltype(kind)::value == 1) x = __builtin_fmaxf(x, x * 0.1f);
-                v[e] = x;
-            }
-        };
-        if (a.leaky == 2) act(std::integral_constant<int, 2>{});
-        else if (a.leaky) act(std::integral_constant<int, 1>{});
-        else act(std::integral_constant<int, 0>{});
-        if constexpr (RES && F16) {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) v[e] += (float)qh[e];
-        } else if constexpr (RES) {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) v[e] += (float)qh[e] + (float)ql[e];
-        }
-        _Float16* q = reinterpret_cast<_Float16*>(a.out) + a.out_coff + (int64_t)m * 2 * a.out_ldc + c8;
-        if constexpr (F16) {
-            f16x8 ph;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) ph[e] = f16_sat(v[e], amax);
-            store_act16(q, ph, false);
-        } else {
-            f16x8 ph, pl;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) { _Float16 h, l; split_f16(v[e], h, l, amax); ph[e] = h; pl[e] = l; }
-            store_act16(q, ph, false);
-            store_act16(q + a.out_ldc, pl, false);
-        }
+            for (int e = 0; e < 8; ++e)
+                v[e] = epi_scale_act1<decltype(act)::value>(s[e], (e < 4 ? iv0[e] : iv1[e - 4]) * SPLIT_SCALE, (e < 4 ? bs0[e] : bs1[e - 4]) * SPLIT_SCALE, 1.0f / SPLIT_SCALE);
+        });
+        if constexpr (RES) epi_add_shortcut8<F16>(v, qh, ql);
+        f16x8 ph, pl;
+        epi_split8<F16>(v, ph, pl, amax);
+        epi_store8<F16>(reinterpret_cast<_Float16*>(a.out) + a.out_coff + (int64_t)m * 2 * a.out_ldc + c8, a.out_ldc, ph, pl, false);
     }
     split_overflow_report(a.ovf, amax);
 }

@@ -344,21 +344,16 @@ void conv_stem2_f16s3_kernel(const Stem2Args a) {
             const int c0 = 32 * P + 8 * lh;
             const f32x4 i0 = *reinterpret_cast<const f32x4*>(tab + c0), i1 = *reinterpret_cast<const f32x4*>(tab + c0 + 4);
             const f32x4 b0 = *reinterpret_cast<const f32x4*>(tab + 64 + c0), b1 = *reinterpret_cast<const f32x4*>(tab + 64 + c0 + 4);
-            f16x8 ph, pl;
+            float v[8];
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
                 const float s = e < 4 ? acc[2 * P][e] : acc[2 * P + 1][e - 4];
-                float v = s * (e < 4 ? i0[e] : i1[e - 4]) + (e < 4 ? b0[e] : b1[e - 4]);
-                v = fmaxf(v, v * slope1);
-                _Float16 h, l;
-                split_f16(v, h, l, amax);
-                ph[e] = h; pl[e] = l;
+                v[e] = s * (e < 4 ? i0[e] : i1[e - 4]) + (e < 4 ? b0[e] : b1[e - 4]);
+                v[e] = fmaxf(v[e], v[e] * slope1);
             }
-            if (pok) {
-                _Float16* q = o1 + m * 2 * c.out_ldc + c0;
-                store_act16(q, ph, false);
-                store_act16(q + c.out_ldc, pl, false);
-            }
+            f16x8 ph, pl;
+            epi_split8<false>(v, ph, pl, amax);
+            if (pok) epi_store8<false>(o1 + m * 2 * c.out_ldc + c0, c.out_ldc, ph, pl, false);
             if constexpr (PW) {                                          // the stored values are the 1x1 conv's operand of k chunk P
 #pragma unroll
                 for (int t = 0; t < 2; ++t) {
@@ -372,21 +367,16 @@ void conv_stem2_f16s3_kernel(const Stem2Args a) {
             const int c0 = 8 * lh;
             const f32x4 i0 = *reinterpret_cast<const f32x4*>(tab + 128 + c0), i1 = *reinterpret_cast<const f32x4*>(tab + 128 + c0 + 4);
             const f32x4 b0 = *reinterpret_cast<const f32x4*>(tab + 160 + c0), b1 = *reinterpret_cast<const f32x4*>(tab + 160 + c0 + 4);
-            f16x8 ph, pl;
+            float v[8];
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
                 const float s = e < 4 ? acc2[0][e] : acc2[1][e - 4];
-                float v = s * (e < 4 ? i0[e] : i1[e - 4]) + (e < 4 ? b0[e] : b1[e - 4]);
-                v = fmaxf(v, v * slope2);
-                _Float16 h, l;
-                split_f16(v, h, l, amax);
-                ph[e] = h; pl[e] = l;
+                v[e] = s * (e < 4 ? i0[e] : i1[e - 4]) + (e < 4 ? b0[e] : b1[e - 4]);
+                v[e] = fmaxf(v[e], v[e] * slope2);
             }
-            if (pok) {
-                _Float16* q = o2 + m * 2 * c.pw_out_ldc + c0;
-                store_act16(q, ph, false);
-                store_act16(q + c.pw_out_ldc, pl, false);
-            }
+            f16x8 ph, pl;
+            epi_split8<false>(v, ph, pl, amax);
+            if (pok) epi_store8<false>(o2 + m * 2 * c.pw_out_ldc + c0, c.pw_out_ldc, ph, pl, false);
         }
     };
 

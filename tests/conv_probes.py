@@ -100,6 +100,8 @@ PROBES = [
     _p("narrow_c16", (9, 21, 16, 32, 3, 1), 3, "Cin = 16 from a 16-filter stem", options=(("narrow_cin", 1),)),
     _p("ks_pw_c256", (9, 21, 256, 96, 1, 1), 3, "K-sliced 1x1: 8 chunks in slices of 2", options=(("k_slices_split", 1),)),
     _p("ks_c64", (9, 21, 64, 64, 3, 1), 3, "K-sliced 3x3: 18 chunks in slices of 4, the last of 2", options=(("k_slices_split", 1),)),
+    _p("ks_c64_shortcut", (9, 21, 64, 64, 3, 1), 3, "K-sliced 3x3 with the fused shortcut: the shortcut operand in the reduce kernel / the last slice's epilogue",
+       options=(("k_slices_split", 1),), shortcut=True),
 ]
 BY_NAME = {p.name: p for p in PROBES}
 
