@@ -438,6 +438,50 @@ int rtod_conv1x1_wgrad_workspace(int batch, int cout, int cin, int pixels, size_
 int rtod_conv1x1_wgrad(const float* dz_dev, const float* x_dev, int batch, int cout, int cin, int pixels,
                        float* dw_dev, float* db_dev, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- optimiser step of a detection-head conv, on the stream ------------------------------------------
+ * replaces optim.Adam(self.darknet.parameters(), lr=1e-2) + optimizer.step()     train.py:57, 412-425
+ * for the convs rtod_plan_update_conv accepts that are 1x1 (the convs in front of the [yolo] layers).  One kernel per call
+ * (head_step.hip) applies the step to the caller's float32 masters and moments IN PLACE and writes the conv's ranges of the plan's
+ * packed weight image — fp32 panel, or split-f16 hi / lo planes with the per-channel power-of-two pre-scale and its inverse, and
+ * the bias — with the bits rtod_plan_load_weights / rtod_plan_update_conv would give for those masters.  The image keeps its
+ * addresses: the next forward on that stream, and a captured graph of the forward, read the new weights.  Padding channels,
+ * padding K and every other conv's block are not written.
+ *   kind 0, SGD    w' = fl(w - fl(lr32 * g)), lr32 = (float)lr: two roundings, no fused multiply-add (torch's w.sub_(g * lr));
+ *                  beta1, beta2, eps, step and the moment pointers are ignored (pass NULL).
+ *   kind 1, Adam   torch.optim.Adam without weight decay and amsgrad; `step` is the 1-based count t of this step.  The host forms
+ *                  in double and rounds to float:  a = lr / (1 - beta1^t),  r = sqrt(1 - beta2^t),  c1 = 1 - beta1,  c2 = 1 - beta2,
+ *                  where lr, beta1 and beta2 are read as the SHORTEST DECIMAL that rounds to the float given (0.999f means 0.999,
+ *                  as it prints; 1 - (double)0.999f would miss 0.001 by 2^-25 / 0.001, hundreds of ulps of every v');
+ *                  beta2 and eps reach the kernel as the floats given.  Per element, fp32, one rounding per line (fmaf = one):
+ *                      d   = g - m
+ *                      m'  = fmaf(d, c1, m)
+ *                      q   = g * g
+ *                      p   = beta2 * v
+ *                      v'  = fmaf(q, c2, p)
+ *                      s   = sqrt(v')             (correctly rounded)
+ *                      s   = s / r                (correctly rounded)
+ *                      den = s + eps
+ *                      u   = m' / den             (correctly rounded)
+ *                      w'  = fmaf(-a, u, w)
+ *                  m_w_dev / v_w_dev ([Cout, Cin], torch's exp_avg / exp_avg_sq) and m_b_dev / v_b_dev ([Cout]) are read and written.
+ * weight_dev [Cout, Cin] (OIHW of a 1x1 conv) and bias_dev [Cout] are read and written; dw_dev / db_dev are what rtod_conv1x1_wgrad
+ * wrote.  The bias takes the same step.  No floating-point atomics: results are bit-identical from call to call.
+ * Enqueues only — no allocation, no host copy, no synchronisation: legal under stream capture, the promise of rtod_forward.  It is
+ * ordered against forwards by stream order alone; a forward of this plan in flight on ANOTHER stream may read a half-written
+ * block, which is the caller's business.
+ * RTOD_E_ARG, all decided before anything touches the device: a null plan, opt or required pointer; a layer that is not a
+ * convolution, has BatchNorm or is part of a fused pointwise pair (as rtod_plan_update_conv); a stem or narrow (Cin == 16) layout
+ * or a kernel size other than 1; kind outside {0, 1}; a non-finite lr; Adam with step < 1, a beta outside [0, 1), a negative eps
+ * or a null moment pointer.  RTOD_E_STATE before rtod_plan_load_weights. */
+typedef struct rtod_opt_step { int kind; float lr, beta1, beta2, eps; int step; } rtod_opt_step;
+int rtod_plan_step_conv(rtod_plan* plan, int layer, const rtod_opt_step* opt,
+                        float* weight_dev, float* bias_dev, const float* dw_dev, const float* db_dev,
+                        float* m_w_dev, float* v_w_dev, float* m_b_dev, float* v_b_dev, void* stream);
+/* (tests, debugging) The packed weight image as it is on the device now, copied to the host; SYNCHRONISES the device.  Size query
+ * as rtod_plan_pack_weights: *needed (if given) receives the image's floats, with out_host == NULL nothing else happens, else
+ * capacity_floats must cover it (RTOD_E_SIZE).  RTOD_E_STATE before rtod_plan_load_weights. */
+int rtod_plan_read_packed_weights(rtod_plan* plan, float* out_host, size_t capacity_floats, size_t* needed);
+
 #ifdef __cplusplus
 }
 #endif

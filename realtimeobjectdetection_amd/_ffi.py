@@ -36,6 +36,10 @@ class YoloHead(C.Structure):
     _fields_ = [("grid_h", C.c_int), ("grid_w", C.c_int), ("stride", C.c_int), ("n_anchors", C.c_int), ("anchors", C.c_int * 16)]
 
 
+class OptStep(C.Structure):
+    _fields_ = [("kind", C.c_int), ("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("step", C.c_int)]
+
+
 # name -> (restype, argtypes): every symbol include/rtod.h declares
 SIGNATURES = {
     "rtod_version": (C.c_int, []),
@@ -87,6 +91,9 @@ SIGNATURES = {
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "rtod_plan_head_layers": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int]),
     "rtod_plan_update_conv": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "rtod_plan_step_conv": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(OptStep), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rtod_plan_read_packed_weights": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
 }
 # ... and the entry points whose names hold a digit (the scan of the header for declared names reads lower-case letters and '_')
 SIGNATURES_DIGIT_NAMES = {

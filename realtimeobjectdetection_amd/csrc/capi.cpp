@@ -435,6 +435,21 @@ int rtod_plan_update_conv(rtod_plan* plan, int layer, const float* weight_oihw_h
     RTOD_GUARD_END
 }
 
+int rtod_plan_step_conv(rtod_plan* plan, int layer, const rtod_opt_step* opt, float* weight_dev, float* bias_dev, const float* dw_dev, const float* db_dev,
+                        float* m_w_dev, float* v_w_dev, float* m_b_dev, float* v_b_dev, void* stream) {
+    RTOD_GUARD_BEGIN
+    if (!plan) { set_error("step_conv: null plan"); return RTOD_E_ARG; }
+    return plan->p.step_conv(layer, opt, weight_dev, bias_dev, dw_dev, db_dev, m_w_dev, v_w_dev, m_b_dev, v_b_dev, (hipStream_t)stream);
+    RTOD_GUARD_END
+}
+
+int rtod_plan_read_packed_weights(rtod_plan* plan, float* out_host, size_t capacity_floats, size_t* needed) {
+    RTOD_GUARD_BEGIN
+    if (!plan) { set_error("read_packed_weights: null plan"); return RTOD_E_ARG; }
+    return plan->p.read_packed_weights(out_host, capacity_floats, needed);
+    RTOD_GUARD_END
+}
+
 int rtod_write_results_workspace(int batch, int n, size_t* bytes) {
     if (!bytes || batch < 1 || n < 1) { set_error("write_results_workspace: bad args"); return RTOD_E_ARG; }
     *bytes = nms_workspace_bytes(batch, n);

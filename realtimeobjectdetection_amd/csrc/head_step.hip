@@ -1,0 +1,153 @@
+// Optimiser step of one 1x1 convolution without BatchNorm (a detection head) fused with the re-pack of its block of the weight
+// image, gfx950.  One launch per conv, one workgroup per output channel o (plus one for the bias vector):
+//   pass 1  every thread walks c = tid, tid + 256, ...: reads the float32 master w[o][c], the gradient and (Adam) the moments,
+//           applies the step (opt_update: the fp32 sequence documented at rtod_plan_step_conv in include/rtod.h), writes master
+//           and moments back and keeps the largest |w'| it saw (as integer bits: order-preserving for finite floats, exact);
+//   reduce  the workgroup's maximum through LDS (a max is order-independent, so this is exact);
+//   pass 2  the same thread re-reads the masters it wrote and places them where Plan::pack_conv (plan_weights.cpp) would:
+//           fp32 plans   panel[o * Kpad + c] = w'
+//           split plans  e = 13 - exponent(max|w'|) held to -24 .. 40 (0 for an all-zero channel), inv[o] = 2^-e / ACT_SCALE_F16S3,
+//                        vs = w' * 2^e (exact), hi = f16_rn(vs), lo = f16_rn(vs - hi) at half ((c / 32) * Npad + o) * 32 + c % 32
+//                        of the hi and lo planes.
+// f32 -> f16 is the host's integer routine (f32_to_f16_rn), restated here: round to nearest even, subnormal halves kept, values at
+// or below 2^-25 to (signed) zero — independent of the denormal mode the library is built with.  Nothing outside channel rows
+// [0, Cout) and columns [0, Cin) of this conv's block is written: padding channels, padding K and other convs keep their bits.
+// Plain vector stores only; no atomics; bit-identical from call to call.  Built with -ffp-contract=off and correctly rounded
+// fp32 divide / sqrt (Makefile: PARITY_FLAGS), so every operator below is one IEEE operation with one rounding and the only
+// fused multiply-adds are the ones written as fmaf.
+#include "rtod_internal.h"
+
+namespace rtod {
+
+__device__ __forceinline__ uint32_t f32_bits(float f) { return __float_as_uint(f); }
+
+__device__ __forceinline__ uint32_t f32_to_f16_rn_dev(float f) {
+    uint32_t x = f32_bits(f);
+    const uint32_t sign = (x >> 16) & 0x8000u;
+    x &= 0x7FFFFFFFu;
+    if (x >= 0x7F800000u) return sign | (x > 0x7F800000u ? 0x7E00u : 0x7C00u);
+    if (x >= 0x477FF000u) return sign | 0x7C00u;
+    if (x < 0x33000001u) return sign;
+    const int e = (int)(x >> 23) - 127;
+    const uint32_t m = (x & 0x7FFFFFu) | 0x800000u;
+    const int shift = (e < -14) ? (13 + (-14 - e)) : 13;                     // <= 24 here: e >= -25
+    uint32_t half_m = m >> shift;
+    const uint32_t rem = m & ((1u << shift) - 1u), halfway = 1u << (shift - 1);
+    if (rem > halfway || (rem == halfway && (half_m & 1u))) ++half_m;
+    const uint32_t out = (e < -14) ? half_m : (((uint32_t)(e + 15) << 10) + (half_m - 0x400u));
+    return sign | out;
+}
+
+__device__ __forceinline__ float f16_to_f32_dev(uint32_t h) {
+    const uint32_t sign = (h & 0x8000u) << 16;
+    const uint32_t e = (h >> 10) & 0x1Fu, m = h & 0x3FFu;
+    uint32_t x;
+    if (e == 0) x = f32_bits((float)m * 5.9604644775390625e-8f);    // m * 2^-24, exact and normal in fp32
+    else if (e == 31) x = m ? 0x7FC00000u : 0x7F800000u;
+    else x = ((e + 112u) << 23) | (m << 13);
+    return __uint_as_float(x | sign);
+}
+
+struct StepArgs {
+    int kind;                       // 0 SGD, 1 Adam
+    float lr;                       // SGD: (float)lr.  Adam: (float)(lr / (1 - beta1^t))
+    float beta2, omb1, omb2;        // (float)beta2, (float)(1 - beta1), (float)(1 - beta2)
+    float bc2_sqrt, eps;            // (float)sqrt(1 - beta2^t), (float)eps
+    int cout, cin;
+    int split;                      // 0: fp32 panel, 1: f16 hi / lo planes
+    int Kpad, Npad;
+    float* w; float* b;             // masters
+    const float* dw; const float* db;
+    float* m_w; float* v_w; float* m_b; float* v_b;
+    float* panel;                   // fp32 plans: [Npad][Kpad]
+    uint16_t* hi; uint16_t* lo;     // split plans: [Kpad / 32][Npad][32] halves each
+    float* inv;                     // split plans: [Npad]
+    float* bias;                    // [Npad]
+};
+
+// one element: (w, g, m, v) -> w'; m, v updated in place (Adam)
+__device__ __forceinline__ float opt_update(const StepArgs& a, float w, float g, float& m, float& v) {
+#pragma clang fp contract(off)
+    if (a.kind == 0) { const float d = a.lr * g; return w - d; }
+    const float gm = g - m;
+    m = __builtin_fmaf(gm, a.omb1, m);
+    const float gg = g * g, bv = a.beta2 * v;
+    v = __builtin_fmaf(gg, a.omb2, bv);
+    const float root = __builtin_sqrtf(v) / a.bc2_sqrt;
+    const float denom = root + a.eps;
+    const float ratio = m / denom;
+    return __builtin_fmaf(-a.lr, ratio, w);
+}
+
+__global__ __launch_bounds__(256)
+void head_step_kernel(StepArgs a) {
+    __shared__ uint32_t smax[256];
+    const int tid = threadIdx.x;
+    const int o = blockIdx.x;
+    if (o == a.cout) {                                              // the bias vector: masters, moments and the image's copy
+        for (int q = tid; q < a.cout; q += 256) {
+            float m = 0.f, v = 0.f;
+            if (a.kind == 1) { m = a.m_b[q]; v = a.v_b[q]; }
+            const float nb = opt_update(a, a.b[q], a.db[q], m, v);
+            if (a.kind == 1) { a.m_b[q] = m; a.v_b[q] = v; }
+            a.b[q] = nb;
+            a.bias[q] = nb;
+        }
+        return;
+    }
+    const int64_t row = (int64_t)o * a.cin;
+    uint32_t mx = 0;
+    for (int c = tid; c < a.cin; c += 256) {
+        float m = 0.f, v = 0.f;
+        if (a.kind == 1) { m = a.m_w[row + c]; v = a.v_w[row + c]; }
+        const float nw = opt_update(a, a.w[row + c], a.dw[row + c], m, v);
+        if (a.kind == 1) { a.m_w[row + c] = m; a.v_w[row + c] = v; }
+        a.w[row + c] = nw;
+        const uint32_t ab = f32_bits(nw) & 0x7FFFFFFFu;
+        if (ab <= 0x7F800000u && ab > mx) mx = ab;                  // a NaN takes no part (std::max on the host keeps the other operand)
+    }
+    if (!a.split) {
+        for (int c = tid; c < a.cin; c += 256) a.panel[(int64_t)o * a.Kpad + c] = a.w[row + c];
+        return;
+    }
+    smax[tid] = mx;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (tid < s) smax[tid] = max(smax[tid], smax[tid + s]);
+        __syncthreads();
+    }
+    mx = smax[0];
+    // frexp(mx) = (f, ex), f in [0.5, 1): ex = floor(log2 mx) + 1; e = 13 - ex.  A subnormal fp32 maximum gives e > 40 either way
+    int e = 0;
+    if (mx != 0) e = 12 - ((int)(mx >> 23) - 127);
+    e = max(-24, min(40, e));
+    const float ps = __uint_as_float((uint32_t)(127 + e) << 23);            // 2^e
+    if (tid == 0) a.inv[o] = __uint_as_float((uint32_t)(127 - e - 3) << 23); // 2^-e / 8 (ACT_SCALE_F16S3 = 8)
+    for (int c = tid; c < a.cin; c += 256) {
+        const float vs = a.w[row + c] * ps;                         // exact: a power of two
+        const uint32_t h = f32_to_f16_rn_dev(vs);
+        const float rest = vs - f16_to_f32_dev(h);
+        const uint32_t l = f32_to_f16_rn_dev(rest);
+        const int64_t idx = ((int64_t)(c >> 5) * a.Npad + o) * 32 + (c & 31);
+        a.hi[idx] = (uint16_t)h;
+        a.lo[idx] = (uint16_t)l;
+    }
+}
+
+static_assert(ACT_SCALE_F16S3 == 8.0f, "head_step_kernel builds 2^-e / ACT_SCALE_F16S3 from the exponent");
+
+int launch_head_step(const HeadStepLaunch& h, hipStream_t s) {
+    StepArgs a;
+    a.kind = h.kind; a.lr = h.lr; a.beta2 = h.beta2; a.omb1 = h.omb1; a.omb2 = h.omb2; a.bc2_sqrt = h.bc2_sqrt; a.eps = h.eps;
+    a.cout = h.cout; a.cin = h.cin; a.split = h.split; a.Kpad = h.Kpad; a.Npad = h.Npad;
+    a.w = h.w; a.b = h.b; a.dw = h.dw; a.db = h.db; a.m_w = h.m_w; a.v_w = h.v_w; a.m_b = h.m_b; a.v_b = h.v_b;
+    a.panel = h.blk;
+    a.hi = reinterpret_cast<uint16_t*>(h.blk);
+    a.lo = reinterpret_cast<uint16_t*>(h.blk + h.lo_off);
+    a.inv = h.blk + h.inv_off;
+    a.bias = h.blk + h.bias_off;
+    hipLaunchKernelGGL(head_step_kernel, dim3((unsigned)(h.cout + 1)), dim3(256), 0, s, a);
+    return hip_fail(hipGetLastError(), "head_step launch");
+}
+
+}  // namespace rtod

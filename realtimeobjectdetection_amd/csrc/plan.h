@@ -78,7 +78,7 @@ struct PackedConv {
 };
 
 // One struct, defined over five files by concern: plan_cfg.cpp (parse, resolve_shapes: no HIP call), plan_build.cpp (options, buffer
-// planning, weight layout, describe), plan_weights.cpp (pack_conv, pack_weights, load_weights, update_conv), plan_tiles.cpp (which kernel variant a conv
+// planning, weight layout, describe), plan_weights.cpp (pack_conv, pack_weights, load_weights, update_conv, step_conv), plan_tiles.cpp (which kernel variant a conv
 // launch runs, autotune), plan_forward.cpp (the launch list on a stream, launch records).
 struct Plan {
     int height = 0, width = 0, max_batch = 0, device = 0;
@@ -151,6 +151,10 @@ struct Plan {
     int64_t conv_block_floats(size_t slot) const;                                   // floats of that block: every range of the conv, padding to the next conv included
     int load_weights(const float* w, size_t n);
     int update_conv(int layer, const float* weight_oihw, const float* bias);        // re-pack and upload one conv without BatchNorm (rtod_plan_update_conv)
+    int replaceable_conv(const char* who, int layer, size_t& slot) const;            // the conv's slot, or why it cannot be replaced alone
+    int step_conv(int layer, const rtod_opt_step* opt, float* weight, float* bias, const float* dw, const float* db,
+                  float* m_w, float* v_w, float* m_b, float* v_b, hipStream_t s);   // optimiser step + re-pack on the stream (rtod_plan_step_conv)
+    int read_packed_weights(float* out, size_t capacity, size_t* needed) const;     // the device image back on the host (synchronises)
     bool feeds_yolo(int layer) const { return layers[layer].type == LT_CONV && layer + 1 < (int)layers.size() && layers[layer + 1].type == LT_YOLO; }
     int forward(const float* x, int batch, float* out, hipStream_t s, float* launch_ms, bool tune = false);
     // the launches of one LK_CONV / LK_STEM step of forward, in order

@@ -4,6 +4,8 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstdio>
+#include <cstdlib>
 #include <cstring>
 
 namespace rtod {
@@ -139,21 +141,28 @@ int Plan::pack_weights(const float* w, size_t n, std::vector<float>& packed) con
     return RTOD_OK;
 }
 
+// The slot in `convs` of a conv whose weights may be replaced alone (update_conv, step_conv): no BatchNorm, no fused pointwise pair.
+int Plan::replaceable_conv(const char* who, int layer, size_t& slot) const {
+    if (layer < 0 || layer >= (int)layers.size() || layers[layer].type != LT_CONV) { set_error("%s: layer %d is not a convolution", who, layer); return RTOD_E_ARG; }
+    if (layers[layer].bn) { set_error("%s: layer %d has BatchNorm (only convs without it can be replaced)", who, layer); return RTOD_E_ARG; }
+    slot = convs.size();
+    for (const auto& l : launches) {
+        if ((l.kind != LK_CONV && l.kind != LK_STEM) || l.layer != layer || l.conv_slot < 0) continue;
+        if (l.pw_guest >= 0 || l.pw_host >= 0) { set_error("%s: layer %d is part of a fused pointwise pair", who, layer); return RTOD_E_ARG; }
+        slot = (size_t)l.conv_slot;
+    }
+    if (slot >= convs.size()) { set_error("%s: layer %d has no packed weights", who, layer); return RTOD_E_ARG; }
+    return RTOD_OK;
+}
+
 // One conv without BatchNorm re-packed from (weight OIHW, bias) and its block alone copied to the device: the bits a full
 // load_weights of the edited stream gives, since both go through pack_conv.  Synchronises the device (a forward in flight may
 // still read the old block).
 int Plan::update_conv(int layer, const float* weight_oihw, const float* bias) {
     if (!weight_oihw || !bias) { set_error("update_conv: null pointer"); return RTOD_E_ARG; }
-    if (layer < 0 || layer >= (int)layers.size() || layers[layer].type != LT_CONV) { set_error("update_conv: layer %d is not a convolution", layer); return RTOD_E_ARG; }
+    size_t slot = 0;
+    if (int rc = replaceable_conv("update_conv", layer, slot)) return rc;
     const Layer& L = layers[layer];
-    if (L.bn) { set_error("update_conv: layer %d has BatchNorm (only convs without it can be replaced)", layer); return RTOD_E_ARG; }
-    size_t slot = convs.size();
-    for (const auto& l : launches) {
-        if ((l.kind != LK_CONV && l.kind != LK_STEM) || l.layer != layer || l.conv_slot < 0) continue;
-        if (l.pw_guest >= 0 || l.pw_host >= 0) { set_error("update_conv: layer %d is part of a fused pointwise pair", layer); return RTOD_E_ARG; }
-        slot = (size_t)l.conv_slot;
-    }
-    if (slot >= convs.size()) { set_error("update_conv: layer %d has no packed weights", layer); return RTOD_E_ARG; }
     if (!weights_loaded || !d_weights) { set_error("update_conv: call rtod_plan_load_weights first"); return RTOD_E_STATE; }
     const PackedConv& pc = convs[slot];
     const int64_t nw = (int64_t)L.cout * L.cin * L.size * L.size;
@@ -166,6 +175,69 @@ int Plan::update_conv(int layer, const float* weight_oihw, const float* bias) {
     RTOD_HIP(hipDeviceSynchronize());
     RTOD_HIP(hipMemcpy(d_weights + pc.w_off, blk.data(), sizeof(float) * blk.size(), hipMemcpyHostToDevice));
     RTOD_HIP(hipDeviceSynchronize());
+    return RTOD_OK;
+}
+
+// A float field of rtod_opt_step read as the shortest decimal that rounds to it (0.999f means 0.999, as it prints): 1 - beta2 taken
+// from the float's own value would be off by 2^-25 / 0.001, hundreds of fp32 ulps of every v'.
+static double shortest_decimal(float f) {
+    if (!std::isfinite(f)) return (double)f;
+    char buf[40];
+    for (int prec = 1; prec <= 9; ++prec) {
+        snprintf(buf, sizeof buf, "%.*g", prec, (double)f);
+        const double d = strtod(buf, nullptr);
+        if ((float)d == f) return d;
+    }
+    return (double)f;
+}
+
+// The device twin of update_conv for a 1x1 conv: one kernel (head_step.hip) applies the optimiser step to the caller's float32
+// masters and writes the conv's ranges of the image where pack_conv would, bit for bit.  Enqueues only: every refusal is decided
+// before anything touches the device, and the scalars of the step are derived here in double and passed as floats.
+int Plan::step_conv(int layer, const rtod_opt_step* opt, float* weight, float* bias, const float* dw, const float* db,
+                    float* m_w, float* v_w, float* m_b, float* v_b, hipStream_t s) {
+    if (!opt || !weight || !bias || !dw || !db) { set_error("step_conv: null pointer"); return RTOD_E_ARG; }
+    size_t slot = 0;
+    if (int rc = replaceable_conv("step_conv", layer, slot)) return rc;
+    const Layer& L = layers[layer];
+    const PackedConv& pc = convs[slot];
+    if (L.size != 1 || pc.stem || pc.stem16 || pc.narrow) { set_error("step_conv: layer %d is not a 1x1 conv of the generic layouts (size %d%s)", layer, L.size, pc.narrow ? ", narrow" : pc.stem ? ", stem" : ""); return RTOD_E_ARG; }
+    if (pc.Kpad < L.cin || L.cout > pc.Npad || (pc.split && L.cin % 32 != 0)) { set_error("step_conv: layer %d has an unexpected packed layout", layer); return RTOD_E_ARG; }
+    if (opt->kind != 0 && opt->kind != 1) { set_error("step_conv: kind %d (0 = SGD, 1 = Adam)", opt->kind); return RTOD_E_ARG; }
+    if (!std::isfinite(opt->lr)) { set_error("step_conv: lr is not finite"); return RTOD_E_ARG; }
+    HeadStepLaunch h;
+    h.kind = opt->kind;
+    h.lr = opt->lr;
+    if (opt->kind == 1) {
+        if (opt->step < 1) { set_error("step_conv: Adam needs the 1-based step count, got %d", opt->step); return RTOD_E_ARG; }
+        if (!(opt->beta1 >= 0.f && opt->beta1 < 1.f) || !(opt->beta2 >= 0.f && opt->beta2 < 1.f)) { set_error("step_conv: Adam betas must lie in [0, 1)"); return RTOD_E_ARG; }
+        if (!(opt->eps >= 0.f)) { set_error("step_conv: Adam eps must be >= 0"); return RTOD_E_ARG; }
+        if (!m_w || !v_w || !m_b || !v_b) { set_error("step_conv: Adam needs the four moment buffers"); return RTOD_E_ARG; }
+        const double b1 = shortest_decimal(opt->beta1), b2 = shortest_decimal(opt->beta2);
+        h.lr = (float)(shortest_decimal(opt->lr) / (1.0 - std::pow(b1, (double)opt->step)));
+        h.bc2_sqrt = (float)std::sqrt(1.0 - std::pow(b2, (double)opt->step));
+        h.beta2 = opt->beta2;
+        h.omb1 = (float)(1.0 - b1);
+        h.omb2 = (float)(1.0 - b2);
+        h.eps = opt->eps;
+    }
+    if (!weights_loaded || !d_weights) { set_error("step_conv: call rtod_plan_load_weights first"); return RTOD_E_STATE; }
+    h.cout = L.cout; h.cin = L.cin; h.split = pc.split ? 1 : 0; h.Kpad = pc.Kpad; h.Npad = pc.Npad;
+    h.w = weight; h.b = bias; h.dw = dw; h.db = db; h.m_w = m_w; h.v_w = v_w; h.m_b = m_b; h.v_b = v_b;
+    h.blk = d_weights + pc.w_off;
+    h.lo_off = pc.wl_off - pc.w_off; h.inv_off = pc.s_off - pc.w_off; h.bias_off = pc.b_off - pc.w_off;
+    return launch_head_step(h, s);
+}
+
+// The device image as it is now (tests, debugging): synchronises.
+int Plan::read_packed_weights(float* out, size_t capacity, size_t* needed) const {
+    if (needed) *needed = (size_t)packed_floats;
+    if (!out) return RTOD_OK;
+    if (capacity < (size_t)packed_floats) { set_error("read_packed_weights: capacity %zu < %lld floats", capacity, (long long)packed_floats); return RTOD_E_SIZE; }
+    if (!weights_loaded || !d_weights) { set_error("read_packed_weights: call rtod_plan_load_weights first"); return RTOD_E_STATE; }
+    RTOD_HIP(hipSetDevice(device));
+    RTOD_HIP(hipDeviceSynchronize());
+    RTOD_HIP(hipMemcpy(out, d_weights, sizeof(float) * (size_t)packed_floats, hipMemcpyDeviceToHost));
     return RTOD_OK;
 }
 

@@ -367,5 +367,18 @@ int64_t wgrad_slice_len(int64_t K);
 size_t wgrad_workspace_bytes(int batch, int cout, int cin, int pixels);
 int launch_conv1x1_wgrad(const float* dz, const float* x, int batch, int cout, int cin, int pixels, float* dw, float* db,
                          void* ws, size_t ws_bytes, hipStream_t s);
+// optimiser step of one 1x1 conv without BatchNorm fused with the re-pack of its block of the weight image (head_step.hip).
+// The scalars are what the host derived in double (Plan::step_conv); blk = d_weights + the conv's w_off, the offsets in floats
+struct HeadStepLaunch {
+    int kind = 0;                                   // 0 SGD, 1 Adam
+    float lr = 0.f, beta2 = 0.f, omb1 = 0.f, omb2 = 0.f, bc2_sqrt = 1.f, eps = 0.f;
+    int cout = 0, cin = 0, split = 0, Kpad = 0, Npad = 0;
+    float *w = nullptr, *b = nullptr;
+    const float *dw = nullptr, *db = nullptr;
+    float *m_w = nullptr, *v_w = nullptr, *m_b = nullptr, *v_b = nullptr;
+    float* blk = nullptr;
+    int64_t lo_off = 0, inv_off = 0, bias_off = 0;
+};
+int launch_head_step(const HeadStepLaunch& h, hipStream_t s);
 
 }  // namespace rtod

@@ -130,6 +130,7 @@ class Darknet(nn.Module):
         self._stats_version = 0             # running_mean / running_var updates of training-mode forwards (eval plans fold them)
         self._plan_weights_version = -1
         self._info = None
+        self._stepped = {}                  # step_conv: {conv layer: (weight master, bias master)} the module's parameters lag behind
 
     # ------------------------------------------------------------------ reference getters
     def get_blocks(self) -> list:
@@ -197,6 +198,7 @@ class Darknet(nn.Module):
 
     def load_weight_stream(self, w: np.ndarray):
         ptr = 0
+        self._stepped.clear()                                     # every parameter is replaced: nothing lags any more
         with torch.no_grad():
             for m in self.module_list:
                 conv = bn = None
@@ -219,7 +221,9 @@ class Darknet(nn.Module):
         return ptr
 
     def weight_stream(self) -> np.ndarray:
-        """Current parameters as a ``.weights`` float payload (host, float32)."""
+        """Current parameters as a ``.weights`` float payload (host, float32).  Convs stepped on the device (``step_conv``) are
+        brought up to date first (``sync_stepped_parameters``), so the stream — and every re-pack, which reads it — holds them."""
+        self.sync_stepped_parameters()
         parts = []
         for m in self.module_list:
             conv = bn = None
@@ -238,12 +242,19 @@ class Darknet(nn.Module):
         return np.concatenate([p.detach().float().cpu().numpy().reshape(-1) for p in parts]).astype(np.float32, copy=False)
 
     def load_state_dict(self, *args, **kwargs):
+        self.sync_stepped_parameters()                            # a partial (strict=False) dict keeps the stepped convs it does not name
         r = super().load_state_dict(*args, **kwargs)
         self._weights_version += 1
         return r
 
+    def state_dict(self, *args, **kwargs):
+        self.sync_stepped_parameters()
+        return super().state_dict(*args, **kwargs)
+
     def invalidate_weights(self):
-        """Call after mutating parameters in place so the next forward re-packs them."""
+        """Call after mutating parameters in place so the next forward re-packs them.  Convs stepped on the device are brought up
+        to date first (mutate after this call's predecessors, not between ``step_conv`` and it: the masters would win)."""
+        self.sync_stepped_parameters()
         self._weights_version += 1
 
     # ------------------------------------------------------------------ detection heads
@@ -274,14 +285,77 @@ class Darknet(nn.Module):
         with torch.no_grad():
             conv.weight.copy_(w)
             conv.bias.copy_(b)
-        batch_bn = bool(self.training and not self.bn_running_stats_in_train)
-        current = (self._weights_version, 0 if batch_bn else self._stats_version)
-        if self._plan is not None and self._plan_weights_version == current:
+        self._stepped.pop(int(layer), None)                       # the parameters are current again
+        if self._plan_is_current():
             wh = np.ascontiguousarray(w.cpu().numpy())
             bh = np.ascontiguousarray(b.cpu().numpy())
             with torch.cuda.device(self._plan_key[2]):
                 _ffi.check(_ffi.lib().rtod_plan_update_conv(self._plan, int(layer), wh.ctypes.data_as(C.c_void_p), bh.ctypes.data_as(C.c_void_p)))
         # the plan's weight version stays current: parameters and plan agree again (a plan that was stale before still re-packs)
+
+    def _plan_is_current(self) -> bool:
+        """A plan exists and holds the packed image of the parameters as they are (no re-pack is due at the next forward)."""
+        batch_bn = bool(self.training and not self.bn_running_stats_in_train)
+        return self._plan is not None and self._plan_weights_version == (self._weights_version, 0 if batch_bn else self._stats_version)
+
+    def step_conv(self, layer: int, opt, weight, bias, dw, db, moments=None) -> None:
+        """One optimiser step of a detection-head conv on the current stream (rtod_plan_step_conv): ``weight`` [Cout,Cin,1,1] and
+        ``bias`` [Cout] are the caller's float32 device masters, updated IN PLACE from ``dw`` / ``db`` (``conv1x1_wgrad_async``)
+        and, for Adam, ``moments = (exp_avg_w, exp_avg_sq_w, exp_avg_b, exp_avg_sq_b)``; the same kernel re-packs the conv's block
+        of the plan's weight image in place.  ``opt``: an ``_ffi.OptStep`` or a mapping with its fields (kind 0 SGD / 1 Adam, lr,
+        beta1, beta2, eps, step).  Nothing synchronises, nothing is allocated: legal under stream capture.  Needs a loaded plan
+        that is current (a forward has run since the parameters last changed).  The module's ``conv.weight`` / ``conv.bias`` are
+        NOT touched and lag behind from here on; ``weight_stream()``, ``state_dict()``, ``invalidate_weights()`` and every
+        re-pack bring them up to date from these masters first (``sync_stepped_parameters``), reading ``conv.weight`` directly
+        does not."""
+        layer = int(layer)
+        if not self._plan_is_current():
+            raise RuntimeError("Darknet.step_conv: no loaded plan holds the current parameters; run a forward first")
+        dev = torch.device("cuda", self._plan_key[2])
+        if moments is not None and len(moments) != 4:
+            raise ValueError("Darknet.step_conv: moments = (exp_avg_w, exp_avg_sq_w, exp_avg_b, exp_avg_sq_b)")
+        like_w = [weight, dw] + ([moments[0], moments[1]] if moments is not None else [])
+        like_b = [bias, db] + ([moments[2], moments[3]] if moments is not None else [])
+        for t in like_w + like_b:
+            if not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != torch.float32 or not t.is_contiguous():
+                raise ValueError("Darknet.step_conv: every tensor must be a contiguous float32 tensor on %s" % dev)
+        if any(t.numel() != weight.numel() for t in like_w) or any(t.numel() != bias.numel() for t in like_b):
+            raise ValueError("Darknet.step_conv: gradients and moments must have the sizes of weight %s and bias %s" % (tuple(weight.shape), tuple(bias.shape)))
+        conv = next((sub for name, sub in self.module_list[layer].named_children() if name.startswith("conv_")), None) if 0 <= layer < len(self.module_list) else None
+        if conv is None or conv.bias is None or tuple(weight.shape) != tuple(conv.weight.shape) or tuple(bias.shape) != tuple(conv.bias.shape):
+            raise ValueError("Darknet.step_conv: layer %d is not a convolution without BatchNorm with weight %s and bias %s" % (layer, tuple(weight.shape), tuple(bias.shape)))
+        if not isinstance(opt, _ffi.OptStep):
+            opt = _ffi.OptStep(int(opt["kind"]), float(opt["lr"]), float(opt.get("beta1", 0.0)), float(opt.get("beta2", 0.0)), float(opt.get("eps", 0.0)), int(opt.get("step", 0)))
+        ptr = lambda t: C.c_void_p(t.data_ptr())
+        mom = [ptr(t) for t in moments] if moments is not None else [None] * 4
+        with torch.cuda.device(dev):
+            _ffi.check(_ffi.lib().rtod_plan_step_conv(self._plan, layer, C.byref(opt), ptr(weight), ptr(bias), ptr(dw), ptr(db), *mom,
+                                                      C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        self._stepped[layer] = (weight, bias)
+
+    def sync_stepped_parameters(self) -> None:
+        """Copy the masters of every conv ``step_conv`` has stepped into the module's ``conv.weight`` / ``conv.bias`` (waits for the
+        steps in flight).  The plan's image already holds them, so it stays valid: no re-pack follows."""
+        if not self._stepped:
+            return
+        with torch.no_grad():
+            for layer, (w, b) in self._stepped.items():
+                conv = next(sub for name, sub in self.module_list[layer].named_children() if name.startswith("conv_"))
+                conv.weight.copy_(w)
+                conv.bias.copy_(b)
+        self._stepped.clear()
+
+    def packed_weights(self) -> np.ndarray:
+        """The plan's packed weight image as it is on the device now, as uint32 words (rtod_plan_read_packed_weights; tests and
+        debugging; synchronises)."""
+        if self._plan is None:
+            raise RuntimeError("Darknet.packed_weights: no plan yet; run a forward first")
+        need = C.c_size_t()
+        _ffi.check(_ffi.lib().rtod_plan_read_packed_weights(self._plan, None, 0, C.byref(need)))
+        out = np.zeros(need.value, np.float32)
+        with torch.cuda.device(self._plan_key[2]):
+            _ffi.check(_ffi.lib().rtod_plan_read_packed_weights(self._plan, out.ctypes.data_as(C.c_void_p), out.size, None))
+        return out.view(np.uint32)
 
     # ------------------------------------------------------------------ plan
     def _destroy_plan(self):

@@ -4,8 +4,10 @@ The FORWARD VALUE of the loss: targets from ground-truth boxes (``target_creator
 (``darknet_loss``), the last step of ``feed_forward_through_model`` (train.py:412-425); and the first layer of its backward pass:
 the gradient with respect to the raw head maps and from it ``dW``, ``db`` of the detection-head convs (the 1x1 convs without
 BatchNorm in front of the [yolo] blocks), with a plain SGD step on them — fine-tuning the heads with the backbone frozen.  Backward
-through the trunk, BatchNorm gradients, other optimisers, epochs and data loaders are out of scope.  Same names and
-return conventions as the reference:
+through the trunk, BatchNorm gradients, weight decay, epochs and data loaders are out of scope.  The reference's
+optimiser — ``optim.Adam(lr=1e-2)``, train.py:57 — runs on the heads as one kernel per conv that also re-packs the conv's weights in
+place (``HeadOptimizer``, ``feed_forward_through_model``): that path never synchronises.  Same names and return conventions as the
+reference:
 
 * ``DarknetTrainer.anchor_fit(box, anchors)``, ``target_layer(bboxes, scale, anchors)``     host mirrors, train.py:167-209
 * ``DarknetTrainer.target_creator(bndbox) -> (target, mask)``                               train.py:129-149, one launch sequence
@@ -14,6 +16,8 @@ return conventions as the reference:
 * ``DarknetTrainer.forward_loss(frames_or_x, bndbox)``                                      forward under ``train_mode()`` + loss
 * ``DarknetTrainer.head_gradients(frames_or_x, bndbox) -> (loss, {conv_layer: (dW, db)})``  (new) what ``loss.backward()`` leaves on the heads
 * ``DarknetTrainer.head_step(frames_or_x, bndbox, lr)``                                     (new) ``w -= lr * dW``, ``b -= lr * db`` on the heads
+* ``DarknetTrainer.feed_forward_through_model(batch_data, bndbox)``                         train.py:412-425: forward, loss, backward, ``optimizer`` step
+* ``DarknetTrainer.optimizer`` (``HeadOptimizer``: Adam or SGD on the heads), ``sync_parameters()``    train.py:57
 
 The reference's behaviour is kept as it is: only boxes whose class-0 slot is 1 and whose sides are at least
 ``min_box_size`` (24) count, ``anchor_fit`` compares a box with a square of the anchor's WIDTH, target slot 0 holds the y fraction
@@ -23,6 +27,7 @@ outside a head's grid is skipped there and sets bit 0 of ``status``.  Loss kerne
 """
 import ctypes as C
 import math
+import weakref
 
 import numpy as np
 import torch
@@ -188,10 +193,63 @@ def model_heads(model, height=None, width=None):
     return heads, classes
 
 
+class HeadOptimizer:
+    """Adam (the reference's ``optim.Adam(self.darknet.parameters(), lr=1e-2)``, train.py:57: no weight decay, no amsgrad) or plain
+    SGD on the detection-head convs, run by ``Darknet.step_conv``: one kernel per conv that steps the float32 masters and re-packs
+    the conv's block of the plan's weight image in place; nothing synchronises.
+
+    ``state``: ``{conv_layer: {"step": t, "weight", "bias", "exp_avg", "exp_avg_sq", "exp_avg_bias", "exp_avg_sq_bias"}}`` — the
+    masters (the very tensors of ``DarknetTrainer._head_masters``, so ``head_step`` and this path can be mixed), torch's moment
+    names and the number of steps taken; SGD keeps no moments.  ``lr`` may be changed between steps."""
+
+    KINDS = {"sgd": 0, "adam": 1}
+
+    def __init__(self, kind="adam", lr=1e-2, betas=(0.9, 0.999), eps=1e-8):
+        if kind not in self.KINDS:
+            raise ValueError("HeadOptimizer: kind must be 'adam' or 'sgd', got %r" % (kind,))
+        self.kind, self.lr, self.betas, self.eps = kind, float(lr), (float(betas[0]), float(betas[1])), float(eps)
+        self.state = {}
+        self._trainer = None               # weak reference to the DarknetTrainer this optimiser is the ``optimizer`` of
+
+    def _entry(self, layer, masters):
+        st = self.state.get(layer)
+        if st is None or st["weight"] is not masters[0] or st["bias"] is not masters[1]:
+            st = self.state[layer] = {"step": 0 if st is None else st["step"], "weight": masters[0], "bias": masters[1]}
+        if self.kind == "adam" and "exp_avg" not in st:
+            st.update(exp_avg=torch.zeros_like(masters[0]), exp_avg_sq=torch.zeros_like(masters[0]),
+                      exp_avg_bias=torch.zeros_like(masters[1]), exp_avg_sq_bias=torch.zeros_like(masters[1]))
+        return st
+
+    def step(self, model, masters, grads):
+        """One step of every conv in ``grads`` (``{conv_layer: (dW, db)}``) on ``masters`` (``{conv_layer: [weight, bias]}``)."""
+        for layer, (dw, db) in grads.items():
+            st = self._entry(layer, masters[layer])
+            st["step"] += 1
+            opt = _ffi.OptStep(self.KINDS[self.kind], self.lr, self.betas[0], self.betas[1], self.eps, st["step"])
+            moments = (st["exp_avg"], st["exp_avg_sq"], st["exp_avg_bias"], st["exp_avg_sq_bias"]) if self.kind == "adam" else None
+            model.step_conv(layer, opt, st["weight"], st["bias"], dw, db, moments)
+
+    def state_dict(self):
+        """``{conv_layer: {"step": int, name: tensor}}`` of the masters and moments (the tensors themselves, as torch's does)."""
+        return {layer: dict(st) for layer, st in self.state.items()}
+
+    def load_state_dict(self, state):
+        """Take copies of a ``state_dict()``'s tensors.  As a trainer's ``optimizer`` it also makes the masters that trainer's and
+        hands them to its model (``Darknet.update_conv`` per conv: synchronises), so a second trainer continues where the first
+        one's state was taken."""
+        self.state = {int(layer): {k: (v.detach().clone() if isinstance(v, torch.Tensor) else int(v)) for k, v in st.items()} for layer, st in state.items()}
+        trainer = self._trainer() if self._trainer is not None else None
+        if trainer is not None:
+            trainer._head_masters = {layer: [st["weight"], st["bias"]] for layer, st in self.state.items()}
+            for layer, (w, b) in trainer._head_masters.items():
+                trainer.darknet.update_conv(layer, w, b)
+
+
 class DarknetTrainer:
     """The loss side of the reference's trainer around a built ``Darknet`` (no optimiser, no epochs, no data loaders).
 
-    Attributes (the reference's): darknet, resolution, num_classes, criterion, TINY, history.  New: ``heads`` (from the cfg),
+    Attributes (the reference's): darknet, resolution, num_classes, criterion, TINY, history, optimizer (a ``HeadOptimizer``: the
+    heads alone are trained).  New: ``heads`` (from the cfg),
     ``min_box_size`` (the literal 24 of target_layer), ``status`` (device int32 [1]: bit 0 = a box's cell lay outside a grid and
     was skipped; OR-ed by every call, read it when you synchronise anyway), ``last_components`` (device float64 [6] of the
     last loss: total, xy, wh, obj, noobj, cls)."""
@@ -212,7 +270,17 @@ class DarknetTrainer:
         self.history = dict()
         self.status = None
         self.last_components = None
-        self._head_masters = None          # head_step: {conv_layer: [weight, bias]} float32 device masters of the head convs
+        self._head_masters = None          # head_step / optimizer: {conv_layer: [weight, bias]} float32 device masters of the head convs
+        self.optimizer = HeadOptimizer()
+
+    @property
+    def optimizer(self):
+        return self._optimizer
+
+    @optimizer.setter
+    def optimizer(self, opt):
+        opt._trainer = weakref.ref(self)
+        self._optimizer = opt
 
     # ------------------------------------------------------------------ host mirrors (small and exact)
     @staticmethod
@@ -347,14 +415,37 @@ class DarknetTrainer:
         from before the step (0-dim float32 device tensor)."""
         loss, grads = self.head_gradients(frames_or_x, bndbox)
         model = self.darknet
-        if self._head_masters is None:
-            self._head_masters = {}
-            for layer in grads:
-                conv = next(sub for name, sub in model.module_list[layer].named_children() if name.startswith("conv_"))
-                self._head_masters[layer] = [conv.weight.detach().to(loss.device, torch.float32).clone(), conv.bias.detach().to(loss.device, torch.float32).clone()]
+        masters = self._masters(grads, loss.device)
         for layer, (dw, db) in grads.items():
-            w, b = self._head_masters[layer]
+            w, b = masters[layer]
             w.sub_(dw * float(lr))
             b.sub_(db * float(lr))
             model.update_conv(layer, w, b)
         return loss
+
+    def _masters(self, layers, dev):
+        """The float32 device masters of the head convs, taken from the model's parameters the first time they are needed."""
+        if self._head_masters is None:
+            self.darknet.sync_stepped_parameters()
+            self._head_masters = {}
+            for layer in layers:
+                conv = next(sub for name, sub in self.darknet.module_list[layer].named_children() if name.startswith("conv_"))
+                self._head_masters[layer] = [conv.weight.detach().to(dev, torch.float32).clone(), conv.bias.detach().to(dev, torch.float32).clone()]
+        return self._head_masters
+
+    # ------------------------------------------------------------------ the reference's training step, on the heads
+    def feed_forward_through_model(self, batch_data, bndbox):
+        """The reference's training step (train.py:412-425) with the backbone frozen: forward under ``train_mode()``, loss, the
+        heads' gradients (``head_gradients``) and one ``optimizer`` step per head conv (``Darknet.step_conv``: masters, moments
+        and the packed weights updated by one kernel each).  Everything is enqueued on the current stream and nothing
+        synchronises; the next forward on that stream runs the new weights.  Returns the loss from before the step as a 0-dim
+        float32 device tensor.  The module's ``conv.weight`` / ``conv.bias`` lag behind until ``sync_parameters()`` (or anything
+        that reads the model's parameters as a whole: ``weight_stream()``, ``state_dict()``, a re-pack)."""
+        loss, grads = self.head_gradients(batch_data, bndbox)
+        self.optimizer.step(self.darknet, self._masters(grads, loss.device), grads)
+        return loss
+
+    def sync_parameters(self):
+        """Copy the masters into the module's ``conv.weight`` / ``conv.bias`` (one synchronisation).  The plan already runs these
+        weights, so it is not invalidated: no re-pack follows."""
+        self.darknet.sync_stepped_parameters()
