@@ -37,7 +37,12 @@ int rtod_device_count(int* out) {
     return RTOD_OK;
 }
 
-static int plan_create(const char* cfg_text, size_t len, int height, int width, int max_batch, int device, rtod_plan** out) {
+// rtod_plan_create (`who` = "plan_create": square inputs only) and rtod_plan_create_rect
+static int plan_create(const char* who, bool square, const char* cfg_text, size_t len, int height, int width, int max_batch, int device, rtod_plan** out) {
+    if (!cfg_text || !out) { set_error("%s: null pointer", who); return RTOD_E_ARG; }
+    *out = nullptr;
+    if (height < 1 || width < 1 || max_batch < 1 || device < 0) { set_error("%s: bad geometry %dx%d batch %d device %d", who, height, width, max_batch, device); return RTOD_E_ARG; }
+    if (square && height != width) { set_error("%s: only square inputs are supported (the reference derives every stride from net_info['height']); use rtod_plan_create_rect", who); return RTOD_E_ARG; }
     rtod_plan* h = new rtod_plan();
     h->p.height = height; h->p.width = width; h->p.max_batch = max_batch; h->p.device = device;
     int rc = h->p.parse(std::string(cfg_text, len));
@@ -50,20 +55,13 @@ static int plan_create(const char* cfg_text, size_t len, int height, int width, 
 
 int rtod_plan_create(const char* cfg_text, size_t len, int height, int width, int max_batch, int device, rtod_plan** out) {
     RTOD_GUARD_BEGIN
-    if (!cfg_text || !out) { set_error("plan_create: null pointer"); return RTOD_E_ARG; }
-    *out = nullptr;
-    if (height < 1 || width < 1 || max_batch < 1 || device < 0) { set_error("plan_create: bad geometry %dx%d batch %d device %d", height, width, max_batch, device); return RTOD_E_ARG; }
-    if (height != width) { set_error("plan_create: only square inputs are supported (the reference derives every stride from net_info['height']); use rtod_plan_create_rect"); return RTOD_E_ARG; }
-    return plan_create(cfg_text, len, height, width, max_batch, device, out);
+    return plan_create("plan_create", true, cfg_text, len, height, width, max_batch, device, out);
     RTOD_GUARD_END
 }
 
 int rtod_plan_create_rect(const char* cfg_text, size_t len, int height, int width, int max_batch, int device, rtod_plan** out) {
     RTOD_GUARD_BEGIN
-    if (!cfg_text || !out) { set_error("plan_create_rect: null pointer"); return RTOD_E_ARG; }
-    *out = nullptr;
-    if (height < 1 || width < 1 || max_batch < 1 || device < 0) { set_error("plan_create_rect: bad geometry %dx%d batch %d device %d", height, width, max_batch, device); return RTOD_E_ARG; }
-    return plan_create(cfg_text, len, height, width, max_batch, device, out);
+    return plan_create("plan_create_rect", false, cfg_text, len, height, width, max_batch, device, out);
     RTOD_GUARD_END
 }
 
@@ -140,18 +138,17 @@ int rtod_conv_kernel_name(int variant, int epilogue, char* buf, size_t len) {
 int rtod_plan_launch_kernel_name(const rtod_plan* plan, int index, char* buf, size_t len) {
     RTOD_GUARD_BEGIN
     if (!plan || !buf || len == 0 || index < 0 || index >= (int)plan->p.launches.size()) { set_error("launch_kernel_name: bad args"); return RTOD_E_ARG; }
-    rtod_launch_info li;
-    plan->p.fill_launch_info(index, &li, plan->p.tuned.empty() ? plan->p.max_batch : plan->p.tuned.rbegin()->first);
+    const LaunchForm f = plan->p.form(index);
     buf[0] = 0;
-    if (li.kind != LK_CONV || li.flops_per_frame == 0) return RTOD_OK;                 // non-conv launch / conv hosted by the previous launch: empty name
-    int epi = li.fused_decode ? 2 : (li.fused_pointwise ? (li.fused_residual ? 4 : 3) : (li.fused_residual ? 1 : 0));
-    if (plan->p.precision == 2 && li.variant >= 100) epi |= EPI_F16;              // plain-f16 instance of the split kernels
-    if (plan->p.raw_launch(plan->p.launches[index]) && li.variant >= 100) epi = EPI_RAW;   // raw-sum instance (the shortcut rides the normalise kernel)
-    int n = -1;
-    if (li.variant == 100 + STEM2_VARIANT) n = conv_stem2_kernel_name(li.fused_pointwise, buf, len);
-    else return rtod_conv_kernel_name(li.variant, epi, buf, len);
-    if (n < 0 || (size_t)n >= len) { set_error("launch_kernel_name: buffer too small"); return RTOD_E_ARG; }
-    return RTOD_OK;
+    if (plan->p.launches[index].kind != LK_CONV || f.inside >= 0) return RTOD_OK;      // non-conv launch / conv hosted by the previous launch: empty name
+    if (f.stem2) {
+        const int n = conv_stem2_kernel_name(f.guest >= 0, buf, len);
+        if (n < 0 || (size_t)n >= len) { set_error("launch_kernel_name: buffer too small"); return RTOD_E_ARG; }
+        return RTOD_OK;
+    }
+    rtod_launch_info li;                                                               // (the tile the plan reports for this launch)
+    plan->p.fill_launch_info(index, &li, plan->p.tuned.empty() ? plan->p.max_batch : plan->p.tuned.rbegin()->first);
+    return rtod_conv_kernel_name(li.variant, f.epi, buf, len);
     RTOD_GUARD_END
 }
 
@@ -247,7 +244,7 @@ int rtod_plan_set_keep_all_layers(rtod_plan* plan, int keep) {
 int rtod_plan_layer_shape(const rtod_plan* plan, int layer, int* c, int* h, int* w) {
     if (!plan || layer < 0 || layer >= (int)plan->p.layers.size() || !c || !h || !w) { set_error("layer_shape: bad args"); return RTOD_E_ARG; }
     const View v = plan->p.view_of(layer);
-    if (v.C == 0 || (layer == 0 && plan->p.stem_pool_fused()) || plan->p.bn_pool_fused(layer)) { set_error("layer %d is fused into its consumer and has no materialised output", layer); return RTOD_E_STATE; }
+    if (v.C == 0 || !plan->p.layer_form(layer).readable) { set_error("layer %d is fused into its consumer and has no materialised output", layer); return RTOD_E_STATE; }
     *c = v.C; *h = v.H; *w = v.W;
     return RTOD_OK;
 }
@@ -257,7 +254,7 @@ int rtod_plan_read_layer(rtod_plan* plan, int layer, int batch, float* out_dev_n
     if (!plan || layer < 0 || layer >= (int)plan->p.layers.size()) { set_error("read_layer: bad args"); return RTOD_E_ARG; }
     if (batch < 1 || batch > plan->p.max_batch) { set_error("read_layer: bad batch"); return RTOD_E_ARG; }
     const View v = plan->p.view_of(layer);
-    if (!v.base || (layer == 0 && plan->p.stem_pool_fused()) || plan->p.bn_pool_fused(layer)) { set_error("layer %d has no materialised output (fused) or weights not loaded", layer); return RTOD_E_STATE; }
+    if (!v.base || !plan->p.layer_form(layer).readable) { set_error("layer %d has no materialised output (fused) or weights not loaded", layer); return RTOD_E_STATE; }
     return launch_view_to_nchw(v, batch, out_dev_nchw, (hipStream_t)stream);
     RTOD_GUARD_END
 }
@@ -291,10 +288,8 @@ int rtod_plan_bn_update_running(rtod_plan* plan, int batch, float* const* runnin
         const int k = (int)ent.size();
         if (k >= n_bn) { set_error("bn_update_running: %d pointers for more BatchNorm layers", n_bn); return RTOD_E_ARG; }
         if (!running_mean_dev[k] || !running_var_dev[k]) { set_error("bn_update_running: null buffer %d", k); return RTOD_E_ARG; }
-        const View v = plan->p.view_of(pc.layer);
         const auto& L = plan->p.layers[pc.layer];
         const int64_t n = (int64_t)batch * L.hout * L.wout;
-        (void)v;
         ent.push_back(BnUpdateEntry{running_mean_dev[k], running_var_dev[k], pc.stats_off, (double)n / (double)(n > 1 ? n - 1 : 1), pc.Npad, L.cout});
     }
     if ((int)ent.size() != n_bn) { set_error("bn_update_running: the plan has %d BatchNorm layers, %d pointers given", (int)ent.size(), n_bn); return RTOD_E_ARG; }

@@ -33,7 +33,7 @@ struct Layer {
     int buf = -1, coff = 0;   // materialised output: arena buffer id + channel offset (-1: none/alias)
     int alias_of = -1;        // single-source route / yolo: same view as that layer
     int bn_pool = -1;         // BatchNorm conv of a batch-statistics split plan (options bn_split_narrow + fuse_bn_pool): index of the 2x2 / stride-2
-                              // max-pool that alone reads it and that its normalise kernel can run (Plan::bn_pool_fused decides at run time)
+                              // max-pool that alone reads it and that its normalise kernel can run (candidate; Plan::form decides at run time)
 };
 
 struct Buffer {
@@ -57,9 +57,24 @@ struct Launch {
     // split-f16 plans: a 1x1 conv that directly follows a conv whose workgroups hold all output channels runs in that
     // conv's epilogue (conv_f16s3_common.h).  pw_guest: launch index of the 1x1 conv hosted by this launch; pw_host:
     // launch index of the host (this launch is then skipped).  Candidates are found at plan build (liveness covers
-    // both schedules); Plan::pw_active() decides at run time.
+    // both schedules); Plan::form decides at run time.
     int pw_guest = -1, pw_host = -1;
 };
+
+// The form in which a launch runs: the plan's candidates (Launch::pw_guest / pw_host, Layer::bn_pool, Plan::stem2_pattern,
+// stem_pool_pattern) under the precision, the options and keep_all_layers.  Plan::form is the one place that decides it.
+struct LaunchForm {
+    int inside = -1;       // >= 0: this launch enqueues nothing, that launch's kernel does its work (stem in layer 1's kernel, max-pool in the
+                           // stem's or in a conv's normalise kernel, 1x1 guest in its host's epilogue)
+    // conv and stem launches that run
+    bool stem2 = false;    // conv: the fused stem kernel (conv_stem2_f16s3.hip); launch 0's stem rides here
+    int guest = -1;        // conv: launch index of the 1x1 conv it hosts in its epilogue
+    bool raw = false;      // raw-sum step of a batch-statistics split plan: raw sums, statistics, normalise
+    int pool = -1;         // layer index of the 2x2 max-pool that its kernel (16-filter stem) or its normalise kernel also runs
+    int epi = 0;           // conv: epilogue code of the kernel instance (EPI_* of conv_f16s3_common.h, | EPI_F16, or EPI_RAW)
+};
+// ... and what that leaves of a layer: the fused_into it reports, and whether its own output is stored and can be read back
+struct LayerForm { int fused_into; bool readable; };
 
 struct PackedConv {
     int layer = 0;
@@ -77,7 +92,7 @@ struct PackedConv {
     int ks_chunks = 0;                // split, option k_slices_split: sliced layer (slices of this many K-chunks), runs on conv_ks_f16s3 only; 0: not sliced
 };
 
-// One struct, defined over five files by concern: plan_cfg.cpp (parse, resolve_shapes: no HIP call), plan_build.cpp (options, buffer
+// One struct, defined over five files by concern (the run-time fused form of every launch is decided in one place, Plan::form in plan_forward.cpp): plan_cfg.cpp (parse, resolve_shapes: no HIP call), plan_build.cpp (options, buffer
 // planning, weight layout, describe), plan_weights.cpp (pack_conv, pack_weights, load_weights, update_conv, step_conv), plan_tiles.cpp (which kernel variant a conv
 // launch runs, autotune), plan_forward.cpp (the launch list on a stream, launch records).
 struct Plan {
@@ -158,12 +173,12 @@ struct Plan {
     bool feeds_yolo(int layer) const { return layers[layer].type == LT_CONV && layer + 1 < (int)layers.size() && layers[layer + 1].type == LT_YOLO; }
     int forward(const float* x, int batch, float* out, hipStream_t s, float* launch_ms, bool tune = false);
     // the launches of one LK_CONV / LK_STEM step of forward, in order
-    int run_conv(size_t li, const float* x, int batch, float* out, hipStream_t s, bool tune_now);
-    int run_conv_f32(const Launch& l, ConvArgs& a, int batch, hipStream_t s) const;
-    int run_conv_split(size_t li, ConvArgs& a, int batch, hipStream_t s, bool tune_now);
-    int run_stem(const Launch& l, const float* x, int batch, hipStream_t s) const;
+    int run_conv(size_t li, const LaunchForm& f, const float* x, int batch, float* out, hipStream_t s, bool tune_now);
+    int run_conv_f32(const Launch& l, const LaunchForm& f, ConvArgs& a, int batch, hipStream_t s) const;
+    int run_conv_split(size_t li, const LaunchForm& f, ConvArgs& a, int batch, hipStream_t s, bool tune_now);
+    int run_stem(const Launch& l, const LaunchForm& f, const float* x, int batch, hipStream_t s) const;
     int raw_bn_begin(const Launch& l, int batch, bool site_ok, View& raw) const;        // raw view of a batch-statistics BatchNorm step, checked once
-    int run_raw_bn(const Launch& l, const View& raw, int batch, hipStream_t s) const;   // ... its statistics + normalise (the only caller of launch_bn_batch_split)
+    int run_raw_bn(const Launch& l, const View& raw, int pool, int batch, hipStream_t s) const;   // ... its statistics + normalise (+ max-pool layer `pool`); the only caller of launch_bn_batch_split
     int finish_decode(float* out, int batch, hipStream_t s) const;   // TRAIN=True output -> eval decode in place (rtod_plan_finish_decode)
     int set_option(const char* name, int value);
     int set_precision(int mode);              // re-plans: the launch list depends on the precision (option stem_pool)
@@ -171,7 +186,7 @@ struct Plan {
     void reset_planning();
     View view_of(int layer) const;            // resolves aliases; base == nullptr if not materialised
     int choose_variant(const Layer& L, int batch) const;
-    int build_conv_args(const Launch& l, int batch, float* out, ConvArgs& a) const;
+    int build_conv_args(const Launch& l, const LaunchForm& f, int batch, float* out, ConvArgs& a) const;
     int tune_launch(size_t li, ConvArgs& a, int batch, hipStream_t s);
     std::vector<int> tuning;                    // scratch of the tuning forward
     std::map<std::vector<int>, int> tune_cache;
@@ -187,17 +202,19 @@ struct Plan {
     bool raw_launch(const Launch& l) const { return bn_split_active() && l.kind == LK_CONV && layers[l.layer].bn; }   // a BatchNorm conv of such a plan: raw sums, then normalise
     bool bn_narrow_active() const { return bn_split_active() && opt_bn_split_narrow; }   // ... narrow tiles, 16-filter stem and fused pools included
     int raw_stride(const PackedConv& pc) const;           // floats per row of the raw-sum scratch: Npad; narrow tiles and the 16-filter stem: Cout rounded up to 8
-    bool bn_pool_fused(int layer) const;                  // the BatchNorm conv `layer` is normalised and pooled by one kernel: its own map is never stored
-    bool pool_fused_away(int layer) const { return layer > 0 && layers[layer - 1].bn_pool == layer && bn_pool_fused(layer - 1); }   // max-pool `layer` runs in that kernel
     View bn_raw_view(const Launch& l, int batch) const;   // fp32 view over d_bn_raw for this launch's conv
-    bool pw_active() const;                     // fused pointwise convs in use (precision 1, option fuse_pointwise)
-    bool stem2_pattern = false;                 // launches 0 / 1 are a stem and the stride-2 conv conv_stem2_f16s3 fuses (set by plan_buffers)
-    bool stem2_active() const;                  // ... and the plan runs them fused (split-f16 precision, option stem2_kernel)
-    bool stem_pool_pattern = false;             // launch 0 is the 16-filter stem and launch 1 the 2x2 / stride-2 max-pool that alone reads it (set by plan_buffers)
-    bool stem_pool_fused() const;               // ... and the plan runs them as one kernel (not under keep_all_layers)
+    bool stem2_pattern = false;                 // launches 0 / 1 are a stem and the stride-2 conv conv_stem2_f16s3 fuses (candidate, set by plan_buffers)
+    bool stem_pool_pattern = false;             // launch 0 is the 16-filter stem and launch 1 the 2x2 / stride-2 max-pool that alone reads it (candidate, set by plan_buffers)
+    LaunchForm form(size_t li) const;           // how launch li runs; computed on demand (keep_all_layers changes it without planning again)
+    LayerForm layer_form(int layer) const;      // ... and what describe and the layer readers report of a layer
     std::map<int, std::vector<int>> tuned;     // batch -> per-launch split-f16 tile variant (-1: heuristic)
     std::string describe() const;
     void fill_launch_info(int idx, rtod_launch_info* o, int batch) const;
+
+private:                                        // the run-time predicates over the candidates: read by form / layer_form alone
+    bool pw_active() const;                     // fused pointwise convs in use (precision 1, option fuse_pointwise)
+    bool stem2_active() const;                  // stem2_pattern, and the plan runs it fused (split-f16 precision, option stem2_kernel, not under keep_all_layers)
+    int fused_pool(int layer) const;            // the max-pool layer that conv `layer`'s kernel (stem_pool_pattern) or normalise kernel (Layer::bn_pool) runs, or -1
 };
 
 }  // namespace rtod

@@ -270,7 +270,7 @@ int Plan::plan_buffers() {
                 cons[i].size() == 1 && cons[i][0] == i + 1 && L.hout % 2 == 0 && L.wout % 2 == 0)
                 L.bn_pool = i + 1;
         }
-    // liveness per buffer over launch time (= layer index of the launch)
+    // liveness per buffer over launch time (= layer index of the launch).  Candidates, not forms: the arena covers the fused and the stand-alone schedule
     const int NB = (int)bufs.size();
     for (auto& b : bufs) { b.first = 1 << 30; b.last = -1; }
     auto touch = [&](int buf, int t) { if (buf < 0) return; bufs[buf].first = std::min(bufs[buf].first, t); bufs[buf].last = std::max(bufs[buf].last, t); };
@@ -398,7 +398,7 @@ void Plan::layout_weights() {
             pc.s_off = packed_floats; packed_floats += pc.Npad;
             pc.narrow = opt_narrow_cin && conv_c16_supported(L.cin);
             const Launch* ll = launch_of[&pc - &convs[0]];
-            pc.ks_chunks = 0;
+            pc.ks_chunks = 0;                                         // (candidates, not forms: a sliced conv is never part of a pair that may fuse)
             if (opt_k_slices_split && ll && !pc.narrow && ll->out_layer != -2 && ll->pw_guest < 0 && ll->pw_host < 0 &&
                 !(stem2_pattern && pc.layer == 1) && pc.K == pc.Kpad && L.cin % 32 == 0)
                 pc.ks_chunks = split_slice_chunks(L, pc.Kpad);
@@ -485,7 +485,7 @@ std::string Plan::describe() const {
         os << "],\"anchors\":[";
         for (size_t a = 0; a < L.anchors.size(); ++a) os << (a ? "," : "") << "[" << L.anchors[a].first << "," << L.anchors[a].second << "]";
         os << "],\"classes\":" << L.classes << ",\"row_offset\":" << L.row_offset << ",\"rows\":" << L.rows << ",\"w_off\":" << L.w_off
-           << ",\"fused_into\":" << ((i == 0 && (stem2_active() || stem_pool_fused())) ? 1 : bn_pool_fused((int)i) ? L.bn_pool : L.fused_into) << ",\"fused_away\":" << (L.fused_away ? "true" : "false") << ",\"alias_of\":" << L.alias_of
+           << ",\"fused_into\":" << layer_form((int)i).fused_into << ",\"fused_away\":" << (L.fused_away ? "true" : "false") << ",\"alias_of\":" << L.alias_of
            << ",\"buf\":" << L.buf << ",\"coff\":" << L.coff;
         if (L.type == LT_CONV)                                                       // sliced layers only (option k_slices_split)
             for (const auto& pc : convs)

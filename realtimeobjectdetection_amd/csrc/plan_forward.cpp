@@ -6,7 +6,48 @@
 
 namespace rtod {
 
-int Plan::build_conv_args(const Launch& l, int batch, float* out, ConvArgs& a) const {
+// The run-time predicates over the candidates that planning found; form / layer_form below are their only readers
+bool Plan::pw_active() const { return precision == 1 && opt_fuse_pointwise && !bn_split_active(); }
+bool Plan::stem2_active() const { return precision == 1 && !bn_split_active() && opt_stem2_kernel && stem2_pattern && !keep_all && convs[launches[0].conv_slot].split; }
+int Plan::fused_pool(int layer) const {
+    if (keep_all) return -1;                                     // every layer's own map is stored
+    if (layer == 0 && precision >= 1 && stem_pool_pattern && convs[launches[0].conv_slot].stem16) return 1;
+    return bn_narrow_active() && opt_fuse_bn_pool ? layers[layer].bn_pool : -1;
+}
+
+// How launch li runs (LaunchForm, plan.h): the one place that puts candidates and predicates together.  A few compares per call
+LaunchForm Plan::form(size_t li) const {
+    LaunchForm f;
+    const Launch& l = launches[li];
+    switch (l.kind) {
+        case LK_MAXPOOL:                                         // a fused pool is the launch after its conv's / stem's
+            if (li > 0 && launches[li - 1].conv_slot >= 0 && fused_pool(launches[li - 1].layer) == l.layer) f.inside = (int)li - 1;
+            return f;
+        case LK_STEM: if (stem2_active()) f.inside = 1; break;
+        case LK_CONV:
+            if (l.pw_host >= 0 && pw_active()) f.inside = l.pw_host;
+            else { f.stem2 = li == 1 && stem2_active(); f.guest = l.pw_guest >= 0 && pw_active() ? l.pw_guest : -1; }
+            break;
+        default: return f;
+    }
+    if (f.inside >= 0) return f;
+    const bool split = convs[l.conv_slot].split;
+    f.raw = bn_split_active() && layers[l.layer].bn;
+    f.pool = fused_pool(l.layer);
+    f.epi = l.out_layer == -2 ? 2 : (f.guest >= 0 ? 3 : 0) + (l.in2_layer >= 0 ? 1 : 0);
+    if (split && precision == 2) f.epi |= EPI_F16;                // plain-f16 instance of the split kernels
+    if (split && f.raw) f.epi = EPI_RAW;                          // raw-sum instance (the shortcut rides the normalise kernel)
+    return f;
+}
+
+// Layer 0 inside the fused stem kernel keeps its arena buffer (liveness covers both schedules) and stays readable, though no kernel writes it
+LayerForm Plan::layer_form(int layer) const {
+    const int pool = fused_pool(layer);
+    if (pool >= 0) return {pool, false};
+    return {layer == 0 && stem2_active() ? 1 : layers[layer].fused_into, true};
+}
+
+int Plan::build_conv_args(const Launch& l, const LaunchForm& f, int batch, float* out, ConvArgs& a) const {
     const Layer& L = layers[l.layer];
     const PackedConv& pc = convs[l.conv_slot];
     const View in = view_of(l.in_layer);
@@ -36,8 +77,8 @@ int Plan::build_conv_args(const Launch& l, int batch, float* out, ConvArgs& a) c
         if (!r.base || r.C != L.cout || r.H != L.hout || r.W != L.wout) { set_error("forward: layer %d residual view mismatch", l.layer); return RTOD_E_STATE; }
         a.res = r.base; a.res_ldc = r.ldc; a.res_coff = r.coff;
     }
-    if (l.pw_guest >= 0 && pw_active()) {
-        const Launch& g = launches[l.pw_guest];
+    if (f.guest >= 0) {
+        const Launch& g = launches[f.guest];
         const Layer& G = layers[g.layer];
         const PackedConv& gc = convs[g.conv_slot];
         const View o = view_of(g.out_layer);
@@ -60,10 +101,6 @@ View Plan::bn_raw_view(const Launch& l, int batch) const {
     v.base = d_bn_raw; v.ldc = raw_stride(pc); v.coff = 0; v.C = L.cout; v.H = L.hout; v.W = L.wout;
     return v;
 }
-bool Plan::pw_active() const { return precision == 1 && opt_fuse_pointwise && !bn_split_active(); }
-bool Plan::stem_pool_fused() const { return precision >= 1 && stem_pool_pattern && !keep_all && convs[launches[0].conv_slot].stem16; }
-bool Plan::bn_pool_fused(int layer) const { return bn_narrow_active() && opt_fuse_bn_pool && !keep_all && layers[layer].bn_pool >= 0; }
-bool Plan::stem2_active() const { return precision == 1 && !bn_split_active() && opt_stem2_kernel && stem2_pattern && !keep_all && convs[launches[0].conv_slot].split; }
 
 // Every head of the plan, in the arithmetic of the kernel that decodes it in a forward: fused into a split-f16 / f16 conv the
 // epilogue of conv_f16s3_common.h (hardware exp2), otherwise the exact-fp32 conv epilogue or the stand-alone kernel (libm expf).
@@ -89,18 +126,17 @@ int Plan::raw_bn_begin(const Launch& l, int batch, bool site_ok, View& raw) cons
 }
 
 // ... after the raw conv has been enqueued: statistics, then normalise + activation + shortcut into the split format, with the
-// max-pool that follows into the pool's view when bn_pool_fused
-int Plan::run_raw_bn(const Launch& l, const View& raw, int batch, hipStream_t s) const {
+// max-pool that follows into the view of that layer (`pool`, LaunchForm::pool) when the form says so
+int Plan::run_raw_bn(const Launch& l, const View& raw, int pool, int batch, hipStream_t s) const {
     const Layer& L = layers[l.layer];
     const PackedConv& pc = convs[l.conv_slot];
-    const bool pool = bn_pool_fused(l.layer);
     View r; if (l.in2_layer >= 0) r = view_of(l.in2_layer);
-    return launch_bn_batch_split(raw, view_of(pool ? L.bn_pool : l.out_layer), l.in2_layer >= 0 ? &r : nullptr, batch, d_bn_stats + pc.stats_off, pc.Npad, d_weights + pc.bn_off, pc.Npad,
-                                 L.act, d_bn_partial, bn_partial_count, overflow_flag, s, pool ? 1 : 0);
+    return launch_bn_batch_split(raw, view_of(pool >= 0 ? pool : l.out_layer), l.in2_layer >= 0 ? &r : nullptr, batch, d_bn_stats + pc.stats_off, pc.Npad, d_weights + pc.bn_off, pc.Npad,
+                                 L.act, d_bn_partial, bn_partial_count, overflow_flag, s, pool >= 0 ? 1 : 0);
 }
 
 // A conv on the exact-fp32 kernels: every conv of an fp32 plan, layer 0 of a split plan without a stem kernel
-int Plan::run_conv_f32(const Launch& l, ConvArgs& a, int batch, hipStream_t s) const {
+int Plan::run_conv_f32(const Launch& l, const LaunchForm& f, ConvArgs& a, int batch, hipStream_t s) const {
     const Layer& L = layers[l.layer];
     const PackedConv& pc = convs[l.conv_slot];
     const int v = choose_variant(L, batch);
@@ -116,7 +152,7 @@ int Plan::run_conv_f32(const Launch& l, ConvArgs& a, int batch, hipStream_t s) c
         if (!rv.base) { set_error("forward: layer %d: no raw-sum scratch", l.layer); return RTOD_E_STATE; }
         a.out = rv.base; a.out_ldc = rv.ldc; a.out_coff = 0; a.out_split = 0;
         if (int rc = launch_conv(a, v, s)) return rc;
-        return run_raw_bn(l, rv, batch, s);
+        return run_raw_bn(l, rv, f.pool, batch, s);
     }
     if (int rc = launch_conv(a, v, s)) return rc;
     const View o = view_of(l.out_layer);
@@ -124,39 +160,35 @@ int Plan::run_conv_f32(const Launch& l, ConvArgs& a, int batch, hipStream_t s) c
     return launch_bn_batch(o, o, l.in2_layer >= 0 ? &r : nullptr, batch, d_bn_stats + pc.stats_off, pc.Npad, d_weights + pc.bn_off, pc.Npad, L.act, d_bn_partial, bn_partial_count, s);
 }
 
-// A conv on a split-f16 / f16 tile; a BatchNorm conv of a batch-statistics split plan (raw_launch): raw sums, statistics, normalise
-int Plan::run_conv_split(size_t li, ConvArgs& a, int batch, hipStream_t s, bool tune_now) {
+// A conv on a split-f16 / f16 tile; a BatchNorm conv of a batch-statistics split plan (LaunchForm::raw): raw sums, statistics, normalise
+int Plan::run_conv_split(size_t li, const LaunchForm& f, ConvArgs& a, int batch, hipStream_t s, bool tune_now) {
     const Launch& l = launches[li];
     const PackedConv& pc = convs[l.conv_slot];
-    const bool raw = raw_launch(l);
     View rv;
-    if (raw) {
+    if (f.raw) {
         if (int rc = raw_bn_begin(l, batch, !a.dec.enabled && !a.pw_wh, rv)) return rc;
         a.raw_out = rv.base; a.raw_ld = (int)rv.ldc; a.res = nullptr; a.leaky = 0;
     }
     if (tune_now) { if (int rc = tune_launch(li, a, batch, s)) return rc; }      // (never reached for the fused stem launch)
     if (int rc = launch_split_variant(a, pc, tune_now && tuning[li] >= 0 ? tuning[li] : variant_for(l, batch), s)) return rc;
-    return raw ? run_raw_bn(l, rv, batch, s) : RTOD_OK;
+    return f.raw ? run_raw_bn(l, rv, f.pool, batch, s) : RTOD_OK;
 }
 
-int Plan::run_conv(size_t li, const float* x, int batch, float* out, hipStream_t s, bool tune_now) {
+int Plan::run_conv(size_t li, const LaunchForm& f, const float* x, int batch, float* out, hipStream_t s, bool tune_now) {
     const Launch& l = launches[li];
-    if (l.pw_host >= 0 && pw_active()) return RTOD_OK;           // runs in the host conv's epilogue
     ConvArgs a;
-    if (int rc = build_conv_args(l, batch, out, a)) return rc;
-    if (!convs[l.conv_slot].split) return run_conv_f32(l, a, batch, s);
-    if (!(li == 1 && stem2_active())) return run_conv_split(li, a, batch, s, tune_now);
+    if (int rc = build_conv_args(l, f, batch, out, a)) return rc;
+    if (!convs[l.conv_slot].split) return run_conv_f32(l, f, a, batch, s);
+    if (!f.stem2) return run_conv_split(li, f, a, batch, s, tune_now);
     // stem + this conv (+ its hosted 1x1) in one kernel
     const PackedConv& p0 = convs[launches[0].conv_slot];
-    if (!(l.pw_guest >= 0 && pw_active())) { a.pw_wh = nullptr; a.pw_wl = nullptr; }
     return launch_conv_stem2_f16s3(x, batch, height, width, reinterpret_cast<const _Float16*>(d_weights + p0.w_off),
                                    reinterpret_cast<const _Float16*>(d_weights + p0.wl_off), d_weights + p0.s_off, d_weights + p0.b_off,
                                    layers[0].act, a, s);
 }
 
 // Layer 0 on a kernel that reads the NCHW input itself
-int Plan::run_stem(const Launch& l, const float* x, int batch, hipStream_t s) const {
-    if (stem2_active()) return RTOD_OK;                          // computed inside layer 1's kernel
+int Plan::run_stem(const Launch& l, const LaunchForm& f, const float* x, int batch, hipStream_t s) const {
     const Layer& L = layers[l.layer];
     const PackedConv& pc = convs[l.conv_slot];
     const View o = view_of(l.out_layer);
@@ -168,14 +200,13 @@ int Plan::run_stem(const Launch& l, const float* x, int batch, hipStream_t s) co
     }
     // 16 filters: stand-alone, or with layer 1's max-pool (writes layer 1's view)
     if (!pc.split) { set_error("forward: the 16-filter stem needs a split-f16 / f16 plan"); return RTOD_E_STATE; }
-    if (bn_split_active() && L.bn) {                             // raw sums (unfolded weights), statistics, normalise (+ the max-pool that follows)
+    if (f.raw) {                                                 // raw sums (unfolded weights), statistics, normalise (+ the max-pool that follows)
         View rv;
         if (int rc = raw_bn_begin(l, batch, opt_bn_split_narrow, rv)) return rc;
         if (int rc = launch_conv_stem16_raw(x, wh, wl, d_weights + pc.s_off, rv, batch, height, width, s)) return rc;
-        return run_raw_bn(l, rv, batch, s);
+        return run_raw_bn(l, rv, f.pool, batch, s);
     }
-    const bool pool = stem_pool_fused();
-    return launch_conv_stem16_f16s3(x, wh, wl, d_weights + pc.s_off, d_weights + pc.b_off, pool ? view_of(1) : o, batch, height, width, L.act, pool ? 1 : 0, overflow_flag, s);
+    return launch_conv_stem16_f16s3(x, wh, wl, d_weights + pc.s_off, d_weights + pc.b_off, f.pool >= 0 ? view_of(f.pool) : o, batch, height, width, L.act, f.pool >= 0 ? 1 : 0, overflow_flag, s);
 }
 
 int Plan::forward(const float* x, int batch, float* out, hipStream_t s, float* launch_ms, bool tune) {
@@ -193,22 +224,21 @@ int Plan::forward(const float* x, int batch, float* out, hipStream_t s, float* l
     for (size_t li = 0; li < nl; ++li) {
         const Launch& l = launches[li];
         if (launch_ms) RTOD_HIP(hipEventRecord(events[2 * li], s));
+        const LaunchForm f = form(li);
         int rc = RTOD_OK;
-        switch (l.kind) {
+        if (f.inside < 0) switch (l.kind) {                             // (inside >= 0: that launch's kernel does the work)
             case LK_PACK: {
                 View v = view_of(-1);
                 rc = launch_pack_input(x, batch, 3, height, width, v.base, 4, s);
                 break;
             }
-            case LK_CONV: rc = run_conv(li, x, batch, out, s, tune_now); break;
-            case LK_STEM: rc = run_stem(l, x, batch, s); break;
+            case LK_CONV: rc = run_conv(li, f, x, batch, out, s, tune_now); break;
+            case LK_STEM: rc = run_stem(l, f, x, batch, s); break;
             case LK_UPSAMPLE:
                 rc = layers[l.layer].nearest ? launch_upsample_nearest2x(view_of(l.in_layer), view_of(l.out_layer), batch, s)
                                              : launch_upsample2x(view_of(l.in_layer), view_of(l.out_layer), batch, s);
                 break;
             case LK_MAXPOOL:
-                if (li == 1 && stem_pool_fused()) break;                // computed inside the stem's kernel
-                if (pool_fused_away(l.layer)) break;                    // ... inside the conv's normalise kernel
                 rc = launch_maxpool(view_of(l.in_layer), view_of(l.out_layer), batch, layers[l.layer].size, layers[l.layer].stride, layers[l.layer].pool_pad, s); break;
             case LK_ADD: rc = launch_add(view_of(l.in_layer), view_of(l.in2_layer), view_of(l.out_layer), batch, s); break;
             case LK_COPY: {
@@ -237,6 +267,12 @@ int Plan::forward(const float* x, int batch, float* out, hipStream_t s, float* l
     return RTOD_OK;
 }
 
+// FLOPs and weight bytes of one conv layer, added to the launch that runs it
+static void add_conv_cost(const Layer& L, rtod_launch_info* o) {
+    o->flops_per_frame += 2ll * L.hout * L.wout * L.cout * L.cin * L.size * L.size;
+    o->weight_bytes += ((int64_t)L.cout * L.cin * L.size * L.size + L.cout) * 4;
+}
+
 void Plan::fill_launch_info(int idx, rtod_launch_info* o, int batch) const {
     memset(o, 0, sizeof(*o));
     const Launch& l = launches[idx];
@@ -244,38 +280,28 @@ void Plan::fill_launch_info(int idx, rtod_launch_info* o, int batch) const {
     if (l.kind == LK_PACK) { o->bytes_per_frame = (int64_t)height * width * (3 + 4) * 4; return; }
     const Layer& L = layers[l.layer];
     o->ksize = L.size; o->stride = L.stride; o->cin = L.cin; o->cout = L.cout; o->hout = L.hout; o->wout = L.wout;
+    const LaunchForm f = form(idx);
+    if (f.inside >= 0) return;                                                       // accounted on the launch that does its work
     const int64_t in_b = (int64_t)L.hin * L.win * L.cin * 4, out_b = (int64_t)L.hout * L.wout * L.cout * 4;
     switch (l.kind) {
-        case LK_STEM:
-            if (stem2_active()) { o->bytes_per_frame = 0; break; }                   // accounted on layer 1's launch
-            o->flops_per_frame = 2ll * L.hout * L.wout * L.cout * L.cin * L.size * L.size;
-            o->bytes_per_frame = in_b + (stem_pool_fused() || bn_pool_fused(l.layer) ? out_b / 4 : out_b);  // fused 2x2 pool: the pooled map is what is written
-            o->weight_bytes = ((int64_t)L.cout * L.cin * L.size * L.size + L.cout) * 4;
-            break;
-        case LK_MAXPOOL:
-            o->bytes_per_frame = (idx == 1 && stem_pool_fused()) || pool_fused_away(l.layer) ? 0 : in_b + out_b;   // fused: accounted on the stem's / conv's launch
-            break;
         case LK_CONV:
-            if (l.pw_host >= 0 && pw_active()) { o->bytes_per_frame = 0; break; }    // accounted on the host conv's launch
-            if (convs[l.conv_slot].split) o->variant = 100 + variant_for(l, batch);
+            if (f.stem2) o->variant = 100 + STEM2_VARIANT;
+            else if (convs[l.conv_slot].split) o->variant = 100 + variant_for(l, batch);
             else { const int v = choose_variant(L, batch); o->variant = v + 10 * f32_slice_mode(l, batch, v); }   // tile + 10 * K-slice schedule
-            o->flops_per_frame = 2ll * L.hout * L.wout * L.cout * L.cin * L.size * L.size;
             o->fused_residual = l.in2_layer >= 0; o->fused_decode = l.out_layer == -2;
-            o->bytes_per_frame = in_b + (bn_pool_fused(l.layer) ? out_b / 4 : out_b) + (l.in2_layer >= 0 ? out_b : 0);   // (fused 2x2 pool: the pooled map is what is written)
-            o->weight_bytes = ((int64_t)L.cout * L.cin * L.size * L.size + L.cout) * 4;
-            if (idx == 1 && stem2_active()) {                                        // fused stem: its FLOPs ride here, its output is never written
-                const Layer& S = layers[0];
-                o->variant = 100 + STEM2_VARIANT;
-                o->flops_per_frame += 2ll * S.hout * S.wout * S.cout * S.cin * S.size * S.size;
-                o->bytes_per_frame = (int64_t)S.hin * S.win * S.cin * 4 + out_b;
-                o->weight_bytes += ((int64_t)S.cout * S.cin * S.size * S.size + S.cout) * 4;
+            [[fallthrough]];
+        case LK_STEM:                                                                // (never a shortcut, a hosted 1x1 or the fused stem kernel)
+            add_conv_cost(L, o);
+            o->bytes_per_frame = in_b + (f.pool >= 0 ? out_b / 4 : out_b) + (l.in2_layer >= 0 ? out_b : 0);   // (fused 2x2 pool: the pooled map is what is written)
+            if (f.stem2) {                                                           // fused stem: its FLOPs ride here, its output is never written
+                add_conv_cost(layers[0], o);
+                o->bytes_per_frame = (int64_t)layers[0].hin * layers[0].win * layers[0].cin * 4 + out_b;
             }
-            if (l.pw_guest >= 0 && pw_active()) {
-                const Layer& G = layers[launches[l.pw_guest].layer];
+            if (f.guest >= 0) {
+                const Layer& G = layers[launches[f.guest].layer];
                 o->fused_pointwise = 1;
-                o->flops_per_frame += 2ll * G.hout * G.wout * G.cout * G.cin;
+                add_conv_cost(G, o);
                 o->bytes_per_frame += (int64_t)G.hout * G.wout * G.cout * 4;
-                o->weight_bytes += ((int64_t)G.cout * G.cin + G.cout) * 4;
             }
             break;
         case LK_ADD: o->bytes_per_frame = 3 * out_b; break;

@@ -36,7 +36,7 @@ int Plan::f32_slice_mode(const Launch& l, int batch, int variant) const {
 // whose panels do not fit the scratch is legal here: variant_for runs schedule A of the same tile (same bits), set_tiles refuses it.
 // Plain-f16 plans (precision 2) run the tiles that have an f16 instance (the f16 column of the family table): the generic, bandd
 // (band layers, and the wide tile of the other 3x3 stride-1 layers), 1x1 slab, narrow and K-sliced tiles; never conv_band / ring /
-// patch, and no hosted pointwise epilogue (pw_active).
+// patch, and no hosted pointwise epilogue (LaunchForm::guest).
 // A BatchNorm conv of a batch-statistics split plan (raw_launch) runs the tiles with a raw-sum instance (the raw column) that its
 // family rules admit; for layers that are neither narrow nor sliced that is the set of a plain-f16 plan.
 bool Plan::tile_legal(const Launch& l, int v) const {
@@ -51,7 +51,7 @@ bool Plan::tile_legal(const Launch& l, int v) const {
     if (pc.ks_chunks > 0 || t.is(TF_KS)) return pc.ks_chunks > 0 && t.is(TF_KS);
     if (pc.band) return t.is(TF_BAND) && conv_band_mode_valid(t.mode, L.cin, L.hin, L.win);
     // the other layers: generic K order.  plain = no fused head decode, no hosted pointwise conv
-    const bool hosts_pw = l.pw_guest >= 0 && pw_active(), plain = l.out_layer != -2 && !hosts_pw, same_map = L.hout == L.hin && L.wout == L.win;
+    const bool hosts_pw = form(&l - &launches[0]).guest >= 0, plain = l.out_layer != -2 && !hosts_pw, same_map = L.hout == L.hin && L.wout == L.win;
     switch (t.fam->id) {
         case TF_GENERIC: return !(hosts_pw && t.fam->info(t.mode).bn < L.cout);        // fused pointwise: one N tile must cover every output channel
         // the one-buffer bandd tile: 3x3 stride-1 layers too wide for the band family's LDS budget at three workgroups per CU

@@ -148,6 +148,7 @@ int Plan::replaceable_conv(const char* who, int layer, size_t& slot) const {
     slot = convs.size();
     for (const auto& l : launches) {
         if ((l.kind != LK_CONV && l.kind != LK_STEM) || l.layer != layer || l.conv_slot < 0) continue;
+        // (candidates, not forms: a pair that may fuse is refused whether or not it runs fused now)
         if (l.pw_guest >= 0 || l.pw_host >= 0) { set_error("%s: layer %d is part of a fused pointwise pair", who, layer); return RTOD_E_ARG; }
         slot = (size_t)l.conv_slot;
     }
