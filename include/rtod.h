@@ -192,6 +192,9 @@ int rtod_plan_set_precision(rtod_plan* plan, int mode);
  *                       keeps its lifetime to the end of the forward, so rtod_plan_read_layer of that input layer is valid after a
  *                       forward in every precision: the activations rtod_conv1x1_wgrad needs.  Liveness only: launches, tiles and
  *                       output bits are those of the plan without the option; arena_bytes may grow
+ *   "keep_block_inputs" (default 0) likewise the buffer read by every detection BLOCK conv (rtod_plan_head_blocks), a concat buffer
+ *                       where that input is a route: the activations rtod_conv_wgrad needs.  Liveness only as well; in addition
+ *                       rtod_plan_load_weights then keeps the blocks' frozen BatchNorm scales on the device (rtod_plan_conv_scale)
  *   "force_f16s3_variant" / "force_f32_variant"   >= 0: one tile variant for every conv (tests, A/B runs)
  * Options that leave a cfg inexpressible in the split-f16 format return RTOD_E_CFG when precision is 1 or 2 (so does setting
  * "narrow_cin" back to 0 on a plan that needs it); the plan then stays as it was. */
@@ -218,6 +221,31 @@ int rtod_plan_head_layers(const rtod_plan* plan, int* conv_layers, int* input_la
  * layer that is not a convolution, a conv with BatchNorm, a conv that hosts or is hosted in a fused pointwise pair;
  * RTOD_E_STATE: before rtod_plan_load_weights. */
 int rtod_plan_update_conv(rtod_plan* plan, int layer, const float* weight_oihw_host, const float* bias_host);
+/* (new) The detection BLOCKS of a plan, one entry per head in cfg order: head_conv_layers[i] as rtod_plan_head_layers,
+ * block_conv_layers[i] the layer that head conv reads (head - 1) if it is a block, else -1, block_input_layers[i] the layer the
+ * block reads (block - 1, possibly a route; -1 without a block; see option "keep_block_inputs").  A block is a convolution
+ *   with BatchNorm, folded (plans with option "bn_batch_stats" have no blocks), of size 1 or 3, stride 1, pad size / 2,
+ *   activation leaky or linear, Cin a multiple of 32,
+ *   packed in one of the two generic layouts — not a stem, not narrow (Cin == 16), neither host nor guest of a fused pointwise
+ *   candidate pair (a conv under "k_slices_split" packs by the generic formula and qualifies) — for every tap and channel
+ *       fp32 panel    float  o * Kpad + tap * Cin + c
+ *       split planes  half   (((c / 32) * taps + tap) * Npad + o) * 32 + c % 32      of the hi and of the lo plane,
+ *   and whose own output is stored (not computed inside another layer's kernel).
+ * A head that reads a max-pool, a stride-2 conv, a SiLU conv or a conv without BatchNorm has none.  Returns the number of heads,
+ * capacity as rtod_plan_head_layers. */
+int rtod_plan_head_blocks(const rtod_plan* plan, int* head_conv_layers, int* block_conv_layers, int* block_input_layers, int capacity);
+/* (new) The frozen BatchNorm scale of a block conv, s[o] = (double)gamma[o] / sqrt((double)var[o] + 1e-5), exactly the factor
+ * rtod_plan_load_weights folded into the conv, taken from the stream last loaded.  scale_host (may be NULL): `channels` doubles
+ * are copied out.  scale_dev (may be NULL): receives a device pointer to the same doubles, owned by the plan and valid until
+ * it is destroyed; the plan keeps them on the device with option "keep_block_inputs" only (else RTOD_E_STATE).  RTOD_E_ARG: a
+ * layer that is not a block (the message says why), channels != Cout; RTOD_E_STATE: before rtod_plan_load_weights. */
+int rtod_plan_conv_scale(const rtod_plan* plan, int layer, const double** scale_dev, double* scale_host, int channels);
+/* (new) rtod_plan_update_conv for a block conv, BatchNorm frozen: weight_oihw_host [Cout,Cin,k,k] replaces the conv's weights;
+ * its block of the image is packed again by the function rtod_plan_load_weights packs with, from the BatchNorm parameters of
+ * the stream last loaded and these weights, so the plan holds the bits a full load of the edited stream gives (the bias slot
+ * beta - mean * s included, unchanged).  Synchronises the device.  RTOD_E_ARG: a null pointer, a layer that is not a block;
+ * RTOD_E_STATE: before rtod_plan_load_weights. */
+int rtod_plan_update_conv_weight(rtod_plan* plan, int layer, const float* weight_oihw_host);
 
 /* replaces Darknet.forward                                   src/darknet.py:199-303
  * x_dev: [batch,3,H,W] NCHW float32; out_dev: [batch,N,5+C] (new contiguous tensor in the
@@ -437,6 +465,40 @@ int rtod_yolo_loss_grad(const float* pred_dev, int batch, int n_rows, int num_cl
 int rtod_conv1x1_wgrad_workspace(int batch, int cout, int cin, int pixels, size_t* bytes);
 int rtod_conv1x1_wgrad(const float* dz_dev, const float* x_dev, int batch, int cout, int cin, int pixels,
                        float* dw_dev, float* db_dev, void* workspace, size_t workspace_bytes, void* stream);
+/* ---- gradients of the detection BLOCK convs (the BatchNorm conv a head conv reads), BatchNorm frozen ------------------
+ * What torch's autograd leaves on conv.weight of the block under .eval() (running statistics, gamma / beta not trained).
+ * Data gradient through a 1x1 convolution z = W y with the derivative of the activation that produced y:
+ *   dx[b,c,p] = m(y[b,c,p]) * sum_o w[o,c] * dz[b,o,p],     m(y) = 1 for y > 0, else slope   (torch's leaky_relu backward; y == 0
+ *   takes the slope).  y_dev is the STORED output of the block conv (rtod_plan_read_layer): a leaky-ReLU keeps the sign of its
+ *   input, so no pre-activation is kept.  y_dev == NULL or slope == 1: linear, dx is the plain sum.
+ * w_dev [cout, cin] (the head conv's float32 weights), dz_dev [batch, cout, pixels], y_dev / dx_dev [batch, cin, pixels].
+ * Exact-fp32 MFMA: every dx element is ONE fmaf chain over o = 0 .. cout-1 (no K slices; ragged cout is padded with zeros, which
+ * leave the chain unchanged), then one fp32 multiplication by the slope where the mask says so.  Plain stores, no atomics:
+ * bit-identical from call to call.  Enqueues only.  RTOD_E_ARG: a null w / dz / dx, batch, cout or pixels < 1, cin not a
+ * positive multiple of 32, slope NaN, batch * pixels >= 2^31 - 64. */
+int rtod_conv1x1_dgrad(const float* w_dev, const float* dz_dev, const float* y_dev, float slope, int batch, int cout, int cin, int pixels,
+                       float* dx_dev, void* stream);
+/* Weight gradient of a size x size (1 or 3), stride 1, pad size / 2 convolution over dense NCHW maps:
+ *   dw_dev[o][c][ky][kx] = sum_{b,y,x} dz[b,o,y,x] * x[b,c,y+ky-pad,x+kx-pad]     (OIHW, overwritten; a tap outside the map adds an exact 0)
+ *   db_dev[o] = sum_{b,y,x} dz[b,o,y,x]                                           (may be NULL)
+ * row_scale_dev (double [cout], may be NULL): the reduced sum of every element of row o of dW is multiplied by it once,
+ * (float)((double)sum * row_scale[o]), one more rounding — the frozen BatchNorm scale of rtod_plan_conv_scale, which turns the
+ * gradient of the folded conv into that of conv.weight.  db is never scaled.
+ * The kernel of rtod_conv1x1_wgrad as an implicit GEMM with columns n = c * size * size + tap: exact-fp32 MFMA, one workgroup per
+ * (64 x 64 tile of the [cout, cin * size * size] matrix, K slice), K = batch * height * width summed in S contiguous slices that
+ * a second kernel adds in ascending order; no floating-point atomics; bit-identical from call to call and device to device.
+ * Slice rule (K and the number of tiles alone):
+ *   tiles = ceil(cout / 64) * ceil(cin * size * size / 64);   cap = min(16, ceil(1024 / tiles));
+ *   units = ceil(K / 8);   slice length L = 8 * ceil(units / cap);   S = ceil(K / L) <= cap.
+ * A grid of a thousand tiles fills the device unsliced (YOLOv3's 13 x 13 block: 1152 tiles, S = 1); the 26 x 26 block (288 tiles)
+ * gets at most 4 slices, the 52 x 52 block (72 tiles) at most 15.
+ * Workspace: 4 * S * (cout * cin * size * size + cout) bytes, 16-byte aligned (at most 19 MB for the YOLOv3 / YOLOv3-tiny blocks at
+ * 416 x 416, batch 8).  Enqueues only.  RTOD_E_ARG: a null pointer, batch / cout / height / width < 1, cin not a positive
+ * multiple of 32, size not 1 or 3, batch * height * width >= 2^31 - 64, cout * cin * size * size >= 2^31, a workspace that is
+ * too small or misaligned. */
+int rtod_conv_wgrad_workspace(int batch, int cout, int cin, int height, int width, int size, size_t* bytes);
+int rtod_conv_wgrad(const float* dz_dev, const float* x_dev, int batch, int cout, int cin, int height, int width, int size,
+                    const double* row_scale_dev, float* dw_dev, float* db_dev, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- optimiser step of a detection-head conv, on the stream ------------------------------------------
  * replaces optim.Adam(self.darknet.parameters(), lr=1e-2) + optimizer.step()     train.py:57, 412-425
@@ -477,6 +539,20 @@ typedef struct rtod_opt_step { int kind; float lr, beta1, beta2, eps; int step; 
 int rtod_plan_step_conv(rtod_plan* plan, int layer, const rtod_opt_step* opt,
                         float* weight_dev, float* bias_dev, const float* dw_dev, const float* db_dev,
                         float* m_w_dev, float* v_w_dev, float* m_b_dev, float* v_b_dev, void* stream);
+/* (new) The same step for a detection BLOCK conv (rtod_plan_head_blocks), BatchNorm frozen: the device twin of
+ * rtod_plan_update_conv_weight.  One kernel, one workgroup per output channel: the step above (same fp32 sequence, same host-derived
+ * scalars) on the RAW float32 master weight_dev [Cout, Cin, k, k] and the moments m_w_dev / v_w_dev of that shape, from dw_dev (what
+ * rtod_conv_wgrad wrote with the plan's scale), then the row is packed again as rtod_plan_load_weights packs a BatchNorm conv, with
+ * s = rtod_plan_conv_scale:   folded v = (float)((double)w' * s[o]);   split plans: channel exponent e from max |(double)w' * s[o]|
+ * (e = 13 - frexp exponent, held to -24 .. 40, 0 for an all-zero row), vs = v * 2^e, hi = f16_rn(vs), lo = f16_rn(vs - hi),
+ * inv[o] = 2^-e / 8;   fp32 plans: the panel element v.  The bias slot (beta - mean * s) and everything outside rows [0, Cout) x
+ * columns [0, Cin * k * k) of the conv's block keep their bits.  Enqueues only (legal under stream capture), ordered by the stream.
+ * RTOD_E_ARG, all decided before anything is enqueued: a null plan, opt, weight_dev or dw_dev; a layer that is not a block (no
+ * BatchNorm, a stem, a narrow conv, a pair member, any other conv: the message says which); the opt refusals of
+ * rtod_plan_step_conv (Adam needs both moment pointers).  RTOD_E_STATE: before rtod_plan_load_weights; a plan without option
+ * "keep_block_inputs" (its scales are not on the device). */
+int rtod_plan_step_conv_folded(rtod_plan* plan, int layer, const rtod_opt_step* opt, float* weight_dev, const float* dw_dev,
+                               float* m_w_dev, float* v_w_dev, void* stream);
 /* (tests, debugging) The packed weight image as it is on the device now, copied to the host; SYNCHRONISES the device.  Size query
  * as rtod_plan_pack_weights: *needed (if given) receives the image's floats, with out_host == NULL nothing else happens, else
  * capacity_floats must cover it (RTOD_E_SIZE).  RTOD_E_STATE before rtod_plan_load_weights. */

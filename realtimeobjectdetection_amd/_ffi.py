@@ -94,11 +94,19 @@ SIGNATURES = {
     "rtod_plan_step_conv": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(OptStep), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rtod_plan_read_packed_weights": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "rtod_plan_head_blocks": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int]),
+    "rtod_plan_conv_scale": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_void_p, C.c_int]),
+    "rtod_plan_update_conv_weight": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "rtod_plan_step_conv_folded": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(OptStep), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rtod_conv_wgrad_workspace": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    "rtod_conv_wgrad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_size_t, C.c_void_p]),
 }
 # ... and the entry points whose names hold a digit (the scan of the header for declared names reads lower-case letters and '_')
 SIGNATURES_DIGIT_NAMES = {
     "rtod_conv1x1_wgrad_workspace": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
     "rtod_conv1x1_wgrad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "rtod_conv1x1_dgrad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

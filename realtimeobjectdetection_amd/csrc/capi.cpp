@@ -423,6 +423,63 @@ int rtod_plan_head_layers(const rtod_plan* plan, int* conv_layers, int* input_la
     return n;
 }
 
+int rtod_conv_wgrad_workspace(int batch, int cout, int cin, int height, int width, int size, size_t* bytes) {
+    if (!bytes) { set_error("conv_wgrad_workspace: null pointer"); return RTOD_E_ARG; }
+    if (int rc = conv_wgrad_check_shape("conv_wgrad_workspace", batch, cout, cin, height, width, size)) return rc;
+    *bytes = conv_wgrad_workspace_bytes(batch, cout, cin, height, width, size);
+    return RTOD_OK;
+}
+
+int rtod_conv_wgrad(const float* dz_dev, const float* x_dev, int batch, int cout, int cin, int height, int width, int size,
+                    const double* row_scale_dev, float* dw_dev, float* db_dev, void* workspace, size_t workspace_bytes, void* stream) {
+    RTOD_GUARD_BEGIN
+    return launch_conv_wgrad(dz_dev, x_dev, batch, cout, cin, height, width, size, row_scale_dev, dw_dev, db_dev, workspace, workspace_bytes, (hipStream_t)stream);
+    RTOD_GUARD_END
+}
+
+int rtod_conv1x1_dgrad(const float* w_dev, const float* dz_dev, const float* y_dev, float slope, int batch, int cout, int cin, int pixels,
+                       float* dx_dev, void* stream) {
+    RTOD_GUARD_BEGIN
+    return launch_conv1x1_dgrad(w_dev, dz_dev, y_dev, slope, batch, cout, cin, pixels, dx_dev, (hipStream_t)stream);
+    RTOD_GUARD_END
+}
+
+int rtod_plan_head_blocks(const rtod_plan* plan, int* head_conv_layers, int* block_conv_layers, int* block_input_layers, int capacity) {
+    if (!plan || capacity < 0 || (capacity > 0 && (!head_conv_layers || !block_conv_layers || !block_input_layers))) { set_error("plan_head_blocks: bad args"); return RTOD_E_ARG; }
+    int n = 0;
+    for (const auto& L : plan->p.layers) {
+        if (!plan->p.feeds_yolo(L.index)) continue;
+        if (n < capacity) {
+            const int blk = plan->p.block_of_head(L.index);
+            head_conv_layers[n] = L.index; block_conv_layers[n] = blk; block_input_layers[n] = blk < 0 ? -1 : blk - 1;
+        }
+        ++n;
+    }
+    return n;
+}
+
+int rtod_plan_conv_scale(const rtod_plan* plan, int layer, const double** scale_dev, double* scale_host, int channels) {
+    RTOD_GUARD_BEGIN
+    if (!plan) { set_error("conv_scale: null plan"); return RTOD_E_ARG; }
+    return plan->p.conv_scale(layer, scale_dev, scale_host, channels);
+    RTOD_GUARD_END
+}
+
+int rtod_plan_update_conv_weight(rtod_plan* plan, int layer, const float* weight_oihw_host) {
+    RTOD_GUARD_BEGIN
+    if (!plan) { set_error("update_conv_weight: null plan"); return RTOD_E_ARG; }
+    return plan->p.update_conv_weight(layer, weight_oihw_host);
+    RTOD_GUARD_END
+}
+
+int rtod_plan_step_conv_folded(rtod_plan* plan, int layer, const rtod_opt_step* opt, float* weight_dev, const float* dw_dev,
+                               float* m_w_dev, float* v_w_dev, void* stream) {
+    RTOD_GUARD_BEGIN
+    if (!plan) { set_error("step_conv_folded: null plan"); return RTOD_E_ARG; }
+    return plan->p.step_conv_folded(layer, opt, weight_dev, dw_dev, m_w_dev, v_w_dev, (hipStream_t)stream);
+    RTOD_GUARD_END
+}
+
 int rtod_plan_update_conv(rtod_plan* plan, int layer, const float* weight_oihw_host, const float* bias_host) {
     RTOD_GUARD_BEGIN
     if (!plan) { set_error("update_conv: null plan"); return RTOD_E_ARG; }

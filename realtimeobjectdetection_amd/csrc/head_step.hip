@@ -9,6 +9,12 @@
 //           split plans  e = 13 - exponent(max|w'|) held to -24 .. 40 (0 for an all-zero channel), inv[o] = 2^-e / ACT_SCALE_F16S3,
 //                        vs = w' * 2^e (exact), hi = f16_rn(vs), lo = f16_rn(vs - hi) at half ((c / 32) * Npad + o) * 32 + c % 32
 //                        of the hi and lo planes.
+// The same kernel steps a detection BLOCK conv (rtod_plan_step_conv_folded: 1x1 or 3x3, BatchNorm frozen) and folds while it
+// re-packs, as pack_conv does for a BatchNorm conv: the master row is OIHW, q = c * taps + tap; with s = the frozen
+// gamma / sqrt(var + 1e-5) of channel o (a double), the folded weight is v = (float)((double)w' * s), the channel's exponent comes
+// from max |(double)w' * s| (kept as the double's integer bits), and v lands at panel[o * Kpad + tap * cin_p + c] or at half
+// (((c / 32) * taps + tap) * Npad + o) * 32 + c % 32.  There is no bias workgroup: the bias slot (beta - mean * s) keeps its bits.
+// A head conv is the case taps = 1, s = 1: (double)w' * 1.0 is w' itself, and the exponent of a double equals that of the float.
 // f32 -> f16 is the host's integer routine (f32_to_f16_rn), restated here: round to nearest even, subnormal halves kept, values at
 // or below 2^-25 to (signed) zero — independent of the denormal mode the library is built with.  Nothing outside channel rows
 // [0, Cout) and columns [0, Cin) of this conv's block is written: padding channels, padding K and other convs keep their bits.
@@ -53,12 +59,13 @@ struct StepArgs {
     float lr;                       // SGD: (float)lr.  Adam: (float)(lr / (1 - beta1^t))
     float beta2, omb1, omb2;        // (float)beta2, (float)(1 - beta1), (float)(1 - beta2)
     float bc2_sqrt, eps;            // (float)sqrt(1 - beta2^t), (float)eps
-    int cout, cin;
+    int cout, cin, taps, cin_p;     // taps = size * size; cin_p: channels per tap of the fp32 panel's K order
     int split;                      // 0: fp32 panel, 1: f16 hi / lo planes
     int Kpad, Npad;
-    float* w; float* b;             // masters
+    float* w; float* b;             // masters (b == NULL: a BatchNorm conv, whose bias slot is not written)
     const float* dw; const float* db;
     float* m_w; float* v_w; float* m_b; float* v_b;
+    const double* scale;            // BatchNorm convs: the frozen gamma / sqrt(var + 1e-5) per output channel (NULL: 1)
     float* panel;                   // fp32 plans: [Npad][Kpad]
     uint16_t* hi; uint16_t* lo;     // split plans: [Kpad / 32][Npad][32] halves each
     float* inv;                     // split plans: [Npad]
@@ -81,7 +88,7 @@ __device__ __forceinline__ float opt_update(const StepArgs& a, float w, float g,
 
 __global__ __launch_bounds__(256)
 void head_step_kernel(StepArgs a) {
-    __shared__ uint32_t smax[256];
+    __shared__ unsigned long long smax[256];
     const int tid = threadIdx.x;
     const int o = blockIdx.x;
     if (o == a.cout) {                                              // the bias vector: masters, moments and the image's copy
@@ -95,19 +102,25 @@ void head_step_kernel(StepArgs a) {
         }
         return;
     }
-    const int64_t row = (int64_t)o * a.cin;
-    uint32_t mx = 0;
-    for (int c = tid; c < a.cin; c += 256) {
+    const int n = a.cin * a.taps;                                   // the row of the OIHW master: q = c * taps + tap
+    const int64_t row = (int64_t)o * n;
+    const double sc = a.scale ? a.scale[o] : 1.0;                   // (double)w' * 1.0 is w' itself
+    unsigned long long mx = 0;
+    for (int q = tid; q < n; q += 256) {
         float m = 0.f, v = 0.f;
-        if (a.kind == 1) { m = a.m_w[row + c]; v = a.v_w[row + c]; }
-        const float nw = opt_update(a, a.w[row + c], a.dw[row + c], m, v);
-        if (a.kind == 1) { a.m_w[row + c] = m; a.v_w[row + c] = v; }
-        a.w[row + c] = nw;
-        const uint32_t ab = f32_bits(nw) & 0x7FFFFFFFu;
-        if (ab <= 0x7F800000u && ab > mx) mx = ab;                  // a NaN takes no part (std::max on the host keeps the other operand)
+        if (a.kind == 1) { m = a.m_w[row + q]; v = a.v_w[row + q]; }
+        const float nw = opt_update(a, a.w[row + q], a.dw[row + q], m, v);
+        if (a.kind == 1) { a.m_w[row + q] = m; a.v_w[row + q] = v; }
+        a.w[row + q] = nw;
+        // |(double)w' * s| as integer bits: order-preserving for non-negative doubles, exact
+        const unsigned long long ab = (unsigned long long)__double_as_longlong((double)nw * sc) & 0x7FFFFFFFFFFFFFFFull;
+        if (ab <= 0x7FF0000000000000ull && ab > mx) mx = ab;        // a NaN takes no part (std::max on the host keeps the other operand)
     }
     if (!a.split) {
-        for (int c = tid; c < a.cin; c += 256) a.panel[(int64_t)o * a.Kpad + c] = a.w[row + c];
+        for (int q = tid; q < n; q += 256) {
+            const int c = q / a.taps, tap = q - c * a.taps;
+            a.panel[(int64_t)o * a.Kpad + tap * a.cin_p + c] = (float)((double)a.w[row + q] * sc);
+        }
         return;
     }
     smax[tid] = mx;
@@ -117,18 +130,20 @@ void head_step_kernel(StepArgs a) {
         __syncthreads();
     }
     mx = smax[0];
-    // frexp(mx) = (f, ex), f in [0.5, 1): ex = floor(log2 mx) + 1; e = 13 - ex.  A subnormal fp32 maximum gives e > 40 either way
+    // frexp(mx) = (f, ex), f in [0.5, 1): ex = floor(log2 mx) + 1; e = 13 - ex.  A subnormal maximum gives e > 40 either way
     int e = 0;
-    if (mx != 0) e = 12 - ((int)(mx >> 23) - 127);
+    if (mx != 0) e = 12 - ((int)(mx >> 52) - 1023);
     e = max(-24, min(40, e));
     const float ps = __uint_as_float((uint32_t)(127 + e) << 23);            // 2^e
     if (tid == 0) a.inv[o] = __uint_as_float((uint32_t)(127 - e - 3) << 23); // 2^-e / 8 (ACT_SCALE_F16S3 = 8)
-    for (int c = tid; c < a.cin; c += 256) {
-        const float vs = a.w[row + c] * ps;                         // exact: a power of two
+    for (int q = tid; q < n; q += 256) {
+        const int c = q / a.taps, tap = q - c * a.taps;
+        const float fv = (float)((double)a.w[row + q] * sc);        // the fp32 folded weight
+        const float vs = fv * ps;                                   // one rounding, as (float)((double)fv * 2^e): exact but for subnormal results
         const uint32_t h = f32_to_f16_rn_dev(vs);
         const float rest = vs - f16_to_f32_dev(h);
         const uint32_t l = f32_to_f16_rn_dev(rest);
-        const int64_t idx = ((int64_t)(c >> 5) * a.Npad + o) * 32 + (c & 31);
+        const int64_t idx = ((int64_t)((c >> 5) * a.taps + tap) * a.Npad + o) * 32 + (c & 31);
         a.hi[idx] = (uint16_t)h;
         a.lo[idx] = (uint16_t)l;
     }
@@ -139,14 +154,15 @@ static_assert(ACT_SCALE_F16S3 == 8.0f, "head_step_kernel builds 2^-e / ACT_SCALE
 int launch_head_step(const HeadStepLaunch& h, hipStream_t s) {
     StepArgs a;
     a.kind = h.kind; a.lr = h.lr; a.beta2 = h.beta2; a.omb1 = h.omb1; a.omb2 = h.omb2; a.bc2_sqrt = h.bc2_sqrt; a.eps = h.eps;
-    a.cout = h.cout; a.cin = h.cin; a.split = h.split; a.Kpad = h.Kpad; a.Npad = h.Npad;
+    a.cout = h.cout; a.cin = h.cin; a.taps = h.taps; a.cin_p = h.cin_p; a.split = h.split; a.Kpad = h.Kpad; a.Npad = h.Npad;
+    a.scale = h.scale;
     a.w = h.w; a.b = h.b; a.dw = h.dw; a.db = h.db; a.m_w = h.m_w; a.v_w = h.v_w; a.m_b = h.m_b; a.v_b = h.v_b;
     a.panel = h.blk;
     a.hi = reinterpret_cast<uint16_t*>(h.blk);
     a.lo = reinterpret_cast<uint16_t*>(h.blk + h.lo_off);
     a.inv = h.blk + h.inv_off;
     a.bias = h.blk + h.bias_off;
-    hipLaunchKernelGGL(head_step_kernel, dim3((unsigned)(h.cout + 1)), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(head_step_kernel, dim3((unsigned)(h.cout + (h.b ? 1 : 0))), dim3(256), 0, s, a);   // no bias workgroup for a BatchNorm conv
     return hip_fail(hipGetLastError(), "head_step launch");
 }
 

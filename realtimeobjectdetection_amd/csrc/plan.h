@@ -93,7 +93,7 @@ struct PackedConv {
 };
 
 // One struct, defined over five files by concern (the run-time fused form of every launch is decided in one place, Plan::form in plan_forward.cpp): plan_cfg.cpp (parse, resolve_shapes: no HIP call), plan_build.cpp (options, buffer
-// planning, weight layout, describe), plan_weights.cpp (pack_conv, pack_weights, load_weights, update_conv, step_conv), plan_tiles.cpp (which kernel variant a conv
+// planning, weight layout, describe), plan_weights.cpp (pack_conv, pack_weights, load_weights, update_conv, step_conv and their twins for the detection blocks), plan_tiles.cpp (which kernel variant a conv
 // launch runs, autotune), plan_forward.cpp (the launch list on a stream, launch records).
 struct Plan {
     int height = 0, width = 0, max_batch = 0, device = 0;
@@ -145,6 +145,8 @@ struct Plan {
     bool opt_stem_pool = false;       // precisions 1 / 2: a 3x3 / stride 1 / 16-filter layer 0 runs the split-f16 stem of conv_stem16_f16s3.hip (no pack launch)
     bool opt_keep_head_inputs = false; // the buffer every conv in front of a [yolo] layer reads stays live to the end of the forward (rtod_plan_read_layer after it:
                                       // the activations of rtod_conv1x1_wgrad); liveness only: launches, tiles and output bits are unchanged
+    bool opt_keep_block_inputs = false; // ... and the buffer every BLOCK conv reads (block_shape_ok: the BatchNorm conv a head conv reads): the activations of
+                                      // rtod_conv_wgrad.  Liveness only as well; the frozen BatchNorm scales then also live on the device (d_block_scale)
     bool opt_fuse_stem_pool = true;   // ... with the 2x2 / stride-2 max-pool that follows it in the same kernel where the plan allows it (off: A/B and tests)
     int opt_force_f16s3_variant = -1; // >= 0: tile variant for every split-f16 conv (>= BAND_VARIANT_BASE: band layers)
     int opt_force_f32_variant = -1;   // >= 0: tile variant for every exact-fp32 conv
@@ -170,6 +172,19 @@ struct Plan {
     int step_conv(int layer, const rtod_opt_step* opt, float* weight, float* bias, const float* dw, const float* db,
                   float* m_w, float* v_w, float* m_b, float* v_b, hipStream_t s);   // optimiser step + re-pack on the stream (rtod_plan_step_conv)
     int read_packed_weights(float* out, size_t capacity, size_t* needed) const;     // the device image back on the host (synchronises)
+    // detection blocks (rtod_plan_head_blocks): the BatchNorm conv that a head conv reads, trained with BatchNorm frozen
+    bool block_shape_ok(int layer) const;                                           // the cfg's part of the definition (what keep_block_inputs keeps alive)
+    int block_of_head(int head_conv_layer) const;                                   // the block conv of that head conv, or -1
+    int block_conv(const char* who, int layer, size_t& slot) const;                 // the slot of a block conv, or why `layer` is none
+    int update_conv_weight(int layer, const float* weight_oihw);                    // re-pack and upload one block conv, BatchNorm as loaded (rtod_plan_update_conv_weight)
+    int step_conv_folded(int layer, const rtod_opt_step* opt, float* weight, const float* dw, float* m_w, float* v_w, hipStream_t s);   // rtod_plan_step_conv_folded
+    int conv_scale(int layer, const double** scale_dev, double* scale_host, int channels) const;   // rtod_plan_conv_scale
+    int opt_scalars(const char* who, const rtod_opt_step* opt, bool moments, HeadStepLaunch& h) const;   // the checked step scalars of step_conv / step_conv_folded
+    std::map<int, std::vector<float>> block_bn;     // block conv layer -> its [beta, gamma, mean, var] of the stream last loaded
+    std::map<int, std::vector<double>> block_scale; // ... -> gamma / sqrt(var + 1e-5), the frozen scale pack_conv folds
+    std::map<int, int64_t> block_scale_off;         // ... -> offset in d_block_scale (doubles)
+    double* d_block_scale = nullptr;                // option keep_block_inputs: the scales on the device, allocated at the first load
+    int64_t block_scale_doubles = 0;                // ... and how many doubles that allocation holds
     bool feeds_yolo(int layer) const { return layers[layer].type == LT_CONV && layer + 1 < (int)layers.size() && layers[layer + 1].type == LT_YOLO; }
     int forward(const float* x, int batch, float* out, hipStream_t s, float* launch_ms, bool tune = false);
     // the launches of one LK_CONV / LK_STEM step of forward, in order

@@ -38,6 +38,7 @@ Plan::~Plan() {
     if (d_bn_stats) (void)hipFree(d_bn_stats);
     if (d_bn_partial) (void)hipFree(d_bn_partial);
     if (d_bn_raw) (void)hipFree(d_bn_raw);
+    if (d_block_scale) (void)hipFree(d_block_scale);
     if (d_weights) (void)hipFree(d_weights);
 }
 
@@ -63,6 +64,7 @@ int Plan::set_option(const char* name, int value) {
         {"stem_kernel", &Plan::opt_stem_kernel}, {"band_kernel", &Plan::opt_band_kernel}, {"fuse_shortcut", &Plan::opt_fuse_shortcut},
         {"fuse_decode", &Plan::opt_fuse_decode}, {"zero_copy_concat", &Plan::opt_zero_copy_concat}, {"narrow_cin", &Plan::opt_narrow_cin},
         {"stem_pool", &Plan::opt_stem_pool}, {"fuse_stem_pool", &Plan::opt_fuse_stem_pool}, {"keep_head_inputs", &Plan::opt_keep_head_inputs},
+        {"keep_block_inputs", &Plan::opt_keep_block_inputs},
     };
     const std::string k(name);
     bool* flag = nullptr; int* num = nullptr;
@@ -296,6 +298,11 @@ int Plan::plan_buffers() {
     if (opt_keep_head_inputs)
         for (const auto& l : launches)
             if (l.kind == LK_CONV && feeds_yolo(l.layer)) touch(buf_of_layer(l.in_layer), n);
+    // option keep_block_inputs: likewise what the conv in front of a head conv reads, where the cfg makes that conv a detection
+    // block (block_shape_ok; a route is kept as its concat buffer)
+    if (opt_keep_block_inputs)
+        for (const auto& l : launches)
+            if (l.kind == LK_CONV && l.layer + 1 < n && feeds_yolo(l.layer + 1) && block_shape_ok(l.layer)) touch(buf_of_layer(l.in_layer), n);
     // a concat buffer is live from its first producer to its last consumer: touches above cover both
     for (int b = 0; b < NB; ++b) {
         if (bufs[b].last < 0) { bufs[b].first = bufs[b].last = 0; }      // never used (dead layer): still give it space
@@ -304,6 +311,30 @@ int Plan::plan_buffers() {
     assign_arena();
     layout_weights();
     return RTOD_OK;
+}
+
+// Detection blocks.  The cfg's part of the definition: a BatchNorm conv, 1x1 or 3x3 / stride 1 / same padding, leaky or linear,
+// reading a multiple of 32 channels, whose BatchNorm is folded (no batch statistics).  Layer 0 reads three channels and is none.
+bool Plan::block_shape_ok(int layer) const {
+    if (layer < 1 || layer >= (int)layers.size() || opt_bn_batch_stats) return false;
+    const Layer& L = layers[layer];
+    return L.type == LT_CONV && L.bn && (L.size == 1 || L.size == 3) && L.stride == 1 && L.pad == L.size / 2 && L.act <= 1 &&
+           L.cin % 32 == 0 && L.fused_into < 0;
+}
+
+// ... and the plan's part: packed in one of the two generic layouts (no stem, not narrow), neither host nor guest of a
+// fused-pointwise candidate pair (candidates, not forms, as replaceable_conv), its output stored where rtod_plan_read_layer finds it
+int Plan::block_of_head(int head) const {
+    if (head < 1 || head >= (int)layers.size() || !feeds_yolo(head) || !block_shape_ok(head - 1)) return -1;
+    const int layer = head - 1;
+    for (const auto& l : launches) {
+        if (l.kind != LK_CONV || l.layer != layer || l.conv_slot < 0) continue;
+        const PackedConv& pc = convs[l.conv_slot];
+        if (pc.stem || pc.stem16 || pc.narrow || l.pw_guest >= 0 || l.pw_host >= 0 || l.out_layer != layer) return -1;
+        if (pc.Kpad < pc.K || layers[layer].cout > pc.Npad || pc.cin_p != layers[layer].cin) return -1;
+        return layer_form(layer).readable && layers[layer].buf >= 0 ? layer : -1;
+    }
+    return -1;
 }
 
 bool Plan::uses_split(const Layer& L) const {

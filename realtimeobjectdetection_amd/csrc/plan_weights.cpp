@@ -204,16 +204,27 @@ int Plan::step_conv(int layer, const rtod_opt_step* opt, float* weight, float* b
     const PackedConv& pc = convs[slot];
     if (L.size != 1 || pc.stem || pc.stem16 || pc.narrow) { set_error("step_conv: layer %d is not a 1x1 conv of the generic layouts (size %d%s)", layer, L.size, pc.narrow ? ", narrow" : pc.stem ? ", stem" : ""); return RTOD_E_ARG; }
     if (pc.Kpad < L.cin || L.cout > pc.Npad || (pc.split && L.cin % 32 != 0)) { set_error("step_conv: layer %d has an unexpected packed layout", layer); return RTOD_E_ARG; }
-    if (opt->kind != 0 && opt->kind != 1) { set_error("step_conv: kind %d (0 = SGD, 1 = Adam)", opt->kind); return RTOD_E_ARG; }
-    if (!std::isfinite(opt->lr)) { set_error("step_conv: lr is not finite"); return RTOD_E_ARG; }
     HeadStepLaunch h;
+    if (int rc = opt_scalars("step_conv", opt, m_w && v_w && m_b && v_b, h)) return rc;
+    if (!weights_loaded || !d_weights) { set_error("step_conv: call rtod_plan_load_weights first"); return RTOD_E_STATE; }
+    h.cout = L.cout; h.cin = L.cin; h.taps = 1; h.cin_p = pc.cin_p; h.split = pc.split ? 1 : 0; h.Kpad = pc.Kpad; h.Npad = pc.Npad;
+    h.w = weight; h.b = bias; h.dw = dw; h.db = db; h.m_w = m_w; h.v_w = v_w; h.m_b = m_b; h.v_b = v_b;
+    h.blk = d_weights + pc.w_off;
+    h.lo_off = pc.wl_off - pc.w_off; h.inv_off = pc.s_off - pc.w_off; h.bias_off = pc.b_off - pc.w_off;
+    return launch_head_step(h, s);
+}
+
+// The scalars of one step, checked and derived in double (step_conv, step_conv_folded); `moments`: every moment buffer Adam needs is there
+int Plan::opt_scalars(const char* who, const rtod_opt_step* opt, bool moments, HeadStepLaunch& h) const {
+    if (opt->kind != 0 && opt->kind != 1) { set_error("%s: kind %d (0 = SGD, 1 = Adam)", who, opt->kind); return RTOD_E_ARG; }
+    if (!std::isfinite(opt->lr)) { set_error("%s: lr is not finite", who); return RTOD_E_ARG; }
     h.kind = opt->kind;
     h.lr = opt->lr;
     if (opt->kind == 1) {
-        if (opt->step < 1) { set_error("step_conv: Adam needs the 1-based step count, got %d", opt->step); return RTOD_E_ARG; }
-        if (!(opt->beta1 >= 0.f && opt->beta1 < 1.f) || !(opt->beta2 >= 0.f && opt->beta2 < 1.f)) { set_error("step_conv: Adam betas must lie in [0, 1)"); return RTOD_E_ARG; }
-        if (!(opt->eps >= 0.f)) { set_error("step_conv: Adam eps must be >= 0"); return RTOD_E_ARG; }
-        if (!m_w || !v_w || !m_b || !v_b) { set_error("step_conv: Adam needs the four moment buffers"); return RTOD_E_ARG; }
+        if (opt->step < 1) { set_error("%s: Adam needs the 1-based step count, got %d", who, opt->step); return RTOD_E_ARG; }
+        if (!(opt->beta1 >= 0.f && opt->beta1 < 1.f) || !(opt->beta2 >= 0.f && opt->beta2 < 1.f)) { set_error("%s: Adam betas must lie in [0, 1)", who); return RTOD_E_ARG; }
+        if (!(opt->eps >= 0.f)) { set_error("%s: Adam eps must be >= 0", who); return RTOD_E_ARG; }
+        if (!moments) { set_error("%s: Adam needs the moment buffers", who); return RTOD_E_ARG; }
         const double b1 = shortest_decimal(opt->beta1), b2 = shortest_decimal(opt->beta2);
         h.lr = (float)(shortest_decimal(opt->lr) / (1.0 - std::pow(b1, (double)opt->step)));
         h.bc2_sqrt = (float)std::sqrt(1.0 - std::pow(b2, (double)opt->step));
@@ -222,9 +233,80 @@ int Plan::step_conv(int layer, const rtod_opt_step* opt, float* weight, float* b
         h.omb2 = (float)(1.0 - b2);
         h.eps = opt->eps;
     }
-    if (!weights_loaded || !d_weights) { set_error("step_conv: call rtod_plan_load_weights first"); return RTOD_E_STATE; }
-    h.cout = L.cout; h.cin = L.cin; h.split = pc.split ? 1 : 0; h.Kpad = pc.Kpad; h.Npad = pc.Npad;
-    h.w = weight; h.b = bias; h.dw = dw; h.db = db; h.m_w = m_w; h.v_w = v_w; h.m_b = m_b; h.v_b = v_b;
+    return RTOD_OK;
+}
+
+// The slot of a detection block conv (rtod_plan_head_blocks), or why `layer` is none: what update_conv_weight and step_conv_folded accept
+int Plan::block_conv(const char* who, int layer, size_t& slot) const {
+    if (layer < 0 || layer >= (int)layers.size() || layers[layer].type != LT_CONV) { set_error("%s: layer %d is not a convolution", who, layer); return RTOD_E_ARG; }
+    if (!layers[layer].bn) { set_error("%s: layer %d has no BatchNorm (rtod_plan_update_conv / rtod_plan_step_conv take such convs)", who, layer); return RTOD_E_ARG; }
+    if (block_of_head(layer + 1) != layer) {
+        const PackedConv* pc = nullptr; const Launch* ll = nullptr;
+        for (const auto& l : launches) if ((l.kind == LK_CONV || l.kind == LK_STEM) && l.layer == layer && l.conv_slot >= 0) { ll = &l; pc = &convs[l.conv_slot]; }
+        const char* why = opt_bn_batch_stats ? "the plan runs batch-statistics BatchNorm: the conv is not folded"
+                        : pc && (pc->stem || pc->stem16) ? "a stem layout" : pc && pc->narrow ? "a narrow (Cin == 16) layout"
+                        : ll && (ll->pw_guest >= 0 || ll->pw_host >= 0) ? "part of a fused pointwise pair"
+                        : "not the 1x1 / 3x3 stride-1 leaky or linear BatchNorm conv that a detection-head conv reads";
+        set_error("%s: layer %d is not a detection block (%s)", who, layer, why);
+        return RTOD_E_ARG;
+    }
+    for (const auto& l : launches) if (l.kind == LK_CONV && l.layer == layer) slot = (size_t)l.conv_slot;
+    return RTOD_OK;
+}
+
+// The frozen BatchNorm scale of a block conv, as pack_conv folds it: on the host (copied out) and, with option keep_block_inputs, on the device
+int Plan::conv_scale(int layer, const double** scale_dev, double* scale_host, int channels) const {
+    size_t slot = 0;
+    if (int rc = block_conv("conv_scale", layer, slot)) return rc;
+    if (channels != layers[layer].cout) { set_error("conv_scale: layer %d has %d output channels, %d given", layer, layers[layer].cout, channels); return RTOD_E_ARG; }
+    const auto it = block_scale.find(layer);
+    if (!weights_loaded || it == block_scale.end()) { set_error("conv_scale: call rtod_plan_load_weights first"); return RTOD_E_STATE; }
+    if (scale_dev) {
+        if (!d_block_scale) { set_error("conv_scale: the scales live on the device with option keep_block_inputs only"); return RTOD_E_STATE; }
+        *scale_dev = d_block_scale + block_scale_off.at(layer);
+    }
+    if (scale_host) memcpy(scale_host, it->second.data(), sizeof(double) * (size_t)channels);
+    return RTOD_OK;
+}
+
+// The host twin of step_conv_folded, update_conv for a block conv: the stream of the conv is assembled from the BatchNorm parameters
+// kept at load time and the new OIHW weights and goes through pack_conv, so the block holds the bits a full load of the edited
+// stream gives.  Synchronises the device.
+int Plan::update_conv_weight(int layer, const float* weight_oihw) {
+    if (!weight_oihw) { set_error("update_conv_weight: null pointer"); return RTOD_E_ARG; }
+    size_t slot = 0;
+    if (int rc = block_conv("update_conv_weight", layer, slot)) return rc;
+    const auto it = block_bn.find(layer);
+    if (!weights_loaded || !d_weights || it == block_bn.end()) { set_error("update_conv_weight: call rtod_plan_load_weights first"); return RTOD_E_STATE; }
+    const Layer& L = layers[layer];
+    const PackedConv& pc = convs[slot];
+    const int64_t nw = (int64_t)L.cout * L.cin * L.size * L.size;
+    std::vector<float> stream(it->second);
+    stream.insert(stream.end(), weight_oihw, weight_oihw + nw);
+    std::vector<float> blk((size_t)conv_block_floats(slot), 0.0f);
+    pack_conv(pc, stream.data(), blk.data());
+    RTOD_HIP(hipSetDevice(device));
+    RTOD_HIP(hipDeviceSynchronize());
+    RTOD_HIP(hipMemcpy(d_weights + pc.w_off, blk.data(), sizeof(float) * blk.size(), hipMemcpyHostToDevice));
+    RTOD_HIP(hipDeviceSynchronize());
+    return RTOD_OK;
+}
+
+// The device twin: head_step.hip's kernel on the raw float32 master [Cout, Cin, k, k], folding the frozen scale while it re-packs.
+// No bias: beta - mean * s does not depend on the weights.  Enqueues only; every refusal is decided before anything is enqueued.
+int Plan::step_conv_folded(int layer, const rtod_opt_step* opt, float* weight, const float* dw, float* m_w, float* v_w, hipStream_t s) {
+    if (!opt || !weight || !dw) { set_error("step_conv_folded: null pointer"); return RTOD_E_ARG; }
+    size_t slot = 0;
+    if (int rc = block_conv("step_conv_folded", layer, slot)) return rc;
+    HeadStepLaunch h;
+    if (int rc = opt_scalars("step_conv_folded", opt, m_w && v_w, h)) return rc;
+    if (!weights_loaded || !d_weights) { set_error("step_conv_folded: call rtod_plan_load_weights first"); return RTOD_E_STATE; }
+    if (!d_block_scale) { set_error("step_conv_folded: the plan needs option keep_block_inputs (it puts the frozen scales on the device)"); return RTOD_E_STATE; }
+    const Layer& L = layers[layer];
+    const PackedConv& pc = convs[slot];
+    h.cout = L.cout; h.cin = L.cin; h.taps = L.size * L.size; h.cin_p = pc.cin_p; h.split = pc.split ? 1 : 0; h.Kpad = pc.Kpad; h.Npad = pc.Npad;
+    h.w = weight; h.dw = dw; h.m_w = m_w; h.v_w = v_w;
+    h.scale = d_block_scale + block_scale_off.at(layer);
     h.blk = d_weights + pc.w_off;
     h.lo_off = pc.wl_off - pc.w_off; h.inv_off = pc.s_off - pc.w_off; h.bias_off = pc.b_off - pc.w_off;
     return launch_head_step(h, s);
@@ -270,6 +352,31 @@ int Plan::load_weights(const float* w, size_t n) {
             scratch_floats = KS_SCRATCH_FLOATS;                                   // 32 MB: L2 / Infinity-Cache resident; larger panels run the in-workgroup schedule
             RTOD_HIP(hipMalloc((void**)&d_scratch, sizeof(float) * (size_t)scratch_floats));
         }
+    }
+    // detection blocks: the BatchNorm parameters of the stream (update_conv_weight assembles its stream from them) and the frozen
+    // scale pack_conv folded, on the host; with option keep_block_inputs on the device too, so that a later step allocates nothing
+    block_bn.clear(); block_scale.clear(); block_scale_off.clear();
+    std::vector<double> scales;
+    for (const auto& L : layers) {
+        if (!feeds_yolo(L.index)) continue;
+        const int blk = block_of_head(L.index);
+        if (blk < 0) continue;
+        const int C = layers[blk].cout;
+        const float* p = w + layers[blk].w_off;
+        block_bn[blk].assign(p, p + 4 * C);
+        std::vector<double>& sc = block_scale[blk];
+        sc.resize(C);
+        for (int o = 0; o < C; ++o) sc[o] = (double)p[C + o] / std::sqrt((double)p[3 * C + o] + 1e-5);
+        block_scale_off[blk] = (int64_t)scales.size();
+        scales.insert(scales.end(), sc.begin(), sc.end());
+    }
+    if (opt_keep_block_inputs && !scales.empty()) {
+        if ((int64_t)scales.size() > block_scale_doubles) {           // first load (a later one never has more blocks today; if it had, the buffer grows)
+            if (d_block_scale) { RTOD_HIP(hipDeviceSynchronize()); RTOD_HIP(hipFree(d_block_scale)); d_block_scale = nullptr; block_scale_doubles = 0; }
+            RTOD_HIP(hipMalloc((void**)&d_block_scale, sizeof(double) * scales.size()));
+            block_scale_doubles = (int64_t)scales.size();
+        }
+        RTOD_HIP(hipMemcpy(d_block_scale, scales.data(), sizeof(double) * scales.size(), hipMemcpyHostToDevice));
     }
     RTOD_HIP(hipMemcpy(d_weights, packed.data(), sizeof(float) * (size_t)packed_floats, hipMemcpyHostToDevice));
     RTOD_HIP(hipDeviceSynchronize());

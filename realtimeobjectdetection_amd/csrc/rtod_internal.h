@@ -367,15 +367,26 @@ int64_t wgrad_slice_len(int64_t K);
 size_t wgrad_workspace_bytes(int batch, int cout, int cin, int pixels);
 int launch_conv1x1_wgrad(const float* dz, const float* x, int batch, int cout, int cin, int pixels, float* dw, float* db,
                          void* ws, size_t ws_bytes, hipStream_t s);
-// optimiser step of one 1x1 conv without BatchNorm fused with the re-pack of its block of the weight image (head_step.hip).
-// The scalars are what the host derived in double (Plan::step_conv); blk = d_weights + the conv's w_off, the offsets in floats
+// ... of a 1x1 or 3x3 convolution, K slices by K and the number of tiles, an optional double scale per row of dW (wgrad.hip)
+int64_t conv_wgrad_slice_len(int64_t K, int64_t tiles);
+size_t conv_wgrad_workspace_bytes(int batch, int cout, int cin, int h, int w, int size);
+int conv_wgrad_check_shape(const char* who, int batch, int cout, int cin, int h, int w, int size);
+int launch_conv_wgrad(const float* dz, const float* x, int batch, int cout, int cin, int h, int w, int size, const double* row_scale,
+                      float* dw, float* db, void* ws, size_t ws_bytes, hipStream_t s);
+// data gradient of a 1x1 convolution with the leaky-ReLU derivative of the stored activation in its epilogue (dgrad.hip)
+int launch_conv1x1_dgrad(const float* w, const float* dz, const float* y, float slope, int batch, int cout, int cin, int pixels,
+                         float* dx, hipStream_t s);
+// optimiser step of one conv fused with the re-pack of its block of the weight image (head_step.hip): a 1x1 conv without BatchNorm
+// with its bias (Plan::step_conv), or a conv whose frozen BatchNorm scale is folded while it re-packs (b == NULL, scale given:
+// Plan::step_conv_folded).  The scalars are what the host derived in double; blk = d_weights + the conv's w_off, the offsets in floats
 struct HeadStepLaunch {
     int kind = 0;                                   // 0 SGD, 1 Adam
     float lr = 0.f, beta2 = 0.f, omb1 = 0.f, omb2 = 0.f, bc2_sqrt = 1.f, eps = 0.f;
-    int cout = 0, cin = 0, split = 0, Kpad = 0, Npad = 0;
+    int cout = 0, cin = 0, taps = 1, cin_p = 0, split = 0, Kpad = 0, Npad = 0;
     float *w = nullptr, *b = nullptr;
     const float *dw = nullptr, *db = nullptr;
     float *m_w = nullptr, *v_w = nullptr, *m_b = nullptr, *v_b = nullptr;
+    const double* scale = nullptr;
     float* blk = nullptr;
     int64_t lo_off = 0, inv_off = 0, bias_off = 0;
 };

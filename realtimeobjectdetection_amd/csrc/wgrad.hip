@@ -18,6 +18,13 @@
 //   units = ceil(K / 8);  slice length = 8 * ceil(units / 16);  S = ceil(K / slice length)  (<= 16)
 // Every accumulator is an fmaf chain over its slice in a fixed permutation of k; db is a plain fp32 sum over the slice in
 // ascending k, kept by the workgroups of the first column of tiles.
+//
+// 3x3 convs (rtod_conv_wgrad, TAPS = 9).  The same kernel as an implicit GEMM: the column index is n = c * 9 + tap, OIHW order, so
+// the dW stores stay coalesced, and B[n][k] = x[b, c, y + ky - 1, x + kx - 1], an exact zero outside the map.  A thread's eight
+// columns (channel and tap offsets) do not depend on k and are resolved once; k -> (b, y, x) costs two divisions per staged chunk.
+// The 1x1 instance (TAPS = 1) is the kernel above, instruction for instruction.  The slice count of that entry also sees the
+// number of tiles (conv_wgrad_slices: a 13 x 13 block has a thousand tiles already and is not sliced), and its reduce kernel
+// multiplies the reduced sum of a row by a caller-supplied double once — the frozen BatchNorm scale of the conv.
 #include "rtod_internal.h"
 
 namespace rtod {
@@ -41,10 +48,29 @@ size_t wgrad_workspace_bytes(int batch, int cout, int cin, int pixels) {
     return sizeof(float) * (size_t)S * ((size_t)cout * cin + (size_t)cout);
 }
 
-// part: [S][cout][cin] slice sums of dW, then [S][cout] slice sums of db
+// the slice count of rtod_conv_wgrad (rtod.h): as above with at most min(16, ceil(1024 / tiles)) slices
+constexpr int64_t WG_TILE_TARGET = 1024;
+static int64_t conv_wgrad_max_slices(int64_t tiles) { return std::min<int64_t>(WG_MAX_SLICES, (WG_TILE_TARGET + tiles - 1) / tiles); }
+int64_t conv_wgrad_slice_len(int64_t K, int64_t tiles) {
+    const int64_t units = (K + 7) / 8, cap = conv_wgrad_max_slices(tiles);
+    return 8 * ((units + cap - 1) / cap);
+}
+static int64_t conv_wgrad_tiles(int cout, int cin, int size) {
+    return (int64_t)((cout + WG_T - 1) / WG_T) * (((int64_t)cin * size * size + WG_T - 1) / WG_T);
+}
+static int64_t conv_wgrad_slices(int64_t K, int64_t tiles) { const int64_t L = conv_wgrad_slice_len(K, tiles); return (K + L - 1) / L; }
+
+size_t conv_wgrad_workspace_bytes(int batch, int cout, int cin, int h, int w, int size) {
+    const int64_t S = conv_wgrad_slices((int64_t)batch * h * w, conv_wgrad_tiles(cout, cin, size));
+    return sizeof(float) * (size_t)S * ((size_t)cout * cin * size * size + (size_t)cout);
+}
+
+// part: [S][cout][ncol] slice sums of dW (ncol = cin * TAPS), then [S][cout] slice sums of db.  TAPS == 1: H and W are not read
+template <int TAPS>
 __global__ __launch_bounds__(256)
-void wgrad_slice_kernel(const float* __restrict__ dz, const float* __restrict__ x, int cout, int cin, int pixels, int K, int slice_len,
+void wgrad_slice_kernel(const float* __restrict__ dz, const float* __restrict__ x, int cout, int cin, int pixels, int H, int W, int K, int slice_len,
                         int grid_m, int grid_n, float* __restrict__ part, float* __restrict__ part_db) {
+    const int ncol = cin * TAPS;
     __shared__ __attribute__((aligned(16))) float smem[2 * WG_T * WG_LD];
     float* sA = smem;
     float* sB = smem + WG_T * WG_LD;
@@ -68,16 +94,35 @@ void wgrad_slice_kernel(const float* __restrict__ dz, const float* __restrict__ 
 
     // one register stage, as in conv_igemm_f32.hip: chunk kc + 1 is fetched while chunk kc computes
     float ra[WG_T / 8], rb[WG_T / 8];
+    int col_c[WG_T / 8], col_dy[WG_T / 8], col_dx[WG_T / 8];      // TAPS > 1: channel and tap offsets of this thread's columns
+    if (TAPS > 1) {
+#pragma unroll
+        for (int i = 0; i < WG_T / 8; ++i) {
+            const int n = bn * WG_T + row0 + i * 8;
+            const int tap = n % TAPS;
+            col_c[i] = n / TAPS;
+            col_dy[i] = tap / 3 - 1;
+            col_dx[i] = tap % 3 - 1;
+        }
+    }
     auto gload = [&](int kc) {
         const int k = kc + kk;
         const bool kok = k < k1;
         const int b = kok ? k / pixels : 0;
         const int p = kok ? k - b * pixels : 0;
+        const int py = TAPS > 1 ? p / W : 0;
+        const int px = TAPS > 1 ? p - py * W : 0;
 #pragma unroll
         for (int i = 0; i < WG_T / 8; ++i) {
             const int o = bm * WG_T + row0 + i * 8, c = bn * WG_T + row0 + i * 8;
             ra[i] = (kok && o < cout) ? dz[((int64_t)b * cout + o) * pixels + p] : 0.f;
-            rb[i] = (kok && c < cin) ? x[((int64_t)b * cin + c) * pixels + p] : 0.f;
+            if (TAPS == 1) {
+                rb[i] = (kok && c < cin) ? x[((int64_t)b * cin + c) * pixels + p] : 0.f;
+            } else {
+                const int yy = py + col_dy[i], xx = px + col_dx[i];
+                const bool in = kok && c < ncol && yy >= 0 && yy < H && xx >= 0 && xx < W;
+                rb[i] = in ? x[((int64_t)b * cin + col_c[i]) * pixels + yy * W + xx] : 0.f;
+            }
         }
     };
     gload(k0);
@@ -105,12 +150,12 @@ void wgrad_slice_kernel(const float* __restrict__ dz, const float* __restrict__ 
     }
     // D: column = lane & 31 (c), row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5) (o)
     const int c = bn * WG_T + wn * 32 + lr;
-    float* out = part + (int64_t)slice * cout * cin;
-    if (c < cin) {
+    float* out = part + (int64_t)slice * cout * ncol;
+    if (c < ncol) {
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
             const int o = bm * WG_T + wm * 32 + (e & 3) + 8 * (e >> 2) + 4 * lh;
-            if (o < cout) out[(int64_t)o * cin + c] = acc[e];
+            if (o < cout) out[(int64_t)o * ncol + c] = acc[e];
         }
     }
     if (part_db && bn == 0 && tid < WG_T) {
@@ -119,15 +164,17 @@ void wgrad_slice_kernel(const float* __restrict__ dz, const float* __restrict__ 
     }
 }
 
-// the slice sums added in ascending slice order: one thread per element of dW, then of db
+// the slice sums added in ascending slice order: one thread per element of dW, then of db.  row_scale (may be NULL): the reduced
+// sum of row o of dW (ncol elements) times row_scale[o] in double, rounded once; db is the plain sum
 __global__ __launch_bounds__(256)
 void wgrad_reduce_kernel(const float* __restrict__ part, const float* __restrict__ part_db, int64_t n_dw, int cout, int slices,
-                         float* __restrict__ dw, float* __restrict__ db) {
+                         const double* __restrict__ row_scale, int ncol, float* __restrict__ dw, float* __restrict__ db) {
 #pragma clang fp contract(off)
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i < n_dw) {
         float v = part[i];
         for (int s = 1; s < slices; ++s) v = v + part[(int64_t)s * n_dw + i];
+        if (row_scale) v = (float)((double)v * row_scale[i / ncol]);
         dw[i] = v;
     } else if (db && i < n_dw + cout) {
         const int64_t o = i - n_dw;
@@ -153,11 +200,43 @@ int launch_conv1x1_wgrad(const float* dz, const float* x, int batch, int cout, i
     if ((int64_t)gm * gn * S > INT32_MAX) { set_error("conv1x1_wgrad: grid too large"); return RTOD_E_ARG; }
     float* part = (float*)ws;
     float* part_db = part + (int64_t)S * cout * cin;
-    hipLaunchKernelGGL(wgrad_slice_kernel, dim3((unsigned)(gm * gn * S)), dim3(256), 0, s, dz, x, cout, cin, pixels, (int)K, (int)wgrad_slice_len(K),
+    hipLaunchKernelGGL(wgrad_slice_kernel<1>, dim3((unsigned)(gm * gn * S)), dim3(256), 0, s, dz, x, cout, cin, pixels, 1, pixels, (int)K, (int)wgrad_slice_len(K),
                        gm, gn, part, db ? part_db : (float*)nullptr);
     const int64_t n = (int64_t)cout * cin + (db ? cout : 0);
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, part, part_db, (int64_t)cout * cin, cout, S, dw, db);
+    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, part, part_db, (int64_t)cout * cin, cout, S,
+                       (const double*)nullptr, cin, dw, db);
     return hip_fail(hipGetLastError(), "conv1x1_wgrad launch");
+}
+
+int conv_wgrad_check_shape(const char* who, int batch, int cout, int cin, int h, int w, int size) {
+    const int64_t K = (int64_t)batch * h * w, taps = (int64_t)size * size;
+    if (batch < 1 || cout < 1 || cin < 32 || cin % 32 || h < 1 || w < 1 || (size != 1 && size != 3)) {
+        set_error("%s: unsupported shape (batch=%d cout=%d cin=%d h=%d w=%d size=%d; cin must be a multiple of 32, size 1 or 3)", who, batch, cout, cin, h, w, size);
+        return RTOD_E_ARG;
+    }
+    if ((int64_t)h * w > INT32_MAX || K > INT32_MAX - 64 || (int64_t)cout * cin * taps > INT32_MAX) { set_error("%s: batch * h * w or cout * cin * size * size exceeds int32", who); return RTOD_E_ARG; }
+    return RTOD_OK;
+}
+
+int launch_conv_wgrad(const float* dz, const float* x, int batch, int cout, int cin, int h, int w, int size, const double* row_scale,
+                      float* dw, float* db, void* ws, size_t ws_bytes, hipStream_t s) {
+    if (!dz || !x || !dw || !ws) { set_error("conv_wgrad: null pointer"); return RTOD_E_ARG; }
+    if (int rc = conv_wgrad_check_shape("conv_wgrad", batch, cout, cin, h, w, size)) return rc;
+    if (ws_bytes < conv_wgrad_workspace_bytes(batch, cout, cin, h, w, size)) { set_error("conv_wgrad: workspace too small"); return RTOD_E_ARG; }
+    if ((uintptr_t)ws & 15) { set_error("conv_wgrad: workspace must be 16-byte aligned"); return RTOD_E_ARG; }
+    const int pixels = h * w, ncol = cin * size * size;
+    const int64_t K = (int64_t)batch * pixels, tiles = conv_wgrad_tiles(cout, cin, size);
+    const int S = (int)conv_wgrad_slices(K, tiles), L = (int)conv_wgrad_slice_len(K, tiles);
+    const int gm = (cout + WG_T - 1) / WG_T, gn = (ncol + WG_T - 1) / WG_T;
+    if (tiles * S > INT32_MAX) { set_error("conv_wgrad: grid too large"); return RTOD_E_ARG; }
+    float* part = (float*)ws;
+    float* part_db = part + (int64_t)S * cout * ncol;
+    float* pdb = db ? part_db : (float*)nullptr;
+    if (size == 1) hipLaunchKernelGGL(wgrad_slice_kernel<1>, dim3((unsigned)(tiles * S)), dim3(256), 0, s, dz, x, cout, cin, pixels, h, w, (int)K, L, gm, gn, part, pdb);
+    else hipLaunchKernelGGL(wgrad_slice_kernel<9>, dim3((unsigned)(tiles * S)), dim3(256), 0, s, dz, x, cout, cin, pixels, h, w, (int)K, L, gm, gn, part, pdb);
+    const int64_t n = (int64_t)cout * ncol + (db ? cout : 0);
+    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, part, part_db, (int64_t)cout * ncol, cout, S, row_scale, ncol, dw, db);
+    return hip_fail(hipGetLastError(), "conv_wgrad launch");
 }
 
 }  // namespace rtod

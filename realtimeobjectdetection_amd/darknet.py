@@ -342,8 +342,93 @@ class Darknet(nn.Module):
             for layer, (w, b) in self._stepped.items():
                 conv = next(sub for name, sub in self.module_list[layer].named_children() if name.startswith("conv_"))
                 conv.weight.copy_(w)
-                conv.bias.copy_(b)
+                if b is not None:                                 # (a block conv has BatchNorm and no bias: weight-only entry)
+                    conv.bias.copy_(b)
         self._stepped.clear()
+
+    # ------------------------------------------------------------------ detection blocks (the BatchNorm conv a head conv reads)
+    def head_blocks(self) -> list:
+        """``[(head_conv_layer, block_conv_layer, block_input_layer)]`` per head in cfg order (rtod_plan_head_blocks): the block
+        conv is the 1x1 / 3x3 stride-1 leaky or linear BatchNorm conv the head conv reads, where the plan can train it with
+        BatchNorm frozen; ``(head, -1, -1)`` for a head without one.  ``read_layer(block_input_layer)`` is valid after a forward
+        with options ``keep_block_inputs``.  Asks the plan, so a forward (or ``prepare``) must have run."""
+        if self._plan is None:
+            raise RuntimeError("Darknet.head_blocks: no plan yet; run a forward first")
+        lib = _ffi.lib()
+        n = lib.rtod_plan_head_blocks(self._plan, None, None, None, 0)
+        if n < 0:
+            _ffi.check(n)
+        h, b, i = (C.c_int * n)(), (C.c_int * n)(), (C.c_int * n)()
+        lib.rtod_plan_head_blocks(self._plan, h, b, i, n)
+        return list(zip(h, b, i))
+
+    def conv_scale(self, layer: int):
+        """``(device address, host float64 array [Cout])`` of a block conv's frozen BatchNorm scale ``gamma / sqrt(var + 1e-5)`` as
+        the plan folded it (rtod_plan_conv_scale); the address is what ``train.conv_wgrad_async(row_scale=...)`` takes and needs
+        options ``keep_block_inputs``."""
+        if not self._plan_is_current():
+            raise RuntimeError("Darknet.conv_scale: no loaded plan holds the current parameters; run a forward first")
+        conv = self._block_conv("conv_scale", layer)
+        host = np.zeros(conv.out_channels, np.float64)
+        dev = C.c_void_p()
+        _ffi.check(_ffi.lib().rtod_plan_conv_scale(self._plan, int(layer), C.byref(dev), host.ctypes.data_as(C.c_void_p), host.size))
+        return dev.value, host
+
+    def _block_conv(self, who, layer):
+        conv = bn = None
+        if 0 <= int(layer) < len(self.module_list):
+            for name, sub in self.module_list[int(layer)].named_children():
+                if name.startswith("conv_"):
+                    conv = sub
+                elif name.startswith("batch_norm_"):
+                    bn = sub
+        if conv is None or bn is None:
+            raise ValueError("Darknet.%s: layer %d is not a convolution with BatchNorm" % (who, int(layer)))
+        return conv
+
+    def update_conv_weight(self, layer: int, weight) -> None:
+        """``update_conv`` for a detection block conv, BatchNorm untouched: ``weight`` [Cout,Cin,k,k] goes into the module's
+        ``conv.weight`` and, when a plan with current weights is loaded, into that plan through rtod_plan_update_conv_weight,
+        which re-packs this conv alone (the bits a full re-pack gives).  Synchronises."""
+        conv = self._block_conv("update_conv_weight", layer)
+        w = torch.as_tensor(weight).detach().to(torch.float32)
+        if tuple(w.shape) != tuple(conv.weight.shape):
+            raise ValueError("Darknet.update_conv_weight: layer %d takes weight %s, got %s" % (int(layer), tuple(conv.weight.shape), tuple(w.shape)))
+        with torch.no_grad():
+            conv.weight.copy_(w)
+        self._stepped.pop(int(layer), None)
+        if self._plan_is_current():
+            wh = np.ascontiguousarray(w.cpu().numpy())
+            with torch.cuda.device(self._plan_key[2]):
+                _ffi.check(_ffi.lib().rtod_plan_update_conv_weight(self._plan, int(layer), wh.ctypes.data_as(C.c_void_p)))
+
+    def step_conv_folded(self, layer: int, opt, weight, dw, moments=None) -> None:
+        """``step_conv`` for a detection block conv (rtod_plan_step_conv_folded): ``weight`` [Cout,Cin,k,k] is the caller's RAW
+        float32 device master (the module's ``conv.weight``, not the folded one), updated IN PLACE from ``dw``
+        (``conv_wgrad_async`` with the plan's scale) and, for Adam, ``moments = (exp_avg, exp_avg_sq)``; the same kernel folds the
+        frozen BatchNorm scale and re-packs the conv's block of the plan's weight image in place.  Nothing synchronises, nothing
+        is allocated.  Needs a current plan with options ``keep_block_inputs``.  ``conv.weight`` lags behind as after ``step_conv``."""
+        layer = int(layer)
+        if not self._plan_is_current():
+            raise RuntimeError("Darknet.step_conv_folded: no loaded plan holds the current parameters; run a forward first")
+        dev = torch.device("cuda", self._plan_key[2])
+        if moments is not None and len(moments) != 2:
+            raise ValueError("Darknet.step_conv_folded: moments = (exp_avg, exp_avg_sq)")
+        tensors = [weight, dw] + (list(moments) if moments is not None else [])
+        for t in tensors:
+            if not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != torch.float32 or not t.is_contiguous():
+                raise ValueError("Darknet.step_conv_folded: every tensor must be a contiguous float32 tensor on %s" % dev)
+        conv = self._block_conv("step_conv_folded", layer)
+        if tuple(weight.shape) != tuple(conv.weight.shape) or any(t.numel() != weight.numel() for t in tensors):
+            raise ValueError("Darknet.step_conv_folded: layer %d takes weight, gradient and moments of shape %s" % (layer, tuple(conv.weight.shape)))
+        if not isinstance(opt, _ffi.OptStep):
+            opt = _ffi.OptStep(int(opt["kind"]), float(opt["lr"]), float(opt.get("beta1", 0.0)), float(opt.get("beta2", 0.0)), float(opt.get("eps", 0.0)), int(opt.get("step", 0)))
+        ptr = lambda t: C.c_void_p(t.data_ptr())
+        mom = [ptr(t) for t in moments] if moments is not None else [None] * 2
+        with torch.cuda.device(dev):
+            _ffi.check(_ffi.lib().rtod_plan_step_conv_folded(self._plan, layer, C.byref(opt), ptr(weight), ptr(dw), *mom,
+                                                             C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        self._stepped[layer] = (weight, None)
 
     def packed_weights(self) -> np.ndarray:
         """The plan's packed weight image as it is on the device now, as uint32 words (rtod_plan_read_packed_weights; tests and

@@ -3,8 +3,9 @@
 The FORWARD VALUE of the loss: targets from ground-truth boxes (``target_creator``) and the five-term sum of squares
 (``darknet_loss``), the last step of ``feed_forward_through_model`` (train.py:412-425); and the first layer of its backward pass:
 the gradient with respect to the raw head maps and from it ``dW``, ``db`` of the detection-head convs (the 1x1 convs without
-BatchNorm in front of the [yolo] blocks), with a plain SGD step on them — fine-tuning the heads with the backbone frozen.  Backward
-through the trunk, BatchNorm gradients, weight decay, epochs and data loaders are out of scope.  The reference's
+BatchNorm in front of the [yolo] blocks), with a plain SGD step on them — fine-tuning the heads with the backbone frozen — and, with
+``trainable="blocks"``, one layer further: the weight gradient of the BatchNorm conv each head conv reads, BatchNorm frozen.  Backward
+through the rest of the trunk, BatchNorm gradients, weight decay, epochs and data loaders are out of scope.  The reference's
 optimiser — ``optim.Adam(lr=1e-2)``, train.py:57 — runs on the heads as one kernel per conv that also re-packs the conv's weights in
 place (``HeadOptimizer``, ``feed_forward_through_model``): that path never synchronises.  Same names and return conventions as the
 reference:
@@ -18,6 +19,8 @@ reference:
 * ``DarknetTrainer.head_step(frames_or_x, bndbox, lr)``                                     (new) ``w -= lr * dW``, ``b -= lr * db`` on the heads
 * ``DarknetTrainer.feed_forward_through_model(batch_data, bndbox)``                         train.py:412-425: forward, loss, backward, ``optimizer`` step
 * ``DarknetTrainer.optimizer`` (``HeadOptimizer``: Adam or SGD on the heads), ``sync_parameters()``    train.py:57
+* ``DarknetTrainer(model, trainable="blocks")``, ``block_gradients(frames_or_x, bndbox)``             (new) the step also trains the conv in front of
+                                                                                            each head conv: ``(loss, head grads, {block_conv_layer: dW})``
 
 The reference's behaviour is kept as it is: only boxes whose class-0 slot is 1 and whose sides are at least
 ``min_box_size`` (24) count, ``anchor_fit`` compares a box with a square of the anchor's WIDTH, target slot 0 holds the y fraction
@@ -176,6 +179,69 @@ def conv1x1_wgrad_async(dz, x, bias=True):
     return dw, db
 
 
+def _scale_ptr(row_scale, cout, dev):
+    """``row_scale`` of ``conv_wgrad_async`` as a pointer: None, a float64 device tensor [Cout], or an integer device address
+    (what ``Darknet.conv_scale`` hands out)."""
+    if row_scale is None:
+        return None
+    if isinstance(row_scale, torch.Tensor):
+        if row_scale.device != dev or row_scale.dtype != torch.float64 or row_scale.numel() != cout or not row_scale.is_contiguous():
+            raise ValueError("conv_wgrad: row_scale must be a contiguous float64 tensor [%d] on %s" % (cout, dev))
+        return C.c_void_p(row_scale.data_ptr())
+    return C.c_void_p(int(row_scale))
+
+
+def conv_wgrad_async(dz, x, size, row_scale=None, bias=False):
+    """Enqueue rtod_conv_wgrad: ``dz`` [B,Cout,H,W] and ``x`` [B,Cin,H,W] (contiguous float32 device tensors, Cin a multiple of
+    32) -> ``(dW [Cout,Cin,size,size], db [Cout] or None)`` of a ``size`` x ``size`` (1 or 3), stride-1, same-padding conv.
+    ``row_scale`` (float64 device tensor [Cout], or the device address ``Darknet.conv_scale`` returns): every row of dW times it,
+    one rounding.  Nothing synchronises; the workspace is cached per shape."""
+    _need_cuda(dz, "conv_wgrad")
+    _need_cuda(x, "conv_wgrad")
+    if dz.dim() != 4 or x.dim() != 4 or dz.size(0) != x.size(0) or tuple(dz.shape[2:]) != tuple(x.shape[2:]) or dz.dtype != torch.float32 or x.dtype != torch.float32:
+        raise ValueError("conv_wgrad: expected float32 dz [B,Cout,H,W] and x [B,Cin,H,W], got %s and %s" % (tuple(dz.shape), tuple(x.shape)))
+    dz, x = dz.contiguous(), x.contiguous()
+    B, cout, cin, H, W, size = dz.size(0), dz.size(1), x.size(1), dz.size(2), dz.size(3), int(size)
+    dev = dz.device
+    key = (dev.index, B, cout, cin, H, W, size)
+    ws = _wgrad_ws.get(key)
+    if ws is None:
+        nbytes = C.c_size_t()
+        _ffi.check(_ffi.lib().rtod_conv_wgrad_workspace(B, cout, cin, H, W, size, C.byref(nbytes)))
+        if len(_wgrad_ws) > 16:
+            _wgrad_ws.clear()
+        ws = _wgrad_ws[key] = (torch.empty((nbytes.value + 7) // 8, dtype=torch.float64, device=dev), nbytes.value)
+    dw = torch.empty((cout, cin, size, size), dtype=torch.float32, device=dev)
+    db = torch.empty(cout, dtype=torch.float32, device=dev) if bias else None
+    with torch.cuda.device(dev):
+        _ffi.check(_ffi.lib().rtod_conv_wgrad(C.c_void_p(dz.data_ptr()), C.c_void_p(x.data_ptr()), B, cout, cin, H, W, size, _scale_ptr(row_scale, cout, dev),
+                                              C.c_void_p(dw.data_ptr()), C.c_void_p(db.data_ptr()) if bias else None, C.c_void_p(ws[0].data_ptr()), ws[1], _stream(dev)))
+    return dw, db
+
+
+def conv1x1_dgrad_async(w, dz, y=None, slope=1.0):
+    """Enqueue rtod_conv1x1_dgrad: ``w`` [Cout,Cin(,1,1)], ``dz`` [B,Cout,H,W] and, for a leaky layer, ``y`` [B,Cin,H,W] (the STORED
+    output of the layer the conv reads) -> ``dx`` [B,Cin,H,W] = ``m(y) * W^T dz`` with ``m = 1`` where ``y > 0`` and ``slope``
+    elsewhere.  Contiguous float32 device tensors, Cin a multiple of 32; nothing synchronises."""
+    for t in (w, dz) + ((y,) if y is not None else ()):
+        _need_cuda(t, "conv1x1_dgrad")
+    ok = dz.dim() == 4 and w.dim() in (2, 4) and w.numel() == w.size(0) * w.size(1) and w.size(0) == dz.size(1) and w.dtype == dz.dtype == torch.float32
+    if ok and y is not None:
+        ok = y.dtype == torch.float32 and tuple(y.shape) == (dz.size(0), w.size(1), dz.size(2), dz.size(3))
+    if not ok:
+        raise ValueError("conv1x1_dgrad: expected float32 w [Cout,Cin], dz [B,Cout,H,W] and y [B,Cin,H,W], got %s, %s and %s"
+                         % (tuple(w.shape), tuple(dz.shape), None if y is None else tuple(y.shape)))
+    w, dz = w.contiguous(), dz.contiguous()
+    y = None if y is None else y.contiguous()
+    B, cout, cin, H, W = dz.size(0), dz.size(1), w.size(1), dz.size(2), dz.size(3)
+    dev = dz.device
+    dx = torch.empty((B, cin, H, W), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _ffi.check(_ffi.lib().rtod_conv1x1_dgrad(C.c_void_p(w.data_ptr()), C.c_void_p(dz.data_ptr()), C.c_void_p(y.data_ptr()) if y is not None else None,
+                                                 float(slope), B, cout, cin, H * W, C.c_void_p(dx.data_ptr()), _stream(dev)))
+    return dx
+
+
 def model_heads(model, height=None, width=None):
     """``[(grid_h, grid_w, stride, anchors)]`` of a Darknet's [yolo] layers in cfg order, and its number of classes."""
     h = int(model.net_info["height"]) if height is None else int(height)
@@ -213,21 +279,29 @@ class HeadOptimizer:
 
     def _entry(self, layer, masters):
         st = self.state.get(layer)
-        if st is None or st["weight"] is not masters[0] or st["bias"] is not masters[1]:
-            st = self.state[layer] = {"step": 0 if st is None else st["step"], "weight": masters[0], "bias": masters[1]}
+        if st is None or st["weight"] is not masters[0] or st.get("bias") is not masters[1]:
+            st = self.state[layer] = {"step": 0 if st is None else st["step"], "weight": masters[0]}
+            if masters[1] is not None:                             # (a block conv has no bias: no bias keys)
+                st["bias"] = masters[1]
         if self.kind == "adam" and "exp_avg" not in st:
-            st.update(exp_avg=torch.zeros_like(masters[0]), exp_avg_sq=torch.zeros_like(masters[0]),
-                      exp_avg_bias=torch.zeros_like(masters[1]), exp_avg_sq_bias=torch.zeros_like(masters[1]))
+            st.update(exp_avg=torch.zeros_like(masters[0]), exp_avg_sq=torch.zeros_like(masters[0]))
+            if masters[1] is not None:
+                st.update(exp_avg_bias=torch.zeros_like(masters[1]), exp_avg_sq_bias=torch.zeros_like(masters[1]))
         return st
 
     def step(self, model, masters, grads):
-        """One step of every conv in ``grads`` (``{conv_layer: (dW, db)}``) on ``masters`` (``{conv_layer: [weight, bias]}``)."""
+        """One step of every conv in ``grads`` on ``masters``: ``{conv_layer: (dW, db)}`` and ``{conv_layer: [weight, bias]}`` for a
+        head conv (``Darknet.step_conv``), ``(dW, None)`` and ``[weight, None]`` for a block conv (``Darknet.step_conv_folded``)."""
         for layer, (dw, db) in grads.items():
             st = self._entry(layer, masters[layer])
             st["step"] += 1
             opt = _ffi.OptStep(self.KINDS[self.kind], self.lr, self.betas[0], self.betas[1], self.eps, st["step"])
-            moments = (st["exp_avg"], st["exp_avg_sq"], st["exp_avg_bias"], st["exp_avg_sq_bias"]) if self.kind == "adam" else None
-            model.step_conv(layer, opt, st["weight"], st["bias"], dw, db, moments)
+            adam = self.kind == "adam"
+            if db is None:
+                model.step_conv_folded(layer, opt, st["weight"], dw, (st["exp_avg"], st["exp_avg_sq"]) if adam else None)
+            else:
+                moments = (st["exp_avg"], st["exp_avg_sq"], st["exp_avg_bias"], st["exp_avg_sq_bias"]) if adam else None
+                model.step_conv(layer, opt, st["weight"], st["bias"], dw, db, moments)
 
     def state_dict(self):
         """``{conv_layer: {"step": int, name: tensor}}`` of the masters and moments (the tensors themselves, as torch's does)."""
@@ -240,9 +314,12 @@ class HeadOptimizer:
         self.state = {int(layer): {k: (v.detach().clone() if isinstance(v, torch.Tensor) else int(v)) for k, v in st.items()} for layer, st in state.items()}
         trainer = self._trainer() if self._trainer is not None else None
         if trainer is not None:
-            trainer._head_masters = {layer: [st["weight"], st["bias"]] for layer, st in self.state.items()}
+            trainer._head_masters = {layer: [st["weight"], st.get("bias")] for layer, st in self.state.items()}
             for layer, (w, b) in trainer._head_masters.items():
-                trainer.darknet.update_conv(layer, w, b)
+                if b is None:
+                    trainer.darknet.update_conv_weight(layer, w)
+                else:
+                    trainer.darknet.update_conv(layer, w, b)
 
 
 class DarknetTrainer:
@@ -254,7 +331,10 @@ class DarknetTrainer:
     was skipped; OR-ed by every call, read it when you synchronise anyway), ``last_components`` (device float64 [6] of the
     last loss: total, xy, wh, obj, noobj, cls)."""
 
-    def __init__(self, model, resolution=None, num_classes=None):
+    def __init__(self, model, resolution=None, num_classes=None, trainable="heads"):
+        if trainable not in ("heads", "blocks"):
+            raise ValueError("DarknetTrainer: trainable must be 'heads' or 'blocks', got %r" % (trainable,))
+        self.trainable = trainable         # "blocks": feed_forward_through_model also trains the BatchNorm conv in front of each head conv
         self.darknet = model
         if resolution is not None:
             assert isinstance(resolution, int) and resolution % 32 == 0
@@ -271,6 +351,7 @@ class DarknetTrainer:
         self.status = None
         self.last_components = None
         self._head_masters = None          # head_step / optimizer: {conv_layer: [weight, bias]} float32 device masters of the head convs
+        self._block_cache = None           # block_gradients: (plan and weight version, the plan's blocks with their scales)
         self.optimizer = HeadOptimizer()
 
     @property
@@ -391,6 +472,12 @@ class DarknetTrainer:
         detection-head convs.  Forward under ``train_mode()`` (inputs as ``forward_loss``), rtod_yolo_loss_grad, then per head
         ``read_layer`` of the conv's input and rtod_conv1x1_wgrad; all on the current stream, nothing synchronises.  The model's
         ``options`` must hold ``keep_head_inputs`` (the head inputs are otherwise overwritten before the forward ends)."""
+        loss, grads, _ = self._head_pass(frames_or_x, bndbox)
+        return loss, grads
+
+    def _head_pass(self, frames_or_x, bndbox):
+        """The body of ``head_gradients``, which ``block_gradients`` goes on from: ``(loss, {conv_layer: (dW, db)}, {conv_layer: (dz,
+        x)})`` with dz the gradient of the head's raw map and x the dense copy of the head conv's input."""
         model = self.darknet
         if not int(getattr(model, "options", {}).get("keep_head_inputs", 0)):
             raise RuntimeError("DarknetTrainer.head_gradients: set model.options['keep_head_inputs'] = 1 before the first forward; "
@@ -401,12 +488,14 @@ class DarknetTrainer:
         layers = model.head_layers()
         if len(layers) != len(self.heads):
             raise RuntimeError("DarknetTrainer.head_gradients: %d [yolo] layers but %d of them follow a convolution" % (len(self.heads), len(layers)))
-        grads = {}
+        grads, operands = {}, {}
         for (conv_layer, input_layer), dz in zip(layers, out["grad_raw"]):
             if input_layer < 0:
                 raise RuntimeError("DarknetTrainer.head_gradients: head conv %d reads the network input" % conv_layer)
-            grads[conv_layer] = conv1x1_wgrad_async(dz, model.read_layer(input_layer, pred.size(0)))
-        return out["components"][0].float(), grads
+            x = model.read_layer(input_layer, pred.size(0))
+            grads[conv_layer] = conv1x1_wgrad_async(dz, x)
+            operands[conv_layer] = (dz, x)
+        return out["components"][0].float(), grads, operands
 
     def head_step(self, frames_or_x, bndbox, lr):
         """One plain SGD step on the detection-head convs, ``w -= lr * dW``, ``b -= lr * db``, on float32 device masters the
@@ -424,14 +513,58 @@ class DarknetTrainer:
         return loss
 
     def _masters(self, layers, dev):
-        """The float32 device masters of the head convs, taken from the model's parameters the first time they are needed."""
+        """The float32 device masters ``[weight, bias]`` of the trained convs (bias None for a block conv: it has BatchNorm), taken
+        from the model's parameters the first time each is needed."""
         if self._head_masters is None:
-            self.darknet.sync_stepped_parameters()
             self._head_masters = {}
-            for layer in layers:
+        missing = [layer for layer in layers if layer not in self._head_masters]
+        if missing:
+            self.darknet.sync_stepped_parameters()
+            for layer in missing:
                 conv = next(sub for name, sub in self.darknet.module_list[layer].named_children() if name.startswith("conv_"))
-                self._head_masters[layer] = [conv.weight.detach().to(dev, torch.float32).clone(), conv.bias.detach().to(dev, torch.float32).clone()]
+                bias = None if conv.bias is None else conv.bias.detach().to(dev, torch.float32).clone()
+                self._head_masters[layer] = [conv.weight.detach().to(dev, torch.float32).clone(), bias]
         return self._head_masters
+
+    # ------------------------------------------------------------------ gradients of the detection blocks
+    def block_gradients(self, frames_or_x, bndbox):
+        """``(loss, {head_conv_layer: (dW, db)}, {block_conv_layer: dW [Cout,Cin,k,k]})``: what ``loss.backward()`` of the reference
+        under ``.eval()`` leaves on the head convs and on ``conv.weight`` of the detection blocks (``Darknet.head_blocks``: the
+        BatchNorm conv each head conv reads; BatchNorm frozen, its parameters are not trained).  ``head_gradients``, then per head
+        with a block: rtod_conv1x1_dgrad from the head's float32 master weights and ``read_layer`` of the block conv's output (whose
+        sign gives the leaky-ReLU derivative), and rtod_conv_wgrad over ``read_layer`` of the block's input with the plan's frozen
+        scale.  All on the current stream, nothing synchronises.  The model's ``options`` must hold ``keep_head_inputs`` and
+        ``keep_block_inputs``."""
+        model = self.darknet
+        opts = getattr(model, "options", {})
+        if not (int(opts.get("keep_head_inputs", 0)) and int(opts.get("keep_block_inputs", 0))):
+            raise RuntimeError("DarknetTrainer.block_gradients: set model.options['keep_head_inputs'] = 1 and model.options['keep_block_inputs'] = 1 "
+                               "before the first forward; without them the activations that feed the head convs and the block convs do not "
+                               "survive the forward")
+        loss, head_grads, operands = self._head_pass(frames_or_x, bndbox)
+        masters = self._masters(head_grads, loss.device)
+        block_grads = {}
+        for head, block, block_in, leaky, size, scale in self._blocks():
+            dz, y = operands[head]                                    # the head conv's input is the block conv's stored output
+            dy = conv1x1_dgrad_async(masters[head][0], dz, y if leaky else None, 0.1 if leaky else 1.0)
+            block_grads[block] = conv_wgrad_async(dy, model.read_layer(block_in, y.size(0)), size, row_scale=scale)[0]
+        return loss, head_grads, block_grads
+
+    def _blocks(self):
+        """``[(head_conv, block_conv, block_input, leaky, kernel size, device address of the frozen scale)]`` of the heads that have a
+        block, asked of the plan once per plan and weight load (kept beside the masters)."""
+        model = self.darknet
+        key = (model._plan.value, model._plan_weights_version)
+        if self._block_cache is None or self._block_cache[0] != key:
+            found = []
+            for head, block, block_in in model.head_blocks():
+                if block < 0:
+                    continue
+                names = dict(model.module_list[block].named_children())
+                conv = next(sub for name, sub in names.items() if name.startswith("conv_"))
+                found.append((head, block, block_in, any(name.startswith("leaky_") for name in names), conv.kernel_size[0], model.conv_scale(block)[0]))
+            self._block_cache = (key, found)
+        return self._block_cache[1]
 
     # ------------------------------------------------------------------ the reference's training step, on the heads
     def feed_forward_through_model(self, batch_data, bndbox):
@@ -441,7 +574,14 @@ class DarknetTrainer:
         synchronises; the next forward on that stream runs the new weights.  Returns the loss from before the step as a 0-dim
         float32 device tensor.  The module's ``conv.weight`` / ``conv.bias`` lag behind until ``sync_parameters()`` (or anything
         that reads the model's parameters as a whole: ``weight_stream()``, ``state_dict()``, a re-pack)."""
-        loss, grads = self.head_gradients(batch_data, bndbox)
+        if self.trainable == "blocks":
+            # every gradient kernel of the batch is enqueued before the first step, as autograd has it: step_conv updates the head
+            # masters in place, and the data gradient through a head reads them
+            loss, grads, block_grads = self.block_gradients(batch_data, bndbox)
+            grads = dict(grads)
+            grads.update({layer: (dw, None) for layer, dw in block_grads.items()})
+        else:
+            loss, grads = self.head_gradients(batch_data, bndbox)
         self.optimizer.step(self.darknet, self._masters(grads, loss.device), grads)
         return loss
 
