@@ -397,18 +397,17 @@ int rtod_yolo_loss_grad(const float* pred_dev, int batch, int n_rows, int num_cl
 }
 
 int rtod_conv1x1_wgrad_workspace(int batch, int cout, int cin, int pixels, size_t* bytes) {
-    if (!bytes || batch < 1 || cout < 1 || cin < 32 || cin % 32 || pixels < 1 || (int64_t)batch * pixels > INT32_MAX - 64 || (int64_t)cout * cin > INT32_MAX) {
-        set_error("conv1x1_wgrad_workspace: bad args (batch=%d cout=%d cin=%d pixels=%d; cin must be a multiple of 32)", batch, cout, cin, pixels);
-        return RTOD_E_ARG;
-    }
-    *bytes = wgrad_workspace_bytes(batch, cout, cin, pixels);
+    if (!bytes) { set_error("conv1x1_wgrad_workspace: null pointer"); return RTOD_E_ARG; }
+    if (int rc = wgrad_check_shape("conv1x1_wgrad_workspace", batch, cout, cin, 1, pixels, 1)) return rc;
+    *bytes = wgrad_workspace_bytes(batch, cout, cin, 1, pixels, 1, WGRAD_MAX_SLICES);
     return RTOD_OK;
 }
 
 int rtod_conv1x1_wgrad(const float* dz_dev, const float* x_dev, int batch, int cout, int cin, int pixels, float* dw_dev, float* db_dev,
                        void* workspace, size_t workspace_bytes, void* stream) {
     RTOD_GUARD_BEGIN
-    return launch_conv1x1_wgrad(dz_dev, x_dev, batch, cout, cin, pixels, dw_dev, db_dev, workspace, workspace_bytes, (hipStream_t)stream);
+    return launch_wgrad("conv1x1_wgrad", dz_dev, x_dev, batch, cout, cin, 1, pixels, 1, WGRAD_MAX_SLICES, nullptr, dw_dev, db_dev, workspace, workspace_bytes,
+                        (hipStream_t)stream);
     RTOD_GUARD_END
 }
 
@@ -425,15 +424,16 @@ int rtod_plan_head_layers(const rtod_plan* plan, int* conv_layers, int* input_la
 
 int rtod_conv_wgrad_workspace(int batch, int cout, int cin, int height, int width, int size, size_t* bytes) {
     if (!bytes) { set_error("conv_wgrad_workspace: null pointer"); return RTOD_E_ARG; }
-    if (int rc = conv_wgrad_check_shape("conv_wgrad_workspace", batch, cout, cin, height, width, size)) return rc;
-    *bytes = conv_wgrad_workspace_bytes(batch, cout, cin, height, width, size);
+    if (int rc = wgrad_check_shape("conv_wgrad_workspace", batch, cout, cin, height, width, size)) return rc;
+    *bytes = wgrad_workspace_bytes(batch, cout, cin, height, width, size, wgrad_tile_cap(cout, cin, size));
     return RTOD_OK;
 }
 
 int rtod_conv_wgrad(const float* dz_dev, const float* x_dev, int batch, int cout, int cin, int height, int width, int size,
                     const double* row_scale_dev, float* dw_dev, float* db_dev, void* workspace, size_t workspace_bytes, void* stream) {
     RTOD_GUARD_BEGIN
-    return launch_conv_wgrad(dz_dev, x_dev, batch, cout, cin, height, width, size, row_scale_dev, dw_dev, db_dev, workspace, workspace_bytes, (hipStream_t)stream);
+    return launch_wgrad("conv_wgrad", dz_dev, x_dev, batch, cout, cin, height, width, size, wgrad_tile_cap(cout, cin, size), row_scale_dev, dw_dev, db_dev,
+                        workspace, workspace_bytes, (hipStream_t)stream);
     RTOD_GUARD_END
 }
 

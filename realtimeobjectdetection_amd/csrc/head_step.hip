@@ -15,65 +15,19 @@
 // from max |(double)w' * s| (kept as the double's integer bits), and v lands at panel[o * Kpad + tap * cin_p + c] or at half
 // (((c / 32) * taps + tap) * Npad + o) * 32 + c % 32.  There is no bias workgroup: the bias slot (beta - mean * s) keeps its bits.
 // A head conv is the case taps = 1, s = 1: (double)w' * 1.0 is w' itself, and the exponent of a double equals that of the float.
-// f32 -> f16 is the host's integer routine (f32_to_f16_rn), restated here: round to nearest even, subnormal halves kept, values at
-// or below 2^-25 to (signed) zero — independent of the denormal mode the library is built with.  Nothing outside channel rows
+// f32 -> f16 and back are the host's integer routines (f16_round.h: round to nearest even, subnormal halves kept, values at or
+// below 2^-25 to (signed) zero) — independent of the denormal mode the library is built with.  Nothing outside channel rows
 // [0, Cout) and columns [0, Cin) of this conv's block is written: padding channels, padding K and other convs keep their bits.
 // Plain vector stores only; no atomics; bit-identical from call to call.  Built with -ffp-contract=off and correctly rounded
 // fp32 divide / sqrt (Makefile: PARITY_FLAGS), so every operator below is one IEEE operation with one rounding and the only
 // fused multiply-adds are the ones written as fmaf.
 #include "rtod_internal.h"
+#include "f16_round.h"
 
 namespace rtod {
 
-__device__ __forceinline__ uint32_t f32_bits(float f) { return __float_as_uint(f); }
-
-__device__ __forceinline__ uint32_t f32_to_f16_rn_dev(float f) {
-    uint32_t x = f32_bits(f);
-    const uint32_t sign = (x >> 16) & 0x8000u;
-    x &= 0x7FFFFFFFu;
-    if (x >= 0x7F800000u) return sign | (x > 0x7F800000u ? 0x7E00u : 0x7C00u);
-    if (x >= 0x477FF000u) return sign | 0x7C00u;
-    if (x < 0x33000001u) return sign;
-    const int e = (int)(x >> 23) - 127;
-    const uint32_t m = (x & 0x7FFFFFu) | 0x800000u;
-    const int shift = (e < -14) ? (13 + (-14 - e)) : 13;                     // <= 24 here: e >= -25
-    uint32_t half_m = m >> shift;
-    const uint32_t rem = m & ((1u << shift) - 1u), halfway = 1u << (shift - 1);
-    if (rem > halfway || (rem == halfway && (half_m & 1u))) ++half_m;
-    const uint32_t out = (e < -14) ? half_m : (((uint32_t)(e + 15) << 10) + (half_m - 0x400u));
-    return sign | out;
-}
-
-__device__ __forceinline__ float f16_to_f32_dev(uint32_t h) {
-    const uint32_t sign = (h & 0x8000u) << 16;
-    const uint32_t e = (h >> 10) & 0x1Fu, m = h & 0x3FFu;
-    uint32_t x;
-    if (e == 0) x = f32_bits((float)m * 5.9604644775390625e-8f);    // m * 2^-24, exact and normal in fp32
-    else if (e == 31) x = m ? 0x7FC00000u : 0x7F800000u;
-    else x = ((e + 112u) << 23) | (m << 13);
-    return __uint_as_float(x | sign);
-}
-
-struct StepArgs {
-    int kind;                       // 0 SGD, 1 Adam
-    float lr;                       // SGD: (float)lr.  Adam: (float)(lr / (1 - beta1^t))
-    float beta2, omb1, omb2;        // (float)beta2, (float)(1 - beta1), (float)(1 - beta2)
-    float bc2_sqrt, eps;            // (float)sqrt(1 - beta2^t), (float)eps
-    int cout, cin, taps, cin_p;     // taps = size * size; cin_p: channels per tap of the fp32 panel's K order
-    int split;                      // 0: fp32 panel, 1: f16 hi / lo planes
-    int Kpad, Npad;
-    float* w; float* b;             // masters (b == NULL: a BatchNorm conv, whose bias slot is not written)
-    const float* dw; const float* db;
-    float* m_w; float* v_w; float* m_b; float* v_b;
-    const double* scale;            // BatchNorm convs: the frozen gamma / sqrt(var + 1e-5) per output channel (NULL: 1)
-    float* panel;                   // fp32 plans: [Npad][Kpad]
-    uint16_t* hi; uint16_t* lo;     // split plans: [Kpad / 32][Npad][32] halves each
-    float* inv;                     // split plans: [Npad]
-    float* bias;                    // [Npad]
-};
-
 // one element: (w, g, m, v) -> w'; m, v updated in place (Adam)
-__device__ __forceinline__ float opt_update(const StepArgs& a, float w, float g, float& m, float& v) {
+__device__ __forceinline__ float opt_update(const HeadStepLaunch& a, float w, float g, float& m, float& v) {
 #pragma clang fp contract(off)
     if (a.kind == 0) { const float d = a.lr * g; return w - d; }
     const float gm = g - m;
@@ -87,7 +41,7 @@ __device__ __forceinline__ float opt_update(const StepArgs& a, float w, float g,
 }
 
 __global__ __launch_bounds__(256)
-void head_step_kernel(StepArgs a) {
+void head_step_kernel(HeadStepLaunch a) {
     __shared__ unsigned long long smax[256];
     const int tid = threadIdx.x;
     const int o = blockIdx.x;
@@ -140,29 +94,18 @@ void head_step_kernel(StepArgs a) {
         const int c = q / a.taps, tap = q - c * a.taps;
         const float fv = (float)((double)a.w[row + q] * sc);        // the fp32 folded weight
         const float vs = fv * ps;                                   // one rounding, as (float)((double)fv * 2^e): exact but for subnormal results
-        const uint32_t h = f32_to_f16_rn_dev(vs);
-        const float rest = vs - f16_to_f32_dev(h);
-        const uint32_t l = f32_to_f16_rn_dev(rest);
+        const uint16_t h = f32_to_f16_rn(vs);
+        const float rest = vs - f16_to_f32(h);
         const int64_t idx = ((int64_t)((c >> 5) * a.taps + tap) * a.Npad + o) * 32 + (c & 31);
-        a.hi[idx] = (uint16_t)h;
-        a.lo[idx] = (uint16_t)l;
+        a.hi[idx] = h;
+        a.lo[idx] = f32_to_f16_rn(rest);
     }
 }
 
 static_assert(ACT_SCALE_F16S3 == 8.0f, "head_step_kernel builds 2^-e / ACT_SCALE_F16S3 from the exponent");
 
 int launch_head_step(const HeadStepLaunch& h, hipStream_t s) {
-    StepArgs a;
-    a.kind = h.kind; a.lr = h.lr; a.beta2 = h.beta2; a.omb1 = h.omb1; a.omb2 = h.omb2; a.bc2_sqrt = h.bc2_sqrt; a.eps = h.eps;
-    a.cout = h.cout; a.cin = h.cin; a.taps = h.taps; a.cin_p = h.cin_p; a.split = h.split; a.Kpad = h.Kpad; a.Npad = h.Npad;
-    a.scale = h.scale;
-    a.w = h.w; a.b = h.b; a.dw = h.dw; a.db = h.db; a.m_w = h.m_w; a.v_w = h.v_w; a.m_b = h.m_b; a.v_b = h.v_b;
-    a.panel = h.blk;
-    a.hi = reinterpret_cast<uint16_t*>(h.blk);
-    a.lo = reinterpret_cast<uint16_t*>(h.blk + h.lo_off);
-    a.inv = h.blk + h.inv_off;
-    a.bias = h.blk + h.bias_off;
-    hipLaunchKernelGGL(head_step_kernel, dim3((unsigned)(h.cout + (h.b ? 1 : 0))), dim3(256), 0, s, a);   // no bias workgroup for a BatchNorm conv
+    hipLaunchKernelGGL(head_step_kernel, dim3((unsigned)(h.cout + (h.b ? 1 : 0))), dim3(256), 0, s, h);   // no bias workgroup for a BatchNorm conv
     return hip_fail(hipGetLastError(), "head_step launch");
 }
 

@@ -93,7 +93,7 @@ struct PackedConv {
 };
 
 // One struct, defined over five files by concern (the run-time fused form of every launch is decided in one place, Plan::form in plan_forward.cpp): plan_cfg.cpp (parse, resolve_shapes: no HIP call), plan_build.cpp (options, buffer
-// planning, weight layout, describe), plan_weights.cpp (pack_conv, pack_weights, load_weights, update_conv, step_conv and their twins for the detection blocks), plan_tiles.cpp (which kernel variant a conv
+// planning, weight layout, describe), plan_weights.cpp (pack_conv, pack_weights, load_weights; repack_conv under update_conv / update_conv_weight, step_packed under step_conv / step_conv_folded), plan_tiles.cpp (which kernel variant a conv
 // launch runs, autotune), plan_forward.cpp (the launch list on a stream, launch records).
 struct Plan {
     int height = 0, width = 0, max_batch = 0, device = 0;
@@ -167,6 +167,12 @@ struct Plan {
     void pack_conv(const PackedConv& pc, const float* p, float* blk) const;         // one conv: its block of the stream -> its block of the image (blk = image + pc.w_off)
     int64_t conv_block_floats(size_t slot) const;                                   // floats of that block: every range of the conv, padding to the next conv included
     int load_weights(const float* w, size_t n);
+    // one conv trained alone.  Two kinds of conv are accepted, each by its own refusals (replaceable_conv: no BatchNorm; block_conv:
+    // a detection block); underneath there is one host re-pack (repack_conv) and one device step (step_packed)
+    struct ConvSite { int slot = -1; bool pair = false; };                          // slot in `convs` (-1: none); host or guest of a fused-pointwise candidate pair
+    int conv_site(const char* who, int layer, ConvSite& cs) const;                  // refuses a layer that is no convolution
+    int repack_conv(size_t slot, const std::vector<float>& stream);                 // pack_conv of the conv's block of the stream, uploaded alone (synchronises)
+    int step_packed(const char* who, size_t slot, const rtod_opt_step* opt, bool moments, bool folded, HeadStepLaunch& h, hipStream_t s);   // scalars, state, one launch
     int update_conv(int layer, const float* weight_oihw, const float* bias);        // re-pack and upload one conv without BatchNorm (rtod_plan_update_conv)
     int replaceable_conv(const char* who, int layer, size_t& slot) const;            // the conv's slot, or why it cannot be replaced alone
     int step_conv(int layer, const rtod_opt_step* opt, float* weight, float* bias, const float* dw, const float* db,

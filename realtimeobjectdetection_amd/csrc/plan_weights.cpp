@@ -1,6 +1,7 @@
 // Packed weights: the .weights payload -> the image the kernels read (host), and its upload.  Weight stream order in the
 // reference: src/darknet.py:316-410.
 #include "plan.h"
+#include "f16_round.h"
 
 #include <algorithm>
 #include <cmath>
@@ -10,34 +11,9 @@
 
 namespace rtod {
 
-static uint16_t f32_to_f16_rn(float f) {           // IEEE binary16, round to nearest even, host side
-    uint32_t x; memcpy(&x, &f, 4);
-    const uint32_t sign = (x >> 16) & 0x8000u;
-    x &= 0x7FFFFFFFu;
-    if (x >= 0x7F800000u) return (uint16_t)(sign | (x > 0x7F800000u ? 0x7E00u : 0x7C00u));
-    if (x >= 0x477FF000u) return (uint16_t)(sign | 0x7C00u);               // rounds to >= 65520 -> inf
-    if (x < 0x33000001u) return (uint16_t)sign;                             // < 2^-25 -> 0
-    int e = (int)(x >> 23) - 127;
-    uint32_t m = (x & 0x7FFFFFu) | 0x800000u;
-    int shift = (e < -14) ? (13 + (-14 - e)) : 13;                          // subnormal halves lose extra bits
-    uint32_t half_m = m >> shift;
-    const uint32_t rem = m & ((1u << shift) - 1), halfway = 1u << (shift - 1);
-    if (rem > halfway || (rem == halfway && (half_m & 1))) ++half_m;
-    uint32_t out;
-    if (e < -14) out = half_m;                                               // subnormal (may carry into normal)
-    else out = ((uint32_t)(e + 15) << 10) + (half_m - 0x400u);               // carry propagates into the exponent
-    return (uint16_t)(sign | out);
-}
-static float f16_to_f32(uint16_t h) {
-    const uint32_t sign = (uint32_t)(h & 0x8000u) << 16;
-    const int e = (h >> 10) & 0x1F; const uint32_t m = h & 0x3FFu;
-    float v;
-    if (e == 0) v = std::ldexp((float)m, -24);
-    else if (e == 31) v = m ? NAN : INFINITY;
-    else v = std::ldexp((float)(m | 0x400u), e - 25);
-    uint32_t x; memcpy(&x, &v, 4); x |= sign; memcpy(&v, &x, 4);
-    return v;
-}
+// The frozen (eval) BatchNorm scale of one channel.  pack_conv folds it into the weights and the bias, load_weights keeps it for
+// the gradient and the step of the detection blocks: head_step_kernel re-packs bit for bit only while both read this one line.
+static double bn_frozen_scale(float gamma, float var) { return (double)gamma / std::sqrt((double)var + 1e-5); }
 
 // Split layouts, per output channel: a power-of-two pre-scale 2^e puts max|w| in [2^12, 2^13), so that low parts of weights down to
 // 2^-16 of the channel maximum stay normal f16; e is held to -24 .. 40 and an all-zero channel keeps e = 0.  ps = 2^e multiplies
@@ -78,8 +54,7 @@ void Plan::pack_conv(const PackedConv& pc, const float* p, float* blk) const {
         const float *beta = p, *gamma = p + C, *mean = p + 2 * C, *var = p + 3 * C;
         for (int o = 0; o < C; ++o) {
             // eval BatchNorm (x - mean) / sqrt(var + 1e-5) * gamma + beta folded into the conv
-            const double s = (double)gamma[o] / std::sqrt((double)var[o] + 1e-5);
-            scale[o] = s;
+            const double s = scale[o] = bn_frozen_scale(gamma[o], var[o]);
             bias[o] = (float)((double)beta[o] - (double)mean[o] * s);
         }
         p += 4 * C;
@@ -143,33 +118,33 @@ int Plan::pack_weights(const float* w, size_t n, std::vector<float>& packed) con
 
 // The slot in `convs` of a conv whose weights may be replaced alone (update_conv, step_conv): no BatchNorm, no fused pointwise pair.
 int Plan::replaceable_conv(const char* who, int layer, size_t& slot) const {
-    if (layer < 0 || layer >= (int)layers.size() || layers[layer].type != LT_CONV) { set_error("%s: layer %d is not a convolution", who, layer); return RTOD_E_ARG; }
+    ConvSite cs;
+    if (int rc = conv_site(who, layer, cs)) return rc;
     if (layers[layer].bn) { set_error("%s: layer %d has BatchNorm (only convs without it can be replaced)", who, layer); return RTOD_E_ARG; }
-    slot = convs.size();
-    for (const auto& l : launches) {
-        if ((l.kind != LK_CONV && l.kind != LK_STEM) || l.layer != layer || l.conv_slot < 0) continue;
-        // (candidates, not forms: a pair that may fuse is refused whether or not it runs fused now)
-        if (l.pw_guest >= 0 || l.pw_host >= 0) { set_error("%s: layer %d is part of a fused pointwise pair", who, layer); return RTOD_E_ARG; }
-        slot = (size_t)l.conv_slot;
-    }
-    if (slot >= convs.size()) { set_error("%s: layer %d has no packed weights", who, layer); return RTOD_E_ARG; }
+    if (cs.pair) { set_error("%s: layer %d is part of a fused pointwise pair", who, layer); return RTOD_E_ARG; }
+    if (cs.slot < 0) { set_error("%s: layer %d has no packed weights", who, layer); return RTOD_E_ARG; }
+    slot = (size_t)cs.slot;
     return RTOD_OK;
 }
 
-// One conv without BatchNorm re-packed from (weight OIHW, bias) and its block alone copied to the device: the bits a full
-// load_weights of the edited stream gives, since both go through pack_conv.  Synchronises the device (a forward in flight may
-// still read the old block).
-int Plan::update_conv(int layer, const float* weight_oihw, const float* bias) {
-    if (!weight_oihw || !bias) { set_error("update_conv: null pointer"); return RTOD_E_ARG; }
-    size_t slot = 0;
-    if (int rc = replaceable_conv("update_conv", layer, slot)) return rc;
-    const Layer& L = layers[layer];
-    if (!weights_loaded || !d_weights) { set_error("update_conv: call rtod_plan_load_weights first"); return RTOD_E_STATE; }
+// What replaceable_conv and block_conv both ask first: `layer` is a convolution (else refused), the slot of its packed weights (-1:
+// none) and whether it is host or guest of a fused-pointwise pair (candidates, not forms: a pair that may fuse counts whether or
+// not it runs fused now)
+int Plan::conv_site(const char* who, int layer, ConvSite& cs) const {
+    if (layer < 0 || layer >= (int)layers.size() || layers[layer].type != LT_CONV) { set_error("%s: layer %d is not a convolution", who, layer); return RTOD_E_ARG; }
+    for (const auto& l : launches) {
+        if ((l.kind != LK_CONV && l.kind != LK_STEM) || l.layer != layer || l.conv_slot < 0) continue;
+        cs.slot = l.conv_slot;
+        cs.pair = cs.pair || l.pw_guest >= 0 || l.pw_host >= 0;
+    }
+    return RTOD_OK;
+}
+
+// One conv re-packed from its block of the stream (`stream`: [bias] or [beta, gamma, mean, var], then the OIHW weights) and that
+// block alone copied to the device: the bits a full load_weights of the edited stream gives, since both go through pack_conv.
+// Synchronises the device (a forward in flight may still read the old block).
+int Plan::repack_conv(size_t slot, const std::vector<float>& stream) {
     const PackedConv& pc = convs[slot];
-    const int64_t nw = (int64_t)L.cout * L.cin * L.size * L.size;
-    std::vector<float> stream((size_t)(L.cout + nw));
-    memcpy(stream.data(), bias, sizeof(float) * (size_t)L.cout);
-    memcpy(stream.data() + L.cout, weight_oihw, sizeof(float) * (size_t)nw);
     std::vector<float> blk((size_t)conv_block_floats(slot), 0.0f);
     pack_conv(pc, stream.data(), blk.data());
     RTOD_HIP(hipSetDevice(device));
@@ -177,6 +152,18 @@ int Plan::update_conv(int layer, const float* weight_oihw, const float* bias) {
     RTOD_HIP(hipMemcpy(d_weights + pc.w_off, blk.data(), sizeof(float) * blk.size(), hipMemcpyHostToDevice));
     RTOD_HIP(hipDeviceSynchronize());
     return RTOD_OK;
+}
+
+// A conv without BatchNorm from (weight OIHW, bias)
+int Plan::update_conv(int layer, const float* weight_oihw, const float* bias) {
+    if (!weight_oihw || !bias) { set_error("update_conv: null pointer"); return RTOD_E_ARG; }
+    size_t slot = 0;
+    if (int rc = replaceable_conv("update_conv", layer, slot)) return rc;
+    if (!weights_loaded || !d_weights) { set_error("update_conv: call rtod_plan_load_weights first"); return RTOD_E_STATE; }
+    const Layer& L = layers[layer];
+    std::vector<float> stream(bias, bias + L.cout);
+    stream.insert(stream.end(), weight_oihw, weight_oihw + (int64_t)L.cout * L.cin * L.size * L.size);
+    return repack_conv(slot, stream);
 }
 
 // A float field of rtod_opt_step read as the shortest decimal that rounds to it (0.999f means 0.999, as it prints): 1 - beta2 taken
@@ -205,12 +192,25 @@ int Plan::step_conv(int layer, const rtod_opt_step* opt, float* weight, float* b
     if (L.size != 1 || pc.stem || pc.stem16 || pc.narrow) { set_error("step_conv: layer %d is not a 1x1 conv of the generic layouts (size %d%s)", layer, L.size, pc.narrow ? ", narrow" : pc.stem ? ", stem" : ""); return RTOD_E_ARG; }
     if (pc.Kpad < L.cin || L.cout > pc.Npad || (pc.split && L.cin % 32 != 0)) { set_error("step_conv: layer %d has an unexpected packed layout", layer); return RTOD_E_ARG; }
     HeadStepLaunch h;
-    if (int rc = opt_scalars("step_conv", opt, m_w && v_w && m_b && v_b, h)) return rc;
-    if (!weights_loaded || !d_weights) { set_error("step_conv: call rtod_plan_load_weights first"); return RTOD_E_STATE; }
-    h.cout = L.cout; h.cin = L.cin; h.taps = 1; h.cin_p = pc.cin_p; h.split = pc.split ? 1 : 0; h.Kpad = pc.Kpad; h.Npad = pc.Npad;
     h.w = weight; h.b = bias; h.dw = dw; h.db = db; h.m_w = m_w; h.v_w = v_w; h.m_b = m_b; h.v_b = v_b;
-    h.blk = d_weights + pc.w_off;
-    h.lo_off = pc.wl_off - pc.w_off; h.inv_off = pc.s_off - pc.w_off; h.bias_off = pc.b_off - pc.w_off;
+    return step_packed("step_conv", slot, opt, m_w && v_w && m_b && v_b, false, h, s);
+}
+
+// The body of both steps, after the entry's own refusals: the scalars, the state the step needs (folded: the frozen scales of the
+// block convs on the device), then the launch description — h holds the caller's pointers — filled once
+int Plan::step_packed(const char* who, size_t slot, const rtod_opt_step* opt, bool moments, bool folded, HeadStepLaunch& h, hipStream_t s) {
+    if (int rc = opt_scalars(who, opt, moments, h)) return rc;
+    if (!weights_loaded || !d_weights) { set_error("%s: call rtod_plan_load_weights first", who); return RTOD_E_STATE; }
+    if (folded && !d_block_scale) { set_error("%s: the plan needs option keep_block_inputs (it puts the frozen scales on the device)", who); return RTOD_E_STATE; }
+    const PackedConv& pc = convs[slot];
+    const Layer& L = layers[pc.layer];
+    h.cout = L.cout; h.cin = L.cin; h.taps = L.size * L.size; h.cin_p = pc.cin_p; h.split = pc.split ? 1 : 0; h.Kpad = pc.Kpad; h.Npad = pc.Npad;
+    if (folded) h.scale = d_block_scale + block_scale_off.at(pc.layer);
+    h.panel = d_weights + pc.w_off;
+    h.hi = reinterpret_cast<uint16_t*>(d_weights + pc.w_off);
+    h.lo = reinterpret_cast<uint16_t*>(d_weights + pc.wl_off);
+    h.inv = d_weights + pc.s_off;
+    h.bias = d_weights + pc.b_off;
     return launch_head_step(h, s);
 }
 
@@ -238,19 +238,19 @@ int Plan::opt_scalars(const char* who, const rtod_opt_step* opt, bool moments, H
 
 // The slot of a detection block conv (rtod_plan_head_blocks), or why `layer` is none: what update_conv_weight and step_conv_folded accept
 int Plan::block_conv(const char* who, int layer, size_t& slot) const {
-    if (layer < 0 || layer >= (int)layers.size() || layers[layer].type != LT_CONV) { set_error("%s: layer %d is not a convolution", who, layer); return RTOD_E_ARG; }
+    ConvSite cs;
+    if (int rc = conv_site(who, layer, cs)) return rc;
     if (!layers[layer].bn) { set_error("%s: layer %d has no BatchNorm (rtod_plan_update_conv / rtod_plan_step_conv take such convs)", who, layer); return RTOD_E_ARG; }
     if (block_of_head(layer + 1) != layer) {
-        const PackedConv* pc = nullptr; const Launch* ll = nullptr;
-        for (const auto& l : launches) if ((l.kind == LK_CONV || l.kind == LK_STEM) && l.layer == layer && l.conv_slot >= 0) { ll = &l; pc = &convs[l.conv_slot]; }
+        const PackedConv* pc = cs.slot >= 0 ? &convs[cs.slot] : nullptr;
         const char* why = opt_bn_batch_stats ? "the plan runs batch-statistics BatchNorm: the conv is not folded"
                         : pc && (pc->stem || pc->stem16) ? "a stem layout" : pc && pc->narrow ? "a narrow (Cin == 16) layout"
-                        : ll && (ll->pw_guest >= 0 || ll->pw_host >= 0) ? "part of a fused pointwise pair"
+                        : cs.pair ? "part of a fused pointwise pair"
                         : "not the 1x1 / 3x3 stride-1 leaky or linear BatchNorm conv that a detection-head conv reads";
         set_error("%s: layer %d is not a detection block (%s)", who, layer, why);
         return RTOD_E_ARG;
     }
-    for (const auto& l : launches) if (l.kind == LK_CONV && l.layer == layer) slot = (size_t)l.conv_slot;
+    slot = (size_t)cs.slot;                                          // block_of_head found it: a block has packed weights
     return RTOD_OK;
 }
 
@@ -279,17 +279,9 @@ int Plan::update_conv_weight(int layer, const float* weight_oihw) {
     const auto it = block_bn.find(layer);
     if (!weights_loaded || !d_weights || it == block_bn.end()) { set_error("update_conv_weight: call rtod_plan_load_weights first"); return RTOD_E_STATE; }
     const Layer& L = layers[layer];
-    const PackedConv& pc = convs[slot];
-    const int64_t nw = (int64_t)L.cout * L.cin * L.size * L.size;
     std::vector<float> stream(it->second);
-    stream.insert(stream.end(), weight_oihw, weight_oihw + nw);
-    std::vector<float> blk((size_t)conv_block_floats(slot), 0.0f);
-    pack_conv(pc, stream.data(), blk.data());
-    RTOD_HIP(hipSetDevice(device));
-    RTOD_HIP(hipDeviceSynchronize());
-    RTOD_HIP(hipMemcpy(d_weights + pc.w_off, blk.data(), sizeof(float) * blk.size(), hipMemcpyHostToDevice));
-    RTOD_HIP(hipDeviceSynchronize());
-    return RTOD_OK;
+    stream.insert(stream.end(), weight_oihw, weight_oihw + (int64_t)L.cout * L.cin * L.size * L.size);
+    return repack_conv(slot, stream);
 }
 
 // The device twin: head_step.hip's kernel on the raw float32 master [Cout, Cin, k, k], folding the frozen scale while it re-packs.
@@ -299,17 +291,8 @@ int Plan::step_conv_folded(int layer, const rtod_opt_step* opt, float* weight, c
     size_t slot = 0;
     if (int rc = block_conv("step_conv_folded", layer, slot)) return rc;
     HeadStepLaunch h;
-    if (int rc = opt_scalars("step_conv_folded", opt, m_w && v_w, h)) return rc;
-    if (!weights_loaded || !d_weights) { set_error("step_conv_folded: call rtod_plan_load_weights first"); return RTOD_E_STATE; }
-    if (!d_block_scale) { set_error("step_conv_folded: the plan needs option keep_block_inputs (it puts the frozen scales on the device)"); return RTOD_E_STATE; }
-    const Layer& L = layers[layer];
-    const PackedConv& pc = convs[slot];
-    h.cout = L.cout; h.cin = L.cin; h.taps = L.size * L.size; h.cin_p = pc.cin_p; h.split = pc.split ? 1 : 0; h.Kpad = pc.Kpad; h.Npad = pc.Npad;
     h.w = weight; h.dw = dw; h.m_w = m_w; h.v_w = v_w;
-    h.scale = d_block_scale + block_scale_off.at(layer);
-    h.blk = d_weights + pc.w_off;
-    h.lo_off = pc.wl_off - pc.w_off; h.inv_off = pc.s_off - pc.w_off; h.bias_off = pc.b_off - pc.w_off;
-    return launch_head_step(h, s);
+    return step_packed("step_conv_folded", slot, opt, m_w && v_w, true, h, s);
 }
 
 // The device image as it is now (tests, debugging): synchronises.
@@ -366,7 +349,7 @@ int Plan::load_weights(const float* w, size_t n) {
         block_bn[blk].assign(p, p + 4 * C);
         std::vector<double>& sc = block_scale[blk];
         sc.resize(C);
-        for (int o = 0; o < C; ++o) sc[o] = (double)p[C + o] / std::sqrt((double)p[3 * C + o] + 1e-5);
+        for (int o = 0; o < C; ++o) sc[o] = bn_frozen_scale(p[C + o], p[3 * C + o]);
         block_scale_off[blk] = (int64_t)scales.size();
         scales.insert(scales.end(), sc.begin(), sc.end());
     }

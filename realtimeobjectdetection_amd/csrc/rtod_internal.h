@@ -362,33 +362,39 @@ int launch_darknet_loss_dense(const float* pred, const float* target, const uint
 int launch_yolo_loss_grad(const float* pred, int batch, int n_rows, int num_class, const rtod_yolo_head* heads, int n_heads,
                           const float* boxes, const int32_t* box_off, float min_box_size, float* grad_raw, float* grad_pred, double* loss,
                           int32_t* n_obj, int32_t* status, void* ws, size_t ws_bytes, hipStream_t s);
-// weight / bias gradient of a 1x1 convolution on the exact-fp32 MFMA, K slices added in order (wgrad.hip)
-int64_t wgrad_slice_len(int64_t K);
-size_t wgrad_workspace_bytes(int batch, int cout, int cin, int pixels);
-int launch_conv1x1_wgrad(const float* dz, const float* x, int batch, int cout, int cin, int pixels, float* dw, float* db,
-                         void* ws, size_t ws_bytes, hipStream_t s);
-// ... of a 1x1 or 3x3 convolution, K slices by K and the number of tiles, an optional double scale per row of dW (wgrad.hip)
-int64_t conv_wgrad_slice_len(int64_t K, int64_t tiles);
-size_t conv_wgrad_workspace_bytes(int batch, int cout, int cin, int h, int w, int size);
-int conv_wgrad_check_shape(const char* who, int batch, int cout, int cin, int h, int w, int size);
-int launch_conv_wgrad(const float* dz, const float* x, int batch, int cout, int cin, int h, int w, int size, const double* row_scale,
-                      float* dw, float* db, void* ws, size_t ws_bytes, hipStream_t s);
+// weight / bias gradient of a 1x1 or 3x3 convolution on the exact-fp32 MFMA, K slices added in order, an optional double scale
+// per row of dW (wgrad.hip).  One path under both entries: rtod_conv1x1_wgrad is size = 1, h = 1, w = pixels, cap =
+// WGRAD_MAX_SLICES, no row scale; rtod_conv_wgrad passes cap = wgrad_tile_cap.  `who` names the entry in the error texts.
+constexpr int WGRAD_MAX_SLICES = 16;
+int wgrad_tile_cap(int cout, int cin, int size);                    // min(16, ceil(1024 / tiles))
+int64_t wgrad_slice_len(int64_t K, int cap);
+size_t wgrad_workspace_bytes(int batch, int cout, int cin, int h, int w, int size, int cap);
+int wgrad_check_shape(const char* who, int batch, int cout, int cin, int h, int w, int size);
+int launch_wgrad(const char* who, const float* dz, const float* x, int batch, int cout, int cin, int h, int w, int size, int cap,
+                 const double* row_scale, float* dw, float* db, void* ws, size_t ws_bytes, hipStream_t s);
 // data gradient of a 1x1 convolution with the leaky-ReLU derivative of the stored activation in its epilogue (dgrad.hip)
 int launch_conv1x1_dgrad(const float* w, const float* dz, const float* y, float slope, int batch, int cout, int cin, int pixels,
                          float* dx, hipStream_t s);
 // optimiser step of one conv fused with the re-pack of its block of the weight image (head_step.hip): a 1x1 conv without BatchNorm
 // with its bias (Plan::step_conv), or a conv whose frozen BatchNorm scale is folded while it re-packs (b == NULL, scale given:
-// Plan::step_conv_folded).  The scalars are what the host derived in double; blk = d_weights + the conv's w_off, the offsets in floats
+// Plan::step_conv_folded).  The kernel's own argument: the scalars are what the host derived in double (Plan::opt_scalars), the
+// image pointers are the conv's ranges of the device image (Plan::step_packed)
 struct HeadStepLaunch {
     int kind = 0;                                   // 0 SGD, 1 Adam
-    float lr = 0.f, beta2 = 0.f, omb1 = 0.f, omb2 = 0.f, bc2_sqrt = 1.f, eps = 0.f;
-    int cout = 0, cin = 0, taps = 1, cin_p = 0, split = 0, Kpad = 0, Npad = 0;
-    float *w = nullptr, *b = nullptr;
+    float lr = 0.f;                                 // SGD: (float)lr.  Adam: (float)(lr / (1 - beta1^t))
+    float beta2 = 0.f, omb1 = 0.f, omb2 = 0.f;      // (float)beta2, (float)(1 - beta1), (float)(1 - beta2)
+    float bc2_sqrt = 1.f, eps = 0.f;                // (float)sqrt(1 - beta2^t), (float)eps
+    int cout = 0, cin = 0, taps = 1, cin_p = 0;     // taps = size * size; cin_p: channels per tap of the fp32 panel's K order
+    int split = 0;                                  // 0: fp32 panel, 1: f16 hi / lo planes
+    int Kpad = 0, Npad = 0;
+    float *w = nullptr, *b = nullptr;               // masters (b == NULL: a BatchNorm conv, whose bias slot is not written)
     const float *dw = nullptr, *db = nullptr;
     float *m_w = nullptr, *v_w = nullptr, *m_b = nullptr, *v_b = nullptr;
-    const double* scale = nullptr;
-    float* blk = nullptr;
-    int64_t lo_off = 0, inv_off = 0, bias_off = 0;
+    const double* scale = nullptr;                  // BatchNorm convs: the frozen gamma / sqrt(var + 1e-5) per output channel (NULL: 1)
+    float* panel = nullptr;                         // fp32 plans: [Npad][Kpad]
+    uint16_t *hi = nullptr, *lo = nullptr;          // split plans: [Kpad / 32][Npad][32] halves each
+    float* inv = nullptr;                           // split plans: [Npad]
+    float* bias = nullptr;                          // [Npad]
 };
 int launch_head_step(const HeadStepLaunch& h, hipStream_t s);
 

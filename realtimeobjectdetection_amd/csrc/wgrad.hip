@@ -14,16 +14,16 @@
 //
 // K slices.  The tile grid is small (4 x 16 tiles at most), so K is split into S contiguous slices, one workgroup per (tile,
 // slice); slice sums go to the workspace and wgrad_reduce_kernel adds them in ascending slice order.  No floating-point atomics:
-// the result is bit-identical from call to call.  The slice rule sees K alone (wgrad_slice_len, documented in rtod.h):
-//   units = ceil(K / 8);  slice length = 8 * ceil(units / 16);  S = ceil(K / slice length)  (<= 16)
+// the result is bit-identical from call to call.  The slice rule (wgrad_slice_len, documented in rtod.h) sees K and a cap:
+//   units = ceil(K / 8);  slice length = 8 * ceil(units / cap);  S = ceil(K / slice length)  (<= cap; rtod_conv1x1_wgrad: cap = 16)
 // Every accumulator is an fmaf chain over its slice in a fixed permutation of k; db is a plain fp32 sum over the slice in
 // ascending k, kept by the workgroups of the first column of tiles.
 //
 // 3x3 convs (rtod_conv_wgrad, TAPS = 9).  The same kernel as an implicit GEMM: the column index is n = c * 9 + tap, OIHW order, so
 // the dW stores stay coalesced, and B[n][k] = x[b, c, y + ky - 1, x + kx - 1], an exact zero outside the map.  A thread's eight
 // columns (channel and tap offsets) do not depend on k and are resolved once; k -> (b, y, x) costs two divisions per staged chunk.
-// The 1x1 instance (TAPS = 1) is the kernel above, instruction for instruction.  The slice count of that entry also sees the
-// number of tiles (conv_wgrad_slices: a 13 x 13 block has a thousand tiles already and is not sliced), and its reduce kernel
+// The 1x1 instance (TAPS = 1) is the kernel above, instruction for instruction.  The cap of that entry also sees the
+// number of tiles (wgrad_tile_cap: a 13 x 13 block has a thousand tiles already and is not sliced), and its reduce kernel
 // multiplies the reduced sum of a row by a caller-supplied double once — the frozen BatchNorm scale of the conv.
 #include "rtod_internal.h"
 
@@ -35,33 +35,26 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 constexpr int WG_BK = 32;               // k per LDS stage
 constexpr int WG_LD = WG_BK + 4;        // padded row (floats)
 constexpr int WG_T = 64;                // tile edge (rows of dz and rows of x per workgroup)
-constexpr int WG_MAX_SLICES = 16;
 
-int64_t wgrad_slice_len(int64_t K) {
+// The slice rule (rtod.h): units = ceil(K / 8); slice length = 8 * ceil(units / cap); S = ceil(K / slice length) <= cap.  The two
+// entries differ in the cap alone: rtod_conv1x1_wgrad always allows WGRAD_MAX_SLICES, rtod_conv_wgrad wgrad_tile_cap.
+int64_t wgrad_slice_len(int64_t K, int cap) {
     const int64_t units = (K + 7) / 8;
-    return 8 * ((units + WG_MAX_SLICES - 1) / WG_MAX_SLICES);
-}
-static int64_t wgrad_slices(int64_t K) { const int64_t L = wgrad_slice_len(K); return (K + L - 1) / L; }
-
-size_t wgrad_workspace_bytes(int batch, int cout, int cin, int pixels) {
-    const int64_t S = wgrad_slices((int64_t)batch * pixels);
-    return sizeof(float) * (size_t)S * ((size_t)cout * cin + (size_t)cout);
-}
-
-// the slice count of rtod_conv_wgrad (rtod.h): as above with at most min(16, ceil(1024 / tiles)) slices
-constexpr int64_t WG_TILE_TARGET = 1024;
-static int64_t conv_wgrad_max_slices(int64_t tiles) { return std::min<int64_t>(WG_MAX_SLICES, (WG_TILE_TARGET + tiles - 1) / tiles); }
-int64_t conv_wgrad_slice_len(int64_t K, int64_t tiles) {
-    const int64_t units = (K + 7) / 8, cap = conv_wgrad_max_slices(tiles);
     return 8 * ((units + cap - 1) / cap);
 }
-static int64_t conv_wgrad_tiles(int cout, int cin, int size) {
+static int64_t wgrad_slices(int64_t K, int cap) { const int64_t L = wgrad_slice_len(K, cap); return (K + L - 1) / L; }
+static int64_t wgrad_tiles(int cout, int cin, int size) {
     return (int64_t)((cout + WG_T - 1) / WG_T) * (((int64_t)cin * size * size + WG_T - 1) / WG_T);
 }
-static int64_t conv_wgrad_slices(int64_t K, int64_t tiles) { const int64_t L = conv_wgrad_slice_len(K, tiles); return (K + L - 1) / L; }
+// min(16, ceil(1024 / tiles)): a grid that has a thousand tiles already is not sliced.  (No tiles: a shape wgrad_check_shape refuses.)
+int wgrad_tile_cap(int cout, int cin, int size) {
+    constexpr int64_t WG_TILE_TARGET = 1024;
+    const int64_t tiles = wgrad_tiles(cout, cin, size);
+    return tiles < 1 ? WGRAD_MAX_SLICES : (int)std::min<int64_t>(WGRAD_MAX_SLICES, (WG_TILE_TARGET + tiles - 1) / tiles);
+}
 
-size_t conv_wgrad_workspace_bytes(int batch, int cout, int cin, int h, int w, int size) {
-    const int64_t S = conv_wgrad_slices((int64_t)batch * h * w, conv_wgrad_tiles(cout, cin, size));
+size_t wgrad_workspace_bytes(int batch, int cout, int cin, int h, int w, int size, int cap) {
+    const int64_t S = wgrad_slices((int64_t)batch * h * w, cap);
     return sizeof(float) * (size_t)S * ((size_t)cout * cin * size * size + (size_t)cout);
 }
 
@@ -184,31 +177,7 @@ void wgrad_reduce_kernel(const float* __restrict__ part, const float* __restrict
     }
 }
 
-int launch_conv1x1_wgrad(const float* dz, const float* x, int batch, int cout, int cin, int pixels, float* dw, float* db,
-                         void* ws, size_t ws_bytes, hipStream_t s) {
-    if (!dz || !x || !dw || !ws) { set_error("conv1x1_wgrad: null pointer"); return RTOD_E_ARG; }
-    if (batch < 1 || cout < 1 || cin < 32 || cin % 32 || pixels < 1) {
-        set_error("conv1x1_wgrad: unsupported shape (batch=%d cout=%d cin=%d pixels=%d; cin must be a multiple of 32)", batch, cout, cin, pixels);
-        return RTOD_E_ARG;
-    }
-    const int64_t K = (int64_t)batch * pixels;
-    if (K > INT32_MAX - 64 || (int64_t)cout * cin > INT32_MAX) { set_error("conv1x1_wgrad: batch * pixels or cout * cin exceeds int32"); return RTOD_E_ARG; }
-    if (ws_bytes < wgrad_workspace_bytes(batch, cout, cin, pixels)) { set_error("conv1x1_wgrad: workspace too small"); return RTOD_E_ARG; }
-    if ((uintptr_t)ws & 15) { set_error("conv1x1_wgrad: workspace must be 16-byte aligned"); return RTOD_E_ARG; }
-    const int S = (int)wgrad_slices(K);
-    const int gm = (cout + WG_T - 1) / WG_T, gn = (cin + WG_T - 1) / WG_T;
-    if ((int64_t)gm * gn * S > INT32_MAX) { set_error("conv1x1_wgrad: grid too large"); return RTOD_E_ARG; }
-    float* part = (float*)ws;
-    float* part_db = part + (int64_t)S * cout * cin;
-    hipLaunchKernelGGL(wgrad_slice_kernel<1>, dim3((unsigned)(gm * gn * S)), dim3(256), 0, s, dz, x, cout, cin, pixels, 1, pixels, (int)K, (int)wgrad_slice_len(K),
-                       gm, gn, part, db ? part_db : (float*)nullptr);
-    const int64_t n = (int64_t)cout * cin + (db ? cout : 0);
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, part, part_db, (int64_t)cout * cin, cout, S,
-                       (const double*)nullptr, cin, dw, db);
-    return hip_fail(hipGetLastError(), "conv1x1_wgrad launch");
-}
-
-int conv_wgrad_check_shape(const char* who, int batch, int cout, int cin, int h, int w, int size) {
+int wgrad_check_shape(const char* who, int batch, int cout, int cin, int h, int w, int size) {
     const int64_t K = (int64_t)batch * h * w, taps = (int64_t)size * size;
     if (batch < 1 || cout < 1 || cin < 32 || cin % 32 || h < 1 || w < 1 || (size != 1 && size != 3)) {
         set_error("%s: unsupported shape (batch=%d cout=%d cin=%d h=%d w=%d size=%d; cin must be a multiple of 32, size 1 or 3)", who, batch, cout, cin, h, w, size);
@@ -218,17 +187,18 @@ int conv_wgrad_check_shape(const char* who, int batch, int cout, int cin, int h,
     return RTOD_OK;
 }
 
-int launch_conv_wgrad(const float* dz, const float* x, int batch, int cout, int cin, int h, int w, int size, const double* row_scale,
-                      float* dw, float* db, void* ws, size_t ws_bytes, hipStream_t s) {
-    if (!dz || !x || !dw || !ws) { set_error("conv_wgrad: null pointer"); return RTOD_E_ARG; }
-    if (int rc = conv_wgrad_check_shape("conv_wgrad", batch, cout, cin, h, w, size)) return rc;
-    if (ws_bytes < conv_wgrad_workspace_bytes(batch, cout, cin, h, w, size)) { set_error("conv_wgrad: workspace too small"); return RTOD_E_ARG; }
-    if ((uintptr_t)ws & 15) { set_error("conv_wgrad: workspace must be 16-byte aligned"); return RTOD_E_ARG; }
+// `who` names the entry in every error text; `cap` is the entry's cap on the slice count (at most WGRAD_MAX_SLICES)
+int launch_wgrad(const char* who, const float* dz, const float* x, int batch, int cout, int cin, int h, int w, int size, int cap,
+                 const double* row_scale, float* dw, float* db, void* ws, size_t ws_bytes, hipStream_t s) {
+    if (!dz || !x || !dw || !ws) { set_error("%s: null pointer", who); return RTOD_E_ARG; }
+    if (int rc = wgrad_check_shape(who, batch, cout, cin, h, w, size)) return rc;
+    if (ws_bytes < wgrad_workspace_bytes(batch, cout, cin, h, w, size, cap)) { set_error("%s: workspace too small", who); return RTOD_E_ARG; }
+    if ((uintptr_t)ws & 15) { set_error("%s: workspace must be 16-byte aligned", who); return RTOD_E_ARG; }
     const int pixels = h * w, ncol = cin * size * size;
-    const int64_t K = (int64_t)batch * pixels, tiles = conv_wgrad_tiles(cout, cin, size);
-    const int S = (int)conv_wgrad_slices(K, tiles), L = (int)conv_wgrad_slice_len(K, tiles);
+    const int64_t K = (int64_t)batch * pixels, tiles = wgrad_tiles(cout, cin, size);
+    const int S = (int)wgrad_slices(K, cap), L = (int)wgrad_slice_len(K, cap);
     const int gm = (cout + WG_T - 1) / WG_T, gn = (ncol + WG_T - 1) / WG_T;
-    if (tiles * S > INT32_MAX) { set_error("conv_wgrad: grid too large"); return RTOD_E_ARG; }
+    if (tiles * S > INT32_MAX) { set_error("%s: grid too large", who); return RTOD_E_ARG; }
     float* part = (float*)ws;
     float* part_db = part + (int64_t)S * cout * ncol;
     float* pdb = db ? part_db : (float*)nullptr;
@@ -236,7 +206,7 @@ int launch_conv_wgrad(const float* dz, const float* x, int batch, int cout, int 
     else hipLaunchKernelGGL(wgrad_slice_kernel<9>, dim3((unsigned)(tiles * S)), dim3(256), 0, s, dz, x, cout, cin, pixels, h, w, (int)K, L, gm, gn, part, pdb);
     const int64_t n = (int64_t)cout * ncol + (db ? cout : 0);
     hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, part, part_db, (int64_t)cout * ncol, cout, S, row_scale, ncol, dw, db);
-    return hip_fail(hipGetLastError(), "conv_wgrad launch");
+    return hip_fail(hipGetLastError(), (std::string(who) + " launch").c_str());
 }
 
 }  // namespace rtod

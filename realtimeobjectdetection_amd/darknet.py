@@ -225,13 +225,8 @@ class Darknet(nn.Module):
         brought up to date first (``sync_stepped_parameters``), so the stream — and every re-pack, which reads it — holds them."""
         self.sync_stepped_parameters()
         parts = []
-        for m in self.module_list:
-            conv = bn = None
-            for name, sub in m.named_children():
-                if name.startswith("conv_"):
-                    conv = sub
-                elif name.startswith("batch_norm_"):
-                    bn = sub
+        for layer in range(len(self.module_list)):
+            conv, bn = self._conv_bn(layer)
             if conv is None:
                 continue
             if bn is not None:
@@ -268,6 +263,12 @@ class Darknet(nn.Module):
         """Replace the weights of one conv without BatchNorm: ``weight`` [Cout,Cin,k,k] and ``bias`` [Cout] go into the module's
         parameters and, when a plan with current weights is loaded, into that plan through rtod_plan_update_conv, which re-packs
         this conv alone (the bits a full re-pack gives) — the next forward does not re-pack the network.  Synchronises."""
+        self._update("update_conv", layer, weight, bias, folded=False)
+
+    # ---- what the head entries (a conv without BatchNorm: weight and bias) and the block entries (a conv with frozen BatchNorm:
+    # weight alone, ``folded``) share
+    def _conv_bn(self, layer):
+        """``(conv, batch_norm)`` modules of a layer, None for what it does not have (or for a layer out of range)."""
         conv = bn = None
         if 0 <= int(layer) < len(self.module_list):
             for name, sub in self.module_list[int(layer)].named_children():
@@ -275,23 +276,70 @@ class Darknet(nn.Module):
                     conv = sub
                 elif name.startswith("batch_norm_"):
                     bn = sub
-        if conv is None or bn is not None:
-            raise ValueError("Darknet.update_conv: layer %d is not a convolution without BatchNorm" % int(layer))
-        w = torch.as_tensor(weight).detach().to(torch.float32)
-        b = torch.as_tensor(bias).detach().to(torch.float32)
-        if tuple(w.shape) != tuple(conv.weight.shape) or tuple(b.shape) != tuple(conv.bias.shape):
-            raise ValueError("Darknet.update_conv: layer %d takes weight %s and bias %s, got %s and %s"
-                             % (int(layer), tuple(conv.weight.shape), tuple(conv.bias.shape), tuple(w.shape), tuple(b.shape)))
+        return conv, bn
+
+    def _trained_conv(self, who, layer, with_bn):
+        conv, bn = self._conv_bn(layer)
+        if conv is None or (bn is not None) != with_bn:
+            raise ValueError("Darknet.%s: layer %d is not a convolution %s BatchNorm" % (who, int(layer), "with" if with_bn else "without"))
+        return conv
+
+    @staticmethod
+    def _opt_step(opt):
+        if isinstance(opt, _ffi.OptStep):
+            return opt
+        return _ffi.OptStep(int(opt["kind"]), float(opt["lr"]), float(opt.get("beta1", 0.0)), float(opt.get("beta2", 0.0)), float(opt.get("eps", 0.0)), int(opt.get("step", 0)))
+
+    @staticmethod
+    def _need_f32_on(who, dev, tensors):
+        for t in tensors:
+            if not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != torch.float32 or not t.is_contiguous():
+                raise ValueError("Darknet.%s: every tensor must be a contiguous float32 tensor on %s" % (who, dev))
+
+    def _update(self, who, layer, weight, bias, folded):
+        """The parameters of one conv replaced in the module and, when a plan with current weights is loaded, re-packed there alone."""
+        layer = int(layer)
+        conv = self._trained_conv(who, layer, with_bn=folded)
+        new = [("weight", conv.weight, weight)] + ([("bias", conv.bias, bias)] if not folded else [])
+        new = [(name, p, torch.as_tensor(t).detach().to(torch.float32)) for name, p, t in new]
+        if any(tuple(t.shape) != tuple(p.shape) for _, p, t in new):
+            raise ValueError("Darknet.%s: layer %d takes %s, got %s" % (who, layer, " and ".join("%s %s" % (name, tuple(p.shape)) for name, p, _ in new),
+                                                                      " and ".join(str(tuple(t.shape)) for _, _, t in new)))
         with torch.no_grad():
-            conv.weight.copy_(w)
-            conv.bias.copy_(b)
-        self._stepped.pop(int(layer), None)                       # the parameters are current again
+            for _, p, t in new:
+                p.copy_(t)
+        self._stepped.pop(layer, None)                            # the parameters are current again
         if self._plan_is_current():
-            wh = np.ascontiguousarray(w.cpu().numpy())
-            bh = np.ascontiguousarray(b.cpu().numpy())
+            host = [np.ascontiguousarray(t.cpu().numpy()) for _, _, t in new]
+            fn = _ffi.lib().rtod_plan_update_conv_weight if folded else _ffi.lib().rtod_plan_update_conv
             with torch.cuda.device(self._plan_key[2]):
-                _ffi.check(_ffi.lib().rtod_plan_update_conv(self._plan, int(layer), wh.ctypes.data_as(C.c_void_p), bh.ctypes.data_as(C.c_void_p)))
+                _ffi.check(fn(self._plan, layer, *[h.ctypes.data_as(C.c_void_p) for h in host]))
         # the plan's weight version stays current: parameters and plan agree again (a plan that was stale before still re-packs)
+
+    def _step(self, who, layer, opt, weight, bias, dw, db, moments, folded):
+        """One optimiser step of one conv on the current stream: masters and moments in place, the conv's block of the image re-packed."""
+        layer = int(layer)
+        if not self._plan_is_current():
+            raise RuntimeError("Darknet.%s: no loaded plan holds the current parameters; run a forward first" % who)
+        dev = torch.device("cuda", self._plan_key[2])
+        n_mom = 2 if folded else 4
+        if moments is not None and len(moments) != n_mom:
+            raise ValueError("Darknet.%s: moments = %s" % (who, "(exp_avg, exp_avg_sq)" if folded else "(exp_avg_w, exp_avg_sq_w, exp_avg_b, exp_avg_sq_b)"))
+        mom = list(moments) if moments is not None else []
+        like_w, like_b = [weight, dw] + mom[:2], ([] if folded else [bias, db] + mom[2:])
+        tensors = like_w if folded else [weight, bias, dw, db] + mom                    # in the order the entry takes them
+        self._need_f32_on(who, dev, tensors)
+        conv = self._trained_conv(who, layer, folded)
+        if (tuple(weight.shape) != tuple(conv.weight.shape) or any(t.numel() != weight.numel() for t in like_w)
+                or (not folded and (tuple(bias.shape) != tuple(conv.bias.shape) or any(t.numel() != bias.numel() for t in like_b)))):
+            raise ValueError("Darknet.%s: layer %d takes weight %s%s, and gradients and moments of their sizes"
+                             % (who, layer, tuple(conv.weight.shape), "" if folded else " and bias %s" % (tuple(conv.bias.shape),)))
+        opt = self._opt_step(opt)
+        args = [C.c_void_p(t.data_ptr()) for t in tensors] + [None] * (n_mom - len(mom))
+        fn = _ffi.lib().rtod_plan_step_conv_folded if folded else _ffi.lib().rtod_plan_step_conv
+        with torch.cuda.device(dev):
+            _ffi.check(fn(self._plan, layer, C.byref(opt), *args, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        self._stepped[layer] = (weight, bias)
 
     def _plan_is_current(self) -> bool:
         """A plan exists and holds the packed image of the parameters as they are (no re-pack is due at the next forward)."""
@@ -308,30 +356,7 @@ class Darknet(nn.Module):
         NOT touched and lag behind from here on; ``weight_stream()``, ``state_dict()``, ``invalidate_weights()`` and every
         re-pack bring them up to date from these masters first (``sync_stepped_parameters``), reading ``conv.weight`` directly
         does not."""
-        layer = int(layer)
-        if not self._plan_is_current():
-            raise RuntimeError("Darknet.step_conv: no loaded plan holds the current parameters; run a forward first")
-        dev = torch.device("cuda", self._plan_key[2])
-        if moments is not None and len(moments) != 4:
-            raise ValueError("Darknet.step_conv: moments = (exp_avg_w, exp_avg_sq_w, exp_avg_b, exp_avg_sq_b)")
-        like_w = [weight, dw] + ([moments[0], moments[1]] if moments is not None else [])
-        like_b = [bias, db] + ([moments[2], moments[3]] if moments is not None else [])
-        for t in like_w + like_b:
-            if not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != torch.float32 or not t.is_contiguous():
-                raise ValueError("Darknet.step_conv: every tensor must be a contiguous float32 tensor on %s" % dev)
-        if any(t.numel() != weight.numel() for t in like_w) or any(t.numel() != bias.numel() for t in like_b):
-            raise ValueError("Darknet.step_conv: gradients and moments must have the sizes of weight %s and bias %s" % (tuple(weight.shape), tuple(bias.shape)))
-        conv = next((sub for name, sub in self.module_list[layer].named_children() if name.startswith("conv_")), None) if 0 <= layer < len(self.module_list) else None
-        if conv is None or conv.bias is None or tuple(weight.shape) != tuple(conv.weight.shape) or tuple(bias.shape) != tuple(conv.bias.shape):
-            raise ValueError("Darknet.step_conv: layer %d is not a convolution without BatchNorm with weight %s and bias %s" % (layer, tuple(weight.shape), tuple(bias.shape)))
-        if not isinstance(opt, _ffi.OptStep):
-            opt = _ffi.OptStep(int(opt["kind"]), float(opt["lr"]), float(opt.get("beta1", 0.0)), float(opt.get("beta2", 0.0)), float(opt.get("eps", 0.0)), int(opt.get("step", 0)))
-        ptr = lambda t: C.c_void_p(t.data_ptr())
-        mom = [ptr(t) for t in moments] if moments is not None else [None] * 4
-        with torch.cuda.device(dev):
-            _ffi.check(_ffi.lib().rtod_plan_step_conv(self._plan, layer, C.byref(opt), ptr(weight), ptr(bias), ptr(dw), ptr(db), *mom,
-                                                      C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
-        self._stepped[layer] = (weight, bias)
+        self._step("step_conv", layer, opt, weight, bias, dw, db, moments, folded=False)
 
     def sync_stepped_parameters(self) -> None:
         """Copy the masters of every conv ``step_conv`` has stepped into the module's ``conv.weight`` / ``conv.bias`` (waits for the
@@ -340,7 +365,7 @@ class Darknet(nn.Module):
             return
         with torch.no_grad():
             for layer, (w, b) in self._stepped.items():
-                conv = next(sub for name, sub in self.module_list[layer].named_children() if name.startswith("conv_"))
+                conv = self._conv_bn(layer)[0]
                 conv.weight.copy_(w)
                 if b is not None:                                 # (a block conv has BatchNorm and no bias: weight-only entry)
                     conv.bias.copy_(b)
@@ -368,39 +393,17 @@ class Darknet(nn.Module):
         options ``keep_block_inputs``."""
         if not self._plan_is_current():
             raise RuntimeError("Darknet.conv_scale: no loaded plan holds the current parameters; run a forward first")
-        conv = self._block_conv("conv_scale", layer)
+        conv = self._trained_conv("conv_scale", layer, with_bn=True)
         host = np.zeros(conv.out_channels, np.float64)
         dev = C.c_void_p()
         _ffi.check(_ffi.lib().rtod_plan_conv_scale(self._plan, int(layer), C.byref(dev), host.ctypes.data_as(C.c_void_p), host.size))
         return dev.value, host
 
-    def _block_conv(self, who, layer):
-        conv = bn = None
-        if 0 <= int(layer) < len(self.module_list):
-            for name, sub in self.module_list[int(layer)].named_children():
-                if name.startswith("conv_"):
-                    conv = sub
-                elif name.startswith("batch_norm_"):
-                    bn = sub
-        if conv is None or bn is None:
-            raise ValueError("Darknet.%s: layer %d is not a convolution with BatchNorm" % (who, int(layer)))
-        return conv
-
     def update_conv_weight(self, layer: int, weight) -> None:
         """``update_conv`` for a detection block conv, BatchNorm untouched: ``weight`` [Cout,Cin,k,k] goes into the module's
         ``conv.weight`` and, when a plan with current weights is loaded, into that plan through rtod_plan_update_conv_weight,
         which re-packs this conv alone (the bits a full re-pack gives).  Synchronises."""
-        conv = self._block_conv("update_conv_weight", layer)
-        w = torch.as_tensor(weight).detach().to(torch.float32)
-        if tuple(w.shape) != tuple(conv.weight.shape):
-            raise ValueError("Darknet.update_conv_weight: layer %d takes weight %s, got %s" % (int(layer), tuple(conv.weight.shape), tuple(w.shape)))
-        with torch.no_grad():
-            conv.weight.copy_(w)
-        self._stepped.pop(int(layer), None)
-        if self._plan_is_current():
-            wh = np.ascontiguousarray(w.cpu().numpy())
-            with torch.cuda.device(self._plan_key[2]):
-                _ffi.check(_ffi.lib().rtod_plan_update_conv_weight(self._plan, int(layer), wh.ctypes.data_as(C.c_void_p)))
+        self._update("update_conv_weight", layer, weight, None, folded=True)
 
     def step_conv_folded(self, layer: int, opt, weight, dw, moments=None) -> None:
         """``step_conv`` for a detection block conv (rtod_plan_step_conv_folded): ``weight`` [Cout,Cin,k,k] is the caller's RAW
@@ -408,27 +411,7 @@ class Darknet(nn.Module):
         (``conv_wgrad_async`` with the plan's scale) and, for Adam, ``moments = (exp_avg, exp_avg_sq)``; the same kernel folds the
         frozen BatchNorm scale and re-packs the conv's block of the plan's weight image in place.  Nothing synchronises, nothing
         is allocated.  Needs a current plan with options ``keep_block_inputs``.  ``conv.weight`` lags behind as after ``step_conv``."""
-        layer = int(layer)
-        if not self._plan_is_current():
-            raise RuntimeError("Darknet.step_conv_folded: no loaded plan holds the current parameters; run a forward first")
-        dev = torch.device("cuda", self._plan_key[2])
-        if moments is not None and len(moments) != 2:
-            raise ValueError("Darknet.step_conv_folded: moments = (exp_avg, exp_avg_sq)")
-        tensors = [weight, dw] + (list(moments) if moments is not None else [])
-        for t in tensors:
-            if not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != torch.float32 or not t.is_contiguous():
-                raise ValueError("Darknet.step_conv_folded: every tensor must be a contiguous float32 tensor on %s" % dev)
-        conv = self._block_conv("step_conv_folded", layer)
-        if tuple(weight.shape) != tuple(conv.weight.shape) or any(t.numel() != weight.numel() for t in tensors):
-            raise ValueError("Darknet.step_conv_folded: layer %d takes weight, gradient and moments of shape %s" % (layer, tuple(conv.weight.shape)))
-        if not isinstance(opt, _ffi.OptStep):
-            opt = _ffi.OptStep(int(opt["kind"]), float(opt["lr"]), float(opt.get("beta1", 0.0)), float(opt.get("beta2", 0.0)), float(opt.get("eps", 0.0)), int(opt.get("step", 0)))
-        ptr = lambda t: C.c_void_p(t.data_ptr())
-        mom = [ptr(t) for t in moments] if moments is not None else [None] * 2
-        with torch.cuda.device(dev):
-            _ffi.check(_ffi.lib().rtod_plan_step_conv_folded(self._plan, layer, C.byref(opt), ptr(weight), ptr(dw), *mom,
-                                                             C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
-        self._stepped[layer] = (weight, None)
+        self._step("step_conv_folded", layer, opt, weight, None, dw, None, moments, folded=True)
 
     def packed_weights(self) -> np.ndarray:
         """The plan's packed weight image as it is on the device now, as uint32 words (rtod_plan_read_packed_weights; tests and

@@ -85,23 +85,29 @@ def pack_boxes(bndbox, attrs, dev):
     return boxes, torch.tensor(offs, dtype=torch.int32).pin_memory().to(dev, non_blocking=True)
 
 
+def _loss_prelude(who, pred, bndbox, num_class, status):
+    """What ``yolo_loss_async`` and ``yolo_loss_grad_async`` do before their launch: the checks of ``pred`` and ``bndbox``, the
+    packed boxes, the workspace, and the outputs both have.  Returns ``(B, N, attrs, dev, boxes, offsets, (workspace, bytes), out)``."""
+    _need_cuda(pred, who)
+    attrs = 5 + int(num_class)
+    if pred.dim() != 3 or pred.size(2) != attrs or not pred.is_contiguous():
+        raise ValueError("%s: expected contiguous predictions [B,N,%d], got %s" % (who, attrs, tuple(pred.shape)))
+    B, N = pred.size(0), pred.size(1)
+    if len(bndbox) != B:
+        raise ValueError("%s: %d box lists for a batch of %d" % (who, len(bndbox), B))
+    dev = pred.device
+    boxes, offs = pack_boxes(bndbox, attrs, dev)
+    out = {"components": torch.empty(6, dtype=torch.float64, device=dev), "n_obj": torch.empty(B, dtype=torch.int32, device=dev),
+           "status": status if status is not None else torch.zeros(1, dtype=torch.int32, device=dev)}
+    return B, N, attrs, dev, boxes, offs, _workspace(dev, B, N), out
+
+
 def yolo_loss_async(pred, bndbox, heads, num_class, min_box_size=24, dense=False, per_image=False, status=None):
     """Enqueue rtod_yolo_loss for one batch; nothing synchronises.  ``pred`` [B,N,5+C] (TRAIN=True decode), ``bndbox`` one
     ``[T_i, 5+C]`` tensor (or None / empty) per image, ``heads`` as for ``make_heads``.  Returns a dict of device tensors:
     ``components`` float64 [6] (total, xy, wh, obj, noobj, cls), ``n_obj`` int32 [B], ``status`` int32 [1] (OR-ed into the caller's
     if given), and with ``per_image`` float64 [B,6], with ``dense`` ``target`` float32 [B,N,5+C] and ``mask`` uint8 [B,N]."""
-    _need_cuda(pred, "yolo_loss")
-    attrs = 5 + int(num_class)
-    if pred.dim() != 3 or pred.size(2) != attrs or not pred.is_contiguous():
-        raise ValueError("yolo_loss: expected contiguous predictions [B,N,%d], got %s" % (attrs, tuple(pred.shape)))
-    B, N = pred.size(0), pred.size(1)
-    if len(bndbox) != B:
-        raise ValueError("yolo_loss: %d box lists for a batch of %d" % (len(bndbox), B))
-    dev = pred.device
-    boxes, offs = pack_boxes(bndbox, attrs, dev)
-    ws, nbytes = _workspace(dev, B, N)
-    out = {"components": torch.empty(6, dtype=torch.float64, device=dev), "n_obj": torch.empty(B, dtype=torch.int32, device=dev),
-           "status": status if status is not None else torch.zeros(1, dtype=torch.int32, device=dev)}
+    B, N, attrs, dev, boxes, offs, (ws, nbytes), out = _loss_prelude("yolo_loss", pred, bndbox, num_class, status)
     if per_image:
         out["per_image"] = torch.empty((B, 6), dtype=torch.float64, device=dev)
     if dense:
@@ -121,18 +127,8 @@ def yolo_loss_grad_async(pred, bndbox, heads, num_class, min_box_size=24, grad_p
     device tensors: ``grad_raw`` a list with one ``[B, A*attrs, GH, GW]`` view per head (the gradient with respect to the raw head
     maps, views of one buffer ``grad_raw_flat``), ``components`` float64 [6] (bit-identical to ``yolo_loss_async``), ``n_obj``,
     ``status``, and with ``grad_pred`` the gradient with respect to ``pred`` [B,N,5+C]."""
-    _need_cuda(pred, "yolo_loss_grad")
-    attrs = 5 + int(num_class)
-    if pred.dim() != 3 or pred.size(2) != attrs or not pred.is_contiguous():
-        raise ValueError("yolo_loss_grad: expected contiguous predictions [B,N,%d], got %s" % (attrs, tuple(pred.shape)))
-    B, N = pred.size(0), pred.size(1)
-    if len(bndbox) != B:
-        raise ValueError("yolo_loss_grad: %d box lists for a batch of %d" % (len(bndbox), B))
-    dev = pred.device
-    boxes, offs = pack_boxes(bndbox, attrs, dev)
-    ws, nbytes = _workspace(dev, B, N)
-    out = {"grad_raw_flat": torch.empty(B * N * attrs, dtype=torch.float32, device=dev), "components": torch.empty(6, dtype=torch.float64, device=dev),
-           "n_obj": torch.empty(B, dtype=torch.int32, device=dev), "status": status if status is not None else torch.zeros(1, dtype=torch.int32, device=dev)}
+    B, N, attrs, dev, boxes, offs, (ws, nbytes), out = _loss_prelude("yolo_loss_grad", pred, bndbox, num_class, status)
+    out["grad_raw_flat"] = torch.empty(B * N * attrs, dtype=torch.float32, device=dev)
     if grad_pred:
         out["grad_pred"] = torch.empty((B, N, attrs), dtype=torch.float32, device=dev)
     ptr = lambda k: C.c_void_p(out[k].data_ptr()) if k in out else None
@@ -153,30 +149,40 @@ def yolo_loss_grad_async(pred, bndbox, heads, num_class, min_box_size=24, grad_p
 _wgrad_ws = {}
 
 
-def conv1x1_wgrad_async(dz, x, bias=True):
-    """Enqueue rtod_conv1x1_wgrad: ``dz`` [B,Cout,H,W] and ``x`` [B,Cin,H,W] (contiguous float32 device tensors, Cin a multiple
-    of 32) -> ``(dW [Cout,Cin,1,1], db [Cout] or None)``; nothing synchronises."""
-    _need_cuda(dz, "conv1x1_wgrad")
-    _need_cuda(x, "conv1x1_wgrad")
+def _wgrad(who, dz, x, size, row_scale, bias):
+    """The body of ``conv1x1_wgrad_async`` (``size`` None: rtod_conv1x1_wgrad, shape (B, Cout, Cin, pixels)) and ``conv_wgrad_async``
+    (rtod_conv_wgrad, shape (B, Cout, Cin, H, W, size)): the tensor checks, the workspace cached per shape, the outputs, the launch."""
+    _need_cuda(dz, who)
+    _need_cuda(x, who)
     if dz.dim() != 4 or x.dim() != 4 or dz.size(0) != x.size(0) or tuple(dz.shape[2:]) != tuple(x.shape[2:]) or dz.dtype != torch.float32 or x.dtype != torch.float32:
-        raise ValueError("conv1x1_wgrad: expected float32 dz [B,Cout,H,W] and x [B,Cin,H,W], got %s and %s" % (tuple(dz.shape), tuple(x.shape)))
+        raise ValueError("%s: expected float32 dz [B,Cout,H,W] and x [B,Cin,H,W], got %s and %s" % (who, tuple(dz.shape), tuple(x.shape)))
     dz, x = dz.contiguous(), x.contiguous()
-    B, cout, cin, pixels = dz.size(0), dz.size(1), x.size(1), dz.size(2) * dz.size(3)
-    dev = dz.device
-    key = (dev.index, B, cout, cin, pixels)
+    B, cout, cin, H, W = dz.size(0), dz.size(1), x.size(1), dz.size(2), dz.size(3)
+    shape = (B, cout, cin, H * W) if size is None else (B, cout, cin, H, W, int(size))
+    lib, dev = _ffi.lib(), dz.device
+    key = (dev.index,) + shape
     ws = _wgrad_ws.get(key)
     if ws is None:
         nbytes = C.c_size_t()
-        _ffi.check(_ffi.lib().rtod_conv1x1_wgrad_workspace(B, cout, cin, pixels, C.byref(nbytes)))
+        _ffi.check((lib.rtod_conv1x1_wgrad_workspace if size is None else lib.rtod_conv_wgrad_workspace)(*shape, C.byref(nbytes)))
         if len(_wgrad_ws) > 16:
             _wgrad_ws.clear()
         ws = _wgrad_ws[key] = (torch.empty((nbytes.value + 7) // 8, dtype=torch.float64, device=dev), nbytes.value)
-    dw = torch.empty((cout, cin, 1, 1), dtype=torch.float32, device=dev)
+    k = 1 if size is None else int(size)
+    dw = torch.empty((cout, cin, k, k), dtype=torch.float32, device=dev)
     db = torch.empty(cout, dtype=torch.float32, device=dev) if bias else None
+    scale = () if size is None else (_scale_ptr(row_scale, cout, dev),)
     with torch.cuda.device(dev):
-        _ffi.check(_ffi.lib().rtod_conv1x1_wgrad(C.c_void_p(dz.data_ptr()), C.c_void_p(x.data_ptr()), B, cout, cin, pixels, C.c_void_p(dw.data_ptr()),
-                                                 C.c_void_p(db.data_ptr()) if bias else None, C.c_void_p(ws[0].data_ptr()), ws[1], _stream(dev)))
+        _ffi.check((lib.rtod_conv1x1_wgrad if size is None else lib.rtod_conv_wgrad)(
+            C.c_void_p(dz.data_ptr()), C.c_void_p(x.data_ptr()), *shape, *scale, C.c_void_p(dw.data_ptr()), C.c_void_p(db.data_ptr()) if bias else None,
+            C.c_void_p(ws[0].data_ptr()), ws[1], _stream(dev)))
     return dw, db
+
+
+def conv1x1_wgrad_async(dz, x, bias=True):
+    """Enqueue rtod_conv1x1_wgrad: ``dz`` [B,Cout,H,W] and ``x`` [B,Cin,H,W] (contiguous float32 device tensors, Cin a multiple
+    of 32) -> ``(dW [Cout,Cin,1,1], db [Cout] or None)``; nothing synchronises."""
+    return _wgrad("conv1x1_wgrad", dz, x, None, None, bias)
 
 
 def _scale_ptr(row_scale, cout, dev):
@@ -196,27 +202,7 @@ def conv_wgrad_async(dz, x, size, row_scale=None, bias=False):
     32) -> ``(dW [Cout,Cin,size,size], db [Cout] or None)`` of a ``size`` x ``size`` (1 or 3), stride-1, same-padding conv.
     ``row_scale`` (float64 device tensor [Cout], or the device address ``Darknet.conv_scale`` returns): every row of dW times it,
     one rounding.  Nothing synchronises; the workspace is cached per shape."""
-    _need_cuda(dz, "conv_wgrad")
-    _need_cuda(x, "conv_wgrad")
-    if dz.dim() != 4 or x.dim() != 4 or dz.size(0) != x.size(0) or tuple(dz.shape[2:]) != tuple(x.shape[2:]) or dz.dtype != torch.float32 or x.dtype != torch.float32:
-        raise ValueError("conv_wgrad: expected float32 dz [B,Cout,H,W] and x [B,Cin,H,W], got %s and %s" % (tuple(dz.shape), tuple(x.shape)))
-    dz, x = dz.contiguous(), x.contiguous()
-    B, cout, cin, H, W, size = dz.size(0), dz.size(1), x.size(1), dz.size(2), dz.size(3), int(size)
-    dev = dz.device
-    key = (dev.index, B, cout, cin, H, W, size)
-    ws = _wgrad_ws.get(key)
-    if ws is None:
-        nbytes = C.c_size_t()
-        _ffi.check(_ffi.lib().rtod_conv_wgrad_workspace(B, cout, cin, H, W, size, C.byref(nbytes)))
-        if len(_wgrad_ws) > 16:
-            _wgrad_ws.clear()
-        ws = _wgrad_ws[key] = (torch.empty((nbytes.value + 7) // 8, dtype=torch.float64, device=dev), nbytes.value)
-    dw = torch.empty((cout, cin, size, size), dtype=torch.float32, device=dev)
-    db = torch.empty(cout, dtype=torch.float32, device=dev) if bias else None
-    with torch.cuda.device(dev):
-        _ffi.check(_ffi.lib().rtod_conv_wgrad(C.c_void_p(dz.data_ptr()), C.c_void_p(x.data_ptr()), B, cout, cin, H, W, size, _scale_ptr(row_scale, cout, dev),
-                                              C.c_void_p(dw.data_ptr()), C.c_void_p(db.data_ptr()) if bias else None, C.c_void_p(ws[0].data_ptr()), ws[1], _stream(dev)))
-    return dw, db
+    return _wgrad("conv_wgrad", dz, x, int(size), row_scale, bias)
 
 
 def conv1x1_dgrad_async(w, dz, y=None, slope=1.0):
@@ -521,7 +507,7 @@ class DarknetTrainer:
         if missing:
             self.darknet.sync_stepped_parameters()
             for layer in missing:
-                conv = next(sub for name, sub in self.darknet.module_list[layer].named_children() if name.startswith("conv_"))
+                conv = self.darknet._conv_bn(layer)[0]
                 bias = None if conv.bias is None else conv.bias.detach().to(dev, torch.float32).clone()
                 self._head_masters[layer] = [conv.weight.detach().to(dev, torch.float32).clone(), bias]
         return self._head_masters

@@ -1,0 +1,113 @@
+"""GPU test that pins the float bits of the training path across commits: the weight gradients (csrc/wgrad.hip through
+rtod_conv1x1_wgrad and rtod_conv_wgrad), the optimiser steps that re-pack in place (csrc/head_step.hip through
+rtod_plan_step_conv and rtod_plan_step_conv_folded) and their host twins (rtod_plan_update_conv, rtod_plan_update_conv_weight).
+Run on an MI355X with ``pytest -m gpu``.
+
+The other GPU tests hold these kernels to integer exactness, to a summation bound, to the host pack and to call-to-call
+reproducibility; none of that fixes the bits of a float sum from one commit to the next.  This file compares them with a record,
+tests/golden/train_bits.json, written once by tools/dump_train_bits.py from the library as it stood BEFORE the head and block
+entries were put on one code path (its "recorded_from" names the commit).  It is not regenerated: a change of these bits is a
+change of the arithmetic, of the slice rule or of the summation order and has to be argued as such.
+
+* Weight gradients: SHA-256 of the float32 bytes of dW and of db on shapes from head_grad_cases.py / block_grad_cases.py — one
+  slice, the slice cap below 16 (524 tiles: cap 2, with a random float64 row scale), 16 slices with K one short of a slice
+  boundary, Cout tails, chunks that cross an image boundary.  Inputs are seeded standard normals.
+* Steps: mini_cfg(64, 64) with both keep options, trainable="blocks", on the batch of test_block_grad_gpu._batch(): one SGD step,
+  then two Adam steps; after each phase the packed image, every master and every moment are hashed.
+* Updates: update_conv / update_conv_weight of every trained conv with its master; the packed image keeps its hash.
+"""
+import hashlib
+import json
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from realtimeobjectdetection_amd import cfgs, train as T
+from realtimeobjectdetection_amd.train import HeadOptimizer
+from test_block_grad_gpu import _batch, _block_trainer
+
+pytestmark = pytest.mark.gpu
+F = np.float32
+RECORD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "train_bits.json")
+
+HEAD_SHAPES = [(2, 18, 32, 2, 2), (3, 255, 96, 13, 13), (1, 64, 64, 127, 1)]      # (B, Cout, Cin, H, W)
+CAP_SHAPE = (2, 256, 928, 4, 4)                                                    # size 3: 524 tiles, at most 2 slices
+WGRAD_CASES = [("conv1x1_wgrad", 1, s) for s in HEAD_SHAPES] + [("conv_wgrad", size, s) for size in (1, 3) for s in HEAD_SHAPES + [CAP_SHAPE]]
+PRECISIONS = ["fp32", "f16s3"]
+
+
+def sha(t):
+    a = t.detach().cpu().contiguous().numpy() if isinstance(t, torch.Tensor) else np.ascontiguousarray(t)
+    return hashlib.sha256(a.tobytes()).hexdigest()
+
+
+def wgrad_key(entry, size, shape):
+    return "%s/size%d/%s" % (entry, size, "x".join(str(v) for v in shape))
+
+
+def wgrad_digest(entry, size, shape):
+    """{"dw", "db"}: digests of one weight-gradient call on seeded inputs."""
+    B, cout, cin, H, W = shape
+    rng = np.random.RandomState(1000 * B + 10 * cout + H * W + size)
+    dz = torch.from_numpy(rng.standard_normal((B, cout, H, W)).astype(F)).cuda()
+    x = torch.from_numpy(rng.standard_normal((B, cin, H, W)).astype(F)).cuda()
+    if entry == "conv1x1_wgrad":
+        dw, db = T.conv1x1_wgrad_async(dz, x)
+    else:
+        scale = torch.from_numpy(rng.uniform(0.2, 3.0, cout) * rng.choice([-1.0, 1.0], cout)).cuda() if shape == CAP_SHAPE else None
+        dw, db = T.conv_wgrad_async(dz, x, size, row_scale=scale, bias=True)
+    assert tuple(dw.shape) == (cout, cin, size, size) and tuple(db.shape) == (cout,)
+    return {"dw": sha(dw), "db": sha(db)}
+
+
+def _state_digest(m, t):
+    out = {"image": sha(m.packed_weights())}
+    for layer, st in sorted(t.optimizer.state.items()):
+        for k, v in sorted(st.items()):
+            out["%d.%s" % (layer, k)] = sha(v) if isinstance(v, torch.Tensor) else int(v)
+    return out
+
+
+def step_digest(precision, d):
+    """{"sgd", "adam", "update"}: digests of the packed image, the masters and the moments after one SGD step, after two further
+    Adam steps, and of the image after the host twins re-packed every trained conv from its master."""
+    m, t = _block_trainer(d, cfgs.mini_cfg(64, 64), 64, precision)
+    xd, bnd = _batch()
+    out = {}
+    t.optimizer = HeadOptimizer("sgd", lr=1e-4)
+    t.feed_forward_through_model(xd, bnd)
+    out["sgd"] = _state_digest(m, t)
+    t.optimizer = HeadOptimizer("adam", lr=1e-4)
+    for _ in range(2):
+        t.feed_forward_through_model(xd, bnd)
+    out["adam"] = _state_digest(m, t)
+    assert m.active_precision == precision and sorted(t._head_masters) == [13, 14, 21, 22]
+    for layer, (w, b) in sorted(t._head_masters.items()):
+        if b is None:
+            m.update_conv_weight(layer, w)
+        else:
+            m.update_conv(layer, w, b)
+    out["update"] = {"image": sha(m.packed_weights())}
+    return out
+
+
+def _record():
+    with open(RECORD) as f:
+        return json.load(f)["digests"]
+
+
+@pytest.mark.parametrize("entry,size,shape", WGRAD_CASES)
+def test_weight_gradient_has_the_recorded_bits(entry, size, shape):
+    got = wgrad_digest(entry, size, shape)
+    print("TRAIN BITS %s: %s" % (wgrad_key(entry, size, shape), got))
+    assert got == _record()[wgrad_key(entry, size, shape)]
+
+
+@pytest.mark.parametrize("precision", PRECISIONS)
+def test_steps_and_updates_have_the_recorded_bits(tmp_path, precision):
+    got = step_digest(precision, tmp_path)
+    print("TRAIN BITS step/%s: %s" % (precision, got))
+    assert got["update"]["image"] == got["adam"]["image"]             # the host twin of the masters changes no bit of the image
+    assert got == _record()["step/" + precision]
