@@ -195,6 +195,11 @@ int rtod_plan_set_precision(rtod_plan* plan, int mode);
  *   "keep_block_inputs" (default 0) likewise the buffer read by every detection BLOCK conv (rtod_plan_head_blocks), a concat buffer
  *                       where that input is a route: the activations rtod_conv_wgrad needs.  Liveness only as well; in addition
  *                       rtod_plan_load_weights then keeps the blocks' frozen BatchNorm scales on the device (rtod_plan_conv_scale)
+ *   "keep_neck_activations" (default 0) likewise every buffer that a NECK conv (rtod_plan_neck_layers) or a detection-head conv reads or
+ *                       writes, routes as their concat buffers: the activations of the walk behind the backbone (rtod_conv_dgrad,
+ *                       rtod_upsample2x_grad, rtod_conv_wgrad).  Requires no other option.  Liveness only as well; rtod_plan_load_weights
+ *                       then keeps the frozen BatchNorm scales of ALL neck convs on the device, and rtod_plan_conv_scale,
+ *                       rtod_plan_update_conv_weight and rtod_plan_step_conv_folded accept any neck conv (without it: blocks alone)
  *   "force_f16s3_variant" / "force_f32_variant"   >= 0: one tile variant for every conv (tests, A/B runs)
  * Options that leave a cfg inexpressible in the split-f16 format return RTOD_E_CFG when precision is 1 or 2 (so does setting
  * "narrow_cin" back to 0 on a plan that needs it); the plan then stays as it was. */
@@ -234,6 +239,16 @@ int rtod_plan_update_conv(rtod_plan* plan, int layer, const float* weight_oihw_h
  * A head that reads a max-pool, a stride-2 conv, a SiLU conv or a conv without BatchNorm has none.  Returns the number of heads,
  * capacity as rtod_plan_head_layers. */
 int rtod_plan_head_blocks(const rtod_plan* plan, int* head_conv_layers, int* block_conv_layers, int* block_input_layers, int capacity);
+/* (new) The detection NECK of a plan: the BatchNorm convs, in ascending order, of the largest set G of traversable layers that is
+ * closed downstream — a layer is in G only if every reader of its output is in G or is a [yolo] layer — so that nothing outside G
+ * lies between a neck conv and the loss and the walk back through G gives exact gradients (BatchNorm frozen).  Traversable:
+ *   a conv in front of a [yolo] layer (1x1, no BatchNorm, Cin a multiple of 32, read by [yolo] layers alone);
+ *   a conv that is a block by the definition at rtod_plan_head_blocks except for its position (any place in the cfg);
+ *   a [route];  a 2x [upsample], bilinear or nearest.
+ * conv_layers[i] is a neck conv, input_layers[i] the layer it reads (conv - 1, possibly a route or an upsample; see option
+ * "keep_neck_activations").  YOLOv3: 75-80, 84, 87-92, 96, 99-104; YOLOv3-tiny: 12, 13, 14, 18, 21 (layer 8 is read by a max-pool).
+ * The listing does not depend on the option.  Returns the number of neck convs, capacity as rtod_plan_head_layers. */
+int rtod_plan_neck_layers(const rtod_plan* plan, int* conv_layers, int* input_layers, int capacity);
 /* (new) The frozen BatchNorm scale of a block conv, s[o] = (double)gamma[o] / sqrt((double)var[o] + 1e-5), exactly the factor
  * rtod_plan_load_weights folded into the conv, taken from the stream last loaded.  scale_host (may be NULL): `channels` doubles
  * are copied out.  scale_dev (may be NULL): receives a device pointer to the same doubles, owned by the plan and valid until
@@ -478,6 +493,32 @@ int rtod_conv1x1_wgrad(const float* dz_dev, const float* x_dev, int batch, int c
  * positive multiple of 32, slope NaN, batch * pixels >= 2^31 - 64. */
 int rtod_conv1x1_dgrad(const float* w_dev, const float* dz_dev, const float* y_dev, float slope, int batch, int cout, int cin, int pixels,
                        float* dx_dev, void* stream);
+/* (new) Data gradient through a size x size (1 or 3), stride 1, pad size / 2 convolution over dense NCHW maps, the generalisation of
+ * rtod_conv1x1_dgrad over the taps:
+ *   dx[b,c,y,x] = m(y_in[b,c,y,x]) * sum_{ky,kx,o} v[o,c,ky,kx] * dz[b,o,y+pad-ky,x+pad-kx]      (dz outside the map: an exact 0)
+ *   v = (float)((double)w * s[o]): the folded fp32 weight rtod_plan_load_weights computes from the raw master w_oihw_dev
+ *   [cout,cin,size,size] and the frozen scale row_scale_dev (rtod_plan_conv_scale); v = w when row_scale_dev is NULL.
+ * m, y_dev and slope as rtod_conv1x1_dgrad: y_dev [batch,cin,height,width] is the STORED output of the layer the conv reads.
+ * Exact-fp32 MFMA, 64 x 64 tiles of the [cin, batch * height * width] matrix.  The order of every sum is fixed by the shape alone:
+ * tap-major (tap = ky * size + kx ascending), o ascending within a tap (as pairs (o, o + 1), like rtod_conv1x1_dgrad), cout padded
+ * to a multiple of 32 with zeros.  Size 1: every dx element is ONE fmaf chain over o.  Size 3: one fmaf chain PER TAP over o, and the
+ * nine tap sums are added in ascending tap order, total = total + chain, one fp32 add each, in the kernel's registers (a single chain
+ * over 9 * cout terms errs by about 2^-24 sqrt(K) of the result, which at K = 4608 / 9216 was measured outside the project's 4 x the
+ * float32 floor).  Then one fp32 multiplication by the slope where the mask says so.  No workspace, no second kernel, plain stores,
+ * no atomics: bit-identical from call to call.  The size 1 call without a row scale is rtod_conv1x1_dgrad, bit for bit.  Enqueues only.  RTOD_E_ARG: as rtod_conv1x1_dgrad with height * width
+ * for pixels, and size not 1 or 3, cout * cin * size * size >= 2^31. */
+int rtod_conv_dgrad(const float* w_oihw_dev, const double* row_scale_dev, const float* dz_dev, const float* y_dev, float slope,
+                    int batch, int cout, int cin, int height, int width, int size, float* dx_dev, void* stream);
+/* (new) Backward of the 2x [upsample]: dz_dev [batch,channels,2*height,2*width] -> dx_dev [batch,channels,height,width].
+ * mode 0: bilinear, align_corners=False (the plan's forward, the reference's nn.Upsample): input row i is read by output rows
+ * 2i-1 .. 2i+2 with weights 0.25, 0.75, 0.75, 0.25, the edge clamp of the forward putting both weights of a border row on the edge
+ * (0.75 -> 1, the row outside dropped), columns alike; mode 1: nearest, the 2 x 2 outputs.  Gather form, one thread per input
+ * pixel: acc = acc + (wy * wx) * dz over the (at most 4 x 4) outputs, rows ascending, then columns, fp32 without contraction, then
+ * one multiplication by the mask m(y_dev) of the producing conv as in rtod_conv_dgrad (y_dev [batch,channels,height,width], NULL or
+ * slope == 1: none).  No atomics: bit-identical from call to call.  Enqueues only.  RTOD_E_ARG: a null dz / dx, batch, channels,
+ * height or width < 1, mode outside {0, 1}, slope NaN, 4 * height * width >= 2^31. */
+int rtod_upsample2x_grad(const float* dz_dev, const float* y_dev, float slope, int mode, int batch, int channels, int height, int width,
+                         float* dx_dev, void* stream);
 /* Weight gradient of a size x size (1 or 3), stride 1, pad size / 2 convolution over dense NCHW maps:
  *   dw_dev[o][c][ky][kx] = sum_{b,y,x} dz[b,o,y,x] * x[b,c,y+ky-pad,x+kx-pad]     (OIHW, overwritten; a tap outside the map adds an exact 0)
  *   db_dev[o] = sum_{b,y,x} dz[b,o,y,x]                                           (may be NULL)

@@ -440,8 +440,34 @@ int rtod_conv_wgrad(const float* dz_dev, const float* x_dev, int batch, int cout
 int rtod_conv1x1_dgrad(const float* w_dev, const float* dz_dev, const float* y_dev, float slope, int batch, int cout, int cin, int pixels,
                        float* dx_dev, void* stream) {
     RTOD_GUARD_BEGIN
-    return launch_conv1x1_dgrad(w_dev, dz_dev, y_dev, slope, batch, cout, cin, pixels, dx_dev, (hipStream_t)stream);
+    return launch_conv_dgrad("conv1x1_dgrad", w_dev, nullptr, dz_dev, y_dev, slope, batch, cout, cin, 1, pixels, 1, dx_dev, (hipStream_t)stream);
     RTOD_GUARD_END
+}
+
+int rtod_conv_dgrad(const float* w_oihw_dev, const double* row_scale_dev, const float* dz_dev, const float* y_dev, float slope,
+                    int batch, int cout, int cin, int height, int width, int size, float* dx_dev, void* stream) {
+    RTOD_GUARD_BEGIN
+    return launch_conv_dgrad("conv_dgrad", w_oihw_dev, row_scale_dev, dz_dev, y_dev, slope, batch, cout, cin, height, width, size, dx_dev, (hipStream_t)stream);
+    RTOD_GUARD_END
+}
+
+int rtod_upsample2x_grad(const float* dz_dev, const float* y_dev, float slope, int mode, int batch, int channels, int height, int width,
+                         float* dx_dev, void* stream) {
+    RTOD_GUARD_BEGIN
+    return launch_upsample2x_grad(dz_dev, y_dev, slope, mode, batch, channels, height, width, dx_dev, (hipStream_t)stream);
+    RTOD_GUARD_END
+}
+
+int rtod_plan_neck_layers(const rtod_plan* plan, int* conv_layers, int* input_layers, int capacity) {
+    if (!plan || capacity < 0 || (capacity > 0 && (!conv_layers || !input_layers))) { set_error("plan_neck_layers: bad args"); return RTOD_E_ARG; }
+    const std::vector<char> neck = plan->p.neck_graph();
+    int n = 0;
+    for (const auto& L : plan->p.layers) {
+        if (L.type != LT_CONV || !L.bn || !neck[L.index]) continue;
+        if (n < capacity) { conv_layers[n] = L.index; input_layers[n] = L.index - 1; }
+        ++n;
+    }
+    return n;
 }
 
 int rtod_plan_head_blocks(const rtod_plan* plan, int* head_conv_layers, int* block_conv_layers, int* block_input_layers, int capacity) {

@@ -1,18 +1,26 @@
-// Data gradient of a 1x1 convolution z = W y with the derivative of the activation that produced y fused, on the exact-fp32 MFMA
-// (v_mfma_f32_32x32x2_f32), gfx950:
-//   dx[b][c][p] = m(y[b][c][p]) * sum_o w[o][c] * dz[b][o][p]        m(y) = 1 for y > 0, else slope   (torch's leaky_relu backward)
-// w [cout, cin] (the float32 masters of a detection-head conv), dz [batch, cout, pixels] (rtod_yolo_loss_grad's map of that head),
-// y [batch, cin, pixels] the STORED output of the conv in front of it (rtod_plan_read_layer): the sign of a leaky-ReLU's output is
-// the sign of its input, so no pre-activation buffer is kept.  y == NULL or slope == 1: linear, no mask.
+// Data gradient of a size x size (1 or 3), stride 1, pad size / 2 convolution z = V * y with the derivative of the activation that
+// produced y fused, on the exact-fp32 MFMA (v_mfma_f32_32x32x2_f32), gfx950:
+//   dx[b][c][y][x] = m(y_in[b][c][y][x]) * sum_{ky,kx,o} v[o][c][ky][kx] * dz[b][o][y + pad - ky][x + pad - kx]
+//   m(y) = 1 for y > 0, else slope   (torch's leaky_relu backward)        v = (float)((double)w * s[o]), or w without a row scale
+// w [cout, cin, size, size] (OIHW: the float32 masters of a detection-head conv, or the raw masters of a BatchNorm conv with its
+// frozen scale s, which gives the folded weight pack_conv computes), dz [batch, cout, h, w], y_in [batch, cin, h, w] the STORED
+// output of the layer the conv reads (rtod_plan_read_layer): the sign of a leaky-ReLU's output is the sign of its input, so no
+// pre-activation buffer is kept.  y == NULL or slope == 1: linear, no mask.  dz positions outside the map are exact zeros.
 //
 // GEMM view:  D[m][n] = sum_k A[m][k] * B[k][n],  m = c (MFMA rows), n = b * pixels + p (MFMA columns, on the lane: coalesced dx
-// stores), k = o.  Both operands are contiguous along their free index (w along c, dz along p), so a thread stages one row index
-// for eight k and LDS holds a K-chunk k-major, [32][64 + 32] floats per operand: a wave's ds_read_b32 of one k takes 32
-// consecutive floats per lane half and the halves (k, k + 1) sit 96 floats = 32 banks apart.
+// stores), k = tap * cout32 + o with tap = ky * size + kx and cout32 = cout rounded up to 32.  A is contiguous along c up to the
+// tap stride, B along p: column n reads dz at the pixel shifted by the tap, so a thread stages one row index for eight k and LDS
+// holds a K-chunk k-major, [32][64 + 32] floats per operand: a wave's ds_read_b32 of one k takes 32 consecutive floats per lane
+// half and the halves (k, k + 1) sit 96 floats = 32 banks apart.  A chunk never straddles two taps, so the shift and the bounds
+// test of a staged pixel are taken once per chunk; tiles cross row and image boundaries freely (every column has its own (b, y, x)).
 // Workgroup: 4 waves, a 64 x 64 tile of dx, one 32 x 32 accumulator per wave; the next chunk's global loads are in flight during
-// the MFMAs.  K = cout is short and ragged (255): rows past cout are staged as zeros, which leave an fmaf chain unchanged, and
-// there are no K slices — every dx element is ONE fmaf chain over o in ascending pairs (o, o + 1), then one multiplication by
-// the mask.  Plain vector stores, no atomics: bit-identical from call to call.
+// the MFMAs.  cout is ragged (255): rows past cout are staged as zeros, which leave an fmaf chain unchanged.  Size 1: every dx
+// element is ONE fmaf chain over o in ascending pairs (o, o + 1).  Size 3: one such chain PER TAP, and the nine tap sums are added
+// in ascending tap order with one fp32 add each (total = total + chain, in registers: no workspace, no second kernel).  One chain
+// over all 9 * cout terms was measured first: at K = 4608 / 9216 its rounding error, about u sqrt(K) of the result, put dW of the
+// convs behind it at 4.2 - 4.4 x the error of torch's blocked float32 sums, past the project's 4 x gate; chains of cout terms stay
+// inside it.  Then one multiplication by the mask.  Plain vector stores, no atomics: bit-identical from call to call.  The size 1
+// instance without a row scale is the kernel of rtod_conv1x1_dgrad as it was.
 #include "rtod_internal.h"
 
 namespace rtod {
@@ -23,9 +31,18 @@ constexpr int DG_BK = 32;               // k per LDS stage
 constexpr int DG_T = 64;                // tile edge
 constexpr int DG_LD = DG_T + 32;        // floats per k row
 
+// what the instances other than <1, false> take behind the arguments of the 1x1 kernel: that instance keeps the old argument list, and
+// with it the old code, register for register
+struct DgradExtra { const double* scale; int height, width; };
+
+template <int SIZE, bool SCALED, class... Extra>
 __global__ __launch_bounds__(256)
 void dgrad_kernel(const float* __restrict__ w, const float* __restrict__ dz, const float* __restrict__ y, float slope,
-                  int cout, int cin, int pixels, int N, int grid_n, float* __restrict__ dx) {
+                  int cout, int cin, int pixels, int N, int grid_n, float* __restrict__ dx, Extra... extra) {
+    [[maybe_unused]] const double* scale = nullptr;
+    [[maybe_unused]] int height = 1, width = pixels;
+    if constexpr (sizeof...(Extra) > 0) { const DgradExtra x = (extra, ...); scale = x.scale; height = x.height; width = x.width; }
+    constexpr int TAPS = SIZE * SIZE;
     __shared__ float sA[DG_BK * DG_LD];
     __shared__ float sB[DG_BK * DG_LD];
     const int bm = blockIdx.x / grid_n, bn = blockIdx.x - bm * grid_n;
@@ -40,37 +57,57 @@ void dgrad_kernel(const float* __restrict__ w, const float* __restrict__ dz, con
     const bool c_ok = sc < cin, n_ok = sn < N;
     const int sb = n_ok ? sn / pixels : 0;
     const int sp = n_ok ? sn - sb * pixels : 0;
-    const float* wcol = w + sc;
+    const int sy = SIZE == 1 ? 0 : sp / width, sx = SIZE == 1 ? 0 : sp - sy * width;
+    const float* wcol = w + (int64_t)sc * TAPS;
     const float* dzrow = dz + (int64_t)sb * cout * pixels + sp;
 
     f32x16 acc;
 #pragma unroll
     for (int e = 0; e < 16; ++e) acc[e] = 0.f;
     float ra[DG_BK / 4], rb[DG_BK / 4];
-    auto gload = [&](int kc) {
+    auto gload = [&](int tap, int kc) {
+        bool t_ok = n_ok;                                         // the pixel this column reads under the tap lies inside the map
+        int shift = 0;
+        if constexpr (SIZE > 1) {
+            const int ty = SIZE / 2 - tap / SIZE, tx = SIZE / 2 - tap % SIZE;
+            t_ok = n_ok && (unsigned)(sy + ty) < (unsigned)height && (unsigned)(sx + tx) < (unsigned)width;
+            shift = ty * width + tx;
+        }
 #pragma unroll
         for (int i = 0; i < DG_BK / 4; ++i) {
             const int o = kc + ks + 4 * i;
-            ra[i] = (c_ok && o < cout) ? wcol[(int64_t)o * cin] : 0.f;
-            rb[i] = (n_ok && o < cout) ? dzrow[(int64_t)o * pixels] : 0.f;
+            ra[i] = (c_ok && o < cout) ? wcol[(int64_t)o * cin * TAPS + tap] : 0.f;
+            if constexpr (SCALED) ra[i] = (float)((double)ra[i] * (o < cout ? scale[o] : 0.0));
+            rb[i] = (t_ok && o < cout) ? dzrow[(int64_t)o * pixels + shift] : 0.f;
         }
     };
-    gload(0);
+    gload(0, 0);
     const float* pa = sA + lh * DG_LD + wm * 32 + lr;
     const float* pb = sB + lh * DG_LD + wn * 32 + lr;
-    for (int kc = 0; kc < cout; kc += DG_BK) {
-        __syncthreads();                                          // the previous chunk's LDS reads are done
+    [[maybe_unused]] f32x16 total;                                    // 3x3: the sum of the finished taps (the 1x1 instances have none)
+    if constexpr (SIZE > 1) total = acc;
+#pragma unroll 1
+    for (int tap = 0; tap < TAPS; ++tap)
+        for (int kc = 0; kc < cout; kc += DG_BK) {
+            __syncthreads();                                          // the previous chunk's LDS reads are done
 #pragma unroll
-        for (int i = 0; i < DG_BK / 4; ++i) {
-            sA[(ks + 4 * i) * DG_LD + r] = ra[i];
-            sB[(ks + 4 * i) * DG_LD + r] = rb[i];
+            for (int i = 0; i < DG_BK / 4; ++i) {
+                sA[(ks + 4 * i) * DG_LD + r] = ra[i];
+                sB[(ks + 4 * i) * DG_LD + r] = rb[i];
+            }
+            __syncthreads();
+            if (kc + DG_BK < cout) gload(tap, kc + DG_BK);            // in flight while the MFMAs below run
+            else if (SIZE > 1 && tap + 1 < TAPS) gload(tap + 1, 0);
+#pragma unroll
+            for (int t = 0; t < DG_BK / 2; ++t)                       // lane half lh supplies k = 2 t + lh
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(pa[2 * t * DG_LD], pb[2 * t * DG_LD], acc, 0, 0, 0);
+            if constexpr (SIZE > 1)
+                if (kc + DG_BK >= cout) {                             // the tap's chain joins the total: one fp32 add per tap, ascending
+#pragma unroll
+                    for (int e = 0; e < 16; ++e) { total[e] = total[e] + acc[e]; acc[e] = 0.f; }
+                }
         }
-        __syncthreads();
-        if (kc + DG_BK < cout) gload(kc + DG_BK);                 // in flight while the MFMAs below run
-#pragma unroll
-        for (int t = 0; t < DG_BK / 2; ++t)                       // lane half lh supplies k = 2 t + lh
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(pa[2 * t * DG_LD], pb[2 * t * DG_LD], acc, 0, 0, 0);
-    }
+    if constexpr (SIZE > 1) acc = total;
     // D: column = lane & 31 (n), row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5) (c)
     const int n = bn * DG_T + wn * 32 + lr;
     if (n >= N) return;
@@ -87,19 +124,31 @@ void dgrad_kernel(const float* __restrict__ w, const float* __restrict__ dz, con
     }
 }
 
-int launch_conv1x1_dgrad(const float* w, const float* dz, const float* y, float slope, int batch, int cout, int cin, int pixels,
-                         float* dx, hipStream_t s) {
-    if (!w || !dz || !dx) { set_error("conv1x1_dgrad: null pointer"); return RTOD_E_ARG; }
-    if (batch < 1 || cout < 1 || cin < 32 || cin % 32 || pixels < 1 || !(slope == slope)) {
-        set_error("conv1x1_dgrad: unsupported arguments (batch=%d cout=%d cin=%d pixels=%d slope=%g; cin must be a multiple of 32)", batch, cout, cin, pixels, (double)slope);
+int launch_conv_dgrad(const char* who, const float* w, const double* row_scale, const float* dz, const float* y, float slope, int batch, int cout,
+                      int cin, int h, int w_, int size, float* dx, hipStream_t s) {
+    if (!w || !dz || !dx) { set_error("%s: null pointer", who); return RTOD_E_ARG; }
+    if (batch < 1 || cout < 1 || cin < 32 || cin % 32 || h < 1 || w_ < 1 || (size != 1 && size != 3) || !(slope == slope)) {
+        set_error("%s: unsupported arguments (batch=%d cout=%d cin=%d height=%d width=%d size=%d slope=%g; cin must be a multiple of 32, size 1 or 3)",
+                  who, batch, cout, cin, h, w_, size, (double)slope);
         return RTOD_E_ARG;
     }
-    const int64_t N = (int64_t)batch * pixels;
-    if (N > INT32_MAX - 64 || (int64_t)cout * cin > INT32_MAX) { set_error("conv1x1_dgrad: batch * pixels or cout * cin exceeds int32"); return RTOD_E_ARG; }
+    const int64_t N = (int64_t)batch * h * w_;
+    if ((int64_t)h * w_ > INT32_MAX || N > INT32_MAX - 64 || (int64_t)cout * cin * size * size > INT32_MAX) {
+        set_error("%s: batch * pixels or cout * cin * size * size exceeds int32", who);
+        return RTOD_E_ARG;
+    }
     const int64_t gm = (cin + DG_T - 1) / DG_T, gn = (N + DG_T - 1) / DG_T;
-    if (gm * gn > INT32_MAX) { set_error("conv1x1_dgrad: grid too large"); return RTOD_E_ARG; }
-    hipLaunchKernelGGL(dgrad_kernel, dim3((unsigned)(gm * gn)), dim3(256), 0, s, w, dz, y, slope, cout, cin, pixels, (int)N, (int)gn, dx);
-    return hip_fail(hipGetLastError(), "conv1x1_dgrad launch");
+    if (gm * gn > INT32_MAX) { set_error("%s: grid too large", who); return RTOD_E_ARG; }
+    const dim3 grid((unsigned)(gm * gn)), block(256);
+    const int pixels = h * w_;
+    const DgradExtra x{row_scale, h, w_};
+#define RTOD_DGRAD(SIZE, SCALED) hipLaunchKernelGGL((dgrad_kernel<SIZE, SCALED, DgradExtra>), grid, block, 0, s, w, dz, y, slope, cout, cin, pixels, (int)N, (int)gn, dx, x)
+    if (size == 1 && !row_scale) hipLaunchKernelGGL((dgrad_kernel<1, false>), grid, block, 0, s, w, dz, y, slope, cout, cin, pixels, (int)N, (int)gn, dx);
+    else if (size == 1) RTOD_DGRAD(1, true);
+    else if (row_scale) RTOD_DGRAD(3, true);
+    else RTOD_DGRAD(3, false);
+#undef RTOD_DGRAD
+    return hip_fail(hipGetLastError(), who);
 }
 
 }  // namespace rtod

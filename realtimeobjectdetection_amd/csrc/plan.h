@@ -147,6 +147,8 @@ struct Plan {
                                       // the activations of rtod_conv1x1_wgrad); liveness only: launches, tiles and output bits are unchanged
     bool opt_keep_block_inputs = false; // ... and the buffer every BLOCK conv reads (block_shape_ok: the BatchNorm conv a head conv reads): the activations of
                                       // rtod_conv_wgrad.  Liveness only as well; the frozen BatchNorm scales then also live on the device (d_block_scale)
+    bool opt_keep_neck_activations = false; // ... and every buffer a NECK conv (neck_graph) or a head conv reads or writes: the activations of the walk behind the
+                                      // backbone (rtod_conv_dgrad, rtod_upsample2x_grad, rtod_conv_wgrad).  Liveness only; the scales of all neck convs on the device
     bool opt_fuse_stem_pool = true;   // ... with the 2x2 / stride-2 max-pool that follows it in the same kernel where the plan allows it (off: A/B and tests)
     int opt_force_f16s3_variant = -1; // >= 0: tile variant for every split-f16 conv (>= BAND_VARIANT_BASE: band layers)
     int opt_force_f32_variant = -1;   // >= 0: tile variant for every exact-fp32 conv
@@ -180,7 +182,14 @@ struct Plan {
     int read_packed_weights(float* out, size_t capacity, size_t* needed) const;     // the device image back on the host (synchronises)
     // detection blocks (rtod_plan_head_blocks): the BatchNorm conv that a head conv reads, trained with BatchNorm frozen
     bool block_shape_ok(int layer) const;                                           // the cfg's part of the definition (what keep_block_inputs keeps alive)
+    bool block_plan_ok(int layer) const;                                            // the plan's part: generic packed layout, no pair member, output stored
     int block_of_head(int head_conv_layer) const;                                   // the block conv of that head conv, or -1
+    // the detection neck (rtod_plan_neck_layers): the largest set of traversable layers (head convs, block-shaped BatchNorm convs that pass
+    // block_plan_ok, routes, 2x upsamples) closed downstream: every reader of a member is a member or a [yolo] layer
+    std::vector<std::vector<int>> consumers() const;                                // the readers of every layer's output, ascending
+    std::vector<char> neck_graph() const;                                           // membership per layer
+    bool neck_conv(int layer) const;                                                // a BatchNorm conv of the neck
+    bool trains_folded(int layer) const;                                            // what block_conv accepts: a block conv; with keep_neck_activations any neck conv
     int block_conv(const char* who, int layer, size_t& slot) const;                 // the slot of a block conv, or why `layer` is none
     int update_conv_weight(int layer, const float* weight_oihw);                    // re-pack and upload one block conv, BatchNorm as loaded (rtod_plan_update_conv_weight)
     int step_conv_folded(int layer, const rtod_opt_step* opt, float* weight, const float* dw, float* m_w, float* v_w, hipStream_t s);   // rtod_plan_step_conv_folded
@@ -189,7 +198,7 @@ struct Plan {
     std::map<int, std::vector<float>> block_bn;     // block conv layer -> its [beta, gamma, mean, var] of the stream last loaded
     std::map<int, std::vector<double>> block_scale; // ... -> gamma / sqrt(var + 1e-5), the frozen scale pack_conv folds
     std::map<int, int64_t> block_scale_off;         // ... -> offset in d_block_scale (doubles)
-    double* d_block_scale = nullptr;                // option keep_block_inputs: the scales on the device, allocated at the first load
+    double* d_block_scale = nullptr;                // options keep_block_inputs / keep_neck_activations: the scales on the device, allocated at the first load
     int64_t block_scale_doubles = 0;                // ... and how many doubles that allocation holds
     bool feeds_yolo(int layer) const { return layers[layer].type == LT_CONV && layer + 1 < (int)layers.size() && layers[layer + 1].type == LT_YOLO; }
     int forward(const float* x, int batch, float* out, hipStream_t s, float* launch_ms, bool tune = false);

@@ -64,7 +64,7 @@ int Plan::set_option(const char* name, int value) {
         {"stem_kernel", &Plan::opt_stem_kernel}, {"band_kernel", &Plan::opt_band_kernel}, {"fuse_shortcut", &Plan::opt_fuse_shortcut},
         {"fuse_decode", &Plan::opt_fuse_decode}, {"zero_copy_concat", &Plan::opt_zero_copy_concat}, {"narrow_cin", &Plan::opt_narrow_cin},
         {"stem_pool", &Plan::opt_stem_pool}, {"fuse_stem_pool", &Plan::opt_fuse_stem_pool}, {"keep_head_inputs", &Plan::opt_keep_head_inputs},
-        {"keep_block_inputs", &Plan::opt_keep_block_inputs},
+        {"keep_block_inputs", &Plan::opt_keep_block_inputs}, {"keep_neck_activations", &Plan::opt_keep_neck_activations},
     };
     const std::string k(name);
     bool* flag = nullptr; int* num = nullptr;
@@ -118,10 +118,9 @@ DecodeArgs Plan::decode_args(const Layer& Y) const {
     return d;
 }
 
-int Plan::plan_buffers() {
-    const int n = (int)layers.size();
-    // consumers of every layer's output
-    std::vector<std::vector<int>> cons(n);
+// consumers of every layer's output
+std::vector<std::vector<int>> Plan::consumers() const {
+    std::vector<std::vector<int>> cons(layers.size());
     for (const auto& L : layers) {
         const int i = L.index;
         switch (L.type) {
@@ -129,6 +128,12 @@ int Plan::plan_buffers() {
             case LT_SHORTCUT: case LT_ROUTE: for (int s : L.srcs) cons[s].push_back(i); break;
         }
     }
+    return cons;
+}
+
+int Plan::plan_buffers() {
+    const int n = (int)layers.size();
+    const std::vector<std::vector<int>> cons = consumers();
     // aliases
     for (auto& L : layers) {
         if (L.type == LT_ROUTE && L.srcs.size() == 1) L.alias_of = L.srcs[0];
@@ -303,6 +308,16 @@ int Plan::plan_buffers() {
     if (opt_keep_block_inputs)
         for (const auto& l : launches)
             if (l.kind == LK_CONV && l.layer + 1 < n && feeds_yolo(l.layer + 1) && block_shape_ok(l.layer)) touch(buf_of_layer(l.in_layer), n);
+    // option keep_neck_activations: what every neck conv and every head conv reads and writes (the walk reads outputs for the
+    // activation masks, inputs for the weight gradients; routes are kept as their concat buffers)
+    if (opt_keep_neck_activations) {
+        const std::vector<char> neck = neck_graph();
+        for (const auto& l : launches)
+            if (l.kind == LK_CONV && (neck[l.layer] || feeds_yolo(l.layer))) {
+                touch(buf_of_layer(l.in_layer), n);
+                if (l.out_layer >= 0) touch(buf_of_layer(l.out_layer), n);
+            }
+    }
     // a concat buffer is live from its first producer to its last consumer: touches above cover both
     for (int b = 0; b < NB; ++b) {
         if (bufs[b].last < 0) { bufs[b].first = bufs[b].last = 0; }      // never used (dead layer): still give it space
@@ -324,17 +339,51 @@ bool Plan::block_shape_ok(int layer) const {
 
 // ... and the plan's part: packed in one of the two generic layouts (no stem, not narrow), neither host nor guest of a
 // fused-pointwise candidate pair (candidates, not forms, as replaceable_conv), its output stored where rtod_plan_read_layer finds it
-int Plan::block_of_head(int head) const {
-    if (head < 1 || head >= (int)layers.size() || !feeds_yolo(head) || !block_shape_ok(head - 1)) return -1;
-    const int layer = head - 1;
+bool Plan::block_plan_ok(int layer) const {
     for (const auto& l : launches) {
         if (l.kind != LK_CONV || l.layer != layer || l.conv_slot < 0) continue;
         const PackedConv& pc = convs[l.conv_slot];
-        if (pc.stem || pc.stem16 || pc.narrow || l.pw_guest >= 0 || l.pw_host >= 0 || l.out_layer != layer) return -1;
-        if (pc.Kpad < pc.K || layers[layer].cout > pc.Npad || pc.cin_p != layers[layer].cin) return -1;
-        return layer_form(layer).readable && layers[layer].buf >= 0 ? layer : -1;
+        if (pc.stem || pc.stem16 || pc.narrow || l.pw_guest >= 0 || l.pw_host >= 0 || l.out_layer != layer) return false;
+        if (pc.Kpad < pc.K || layers[layer].cout > pc.Npad || pc.cin_p != layers[layer].cin) return false;
+        return layer_form(layer).readable && layers[layer].buf >= 0;
     }
-    return -1;
+    return false;
+}
+
+int Plan::block_of_head(int head) const {
+    if (head < 1 || head >= (int)layers.size() || !feeds_yolo(head) || !block_shape_ok(head - 1)) return -1;
+    return block_plan_ok(head - 1) ? head - 1 : -1;
+}
+
+// The detection neck.  Traversable: a 1x1 head conv (no BatchNorm, Cin a multiple of 32) that [yolo] layers alone read, a BatchNorm
+// conv that is a block by both parts of the definition above, a route, a 2x upsample.  A layer is in the graph if it is traversable
+// and every reader of its output is in the graph or a [yolo] layer; readers have higher indices, so one descending pass decides it.
+// Closure is what makes the gradients exact: nothing outside the graph lies between a member and the loss.
+std::vector<char> Plan::neck_graph() const {
+    const int n = (int)layers.size();
+    const std::vector<std::vector<int>> cons = consumers();
+    std::vector<char> in(n, 0);
+    for (int i = n - 1; i >= 0; --i) {
+        const Layer& L = layers[i];
+        bool ok = !cons[i].empty();
+        if (L.type == LT_CONV && feeds_yolo(i)) {
+            ok = ok && !L.bn && L.size == 1 && L.stride == 1 && L.cin % 32 == 0;
+            for (int r : cons[i]) ok = ok && layers[r].type == LT_YOLO;
+        } else if (L.type == LT_CONV) ok = ok && block_shape_ok(i) && block_plan_ok(i);
+        else if (L.type == LT_UPSAMPLE) ok = ok && L.stride == 2;
+        else ok = ok && L.type == LT_ROUTE;
+        for (int r : cons[i]) ok = ok && (layers[r].type == LT_YOLO || in[r]);
+        in[i] = ok ? 1 : 0;
+    }
+    return in;
+}
+
+bool Plan::neck_conv(int layer) const {
+    return layer >= 0 && layer < (int)layers.size() && layers[layer].type == LT_CONV && layers[layer].bn && neck_graph()[layer];
+}
+
+bool Plan::trains_folded(int layer) const {
+    return block_of_head(layer + 1) == layer || (opt_keep_neck_activations && neck_conv(layer));
 }
 
 bool Plan::uses_split(const Layer& L) const {

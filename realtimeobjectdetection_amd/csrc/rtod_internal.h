@@ -372,9 +372,13 @@ size_t wgrad_workspace_bytes(int batch, int cout, int cin, int h, int w, int siz
 int wgrad_check_shape(const char* who, int batch, int cout, int cin, int h, int w, int size);
 int launch_wgrad(const char* who, const float* dz, const float* x, int batch, int cout, int cin, int h, int w, int size, int cap,
                  const double* row_scale, float* dw, float* db, void* ws, size_t ws_bytes, hipStream_t s);
-// data gradient of a 1x1 convolution with the leaky-ReLU derivative of the stored activation in its epilogue (dgrad.hip)
-int launch_conv1x1_dgrad(const float* w, const float* dz, const float* y, float slope, int batch, int cout, int cin, int pixels,
-                         float* dx, hipStream_t s);
+// data gradient of a 1x1 or 3x3 / stride 1 / same-padding convolution with the leaky-ReLU derivative of the stored activation in its
+// epilogue and an optional double scale per filter folded into the weights (dgrad.hip).  One path under both entries:
+// rtod_conv1x1_dgrad is size = 1, h = 1, w = pixels, no row scale.  `who` names the entry in the error texts.
+int launch_conv_dgrad(const char* who, const float* w, const double* row_scale, const float* dz, const float* y, float slope, int batch, int cout,
+                      int cin, int h, int w_, int size, float* dx, hipStream_t s);
+// backward of the 2x upsample (bilinear align_corners=False, or nearest) in gather form, the producing conv's mask fused (upsample_grad.hip)
+int launch_upsample2x_grad(const float* dz, const float* y, float slope, int mode, int batch, int channels, int h, int w, float* dx, hipStream_t s);
 // optimiser step of one conv fused with the re-pack of its block of the weight image (head_step.hip): a 1x1 conv without BatchNorm
 // with its bias (Plan::step_conv), or a conv whose frozen BatchNorm scale is folded while it re-packs (b == NULL, scale given:
 // Plan::step_conv_folded).  The kernel's own argument: the scalars are what the host derived in double (Plan::opt_scalars), the

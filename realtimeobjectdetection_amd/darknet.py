@@ -387,10 +387,26 @@ class Darknet(nn.Module):
         lib.rtod_plan_head_blocks(self._plan, h, b, i, n)
         return list(zip(h, b, i))
 
+    def neck_layers(self) -> list:
+        """``[(neck_conv_layer, input_layer)]`` in ascending order (rtod_plan_neck_layers): the BatchNorm convs behind the backbone
+        that the plan can train with the exact gradient of the loss, BatchNorm frozen — every reader of a neck layer is a neck
+        layer or a [yolo] layer.  With options ``keep_neck_activations`` their inputs and outputs are valid ``read_layer`` targets
+        after a forward and ``conv_scale`` / ``update_conv_weight`` / ``step_conv_folded`` accept each of them.  Asks the plan, so
+        a forward (or ``prepare``) must have run."""
+        if self._plan is None:
+            raise RuntimeError("Darknet.neck_layers: no plan yet; run a forward first")
+        lib = _ffi.lib()
+        n = lib.rtod_plan_neck_layers(self._plan, None, None, 0)
+        if n < 0:
+            _ffi.check(n)
+        c, i = (C.c_int * max(n, 1))(), (C.c_int * max(n, 1))()
+        lib.rtod_plan_neck_layers(self._plan, c, i, n)
+        return list(zip(list(c)[:n], list(i)[:n]))
+
     def conv_scale(self, layer: int):
         """``(device address, host float64 array [Cout])`` of a block conv's frozen BatchNorm scale ``gamma / sqrt(var + 1e-5)`` as
         the plan folded it (rtod_plan_conv_scale); the address is what ``train.conv_wgrad_async(row_scale=...)`` takes and needs
-        options ``keep_block_inputs``."""
+        options ``keep_block_inputs`` (or ``keep_neck_activations``, under which any neck conv is accepted)."""
         if not self._plan_is_current():
             raise RuntimeError("Darknet.conv_scale: no loaded plan holds the current parameters; run a forward first")
         conv = self._trained_conv("conv_scale", layer, with_bn=True)

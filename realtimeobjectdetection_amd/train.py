@@ -4,8 +4,8 @@ The FORWARD VALUE of the loss: targets from ground-truth boxes (``target_creator
 (``darknet_loss``), the last step of ``feed_forward_through_model`` (train.py:412-425); and the first layer of its backward pass:
 the gradient with respect to the raw head maps and from it ``dW``, ``db`` of the detection-head convs (the 1x1 convs without
 BatchNorm in front of the [yolo] blocks), with a plain SGD step on them — fine-tuning the heads with the backbone frozen — and, with
-``trainable="blocks"``, one layer further: the weight gradient of the BatchNorm conv each head conv reads, BatchNorm frozen.  Backward
-through the rest of the trunk, BatchNorm gradients, weight decay, epochs and data loaders are out of scope.  The reference's
+``trainable="blocks"``, one layer further: the weight gradient of the BatchNorm conv each head conv reads, BatchNorm frozen, and with ``trainable="neck"`` every BatchNorm conv behind the backbone.  Backward
+through the backbone, BatchNorm gradients, weight decay, epochs and data loaders are out of scope.  The reference's
 optimiser — ``optim.Adam(lr=1e-2)``, train.py:57 — runs on the heads as one kernel per conv that also re-packs the conv's weights in
 place (``HeadOptimizer``, ``feed_forward_through_model``): that path never synchronises.  Same names and return conventions as the
 reference:
@@ -21,6 +21,9 @@ reference:
 * ``DarknetTrainer.optimizer`` (``HeadOptimizer``: Adam or SGD on the heads), ``sync_parameters()``    train.py:57
 * ``DarknetTrainer(model, trainable="blocks")``, ``block_gradients(frames_or_x, bndbox)``             (new) the step also trains the conv in front of
                                                                                             each head conv: ``(loss, head grads, {block_conv_layer: dW})``
+* ``DarknetTrainer(model, trainable="neck")``, ``neck_gradients(frames_or_x, bndbox)``                (new) ... and every BatchNorm conv behind the
+                                                                                            backbone (``Darknet.neck_layers``), through 3x3 convs, routes and the
+                                                                                            upsample: ``(loss, head grads, {neck_conv_layer: dW})``
 
 The reference's behaviour is kept as it is: only boxes whose class-0 slot is 1 and whose sides are at least
 ``min_box_size`` (24) count, ``anchor_fit`` compares a box with a square of the anchor's WIDTH, target slot 0 holds the y fraction
@@ -228,6 +231,57 @@ def conv1x1_dgrad_async(w, dz, y=None, slope=1.0):
     return dx
 
 
+def conv_dgrad_async(w, dz, size, row_scale=None, y=None, slope=1.0):
+    """Enqueue rtod_conv_dgrad: ``w`` [Cout,Cin,size,size] (raw float32 masters), ``dz`` [B,Cout,H,W] and, for a leaky producer, ``y``
+    [B,Cin,H,W] (the STORED output of the layer the conv reads) -> ``dx`` [B,Cin,H,W] = ``m(y) * conv_transpose(dz, v)`` of a ``size``
+    x ``size`` (1 or 3), stride-1, same-padding conv with ``v = float32(float64(w) * row_scale[o])`` (``row_scale``: None, a float64
+    device tensor [Cout] or the device address ``Darknet.conv_scale`` returns).  Contiguous float32 device tensors, Cin a multiple
+    of 32; one fmaf chain per tap, the tap sums added in ascending order: an order the shape fixes; nothing synchronises."""
+    for t in (w, dz) + ((y,) if y is not None else ()):
+        _need_cuda(t, "conv_dgrad")
+    size = int(size)
+    ok = dz.dim() == 4 and w.dim() in (2, 4) and w.size(0) == dz.size(1) and w.numel() == w.size(0) * w.size(1) * size * size and w.dtype == dz.dtype == torch.float32
+    if ok and y is not None:
+        ok = y.dtype == torch.float32 and tuple(y.shape) == (dz.size(0), w.size(1), dz.size(2), dz.size(3))
+    if not ok:
+        raise ValueError("conv_dgrad: expected float32 w [Cout,Cin,%d,%d], dz [B,Cout,H,W] and y [B,Cin,H,W], got %s, %s and %s"
+                         % (size, size, tuple(w.shape), tuple(dz.shape), None if y is None else tuple(y.shape)))
+    w, dz = w.contiguous(), dz.contiguous()
+    y = None if y is None else y.contiguous()
+    B, cout, cin, H, W = dz.size(0), dz.size(1), w.size(1), dz.size(2), dz.size(3)
+    dev = dz.device
+    dx = torch.empty((B, cin, H, W), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _ffi.check(_ffi.lib().rtod_conv_dgrad(C.c_void_p(w.data_ptr()), _scale_ptr(row_scale, cout, dev), C.c_void_p(dz.data_ptr()),
+                                              C.c_void_p(y.data_ptr()) if y is not None else None, float(slope), B, cout, cin, H, W, size,
+                                              C.c_void_p(dx.data_ptr()), _stream(dev)))
+    return dx
+
+
+def upsample2x_grad_async(dz, y=None, slope=1.0, mode="bilinear"):
+    """Enqueue rtod_upsample2x_grad: ``dz`` [B,C,2H,2W] -> ``dx`` [B,C,H,W], the backward of the 2x upsample (``mode`` "bilinear":
+    align_corners=False, or "nearest") in gather form without atomics, times ``m(y)`` for a leaky producer's stored output ``y``
+    [B,C,H,W].  Contiguous float32 device tensors; nothing synchronises."""
+    for t in (dz,) + ((y,) if y is not None else ()):
+        _need_cuda(t, "upsample2x_grad")
+    if mode not in ("bilinear", "nearest"):
+        raise ValueError("upsample2x_grad: mode must be 'bilinear' or 'nearest', got %r" % (mode,))
+    ok = dz.dim() == 4 and dz.dtype == torch.float32 and dz.size(2) % 2 == 0 and dz.size(3) % 2 == 0
+    if ok and y is not None:
+        ok = y.dtype == torch.float32 and tuple(y.shape) == (dz.size(0), dz.size(1), dz.size(2) // 2, dz.size(3) // 2)
+    if not ok:
+        raise ValueError("upsample2x_grad: expected float32 dz [B,C,2H,2W] and y [B,C,H,W], got %s and %s" % (tuple(dz.shape), None if y is None else tuple(y.shape)))
+    dz = dz.contiguous()
+    y = None if y is None else y.contiguous()
+    B, ch, H, W = dz.size(0), dz.size(1), dz.size(2) // 2, dz.size(3) // 2
+    dev = dz.device
+    dx = torch.empty((B, ch, H, W), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _ffi.check(_ffi.lib().rtod_upsample2x_grad(C.c_void_p(dz.data_ptr()), C.c_void_p(y.data_ptr()) if y is not None else None, float(slope),
+                                                   1 if mode == "nearest" else 0, B, ch, H, W, C.c_void_p(dx.data_ptr()), _stream(dev)))
+    return dx
+
+
 def model_heads(model, height=None, width=None):
     """``[(grid_h, grid_w, stride, anchors)]`` of a Darknet's [yolo] layers in cfg order, and its number of classes."""
     h = int(model.net_info["height"]) if height is None else int(height)
@@ -318,9 +372,10 @@ class DarknetTrainer:
     last loss: total, xy, wh, obj, noobj, cls)."""
 
     def __init__(self, model, resolution=None, num_classes=None, trainable="heads"):
-        if trainable not in ("heads", "blocks"):
-            raise ValueError("DarknetTrainer: trainable must be 'heads' or 'blocks', got %r" % (trainable,))
-        self.trainable = trainable         # "blocks": feed_forward_through_model also trains the BatchNorm conv in front of each head conv
+        if trainable not in ("heads", "blocks", "neck"):
+            raise ValueError("DarknetTrainer: trainable must be 'heads', 'blocks' or 'neck', got %r" % (trainable,))
+        self.trainable = trainable         # "blocks": feed_forward_through_model also trains the BatchNorm conv in front of each head conv;
+                                           # "neck": every BatchNorm conv behind the backbone (Darknet.neck_layers)
         self.darknet = model
         if resolution is not None:
             assert isinstance(resolution, int) and resolution % 32 == 0
@@ -338,6 +393,7 @@ class DarknetTrainer:
         self.last_components = None
         self._head_masters = None          # head_step / optimizer: {conv_layer: [weight, bias]} float32 device masters of the head convs
         self._block_cache = None           # block_gradients: (plan and weight version, the plan's blocks with their scales)
+        self._neck_cache = None            # neck_gradients: (plan and weight version, the neck graph with its scales)
         self.optimizer = HeadOptimizer()
 
     @property
@@ -552,6 +608,113 @@ class DarknetTrainer:
             self._block_cache = (key, found)
         return self._block_cache[1]
 
+    # ------------------------------------------------------------------ gradients of the whole detection neck
+    def neck_gradients(self, frames_or_x, bndbox):
+        """``(loss, {head_conv_layer: (dW, db)}, {neck_conv_layer: dW [Cout,Cin,k,k]})``: what ``loss.backward()`` of the reference
+        under ``.eval()`` leaves on the head convs and on ``conv.weight`` of every neck conv (``Darknet.neck_layers``: the BatchNorm
+        convs behind the backbone; BatchNorm frozen).  ``head_gradients``, then a walk through the neck graph in descending layer
+        order that keeps the gradient with respect to each layer's OUTPUT:
+
+        * a conv with ``dz`` (its output gradient times the mask of its own activation): ``dW`` by rtod_conv_wgrad over
+          ``read_layer`` of its input with the plan's frozen scale, and, where its input is a neck layer, rtod_conv_dgrad from the
+          float32 masters and that scale; the conv at the boundary of the graph gets a ``dW`` and sends nothing further;
+        * a route hands each source its channel range; an upsample calls rtod_upsample2x_grad;
+        * a producer with ONE reader has its mask fused into that reader's call; one with several readers (or a route as its
+          reader) gets the plain contributions, added in ascending reader order with float32 adds, then one multiplication by
+          the mask.  Either way an element is chain(s), adds in a fixed order, one multiplication: bit-identical from call to call.
+
+        All on the current stream, nothing synchronises.  The model's ``options`` must hold ``keep_head_inputs`` and
+        ``keep_neck_activations``."""
+        model = self.darknet
+        opts = getattr(model, "options", {})
+        if not (int(opts.get("keep_head_inputs", 0)) and int(opts.get("keep_neck_activations", 0))):
+            raise RuntimeError("DarknetTrainer.neck_gradients: set model.options['keep_head_inputs'] = 1 and model.options['keep_neck_activations'] = 1 "
+                               "before the first forward; without them the activations of the neck do not survive the forward")
+        loss, head_grads, operands = self._head_pass(frames_or_x, bndbox)
+        layers, readers, member, scales = self._neck()
+        masters = self._masters(list(head_grads) + sorted(scales), loss.device)
+        B = next(iter(operands.values()))[0].size(0)
+        stored = {}
+
+        def read(layer):                                              # dense copies, one per layer and walk
+            if layer not in stored:
+                stored[layer] = model.read_layer(layer, B)
+            return stored[layer]
+
+        parts = {}                                                    # producer -> [(reader, contribution)], or the finished gradient
+
+        def send(producer, reader, contribution, fusable):
+            """``contribution(y, slope)`` of ``reader`` to the output gradient of ``producer``."""
+            if not member[producer]:
+                return
+            P = layers[producer]
+            leaky = P.type == "convolutional" and P.leaky
+            if fusable and leaky and len(readers[producer]) == 1:
+                parts[producer] = contribution(read(producer), 0.1)
+            else:
+                parts.setdefault(producer, []).append((reader, contribution(None, 1.0)))
+
+        def gradient(layer):
+            """The gradient with respect to the layer's output; for a conv, times the mask of its activation."""
+            got = parts.pop(layer)
+            if not isinstance(got, list):
+                return got
+            got.sort(key=lambda rc: rc[0])
+            total = got[0][1]
+            for _, c in got[1:]:
+                total = total + c
+            L = layers[layer]
+            if L.type == "convolutional" and L.leaky:
+                y = read(layer)
+                total = total * torch.full_like(y, 0.1).masked_fill_(y > 0, 1.0)
+            return total
+
+        neck_grads = {}
+        for i in range(len(layers) - 1, -1, -1):
+            if not member[i]:
+                continue
+            L = layers[i]
+            if L.type == "convolutional":
+                head = i in operands
+                dz = operands[i][0] if head else gradient(i)
+                scale = None if head else scales[i]
+                if not head:
+                    neck_grads[i] = conv_wgrad_async(dz, read(i - 1), L.size, row_scale=scale)[0]
+                if i > 0:
+                    send(i - 1, i, lambda y, slope, dz=dz, scale=scale, L=L: conv_dgrad_async(masters[i][0], dz, L.size, scale, y, slope), True)
+            elif L.type == "upsample":
+                g = gradient(i)
+                send(i - 1, i, lambda y, slope, g=g, L=L: upsample2x_grad_async(g, y, slope, "nearest" if L.nearest else "bilinear"), True)
+            else:                                                     # route: every source takes its channel range
+                g, off = gradient(i), 0
+                for s in L.srcs:
+                    send(s, i, lambda y, slope, g=g, off=off, s=s: g.narrow(1, off, layers[s].cout).contiguous(), False)
+                    off += layers[s].cout
+        return loss, head_grads, {layer: neck_grads[layer] for layer in sorted(neck_grads)}
+
+    def _neck(self):
+        """``(IR layers, readers per layer, membership per layer, {neck conv: device address of its frozen scale})`` of the neck graph,
+        asked of the plan once per plan and weight load.  The plan decides which convs belong (``Darknet.neck_layers``); routes and
+        upsamples follow by the same closure rule: every reader is a member or a [yolo] layer."""
+        model = self.darknet
+        key = (model._plan.value, model._plan_weights_version)
+        if self._neck_cache is None or self._neck_cache[0] != key:
+            h = int(model.net_info["height"])
+            w = int(model.input_width) if getattr(model, "input_width", None) is not None else h
+            layers = build_ir(model.blocks, h, w).layers
+            readers = [[] for _ in layers]
+            for L in layers:
+                for s in (L.srcs if L.type in ("route", "shortcut") else ((L.index - 1,) if L.index > 0 else ())):
+                    readers[s].append(L.index)
+            convs = {c for c, _ in model.neck_layers()} | {c for c, _ in model.head_layers()}
+            member = [False] * len(layers)
+            for L in reversed(layers):
+                ok = L.index in convs if L.type == "convolutional" else L.type in ("route", "upsample") and bool(readers[L.index])
+                member[L.index] = ok and all(layers[r].type == "yolo" or member[r] for r in readers[L.index])
+            scales = {c: model.conv_scale(c)[0] for c, _ in model.neck_layers()}
+            self._neck_cache = (key, (layers, readers, member, scales))
+        return self._neck_cache[1]
+
     # ------------------------------------------------------------------ the reference's training step, on the heads
     def feed_forward_through_model(self, batch_data, bndbox):
         """The reference's training step (train.py:412-425) with the backbone frozen: forward under ``train_mode()``, loss, the
@@ -560,10 +723,10 @@ class DarknetTrainer:
         synchronises; the next forward on that stream runs the new weights.  Returns the loss from before the step as a 0-dim
         float32 device tensor.  The module's ``conv.weight`` / ``conv.bias`` lag behind until ``sync_parameters()`` (or anything
         that reads the model's parameters as a whole: ``weight_stream()``, ``state_dict()``, a re-pack)."""
-        if self.trainable == "blocks":
-            # every gradient kernel of the batch is enqueued before the first step, as autograd has it: step_conv updates the head
-            # masters in place, and the data gradient through a head reads them
-            loss, grads, block_grads = self.block_gradients(batch_data, bndbox)
+        if self.trainable in ("blocks", "neck"):
+            # every gradient kernel of the batch is enqueued before the first step, as autograd has it: the steps update the
+            # masters in place, and the data gradients through the heads and the neck convs read them
+            loss, grads, block_grads = (self.block_gradients if self.trainable == "blocks" else self.neck_gradients)(batch_data, bndbox)
             grads = dict(grads)
             grads.update({layer: (dw, None) for layer, dw in block_grads.items()})
         else:

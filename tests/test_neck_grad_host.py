@@ -1,0 +1,207 @@
+"""Host tests of the neck training path (every BatchNorm conv behind the backbone, BatchNorm frozen): rtod_plan_neck_layers on the
+shipped and the test cfgs, the liveness that option keep_neck_activations adds and nothing else, the refusals of the folded-conv
+entries with and without the option, the argument checks of rtod_conv_dgrad / rtod_upsample2x_grad and the trainer's errors — all
+decided on the host.  The device is covered by tests/test_neck_grad_gpu.py."""
+import ctypes as C
+import types
+
+import numpy as np
+import pytest
+
+from block_grad_cases import head_blocks
+from head_grad_cases import describe, head_layers, pack, plan
+from neck_grad_cases import NECK, neck_layers
+from realtimeobjectdetection_amd import _ffi, cfgs, synth
+from realtimeobjectdetection_amd.cfg import build_ir, parse_cfg_text
+from realtimeobjectdetection_amd.train import DarknetTrainer
+
+F = np.float32
+ONE = C.c_void_p(64)                                                  # never dereferenced: every refusal is decided on the host
+NETS = {"yolov3": (cfgs.yolov3_cfg, 416), "tiny": (cfgs.yolov3_tiny_cfg, 416), "mini": (cfgs.mini_cfg, 64), "fallback": (cfgs.mini_fallback_cfg, 64),
+        "v5": (cfgs.v5_style_mini_cfg, 128)}
+
+
+def _text(net):
+    gen, res = NETS[net]
+    return gen(res, res), res
+
+
+# ---------------------------------------------------------------------------------------------- 1. rtod_plan_neck_layers
+def test_neck_layers_of_the_shipped_and_the_test_cfgs():
+    """The full sets at every precision: no neck conv of these cfgs is narrow, a stem or a member of a fused-pointwise candidate pair
+    (their hosts have at most 64 filters, every neck conv here has at least 128), and a K-sliced conv packs by the generic formula,
+    so the plan's part of the definition removes none at f16s3 / f16 / k_slices_split either."""
+    lib = _ffi.lib()
+    for net, precision, options in (("yolov3", 0, ()), ("yolov3", 1, ()), ("yolov3", 2, ()), ("yolov3", 1, (("k_slices_split", 1),)),
+                                    ("tiny", 0, ()), ("tiny", 1, (("narrow_cin", 1),)), ("tiny", 2, (("narrow_cin", 1),)),
+                                    ("mini", 0, ()), ("mini", 1, ()), ("mini", 2, ()), ("mini", 1, (("k_slices_split", 1),)),
+                                    ("fallback", 0, ()), ("v5", 0, ()),
+                                    ("mini", 0, (("keep_neck_activations", 1),)), ("tiny", 0, (("keep_head_inputs", 1), ("keep_neck_activations", 1)))):
+        text, res = _text(net)
+        h = plan(text, res, 4, precision, options)
+        got = neck_layers(h)
+        assert [c for c, _ in got] == NECK[net] and all(i == c - 1 for c, i in got), (net, precision, options, got)
+        d = describe(h)
+        for c, _ in got:
+            L = d["layers"][c]
+            assert L["type"] == "convolutional" and L["bn"] and L["size"] in (1, 3) and L["stride"] == 1 and L["cin"] % 32 == 0
+        blocks = [b for _, b, _ in head_blocks(h) if b >= 0]
+        assert set(blocks) <= set(NECK[net]) and (len(blocks) > 0) == (len(got) > 0)        # every block is a neck conv
+        if got:                                                       # the count; capacity entries written; bad arguments
+            one = [(C.c_int * 1)() for _ in range(2)]
+            assert lib.rtod_plan_neck_layers(h, *one, 1) == len(got) and (one[0][0], one[1][0]) == got[0]
+        assert lib.rtod_plan_neck_layers(h, None, None, 1) == -1 and lib.rtod_plan_neck_layers(None, None, None, 0) == -1
+        assert lib.rtod_plan_neck_layers(h, None, None, 0) == len(got)
+        lib.rtod_plan_destroy(h)
+    for options in ((("bn_batch_stats", 1),), (("bn_batch_stats", 1), ("bn_batch_split", 1))):   # the convs are not folded there
+        h = plan(cfgs.mini_cfg(64, 64), 64, 4, len(options) - 1, options)
+        assert neck_layers(h) == []
+        lib.rtod_plan_destroy(h)
+    d = describe(plan(*_text("tiny")))
+    assert d["layers"][9]["type"] == "maxpool" and d["layers"][8]["bn"] and d["layers"][8]["stride"] == 1      # why layer 8 is out
+
+
+# ---------------------------------------------------------------------------------------------- 2. keep_neck_activations: liveness only
+def _resolve(layers, i):
+    while layers[i]["alias_of"] >= 0:
+        i = layers[i]["alias_of"]
+    return i
+
+
+@pytest.mark.parametrize("net,precision", [("yolov3", 0), ("yolov3", 1), ("yolov3", 2), ("tiny", 0), ("tiny", 1), ("tiny", 2), ("mini", 0), ("mini", 1), ("mini", 2),
+                                           ("fallback", 0)])
+def test_keep_neck_activations_keeps_the_neck_alive_and_nothing_else(net, precision):
+    text, res = _text(net)
+    B = 4
+    base = [("narrow_cin", 1)] if net == "tiny" and precision else []
+    off, on = plan(text, res, B, precision, base), plan(text, res, B, precision, base + [("keep_neck_activations", 1)])
+    d0, d1 = describe(off), describe(on)
+    n_layers = len(d1["layers"])
+    assert neck_layers(off) == neck_layers(on) and [c for c, _ in neck_layers(on)] == NECK[net]
+    L1 = d1["layers"]
+    # every buffer a neck conv or a head conv reads or writes (a head conv with a fused decode writes the final tensor: no buffer;
+    # the fallback cfg has no neck conv, and its first head conv stores its map for a stand-alone decode)
+    heads = [c for c, _ in head_layers(on)]
+    kept = set()
+    for c in NECK[net] + heads:
+        kept.add(L1[_resolve(L1, c - 1)]["buf"])
+        if L1[c]["fused_into"] < 0:
+            kept.add(L1[_resolve(L1, c)]["buf"])
+    assert -1 not in kept and len(kept) >= len(NECK[net])
+    if net == "tiny":                                                  # conv 21 reads route(-1, 8): its concat buffer is what stays
+        assert d1["bufs"][L1[20]["buf"]]["C"] == 384 and L1[20]["buf"] in kept
+    size = lambda b: (b["floats_per_frame"] * B + 63) // 64 * 64
+    for i, a in enumerate(d1["bufs"]):
+        if i in kept:
+            assert a["last"] >= n_layers - 1                          # live to the end of the forward
+        for j, b in enumerate(d1["bufs"]):
+            if j <= i:
+                continue
+            live = not (a["last"] < b["first"] or b["last"] < a["first"])
+            mem = not (a["offset"] + size(a) <= b["offset"] or b["offset"] + size(b) <= a["offset"])
+            assert not (live and mem), (a, b)
+            if mem and (i in kept) != (j in kept):                    # whatever shares a kept buffer's space is dead before it is written
+                hb, ob = (a, b) if i in kept else (b, a)
+                assert ob["last"] < hb["first"], (hb, ob)
+    # everything but liveness and arena placement is the plan without the option
+    assert d0["layers"] == d1["layers"] and d0["n_launches"] == d1["n_launches"] and d1["arena_floats"] >= d0["arena_floats"]
+    assert [(b["C"], b["H"], b["W"], b["first"]) for b in d0["bufs"]] == [(b["C"], b["H"], b["W"], b["first"]) for b in d1["bufs"]]
+    assert [b["last"] for i, b in enumerate(d0["bufs"]) if i not in kept] == [b["last"] for i, b in enumerate(d1["bufs"]) if i not in kept]
+    if net == "fallback":
+        assert L1[12]["fused_into"] < 0 and L1[12]["buf"] in kept
+    lib = _ffi.lib()
+    li0, li1 = _ffi.LaunchInfo(), _ffi.LaunchInfo()
+    for k in range(d0["n_launches"]):
+        assert lib.rtod_plan_get_launch(off, k, C.byref(li0)) == 0 and lib.rtod_plan_get_launch(on, k, C.byref(li1)) == 0
+        assert bytes(li0) == bytes(li1), k
+    w = synth.synth_weights(build_ir(parse_cfg_text(text), res))
+    assert np.array_equal(pack(off, w), pack(on, w))
+    # the describe text of a plan without the option does not know the option exists: setting it and taking it back gives the same bytes
+    back = plan(text, res, B, precision, base + [("keep_neck_activations", 1), ("keep_neck_activations", 0)])
+    assert describe(back) == d0
+    for h in (off, on, back):
+        lib.rtod_plan_destroy(h)
+
+
+# ---------------------------------------------------------------------------------------------- 3. refusals, decided on the host
+def SGD(lr=1e-3):
+    return _ffi.OptStep(0, lr, 0, 0, 0, 0)
+
+
+def _step(h, layer, opt=None, w=ONE, dw=ONE, moments=(ONE, ONE)):
+    return _ffi.lib().rtod_plan_step_conv_folded(h, layer, C.byref(opt) if opt is not None else None, w, dw, *moments, None)
+
+
+def test_folded_entries_accept_a_neck_conv_with_the_option_only():
+    lib = _ffi.lib()
+    err = _ffi.last_error
+    upd = lambda h, layer, w=ONE: lib.rtod_plan_update_conv_weight(h, layer, w)
+    scale = lambda h, layer, ch: lib.rtod_plan_conv_scale(h, layer, None, None, ch)
+    text = cfgs.mini_cfg(64, 64)
+    for precision in (0, 1):
+        on, off = plan(text, 64, 4, precision, [("keep_neck_activations", 1)]), plan(text, 64, 4, precision)
+        # with the option layer 12 is accepted: the calls get as far as the state check
+        assert scale(on, 12, 512) == -4 and "load_weights" in err()
+        assert _step(on, 12, SGD(), moments=(None, None)) == -4 and "load_weights" in err() and upd(on, 12) == -4 and "load_weights" in err()
+        assert scale(on, 12, 511) == -1 and "channels" in err()
+        for layer in (13, 17, 20, 21):
+            assert _step(on, layer, SGD(), moments=(None, None)) == -4, layer
+        # without it, as before
+        for call in (lambda layer: _step(off, layer, SGD()), lambda layer: upd(off, layer), lambda layer: scale(off, layer, 512)):
+            assert call(12) == -1 and "not a detection block" in err()
+        assert _step(off, 13, SGD(), moments=(None, None)) == -4 and upd(off, 13) == -4 and scale(off, 13, 1024) == -4
+        # what is no neck conv is refused with the reason
+        for call in (lambda layer: _step(on, layer, SGD()), lambda layer: upd(on, layer), lambda layer: scale(on, layer, 1)):
+            assert call(10) == -1 and "not a neck conv" in err() and "stride-1" in err()       # stride 2
+            assert call(11) == -1 and "not a neck conv" in err()
+            assert call(14) == -1 and "no BatchNorm" in err()                                   # a head conv
+            assert call(16) == -1 and "not a convolution" in err()                              # a route
+            assert call(18) == -1 and "not a convolution" in err()                              # the upsample
+            assert call(0) == -1 and "stem" in err()
+            assert call(-1) == -1 and call(1000) == -1
+        lib.rtod_plan_destroy(on)
+        lib.rtod_plan_destroy(off)
+    # a shape-ok conv whose output a layer outside the neck reads: yolov3-tiny's layer 8 (max-pool 9)
+    h = plan(cfgs.yolov3_tiny_cfg(416, 416), 416, 4, 0, [("keep_neck_activations", 1)])
+    assert _step(h, 8, SGD()) == -1 and "outside the neck" in err()
+    lib.rtod_plan_destroy(h)
+    h = plan(text, 64, 4, 0, [("bn_batch_stats", 1), ("keep_neck_activations", 1)])
+    assert _step(h, 12, SGD()) == -1 and "batch-statistics" in err()
+    lib.rtod_plan_destroy(h)
+
+
+def test_conv_dgrad_argument_checks():
+    lib = _ffi.lib()
+    call = lambda w=ONE, s=None, dz=ONE, y=ONE, slope=0.1, shape=(1, 1, 32, 1, 1, 3), dx=ONE: lib.rtod_conv_dgrad(w, s, dz, y, slope, *shape, dx, None)
+    for kw in (dict(w=None), dict(dz=None), dict(dx=None), dict(slope=float("nan")), dict(shape=(0, 1, 32, 1, 1, 3)), dict(shape=(1, 0, 32, 1, 1, 3)),
+               dict(shape=(1, 1, 0, 1, 1, 3)), dict(shape=(1, 1, 48, 1, 1, 3)), dict(shape=(1, 1, 16, 1, 1, 1)), dict(shape=(1, 1, 32, 0, 1, 3)),
+               dict(shape=(1, 1, 32, 1, 0, 3)), dict(shape=(1, 1, 32, 1, 1, 2)), dict(shape=(1, 1, 32, 1, 1, 5)), dict(shape=(1, 1, 32, 1, 1, 0)),
+               dict(shape=(1 << 8, 1, 32, 1 << 12, 1 << 12, 3)), dict(shape=(1, 1, 32, 1 << 16, 1 << 16, 1)), dict(shape=(1, 1 << 14, 1 << 14, 1, 1, 3)),
+               dict(shape=(1, 1 << 16, 1 << 15, 1, 1, 1))):
+        assert call(**kw) == -1, kw
+        assert "conv_dgrad" in _ffi.last_error(), kw
+    # the 1x1 entry keeps its own name in its refusals
+    assert lib.rtod_conv1x1_dgrad(ONE, ONE, ONE, 0.1, 1, 1, 48, 1, ONE, None) == -1 and "conv1x1_dgrad" in _ffi.last_error()
+
+
+def test_upsample2x_grad_argument_checks():
+    lib = _ffi.lib()
+    call = lambda dz=ONE, y=ONE, slope=0.1, mode=0, shape=(1, 1, 1, 1), dx=ONE: lib.rtod_upsample2x_grad(dz, y, slope, mode, *shape, dx, None)
+    for kw in (dict(dz=None), dict(dx=None), dict(slope=float("nan")), dict(mode=2), dict(mode=-1), dict(shape=(0, 1, 1, 1)), dict(shape=(1, 0, 1, 1)),
+               dict(shape=(1, 1, 0, 1)), dict(shape=(1, 1, 1, 0)), dict(shape=(1, 1, 1 << 15, 1 << 15)), dict(shape=(1, 1, 1 << 30, 1))):
+        assert call(**kw) == -1, kw
+        assert "upsample2x_grad" in _ffi.last_error(), kw
+
+
+def test_trainer_asks_for_the_neck_options():
+    stub = lambda opts: types.SimpleNamespace(blocks=parse_cfg_text(cfgs.mini_cfg(64, 64)), net_info={"height": 64}, input_width=None, options=opts)
+    with pytest.raises(ValueError, match="trainable"):
+        DarknetTrainer(stub({}), trainable="trunk")
+    assert DarknetTrainer(stub({}), trainable="neck").trainable == "neck"
+    for opts, missing in (({}, "keep_neck_activations"), ({"keep_head_inputs": 1}, "keep_neck_activations"), ({"keep_neck_activations": 1}, "keep_head_inputs"),
+                          ({"keep_head_inputs": 1, "keep_block_inputs": 1}, "keep_neck_activations")):
+        t = DarknetTrainer(stub(opts), trainable="neck")
+        with pytest.raises(RuntimeError, match=missing):
+            t.neck_gradients(np.zeros((1, 3, 64, 64), F), [None])
+        with pytest.raises(RuntimeError, match=missing):
+            t.feed_forward_through_model(np.zeros((1, 3, 64, 64), F), [None])
