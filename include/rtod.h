@@ -200,6 +200,13 @@ int rtod_plan_set_precision(rtod_plan* plan, int mode);
  *                       rtod_upsample2x_grad, rtod_conv_wgrad).  Requires no other option.  Liveness only as well; rtod_plan_load_weights
  *                       then keeps the frozen BatchNorm scales of ALL neck convs on the device, and rtod_plan_conv_scale,
  *                       rtod_plan_update_conv_weight and rtod_plan_step_conv_folded accept any neck conv (without it: blocks alone)
+ *   "keep_backbone_activations" (default 0) a superset of "keep_neck_activations" over the TRAINABLE convs (rtod_plan_trainable_layers):
+ *                       every buffer one of them or a detection-head conv reads or writes stays live to the end of the forward, the
+ *                       frozen scales of all of them go to the device, and the three folded-conv entries accept every one of them, the
+ *                       stride-2 convs included.  Not liveness only: while it is set the plan forms no fusion that would leave a
+ *                       trainable conv's own output unstored or its packed layout out of reach — no shortcut in a conv's epilogue,
+ *                       no fused pointwise pair, no fused stem + layer 1 kernel — so the forward is, bit for bit and tile for tile,
+ *                       that of a plan with "fuse_shortcut" = 0, "fuse_pointwise" = 0, "stem2_kernel" = 0.  Default plans do not change
  *   "force_f16s3_variant" / "force_f32_variant"   >= 0: one tile variant for every conv (tests, A/B runs)
  * Options that leave a cfg inexpressible in the split-f16 format return RTOD_E_CFG when precision is 1 or 2 (so does setting
  * "narrow_cin" back to 0 on a plan that needs it); the plan then stays as it was. */
@@ -249,6 +256,17 @@ int rtod_plan_head_blocks(const rtod_plan* plan, int* head_conv_layers, int* blo
  * "keep_neck_activations").  YOLOv3: 75-80, 84, 87-92, 96, 99-104; YOLOv3-tiny: 12, 13, 14, 18, 21 (layer 8 is read by a max-pool).
  * The listing does not depend on the option.  Returns the number of neck convs, capacity as rtod_plan_head_layers. */
 int rtod_plan_neck_layers(const rtod_plan* plan, int* conv_layers, int* input_layers, int capacity);
+/* (new) The TRAINABLE convs of a plan: the BatchNorm convs, in ascending order, of the set rtod_plan_neck_layers defines with two more
+ * traversable kinds:
+ *   a conv that is a block except that it is 3x3 / stride 2 / pad 1 (leaky or linear, Cin a multiple of 32, generic packed layout, its
+ *   own output stored);
+ *   a two-source [shortcut] with linear activation.
+ * Layer 0 (three input channels, stem layouts), max-pools, SiLU convs and plans with "bn_batch_stats" are not traversable.  The plan's
+ * fusions decide membership: on a default plan a conv whose shortcut runs in its epilogue, a pointwise pair and the fused stem are not
+ * members, and the closure rule then drops what they read; with option "keep_backbone_activations" none of these is formed.  With
+ * it: YOLOv3 every BatchNorm conv except layer 0 (71); YOLOv3-tiny the neck (12, 13, 14, 18, 21: its backbone is max-pools).
+ * conv_layers / input_layers / capacity and the return value as rtod_plan_neck_layers. */
+int rtod_plan_trainable_layers(const rtod_plan* plan, int* conv_layers, int* input_layers, int capacity);
 /* (new) The frozen BatchNorm scale of a block conv, s[o] = (double)gamma[o] / sqrt((double)var[o] + 1e-5), exactly the factor
  * rtod_plan_load_weights folded into the conv, taken from the stream last loaded.  scale_host (may be NULL): `channels` doubles
  * are copied out.  scale_dev (may be NULL): receives a device pointer to the same doubles, owned by the plan and valid until
@@ -509,6 +527,25 @@ int rtod_conv1x1_dgrad(const float* w_dev, const float* dz_dev, const float* y_d
  * for pixels, and size not 1 or 3, cout * cin * size * size >= 2^31. */
 int rtod_conv_dgrad(const float* w_oihw_dev, const double* row_scale_dev, const float* dz_dev, const float* y_dev, float slope,
                     int batch, int cout, int cin, int height, int width, int size, float* dx_dev, void* stream);
+/* (new) Data gradient through a 3x3, stride 2, pad 1 convolution over dense NCHW maps.  height x width is the conv's INPUT map;
+ * ho = (height - 1) / 2 + 1, wo likewise; dz_dev [batch,cout,ho,wo], dx_dev and y_dev [batch,cin,height,width]:
+ *   dx[b,c,iy,ix] = m(y[b,c,iy,ix]) * sum over taps (ky,kx) with (iy+1-ky) and (ix+1-kx) even, oy = (iy+1-ky)/2 in [0,ho),
+ *                   ox = (ix+1-kx)/2 in [0,wo), of  chain_o v[o,c,ky,kx] * dz[b,o,oy,ox]
+ * v, m, y_dev, slope and row_scale_dev exactly as rtod_conv_dgrad.  An even row takes ky = 1, an odd row ky = 0 and 2, columns
+ * likewise: 1, 2, 2 or 4 taps by the pixel's parity class.  One fmaf chain per tap over o in ascending pairs, cout padded to 32 with
+ * zeros; the class's taps are added in ascending tap order, total = total + chain, one fp32 add each; a tap of the class whose dz
+ * pixel lies outside the map adds an exact 0; then one multiplication by the mask.  The GEMM columns are ordered by (class, b, iy / 2,
+ * ix / 2) and each class is rounded up to whole 64-column tiles, so a workgroup runs its class's taps alone.  No workspace, plain
+ * stores, no atomics: bit-identical from call to call.  Enqueues only.  Any height, width >= 1.  RTOD_E_ARG: as rtod_conv_dgrad, and
+ * size not 3. */
+int rtod_conv_dgrad_s2(const float* w_oihw_dev, const double* row_scale_dev, const float* dz_dev, const float* y_dev, float slope,
+                       int batch, int cout, int cin, int height, int width, int size, float* dx_dev, void* stream);
+/* (new) The fan-out point of the gradient walk in one launch: out[i] = m(y[i]) * (((c0[i] + c1[i]) + c2[i]) + c3[i]) over n floats,
+ * `count` (1 to 4) contributions in contributions_dev_ptrs (a HOST array of device pointers), added left to right with one fp32 add
+ * each, then one multiplication by slope where !(y > 0) (y_dev NULL or slope == 1: no mask; count 1 is the mask alone).  16-byte
+ * loads where every pointer is 16-byte aligned, a scalar tail.  Bit-identical from call to call.  Enqueues only.  RTOD_E_ARG: a null
+ * pointer, count outside 1..4, n < 1, slope NaN. */
+int rtod_grad_join(const float* const* contributions_dev_ptrs, int count, const float* y_dev, float slope, long long n, float* out_dev, void* stream);
 /* (new) Backward of the 2x [upsample]: dz_dev [batch,channels,2*height,2*width] -> dx_dev [batch,channels,height,width].
  * mode 0: bilinear, align_corners=False (the plan's forward, the reference's nn.Upsample): input row i is read by output rows
  * 2i-1 .. 2i+2 with weights 0.25, 0.75, 0.75, 0.25, the edge clamp of the forward putting both weights of a border row on the edge
@@ -540,6 +577,14 @@ int rtod_upsample2x_grad(const float* dz_dev, const float* y_dev, float slope, i
 int rtod_conv_wgrad_workspace(int batch, int cout, int cin, int height, int width, int size, size_t* bytes);
 int rtod_conv_wgrad(const float* dz_dev, const float* x_dev, int batch, int cout, int cin, int height, int width, int size,
                     const double* row_scale_dev, float* dw_dev, float* db_dev, void* workspace, size_t workspace_bytes, void* stream);
+/* (new) Weight gradient of a 3x3, stride 2, pad 1 convolution.  height x width is the conv's INPUT map (x_dev [batch,cin,height,width]);
+ * dz_dev [batch,cout,ho,wo] with ho = (height - 1) / 2 + 1, wo likewise:
+ *   dw_dev[o][c][ky][kx] = sum_{b,oy,ox} dz[b,o,oy,ox] * x[b,c,2*oy+ky-1,2*ox+kx-1]      (a tap outside the map adds an exact 0)
+ * db_dev, row_scale_dev, the two kernels, the slice rule and the workspace formula are those of rtod_conv_wgrad with K = batch * ho *
+ * wo (the slice kernel is the same template with the stride as a parameter).  RTOD_E_ARG: as rtod_conv_wgrad, and size not 3. */
+int rtod_conv_wgrad_s2_workspace(int batch, int cout, int cin, int height, int width, int size, size_t* bytes);
+int rtod_conv_wgrad_s2(const float* dz_dev, const float* x_dev, int batch, int cout, int cin, int height, int width, int size,
+                       const double* row_scale_dev, float* dw_dev, float* db_dev, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- optimiser step of a detection-head conv, on the stream ------------------------------------------
  * replaces optim.Adam(self.darknet.parameters(), lr=1e-2) + optimizer.step()     train.py:57, 412-425

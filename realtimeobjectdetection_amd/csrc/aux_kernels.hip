@@ -166,8 +166,49 @@ __global__ void add_kernel(View a, View b, View out, int B) {
     }
 }
 
-int launch_add(const View& a, const View& b, const View& out, int B, hipStream_t s) {
-    if (a.split || b.split || out.split) { set_error("add: split-format views unsupported (shortcut must fuse into a conv)"); return RTOD_E_ARG; }
+// split-format variant (plans with option keep_backbone_activations, which hold the shortcut out of the conv's epilogue): 8 channels
+// (16 B of each plane) per thread.  Both operands are read as hi + lo (exact in fp32), added with one fp32 add in the format's own
+// domain (8 x) and split again: the sum rounds once, at its store, and saturates and reports like every other split producer.
+// F16 (plain-f16 plans): the hi planes alone, the sum rounded to f16 (RNE).
+template <bool F16>
+__global__ void add_split_kernel(View a, View b, View out, int B, int32_t* ovf) {
+    const int C8 = a.C / 8;
+    const int64_t total = (int64_t)B * a.H * a.W * C8;
+    const _Float16* ab = reinterpret_cast<const _Float16*>(a.base);
+    const _Float16* bb = reinterpret_cast<const _Float16*>(b.base);
+    _Float16* ob = reinterpret_cast<_Float16*>(out.base);
+    float amax = 0.f;
+    for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
+        const int c = (int)(t % C8) * 8;
+        const int64_t p = t / C8;
+        const _Float16* qa = ab + p * 2 * a.ldc + a.coff + c;
+        const _Float16* qb = bb + p * 2 * b.ldc + b.coff + c;
+        const f16x8a ah = *reinterpret_cast<const f16x8a*>(qa), bh = *reinterpret_cast<const f16x8a*>(qb);
+        f16x8a al = ah, bl = bh;
+        if constexpr (!F16) { al = *reinterpret_cast<const f16x8a*>(qa + a.ldc); bl = *reinterpret_cast<const f16x8a*>(qb + b.ldc); }
+        f16x8a rh, rl;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            if constexpr (F16) { rh[e] = f16_sat((float)ah[e] + (float)bh[e], amax); rl[e] = (_Float16)0.f; }
+            else { _Float16 h, l; split_f16(((float)ah[e] + (float)al[e]) + ((float)bh[e] + (float)bl[e]), h, l, amax); rh[e] = h; rl[e] = l; }
+        }
+        _Float16* q = ob + p * 2 * out.ldc + out.coff + c;
+        *reinterpret_cast<f16x8a*>(q) = rh;
+        if constexpr (!F16) *reinterpret_cast<f16x8a*>(q + out.ldc) = rl;
+    }
+    split_overflow_report(ovf, amax);
+}
+
+int launch_add(const View& a, const View& b, const View& out, int B, hipStream_t s, int32_t* ovf) {
+    if (a.split || b.split || out.split) {
+        const auto ok8 = [](const View& v) { return v.base && v.C % 8 == 0 && v.ldc % 8 == 0 && v.coff % 8 == 0; };
+        if (a.split != b.split || a.split != out.split || !ok8(a) || !ok8(b) || !ok8(out) || a.C != b.C || a.C != out.C || a.H != b.H || a.W != b.W ||
+            a.H != out.H || a.W != out.W) { set_error("add(split): bad views"); return RTOD_E_ARG; }
+        const int64_t total = (int64_t)B * a.H * a.W * (a.C / 8);
+        if (a.split == 2) hipLaunchKernelGGL(add_split_kernel<true>, dim3(grid_for(total, 256)), dim3(256), 0, s, a, b, out, B, ovf);
+        else hipLaunchKernelGGL(add_split_kernel<false>, dim3(grid_for(total, 256)), dim3(256), 0, s, a, b, out, B, ovf);
+        return hip_fail(hipGetLastError(), "add(split) launch");
+    }
     if (!view_ok4(a) || !view_ok4(b) || !view_ok4(out) || a.C != b.C || a.C != out.C || a.H != b.H || a.W != b.W) {
         set_error("add: bad views"); return RTOD_E_ARG;
     }

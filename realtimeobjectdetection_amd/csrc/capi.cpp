@@ -451,6 +451,35 @@ int rtod_conv_dgrad(const float* w_oihw_dev, const double* row_scale_dev, const 
     RTOD_GUARD_END
 }
 
+int rtod_conv_dgrad_s2(const float* w_oihw_dev, const double* row_scale_dev, const float* dz_dev, const float* y_dev, float slope,
+                       int batch, int cout, int cin, int height, int width, int size, float* dx_dev, void* stream) {
+    RTOD_GUARD_BEGIN
+    return launch_conv_dgrad_s2(w_oihw_dev, row_scale_dev, dz_dev, y_dev, slope, batch, cout, cin, height, width, size, dx_dev, (hipStream_t)stream);
+    RTOD_GUARD_END
+}
+
+int rtod_conv_wgrad_s2_workspace(int batch, int cout, int cin, int height, int width, int size, size_t* bytes) {
+    if (!bytes) { set_error("conv_wgrad_s2_workspace: null pointer"); return RTOD_E_ARG; }
+    if (int rc = wgrad_check_shape("conv_wgrad_s2_workspace", batch, cout, cin, height, width, size)) return rc;
+    if (int rc = wgrad_s2_check("conv_wgrad_s2_workspace", size)) return rc;
+    *bytes = wgrad_workspace_bytes(batch, cout, cin, (height - 1) / 2 + 1, (width - 1) / 2 + 1, size, wgrad_tile_cap(cout, cin, size));
+    return RTOD_OK;
+}
+
+int rtod_conv_wgrad_s2(const float* dz_dev, const float* x_dev, int batch, int cout, int cin, int height, int width, int size,
+                       const double* row_scale_dev, float* dw_dev, float* db_dev, void* workspace, size_t workspace_bytes, void* stream) {
+    RTOD_GUARD_BEGIN
+    return launch_wgrad("conv_wgrad_s2", dz_dev, x_dev, batch, cout, cin, height, width, size, wgrad_tile_cap(cout, cin, size), row_scale_dev, dw_dev, db_dev,
+                        workspace, workspace_bytes, (hipStream_t)stream, 2);
+    RTOD_GUARD_END
+}
+
+int rtod_grad_join(const float* const* contributions_dev_ptrs, int count, const float* y_dev, float slope, long long n, float* out_dev, void* stream) {
+    RTOD_GUARD_BEGIN
+    return launch_grad_join(contributions_dev_ptrs, count, y_dev, slope, (int64_t)n, out_dev, (hipStream_t)stream);
+    RTOD_GUARD_END
+}
+
 int rtod_upsample2x_grad(const float* dz_dev, const float* y_dev, float slope, int mode, int batch, int channels, int height, int width,
                          float* dx_dev, void* stream) {
     RTOD_GUARD_BEGIN
@@ -464,6 +493,18 @@ int rtod_plan_neck_layers(const rtod_plan* plan, int* conv_layers, int* input_la
     int n = 0;
     for (const auto& L : plan->p.layers) {
         if (L.type != LT_CONV || !L.bn || !neck[L.index]) continue;
+        if (n < capacity) { conv_layers[n] = L.index; input_layers[n] = L.index - 1; }
+        ++n;
+    }
+    return n;
+}
+
+int rtod_plan_trainable_layers(const rtod_plan* plan, int* conv_layers, int* input_layers, int capacity) {
+    if (!plan || capacity < 0 || (capacity > 0 && (!conv_layers || !input_layers))) { set_error("plan_trainable_layers: bad args"); return RTOD_E_ARG; }
+    const std::vector<char> graph = plan->p.train_graph();
+    int n = 0;
+    for (const auto& L : plan->p.layers) {
+        if (L.type != LT_CONV || !L.bn || !graph[L.index]) continue;
         if (n < capacity) { conv_layers[n] = L.index; input_layers[n] = L.index - 1; }
         ++n;
     }

@@ -149,6 +149,8 @@ struct Plan {
                                       // rtod_conv_wgrad.  Liveness only as well; the frozen BatchNorm scales then also live on the device (d_block_scale)
     bool opt_keep_neck_activations = false; // ... and every buffer a NECK conv (neck_graph) or a head conv reads or writes: the activations of the walk behind the
                                       // backbone (rtod_conv_dgrad, rtod_upsample2x_grad, rtod_conv_wgrad).  Liveness only; the scales of all neck convs on the device
+    bool opt_keep_backbone_activations = false; // a superset of keep_neck_activations over the TRAINABLE convs (train_graph: stride-2 convs and shortcuts too).  Not
+                                      // liveness only: the plan then forms no fusion that hides a trainable conv (fusions_held, next to form)
     bool opt_fuse_stem_pool = true;   // ... with the 2x2 / stride-2 max-pool that follows it in the same kernel where the plan allows it (off: A/B and tests)
     int opt_force_f16s3_variant = -1; // >= 0: tile variant for every split-f16 conv (>= BAND_VARIANT_BASE: band layers)
     int opt_force_f32_variant = -1;   // >= 0: tile variant for every exact-fp32 conv
@@ -188,8 +190,15 @@ struct Plan {
     // block_plan_ok, routes, 2x upsamples) closed downstream: every reader of a member is a member or a [yolo] layer
     std::vector<std::vector<int>> consumers() const;                                // the readers of every layer's output, ascending
     std::vector<char> neck_graph() const;                                           // membership per layer
+    std::vector<char> closed_graph(bool backbone) const;                            // the closure under neck_graph and train_graph (backbone: the two more kinds)
     bool neck_conv(int layer) const;                                                // a BatchNorm conv of the neck
-    bool trains_folded(int layer) const;                                            // what block_conv accepts: a block conv; with keep_neck_activations any neck conv
+    // the trainable graph (rtod_plan_trainable_layers): neck_graph's closure rule with two more traversable kinds, a block-shaped conv
+    // that is 3x3 / stride 2 / pad 1 instead of stride 1, and a two-source linear [shortcut]
+    bool train_shape_ok(int layer) const;                                           // block_shape_ok, or block_shape_ok but for that stride
+    std::vector<char> train_graph() const;                                          // membership per layer
+    bool train_conv(int layer) const;                                               // a BatchNorm conv of the trainable graph
+    bool trains_folded(int layer) const;                                            // what block_conv accepts: a block conv; with keep_neck_activations any neck conv;
+                                                                                    // with keep_backbone_activations any trainable conv
     int block_conv(const char* who, int layer, size_t& slot) const;                 // the slot of a block conv, or why `layer` is none
     int update_conv_weight(int layer, const float* weight_oihw);                    // re-pack and upload one block conv, BatchNorm as loaded (rtod_plan_update_conv_weight)
     int step_conv_folded(int layer, const rtod_opt_step* opt, float* weight, const float* dw, float* m_w, float* v_w, hipStream_t s);   // rtod_plan_step_conv_folded
@@ -198,7 +207,7 @@ struct Plan {
     std::map<int, std::vector<float>> block_bn;     // block conv layer -> its [beta, gamma, mean, var] of the stream last loaded
     std::map<int, std::vector<double>> block_scale; // ... -> gamma / sqrt(var + 1e-5), the frozen scale pack_conv folds
     std::map<int, int64_t> block_scale_off;         // ... -> offset in d_block_scale (doubles)
-    double* d_block_scale = nullptr;                // options keep_block_inputs / keep_neck_activations: the scales on the device, allocated at the first load
+    double* d_block_scale = nullptr;                // options keep_block_inputs / keep_neck_activations / keep_backbone_activations: the scales on the device, allocated at the first load
     int64_t block_scale_doubles = 0;                // ... and how many doubles that allocation holds
     bool feeds_yolo(int layer) const { return layers[layer].type == LT_CONV && layer + 1 < (int)layers.size() && layers[layer + 1].type == LT_YOLO; }
     int forward(const float* x, int batch, float* out, hipStream_t s, float* launch_ms, bool tune = false);
@@ -235,6 +244,7 @@ struct Plan {
     View bn_raw_view(const Launch& l, int batch) const;   // fp32 view over d_bn_raw for this launch's conv
     bool stem2_pattern = false;                 // launches 0 / 1 are a stem and the stride-2 conv conv_stem2_f16s3 fuses (candidate, set by plan_buffers)
     bool stem_pool_pattern = false;             // launch 0 is the 16-filter stem and launch 1 the 2x2 / stride-2 max-pool that alone reads it (candidate, set by plan_buffers)
+    bool fusions_held() const;                  // option keep_backbone_activations: plan_buffers forms no shortcut fusion, no pointwise pair, no stem2 pattern
     LaunchForm form(size_t li) const;           // how launch li runs; computed on demand (keep_all_layers changes it without planning again)
     LayerForm layer_form(int layer) const;      // ... and what describe and the layer readers report of a layer
     std::map<int, std::vector<int>> tuned;     // batch -> per-launch split-f16 tile variant (-1: heuristic)

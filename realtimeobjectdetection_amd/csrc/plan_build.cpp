@@ -65,6 +65,7 @@ int Plan::set_option(const char* name, int value) {
         {"fuse_decode", &Plan::opt_fuse_decode}, {"zero_copy_concat", &Plan::opt_zero_copy_concat}, {"narrow_cin", &Plan::opt_narrow_cin},
         {"stem_pool", &Plan::opt_stem_pool}, {"fuse_stem_pool", &Plan::opt_fuse_stem_pool}, {"keep_head_inputs", &Plan::opt_keep_head_inputs},
         {"keep_block_inputs", &Plan::opt_keep_block_inputs}, {"keep_neck_activations", &Plan::opt_keep_neck_activations},
+        {"keep_backbone_activations", &Plan::opt_keep_backbone_activations},
     };
     const std::string k(name);
     bool* flag = nullptr; int* num = nullptr;
@@ -145,7 +146,7 @@ int Plan::plan_buffers() {
         if (i == 0) continue;
         Layer& P = layers[i - 1];
         if (P.type != LT_CONV || P.fused_into >= 0 || cons[i - 1].size() != 1) continue;
-        if (L.type == LT_SHORTCUT && L.srcs[1] != i - 1 && opt_fuse_shortcut) { P.fused_into = i; L.fused_away = true; }
+        if (L.type == LT_SHORTCUT && L.srcs[1] != i - 1 && opt_fuse_shortcut && !fusions_held()) { P.fused_into = i; L.fused_away = true; }
         else if (L.type == LT_YOLO && cons[i].empty() && opt_fuse_decode) { P.fused_into = i; L.fused_away = true; }
     }
     // materialised producers: every non-alias layer except convs fused into the next layer and
@@ -241,7 +242,7 @@ int Plan::plan_buffers() {
     }
     // fused-pointwise candidates: conv launch i immediately followed by a 1x1 / stride 1 conv launch that reads exactly
     // i's output, with Cout_i <= 64 (one N tile; wider hosts measured no gain), Cout_j in {16, 32, 64}, no residual / decode on j (conv_f16s3_common.h)
-    for (size_t i = 0; i + 1 < launches.size(); ++i) {
+    for (size_t i = 0; i + 1 < launches.size() && !fusions_held(); ++i) {
         Launch& h = launches[i]; Launch& g = launches[i + 1];
         if (h.kind != LK_CONV || g.kind != LK_CONV || h.out_layer < 0 || g.out_layer < 0 || g.in2_layer >= 0 || h.pw_host >= 0) continue;
         const Layer& H = layers[h.layer]; const Layer& G = layers[g.layer];
@@ -253,7 +254,7 @@ int Plan::plan_buffers() {
     }
     // stem + layer 1 fusion candidate: launch 0 is the stem kernel, launch 1 the conv of layer 1 reading only it, nothing else reads layer 0
     stem2_pattern = false;
-    if (launches.size() >= 2 && launches[0].kind == LK_STEM && launches[1].kind == LK_CONV && launches[1].layer == 1 && launches[1].in_layer == 0 &&
+    if (!fusions_held() && launches.size() >= 2 && launches[0].kind == LK_STEM && launches[1].kind == LK_CONV && launches[1].layer == 1 && launches[1].in_layer == 0 &&
         launches[1].in2_layer < 0 && launches[1].out_layer == 1 && cons[0].size() == 1 && n > 1) {
         const Layer& L0 = layers[0]; const Layer& L1 = layers[1];
         int pwc = 0;
@@ -310,8 +311,9 @@ int Plan::plan_buffers() {
             if (l.kind == LK_CONV && l.layer + 1 < n && feeds_yolo(l.layer + 1) && block_shape_ok(l.layer)) touch(buf_of_layer(l.in_layer), n);
     // option keep_neck_activations: what every neck conv and every head conv reads and writes (the walk reads outputs for the
     // activation masks, inputs for the weight gradients; routes are kept as their concat buffers)
-    if (opt_keep_neck_activations) {
-        const std::vector<char> neck = neck_graph();
+    // option keep_backbone_activations: the same over the trainable graph, which contains the neck
+    if (opt_keep_neck_activations || opt_keep_backbone_activations) {
+        const std::vector<char> neck = opt_keep_backbone_activations ? train_graph() : neck_graph();
         for (const auto& l : launches)
             if (l.kind == LK_CONV && (neck[l.layer] || feeds_yolo(l.layer))) {
                 touch(buf_of_layer(l.in_layer), n);
@@ -359,7 +361,20 @@ int Plan::block_of_head(int head) const {
 // conv that is a block by both parts of the definition above, a route, a 2x upsample.  A layer is in the graph if it is traversable
 // and every reader of its output is in the graph or a [yolo] layer; readers have higher indices, so one descending pass decides it.
 // Closure is what makes the gradients exact: nothing outside the graph lies between a member and the loss.
-std::vector<char> Plan::neck_graph() const {
+std::vector<char> Plan::neck_graph() const { return closed_graph(false); }
+
+// The trainable graph: the same closure with the two operations Darknet-53's backbone consists of, the 3x3 / stride-2 conv and the
+// residual [shortcut] (two sources, linear: it adds and carries no mask of its own).  A superset of the neck on every plan
+std::vector<char> Plan::train_graph() const { return closed_graph(true); }
+
+bool Plan::train_shape_ok(int layer) const {
+    if (block_shape_ok(layer)) return true;
+    if (layer < 1 || layer >= (int)layers.size() || opt_bn_batch_stats) return false;
+    const Layer& L = layers[layer];
+    return L.type == LT_CONV && L.bn && L.size == 3 && L.stride == 2 && L.pad == 1 && L.act <= 1 && L.cin % 32 == 0 && L.fused_into < 0;
+}
+
+std::vector<char> Plan::closed_graph(bool backbone) const {
     const int n = (int)layers.size();
     const std::vector<std::vector<int>> cons = consumers();
     std::vector<char> in(n, 0);
@@ -369,8 +384,9 @@ std::vector<char> Plan::neck_graph() const {
         if (L.type == LT_CONV && feeds_yolo(i)) {
             ok = ok && !L.bn && L.size == 1 && L.stride == 1 && L.cin % 32 == 0;
             for (int r : cons[i]) ok = ok && layers[r].type == LT_YOLO;
-        } else if (L.type == LT_CONV) ok = ok && block_shape_ok(i) && block_plan_ok(i);
+        } else if (L.type == LT_CONV) ok = ok && (backbone ? train_shape_ok(i) : block_shape_ok(i)) && block_plan_ok(i);
         else if (L.type == LT_UPSAMPLE) ok = ok && L.stride == 2;
+        else if (L.type == LT_SHORTCUT) ok = ok && backbone && L.srcs.size() == 2 && L.act == 0 && !L.fused_away;
         else ok = ok && L.type == LT_ROUTE;
         for (int r : cons[i]) ok = ok && (layers[r].type == LT_YOLO || in[r]);
         in[i] = ok ? 1 : 0;
@@ -378,12 +394,16 @@ std::vector<char> Plan::neck_graph() const {
     return in;
 }
 
+bool Plan::train_conv(int layer) const {
+    return layer >= 0 && layer < (int)layers.size() && layers[layer].type == LT_CONV && layers[layer].bn && train_graph()[layer];
+}
+
 bool Plan::neck_conv(int layer) const {
     return layer >= 0 && layer < (int)layers.size() && layers[layer].type == LT_CONV && layers[layer].bn && neck_graph()[layer];
 }
 
 bool Plan::trains_folded(int layer) const {
-    return block_of_head(layer + 1) == layer || (opt_keep_neck_activations && neck_conv(layer));
+    return block_of_head(layer + 1) == layer || (opt_keep_neck_activations && neck_conv(layer)) || (opt_keep_backbone_activations && train_conv(layer));
 }
 
 bool Plan::uses_split(const Layer& L) const {
@@ -419,6 +439,7 @@ int Plan::check_split_supported(int mode) const {
     // precisions 1 and 2 keep every activation in the split f16 layout: every conv but the stem must read
     // 32-channel K-chunks (or, with option narrow_cin, exactly 16 channels), every shortcut / head must ride a conv epilogue, concats must be zero-copy
     for (const auto& l : launches) {
+        if (l.kind == LK_ADD && fusions_held()) continue;                         // option keep_backbone_activations: the held shortcuts run the split-format add
         if (l.kind == LK_ADD || l.kind == LK_COPY || l.kind == LK_DECODE) {       // (max-pool and both upsamples have split-format kernels)
             set_error("precision %s unsupported for this cfg (layer %d needs a stand-alone %s kernel); use fp32", pn, l.layer,
                       l.kind == LK_ADD ? "add" : l.kind == LK_COPY ? "copy" : "decode");

@@ -9,6 +9,11 @@ namespace rtod {
 // The run-time predicates over the candidates that planning found; form / layer_form below are their only readers
 bool Plan::pw_active() const { return precision == 1 && opt_fuse_pointwise && !bn_split_active(); }
 bool Plan::stem2_active() const { return precision == 1 && !bn_split_active() && opt_stem2_kernel && stem2_pattern && !keep_all && convs[launches[0].conv_slot].split; }
+// The one decision of option keep_backbone_activations: the three fusions that leave a trainable conv's own output unstored (a
+// shortcut in its epilogue, the stem2 kernel's layer 1) or make block_plan_ok refuse it (a pointwise candidate pair) are not formed
+// as CANDIDATES (plan_buffers asks), so the predicates above never see them and the forward is that of a plan with fuse_shortcut,
+// fuse_pointwise and stem2_kernel off
+bool Plan::fusions_held() const { return opt_keep_backbone_activations; }
 int Plan::fused_pool(int layer) const {
     if (keep_all) return -1;                                     // every layer's own map is stored
     if (layer == 0 && precision >= 1 && stem_pool_pattern && convs[launches[0].conv_slot].stem16) return 1;
@@ -240,7 +245,7 @@ int Plan::forward(const float* x, int batch, float* out, hipStream_t s, float* l
                 break;
             case LK_MAXPOOL:
                 rc = launch_maxpool(view_of(l.in_layer), view_of(l.out_layer), batch, layers[l.layer].size, layers[l.layer].stride, layers[l.layer].pool_pad, s); break;
-            case LK_ADD: rc = launch_add(view_of(l.in_layer), view_of(l.in2_layer), view_of(l.out_layer), batch, s); break;
+            case LK_ADD: rc = launch_add(view_of(l.in_layer), view_of(l.in2_layer), view_of(l.out_layer), batch, s, overflow_flag); break;
             case LK_COPY: {
                 const View in = view_of(l.in_layer);
                 View o; const Buffer& b = bufs[l.out_buf];

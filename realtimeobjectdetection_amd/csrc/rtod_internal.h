@@ -309,7 +309,7 @@ int launch_prep_image(const unsigned char* img, int h, int w, int bgr, int inp_d
 int launch_prep_frames(const unsigned char* frames, int batch, int h, int w, int bgr, int out_h, int out_w, float* out, hipStream_t s);
 int launch_pack_input(const float* x_nchw, int B, int C, int H, int W, float* out_nhwc, int Cp, hipStream_t s);
 int launch_upsample2x(const View& in, const View& out, int B, hipStream_t s);
-int launch_add(const View& a, const View& b, const View& out, int B, hipStream_t s);
+int launch_add(const View& a, const View& b, const View& out, int B, hipStream_t s, int32_t* ovf = nullptr);   // ovf: split-format views' overflow word
 int launch_maxpool(const View& in, const View& out, int B, int size, int stride, int pad, hipStream_t s);   // pad > 0: symmetric -inf padding
 int launch_upsample_nearest2x(const View& in, const View& out, int B, hipStream_t s);
 // batch-statistics BatchNorm (+ activation + shortcut) over a conv's raw output, in place (aux_kernels.hip); stats: 2*C doubles of scratch
@@ -371,12 +371,18 @@ int64_t wgrad_slice_len(int64_t K, int cap);
 size_t wgrad_workspace_bytes(int batch, int cout, int cin, int h, int w, int size, int cap);
 int wgrad_check_shape(const char* who, int batch, int cout, int cin, int h, int w, int size);
 int launch_wgrad(const char* who, const float* dz, const float* x, int batch, int cout, int cin, int h, int w, int size, int cap,
-                 const double* row_scale, float* dw, float* db, void* ws, size_t ws_bytes, hipStream_t s);
+                 const double* row_scale, float* dw, float* db, void* ws, size_t ws_bytes, hipStream_t s, int stride = 1);
+int wgrad_s2_check(const char* who, int size);                      // rtod_conv_wgrad_s2: stride 2 (h x w the conv's input map) takes size 3 alone
 // data gradient of a 1x1 or 3x3 / stride 1 / same-padding convolution with the leaky-ReLU derivative of the stored activation in its
 // epilogue and an optional double scale per filter folded into the weights (dgrad.hip).  One path under both entries:
 // rtod_conv1x1_dgrad is size = 1, h = 1, w = pixels, no row scale.  `who` names the entry in the error texts.
 int launch_conv_dgrad(const char* who, const float* w, const double* row_scale, const float* dz, const float* y, float slope, int batch, int cout,
                       int cin, int h, int w_, int size, float* dx, hipStream_t s);
+// ... of a 3x3 / stride 2 / pad 1 convolution, h x w its input map: the same chains over parity-class tiles (dgrad.hip)
+int launch_conv_dgrad_s2(const float* w, const double* row_scale, const float* dz, const float* y, float slope, int batch, int cout, int cin,
+                         int h, int w_, int size, float* dx, hipStream_t s);
+// out = m(y) * (((c0 + c1) + c2) + c3): the fan-out sum of the gradient walk, 1 to 4 contributions, in one launch (grad_join.hip)
+int launch_grad_join(const float* const* contributions, int count, const float* y, float slope, int64_t n, float* out, hipStream_t s);
 // backward of the 2x upsample (bilinear align_corners=False, or nearest) in gather form, the producing conv's mask fused (upsample_grad.hip)
 int launch_upsample2x_grad(const float* dz, const float* y, float slope, int mode, int batch, int channels, int h, int w, float* dx, hipStream_t s);
 // optimiser step of one conv fused with the re-pack of its block of the weight image (head_step.hip): a 1x1 conv without BatchNorm

@@ -44,7 +44,7 @@ int64_t wgrad_slice_len(int64_t K, int cap) {
 }
 static int64_t wgrad_slices(int64_t K, int cap) { const int64_t L = wgrad_slice_len(K, cap); return (K + L - 1) / L; }
 static int64_t wgrad_tiles(int cout, int cin, int size) {
-    return (int64_t)((cout + WG_T - 1) / WG_T) * (((int64_t)cin * size * size + WG_T - 1) / WG_T);
+    return (((int64_t)cout + WG_T - 1) / WG_T) * (((int64_t)cin * size * size + WG_T - 1) / WG_T);    // (the entries call this before their shape checks)
 }
 // min(16, ceil(1024 / tiles)): a grid that has a thousand tiles already is not sliced.  (No tiles: a shape wgrad_check_shape refuses.)
 int wgrad_tile_cap(int cout, int cin, int size) {
@@ -58,11 +58,18 @@ size_t wgrad_workspace_bytes(int batch, int cout, int cin, int h, int w, int siz
     return sizeof(float) * (size_t)S * ((size_t)cout * cin * size * size + (size_t)cout);
 }
 
-// part: [S][cout][ncol] slice sums of dW (ncol = cin * TAPS), then [S][cout] slice sums of db.  TAPS == 1: H and W are not read
-template <int TAPS>
+// what the stride-2 instance takes behind the arguments of the stride-1 kernel, which keeps its argument list and its code: the map x lives on
+struct WgradS2 { int xh, xw; };
+
+// part: [S][cout][ncol] slice sums of dW (ncol = cin * TAPS), then [S][cout] slice sums of db.  TAPS == 1: H and W are not read.
+// STRIDE == 2 (rtod_conv_wgrad_s2, TAPS == 9): pixels, H, W describe the map of dz, the conv's OUTPUT, which k = (b, oy, ox) runs over;
+// B[n][k] = x[b, c, 2 oy + ky - 1, 2 ox + kx - 1] on the xh x xw input map, an exact zero outside it
+template <int TAPS, int STRIDE = 1, class... Extra>
 __global__ __launch_bounds__(256)
 void wgrad_slice_kernel(const float* __restrict__ dz, const float* __restrict__ x, int cout, int cin, int pixels, int H, int W, int K, int slice_len,
-                        int grid_m, int grid_n, float* __restrict__ part, float* __restrict__ part_db) {
+                        int grid_m, int grid_n, float* __restrict__ part, float* __restrict__ part_db, Extra... extra) {
+    [[maybe_unused]] int xh = H, xw = W;
+    if constexpr (sizeof...(Extra) > 0) { const WgradS2 e = (extra, ...); xh = e.xh; xw = e.xw; }
     const int ncol = cin * TAPS;
     __shared__ __attribute__((aligned(16))) float smem[2 * WG_T * WG_LD];
     float* sA = smem;
@@ -111,6 +118,10 @@ void wgrad_slice_kernel(const float* __restrict__ dz, const float* __restrict__ 
             ra[i] = (kok && o < cout) ? dz[((int64_t)b * cout + o) * pixels + p] : 0.f;
             if (TAPS == 1) {
                 rb[i] = (kok && c < cin) ? x[((int64_t)b * cin + c) * pixels + p] : 0.f;
+            } else if constexpr (STRIDE == 2) {
+                const int yy = 2 * py + col_dy[i], xx = 2 * px + col_dx[i];
+                const bool in = kok && c < ncol && yy >= 0 && yy < xh && xx >= 0 && xx < xw;
+                rb[i] = in ? x[((int64_t)b * cin + col_c[i]) * ((int64_t)xh * xw) + (int64_t)yy * xw + xx] : 0.f;
             } else {
                 const int yy = py + col_dy[i], xx = px + col_dx[i];
                 const bool in = kok && c < ncol && yy >= 0 && yy < H && xx >= 0 && xx < W;
@@ -187,11 +198,20 @@ int wgrad_check_shape(const char* who, int batch, int cout, int cin, int h, int 
     return RTOD_OK;
 }
 
-// `who` names the entry in every error text; `cap` is the entry's cap on the slice count (at most WGRAD_MAX_SLICES)
+// `who` names the entry in every error text; `cap` is the entry's cap on the slice count (at most WGRAD_MAX_SLICES).  stride 2
+// (rtod_conv_wgrad_s2: size 3, pad 1): h x w is the conv's INPUT map, dz lives on the output map and K = batch * ho * wo
+int wgrad_s2_check(const char* who, int size) {
+    if (size != 3) { set_error("%s: unsupported shape (size=%d; the stride-2 entry takes 3x3 convs)", who, size); return RTOD_E_ARG; }
+    return RTOD_OK;
+}
+
 int launch_wgrad(const char* who, const float* dz, const float* x, int batch, int cout, int cin, int h, int w, int size, int cap,
-                 const double* row_scale, float* dw, float* db, void* ws, size_t ws_bytes, hipStream_t s) {
+                 const double* row_scale, float* dw, float* db, void* ws, size_t ws_bytes, hipStream_t s, int stride) {
     if (!dz || !x || !dw || !ws) { set_error("%s: null pointer", who); return RTOD_E_ARG; }
     if (int rc = wgrad_check_shape(who, batch, cout, cin, h, w, size)) return rc;
+    if (stride == 2) { if (int rc = wgrad_s2_check(who, size)) return rc; }
+    const int xh = h, xw = w;
+    if (stride == 2) { h = (xh - 1) / 2 + 1; w = (xw - 1) / 2 + 1; }  // from here on the map that k runs over
     if (ws_bytes < wgrad_workspace_bytes(batch, cout, cin, h, w, size, cap)) { set_error("%s: workspace too small", who); return RTOD_E_ARG; }
     if ((uintptr_t)ws & 15) { set_error("%s: workspace must be 16-byte aligned", who); return RTOD_E_ARG; }
     const int pixels = h * w, ncol = cin * size * size;
@@ -202,7 +222,8 @@ int launch_wgrad(const char* who, const float* dz, const float* x, int batch, in
     float* part = (float*)ws;
     float* part_db = part + (int64_t)S * cout * ncol;
     float* pdb = db ? part_db : (float*)nullptr;
-    if (size == 1) hipLaunchKernelGGL(wgrad_slice_kernel<1>, dim3((unsigned)(tiles * S)), dim3(256), 0, s, dz, x, cout, cin, pixels, h, w, (int)K, L, gm, gn, part, pdb);
+    if (stride == 2) hipLaunchKernelGGL((wgrad_slice_kernel<9, 2, WgradS2>), dim3((unsigned)(tiles * S)), dim3(256), 0, s, dz, x, cout, cin, pixels, h, w, (int)K, L, gm, gn, part, pdb, WgradS2{xh, xw});
+    else if (size == 1) hipLaunchKernelGGL(wgrad_slice_kernel<1>, dim3((unsigned)(tiles * S)), dim3(256), 0, s, dz, x, cout, cin, pixels, h, w, (int)K, L, gm, gn, part, pdb);
     else hipLaunchKernelGGL(wgrad_slice_kernel<9>, dim3((unsigned)(tiles * S)), dim3(256), 0, s, dz, x, cout, cin, pixels, h, w, (int)K, L, gm, gn, part, pdb);
     const int64_t n = (int64_t)cout * ncol + (db ? cout : 0);
     hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, part, part_db, (int64_t)cout * ncol, cout, S, row_scale, ncol, dw, db);

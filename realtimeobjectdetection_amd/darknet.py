@@ -403,6 +403,22 @@ class Darknet(nn.Module):
         lib.rtod_plan_neck_layers(self._plan, c, i, n)
         return list(zip(list(c)[:n], list(i)[:n]))
 
+    def trainable_layers(self) -> list:
+        """``[(conv_layer, input_layer)]`` in ascending order (rtod_plan_trainable_layers): the BatchNorm convs of the neck graph
+        extended through 3x3 / stride-2 convs and ``[shortcut]`` layers — with options ``keep_backbone_activations`` every BatchNorm
+        conv of YOLOv3 except layer 0; on YOLOv3-tiny the neck (its backbone is max-pools).  With that option their inputs and
+        outputs are valid ``read_layer`` targets after a forward and ``conv_scale`` / ``update_conv_weight`` /
+        ``step_conv_folded`` accept each of them.  Asks the plan, so a forward (or ``prepare``) must have run."""
+        if self._plan is None:
+            raise RuntimeError("Darknet.trainable_layers: no plan yet; run a forward first")
+        lib = _ffi.lib()
+        n = lib.rtod_plan_trainable_layers(self._plan, None, None, 0)
+        if n < 0:
+            _ffi.check(n)
+        c, i = (C.c_int * max(n, 1))(), (C.c_int * max(n, 1))()
+        lib.rtod_plan_trainable_layers(self._plan, c, i, n)
+        return list(zip(list(c)[:n], list(i)[:n]))
+
     def conv_scale(self, layer: int):
         """``(device address, host float64 array [Cout])`` of a block conv's frozen BatchNorm scale ``gamma / sqrt(var + 1e-5)`` as
         the plan folded it (rtod_plan_conv_scale); the address is what ``train.conv_wgrad_async(row_scale=...)`` takes and needs

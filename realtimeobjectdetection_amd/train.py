@@ -4,9 +4,12 @@ The FORWARD VALUE of the loss: targets from ground-truth boxes (``target_creator
 (``darknet_loss``), the last step of ``feed_forward_through_model`` (train.py:412-425); and the first layer of its backward pass:
 the gradient with respect to the raw head maps and from it ``dW``, ``db`` of the detection-head convs (the 1x1 convs without
 BatchNorm in front of the [yolo] blocks), with a plain SGD step on them — fine-tuning the heads with the backbone frozen — and, with
-``trainable="blocks"``, one layer further: the weight gradient of the BatchNorm conv each head conv reads, BatchNorm frozen, and with ``trainable="neck"`` every BatchNorm conv behind the backbone.  Backward
-through the backbone, BatchNorm gradients, weight decay, epochs and data loaders are out of scope.  The reference's
-optimiser — ``optim.Adam(lr=1e-2)``, train.py:57 — runs on the heads as one kernel per conv that also re-packs the conv's weights in
+``trainable="blocks"``, one layer further: the weight gradient of the BatchNorm conv each head conv reads, BatchNorm frozen, with
+``trainable="neck"`` every BatchNorm conv behind the backbone, and with ``trainable="backbone"`` the backbone too: every BatchNorm conv
+the plan can train (``Darknet.trainable_layers``: on YOLOv3 all but layer 0), through 3x3 / stride-2 convs and residual shortcuts.
+Layer 0, BatchNorm gradients and batch statistics, max-pool and SiLU backward, weight decay, epochs and data loaders are out of scope
+(DESIGN.md §8).  The reference's
+optimiser — ``optim.Adam(lr=1e-2)``, train.py:57 — runs on the trained convs as one kernel per conv that also re-packs the conv's weights in
 place (``HeadOptimizer``, ``feed_forward_through_model``): that path never synchronises.  Same names and return conventions as the
 reference:
 
@@ -24,6 +27,9 @@ reference:
 * ``DarknetTrainer(model, trainable="neck")``, ``neck_gradients(frames_or_x, bndbox)``                (new) ... and every BatchNorm conv behind the
                                                                                             backbone (``Darknet.neck_layers``), through 3x3 convs, routes and the
                                                                                             upsample: ``(loss, head grads, {neck_conv_layer: dW})``
+* ``DarknetTrainer(model, trainable="backbone")``, ``backbone_gradients(frames_or_x, bndbox)``        (new) ... and the backbone (``Darknet.trainable_layers``),
+                                                                                            through stride-2 convs (``conv_dgrad_async`` / ``conv_wgrad_async``
+                                                                                            with ``stride=2``) and shortcuts, fan-out sums by ``grad_join_async``
 
 The reference's behaviour is kept as it is: only boxes whose class-0 slot is 1 and whose sides are at least
 ``min_box_size`` (24) count, ``anchor_fit`` compares a box with a square of the anchor's WIDTH, target slot 0 holds the y fraction
@@ -152,22 +158,29 @@ def yolo_loss_grad_async(pred, bndbox, heads, num_class, min_box_size=24, grad_p
 _wgrad_ws = {}
 
 
-def _wgrad(who, dz, x, size, row_scale, bias):
+def _wgrad(who, dz, x, size, row_scale, bias, stride=1):
     """The body of ``conv1x1_wgrad_async`` (``size`` None: rtod_conv1x1_wgrad, shape (B, Cout, Cin, pixels)) and ``conv_wgrad_async``
-    (rtod_conv_wgrad, shape (B, Cout, Cin, H, W, size)): the tensor checks, the workspace cached per shape, the outputs, the launch."""
+    (rtod_conv_wgrad, shape (B, Cout, Cin, H, W, size); ``stride`` 2: rtod_conv_wgrad_s2, H x W the map of ``x``): the tensor checks, the
+    workspace cached per shape, the outputs, the launch."""
     _need_cuda(dz, who)
     _need_cuda(x, who)
-    if dz.dim() != 4 or x.dim() != 4 or dz.size(0) != x.size(0) or tuple(dz.shape[2:]) != tuple(x.shape[2:]) or dz.dtype != torch.float32 or x.dtype != torch.float32:
-        raise ValueError("%s: expected float32 dz [B,Cout,H,W] and x [B,Cin,H,W], got %s and %s" % (who, tuple(dz.shape), tuple(x.shape)))
+    if stride not in (1, 2) or (stride == 2 and size is None):
+        raise ValueError("%s: stride must be 1 or 2, got %r" % (who, stride))
+    s2 = stride == 2
+    ok = dz.dim() == 4 and x.dim() == 4 and dz.size(0) == x.size(0) and dz.dtype == torch.float32 and x.dtype == torch.float32
+    if ok:
+        ok = tuple(dz.shape[2:]) == (tuple((n - 1) // 2 + 1 for n in x.shape[2:]) if s2 else tuple(x.shape[2:]))
+    if not ok:
+        raise ValueError("%s: expected float32 dz [B,Cout,%s] and x [B,Cin,H,W], got %s and %s" % (who, "(H-1)//2+1,(W-1)//2+1" if s2 else "H,W", tuple(dz.shape), tuple(x.shape)))
     dz, x = dz.contiguous(), x.contiguous()
-    B, cout, cin, H, W = dz.size(0), dz.size(1), x.size(1), dz.size(2), dz.size(3)
+    B, cout, cin, H, W = dz.size(0), dz.size(1), x.size(1), x.size(2), x.size(3)
     shape = (B, cout, cin, H * W) if size is None else (B, cout, cin, H, W, int(size))
     lib, dev = _ffi.lib(), dz.device
-    key = (dev.index,) + shape
+    key = (dev.index, stride) + shape
     ws = _wgrad_ws.get(key)
     if ws is None:
         nbytes = C.c_size_t()
-        _ffi.check((lib.rtod_conv1x1_wgrad_workspace if size is None else lib.rtod_conv_wgrad_workspace)(*shape, C.byref(nbytes)))
+        _ffi.check((lib.rtod_conv1x1_wgrad_workspace if size is None else lib.rtod_conv_wgrad_s2_workspace if s2 else lib.rtod_conv_wgrad_workspace)(*shape, C.byref(nbytes)))
         if len(_wgrad_ws) > 16:
             _wgrad_ws.clear()
         ws = _wgrad_ws[key] = (torch.empty((nbytes.value + 7) // 8, dtype=torch.float64, device=dev), nbytes.value)
@@ -176,7 +189,7 @@ def _wgrad(who, dz, x, size, row_scale, bias):
     db = torch.empty(cout, dtype=torch.float32, device=dev) if bias else None
     scale = () if size is None else (_scale_ptr(row_scale, cout, dev),)
     with torch.cuda.device(dev):
-        _ffi.check((lib.rtod_conv1x1_wgrad if size is None else lib.rtod_conv_wgrad)(
+        _ffi.check((lib.rtod_conv1x1_wgrad if size is None else lib.rtod_conv_wgrad_s2 if s2 else lib.rtod_conv_wgrad)(
             C.c_void_p(dz.data_ptr()), C.c_void_p(x.data_ptr()), *shape, *scale, C.c_void_p(dw.data_ptr()), C.c_void_p(db.data_ptr()) if bias else None,
             C.c_void_p(ws[0].data_ptr()), ws[1], _stream(dev)))
     return dw, db
@@ -200,12 +213,13 @@ def _scale_ptr(row_scale, cout, dev):
     return C.c_void_p(int(row_scale))
 
 
-def conv_wgrad_async(dz, x, size, row_scale=None, bias=False):
+def conv_wgrad_async(dz, x, size, row_scale=None, bias=False, stride=1):
     """Enqueue rtod_conv_wgrad: ``dz`` [B,Cout,H,W] and ``x`` [B,Cin,H,W] (contiguous float32 device tensors, Cin a multiple of
     32) -> ``(dW [Cout,Cin,size,size], db [Cout] or None)`` of a ``size`` x ``size`` (1 or 3), stride-1, same-padding conv.
     ``row_scale`` (float64 device tensor [Cout], or the device address ``Darknet.conv_scale`` returns): every row of dW times it,
-    one rounding.  Nothing synchronises; the workspace is cached per shape."""
-    return _wgrad("conv_wgrad", dz, x, int(size), row_scale, bias)
+    one rounding.  ``stride`` 2 (rtod_conv_wgrad_s2): a 3x3 / stride-2 / pad-1 conv, ``dz`` [B,Cout,(H-1)//2+1,(W-1)//2+1] on the
+    conv's output map.  Nothing synchronises; the workspace is cached per shape."""
+    return _wgrad("conv_wgrad", dz, x, int(size), row_scale, bias, stride)
 
 
 def conv1x1_dgrad_async(w, dz, y=None, slope=1.0):
@@ -231,31 +245,73 @@ def conv1x1_dgrad_async(w, dz, y=None, slope=1.0):
     return dx
 
 
-def conv_dgrad_async(w, dz, size, row_scale=None, y=None, slope=1.0):
+def conv_dgrad_async(w, dz, size, row_scale=None, y=None, slope=1.0, stride=1, in_hw=None):
     """Enqueue rtod_conv_dgrad: ``w`` [Cout,Cin,size,size] (raw float32 masters), ``dz`` [B,Cout,H,W] and, for a leaky producer, ``y``
     [B,Cin,H,W] (the STORED output of the layer the conv reads) -> ``dx`` [B,Cin,H,W] = ``m(y) * conv_transpose(dz, v)`` of a ``size``
     x ``size`` (1 or 3), stride-1, same-padding conv with ``v = float32(float64(w) * row_scale[o])`` (``row_scale``: None, a float64
     device tensor [Cout] or the device address ``Darknet.conv_scale`` returns).  Contiguous float32 device tensors, Cin a multiple
-    of 32; one fmaf chain per tap, the tap sums added in ascending order: an order the shape fixes; nothing synchronises."""
+    of 32; one fmaf chain per tap, the tap sums added in ascending order: an order the shape fixes; nothing synchronises.
+    ``stride`` 2 (rtod_conv_dgrad_s2): a 3x3 / stride-2 / pad-1 conv, ``dz`` [B,Cout,Ho,Wo] on its output map and ``dx`` on its
+    INPUT map, whose size comes from ``y``, else from ``in_hw = (H, W)``: ``Ho`` alone does not tell ``2 Ho`` from ``2 Ho - 1``."""
     for t in (w, dz) + ((y,) if y is not None else ()):
         _need_cuda(t, "conv_dgrad")
     size = int(size)
+    if stride not in (1, 2):
+        raise ValueError("conv_dgrad: stride must be 1 or 2, got %r" % (stride,))
     ok = dz.dim() == 4 and w.dim() in (2, 4) and w.size(0) == dz.size(1) and w.numel() == w.size(0) * w.size(1) * size * size and w.dtype == dz.dtype == torch.float32
+    H, W = (dz.size(2), dz.size(3)) if ok else (0, 0)
+    if ok and stride == 2:
+        if y is not None and y.dim() == 4:
+            H, W = y.size(2), y.size(3)
+        elif in_hw is not None:
+            H, W = int(in_hw[0]), int(in_hw[1])
+        else:
+            raise ValueError("conv_dgrad: stride 2 needs the size of the conv's input map: pass y or in_hw=(H, W)")
+        ok = H >= 1 and W >= 1 and (dz.size(2), dz.size(3)) == ((H - 1) // 2 + 1, (W - 1) // 2 + 1) and (in_hw is None or (H, W) == (int(in_hw[0]), int(in_hw[1])))
     if ok and y is not None:
-        ok = y.dtype == torch.float32 and tuple(y.shape) == (dz.size(0), w.size(1), dz.size(2), dz.size(3))
+        ok = y.dtype == torch.float32 and tuple(y.shape) == (dz.size(0), w.size(1), H, W)
     if not ok:
-        raise ValueError("conv_dgrad: expected float32 w [Cout,Cin,%d,%d], dz [B,Cout,H,W] and y [B,Cin,H,W], got %s, %s and %s"
-                         % (size, size, tuple(w.shape), tuple(dz.shape), None if y is None else tuple(y.shape)))
+        raise ValueError("conv_dgrad: expected float32 w [Cout,Cin,%d,%d], dz [B,Cout,%s] and y [B,Cin,H,W], got %s, %s and %s"
+                         % (size, size, "(H-1)//2+1,(W-1)//2+1" if stride == 2 else "H,W", tuple(w.shape), tuple(dz.shape), None if y is None else tuple(y.shape)))
     w, dz = w.contiguous(), dz.contiguous()
     y = None if y is None else y.contiguous()
-    B, cout, cin, H, W = dz.size(0), dz.size(1), w.size(1), dz.size(2), dz.size(3)
+    B, cout, cin = dz.size(0), dz.size(1), w.size(1)
     dev = dz.device
     dx = torch.empty((B, cin, H, W), dtype=torch.float32, device=dev)
+    entry = _ffi.lib().rtod_conv_dgrad_s2 if stride == 2 else _ffi.lib().rtod_conv_dgrad
     with torch.cuda.device(dev):
-        _ffi.check(_ffi.lib().rtod_conv_dgrad(C.c_void_p(w.data_ptr()), _scale_ptr(row_scale, cout, dev), C.c_void_p(dz.data_ptr()),
-                                              C.c_void_p(y.data_ptr()) if y is not None else None, float(slope), B, cout, cin, H, W, size,
-                                              C.c_void_p(dx.data_ptr()), _stream(dev)))
+        _ffi.check(entry(C.c_void_p(w.data_ptr()), _scale_ptr(row_scale, cout, dev), C.c_void_p(dz.data_ptr()),
+                         C.c_void_p(y.data_ptr()) if y is not None else None, float(slope), B, cout, cin, H, W, size,
+                         C.c_void_p(dx.data_ptr()), _stream(dev)))
     return dx
+
+
+def grad_join_async(contributions, y=None, slope=1.0):
+    """Enqueue rtod_grad_join: ``m(y) * (((c0 + c1) + c2) + c3)`` over equally shaped contiguous float32 device tensors, float32
+    adds from left to right, then one multiplication by ``slope`` where ``not (y > 0)`` (``y`` None or ``slope`` 1: no mask) — the
+    bits of ``(c0 + c1 + ...) * full_like(y, slope).masked_fill_(y > 0, 1)`` in one launch.  More than four contributions go
+    through several launches in the same order, the mask in the last.  A new tensor; nothing synchronises."""
+    cs = list(contributions)
+    if not cs:
+        raise ValueError("grad_join: no contribution")
+    for t in cs + ([y] if y is not None else []):
+        _need_cuda(t, "grad_join")
+        if t.dtype != torch.float32 or tuple(t.shape) != tuple(cs[0].shape):
+            raise ValueError("grad_join: expected equally shaped float32 tensors, got %s and %s" % (tuple(cs[0].shape), tuple(t.shape)))
+    cs = [c.contiguous() for c in cs]
+    y = None if y is None else y.contiguous()
+    dev, lib = cs[0].device, _ffi.lib()
+    while True:
+        now, cs = cs[:4], cs[4:]
+        last = not cs
+        out = torch.empty_like(now[0])
+        ptrs = (C.c_void_p * 4)(*[c.data_ptr() for c in now])
+        with torch.cuda.device(dev):
+            _ffi.check(lib.rtod_grad_join(ptrs, len(now), C.c_void_p(y.data_ptr()) if last and y is not None else None, float(slope) if last else 1.0,
+                                          out.numel(), C.c_void_p(out.data_ptr()), _stream(dev)))
+        if last:
+            return out
+        cs = [out] + cs
 
 
 def upsample2x_grad_async(dz, y=None, slope=1.0, mode="bilinear"):
@@ -372,10 +428,11 @@ class DarknetTrainer:
     last loss: total, xy, wh, obj, noobj, cls)."""
 
     def __init__(self, model, resolution=None, num_classes=None, trainable="heads"):
-        if trainable not in ("heads", "blocks", "neck"):
-            raise ValueError("DarknetTrainer: trainable must be 'heads', 'blocks' or 'neck', got %r" % (trainable,))
+        if trainable not in ("heads", "blocks", "neck", "backbone"):
+            raise ValueError("DarknetTrainer: trainable must be 'heads', 'blocks', 'neck' or 'backbone', got %r" % (trainable,))
         self.trainable = trainable         # "blocks": feed_forward_through_model also trains the BatchNorm conv in front of each head conv;
-                                           # "neck": every BatchNorm conv behind the backbone (Darknet.neck_layers)
+                                           # "neck": every BatchNorm conv behind the backbone (Darknet.neck_layers);
+                                           # "backbone": every conv the plan can train (Darknet.trainable_layers: all but layer 0 on YOLOv3)
         self.darknet = model
         if resolution is not None:
             assert isinstance(resolution, int) and resolution % 32 == 0
@@ -627,11 +684,35 @@ class DarknetTrainer:
         ``keep_neck_activations``."""
         model = self.darknet
         opts = getattr(model, "options", {})
-        if not (int(opts.get("keep_head_inputs", 0)) and int(opts.get("keep_neck_activations", 0))):
+        if not (int(opts.get("keep_head_inputs", 0)) and (int(opts.get("keep_neck_activations", 0)) or int(opts.get("keep_backbone_activations", 0)))):
             raise RuntimeError("DarknetTrainer.neck_gradients: set model.options['keep_head_inputs'] = 1 and model.options['keep_neck_activations'] = 1 "
                                "before the first forward; without them the activations of the neck do not survive the forward")
         loss, head_grads, operands = self._head_pass(frames_or_x, bndbox)
-        layers, readers, member, scales = self._neck()
+        return loss, head_grads, self._walk(loss, head_grads, operands, self._neck())
+
+    def backbone_gradients(self, frames_or_x, bndbox):
+        """``(loss, {head_conv_layer: (dW, db)}, {conv_layer: dW [Cout,Cin,k,k]})`` over ``Darknet.trainable_layers()``: the walk of
+        ``neck_gradients`` carried on through the backbone, with two more kinds of layer.  A 3x3 / stride-2 conv calls
+        rtod_conv_wgrad_s2 and rtod_conv_dgrad_s2.  A ``[shortcut]`` hands the gradient of its output to both sources unchanged; it
+        carries no mask of its own, and a leaky conv that it alone reads has its mask applied by rtod_grad_join with that one
+        contribution.  Layer 0 is not trained: the walk ends at the first layer whose input is outside the graph.  All
+        on the current stream, nothing synchronises.  The model's ``options`` must hold ``keep_head_inputs`` and
+        ``keep_backbone_activations``."""
+        model = self.darknet
+        opts = getattr(model, "options", {})
+        if not (int(opts.get("keep_head_inputs", 0)) and int(opts.get("keep_backbone_activations", 0))):
+            raise RuntimeError("DarknetTrainer.backbone_gradients: set model.options['keep_head_inputs'] = 1 and model.options['keep_backbone_activations'] = 1 "
+                               "before the first forward; without them the plan fuses convs of the backbone into other kernels and their activations do not survive the forward")
+        loss, head_grads, operands = self._head_pass(frames_or_x, bndbox)
+        return loss, head_grads, self._walk(loss, head_grads, operands, self._graph("backbone"))
+
+    def _walk(self, loss, head_grads, operands, graph):
+        """The one walk under ``neck_gradients`` and ``backbone_gradients``: ``{conv_layer: dW}`` of the BatchNorm convs of ``graph =
+        (layers, readers, member, scales)``, in descending layer order, from the heads' ``operands`` (``_head_pass``).  A layer's dense
+        ``read_layer`` copy is dropped once the walk has passed the layer (every use of it lies at or behind it), and its entry of
+        ``parts`` when its gradient is taken."""
+        model = self.darknet
+        layers, readers, member, scales = graph
         masters = self._masters(list(head_grads) + sorted(scales), loss.device)
         B = next(iter(operands.values()))[0].size(0)
         stored = {}
@@ -660,16 +741,13 @@ class DarknetTrainer:
             if not isinstance(got, list):
                 return got
             got.sort(key=lambda rc: rc[0])
-            total = got[0][1]
-            for _, c in got[1:]:
-                total = total + c
             L = layers[layer]
-            if L.type == "convolutional" and L.leaky:
-                y = read(layer)
-                total = total * torch.full_like(y, 0.1).masked_fill_(y > 0, 1.0)
-            return total
+            leaky = L.type == "convolutional" and L.leaky
+            if len(got) == 1 and not leaky:
+                return got[0][1]
+            return grad_join_async([c for _, c in got], read(layer) if leaky else None, 0.1 if leaky else 1.0)
 
-        neck_grads = {}
+        grads = {}
         for i in range(len(layers) - 1, -1, -1):
             if not member[i]:
                 continue
@@ -679,25 +757,36 @@ class DarknetTrainer:
                 dz = operands[i][0] if head else gradient(i)
                 scale = None if head else scales[i]
                 if not head:
-                    neck_grads[i] = conv_wgrad_async(dz, read(i - 1), L.size, row_scale=scale)[0]
+                    grads[i] = conv_wgrad_async(dz, read(i - 1), L.size, row_scale=scale, stride=L.stride)[0]
                 if i > 0:
-                    send(i - 1, i, lambda y, slope, dz=dz, scale=scale, L=L: conv_dgrad_async(masters[i][0], dz, L.size, scale, y, slope), True)
+                    hw = (layers[i - 1].hout, layers[i - 1].wout)
+                    send(i - 1, i, lambda y, slope, dz=dz, scale=scale, L=L, hw=hw: conv_dgrad_async(masters[i][0], dz, L.size, scale, y, slope, L.stride, hw), True)
             elif L.type == "upsample":
                 g = gradient(i)
                 send(i - 1, i, lambda y, slope, g=g, L=L: upsample2x_grad_async(g, y, slope, "nearest" if L.nearest else "bilinear"), True)
+            elif L.type == "shortcut":                                # both sources take the gradient as it is
+                g = gradient(i)
+                for s in L.srcs:
+                    send(s, i, lambda y, slope, g=g: g if y is None else grad_join_async([g], y, slope), True)
             else:                                                     # route: every source takes its channel range
                 g, off = gradient(i), 0
                 for s in L.srcs:
                     send(s, i, lambda y, slope, g=g, off=off, s=s: g.narrow(1, off, layers[s].cout).contiguous(), False)
                     off += layers[s].cout
-        return loss, head_grads, {layer: neck_grads[layer] for layer in sorted(neck_grads)}
+            for k in [k for k in stored if k >= i]:                   # every use of layer k's copy lies at or behind layer k
+                del stored[k]
+        return {layer: grads[layer] for layer in sorted(grads)}
 
     def _neck(self):
-        """``(IR layers, readers per layer, membership per layer, {neck conv: device address of its frozen scale})`` of the neck graph,
-        asked of the plan once per plan and weight load.  The plan decides which convs belong (``Darknet.neck_layers``); routes and
-        upsamples follow by the same closure rule: every reader is a member or a [yolo] layer."""
+        return self._graph("neck")
+
+    def _graph(self, which):
+        """``(IR layers, readers per layer, membership per layer, {conv: device address of its frozen scale})`` of the neck graph
+        (``which`` "neck") or of the trainable graph ("backbone"), asked of the plan once per plan and weight load.  The plan decides
+        which convs belong (``Darknet.neck_layers`` / ``trainable_layers``); routes, upsamples and, in the trainable graph, shortcuts
+        follow by the same closure rule: every reader is a member or a [yolo] layer."""
         model = self.darknet
-        key = (model._plan.value, model._plan_weights_version)
+        key = (which, model._plan.value, model._plan_weights_version)
         if self._neck_cache is None or self._neck_cache[0] != key:
             h = int(model.net_info["height"])
             w = int(model.input_width) if getattr(model, "input_width", None) is not None else h
@@ -706,12 +795,14 @@ class DarknetTrainer:
             for L in layers:
                 for s in (L.srcs if L.type in ("route", "shortcut") else ((L.index - 1,) if L.index > 0 else ())):
                     readers[s].append(L.index)
-            convs = {c for c, _ in model.neck_layers()} | {c for c, _ in model.head_layers()}
+            trained = model.neck_layers() if which == "neck" else model.trainable_layers()
+            convs = {c for c, _ in trained} | {c for c, _ in model.head_layers()}
+            passive = ("route", "upsample") if which == "neck" else ("route", "upsample", "shortcut")
             member = [False] * len(layers)
             for L in reversed(layers):
-                ok = L.index in convs if L.type == "convolutional" else L.type in ("route", "upsample") and bool(readers[L.index])
+                ok = L.index in convs if L.type == "convolutional" else L.type in passive and bool(readers[L.index])
                 member[L.index] = ok and all(layers[r].type == "yolo" or member[r] for r in readers[L.index])
-            scales = {c: model.conv_scale(c)[0] for c, _ in model.neck_layers()}
+            scales = {c: model.conv_scale(c)[0] for c, _ in trained}
             self._neck_cache = (key, (layers, readers, member, scales))
         return self._neck_cache[1]
 
@@ -723,10 +814,10 @@ class DarknetTrainer:
         synchronises; the next forward on that stream runs the new weights.  Returns the loss from before the step as a 0-dim
         float32 device tensor.  The module's ``conv.weight`` / ``conv.bias`` lag behind until ``sync_parameters()`` (or anything
         that reads the model's parameters as a whole: ``weight_stream()``, ``state_dict()``, a re-pack)."""
-        if self.trainable in ("blocks", "neck"):
+        if self.trainable in ("blocks", "neck", "backbone"):
             # every gradient kernel of the batch is enqueued before the first step, as autograd has it: the steps update the
             # masters in place, and the data gradients through the heads and the neck convs read them
-            loss, grads, block_grads = (self.block_gradients if self.trainable == "blocks" else self.neck_gradients)(batch_data, bndbox)
+            loss, grads, block_grads = {"blocks": self.block_gradients, "neck": self.neck_gradients, "backbone": self.backbone_gradients}[self.trainable](batch_data, bndbox)
             grads = dict(grads)
             grads.update({layer: (dw, None) for layer, dw in block_grads.items()})
         else:

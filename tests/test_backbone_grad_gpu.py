@@ -1,0 +1,491 @@
+"""GPU tests of the backbone training path: rtod_conv_dgrad_s2 (csrc/dgrad.hip), rtod_conv_wgrad_s2 (csrc/wgrad.hip) and rtod_grad_join
+(csrc/grad_join.hip) against exact integer and float64 results, option keep_backbone_activations, and DarknetTrainer.backbone_gradients /
+feed_forward_through_model(trainable="backbone") end to end against torch autograd of the whole trainable sub-graph.
+
+Gates, with u = 2^-24.
+* Integers: operands in [-4, 4], power-of-two scales and the slope 0.5 make every product and partial sum exactly representable, so
+  the results equal the int64 sums bit for bit in any order.
+* dgrad stride 2 on floats: |dx - float64| <= ((K + 2) u + 2^-52) |m| sum |v| |dz|, K = (taps that reach the pixel) * Cout <= 4 Cout:
+  the derived bound of the stride-1 test (tests/test_neck_grad_gpu.py) — one rounding of the folded weight, Cout roundings of a tap's
+  chain and one per added tap (fewer than taps * Cout), the mask multiplication.
+* wgrad stride 2 on floats: the bound tests/test_block_grad_gpu.py applies to rtod_conv_wgrad with K = B * Ho * Wo.
+* rtod_grad_join: the bits of the torch expression it replaces.
+* End to end: the docstrings of the tests."""
+import numpy as np
+import pytest
+import torch
+
+from backbone_grad_cases import BACKBONE, MINI_S2, S2_SHAPES, TRAINABLE, U, UNFUSED, conv_dgrad_s2_ref, conv_wgrad_s2_ref, out_hw, taps_per_pixel
+from block_grad_cases import opt_update_f32
+from head_grad_cases import cpu_head_model, pack
+from loss_cases import bits
+from neck_grad_cases import NECK
+from test_block_grad_gpu import GATES, _bn_of, _frames, _t64
+from test_head_grad_gpu import _conv_of, _forward, _model, step_batch
+from realtimeobjectdetection_amd import _ffi, cfgs, train as T
+from realtimeobjectdetection_amd.train import HeadOptimizer
+
+pytestmark = pytest.mark.gpu
+F = np.float32
+fn = torch.nn.functional
+HEADS = [14, 22]
+
+
+def _dev(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+def _same(a, b):
+    return np.array_equal(bits(a.detach().cpu().numpy()), bits(b.detach().cpu().numpy()))
+
+
+# ------------------------------------------------------------------------------------------ 1a. the stride-2 data gradient
+def _dgrad(w, dz, hw, scale=None, y=None, slope=1.0):
+    return T.conv_dgrad_async(_dev(w), _dev(dz), 3, None if scale is None else _dev(scale), None if y is None else _dev(y), slope, stride=2, in_hw=hw).cpu().numpy()
+
+
+@pytest.mark.parametrize("shape", S2_SHAPES)
+def test_conv_dgrad_s2_exact_on_small_integers(shape):
+    B, cout, cin, H, W = shape
+    Ho, Wo = out_hw(H, W)
+    assert 16 * 4 * cout < 2 ** 24
+    rng = np.random.default_rng(B * 1000 + H * W)
+    w, dz, y = rng.integers(-4, 5, (cout, cin, 3, 3)), rng.integers(-4, 5, (B, cout, Ho, Wo)), rng.integers(-1, 2, (B, cin, H, W))
+    want = conv_dgrad_s2_ref(w, dz, H, W, np.int64).astype(np.float64)
+    wf, dzf, yf = w.astype(F), dz.astype(F), y.astype(F)
+    m = np.where(y > 0, 1.0, 0.5)                                     # y == 0 takes the slope
+    got = _dgrad(wf, dzf, (H, W), None, yf, 0.5)
+    assert got.shape == (B, cin, H, W) and np.array_equal(got.astype(np.float64), want * m), shape
+    assert np.array_equal(_dgrad(wf, dzf, (H, W), None, None, 0.5).astype(np.float64), want), shape                # no y: linear
+    assert np.array_equal(_dgrad(wf, dzf, (H, W), None, yf, 1.0).astype(np.float64), want), shape                  # slope 1: linear
+    if H == 1 and W == 1:                                             # only the centre tap sees the pixel
+        assert np.array_equal(want[:, :, 0, 0], np.einsum("oc,bo->bc", w[:, :, 1, 1], dz[:, :, 0, 0])) and want.any()
+    s = 2.0 ** rng.integers(-3, 4, cout).astype(np.float64)           # power-of-two row scales keep the integers exact
+    wants = conv_dgrad_s2_ref(w.astype(np.float64) * s[:, None, None, None], dz, H, W, np.float64)
+    assert np.array_equal(_dgrad(wf, dzf, (H, W), s, yf, 0.5).astype(np.float64), wants * m), shape
+
+
+@pytest.mark.parametrize("shape", S2_SHAPES)
+def test_conv_dgrad_s2_floats_within_the_chain_bound_and_reproducible(shape):
+    B, cout, cin, H, W = shape
+    Ho, Wo = out_hw(H, W)
+    K = (taps_per_pixel(H, W) * cout)[None, None]                     # per input pixel: 1, 2, 2 or 4 taps of Cout terms
+    rng = np.random.default_rng(B * 77 + H * W)
+    w, dz, y = (rng.standard_normal(s).astype(F) for s in ((cout, cin, 3, 3), (B, cout, Ho, Wo), (B, cin, H, W)))
+    y[0, 0, 0, 0] = 0.0
+    s = (rng.uniform(0.2, 3.0, cout) * rng.choice([-1.0, 1.0], cout)).astype(np.float64)
+    slope = F(0.1)
+    m = np.where(y > 0, 1.0, float(slope))
+    for scale in (None, s):
+        v64 = w.astype(np.float64) * (1.0 if scale is None else scale[:, None, None, None])
+        dx = _dgrad(w, dz, (H, W), scale, y, float(slope))
+        want = m * conv_dgrad_s2_ref(v64, dz, H, W, np.float64)
+        bound = ((K + 2) * U + 2.0 ** -52) * m * conv_dgrad_s2_ref(np.abs(v64), np.abs(dz), H, W, np.float64)
+        worst = float(np.divide(np.abs(dx - want), bound, out=np.zeros_like(want), where=bound > 0).max())
+        print("dgrad_s2 %s %s: worst error / bound %.3g" % (shape, "scaled" if scale is not None else "plain", worst))
+        assert (np.abs(dx - want) <= bound).all(), (shape, scale is not None, worst)
+        assert dx.tobytes() == _dgrad(w, dz, (H, W), scale, y, float(slope)).tobytes(), shape
+    # the input size from y alone (no in_hw) gives the same call
+    dx_y = T.conv_dgrad_async(_dev(w), _dev(dz), 3, None, _dev(y), float(slope), stride=2).cpu().numpy()
+    assert dx_y.tobytes() == _dgrad(w, dz, (H, W), None, y, float(slope)).tobytes()
+    with pytest.raises(ValueError, match="in_hw"):
+        T.conv_dgrad_async(_dev(w), _dev(dz), 3, stride=2)
+
+
+# ------------------------------------------------------------------------------------------ 1b. the stride-2 weight gradient
+def _wgrad(dz, x, scale=None, bias=True):
+    dw, db = T.conv_wgrad_async(_dev(dz), _dev(x), 3, row_scale=None if scale is None else _dev(scale), bias=bias, stride=2)
+    return dw.cpu().numpy(), None if db is None else db.cpu().numpy()
+
+
+@pytest.mark.parametrize("shape", S2_SHAPES)
+def test_conv_wgrad_s2_exact_on_small_integers(shape):
+    B, cout, cin, H, W = shape
+    Ho, Wo = out_hw(H, W)
+    rng = np.random.default_rng(B * 1000 + H * W + 3)
+    dz, x = rng.integers(-4, 5, (B, cout, Ho, Wo)), rng.integers(-4, 5, (B, cin, H, W))
+    assert 16 * B * Ho * Wo < 2 ** 24
+    dw, db = _wgrad(dz.astype(F), x.astype(F))
+    want = conv_wgrad_s2_ref(dz, x, np.int64)
+    assert dw.shape == (cout, cin, 3, 3) and np.array_equal(dw.astype(np.int64), want) and np.array_equal(dw, np.rint(dw)), shape
+    assert np.array_equal(db.astype(np.int64), dz.sum(axis=(0, 2, 3))), shape
+    if H == 1 and W == 1:                                             # only the centre tap sees the pixel: the other eight are exactly 0
+        off = np.ones((3, 3), bool)
+        off[1, 1] = False
+        assert not dw[:, :, off].any() and dw[:, :, 1, 1].any()
+    s = 2.0 ** rng.integers(-3, 4, cout).astype(np.float64)
+    dws, dbs = _wgrad(dz.astype(F), x.astype(F), scale=s)
+    assert np.array_equal(dws.astype(np.float64), want * s[:, None, None, None]) and np.array_equal(dbs, db), shape
+
+
+@pytest.mark.parametrize("shape", S2_SHAPES)
+def test_conv_wgrad_s2_floats_within_the_summation_bound_and_reproducible(shape):
+    B, cout, cin, H, W = shape
+    Ho, Wo = out_hw(H, W)
+    K = B * Ho * Wo
+    rng = np.random.default_rng(B * 77 + H * W + 3)
+    dz, x = rng.standard_normal((B, cout, Ho, Wo)).astype(F), rng.standard_normal((B, cin, H, W)).astype(F)
+    s = (rng.uniform(0.2, 3.0, cout) * rng.choice([-1.0, 1.0], cout)).astype(np.float64)
+    dw, db = _wgrad(dz, x)
+    dws, dbs = _wgrad(dz, x, scale=s)
+    want = conv_wgrad_s2_ref(dz, x, np.float64)
+    mass = conv_wgrad_s2_ref(np.abs(dz), np.abs(x), np.float64)
+    s4 = s[:, None, None, None]
+    if K == 1:                                                        # the bound is 0: the correctly rounded product, bit for bit ...
+        assert np.array_equal(bits(dw), bits(want.astype(F))), shape
+        assert np.array_equal(bits(dws), bits((want.astype(F).astype(np.float64) * s4).astype(F))), shape          # ... and its one scaling
+    else:
+        assert (np.abs(dw - want) <= (K - 1) * U * mass).all(), (shape, float((np.abs(dw - want) / np.maximum((K - 1) * U * mass, 1e-300)).max()))
+        assert (np.abs(dws - want * s4) <= (K * U + (K - 1) * U * U + 2.0 ** -52) * mass * np.abs(s4)).all(), shape
+    want_b, mass_b = dz.astype(np.float64).sum(axis=(0, 2, 3)), np.abs(dz).astype(np.float64).sum(axis=(0, 2, 3))
+    assert (np.abs(db - want_b) <= (K - 1) * U * mass_b).all() and np.array_equal(bits(db), bits(dbs)), shape
+    dw2, db2 = _wgrad(dz, x)
+    dws2, _ = _wgrad(dz, x, scale=s, bias=False)
+    assert dw.tobytes() == dw2.tobytes() and db.tobytes() == db2.tobytes() and dws.tobytes() == dws2.tobytes(), shape
+
+
+# ------------------------------------------------------------------------------------------ 1c. the join
+@pytest.mark.parametrize("n", [1, 63, 64, 4099])
+@pytest.mark.parametrize("count", [1, 2, 3, 4])
+def test_grad_join_is_the_torch_expression_bit_for_bit(count, n):
+    rng = np.random.default_rng(count * 10000 + n)
+    cs = [_dev(rng.standard_normal(n).astype(F) * F(10.0) ** rng.integers(-3, 4, n).astype(F)) for _ in range(count)]
+    y = rng.standard_normal(n).astype(F)
+    y[::5] = 0.0                                                      # y == 0 takes the slope
+    y = _dev(y)
+    total = cs[0]
+    for c in cs[1:]:
+        total = total + c
+    masked = total * torch.full_like(y, 0.1).masked_fill_(y > 0, 1.0)
+    assert _same(T.grad_join_async(cs, y, 0.1), masked), (count, n)
+    assert _same(T.grad_join_async(cs), total) and _same(T.grad_join_async(cs, y, 1.0), total), (count, n)
+    if n > 1:                                                         # views that start 4 bytes into an allocation: the scalar form
+        odd = [torch.cat([c[:1], c])[1:] for c in cs]
+        assert all(o.data_ptr() % 16 for o in odd) and _same(T.grad_join_async(odd, y, 0.1), masked), (count, n)
+    more = cs + [_dev(rng.standard_normal(n).astype(F)) for _ in range(3)]      # more than four: several launches, the same order
+    total = more[0]
+    for c in more[1:]:
+        total = total + c
+    assert _same(T.grad_join_async(more, y, 0.1), total * torch.full_like(y, 0.1).masked_fill_(y > 0, 1.0)), (count, n)
+
+
+# ------------------------------------------------------------------------------------------ 2. keep_backbone_activations alone
+def _resplit(a, b, precision):
+    """The stand-alone shortcut of a split-f16 / f16 plan from the stored values of its two sources (read_layer: (hi + lo) / 8, exact):
+    one fp32 add in the format's domain, then the store split (RNE halves, saturated at the f16 range), read back as read_layer does."""
+    s = (a * F(8)) + (b * F(8))
+    s = np.clip(s, F(-65504.0), F(65504.0)).astype(F)
+    h = s.astype(np.float16)
+    if precision == "f16":
+        return h.astype(F) * F(0.125)
+    l = (s - h.astype(F)).astype(F).astype(np.float16)
+    return (h.astype(F) + l.astype(F)) * F(0.125)
+
+
+@pytest.mark.parametrize("net,precision,width", [("mini", "fp32", None), ("mini", "f16s3", None), ("mini", "f16", None), ("mini", "fp32", 96), ("tiny", "fp32", None)])
+def test_keep_backbone_activations_is_the_plan_with_the_three_fusions_off(tmp_path, net, precision, width):
+    """fp32: outputs under both decodes bit-identical to the twin plan with fuse_shortcut, fuse_pointwise and stem2_kernel off, the
+    same launch variants, every member conv's output and input as a keep_all plan holds them, arena_bytes not below the default plan's.
+
+    f16s3 / f16: that twin cannot be built — the library refuses fuse_shortcut = 0 at these precisions by itself (only a plan with the
+    option may run the split-format add: tests/test_ffi_host.py pins the refusal), which the test asserts.  There the outputs and the
+    stored layers are held to a keep_all plan with the option, and every shortcut's stored map to the bits of the documented
+    arithmetic of the new add kernel from its two stored sources (_resplit)."""
+    res, B = 64, 3
+    text = cfgs.mini_cfg(res, width or res) if net == "mini" else cfgs.yolov3_tiny_cfg(res, res)
+    x = _frames(B, res, width)
+    opt = {"keep_backbone_activations": 1}
+    default = _model(tmp_path, text, res, precision, name="default")
+    on = _model(tmp_path, text, res, precision, opt, name="on")
+    every = _model(tmp_path, text, res, precision, opt, keep_all=True, name="all")
+    models = [default, on, every]
+    twin = None
+    if precision == "fp32":
+        twin = _model(tmp_path, text, res, precision, UNFUSED, name="twin")
+        models.append(twin)
+    for model in models:
+        model.input_width = width
+    if precision != "fp32":
+        refused = _model(tmp_path, text, res, precision, UNFUSED, name="refused")
+        with pytest.raises(_ffi.RtodError, match="add"):
+            _forward(refused, x)
+    for td in (False, True):
+        y_def, y_on, y_all = _forward(default, x, td), _forward(on, x, td), _forward(every, x, td)
+        assert on.active_precision == precision and _same(y_on, y_all)
+        if twin is not None:
+            assert _same(y_on, _forward(twin, x, td)) and y_def.shape == y_on.shape
+        assert [c for c, _ in on.trainable_layers()] == TRAINABLE[net] and [c for c, _ in on.neck_layers()] == NECK[net]
+        for conv, inp in on.trainable_layers():                       # what the walk reads is what a plan that keeps everything holds
+            for layer in (conv, inp):
+                got, want = on.read_layer(layer, B), every.read_layer(layer, B)
+                assert got.abs().sum() > 0 and torch.equal(got, want), (net, precision, layer)
+        if precision != "fp32" and net == "mini":
+            for sc, (a, b) in ((4, (3, 1)), (8, (7, 5))):
+                want = _resplit(every.read_layer(a, B).cpu().numpy(), every.read_layer(b, B).cpu().numpy(), precision)
+                assert np.array_equal(bits(every.read_layer(sc, B).cpu().numpy()), bits(want)), (precision, sc)
+    if twin is not None:
+        assert [li.variant for li in twin.launch_infos()] == [li.variant for li in on.launch_infos()]
+        assert on._info.arena_bytes >= twin._info.arena_bytes
+    assert on._info.arena_bytes >= default._info.arena_bytes
+    assert int(on._ovf.item()) == 0
+
+
+# ------------------------------------------------------------------------------------------ 3. backbone_gradients against autograd
+def _backbone_trainer(tmp_path, text, res, precision, width=None, name="m", trainable="backbone", options=BACKBONE):
+    m = _model(tmp_path, text, res, precision, options, name=name)
+    if width is not None:
+        m.input_width = width
+    t = T.DarknetTrainer(m, trainable=trainable)
+    t.min_box_size = 4
+    return m, t
+
+
+def _cpu_graph(m, t, B, dtype, weights=None, masks=None, cut=None):
+    """The trainable sub-graph on the CPU in ``dtype`` from the module's parameters: conv (stride 1 or 2) -> eval BatchNorm -> leaky
+    (written as a product with ``masks[layer]``, the DEVICE's, where given; else torch's leaky_relu), shortcuts, routes, F.interpolate,
+    head convs; fed the device's boundary inputs (read_layer of the layers the graph reads from outside: layer 0).  ``weights``:
+    {conv: weight} in place of the module's; ``cut = (producer, reader)``: that reader sees the producer's value detached.
+    Returns (values per layer, {conv: leaf weight}, {conv: (pre-activation, input)})."""
+    layers, readers, member, scales = t._graph("backbone")
+    cast = lambda a: torch.as_tensor(a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)).to(dtype)
+    val, leaves, pres = {}, {}, {}
+
+    def value(src, reader):
+        if src not in val:
+            assert not member[src]
+            val[src] = cast(m.read_layer(src, B))
+        return val[src].detach() if cut == (src, reader) else val[src]
+
+    for L in layers:
+        i = L.index
+        if not member[i]:
+            continue
+        if L.type == "convolutional":
+            conv, x = _conv_of(m, i), value(i - 1, i)
+            W = cast(conv.weight if weights is None or i not in weights else weights[i])
+            if i in scales:
+                W.requires_grad_(True)
+                leaves[i] = W
+                bn = _bn_of(m, i)
+                pre = fn.batch_norm(fn.conv2d(x, W, stride=L.stride, padding=L.size // 2), cast(bn.running_mean), cast(bn.running_var), cast(bn.weight), cast(bn.bias),
+                                    False, 0.0, 1e-5)
+                pres[i] = (pre, x)
+                val[i] = pre if not L.leaky else pre * cast(masks[i]) if masks is not None else fn.leaky_relu(pre, 0.1)
+            else:
+                val[i] = fn.conv2d(x, W, cast(conv.bias))
+        elif L.type == "upsample":
+            x = value(i - 1, i)
+            val[i] = fn.interpolate(x, scale_factor=2, mode="nearest") if L.nearest else fn.interpolate(x, scale_factor=2, mode="bilinear", align_corners=False)
+        elif L.type == "shortcut":
+            val[i] = value(L.srcs[0], i) + value(L.srcs[1], i)
+        else:
+            parts, off = [], 0
+            for s in L.srcs:
+                parts.append(value(s, i) if member[s] else cast(m.read_layer(i, B))[:, off:off + layers[s].cout])
+                off += layers[s].cout
+            val[i] = torch.cat(parts, 1)
+    return val, leaves, pres
+
+
+def _cpu_graph_grads(m, t, B, dtype, masks, dzs, cut=None):
+    val, leaves, pres = _cpu_graph(m, t, B, dtype, masks=masks, cut=cut)
+    total = sum((val[head] * dz.detach().cpu().to(dtype)).sum() for (head, _), dz in zip(m.head_layers(), dzs))
+    total.backward()
+    return {i: W.grad.numpy().astype(np.float64) for i, W in leaves.items()}, pres
+
+
+def _tenth_heads(m):
+    for head, _ in m.head_layers():                                   # a tenth of the synthetic head weights: sigmoids that do not saturate
+        m.update_conv(head, _conv_of(m, head).weight.detach() * 0.1, _conv_of(m, head).bias.detach() * 0.1)
+
+
+@pytest.mark.parametrize("precision,width", [("fp32", None), ("f16s3", None), ("fp32", 96)])
+def test_backbone_gradients_against_autograd(tmp_path, precision, width):
+    """dW of DarknetTrainer.backbone_gradients for all 14 trainable convs of mini_cfg against torch autograd of the whole trainable
+    sub-graph (_cpu_graph: layers 1-22) with the DEVICE's masks, fed the device's boundary input (read_layer(0)) and pulled back from
+    the device's dz, once in float64 (the truth) and once in float32 torch (the reference's own arithmetic, the floor).
+
+    The masks: a flip of the device's mask against the float64 forward's pre-activation is legitimate only where |pre_64| is within
+    the forward's own error, (K1 + 2) u (sum |w s| |x| + |bias|) at fp32 and 1e-4 (f16s3) of that mass — the rule of
+    test_neck_gradients_against_autograd, unchanged.
+
+    The gate per conv: rms and max of (dW_dev - dW_64) / max |dW_64| are at most 4 x the same figures of (dW_32 - dW_64), the
+    project's 4 x the float32 floor.
+
+    Fan-out (fp32 64): mini has readers[1] == [2, 4], readers[5] == [6, 8], readers[10] == [11, 19]; cutting either reader in the
+    float64 model changes dW of every trainable conv at or below the producer and of no other.
+
+    Measured on an MI355X, rms ratio / max ratio per conv (one mask flipped: f16s3 conv 21, inside its gate):
+      conv             1          2          3          5          6          7          9          10         11         12         13         17         20         21
+      64 fp32      1.08/1.18  1.03/0.90  1.03/0.86  0.96/0.76  1.12/2.12  0.91/0.54  1.09/1.55  1.23/0.82  1.39/1.61  1.33/1.51  1.13/1.26  1.20/1.42  1.27/1.36  1.09/1.58
+      64 f16s3     1.14/1.25  0.94/0.67  1.13/1.05  0.94/0.61  1.23/1.71  1.00/0.91  1.13/1.07  1.27/0.92  1.54/2.01  1.86/3.07  1.76/1.58  1.83/3.00  1.61/2.02  1.47/1.65
+      64x96 fp32   0.86/0.79  1.07/1.21  0.93/0.92  0.74/0.57  1.07/1.35  0.83/0.65  1.14/1.02  1.16/1.54  1.34/1.72  1.37/1.72  1.11/1.33  1.18/1.38  1.14/1.08  0.94/0.68
+    The stride-2 convs (1, 5, 9, 10, 11) and everything behind the stride-2 data gradients sit where the stride-1 layers do."""
+    res, B = 64, 3
+    text = cfgs.mini_cfg(res, width or res)
+    m, t = _backbone_trainer(tmp_path, text, res, precision, width)
+    xd = _frames(B, res, width)
+    bnd = [torch.from_numpy(im) for im in step_batch()[1]]
+    _forward(m, xd)
+    _tenth_heads(m)
+    loss, head_grads, grads = t.backbone_gradients(xd, bnd)
+    want_layers = TRAINABLE["mini"]
+    assert m.active_precision == precision and int(t.status.item()) == 0 and sorted(grads) == want_layers == [c for c, _ in m.trainable_layers()]
+    loss2, _, again = t.backbone_gradients(xd, bnd)                   # twice the same bytes; the heads' part is head_gradients
+    assert _same(loss, loss2) and all(_same(grads[k], again[k]) for k in grads)
+    loss_h, grads_h = t.head_gradients(xd, bnd)
+    assert _same(loss, loss_h) and all(_same(head_grads[k][0], grads_h[k][0]) and _same(head_grads[k][1], grads_h[k][1]) for k in grads_h)
+    layers, readers, member, scales = t._graph("backbone")
+    assert sorted(scales) == want_layers and all(member[i] for i in range(1, 23) if layers[i].type != "yolo") and not member[0]
+    masks = {c: np.where(m.read_layer(c, B).cpu().numpy() > 0, 1.0, 0.1) for c in want_layers if layers[c].leaky}
+    dzs = T.yolo_loss_grad_async(t._forward_train(xd), bnd, t.heads, t.num_classes, t.min_box_size)["grad_raw"]
+    want, pres = _cpu_graph_grads(m, t, B, torch.float64, masks, dzs)
+    floor, _ = _cpu_graph_grads(m, t, B, torch.float32, masks, dzs)
+    over = []
+    for c in want_layers:
+        conv, bn, L = _conv_of(m, c), _bn_of(m, c), layers[c]
+        pre, x = (a.detach() for a in pres[c])
+        gamma, beta, mean, var = (_t64(v) for v in (bn.weight, bn.bias, bn.running_mean, bn.running_var))
+        s = (gamma / torch.sqrt(var + 1e-5))
+        mass = fn.conv2d(x.abs(), (_t64(conv.weight) * s[:, None, None, None]).abs(), stride=L.stride, padding=L.size // 2).numpy() + \
+            np.abs((beta - mean * s).numpy())[None, :, None, None]
+        gate = ((conv.in_channels * L.size * L.size + 2) * U if GATES[precision] is None else GATES[precision]) * mass
+        y_dev = m.read_layer(c, B).cpu().numpy()
+        flips = (pre.numpy() > 0) != (y_dev > 0)
+        assert (np.abs(pre.numpy())[flips] <= gate[flips]).all(), (precision, c, int(flips.sum()))
+        got, ref = grads[c].cpu().numpy().astype(np.float64), np.abs(want[c]).max()
+        assert got.shape == want[c].shape and ref > 0
+        e_dev, e_32 = (got - want[c]) / ref, (floor[c] - want[c]) / ref
+        rms = lambda e: float(np.sqrt(np.mean(e * e)))
+        print("mini %s%s conv %d (stride %d, %d flips): rms %.3g (float32 floor %.3g, ratio %.2f)  max %.3g (floor %.3g, ratio %.2f)" % (
+            precision, "" if width is None else " 64x%d" % width, c, L.stride, int(flips.sum()), rms(e_dev), rms(e_32), rms(e_dev) / rms(e_32),
+            np.abs(e_dev).max(), np.abs(e_32).max(), np.abs(e_dev).max() / np.abs(e_32).max()))
+        if not (rms(e_dev) <= 4 * rms(e_32) and np.abs(e_dev).max() <= 4 * np.abs(e_32).max()):
+            over.append((c, round(rms(e_dev) / rms(e_32), 2), round(float(np.abs(e_dev).max() / np.abs(e_32).max()), 2)))
+    if precision == "fp32" and width is None:                         # the fan-out sums
+        assert readers[1] == [2, 4] and readers[5] == [6, 8] and readers[10] == [11, 19]
+        for producer in (1, 5, 10):
+            for reader in readers[producer]:
+                part, _ = _cpu_graph_grads(m, t, B, torch.float64, masks, dzs, cut=(producer, reader))
+                for c in want_layers:
+                    if c <= producer:
+                        assert not np.allclose(part[c], want[c], rtol=1e-3, atol=1e-6 * np.abs(want[c]).max()), (producer, reader, c)
+                    else:
+                        assert np.array_equal(part[c], want[c]), (producer, reader, c)
+    assert not over, (precision, width, "(conv, rms ratio, max ratio) over 4 x the float32 floor", over)            # after every figure is printed
+
+
+# ------------------------------------------------------------------------------------------ 4. the same bits as the neck
+@pytest.mark.parametrize("precision", ["fp32", "f16s3"])
+def test_backbone_gradients_hold_the_bits_of_neck_gradients(tmp_path, precision):
+    """The neck entries of backbone_gradients equal neck_gradients of a trainable="neck" trainer on a plan with the three fusions off
+    (fp32), and the losses are equal.  f16s3: that plan is refused by the library (no split-format add without the option), so the neck
+    trainer runs on a plan with the option, which keep_neck_activations' walk accepts as a superset."""
+    text = cfgs.mini_cfg(64, 64)
+    xd, bnd = _frames(3, 64, None), [torch.from_numpy(im) for im in step_batch()[1]]
+    m, t = _backbone_trainer(tmp_path, text, 64, precision)
+    neck_options = dict(UNFUSED, keep_head_inputs=1, keep_neck_activations=1) if precision == "fp32" else BACKBONE
+    mn, tn = _backbone_trainer(tmp_path, text, 64, precision, name="neck", trainable="neck", options=neck_options)
+    for model in (m, mn):
+        _forward(model, xd)
+        _tenth_heads(model)
+    loss, hg, grads = t.backbone_gradients(xd, bnd)
+    loss_n, hg_n, neck = tn.neck_gradients(xd, bnd)
+    assert sorted(neck) == NECK["mini"] and _same(loss, loss_n)
+    assert all(_same(grads[k], neck[k]) for k in neck) and all(_same(hg[k][0], hg_n[k][0]) and _same(hg[k][1], hg_n[k][1]) for k in hg_n)
+
+
+# ------------------------------------------------------------------------------------------ 5. the directional derivative
+def test_the_loss_falls_along_the_backbone_gradient_by_what_it_says(tmp_path):
+    """The central difference of the device loss along -g, all 14 trainable convs of mini_cfg(64, 64) moved together by
+    update_conv_weight, against ||g||^2 of backbone_gradients (fp32 plan, the batch of step_batch).  eps and the allowed gap come from
+    the float64 CPU model of the sub-graph on the device's boundary input with torch's own leaky_relu, never from a device result,
+    exactly as test_the_loss_falls_along_the_neck_gradient_by_what_it_says derives them: eps is the smallest of 1e-2, 3e-3, ... at which
+    the modelled truncation gap still exceeds the float32 evaluation noise tenfold, and the test allows
+    4 * |fd_cpu - dd_cpu| + 2 * noise / (2 eps), dd_cpu the model's central difference at a tenth of eps."""
+    B = 3
+    m, t = _backbone_trainer(tmp_path, cfgs.mini_cfg(64, 64), 64, "fp32")
+    x, images = step_batch()
+    xd, bnd = torch.from_numpy(x).cuda(), [torch.from_numpy(im) for im in images]
+    _, _, grads = t.backbone_gradients(xd, bnd)
+    l0 = float(t.last_components[0].item())
+    assert sorted(grads) == TRAINABLE["mini"]
+    g2 = sum(float((dw.double() ** 2).sum()) for dw in grads.values())
+    W0 = {c: _conv_of(m, c).weight.detach().clone() for c in grads}
+    heads = [h for h, _ in m.head_layers()]
+
+    def cpu(s, dtype=torch.float64):
+        with torch.no_grad():
+            val, _, _ = _cpu_graph(m, t, B, dtype, weights={c: W0[c].double() + s * grads[c].cpu().double() for c in grads})
+        val = {k: v.detach() for k, v in val.items()}
+        acts = [val[h - 1].numpy() for h in heads]
+        ws = [_t64(_conv_of(m, h).weight).numpy() for h in heads]
+        bs = [_t64(_conv_of(m, h).bias).numpy() for h in heads]
+        if dtype != torch.float64:
+            ws, bs = [a.astype(F) for a in ws], [a.astype(F) for a in bs]
+        return cpu_head_model(acts, ws, bs, t.heads, images, 4, None if dtype == torch.float64 else dtype)["loss"]
+    noise_at = lambda s: abs(cpu(s, torch.float32) - cpu(s))
+    noise = noise_at(0.0)
+    eps = gap_cpu = None
+    for e in (1e-2, 3e-3, 1e-3, 3e-4, 1e-4, 3e-5, 1e-5, 3e-6, 1e-6, 3e-7, 1e-7):
+        fd, dd = (cpu(e) - cpu(-e)) / (2 * e), (cpu(e / 10) - cpu(-e / 10)) / (2 * e / 10)
+        if abs(fd - dd) >= 10 * noise / e:
+            eps, gap_cpu = e, abs(fd - dd)
+    assert eps is not None
+    noise = max(noise, noise_at(eps), noise_at(-eps))
+    allowed = 4 * gap_cpu + 2 * noise / (2 * eps)
+    masters = {c: W0[c].cuda() for c in grads}
+
+    def loss_at(s):
+        for c in grads:
+            m.update_conv_weight(c, masters[c] + s * grads[c])
+        t.forward_loss(xd, bnd)
+        return float(t.last_components[0].item())
+    fd_dev = (loss_at(eps) - loss_at(-eps)) / (2 * eps)
+    assert loss_at(0.0) == l0                                         # the weights are back, bit for bit
+    print("||g||^2 device %.8g; eps %.0e; central difference device %.8g; gap %.4g, allowed %.4g (cpu gap %.4g, noise %.4g)" % (g2, eps, fd_dev, abs(fd_dev - g2), allowed, gap_cpu, noise))
+    assert g2 > 0 and abs(fd_dev - g2) <= allowed
+
+
+# ------------------------------------------------------------------------------------------ 6. the training step
+@pytest.mark.parametrize("precision,width", [("fp32", None), ("f16s3", None), ("f16s3", 96)])
+def test_training_step_on_the_backbone(tmp_path, precision, width):
+    """feed_forward_through_model(trainable="backbone"), an SGD step and then two Adam steps: after each, the masters and moments of both
+    heads and of all 14 trainable convs equal block_grad_cases.opt_update_f32 of the gradients backbone_gradients returned for the state
+    before the step, and the packed image, as uint32 words, equals the host pack of the synchronised parameters — the stride-2 convs 1,
+    5, 9, 10 and 11 included.  The loss of the next forward differs from the first."""
+    text = cfgs.mini_cfg(64, width or 64)
+    xd, bnd = _frames(3, 64, width), [torch.from_numpy(im) for im in step_batch()[1]]
+    m, t = _backbone_trainer(tmp_path, text, 64, precision, width)
+    layers = sorted(TRAINABLE["mini"] + HEADS)
+    assert set(MINI_S2) <= set(layers)
+    losses = []
+    host = lambda a: None if a is None else a.detach().cpu().numpy()
+    for step, kind in enumerate(["sgd", "adam", "adam"]):
+        if step < 2:
+            t.optimizer = HeadOptimizer(kind, lr=1e-4)
+        _, hg, ng = t.backbone_gradients(xd, bnd)
+        grads = {k: (host(dw), host(db)) for k, (dw, db) in hg.items()}
+        grads.update({k: (host(dw), None) for k, dw in ng.items()})
+        assert sorted(grads) == layers
+        masters = t._masters(grads, xd.device)
+        before = {k: (host(masters[k][0]), host(masters[k][1])) for k in layers}
+        state = {k: {n: host(v) for n, v in t.optimizer.state.get(k, {}).items() if n.startswith("exp_avg")} for k in layers}
+        losses.append(float(t.feed_forward_through_model(xd, bnd)))
+        for k in layers:
+            st = t.optimizer.state[k]
+            assert st["step"] == (1 if step < 2 else 2) and st["weight"] is t._head_masters[k][0]
+            for which, name, sfx in ((0, "weight", ""), (1, "bias", "_bias")):
+                if before[k][which] is None:
+                    assert which == 1 and "bias" not in st and k in TRAINABLE["mini"]
+                    continue
+                zero = np.zeros_like(before[k][which])
+                w1, m1, v1 = opt_update_f32(kind, before[k][which], grads[k][which], state[k].get("exp_avg" + sfx, zero), state[k].get("exp_avg_sq" + sfx, zero),
+                                            1e-4, step=st["step"])
+                assert np.array_equal(bits(host(st[name])), bits(w1)), (precision, step, k, name)
+                if kind == "adam":
+                    assert np.array_equal(bits(host(st["exp_avg" + sfx])), bits(m1)) and np.array_equal(bits(host(st["exp_avg_sq" + sfx])), bits(v1)), (precision, step, k, name)
+        image = m.packed_weights()
+        stream = m.weight_stream().copy()                             # synchronises the masters into the module's parameters
+        assert all(_same(_conv_of(m, c).weight, t._head_masters[c][0]) for c in MINI_S2) and np.array_equal(image, pack(m._plan, stream)), (precision, step)
+    assert losses[1] != losses[0] and np.isfinite(losses).all(), losses
