@@ -487,21 +487,10 @@ int rtod_upsample2x_grad(const float* dz_dev, const float* y_dev, float slope, i
     RTOD_GUARD_END
 }
 
-int rtod_plan_neck_layers(const rtod_plan* plan, int* conv_layers, int* input_layers, int capacity) {
-    if (!plan || capacity < 0 || (capacity > 0 && (!conv_layers || !input_layers))) { set_error("plan_neck_layers: bad args"); return RTOD_E_ARG; }
-    const std::vector<char> neck = plan->p.neck_graph();
-    int n = 0;
-    for (const auto& L : plan->p.layers) {
-        if (L.type != LT_CONV || !L.bn || !neck[L.index]) continue;
-        if (n < capacity) { conv_layers[n] = L.index; input_layers[n] = L.index - 1; }
-        ++n;
-    }
-    return n;
-}
-
-int rtod_plan_trainable_layers(const rtod_plan* plan, int* conv_layers, int* input_layers, int capacity) {
-    if (!plan || capacity < 0 || (capacity > 0 && (!conv_layers || !input_layers))) { set_error("plan_trainable_layers: bad args"); return RTOD_E_ARG; }
-    const std::vector<char> graph = plan->p.train_graph();
+// The BatchNorm convs of one graph of the plan and the layer each reads, ascending
+static int list_scope_convs(const char* who, const rtod_plan* plan, Scope scope, int* conv_layers, int* input_layers, int capacity) {
+    if (!plan || capacity < 0 || (capacity > 0 && (!conv_layers || !input_layers))) { set_error("%s: bad args", who); return RTOD_E_ARG; }
+    const std::vector<char> graph = plan->p.scope_graph(scope);
     int n = 0;
     for (const auto& L : plan->p.layers) {
         if (L.type != LT_CONV || !L.bn || !graph[L.index]) continue;
@@ -509,6 +498,14 @@ int rtod_plan_trainable_layers(const rtod_plan* plan, int* conv_layers, int* inp
         ++n;
     }
     return n;
+}
+
+int rtod_plan_neck_layers(const rtod_plan* plan, int* conv_layers, int* input_layers, int capacity) {
+    return list_scope_convs("plan_neck_layers", plan, SCOPE_NECK, conv_layers, input_layers, capacity);
+}
+
+int rtod_plan_trainable_layers(const rtod_plan* plan, int* conv_layers, int* input_layers, int capacity) {
+    return list_scope_convs("plan_trainable_layers", plan, SCOPE_BACKBONE, conv_layers, input_layers, capacity);
 }
 
 int rtod_plan_head_blocks(const rtod_plan* plan, int* head_conv_layers, int* block_conv_layers, int* block_input_layers, int capacity) {

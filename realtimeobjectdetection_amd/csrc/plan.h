@@ -92,6 +92,10 @@ struct PackedConv {
     int ks_chunks = 0;                // split, option k_slices_split: sliced layer (slices of this many K-chunks), runs on conv_ks_f16s3 only; 0: not sliced
 };
 
+// What a plan can train with BatchNorm frozen, narrowest first: the conv in front of each head conv, the neck, everything but layer 0.
+// Options keep_block_inputs / keep_neck_activations / keep_backbone_activations keep the activations of one each (Plan::kept_scope)
+enum Scope { SCOPE_NONE = 0, SCOPE_BLOCKS, SCOPE_NECK, SCOPE_BACKBONE };
+
 // One struct, defined over five files by concern (the run-time fused form of every launch is decided in one place, Plan::form in plan_forward.cpp): plan_cfg.cpp (parse, resolve_shapes: no HIP call), plan_build.cpp (options, buffer
 // planning, weight layout, describe), plan_weights.cpp (pack_conv, pack_weights, load_weights; repack_conv under update_conv / update_conv_weight, step_packed under step_conv / step_conv_folded), plan_tiles.cpp (which kernel variant a conv
 // launch runs, autotune), plan_forward.cpp (the launch list on a stream, launch records).
@@ -147,9 +151,9 @@ struct Plan {
                                       // the activations of rtod_conv1x1_wgrad); liveness only: launches, tiles and output bits are unchanged
     bool opt_keep_block_inputs = false; // ... and the buffer every BLOCK conv reads (block_shape_ok: the BatchNorm conv a head conv reads): the activations of
                                       // rtod_conv_wgrad.  Liveness only as well; the frozen BatchNorm scales then also live on the device (d_block_scale)
-    bool opt_keep_neck_activations = false; // ... and every buffer a NECK conv (neck_graph) or a head conv reads or writes: the activations of the walk behind the
+    bool opt_keep_neck_activations = false; // ... and every buffer a NECK conv (scope_graph) or a head conv reads or writes: the activations of the walk behind the
                                       // backbone (rtod_conv_dgrad, rtod_upsample2x_grad, rtod_conv_wgrad).  Liveness only; the scales of all neck convs on the device
-    bool opt_keep_backbone_activations = false; // a superset of keep_neck_activations over the TRAINABLE convs (train_graph: stride-2 convs and shortcuts too).  Not
+    bool opt_keep_backbone_activations = false; // a superset of keep_neck_activations over the TRAINABLE convs (scope_graph: stride-2 convs and shortcuts too).  Not
                                       // liveness only: the plan then forms no fusion that hides a trainable conv (fusions_held, next to form)
     bool opt_fuse_stem_pool = true;   // ... with the 2x2 / stride-2 max-pool that follows it in the same kernel where the plan allows it (off: A/B and tests)
     int opt_force_f16s3_variant = -1; // >= 0: tile variant for every split-f16 conv (>= BAND_VARIANT_BASE: band layers)
@@ -189,16 +193,16 @@ struct Plan {
     // the detection neck (rtod_plan_neck_layers): the largest set of traversable layers (head convs, block-shaped BatchNorm convs that pass
     // block_plan_ok, routes, 2x upsamples) closed downstream: every reader of a member is a member or a [yolo] layer
     std::vector<std::vector<int>> consumers() const;                                // the readers of every layer's output, ascending
-    std::vector<char> neck_graph() const;                                           // membership per layer
-    std::vector<char> closed_graph(bool backbone) const;                            // the closure under neck_graph and train_graph (backbone: the two more kinds)
-    bool neck_conv(int layer) const;                                                // a BatchNorm conv of the neck
-    // the trainable graph (rtod_plan_trainable_layers): neck_graph's closure rule with two more traversable kinds, a block-shaped conv
+    std::vector<char> scope_graph(Scope scope) const;                               // membership per layer of the neck (SCOPE_NECK) or of the trainable graph
+                                                                                    // (SCOPE_BACKBONE: the two more kinds); no member below SCOPE_NECK
+    // the trainable graph (rtod_plan_trainable_layers): the neck's closure rule with two more traversable kinds, a block-shaped conv
     // that is 3x3 / stride 2 / pad 1 instead of stride 1, and a two-source linear [shortcut]
     bool train_shape_ok(int layer) const;                                           // block_shape_ok, or block_shape_ok but for that stride
-    std::vector<char> train_graph() const;                                          // membership per layer
-    bool train_conv(int layer) const;                                               // a BatchNorm conv of the trainable graph
-    bool trains_folded(int layer) const;                                            // what block_conv accepts: a block conv; with keep_neck_activations any neck conv;
-                                                                                    // with keep_backbone_activations any trainable conv
+    Scope kept_scope() const {                                                      // the widest scope whose activations the options keep: decided here alone
+        return opt_keep_backbone_activations ? SCOPE_BACKBONE : opt_keep_neck_activations ? SCOPE_NECK : opt_keep_block_inputs ? SCOPE_BLOCKS : SCOPE_NONE;
+    }
+    bool trains_folded(int layer, const std::vector<char>& kept) const;             // what block_conv accepts: a block conv on every plan, and every BatchNorm conv of
+    bool trains_folded(int layer) const;                                            // kept = scope_graph(kept_scope()) (load_weights asks that graph once for all layers)
     int block_conv(const char* who, int layer, size_t& slot) const;                 // the slot of a block conv, or why `layer` is none
     int update_conv_weight(int layer, const float* weight_oihw);                    // re-pack and upload one block conv, BatchNorm as loaded (rtod_plan_update_conv_weight)
     int step_conv_folded(int layer, const rtod_opt_step* opt, float* weight, const float* dw, float* m_w, float* v_w, hipStream_t s);   // rtod_plan_step_conv_folded

@@ -312,8 +312,8 @@ int Plan::plan_buffers() {
     // option keep_neck_activations: what every neck conv and every head conv reads and writes (the walk reads outputs for the
     // activation masks, inputs for the weight gradients; routes are kept as their concat buffers)
     // option keep_backbone_activations: the same over the trainable graph, which contains the neck
-    if (opt_keep_neck_activations || opt_keep_backbone_activations) {
-        const std::vector<char> neck = opt_keep_backbone_activations ? train_graph() : neck_graph();
+    if (kept_scope() >= SCOPE_NECK) {
+        const std::vector<char> neck = scope_graph(kept_scope());
         for (const auto& l : launches)
             if (l.kind == LK_CONV && (neck[l.layer] || feeds_yolo(l.layer))) {
                 touch(buf_of_layer(l.in_layer), n);
@@ -361,12 +361,9 @@ int Plan::block_of_head(int head) const {
 // conv that is a block by both parts of the definition above, a route, a 2x upsample.  A layer is in the graph if it is traversable
 // and every reader of its output is in the graph or a [yolo] layer; readers have higher indices, so one descending pass decides it.
 // Closure is what makes the gradients exact: nothing outside the graph lies between a member and the loss.
-std::vector<char> Plan::neck_graph() const { return closed_graph(false); }
-
-// The trainable graph: the same closure with the two operations Darknet-53's backbone consists of, the 3x3 / stride-2 conv and the
-// residual [shortcut] (two sources, linear: it adds and carries no mask of its own).  A superset of the neck on every plan
-std::vector<char> Plan::train_graph() const { return closed_graph(true); }
-
+//
+// The trainable graph (SCOPE_BACKBONE): the same closure with the two operations Darknet-53's backbone consists of, the 3x3 / stride-2
+// conv and the residual [shortcut] (two sources, linear: it adds and carries no mask of its own).  A superset of the neck on every plan
 bool Plan::train_shape_ok(int layer) const {
     if (block_shape_ok(layer)) return true;
     if (layer < 1 || layer >= (int)layers.size() || opt_bn_batch_stats) return false;
@@ -374,10 +371,12 @@ bool Plan::train_shape_ok(int layer) const {
     return L.type == LT_CONV && L.bn && L.size == 3 && L.stride == 2 && L.pad == 1 && L.act <= 1 && L.cin % 32 == 0 && L.fused_into < 0;
 }
 
-std::vector<char> Plan::closed_graph(bool backbone) const {
+std::vector<char> Plan::scope_graph(Scope scope) const {
     const int n = (int)layers.size();
-    const std::vector<std::vector<int>> cons = consumers();
     std::vector<char> in(n, 0);
+    if (scope < SCOPE_NECK) return in;
+    const bool backbone = scope == SCOPE_BACKBONE;
+    const std::vector<std::vector<int>> cons = consumers();
     for (int i = n - 1; i >= 0; --i) {
         const Layer& L = layers[i];
         bool ok = !cons[i].empty();
@@ -394,17 +393,12 @@ std::vector<char> Plan::closed_graph(bool backbone) const {
     return in;
 }
 
-bool Plan::train_conv(int layer) const {
-    return layer >= 0 && layer < (int)layers.size() && layers[layer].type == LT_CONV && layers[layer].bn && train_graph()[layer];
+// A block stays a block on every plan; the kept graph adds its BatchNorm convs
+bool Plan::trains_folded(int layer, const std::vector<char>& kept) const {
+    return block_of_head(layer + 1) == layer || (layer >= 0 && layer < (int)layers.size() && layers[layer].type == LT_CONV && layers[layer].bn && kept[layer]);
 }
 
-bool Plan::neck_conv(int layer) const {
-    return layer >= 0 && layer < (int)layers.size() && layers[layer].type == LT_CONV && layers[layer].bn && neck_graph()[layer];
-}
-
-bool Plan::trains_folded(int layer) const {
-    return block_of_head(layer + 1) == layer || (opt_keep_neck_activations && neck_conv(layer)) || (opt_keep_backbone_activations && train_conv(layer));
-}
+bool Plan::trains_folded(int layer) const { return trains_folded(layer, scope_graph(kept_scope())); }
 
 bool Plan::uses_split(const Layer& L) const {
     return precision >= 1 && L.index > 0;      // layer 0 stays on an exact-fp32 kernel and writes the split format

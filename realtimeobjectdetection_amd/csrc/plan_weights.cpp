@@ -201,7 +201,7 @@ int Plan::step_conv(int layer, const rtod_opt_step* opt, float* weight, float* b
 int Plan::step_packed(const char* who, size_t slot, const rtod_opt_step* opt, bool moments, bool folded, HeadStepLaunch& h, hipStream_t s) {
     if (int rc = opt_scalars(who, opt, moments, h)) return rc;
     if (!weights_loaded || !d_weights) { set_error("%s: call rtod_plan_load_weights first", who); return RTOD_E_STATE; }
-    if (folded && !d_block_scale) { set_error("%s: the plan needs option keep_block_inputs, keep_neck_activations or keep_backbone_activations (they put the frozen scales on the device)", who); return RTOD_E_STATE; }
+    if (folded && (kept_scope() == SCOPE_NONE || !d_block_scale)) { set_error("%s: the plan needs option keep_block_inputs, keep_neck_activations or keep_backbone_activations (they put the frozen scales on the device)", who); return RTOD_E_STATE; }
     const PackedConv& pc = convs[slot];
     const Layer& L = layers[pc.layer];
     h.cout = L.cout; h.cin = L.cin; h.taps = L.size * L.size; h.cin_p = pc.cin_p; h.split = pc.split ? 1 : 0; h.Kpad = pc.Kpad; h.Npad = pc.Npad;
@@ -243,18 +243,23 @@ int Plan::block_conv(const char* who, int layer, size_t& slot) const {
     ConvSite cs;
     if (int rc = conv_site(who, layer, cs)) return rc;
     if (!layers[layer].bn) { set_error("%s: layer %d has no BatchNorm (rtod_plan_update_conv / rtod_plan_step_conv take such convs)", who, layer); return RTOD_E_ARG; }
-    if (!trains_folded(layer)) {                                     // a block; on a plan with option keep_neck_activations any neck conv
+    if (!trains_folded(layer)) {
+        // per kept scope: what the plan trains, the shape such a conv has, and what else keeps a conv of that shape out
+        static const struct { const char* what; const char* shape; const char* closure; } kText[] = {
+            {"detection block", "not the 1x1 / 3x3 stride-1 leaky or linear BatchNorm conv that a detection-head conv reads", nullptr},
+            {"detection block", "not the 1x1 / 3x3 stride-1 leaky or linear BatchNorm conv that a detection-head conv reads", nullptr},
+            {"neck conv", "not a 1x1 / 3x3 stride-1 same-padding leaky or linear BatchNorm conv that reads a multiple of 32 channels",
+             "a layer outside the neck reads its output, or the plan computes it inside another layer's kernel"},
+            {"trainable conv", "not a 1x1 / 3x3 stride-1 or 3x3 stride-2 same-padding leaky or linear BatchNorm conv that reads a multiple of 32 channels",
+             "a layer outside the trainable graph reads its output, or the plan computes it inside another layer's kernel"}};
+        const Scope kept = kept_scope();
+        const bool shape_ok = kept == SCOPE_BACKBONE ? train_shape_ok(layer) : kept == SCOPE_NECK && block_shape_ok(layer);
         const PackedConv* pc = cs.slot >= 0 ? &convs[cs.slot] : nullptr;
         const char* why = opt_bn_batch_stats ? "the plan runs batch-statistics BatchNorm: the conv is not folded"
                         : pc && (pc->stem || pc->stem16) ? "a stem layout" : pc && pc->narrow ? "a narrow (Cin == 16) layout"
                         : cs.pair ? "part of a fused pointwise pair"
-                        : opt_keep_backbone_activations ? (!train_shape_ok(layer)
-                              ? "not a 1x1 / 3x3 stride-1 or 3x3 stride-2 same-padding leaky or linear BatchNorm conv that reads a multiple of 32 channels"
-                              : "a layer outside the trainable graph reads its output, or the plan computes it inside another layer's kernel")
-                        : !opt_keep_neck_activations ? "not the 1x1 / 3x3 stride-1 leaky or linear BatchNorm conv that a detection-head conv reads"
-                        : !block_shape_ok(layer) ? "not a 1x1 / 3x3 stride-1 same-padding leaky or linear BatchNorm conv that reads a multiple of 32 channels"
-                        : "a layer outside the neck reads its output, or the plan computes it inside another layer's kernel";
-        set_error("%s: layer %d is not a %s (%s)", who, layer, opt_keep_backbone_activations ? "trainable conv" : opt_keep_neck_activations ? "neck conv" : "detection block", why);
+                        : shape_ok ? kText[kept].closure : kText[kept].shape;
+        set_error("%s: layer %d is not a %s (%s)", who, layer, kText[kept].what, why);
         return RTOD_E_ARG;
     }
     slot = (size_t)cs.slot;                                          // block_of_head found it: a block has packed weights
@@ -347,8 +352,9 @@ int Plan::load_weights(const float* w, size_t n) {
     // scale pack_conv folded, on the host; with option keep_block_inputs on the device too, so that a later step allocates nothing
     block_bn.clear(); block_scale.clear(); block_scale_off.clear();
     std::vector<double> scales;
-    for (const auto& L : layers) {                                    // (option keep_neck_activations: of every neck conv, the blocks among them)
-        if (L.type != LT_CONV || !trains_folded(L.index)) continue;
+    const std::vector<char> kept = scope_graph(kept_scope());         // (of every conv of the kept graph, the blocks among them)
+    for (const auto& L : layers) {
+        if (L.type != LT_CONV || !trains_folded(L.index, kept)) continue;
         const int blk = L.index;
         const int C = layers[blk].cout;
         const float* p = w + layers[blk].w_off;
@@ -359,7 +365,7 @@ int Plan::load_weights(const float* w, size_t n) {
         block_scale_off[blk] = (int64_t)scales.size();
         scales.insert(scales.end(), sc.begin(), sc.end());
     }
-    if ((opt_keep_block_inputs || opt_keep_neck_activations || opt_keep_backbone_activations) && !scales.empty()) {
+    if (kept_scope() != SCOPE_NONE && !scales.empty()) {
         if ((int64_t)scales.size() > block_scale_doubles) {           // first load (a later one never has more blocks today; if it had, the buffer grows)
             if (d_block_scale) { RTOD_HIP(hipDeviceSynchronize()); RTOD_HIP(hipFree(d_block_scale)); d_block_scale = nullptr; block_scale_doubles = 0; }
             RTOD_HIP(hipMalloc((void**)&d_block_scale, sizeof(double) * scales.size()));

@@ -372,20 +372,24 @@ class Darknet(nn.Module):
         self._stepped.clear()
 
     # ------------------------------------------------------------------ detection blocks (the BatchNorm conv a head conv reads)
+    def _plan_list(self, who, entry, columns) -> list:
+        """What ``head_blocks``, ``neck_layers`` and ``trainable_layers`` share: the plan's ``entry`` asked for its count, then for
+        that many rows of ``columns`` ints."""
+        if self._plan is None:
+            raise RuntimeError("Darknet.%s: no plan yet; run a forward first" % who)
+        n = entry(self._plan, *[None] * columns, 0)
+        if n < 0:
+            _ffi.check(n)
+        arrays = [(C.c_int * max(n, 1))() for _ in range(columns)]
+        entry(self._plan, *arrays, n)
+        return list(zip(*[list(a)[:n] for a in arrays]))
+
     def head_blocks(self) -> list:
         """``[(head_conv_layer, block_conv_layer, block_input_layer)]`` per head in cfg order (rtod_plan_head_blocks): the block
         conv is the 1x1 / 3x3 stride-1 leaky or linear BatchNorm conv the head conv reads, where the plan can train it with
         BatchNorm frozen; ``(head, -1, -1)`` for a head without one.  ``read_layer(block_input_layer)`` is valid after a forward
         with options ``keep_block_inputs``.  Asks the plan, so a forward (or ``prepare``) must have run."""
-        if self._plan is None:
-            raise RuntimeError("Darknet.head_blocks: no plan yet; run a forward first")
-        lib = _ffi.lib()
-        n = lib.rtod_plan_head_blocks(self._plan, None, None, None, 0)
-        if n < 0:
-            _ffi.check(n)
-        h, b, i = (C.c_int * n)(), (C.c_int * n)(), (C.c_int * n)()
-        lib.rtod_plan_head_blocks(self._plan, h, b, i, n)
-        return list(zip(h, b, i))
+        return self._plan_list("head_blocks", _ffi.lib().rtod_plan_head_blocks, 3)
 
     def neck_layers(self) -> list:
         """``[(neck_conv_layer, input_layer)]`` in ascending order (rtod_plan_neck_layers): the BatchNorm convs behind the backbone
@@ -393,15 +397,7 @@ class Darknet(nn.Module):
         layer or a [yolo] layer.  With options ``keep_neck_activations`` their inputs and outputs are valid ``read_layer`` targets
         after a forward and ``conv_scale`` / ``update_conv_weight`` / ``step_conv_folded`` accept each of them.  Asks the plan, so
         a forward (or ``prepare``) must have run."""
-        if self._plan is None:
-            raise RuntimeError("Darknet.neck_layers: no plan yet; run a forward first")
-        lib = _ffi.lib()
-        n = lib.rtod_plan_neck_layers(self._plan, None, None, 0)
-        if n < 0:
-            _ffi.check(n)
-        c, i = (C.c_int * max(n, 1))(), (C.c_int * max(n, 1))()
-        lib.rtod_plan_neck_layers(self._plan, c, i, n)
-        return list(zip(list(c)[:n], list(i)[:n]))
+        return self._plan_list("neck_layers", _ffi.lib().rtod_plan_neck_layers, 2)
 
     def trainable_layers(self) -> list:
         """``[(conv_layer, input_layer)]`` in ascending order (rtod_plan_trainable_layers): the BatchNorm convs of the neck graph
@@ -409,20 +405,13 @@ class Darknet(nn.Module):
         conv of YOLOv3 except layer 0; on YOLOv3-tiny the neck (its backbone is max-pools).  With that option their inputs and
         outputs are valid ``read_layer`` targets after a forward and ``conv_scale`` / ``update_conv_weight`` /
         ``step_conv_folded`` accept each of them.  Asks the plan, so a forward (or ``prepare``) must have run."""
-        if self._plan is None:
-            raise RuntimeError("Darknet.trainable_layers: no plan yet; run a forward first")
-        lib = _ffi.lib()
-        n = lib.rtod_plan_trainable_layers(self._plan, None, None, 0)
-        if n < 0:
-            _ffi.check(n)
-        c, i = (C.c_int * max(n, 1))(), (C.c_int * max(n, 1))()
-        lib.rtod_plan_trainable_layers(self._plan, c, i, n)
-        return list(zip(list(c)[:n], list(i)[:n]))
+        return self._plan_list("trainable_layers", _ffi.lib().rtod_plan_trainable_layers, 2)
 
     def conv_scale(self, layer: int):
         """``(device address, host float64 array [Cout])`` of a block conv's frozen BatchNorm scale ``gamma / sqrt(var + 1e-5)`` as
         the plan folded it (rtod_plan_conv_scale); the address is what ``train.conv_wgrad_async(row_scale=...)`` takes and needs
-        options ``keep_block_inputs`` (or ``keep_neck_activations``, under which any neck conv is accepted)."""
+        options ``keep_block_inputs`` (or ``keep_neck_activations`` / ``keep_backbone_activations``, under which any neck conv / any
+        trainable conv is accepted)."""
         if not self._plan_is_current():
             raise RuntimeError("Darknet.conv_scale: no loaded plan holds the current parameters; run a forward first")
         conv = self._trained_conv("conv_scale", layer, with_bn=True)
@@ -442,7 +431,8 @@ class Darknet(nn.Module):
         float32 device master (the module's ``conv.weight``, not the folded one), updated IN PLACE from ``dw``
         (``conv_wgrad_async`` with the plan's scale) and, for Adam, ``moments = (exp_avg, exp_avg_sq)``; the same kernel folds the
         frozen BatchNorm scale and re-packs the conv's block of the plan's weight image in place.  Nothing synchronises, nothing
-        is allocated.  Needs a current plan with options ``keep_block_inputs``.  ``conv.weight`` lags behind as after ``step_conv``."""
+        is allocated.  Needs a current plan with options ``keep_block_inputs``, ``keep_neck_activations`` or ``keep_backbone_activations``
+        (the widest of them decides which convs are accepted).  ``conv.weight`` lags behind as after ``step_conv``."""
         self._step("step_conv_folded", layer, opt, weight, None, dw, None, moments, folded=True)
 
     def packed_weights(self) -> np.ndarray:

@@ -22,6 +22,9 @@ reference:
 * ``DarknetTrainer.head_step(frames_or_x, bndbox, lr)``                                     (new) ``w -= lr * dW``, ``b -= lr * db`` on the heads
 * ``DarknetTrainer.feed_forward_through_model(batch_data, bndbox)``                         train.py:412-425: forward, loss, backward, ``optimizer`` step
 * ``DarknetTrainer.optimizer`` (``HeadOptimizer``: Adam or SGD on the heads), ``sync_parameters()``    train.py:57
+* ``DarknetTrainer.gradients(frames_or_x, bndbox, scope=None)``                             (new) ``(loss, head grads, {conv_layer: dW})`` behind the heads: ONE walk
+                                                                                            (``_walk``) over the graph of ``scope`` (``_graph``); the three entries
+                                                                                            below are ``gradients`` with their scope
 * ``DarknetTrainer(model, trainable="blocks")``, ``block_gradients(frames_or_x, bndbox)``             (new) the step also trains the conv in front of
                                                                                             each head conv: ``(loss, head grads, {block_conv_layer: dW})``
 * ``DarknetTrainer(model, trainable="neck")``, ``neck_gradients(frames_or_x, bndbox)``                (new) ... and every BatchNorm conv behind the
@@ -222,27 +225,50 @@ def conv_wgrad_async(dz, x, size, row_scale=None, bias=False, stride=1):
     return _wgrad("conv_wgrad", dz, x, int(size), row_scale, bias, stride)
 
 
+def _dgrad(who, w, dz, size, row_scale, y, slope, stride=1, in_hw=None):
+    """The body of ``conv1x1_dgrad_async`` (``size`` None: rtod_conv1x1_dgrad, shape (B, Cout, Cin, pixels), no scale) and
+    ``conv_dgrad_async`` (rtod_conv_dgrad, shape (B, Cout, Cin, H, W, size); ``stride`` 2: rtod_conv_dgrad_s2, H x W the conv's INPUT
+    map): the tensor checks, the output, the launch."""
+    for t in (w, dz) + ((y,) if y is not None else ()):
+        _need_cuda(t, who)
+    k = 1 if size is None else int(size)
+    if stride not in (1, 2) or (stride == 2 and size is None):
+        raise ValueError("%s: stride must be 1 or 2, got %r" % (who, stride))
+    ok = dz.dim() == 4 and w.dim() in (2, 4) and w.size(0) == dz.size(1) and w.numel() == w.size(0) * w.size(1) * k * k and w.dtype == dz.dtype == torch.float32
+    H, W = (dz.size(2), dz.size(3)) if ok else (0, 0)
+    if ok and stride == 2:
+        if y is not None and y.dim() == 4:
+            H, W = y.size(2), y.size(3)
+        elif in_hw is not None:
+            H, W = int(in_hw[0]), int(in_hw[1])
+        else:
+            raise ValueError("%s: stride 2 needs the size of the conv's input map: pass y or in_hw=(H, W)" % who)
+        ok = H >= 1 and W >= 1 and (dz.size(2), dz.size(3)) == ((H - 1) // 2 + 1, (W - 1) // 2 + 1) and (in_hw is None or (H, W) == (int(in_hw[0]), int(in_hw[1])))
+    if ok and y is not None:
+        ok = y.dtype == torch.float32 and tuple(y.shape) == (dz.size(0), w.size(1), H, W)
+    if not ok:
+        raise ValueError("%s: expected float32 w [Cout,Cin%s], dz [B,Cout,%s] and y [B,Cin,H,W], got %s, %s and %s"
+                         % (who, "" if size is None else ",%d,%d" % (k, k), "(H-1)//2+1,(W-1)//2+1" if stride == 2 else "H,W", tuple(w.shape), tuple(dz.shape),
+                            None if y is None else tuple(y.shape)))
+    w, dz = w.contiguous(), dz.contiguous()
+    y = None if y is None else y.contiguous()
+    B, cout, cin = dz.size(0), dz.size(1), w.size(1)
+    shape = (B, cout, cin, H * W) if size is None else (B, cout, cin, H, W, k)
+    lib, dev = _ffi.lib(), dz.device
+    dx = torch.empty((B, cin, H, W), dtype=torch.float32, device=dev)
+    scale = () if size is None else (_scale_ptr(row_scale, cout, dev),)
+    with torch.cuda.device(dev):
+        _ffi.check((lib.rtod_conv1x1_dgrad if size is None else lib.rtod_conv_dgrad_s2 if stride == 2 else lib.rtod_conv_dgrad)(
+            C.c_void_p(w.data_ptr()), *scale, C.c_void_p(dz.data_ptr()), C.c_void_p(y.data_ptr()) if y is not None else None, float(slope), *shape,
+            C.c_void_p(dx.data_ptr()), _stream(dev)))
+    return dx
+
+
 def conv1x1_dgrad_async(w, dz, y=None, slope=1.0):
     """Enqueue rtod_conv1x1_dgrad: ``w`` [Cout,Cin(,1,1)], ``dz`` [B,Cout,H,W] and, for a leaky layer, ``y`` [B,Cin,H,W] (the STORED
     output of the layer the conv reads) -> ``dx`` [B,Cin,H,W] = ``m(y) * W^T dz`` with ``m = 1`` where ``y > 0`` and ``slope``
     elsewhere.  Contiguous float32 device tensors, Cin a multiple of 32; nothing synchronises."""
-    for t in (w, dz) + ((y,) if y is not None else ()):
-        _need_cuda(t, "conv1x1_dgrad")
-    ok = dz.dim() == 4 and w.dim() in (2, 4) and w.numel() == w.size(0) * w.size(1) and w.size(0) == dz.size(1) and w.dtype == dz.dtype == torch.float32
-    if ok and y is not None:
-        ok = y.dtype == torch.float32 and tuple(y.shape) == (dz.size(0), w.size(1), dz.size(2), dz.size(3))
-    if not ok:
-        raise ValueError("conv1x1_dgrad: expected float32 w [Cout,Cin], dz [B,Cout,H,W] and y [B,Cin,H,W], got %s, %s and %s"
-                         % (tuple(w.shape), tuple(dz.shape), None if y is None else tuple(y.shape)))
-    w, dz = w.contiguous(), dz.contiguous()
-    y = None if y is None else y.contiguous()
-    B, cout, cin, H, W = dz.size(0), dz.size(1), w.size(1), dz.size(2), dz.size(3)
-    dev = dz.device
-    dx = torch.empty((B, cin, H, W), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        _ffi.check(_ffi.lib().rtod_conv1x1_dgrad(C.c_void_p(w.data_ptr()), C.c_void_p(dz.data_ptr()), C.c_void_p(y.data_ptr()) if y is not None else None,
-                                                 float(slope), B, cout, cin, H * W, C.c_void_p(dx.data_ptr()), _stream(dev)))
-    return dx
+    return _dgrad("conv1x1_dgrad", w, dz, None, None, y, slope)
 
 
 def conv_dgrad_async(w, dz, size, row_scale=None, y=None, slope=1.0, stride=1, in_hw=None):
@@ -253,37 +279,7 @@ def conv_dgrad_async(w, dz, size, row_scale=None, y=None, slope=1.0, stride=1, i
     of 32; one fmaf chain per tap, the tap sums added in ascending order: an order the shape fixes; nothing synchronises.
     ``stride`` 2 (rtod_conv_dgrad_s2): a 3x3 / stride-2 / pad-1 conv, ``dz`` [B,Cout,Ho,Wo] on its output map and ``dx`` on its
     INPUT map, whose size comes from ``y``, else from ``in_hw = (H, W)``: ``Ho`` alone does not tell ``2 Ho`` from ``2 Ho - 1``."""
-    for t in (w, dz) + ((y,) if y is not None else ()):
-        _need_cuda(t, "conv_dgrad")
-    size = int(size)
-    if stride not in (1, 2):
-        raise ValueError("conv_dgrad: stride must be 1 or 2, got %r" % (stride,))
-    ok = dz.dim() == 4 and w.dim() in (2, 4) and w.size(0) == dz.size(1) and w.numel() == w.size(0) * w.size(1) * size * size and w.dtype == dz.dtype == torch.float32
-    H, W = (dz.size(2), dz.size(3)) if ok else (0, 0)
-    if ok and stride == 2:
-        if y is not None and y.dim() == 4:
-            H, W = y.size(2), y.size(3)
-        elif in_hw is not None:
-            H, W = int(in_hw[0]), int(in_hw[1])
-        else:
-            raise ValueError("conv_dgrad: stride 2 needs the size of the conv's input map: pass y or in_hw=(H, W)")
-        ok = H >= 1 and W >= 1 and (dz.size(2), dz.size(3)) == ((H - 1) // 2 + 1, (W - 1) // 2 + 1) and (in_hw is None or (H, W) == (int(in_hw[0]), int(in_hw[1])))
-    if ok and y is not None:
-        ok = y.dtype == torch.float32 and tuple(y.shape) == (dz.size(0), w.size(1), H, W)
-    if not ok:
-        raise ValueError("conv_dgrad: expected float32 w [Cout,Cin,%d,%d], dz [B,Cout,%s] and y [B,Cin,H,W], got %s, %s and %s"
-                         % (size, size, "(H-1)//2+1,(W-1)//2+1" if stride == 2 else "H,W", tuple(w.shape), tuple(dz.shape), None if y is None else tuple(y.shape)))
-    w, dz = w.contiguous(), dz.contiguous()
-    y = None if y is None else y.contiguous()
-    B, cout, cin = dz.size(0), dz.size(1), w.size(1)
-    dev = dz.device
-    dx = torch.empty((B, cin, H, W), dtype=torch.float32, device=dev)
-    entry = _ffi.lib().rtod_conv_dgrad_s2 if stride == 2 else _ffi.lib().rtod_conv_dgrad
-    with torch.cuda.device(dev):
-        _ffi.check(entry(C.c_void_p(w.data_ptr()), _scale_ptr(row_scale, cout, dev), C.c_void_p(dz.data_ptr()),
-                         C.c_void_p(y.data_ptr()) if y is not None else None, float(slope), B, cout, cin, H, W, size,
-                         C.c_void_p(dx.data_ptr()), _stream(dev)))
-    return dx
+    return _dgrad("conv_dgrad", w, dz, int(size), row_scale, y, slope, stride, in_hw)
 
 
 def grad_join_async(contributions, y=None, slope=1.0):
@@ -449,8 +445,7 @@ class DarknetTrainer:
         self.status = None
         self.last_components = None
         self._head_masters = None          # head_step / optimizer: {conv_layer: [weight, bias]} float32 device masters of the head convs
-        self._block_cache = None           # block_gradients: (plan and weight version, the plan's blocks with their scales)
-        self._neck_cache = None            # neck_gradients: (plan and weight version, the neck graph with its scales)
+        self._graph_cache = None           # gradients: (scope, plan and weight version, the graph of that scope with its scales)
         self.optimizer = HeadOptimizer()
 
     @property
@@ -575,7 +570,7 @@ class DarknetTrainer:
         return loss, grads
 
     def _head_pass(self, frames_or_x, bndbox):
-        """The body of ``head_gradients``, which ``block_gradients`` goes on from: ``(loss, {conv_layer: (dW, db)}, {conv_layer: (dz,
+        """The body of ``head_gradients``, which ``gradients`` goes on from: ``(loss, {conv_layer: (dW, db)}, {conv_layer: (dz,
         x)})`` with dz the gradient of the head's raw map and x the dense copy of the head conv's input."""
         model = self.darknet
         if not int(getattr(model, "options", {}).get("keep_head_inputs", 0)):
@@ -625,47 +620,38 @@ class DarknetTrainer:
                 self._head_masters[layer] = [conv.weight.detach().to(dev, torch.float32).clone(), bias]
         return self._head_masters
 
-    # ------------------------------------------------------------------ gradients of the detection blocks
+    # ------------------------------------------------------------------ gradients behind the heads: one entry, three scopes
+    # scope -> (its named entry; the options that keep its activations: any one of them, beside keep_head_inputs; what is lost without them)
+    SCOPES = {"blocks": ("block_gradients", ("keep_block_inputs",), "the activations that feed the head convs and the block convs do not survive the forward"),
+              "neck": ("neck_gradients", ("keep_neck_activations", "keep_backbone_activations"), "the activations of the neck do not survive the forward"),
+              "backbone": ("backbone_gradients", ("keep_backbone_activations",),
+                           "the plan fuses convs of the backbone into other kernels and their activations do not survive the forward")}
+
+    def gradients(self, frames_or_x, bndbox, scope=None):
+        """``(loss, {head_conv_layer: (dW, db)}, {conv_layer: dW [Cout,Cin,k,k]})`` over the BatchNorm convs of ``scope`` ("blocks",
+        "neck" or "backbone"; default ``self.trainable``): ``head_gradients``, then ``_walk`` through ``_graph(scope)``.  All on the
+        current stream, nothing synchronises.  The model's ``options`` must hold ``keep_head_inputs`` and the option of the scope."""
+        scope = self.trainable if scope is None else scope
+        if scope not in self.SCOPES:
+            raise ValueError("DarknetTrainer.gradients: scope must be 'blocks', 'neck' or 'backbone', got %r" % (scope,))
+        entry, kept, lost = self.SCOPES[scope]
+        opts = getattr(self.darknet, "options", {})
+        if not (int(opts.get("keep_head_inputs", 0)) and any(int(opts.get(name, 0)) for name in kept)):
+            raise RuntimeError("DarknetTrainer.%s: set model.options['keep_head_inputs'] = 1 and model.options['%s'] = 1 before the first forward; "
+                               "without them %s" % (entry, kept[0], lost))
+        loss, head_grads, operands = self._head_pass(frames_or_x, bndbox)
+        return loss, head_grads, self._walk(loss, head_grads, operands, self._graph(scope))
+
     def block_gradients(self, frames_or_x, bndbox):
         """``(loss, {head_conv_layer: (dW, db)}, {block_conv_layer: dW [Cout,Cin,k,k]})``: what ``loss.backward()`` of the reference
         under ``.eval()`` leaves on the head convs and on ``conv.weight`` of the detection blocks (``Darknet.head_blocks``: the
-        BatchNorm conv each head conv reads; BatchNorm frozen, its parameters are not trained).  ``head_gradients``, then per head
-        with a block: rtod_conv1x1_dgrad from the head's float32 master weights and ``read_layer`` of the block conv's output (whose
-        sign gives the leaky-ReLU derivative), and rtod_conv_wgrad over ``read_layer`` of the block's input with the plan's frozen
-        scale.  All on the current stream, nothing synchronises.  The model's ``options`` must hold ``keep_head_inputs`` and
-        ``keep_block_inputs``."""
-        model = self.darknet
-        opts = getattr(model, "options", {})
-        if not (int(opts.get("keep_head_inputs", 0)) and int(opts.get("keep_block_inputs", 0))):
-            raise RuntimeError("DarknetTrainer.block_gradients: set model.options['keep_head_inputs'] = 1 and model.options['keep_block_inputs'] = 1 "
-                               "before the first forward; without them the activations that feed the head convs and the block convs do not "
-                               "survive the forward")
-        loss, head_grads, operands = self._head_pass(frames_or_x, bndbox)
-        masters = self._masters(head_grads, loss.device)
-        block_grads = {}
-        for head, block, block_in, leaky, size, scale in self._blocks():
-            dz, y = operands[head]                                    # the head conv's input is the block conv's stored output
-            dy = conv1x1_dgrad_async(masters[head][0], dz, y if leaky else None, 0.1 if leaky else 1.0)
-            block_grads[block] = conv_wgrad_async(dy, model.read_layer(block_in, y.size(0)), size, row_scale=scale)[0]
-        return loss, head_grads, block_grads
+        BatchNorm conv each head conv reads; BatchNorm frozen, its parameters are not trained).  ``head_gradients``, then the walk of
+        ``neck_gradients`` over the heads and their blocks alone: per head with a block the data gradient from the head's float32
+        master weights, the mask of the block conv's stored output (whose sign gives the leaky-ReLU derivative) fused into it, and
+        rtod_conv_wgrad over ``read_layer`` of the block's input with the plan's frozen scale.  All on the current stream, nothing
+        synchronises.  The model's ``options`` must hold ``keep_head_inputs`` and ``keep_block_inputs``."""
+        return self.gradients(frames_or_x, bndbox, "blocks")
 
-    def _blocks(self):
-        """``[(head_conv, block_conv, block_input, leaky, kernel size, device address of the frozen scale)]`` of the heads that have a
-        block, asked of the plan once per plan and weight load (kept beside the masters)."""
-        model = self.darknet
-        key = (model._plan.value, model._plan_weights_version)
-        if self._block_cache is None or self._block_cache[0] != key:
-            found = []
-            for head, block, block_in in model.head_blocks():
-                if block < 0:
-                    continue
-                names = dict(model.module_list[block].named_children())
-                conv = next(sub for name, sub in names.items() if name.startswith("conv_"))
-                found.append((head, block, block_in, any(name.startswith("leaky_") for name in names), conv.kernel_size[0], model.conv_scale(block)[0]))
-            self._block_cache = (key, found)
-        return self._block_cache[1]
-
-    # ------------------------------------------------------------------ gradients of the whole detection neck
     def neck_gradients(self, frames_or_x, bndbox):
         """``(loss, {head_conv_layer: (dW, db)}, {neck_conv_layer: dW [Cout,Cin,k,k]})``: what ``loss.backward()`` of the reference
         under ``.eval()`` leaves on the head convs and on ``conv.weight`` of every neck conv (``Darknet.neck_layers``: the BatchNorm
@@ -676,19 +662,14 @@ class DarknetTrainer:
           ``read_layer`` of its input with the plan's frozen scale, and, where its input is a neck layer, rtod_conv_dgrad from the
           float32 masters and that scale; the conv at the boundary of the graph gets a ``dW`` and sends nothing further;
         * a route hands each source its channel range; an upsample calls rtod_upsample2x_grad;
-        * a producer with ONE reader has its mask fused into that reader's call; one with several readers (or a route as its
-          reader) gets the plain contributions, added in ascending reader order with float32 adds, then one multiplication by
-          the mask.  Either way an element is chain(s), adds in a fixed order, one multiplication: bit-identical from call to call.
+        * a producer with ONE reader inside the graph has its mask fused into that reader's call; one with several readers (or a
+          route as its reader) gets the plain contributions, added in ascending reader order with float32 adds, then one
+          multiplication by the mask.  Either way an element is chain(s), adds in a fixed order, one multiplication: bit-identical
+          from call to call.
 
         All on the current stream, nothing synchronises.  The model's ``options`` must hold ``keep_head_inputs`` and
-        ``keep_neck_activations``."""
-        model = self.darknet
-        opts = getattr(model, "options", {})
-        if not (int(opts.get("keep_head_inputs", 0)) and (int(opts.get("keep_neck_activations", 0)) or int(opts.get("keep_backbone_activations", 0)))):
-            raise RuntimeError("DarknetTrainer.neck_gradients: set model.options['keep_head_inputs'] = 1 and model.options['keep_neck_activations'] = 1 "
-                               "before the first forward; without them the activations of the neck do not survive the forward")
-        loss, head_grads, operands = self._head_pass(frames_or_x, bndbox)
-        return loss, head_grads, self._walk(loss, head_grads, operands, self._neck())
+        ``keep_neck_activations`` (or ``keep_backbone_activations``, which keeps a superset)."""
+        return self.gradients(frames_or_x, bndbox, "neck")
 
     def backbone_gradients(self, frames_or_x, bndbox):
         """``(loss, {head_conv_layer: (dW, db)}, {conv_layer: dW [Cout,Cin,k,k]})`` over ``Darknet.trainable_layers()``: the walk of
@@ -698,26 +679,20 @@ class DarknetTrainer:
         contribution.  Layer 0 is not trained: the walk ends at the first layer whose input is outside the graph.  All
         on the current stream, nothing synchronises.  The model's ``options`` must hold ``keep_head_inputs`` and
         ``keep_backbone_activations``."""
-        model = self.darknet
-        opts = getattr(model, "options", {})
-        if not (int(opts.get("keep_head_inputs", 0)) and int(opts.get("keep_backbone_activations", 0))):
-            raise RuntimeError("DarknetTrainer.backbone_gradients: set model.options['keep_head_inputs'] = 1 and model.options['keep_backbone_activations'] = 1 "
-                               "before the first forward; without them the plan fuses convs of the backbone into other kernels and their activations do not survive the forward")
-        loss, head_grads, operands = self._head_pass(frames_or_x, bndbox)
-        return loss, head_grads, self._walk(loss, head_grads, operands, self._graph("backbone"))
+        return self.gradients(frames_or_x, bndbox, "backbone")
 
     def _walk(self, loss, head_grads, operands, graph):
-        """The one walk under ``neck_gradients`` and ``backbone_gradients``: ``{conv_layer: dW}`` of the BatchNorm convs of ``graph =
-        (layers, readers, member, scales)``, in descending layer order, from the heads' ``operands`` (``_head_pass``).  A layer's dense
-        ``read_layer`` copy is dropped once the walk has passed the layer (every use of it lies at or behind it), and its entry of
-        ``parts`` when its gradient is taken."""
+        """The one walk under ``gradients``: ``{conv_layer: dW}`` of the BatchNorm convs of ``graph = (layers, readers, member,
+        scales)``, in descending layer order, from the heads' ``operands`` (``_head_pass``).  No layer is copied twice in one call:
+        ``stored`` starts out with the head-conv inputs ``_head_pass`` read.  A layer's dense ``read_layer`` copy is dropped once the
+        walk has passed the layer (every use of it lies at or behind it), and its entry of ``parts`` when its gradient is taken."""
         model = self.darknet
         layers, readers, member, scales = graph
         masters = self._masters(list(head_grads) + sorted(scales), loss.device)
         B = next(iter(operands.values()))[0].size(0)
-        stored = {}
+        stored = {head - 1: x for head, (_, x) in operands.items()}
 
-        def read(layer):                                              # dense copies, one per layer and walk
+        def read(layer):                                              # dense copies, one per layer and call
             if layer not in stored:
                 stored[layer] = model.read_layer(layer, B)
             return stored[layer]
@@ -730,7 +705,7 @@ class DarknetTrainer:
                 return
             P = layers[producer]
             leaky = P.type == "convolutional" and P.leaky
-            if fusable and leaky and len(readers[producer]) == 1:
+            if fusable and leaky and sum(member[r] for r in readers[producer]) == 1:
                 parts[producer] = contribution(read(producer), 0.1)
             else:
                 parts.setdefault(producer, []).append((reader, contribution(None, 1.0)))
@@ -777,17 +752,15 @@ class DarknetTrainer:
                 del stored[k]
         return {layer: grads[layer] for layer in sorted(grads)}
 
-    def _neck(self):
-        return self._graph("neck")
-
-    def _graph(self, which):
-        """``(IR layers, readers per layer, membership per layer, {conv: device address of its frozen scale})`` of the neck graph
-        (``which`` "neck") or of the trainable graph ("backbone"), asked of the plan once per plan and weight load.  The plan decides
-        which convs belong (``Darknet.neck_layers`` / ``trainable_layers``); routes, upsamples and, in the trainable graph, shortcuts
-        follow by the same closure rule: every reader is a member or a [yolo] layer."""
+    def _graph(self, scope):
+        """``(IR layers, readers per layer, membership per layer, {conv: device address of its frozen scale})`` of the graph ``_walk``
+        goes through for ``scope``, asked of the plan once per plan and weight load.  The plan decides which BatchNorm convs belong
+        (``Darknet.head_blocks`` / ``neck_layers`` / ``trainable_layers``).  "blocks": they and the head convs are the graph.  "neck"
+        and "backbone": routes, upsamples and, in the trainable graph, shortcuts follow by the plan's closure rule: every reader is
+        a member or a [yolo] layer."""
         model = self.darknet
-        key = (which, model._plan.value, model._plan_weights_version)
-        if self._neck_cache is None or self._neck_cache[0] != key:
+        key = (scope, model._plan.value, model._plan_weights_version)
+        if self._graph_cache is None or self._graph_cache[0] != key:
             h = int(model.net_info["height"])
             w = int(model.input_width) if getattr(model, "input_width", None) is not None else h
             layers = build_ir(model.blocks, h, w).layers
@@ -795,16 +768,19 @@ class DarknetTrainer:
             for L in layers:
                 for s in (L.srcs if L.type in ("route", "shortcut") else ((L.index - 1,) if L.index > 0 else ())):
                     readers[s].append(L.index)
-            trained = model.neck_layers() if which == "neck" else model.trainable_layers()
-            convs = {c for c, _ in trained} | {c for c, _ in model.head_layers()}
-            passive = ("route", "upsample") if which == "neck" else ("route", "upsample", "shortcut")
+            if scope == "blocks":
+                trained = [block for _, block, _ in model.head_blocks() if block >= 0]
+            else:
+                trained = [conv for conv, _ in (model.neck_layers() if scope == "neck" else model.trainable_layers())]
+            convs = set(trained) | {c for c, _ in model.head_layers()}
+            passive = {"blocks": (), "neck": ("route", "upsample"), "backbone": ("route", "upsample", "shortcut")}[scope]
             member = [False] * len(layers)
             for L in reversed(layers):
                 ok = L.index in convs if L.type == "convolutional" else L.type in passive and bool(readers[L.index])
-                member[L.index] = ok and all(layers[r].type == "yolo" or member[r] for r in readers[L.index])
-            scales = {c: model.conv_scale(c)[0] for c, _ in trained}
-            self._neck_cache = (key, (layers, readers, member, scales))
-        return self._neck_cache[1]
+                member[L.index] = ok and (scope == "blocks" or all(layers[r].type == "yolo" or member[r] for r in readers[L.index]))
+            scales = {c: model.conv_scale(c)[0] for c in trained}
+            self._graph_cache = (key, (layers, readers, member, scales))
+        return self._graph_cache[1]
 
     # ------------------------------------------------------------------ the reference's training step, on the heads
     def feed_forward_through_model(self, batch_data, bndbox):
@@ -814,10 +790,10 @@ class DarknetTrainer:
         synchronises; the next forward on that stream runs the new weights.  Returns the loss from before the step as a 0-dim
         float32 device tensor.  The module's ``conv.weight`` / ``conv.bias`` lag behind until ``sync_parameters()`` (or anything
         that reads the model's parameters as a whole: ``weight_stream()``, ``state_dict()``, a re-pack)."""
-        if self.trainable in ("blocks", "neck", "backbone"):
+        if self.trainable in self.SCOPES:
             # every gradient kernel of the batch is enqueued before the first step, as autograd has it: the steps update the
             # masters in place, and the data gradients through the heads and the neck convs read them
-            loss, grads, block_grads = {"blocks": self.block_gradients, "neck": self.neck_gradients, "backbone": self.backbone_gradients}[self.trainable](batch_data, bndbox)
+            loss, grads, block_grads = self.gradients(batch_data, bndbox)
             grads = dict(grads)
             grads.update({layer: (dw, None) for layer, dw in block_grads.items()})
         else:

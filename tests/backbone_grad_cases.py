@@ -1,14 +1,12 @@
 """What tests/test_backbone_grad_host.py and tests/test_backbone_grad_gpu.py share: rtod_plan_trainable_layers on the C ABI, the trainable
 convs expected per cfg, the shapes of the stride-2 kernel tests and exact numpy references of rtod_conv_dgrad_s2 / rtod_conv_wgrad_s2."""
-import ctypes as C
-
 import numpy as np
 
-from realtimeobjectdetection_amd import _ffi
+from scope_grad_cases import KEEP, plan_list
 
 F = np.float32
 U = 2.0 ** -24
-BACKBONE = {"keep_head_inputs": 1, "keep_backbone_activations": 1}
+BACKBONE = KEEP["backbone"]
 UNFUSED = {"fuse_shortcut": 0, "fuse_pointwise": 0, "stem2_kernel": 0}
 
 # with option keep_backbone_activations.  mini_cfg: every BatchNorm conv but layer 0; stride 2: 1, 5, 9, 10, 11; shortcuts 4 and 8;
@@ -28,12 +26,7 @@ def out_hw(H, W):
 
 
 def trainable_layers(h):
-    lib = _ffi.lib()
-    n = lib.rtod_plan_trainable_layers(h, None, None, 0)
-    assert n >= 0
-    conv, inp = (C.c_int * max(n, 1))(), (C.c_int * max(n, 1))()
-    assert lib.rtod_plan_trainable_layers(h, conv, inp, n) == n
-    return list(zip(list(conv)[:n], list(inp)[:n]))
+    return plan_list("rtod_plan_trainable_layers", h, 2)
 
 
 def _tap_ranges(n_in, n_out, k):

@@ -1,11 +1,9 @@
 """What tests/test_block_grad_host.py and tests/test_block_grad_gpu.py share: the slice rule of rtod_conv_wgrad restated from
 include/rtod.h, rtod_plan_head_blocks on the C ABI, exact references of the two gradient kernels, and the optimiser step of
 rtod_plan_step_conv restated in float32 numpy (one rounding per documented line)."""
-import ctypes as C
-
 import numpy as np
 
-from realtimeobjectdetection_amd import _ffi
+from scope_grad_cases import plan_list
 
 F = np.float32
 U = 2.0 ** -24
@@ -31,12 +29,7 @@ WGRAD_SHAPES = [(1, 1, 32, 1, 1), (2, 18, 32, 2, 2), (1, 64, 64, 5, 7), (3, 255,
 
 
 def head_blocks(h):
-    lib = _ffi.lib()
-    n = lib.rtod_plan_head_blocks(h, None, None, None, 0)
-    assert n >= 0
-    arrs = [(C.c_int * max(n, 1))() for _ in range(3)]
-    assert lib.rtod_plan_head_blocks(h, *arrs, n) == n
-    return list(zip(*[list(a)[:n] for a in arrs]))
+    return plan_list("rtod_plan_head_blocks", h, 3)
 
 
 # ---------------------------------------------------------------------------------------------- references of the kernels

@@ -11,32 +11,23 @@ Gates, with u = 2^-24.
 * wgrad stride 2 on floats: the bound tests/test_block_grad_gpu.py applies to rtod_conv_wgrad with K = B * Ho * Wo.
 * rtod_grad_join: the bits of the torch expression it replaces.
 * End to end: the docstrings of the tests."""
+import functools
+
 import numpy as np
 import pytest
 import torch
 
 from backbone_grad_cases import BACKBONE, MINI_S2, S2_SHAPES, TRAINABLE, U, UNFUSED, conv_dgrad_s2_ref, conv_wgrad_s2_ref, out_hw, taps_per_pixel
-from block_grad_cases import opt_update_f32
-from head_grad_cases import cpu_head_model, pack
 from loss_cases import bits
 from neck_grad_cases import NECK
-from test_block_grad_gpu import GATES, _bn_of, _frames, _t64
-from test_head_grad_gpu import _conv_of, _forward, _model, step_batch
+from scope_grad_cases import _dev, _forward, _frames, _model, _same, check_directional_derivative, check_training_steps, cpu_graph_grads, cpu_scope_loss
+from scope_grad_cases import over_the_floor, scope_trainer, step_batch, tenth_heads as _tenth_heads
 from realtimeobjectdetection_amd import _ffi, cfgs, train as T
-from realtimeobjectdetection_amd.train import HeadOptimizer
 
 pytestmark = pytest.mark.gpu
 F = np.float32
 fn = torch.nn.functional
 HEADS = [14, 22]
-
-
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def _same(a, b):
-    return np.array_equal(bits(a.detach().cpu().numpy()), bits(b.detach().cpu().numpy()))
 
 
 # ------------------------------------------------------------------------------------------ 1a. the stride-2 data gradient
@@ -231,78 +222,14 @@ def test_keep_backbone_activations_is_the_plan_with_the_three_fusions_off(tmp_pa
 
 
 # ------------------------------------------------------------------------------------------ 3. backbone_gradients against autograd
-def _backbone_trainer(tmp_path, text, res, precision, width=None, name="m", trainable="backbone", options=BACKBONE):
-    m = _model(tmp_path, text, res, precision, options, name=name)
-    if width is not None:
-        m.input_width = width
-    t = T.DarknetTrainer(m, trainable=trainable)
-    t.min_box_size = 4
-    return m, t
-
-
-def _cpu_graph(m, t, B, dtype, weights=None, masks=None, cut=None):
-    """The trainable sub-graph on the CPU in ``dtype`` from the module's parameters: conv (stride 1 or 2) -> eval BatchNorm -> leaky
-    (written as a product with ``masks[layer]``, the DEVICE's, where given; else torch's leaky_relu), shortcuts, routes, F.interpolate,
-    head convs; fed the device's boundary inputs (read_layer of the layers the graph reads from outside: layer 0).  ``weights``:
-    {conv: weight} in place of the module's; ``cut = (producer, reader)``: that reader sees the producer's value detached.
-    Returns (values per layer, {conv: leaf weight}, {conv: (pre-activation, input)})."""
-    layers, readers, member, scales = t._graph("backbone")
-    cast = lambda a: torch.as_tensor(a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)).to(dtype)
-    val, leaves, pres = {}, {}, {}
-
-    def value(src, reader):
-        if src not in val:
-            assert not member[src]
-            val[src] = cast(m.read_layer(src, B))
-        return val[src].detach() if cut == (src, reader) else val[src]
-
-    for L in layers:
-        i = L.index
-        if not member[i]:
-            continue
-        if L.type == "convolutional":
-            conv, x = _conv_of(m, i), value(i - 1, i)
-            W = cast(conv.weight if weights is None or i not in weights else weights[i])
-            if i in scales:
-                W.requires_grad_(True)
-                leaves[i] = W
-                bn = _bn_of(m, i)
-                pre = fn.batch_norm(fn.conv2d(x, W, stride=L.stride, padding=L.size // 2), cast(bn.running_mean), cast(bn.running_var), cast(bn.weight), cast(bn.bias),
-                                    False, 0.0, 1e-5)
-                pres[i] = (pre, x)
-                val[i] = pre if not L.leaky else pre * cast(masks[i]) if masks is not None else fn.leaky_relu(pre, 0.1)
-            else:
-                val[i] = fn.conv2d(x, W, cast(conv.bias))
-        elif L.type == "upsample":
-            x = value(i - 1, i)
-            val[i] = fn.interpolate(x, scale_factor=2, mode="nearest") if L.nearest else fn.interpolate(x, scale_factor=2, mode="bilinear", align_corners=False)
-        elif L.type == "shortcut":
-            val[i] = value(L.srcs[0], i) + value(L.srcs[1], i)
-        else:
-            parts, off = [], 0
-            for s in L.srcs:
-                parts.append(value(s, i) if member[s] else cast(m.read_layer(i, B))[:, off:off + layers[s].cout])
-                off += layers[s].cout
-            val[i] = torch.cat(parts, 1)
-    return val, leaves, pres
-
-
-def _cpu_graph_grads(m, t, B, dtype, masks, dzs, cut=None):
-    val, leaves, pres = _cpu_graph(m, t, B, dtype, masks=masks, cut=cut)
-    total = sum((val[head] * dz.detach().cpu().to(dtype)).sum() for (head, _), dz in zip(m.head_layers(), dzs))
-    total.backward()
-    return {i: W.grad.numpy().astype(np.float64) for i, W in leaves.items()}, pres
-
-
-def _tenth_heads(m):
-    for head, _ in m.head_layers():                                   # a tenth of the synthetic head weights: sigmoids that do not saturate
-        m.update_conv(head, _conv_of(m, head).weight.detach() * 0.1, _conv_of(m, head).bias.detach() * 0.1)
+_backbone_trainer = functools.partial(scope_trainer, trainable="backbone", options=BACKBONE)
+_cpu_graph_grads = functools.partial(cpu_graph_grads, scope="backbone")   # autograd of the whole trainable sub-graph (scope_grad_cases.cpu_graph), the DEVICE's masks
 
 
 @pytest.mark.parametrize("precision,width", [("fp32", None), ("f16s3", None), ("fp32", 96)])
 def test_backbone_gradients_against_autograd(tmp_path, precision, width):
     """dW of DarknetTrainer.backbone_gradients for all 14 trainable convs of mini_cfg against torch autograd of the whole trainable
-    sub-graph (_cpu_graph: layers 1-22) with the DEVICE's masks, fed the device's boundary input (read_layer(0)) and pulled back from
+    sub-graph (scope_grad_cases.cpu_graph: layers 1-22) with the DEVICE's masks, fed the device's boundary input (read_layer(0)) and pulled back from
     the device's dz, once in float64 (the truth) and once in float32 torch (the reference's own arithmetic, the floor).
 
     The masks: a flip of the device's mask against the float64 forward's pre-activation is legitimate only where |pre_64| is within
@@ -341,27 +268,7 @@ def test_backbone_gradients_against_autograd(tmp_path, precision, width):
     dzs = T.yolo_loss_grad_async(t._forward_train(xd), bnd, t.heads, t.num_classes, t.min_box_size)["grad_raw"]
     want, pres = _cpu_graph_grads(m, t, B, torch.float64, masks, dzs)
     floor, _ = _cpu_graph_grads(m, t, B, torch.float32, masks, dzs)
-    over = []
-    for c in want_layers:
-        conv, bn, L = _conv_of(m, c), _bn_of(m, c), layers[c]
-        pre, x = (a.detach() for a in pres[c])
-        gamma, beta, mean, var = (_t64(v) for v in (bn.weight, bn.bias, bn.running_mean, bn.running_var))
-        s = (gamma / torch.sqrt(var + 1e-5))
-        mass = fn.conv2d(x.abs(), (_t64(conv.weight) * s[:, None, None, None]).abs(), stride=L.stride, padding=L.size // 2).numpy() + \
-            np.abs((beta - mean * s).numpy())[None, :, None, None]
-        gate = ((conv.in_channels * L.size * L.size + 2) * U if GATES[precision] is None else GATES[precision]) * mass
-        y_dev = m.read_layer(c, B).cpu().numpy()
-        flips = (pre.numpy() > 0) != (y_dev > 0)
-        assert (np.abs(pre.numpy())[flips] <= gate[flips]).all(), (precision, c, int(flips.sum()))
-        got, ref = grads[c].cpu().numpy().astype(np.float64), np.abs(want[c]).max()
-        assert got.shape == want[c].shape and ref > 0
-        e_dev, e_32 = (got - want[c]) / ref, (floor[c] - want[c]) / ref
-        rms = lambda e: float(np.sqrt(np.mean(e * e)))
-        print("mini %s%s conv %d (stride %d, %d flips): rms %.3g (float32 floor %.3g, ratio %.2f)  max %.3g (floor %.3g, ratio %.2f)" % (
-            precision, "" if width is None else " 64x%d" % width, c, L.stride, int(flips.sum()), rms(e_dev), rms(e_32), rms(e_dev) / rms(e_32),
-            np.abs(e_dev).max(), np.abs(e_32).max(), np.abs(e_dev).max() / np.abs(e_32).max()))
-        if not (rms(e_dev) <= 4 * rms(e_32) and np.abs(e_dev).max() <= 4 * np.abs(e_32).max()):
-            over.append((c, round(rms(e_dev) / rms(e_32), 2), round(float(np.abs(e_dev).max() / np.abs(e_32).max()), 2)))
+    over = over_the_floor("mini %s%s" % (precision, "" if width is None else " 64x%d" % width), m, layers, want_layers, precision, B, grads, want, floor, pres)
     if precision == "fp32" and width is None:                         # the fan-out sums
         assert readers[1] == [2, 4] and readers[5] == [6, 8] and readers[10] == [11, 19]
         for producer in (1, 5, 10):
@@ -410,41 +317,7 @@ def test_the_loss_falls_along_the_backbone_gradient_by_what_it_says(tmp_path):
     _, _, grads = t.backbone_gradients(xd, bnd)
     l0 = float(t.last_components[0].item())
     assert sorted(grads) == TRAINABLE["mini"]
-    g2 = sum(float((dw.double() ** 2).sum()) for dw in grads.values())
-    W0 = {c: _conv_of(m, c).weight.detach().clone() for c in grads}
-    heads = [h for h, _ in m.head_layers()]
-
-    def cpu(s, dtype=torch.float64):
-        with torch.no_grad():
-            val, _, _ = _cpu_graph(m, t, B, dtype, weights={c: W0[c].double() + s * grads[c].cpu().double() for c in grads})
-        val = {k: v.detach() for k, v in val.items()}
-        acts = [val[h - 1].numpy() for h in heads]
-        ws = [_t64(_conv_of(m, h).weight).numpy() for h in heads]
-        bs = [_t64(_conv_of(m, h).bias).numpy() for h in heads]
-        if dtype != torch.float64:
-            ws, bs = [a.astype(F) for a in ws], [a.astype(F) for a in bs]
-        return cpu_head_model(acts, ws, bs, t.heads, images, 4, None if dtype == torch.float64 else dtype)["loss"]
-    noise_at = lambda s: abs(cpu(s, torch.float32) - cpu(s))
-    noise = noise_at(0.0)
-    eps = gap_cpu = None
-    for e in (1e-2, 3e-3, 1e-3, 3e-4, 1e-4, 3e-5, 1e-5, 3e-6, 1e-6, 3e-7, 1e-7):
-        fd, dd = (cpu(e) - cpu(-e)) / (2 * e), (cpu(e / 10) - cpu(-e / 10)) / (2 * e / 10)
-        if abs(fd - dd) >= 10 * noise / e:
-            eps, gap_cpu = e, abs(fd - dd)
-    assert eps is not None
-    noise = max(noise, noise_at(eps), noise_at(-eps))
-    allowed = 4 * gap_cpu + 2 * noise / (2 * eps)
-    masters = {c: W0[c].cuda() for c in grads}
-
-    def loss_at(s):
-        for c in grads:
-            m.update_conv_weight(c, masters[c] + s * grads[c])
-        t.forward_loss(xd, bnd)
-        return float(t.last_components[0].item())
-    fd_dev = (loss_at(eps) - loss_at(-eps)) / (2 * eps)
-    assert loss_at(0.0) == l0                                         # the weights are back, bit for bit
-    print("||g||^2 device %.8g; eps %.0e; central difference device %.8g; gap %.4g, allowed %.4g (cpu gap %.4g, noise %.4g)" % (g2, eps, fd_dev, abs(fd_dev - g2), allowed, gap_cpu, noise))
-    assert g2 > 0 and abs(fd_dev - g2) <= allowed
+    check_directional_derivative(m, t, xd, bnd, grads, cpu_scope_loss(m, t, B, images, grads, "backbone"), l0)
 
 
 # ------------------------------------------------------------------------------------------ 6. the training step
@@ -459,33 +332,4 @@ def test_training_step_on_the_backbone(tmp_path, precision, width):
     m, t = _backbone_trainer(tmp_path, text, 64, precision, width)
     layers = sorted(TRAINABLE["mini"] + HEADS)
     assert set(MINI_S2) <= set(layers)
-    losses = []
-    host = lambda a: None if a is None else a.detach().cpu().numpy()
-    for step, kind in enumerate(["sgd", "adam", "adam"]):
-        if step < 2:
-            t.optimizer = HeadOptimizer(kind, lr=1e-4)
-        _, hg, ng = t.backbone_gradients(xd, bnd)
-        grads = {k: (host(dw), host(db)) for k, (dw, db) in hg.items()}
-        grads.update({k: (host(dw), None) for k, dw in ng.items()})
-        assert sorted(grads) == layers
-        masters = t._masters(grads, xd.device)
-        before = {k: (host(masters[k][0]), host(masters[k][1])) for k in layers}
-        state = {k: {n: host(v) for n, v in t.optimizer.state.get(k, {}).items() if n.startswith("exp_avg")} for k in layers}
-        losses.append(float(t.feed_forward_through_model(xd, bnd)))
-        for k in layers:
-            st = t.optimizer.state[k]
-            assert st["step"] == (1 if step < 2 else 2) and st["weight"] is t._head_masters[k][0]
-            for which, name, sfx in ((0, "weight", ""), (1, "bias", "_bias")):
-                if before[k][which] is None:
-                    assert which == 1 and "bias" not in st and k in TRAINABLE["mini"]
-                    continue
-                zero = np.zeros_like(before[k][which])
-                w1, m1, v1 = opt_update_f32(kind, before[k][which], grads[k][which], state[k].get("exp_avg" + sfx, zero), state[k].get("exp_avg_sq" + sfx, zero),
-                                            1e-4, step=st["step"])
-                assert np.array_equal(bits(host(st[name])), bits(w1)), (precision, step, k, name)
-                if kind == "adam":
-                    assert np.array_equal(bits(host(st["exp_avg" + sfx])), bits(m1)) and np.array_equal(bits(host(st["exp_avg_sq" + sfx])), bits(v1)), (precision, step, k, name)
-        image = m.packed_weights()
-        stream = m.weight_stream().copy()                             # synchronises the masters into the module's parameters
-        assert all(_same(_conv_of(m, c).weight, t._head_masters[c][0]) for c in MINI_S2) and np.array_equal(image, pack(m._plan, stream)), (precision, step)
-    assert losses[1] != losses[0] and np.isfinite(losses).all(), losses
+    check_training_steps(m, t, xd, bnd, "backbone", layers, TRAINABLE["mini"], MINI_S2)

@@ -227,5 +227,7 @@ def test_trainer_asks_for_the_backbone_options():
     stub = lambda opts: types.SimpleNamespace(blocks=parse_cfg_text(cfgs.mini_cfg(64, 64)), net_info={"height": 64}, input_width=None, options=opts)
     assert DarknetTrainer(stub({}), trainable="backbone").trainable == "backbone"
     for opts in ({}, {"keep_head_inputs": 1}, {"keep_backbone_activations": 1}, {"keep_head_inputs": 1, "keep_neck_activations": 1}):
-        with pytest.raises(RuntimeError, match="keep_backbone_activations"):
-            DarknetTrainer(stub(opts), trainable="backbone").backbone_gradients(None, [])
+        t = DarknetTrainer(stub(opts), trainable="backbone")
+        for call in (t.backbone_gradients, t.gradients, lambda x, b: DarknetTrainer(stub(opts)).gradients(x, b, scope="backbone")):
+            with pytest.raises(RuntimeError, match="keep_backbone_activations"):
+                call(None, [])

@@ -15,6 +15,8 @@ Gates, with u = 2^-24.
 * dgrad on floats: one fmaf chain over Cout terms, then one multiplication: |dx - float64| <= (Cout + 1) u |m| sum_o |w| |dz|.
 * Folded step: identical bits — masters and moments against block_grad_cases.opt_update_f32, the packed image as uint32 words.
 * End to end: the docstrings of the tests."""
+import functools
+
 import numpy as np
 import pytest
 import torch
@@ -23,22 +25,15 @@ import head_opt_cases as A
 from block_grad_cases import U, WGRAD_SHAPES, dgrad_ref, opt_update_f32, wgrad_ref
 from head_grad_cases import conv_stream_ranges, cpu_head_model, pack
 from loss_cases import bits
-from test_head_grad_gpu import _conv_of, _forward, _model, step_batch
+from scope_grad_cases import GATES, KEEP, _bn_of, _conv_of, _dev, _forward, _frames, _model, _same, _t64, scope_trainer, step_batch, tenth_heads
+from scope_grad_cases import check_directional_derivative
 from realtimeobjectdetection_amd import _ffi, cfgs, synth, train as T
 from realtimeobjectdetection_amd.cfg import build_ir, parse_cfg_text
 from realtimeobjectdetection_amd.train import HeadOptimizer
 
 pytestmark = pytest.mark.gpu
 F = np.float32
-KEEP = {"keep_head_inputs": 1, "keep_block_inputs": 1}
-
-
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def _same(a, b):
-    return np.array_equal(bits(a.detach().cpu().numpy()), bits(b.detach().cpu().numpy()))
+KEEP = KEEP["blocks"]
 
 
 # ------------------------------------------------------------------------------------------ 1 / 2. the weight gradient
@@ -237,30 +232,7 @@ def test_keep_block_inputs_changes_no_output_bit(tmp_path, net, precision, width
 
 
 # ------------------------------------------------------------------------------------------ 6. block_gradients against autograd
-def _block_trainer(tmp_path, text, res, precision, width=None, name="m", trainable="blocks", options=KEEP):
-    m = _model(tmp_path, text, res, precision, options, name=name)
-    if width is not None:
-        m.input_width = width
-    t = T.DarknetTrainer(m, trainable=trainable)
-    t.min_box_size = 4
-    return m, t
-
-
-def _frames(B, res, width):
-    if width is None:
-        return torch.from_numpy(synth.synth_frames(B, res, seed=12)).cuda()
-    return torch.from_numpy(np.random.default_rng(12).random((B, 3, res, width)).astype(F)).cuda()
-
-
-def _bn_of(m, layer):
-    return next(sub for name, sub in m.module_list[layer].named_children() if name.startswith("batch_norm_"))
-
-
-def _t64(a):
-    return torch.as_tensor(a.detach().cpu().numpy().astype(np.float64) if isinstance(a, torch.Tensor) else np.asarray(a, np.float64))
-
-
-GATES = {"fp32": None, "f16s3": 1e-4, "f16": 1e-3}
+_block_trainer = functools.partial(scope_trainer, trainable="blocks", options=KEEP)
 
 
 @pytest.mark.parametrize("net,precision,width", [("mini", "fp32", None), ("mini", "f16s3", None), ("mini", "fp32", 96), ("mini", "f16s3", 96), ("tiny", "fp32", None)])
@@ -287,8 +259,7 @@ def test_block_gradients_against_autograd(tmp_path, net, precision, width):
     _, images = step_batch()
     bnd = [torch.from_numpy(im) for im in images]
     _forward(m, xd)
-    for head, _, _ in m.head_blocks():                                # a tenth of the synthetic head weights: sigmoids that do not saturate
-        m.update_conv(head, _conv_of(m, head).weight.detach() * 0.1, _conv_of(m, head).bias.detach() * 0.1)
+    tenth_heads(m)
     loss, head_grads, block_grads = t.block_gradients(xd, bnd)
     blocks = m.head_blocks()
     assert m.active_precision == precision and int(t.status.item()) == 0
@@ -374,32 +345,11 @@ def test_the_loss_falls_along_the_block_gradient_by_what_it_says(tmp_path):
     loss0, _, grads = t.block_gradients(xd, bnd)
     l0 = float(t.last_components[0].item())
     blocks = m.head_blocks()
-    g2 = sum(float((dw.double() ** 2).sum()) for dw in grads.values())
     xs = [m.read_layer(inp, B).cpu().numpy().astype(np.float64) for _, _, inp in blocks]
     W1s = [_t64(_conv_of(m, b).weight).numpy() for _, b, _ in blocks]
     gs = [grads[b].cpu().numpy().astype(np.float64) for _, b, _ in blocks]
-    cpu = lambda s, dtype=None: _cpu_loss(m, t, xs, [w + s * g for w, g in zip(W1s, gs)], images, dtype)
-    noise_at = lambda s: abs(cpu(s, torch.float32) - cpu(s))
-    noise = noise_at(0.0)
-    eps = gap_cpu = None
-    for e in (1e-2, 3e-3, 1e-3, 3e-4, 1e-4, 3e-5, 1e-5, 3e-6, 1e-6, 3e-7, 1e-7):
-        fd, dd = (cpu(e) - cpu(-e)) / (2 * e), (cpu(e / 10) - cpu(-e / 10)) / (2 * e / 10)
-        if abs(fd - dd) >= 10 * noise / e:
-            eps, gap_cpu = e, abs(fd - dd)
-    assert eps is not None
-    noise = max(noise, noise_at(eps), noise_at(-eps))                 # the largest of the three evaluations the quotient and the base use
-    allowed = 4 * gap_cpu + 2 * noise / (2 * eps)
-    masters = {b: _conv_of(m, b).weight.detach().clone().cuda() for _, b, _ in blocks}
-
-    def loss_at(s):
-        for _, b, _ in blocks:
-            m.update_conv_weight(b, masters[b] + s * grads[b])
-        t.forward_loss(xd, bnd)
-        return float(t.last_components[0].item())
-    fd_dev = (loss_at(eps) - loss_at(-eps)) / (2 * eps)
-    assert loss_at(0.0) == l0                                         # the weights are back, bit for bit
-    print("||g||^2 device %.8g; eps %.0e; central difference device %.8g; gap %.4g, allowed %.4g (cpu gap %.4g, noise %.4g)" % (g2, eps, fd_dev, abs(fd_dev - g2), allowed, gap_cpu, noise))
-    assert g2 > 0 and abs(fd_dev - g2) <= allowed
+    cpu = lambda s, dtype: _cpu_loss(m, t, xs, [w + s * g for w, g in zip(W1s, gs)], images, None if dtype == torch.float64 else dtype)
+    check_directional_derivative(m, t, xd, bnd, grads, cpu, l0)
 
 
 # ------------------------------------------------------------------------------------------ 8. the training step

@@ -166,8 +166,9 @@ def test_trainer_asks_for_both_keep_options():
     assert DarknetTrainer(stub({})).trainable == "heads"
     for opts in ({}, {"keep_head_inputs": 1}, {"keep_block_inputs": 1}):
         t = DarknetTrainer(stub(opts), trainable="blocks")
-        with pytest.raises(RuntimeError, match="keep_block_inputs"):
-            t.block_gradients(np.zeros((1, 3, 64, 64), F), [None])
+        for call in (t.block_gradients, t.gradients, lambda x, b: DarknetTrainer(stub(opts)).gradients(x, b, scope="blocks")):
+            with pytest.raises(RuntimeError, match="keep_block_inputs"):
+                call(np.zeros((1, 3, 64, 64), F), [None])
         with pytest.raises(RuntimeError, match="keep_head_inputs"):
             t.feed_forward_through_model(np.zeros((1, 3, 64, 64), F), [None])
 

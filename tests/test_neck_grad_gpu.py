@@ -13,31 +13,21 @@ Gates, with u = 2^-24.
   tests/test_block_grad_gpu.py: a K-term chain of random signs errs by about sqrt(K) u, far inside.
 * upsample grad: integer dz make every bilinear sum an exact multiple of 1/16: float64 autograd of F.interpolate bit for bit.
 * End to end: the docstrings of the tests."""
+import functools
+
 import numpy as np
 import pytest
 import torch
 
-from block_grad_cases import opt_update_f32
-from head_grad_cases import cpu_head_model, pack
-from loss_cases import bits
 from neck_grad_cases import DGRAD_SHAPES, NECK, U, UPSAMPLE_SHAPES, conv_dgrad_ref
-from test_block_grad_gpu import GATES, _bn_of, _frames, _t64
-from test_head_grad_gpu import _conv_of, _forward, _model, step_batch
+from scope_grad_cases import KEEP, _dev, _forward, _frames, _model, _same, check_directional_derivative, check_training_steps, cpu_graph_grads, cpu_scope_loss
+from scope_grad_cases import over_the_floor, scope_trainer, step_batch, tenth_heads
 from realtimeobjectdetection_amd import cfgs, train as T
-from realtimeobjectdetection_amd.train import HeadOptimizer
 
 pytestmark = pytest.mark.gpu
 F = np.float32
-KEEP = {"keep_head_inputs": 1, "keep_neck_activations": 1}
+KEEP = KEEP["neck"]
 fn = torch.nn.functional
-
-
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def _same(a, b):
-    return np.array_equal(bits(a.detach().cpu().numpy()), bits(b.detach().cpu().numpy()))
 
 
 # ------------------------------------------------------------------------------------------ 4 / 5. the data gradient
@@ -135,69 +125,13 @@ def test_keep_neck_activations_changes_no_output_bit(tmp_path, net, precision, w
 
 
 # ------------------------------------------------------------------------------------------ 8. neck_gradients against autograd
-def _neck_trainer(tmp_path, text, res, precision, width=None, name="m", trainable="neck", options=KEEP):
-    m = _model(tmp_path, text, res, precision, options, name=name)
-    if width is not None:
-        m.input_width = width
-    t = T.DarknetTrainer(m, trainable=trainable)
-    t.min_box_size = 4
-    return m, t
-
-
-def _cpu_neck(m, t, B, dtype, weights=None, masks=None, cut=None):
-    """The neck sub-graph on the CPU in ``dtype`` from the module's parameters: conv -> eval BatchNorm -> leaky (written as a product with
-    ``masks[layer]``, the DEVICE's, where given; else torch's leaky_relu), routes, F.interpolate, head convs; fed the device's boundary
-    inputs (read_layer of the layers the graph reads from outside).  ``weights``: {neck conv: weight} in place of the module's;
-    ``cut = (producer, reader)``: that reader sees the producer's value detached (its contribution to the producer's gradient is zero).
-    Returns (values per layer, {neck conv: leaf weight}, {neck conv: (pre-activation, input)})."""
-    layers, readers, member, scales = t._neck()
-    cast = lambda a: torch.as_tensor(a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)).to(dtype)
-    val, leaves, pres = {}, {}, {}
-
-    def value(src, reader):
-        if src not in val:
-            assert not member[src]
-            val[src] = cast(m.read_layer(src, B))
-        return val[src].detach() if cut == (src, reader) else val[src]
-
-    for L in layers:
-        i = L.index
-        if not member[i]:
-            continue
-        if L.type == "convolutional":
-            conv, x = _conv_of(m, i), value(i - 1, i)
-            W = cast(conv.weight if weights is None or i not in weights else weights[i])
-            if i in scales:
-                W.requires_grad_(True)
-                leaves[i] = W
-                bn = _bn_of(m, i)
-                pre = fn.batch_norm(fn.conv2d(x, W, padding=L.size // 2), cast(bn.running_mean), cast(bn.running_var), cast(bn.weight), cast(bn.bias), False, 0.0, 1e-5)
-                pres[i] = (pre, x)
-                val[i] = pre if not L.leaky else pre * cast(masks[i]) if masks is not None else fn.leaky_relu(pre, 0.1)
-            else:
-                val[i] = fn.conv2d(x, W, cast(conv.bias))
-        elif L.type == "upsample":
-            x = value(i - 1, i)
-            val[i] = fn.interpolate(x, scale_factor=2, mode="nearest") if L.nearest else fn.interpolate(x, scale_factor=2, mode="bilinear", align_corners=False)
-        else:                                                         # a source outside the graph: its slice of the kept concat buffer
-            parts, off = [], 0
-            for s in L.srcs:
-                parts.append(value(s, i) if member[s] else cast(m.read_layer(i, B))[:, off:off + layers[s].cout])
-                off += layers[s].cout
-            val[i] = torch.cat(parts, 1)
-    return val, leaves, pres
-
-
-def _cpu_neck_grads(m, t, B, dtype, masks, dzs, cut=None):
-    val, leaves, pres = _cpu_neck(m, t, B, dtype, masks=masks, cut=cut)
-    total = sum((val[head] * dz.detach().cpu().to(dtype)).sum() for (head, _), dz in zip(m.head_layers(), dzs))
-    total.backward()
-    return {i: W.grad.numpy().astype(np.float64) for i, W in leaves.items()}, pres
+_neck_trainer = functools.partial(scope_trainer, trainable="neck", options=KEEP)
+_cpu_neck_grads = functools.partial(cpu_graph_grads, scope="neck")   # autograd of the neck sub-graph (scope_grad_cases.cpu_graph) with the DEVICE's masks
 
 
 @pytest.mark.parametrize("net,precision,width", [("mini", "fp32", None), ("mini", "f16s3", None), ("mini", "fp32", 96), ("tiny", "fp32", None)])
 def test_neck_gradients_against_autograd(tmp_path, net, precision, width):
-    """dW of DarknetTrainer.neck_gradients for every neck conv against torch autograd of the neck sub-graph (_cpu_neck) with the DEVICE's
+    """dW of DarknetTrainer.neck_gradients for every neck conv against torch autograd of the neck sub-graph (scope_grad_cases.cpu_graph) with the DEVICE's
     masks, fed the device's boundary inputs and pulled back from the device's dz, once in float64 (the truth) and once in float32
     torch (the reference's own arithmetic, the floor).
 
@@ -222,8 +156,7 @@ def test_neck_gradients_against_autograd(tmp_path, net, precision, width):
     xd = _frames(B, res, width)
     bnd = [torch.from_numpy(im) for im in step_batch()[1]]
     _forward(m, xd)
-    for head, _ in m.head_layers():                                   # a tenth of the synthetic head weights: sigmoids that do not saturate
-        m.update_conv(head, _conv_of(m, head).weight.detach() * 0.1, _conv_of(m, head).bias.detach() * 0.1)
+    tenth_heads(m)
     loss, head_grads, neck_grads = t.neck_gradients(xd, bnd)
     assert m.active_precision == precision and int(t.status.item()) == 0 and sorted(neck_grads) == NECK[net] == [c for c, _ in m.neck_layers()]
     # twice the same bytes; the heads' part is head_gradients; the block convs' entries are block_gradients of a "blocks" trainer
@@ -233,35 +166,16 @@ def test_neck_gradients_against_autograd(tmp_path, net, precision, width):
     assert _same(loss, loss_h) and all(_same(head_grads[k][0], grads_h[k][0]) and _same(head_grads[k][1], grads_h[k][1]) for k in grads_h)
     mb, tb = _neck_trainer(tmp_path, text, res, precision, width, name="blocks", trainable="blocks", options={"keep_head_inputs": 1, "keep_block_inputs": 1})
     _forward(mb, xd)
-    for head, _ in mb.head_layers():
-        mb.update_conv(head, _conv_of(mb, head).weight.detach() * 0.1, _conv_of(mb, head).bias.detach() * 0.1)
+    tenth_heads(mb)
     loss_b, _, block_grads = tb.block_gradients(xd, bnd)
     assert _same(loss, loss_b) and len(block_grads) == len(m.head_layers()) and all(_same(neck_grads[k], block_grads[k]) for k in block_grads)
     # the CPU model with the device's masks
-    layers, readers, member, scales = t._neck()
+    layers, readers, member, scales = t._graph("neck")
     masks = {c: np.where(m.read_layer(c, B).cpu().numpy() > 0, 1.0, 0.1) for c in NECK[net] if layers[c].leaky}
     dzs = T.yolo_loss_grad_async(t._forward_train(xd), bnd, t.heads, t.num_classes, t.min_box_size)["grad_raw"]
     want, pres = _cpu_neck_grads(m, t, B, torch.float64, masks, dzs)
     floor, _ = _cpu_neck_grads(m, t, B, torch.float32, masks, dzs)
-    over = []
-    for c in NECK[net]:
-        conv, bn, size = _conv_of(m, c), _bn_of(m, c), layers[c].size
-        pre, x = (a.detach() for a in pres[c])
-        gamma, beta, mean, var = (_t64(v) for v in (bn.weight, bn.bias, bn.running_mean, bn.running_var))
-        s = (gamma / torch.sqrt(var + 1e-5))
-        mass = fn.conv2d(x.abs(), (_t64(conv.weight) * s[:, None, None, None]).abs(), padding=size // 2).numpy() + np.abs((beta - mean * s).numpy())[None, :, None, None]
-        gate = ((conv.in_channels * size * size + 2) * U if GATES[precision] is None else GATES[precision]) * mass
-        y_dev = m.read_layer(c, B).cpu().numpy()
-        flips = (pre.numpy() > 0) != (y_dev > 0)
-        assert (np.abs(pre.numpy())[flips] <= gate[flips]).all(), (net, precision, c, int(flips.sum()))
-        got, ref = neck_grads[c].cpu().numpy().astype(np.float64), np.abs(want[c]).max()
-        assert got.shape == want[c].shape and ref > 0
-        e_dev, e_32 = (got - want[c]) / ref, (floor[c] - want[c]) / ref
-        rms = lambda e: float(np.sqrt(np.mean(e * e)))
-        print("%s %s conv %d (%d flips): rms %.3g (float32 floor %.3g, ratio %.2f)  max %.3g (floor %.3g, ratio %.2f)" % (
-            net, precision, c, int(flips.sum()), rms(e_dev), rms(e_32), rms(e_dev) / rms(e_32), np.abs(e_dev).max(), np.abs(e_32).max(), np.abs(e_dev).max() / np.abs(e_32).max()))
-        if not (rms(e_dev) <= 4 * rms(e_32) and np.abs(e_dev).max() <= 4 * np.abs(e_32).max()):
-            over.append((c, round(rms(e_dev) / rms(e_32), 2), round(float(np.abs(e_dev).max() / np.abs(e_32).max()), 2)))
+    over = over_the_floor("%s %s" % (net, precision), m, layers, NECK[net], precision, B, neck_grads, want, floor, pres)
     if net == "mini" and width is None:                               # the fan-out sum: layer 12 is read by conv 13 and by route 16
         assert readers[12] == [13, 16] and neck_grads[12].abs().sum() > 0
         for cut in ((12, 13), (12, 16)):
@@ -286,41 +200,7 @@ def test_the_loss_falls_along_the_neck_gradient_by_what_it_says(tmp_path):
     _, _, grads = t.neck_gradients(xd, bnd)
     l0 = float(t.last_components[0].item())
     assert sorted(grads) == NECK["mini"]
-    g2 = sum(float((dw.double() ** 2).sum()) for dw in grads.values())
-    W0 = {c: _conv_of(m, c).weight.detach().clone() for c in grads}
-    heads = [h for h, _ in m.head_layers()]
-
-    def cpu(s, dtype=torch.float64):
-        with torch.no_grad():
-            val, _, _ = _cpu_neck(m, t, B, dtype, weights={c: W0[c].double() + s * grads[c].cpu().double() for c in grads})
-        val = {k: v.detach() for k, v in val.items()}
-        acts = [val[h - 1].numpy() for h in heads]
-        ws = [_t64(_conv_of(m, h).weight).numpy() for h in heads]
-        bs = [_t64(_conv_of(m, h).bias).numpy() for h in heads]
-        if dtype != torch.float64:
-            ws, bs = [a.astype(F) for a in ws], [a.astype(F) for a in bs]
-        return cpu_head_model(acts, ws, bs, t.heads, images, 4, None if dtype == torch.float64 else dtype)["loss"]
-    noise_at = lambda s: abs(cpu(s, torch.float32) - cpu(s))
-    noise = noise_at(0.0)
-    eps = gap_cpu = None
-    for e in (1e-2, 3e-3, 1e-3, 3e-4, 1e-4, 3e-5, 1e-5, 3e-6, 1e-6, 3e-7, 1e-7):
-        fd, dd = (cpu(e) - cpu(-e)) / (2 * e), (cpu(e / 10) - cpu(-e / 10)) / (2 * e / 10)
-        if abs(fd - dd) >= 10 * noise / e:
-            eps, gap_cpu = e, abs(fd - dd)
-    assert eps is not None
-    noise = max(noise, noise_at(eps), noise_at(-eps))
-    allowed = 4 * gap_cpu + 2 * noise / (2 * eps)
-    masters = {c: W0[c].cuda() for c in grads}
-
-    def loss_at(s):
-        for c in grads:
-            m.update_conv_weight(c, masters[c] + s * grads[c])
-        t.forward_loss(xd, bnd)
-        return float(t.last_components[0].item())
-    fd_dev = (loss_at(eps) - loss_at(-eps)) / (2 * eps)
-    assert loss_at(0.0) == l0                                         # the weights are back, bit for bit
-    print("||g||^2 device %.8g; eps %.0e; central difference device %.8g; gap %.4g, allowed %.4g (cpu gap %.4g, noise %.4g)" % (g2, eps, fd_dev, abs(fd_dev - g2), allowed, gap_cpu, noise))
-    assert g2 > 0 and abs(fd_dev - g2) <= allowed
+    check_directional_derivative(m, t, xd, bnd, grads, cpu_scope_loss(m, t, B, images, grads, "neck"), l0)
 
 
 # ------------------------------------------------------------------------------------------ 10. the training step
@@ -335,36 +215,7 @@ def test_training_step_on_the_neck(tmp_path, precision, width):
     xd, bnd = _frames(3, 64, width), [torch.from_numpy(im) for im in step_batch()[1]]
     m, t = _neck_trainer(tmp_path, text, 64, precision, width)
     layers = [12, 13, 14, 17, 20, 21, 22]
-    losses = []
-    host = lambda a: None if a is None else a.detach().cpu().numpy()
-    for step, kind in enumerate(["sgd", "adam", "adam"]):
-        if step < 2:
-            t.optimizer = HeadOptimizer(kind, lr=1e-4)
-        _, hg, ng = t.neck_gradients(xd, bnd)
-        grads = {k: (host(dw), host(db)) for k, (dw, db) in hg.items()}
-        grads.update({k: (host(dw), None) for k, dw in ng.items()})
-        assert sorted(grads) == layers
-        masters = t._masters(grads, xd.device)
-        before = {k: (host(masters[k][0]), host(masters[k][1])) for k in layers}
-        state = {k: {n: host(v) for n, v in t.optimizer.state.get(k, {}).items() if n.startswith("exp_avg")} for k in layers}
-        losses.append(float(t.feed_forward_through_model(xd, bnd)))
-        for k in layers:
-            st = t.optimizer.state[k]
-            assert st["step"] == (1 if step < 2 else 2) and st["weight"] is t._head_masters[k][0]
-            for which, name, sfx in ((0, "weight", ""), (1, "bias", "_bias")):
-                if before[k][which] is None:
-                    assert which == 1 and "bias" not in st and k in NECK["mini"]
-                    continue
-                zero = np.zeros_like(before[k][which])
-                w1, m1, v1 = opt_update_f32(kind, before[k][which], grads[k][which], state[k].get("exp_avg" + sfx, zero), state[k].get("exp_avg_sq" + sfx, zero),
-                                            1e-4, step=st["step"])
-                assert np.array_equal(bits(host(st[name])), bits(w1)), (precision, step, k, name)
-                if kind == "adam":
-                    assert np.array_equal(bits(host(st["exp_avg" + sfx])), bits(m1)) and np.array_equal(bits(host(st["exp_avg_sq" + sfx])), bits(v1)), (precision, step, k, name)
-        image = m.packed_weights()
-        stream = m.weight_stream().copy()                             # synchronises the masters into the module's parameters
-        assert _same(_conv_of(m, 12).weight, t._head_masters[12][0]) and np.array_equal(image, pack(m._plan, stream)), (precision, step)
-    assert losses[1] != losses[0] and np.isfinite(losses).all(), losses
+    losses = check_training_steps(m, t, xd, bnd, "neck", layers, NECK["mini"], [12])
     # the block path on a twin: the same bits with and without the new option
     out = []
     for name, options in (("b0", {"keep_head_inputs": 1, "keep_block_inputs": 1}), ("b1", dict(KEEP, keep_block_inputs=1))):

@@ -201,7 +201,8 @@ def test_trainer_asks_for_the_neck_options():
     for opts, missing in (({}, "keep_neck_activations"), ({"keep_head_inputs": 1}, "keep_neck_activations"), ({"keep_neck_activations": 1}, "keep_head_inputs"),
                           ({"keep_head_inputs": 1, "keep_block_inputs": 1}, "keep_neck_activations")):
         t = DarknetTrainer(stub(opts), trainable="neck")
-        with pytest.raises(RuntimeError, match=missing):
-            t.neck_gradients(np.zeros((1, 3, 64, 64), F), [None])
+        for call in (t.neck_gradients, t.gradients, lambda x, b: DarknetTrainer(stub(opts)).gradients(x, b, scope="neck")):
+            with pytest.raises(RuntimeError, match=missing):
+                call(np.zeros((1, 3, 64, 64), F), [None])
         with pytest.raises(RuntimeError, match=missing):
             t.feed_forward_through_model(np.zeros((1, 3, 64, 64), F), [None])
