@@ -440,28 +440,27 @@ int rtod_conv_wgrad(const float* dz_dev, const float* x_dev, int batch, int cout
 int rtod_conv1x1_dgrad(const float* w_dev, const float* dz_dev, const float* y_dev, float slope, int batch, int cout, int cin, int pixels,
                        float* dx_dev, void* stream) {
     RTOD_GUARD_BEGIN
-    return launch_conv_dgrad("conv1x1_dgrad", w_dev, nullptr, dz_dev, y_dev, slope, batch, cout, cin, 1, pixels, 1, dx_dev, (hipStream_t)stream);
+    return launch_conv_dgrad("conv1x1_dgrad", w_dev, nullptr, dz_dev, y_dev, slope, batch, cout, cin, 1, pixels, 1, 1, dx_dev, (hipStream_t)stream);
     RTOD_GUARD_END
 }
 
 int rtod_conv_dgrad(const float* w_oihw_dev, const double* row_scale_dev, const float* dz_dev, const float* y_dev, float slope,
                     int batch, int cout, int cin, int height, int width, int size, float* dx_dev, void* stream) {
     RTOD_GUARD_BEGIN
-    return launch_conv_dgrad("conv_dgrad", w_oihw_dev, row_scale_dev, dz_dev, y_dev, slope, batch, cout, cin, height, width, size, dx_dev, (hipStream_t)stream);
+    return launch_conv_dgrad("conv_dgrad", w_oihw_dev, row_scale_dev, dz_dev, y_dev, slope, batch, cout, cin, height, width, size, 1, dx_dev, (hipStream_t)stream);
     RTOD_GUARD_END
 }
 
 int rtod_conv_dgrad_s2(const float* w_oihw_dev, const double* row_scale_dev, const float* dz_dev, const float* y_dev, float slope,
                        int batch, int cout, int cin, int height, int width, int size, float* dx_dev, void* stream) {
     RTOD_GUARD_BEGIN
-    return launch_conv_dgrad_s2(w_oihw_dev, row_scale_dev, dz_dev, y_dev, slope, batch, cout, cin, height, width, size, dx_dev, (hipStream_t)stream);
+    return launch_conv_dgrad("conv_dgrad_s2", w_oihw_dev, row_scale_dev, dz_dev, y_dev, slope, batch, cout, cin, height, width, size, 2, dx_dev, (hipStream_t)stream);
     RTOD_GUARD_END
 }
 
 int rtod_conv_wgrad_s2_workspace(int batch, int cout, int cin, int height, int width, int size, size_t* bytes) {
     if (!bytes) { set_error("conv_wgrad_s2_workspace: null pointer"); return RTOD_E_ARG; }
-    if (int rc = wgrad_check_shape("conv_wgrad_s2_workspace", batch, cout, cin, height, width, size)) return rc;
-    if (int rc = wgrad_s2_check("conv_wgrad_s2_workspace", size)) return rc;
+    if (int rc = wgrad_check_shape("conv_wgrad_s2_workspace", batch, cout, cin, height, width, size, 2)) return rc;
     *bytes = wgrad_workspace_bytes(batch, cout, cin, (height - 1) / 2 + 1, (width - 1) / 2 + 1, size, wgrad_tile_cap(cout, cin, size));
     return RTOD_OK;
 }

@@ -365,22 +365,21 @@ int launch_yolo_loss_grad(const float* pred, int batch, int n_rows, int num_clas
 // weight / bias gradient of a 1x1 or 3x3 convolution on the exact-fp32 MFMA, K slices added in order, an optional double scale
 // per row of dW (wgrad.hip).  One path under both entries: rtod_conv1x1_wgrad is size = 1, h = 1, w = pixels, cap =
 // WGRAD_MAX_SLICES, no row scale; rtod_conv_wgrad passes cap = wgrad_tile_cap.  `who` names the entry in the error texts.
+// stride 2 (rtod_conv_wgrad_s2, size 3 alone): h x w is the conv's INPUT map, which x lives on; the same kernel with the tap
+// positions doubled.
 constexpr int WGRAD_MAX_SLICES = 16;
 int wgrad_tile_cap(int cout, int cin, int size);                    // min(16, ceil(1024 / tiles))
 int64_t wgrad_slice_len(int64_t K, int cap);
 size_t wgrad_workspace_bytes(int batch, int cout, int cin, int h, int w, int size, int cap);
-int wgrad_check_shape(const char* who, int batch, int cout, int cin, int h, int w, int size);
+int wgrad_check_shape(const char* who, int batch, int cout, int cin, int h, int w, int size, int stride = 1);
 int launch_wgrad(const char* who, const float* dz, const float* x, int batch, int cout, int cin, int h, int w, int size, int cap,
                  const double* row_scale, float* dw, float* db, void* ws, size_t ws_bytes, hipStream_t s, int stride = 1);
-int wgrad_s2_check(const char* who, int size);                      // rtod_conv_wgrad_s2: stride 2 (h x w the conv's input map) takes size 3 alone
-// data gradient of a 1x1 or 3x3 / stride 1 / same-padding convolution with the leaky-ReLU derivative of the stored activation in its
-// epilogue and an optional double scale per filter folded into the weights (dgrad.hip).  One path under both entries:
-// rtod_conv1x1_dgrad is size = 1, h = 1, w = pixels, no row scale.  `who` names the entry in the error texts.
+// data gradient of a 1x1 or 3x3 / same-padding convolution with the leaky-ReLU derivative of the stored activation in its epilogue
+// and an optional double scale per filter folded into the weights (dgrad.hip): one tile body under three geometries.  One path under
+// the three entries: rtod_conv1x1_dgrad is size = 1, h = 1, w = pixels, no row scale; rtod_conv_dgrad_s2 is stride = 2 (size 3
+// alone), h x w the conv's INPUT map, the same chains over parity-class tiles.  `who` names the entry in the error texts.
 int launch_conv_dgrad(const char* who, const float* w, const double* row_scale, const float* dz, const float* y, float slope, int batch, int cout,
-                      int cin, int h, int w_, int size, float* dx, hipStream_t s);
-// ... of a 3x3 / stride 2 / pad 1 convolution, h x w its input map: the same chains over parity-class tiles (dgrad.hip)
-int launch_conv_dgrad_s2(const float* w, const double* row_scale, const float* dz, const float* y, float slope, int batch, int cout, int cin,
-                         int h, int w_, int size, float* dx, hipStream_t s);
+                      int cin, int h, int w_, int size, int stride, float* dx, hipStream_t s);
 // out = m(y) * (((c0 + c1) + c2) + c3): the fan-out sum of the gradient walk, 1 to 4 contributions, in one launch (grad_join.hip)
 int launch_grad_join(const float* const* contributions, int count, const float* y, float slope, int64_t n, float* out, hipStream_t s);
 // backward of the 2x upsample (bilinear align_corners=False, or nearest) in gather form, the producing conv's mask fused (upsample_grad.hip)

@@ -22,7 +22,8 @@
 // 3x3 convs (rtod_conv_wgrad, TAPS = 9).  The same kernel as an implicit GEMM: the column index is n = c * 9 + tap, OIHW order, so
 // the dW stores stay coalesced, and B[n][k] = x[b, c, y + ky - 1, x + kx - 1], an exact zero outside the map.  A thread's eight
 // columns (channel and tap offsets) do not depend on k and are resolved once; k -> (b, y, x) costs two divisions per staged chunk.
-// The 1x1 instance (TAPS = 1) is the kernel above, instruction for instruction.  The cap of that entry also sees the
+// Stride 2 (rtod_conv_wgrad_s2) is the same column with the tap positions doubled: k runs over the conv's OUTPUT map, x lives on
+// its input map.  The 1x1 instance (TAPS = 1) reads x where it reads dz.  The cap of rtod_conv_wgrad also sees the
 // number of tiles (wgrad_tile_cap: a 13 x 13 block has a thousand tiles already and is not sliced), and its reduce kernel
 // multiplies the reduced sum of a row by a caller-supplied double once — the frozen BatchNorm scale of the conv.
 #include "rtod_internal.h"
@@ -58,18 +59,13 @@ size_t wgrad_workspace_bytes(int batch, int cout, int cin, int h, int w, int siz
     return sizeof(float) * (size_t)S * ((size_t)cout * cin * size * size + (size_t)cout);
 }
 
-// what the stride-2 instance takes behind the arguments of the stride-1 kernel, which keeps its argument list and its code: the map x lives on
-struct WgradS2 { int xh, xw; };
-
-// part: [S][cout][ncol] slice sums of dW (ncol = cin * TAPS), then [S][cout] slice sums of db.  TAPS == 1: H and W are not read.
-// STRIDE == 2 (rtod_conv_wgrad_s2, TAPS == 9): pixels, H, W describe the map of dz, the conv's OUTPUT, which k = (b, oy, ox) runs over;
-// B[n][k] = x[b, c, 2 oy + ky - 1, 2 ox + kx - 1] on the xh x xw input map, an exact zero outside it
-template <int TAPS, int STRIDE = 1, class... Extra>
+// part: [S][cout][ncol] slice sums of dW (ncol = cin * TAPS), then [S][cout] slice sums of db.  pixels and W describe the map of dz, the
+// conv's OUTPUT, which k = (b, oy, ox) runs over; B[n][k] = x[b, c, STRIDE * oy + ky - 1, STRIDE * ox + kx - 1] on the xh x xw input
+// map (stride 1: the same map), an exact zero outside it.  TAPS == 1: W, xh and xw are not read.
+template <int TAPS, int STRIDE = 1>
 __global__ __launch_bounds__(256)
-void wgrad_slice_kernel(const float* __restrict__ dz, const float* __restrict__ x, int cout, int cin, int pixels, int H, int W, int K, int slice_len,
-                        int grid_m, int grid_n, float* __restrict__ part, float* __restrict__ part_db, Extra... extra) {
-    [[maybe_unused]] int xh = H, xw = W;
-    if constexpr (sizeof...(Extra) > 0) { const WgradS2 e = (extra, ...); xh = e.xh; xw = e.xw; }
+void wgrad_slice_kernel(const float* __restrict__ dz, const float* __restrict__ x, int cout, int cin, int pixels, int W, int xh, int xw, int K, int slice_len,
+                        int grid_m, int grid_n, float* __restrict__ part, float* __restrict__ part_db) {
     const int ncol = cin * TAPS;
     __shared__ __attribute__((aligned(16))) float smem[2 * WG_T * WG_LD];
     float* sA = smem;
@@ -118,14 +114,10 @@ void wgrad_slice_kernel(const float* __restrict__ dz, const float* __restrict__ 
             ra[i] = (kok && o < cout) ? dz[((int64_t)b * cout + o) * pixels + p] : 0.f;
             if (TAPS == 1) {
                 rb[i] = (kok && c < cin) ? x[((int64_t)b * cin + c) * pixels + p] : 0.f;
-            } else if constexpr (STRIDE == 2) {
-                const int yy = 2 * py + col_dy[i], xx = 2 * px + col_dx[i];
-                const bool in = kok && c < ncol && yy >= 0 && yy < xh && xx >= 0 && xx < xw;
-                rb[i] = in ? x[((int64_t)b * cin + col_c[i]) * ((int64_t)xh * xw) + (int64_t)yy * xw + xx] : 0.f;
             } else {
-                const int yy = py + col_dy[i], xx = px + col_dx[i];
-                const bool in = kok && c < ncol && yy >= 0 && yy < H && xx >= 0 && xx < W;
-                rb[i] = in ? x[((int64_t)b * cin + col_c[i]) * pixels + yy * W + xx] : 0.f;
+                const int yy = STRIDE * py + col_dy[i], xx = STRIDE * px + col_dx[i];
+                const bool in = kok && c < ncol && yy >= 0 && yy < xh && xx >= 0 && xx < xw;
+                rb[i] = in ? x[((int64_t)b * cin + col_c[i]) * xh * xw + yy * xw + xx] : 0.f;
             }
         }
     };
@@ -188,28 +180,24 @@ void wgrad_reduce_kernel(const float* __restrict__ part, const float* __restrict
     }
 }
 
-int wgrad_check_shape(const char* who, int batch, int cout, int cin, int h, int w, int size) {
+// stride 2 (h x w the conv's input map) takes size 3 alone
+int wgrad_check_shape(const char* who, int batch, int cout, int cin, int h, int w, int size, int stride) {
     const int64_t K = (int64_t)batch * h * w, taps = (int64_t)size * size;
     if (batch < 1 || cout < 1 || cin < 32 || cin % 32 || h < 1 || w < 1 || (size != 1 && size != 3)) {
         set_error("%s: unsupported shape (batch=%d cout=%d cin=%d h=%d w=%d size=%d; cin must be a multiple of 32, size 1 or 3)", who, batch, cout, cin, h, w, size);
         return RTOD_E_ARG;
     }
     if ((int64_t)h * w > INT32_MAX || K > INT32_MAX - 64 || (int64_t)cout * cin * taps > INT32_MAX) { set_error("%s: batch * h * w or cout * cin * size * size exceeds int32", who); return RTOD_E_ARG; }
+    if (stride == 2 && size != 3) { set_error("%s: unsupported shape (size=%d; the stride-2 entry takes 3x3 convs)", who, size); return RTOD_E_ARG; }
     return RTOD_OK;
 }
 
 // `who` names the entry in every error text; `cap` is the entry's cap on the slice count (at most WGRAD_MAX_SLICES).  stride 2
 // (rtod_conv_wgrad_s2: size 3, pad 1): h x w is the conv's INPUT map, dz lives on the output map and K = batch * ho * wo
-int wgrad_s2_check(const char* who, int size) {
-    if (size != 3) { set_error("%s: unsupported shape (size=%d; the stride-2 entry takes 3x3 convs)", who, size); return RTOD_E_ARG; }
-    return RTOD_OK;
-}
-
 int launch_wgrad(const char* who, const float* dz, const float* x, int batch, int cout, int cin, int h, int w, int size, int cap,
                  const double* row_scale, float* dw, float* db, void* ws, size_t ws_bytes, hipStream_t s, int stride) {
     if (!dz || !x || !dw || !ws) { set_error("%s: null pointer", who); return RTOD_E_ARG; }
-    if (int rc = wgrad_check_shape(who, batch, cout, cin, h, w, size)) return rc;
-    if (stride == 2) { if (int rc = wgrad_s2_check(who, size)) return rc; }
+    if (int rc = wgrad_check_shape(who, batch, cout, cin, h, w, size, stride)) return rc;
     const int xh = h, xw = w;
     if (stride == 2) { h = (xh - 1) / 2 + 1; w = (xw - 1) / 2 + 1; }  // from here on the map that k runs over
     if (ws_bytes < wgrad_workspace_bytes(batch, cout, cin, h, w, size, cap)) { set_error("%s: workspace too small", who); return RTOD_E_ARG; }
@@ -222,9 +210,11 @@ int launch_wgrad(const char* who, const float* dz, const float* x, int batch, in
     float* part = (float*)ws;
     float* part_db = part + (int64_t)S * cout * ncol;
     float* pdb = db ? part_db : (float*)nullptr;
-    if (stride == 2) hipLaunchKernelGGL((wgrad_slice_kernel<9, 2, WgradS2>), dim3((unsigned)(tiles * S)), dim3(256), 0, s, dz, x, cout, cin, pixels, h, w, (int)K, L, gm, gn, part, pdb, WgradS2{xh, xw});
-    else if (size == 1) hipLaunchKernelGGL(wgrad_slice_kernel<1>, dim3((unsigned)(tiles * S)), dim3(256), 0, s, dz, x, cout, cin, pixels, h, w, (int)K, L, gm, gn, part, pdb);
-    else hipLaunchKernelGGL(wgrad_slice_kernel<9>, dim3((unsigned)(tiles * S)), dim3(256), 0, s, dz, x, cout, cin, pixels, h, w, (int)K, L, gm, gn, part, pdb);
+#define RTOD_WGRAD(...) hipLaunchKernelGGL((wgrad_slice_kernel<__VA_ARGS__>), dim3((unsigned)(tiles * S)), dim3(256), 0, s, dz, x, cout, cin, pixels, w, xh, xw, (int)K, L, gm, gn, part, pdb)
+    if (stride == 2) RTOD_WGRAD(9, 2);
+    else if (size == 1) RTOD_WGRAD(1);
+    else RTOD_WGRAD(9);
+#undef RTOD_WGRAD
     const int64_t n = (int64_t)cout * ncol + (db ? cout : 0);
     hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, part, part_db, (int64_t)cout * ncol, cout, S, row_scale, ncol, dw, db);
     return hip_fail(hipGetLastError(), (std::string(who) + " launch").c_str());

@@ -179,11 +179,13 @@ def _wgrad(who, dz, x, size, row_scale, bias, stride=1):
     B, cout, cin, H, W = dz.size(0), dz.size(1), x.size(1), x.size(2), x.size(3)
     shape = (B, cout, cin, H * W) if size is None else (B, cout, cin, H, W, int(size))
     lib, dev = _ffi.lib(), dz.device
+    entry, entry_workspace = ((lib.rtod_conv1x1_wgrad, lib.rtod_conv1x1_wgrad_workspace) if size is None else
+                              (lib.rtod_conv_wgrad_s2, lib.rtod_conv_wgrad_s2_workspace) if s2 else (lib.rtod_conv_wgrad, lib.rtod_conv_wgrad_workspace))
     key = (dev.index, stride) + shape
     ws = _wgrad_ws.get(key)
     if ws is None:
         nbytes = C.c_size_t()
-        _ffi.check((lib.rtod_conv1x1_wgrad_workspace if size is None else lib.rtod_conv_wgrad_s2_workspace if s2 else lib.rtod_conv_wgrad_workspace)(*shape, C.byref(nbytes)))
+        _ffi.check(entry_workspace(*shape, C.byref(nbytes)))
         if len(_wgrad_ws) > 16:
             _wgrad_ws.clear()
         ws = _wgrad_ws[key] = (torch.empty((nbytes.value + 7) // 8, dtype=torch.float64, device=dev), nbytes.value)
@@ -192,7 +194,7 @@ def _wgrad(who, dz, x, size, row_scale, bias, stride=1):
     db = torch.empty(cout, dtype=torch.float32, device=dev) if bias else None
     scale = () if size is None else (_scale_ptr(row_scale, cout, dev),)
     with torch.cuda.device(dev):
-        _ffi.check((lib.rtod_conv1x1_wgrad if size is None else lib.rtod_conv_wgrad_s2 if s2 else lib.rtod_conv_wgrad)(
+        _ffi.check(entry(
             C.c_void_p(dz.data_ptr()), C.c_void_p(x.data_ptr()), *shape, *scale, C.c_void_p(dw.data_ptr()), C.c_void_p(db.data_ptr()) if bias else None,
             C.c_void_p(ws[0].data_ptr()), ws[1], _stream(dev)))
     return dw, db
@@ -255,10 +257,11 @@ def _dgrad(who, w, dz, size, row_scale, y, slope, stride=1, in_hw=None):
     B, cout, cin = dz.size(0), dz.size(1), w.size(1)
     shape = (B, cout, cin, H * W) if size is None else (B, cout, cin, H, W, k)
     lib, dev = _ffi.lib(), dz.device
+    entry = lib.rtod_conv1x1_dgrad if size is None else lib.rtod_conv_dgrad_s2 if stride == 2 else lib.rtod_conv_dgrad
     dx = torch.empty((B, cin, H, W), dtype=torch.float32, device=dev)
     scale = () if size is None else (_scale_ptr(row_scale, cout, dev),)
     with torch.cuda.device(dev):
-        _ffi.check((lib.rtod_conv1x1_dgrad if size is None else lib.rtod_conv_dgrad_s2 if stride == 2 else lib.rtod_conv_dgrad)(
+        _ffi.check(entry(
             C.c_void_p(w.data_ptr()), *scale, C.c_void_p(dz.data_ptr()), C.c_void_p(y.data_ptr()) if y is not None else None, float(slope), *shape,
             C.c_void_p(dx.data_ptr()), _stream(dev)))
     return dx

@@ -15,6 +15,16 @@ change of the arithmetic, of the slice rule or of the summation order and has to
 * Steps: mini_cfg(64, 64) with both keep options, trainable="blocks", on the batch of test_block_grad_gpu._batch(): one SGD step,
   then two Adam steps; after each phase the packed image, every master and every moment are hashed.
 * Updates: update_conv / update_conv_weight of every trained conv with its master; the packed image keeps its hash.
+
+A second record, tests/golden/grad_bits.json, holds the data gradients (csrc/dgrad.hip through rtod_conv1x1_dgrad, rtod_conv_dgrad and
+rtod_conv_dgrad_s2) and the stride-2 weight gradient (rtod_conv_wgrad_s2) to the bits they had BEFORE their kernels were put on one
+tile loop; the same dumper writes it (``--grad``) and it is not regenerated either.
+
+* Data gradients: SHA-256 of dx on neck_grad_cases.DGRAD_SHAPES (1x1 entry; rtod_conv_dgrad sizes 1 and 3) and on
+  backbone_grad_cases.S2_SHAPES (stride 2), plain and with the random signed float64 row scale of CAP_SHAPE above, with y given and
+  slope 0.1; y is a standard normal with every 7th element set to 0.0, so the mask sees positives, negatives and exact zeros.  One
+  further digest per size runs without y.
+* Stride-2 weight gradients: dW and db on S2_SHAPES, and with the row scale on the ragged-Cout shape.
 """
 import hashlib
 import json
@@ -26,6 +36,8 @@ import torch
 
 from realtimeobjectdetection_amd import cfgs, train as T
 from realtimeobjectdetection_amd.train import HeadOptimizer
+from backbone_grad_cases import S2_SHAPES, out_hw
+from neck_grad_cases import DGRAD_SHAPES
 from test_block_grad_gpu import _batch, _block_trainer
 
 pytestmark = pytest.mark.gpu
@@ -36,6 +48,15 @@ HEAD_SHAPES = [(2, 18, 32, 2, 2), (3, 255, 96, 13, 13), (1, 64, 64, 127, 1)]    
 CAP_SHAPE = (2, 256, 928, 4, 4)                                                    # size 3: 524 tiles, at most 2 slices
 WGRAD_CASES = [("conv1x1_wgrad", 1, s) for s in HEAD_SHAPES] + [("conv_wgrad", size, s) for size in (1, 3) for s in HEAD_SHAPES + [CAP_SHAPE]]
 PRECISIONS = ["fp32", "f16s3"]
+
+GRAD_RECORD = os.path.join(os.path.dirname(RECORD), "grad_bits.json")
+RAGGED = (3, 255, 96, 13, 13)                                                      # Cout 255, a Cin tail tile, tiles across images
+# (entry, size, stride, shape, scaled, masked): stride 2 reads shape's H x W as the conv's INPUT map
+GRAD_CASES = ([("conv1x1_dgrad", 1, 1, s, False, True) for s in DGRAD_SHAPES]
+              + [("conv_dgrad", size, 1, s, scaled, True) for size in (1, 3) for s in DGRAD_SHAPES for scaled in (False, True)]
+              + [("conv_dgrad", size, 1, RAGGED, False, False) for size in (1, 3)]
+              + [("conv_dgrad", 3, 2, s, scaled, True) for s in S2_SHAPES for scaled in (False, True)]
+              + [("conv_wgrad", 3, 2, s, False, False) for s in S2_SHAPES] + [("conv_wgrad", 3, 2, RAGGED, True, False)])
 
 
 def sha(t):
@@ -60,6 +81,34 @@ def wgrad_digest(entry, size, shape):
         dw, db = T.conv_wgrad_async(dz, x, size, row_scale=scale, bias=True)
     assert tuple(dw.shape) == (cout, cin, size, size) and tuple(db.shape) == (cout,)
     return {"dw": sha(dw), "db": sha(db)}
+
+
+def grad_key(entry, size, stride, shape, scaled, masked):
+    return "%s/size%d/stride%d/%s/%s%s" % (entry, size, stride, "x".join(str(v) for v in shape), "scaled" if scaled else "plain",
+                                           "" if masked or "wgrad" in entry else "/linear")
+
+
+def grad_digest(entry, size, stride, shape, scaled, masked):
+    """{"dx"} of one data-gradient call or {"dw", "db"} of one stride-2 weight-gradient call on seeded inputs."""
+    B, cout, cin, H, W = shape
+    Ho, Wo = out_hw(H, W) if stride == 2 else (H, W)
+    rng = np.random.RandomState(1000 * B + 10 * cout + H * W + size + 7 * stride)
+    w = torch.from_numpy(rng.standard_normal((cout, cin, size, size)).astype(F)).cuda()
+    dz = torch.from_numpy(rng.standard_normal((B, cout, Ho, Wo)).astype(F)).cuda()
+    y = rng.standard_normal((B, cin, H, W)).astype(F)                 # the conv's input map: y of a data gradient, x of a weight gradient
+    scale = torch.from_numpy(rng.uniform(0.2, 3.0, cout) * rng.choice([-1.0, 1.0], cout)).cuda() if scaled else None
+    if entry == "conv_wgrad":
+        dw, db = T.conv_wgrad_async(dz, torch.from_numpy(y).cuda(), size, row_scale=scale, bias=True, stride=stride)
+        assert tuple(dw.shape) == (cout, cin, size, size) and tuple(db.shape) == (cout,)
+        return {"dw": sha(dw), "db": sha(db)}
+    y.reshape(-1)[::7] = 0.0                                          # exact zeros next to the negatives: the !(y > 0) branch
+    y = torch.from_numpy(y).cuda() if masked else None
+    if entry == "conv1x1_dgrad":
+        dx = T.conv1x1_dgrad_async(w, dz, y=y, slope=0.1)
+    else:
+        dx = T.conv_dgrad_async(w, dz, size, row_scale=scale, y=y, slope=0.1, stride=stride, in_hw=(H, W))
+    assert tuple(dx.shape) == (B, cin, H, W)
+    return {"dx": sha(dx)}
 
 
 def _state_digest(m, t):
@@ -93,8 +142,8 @@ def step_digest(precision, d):
     return out
 
 
-def _record():
-    with open(RECORD) as f:
+def _record(path=RECORD):
+    with open(path) as f:
         return json.load(f)["digests"]
 
 
@@ -103,6 +152,13 @@ def test_weight_gradient_has_the_recorded_bits(entry, size, shape):
     got = wgrad_digest(entry, size, shape)
     print("TRAIN BITS %s: %s" % (wgrad_key(entry, size, shape), got))
     assert got == _record()[wgrad_key(entry, size, shape)]
+
+
+@pytest.mark.parametrize("case", GRAD_CASES, ids=lambda c: grad_key(*c))
+def test_data_and_stride2_gradients_have_the_recorded_bits(case):
+    got = grad_digest(*case)
+    print("GRAD BITS %s: %s" % (grad_key(*case), got))
+    assert got == _record(GRAD_RECORD)[grad_key(*case)]
 
 
 @pytest.mark.parametrize("precision", PRECISIONS)

@@ -4,7 +4,9 @@ tests/test_train_bits_gpu.py: writes tests/golden/train_bits.json.  Needs the GP
 
 The record is a before-image: it is taken from the library of the commit named in "recorded_from" and is NOT regenerated when
 the code around the kernels changes (the test exists to show that it still gives these bits).
-    python tools/dump_train_bits.py COMMIT [FILE]"""
+    python tools/dump_train_bits.py COMMIT [FILE]
+    python tools/dump_train_bits.py --grad COMMIT [FILE]    only tests/golden/grad_bits.json: the data gradients and the stride-2 weight
+                                                            gradient on that file's GRAD_CASES; train_bits.json is left alone"""
 import json
 import os
 import pathlib
@@ -16,16 +18,22 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import test_train_bits_gpu as T  # noqa: E402
 
-commit = sys.argv[1]
-out = sys.argv[2] if len(sys.argv) > 2 else T.RECORD
-digests = {T.wgrad_key(*case): T.wgrad_digest(*case) for case in T.WGRAD_CASES}
-with tempfile.TemporaryDirectory() as d:
-    for p in T.PRECISIONS:
-        digests["step/" + p] = T.step_digest(p, pathlib.Path(d))
+args = [a for a in sys.argv[1:] if a != "--grad"]
+grad = len(args) < len(sys.argv) - 1
+commit = args[0]
+out = args[1] if len(args) > 1 else T.GRAD_RECORD if grad else T.RECORD
+if grad:
+    digests = {T.grad_key(*case): T.grad_digest(*case) for case in T.GRAD_CASES}
+    content = "sha256 of the float32 bytes of dx, or of dW / db"
+else:
+    digests = {T.wgrad_key(*case): T.wgrad_digest(*case) for case in T.WGRAD_CASES}
+    content = "sha256 of the float32 bytes of dW / db, of the packed weight image, and of every master and moment"
+    with tempfile.TemporaryDirectory() as d:
+        for p in T.PRECISIONS:
+            digests["step/" + p] = T.step_digest(p, pathlib.Path(d))
 for k, v in digests.items():
     print(k, json.dumps(v, sort_keys=True))
 os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
 with open(out, "w") as f:
-    json.dump({"recorded_from": commit, "content": "sha256 of the float32 bytes of dW / db, of the packed weight image, and of every master and moment",
-               "digests": digests}, f, indent=1, sort_keys=True)
+    json.dump({"recorded_from": commit, "content": content, "digests": digests}, f, indent=1, sort_keys=True)
     f.write("\n")

@@ -20,14 +20,12 @@ and the split of (d)'s walk on (d)'s model, each kernel group alone on the opera
 Rates are over the USEFUL flops: 2 B Ho Wo k^2 Cout Cin of a conv's data or weight gradient, stride 2 included.  Alternating rounds,
 HIP events around windows of --iters calls, medians.  The learning rate is tiny (1e-9): the weights stay where they are over a run,
 and no kernel's time depends on them.  The peak of torch's allocator is taken over one backbone step after a reset of its statistics."""
-import argparse, json, os, statistics, sys, tempfile
+import argparse, json, os, statistics, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import numpy as np
+import grad_walk
 import torch
-from realtimeobjectdetection_amd import _ffi, cfgs, synth, train as T
+from realtimeobjectdetection_amd import _ffi, cfgs, synth
 from realtimeobjectdetection_amd.cfg import parse_cfg_text, build_ir
-from realtimeobjectdetection_amd.darknet import Darknet
-from realtimeobjectdetection_amd.train import DarknetTrainer, HeadOptimizer
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--res", type=int, default=416); ap.add_argument("--batch", type=int, default=8)
@@ -39,63 +37,13 @@ assert torch.cuda.is_available(), "exp_backbone_grad.py measures on the GPU"
 LR = 1e-9
 
 
-def events(fn):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(args.iters):
-        fn()
-    e1.record(); torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / args.iters * 1e3                 # us per call
-
-
-def trainer(cfg_text, ir, precision, trainable, options):
-    with tempfile.TemporaryDirectory() as d:
-        m = Darknet(cfgs.write_cfg(os.path.join(d, "t.cfg"), cfg_text), True).eval()
-        m.net_info["height"] = args.res
-        m.precision = precision
-        m.options = dict(options)
-        m.load_weights(synth.write_weights_file(os.path.join(d, "t.weights"), synth.synth_weights(ir)))
-    t = DarknetTrainer(m, trainable=trainable)
-    t.optimizer = HeadOptimizer("adam", lr=LR)
-    return t
-
-
-NAMES = {"conv_dgrad_async": "dgrad", "upsample2x_grad_async": "upsample_grad", "conv_wgrad_async": "wgrad", "grad_join_async": "joins"}
-
-
-def record(tc, x, targets):
-    """One backbone_gradients walk with every kernel call's arguments written down: {group: [(function, args, kwargs)]}."""
-    calls = {g: [] for g in list(NAMES.values()) + ["read_layer"]}
-    saved = {n: getattr(T, n) for n in NAMES}
-    read = tc.darknet.read_layer
-
-    def wrap(n):
-        def f(*a, **k):
-            calls[NAMES[n]].append((saved[n], a, k))
-            return saved[n](*a, **k)
-        return f
-    for n in NAMES:
-        setattr(T, n, wrap(n))
-    tc.darknet.read_layer = lambda *a, **k: (calls["read_layer"].append((read, a, k)), read(*a, **k))[1]
-    try:
-        _, _, grads = tc.backbone_gradients(x, targets)
-    finally:
-        for n in NAMES:
-            setattr(T, n, saved[n])
-        del tc.darknet.read_layer
-    return calls, grads
+events = lambda fn: grad_walk.events(fn, args.iters)
+trainer = lambda cfg_text, ir, precision, trainable, options: grad_walk.trainer(cfg_text, ir, args.res, precision, trainable, options, LR)
+record, stride_of = grad_walk.record, grad_walk.stride_of
 
 
 x = torch.from_numpy(synth.synth_frames(args.batch, args.res)).cuda()
-rng = np.random.default_rng(1)
-targets = []
-for b in range(args.batch):
-    t = np.zeros((args.boxes, 85), np.float32)
-    t[:, 0:2] = rng.uniform(1, args.res - 1, (args.boxes, 2))
-    t[:, 2:4] = rng.uniform(12, args.res / 2, (args.boxes, 2))
-    t[:, 4] = 1
-    t[np.arange(args.boxes), 5 + rng.choice([0, 0, 0, 0, 16], args.boxes)] = 1
-    targets.append(torch.from_numpy(t).cuda())
+targets = grad_walk.boxes(args.batch, args.res, args.boxes)
 
 NECK = {"keep_head_inputs": 1, "keep_neck_activations": 1}
 BACKBONE = {"keep_head_inputs": 1, "keep_backbone_activations": 1}
@@ -114,7 +62,6 @@ torch.cuda.synchronize()
 peak = int(torch.cuda.max_memory_allocated())
 calls, grads = record(tc, x, targets)
 replay = lambda group: (lambda: [f(*a, **k) for f, a, k in group])
-stride_of = lambda c: int(c[2].get("stride", c[1][6] if len(c[1]) > 6 else 1))
 d1 = [c for c in calls["dgrad"] if stride_of(c) == 1]
 d2 = [c for c in calls["dgrad"] if stride_of(c) == 2]
 d13 = [c for c in d1 if int(c[1][2]) == 3]

@@ -1,0 +1,72 @@
+"""What tools/exp_backbone_grad.py and tools/exp_grad_ab.py share: HIP-event windows, a trainer on synthetic weights, seeded boxes and
+the recorder that writes down the arguments of every kernel call of one backbone walk."""
+import os, tempfile
+import numpy as np
+import torch
+from realtimeobjectdetection_amd import cfgs, synth, train as T
+from realtimeobjectdetection_amd.darknet import Darknet
+from realtimeobjectdetection_amd.train import DarknetTrainer, HeadOptimizer
+
+
+def events(fn, iters):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(iters):
+        fn()
+    e1.record(); torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / iters * 1e3                      # us per call
+
+
+def trainer(cfg_text, ir, res, precision, trainable, options, lr):
+    with tempfile.TemporaryDirectory() as d:
+        m = Darknet(cfgs.write_cfg(os.path.join(d, "t.cfg"), cfg_text), True).eval()
+        m.net_info["height"] = res
+        m.precision = precision
+        m.options = dict(options)
+        m.load_weights(synth.write_weights_file(os.path.join(d, "t.weights"), synth.synth_weights(ir)))
+    t = DarknetTrainer(m, trainable=trainable)
+    t.optimizer = HeadOptimizer("adam", lr=lr)
+    return t
+
+
+def boxes(batch, res, per_image):
+    rng = np.random.default_rng(1)
+    targets = []
+    for b in range(batch):
+        t = np.zeros((per_image, 85), np.float32)
+        t[:, 0:2] = rng.uniform(1, res - 1, (per_image, 2))
+        t[:, 2:4] = rng.uniform(12, res / 2, (per_image, 2))
+        t[:, 4] = 1
+        t[np.arange(per_image), 5 + rng.choice([0, 0, 0, 0, 16], per_image)] = 1
+        targets.append(torch.from_numpy(t).cuda())
+    return targets
+
+
+NAMES = {"conv_dgrad_async": "dgrad", "upsample2x_grad_async": "upsample_grad", "conv_wgrad_async": "wgrad", "grad_join_async": "joins"}
+
+
+def record(tc, x, targets):
+    """One backbone_gradients walk with every kernel call's arguments written down: {group: [(function, args, kwargs)]}."""
+    calls = {g: [] for g in list(NAMES.values()) + ["read_layer"]}
+    saved = {n: getattr(T, n) for n in NAMES}
+    read = tc.darknet.read_layer
+
+    def wrap(n):
+        def f(*a, **k):
+            calls[NAMES[n]].append((saved[n], a, k))
+            return saved[n](*a, **k)
+        return f
+    for n in NAMES:
+        setattr(T, n, wrap(n))
+    tc.darknet.read_layer = lambda *a, **k: (calls["read_layer"].append((read, a, k)), read(*a, **k))[1]
+    try:
+        _, _, grads = tc.backbone_gradients(x, targets)
+    finally:
+        for n in NAMES:
+            setattr(T, n, saved[n])
+        del tc.darknet.read_layer
+    return calls, grads
+
+
+def stride_of(call):
+    return int(call[2].get("stride", call[1][6] if len(call[1]) > 6 else 1))
