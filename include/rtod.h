@@ -207,6 +207,8 @@ int rtod_plan_set_precision(rtod_plan* plan, int mode);
  *                       trainable conv's own output unstored or its packed layout out of reach — no shortcut in a conv's epilogue,
  *                       no fused pointwise pair, no fused stem + layer 1 kernel — so the forward is, bit for bit and tile for tile,
  *                       that of a plan with "fuse_shortcut" = 0, "fuse_pointwise" = 0, "stem2_kernel" = 0.  Default plans do not change
+ *   "keep_full_activations" (default 0) a superset of "keep_backbone_activations" over the FULL graph (rtod_plan_full_layers): thin
+ *                       convs (any Cin, layer 0 on a generic layout) and size-2 max-pools too.  Holds the same fusions
  *   "force_f16s3_variant" / "force_f32_variant"   >= 0: one tile variant for every conv (tests, A/B runs)
  * Options that leave a cfg inexpressible in the split-f16 format return RTOD_E_CFG when precision is 1 or 2 (so does setting
  * "narrow_cin" back to 0 on a plan that needs it); the plan then stays as it was. */
@@ -585,6 +587,56 @@ int rtod_conv_wgrad(const float* dz_dev, const float* x_dev, int batch, int cout
 int rtod_conv_wgrad_s2_workspace(int batch, int cout, int cin, int height, int width, int size, size_t* bytes);
 int rtod_conv_wgrad_s2(const float* dz_dev, const float* x_dev, int batch, int cout, int cin, int height, int width, int size,
                        const double* row_scale_dev, float* dw_dev, float* db_dev, void* workspace, size_t workspace_bytes, void* stream);
+/* (new) Backward of a size-2 [maxpool] over dense NCHW maps.  x_dev [batch,channels,height,width] is the pool's stored INPUT (a dense
+ * rtod_plan_read_layer copy), dz_dev lives on the pool's output map, dx_dev [batch,channels,height,width] is overwritten.
+ *   stride 2: floor mode, output [height / 2, width / 2]; an odd last row or column is covered by no window and gets an exact +0
+ *             (a one-pixel-wide or -high map has an empty output: dz_dev is then not read and may be NULL);
+ *   stride 1: the clamped window of the forward (the reference's MaxPoolStride1: replicate pad right / bottom, MaxPool2d(2, 1)),
+ *             output [height, width].
+ * Gather form, one thread per input element: it visits the one window (stride 2) or the at most four windows (stride 1) that cover
+ * it, recomputes each window's winner from x with the forward's rule — scan dy then dx, replace on strictly greater, so the FIRST
+ * maximum wins (torch's rule); in a clamped window the duplicated edge taps are the same pixel, and the winner decided in scan order
+ * is mapped to that pixel — and adds dz of the windows it won in ascending (oy, ox) order with fp32 adds; then one multiplication by
+ * m(x) = x > 0 ? 1 : slope, the leaky mask of the conv that produced x, as rtod_upsample2x_grad (slope == 1: none).  On a split-f16
+ * plan the dense copy is (hi + lo) / 8, exact, so the winner is the forward's.  No atomics, plain stores: bit-identical from call to
+ * call.  Enqueues only.  NaN inputs are out of contract (the forward's comparison never picks a NaN, torch's propagates it).
+ * RTOD_E_ARG: a null pointer, batch / channels / height / width < 1, size != 2, stride outside {1, 2}, slope NaN,
+ * height * width >= 2^31.  A symmetric (padded) pool has no entry. */
+int rtod_maxpool_grad(const float* dz_dev, const float* x_dev, float slope, int batch, int channels, int height, int width, int size,
+                      int stride, float* dx_dev, void* stream);
+/* (new) rtod_conv_wgrad for THIN convs: any cin >= 1, 1x1 or 3x3, stride 1, pad size / 2, no db.  The operands, the formula of dW,
+ * row_scale_dev and the slice kernel are those of rtod_conv_wgrad; the tile is 32 x 128 of the [cout, cin * size * size] matrix (YOLOv3-
+ * tiny's layer 0, 16 x 27, is one tile), and the slice count is cut for K = batch * height * width instead of capped at 16:
+ *   tiles = ceil(cout / 32) * ceil(cin * size * size / 128);   target = ceil(1024 / tiles);
+ *   L = 8 * ceil(ceil(K / 8) / target) clamped to [256, 1024];   S = ceil(K / L)            (rtod_conv_wgrad_thin_slices returns S and L)
+ * so a large K launches at least 1024 workgroups (layer 0 at 416 x 416, batch 8: K = 1,384,448, L = 1024, S = 1352) and no fmaf chain
+ * has more than 1024 terms — the longest chain measured inside the project's 4 x the-float32-floor gate (the per-tap chain of a
+ * 1024-filter conv in rtod_conv_dgrad; single chains of 4608 and 9216 terms were measured outside it).  The S slice sums of an element
+ * are added as a fixed two-level tree: groups of 32 consecutive slices in ascending order, then the group sums in ascending order;
+ * then row_scale once, in double, as rtod_conv_wgrad.  Plain stores, no atomics: bit-identical from call to call.
+ * Workspace: 4 * S * cout * cin * size * size bytes, 16-byte aligned.  Enqueues only.  RTOD_E_ARG: a null pointer, batch / cout / cin /
+ * height / width < 1, size not 1 or 3, batch * height * width >= 2^31 - 1024, cout * cin * size * size >= 2^31, a workspace that is
+ * too small or misaligned. */
+int rtod_conv_wgrad_thin_slices(int batch, int cout, int cin, int height, int width, int size, int* slices, int* slice_len);
+int rtod_conv_wgrad_thin_workspace(int batch, int cout, int cin, int height, int width, int size, size_t* bytes);
+int rtod_conv_wgrad_thin(const float* dz_dev, const float* x_dev, int batch, int cout, int cin, int height, int width, int size,
+                         const double* row_scale_dev, float* dw_dev, void* workspace, size_t workspace_bytes, void* stream);
+/* (new) rtod_conv_dgrad for THIN convs: any cin >= 1, 1x1 or 3x3, stride 1.  The recipe of rtod_conv_dgrad element for element: one
+ * fmaf chain per tap over o in ascending pairs, the tap sums added in ascending tap order, one multiplication by the mask.  Rows past
+ * cin are staged as zeros and never stored.  RTOD_E_ARG: as rtod_conv_dgrad without the multiple-of-32 rule. */
+int rtod_conv_dgrad_thin(const float* w_oihw_dev, const double* row_scale_dev, const float* dz_dev, const float* y_dev, float slope,
+                         int batch, int cout, int cin, int height, int width, int size, float* dx_dev, void* stream);
+/* (new) The FULL graph of a plan: the BatchNorm convs, in ascending order, of the set rtod_plan_trainable_layers defines with two more
+ * traversable kinds:
+ *   a folded-BatchNorm conv, 1x1 or 3x3 / stride 1 / same padding, leaky or linear, of ANY Cin, layer 0 included, packed in a generic
+ *   layout (layer 0's fp32 panel pads its 3 channels per tap to 4; a stem-layout layer 0 and a narrow-layout conv stay out);
+ *   a [maxpool] of size 2, stride 1 or 2, without symmetric padding (rtod_maxpool_grad).
+ * Option "keep_full_activations" (default 0) is to this graph what "keep_backbone_activations" is to the trainable graph, and a
+ * superset of it: the same fusions are held, every buffer a full-graph conv or pool reads or writes stays live, the frozen scales of
+ * all its convs go to the device and the three folded-conv entries accept them.  With it, fp32: YOLOv3-tiny all 11 BatchNorm convs
+ * (0, 2, 4, 6, 8, 10, 12, 13, 14, 18, 21); YOLOv3 the trainable list (its layer 0 runs the stem kernel; with "stem_kernel" = 0 all 72).
+ * conv_layers / input_layers (-1 for layer 0: the network input) / capacity and the return value as rtod_plan_neck_layers. */
+int rtod_plan_full_layers(const rtod_plan* plan, int* conv_layers, int* input_layers, int capacity);
 
 /* ---- optimiser step of a detection-head conv, on the stream ------------------------------------------
  * replaces optim.Adam(self.darknet.parameters(), lr=1e-2) + optimizer.step()     train.py:57, 412-425

@@ -106,6 +106,14 @@ SIGNATURES = {
                                   C.c_void_p, C.c_void_p]),
     "rtod_plan_trainable_layers": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int]),
     "rtod_grad_join": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_float, C.c_longlong, C.c_void_p, C.c_void_p]),
+    "rtod_plan_full_layers": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int]),
+    "rtod_maxpool_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "rtod_conv_wgrad_thin_slices": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "rtod_conv_wgrad_thin_workspace": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    "rtod_conv_wgrad_thin": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_size_t, C.c_void_p]),
+    "rtod_conv_dgrad_thin": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                       C.c_void_p, C.c_void_p]),
 }
 # ... and the entry points whose names hold a digit (the scan of the header for declared names reads lower-case letters and '_')
 SIGNATURES_DIGIT_NAMES = {

@@ -193,6 +193,27 @@ def bn_pool_mini_cfg(height=64, width=64, classes=3) -> str:
     return "\n".join(L) + "\n"
 
 
+def pool_train_mini_cfg(height=64, width=64, classes=3, stem=16) -> str:
+    """YOLOv3-tiny's shape in small, for training through max-pools and thin convs (trainable="full"): conv / pool pairs, a conv that
+    a 2x2 / stride-2 pool AND the second head's route read (tiny's layer 8), a size-2 / stride-1 pool, two heads at strides 8 and 4.
+    ``stem`` = 16: layer 0 reads 3 channels and layer 2 reads 16 (the thin gradient entries; fp32 plans).  ``stem`` = 32 puts layer 0
+    on the stem kernel and every later conv on Cin % 32 == 0: expressible in the split-f16 format, the full graph is everything but
+    layer 0.  64x64, 64x96 and 40x40 (maps 40, 20, 10, 5: the stride-1 pool on an odd map) are legal shapes."""
+    nout = 3 * (5 + classes)
+    L = _net(height, width)
+    L += _conv(stem, 3, 1) + _maxpool(2, 2)            # 0, 1: stem, stem @ H/2
+    L += _conv(32, 3, 1) + _maxpool(2, 2)              # 2, 3: Cin = stem, 32 @ H/4
+    L += _conv(64, 3, 1) + _maxpool(2, 2)              # 4, 5: read by pool 5 and by route 16; 64 @ H/8
+    L += _conv(128, 3, 1) + _maxpool(2, 1)             # 6, 7: the size-2 / stride-1 pool, 128 @ H/8
+    L += _conv(256, 3, 1) + _conv(128, 1, 1) + _conv(256, 3, 1)   # 8, 9, 10
+    L += _conv(nout, 1, 1, bn=False, act="linear") + _yolo((3, 4, 5), _ANCHORS_TINY, 6, classes)   # 11, 12: head at stride 8
+    L += _route(-4) + _conv(64, 1, 1) + _upsample()    # 13 (layer 9), 14, 15: 64 @ H/4
+    L += _route(-1, 4)                                 # 16: layers 15 and 4, 128 @ H/4
+    L += _conv(128, 3, 1)                              # 17
+    L += _conv(nout, 1, 1, bn=False, act="linear") + _yolo((0, 1, 2), _ANCHORS_TINY, 6, classes)   # 18, 19: head at stride 4
+    return "\n".join(L) + "\n"
+
+
 def kslice_mini_cfg(height=64, width=64, classes=3) -> str:
     """Small test network for the K-sliced split-f16 convolutions (plan option k_slices_split).  Every map is at most 52x52 at the
     test shapes, so the rule slices each conv with at least 8 K-chunks of 32 that has no fused head decode: slices of 2 chunks

@@ -507,6 +507,47 @@ int rtod_plan_trainable_layers(const rtod_plan* plan, int* conv_layers, int* inp
     return list_scope_convs("plan_trainable_layers", plan, SCOPE_BACKBONE, conv_layers, input_layers, capacity);
 }
 
+int rtod_plan_full_layers(const rtod_plan* plan, int* conv_layers, int* input_layers, int capacity) {
+    return list_scope_convs("plan_full_layers", plan, SCOPE_FULL, conv_layers, input_layers, capacity);
+}
+
+int rtod_maxpool_grad(const float* dz_dev, const float* x_dev, float slope, int batch, int channels, int height, int width, int size,
+                      int stride, float* dx_dev, void* stream) {
+    RTOD_GUARD_BEGIN
+    return launch_maxpool_grad(dz_dev, x_dev, slope, batch, channels, height, width, size, stride, dx_dev, (hipStream_t)stream);
+    RTOD_GUARD_END
+}
+
+int rtod_conv_wgrad_thin_slices(int batch, int cout, int cin, int height, int width, int size, int* slices, int* slice_len) {
+    if (!slices || !slice_len) { set_error("conv_wgrad_thin_slices: null pointer"); return RTOD_E_ARG; }
+    if (int rc = wgrad_thin_check_shape("conv_wgrad_thin_slices", batch, cout, cin, height, width, size)) return rc;
+    int64_t S = 0, L = 0;
+    wgrad_thin_slices((int64_t)batch * height * width, cout, cin, size, &S, &L);
+    *slices = (int)S; *slice_len = (int)L;
+    return RTOD_OK;
+}
+
+int rtod_conv_wgrad_thin_workspace(int batch, int cout, int cin, int height, int width, int size, size_t* bytes) {
+    if (!bytes) { set_error("conv_wgrad_thin_workspace: null pointer"); return RTOD_E_ARG; }
+    if (int rc = wgrad_thin_check_shape("conv_wgrad_thin_workspace", batch, cout, cin, height, width, size)) return rc;
+    *bytes = wgrad_thin_workspace_bytes(batch, cout, cin, height, width, size);
+    return RTOD_OK;
+}
+
+int rtod_conv_wgrad_thin(const float* dz_dev, const float* x_dev, int batch, int cout, int cin, int height, int width, int size,
+                         const double* row_scale_dev, float* dw_dev, void* workspace, size_t workspace_bytes, void* stream) {
+    RTOD_GUARD_BEGIN
+    return launch_wgrad_thin(dz_dev, x_dev, batch, cout, cin, height, width, size, row_scale_dev, dw_dev, workspace, workspace_bytes, (hipStream_t)stream);
+    RTOD_GUARD_END
+}
+
+int rtod_conv_dgrad_thin(const float* w_oihw_dev, const double* row_scale_dev, const float* dz_dev, const float* y_dev, float slope,
+                         int batch, int cout, int cin, int height, int width, int size, float* dx_dev, void* stream) {
+    RTOD_GUARD_BEGIN
+    return launch_conv_dgrad("conv_dgrad_thin", w_oihw_dev, row_scale_dev, dz_dev, y_dev, slope, batch, cout, cin, height, width, size, 1, dx_dev, (hipStream_t)stream, true);
+    RTOD_GUARD_END
+}
+
 int rtod_plan_head_blocks(const rtod_plan* plan, int* head_conv_layers, int* block_conv_layers, int* block_input_layers, int capacity) {
     if (!plan || capacity < 0 || (capacity > 0 && (!head_conv_layers || !block_conv_layers || !block_input_layers))) { set_error("plan_head_blocks: bad args"); return RTOD_E_ARG; }
     int n = 0;

@@ -37,6 +37,10 @@
 // element); pairing the two column classes in one workgroup would make the stores dense but give one wave 1 and 2 (or 2 and 4)
 // taps to loop over, and the fixed tap order per element is what the entry promises.  Not avoided here.
 //
+// Thin convs (rtod_conv_dgrad_thin): any cin >= 1 through the same stride-1 instances.  Rows past cin are staged as zeros (c_ok) and
+// never stored, so an element's chain, tap order and mask are those of the entries above; a 16-channel conv fills a quarter of the row
+// tile's accumulators, which is accepted here (its cost is the dz staging, shared with a full tile).
+//
 // One body, three geometries.  dgrad_tile below is the whole recipe: staging, prefetch, MFMAs, total = total + chain, masked store.
 // Its `if constexpr` arms hold only what differs between 1x1 pixels, 3x3 stride 1 and 3x3 stride 2 (one parity class per workgroup): how
 // a GEMM column becomes a pixel, which taps that pixel has, which dz element a tap reads, where dx goes.
@@ -176,12 +180,13 @@ void dgrad_kernel(const float* __restrict__ w, const float* __restrict__ dz, con
 }
 
 int launch_conv_dgrad(const char* who, const float* w, const double* row_scale, const float* dz, const float* y, float slope, int batch, int cout,
-                      int cin, int h, int w_, int size, int stride, float* dx, hipStream_t s) {
+                      int cin, int h, int w_, int size, int stride, float* dx, hipStream_t s, bool thin) {
     const bool s2 = stride == 2;
     if (!w || !dz || !dx) { set_error("%s: null pointer", who); return RTOD_E_ARG; }
-    if (batch < 1 || cout < 1 || cin < 32 || cin % 32 || h < 1 || w_ < 1 || (size != 3 && (size != 1 || s2)) || (stride != 1 && !s2) || !(slope == slope)) {
-        set_error("%s: unsupported arguments (batch=%d cout=%d cin=%d height=%d width=%d size=%d slope=%g; cin must be a multiple of 32, size %s)",
-                  who, batch, cout, cin, h, w_, size, (double)slope, s2 ? "3" : "1 or 3");
+    if (thin && s2) { set_error("%s: stride 1 only", who); return RTOD_E_ARG; }
+    if (batch < 1 || cout < 1 || cin < 1 || (!thin && cin % 32) || h < 1 || w_ < 1 || (size != 3 && (size != 1 || s2)) || (stride != 1 && !s2) || !(slope == slope)) {
+        set_error("%s: unsupported arguments (batch=%d cout=%d cin=%d height=%d width=%d size=%d slope=%g; %ssize %s)",
+                  who, batch, cout, cin, h, w_, size, (double)slope, thin ? "" : "cin must be a multiple of 32, ", s2 ? "3" : "1 or 3");
         return RTOD_E_ARG;
     }
     const int64_t N = (int64_t)batch * h * w_;

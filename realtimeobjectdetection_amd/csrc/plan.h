@@ -94,7 +94,8 @@ struct PackedConv {
 
 // What a plan can train with BatchNorm frozen, narrowest first: the conv in front of each head conv, the neck, everything but layer 0.
 // Options keep_block_inputs / keep_neck_activations / keep_backbone_activations keep the activations of one each (Plan::kept_scope)
-enum Scope { SCOPE_NONE = 0, SCOPE_BLOCKS, SCOPE_NECK, SCOPE_BACKBONE };
+// keep_full_activations: the full graph (thin convs, layer 0 on a generic layout and size-2 max-pools too: YOLOv3-tiny's backbone)
+enum Scope { SCOPE_NONE = 0, SCOPE_BLOCKS, SCOPE_NECK, SCOPE_BACKBONE, SCOPE_FULL };
 
 // One struct, defined over five files by concern (the run-time fused form of every launch is decided in one place, Plan::form in plan_forward.cpp): plan_cfg.cpp (parse, resolve_shapes: no HIP call), plan_build.cpp (options, buffer
 // planning, weight layout, describe), plan_weights.cpp (pack_conv, pack_weights, load_weights; repack_conv under update_conv / update_conv_weight, step_packed under step_conv / step_conv_folded), plan_tiles.cpp (which kernel variant a conv
@@ -155,6 +156,8 @@ struct Plan {
                                       // backbone (rtod_conv_dgrad, rtod_upsample2x_grad, rtod_conv_wgrad).  Liveness only; the scales of all neck convs on the device
     bool opt_keep_backbone_activations = false; // a superset of keep_neck_activations over the TRAINABLE convs (scope_graph: stride-2 convs and shortcuts too).  Not
                                       // liveness only: the plan then forms no fusion that hides a trainable conv (fusions_held, next to form)
+    bool opt_keep_full_activations = false; // a superset of keep_backbone_activations over the FULL graph (scope_graph(SCOPE_FULL): convs of any Cin, layer 0 on a generic
+                                      // layout, size-2 max-pools).  Holds the same fusions
     bool opt_fuse_stem_pool = true;   // ... with the 2x2 / stride-2 max-pool that follows it in the same kernel where the plan allows it (off: A/B and tests)
     int opt_force_f16s3_variant = -1; // >= 0: tile variant for every split-f16 conv (>= BAND_VARIANT_BASE: band layers)
     int opt_force_f32_variant = -1;   // >= 0: tile variant for every exact-fp32 conv
@@ -198,8 +201,10 @@ struct Plan {
     // the trainable graph (rtod_plan_trainable_layers): the neck's closure rule with two more traversable kinds, a block-shaped conv
     // that is 3x3 / stride 2 / pad 1 instead of stride 1, and a two-source linear [shortcut]
     bool train_shape_ok(int layer) const;                                           // block_shape_ok, or block_shape_ok but for that stride
+    // the full graph (rtod_plan_full_layers): two more kinds again, a block-shaped conv of ANY Cin (layer 0 included) and a size-2 max-pool
+    bool full_shape_ok(int layer) const;                                            // train_shape_ok, or block_shape_ok but for Cin and the layer-0 rule
     Scope kept_scope() const {                                                      // the widest scope whose activations the options keep: decided here alone
-        return opt_keep_backbone_activations ? SCOPE_BACKBONE : opt_keep_neck_activations ? SCOPE_NECK : opt_keep_block_inputs ? SCOPE_BLOCKS : SCOPE_NONE;
+        return opt_keep_full_activations ? SCOPE_FULL : opt_keep_backbone_activations ? SCOPE_BACKBONE : opt_keep_neck_activations ? SCOPE_NECK : opt_keep_block_inputs ? SCOPE_BLOCKS : SCOPE_NONE;
     }
     bool trains_folded(int layer, const std::vector<char>& kept) const;             // what block_conv accepts: a block conv on every plan, and every BatchNorm conv of
     bool trains_folded(int layer) const;                                            // kept = scope_graph(kept_scope()) (load_weights asks that graph once for all layers)

@@ -65,7 +65,7 @@ int Plan::set_option(const char* name, int value) {
         {"fuse_decode", &Plan::opt_fuse_decode}, {"zero_copy_concat", &Plan::opt_zero_copy_concat}, {"narrow_cin", &Plan::opt_narrow_cin},
         {"stem_pool", &Plan::opt_stem_pool}, {"fuse_stem_pool", &Plan::opt_fuse_stem_pool}, {"keep_head_inputs", &Plan::opt_keep_head_inputs},
         {"keep_block_inputs", &Plan::opt_keep_block_inputs}, {"keep_neck_activations", &Plan::opt_keep_neck_activations},
-        {"keep_backbone_activations", &Plan::opt_keep_backbone_activations},
+        {"keep_backbone_activations", &Plan::opt_keep_backbone_activations}, {"keep_full_activations", &Plan::opt_keep_full_activations},
     };
     const std::string k(name);
     bool* flag = nullptr; int* num = nullptr;
@@ -312,10 +312,11 @@ int Plan::plan_buffers() {
     // option keep_neck_activations: what every neck conv and every head conv reads and writes (the walk reads outputs for the
     // activation masks, inputs for the weight gradients; routes are kept as their concat buffers)
     // option keep_backbone_activations: the same over the trainable graph, which contains the neck
+    // option keep_full_activations: ... over the full graph, which contains that one; its max-pools keep their input and output too
     if (kept_scope() >= SCOPE_NECK) {
         const std::vector<char> neck = scope_graph(kept_scope());
         for (const auto& l : launches)
-            if (l.kind == LK_CONV && (neck[l.layer] || feeds_yolo(l.layer))) {
+            if ((l.kind == LK_CONV && (neck[l.layer] || feeds_yolo(l.layer))) || (l.kind == LK_MAXPOOL && neck[l.layer])) {
                 touch(buf_of_layer(l.in_layer), n);
                 if (l.out_layer >= 0) touch(buf_of_layer(l.out_layer), n);
             }
@@ -346,7 +347,10 @@ bool Plan::block_plan_ok(int layer) const {
         if (l.kind != LK_CONV || l.layer != layer || l.conv_slot < 0) continue;
         const PackedConv& pc = convs[l.conv_slot];
         if (pc.stem || pc.stem16 || pc.narrow || l.pw_guest >= 0 || l.pw_host >= 0 || l.out_layer != layer) return false;
-        if (pc.Kpad < pc.K || layers[layer].cout > pc.Npad || pc.cin_p != layers[layer].cin) return false;
+        // (layer 0's generic fp32 panel pads its 3 channels per tap to 4: the one layout with cin_p != cin, which head_step_kernel's
+        // panel arm writes as it stands; only full_shape_ok lets layer 0 come this far)
+        const bool rgb_panel = layer == 0 && !pc.split && layers[layer].cin == 3 && pc.cin_p == 4;
+        if (pc.Kpad < pc.K || layers[layer].cout > pc.Npad || (pc.cin_p != layers[layer].cin && !rgb_panel)) return false;
         return layer_form(layer).readable && layers[layer].buf >= 0;
     }
     return false;
@@ -371,11 +375,21 @@ bool Plan::train_shape_ok(int layer) const {
     return L.type == LT_CONV && L.bn && L.size == 3 && L.stride == 2 && L.pad == 1 && L.act <= 1 && L.cin % 32 == 0 && L.fused_into < 0;
 }
 
+// The full graph (SCOPE_FULL): the same closure with the two operations YOLOv3-tiny's backbone consists of, the conv that reads any
+// number of channels (layer 0 reads 3, layer 2 reads 16: rtod_conv_wgrad_thin / rtod_conv_dgrad_thin) and the size-2 max-pool
+// (rtod_maxpool_grad).  The plan's part stays block_plan_ok: a stem-layout layer 0 and a narrow-layout conv are no members
+bool Plan::full_shape_ok(int layer) const {
+    if (train_shape_ok(layer)) return true;
+    if (layer < 0 || layer >= (int)layers.size() || opt_bn_batch_stats) return false;
+    const Layer& L = layers[layer];
+    return L.type == LT_CONV && L.bn && (L.size == 1 || L.size == 3) && L.stride == 1 && L.pad == L.size / 2 && L.act <= 1 && L.cin >= 1 && L.fused_into < 0;
+}
+
 std::vector<char> Plan::scope_graph(Scope scope) const {
     const int n = (int)layers.size();
     std::vector<char> in(n, 0);
     if (scope < SCOPE_NECK) return in;
-    const bool backbone = scope == SCOPE_BACKBONE;
+    const bool full = scope == SCOPE_FULL, backbone = scope >= SCOPE_BACKBONE;
     const std::vector<std::vector<int>> cons = consumers();
     for (int i = n - 1; i >= 0; --i) {
         const Layer& L = layers[i];
@@ -383,9 +397,10 @@ std::vector<char> Plan::scope_graph(Scope scope) const {
         if (L.type == LT_CONV && feeds_yolo(i)) {
             ok = ok && !L.bn && L.size == 1 && L.stride == 1 && L.cin % 32 == 0;
             for (int r : cons[i]) ok = ok && layers[r].type == LT_YOLO;
-        } else if (L.type == LT_CONV) ok = ok && (backbone ? train_shape_ok(i) : block_shape_ok(i)) && block_plan_ok(i);
+        } else if (L.type == LT_CONV) ok = ok && (full ? full_shape_ok(i) : backbone ? train_shape_ok(i) : block_shape_ok(i)) && block_plan_ok(i);
         else if (L.type == LT_UPSAMPLE) ok = ok && L.stride == 2;
         else if (L.type == LT_SHORTCUT) ok = ok && backbone && L.srcs.size() == 2 && L.act == 0 && !L.fused_away;
+        else if (L.type == LT_MAXPOOL) ok = ok && full && L.size == 2 && (L.stride == 1 || L.stride == 2) && L.pool_pad == 0 && !L.fused_away;
         else ok = ok && L.type == LT_ROUTE;
         for (int r : cons[i]) ok = ok && (layers[r].type == LT_YOLO || in[r]);
         in[i] = ok ? 1 : 0;

@@ -13,7 +13,8 @@ bool Plan::stem2_active() const { return precision == 1 && !bn_split_active() &&
 // shortcut in its epilogue, the stem2 kernel's layer 1) or make block_plan_ok refuse it (a pointwise candidate pair) are not formed
 // as CANDIDATES (plan_buffers asks), so the predicates above never see them and the forward is that of a plan with fuse_shortcut,
 // fuse_pointwise and stem2_kernel off
-bool Plan::fusions_held() const { return opt_keep_backbone_activations; }
+// (keep_full_activations, its superset, holds the same three)
+bool Plan::fusions_held() const { return opt_keep_backbone_activations || opt_keep_full_activations; }
 int Plan::fused_pool(int layer) const {
     if (keep_all) return -1;                                     // every layer's own map is stored
     if (layer == 0 && precision >= 1 && stem_pool_pattern && convs[launches[0].conv_slot].stem16) return 1;

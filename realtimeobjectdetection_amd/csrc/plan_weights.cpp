@@ -201,7 +201,7 @@ int Plan::step_conv(int layer, const rtod_opt_step* opt, float* weight, float* b
 int Plan::step_packed(const char* who, size_t slot, const rtod_opt_step* opt, bool moments, bool folded, HeadStepLaunch& h, hipStream_t s) {
     if (int rc = opt_scalars(who, opt, moments, h)) return rc;
     if (!weights_loaded || !d_weights) { set_error("%s: call rtod_plan_load_weights first", who); return RTOD_E_STATE; }
-    if (folded && (kept_scope() == SCOPE_NONE || !d_block_scale)) { set_error("%s: the plan needs option keep_block_inputs, keep_neck_activations or keep_backbone_activations (they put the frozen scales on the device)", who); return RTOD_E_STATE; }
+    if (folded && (kept_scope() == SCOPE_NONE || !d_block_scale)) { set_error("%s: the plan needs option keep_block_inputs, keep_neck_activations, keep_backbone_activations or keep_full_activations (they put the frozen scales on the device)", who); return RTOD_E_STATE; }
     const PackedConv& pc = convs[slot];
     const Layer& L = layers[pc.layer];
     h.cout = L.cout; h.cin = L.cin; h.taps = L.size * L.size; h.cin_p = pc.cin_p; h.split = pc.split ? 1 : 0; h.Kpad = pc.Kpad; h.Npad = pc.Npad;
@@ -251,9 +251,11 @@ int Plan::block_conv(const char* who, int layer, size_t& slot) const {
             {"neck conv", "not a 1x1 / 3x3 stride-1 same-padding leaky or linear BatchNorm conv that reads a multiple of 32 channels",
              "a layer outside the neck reads its output, or the plan computes it inside another layer's kernel"},
             {"trainable conv", "not a 1x1 / 3x3 stride-1 or 3x3 stride-2 same-padding leaky or linear BatchNorm conv that reads a multiple of 32 channels",
-             "a layer outside the trainable graph reads its output, or the plan computes it inside another layer's kernel"}};
+             "a layer outside the trainable graph reads its output, or the plan computes it inside another layer's kernel"},
+            {"full-graph conv", "not a 1x1 / 3x3 stride-1 or 3x3 stride-2 same-padding leaky or linear BatchNorm conv",
+             "a layer outside the full graph reads its output, or the plan computes it inside another layer's kernel"}};
         const Scope kept = kept_scope();
-        const bool shape_ok = kept == SCOPE_BACKBONE ? train_shape_ok(layer) : kept == SCOPE_NECK && block_shape_ok(layer);
+        const bool shape_ok = kept == SCOPE_FULL ? full_shape_ok(layer) : kept == SCOPE_BACKBONE ? train_shape_ok(layer) : kept == SCOPE_NECK && block_shape_ok(layer);
         const PackedConv* pc = cs.slot >= 0 ? &convs[cs.slot] : nullptr;
         const char* why = opt_bn_batch_stats ? "the plan runs batch-statistics BatchNorm: the conv is not folded"
                         : pc && (pc->stem || pc->stem16) ? "a stem layout" : pc && pc->narrow ? "a narrow (Cin == 16) layout"

@@ -374,16 +374,28 @@ size_t wgrad_workspace_bytes(int batch, int cout, int cin, int h, int w, int siz
 int wgrad_check_shape(const char* who, int batch, int cout, int cin, int h, int w, int size, int stride = 1);
 int launch_wgrad(const char* who, const float* dz, const float* x, int batch, int cout, int cin, int h, int w, int size, int cap,
                  const double* row_scale, float* dw, float* db, void* ws, size_t ws_bytes, hipStream_t s, int stride = 1);
+// ... of a thin conv (rtod_conv_wgrad_thin: any cin >= 1, stride 1): the slice kernel on a 32 x 128 tile, the slice count cut for K (at
+// least 1024 workgroups for a large K, no fmaf chain past WGRAD_THIN_MAX_CHAIN terms), the slice sums added as a two-level tree
+constexpr int WGRAD_THIN_MAX_CHAIN = 1024;                         // the longest chain measured inside the 4 x gate
+constexpr int WGRAD_THIN_MIN_CHAIN = 256;                          // a small K is not cut into slivers
+constexpr int WGRAD_THIN_GROUP = 32;                               // slices per first-level group of the reduction tree
+void wgrad_thin_slices(int64_t K, int cout, int cin, int size, int64_t* slices, int64_t* slice_len);
+int wgrad_thin_check_shape(const char* who, int batch, int cout, int cin, int h, int w, int size);
+size_t wgrad_thin_workspace_bytes(int batch, int cout, int cin, int h, int w, int size);
+int launch_wgrad_thin(const float* dz, const float* x, int batch, int cout, int cin, int h, int w, int size, const double* row_scale, float* dw,
+                      void* ws, size_t ws_bytes, hipStream_t s);
 // data gradient of a 1x1 or 3x3 / same-padding convolution with the leaky-ReLU derivative of the stored activation in its epilogue
 // and an optional double scale per filter folded into the weights (dgrad.hip): one tile body under three geometries.  One path under
 // the three entries: rtod_conv1x1_dgrad is size = 1, h = 1, w = pixels, no row scale; rtod_conv_dgrad_s2 is stride = 2 (size 3
 // alone), h x w the conv's INPUT map, the same chains over parity-class tiles.  `who` names the entry in the error texts.
 int launch_conv_dgrad(const char* who, const float* w, const double* row_scale, const float* dz, const float* y, float slope, int batch, int cout,
-                      int cin, int h, int w_, int size, int stride, float* dx, hipStream_t s);
+                      int cin, int h, int w_, int size, int stride, float* dx, hipStream_t s, bool thin = false);   // thin (rtod_conv_dgrad_thin): any cin >= 1, stride 1
 // out = m(y) * (((c0 + c1) + c2) + c3): the fan-out sum of the gradient walk, 1 to 4 contributions, in one launch (grad_join.hip)
 int launch_grad_join(const float* const* contributions, int count, const float* y, float slope, int64_t n, float* out, hipStream_t s);
 // backward of the 2x upsample (bilinear align_corners=False, or nearest) in gather form, the producing conv's mask fused (upsample_grad.hip)
 int launch_upsample2x_grad(const float* dz, const float* y, float slope, int mode, int batch, int channels, int h, int w, float* dx, hipStream_t s);
+// backward of the size-2 max-pool (stride 2 floor mode, or stride 1 clamped) in gather form, the producing conv's mask fused (maxpool_grad.hip)
+int launch_maxpool_grad(const float* dz, const float* x, float slope, int batch, int channels, int h, int w, int size, int stride, float* dx, hipStream_t s);
 // optimiser step of one conv fused with the re-pack of its block of the weight image (head_step.hip): a 1x1 conv without BatchNorm
 // with its bias (Plan::step_conv), or a conv whose frozen BatchNorm scale is folded while it re-packs (b == NULL, scale given:
 // Plan::step_conv_folded).  The kernel's own argument: the scalars are what the host derived in double (Plan::opt_scalars), the

@@ -407,6 +407,15 @@ class Darknet(nn.Module):
         ``step_conv_folded`` accept each of them.  Asks the plan, so a forward (or ``prepare``) must have run."""
         return self._plan_list("trainable_layers", _ffi.lib().rtod_plan_trainable_layers, 2)
 
+    def full_layers(self) -> list:
+        """``[(conv_layer, input_layer)]`` in ascending order (rtod_plan_full_layers): the BatchNorm convs of the trainable graph
+        extended through convs of any ``Cin`` (layer 0 on a generic layout: ``input_layer`` -1, the network input) and size-2
+        max-pools — with options ``keep_full_activations`` all 11 BatchNorm convs of YOLOv3-tiny (fp32); on YOLOv3 the trainable
+        list, whose layer 0 runs the stem kernel.  With that option their inputs and outputs are valid ``read_layer`` targets after
+        a forward and ``conv_scale`` / ``update_conv_weight`` / ``step_conv_folded`` accept each of them.  Asks the plan, so a
+        forward (or ``prepare``) must have run."""
+        return self._plan_list("full_layers", _ffi.lib().rtod_plan_full_layers, 2)
+
     def conv_scale(self, layer: int):
         """``(device address, host float64 array [Cout])`` of a block conv's frozen BatchNorm scale ``gamma / sqrt(var + 1e-5)`` as
         the plan folded it (rtod_plan_conv_scale); the address is what ``train.conv_wgrad_async(row_scale=...)`` takes and needs

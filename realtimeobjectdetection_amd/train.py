@@ -6,8 +6,10 @@ the gradient with respect to the raw head maps and from it ``dW``, ``db`` of the
 BatchNorm in front of the [yolo] blocks), with a plain SGD step on them — fine-tuning the heads with the backbone frozen — and, with
 ``trainable="blocks"``, one layer further: the weight gradient of the BatchNorm conv each head conv reads, BatchNorm frozen, with
 ``trainable="neck"`` every BatchNorm conv behind the backbone, and with ``trainable="backbone"`` the backbone too: every BatchNorm conv
-the plan can train (``Darknet.trainable_layers``: on YOLOv3 all but layer 0), through 3x3 / stride-2 convs and residual shortcuts.
-Layer 0, BatchNorm gradients and batch statistics, max-pool and SiLU backward, weight decay, epochs and data loaders are out of scope
+the plan can train (``Darknet.trainable_layers``: on YOLOv3 all but layer 0), through 3x3 / stride-2 convs and residual shortcuts,
+and with ``trainable="full"`` through size-2 max-pools, convs of any Cin and a generic-layout layer 0 too (``Darknet.full_layers``: all
+11 BatchNorm convs of YOLOv3-tiny).
+BatchNorm gradients and batch statistics, symmetric-pool and SiLU backward, weight decay, epochs and data loaders are out of scope
 (DESIGN.md §8).  The reference's
 optimiser — ``optim.Adam(lr=1e-2)``, train.py:57 — runs on the trained convs as one kernel per conv that also re-packs the conv's weights in
 place (``HeadOptimizer``, ``feed_forward_through_model``): that path never synchronises.  Same names and return conventions as the
@@ -33,6 +35,9 @@ reference:
 * ``DarknetTrainer(model, trainable="backbone")``, ``backbone_gradients(frames_or_x, bndbox)``        (new) ... and the backbone (``Darknet.trainable_layers``),
                                                                                             through stride-2 convs (``conv_dgrad_async`` / ``conv_wgrad_async``
                                                                                             with ``stride=2``) and shortcuts, fan-out sums by ``grad_join_async``
+* ``DarknetTrainer(model, trainable="full")``, ``full_gradients(frames_or_x, bndbox)``                (new) ... and YOLOv3-tiny's backbone (``Darknet.full_layers``):
+                                                                                            max-pools (``maxpool_grad_async``), thin convs
+                                                                                            (``conv_wgrad_thin_async`` / ``conv_dgrad_thin_async``) and layer 0
 
 The reference's behaviour is kept as it is: only boxes whose class-0 slot is 1 and whose sides are at least
 ``min_box_size`` (24) count, ``anchor_fit`` compares a box with a square of the anchor's WIDTH, target slot 0 holds the y fraction
@@ -161,10 +166,10 @@ def yolo_loss_grad_async(pred, bndbox, heads, num_class, min_box_size=24, grad_p
 _wgrad_ws = {}
 
 
-def _wgrad(who, dz, x, size, row_scale, bias, stride=1):
+def _wgrad(who, dz, x, size, row_scale, bias, stride=1, thin=False):
     """The body of ``conv1x1_wgrad_async`` (``size`` None: rtod_conv1x1_wgrad, shape (B, Cout, Cin, pixels)) and ``conv_wgrad_async``
     (rtod_conv_wgrad, shape (B, Cout, Cin, H, W, size); ``stride`` 2: rtod_conv_wgrad_s2, H x W the map of ``x``): the tensor checks, the
-    workspace cached per shape, the outputs, the launch."""
+    workspace cached per shape, the outputs, the launch.  ``thin``: rtod_conv_wgrad_thin (any Cin, stride 1, no ``db``)."""
     _need_cuda(dz, who)
     _need_cuda(x, who)
     if stride not in (1, 2) or (stride == 2 and size is None):
@@ -179,9 +184,12 @@ def _wgrad(who, dz, x, size, row_scale, bias, stride=1):
     B, cout, cin, H, W = dz.size(0), dz.size(1), x.size(1), x.size(2), x.size(3)
     shape = (B, cout, cin, H * W) if size is None else (B, cout, cin, H, W, int(size))
     lib, dev = _ffi.lib(), dz.device
+    if thin and (size is None or s2 or bias):
+        raise ValueError("%s: the thin entry takes a size, stride 1 and no bias gradient" % who)
     entry, entry_workspace = ((lib.rtod_conv1x1_wgrad, lib.rtod_conv1x1_wgrad_workspace) if size is None else
+                              (lib.rtod_conv_wgrad_thin, lib.rtod_conv_wgrad_thin_workspace) if thin else
                               (lib.rtod_conv_wgrad_s2, lib.rtod_conv_wgrad_s2_workspace) if s2 else (lib.rtod_conv_wgrad, lib.rtod_conv_wgrad_workspace))
-    key = (dev.index, stride) + shape
+    key = (dev.index, stride, thin) + shape
     ws = _wgrad_ws.get(key)
     if ws is None:
         nbytes = C.c_size_t()
@@ -195,8 +203,8 @@ def _wgrad(who, dz, x, size, row_scale, bias, stride=1):
     scale = () if size is None else (_scale_ptr(row_scale, cout, dev),)
     with torch.cuda.device(dev):
         _ffi.check(entry(
-            C.c_void_p(dz.data_ptr()), C.c_void_p(x.data_ptr()), *shape, *scale, C.c_void_p(dw.data_ptr()), C.c_void_p(db.data_ptr()) if bias else None,
-            C.c_void_p(ws[0].data_ptr()), ws[1], _stream(dev)))
+            C.c_void_p(dz.data_ptr()), C.c_void_p(x.data_ptr()), *shape, *scale, C.c_void_p(dw.data_ptr()),
+            *(() if thin else (C.c_void_p(db.data_ptr()) if bias else None,)), C.c_void_p(ws[0].data_ptr()), ws[1], _stream(dev)))
     return dw, db
 
 
@@ -223,11 +231,29 @@ def conv_wgrad_async(dz, x, size, row_scale=None, bias=False, stride=1):
     32) -> ``(dW [Cout,Cin,size,size], db [Cout] or None)`` of a ``size`` x ``size`` (1 or 3), stride-1, same-padding conv.
     ``row_scale`` (float64 device tensor [Cout], or the device address ``Darknet.conv_scale`` returns): every row of dW times it,
     one rounding.  ``stride`` 2 (rtod_conv_wgrad_s2): a 3x3 / stride-2 / pad-1 conv, ``dz`` [B,Cout,(H-1)//2+1,(W-1)//2+1] on the
-    conv's output map.  Nothing synchronises; the workspace is cached per shape."""
+    conv's output map.  A ``Cin`` that is no multiple of 32 goes to ``conv_wgrad_thin_async`` (stride 1, no ``db``), and only such
+    a one.  Nothing synchronises; the workspace is cached per shape."""
+    if isinstance(x, torch.Tensor) and x.dim() == 4 and x.size(1) % 32 != 0:
+        return conv_wgrad_thin_async(dz, x, size, row_scale, bias, stride), None
     return _wgrad("conv_wgrad", dz, x, int(size), row_scale, bias, stride)
 
 
-def _dgrad(who, w, dz, size, row_scale, y, slope, stride=1, in_hw=None):
+def conv_wgrad_thin_async(dz, x, size, row_scale=None, bias=False, stride=1):
+    """Enqueue rtod_conv_wgrad_thin: ``conv_wgrad_async`` for a 1x1 or 3x3 / stride-1 conv of ANY ``Cin`` (YOLOv3-tiny's layers 0
+    and 2: few channels, a huge K) -> ``dW [Cout,Cin,size,size]``.  A 32 x 128 tile, the slice count cut for K
+    (``conv_wgrad_thin_slices``), the slice sums added as a fixed two-level tree; no ``db`` (these are BatchNorm convs)."""
+    return _wgrad("conv_wgrad_thin", dz, x, int(size), row_scale, bias, stride, thin=True)[0]
+
+
+def conv_wgrad_thin_slices(batch, cout, cin, height, width, size):
+    """``(slices, slice_len)`` of rtod_conv_wgrad_thin for that shape (rtod_conv_wgrad_thin_slices): no fmaf chain is longer than
+    ``slice_len`` terms, and ``slices`` partial sums are added per element."""
+    s, n = C.c_int(), C.c_int()
+    _ffi.check(_ffi.lib().rtod_conv_wgrad_thin_slices(int(batch), int(cout), int(cin), int(height), int(width), int(size), C.byref(s), C.byref(n)))
+    return s.value, n.value
+
+
+def _dgrad(who, w, dz, size, row_scale, y, slope, stride=1, in_hw=None, thin=False):
     """The body of ``conv1x1_dgrad_async`` (``size`` None: rtod_conv1x1_dgrad, shape (B, Cout, Cin, pixels), no scale) and
     ``conv_dgrad_async`` (rtod_conv_dgrad, shape (B, Cout, Cin, H, W, size); ``stride`` 2: rtod_conv_dgrad_s2, H x W the conv's INPUT
     map): the tensor checks, the output, the launch."""
@@ -257,7 +283,9 @@ def _dgrad(who, w, dz, size, row_scale, y, slope, stride=1, in_hw=None):
     B, cout, cin = dz.size(0), dz.size(1), w.size(1)
     shape = (B, cout, cin, H * W) if size is None else (B, cout, cin, H, W, k)
     lib, dev = _ffi.lib(), dz.device
-    entry = lib.rtod_conv1x1_dgrad if size is None else lib.rtod_conv_dgrad_s2 if stride == 2 else lib.rtod_conv_dgrad
+    if thin and (size is None or stride == 2):
+        raise ValueError("%s: the thin entry takes a size and stride 1" % who)
+    entry = lib.rtod_conv1x1_dgrad if size is None else lib.rtod_conv_dgrad_thin if thin else lib.rtod_conv_dgrad_s2 if stride == 2 else lib.rtod_conv_dgrad
     dx = torch.empty((B, cin, H, W), dtype=torch.float32, device=dev)
     scale = () if size is None else (_scale_ptr(row_scale, cout, dev),)
     with torch.cuda.device(dev):
@@ -281,8 +309,40 @@ def conv_dgrad_async(w, dz, size, row_scale=None, y=None, slope=1.0, stride=1, i
     device tensor [Cout] or the device address ``Darknet.conv_scale`` returns).  Contiguous float32 device tensors, Cin a multiple
     of 32; one fmaf chain per tap, the tap sums added in ascending order: an order the shape fixes; nothing synchronises.
     ``stride`` 2 (rtod_conv_dgrad_s2): a 3x3 / stride-2 / pad-1 conv, ``dz`` [B,Cout,Ho,Wo] on its output map and ``dx`` on its
-    INPUT map, whose size comes from ``y``, else from ``in_hw = (H, W)``: ``Ho`` alone does not tell ``2 Ho`` from ``2 Ho - 1``."""
+    INPUT map, whose size comes from ``y``, else from ``in_hw = (H, W)``: ``Ho`` alone does not tell ``2 Ho`` from ``2 Ho - 1``.
+    A ``Cin`` that is no multiple of 32 goes to ``conv_dgrad_thin_async`` (stride 1), and only such a one."""
+    if isinstance(w, torch.Tensor) and w.dim() in (2, 4) and w.size(1) % 32 != 0:
+        return conv_dgrad_thin_async(w, dz, size, row_scale, y, slope, stride)
     return _dgrad("conv_dgrad", w, dz, int(size), row_scale, y, slope, stride, in_hw)
+
+
+def conv_dgrad_thin_async(w, dz, size, row_scale=None, y=None, slope=1.0, stride=1):
+    """Enqueue rtod_conv_dgrad_thin: ``conv_dgrad_async`` for a 1x1 or 3x3 / stride-1 conv of ANY ``Cin`` (YOLOv3-tiny's layer 2
+    reads 16 channels): the same chain per tap, tap order and mask, rows past ``Cin`` staged as zeros and never stored."""
+    return _dgrad("conv_dgrad_thin", w, dz, int(size), row_scale, y, slope, stride, None, thin=True)
+
+
+def maxpool_grad_async(dz, x, slope=1.0, size=2, stride=2):
+    """Enqueue rtod_maxpool_grad: ``dz`` on the pool's output map ([B,C,H//2,W//2] for ``stride`` 2, [B,C,H,W] for the clamped
+    ``stride`` 1 pool) and ``x`` [B,C,H,W], the pool's stored input -> ``dx`` [B,C,H,W]: every window's gradient goes to its first
+    maximum (the forward's and torch's rule), contributions added in ascending window order, then times ``m(x)`` (1 where ``x > 0``,
+    else ``slope``: the leaky mask of the conv that produced ``x``).  Gather form, no atomics; contiguous float32 device tensors;
+    nothing synchronises."""
+    for t in (dz, x):
+        _need_cuda(t, "maxpool_grad")
+    ok = dz.dim() == 4 and x.dim() == 4 and dz.dtype == x.dtype == torch.float32 and tuple(dz.shape[:2]) == tuple(x.shape[:2])
+    if ok and stride in (1, 2):
+        ok = tuple(dz.shape[2:]) == (tuple(x.shape[2:]) if stride == 1 else (x.size(2) // 2, x.size(3) // 2))
+    if not ok:
+        raise ValueError("maxpool_grad: expected float32 dz on the pool's output map and x [B,C,H,W], got %s and %s (stride %r)" % (tuple(dz.shape), tuple(x.shape), stride))
+    dz, x = dz.contiguous(), x.contiguous()
+    B, ch, H, W = x.shape
+    dev = x.device
+    dx = torch.empty((B, ch, H, W), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _ffi.check(_ffi.lib().rtod_maxpool_grad(C.c_void_p(dz.data_ptr()) if dz.numel() else None, C.c_void_p(x.data_ptr()), float(slope), B, ch, H, W,
+                                                int(size), int(stride), C.c_void_p(dx.data_ptr()), _stream(dev)))
+    return dx
 
 
 def grad_join_async(contributions, y=None, slope=1.0):
@@ -427,11 +487,12 @@ class DarknetTrainer:
     last loss: total, xy, wh, obj, noobj, cls)."""
 
     def __init__(self, model, resolution=None, num_classes=None, trainable="heads"):
-        if trainable not in ("heads", "blocks", "neck", "backbone"):
-            raise ValueError("DarknetTrainer: trainable must be 'heads', 'blocks', 'neck' or 'backbone', got %r" % (trainable,))
+        if trainable not in ("heads", "blocks", "neck", "backbone", "full"):
+            raise ValueError("DarknetTrainer: trainable must be 'heads', 'blocks', 'neck', 'backbone' or 'full', got %r" % (trainable,))
         self.trainable = trainable         # "blocks": feed_forward_through_model also trains the BatchNorm conv in front of each head conv;
                                            # "neck": every BatchNorm conv behind the backbone (Darknet.neck_layers);
                                            # "backbone": every conv the plan can train (Darknet.trainable_layers: all but layer 0 on YOLOv3)
+                                           # "full": ... through thin convs and max-pools too (Darknet.full_layers: all 11 BatchNorm convs of YOLOv3-tiny)
         self.darknet = model
         if resolution is not None:
             assert isinstance(resolution, int) and resolution % 32 == 0
@@ -448,6 +509,7 @@ class DarknetTrainer:
         self.status = None
         self.last_components = None
         self._head_masters = None          # head_step / optimizer: {conv_layer: [weight, bias]} float32 device masters of the head convs
+        self._net_input = None             # the prepared input of the last _forward_train (what layer 0 read)
         self._graph_cache = None           # gradients: (scope, plan and weight version, the graph of that scope with its scales)
         self.optimizer = HeadOptimizer()
 
@@ -561,6 +623,7 @@ class DarknetTrainer:
             x = prep_frames(x, (w, h), mode="RGB")
         elif not x.is_cuda:
             x = x.cuda()
+        self._net_input = x
         with torch.no_grad(), self.darknet.train_mode():
             return self.darknet(x)
 
@@ -579,7 +642,7 @@ class DarknetTrainer:
         if not int(getattr(model, "options", {}).get("keep_head_inputs", 0)):
             raise RuntimeError("DarknetTrainer.head_gradients: set model.options['keep_head_inputs'] = 1 before the first forward; "
                                "without it the activations that feed the head convs do not survive the forward")
-        pred = self._forward_train(frames_or_x)
+        pred = self._forward_train(frames_or_x)                        # (leaves the prepared network input in _net_input: layer 0's dW reads it)
         out = yolo_loss_grad_async(pred, bndbox, self.heads, self.num_classes, self.min_box_size, status=self._status(pred.device))
         self.last_components = out["components"]
         layers = model.head_layers()
@@ -626,24 +689,26 @@ class DarknetTrainer:
     # ------------------------------------------------------------------ gradients behind the heads: one entry, three scopes
     # scope -> (its named entry; the options that keep its activations: any one of them, beside keep_head_inputs; what is lost without them)
     SCOPES = {"blocks": ("block_gradients", ("keep_block_inputs",), "the activations that feed the head convs and the block convs do not survive the forward"),
-              "neck": ("neck_gradients", ("keep_neck_activations", "keep_backbone_activations"), "the activations of the neck do not survive the forward"),
-              "backbone": ("backbone_gradients", ("keep_backbone_activations",),
-                           "the plan fuses convs of the backbone into other kernels and their activations do not survive the forward")}
+              "neck": ("neck_gradients", ("keep_neck_activations", "keep_backbone_activations", "keep_full_activations"), "the activations of the neck do not survive the forward"),
+              "backbone": ("backbone_gradients", ("keep_backbone_activations", "keep_full_activations"),
+                           "the plan fuses convs of the backbone into other kernels and their activations do not survive the forward"),
+              "full": ("full_gradients", ("keep_full_activations",),
+                       "the plan fuses convs of the backbone into other kernels and their activations do not survive the forward")}
 
     def gradients(self, frames_or_x, bndbox, scope=None):
         """``(loss, {head_conv_layer: (dW, db)}, {conv_layer: dW [Cout,Cin,k,k]})`` over the BatchNorm convs of ``scope`` ("blocks",
-        "neck" or "backbone"; default ``self.trainable``): ``head_gradients``, then ``_walk`` through ``_graph(scope)``.  All on the
+        "neck", "backbone" or "full"; default ``self.trainable``): ``head_gradients``, then ``_walk`` through ``_graph(scope)``.  All on the
         current stream, nothing synchronises.  The model's ``options`` must hold ``keep_head_inputs`` and the option of the scope."""
         scope = self.trainable if scope is None else scope
         if scope not in self.SCOPES:
-            raise ValueError("DarknetTrainer.gradients: scope must be 'blocks', 'neck' or 'backbone', got %r" % (scope,))
+            raise ValueError("DarknetTrainer.gradients: scope must be 'blocks', 'neck', 'backbone' or 'full', got %r" % (scope,))
         entry, kept, lost = self.SCOPES[scope]
         opts = getattr(self.darknet, "options", {})
         if not (int(opts.get("keep_head_inputs", 0)) and any(int(opts.get(name, 0)) for name in kept)):
             raise RuntimeError("DarknetTrainer.%s: set model.options['keep_head_inputs'] = 1 and model.options['%s'] = 1 before the first forward; "
                                "without them %s" % (entry, kept[0], lost))
         loss, head_grads, operands = self._head_pass(frames_or_x, bndbox)
-        return loss, head_grads, self._walk(loss, head_grads, operands, self._graph(scope))
+        return loss, head_grads, self._walk(loss, head_grads, operands, self._graph(scope), self._net_input)
 
     def block_gradients(self, frames_or_x, bndbox):
         """``(loss, {head_conv_layer: (dW, db)}, {block_conv_layer: dW [Cout,Cin,k,k]})``: what ``loss.backward()`` of the reference
@@ -684,7 +749,17 @@ class DarknetTrainer:
         ``keep_backbone_activations``."""
         return self.gradients(frames_or_x, bndbox, "backbone")
 
-    def _walk(self, loss, head_grads, operands, graph):
+    def full_gradients(self, frames_or_x, bndbox):
+        """``(loss, {head_conv_layer: (dW, db)}, {conv_layer: dW [Cout,Cin,k,k]})`` over ``Darknet.full_layers()``: the walk of
+        ``backbone_gradients`` with two more kinds of layer.  A conv whose ``Cin`` is no multiple of 32 calls rtod_conv_wgrad_thin
+        and rtod_conv_dgrad_thin; layer 0 takes its ``dW`` over the prepared network input and sends nothing further.  A size-2
+        ``[maxpool]`` calls rtod_maxpool_grad with ``read_layer`` of its input, which serves the winners and, where the pool is
+        the one reader of a leaky conv, that conv's mask.  On YOLOv3-tiny this is every BatchNorm conv, what the reference's
+        ``optim.Adam(self.darknet.parameters())`` trains with BatchNorm frozen.  All on the current stream, nothing synchronises.
+        The model's ``options`` must hold ``keep_head_inputs`` and ``keep_full_activations``."""
+        return self.gradients(frames_or_x, bndbox, "full")
+
+    def _walk(self, loss, head_grads, operands, graph, net_input=None):
         """The one walk under ``gradients``: ``{conv_layer: dW}`` of the BatchNorm convs of ``graph = (layers, readers, member,
         scales)``, in descending layer order, from the heads' ``operands`` (``_head_pass``).  No layer is copied twice in one call:
         ``stored`` starts out with the head-conv inputs ``_head_pass`` read.  A layer's dense ``read_layer`` copy is dropped once the
@@ -694,6 +769,8 @@ class DarknetTrainer:
         masters = self._masters(list(head_grads) + sorted(scales), loss.device)
         B = next(iter(operands.values()))[0].size(0)
         stored = {head - 1: x for head, (_, x) in operands.items()}
+        if net_input is not None:
+            stored[-1] = net_input.to(torch.float32).contiguous()     # what layer 0 read: no read_layer(-1)
 
         def read(layer):                                              # dense copies, one per layer and call
             if layer not in stored:
@@ -742,6 +819,9 @@ class DarknetTrainer:
             elif L.type == "upsample":
                 g = gradient(i)
                 send(i - 1, i, lambda y, slope, g=g, L=L: upsample2x_grad_async(g, y, slope, "nearest" if L.nearest else "bilinear"), True)
+            elif L.type == "maxpool":                                 # the pool's input copy gives the winners and the producer's mask
+                g = gradient(i)
+                send(i - 1, i, lambda y, slope, g=g, L=L, i=i: maxpool_grad_async(g, read(i - 1), slope, L.size, L.stride), True)
             elif L.type == "shortcut":                                # both sources take the gradient as it is
                 g = gradient(i)
                 for s in L.srcs:
@@ -759,8 +839,8 @@ class DarknetTrainer:
         """``(IR layers, readers per layer, membership per layer, {conv: device address of its frozen scale})`` of the graph ``_walk``
         goes through for ``scope``, asked of the plan once per plan and weight load.  The plan decides which BatchNorm convs belong
         (``Darknet.head_blocks`` / ``neck_layers`` / ``trainable_layers``).  "blocks": they and the head convs are the graph.  "neck"
-        and "backbone": routes, upsamples and, in the trainable graph, shortcuts follow by the plan's closure rule: every reader is
-        a member or a [yolo] layer."""
+        "backbone" and "full": routes, upsamples, in the trainable graph shortcuts and in the full graph size-2 max-pools follow by
+        the plan's closure rule: every reader is a member or a [yolo] layer."""
         model = self.darknet
         key = (scope, model._plan.value, model._plan_weights_version)
         if self._graph_cache is None or self._graph_cache[0] != key:
@@ -774,12 +854,15 @@ class DarknetTrainer:
             if scope == "blocks":
                 trained = [block for _, block, _ in model.head_blocks() if block >= 0]
             else:
-                trained = [conv for conv, _ in (model.neck_layers() if scope == "neck" else model.trainable_layers())]
+                trained = [conv for conv, _ in (model.neck_layers() if scope == "neck" else model.full_layers() if scope == "full" else model.trainable_layers())]
             convs = set(trained) | {c for c, _ in model.head_layers()}
-            passive = {"blocks": (), "neck": ("route", "upsample"), "backbone": ("route", "upsample", "shortcut")}[scope]
+            passive = {"blocks": (), "neck": ("route", "upsample"), "backbone": ("route", "upsample", "shortcut"),
+                       "full": ("route", "upsample", "shortcut", "maxpool")}[scope]
             member = [False] * len(layers)
             for L in reversed(layers):
                 ok = L.index in convs if L.type == "convolutional" else L.type in passive and bool(readers[L.index])
+                if L.type == "maxpool":                               # rtod_maxpool_grad's pools (the plan's rule)
+                    ok = ok and L.size == 2 and L.stride in (1, 2) and not L.pool_pad
                 member[L.index] = ok and (scope == "blocks" or all(layers[r].type == "yolo" or member[r] for r in readers[L.index]))
             scales = {c: model.conv_scale(c)[0] for c in trained}
             self._graph_cache = (key, (layers, readers, member, scales))

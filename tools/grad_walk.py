@@ -1,4 +1,4 @@
-"""What tools/exp_backbone_grad.py and tools/exp_grad_ab.py share: HIP-event windows, a trainer on synthetic weights, seeded boxes and
+"""What tools/exp_backbone_grad.py, tools/exp_full_grad.py and tools/exp_grad_ab.py share: HIP-event windows, a trainer on synthetic weights, seeded boxes and
 the recorder that writes down the arguments of every kernel call of one backbone walk."""
 import os, tempfile
 import numpy as np
@@ -42,11 +42,12 @@ def boxes(batch, res, per_image):
     return targets
 
 
-NAMES = {"conv_dgrad_async": "dgrad", "upsample2x_grad_async": "upsample_grad", "conv_wgrad_async": "wgrad", "grad_join_async": "joins"}
+NAMES = {"conv_dgrad_async": "dgrad", "upsample2x_grad_async": "upsample_grad", "conv_wgrad_async": "wgrad", "grad_join_async": "joins",
+         "maxpool_grad_async": "maxpool_grad"}
 
 
-def record(tc, x, targets):
-    """One backbone_gradients walk with every kernel call's arguments written down: {group: [(function, args, kwargs)]}."""
+def record(tc, x, targets, entry="backbone_gradients"):
+    """One walk of ``entry`` (backbone_gradients, full_gradients) with every kernel call's arguments written down: {group: [(function, args, kwargs)]}."""
     calls = {g: [] for g in list(NAMES.values()) + ["read_layer"]}
     saved = {n: getattr(T, n) for n in NAMES}
     read = tc.darknet.read_layer
@@ -60,7 +61,7 @@ def record(tc, x, targets):
         setattr(T, n, wrap(n))
     tc.darknet.read_layer = lambda *a, **k: (calls["read_layer"].append((read, a, k)), read(*a, **k))[1]
     try:
-        _, _, grads = tc.backbone_gradients(x, targets)
+        _, _, grads = getattr(tc, entry)(x, targets)
     finally:
         for n in NAMES:
             setattr(T, n, saved[n])
