@@ -396,18 +396,22 @@ int rtod_yolo_loss_grad(const float* pred_dev, int batch, int n_rows, int num_cl
     RTOD_GUARD_END
 }
 
-int rtod_conv1x1_wgrad_workspace(int batch, int cout, int cin, int pixels, size_t* bytes) {
-    if (!bytes) { set_error("conv1x1_wgrad_workspace: null pointer"); return RTOD_E_ARG; }
-    if (int rc = wgrad_check_shape("conv1x1_wgrad_workspace", batch, cout, cin, 1, pixels, 1)) return rc;
-    *bytes = wgrad_workspace_bytes(batch, cout, cin, 1, pixels, 1, WGRAD_MAX_SLICES);
+// The body of every rtod_*wgrad*_workspace entry: the launch's own shape check, schedule and byte count
+static int wgrad_workspace(const char* who, WgradRule rule, int batch, int cout, int cin, int h, int w, int size, int stride, size_t* bytes) {
+    if (!bytes) { set_error("%s: null pointer", who); return RTOD_E_ARG; }
+    if (int rc = wgrad_check_shape(who, rule, batch, cout, cin, h, w, size, stride)) return rc;
+    *bytes = wgrad_workspace_bytes(wgrad_schedule(rule, batch, cout, cin, h, w, size, stride), cout, cin, size);
     return RTOD_OK;
+}
+
+int rtod_conv1x1_wgrad_workspace(int batch, int cout, int cin, int pixels, size_t* bytes) {
+    return wgrad_workspace("conv1x1_wgrad_workspace", WGRAD_HEAD, batch, cout, cin, 1, pixels, 1, 1, bytes);
 }
 
 int rtod_conv1x1_wgrad(const float* dz_dev, const float* x_dev, int batch, int cout, int cin, int pixels, float* dw_dev, float* db_dev,
                        void* workspace, size_t workspace_bytes, void* stream) {
     RTOD_GUARD_BEGIN
-    return launch_wgrad("conv1x1_wgrad", dz_dev, x_dev, batch, cout, cin, 1, pixels, 1, WGRAD_MAX_SLICES, nullptr, dw_dev, db_dev, workspace, workspace_bytes,
-                        (hipStream_t)stream);
+    return launch_wgrad("conv1x1_wgrad", WGRAD_HEAD, dz_dev, x_dev, batch, cout, cin, 1, pixels, 1, 1, nullptr, dw_dev, db_dev, workspace, workspace_bytes, (hipStream_t)stream);
     RTOD_GUARD_END
 }
 
@@ -423,17 +427,13 @@ int rtod_plan_head_layers(const rtod_plan* plan, int* conv_layers, int* input_la
 }
 
 int rtod_conv_wgrad_workspace(int batch, int cout, int cin, int height, int width, int size, size_t* bytes) {
-    if (!bytes) { set_error("conv_wgrad_workspace: null pointer"); return RTOD_E_ARG; }
-    if (int rc = wgrad_check_shape("conv_wgrad_workspace", batch, cout, cin, height, width, size)) return rc;
-    *bytes = wgrad_workspace_bytes(batch, cout, cin, height, width, size, wgrad_tile_cap(cout, cin, size));
-    return RTOD_OK;
+    return wgrad_workspace("conv_wgrad_workspace", WGRAD_TILED, batch, cout, cin, height, width, size, 1, bytes);
 }
 
 int rtod_conv_wgrad(const float* dz_dev, const float* x_dev, int batch, int cout, int cin, int height, int width, int size,
                     const double* row_scale_dev, float* dw_dev, float* db_dev, void* workspace, size_t workspace_bytes, void* stream) {
     RTOD_GUARD_BEGIN
-    return launch_wgrad("conv_wgrad", dz_dev, x_dev, batch, cout, cin, height, width, size, wgrad_tile_cap(cout, cin, size), row_scale_dev, dw_dev, db_dev,
-                        workspace, workspace_bytes, (hipStream_t)stream);
+    return launch_wgrad("conv_wgrad", WGRAD_TILED, dz_dev, x_dev, batch, cout, cin, height, width, size, 1, row_scale_dev, dw_dev, db_dev, workspace, workspace_bytes, (hipStream_t)stream);
     RTOD_GUARD_END
 }
 
@@ -459,17 +459,13 @@ int rtod_conv_dgrad_s2(const float* w_oihw_dev, const double* row_scale_dev, con
 }
 
 int rtod_conv_wgrad_s2_workspace(int batch, int cout, int cin, int height, int width, int size, size_t* bytes) {
-    if (!bytes) { set_error("conv_wgrad_s2_workspace: null pointer"); return RTOD_E_ARG; }
-    if (int rc = wgrad_check_shape("conv_wgrad_s2_workspace", batch, cout, cin, height, width, size, 2)) return rc;
-    *bytes = wgrad_workspace_bytes(batch, cout, cin, (height - 1) / 2 + 1, (width - 1) / 2 + 1, size, wgrad_tile_cap(cout, cin, size));
-    return RTOD_OK;
+    return wgrad_workspace("conv_wgrad_s2_workspace", WGRAD_TILED, batch, cout, cin, height, width, size, 2, bytes);
 }
 
 int rtod_conv_wgrad_s2(const float* dz_dev, const float* x_dev, int batch, int cout, int cin, int height, int width, int size,
                        const double* row_scale_dev, float* dw_dev, float* db_dev, void* workspace, size_t workspace_bytes, void* stream) {
     RTOD_GUARD_BEGIN
-    return launch_wgrad("conv_wgrad_s2", dz_dev, x_dev, batch, cout, cin, height, width, size, wgrad_tile_cap(cout, cin, size), row_scale_dev, dw_dev, db_dev,
-                        workspace, workspace_bytes, (hipStream_t)stream, 2);
+    return launch_wgrad("conv_wgrad_s2", WGRAD_TILED, dz_dev, x_dev, batch, cout, cin, height, width, size, 2, row_scale_dev, dw_dev, db_dev, workspace, workspace_bytes, (hipStream_t)stream);
     RTOD_GUARD_END
 }
 
@@ -520,24 +516,20 @@ int rtod_maxpool_grad(const float* dz_dev, const float* x_dev, float slope, int 
 
 int rtod_conv_wgrad_thin_slices(int batch, int cout, int cin, int height, int width, int size, int* slices, int* slice_len) {
     if (!slices || !slice_len) { set_error("conv_wgrad_thin_slices: null pointer"); return RTOD_E_ARG; }
-    if (int rc = wgrad_thin_check_shape("conv_wgrad_thin_slices", batch, cout, cin, height, width, size)) return rc;
-    int64_t S = 0, L = 0;
-    wgrad_thin_slices((int64_t)batch * height * width, cout, cin, size, &S, &L);
-    *slices = (int)S; *slice_len = (int)L;
+    if (int rc = wgrad_check_shape("conv_wgrad_thin_slices", WGRAD_THIN, batch, cout, cin, height, width, size, 1)) return rc;
+    const WgradSchedule sc = wgrad_schedule(WGRAD_THIN, batch, cout, cin, height, width, size, 1);
+    *slices = sc.slices; *slice_len = sc.slice_len;
     return RTOD_OK;
 }
 
 int rtod_conv_wgrad_thin_workspace(int batch, int cout, int cin, int height, int width, int size, size_t* bytes) {
-    if (!bytes) { set_error("conv_wgrad_thin_workspace: null pointer"); return RTOD_E_ARG; }
-    if (int rc = wgrad_thin_check_shape("conv_wgrad_thin_workspace", batch, cout, cin, height, width, size)) return rc;
-    *bytes = wgrad_thin_workspace_bytes(batch, cout, cin, height, width, size);
-    return RTOD_OK;
+    return wgrad_workspace("conv_wgrad_thin_workspace", WGRAD_THIN, batch, cout, cin, height, width, size, 1, bytes);
 }
 
 int rtod_conv_wgrad_thin(const float* dz_dev, const float* x_dev, int batch, int cout, int cin, int height, int width, int size,
                          const double* row_scale_dev, float* dw_dev, void* workspace, size_t workspace_bytes, void* stream) {
     RTOD_GUARD_BEGIN
-    return launch_wgrad_thin(dz_dev, x_dev, batch, cout, cin, height, width, size, row_scale_dev, dw_dev, workspace, workspace_bytes, (hipStream_t)stream);
+    return launch_wgrad("conv_wgrad_thin", WGRAD_THIN, dz_dev, x_dev, batch, cout, cin, height, width, size, 1, row_scale_dev, dw_dev, nullptr, workspace, workspace_bytes, (hipStream_t)stream);
     RTOD_GUARD_END
 }
 

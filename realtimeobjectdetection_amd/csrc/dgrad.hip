@@ -180,13 +180,13 @@ void dgrad_kernel(const float* __restrict__ w, const float* __restrict__ dz, con
 }
 
 int launch_conv_dgrad(const char* who, const float* w, const double* row_scale, const float* dz, const float* y, float slope, int batch, int cout,
-                      int cin, int h, int w_, int size, int stride, float* dx, hipStream_t s, bool thin) {
+                      int cin, int h, int w_, int size, int stride, float* dx, hipStream_t s, bool any_cin) {
     const bool s2 = stride == 2;
     if (!w || !dz || !dx) { set_error("%s: null pointer", who); return RTOD_E_ARG; }
-    if (thin && s2) { set_error("%s: stride 1 only", who); return RTOD_E_ARG; }
-    if (batch < 1 || cout < 1 || cin < 1 || (!thin && cin % 32) || h < 1 || w_ < 1 || (size != 3 && (size != 1 || s2)) || (stride != 1 && !s2) || !(slope == slope)) {
+    if (any_cin && s2) { set_error("%s: stride 1 only", who); return RTOD_E_ARG; }
+    if (batch < 1 || cout < 1 || cin < 1 || (!any_cin && cin % 32) || h < 1 || w_ < 1 || (size != 3 && (size != 1 || s2)) || (stride != 1 && !s2) || !(slope == slope)) {
         set_error("%s: unsupported arguments (batch=%d cout=%d cin=%d height=%d width=%d size=%d slope=%g; %ssize %s)",
-                  who, batch, cout, cin, h, w_, size, (double)slope, thin ? "" : "cin must be a multiple of 32, ", s2 ? "3" : "1 or 3");
+                  who, batch, cout, cin, h, w_, size, (double)slope, any_cin ? "" : "cin must be a multiple of 32, ", s2 ? "3" : "1 or 3");
         return RTOD_E_ARG;
     }
     const int64_t N = (int64_t)batch * h * w_;

@@ -363,33 +363,35 @@ int launch_yolo_loss_grad(const float* pred, int batch, int n_rows, int num_clas
                           const float* boxes, const int32_t* box_off, float min_box_size, float* grad_raw, float* grad_pred, double* loss,
                           int32_t* n_obj, int32_t* status, void* ws, size_t ws_bytes, hipStream_t s);
 // weight / bias gradient of a 1x1 or 3x3 convolution on the exact-fp32 MFMA, K slices added in order, an optional double scale
-// per row of dW (wgrad.hip).  One path under both entries: rtod_conv1x1_wgrad is size = 1, h = 1, w = pixels, cap =
-// WGRAD_MAX_SLICES, no row scale; rtod_conv_wgrad passes cap = wgrad_tile_cap.  `who` names the entry in the error texts.
-// stride 2 (rtod_conv_wgrad_s2, size 3 alone): h x w is the conv's INPUT map, which x lives on; the same kernel with the tap
-// positions doubled.
+// per row of dW (wgrad.hip).  One path under every entry, which names its slice rule: rtod_conv1x1_wgrad is WGRAD_HEAD with size = 1,
+// h = 1, w = pixels, no row scale; rtod_conv_wgrad and rtod_conv_wgrad_s2 (stride 2, size 3 alone: h x w is the conv's INPUT map,
+// which x lives on; the same kernel with the tap positions doubled) are WGRAD_TILED; rtod_conv_wgrad_thin (any cin >= 1, stride 1, no
+// db) is WGRAD_THIN.  `who` names the entry in the error texts.
+enum WgradRule { WGRAD_HEAD, WGRAD_TILED, WGRAD_THIN };            // cap 16 | cap min(16, ceil(1024 / tiles)) | slice count cut for K
 constexpr int WGRAD_MAX_SLICES = 16;
-int wgrad_tile_cap(int cout, int cin, int size);                    // min(16, ceil(1024 / tiles))
-int64_t wgrad_slice_len(int64_t K, int cap);
-size_t wgrad_workspace_bytes(int batch, int cout, int cin, int h, int w, int size, int cap);
-int wgrad_check_shape(const char* who, int batch, int cout, int cin, int h, int w, int size, int stride = 1);
-int launch_wgrad(const char* who, const float* dz, const float* x, int batch, int cout, int cin, int h, int w, int size, int cap,
-                 const double* row_scale, float* dw, float* db, void* ws, size_t ws_bytes, hipStream_t s, int stride = 1);
-// ... of a thin conv (rtod_conv_wgrad_thin: any cin >= 1, stride 1): the slice kernel on a 32 x 128 tile, the slice count cut for K (at
-// least 1024 workgroups for a large K, no fmaf chain past WGRAD_THIN_MAX_CHAIN terms), the slice sums added as a two-level tree
 constexpr int WGRAD_THIN_MAX_CHAIN = 1024;                         // the longest chain measured inside the 4 x gate
 constexpr int WGRAD_THIN_MIN_CHAIN = 256;                          // a small K is not cut into slivers
 constexpr int WGRAD_THIN_GROUP = 32;                               // slices per first-level group of the reduction tree
-void wgrad_thin_slices(int64_t K, int cout, int cin, int size, int64_t* slices, int64_t* slice_len);
-int wgrad_thin_check_shape(const char* who, int batch, int cout, int cin, int h, int w, int size);
-size_t wgrad_thin_workspace_bytes(int batch, int cout, int cin, int h, int w, int size);
-int launch_wgrad_thin(const float* dz, const float* x, int batch, int cout, int cin, int h, int w, int size, const double* row_scale, float* dw,
-                      void* ws, size_t ws_bytes, hipStream_t s);
+struct WgradSchedule {
+    int tm, tn;                 // tile of dW per workgroup: 64 x 64, thin 32 x 128
+    int h, w;                   // the map k runs over (stride 2: the conv's output map)
+    int64_t K;                  // batch * h * w
+    int slices, slice_len;      // S = ceil(K / L) workgroups per tile, fmaf chains of at most L terms
+    int group;                  // slice sums per first-level group of the reduction tree (head, tiled: S, one group: the ascending sum)
+    int reduce_block;           // threads per workgroup of the reduce kernel
+    bool db;                    // the entry has a db and the workspace its slice sums
+};
+WgradSchedule wgrad_schedule(WgradRule rule, int batch, int cout, int cin, int h, int w, int size, int stride);
+size_t wgrad_workspace_bytes(const WgradSchedule& sc, int cout, int cin, int size);
+int wgrad_check_shape(const char* who, WgradRule rule, int batch, int cout, int cin, int h, int w, int size, int stride);
+int launch_wgrad(const char* who, WgradRule rule, const float* dz, const float* x, int batch, int cout, int cin, int h, int w, int size, int stride,
+                 const double* row_scale, float* dw, float* db, void* ws, size_t ws_bytes, hipStream_t s);
 // data gradient of a 1x1 or 3x3 / same-padding convolution with the leaky-ReLU derivative of the stored activation in its epilogue
 // and an optional double scale per filter folded into the weights (dgrad.hip): one tile body under three geometries.  One path under
 // the three entries: rtod_conv1x1_dgrad is size = 1, h = 1, w = pixels, no row scale; rtod_conv_dgrad_s2 is stride = 2 (size 3
 // alone), h x w the conv's INPUT map, the same chains over parity-class tiles.  `who` names the entry in the error texts.
 int launch_conv_dgrad(const char* who, const float* w, const double* row_scale, const float* dz, const float* y, float slope, int batch, int cout,
-                      int cin, int h, int w_, int size, int stride, float* dx, hipStream_t s, bool thin = false);   // thin (rtod_conv_dgrad_thin): any cin >= 1, stride 1
+                      int cin, int h, int w_, int size, int stride, float* dx, hipStream_t s, bool any_cin = false);   // any_cin (rtod_conv_dgrad_thin): cin % 32 is not refused, stride 2 is
 // out = m(y) * (((c0 + c1) + c2) + c3): the fan-out sum of the gradient walk, 1 to 4 contributions, in one launch (grad_join.hip)
 int launch_grad_join(const float* const* contributions, int count, const float* y, float slope, int64_t n, float* out, hipStream_t s);
 // backward of the 2x upsample (bilinear align_corners=False, or nearest) in gather form, the producing conv's mask fused (upsample_grad.hip)

@@ -13,19 +13,32 @@
 // Rows past cout / cin and k past the slice are staged as zeros, which leave an fmaf chain unchanged.
 //
 // K slices.  The tile grid is small (4 x 16 tiles at most), so K is split into S contiguous slices, one workgroup per (tile,
-// slice); slice sums go to the workspace and wgrad_reduce_kernel adds them in ascending slice order.  No floating-point atomics:
-// the result is bit-identical from call to call.  The slice rule (wgrad_slice_len, documented in rtod.h) sees K and a cap:
-//   units = ceil(K / 8);  slice length = 8 * ceil(units / cap);  S = ceil(K / slice length)  (<= cap; rtod_conv1x1_wgrad: cap = 16)
-// Every accumulator is an fmaf chain over its slice in a fixed permutation of k; db is a plain fp32 sum over the slice in
-// ascending k, kept by the workgroups of the first column of tiles.
+// slice); slice sums go to the workspace and wgrad_reduce_kernel adds them in a fixed order.  No floating-point atomics: the
+// result is bit-identical from call to call.  Every accumulator is an fmaf chain over its slice in a fixed permutation of k; db
+// is a plain fp32 sum over the slice in ascending k, kept by the workgroups of the first column of tiles.
+//
+// One launcher, three slice rules.  Every entry goes through launch_wgrad: one shape check, one schedule (wgrad_schedule: tile,
+// K, S, slice length L, reduction group), one workspace size, one slice kernel, one reduce kernel.  The entries differ in the
+// rule alone (documented in rtod.h), a pure function of the shape:
+//   head  (rtod_conv1x1_wgrad)            cap = 16
+//   tiled (rtod_conv_wgrad, _s2)          cap = min(16, ceil(1024 / tiles)): a 13 x 13 block has a thousand tiles already and is not sliced
+//       both: 64 x 64 tiles;  L = 8 * ceil(ceil(K / 8) / cap);  S = ceil(K / L) <= cap;  the S sums added in ascending order
+//   thin  (rtod_conv_wgrad_thin: any cin, stride 1, no db)   few channels, a huge K — YOLOv3-tiny's layer 0 at 416 x 416 batch 8
+//       is a 16 x 27 dW over K = 1,384,448.  32 x 128 tiles (layer 0: one tile, layer 2's 32 x 144: two);  target = ceil(1024 / tiles);
+//       L = 8 * ceil(ceil(K / 8) / target) clamped to [WGRAD_THIN_MIN_CHAIN, WGRAD_THIN_MAX_CHAIN];  S = ceil(K / L)
+//       (rtod_conv_wgrad_thin_slices), so a large K gets at least 1024 workgroups and no fmaf chain is longer than 1024 terms: the
+//       longest chain measured inside the 4 x gate (dgrad.hip's per-tap chain of a 1024-filter conv; one chain of 4608 / 9216
+//       terms was measured outside).  The S sums are added as a fixed two-level tree: groups of WGRAD_THIN_GROUP = 32 consecutive
+//       slices in ascending order, then the group sums in ascending order (S = 1352 at layer 0: the longest run of fp32 adds is
+//       31 + 42, not 1351).
+// The ascending sum of the first two rules is the same tree with one group that holds every slice.
 //
 // 3x3 convs (rtod_conv_wgrad, TAPS = 9).  The same kernel as an implicit GEMM: the column index is n = c * 9 + tap, OIHW order, so
 // the dW stores stay coalesced, and B[n][k] = x[b, c, y + ky - 1, x + kx - 1], an exact zero outside the map.  A thread's eight
 // columns (channel and tap offsets) do not depend on k and are resolved once; k -> (b, y, x) costs two divisions per staged chunk.
 // Stride 2 (rtod_conv_wgrad_s2) is the same column with the tap positions doubled: k runs over the conv's OUTPUT map, x lives on
-// its input map.  The 1x1 instance (TAPS = 1) reads x where it reads dz.  The cap of rtod_conv_wgrad also sees the
-// number of tiles (wgrad_tile_cap: a 13 x 13 block has a thousand tiles already and is not sliced), and its reduce kernel
-// multiplies the reduced sum of a row by a caller-supplied double once — the frozen BatchNorm scale of the conv.
+// its input map.  The 1x1 instance (TAPS = 1) reads x where it reads dz.  The reduce kernel multiplies the reduced sum of a
+// row by a caller-supplied double once — the frozen BatchNorm scale of the conv.
 #include "rtod_internal.h"
 
 namespace rtod {
@@ -37,26 +50,34 @@ constexpr int WG_BK = 32;               // k per LDS stage
 constexpr int WG_LD = WG_BK + 4;        // padded row (floats)
 constexpr int WG_T = 64;                // tile edge (rows of dz and rows of x per workgroup)
 
-// The slice rule (rtod.h): units = ceil(K / 8); slice length = 8 * ceil(units / cap); S = ceil(K / slice length) <= cap.  The two
-// entries differ in the cap alone: rtod_conv1x1_wgrad always allows WGRAD_MAX_SLICES, rtod_conv_wgrad wgrad_tile_cap.
-int64_t wgrad_slice_len(int64_t K, int cap) {
-    const int64_t units = (K + 7) / 8;
-    return 8 * ((units + cap - 1) / cap);
-}
-static int64_t wgrad_slices(int64_t K, int cap) { const int64_t L = wgrad_slice_len(K, cap); return (K + L - 1) / L; }
-static int64_t wgrad_tiles(int cout, int cin, int size) {
-    return (((int64_t)cout + WG_T - 1) / WG_T) * (((int64_t)cin * size * size + WG_T - 1) / WG_T);    // (the entries call this before their shape checks)
-}
-// min(16, ceil(1024 / tiles)): a grid that has a thousand tiles already is not sliced.  (No tiles: a shape wgrad_check_shape refuses.)
-int wgrad_tile_cap(int cout, int cin, int size) {
-    constexpr int64_t WG_TILE_TARGET = 1024;
-    const int64_t tiles = wgrad_tiles(cout, cin, size);
-    return tiles < 1 ? WGRAD_MAX_SLICES : (int)std::min<int64_t>(WGRAD_MAX_SLICES, (WG_TILE_TARGET + tiles - 1) / tiles);
+constexpr int WT_M = 32, WT_N = 128;    // the thin tile
+
+// The three slice rules (header; rtod.h), of a shape wgrad_check_shape accepted.  h x w: the map of x; stride 2: k runs over the conv's output map
+WgradSchedule wgrad_schedule(WgradRule rule, int batch, int cout, int cin, int h, int w, int size, int stride) {
+    const bool thin = rule == WGRAD_THIN;
+    WgradSchedule sc;
+    sc.tm = thin ? WT_M : WG_T;
+    sc.tn = thin ? WT_N : WG_T;
+    sc.h = stride == 2 ? (h - 1) / 2 + 1 : h;
+    sc.w = stride == 2 ? (w - 1) / 2 + 1 : w;
+    sc.K = (int64_t)batch * sc.h * sc.w;
+    const int64_t tiles = std::max<int64_t>(1, (((int64_t)cout + sc.tm - 1) / sc.tm) * (((int64_t)cin * size * size + sc.tn - 1) / sc.tn));
+    const int64_t target = (1024 + tiles - 1) / tiles;              // slices that bring the grid to a thousand workgroups
+    const int64_t units = (sc.K + 7) / 8;
+    const int64_t cap = thin ? target : rule == WGRAD_HEAD ? WGRAD_MAX_SLICES : std::min<int64_t>(WGRAD_MAX_SLICES, target);
+    int64_t L = 8 * ((units + cap - 1) / cap);
+    if (thin) L = std::min<int64_t>(WGRAD_THIN_MAX_CHAIN, std::max<int64_t>(WGRAD_THIN_MIN_CHAIN, L));
+    sc.slice_len = (int)L;
+    sc.slices = (int)((sc.K + L - 1) / L);
+    sc.group = thin ? WGRAD_THIN_GROUP : sc.slices;
+    sc.reduce_block = thin ? 64 : 256;                               // few elements, long sums: more workgroups
+    sc.db = !thin;
+    return sc;
 }
 
-size_t wgrad_workspace_bytes(int batch, int cout, int cin, int h, int w, int size, int cap) {
-    const int64_t S = wgrad_slices((int64_t)batch * h * w, cap);
-    return sizeof(float) * (size_t)S * ((size_t)cout * cin * size * size + (size_t)cout);
+// S slice sums of dW and, where the entry has a db, of db
+size_t wgrad_workspace_bytes(const WgradSchedule& sc, int cout, int cin, int size) {
+    return sizeof(float) * (size_t)sc.slices * ((size_t)cout * cin * size * size + (sc.db ? (size_t)cout : 0));
 }
 
 // part: [S][cout][ncol] slice sums of dW (ncol = cin * TAPS), then [S][cout] slice sums of db.  pixels and W describe the map of dz, the
@@ -166,144 +187,75 @@ void wgrad_slice_kernel(const float* __restrict__ dz, const float* __restrict__ 
     }
 }
 
-// the slice sums added in ascending slice order: one thread per element of dW, then of db.  row_scale (may be NULL): the reduced
-// sum of row o of dW (ncol elements) times row_scale[o] in double, rounded once; db is the plain sum
+// the slice sums added as a fixed two-level tree, one thread per element of dW, then of db: groups of `group` consecutive slices in
+// ascending order, then the group sums in ascending order.  One group (group >= slices) is v = part[0]; v = v + part[s] ascending
+// and no further add.  row_scale (may be NULL): the reduced sum of row o of dW (ncol elements) times row_scale[o] in double,
+// rounded once; db (may be NULL) is the plain sum
 __global__ __launch_bounds__(256)
-void wgrad_reduce_kernel(const float* __restrict__ part, const float* __restrict__ part_db, int64_t n_dw, int cout, int slices,
+void wgrad_reduce_kernel(const float* __restrict__ part, const float* __restrict__ part_db, int64_t n_dw, int cout, int slices, int group,
                          const double* __restrict__ row_scale, int ncol, float* __restrict__ dw, float* __restrict__ db) {
 #pragma clang fp contract(off)
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < n_dw) {
-        float v = part[i];
-        for (int s = 1; s < slices; ++s) v = v + part[(int64_t)s * n_dw + i];
-        if (row_scale) v = (float)((double)v * row_scale[i / ncol]);
-        dw[i] = v;
-    } else if (db && i < n_dw + cout) {
-        const int64_t o = i - n_dw;
-        float v = part_db[o];
-        for (int s = 1; s < slices; ++s) v = v + part_db[(int64_t)s * cout + o];
-        db[o] = v;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool bias = i >= n_dw;
+    if (bias && !(db && i < n_dw + cout)) return;
+    const float* p = bias ? part_db + (i - n_dw) : part + i;
+    const int64_t step = bias ? cout : n_dw;                         // floats between consecutive slices
+    float total = 0.f;
+    for (int g0 = 0; g0 < slices; g0 += group) {
+        const int g1 = min(g0 + group, slices);
+        float v = p[(int64_t)g0 * step];
+#pragma unroll 8
+        for (int s = g0 + 1; s < g1; ++s) v = v + p[(int64_t)s * step];
+        total = g0 == 0 ? v : total + v;
     }
+    if (bias) db[i - n_dw] = total;
+    else dw[i] = row_scale ? (float)((double)total * row_scale[i / ncol]) : total;
 }
 
-// stride 2 (h x w the conv's input map) takes size 3 alone
-int wgrad_check_shape(const char* who, int batch, int cout, int cin, int h, int w, int size, int stride) {
+// stride 2 (h x w the conv's input map) takes size 3 alone; the thin rule takes any cin >= 1
+int wgrad_check_shape(const char* who, WgradRule rule, int batch, int cout, int cin, int h, int w, int size, int stride) {
+    const bool thin = rule == WGRAD_THIN;
     const int64_t K = (int64_t)batch * h * w, taps = (int64_t)size * size;
-    if (batch < 1 || cout < 1 || cin < 32 || cin % 32 || h < 1 || w < 1 || (size != 1 && size != 3)) {
-        set_error("%s: unsupported shape (batch=%d cout=%d cin=%d h=%d w=%d size=%d; cin must be a multiple of 32, size 1 or 3)", who, batch, cout, cin, h, w, size);
+    if (batch < 1 || cout < 1 || cin < 1 || (!thin && cin % 32) || h < 1 || w < 1 || (size != 1 && size != 3)) {
+        set_error("%s: unsupported shape (batch=%d cout=%d cin=%d h=%d w=%d size=%d; %ssize 1 or 3)", who, batch, cout, cin, h, w, size,
+                  thin ? "" : "cin must be a multiple of 32, ");
         return RTOD_E_ARG;
     }
-    if ((int64_t)h * w > INT32_MAX || K > INT32_MAX - 64 || (int64_t)cout * cin * taps > INT32_MAX) { set_error("%s: batch * h * w or cout * cin * size * size exceeds int32", who); return RTOD_E_ARG; }
+    if ((int64_t)h * w > INT32_MAX || K > INT32_MAX - (thin ? WGRAD_THIN_MAX_CHAIN : 64) || (int64_t)cout * cin * taps > INT32_MAX) {
+        set_error("%s: batch * h * w or cout * cin * size * size exceeds int32", who);
+        return RTOD_E_ARG;
+    }
     if (stride == 2 && size != 3) { set_error("%s: unsupported shape (size=%d; the stride-2 entry takes 3x3 convs)", who, size); return RTOD_E_ARG; }
     return RTOD_OK;
 }
 
-// `who` names the entry in every error text; `cap` is the entry's cap on the slice count (at most WGRAD_MAX_SLICES).  stride 2
-// (rtod_conv_wgrad_s2: size 3, pad 1): h x w is the conv's INPUT map, dz lives on the output map and K = batch * ho * wo
-int launch_wgrad(const char* who, const float* dz, const float* x, int batch, int cout, int cin, int h, int w, int size, int cap,
-                 const double* row_scale, float* dw, float* db, void* ws, size_t ws_bytes, hipStream_t s, int stride) {
+// `who` names the entry in every error text, `rule` is its slice rule.  stride 2 (rtod_conv_wgrad_s2: size 3, pad 1): h x w is the
+// conv's INPUT map, dz lives on the output map and K = batch * ho * wo.  db may be NULL (the thin entry has none)
+int launch_wgrad(const char* who, WgradRule rule, const float* dz, const float* x, int batch, int cout, int cin, int h, int w, int size, int stride,
+                 const double* row_scale, float* dw, float* db, void* ws, size_t ws_bytes, hipStream_t s) {
     if (!dz || !x || !dw || !ws) { set_error("%s: null pointer", who); return RTOD_E_ARG; }
-    if (int rc = wgrad_check_shape(who, batch, cout, cin, h, w, size, stride)) return rc;
-    const int xh = h, xw = w;
-    if (stride == 2) { h = (xh - 1) / 2 + 1; w = (xw - 1) / 2 + 1; }  // from here on the map that k runs over
-    if (ws_bytes < wgrad_workspace_bytes(batch, cout, cin, h, w, size, cap)) { set_error("%s: workspace too small", who); return RTOD_E_ARG; }
+    if (int rc = wgrad_check_shape(who, rule, batch, cout, cin, h, w, size, stride)) return rc;
+    const WgradSchedule sc = wgrad_schedule(rule, batch, cout, cin, h, w, size, stride);
+    if (!sc.db) db = nullptr;                                         // no db part in the workspace
+    if (ws_bytes < wgrad_workspace_bytes(sc, cout, cin, size)) { set_error("%s: workspace too small", who); return RTOD_E_ARG; }
     if ((uintptr_t)ws & 15) { set_error("%s: workspace must be 16-byte aligned", who); return RTOD_E_ARG; }
-    const int pixels = h * w, ncol = cin * size * size;
-    const int64_t K = (int64_t)batch * pixels, tiles = wgrad_tiles(cout, cin, size);
-    const int S = (int)wgrad_slices(K, cap), L = (int)wgrad_slice_len(K, cap);
-    const int gm = (cout + WG_T - 1) / WG_T, gn = (ncol + WG_T - 1) / WG_T;
-    if (tiles * S > INT32_MAX) { set_error("%s: grid too large", who); return RTOD_E_ARG; }
+    const int pixels = sc.h * sc.w, ncol = cin * size * size, S = sc.slices;
+    const int gm = (cout + sc.tm - 1) / sc.tm, gn = (ncol + sc.tn - 1) / sc.tn;
+    if ((int64_t)gm * gn * S > INT32_MAX) { set_error("%s: grid too large", who); return RTOD_E_ARG; }
+    const int64_t n_dw = (int64_t)cout * ncol;
     float* part = (float*)ws;
-    float* part_db = part + (int64_t)S * cout * ncol;
-    float* pdb = db ? part_db : (float*)nullptr;
-#define RTOD_WGRAD(...) hipLaunchKernelGGL((wgrad_slice_kernel<__VA_ARGS__>), dim3((unsigned)(tiles * S)), dim3(256), 0, s, dz, x, cout, cin, pixels, w, xh, xw, (int)K, L, gm, gn, part, pdb)
-    if (stride == 2) RTOD_WGRAD(9, 2);
+    float* part_db = db ? part + S * n_dw : (float*)nullptr;
+#define RTOD_WGRAD(...) hipLaunchKernelGGL((wgrad_slice_kernel<__VA_ARGS__>), dim3((unsigned)((int64_t)gm * gn * S)), dim3(256), 0, s, dz, x, cout, cin, pixels, sc.w, h, w, (int)sc.K, sc.slice_len, gm, gn, part, part_db)
+    if (sc.tm == WT_M && size == 1) RTOD_WGRAD(1, 1, WT_M, WT_N);
+    else if (sc.tm == WT_M) RTOD_WGRAD(9, 1, WT_M, WT_N);
+    else if (stride == 2) RTOD_WGRAD(9, 2);
     else if (size == 1) RTOD_WGRAD(1);
     else RTOD_WGRAD(9);
 #undef RTOD_WGRAD
-    const int64_t n = (int64_t)cout * ncol + (db ? cout : 0);
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, part, part_db, (int64_t)cout * ncol, cout, S, row_scale, ncol, dw, db);
+    const int64_t n = n_dw + (db ? cout : 0);
+    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((n + sc.reduce_block - 1) / sc.reduce_block)), dim3(sc.reduce_block), 0, s, part, part_db, n_dw, cout, S,
+                       sc.group, row_scale, ncol, dw, db);
     return hip_fail(hipGetLastError(), (std::string(who) + " launch").c_str());
-}
-
-// ---------------------------------------------------------------------------------------------
-// Thin convs (rtod_conv_wgrad_thin): few channels, a huge K — YOLOv3-tiny's layer 0 at 416 x 416 batch 8 is a 16 x 27 dW over
-// K = 1,384,448.  The same slice kernel on a 32 x 128 tile (layer 0: one tile, layer 2's 32 x 144: two) with a slice count cut for K
-// instead of capped at 16.  The slice rule (rtod.h, exported as rtod_conv_wgrad_thin_slices), a pure function of the shape:
-//   tiles = ceil(cout / 32) * ceil(cin * size * size / 128);  target = ceil(1024 / tiles)
-//   L = 8 * ceil(ceil(K / 8) / target), clamped to [WGRAD_THIN_MIN_CHAIN, WGRAD_THIN_MAX_CHAIN];  S = ceil(K / L)
-// so a large K gets at least 1024 workgroups and no fmaf chain is longer than WGRAD_THIN_MAX_CHAIN = 1024 terms: the longest chain
-// measured inside the 4 x gate (dgrad.hip's per-tap chain of a 1024-filter conv; one chain of 4608 / 9216 terms was measured outside).
-// The S slice sums are added as a fixed two-level tree: groups of WGRAD_THIN_GROUP = 32 consecutive slices in ascending order, then the
-// group sums in ascending order (S = 1352 at layer 0: the longest run of fp32 adds is 31 + 42, not 1351).
-constexpr int WT_M = 32, WT_N = 128;
-
-void wgrad_thin_slices(int64_t K, int cout, int cin, int size, int64_t* slices, int64_t* slice_len) {
-    const int64_t tiles = (((int64_t)cout + WT_M - 1) / WT_M) * (((int64_t)cin * size * size + WT_N - 1) / WT_N);
-    const int64_t target = tiles < 1 ? 1 : std::max<int64_t>(1, (1024 + tiles - 1) / tiles);
-    int64_t L = 8 * (((K + 7) / 8 + target - 1) / target);
-    L = std::min<int64_t>(WGRAD_THIN_MAX_CHAIN, std::max<int64_t>(WGRAD_THIN_MIN_CHAIN, L));
-    *slice_len = L;
-    *slices = (K + L - 1) / L;
-}
-
-int wgrad_thin_check_shape(const char* who, int batch, int cout, int cin, int h, int w, int size) {
-    if (batch < 1 || cout < 1 || cin < 1 || h < 1 || w < 1 || (size != 1 && size != 3)) {
-        set_error("%s: unsupported shape (batch=%d cout=%d cin=%d h=%d w=%d size=%d; size 1 or 3)", who, batch, cout, cin, h, w, size);
-        return RTOD_E_ARG;
-    }
-    if ((int64_t)h * w > INT32_MAX || (int64_t)batch * h * w > INT32_MAX - WGRAD_THIN_MAX_CHAIN || (int64_t)cout * cin * size * size > INT32_MAX) {
-        set_error("%s: batch * h * w or cout * cin * size * size exceeds int32", who);
-        return RTOD_E_ARG;
-    }
-    return RTOD_OK;
-}
-
-size_t wgrad_thin_workspace_bytes(int batch, int cout, int cin, int h, int w, int size) {
-    int64_t S = 0, L = 0;
-    wgrad_thin_slices((int64_t)batch * h * w, cout, cin, size, &S, &L);
-    return sizeof(float) * (size_t)S * (size_t)cout * cin * size * size;
-}
-
-// the two-level tree over the slice sums, one thread per element of dW; then row_scale as wgrad_reduce_kernel applies it
-__global__ __launch_bounds__(64)
-void wgrad_thin_reduce_kernel(const float* __restrict__ part, int64_t n_dw, int slices, const double* __restrict__ row_scale, int ncol,
-                              float* __restrict__ dw) {
-#pragma clang fp contract(off)
-    const int64_t i = (int64_t)blockIdx.x * 64 + threadIdx.x;
-    if (i >= n_dw) return;
-    float total = 0.f;
-    for (int g0 = 0; g0 < slices; g0 += WGRAD_THIN_GROUP) {
-        const int g1 = min(g0 + WGRAD_THIN_GROUP, slices);
-        float v = part[(int64_t)g0 * n_dw + i];
-#pragma unroll 8
-        for (int s = g0 + 1; s < g1; ++s) v = v + part[(int64_t)s * n_dw + i];
-        total = g0 == 0 ? v : total + v;
-    }
-    if (row_scale) total = (float)((double)total * row_scale[i / ncol]);
-    dw[i] = total;
-}
-
-int launch_wgrad_thin(const float* dz, const float* x, int batch, int cout, int cin, int h, int w, int size, const double* row_scale, float* dw,
-                      void* ws, size_t ws_bytes, hipStream_t s) {
-    const char* who = "conv_wgrad_thin";
-    if (!dz || !x || !dw || !ws) { set_error("%s: null pointer", who); return RTOD_E_ARG; }
-    if (int rc = wgrad_thin_check_shape(who, batch, cout, cin, h, w, size)) return rc;
-    if (ws_bytes < wgrad_thin_workspace_bytes(batch, cout, cin, h, w, size)) { set_error("%s: workspace too small", who); return RTOD_E_ARG; }
-    if ((uintptr_t)ws & 15) { set_error("%s: workspace must be 16-byte aligned", who); return RTOD_E_ARG; }
-    const int pixels = h * w, ncol = cin * size * size;
-    const int64_t K = (int64_t)batch * pixels;
-    int64_t S = 0, L = 0;
-    wgrad_thin_slices(K, cout, cin, size, &S, &L);
-    const int gm = (cout + WT_M - 1) / WT_M, gn = (ncol + WT_N - 1) / WT_N;
-    if ((int64_t)gm * gn * S > INT32_MAX) { set_error("%s: grid too large", who); return RTOD_E_ARG; }
-    float* part = (float*)ws;
-    const dim3 grid((unsigned)((int64_t)gm * gn * S));
-    if (size == 1) hipLaunchKernelGGL((wgrad_slice_kernel<1, 1, WT_M, WT_N>), grid, dim3(256), 0, s, dz, x, cout, cin, pixels, w, h, w, (int)K, (int)L, gm, gn, part, (float*)nullptr);
-    else hipLaunchKernelGGL((wgrad_slice_kernel<9, 1, WT_M, WT_N>), grid, dim3(256), 0, s, dz, x, cout, cin, pixels, w, h, w, (int)K, (int)L, gm, gn, part, (float*)nullptr);
-    const int64_t n = (int64_t)cout * ncol;
-    hipLaunchKernelGGL(wgrad_thin_reduce_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, part, n, (int)S, row_scale, ncol, dw);
-    return hip_fail(hipGetLastError(), "conv_wgrad_thin launch");
 }
 
 }  // namespace rtod

@@ -164,6 +164,11 @@ def yolo_loss_grad_async(pred, bndbox, heads, num_class, min_box_size=24, grad_p
 
 
 _wgrad_ws = {}
+# (no size, stride, thin) -> the C entry of _wgrad (its workspace entry: the name + "_workspace"), whether it takes a row scale, a db
+_WGRAD_ENTRIES = {(True, 1, False): ("rtod_conv1x1_wgrad", False, True), (False, 1, False): ("rtod_conv_wgrad", True, True),
+                  (False, 2, False): ("rtod_conv_wgrad_s2", True, True), (False, 1, True): ("rtod_conv_wgrad_thin", True, False)}
+_DGRAD_ENTRIES = {(True, 1, False): "rtod_conv1x1_dgrad", (False, 1, False): "rtod_conv_dgrad", (False, 2, False): "rtod_conv_dgrad_s2",
+                  (False, 1, True): "rtod_conv_dgrad_thin"}                 # ... of _dgrad; every entry with a size takes a row scale
 
 
 def _wgrad(who, dz, x, size, row_scale, bias, stride=1, thin=False):
@@ -184,27 +189,24 @@ def _wgrad(who, dz, x, size, row_scale, bias, stride=1, thin=False):
     B, cout, cin, H, W = dz.size(0), dz.size(1), x.size(1), x.size(2), x.size(3)
     shape = (B, cout, cin, H * W) if size is None else (B, cout, cin, H, W, int(size))
     lib, dev = _ffi.lib(), dz.device
-    if thin and (size is None or s2 or bias):
+    name, takes_scale, takes_db = _WGRAD_ENTRIES.get((size is None, stride, bool(thin)), (None, False, False))
+    if thin and (name is None or bias):
         raise ValueError("%s: the thin entry takes a size, stride 1 and no bias gradient" % who)
-    entry, entry_workspace = ((lib.rtod_conv1x1_wgrad, lib.rtod_conv1x1_wgrad_workspace) if size is None else
-                              (lib.rtod_conv_wgrad_thin, lib.rtod_conv_wgrad_thin_workspace) if thin else
-                              (lib.rtod_conv_wgrad_s2, lib.rtod_conv_wgrad_s2_workspace) if s2 else (lib.rtod_conv_wgrad, lib.rtod_conv_wgrad_workspace))
     key = (dev.index, stride, thin) + shape
     ws = _wgrad_ws.get(key)
     if ws is None:
         nbytes = C.c_size_t()
-        _ffi.check(entry_workspace(*shape, C.byref(nbytes)))
+        _ffi.check(getattr(lib, name + "_workspace")(*shape, C.byref(nbytes)))
         if len(_wgrad_ws) > 16:
             _wgrad_ws.clear()
         ws = _wgrad_ws[key] = (torch.empty((nbytes.value + 7) // 8, dtype=torch.float64, device=dev), nbytes.value)
     k = 1 if size is None else int(size)
     dw = torch.empty((cout, cin, k, k), dtype=torch.float32, device=dev)
     db = torch.empty(cout, dtype=torch.float32, device=dev) if bias else None
-    scale = () if size is None else (_scale_ptr(row_scale, cout, dev),)
+    args = (C.c_void_p(dz.data_ptr()), C.c_void_p(x.data_ptr())) + shape + ((_scale_ptr(row_scale, cout, dev),) if takes_scale else ()) + (C.c_void_p(dw.data_ptr()),)
+    args += ((C.c_void_p(db.data_ptr()) if bias else None,) if takes_db else ()) + (C.c_void_p(ws[0].data_ptr()), ws[1], _stream(dev))
     with torch.cuda.device(dev):
-        _ffi.check(entry(
-            C.c_void_p(dz.data_ptr()), C.c_void_p(x.data_ptr()), *shape, *scale, C.c_void_p(dw.data_ptr()),
-            *(() if thin else (C.c_void_p(db.data_ptr()) if bias else None,)), C.c_void_p(ws[0].data_ptr()), ws[1], _stream(dev)))
+        _ffi.check(getattr(lib, name)(*args))
     return dw, db
 
 
@@ -231,11 +233,10 @@ def conv_wgrad_async(dz, x, size, row_scale=None, bias=False, stride=1):
     32) -> ``(dW [Cout,Cin,size,size], db [Cout] or None)`` of a ``size`` x ``size`` (1 or 3), stride-1, same-padding conv.
     ``row_scale`` (float64 device tensor [Cout], or the device address ``Darknet.conv_scale`` returns): every row of dW times it,
     one rounding.  ``stride`` 2 (rtod_conv_wgrad_s2): a 3x3 / stride-2 / pad-1 conv, ``dz`` [B,Cout,(H-1)//2+1,(W-1)//2+1] on the
-    conv's output map.  A ``Cin`` that is no multiple of 32 goes to ``conv_wgrad_thin_async`` (stride 1, no ``db``), and only such
-    a one.  Nothing synchronises; the workspace is cached per shape."""
-    if isinstance(x, torch.Tensor) and x.dim() == 4 and x.size(1) % 32 != 0:
-        return conv_wgrad_thin_async(dz, x, size, row_scale, bias, stride), None
-    return _wgrad("conv_wgrad", dz, x, int(size), row_scale, bias, stride)
+    conv's output map.  A ``Cin`` that is no multiple of 32 goes to the entry of ``conv_wgrad_thin_async`` (stride 1, no ``db``), and
+    only such a one.  Nothing synchronises; the workspace is cached per shape."""
+    thin = isinstance(x, torch.Tensor) and x.dim() == 4 and x.size(1) % 32 != 0
+    return _wgrad("conv_wgrad_thin" if thin else "conv_wgrad", dz, x, int(size), row_scale, bias, stride, thin)
 
 
 def conv_wgrad_thin_async(dz, x, size, row_scale=None, bias=False, stride=1):
@@ -256,7 +257,7 @@ def conv_wgrad_thin_slices(batch, cout, cin, height, width, size):
 def _dgrad(who, w, dz, size, row_scale, y, slope, stride=1, in_hw=None, thin=False):
     """The body of ``conv1x1_dgrad_async`` (``size`` None: rtod_conv1x1_dgrad, shape (B, Cout, Cin, pixels), no scale) and
     ``conv_dgrad_async`` (rtod_conv_dgrad, shape (B, Cout, Cin, H, W, size); ``stride`` 2: rtod_conv_dgrad_s2, H x W the conv's INPUT
-    map): the tensor checks, the output, the launch."""
+    map): the tensor checks, the output, the launch.  ``thin``: rtod_conv_dgrad_thin (any Cin, stride 1)."""
     for t in (w, dz) + ((y,) if y is not None else ()):
         _need_cuda(t, who)
     k = 1 if size is None else int(size)
@@ -283,15 +284,14 @@ def _dgrad(who, w, dz, size, row_scale, y, slope, stride=1, in_hw=None, thin=Fal
     B, cout, cin = dz.size(0), dz.size(1), w.size(1)
     shape = (B, cout, cin, H * W) if size is None else (B, cout, cin, H, W, k)
     lib, dev = _ffi.lib(), dz.device
-    if thin and (size is None or stride == 2):
+    name = _DGRAD_ENTRIES.get((size is None, stride, bool(thin)))
+    if name is None:
         raise ValueError("%s: the thin entry takes a size and stride 1" % who)
-    entry = lib.rtod_conv1x1_dgrad if size is None else lib.rtod_conv_dgrad_thin if thin else lib.rtod_conv_dgrad_s2 if stride == 2 else lib.rtod_conv_dgrad
     dx = torch.empty((B, cin, H, W), dtype=torch.float32, device=dev)
     scale = () if size is None else (_scale_ptr(row_scale, cout, dev),)
+    args = (C.c_void_p(w.data_ptr()),) + scale + (C.c_void_p(dz.data_ptr()), C.c_void_p(y.data_ptr()) if y is not None else None, float(slope)) + shape
     with torch.cuda.device(dev):
-        _ffi.check(entry(
-            C.c_void_p(w.data_ptr()), *scale, C.c_void_p(dz.data_ptr()), C.c_void_p(y.data_ptr()) if y is not None else None, float(slope), *shape,
-            C.c_void_p(dx.data_ptr()), _stream(dev)))
+        _ffi.check(getattr(lib, name)(*args, C.c_void_p(dx.data_ptr()), _stream(dev)))
     return dx
 
 
@@ -310,10 +310,9 @@ def conv_dgrad_async(w, dz, size, row_scale=None, y=None, slope=1.0, stride=1, i
     of 32; one fmaf chain per tap, the tap sums added in ascending order: an order the shape fixes; nothing synchronises.
     ``stride`` 2 (rtod_conv_dgrad_s2): a 3x3 / stride-2 / pad-1 conv, ``dz`` [B,Cout,Ho,Wo] on its output map and ``dx`` on its
     INPUT map, whose size comes from ``y``, else from ``in_hw = (H, W)``: ``Ho`` alone does not tell ``2 Ho`` from ``2 Ho - 1``.
-    A ``Cin`` that is no multiple of 32 goes to ``conv_dgrad_thin_async`` (stride 1), and only such a one."""
-    if isinstance(w, torch.Tensor) and w.dim() in (2, 4) and w.size(1) % 32 != 0:
-        return conv_dgrad_thin_async(w, dz, size, row_scale, y, slope, stride)
-    return _dgrad("conv_dgrad", w, dz, int(size), row_scale, y, slope, stride, in_hw)
+    A ``Cin`` that is no multiple of 32 goes to the entry of ``conv_dgrad_thin_async`` (stride 1), and only such a one."""
+    thin = isinstance(w, torch.Tensor) and w.dim() in (2, 4) and w.size(1) % 32 != 0
+    return _dgrad("conv_dgrad_thin" if thin else "conv_dgrad", w, dz, int(size), row_scale, y, slope, stride, None if thin else in_hw, thin)
 
 
 def conv_dgrad_thin_async(w, dz, size, row_scale=None, y=None, slope=1.0, stride=1):

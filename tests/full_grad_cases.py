@@ -1,20 +1,15 @@
 """What the host and GPU tests of the "full" training scope share (max-pool backward, thin-conv gradients, layer 0): the shapes of the
-kernel tests, numpy references of the max-pool backward with the forward's first-maximum rule, the plan's listing entry, and the CPU
-model of the full sub-graph — scope_grad_cases.cpu_graph with two more kinds: a [maxpool] written as a gather with the DEVICE's winners
-(or torch's own pool), and layer 0 fed the prepared network input."""
+kernel tests, numpy references of the max-pool backward with the forward's first-maximum rule, the plan's listing entry, the fixed
+batch at any size and the winner-flip rule.  The CPU model of the full sub-graph is scope_grad_cases.cpu_graph (its [maxpool] arm and
+its network-input value)."""
 import numpy as np
 import torch
 
-import scope_grad_cases as S
-from head_grad_cases import cpu_head_model
-from scope_grad_cases import _bn_of, _box, _conv_of, _t64, plan_list
+from scope_grad_cases import KEEP, _box, _t64, forward_error, plan_list, torch_pool
 
 F = np.float32
 U = 2.0 ** -24
-fn = torch.nn.functional
-FULL = {"keep_head_inputs": 1, "keep_full_activations": 1}
-S.KEEP.setdefault("full", FULL)                                       # scope_trainer / check_training_steps look their scope up
-S.ENTRY.setdefault("full", "full_gradients")
+FULL = KEEP["full"]
 
 # (B, C, H, W, stride) of rtod_maxpool_grad: one pixel, one window, odd last row / column, the clamped pool on odd maps, tiny's 13 x 13
 # stride-1 pool, more than one block, one row (every window clamped in y), one column whose stride-2 output is empty
@@ -66,11 +61,6 @@ def maxpool_grad_ref(dz, x, stride, dtype=np.float64):
     return out.reshape(B, C_, H, W), mass.reshape(B, C_, H, W)
 
 
-def torch_pool(x, stride):
-    """The reference's two modules: nn.MaxPool2d(2, 2), and MaxPoolStride1 (replicate pad right / bottom, then MaxPool2d(2, 1))."""
-    return fn.max_pool2d(x, 2, 2) if stride == 2 else fn.max_pool2d(fn.pad(x, (0, 1, 0, 1), mode="replicate"), 2, 1)
-
-
 def torch_pool_grad(dz, x, stride):
     """CPU autograd of torch_pool in the dtype of ``x`` (numpy in, numpy out); an empty output map gives zeros."""
     if dz.size == 0:
@@ -89,84 +79,7 @@ def full_batch(height, width, classes, B=3):
             np.stack([box(10, 50, 12, 40), box(52, 12, 20, 20, cls=2), box(40, 30, 60, 60)])][:B]
 
 
-# ---------------------------------------------------------------------------------------------- the CPU model of the full sub-graph
-def cpu_full_graph(m, t, B, dtype, x_in, weights=None, masks=None, winners=None):
-    """scope_grad_cases.cpu_graph for scope "full": ``x_in`` is the prepared network input (what layer 0 reads); a [maxpool] is a gather
-    with ``winners[layer]`` (pool_winners of the DEVICE's read_layer copy of the pool's input) where given, else torch's own pool.
-    Returns (values per layer, {conv: leaf weight}, {conv: (pre-activation, input)}, {pool: its input value})."""
-    layers, readers, member, scales = t._graph("full")
-    cast = lambda a: torch.as_tensor(a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)).to(dtype)
-    val, leaves, pres, pooled = {-1: cast(x_in)}, {}, {}, {}
-
-    def value(src):
-        if src not in val:
-            assert not member[src]
-            val[src] = cast(m.read_layer(src, B))
-        return val[src]
-
-    for L in layers:
-        i = L.index
-        if not member[i]:
-            continue
-        if L.type == "convolutional":
-            conv, x = _conv_of(m, i), value(i - 1)
-            W = cast(conv.weight if weights is None or i not in weights else weights[i])
-            if i in scales:
-                W.requires_grad_(True)
-                leaves[i] = W
-                bn = _bn_of(m, i)
-                pre = fn.batch_norm(fn.conv2d(x, W, stride=L.stride, padding=L.size // 2), cast(bn.running_mean), cast(bn.running_var), cast(bn.weight), cast(bn.bias),
-                                    False, 0.0, 1e-5)
-                pres[i] = (pre, x)
-                val[i] = pre if not L.leaky else pre * cast(masks[i]) if masks is not None else fn.leaky_relu(pre, 0.1)
-            else:
-                val[i] = fn.conv2d(x, W, cast(conv.bias))
-        elif L.type == "maxpool":
-            x = value(i - 1)
-            pooled[i] = x
-            if winners is None:
-                val[i] = torch_pool(x, L.stride)
-            else:
-                idx = torch.from_numpy(winners[i])
-                val[i] = x.flatten(2).gather(2, idx.flatten(2)).reshape(idx.shape)
-        elif L.type == "upsample":
-            x = value(i - 1)
-            val[i] = fn.interpolate(x, scale_factor=2, mode="nearest") if L.nearest else fn.interpolate(x, scale_factor=2, mode="bilinear", align_corners=False)
-        elif L.type == "shortcut":
-            val[i] = value(L.srcs[0]) + value(L.srcs[1])
-        else:
-            parts, off = [], 0
-            for s in L.srcs:
-                parts.append(value(s) if member[s] else cast(m.read_layer(i, B))[:, off:off + layers[s].cout])
-                off += layers[s].cout
-            val[i] = torch.cat(parts, 1)
-    return val, leaves, pres, pooled
-
-
-def cpu_full_grads(m, t, B, dtype, x_in, masks, winners, dzs):
-    val, leaves, pres, pooled = cpu_full_graph(m, t, B, dtype, x_in, masks=masks, winners=winners)
-    total = sum((val[head] * dz.detach().cpu().to(dtype)).sum() for (head, _), dz in zip(m.head_layers(), dzs))
-    total.backward()
-    return {i: W.grad.numpy().astype(np.float64) for i, W in leaves.items()}, pres, pooled
-
-
-def cpu_full_loss(m, t, B, images, grads, x_in):
-    """scope_grad_cases.cpu_scope_loss over cpu_full_graph with torch's own leaky_relu and pools."""
-    W0 = {c: _conv_of(m, c).weight.detach().clone() for c in grads}
-    heads = [h for h, _ in m.head_layers()]
-
-    def cpu(s, dtype):
-        with torch.no_grad():
-            val = cpu_full_graph(m, t, B, dtype, x_in, weights={c: W0[c].double() + s * grads[c].cpu().double() for c in grads})[0]
-        acts = [val[h - 1].detach().numpy() for h in heads]
-        ws = [_t64(_conv_of(m, h).weight).numpy() for h in heads]
-        bs = [_t64(_conv_of(m, h).bias).numpy() for h in heads]
-        if dtype != torch.float64:
-            ws, bs = [a.astype(F) for a in ws], [a.astype(F) for a in bs]
-        return cpu_head_model(acts, ws, bs, t.heads, images, 4, None if dtype == torch.float64 else dtype)["loss"]
-    return cpu
-
-
+# ---------------------------------------------------------------------------------------------- the winner-flip rule
 def winner_flips_within_the_forward_error(label, m, layers, pool, winners, x64, precision, x_in):
     """The winner-flip rule, beside over_the_floor's mask-flip rule: where the device's winner of a window of ``pool`` is not the maximum
     of the float64 model's input ``x64`` [B,C,H,W], the two float64 values may differ by no more than the forward's own error at the conv
@@ -184,13 +97,7 @@ def winner_flips_within_the_forward_error(label, m, layers, pool, winners, x64, 
         return 0
     src = pool - 1
     assert layers[src].type == "convolutional" and layers[src].bn, (label, pool, n)
-    conv, bn, P = _conv_of(m, src), _bn_of(m, src), layers[src]
-    gamma, beta, mean, var = (_t64(v) for v in (bn.weight, bn.bias, bn.running_mean, bn.running_var))
-    s = gamma / torch.sqrt(var + 1e-5)
-    xin = _t64(m.read_layer(src - 1, B)) if src > 0 else _t64(x_in)
-    mass = fn.conv2d(xin.abs(), (_t64(conv.weight) * s[:, None, None, None]).abs(), stride=P.stride, padding=P.size // 2).numpy() + \
-        np.abs((beta - mean * s).numpy())[None, :, None, None]
-    gate = ((conv.in_channels * P.size * P.size + 2) * U if S.GATES[precision] is None else S.GATES[precision]) * mass
+    gate = forward_error(m, layers[src], _t64(m.read_layer(src - 1, B)) if src > 0 else _t64(x_in), precision)
     gate_dev = np.take_along_axis(gate.reshape(B, C_, -1), winners.reshape(B, C_, -1), 2)
     gate_best = torch_pool(torch.from_numpy(gate), L.stride).numpy().reshape(B, C_, -1)     # an upper bound of the true maximum's own gate
     assert (np.abs(dev - best)[flips] <= (gate_dev + gate_best)[flips]).all(), (label, pool, n)

@@ -1,4 +1,4 @@
-"""What the host and GPU tests of the training scopes (heads, blocks, neck, backbone) share: the plan's listing entries on the C ABI,
+"""What the host and GPU tests of the training scopes (heads, blocks, neck, backbone, full) share: the plan's listing entries on the C ABI,
 models and trainers on synthetic weights, the fixed batch of the end-to-end tests, the CPU model of a scope's sub-graph with its
 autograd gradients, and the gate every end-to-end gradient test applies: the mask-flip rule and 4 x the float32 floor."""
 import ctypes as C
@@ -17,8 +17,8 @@ U = 2.0 ** -24
 fn = torch.nn.functional
 GATES = {"fp32": None, "f16s3": 1e-4, "f16": 1e-3}                  # the forward's own error as a fraction of the mass; None: (K1 + 2) u
 KEEP = {"blocks": {"keep_head_inputs": 1, "keep_block_inputs": 1}, "neck": {"keep_head_inputs": 1, "keep_neck_activations": 1},
-        "backbone": {"keep_head_inputs": 1, "keep_backbone_activations": 1}}
-ENTRY = {"blocks": "block_gradients", "neck": "neck_gradients", "backbone": "backbone_gradients"}
+        "backbone": {"keep_head_inputs": 1, "keep_backbone_activations": 1}, "full": {"keep_head_inputs": 1, "keep_full_activations": 1}}
+ENTRY = {"blocks": "block_gradients", "neck": "neck_gradients", "backbone": "backbone_gradients", "full": "full_gradients"}
 
 
 def plan_list(entry, h, columns):
@@ -112,15 +112,22 @@ def tenth_heads(m):
 
 
 # ---------------------------------------------------------------------------------------------- the CPU model of a scope's sub-graph
-def cpu_graph(m, t, B, dtype, weights=None, masks=None, cut=None, *, scope):
+def torch_pool(x, stride):
+    """The reference's two modules: nn.MaxPool2d(2, 2), and MaxPoolStride1 (replicate pad right / bottom, then MaxPool2d(2, 1))."""
+    return fn.max_pool2d(x, 2, 2) if stride == 2 else fn.max_pool2d(fn.pad(x, (0, 1, 0, 1), mode="replicate"), 2, 1)
+
+
+def cpu_graph(m, t, B, dtype, weights=None, masks=None, cut=None, *, scope, x_in=None, winners=None):
     """The sub-graph ``t._graph(scope)`` on the CPU in ``dtype`` from the module's parameters: conv (stride 1 or 2) -> eval BatchNorm ->
     leaky (written as a product with ``masks[layer]``, the DEVICE's, where given; else torch's leaky_relu), shortcuts, routes,
-    F.interpolate, head convs; fed the device's boundary inputs (read_layer of the layers the graph reads from outside).  ``weights``:
-    {conv: weight} in place of the module's; ``cut = (producer, reader)``: that reader sees the producer's value detached (its
-    contribution to the producer's gradient is zero).  Returns (values per layer, {conv: leaf weight}, {conv: (pre-activation, input)})."""
+    F.interpolate, head convs, and a [maxpool] as a gather with ``winners[layer]`` (full_grad_cases.pool_winners of the DEVICE's
+    read_layer copy of the pool's input) where given, else torch's own pool; fed the device's boundary inputs (read_layer of the layers
+    the graph reads from outside) and ``x_in``, the prepared network input, where layer 0 is a member.  ``weights``: {conv: weight} in
+    place of the module's; ``cut = (producer, reader)``: that reader sees the producer's value detached (its contribution to the
+    producer's gradient is zero).  Returns (values per layer, {conv: leaf weight}, {conv: (pre-activation, input), pool: (None, input)})."""
     layers, readers, member, scales = t._graph(scope)
     cast = lambda a: torch.as_tensor(a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)).to(dtype)
-    val, leaves, pres = {}, {}, {}
+    val, leaves, pres = ({} if x_in is None else {-1: cast(x_in)}), {}, {}
 
     def value(src, reader):
         if src not in val:
@@ -145,6 +152,14 @@ def cpu_graph(m, t, B, dtype, weights=None, masks=None, cut=None, *, scope):
                 val[i] = pre if not L.leaky else pre * cast(masks[i]) if masks is not None else fn.leaky_relu(pre, 0.1)
             else:
                 val[i] = fn.conv2d(x, W, cast(conv.bias))
+        elif L.type == "maxpool":
+            x = value(i - 1, i)
+            pres[i] = (None, x)
+            if winners is None:
+                val[i] = torch_pool(x, L.stride)
+            else:
+                idx = torch.from_numpy(winners[i])
+                val[i] = x.flatten(2).gather(2, idx.flatten(2)).reshape(idx.shape)
         elif L.type == "upsample":
             x = value(i - 1, i)
             val[i] = fn.interpolate(x, scale_factor=2, mode="nearest") if L.nearest else fn.interpolate(x, scale_factor=2, mode="bilinear", align_corners=False)
@@ -159,28 +174,35 @@ def cpu_graph(m, t, B, dtype, weights=None, masks=None, cut=None, *, scope):
     return val, leaves, pres
 
 
-def cpu_graph_grads(m, t, B, dtype, masks, dzs, cut=None, *, scope):
-    val, leaves, pres = cpu_graph(m, t, B, dtype, masks=masks, cut=cut, scope=scope)
+def cpu_graph_grads(m, t, B, dtype, masks, dzs, cut=None, *, scope, x_in=None, winners=None):
+    val, leaves, pres = cpu_graph(m, t, B, dtype, masks=masks, cut=cut, scope=scope, x_in=x_in, winners=winners)
     total = sum((val[head] * dz.detach().cpu().to(dtype)).sum() for (head, _), dz in zip(m.head_layers(), dzs))
     total.backward()
     return {i: W.grad.numpy().astype(np.float64) for i, W in leaves.items()}, pres
 
 
 # ---------------------------------------------------------------------------------------------- the gate of the end-to-end tests
+def forward_error(m, L, x, precision):
+    """The forward's own error of the BatchNorm conv of layer row ``L`` on the float64 input ``x``, per output element: (K1 + 2) u x mass
+    at fp32 and GATES[precision] x mass otherwise, mass = sum |w s| |x| + |bias| with the eval BatchNorm folded into s and the bias."""
+    conv, bn = _conv_of(m, L.index), _bn_of(m, L.index)
+    gamma, beta, mean, var = (_t64(v) for v in (bn.weight, bn.bias, bn.running_mean, bn.running_var))
+    s = (gamma / torch.sqrt(var + 1e-5))
+    mass = fn.conv2d(x.abs(), (_t64(conv.weight) * s[:, None, None, None]).abs(), stride=L.stride, padding=L.size // 2).numpy() + \
+        np.abs((beta - mean * s).numpy())[None, :, None, None]
+    return ((conv.in_channels * L.size * L.size + 2) * U if GATES[precision] is None else GATES[precision]) * mass
+
+
 def over_the_floor(label, m, layers, convs, precision, B, grads, want, floor, pres):
     """Per conv of ``convs``: asserts the mask-flip rule — a flip of the device's mask against the float64 pre-activation ``pres[c][0]``
-    is legitimate only where |pre_64| is within the forward's own error, (K1 + 2) u (sum |w s| |x| + |bias|) at fp32 and GATES[precision]
-    of that mass otherwise — prints rms and max of (dW_dev - dW_64) / max |dW_64| beside the same figures of the float32 floor, and
-    returns the [(conv, rms ratio, max ratio)] that exceed 4 x the floor (the caller asserts it empty after every figure is printed)."""
+    is legitimate only where |pre_64| is within the forward's own error (forward_error) — prints rms and max of
+    (dW_dev - dW_64) / max |dW_64| beside the same figures of the float32 floor, and returns the [(conv, rms ratio, max ratio)] that
+    exceed 4 x the floor (the caller asserts it empty after every figure is printed)."""
     over = []
     for c in convs:
-        conv, bn, L = _conv_of(m, c), _bn_of(m, c), layers[c]
+        L = layers[c]
         pre, x = (a.detach() for a in pres[c])
-        gamma, beta, mean, var = (_t64(v) for v in (bn.weight, bn.bias, bn.running_mean, bn.running_var))
-        s = (gamma / torch.sqrt(var + 1e-5))
-        mass = fn.conv2d(x.abs(), (_t64(conv.weight) * s[:, None, None, None]).abs(), stride=L.stride, padding=L.size // 2).numpy() + \
-            np.abs((beta - mean * s).numpy())[None, :, None, None]
-        gate = ((conv.in_channels * L.size * L.size + 2) * U if GATES[precision] is None else GATES[precision]) * mass
+        gate = forward_error(m, L, x, precision)
         y_dev = m.read_layer(c, B).cpu().numpy()
         flips = (pre.numpy() > 0) != (y_dev > 0)
         assert (np.abs(pre.numpy())[flips] <= gate[flips]).all(), (label, c, int(flips.sum()))
@@ -197,15 +219,15 @@ def over_the_floor(label, m, layers, convs, precision, B, grads, want, floor, pr
 
 
 # ---------------------------------------------------------------------------------------------- the directional derivative
-def cpu_scope_loss(m, t, B, images, grads, scope):
-    """``cpu(s, dtype)``: the loss of the CPU model of the scope's sub-graph (torch's own leaky_relu) at weights W + s g, on the device's
-    boundary inputs."""
+def cpu_scope_loss(m, t, B, images, grads, scope, x_in=None):
+    """``cpu(s, dtype)``: the loss of the CPU model of the scope's sub-graph (torch's own leaky_relu and pools) at weights W + s g, on
+    the device's boundary inputs (and ``x_in``, the prepared network input, where layer 0 is a member)."""
     W0 = {c: _conv_of(m, c).weight.detach().clone() for c in grads}
     heads = [h for h, _ in m.head_layers()]
 
     def cpu(s, dtype):
         with torch.no_grad():
-            val, _, _ = cpu_graph(m, t, B, dtype, weights={c: W0[c].double() + s * grads[c].cpu().double() for c in grads}, scope=scope)
+            val, _, _ = cpu_graph(m, t, B, dtype, weights={c: W0[c].double() + s * grads[c].cpu().double() for c in grads}, scope=scope, x_in=x_in)
         acts = [val[h - 1].detach().numpy() for h in heads]
         ws = [_t64(_conv_of(m, h).weight).numpy() for h in heads]
         bs = [_t64(_conv_of(m, h).bias).numpy() for h in heads]

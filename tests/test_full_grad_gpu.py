@@ -17,10 +17,11 @@ import pytest
 import torch
 
 from block_grad_cases import wgrad_ref
-from full_grad_cases import (DGRAD_THIN_SHAPES, FULL, POOL_MINI_FULL, POOL_SHAPES, TINY_FULL, U, WGRAD_THIN_SHAPES, cpu_full_grads, cpu_full_loss, full_batch,
-                             maxpool_grad_ref, pool_out_hw, pool_winners, torch_pool_grad, winner_flips_within_the_forward_error)
+from full_grad_cases import (DGRAD_THIN_SHAPES, FULL, POOL_MINI_FULL, POOL_SHAPES, TINY_FULL, U, WGRAD_THIN_SHAPES, full_batch, maxpool_grad_ref,
+                             pool_out_hw, pool_winners, torch_pool_grad, winner_flips_within_the_forward_error)
 from neck_grad_cases import conv_dgrad_ref
-from scope_grad_cases import _dev, _forward, _frames, _same, check_directional_derivative, check_training_steps, over_the_floor, scope_trainer, tenth_heads
+from scope_grad_cases import _dev, _forward, _frames, _same, check_directional_derivative, check_training_steps, cpu_graph_grads, cpu_scope_loss
+from scope_grad_cases import over_the_floor, scope_trainer, tenth_heads
 from realtimeobjectdetection_amd import cfgs, synth, train as T
 
 pytestmark = pytest.mark.gpu
@@ -166,7 +167,7 @@ def _batch(height, width, classes=3, B=3):
 @pytest.mark.parametrize("height,width,precision,stem", [(64, 64, "fp32", 16), (64, 96, "fp32", 16), (40, 40, "fp32", 16), (64, 64, "f16s3", 32)])
 def test_full_gradients_against_autograd(tmp_path, height, width, precision, stem):
     """dW of DarknetTrainer.full_gradients for every conv of the full graph of pool_train_mini_cfg against torch autograd of that
-    sub-graph (full_grad_cases.cpu_full_graph) with the DEVICE's leaky masks and the DEVICE's pool winners, fed the prepared network
+    sub-graph (scope_grad_cases.cpu_graph) with the DEVICE's leaky masks and the DEVICE's pool winners, fed the prepared network
     input (or, where layer 0 is no member, the device's boundary inputs) and pulled back from the device's dz, once in float64 (the
     truth) and once in float32 torch (the floor).
 
@@ -198,11 +199,11 @@ def test_full_gradients_against_autograd(tmp_path, height, width, precision, ste
     winners = {p: pool_winners(m.read_layer(p - 1, B).cpu().numpy(), layers[p].stride) for p in pools}
     dzs = T.yolo_loss_grad_async(t._forward_train(xd), bnd, t.heads, t.num_classes, t.min_box_size)["grad_raw"]
     x_in = t._net_input
-    want, pres, pooled = cpu_full_grads(m, t, B, torch.float64, x_in, masks, winners, dzs)
-    floor, _, _ = cpu_full_grads(m, t, B, torch.float32, x_in, masks, winners, dzs)
+    want, pres = cpu_graph_grads(m, t, B, torch.float64, masks, dzs, scope="full", x_in=x_in, winners=winners)
+    floor, _ = cpu_graph_grads(m, t, B, torch.float32, masks, dzs, scope="full", x_in=x_in, winners=winners)
     label = "pool_mini %dx%d %s stem %d" % (height, width, precision, stem)
     for p in pools:
-        n = winner_flips_within_the_forward_error(label, m, layers, p, winners[p], pooled[p], precision, x_in)
+        n = winner_flips_within_the_forward_error(label, m, layers, p, winners[p], pres[p][1], precision, x_in)
         print("%s pool %d (stride %d): %d winner flips of %d windows" % (label, p, layers[p].stride, n, winners[p].size))
     over = over_the_floor(label, m, layers, convs, precision, B, grads, want, floor, pres)
     assert all(float(g.abs().sum()) > 0 for g in grads.values())
@@ -234,7 +235,7 @@ def test_the_loss_falls_along_the_full_gradient_by_what_it_says(tmp_path):
     l0 = float(t.last_components[0].item())
     assert sorted(grads) == POOL_MINI_FULL[16]
     images = full_batch(64, 64, 3, B)
-    check_directional_derivative(m, t, xd, bnd, grads, cpu_full_loss(m, t, B, images, grads, t._net_input), l0)
+    check_directional_derivative(m, t, xd, bnd, grads, cpu_scope_loss(m, t, B, images, grads, "full", t._net_input), l0)
 
 
 @pytest.mark.parametrize("precision,stem", [("fp32", 16), ("f16s3", 32)])

@@ -25,6 +25,17 @@ tile loop; the same dumper writes it (``--grad``) and it is not regenerated eith
   slope 0.1; y is a standard normal with every 7th element set to 0.0, so the mask sees positives, negatives and exact zeros.  One
   further digest per size runs without y.
 * Stride-2 weight gradients: dW and db on S2_SHAPES, and with the row scale on the ragged-Cout shape.
+
+A third record, tests/golden/thin_bits.json (``--thin``), holds the thin-conv gradients (rtod_conv_wgrad_thin, rtod_conv_dgrad_thin) and
+one walk of the "full" scope to the bits they had BEFORE the thin weight gradient was folded into the one launcher of csrc/wgrad.hip.
+
+* Thin weight gradients: dW on full_grad_cases.WGRAD_THIN_SHAPES and on THIN_TREE_SHAPES, which a host mirror of the slice rule chose
+  so that the reduction tree has a second level (more than 32 slices), a ragged last group and a short last slice, with the slice length
+  on the lower clamp (256), strictly between the clamps (304) and on the upper one (1024); the test asserts these (slices, slice
+  length) through conv_wgrad_thin_slices.  Two of them also run with the random signed float64 row scale.
+* Thin data gradients: dx on full_grad_cases.DGRAD_THIN_SHAPES, plain and scaled, y and slope as above.
+* One walk: DarknetTrainer.full_gradients on pool_train_mini_cfg(64, 64, classes=3, stem=16), fp32, on the batch of
+  test_full_grad_gpu._batch: one digest per trained conv's dW (the Python routing, and layer 0 over the prepared network input).
 """
 import hashlib
 import json
@@ -37,8 +48,10 @@ import torch
 from realtimeobjectdetection_amd import cfgs, train as T
 from realtimeobjectdetection_amd.train import HeadOptimizer
 from backbone_grad_cases import S2_SHAPES, out_hw
+from full_grad_cases import DGRAD_THIN_SHAPES, POOL_MINI_FULL, WGRAD_THIN_SHAPES
 from neck_grad_cases import DGRAD_SHAPES
 from test_block_grad_gpu import _batch, _block_trainer
+from test_full_grad_gpu import _batch as _full_batch, _full_trainer
 
 pytestmark = pytest.mark.gpu
 F = np.float32
@@ -57,6 +70,18 @@ GRAD_CASES = ([("conv1x1_dgrad", 1, 1, s, False, True) for s in DGRAD_SHAPES]
               + [("conv_dgrad", size, 1, RAGGED, False, False) for size in (1, 3)]
               + [("conv_dgrad", 3, 2, s, scaled, True) for s in S2_SHAPES for scaled in (False, True)]
               + [("conv_wgrad", 3, 2, s, False, False) for s in S2_SHAPES] + [("conv_wgrad", 3, 2, RAGGED, True, False)])
+
+THIN_RECORD = os.path.join(os.path.dirname(RECORD), "thin_bits.json")
+# (B, Cout, Cin, H, W, size) -> (slices, slice length) of rtod_conv_wgrad_thin.  66 slices: groups of 32 + 32 + 2, the last slice 130 terms;
+# 72 slices on 2 x 2 tiles: 32 + 32 + 8; 8 tiles: L = 304 strictly between the clamps, the last slice 96 terms; one tile over
+# K = 1,049,600: L on the upper clamp, 33 groups, the last of one slice
+THIN_TREE_SHAPES = {(1, 16, 3, 129, 130, 3): (66, 256), (2, 40, 16, 96, 96, 3): (72, 256), (1, 97, 16, 160, 240, 3): (127, 304),
+                    (1, 1, 1, 1025, 1024, 1): (1025, 1024)}
+THIN_SCALED = [(1, 16, 3, 129, 130, 3), (1, 97, 16, 160, 240, 3)]
+# (entry, shape, scaled)
+THIN_CASES = ([("conv_wgrad_thin", s, False) for s in WGRAD_THIN_SHAPES + list(THIN_TREE_SHAPES)] + [("conv_wgrad_thin", s, True) for s in THIN_SCALED]
+              + [("conv_dgrad_thin", s, scaled) for s in DGRAD_THIN_SHAPES for scaled in (False, True)])
+THIN_WALK = "full_gradients/pool_train_mini_64x64_stem16/fp32"
 
 
 def sha(t):
@@ -111,6 +136,37 @@ def grad_digest(entry, size, stride, shape, scaled, masked):
     return {"dx": sha(dx)}
 
 
+def thin_key(entry, shape, scaled):
+    return "%s/%s/%s" % (entry, "x".join(str(v) for v in shape), "scaled" if scaled else "plain")
+
+
+def thin_digest(entry, shape, scaled):
+    """{"dw"} of one thin weight-gradient call or {"dx"} of one thin data-gradient call on seeded inputs (grad_digest's y and slope)."""
+    B, cout, cin, H, W, size = shape
+    rng = np.random.RandomState(1000 * B + 10 * cout + H * W + size + cin)
+    w = torch.from_numpy(rng.standard_normal((cout, cin, size, size)).astype(F)).cuda()
+    dz = torch.from_numpy(rng.standard_normal((B, cout, H, W)).astype(F)).cuda()
+    y = rng.standard_normal((B, cin, H, W)).astype(F)
+    scale = torch.from_numpy(rng.uniform(0.2, 3.0, cout) * rng.choice([-1.0, 1.0], cout)).cuda() if scaled else None
+    if entry == "conv_wgrad_thin":
+        dw = T.conv_wgrad_thin_async(dz, torch.from_numpy(y).cuda(), size, row_scale=scale)
+        assert tuple(dw.shape) == (cout, cin, size, size)
+        return {"dw": sha(dw)}
+    y.reshape(-1)[::7] = 0.0
+    dx = T.conv_dgrad_thin_async(w, dz, size, row_scale=scale, y=torch.from_numpy(y).cuda(), slope=0.1)
+    assert tuple(dx.shape) == (B, cin, H, W)
+    return {"dx": sha(dx)}
+
+
+def walk_digest(d):
+    """{conv: digest of its dW} of one full_gradients walk of pool_train_mini_cfg(64, 64, classes=3, stem=16), fp32."""
+    m, t = _full_trainer(d, 64, 64, "fp32", 16)
+    xd, bnd = _full_batch(64, 64)
+    _, _, grads = t.full_gradients(xd, bnd)
+    assert m.active_precision == "fp32" and sorted(grads) == POOL_MINI_FULL[16]
+    return {str(c): sha(dw) for c, dw in sorted(grads.items())}
+
+
 def _state_digest(m, t):
     out = {"image": sha(m.packed_weights())}
     for layer, st in sorted(t.optimizer.state.items()):
@@ -159,6 +215,25 @@ def test_data_and_stride2_gradients_have_the_recorded_bits(case):
     got = grad_digest(*case)
     print("GRAD BITS %s: %s" % (grad_key(*case), got))
     assert got == _record(GRAD_RECORD)[grad_key(*case)]
+
+
+def test_thin_tree_shapes_have_the_slices_they_were_chosen_for():
+    for shape, (S, L) in THIN_TREE_SHAPES.items():
+        assert T.conv_wgrad_thin_slices(*shape) == (S, L), shape
+        assert S > 32 and (S - 1) * L < shape[0] * shape[3] * shape[4] <= S * L      # a second tree level; S slices of L cover K
+
+
+@pytest.mark.parametrize("case", THIN_CASES, ids=lambda c: thin_key(*c))
+def test_thin_gradients_have_the_recorded_bits(case):
+    got = thin_digest(*case)
+    print("THIN BITS %s: %s" % (thin_key(*case), got))
+    assert got == _record(THIN_RECORD)[thin_key(*case)]
+
+
+def test_full_walk_has_the_recorded_bits(tmp_path):
+    got = walk_digest(tmp_path)
+    print("THIN BITS %s: %s" % (THIN_WALK, got))
+    assert got == _record(THIN_RECORD)[THIN_WALK]
 
 
 @pytest.mark.parametrize("precision", PRECISIONS)

@@ -10,7 +10,9 @@ the first library's model and each group of its kernel calls (dgrad_s1, dgrad3_s
 functions of tensors alone) is replayed under every library in alternating rounds, the order reversed every round; neck_step and
 backbone_step run on a trainer per library.  HIP events around windows of --iters calls, medians over --rounds, spread_us = max - min
 over the rounds.  A group PASSES when a candidate's median is not above the yardstick's by more than the yardstick's own spread in
-this run.  Before timing, every replayed call's result is compared bit for bit with the yardstick's."""
+this run.  Before timing, every replayed call's result is compared bit for bit with the yardstick's.
+--tiny adds YOLOv3-tiny (fp32), trainable="full": one full_gradients walk is recorded and replayed the same way (tiny_wgrad and tiny_dgrad:
+the thin entries of layers 0 and 2 among them) and tiny_full_step runs on a trainer per library."""
 import argparse, json, os, statistics, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -24,6 +26,7 @@ ap.add_argument("--groups", default="", help="comma-separated subset of the grou
 ap.add_argument("--res", type=int, default=416); ap.add_argument("--batch", type=int, default=8)
 ap.add_argument("--iters", type=int, default=50); ap.add_argument("--rounds", type=int, default=7)
 ap.add_argument("--boxes", type=int, default=12, help="boxes per image")
+ap.add_argument("--tiny", action="store_true", help="also the full walk of YOLOv3-tiny")
 ap.add_argument("--log", default=os.path.join("profiles", "experiments", "grad_one_loop_ab.log"))
 args = ap.parse_args()
 assert torch.cuda.is_available(), "exp_grad_ab.py measures on the GPU"
@@ -43,13 +46,18 @@ targets = grad_walk.boxes(args.batch, args.res, args.boxes)
 cfg_text = cfgs.yolov3_cfg(args.res, args.res)
 ir = build_ir(parse_cfg_text(cfg_text), args.res)
 SCOPES = {"neck_step": ("neck", {"keep_head_inputs": 1, "keep_neck_activations": 1}), "backbone_step": ("backbone", {"keep_head_inputs": 1, "keep_backbone_activations": 1})}
+if args.tiny:
+    tiny_text = cfgs.yolov3_tiny_cfg(args.res, args.res)
+    SCOPES["tiny_full_step"] = ("full", {"keep_head_inputs": 1, "keep_full_activations": 1})
+RECORDED = ("backbone_step", "tiny_full_step")                        # the first library's trainers of these record the walks
 wanted = args.groups.split(",") if args.groups else None
 steps = {k: {} for k in SCOPES}
 for n in args.libs:
     use(n)
     for k, (scope, options) in SCOPES.items():
-        if wanted is None or k in wanted or (k == "backbone_step" and n == args.libs[0]):      # the first library's backbone trainer records the walk
-            t = grad_walk.trainer(cfg_text, ir, args.res, "f16s3", scope, options, 1e-9)   # the weights stay where they are over a run
+        if wanted is None or k in wanted or (k in RECORDED and n == args.libs[0]):
+            tiny = k == "tiny_full_step"                                                  # the weights stay where they are over a run
+            t = grad_walk.trainer(tiny_text if tiny else cfg_text, build_ir(parse_cfg_text(tiny_text), args.res) if tiny else ir, args.res, "fp32" if tiny else "f16s3", scope, options, 1e-9)
             steps[k][n] = (lambda t=t: t.feed_forward_through_model(x, targets))
             steps[k][n].trainer = t
             grad_walk.events(steps[k][n], 3)                                 # warm-up of every shape (autotune included)
@@ -59,13 +67,18 @@ dgrads, wgrads, stride_of, events = calls["dgrad"], calls["wgrad"], grad_walk.st
 d1 = [c for c in dgrads if stride_of(c) == 1]
 groups = {"dgrad_s1": d1, "dgrad3_s1": [c for c in d1 if int(c[1][2]) == 3], "dgrad_s2": [c for c in dgrads if stride_of(c) == 2],
           "wgrad": wgrads, "wgrad_s2": [c for c in wgrads if stride_of(c) == 2]}
+recorded = dgrads + wgrads
+if args.tiny:
+    tcalls, _ = grad_walk.record(steps["tiny_full_step"][args.libs[0]].trainer, x, targets, "full_gradients")
+    groups.update({"tiny_wgrad": tcalls["wgrad"], "tiny_dgrad": tcalls["dgrad"]})
+    recorded = recorded + tcalls["dgrad"] + tcalls["wgrad"]
 replay = lambda group: (lambda: [f(*a, **k) for f, a, k in group])
 
 # every library gives the yardstick's bits on every recorded call
 results = {}
 for n in args.libs:
     use(n)
-    results[n] = [f(*a, **k) for f, a, k in dgrads + wgrads]
+    results[n] = [f(*a, **k) for f, a, k in recorded]
     torch.cuda.synchronize()
 flat = lambda r: [t for v in r for t in (v if isinstance(v, tuple) else (v,)) if t is not None]
 differing = {n: sum(not torch.equal(p, q) for p, q in zip(flat(results[args.libs[0]]), flat(results[n]))) for n in args.libs[1:]}
@@ -87,7 +100,7 @@ for r in range(args.rounds):
             times[k][n].append(events(fns[k][n], args.iters))
     print("round %d of %d" % (r + 1, args.rounds), file=sys.stderr, flush=True)
 a = args.libs[0]
-res = {"net": "yolov3", "res": args.res, "batch": args.batch, "iters": args.iters, "rounds": args.rounds, "yardstick": a,
+res = {"net": "yolov3 + yolov3-tiny" if args.tiny else "yolov3", "res": args.res, "batch": args.batch, "iters": args.iters, "rounds": args.rounds, "yardstick": a,
        "calls": {k: len(g) for k, g in groups.items()}, "results_differing_in_bits": differing, "groups": {}}
 for k in fns:
     ma, sa = statistics.median(times[k][a]), max(times[k][a]) - min(times[k][a])

@@ -2,7 +2,7 @@
 // run on the CPU (no GPU, no Python):
 //   * f16_round.h: f32_to_f16_rn on the boundary inputs against the outputs of the host routine it replaced (the table below), and
 //     f16_to_f32 of all 65536 halves against that routine's ldexp form;
-//   * the slice rule of wgrad.hip (wgrad_slice_len, wgrad_tile_cap, wgrad_workspace_bytes) on the shapes of the GPU tests;
+//   * the slice rule of wgrad.hip (wgrad_schedule for its three rules, wgrad_check_shape, wgrad_workspace_bytes) on the shapes of the GPU tests;
 //   * Plan::pack_conv through rtod_plan_pack_weights: the cfg given as argv[1] (cfgs.mini_cfg(64, 64) written to a file) packed
 //     for the three precisions from a seeded weight stream.
 // Build (from realtimeobjectdetection_amd/csrc, after `make`; SAN = -Xarch_host -fsanitize=address,undefined):
@@ -61,15 +61,31 @@ int main(int argc, char** argv) {
                                     {1, 1, 32, 1, 1, 3}, {8, 1024, 512, 13, 13, 3}, {1, 64, 64, 16, 8, 3}};
     for (const auto& s : shapes) {
         const int64_t K = (int64_t)s[0] * s[3] * s[4];
-        for (int cap : {WGRAD_MAX_SLICES, wgrad_tile_cap(s[1], s[2], s[5])}) {
-            const int64_t L = wgrad_slice_len(K, cap), S = (K + L - 1) / L;
-            CHECK(cap >= 1 && cap <= WGRAD_MAX_SLICES && L % 8 == 0 && S >= 1 && S <= cap && S * L >= K, "slice rule: K %lld cap %d L %lld S %lld", (long long)K, cap, (long long)L, (long long)S);
-            CHECK(wgrad_workspace_bytes(s[0], s[1], s[2], s[3], s[4], s[5], cap) == 4u * (size_t)S * ((size_t)s[1] * s[2] * s[5] * s[5] + s[1]), "workspace bytes");
+        for (WgradRule rule : {WGRAD_HEAD, WGRAD_TILED}) {
+            const WgradSchedule sc = wgrad_schedule(rule, s[0], s[1], s[2], s[3], s[4], s[5], 1);
+            const int64_t L = sc.slice_len, S = sc.slices;
+            CHECK(sc.K == K && L % 8 == 0 && S >= 1 && S <= WGRAD_MAX_SLICES && S * L >= K && (S - 1) * L < K && sc.group == S && sc.tm == 64 && sc.tn == 64 && sc.db,
+                  "slice rule %d: K %lld L %lld S %lld", (int)rule, (long long)K, (long long)L, (long long)S);
+            CHECK(wgrad_workspace_bytes(sc, s[1], s[2], s[5]) == 4u * (size_t)S * ((size_t)s[1] * s[2] * s[5] * s[5] + s[1]), "workspace bytes");
+            CHECK(wgrad_check_shape("check", rule, s[0], s[1], s[2], s[3], s[4], s[5], 1) == RTOD_OK, "shape refused");
         }
-        CHECK(wgrad_check_shape("check", s[0], s[1], s[2], s[3], s[4], s[5]) == RTOD_OK, "shape refused");
     }
-    CHECK(wgrad_tile_cap(256, 928, 3) == 2 && wgrad_tile_cap(64, 64, 1) == 16 && wgrad_tile_cap(1024, 512, 3) == 1 && wgrad_tile_cap(0, 0, 3) == 16, "tile caps");
-    CHECK(wgrad_check_shape("check", 1, 1, 16, 1, 1, 1) == RTOD_E_ARG && wgrad_check_shape("check", 1, 1, 32, 1, 1, 2) == RTOD_E_ARG, "bad shapes accepted");
+    auto slices = [](WgradRule rule, int b, int cout, int cin, int h, int w, int size, int stride = 1) { return wgrad_schedule(rule, b, cout, cin, h, w, size, stride).slices; };
+    // the tile cap: 524 tiles -> 2, 1 tile -> 16, 1152 tiles -> 1; the head rule does not see the tiles; stride 2: K of the output map
+    CHECK(slices(WGRAD_TILED, 8, 256, 928, 13, 13, 3) == 2 && slices(WGRAD_TILED, 8, 64, 64, 13, 13, 1) == 16 && slices(WGRAD_TILED, 8, 1024, 512, 13, 13, 3) == 1 &&
+          slices(WGRAD_HEAD, 8, 1024, 512, 13, 13, 1) == 16, "tile caps");
+    CHECK(wgrad_schedule(WGRAD_TILED, 2, 64, 32, 13, 15, 3, 2).K == 2 * 7 * 8, "stride-2 K");
+    CHECK(wgrad_check_shape("check", WGRAD_TILED, 1, 1, 16, 1, 1, 1, 1) == RTOD_E_ARG && wgrad_check_shape("check", WGRAD_TILED, 1, 1, 32, 1, 1, 2, 1) == RTOD_E_ARG &&
+          wgrad_check_shape("check", WGRAD_TILED, 1, 1, 32, 4, 4, 1, 2) == RTOD_E_ARG && wgrad_check_shape("check", WGRAD_THIN, 1, 1, 0, 1, 1, 3, 1) == RTOD_E_ARG, "bad shapes accepted");
+    // the thin rule on (B, Cout, Cin, H, W, size) -> (S, L): tests/test_train_bits_gpu.py's THIN_TREE_SHAPES, and layer 0 of YOLOv3-tiny at 416 x 416 batch 8
+    static const int thin[][8] = {{1, 16, 3, 129, 130, 3, 66, 256}, {2, 40, 16, 96, 96, 3, 72, 256}, {1, 97, 16, 160, 240, 3, 127, 304}, {1, 1, 1, 1025, 1024, 1, 1025, 1024},
+                                  {8, 16, 3, 416, 416, 3, 1352, 1024}, {1, 1, 1, 1, 1, 3, 1, 256}};
+    for (const auto& s : thin) {
+        const WgradSchedule sc = wgrad_schedule(WGRAD_THIN, s[0], s[1], s[2], s[3], s[4], s[5], 1);
+        CHECK(wgrad_check_shape("check", WGRAD_THIN, s[0], s[1], s[2], s[3], s[4], s[5], 1) == RTOD_OK, "thin shape refused");
+        CHECK(sc.slices == s[6] && sc.slice_len == s[7] && sc.group == WGRAD_THIN_GROUP && sc.tm == 32 && sc.tn == 128 && !sc.db, "thin rule: S %d L %d", sc.slices, sc.slice_len);
+        CHECK(wgrad_workspace_bytes(sc, s[1], s[2], s[5]) == 4u * (size_t)s[6] * s[1] * s[2] * s[5] * s[5], "thin workspace bytes");
+    }
 
     // pack the cfg's weights on the host for every precision
     if (argc > 1) {
