@@ -1,13 +1,11 @@
-// Bandwidth-bound helper kernels of the Darknet forward (gfx950): input NCHW->NHWC pack, bilinear x2
-// upsample, stand-alone shortcut add, max-pool, channel copy, NHWC->NCHW read-back, stand-alone head
-// decode, confidence mask, IoU.  All are HBM-bound elementwise work: one float4 (16 B) per lane
-// along the channel axis wherever the layout allows, grid capped at ~2048 blocks + grid stride.
+// Bandwidth-bound helper kernels of the Darknet forward (gfx950): input NCHW->NHWC pack, bilinear and nearest x2 upsample, stand-alone
+// shortcut add, channel copy, max-pool, batch-statistics BatchNorm, NHWC->NCHW read-back, stand-alone head decode, confidence mask.
+// All are HBM-bound elementwise work: 16 bytes per lane along the channel axis wherever the layout allows, grid capped at
+// ~2048 blocks + grid stride.  Each op has ONE kernel body over the activation format (Act<F> below).
 #include "conv_f16s3_common.h"
 #include <algorithm>
 
 namespace rtod {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 static inline int grid_for(int64_t work, int block) {
     int64_t g = (work + block - 1) / block;
@@ -45,10 +43,121 @@ int launch_pack_input(const float* x, int B, int C, int H, int W, float* out, in
 }
 
 // ---------------------------------------------------------------------------------------------
+// One accessor per activation format, F = View::split: exact fp32, split f16 (a hi and a lo plane per pixel, values 8 x), plain f16
+// (the same layout, the lo plane never read or written).  A thread owns 16 bytes of a pixel along the channel axis: PER = 4 fp32
+// channels, or 8 halves of each plane.  Stored is what memory holds of them; values() what they mean as floats, in the format's own
+// domain (SPLIT_SCALE carries through every op below).  plain() and saturating() are the two ways back: a bare conversion (split:
+// hi = RNE(x), lo = RNE(x - hi); no range check), and the producers' split_f16 / f16_sat with the overflow sentinel.
+enum { FMT_F32 = 0, FMT_SPLIT = 1, FMT_F16 = 2 };
+
+__host__ __device__ __forceinline__ int64_t pixel_of(const View& v, int b, int y, int x) { return ((int64_t)b * v.H + y) * v.W + x; }
+__device__ __forceinline__ float* f32_at(const View& v, int64_t pix, int c) { return v.base + v.coff + c + pix * v.ldc; }
+// the hi plane of a split / plain-f16 pixel at channel c; the lo plane lies v.ldc halves behind it
+__device__ __forceinline__ _Float16* split_plane(const View& v, int64_t pix, int c) {
+    return reinterpret_cast<_Float16*>(v.base) + pix * 2 * v.ldc + v.coff + c;
+}
+// N = 4 or 8 consecutive floats, 16 bytes at a time
+template <int N> __device__ __forceinline__ void load_f32(const float* p, float (&x)[N]) {
+#pragma unroll
+    for (int i = 0; i < N; i += 4) {
+        const f32x4 v = *reinterpret_cast<const f32x4*>(p + i);
+        x[i] = v[0]; x[i + 1] = v[1]; x[i + 2] = v[2]; x[i + 3] = v[3];
+    }
+}
+
+template <int F> struct Act {                                   // FMT_SPLIT and FMT_F16
+    static_assert(F == FMT_SPLIT || F == FMT_F16, "activation format");
+    static constexpr int PER = 8;
+    static constexpr bool F16 = F == FMT_F16;
+    struct Stored { f16x8 h, l; };                              // (plain f16: l is a placeholder no store reads)
+    static __device__ __forceinline__ Stored load(const View& v, int64_t pix, int c) {
+        const _Float16* q = split_plane(v, pix, c);
+        Stored s;
+        s.h = *reinterpret_cast<const f16x8*>(q);
+        if constexpr (F16) s.l = s.h; else s.l = *reinterpret_cast<const f16x8*>(q + v.ldc);
+        return s;
+    }
+    static __device__ __forceinline__ void values(const Stored& s, float (&x)[PER]) {
+#pragma unroll
+        for (int e = 0; e < PER; ++e) x[e] = F16 ? (float)s.h[e] : (float)s.h[e] + (float)s.l[e];      // exact in fp32: 22 significant bits
+    }
+    static __device__ __forceinline__ Stored none() { return {f16x8{0, 0, 0, 0, 0, 0, 0, 0}, f16x8{0, 0, 0, 0, 0, 0, 0, 0}}; }
+    static __device__ __forceinline__ void copy_element(Stored& to, const Stored& from, int e) { to.h[e] = from.h[e]; if constexpr (!F16) to.l[e] = from.l[e]; }
+    static __device__ __forceinline__ Stored plain(const float (&x)[PER]) {
+        Stored s = none();
+#pragma unroll
+        for (int e = 0; e < PER; ++e) { const _Float16 h = (_Float16)x[e]; s.h[e] = h; s.l[e] = (_Float16)(x[e] - (float)h); }
+        return s;
+    }
+    static __device__ __forceinline__ Stored saturating(const float (&x)[PER], float& amax) {
+        Stored s = none();
+        epi_split8<F16>(x, s.h, s.l, amax);
+        return s;
+    }
+    // SC1: the write-through store of the conv epilogues (store_act16)
+    template <bool SC1 = false> static __device__ __forceinline__ void store(const View& v, int64_t pix, int c, const Stored& s) {
+        _Float16* q = split_plane(v, pix, c);
+        if constexpr (SC1) epi_store8<F16>(q, (int)v.ldc, s.h, s.l, false);
+        else {
+            *reinterpret_cast<f16x8*>(q) = s.h;
+            if constexpr (!F16) *reinterpret_cast<f16x8*>(q + v.ldc) = s.l;
+        }
+    }
+};
+
+template <> struct Act<FMT_F32> {
+    static constexpr int PER = 4;
+    struct Stored { f32x4 v; };
+    static __device__ __forceinline__ Stored load(const View& v, int64_t pix, int c) { return {*reinterpret_cast<const f32x4*>(f32_at(v, pix, c))}; }
+    static __device__ __forceinline__ void values(const Stored& s, float (&x)[PER]) {
+#pragma unroll
+        for (int e = 0; e < PER; ++e) x[e] = s.v[e];
+    }
+    static __device__ __forceinline__ Stored none() { return {f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY}}; }
+    static __device__ __forceinline__ void copy_element(Stored& to, const Stored& from, int e) { to.v[e] = from.v[e]; }
+    static __device__ __forceinline__ Stored plain(const float (&x)[PER]) { return {f32x4{x[0], x[1], x[2], x[3]}}; }
+    static __device__ __forceinline__ Stored saturating(const float (&x)[PER], float&) { return plain(x); }
+    template <bool SC1 = false> static __device__ __forceinline__ void store(const View& v, int64_t pix, int c, const Stored& s) {
+        *reinterpret_cast<f32x4*>(f32_at(v, pix, c)) = s.v;
+    }
+};
+
+// thread index t -> the pixel (b, y, x) of an H x W map (pix = (b * H + y) * W + x) and the first of its `per` channels
+struct Pos { int64_t pix; int b, y, x, c; };
+__device__ __forceinline__ Pos position(int64_t t, int CV, int per, int H, int W) {
+    Pos o;
+    o.c = (int)(t % CV) * per;
+    o.pix = t / CV;
+    int64_t p = o.pix;
+    o.x = (int)(p % W); p /= W;
+    o.y = (int)(p % H);
+    o.b = (int)(p / H);
+    return o;
+}
+
+// Host side: the one view check (16-byte pieces of format `format`, or of `per` channels), the threads of a launch over the pixels of
+// `v`, and the one dispatch on View::split: f(integral_constant<int, F>).
+static int per_thread(int format) { return format ? 8 : 4; }
+static bool view_ok(const View& v, int format, int per = 0) {
+    if (!per) per = per_thread(format);
+    return v.base && format >= FMT_F32 && format <= FMT_F16 && v.split == format && v.C % per == 0 && v.ldc % per == 0 && v.coff % per == 0;
+}
+static bool same_map(const View& a, const View& b) { return a.C == b.C && a.H == b.H && a.W == b.W; }
+static int64_t threads_over(const View& v, int B) { return (int64_t)B * v.H * v.W * (v.C / per_thread(v.split)); }
+template <typename Fn> static void by_format(int format, Fn f) {
+    if (format == FMT_F16) f(std::integral_constant<int, FMT_F16>{});
+    else if (format == FMT_SPLIT) f(std::integral_constant<int, FMT_SPLIT>{});
+    else f(std::integral_constant<int, FMT_F32>{});
+}
+#define RTOD_LAUNCH_BY_FORMAT(format, kernel, total, stream, ...) \
+    by_format(format, [&](auto f_) { hipLaunchKernelGGL((kernel<decltype(f_)::value>), dim3(grid_for(total, 256)), dim3(256), 0, stream, __VA_ARGS__); })
+
+// ---------------------------------------------------------------------------------------------
 // bilinear x2, align_corners=False (reference: nn.Upsample(scale_factor=2, mode="bilinear"),
 // src/darknet.py:587-593).  src = (dst+0.5)/2-0.5 clamped at 0; weights are
 // exactly {1,0} on the borders and {0.25,0.75} inside.  Evaluated as wy0*(wx0*a+wx1*b)+wy1*(wx0*c+wx1*d),
-// ATen's separable order.
+// ATen's separable order.  Interpolation is linear, so the split format runs directly on hi + lo and re-splits the result with the
+// plain conversion (no saturation, no report: the result lies between its inputs); plain f16 rounds once (RNE).
 __device__ __forceinline__ void up_coord(int o, int n, int& i0, int& i1, float& w1) {
     float src = ((float)o + 0.5f) * 0.5f - 0.5f;
     if (src < 0.f) src = 0.f;
@@ -57,185 +166,100 @@ __device__ __forceinline__ void up_coord(int o, int n, int& i0, int& i1, float& 
     w1 = src - (float)i0;
 }
 
+template <int F>
 __global__ void upsample2x_kernel(View in, View out, int B) {
-    const int C4 = in.C / 4;
-    const int64_t total = (int64_t)B * out.H * out.W * C4;
+    using A = Act<F>;
+    const int CV = in.C / A::PER;
+    const int64_t total = (int64_t)B * out.H * out.W * CV;
     for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
-        const int c = (int)(t % C4) * 4;
-        int64_t p = t / C4;
-        const int ox = (int)(p % out.W); p /= out.W;
-        const int oy = (int)(p % out.H);
-        const int b = (int)(p / out.H);
+        const Pos o = position(t, CV, A::PER, out.H, out.W);
         int y0, y1, x0, x1; float wy1, wx1;
-        up_coord(oy, in.H, y0, y1, wy1);
-        up_coord(ox, in.W, x0, x1, wx1);
+        up_coord(o.y, in.H, y0, y1, wy1);
+        up_coord(o.x, in.W, x0, x1, wx1);
         const float wy0 = 1.f - wy1, wx0 = 1.f - wx1;
-        const float* base = in.base + in.coff + c;
-        const int64_t rb = (int64_t)b * in.H;
-        const f32x4 v00 = *reinterpret_cast<const f32x4*>(base + ((rb + y0) * in.W + x0) * in.ldc);
-        const f32x4 v01 = *reinterpret_cast<const f32x4*>(base + ((rb + y0) * in.W + x1) * in.ldc);
-        const f32x4 v10 = *reinterpret_cast<const f32x4*>(base + ((rb + y1) * in.W + x0) * in.ldc);
-        const f32x4 v11 = *reinterpret_cast<const f32x4*>(base + ((rb + y1) * in.W + x1) * in.ldc);
-        f32x4 r;
+        float v00[A::PER], v01[A::PER], v10[A::PER], v11[A::PER], r[A::PER];
+        A::values(A::load(in, pixel_of(in, o.b, y0, x0), o.c), v00);
+        A::values(A::load(in, pixel_of(in, o.b, y0, x1), o.c), v01);
+        A::values(A::load(in, pixel_of(in, o.b, y1, x0), o.c), v10);
+        A::values(A::load(in, pixel_of(in, o.b, y1, x1), o.c), v11);
 #pragma unroll
-        for (int e = 0; e < 4; ++e)
+        for (int e = 0; e < A::PER; ++e)
             r[e] = wy0 * (wx0 * v00[e] + wx1 * v01[e]) + wy1 * (wx0 * v10[e] + wx1 * v11[e]);
-        *reinterpret_cast<f32x4*>(out.base + out.coff + c + (((int64_t)b * out.H + oy) * out.W + ox) * out.ldc) = r;
+        A::store(out, o.pix, o.c, A::plain(r));
     }
 }
-
-// split-format variant: 8 channels (16 B of each plane) per thread; interpolation is linear, so it runs
-// directly on hi+lo (the SPLIT_SCALE factor carries through) and the result is re-split.
-// F16 (plain-f16 plans, View::split == 2): hi planes only, the result rounded to f16 (RNE).
-typedef _Float16 f16x8a __attribute__((ext_vector_type(8)));
-template <bool F16>
-__global__ void upsample2x_split_kernel(View in, View out, int B) {
-    const int C8 = in.C / 8;
-    const int64_t total = (int64_t)B * out.H * out.W * C8;
-    const _Float16* ib = reinterpret_cast<const _Float16*>(in.base);
-    _Float16* ob = reinterpret_cast<_Float16*>(out.base);
-    for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
-        const int c = (int)(t % C8) * 8;
-        int64_t p = t / C8;
-        const int ox = (int)(p % out.W); p /= out.W;
-        const int oy = (int)(p % out.H);
-        const int b = (int)(p / out.H);
-        int y0, y1, x0, x1; float wy1, wx1;
-        up_coord(oy, in.H, y0, y1, wy1);
-        up_coord(ox, in.W, x0, x1, wx1);
-        const float wy0 = 1.f - wy1, wx0 = 1.f - wx1;
-        const int64_t rb = (int64_t)b * in.H;
-        auto ld = [&](int y, int x, float* v) {
-            const _Float16* q = ib + ((rb + y) * in.W + x) * 2 * in.ldc + in.coff + c;
-            const f16x8a h = *reinterpret_cast<const f16x8a*>(q);
-            if constexpr (F16) {
-#pragma unroll
-                for (int e = 0; e < 8; ++e) v[e] = (float)h[e];
-            } else {
-                const f16x8a l = *reinterpret_cast<const f16x8a*>(q + in.ldc);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) v[e] = (float)h[e] + (float)l[e];
-            }
-        };
-        float v00[8], v01[8], v10[8], v11[8];
-        ld(y0, x0, v00); ld(y0, x1, v01); ld(y1, x0, v10); ld(y1, x1, v11);
-        f16x8a rh, rl;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const float r = wy0 * (wx0 * v00[e] + wx1 * v01[e]) + wy1 * (wx0 * v10[e] + wx1 * v11[e]);
-            const _Float16 h = (_Float16)r;
-            rh[e] = h; rl[e] = (_Float16)(r - (float)h);
-        }
-        _Float16* q = ob + (((int64_t)b * out.H + oy) * out.W + ox) * 2 * out.ldc + out.coff + c;
-        *reinterpret_cast<f16x8a*>(q) = rh;
-        if constexpr (!F16) *reinterpret_cast<f16x8a*>(q + out.ldc) = rl;
-    }
-}
-
-static bool view_ok4(const View& v) { return v.base && v.C % 4 == 0 && v.ldc % 4 == 0 && v.coff % 4 == 0; }
 
 int launch_upsample2x(const View& in, const View& out, int B, hipStream_t s) {
-    if (in.split != out.split) { set_error("upsample2x: mixed formats"); return RTOD_E_ARG; }
-    if (in.split) {
-        if (!in.base || !out.base || in.C % 8 || in.ldc % 8 || in.coff % 8 || out.ldc % 8 || out.coff % 8 ||
-            out.H != 2 * in.H || out.W != 2 * in.W || out.C != in.C) { set_error("upsample2x(split): bad views"); return RTOD_E_ARG; }
-        const int64_t total = (int64_t)B * out.H * out.W * (in.C / 8);
-        if (in.split == 2) hipLaunchKernelGGL(upsample2x_split_kernel<true>, dim3(grid_for(total, 256)), dim3(256), 0, s, in, out, B);
-        else hipLaunchKernelGGL(upsample2x_split_kernel<false>, dim3(grid_for(total, 256)), dim3(256), 0, s, in, out, B);
-        return hip_fail(hipGetLastError(), "upsample2x(split) launch");
-    }
-    if (!view_ok4(in) || !view_ok4(out) || out.H != 2 * in.H || out.W != 2 * in.W || out.C != in.C) {
+    if (!view_ok(in, in.split) || !view_ok(out, in.split) || out.H != 2 * in.H || out.W != 2 * in.W || out.C != in.C) {
         set_error("upsample2x: bad views"); return RTOD_E_ARG;
     }
-    const int64_t total = (int64_t)B * out.H * out.W * (in.C / 4);
-    hipLaunchKernelGGL(upsample2x_kernel, dim3(grid_for(total, 256)), dim3(256), 0, s, in, out, B);
+    RTOD_LAUNCH_BY_FORMAT(in.split, upsample2x_kernel, threads_over(out, B), s, in, out, B);
     return hip_fail(hipGetLastError(), "upsample2x launch");
 }
 
-// ---------------------------------------------------------------------------------------------
-// stand-alone shortcut (src/darknet.py:263-268) for cfgs where the add cannot ride a conv epilogue
-__global__ void add_kernel(View a, View b, View out, int B) {
-    const int C4 = a.C / 4;
-    const int64_t total = (int64_t)B * a.H * a.W * C4;
+// nearest x2 (cfg extension `[upsample] mode=nearest`; nn.Upsample(scale_factor=2, mode="nearest")): out(y, x) = in(y/2, x/2).
+// A pure copy of the stored representation in every format.
+template <int F>
+__global__ void upsample_nearest2x_kernel(View in, View out, int B) {
+    using A = Act<F>;
+    const int CV = in.C / A::PER;
+    const int64_t total = (int64_t)B * out.H * out.W * CV;
     for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
-        const int c = (int)(t % C4) * 4;
-        const int64_t p = t / C4;
-        const f32x4 x = *reinterpret_cast<const f32x4*>(a.base + a.coff + c + p * a.ldc);
-        const f32x4 y = *reinterpret_cast<const f32x4*>(b.base + b.coff + c + p * b.ldc);
-        *reinterpret_cast<f32x4*>(out.base + out.coff + c + p * out.ldc) = x + y;
+        const Pos o = position(t, CV, A::PER, out.H, out.W);
+        A::store(out, o.pix, o.c, A::load(in, pixel_of(in, o.b, o.y >> 1, o.x >> 1), o.c));
     }
 }
 
-// split-format variant (plans with option keep_backbone_activations, which hold the shortcut out of the conv's epilogue): 8 channels
-// (16 B of each plane) per thread.  Both operands are read as hi + lo (exact in fp32), added with one fp32 add in the format's own
-// domain (8 x) and split again: the sum rounds once, at its store, and saturates and reports like every other split producer.
-// F16 (plain-f16 plans): the hi planes alone, the sum rounded to f16 (RNE).
-template <bool F16>
-__global__ void add_split_kernel(View a, View b, View out, int B, int32_t* ovf) {
-    const int C8 = a.C / 8;
-    const int64_t total = (int64_t)B * a.H * a.W * C8;
-    const _Float16* ab = reinterpret_cast<const _Float16*>(a.base);
-    const _Float16* bb = reinterpret_cast<const _Float16*>(b.base);
-    _Float16* ob = reinterpret_cast<_Float16*>(out.base);
+int launch_upsample_nearest2x(const View& in, const View& out, int B, hipStream_t s) {
+    if (!view_ok(in, in.split) || !view_ok(out, in.split) || in.C != out.C || out.H != 2 * in.H || out.W != 2 * in.W) { set_error("upsample_nearest: bad views"); return RTOD_E_ARG; }
+    RTOD_LAUNCH_BY_FORMAT(in.split, upsample_nearest2x_kernel, threads_over(out, B), s, in, out, B);
+    return hip_fail(hipGetLastError(), "upsample_nearest launch");
+}
+
+// ---------------------------------------------------------------------------------------------
+// stand-alone shortcut (src/darknet.py:263-268) for cfgs where the add cannot ride a conv epilogue, and for plans with option
+// keep_backbone_activations, which hold the shortcut out of the conv's epilogue.  One fp32 add of the operands' values.  Split
+// format: (ah + al) + (bh + bl) in the format's own domain, split again by split_f16 — the sum rounds once, at its store, and
+// saturates and reports like every other split producer.  Plain f16: ah + bh through f16_sat, no lo plane.
+template <int F>
+__global__ void add_kernel(View a, View b, View out, int B, int32_t* ovf) {
+    using A = Act<F>;
+    const int CV = a.C / A::PER;
     float amax = 0.f;
+    const int64_t total = (int64_t)B * a.H * a.W * CV;
     for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
-        const int c = (int)(t % C8) * 8;
-        const int64_t p = t / C8;
-        const _Float16* qa = ab + p * 2 * a.ldc + a.coff + c;
-        const _Float16* qb = bb + p * 2 * b.ldc + b.coff + c;
-        const f16x8a ah = *reinterpret_cast<const f16x8a*>(qa), bh = *reinterpret_cast<const f16x8a*>(qb);
-        f16x8a al = ah, bl = bh;
-        if constexpr (!F16) { al = *reinterpret_cast<const f16x8a*>(qa + a.ldc); bl = *reinterpret_cast<const f16x8a*>(qb + b.ldc); }
-        f16x8a rh, rl;
+        const Pos o = position(t, CV, A::PER, a.H, a.W);
+        float x[A::PER], y[A::PER], r[A::PER];
+        A::values(A::load(a, o.pix, o.c), x);
+        A::values(A::load(b, o.pix, o.c), y);
 #pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            if constexpr (F16) { rh[e] = f16_sat((float)ah[e] + (float)bh[e], amax); rl[e] = (_Float16)0.f; }
-            else { _Float16 h, l; split_f16(((float)ah[e] + (float)al[e]) + ((float)bh[e] + (float)bl[e]), h, l, amax); rh[e] = h; rl[e] = l; }
-        }
-        _Float16* q = ob + p * 2 * out.ldc + out.coff + c;
-        *reinterpret_cast<f16x8a*>(q) = rh;
-        if constexpr (!F16) *reinterpret_cast<f16x8a*>(q + out.ldc) = rl;
+        for (int e = 0; e < A::PER; ++e) r[e] = x[e] + y[e];
+        A::store(out, o.pix, o.c, A::saturating(r, amax));
     }
-    split_overflow_report(ovf, amax);
+    if constexpr (F != FMT_F32) split_overflow_report(ovf, amax);
 }
 
 int launch_add(const View& a, const View& b, const View& out, int B, hipStream_t s, int32_t* ovf) {
-    if (a.split || b.split || out.split) {
-        const auto ok8 = [](const View& v) { return v.base && v.C % 8 == 0 && v.ldc % 8 == 0 && v.coff % 8 == 0; };
-        if (a.split != b.split || a.split != out.split || !ok8(a) || !ok8(b) || !ok8(out) || a.C != b.C || a.C != out.C || a.H != b.H || a.W != b.W ||
-            a.H != out.H || a.W != out.W) { set_error("add(split): bad views"); return RTOD_E_ARG; }
-        const int64_t total = (int64_t)B * a.H * a.W * (a.C / 8);
-        if (a.split == 2) hipLaunchKernelGGL(add_split_kernel<true>, dim3(grid_for(total, 256)), dim3(256), 0, s, a, b, out, B, ovf);
-        else hipLaunchKernelGGL(add_split_kernel<false>, dim3(grid_for(total, 256)), dim3(256), 0, s, a, b, out, B, ovf);
-        return hip_fail(hipGetLastError(), "add(split) launch");
-    }
-    if (!view_ok4(a) || !view_ok4(b) || !view_ok4(out) || a.C != b.C || a.C != out.C || a.H != b.H || a.W != b.W) {
-        set_error("add: bad views"); return RTOD_E_ARG;
-    }
-    const int64_t total = (int64_t)B * a.H * a.W * (a.C / 4);
-    hipLaunchKernelGGL(add_kernel, dim3(grid_for(total, 256)), dim3(256), 0, s, a, b, out, B);
+    if (!view_ok(a, a.split) || !view_ok(b, a.split) || !view_ok(out, a.split) || !same_map(a, b) || !same_map(a, out)) { set_error("add: bad views"); return RTOD_E_ARG; }
+    RTOD_LAUNCH_BY_FORMAT(a.split, add_kernel, threads_over(a, B), s, a, b, out, B, ovf);
     return hip_fail(hipGetLastError(), "add launch");
 }
 
-// channel-slice copy (fallback when a route concat cannot be zero-copy)
+// channel-slice copy (fallback when a route concat cannot be zero-copy): exact-fp32 plans only
 __global__ void copy_kernel(View a, View out, int B) {
-    const int C4 = a.C / 4;
-    const int64_t total = (int64_t)B * a.H * a.W * C4;
+    using A = Act<FMT_F32>;
+    const int CV = a.C / A::PER;
+    const int64_t total = (int64_t)B * a.H * a.W * CV;
     for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
-        const int c = (int)(t % C4) * 4;
-        const int64_t p = t / C4;
-        *reinterpret_cast<f32x4*>(out.base + out.coff + c + p * out.ldc) =
-            *reinterpret_cast<const f32x4*>(a.base + a.coff + c + p * a.ldc);
+        const Pos o = position(t, CV, A::PER, a.H, a.W);
+        A::store(out, o.pix, o.c, A::load(a, o.pix, o.c));
     }
 }
 
 int launch_copy(const View& a, const View& out, int B, hipStream_t s) {
     if (a.split || out.split) { set_error("copy: split-format views unsupported (route concat must be zero-copy)"); return RTOD_E_ARG; }
-    if (!view_ok4(a) || !view_ok4(out) || a.C != out.C || a.H != out.H || a.W != out.W) {
-        set_error("copy: bad views"); return RTOD_E_ARG;
-    }
-    const int64_t total = (int64_t)B * a.H * a.W * (a.C / 4);
-    hipLaunchKernelGGL(copy_kernel, dim3(grid_for(total, 256)), dim3(256), 0, s, a, out, B);
+    if (!view_ok(a, FMT_F32) || !view_ok(out, FMT_F32) || !same_map(a, out)) { set_error("copy: bad views"); return RTOD_E_ARG; }
+    hipLaunchKernelGGL(copy_kernel, dim3(grid_for(threads_over(a, B), 256)), dim3(256), 0, s, a, out, B);
     return hip_fail(hipGetLastError(), "copy launch");
 }
 
@@ -244,70 +268,45 @@ int launch_copy(const View& a, const View& out, int B, hipStream_t s) {
 // (src/darknet.py:17-46): replicate-pad right/bottom by size-1 then size/1 pool == clamp the window.
 // pad > 0 (cfg extension `symmetric=1`, SPPF-style pools): the window starts pad pixels up / left and out-of-image taps
 // count as -inf (nn.MaxPool2d(size, stride, pad)).
-__global__ void maxpool_kernel(View in, View out, int B, int size, int stride, int pad) {
-    const int C4 = in.C / 4;
-    const int64_t total = (int64_t)B * out.H * out.W * C4;
-    for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
-        const int c = (int)(t % C4) * 4;
-        int64_t p = t / C4;
-        const int ox = (int)(p % out.W); p /= out.W;
-        const int oy = (int)(p % out.H);
-        const int b = (int)(p / out.H);
-        f32x4 m = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-        for (int dy = 0; dy < size; ++dy) {
-            int iy = oy * stride + dy - pad;
-            if (pad) { if ((unsigned)iy >= (unsigned)in.H) continue; } else if (iy > in.H - 1) iy = in.H - 1;
-            for (int dx = 0; dx < size; ++dx) {
-                int ix = ox * stride + dx - pad;
-                if (pad) { if ((unsigned)ix >= (unsigned)in.W) continue; } else if (ix > in.W - 1) ix = in.W - 1;
-                const f32x4 v = *reinterpret_cast<const f32x4*>(in.base + in.coff + c + (((int64_t)b * in.H + iy) * in.W + ix) * in.ldc);
+//
+// The winner rule, stated once (the stand-alone pool and the pool inside the BatchNorm normalise kernel): the values are compared
+// in fp32 (split: hi + lo; plain f16: hi), a candidate replaces the held element only when strictly greater, and the winner's
+// STORED representation is kept as it stands — the (hi, lo) pair of a split tensor is not split again, nothing rounds.
+template <int F> struct PoolMax {
+    using A = Act<F>;
+    float m[A::PER];
+    typename A::Stored held = A::none();
+    __device__ __forceinline__ PoolMax() {
 #pragma unroll
-                for (int e = 0; e < 4; ++e) m[e] = v[e] > m[e] ? v[e] : m[e];
-            }
-        }
-        *reinterpret_cast<f32x4*>(out.base + out.coff + c + (((int64_t)b * out.H + oy) * out.W + ox) * out.ldc) = m;
+        for (int e = 0; e < A::PER; ++e) m[e] = -INFINITY;
     }
-}
-
-// split-format variant: the maximum is taken over hi + lo (exact in fp32: 22 significant bits) and the winning element's
-// (hi, lo) pair is stored as it stands — no re-split, no rounding.  8 channels (16 B of each plane) per thread.
-// F16 (plain-f16 plans): the maximum over the hi plane alone, hi stored.
-template <bool F16>
-__global__ void maxpool_split_kernel(View in, View out, int B, int size, int stride, int pad) {
-    const int C8 = in.C / 8;
-    const int64_t total = (int64_t)B * out.H * out.W * C8;
-    const _Float16* ib = reinterpret_cast<const _Float16*>(in.base);
-    _Float16* ob = reinterpret_cast<_Float16*>(out.base);
-    for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
-        const int c = (int)(t % C8) * 8;
-        int64_t p = t / C8;
-        const int ox = (int)(p % out.W); p /= out.W;
-        const int oy = (int)(p % out.H);
-        const int b = (int)(p / out.H);
-        float m[8];
-        f16x8a mh, ml;
+    __device__ __forceinline__ void take(const typename A::Stored& s) {
+        float x[A::PER];
+        A::values(s, x);
 #pragma unroll
-        for (int e = 0; e < 8; ++e) { m[e] = -INFINITY; mh[e] = (_Float16)0.f; ml[e] = (_Float16)0.f; }
+        for (int e = 0; e < A::PER; ++e)
+            if (x[e] > m[e]) { m[e] = x[e]; A::copy_element(held, s, e); }
+    }
+};
+
+template <int F>
+__global__ void maxpool_kernel(View in, View out, int B, int size, int stride, int pad) {
+    using A = Act<F>;
+    const int CV = in.C / A::PER;
+    const int64_t total = (int64_t)B * out.H * out.W * CV;
+    for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
+        const Pos o = position(t, CV, A::PER, out.H, out.W);
+        PoolMax<F> best;
         for (int dy = 0; dy < size; ++dy) {
-            int iy = oy * stride + dy - pad;
+            int iy = o.y * stride + dy - pad;
             if (pad) { if ((unsigned)iy >= (unsigned)in.H) continue; } else if (iy > in.H - 1) iy = in.H - 1;
             for (int dx = 0; dx < size; ++dx) {
-                int ix = ox * stride + dx - pad;
+                int ix = o.x * stride + dx - pad;
                 if (pad) { if ((unsigned)ix >= (unsigned)in.W) continue; } else if (ix > in.W - 1) ix = in.W - 1;
-                const _Float16* q = ib + (((int64_t)b * in.H + iy) * in.W + ix) * 2 * in.ldc + in.coff + c;
-                const f16x8a h = *reinterpret_cast<const f16x8a*>(q);
-                f16x8a l = mh;
-                if constexpr (!F16) l = *reinterpret_cast<const f16x8a*>(q + in.ldc);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    const float v = F16 ? (float)h[e] : (float)h[e] + (float)l[e];
-                    if (v > m[e]) { m[e] = v; mh[e] = h[e]; ml[e] = l[e]; }
-                }
+                best.take(A::load(in, pixel_of(in, o.b, iy, ix), o.c));
             }
         }
-        _Float16* o = ob + (((int64_t)b * out.H + oy) * out.W + ox) * 2 * out.ldc + out.coff + c;
-        *reinterpret_cast<f16x8a*>(o) = mh;
-        if constexpr (!F16) *reinterpret_cast<f16x8a*>(o + out.ldc) = ml;
+        A::store(out, o.pix, o.c, best.held);
     }
 }
 
@@ -317,68 +316,56 @@ int launch_maxpool(const View& in, const View& out, int B, int size, int stride,
     const int eh = pad ? (in.H + 2 * pad - size) / stride + 1 : (stride != 1 ? (in.H - size) / stride + 1 : in.H);
     const int ew = pad ? (in.W + 2 * pad - size) / stride + 1 : (stride != 1 ? (in.W - size) / stride + 1 : in.W);
     if (out.H != eh || out.W != ew) { set_error("maxpool: output %dx%d, expected %dx%d", out.H, out.W, eh, ew); return RTOD_E_ARG; }
-    if (in.split) {
-        if (!in.base || !out.base || in.C % 8 || in.coff % 8 || out.coff % 8 || in.ldc % 8 || out.ldc % 8) { set_error("maxpool: bad split views"); return RTOD_E_ARG; }
-        const int64_t total = (int64_t)B * out.H * out.W * (in.C / 8);
-        if (in.split == 2) hipLaunchKernelGGL(maxpool_split_kernel<true>, dim3(grid_for(total, 256)), dim3(256), 0, s, in, out, B, size, stride, pad);
-        else hipLaunchKernelGGL(maxpool_split_kernel<false>, dim3(grid_for(total, 256)), dim3(256), 0, s, in, out, B, size, stride, pad);
-        return hip_fail(hipGetLastError(), "maxpool_split launch");
-    }
-    if (!view_ok4(in) || !view_ok4(out)) { set_error("maxpool: bad views"); return RTOD_E_ARG; }
-    const int64_t total = (int64_t)B * out.H * out.W * (in.C / 4);
-    hipLaunchKernelGGL(maxpool_kernel, dim3(grid_for(total, 256)), dim3(256), 0, s, in, out, B, size, stride, pad);
+    if (!view_ok(in, in.split) || !view_ok(out, in.split)) { set_error("maxpool: bad views"); return RTOD_E_ARG; }
+    RTOD_LAUNCH_BY_FORMAT(in.split, maxpool_kernel, threads_over(out, B), s, in, out, B, size, stride, pad);
     return hip_fail(hipGetLastError(), "maxpool launch");
 }
 
 // ---------------------------------------------------------------------------------------------
-// nearest x2 (cfg extension `[upsample] mode=nearest`; nn.Upsample(scale_factor=2, mode="nearest")): out(y, x) = in(y/2, x/2).
-// A pure copy in either activation format (split: both planes move unchanged; plain f16: the hi plane).
-__global__ void upsample_nearest2x_kernel(View in, View out, int B) {
-    const int per = in.split ? 8 : 4;                         // channels per thread: 16 bytes of a plane / of the fp32 pixel
-    const int CV = in.C / per;
-    const int64_t total = (int64_t)B * out.H * out.W * CV;
-    for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
-        const int c = (int)(t % CV) * per;
-        int64_t p = t / CV;
-        const int ox = (int)(p % out.W); p /= out.W;
-        const int oy = (int)(p % out.H);
-        const int b = (int)(p / out.H);
-        const int64_t ip = ((int64_t)b * in.H + (oy >> 1)) * in.W + (ox >> 1), op = ((int64_t)b * out.H + oy) * out.W + ox;
-        if (in.split) {
-            const _Float16* q = reinterpret_cast<const _Float16*>(in.base) + ip * 2 * in.ldc + in.coff + c;
-            _Float16* o = reinterpret_cast<_Float16*>(out.base) + op * 2 * out.ldc + out.coff + c;
-            *reinterpret_cast<f16x8a*>(o) = *reinterpret_cast<const f16x8a*>(q);
-            if (in.split == 1) *reinterpret_cast<f16x8a*>(o + out.ldc) = *reinterpret_cast<const f16x8a*>(q + in.ldc);
-        } else {
-            *reinterpret_cast<f32x4*>(out.base + out.coff + c + op * out.ldc) = *reinterpret_cast<const f32x4*>(in.base + in.coff + c + ip * in.ldc);
-        }
-    }
-}
-
-int launch_upsample_nearest2x(const View& in, const View& out, int B, hipStream_t s) {
-    if (!in.base || !out.base || in.split != out.split || in.C != out.C || out.H != 2 * in.H || out.W != 2 * in.W) { set_error("upsample_nearest: bad views"); return RTOD_E_ARG; }
-    const int per = in.split ? 8 : 4;
-    if (in.C % per || in.coff % per || out.coff % per || in.ldc % per || out.ldc % per) { set_error("upsample_nearest: channel alignment"); return RTOD_E_ARG; }
-    const int64_t total = (int64_t)B * out.H * out.W * (in.C / per);
-    hipLaunchKernelGGL(upsample_nearest2x_kernel, dim3(grid_for(total, 256)), dim3(256), 0, s, in, out, B);
-    return hip_fail(hipGetLastError(), "upsample_nearest launch");
-}
-
-// ---------------------------------------------------------------------------------------------
 // Batch-statistics BatchNorm ("as run" by the reference: detect.py never calls .eval(), so nn.BatchNorm2d normalises
-// with the statistics of the batch, src/darknet.py:493-495).  Optional parity mode of the exact-fp32 plans
-// (plan option bn_batch_stats): the conv writes its raw sums, bn_stats_kernel reduces per-channel mean and biased
-// variance over (B, H, W) in double precision (PyTorch's CPU kernels accumulate float statistics in double), then
-// bn_apply_kernel normalises, applies the activation and the fused shortcut in place.
-// stats layout: [sstride] mean, [sstride] biased variance (doubles).
+// with the statistics of the batch, src/darknet.py:493-495).  Parity mode of the exact-fp32 plans (plan option
+// bn_batch_stats) and of the split-f16 plans (bn_batch_split): the conv writes its raw sums as fp32 rows, the statistics kernels
+// reduce per-channel mean and biased variance over (B, H, W) in double precision (PyTorch's CPU kernels accumulate float
+// statistics in double) and leave the normalisation's per-channel constants, then bn_apply_kernel normalises, applies the
+// activation and the shortcut.
+// stats layout: [sstride] mean, [sstride] biased variance (doubles).  bn: [gstride] beta, [gstride] gamma (the order of the .weights
+// stream, src/darknet.py:356-376).  Constants: [sstride] w, [sstride] b (floats).
+
+// y = (x - mean) / sqrt(var + eps) * gamma + beta = x w + b: the ONE statement of w = gamma / sqrt(var + eps), b = beta - mean w'
+// (double precision, rounded to float once each), evaluated once per channel by whichever kernel finishes the statistics.
+// beta and gamma come by reference on purpose: the loads stay where the expressions use them, which keeps bn_stats_final_kernel's
+// two divisions by npix interleaved (by value they ran one after the other: +0.5 us per BatchNorm layer, measured).
+struct BnConstants { float w, b; };
+__device__ __forceinline__ BnConstants bn_channel_constants(double mean, double var, const float& beta, const float& gamma) {
+    const double invstd = 1.0 / sqrt(var + 1e-5);
+    return {(float)(invstd * (double)gamma), (float)((double)beta - mean * invstd * (double)gamma)};
+}
+// ... and of the normalise step of one value
+__device__ __forceinline__ float bn_normalise(float raw, float w, float b, int act) {
+    const float u = raw * w + b;
+    return apply_act(u, act);
+}
+// what a statistics kernel's finishing thread writes for channel c from the sums over npix pixels
+__device__ __forceinline__ void bn_finish_channel(int c, double sum, double sumsq, double npix, double* __restrict__ stats, int sstride,
+                                                  const float* __restrict__ bn, int gstride, float* __restrict__ wb) {
+    const double mean = sum / npix;
+    double var = sumsq / npix - mean * mean;
+    if (var < 0) var = 0;
+    stats[c] = mean;
+    stats[sstride + c] = var;
+    const BnConstants k = bn_channel_constants(mean, var, bn[c], bn[gstride + c]);
+    wb[c] = k.w;
+    wb[sstride + c] = k.b;
+}
+
+// One stage: one workgroup per group of 4 channels; threads stride over the pixels (deterministic: fixed partition, ordered tree)
 __global__ __launch_bounds__(256)
-void bn_stats_kernel(View x, int B, double* __restrict__ stats, int sstride) {
-    // one workgroup per group of 4 channels; threads stride over the pixels (deterministic: fixed partition, ordered tree)
+void bn_stats_kernel(View x, int B, double* __restrict__ stats, int sstride, const float* __restrict__ bn, int gstride, float* __restrict__ wb) {
     const int c = blockIdx.x * 4;
     const int64_t npix = (int64_t)B * x.H * x.W;
     double s[4] = {0, 0, 0, 0}, q[4] = {0, 0, 0, 0};
     for (int64_t p = threadIdx.x; p < npix; p += 256) {
-        const f32x4 v = *reinterpret_cast<const f32x4*>(x.base + x.coff + c + p * x.ldc);
+        const f32x4 v = *reinterpret_cast<const f32x4*>(f32_at(x, p, c));
 #pragma unroll
         for (int e = 0; e < 4; ++e) { s[e] += (double)v[e]; q[e] += (double)v[e] * (double)v[e]; }
     }
@@ -395,45 +382,16 @@ void bn_stats_kernel(View x, int B, double* __restrict__ stats, int sstride) {
     }
     if (threadIdx.x < 4 && c + (int)threadIdx.x < x.C) {
         const int e = threadIdx.x;
-        const double mean = red[0][e][0] / (double)npix;
-        double var = red[1][e][0] / (double)npix - mean * mean;
-        if (var < 0) var = 0;
-        stats[c + e] = mean;
-        stats[sstride + c + e] = var;
+        bn_finish_channel(c + e, red[0][e][0], red[1][e][0], (double)npix, stats, sstride, bn, gstride, wb);
     }
 }
 
-// y = (x - mean) / sqrt(var + eps) * gamma + beta, activation, + shortcut; x and y may be the same view.
-// bn: [gstride] beta, [gstride] gamma (the order of the .weights stream, src/darknet.py:356-376)
-__global__ void bn_apply_kernel(View x, View y, View res, int has_res, int B, const double* __restrict__ stats, int sstride,
-                                const float* __restrict__ bn, int gstride, int act) {
-    const int C4 = x.C / 4;
-    const int64_t total = (int64_t)B * x.H * x.W * C4;
-    for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
-        const int c = (int)(t % C4) * 4;
-        const int64_t p = t / C4;
-        const f32x4 v = *reinterpret_cast<const f32x4*>(x.base + x.coff + c + p * x.ldc);
-        f32x4 r = {0.f, 0.f, 0.f, 0.f};
-        if (has_res) r = *reinterpret_cast<const f32x4*>(res.base + res.coff + c + p * res.ldc);
-        f32x4 o;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const double invstd = 1.0 / sqrt(stats[sstride + c + e] + 1e-5);
-            const float w = (float)(invstd * (double)bn[gstride + c + e]);                      // gamma / sqrt(var + eps)
-            const float b = (float)((double)bn[c + e] - stats[c + e] * invstd * (double)bn[gstride + c + e]);
-            float u = v[e] * w + b;
-            u = apply_act(u, act);
-            o[e] = has_res ? u + r[e] : u;
-        }
-        *reinterpret_cast<f32x4*>(y.base + y.coff + c + p * y.ldc) = o;
-    }
-}
-
-// Two-stage statistics (round 4): bn_stats_kernel above reads 16 bytes per pixel row from C/4 workgroups (8 for the first layer) —
+// Two stages (round 4): bn_stats_kernel above reads 16 bytes per pixel row from C/4 workgroups (8 for the first layer) —
 // every line of the tensor fetched for one of its eight 16-byte pieces at a time.  Here the pixels are cut into `nparts` ranges, a
 // workgroup reads its range with consecutive threads on consecutive channels (whole lines), reduces its 256 / (C/4) pixel lanes
 // through LDS in a fixed tree and writes per-channel partial sums; bn_stats_final_kernel adds the parts in ascending order.
-// Fixed partition, fixed order: deterministic.  Needs 256 % (C/4) == 0 or (C/4) % 256 == 0; other channel counts keep the old kernel.
+// Fixed partition, fixed order: deterministic.  Needs 256 % (C/4) == 0 or (C/4) % 256 == 0; other channel counts keep the one stage
+// (the two orders of summation differ, so neither replaces the other).
 constexpr int BN_PARTS_MAX = 1024;
 __global__ __launch_bounds__(256)
 void bn_stats_partial_kernel(View x, int B, double* __restrict__ partial, int pstride, int nparts) {
@@ -448,7 +406,7 @@ void bn_stats_partial_kernel(View x, int B, double* __restrict__ partial, int ps
         const int cq = cb + (int)threadIdx.x % W, pl = (int)threadIdx.x / W;
         double s[4] = {0, 0, 0, 0}, q[4] = {0, 0, 0, 0};
         for (int64_t p = p0 + pl; p < p1; p += PL) {
-            const f32x4 v = *reinterpret_cast<const f32x4*>(x.base + x.coff + cq * 4 + p * x.ldc);
+            const f32x4 v = *reinterpret_cast<const f32x4*>(f32_at(x, p, cq * 4));
 #pragma unroll
             for (int e = 0; e < 4; ++e) { s[e] += (double)v[e]; q[e] += (double)v[e] * (double)v[e]; }
         }
@@ -489,215 +447,121 @@ void bn_stats_final_kernel(const double* __restrict__ partial, int pstride, int 
         __syncthreads();
     }
     if (k0 != 0 || c >= C) return;
-    s = red[0][threadIdx.x]; q = red[1][threadIdx.x];
-    const double mean = s / npix;
-    double var = q / npix - mean * mean;
-    if (var < 0) var = 0;
-    stats[c] = mean;
-    stats[sstride + c] = var;
-    // the normalisation's per-channel constants, once per channel instead of once per element (same expressions as bn_apply_kernel)
-    const double invstd = 1.0 / sqrt(var + 1e-5);
-    wb[c] = (float)(invstd * (double)bn[gstride + c]);
-    wb[sstride + c] = (float)((double)bn[c] - mean * invstd * (double)bn[gstride + c]);
-}
-
-// y = x * w + b, activation, + shortcut with the per-channel constants of bn_stats_final_kernel
-__global__ void bn_apply_wb_kernel(View x, View y, View res, int has_res, int B, const float* __restrict__ wb, int sstride, int act) {
-    const int C4 = x.C / 4;
-    const int64_t total = (int64_t)B * x.H * x.W * C4;
-    for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
-        const int c = (int)(t % C4) * 4;
-        const int64_t p = t / C4;
-        const f32x4 v = *reinterpret_cast<const f32x4*>(x.base + x.coff + c + p * x.ldc);
-        const f32x4 w = *reinterpret_cast<const f32x4*>(wb + c), b = *reinterpret_cast<const f32x4*>(wb + sstride + c);
-        f32x4 r = {0.f, 0.f, 0.f, 0.f};
-        if (has_res) r = *reinterpret_cast<const f32x4*>(res.base + res.coff + c + p * res.ldc);
-        f32x4 o;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            float u = v[e] * w[e] + b[e];
-            u = apply_act(u, act);
-            o[e] = has_res ? u + r[e] : u;
-        }
-        *reinterpret_cast<f32x4*>(y.base + y.coff + c + p * y.ldc) = o;
-    }
+    bn_finish_channel(c, red[0][threadIdx.x], red[1][threadIdx.x], npix, stats, sstride, bn, gstride, wb);
 }
 
 size_t bn_partial_doubles(int max_channels) { return (size_t)BN_PARTS_MAX * 2 * (size_t)max_channels + (size_t)max_channels; }   // partial sums + [2][C] float constants
 
-int launch_bn_batch(const View& x, const View& y, const View* res, int B, double* stats, int sstride, const float* bn, int gstride, int act,
-                    double* partial, int64_t partial_doubles, hipStream_t s) {
-    if (x.split || y.split || (res && res->split)) { set_error("bn_batch: exact-fp32 plans only"); return RTOD_E_ARG; }
-    if (!view_ok4(x) || !view_ok4(y) || x.C != y.C || x.H != y.H || x.W != y.W || !stats || !bn || gstride < x.C || sstride < x.C) { set_error("bn_batch: bad views"); return RTOD_E_ARG; }
-    if (res && (!view_ok4(*res) || res->C != x.C || res->H != x.H || res->W != x.W)) { set_error("bn_batch: bad shortcut view"); return RTOD_E_ARG; }
+// The one statistics path of both launchers: mean / variance of the raw fp32 view `x` into `stats` and the constants into the
+// `partial` scratch, whose device pointer comes back in `wb`.  Two stages where the channel count allows (and the scratch holds the
+// parts), else one; the constants lie behind the partial sums, or at the start of a scratch no partial sums use.
+static int bn_statistics(const View& x, int B, double* stats, int sstride, const float* bn, int gstride, double* partial, int64_t partial_doubles,
+                         hipStream_t s, const float*& wb) {
+    if (!partial || partial_doubles < sstride) { set_error("bn statistics: no scratch for the per-channel constants"); return RTOD_E_ARG; }
     const int C4 = x.C / 4;
     const int64_t npix = (int64_t)B * x.H * x.W;
-    int nparts = (int)std::min<int64_t>(BN_PARTS_MAX, std::max<int64_t>(1, npix / 128));
-    if (partial && (256 % C4 == 0 || C4 % 256 == 0) && (int64_t)nparts * 2 * sstride + sstride <= partial_doubles) {
+    const int nparts = (int)std::min<int64_t>(BN_PARTS_MAX, std::max<int64_t>(1, npix / 128));
+    if ((256 % C4 == 0 || C4 % 256 == 0) && (int64_t)nparts * 2 * sstride + sstride <= partial_doubles) {
+        float* w = reinterpret_cast<float*>(partial + (int64_t)nparts * 2 * sstride);
         hipLaunchKernelGGL(bn_stats_partial_kernel, dim3(nparts), dim3(256), 0, s, x, B, partial, sstride, nparts);
         if (hipGetLastError() != hipSuccess) return hip_fail(hipGetLastError(), "bn_stats_partial launch");
-        float* wb = reinterpret_cast<float*>(partial + (int64_t)nparts * 2 * sstride);
-        hipLaunchKernelGGL(bn_stats_final_kernel, dim3((x.C + 15) / 16), dim3(256), 0, s, partial, sstride, nparts, x.C, (double)npix, stats, sstride, bn, gstride, wb);
-        if (hipGetLastError() != hipSuccess) return hip_fail(hipGetLastError(), "bn_stats_final launch");
-        View r = res ? *res : x;
-        hipLaunchKernelGGL(bn_apply_wb_kernel, dim3(grid_for(npix * C4, 256)), dim3(256), 0, s, x, y, r, res ? 1 : 0, B, wb, sstride, act);
-        return hip_fail(hipGetLastError(), "bn_apply launch");
-    } else {
-        hipLaunchKernelGGL(bn_stats_kernel, dim3(x.C / 4), dim3(256), 0, s, x, B, stats, sstride);
-        if (hipGetLastError() != hipSuccess) return hip_fail(hipGetLastError(), "bn_stats launch");
+        hipLaunchKernelGGL(bn_stats_final_kernel, dim3((x.C + 15) / 16), dim3(256), 0, s, partial, sstride, nparts, x.C, (double)npix, stats, sstride, bn, gstride, w);
+        wb = w;
+        return hip_fail(hipGetLastError(), "bn_stats_final launch");
     }
-    const int64_t total = npix * C4;
-    View r = res ? *res : x;
-    hipLaunchKernelGGL(bn_apply_kernel, dim3(grid_for(total, 256)), dim3(256), 0, s, x, y, r, res ? 1 : 0, B, stats, sstride, bn, gstride, act);
-    return hip_fail(hipGetLastError(), "bn_apply launch");
+    float* w = reinterpret_cast<float*>(partial);
+    hipLaunchKernelGGL(bn_stats_kernel, dim3(C4), dim3(256), 0, s, x, B, stats, sstride, bn, gstride, w);
+    wb = w;
+    return hip_fail(hipGetLastError(), "bn_stats launch");
 }
 
-// Batch-statistics BatchNorm on a split-f16 plan (plan option bn_batch_split).  The conv's raw-sum instance (EPI_RAW) has written
-// the convolution sums as dense fp32 rows; the statistics kernels above read them through an fp32 view; this kernel normalises and
-// writes the split format.  One thread per 8 channels of a pixel: two 16-byte fp32 reads, one 16-byte read per plane of the shortcut
-// operand, one 16-byte store per plane.  y = act(raw * w_c + b_c) + (hi + lo) / 8 with w_c / b_c formed by the expressions of
-// bn_apply_kernel (WB: read from the constants bn_stats_final_kernel wrote, the same expressions); 8 y goes through split_f16.
-template <bool WB>
-__global__ void bn_apply_split_kernel(View x, View y, View res, int has_res, int B, const float* __restrict__ wb, const double* __restrict__ stats,
-                                      int sstride, const float* __restrict__ bn, int gstride, int act, int32_t* ovf) {
-    const int C8 = x.C / 8;
-    const int64_t total = (int64_t)B * x.H * x.W * C8;
-    const _Float16* rb = reinterpret_cast<const _Float16*>(res.base);
-    _Float16* yb = reinterpret_cast<_Float16*>(y.base);
+// y = act(x w + b) + shortcut from the raw fp32 view x and the constants, into format F (x and y may be the same fp32 view).  One
+// thread per Act<F>::PER channels of a pixel.  fp32: the shortcut operand is added as it is.  Split (the conv's raw-sum instance,
+// EPI_RAW, wrote x as dense rows): y = act(x w + b) + (hi + lo) / 8, and 8 y goes through split_f16 with the write-through stores
+// of the conv epilogues.
+template <int F>
+__global__ void bn_apply_kernel(View x, View y, View res, int has_res, int B, const float* __restrict__ wb, int sstride, int act, int32_t* ovf) {
+    using A = Act<F>;
+    const int CV = x.C / A::PER;
     float amax = 0.f;
+    const int64_t total = (int64_t)B * x.H * x.W * CV;
     for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
-        const int c = (int)(t % C8) * 8;
-        const int64_t p = t / C8;
-        const float* xp = x.base + x.coff + c + p * x.ldc;
-        const f32x4 v0 = *reinterpret_cast<const f32x4*>(xp), v1 = *reinterpret_cast<const f32x4*>(xp + 4);
-        float w[8], b[8];
-        if constexpr (WB) {
-            const f32x4 w0 = *reinterpret_cast<const f32x4*>(wb + c), w1 = *reinterpret_cast<const f32x4*>(wb + c + 4);
-            const f32x4 b0 = *reinterpret_cast<const f32x4*>(wb + sstride + c), b1 = *reinterpret_cast<const f32x4*>(wb + sstride + c + 4);
+        const Pos o = position(t, CV, A::PER, x.H, x.W);
+        float u[A::PER], w[A::PER], b[A::PER], r[A::PER];
+        load_f32(f32_at(x, o.pix, o.c), u);
+        load_f32(wb + o.c, w);
+        load_f32(wb + sstride + o.c, b);
 #pragma unroll
-            for (int e = 0; e < 8; ++e) { w[e] = e < 4 ? w0[e] : w1[e - 4]; b[e] = e < 4 ? b0[e] : b1[e - 4]; }
-        } else {
+        for (int e = 0; e < A::PER; ++e) r[e] = 0.f;
+        if (has_res) A::values(A::load(res, o.pix, o.c), r);
 #pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const double invstd = 1.0 / sqrt(stats[sstride + c + e] + 1e-5);
-                w[e] = (float)(invstd * (double)bn[gstride + c + e]);                                   // gamma / sqrt(var + eps)
-                b[e] = (float)((double)bn[c + e] - stats[c + e] * invstd * (double)bn[gstride + c + e]);
+        for (int e = 0; e < A::PER; ++e) {
+            u[e] = bn_normalise(u[e], w[e], b[e], act);
+            if constexpr (F == FMT_F32) u[e] = has_res ? u[e] + r[e] : u[e];
+            else {
+                if (has_res) u[e] += r[e] * (1.0f / SPLIT_SCALE);
+                u[e] = u[e] * SPLIT_SCALE;
             }
         }
-        f16x8 qh = {0, 0, 0, 0, 0, 0, 0, 0}, ql = {0, 0, 0, 0, 0, 0, 0, 0};
-        if (has_res) {
-            const _Float16* q = rb + p * 2 * res.ldc + res.coff + c;
-            qh = *reinterpret_cast<const f16x8*>(q);
-            ql = *reinterpret_cast<const f16x8*>(q + res.ldc);
-        }
-        f16x8 ph, pl;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            float u = (e < 4 ? v0[e] : v1[e - 4]) * w[e] + b[e];
-            u = apply_act(u, act);
-            if (has_res) u += ((float)qh[e] + (float)ql[e]) * (1.0f / SPLIT_SCALE);
-            _Float16 h, l;
-            split_f16(u * SPLIT_SCALE, h, l, amax);
-            ph[e] = h; pl[e] = l;
-        }
-        _Float16* o = yb + p * 2 * y.ldc + y.coff + c;
-        store_act16(o, ph, false);
-        store_act16(o + y.ldc, pl, false);
+        A::template store<true>(y, o.pix, o.c, A::saturating(u, amax));
     }
-    split_overflow_report(ovf, amax);
+    if constexpr (F != FMT_F32) split_overflow_report(ovf, amax);
 }
 
 // The same followed by the 2x2 / stride-2 max-pool that alone reads the conv (plan options bn_split_narrow + fuse_bn_pool): the
 // conv's full-resolution split map is never stored.  One thread per 8 channels of a POOLED pixel of `y` (the pool's view).  Every
-// window position, in (dy, dx) order, is normalised, activated and split exactly as bn_apply_split_kernel does it (amax over all
-// four: the range flag equals the stand-alone path's); the winner is chosen as maxpool_split_kernel chooses it — hi + lo compared in
-// fp32, a pair replaces the held one only when strictly greater — and its pair is stored as it stands.  Bit-identical to
-// bn_apply_split_kernel followed by maxpool_split_kernel.  x.H and x.W are even (y.H = x.H / 2, y.W = x.W / 2).
-template <bool WB>
-__global__ void bn_apply_split_pool_kernel(View x, View y, int B, const float* __restrict__ wb, const double* __restrict__ stats,
-                                           int sstride, const float* __restrict__ bn, int gstride, int act, int32_t* ovf) {
-    const int C8 = x.C / 8;
-    const int64_t total = (int64_t)B * y.H * y.W * C8;
-    _Float16* yb = reinterpret_cast<_Float16*>(y.base);
+// window position, in (dy, dx) order, is normalised, activated and split as bn_apply_kernel does it (amax over all four: the range
+// flag equals the stand-alone path's) and offered to the max-pool's own winner rule (PoolMax): bit-identical to bn_apply_kernel
+// followed by maxpool_kernel.  x.H and x.W are even (y.H = x.H / 2, y.W = x.W / 2).
+__global__ void bn_apply_split_pool_kernel(View x, View y, int B, const float* __restrict__ wb, int sstride, int act, int32_t* ovf) {
+    using A = Act<FMT_SPLIT>;
+    const int CV = x.C / A::PER;
     float amax = 0.f;
+    const int64_t total = (int64_t)B * y.H * y.W * CV;
     for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
-        const int c = (int)(t % C8) * 8;
-        int64_t p = t / C8;
-        const int ox = (int)(p % y.W); p /= y.W;
-        const int oy = (int)(p % y.H);
-        const int b = (int)(p / y.H);
-        float w[8], bb[8];
-        if constexpr (WB) {
-            const f32x4 w0 = *reinterpret_cast<const f32x4*>(wb + c), w1 = *reinterpret_cast<const f32x4*>(wb + c + 4);
-            const f32x4 b0 = *reinterpret_cast<const f32x4*>(wb + sstride + c), b1 = *reinterpret_cast<const f32x4*>(wb + sstride + c + 4);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) { w[e] = e < 4 ? w0[e] : w1[e - 4]; bb[e] = e < 4 ? b0[e] : b1[e - 4]; }
-        } else {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const double invstd = 1.0 / sqrt(stats[sstride + c + e] + 1e-5);
-                w[e] = (float)(invstd * (double)bn[gstride + c + e]);                                   // gamma / sqrt(var + eps)
-                bb[e] = (float)((double)bn[c + e] - stats[c + e] * invstd * (double)bn[gstride + c + e]);
-            }
-        }
+        const Pos o = position(t, CV, A::PER, y.H, y.W);
+        float w[A::PER], b[A::PER], v[4][A::PER];
+        load_f32(wb + o.c, w);
+        load_f32(wb + sstride + o.c, b);
         // the four window rows first: eight 16-byte loads in flight
-        f32x4 v0[4], v1[4];
+#pragma unroll
+        for (int pos = 0; pos < 4; ++pos) load_f32(f32_at(x, pixel_of(x, o.b, 2 * o.y + (pos >> 1), 2 * o.x + (pos & 1)), o.c), v[pos]);
+        PoolMax<FMT_SPLIT> best;
 #pragma unroll
         for (int pos = 0; pos < 4; ++pos) {
-            const float* xp = x.base + x.coff + c + (((int64_t)b * x.H + 2 * oy + (pos >> 1)) * x.W + 2 * ox + (pos & 1)) * x.ldc;
-            v0[pos] = *reinterpret_cast<const f32x4*>(xp); v1[pos] = *reinterpret_cast<const f32x4*>(xp + 4);
+            float u[A::PER];
+#pragma unroll
+            for (int e = 0; e < A::PER; ++e) u[e] = bn_normalise(v[pos][e], w[e], b[e], act) * SPLIT_SCALE;
+            best.take(A::saturating(u, amax));
         }
-        float m[8];
-        f16x8 mh, ml;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) { m[e] = -INFINITY; mh[e] = (_Float16)0.f; ml[e] = (_Float16)0.f; }
-#pragma unroll
-        for (int pos = 0; pos < 4; ++pos)
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                float u = (e < 4 ? v0[pos][e] : v1[pos][e - 4]) * w[e] + bb[e];
-                u = apply_act(u, act);
-                _Float16 h, l;
-                split_f16(u * SPLIT_SCALE, h, l, amax);
-                const float s = (float)h + (float)l;
-                if (s > m[e]) { m[e] = s; mh[e] = h; ml[e] = l; }
-            }
-        _Float16* o = yb + (((int64_t)b * y.H + oy) * y.W + ox) * 2 * y.ldc + y.coff + c;
-        store_act16(o, mh, false);
-        store_act16(o + y.ldc, ml, false);
+        A::store<true>(y, o.pix, o.c, best.held);
     }
     split_overflow_report(ovf, amax);
 }
 
-static bool view_ok8_split(const View& v) { return v.base && v.split == 1 && v.C % 8 == 0 && v.ldc % 8 == 0 && v.coff % 8 == 0; }
+int launch_bn_batch(const View& x, const View& y, const View* res, int B, double* stats, int sstride, const float* bn, int gstride, int act,
+                    double* partial, int64_t partial_doubles, hipStream_t s) {
+    if (x.split || y.split || (res && res->split)) { set_error("bn_batch: exact-fp32 plans only"); return RTOD_E_ARG; }
+    if (!view_ok(x, FMT_F32) || !view_ok(y, FMT_F32) || !same_map(x, y) || !stats || !bn || gstride < x.C || sstride < x.C) { set_error("bn_batch: bad views"); return RTOD_E_ARG; }
+    if (res && (!view_ok(*res, FMT_F32) || !same_map(*res, x))) { set_error("bn_batch: bad shortcut view"); return RTOD_E_ARG; }
+    const float* wb = nullptr;
+    if (int rc = bn_statistics(x, B, stats, sstride, bn, gstride, partial, partial_doubles, s, wb)) return rc;
+    hipLaunchKernelGGL(bn_apply_kernel<FMT_F32>, dim3(grid_for(threads_over(x, B), 256)), dim3(256), 0, s, x, y, res ? *res : x, res ? 1 : 0, B, wb, sstride, act, (int32_t*)nullptr);
+    return hip_fail(hipGetLastError(), "bn_apply launch");
+}
 
 int launch_bn_batch_split(const View& raw, const View& y, const View* res, int B, double* stats, int sstride, const float* bn, int gstride, int act,
                           double* partial, int64_t partial_doubles, int32_t* ovf, hipStream_t s, int pool) {
-    if (raw.split || !raw.base || raw.C % 8 || raw.ldc % 8 || raw.coff % 8) { set_error("bn_batch_split: bad raw-sum view"); return RTOD_E_ARG; }
+    if (!view_ok(raw, FMT_F32, 8)) { set_error("bn_batch_split: bad raw-sum view"); return RTOD_E_ARG; }
     if (pool && (res || raw.H % 2 || raw.W % 2)) { set_error("bn_batch_split: the fused 2x2 max-pool needs an even map and no shortcut"); return RTOD_E_ARG; }
     const int yh = pool ? raw.H / 2 : raw.H, yw = pool ? raw.W / 2 : raw.W;
-    if (!view_ok8_split(y) || raw.C != y.C || yh != y.H || yw != y.W || !stats || !bn || gstride < raw.C || sstride < raw.C || B < 1) { set_error("bn_batch_split: bad views"); return RTOD_E_ARG; }
-    if (res && (!view_ok8_split(*res) || res->C != raw.C || res->H != raw.H || res->W != raw.W)) { set_error("bn_batch_split: bad shortcut view"); return RTOD_E_ARG; }
-    const int C4 = raw.C / 4;
-    const int64_t npix = (int64_t)B * raw.H * raw.W;
-    const int64_t total = (int64_t)B * yh * yw * (raw.C / 8);      // threads of the normalise kernel: 8 channels of a written pixel
-    const View r = res ? *res : y;
-    const int nparts = (int)std::min<int64_t>(BN_PARTS_MAX, std::max<int64_t>(1, npix / 128));
-    // the statistics path of launch_bn_batch: two stages where the channel count allows, else one workgroup per 4 channels
-    if (partial && (256 % C4 == 0 || C4 % 256 == 0) && (int64_t)nparts * 2 * sstride + sstride <= partial_doubles) {
-        hipLaunchKernelGGL(bn_stats_partial_kernel, dim3(nparts), dim3(256), 0, s, raw, B, partial, sstride, nparts);
-        if (hipGetLastError() != hipSuccess) return hip_fail(hipGetLastError(), "bn_stats_partial launch");
-        float* wb = reinterpret_cast<float*>(partial + (int64_t)nparts * 2 * sstride);
-        hipLaunchKernelGGL(bn_stats_final_kernel, dim3((raw.C + 15) / 16), dim3(256), 0, s, partial, sstride, nparts, raw.C, (double)npix, stats, sstride, bn, gstride, wb);
-        if (hipGetLastError() != hipSuccess) return hip_fail(hipGetLastError(), "bn_stats_final launch");
-        if (pool) hipLaunchKernelGGL(bn_apply_split_pool_kernel<true>, dim3(grid_for(total, 256)), dim3(256), 0, s, raw, y, B, wb, stats, sstride, bn, gstride, act, ovf);
-        else hipLaunchKernelGGL(bn_apply_split_kernel<true>, dim3(grid_for(total, 256)), dim3(256), 0, s, raw, y, r, res ? 1 : 0, B, wb, stats, sstride, bn, gstride, act, ovf);
-        return hip_fail(hipGetLastError(), "bn_apply_split launch");
-    }
-    hipLaunchKernelGGL(bn_stats_kernel, dim3(raw.C / 4), dim3(256), 0, s, raw, B, stats, sstride);
-    if (hipGetLastError() != hipSuccess) return hip_fail(hipGetLastError(), "bn_stats launch");
-    if (pool) hipLaunchKernelGGL(bn_apply_split_pool_kernel<false>, dim3(grid_for(total, 256)), dim3(256), 0, s, raw, y, B, (const float*)nullptr, stats, sstride, bn, gstride, act, ovf);
-    else hipLaunchKernelGGL(bn_apply_split_kernel<false>, dim3(grid_for(total, 256)), dim3(256), 0, s, raw, y, r, res ? 1 : 0, B, (const float*)nullptr, stats, sstride, bn, gstride, act, ovf);
+    if (!view_ok(y, FMT_SPLIT) || raw.C != y.C || yh != y.H || yw != y.W || !stats || !bn || gstride < raw.C || sstride < raw.C || B < 1) { set_error("bn_batch_split: bad views"); return RTOD_E_ARG; }
+    if (res && (!view_ok(*res, FMT_SPLIT) || !same_map(*res, raw))) { set_error("bn_batch_split: bad shortcut view"); return RTOD_E_ARG; }
+    const float* wb = nullptr;
+    if (int rc = bn_statistics(raw, B, stats, sstride, bn, gstride, partial, partial_doubles, s, wb)) return rc;
+    const dim3 grid(grid_for(threads_over(y, B), 256));           // 8 channels of a written pixel per thread
+    if (pool) hipLaunchKernelGGL(bn_apply_split_pool_kernel, grid, dim3(256), 0, s, raw, y, B, wb, sstride, act, ovf);
+    else hipLaunchKernelGGL(bn_apply_kernel<FMT_SPLIT>, grid, dim3(256), 0, s, raw, y, res ? *res : y, res ? 1 : 0, B, wb, sstride, act, ovf);
     return hip_fail(hipGetLastError(), "bn_apply_split launch");
 }
 
@@ -741,9 +605,9 @@ __global__ void view_to_nchw_kernel(View in, int B, float* __restrict__ out) {
         const int y = (int)(p % in.H); p /= in.H;
         const int c = (int)(p % in.C);
         const int b = (int)(p / in.C);
-        const int64_t pix = ((int64_t)b * in.H + y) * in.W + x;
+        const int64_t pix = pixel_of(in, b, y, x);
         if (in.split) {
-            const _Float16* q = reinterpret_cast<const _Float16*>(in.base) + pix * 2 * in.ldc + in.coff + c;
+            const _Float16* q = split_plane(in, pix, c);
             out[t] = (in.split == 2 ? (float)q[0] : (float)q[0] + (float)q[in.ldc]) * (1.0f / SPLIT_SCALE);     // 2: plain f16, hi plane only
         } else {
             out[t] = in.base[pix * in.ldc + in.coff + c];

@@ -8,8 +8,6 @@
 
 namespace rtod {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int HBK = 32;                  // K elements per LDS stage (64 bytes per panel row)

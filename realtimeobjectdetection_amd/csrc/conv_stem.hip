@@ -12,7 +12,6 @@
 
 namespace rtod {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef _Float16 f16x8s __attribute__((ext_vector_type(8)));
 

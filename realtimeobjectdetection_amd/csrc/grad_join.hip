@@ -9,8 +9,6 @@
 
 namespace rtod {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 struct GradJoin { const float* c[4]; };
 
 template <int COUNT>

@@ -1,11 +1,9 @@
 // bbox_iou in the reference's operation order, shared by nms.hip (write_results, rtod_bbox_iou) and match.hip (the validator).
 // Both files are compiled with -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt: one rounding per operation.
 #pragma once
-#include <hip/hip_runtime.h>
+#include "rtod_internal.h"
 
 namespace rtod {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ float iou_ref(const f32x4 a, const f32x4 b) {
     // bbox_iou, src/util.py:138-151 — same operation order, fp32, one rounding per op

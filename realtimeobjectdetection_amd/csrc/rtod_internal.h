@@ -126,6 +126,9 @@ constexpr float ACT_SCALE_F16S3 = SPLIT_SCALE;
 constexpr float F16_MAX = 65504.0f;
 
 #ifdef __HIPCC__
+// the 16-byte vectors every kernel moves: 4 floats of an fp32 pixel, 8 halves of one plane of a split-f16 pixel
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 // v (already x SPLIT_SCALE) -> hi + lo.  Saturates at the f16 range instead of producing inf (inf + -inf = NaN in the
 // next layer); `amax` tracks max|v| for the overflow sentinel (split_overflow_report).
 __device__ __forceinline__ void split_f16(float v, _Float16& h, _Float16& l, float& amax) {
@@ -308,27 +311,35 @@ int launch_conv_stem16_raw(const float* x_nchw, const _Float16* wh, const _Float
 int launch_prep_image(const unsigned char* img, int h, int w, int bgr, int inp_dim, float* out, hipStream_t s);
 int launch_prep_frames(const unsigned char* frames, int batch, int h, int w, int bgr, int out_h, int out_w, float* out, hipStream_t s);
 int launch_pack_input(const float* x_nchw, int B, int C, int H, int W, float* out_nhwc, int Cp, hipStream_t s);
-int launch_upsample2x(const View& in, const View& out, int B, hipStream_t s);
-int launch_add(const View& a, const View& b, const View& out, int B, hipStream_t s, int32_t* ovf = nullptr);   // ovf: split-format views' overflow word
-int launch_maxpool(const View& in, const View& out, int B, int size, int stride, int pad, hipStream_t s);   // pad > 0: symmetric -inf padding
+// The elementwise helpers (aux_kernels.hip): one kernel template per op over the activation format.  All views of a call share one
+// View::split (0 fp32, 1 split f16, 2 plain f16; launch_copy: fp32 only) and pass the file's one view check: base set, C / ldc / coff
+// multiples of the 16-byte piece (4 fp32 channels, 8 halves of a plane).
+int launch_upsample2x(const View& in, const View& out, int B, hipStream_t s);                              // bilinear; split: re-split without a range check
+int launch_add(const View& a, const View& b, const View& out, int B, hipStream_t s, int32_t* ovf = nullptr);   // ovf: split / plain-f16 views' overflow word (the sum saturates and reports)
+int launch_maxpool(const View& in, const View& out, int B, int size, int stride, int pad, hipStream_t s);   // pad > 0: symmetric -inf padding; the winner's stored bits move unchanged
 int launch_upsample_nearest2x(const View& in, const View& out, int B, hipStream_t s);
-// batch-statistics BatchNorm (+ activation + shortcut) over a conv's raw output, in place (aux_kernels.hip); stats: 2*C doubles of scratch
+// batch-statistics BatchNorm (+ activation + shortcut) over a conv's raw output, in place (aux_kernels.hip); stats: 2*C doubles of scratch.
+// Both launchers run the one statistics path (two stages where 256 % (C/4) == 0 or (C/4) % 256 == 0, else one), which also writes the
+// per-channel constants w = gamma / sqrt(var + eps), b = beta - mean w as [2][sstride] floats into `partial`, and then one normalise
+// kernel that reads those constants.  partial: the plan's scratch of bn_partial_doubles(max channels) doubles (partial sums + constants);
+// REQUIRED — null, or fewer than sstride doubles, is an argument error.
 int launch_bn_batch(const View& x, const View& y, const View* res, int B, double* stats, int sstride, const float* bn, int gstride, int act,
-                    double* partial, int64_t partial_doubles, hipStream_t s);    // partial: scratch of the two-stage statistics (bn_partial_doubles), or null
+                    double* partial, int64_t partial_doubles, hipStream_t s);
 size_t bn_partial_doubles(int max_channels);
-// the same on a split-f16 plan (plan option bn_batch_split): `raw` is the fp32 view of the conv's raw sums (dense scratch rows), the
-// statistics kernels above read it, bn_apply_split_kernel normalises, applies the activation, adds the shortcut operand of its split
+// the same on a split-f16 plan (plan option bn_batch_split): `raw` is the fp32 view of the conv's raw sums (dense scratch rows, C / ldc /
+// coff multiples of 8); bn_apply_kernel's split instance normalises, applies the activation, adds the shortcut operand of its split
 // view and stores the split format into `y` (ldc / coff honoured: concat slices)
 int launch_bn_batch_split(const View& raw, const View& y, const View* res, int B, double* stats, int sstride, const float* bn, int gstride, int act,
                           double* partial, int64_t partial_doubles, int32_t* ovf, hipStream_t s, int pool = 0);
 // pool == 1 (plan options bn_split_narrow + fuse_bn_pool): `y` is the view of the 2x2 / stride-2 max-pool that alone reads the conv
-// (raw.H / 2 x raw.W / 2, both even, no shortcut); bn_apply_split_pool_kernel normalises and pools, bit-identical to pool == 0 + launch_maxpool
+// (raw.H / 2 x raw.W / 2, both even, no shortcut); bn_apply_split_pool_kernel normalises and pools with the max-pool's own winner rule,
+// bit-identical to pool == 0 + launch_maxpool
 // running_mean / running_var update of every BatchNorm layer of a batch-statistics plan in one launch (aux_kernels.hip)
 struct BnUpdateEntry { float* running_mean; float* running_var; int64_t stats_off; double unbias; int sstride; int channels; };
 constexpr int BN_UPDATE_MAX = 32;                 // entries per launch (by-value kernel argument: 32 x 40 bytes)
 struct BnUpdateTable { BnUpdateEntry e[BN_UPDATE_MAX]; };
 int launch_bn_update_running(const BnUpdateEntry* entries, int n, const double* stats, double momentum, hipStream_t s);
-int launch_copy(const View& in, const View& out, int B, hipStream_t s);
+int launch_copy(const View& in, const View& out, int B, hipStream_t s);                                     // fp32 views only
 int launch_view_to_nchw(const View& in, int B, float* out_nchw, hipStream_t s);
 // strided decode: raw element (b, ch, y, x) at raw[b*sb + ch*sc + y*sy + x*sx]
 int launch_finish_decode(float* out, int B, const DecodeArgs& d, int hw_exp, hipStream_t s);

@@ -43,7 +43,6 @@
 
 namespace rtod {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int WG_BK = 32;               // k per LDS stage
