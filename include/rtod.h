@@ -209,6 +209,16 @@ int rtod_plan_set_precision(rtod_plan* plan, int mode);
  *                       that of a plan with "fuse_shortcut" = 0, "fuse_pointwise" = 0, "stem2_kernel" = 0.  Default plans do not change
  *   "keep_full_activations" (default 0) a superset of "keep_backbone_activations" over the FULL graph (rtod_plan_full_layers): thin
  *                       convs (any Cin, layer 0 on a generic layout) and size-2 max-pools too.  Holds the same fusions
+ *   "keep_bn_inputs"    (default 0) training under batch statistics: on a "bn_batch_stats" plan (inert without it) every BatchNorm conv
+ *                       the plan trains — a detection block, and every BatchNorm conv of the graph the keep option above names — writes
+ *                       its raw sums z into an arena buffer of its own (dense rows of Cout floats, never reused during the forward); the
+ *                       normalise step reads it and writes the layer's view, so the forward's values are those of the in-place path bit
+ *                       for bit.  rtod_plan_head_blocks, _neck_layers, _trainable_layers and _full_layers then list what the eval plan
+ *                       with the same keep option lists (without it a batch-statistics plan lists nothing), rtod_plan_read_bn_input
+ *                       returns z, and rtod_plan_step_conv_bn / rtod_plan_update_conv_bn train conv weight, gamma and beta; the
+ *                       folded-conv entries keep refusing the plan.  A conv with a shortcut added in its normalise step is no member
+ *                       (its stored output is not act(u)); SiLU, split-f16 ("bn_batch_split") and rectangular plans are out of scope.
+ *                       Exact-fp32 plans only: RTOD_E_CFG on precision 1 or 2, in either order of the two calls
  *   "force_f16s3_variant" / "force_f32_variant"   >= 0: one tile variant for every conv (tests, A/B runs)
  * Options that leave a cfg inexpressible in the split-f16 format return RTOD_E_CFG when precision is 1 or 2 (so does setting
  * "narrow_cin" back to 0 on a plan that needs it); the plan then stays as it was. */
@@ -637,6 +647,30 @@ int rtod_conv_dgrad_thin(const float* w_oihw_dev, const double* row_scale_dev, c
  * (0, 2, 4, 6, 8, 10, 12, 13, 14, 18, 21); YOLOv3 the trainable list (its layer 0 runs the stem kernel; with "stem_kernel" = 0 all 72).
  * conv_layers / input_layers (-1 for layer 0: the network input) / capacity and the return value as rtod_plan_neck_layers. */
 int rtod_plan_full_layers(const rtod_plan* plan, int* conv_layers, int* input_layers, int capacity);
+/* (new) Backward of batch-statistics BatchNorm (nn.BatchNorm2d in .train(), what the reference's trainer runs: train.py:57, 77) over
+ * dense NCHW float32 maps.  du_dev [batch,channels,pixels]: the gradient with respect to the BatchNorm OUTPUT (the leaky mask already
+ * applied); z_dev, same shape: the raw conv output the forward normalised; mean_dev / var_dev (double [channels]): the statistics
+ * the forward normalised with (biased variance; rtod_plan_bn_batch_stats reads the same values); gamma_dev (float [channels]).  Per
+ * channel, N = batch * pixels, r = 1 / sqrt(var + 1e-5) in double (the forward's expression, one header for both):
+ *   S1 = sum (double)du                      S2 = sum (double)du * ((double)z - mean)
+ *   dbeta_dev[c]  = (float)S1                dgamma_dev[c] = (float)(S2 * r)
+ *   dz_dev[i] = (float)( gamma * r * ( ((double)du[i] - S1 / N) - ((double)z[i] - mean) * (r * r * S2 / N) ) )
+ * double operations with one rounding each, no contraction; dz_dev, dgamma_dev, dbeta_dev are overwritten.
+ * Two launches, no atomics.  A channel's N values, n = b * pixels + p, are cut into `parts` contiguous ranges of `part_len`:
+ *   target = min(256, ceil(2048 / channels));   part_len = 1024 * ceil(ceil(N / target) / 1024);   parts = ceil(N / part_len)
+ * (rtod_bn_grad_parts returns both) — the shape alone, never the device.  The first launch, one workgroup of 256 threads per (channel,
+ * part), adds each thread's values in ascending order and the 256 thread sums in a fixed LDS tree, all in double, and writes one (S1,
+ * S2) pair per (channel, part); the second, on the same grid, adds a channel's pairs in ascending order in every workgroup's
+ * prologue and writes dz over its part.  Planes start at any 4-byte alignment (pixels = 169): a part is walked as the 16-byte
+ * aligned quads of memory it touches, whole quads by 16-byte accesses, a run's head and tail element by element.  Bit-identical from
+ * call to call and from device to device.  Workspace: 16 * channels * parts bytes.  Enqueues only (legal under stream capture).
+ * RTOD_E_ARG: a null pointer; batch, channels or pixels < 1; batch * pixels >= 2^29; channels * parts >= 2^31; du_dev, z_dev, dz_dev
+ * or the workspace not 16-byte aligned, mean_dev or var_dev not 8-byte aligned; a workspace that is too small. */
+int rtod_bn_grad_parts(int batch, int channels, int pixels, int* parts, int* part_len);
+int rtod_bn_grad_workspace(int batch, int channels, int pixels, size_t* bytes);
+int rtod_bn_grad(const float* du_dev, const float* z_dev, const double* mean_dev, const double* var_dev, const float* gamma_dev,
+                 int batch, int channels, int pixels, float* dz_dev, float* dgamma_dev, float* dbeta_dev,
+                 void* workspace_dev, size_t workspace_bytes, void* stream);
 
 /* ---- optimiser step of a detection-head conv, on the stream ------------------------------------------
  * replaces optim.Adam(self.darknet.parameters(), lr=1e-2) + optimizer.step()     train.py:57, 412-425
@@ -691,6 +725,32 @@ int rtod_plan_step_conv(rtod_plan* plan, int layer, const rtod_opt_step* opt,
  * "keep_block_inputs" (its scales are not on the device). */
 int rtod_plan_step_conv_folded(rtod_plan* plan, int layer, const rtod_opt_step* opt, float* weight_dev, const float* dw_dev,
                                float* m_w_dev, float* v_w_dev, void* stream);
+/* ---- training under batch statistics (plan options "bn_batch_stats" + "keep_bn_inputs", exact fp32) ----------------------------
+ * replaces .train() + optim.Adam(self.darknet.parameters()) + loss.backward() through nn.BatchNorm2d     train.py:57, 77, 412-425
+ * (new) rtod_plan_read_bn_input: beside rtod_plan_read_layer, a dense NCHW copy [batch, Cout, H, W] of the raw conv output z that the
+ * last forward's normalise step read for `layer` — the z of rtod_bn_grad.  RTOD_E_ARG: a null pointer, a batch outside 1..max_batch, a
+ * layer that is no BatchNorm conv the plan trains (the message says why: an eval plan, no "keep_bn_inputs", outside the kept scope, a
+ * shortcut in its normalise step).  RTOD_E_STATE before rtod_plan_load_weights. */
+int rtod_plan_read_bn_input(rtod_plan* plan, int layer, int batch, float* out_dev_nchw, void* stream);
+/* (new) Device addresses of the mean and the biased variance (double [Cout] each) the last forward normalised `layer` with, in the style
+ * of rtod_plan_conv_scale: the mean_dev / var_dev of rtod_bn_grad, the values rtod_plan_bn_batch_stats copies to the host.  The
+ * addresses stay valid for the plan's life; every forward overwrites the values.  Any BatchNorm conv of a "bn_batch_stats" plan. */
+int rtod_plan_bn_stats_dev(const rtod_plan* plan, int layer, const double** mean_dev, const double** var_dev);
+/* (new) rtod_plan_step_conv_folded for a conv whose BatchNorm runs on batch statistics: one optimiser step (the fp32 sequence of
+ * rtod_plan_step_conv, same host-derived scalars) on the float32 masters weight_dev [Cout, Cin, k, k], gamma_dev [Cout] and beta_dev
+ * [Cout] from dw_dev, dgamma_dev and dbeta_dev (rtod_conv_wgrad of the dz rtod_bn_grad wrote, and that entry's dgamma / dbeta), Adam
+ * moments m_* / v_* of the same shapes (all six or, for SGD, NULL), and the re-pack in place: the unfolded fp32 panel where
+ * rtod_plan_load_weights puts it (scale 1; the bias slot keeps its zeros) and the [beta, gamma] block of the image — bit-identical
+ * to a load of the stepped stream.  head_step.hip's kernel in one more mode: its extra workgroup steps the two vectors.  One launch;
+ * enqueues only (legal under stream capture); every refusal is decided before anything is enqueued.  RTOD_E_ARG: a null plan, opt
+ * or required pointer, the opt refusals of rtod_plan_step_conv, a layer rtod_plan_read_bn_input refuses (an eval plan: use
+ * rtod_plan_step_conv_folded).  RTOD_E_STATE before rtod_plan_load_weights.  Weight decay is not offered. */
+int rtod_plan_step_conv_bn(rtod_plan* plan, int layer, const rtod_opt_step* opt, float* weight_dev, const float* dw_dev, float* gamma_dev, float* beta_dev,
+                           const float* dgamma_dev, const float* dbeta_dev, float* m_w_dev, float* v_w_dev, float* m_gamma_dev, float* v_gamma_dev,
+                           float* m_beta_dev, float* v_beta_dev, void* stream);
+/* (new) Its host twin, in the style of rtod_plan_update_conv_weight: the conv's block re-packed from the three host arrays through the
+ * packing of rtod_plan_load_weights and uploaded alone.  Synchronises. */
+int rtod_plan_update_conv_bn(rtod_plan* plan, int layer, const float* weight_oihw_host, const float* gamma_host, const float* beta_host);
 /* (tests, debugging) The packed weight image as it is on the device now, copied to the host; SYNCHRONISES the device.  Size query
  * as rtod_plan_pack_weights: *needed (if given) receives the image's floats, with out_host == NULL nothing else happens, else
  * capacity_floats must cover it (RTOD_E_SIZE).  RTOD_E_STATE before rtod_plan_load_weights. */

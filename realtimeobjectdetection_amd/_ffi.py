@@ -114,6 +114,14 @@ SIGNATURES = {
                                        C.c_void_p, C.c_size_t, C.c_void_p]),
     "rtod_conv_dgrad_thin": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                        C.c_void_p, C.c_void_p]),
+    "rtod_plan_read_bn_input": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "rtod_plan_bn_stats_dev": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    "rtod_plan_step_conv_bn": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(OptStep)] + [C.c_void_p] * 13),
+    "rtod_plan_update_conv_bn": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rtod_bn_grad_parts": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "rtod_bn_grad_workspace": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    "rtod_bn_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                               C.c_void_p, C.c_size_t, C.c_void_p]),
 }
 # ... and the entry points whose names hold a digit (the scan of the header for declared names reads lower-case letters and '_')
 SIGNATURES_DIGIT_NAMES = {

@@ -3,6 +3,7 @@
 // All are HBM-bound elementwise work: 16 bytes per lane along the channel axis wherever the layout allows, grid capped at
 // ~2048 blocks + grid stride.  Each op has ONE kernel body over the activation format (Act<F> below).
 #include "conv_f16s3_common.h"
+#include "bn_constants.h"
 #include <algorithm>
 
 namespace rtod {
@@ -337,7 +338,7 @@ int launch_maxpool(const View& in, const View& out, int B, int size, int stride,
 // two divisions by npix interleaved (by value they ran one after the other: +0.5 us per BatchNorm layer, measured).
 struct BnConstants { float w, b; };
 __device__ __forceinline__ BnConstants bn_channel_constants(double mean, double var, const float& beta, const float& gamma) {
-    const double invstd = 1.0 / sqrt(var + 1e-5);
+    const double invstd = bn_inv_std(var);                            // (bn_constants.h: the backward reads the same r)
     return {(float)(invstd * (double)gamma), (float)((double)beta - mean * invstd * (double)gamma)};
 }
 // ... and of the normalise step of one value

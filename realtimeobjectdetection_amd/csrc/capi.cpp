@@ -540,6 +540,19 @@ int rtod_conv_dgrad_thin(const float* w_oihw_dev, const double* row_scale_dev, c
     RTOD_GUARD_END
 }
 
+int rtod_bn_grad_parts(int batch, int channels, int pixels, int* parts, int* part_len) { return bn_grad_parts(batch, channels, pixels, parts, part_len); }
+
+int rtod_bn_grad_workspace(int batch, int channels, int pixels, size_t* bytes) { return bn_grad_workspace(batch, channels, pixels, bytes); }
+
+int rtod_bn_grad(const float* du_dev, const float* z_dev, const double* mean_dev, const double* var_dev, const float* gamma_dev,
+                 int batch, int channels, int pixels, float* dz_dev, float* dgamma_dev, float* dbeta_dev,
+                 void* workspace_dev, size_t workspace_bytes, void* stream) {
+    RTOD_GUARD_BEGIN
+    return launch_bn_grad(du_dev, z_dev, mean_dev, var_dev, gamma_dev, batch, channels, pixels, dz_dev, dgamma_dev, dbeta_dev, workspace_dev, workspace_bytes,
+                          (hipStream_t)stream);
+    RTOD_GUARD_END
+}
+
 int rtod_plan_head_blocks(const rtod_plan* plan, int* head_conv_layers, int* block_conv_layers, int* block_input_layers, int capacity) {
     if (!plan || capacity < 0 || (capacity > 0 && (!head_conv_layers || !block_conv_layers || !block_input_layers))) { set_error("plan_head_blocks: bad args"); return RTOD_E_ARG; }
     int n = 0;
@@ -573,6 +586,37 @@ int rtod_plan_step_conv_folded(rtod_plan* plan, int layer, const rtod_opt_step* 
     RTOD_GUARD_BEGIN
     if (!plan) { set_error("step_conv_folded: null plan"); return RTOD_E_ARG; }
     return plan->p.step_conv_folded(layer, opt, weight_dev, dw_dev, m_w_dev, v_w_dev, (hipStream_t)stream);
+    RTOD_GUARD_END
+}
+
+int rtod_plan_read_bn_input(rtod_plan* plan, int layer, int batch, float* out_dev_nchw, void* stream) {
+    RTOD_GUARD_BEGIN
+    if (!plan) { set_error("read_bn_input: null plan"); return RTOD_E_ARG; }
+    return plan->p.read_bn_input(layer, batch, out_dev_nchw, (hipStream_t)stream);
+    RTOD_GUARD_END
+}
+
+int rtod_plan_bn_stats_dev(const rtod_plan* plan, int layer, const double** mean_dev, const double** var_dev) {
+    RTOD_GUARD_BEGIN
+    if (!plan) { set_error("bn_stats_dev: null plan"); return RTOD_E_ARG; }
+    return plan->p.bn_stats_dev(layer, mean_dev, var_dev);
+    RTOD_GUARD_END
+}
+
+int rtod_plan_step_conv_bn(rtod_plan* plan, int layer, const rtod_opt_step* opt, float* weight_dev, const float* dw_dev, float* gamma_dev, float* beta_dev,
+                           const float* dgamma_dev, const float* dbeta_dev, float* m_w_dev, float* v_w_dev, float* m_gamma_dev, float* v_gamma_dev,
+                           float* m_beta_dev, float* v_beta_dev, void* stream) {
+    RTOD_GUARD_BEGIN
+    if (!plan) { set_error("step_conv_bn: null plan"); return RTOD_E_ARG; }
+    return plan->p.step_conv_bn(layer, opt, weight_dev, dw_dev, gamma_dev, beta_dev, dgamma_dev, dbeta_dev, m_w_dev, v_w_dev, m_gamma_dev, v_gamma_dev,
+                                m_beta_dev, v_beta_dev, (hipStream_t)stream);
+    RTOD_GUARD_END
+}
+
+int rtod_plan_update_conv_bn(rtod_plan* plan, int layer, const float* weight_oihw_host, const float* gamma_host, const float* beta_host) {
+    RTOD_GUARD_BEGIN
+    if (!plan) { set_error("update_conv_bn: null plan"); return RTOD_E_ARG; }
+    return plan->p.update_conv_bn(layer, weight_oihw_host, gamma_host, beta_host);
     RTOD_GUARD_END
 }
 

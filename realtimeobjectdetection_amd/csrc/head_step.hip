@@ -15,6 +15,9 @@
 // from max |(double)w' * s| (kept as the double's integer bits), and v lands at panel[o * Kpad + tap * cin_p + c] or at half
 // (((c / 32) * taps + tap) * Npad + o) * 32 + c % 32.  There is no bias workgroup: the bias slot (beta - mean * s) keeps its bits.
 // A head conv is the case taps = 1, s = 1: (double)w' * 1.0 is w' itself, and the exponent of a double equals that of the float.
+// A conv whose BatchNorm runs on batch statistics (rtod_plan_step_conv_bn) is the case s = 1 with any taps — pack_conv leaves such a
+// conv unfolded — and the extra workgroup steps beta and gamma where a head conv's steps the bias: one mode of this kernel, not a
+// second launch for 2 Cout floats.
 // f32 -> f16 and back are the host's integer routines (f16_round.h: round to nearest even, subnormal halves kept, values at or
 // below 2^-25 to (signed) zero) — independent of the denormal mode the library is built with.  Nothing outside channel rows
 // [0, Cout) and columns [0, Cin) of this conv's block is written: padding channels, padding K and other convs keep their bits.
@@ -45,15 +48,21 @@ void head_step_kernel(HeadStepLaunch a) {
     __shared__ unsigned long long smax[256];
     const int tid = threadIdx.x;
     const int o = blockIdx.x;
-    if (o == a.cout) {                                              // the bias vector: masters, moments and the image's copy
-        for (int q = tid; q < a.cout; q += 256) {
-            float m = 0.f, v = 0.f;
-            if (a.kind == 1) { m = a.m_b[q]; v = a.v_b[q]; }
-            const float nb = opt_update(a, a.b[q], a.db[q], m, v);
-            if (a.kind == 1) { a.m_b[q] = m; a.v_b[q] = v; }
-            a.b[q] = nb;
-            a.bias[q] = nb;
-        }
+    if (o == a.cout) {                                              // the per-channel vectors: masters, moments and the image's copy
+        // the bias of a conv without BatchNorm; or (rtod_plan_step_conv_bn) beta and gamma of a batch-statistics BatchNorm conv,
+        // which take the same step and land in the image's [Npad] beta, [Npad] gamma block as pack_conv places them
+        auto step_vector = [&](float* master, const float* grad, float* mom1, float* mom2, float* image) {
+            for (int q = tid; q < a.cout; q += 256) {
+                float m = 0.f, v = 0.f;
+                if (a.kind == 1) { m = mom1[q]; v = mom2[q]; }
+                const float nb = opt_update(a, master[q], grad[q], m, v);
+                if (a.kind == 1) { mom1[q] = m; mom2[q] = v; }
+                master[q] = nb;
+                image[q] = nb;
+            }
+        };
+        if (a.gamma) { step_vector(a.beta, a.dbeta, a.m_be, a.v_be, a.bn); step_vector(a.gamma, a.dgamma, a.m_g, a.v_g, a.bn + a.Npad); }
+        else step_vector(a.b, a.db, a.m_b, a.v_b, a.bias);
         return;
     }
     const int n = a.cin * a.taps;                                   // the row of the OIHW master: q = c * taps + tap
@@ -105,7 +114,7 @@ void head_step_kernel(HeadStepLaunch a) {
 static_assert(ACT_SCALE_F16S3 == 8.0f, "head_step_kernel builds 2^-e / ACT_SCALE_F16S3 from the exponent");
 
 int launch_head_step(const HeadStepLaunch& h, hipStream_t s) {
-    hipLaunchKernelGGL(head_step_kernel, dim3((unsigned)(h.cout + (h.b ? 1 : 0))), dim3(256), 0, s, h);   // no bias workgroup for a BatchNorm conv
+    hipLaunchKernelGGL(head_step_kernel, dim3((unsigned)(h.cout + (h.b || h.gamma ? 1 : 0))), dim3(256), 0, s, h);   // no extra workgroup for a frozen-BatchNorm conv
     return hip_fail(hipGetLastError(), "head_step launch");
 }
 

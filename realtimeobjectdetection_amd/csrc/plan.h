@@ -32,6 +32,8 @@ struct Layer {
     bool fused_away = false;  // shortcut / yolo executed inside the preceding conv's epilogue
     int buf = -1, coff = 0;   // materialised output: arena buffer id + channel offset (-1: none/alias)
     int alias_of = -1;        // single-source route / yolo: same view as that layer
+    int z_buf = -1;           // BatchNorm conv of a batch-statistics plan with option keep_bn_inputs that the plan trains (Plan::trains_bn): the arena buffer of its
+                              // raw sums z, dense rows of cout floats, live from the conv to the end of the forward (-1: normalised in place)
     int bn_pool = -1;         // BatchNorm conv of a batch-statistics split plan (options bn_split_narrow + fuse_bn_pool): index of the 2x2 / stride-2
                               // max-pool that alone reads it and that its normalise kernel can run (candidate; Plan::form decides at run time)
 };
@@ -41,6 +43,7 @@ struct Buffer {
     int first = 0, last = 0;      // launch-time interval (layer indices) in which it is live
     int64_t floats_per_frame = 0;
     int64_t offset = 0;           // floats from arena base, for max_batch frames
+    bool bn_input = false;        // the kept raw sums of a BatchNorm conv (Layer::z_buf): placed behind the arena of the other buffers, never reused
 };
 
 enum LaunchKind { LK_CONV = 0, LK_PACK = 1, LK_UPSAMPLE = 2, LK_ADD = 3, LK_MAXPOOL = 4, LK_DECODE = 5, LK_COPY = 6, LK_STEM = 7 };
@@ -158,6 +161,9 @@ struct Plan {
                                       // liveness only: the plan then forms no fusion that hides a trainable conv (fusions_held, next to form)
     bool opt_keep_full_activations = false; // a superset of keep_backbone_activations over the FULL graph (scope_graph(SCOPE_FULL): convs of any Cin, layer 0 on a generic
                                       // layout, size-2 max-pools).  Holds the same fusions
+    bool opt_keep_bn_inputs = false;  // batch-statistics fp32 plans (inert without bn_batch_stats, refused on another precision): the raw output z of every BatchNorm
+                                      // conv the plan trains survives the forward in a buffer of its own (Layer::z_buf) — the operand of rtod_bn_grad —, and the
+                                      // *_shape_ok predicates stop excluding the plan: the listings are those of the eval plan with the same keep option
     bool opt_fuse_stem_pool = true;   // ... with the 2x2 / stride-2 max-pool that follows it in the same kernel where the plan allows it (off: A/B and tests)
     int opt_force_f16s3_variant = -1; // >= 0: tile variant for every split-f16 conv (>= BAND_VARIANT_BASE: band layers)
     int opt_force_f32_variant = -1;   // >= 0: tile variant for every exact-fp32 conv
@@ -202,10 +208,22 @@ struct Plan {
     // that is 3x3 / stride 2 / pad 1 instead of stride 1, and a two-source linear [shortcut]
     bool train_shape_ok(int layer) const;                                           // block_shape_ok, or block_shape_ok but for that stride
     // the full graph (rtod_plan_full_layers): two more kinds again, a block-shaped conv of ANY Cin (layer 0 included) and a size-2 max-pool
-    bool full_shape_ok(int layer) const;                                            // train_shape_ok, or block_shape_ok but for Cin and the layer-0 rule
+    bool stem_kernel_shape() const;                                                 // layer 0 has the shape the dedicated stem kernel takes, and option stem_kernel is on
+    bool full_shape_ok(int layer) const;                                           // train_shape_ok, or block_shape_ok but for Cin and the layer-0 rule
     Scope kept_scope() const {                                                      // the widest scope whose activations the options keep: decided here alone
         return opt_keep_full_activations ? SCOPE_FULL : opt_keep_backbone_activations ? SCOPE_BACKBONE : opt_keep_neck_activations ? SCOPE_NECK : opt_keep_block_inputs ? SCOPE_BLOCKS : SCOPE_NONE;
     }
+    bool trained_member(int layer, const std::vector<char>& kept) const;            // a block conv on every plan, and every BatchNorm conv of the kept graph
+    bool batch_trained() const { return opt_bn_batch_stats && opt_keep_bn_inputs; } // batch-statistics BatchNorm whose convs, gamma and beta train
+    bool trains_bn(int layer, const std::vector<char>& kept) const { return batch_trained() && trained_member(layer, kept); }
+    bool trains_bn(int layer) const { return batch_trained() && trained_member(layer, scope_graph(kept_scope())); }
+    int bn_conv(const char* who, int layer, size_t& slot) const;                    // the slot of a conv that trains_bn, or why `layer` is none
+    View bn_input_view(int layer) const;                                            // the kept raw sums z of that conv (base null: none)
+    int read_bn_input(int layer, int batch, float* out_nchw, hipStream_t s) const;  // rtod_plan_read_bn_input
+    int bn_stats_dev(int layer, const double** mean_dev, const double** var_dev) const;   // rtod_plan_bn_stats_dev
+    int step_conv_bn(int layer, const rtod_opt_step* opt, float* weight, const float* dw, float* gamma, float* beta, const float* dgamma, const float* dbeta,
+                     float* m_w, float* v_w, float* m_g, float* v_g, float* m_b, float* v_b, hipStream_t s);   // rtod_plan_step_conv_bn
+    int update_conv_bn(int layer, const float* weight_oihw, const float* gamma, const float* beta);   // its host twin (rtod_plan_update_conv_bn)
     bool trains_folded(int layer, const std::vector<char>& kept) const;             // what block_conv accepts: a block conv on every plan, and every BatchNorm conv of
     bool trains_folded(int layer) const;                                            // kept = scope_graph(kept_scope()) (load_weights asks that graph once for all layers)
     int block_conv(const char* who, int layer, size_t& slot) const;                 // the slot of a block conv, or why `layer` is none

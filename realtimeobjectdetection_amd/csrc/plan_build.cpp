@@ -48,7 +48,7 @@ static int resolve_alias(const std::vector<Layer>& layers, int i) {
 }
 
 void Plan::reset_planning() {
-    for (auto& L : layers) { L.fused_into = -1; L.fused_away = false; L.buf = -1; L.coff = 0; L.alias_of = -1; L.bn_pool = -1; }
+    for (auto& L : layers) { L.fused_into = -1; L.fused_away = false; L.buf = -1; L.coff = 0; L.alias_of = -1; L.bn_pool = -1; L.z_buf = -1; }
     bufs.clear(); launches.clear(); convs.clear(); input_buf = -1;
     tuned.clear(); tune_cache.clear(); tuning.clear();
 }
@@ -66,6 +66,7 @@ int Plan::set_option(const char* name, int value) {
         {"stem_pool", &Plan::opt_stem_pool}, {"fuse_stem_pool", &Plan::opt_fuse_stem_pool}, {"keep_head_inputs", &Plan::opt_keep_head_inputs},
         {"keep_block_inputs", &Plan::opt_keep_block_inputs}, {"keep_neck_activations", &Plan::opt_keep_neck_activations},
         {"keep_backbone_activations", &Plan::opt_keep_backbone_activations}, {"keep_full_activations", &Plan::opt_keep_full_activations},
+        {"keep_bn_inputs", &Plan::opt_keep_bn_inputs},
     };
     const std::string k(name);
     bool* flag = nullptr; int* num = nullptr;
@@ -130,6 +131,11 @@ std::vector<std::vector<int>> Plan::consumers() const {
         }
     }
     return cons;
+}
+
+// Layer 0 is what the dedicated stem kernel (reads NCHW directly) takes: a plain 3x3 / pad 1 conv of 3 channels with 32 or 64 filters
+bool Plan::stem_kernel_shape() const {
+    return layers[0].size == 3 && layers[0].pad == 1 && layers[0].cin == 3 && layers[0].cout % 32 == 0 && layers[0].cout <= 64 && layers[0].fused_into < 0 && opt_stem_kernel;
 }
 
 int Plan::plan_buffers() {
@@ -198,8 +204,7 @@ int Plan::plan_buffers() {
     convs.clear();
     if (layers[0].type != LT_CONV) { set_error("cfg: first layer must be convolutional"); return RTOD_E_CFG; }
     // dedicated stem kernel (reads NCHW directly) when layer 0 is a plain 3x3 / pad 1 conv with 32 or 64 filters
-    const bool use_stem = layers[0].size == 3 && layers[0].pad == 1 && layers[0].cin == 3 && layers[0].cout % 32 == 0 &&
-                          layers[0].cout <= 64 && layers[0].fused_into < 0 && opt_stem_kernel && !(opt_bn_batch_stats && layers[0].bn);
+    const bool use_stem = stem_kernel_shape() && !(opt_bn_batch_stats && layers[0].bn);
     // option stem_pool (split-f16 / f16 plans): a 16-filter layer 0 on the split stem of conv_stem16_f16s3.hip, BatchNorm folded or absent
     const bool use_stem16 = opt_stem_pool && precision >= 1 && layers[0].fused_into < 0 &&
                             conv_stem16_supported(layers[0].size, layers[0].stride, layers[0].pad, layers[0].cin, layers[0].cout, layers[0].act);
@@ -278,6 +283,17 @@ int Plan::plan_buffers() {
                 cons[i].size() == 1 && cons[i][0] == i + 1 && L.hout % 2 == 0 && L.wout % 2 == 0)
                 L.bn_pool = i + 1;
         }
+    // option keep_bn_inputs on a batch-statistics plan: every BatchNorm conv the plan trains writes its raw sums into a buffer of its own
+    // (dense rows of cout floats), which nothing reuses before the end of the forward; the normalise step reads it and writes the layer's view
+    if (batch_trained()) {
+        const std::vector<char> kept = scope_graph(kept_scope());
+        for (auto& L : layers) {
+            if (L.type != LT_CONV || !trained_member(L.index, kept)) continue;
+            Buffer b; b.C = L.cout; b.H = L.hout; b.W = L.wout; b.bn_input = true;
+            L.z_buf = (int)bufs.size();
+            bufs.push_back(b);
+        }
+    }
     // liveness per buffer over launch time (= layer index of the launch).  Candidates, not forms: the arena covers the fused and the stand-alone schedule
     const int NB = (int)bufs.size();
     for (auto& b : bufs) { b.first = 1 << 30; b.last = -1; }
@@ -293,6 +309,7 @@ int Plan::plan_buffers() {
             continue;
         }
         if (l.kind == LK_CONV && layers[l.layer].bn_pool >= 0) touch(buf_of_layer(layers[l.layer].bn_pool), t);   // written by the conv's normalise kernel when fused
+        if (l.kind == LK_CONV && layers[l.layer].z_buf >= 0) { touch(layers[l.layer].z_buf, t); touch(layers[l.layer].z_buf, n); }
         touch(buf_of_layer(l.in_layer), t);
         if (l.in2_layer >= 0) touch(buf_of_layer(l.in2_layer), t);
         if (l.kind == LK_COPY) touch(l.out_buf, t);
@@ -332,9 +349,12 @@ int Plan::plan_buffers() {
 }
 
 // Detection blocks.  The cfg's part of the definition: a BatchNorm conv, 1x1 or 3x3 / stride 1 / same padding, leaky or linear,
-// reading a multiple of 32 channels, whose BatchNorm is folded (no batch statistics).  Layer 0 reads three channels and is none.
+// reading a multiple of 32 channels, whose BatchNorm is folded — or, on a batch-statistics plan, whose raw output is kept (option
+// keep_bn_inputs: the operand of the BatchNorm backward); a batch-statistics plan without it has none.  The mask of a leaky member
+// comes from the sign of its stored output, which is act(u) only while no shortcut is added in its normalise step: fused_into < 0
+// below keeps such a conv out in every scope.  Layer 0 reads three channels and is none.
 bool Plan::block_shape_ok(int layer) const {
-    if (layer < 1 || layer >= (int)layers.size() || opt_bn_batch_stats) return false;
+    if (layer < 1 || layer >= (int)layers.size() || (opt_bn_batch_stats && !opt_keep_bn_inputs)) return false;
     const Layer& L = layers[layer];
     return L.type == LT_CONV && L.bn && (L.size == 1 || L.size == 3) && L.stride == 1 && L.pad == L.size / 2 && L.act <= 1 &&
            L.cin % 32 == 0 && L.fused_into < 0;
@@ -370,7 +390,7 @@ int Plan::block_of_head(int head) const {
 // conv and the residual [shortcut] (two sources, linear: it adds and carries no mask of its own).  A superset of the neck on every plan
 bool Plan::train_shape_ok(int layer) const {
     if (block_shape_ok(layer)) return true;
-    if (layer < 1 || layer >= (int)layers.size() || opt_bn_batch_stats) return false;
+    if (layer < 1 || layer >= (int)layers.size() || (opt_bn_batch_stats && !opt_keep_bn_inputs)) return false;
     const Layer& L = layers[layer];
     return L.type == LT_CONV && L.bn && L.size == 3 && L.stride == 2 && L.pad == 1 && L.act <= 1 && L.cin % 32 == 0 && L.fused_into < 0;
 }
@@ -380,7 +400,10 @@ bool Plan::train_shape_ok(int layer) const {
 // (rtod_maxpool_grad).  The plan's part stays block_plan_ok: a stem-layout layer 0 and a narrow-layout conv are no members
 bool Plan::full_shape_ok(int layer) const {
     if (train_shape_ok(layer)) return true;
-    if (layer < 0 || layer >= (int)layers.size() || opt_bn_batch_stats) return false;
+    if (layer < 0 || layer >= (int)layers.size() || (opt_bn_batch_stats && !opt_keep_bn_inputs)) return false;
+    // (a batch-statistics plan runs every BatchNorm layer 0 on the generic layout; one that the eval plan gives to the stem kernel stays
+    // out all the same, so that a scope names the same convs in both modes)
+    if (layer == 0 && opt_bn_batch_stats && stem_kernel_shape()) return false;
     const Layer& L = layers[layer];
     return L.type == LT_CONV && L.bn && (L.size == 1 || L.size == 3) && L.stride == 1 && L.pad == L.size / 2 && L.act <= 1 && L.cin >= 1 && L.fused_into < 0;
 }
@@ -409,9 +432,12 @@ std::vector<char> Plan::scope_graph(Scope scope) const {
 }
 
 // A block stays a block on every plan; the kept graph adds its BatchNorm convs
-bool Plan::trains_folded(int layer, const std::vector<char>& kept) const {
+bool Plan::trained_member(int layer, const std::vector<char>& kept) const {
     return block_of_head(layer + 1) == layer || (layer >= 0 && layer < (int)layers.size() && layers[layer].type == LT_CONV && layers[layer].bn && kept[layer]);
 }
+
+// ... trained folded on a plan that folds BatchNorm (a batch-statistics plan trains them through trains_bn / rtod_plan_step_conv_bn)
+bool Plan::trains_folded(int layer, const std::vector<char>& kept) const { return !opt_bn_batch_stats && trained_member(layer, kept); }
 
 bool Plan::trains_folded(int layer) const { return trains_folded(layer, scope_graph(kept_scope())); }
 
@@ -421,6 +447,7 @@ bool Plan::uses_split(const Layer& L) const {
 
 int Plan::check_split_supported(int mode) const {
     const char* pn = mode == 2 ? "f16" : "f16s3";
+    if (opt_keep_bn_inputs) { set_error("precision %s unsupported with keep_bn_inputs (the BatchNorm backward reads fp32 raw sums: exact-fp32 plans only)", pn); return RTOD_E_CFG; }
     if (opt_bn_batch_stats && !(opt_bn_batch_split && mode == 1)) {
         set_error("precision %s unsupported with bn_batch_stats (batch-statistics BatchNorm runs on the exact-fp32 kernels%s)", pn,
                   mode == 1 ? "; option bn_batch_split runs it on the split-f16 kernels" : "");
@@ -548,6 +575,7 @@ void Plan::assign_arena() {
     for (int id : order) {
         Buffer& B = bufs[id];
         const int64_t size = (B.floats_per_frame * max_batch + 63) / 64 * 64;   // 256-B granules
+        if (B.bn_input) continue;                                               // (below)
         std::vector<std::pair<int64_t, int64_t>> busy;
         for (int o : done) {
             const Buffer& O = bufs[o];
@@ -561,6 +589,23 @@ void Plan::assign_arena() {
         arena_floats = std::max(arena_floats, off + size);
         done.push_back(id);
     }
+    // the kept BatchNorm inputs (option keep_bn_inputs) live to the end of the forward and are never reused: one after the other behind
+    // the arena above, which is assigned as if they were not there (that of the eval plan with the same keep option)
+    for (auto& B : bufs) {
+        if (!B.bn_input) continue;
+        B.offset = arena_floats;
+        arena_floats += (B.floats_per_frame * max_batch + 63) / 64 * 64;
+    }
+}
+
+View Plan::bn_input_view(int layer) const {
+    View v;
+    if (layer < 0 || layer >= (int)layers.size() || layers[layer].z_buf < 0) return v;
+    const Layer& L = layers[layer];
+    const Buffer& b = bufs[L.z_buf];
+    v.base = d_arena ? d_arena + b.offset : nullptr;
+    v.ldc = b.C; v.coff = 0; v.C = L.cout; v.H = L.hout; v.W = L.wout;
+    return v;
 }
 
 View Plan::view_of(int layer) const {

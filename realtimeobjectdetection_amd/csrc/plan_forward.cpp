@@ -150,7 +150,7 @@ int Plan::run_conv_f32(const Launch& l, const LaunchForm& f, ConvArgs& a, int ba
     a.slice_chunks = mode ? pc.slice_chunks : 0;
     if (mode == 2) { a.partial = d_scratch; a.partial_floats = scratch_floats; }
     if (!(opt_bn_batch_stats && L.bn)) return launch_conv(a, v, s);
-    // raw conv, then statistics + normalise + activation + shortcut in place
+    // raw conv, then statistics + normalise + activation + shortcut, in place unless the raw sums are kept
     if (a.dec.enabled || (a.out_split && !bn_split_active()) || !d_bn_stats || pc.stats_off < 0) { set_error("forward: layer %d: batch-statistics BatchNorm on an unsupported launch", l.layer); return RTOD_E_STATE; }
     a.leaky = 0; a.res = nullptr;
     if (a.out_split) {                           // split plan (option bn_batch_split), layer 0: raw sums to the scratch, normalised into the split format
@@ -160,10 +160,12 @@ int Plan::run_conv_f32(const Launch& l, const LaunchForm& f, ConvArgs& a, int ba
         if (int rc = launch_conv(a, v, s)) return rc;
         return run_raw_bn(l, rv, f.pool, batch, s);
     }
+    // (option keep_bn_inputs, a conv the plan trains: the raw sums go to the conv's own buffer and stay there; the same values, read from there)
+    const View o = view_of(l.out_layer), z = bn_input_view(l.layer);
+    if (z.base) { a.out = z.base; a.out_ldc = z.ldc; a.out_coff = 0; }
     if (int rc = launch_conv(a, v, s)) return rc;
-    const View o = view_of(l.out_layer);
     View r; if (l.in2_layer >= 0) r = view_of(l.in2_layer);
-    return launch_bn_batch(o, o, l.in2_layer >= 0 ? &r : nullptr, batch, d_bn_stats + pc.stats_off, pc.Npad, d_weights + pc.bn_off, pc.Npad, L.act, d_bn_partial, bn_partial_count, s);
+    return launch_bn_batch(z.base ? z : o, o, l.in2_layer >= 0 ? &r : nullptr, batch, d_bn_stats + pc.stats_off, pc.Npad, d_weights + pc.bn_off, pc.Npad, L.act, d_bn_partial, bn_partial_count, s);
 }
 
 // A conv on a split-f16 / f16 tile; a BatchNorm conv of a batch-statistics split plan (LaunchForm::raw): raw sums, statistics, normalise

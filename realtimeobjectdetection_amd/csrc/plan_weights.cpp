@@ -211,6 +211,7 @@ int Plan::step_packed(const char* who, size_t slot, const rtod_opt_step* opt, bo
     h.lo = reinterpret_cast<uint16_t*>(d_weights + pc.wl_off);
     h.inv = d_weights + pc.s_off;
     h.bias = d_weights + pc.b_off;
+    if (h.gamma) h.bn = d_weights + pc.bn_off;                       // step_conv_bn: the [Npad] beta, [Npad] gamma block of a batch-statistics image
     return launch_head_step(h, s);
 }
 
@@ -257,7 +258,7 @@ int Plan::block_conv(const char* who, int layer, size_t& slot) const {
         const Scope kept = kept_scope();
         const bool shape_ok = kept == SCOPE_FULL ? full_shape_ok(layer) : kept == SCOPE_BACKBONE ? train_shape_ok(layer) : kept == SCOPE_NECK && block_shape_ok(layer);
         const PackedConv* pc = cs.slot >= 0 ? &convs[cs.slot] : nullptr;
-        const char* why = opt_bn_batch_stats ? "the plan runs batch-statistics BatchNorm: the conv is not folded"
+        const char* why = opt_bn_batch_stats ? "the plan runs batch-statistics BatchNorm: the conv is not folded; rtod_plan_step_conv_bn / rtod_plan_update_conv_bn train it with option keep_bn_inputs"
                         : pc && (pc->stem || pc->stem16) ? "a stem layout" : pc && pc->narrow ? "a narrow (Cin == 16) layout"
                         : cs.pair ? "part of a fused pointwise pair"
                         : shape_ok ? kText[kept].closure : kText[kept].shape;
@@ -307,6 +308,81 @@ int Plan::step_conv_folded(int layer, const rtod_opt_step* opt, float* weight, c
     HeadStepLaunch h;
     h.w = weight; h.dw = dw; h.m_w = m_w; h.v_w = v_w;
     return step_packed("step_conv_folded", slot, opt, m_w && v_w, true, h, s);
+}
+
+// The slot of a conv whose BatchNorm runs on batch statistics and trains with it (trains_bn: a batch-statistics plan with option
+// keep_bn_inputs, a block conv or a BatchNorm conv of the kept graph), or why `layer` is none: what read_bn_input, step_conv_bn and
+// update_conv_bn accept
+int Plan::bn_conv(const char* who, int layer, size_t& slot) const {
+    ConvSite cs;
+    if (int rc = conv_site(who, layer, cs)) return rc;
+    const Layer& L = layers[layer];
+    if (!L.bn) { set_error("%s: layer %d has no BatchNorm (rtod_plan_update_conv / rtod_plan_step_conv take such convs)", who, layer); return RTOD_E_ARG; }
+    if (!opt_bn_batch_stats) { set_error("%s: the plan folds BatchNorm (an eval plan): rtod_plan_step_conv_folded / rtod_plan_update_conv_weight train layer %d; this entry needs option bn_batch_stats", who, layer); return RTOD_E_ARG; }
+    if (!opt_keep_bn_inputs) { set_error("%s: the plan needs option keep_bn_inputs (it keeps the raw output of the BatchNorm convs the plan trains)", who); return RTOD_E_ARG; }
+    if (!trains_bn(layer) || cs.slot < 0 || L.z_buf < 0) {
+        const bool shortcut = L.fused_into >= 0 && layers[L.fused_into].type == LT_SHORTCUT;
+        set_error("%s: layer %d is not a conv this plan trains (%s)", who, layer,
+                  shortcut ? "a shortcut is added in its normalise step: its stored output is not act(u), so it carries no leaky mask; options keep_backbone_activations / keep_full_activations hold that fusion"
+                           : L.act > 1 ? "SiLU has no backward here"
+                           : "outside the kept scope graph, or no 1x1 / 3x3 leaky or linear BatchNorm conv of a generic layout");
+        return RTOD_E_ARG;
+    }
+    slot = (size_t)cs.slot;
+    return RTOD_OK;
+}
+
+// Dense NCHW copy of the raw sums z the last forward left for that conv
+int Plan::read_bn_input(int layer, int batch, float* out_nchw, hipStream_t s) const {
+    if (!out_nchw) { set_error("read_bn_input: null pointer"); return RTOD_E_ARG; }
+    if (batch < 1 || batch > max_batch) { set_error("read_bn_input: batch %d outside 1..%d", batch, max_batch); return RTOD_E_ARG; }
+    size_t slot = 0;
+    if (int rc = bn_conv("read_bn_input", layer, slot)) return rc;
+    const View z = bn_input_view(layer);
+    if (!weights_loaded || !z.base) { set_error("read_bn_input: call rtod_plan_load_weights first"); return RTOD_E_STATE; }
+    return launch_view_to_nchw(z, batch, out_nchw, s);
+}
+
+// Device addresses of the doubles the last forward normalised that layer with (any BatchNorm conv of a batch-statistics plan)
+int Plan::bn_stats_dev(int layer, const double** mean_dev, const double** var_dev) const {
+    if (!mean_dev || !var_dev) { set_error("bn_stats_dev: null pointer"); return RTOD_E_ARG; }
+    ConvSite cs;
+    if (int rc = conv_site("bn_stats_dev", layer, cs)) return rc;
+    if (!opt_bn_batch_stats || cs.slot < 0 || convs[cs.slot].stats_off < 0) { set_error("bn_stats_dev: layer %d has no batch-statistics BatchNorm (option bn_batch_stats, a BatchNorm conv)", layer); return RTOD_E_ARG; }
+    if (!weights_loaded || !d_bn_stats) { set_error("bn_stats_dev: call rtod_plan_load_weights first"); return RTOD_E_STATE; }
+    const PackedConv& pc = convs[cs.slot];
+    *mean_dev = d_bn_stats + pc.stats_off;
+    *var_dev = d_bn_stats + pc.stats_off + pc.Npad;
+    return RTOD_OK;
+}
+
+// step_conv_folded for a conv whose BatchNorm runs on batch statistics: the same kernel steps the raw master and re-packs it unfolded
+// (scale 1; the bias slot keeps its zeros), and its extra workgroup steps gamma and beta and writes the [beta, gamma] block at bn_off.
+// Enqueues only; every refusal is decided before anything is enqueued.
+int Plan::step_conv_bn(int layer, const rtod_opt_step* opt, float* weight, const float* dw, float* gamma, float* beta, const float* dgamma, const float* dbeta,
+                       float* m_w, float* v_w, float* m_g, float* v_g, float* m_b, float* v_b, hipStream_t s) {
+    if (!opt || !weight || !dw || !gamma || !beta || !dgamma || !dbeta) { set_error("step_conv_bn: null pointer"); return RTOD_E_ARG; }
+    size_t slot = 0;
+    if (int rc = bn_conv("step_conv_bn", layer, slot)) return rc;
+    HeadStepLaunch h;
+    h.w = weight; h.dw = dw; h.m_w = m_w; h.v_w = v_w;
+    h.gamma = gamma; h.beta = beta; h.dgamma = dgamma; h.dbeta = dbeta; h.m_g = m_g; h.v_g = v_g; h.m_be = m_b; h.v_be = v_b;
+    return step_packed("step_conv_bn", slot, opt, m_w && v_w && m_g && v_g && m_b && v_b, false, h, s);
+}
+
+// ... and its host twin, update_conv_weight for such a conv: the conv's block of the stream from the three arrays (the running
+// statistics are not part of a batch-statistics image), through pack_conv.  Synchronises the device.
+int Plan::update_conv_bn(int layer, const float* weight_oihw, const float* gamma, const float* beta) {
+    if (!weight_oihw || !gamma || !beta) { set_error("update_conv_bn: null pointer"); return RTOD_E_ARG; }
+    size_t slot = 0;
+    if (int rc = bn_conv("update_conv_bn", layer, slot)) return rc;
+    if (!weights_loaded || !d_weights) { set_error("update_conv_bn: call rtod_plan_load_weights first"); return RTOD_E_STATE; }
+    const Layer& L = layers[layer];
+    std::vector<float> stream(beta, beta + L.cout);
+    stream.insert(stream.end(), gamma, gamma + L.cout);
+    stream.insert(stream.end(), 2 * (size_t)L.cout, 0.0f);            // running mean / variance: not read by pack_conv in this mode
+    stream.insert(stream.end(), weight_oihw, weight_oihw + (int64_t)L.cout * L.cin * L.size * L.size);
+    return repack_conv(slot, stream);
 }
 
 // The device image as it is now (tests, debugging): synchronises.

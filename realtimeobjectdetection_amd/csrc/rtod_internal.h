@@ -409,6 +409,12 @@ int launch_grad_join(const float* const* contributions, int count, const float* 
 int launch_upsample2x_grad(const float* dz, const float* y, float slope, int mode, int batch, int channels, int h, int w, float* dx, hipStream_t s);
 // backward of the size-2 max-pool (stride 2 floor mode, or stride 1 clamped) in gather form, the producing conv's mask fused (maxpool_grad.hip)
 int launch_maxpool_grad(const float* dz, const float* x, float slope, int batch, int channels, int h, int w, int size, int stride, float* dx, hipStream_t s);
+// backward of batch-statistics BatchNorm over dense NCHW maps: dz, dgamma, dbeta from du, the raw conv output z and the forward's
+// double statistics, two launches over one partition that the shape alone fixes (bn_grad.hip)
+int bn_grad_parts(int batch, int channels, int pixels, int* parts, int* part_len);
+int bn_grad_workspace(int batch, int channels, int pixels, size_t* bytes);
+int launch_bn_grad(const float* du, const float* z, const double* mean, const double* var, const float* gamma, int batch, int channels, int pixels,
+                   float* dz, float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes, hipStream_t s);
 // optimiser step of one conv fused with the re-pack of its block of the weight image (head_step.hip): a 1x1 conv without BatchNorm
 // with its bias (Plan::step_conv), or a conv whose frozen BatchNorm scale is folded while it re-packs (b == NULL, scale given:
 // Plan::step_conv_folded).  The kernel's own argument: the scalars are what the host derived in double (Plan::opt_scalars), the
@@ -429,6 +435,12 @@ struct HeadStepLaunch {
     uint16_t *hi = nullptr, *lo = nullptr;          // split plans: [Kpad / 32][Npad][32] halves each
     float* inv = nullptr;                           // split plans: [Npad]
     float* bias = nullptr;                          // [Npad]
+    // a conv whose BatchNorm runs on batch statistics (Plan::step_conv_bn; b == NULL, scale == NULL: the conv is packed unfolded): the
+    // extra workgroup steps beta and gamma instead of a bias and writes them to the image's [Npad] beta, [Npad] gamma block
+    float *gamma = nullptr, *beta = nullptr;
+    const float *dgamma = nullptr, *dbeta = nullptr;
+    float *m_g = nullptr, *v_g = nullptr, *m_be = nullptr, *v_be = nullptr;
+    float* bn = nullptr;
 };
 int launch_head_step(const HeadStepLaunch& h, hipStream_t s);
 

@@ -364,12 +364,87 @@ class Darknet(nn.Module):
         if not self._stepped:
             return
         with torch.no_grad():
-            for layer, (w, b) in self._stepped.items():
-                conv = self._conv_bn(layer)[0]
+            for layer, (w, b, *gamma_beta) in self._stepped.items():
+                conv, bn = self._conv_bn(layer)
                 conv.weight.copy_(w)
                 if b is not None:                                 # (a block conv has BatchNorm and no bias: weight-only entry)
                     conv.bias.copy_(b)
+                if gamma_beta:                                    # (step_conv_bn: BatchNorm on batch statistics trains gamma and beta too)
+                    bn.weight.copy_(gamma_beta[0])
+                    bn.bias.copy_(gamma_beta[1])
         self._stepped.clear()
+
+    # ------------------------------------------------------------------ training under batch statistics (options keep_bn_inputs)
+    def read_bn_input(self, layer: int, batch: int) -> torch.Tensor:
+        """Dense NCHW copy of the raw conv output ``z`` that the last forward's BatchNorm step read for ``layer``
+        (rtod_plan_read_bn_input): the ``z`` of ``train.bn_grad_async``.  Needs a model in ``.train()`` (batch statistics) with
+        options ``keep_bn_inputs`` and a conv the plan trains under the keep option of the scope."""
+        if self._plan is None:
+            raise RuntimeError("Darknet.read_bn_input: no plan yet; run a forward first")
+        self._trained_conv("read_bn_input", layer, with_bn=True)
+        c, h, w = C.c_int(), C.c_int(), C.c_int()                  # (z has the shape of the layer's own output)
+        _ffi.check(_ffi.lib().rtod_plan_layer_shape(self._plan, int(layer), C.byref(c), C.byref(h), C.byref(w)))
+        dev = torch.device("cuda", self._plan_key[2])
+        out = torch.empty((int(batch), c.value, h.value, w.value), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            _ffi.check(_ffi.lib().rtod_plan_read_bn_input(self._plan, int(layer), int(batch), C.c_void_p(out.data_ptr()),
+                                                          C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        return out
+
+    def bn_stats_dev(self, layer: int):
+        """``(mean address, var address)``: where the plan keeps the float64 mean and biased variance the last forward normalised
+        ``layer`` with (rtod_plan_bn_stats_dev), in the style of ``conv_scale``; what ``train.bn_grad_async`` takes.  The
+        addresses stay valid for the plan's life, every forward overwrites the values."""
+        if not self._plan_is_current():
+            raise RuntimeError("Darknet.bn_stats_dev: no loaded plan holds the current parameters; run a forward first")
+        mean, var = C.c_void_p(), C.c_void_p()
+        _ffi.check(_ffi.lib().rtod_plan_bn_stats_dev(self._plan, int(layer), C.byref(mean), C.byref(var)))
+        return mean.value, var.value
+
+    def step_conv_bn(self, layer: int, opt, weight, dw, gamma, beta, dgamma, dbeta, moments=None) -> None:
+        """``step_conv_folded`` for a conv whose BatchNorm runs on batch statistics (rtod_plan_step_conv_bn): ``weight``
+        [Cout,Cin,k,k], ``gamma`` and ``beta`` [Cout] are the caller's float32 device masters (``conv.weight``, ``bn.weight``,
+        ``bn.bias``), updated IN PLACE from ``dw`` (``conv_wgrad_async`` of the ``dz`` of ``bn_grad_async``), ``dgamma`` and
+        ``dbeta`` and, for Adam, ``moments = (exp_avg, exp_avg_sq)`` of the weight, of gamma, of beta: six tensors.  One kernel
+        re-packs the unfolded conv and the [beta, gamma] block of the plan's image in place.  Nothing synchronises, nothing is
+        allocated.  The module's parameters lag behind as after ``step_conv``."""
+        layer = int(layer)
+        if not self._plan_is_current():
+            raise RuntimeError("Darknet.step_conv_bn: no loaded plan holds the current parameters; run a forward first")
+        dev = torch.device("cuda", self._plan_key[2])
+        if moments is not None and len(moments) != 6:
+            raise ValueError("Darknet.step_conv_bn: moments = (exp_avg_w, exp_avg_sq_w, exp_avg_gamma, exp_avg_sq_gamma, exp_avg_beta, exp_avg_sq_beta)")
+        mom = list(moments) if moments is not None else []
+        tensors = [weight, dw, gamma, beta, dgamma, dbeta] + mom
+        self._need_f32_on("step_conv_bn", dev, tensors)
+        conv = self._trained_conv("step_conv_bn", layer, with_bn=True)
+        like_w, like_c = [weight, dw] + mom[:2], [gamma, beta, dgamma, dbeta] + mom[2:]
+        if tuple(weight.shape) != tuple(conv.weight.shape) or any(t.numel() != weight.numel() for t in like_w) or any(t.numel() != conv.out_channels for t in like_c):
+            raise ValueError("Darknet.step_conv_bn: layer %d takes weight %s, gamma and beta [%d], and gradients and moments of their sizes"
+                             % (layer, tuple(conv.weight.shape), conv.out_channels))
+        args = [C.c_void_p(t.data_ptr()) for t in tensors] + [None] * (6 - len(mom))
+        with torch.cuda.device(dev):
+            _ffi.check(_ffi.lib().rtod_plan_step_conv_bn(self._plan, layer, C.byref(self._opt_step(opt)), *args, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        self._stepped[layer] = (weight, None, gamma, beta)
+
+    def update_conv_bn(self, layer: int, weight, gamma, beta) -> None:
+        """``update_conv_weight`` for a conv whose BatchNorm runs on batch statistics: ``weight`` [Cout,Cin,k,k], ``gamma`` and
+        ``beta`` [Cout] go into ``conv.weight``, ``bn.weight`` and ``bn.bias`` and, when a plan with current weights is loaded,
+        into that plan through rtod_plan_update_conv_bn, which re-packs this conv alone.  Synchronises."""
+        layer = int(layer)
+        conv = self._trained_conv("update_conv_bn", layer, with_bn=True)
+        bn = self._conv_bn(layer)[1]
+        new = [(p, torch.as_tensor(t).detach().to(torch.float32)) for p, t in ((conv.weight, weight), (bn.weight, gamma), (bn.bias, beta))]
+        if any(tuple(t.shape) != tuple(p.shape) for p, t in new):
+            raise ValueError("Darknet.update_conv_bn: layer %d takes weight %s, gamma and beta [%d]" % (layer, tuple(conv.weight.shape), conv.out_channels))
+        with torch.no_grad():
+            for p, t in new:
+                p.copy_(t)
+        self._stepped.pop(layer, None)
+        if self._plan_is_current():
+            host = [np.ascontiguousarray(t.cpu().numpy()) for _, t in new]
+            with torch.cuda.device(self._plan_key[2]):
+                _ffi.check(_ffi.lib().rtod_plan_update_conv_bn(self._plan, layer, *[h.ctypes.data_as(C.c_void_p) for h in host]))
 
     # ------------------------------------------------------------------ detection blocks (the BatchNorm conv a head conv reads)
     def _plan_list(self, who, entry, columns) -> list:

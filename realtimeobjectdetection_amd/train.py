@@ -9,8 +9,10 @@ BatchNorm in front of the [yolo] blocks), with a plain SGD step on them — fine
 the plan can train (``Darknet.trainable_layers``: on YOLOv3 all but layer 0), through 3x3 / stride-2 convs and residual shortcuts,
 and with ``trainable="full"`` through size-2 max-pools, convs of any Cin and a generic-layout layer 0 too (``Darknet.full_layers``: all
 11 BatchNorm convs of YOLOv3-tiny).
-BatchNorm gradients and batch statistics, symmetric-pool and SiLU backward, weight decay, epochs and data loaders are out of scope
-(DESIGN.md §8).  The reference's
+On a model left in ``.train()`` with ``options['keep_bn_inputs']`` (batch mode, exact fp32) every scope trains under the statistics of
+the batch, as the reference's trainer does: the walk goes through the BatchNorm backward (``bn_grad_async``) and ``bn.weight`` and
+``bn.bias`` are stepped beside the conv weights (``batchnorm_gradients``).  Symmetric-pool and SiLU backward, weight decay, epochs and
+data loaders are out of scope.  The reference's
 optimiser — ``optim.Adam(lr=1e-2)``, train.py:57 — runs on the trained convs as one kernel per conv that also re-packs the conv's weights in
 place (``HeadOptimizer``, ``feed_forward_through_model``): that path never synchronises.  Same names and return conventions as the
 reference:
@@ -38,6 +40,12 @@ reference:
 * ``DarknetTrainer(model, trainable="full")``, ``full_gradients(frames_or_x, bndbox)``                (new) ... and YOLOv3-tiny's backbone (``Darknet.full_layers``):
                                                                                             max-pools (``maxpool_grad_async``), thin convs
                                                                                             (``conv_wgrad_thin_async`` / ``conv_dgrad_thin_async``) and layer 0
+
+* ``bn_grad_async(du, z, mean, var, gamma) -> (dz, dgamma, dbeta)``, ``bn_grad_parts(batch, channels, pixels)``   (new) rtod_bn_grad: the backward of
+                                                                                            batch-statistics BatchNorm, double sums over a fixed partition
+* ``DarknetTrainer.batchnorm_gradients(frames_or_x, bndbox, scope=None)``                   (new) ``gradients`` with ``{conv_layer: (dgamma, dbeta)}`` as a
+                                                                                            fourth element; in batch mode ``feed_forward_through_model`` steps
+                                                                                            conv weight, gamma and beta (``Darknet.step_conv_bn``)
 
 The reference's behaviour is kept as it is: only boxes whose class-0 slot is 1 and whose sides are at least
 ``min_box_size`` (24) count, ``anchor_fit`` compares a box with a square of the anchor's WIDTH, target slot 0 holds the y fraction
@@ -344,6 +352,60 @@ def maxpool_grad_async(dz, x, slope=1.0, size=2, stride=2):
     return dx
 
 
+_bn_grad_ws = {}
+
+
+def bn_grad_parts(batch, channels, pixels):
+    """``(parts, part_len)`` of rtod_bn_grad for that shape (rtod_bn_grad_parts): a channel's ``batch * pixels`` values are summed as
+    ``parts`` contiguous ranges of ``part_len``, a rule of the shape alone."""
+    p, n = C.c_int(), C.c_int()
+    _ffi.check(_ffi.lib().rtod_bn_grad_parts(int(batch), int(channels), int(pixels), C.byref(p), C.byref(n)))
+    return p.value, n.value
+
+
+def _stat_ptr(who, t, channels, dev):
+    """``mean`` / ``var`` of ``bn_grad_async`` as a pointer: a contiguous float64 device tensor [C], or an integer device address."""
+    if isinstance(t, torch.Tensor):
+        if t.device != dev or t.dtype != torch.float64 or t.numel() != channels or not t.is_contiguous():
+            raise ValueError("%s: mean and var must be contiguous float64 tensors [%d] on %s" % (who, channels, dev))
+        return C.c_void_p(t.data_ptr())
+    return C.c_void_p(int(t))
+
+
+def bn_grad_async(du, z, mean, var, gamma):
+    """Enqueue rtod_bn_grad, the backward of batch-statistics BatchNorm: ``du`` [B,C,H,W] (the gradient with respect to the BatchNorm
+    output, the leaky mask already applied), ``z`` [B,C,H,W] (the raw conv output the forward normalised), ``mean`` / ``var`` (float64
+    device tensors [C] or integer device addresses: the doubles the forward normalised with) and ``gamma`` (float32 [C]) ->
+    ``(dz [B,C,H,W], dgamma [C], dbeta [C])``.  Double sums over a partition the shape alone fixes (``bn_grad_parts``), two launches,
+    no atomics: bit-identical from call to call.  Contiguous float32 device tensors; the workspace is cached per shape; nothing
+    synchronises."""
+    for t in (du, z, gamma):
+        _need_cuda(t, "bn_grad")
+    if du.dim() != 4 or tuple(du.shape) != tuple(z.shape) or du.dtype != torch.float32 or z.dtype != torch.float32 or gamma.dtype != torch.float32 \
+            or gamma.numel() != du.size(1):
+        raise ValueError("bn_grad: expected float32 du and z [B,C,H,W] and gamma [C], got %s, %s and %s" % (tuple(du.shape), tuple(z.shape), tuple(gamma.shape)))
+    aligned = lambda t: t.contiguous() if t.contiguous().data_ptr() % 16 == 0 else t.contiguous().clone()
+    du, z, gamma = aligned(du), aligned(z), gamma.contiguous()
+    B, ch, pixels = du.size(0), du.size(1), du.size(2) * du.size(3)
+    lib, dev = _ffi.lib(), du.device
+    key = (dev.index, B, ch, pixels)
+    ws = _bn_grad_ws.get(key)
+    if ws is None:
+        nbytes = C.c_size_t()
+        _ffi.check(lib.rtod_bn_grad_workspace(B, ch, pixels, C.byref(nbytes)))
+        if len(_bn_grad_ws) > 16:
+            _bn_grad_ws.clear()
+        ws = _bn_grad_ws[key] = (torch.empty((nbytes.value + 7) // 8, dtype=torch.float64, device=dev), nbytes.value)
+    dz = torch.empty_like(du)
+    dgamma = torch.empty(ch, dtype=torch.float32, device=dev)
+    dbeta = torch.empty(ch, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _ffi.check(lib.rtod_bn_grad(C.c_void_p(du.data_ptr()), C.c_void_p(z.data_ptr()), _stat_ptr("bn_grad", mean, ch, dev), _stat_ptr("bn_grad", var, ch, dev),
+                                    C.c_void_p(gamma.data_ptr()), B, ch, pixels, C.c_void_p(dz.data_ptr()), C.c_void_p(dgamma.data_ptr()),
+                                    C.c_void_p(dbeta.data_ptr()), C.c_void_p(ws[0].data_ptr()), ws[1], _stream(dev)))
+    return dz, dgamma, dbeta
+
+
 def grad_join_async(contributions, y=None, slope=1.0):
     """Enqueue rtod_grad_join: ``m(y) * (((c0 + c1) + c2) + c3)`` over equally shaped contiguous float32 device tensors, float32
     adds from left to right, then one multiplication by ``slope`` where ``not (y > 0)`` (``y`` None or ``slope`` 1: no mask) — the
@@ -420,7 +482,10 @@ class HeadOptimizer:
 
     ``state``: ``{conv_layer: {"step": t, "weight", "bias", "exp_avg", "exp_avg_sq", "exp_avg_bias", "exp_avg_sq_bias"}}`` — the
     masters (the very tensors of ``DarknetTrainer._head_masters``, so ``head_step`` and this path can be mixed), torch's moment
-    names and the number of steps taken; SGD keeps no moments.  ``lr`` may be changed between steps."""
+    names and the number of steps taken; SGD keeps no moments.  ``lr`` may be changed between steps.  A conv whose BatchNorm runs on
+    batch statistics (the trainer's batch mode, ``Darknet.step_conv_bn``) also keeps ``bn_weight`` and ``bn_bias`` (the gamma and beta
+    masters) and, for Adam, ``exp_avg_bn_weight``, ``exp_avg_sq_bn_weight``, ``exp_avg_bn_bias``, ``exp_avg_sq_bn_bias``;
+    ``state_dict`` / ``load_state_dict`` carry them like the rest."""
 
     KINDS = {"sgd": 0, "adam": 1}
 
@@ -441,17 +506,27 @@ class HeadOptimizer:
             st.update(exp_avg=torch.zeros_like(masters[0]), exp_avg_sq=torch.zeros_like(masters[0]))
             if masters[1] is not None:
                 st.update(exp_avg_bias=torch.zeros_like(masters[1]), exp_avg_sq_bias=torch.zeros_like(masters[1]))
+        if len(masters) == 4 and (st.get("bn_weight") is not masters[2] or st.get("bn_bias") is not masters[3]):
+            st.update(bn_weight=masters[2], bn_bias=masters[3])      # BatchNorm on batch statistics: gamma and beta train too
+        if self.kind == "adam" and "bn_weight" in st and "exp_avg_bn_weight" not in st:
+            st.update(exp_avg_bn_weight=torch.zeros_like(st["bn_weight"]), exp_avg_sq_bn_weight=torch.zeros_like(st["bn_weight"]),
+                      exp_avg_bn_bias=torch.zeros_like(st["bn_bias"]), exp_avg_sq_bn_bias=torch.zeros_like(st["bn_bias"]))
         return st
 
     def step(self, model, masters, grads):
         """One step of every conv in ``grads`` on ``masters``: ``{conv_layer: (dW, db)}`` and ``{conv_layer: [weight, bias]}`` for a
-        head conv (``Darknet.step_conv``), ``(dW, None)`` and ``[weight, None]`` for a block conv (``Darknet.step_conv_folded``)."""
-        for layer, (dw, db) in grads.items():
+        head conv (``Darknet.step_conv``), ``(dW, None)`` and ``[weight, None]`` for a block conv (``Darknet.step_conv_folded``),
+        ``(dW, None, dgamma, dbeta)`` and ``[weight, None, gamma, beta]`` for a conv whose BatchNorm runs on batch statistics
+        (``Darknet.step_conv_bn``)."""
+        for layer, (dw, db, *bn) in grads.items():
             st = self._entry(layer, masters[layer])
             st["step"] += 1
             opt = _ffi.OptStep(self.KINDS[self.kind], self.lr, self.betas[0], self.betas[1], self.eps, st["step"])
             adam = self.kind == "adam"
-            if db is None:
+            if bn:
+                moments = tuple(st[k] for k in ("exp_avg", "exp_avg_sq", "exp_avg_bn_weight", "exp_avg_sq_bn_weight", "exp_avg_bn_bias", "exp_avg_sq_bn_bias")) if adam else None
+                model.step_conv_bn(layer, opt, st["weight"], dw, st["bn_weight"], st["bn_bias"], bn[0], bn[1], moments)
+            elif db is None:
                 model.step_conv_folded(layer, opt, st["weight"], dw, (st["exp_avg"], st["exp_avg_sq"]) if adam else None)
             else:
                 moments = (st["exp_avg"], st["exp_avg_sq"], st["exp_avg_bias"], st["exp_avg_sq_bias"]) if adam else None
@@ -468,9 +543,12 @@ class HeadOptimizer:
         self.state = {int(layer): {k: (v.detach().clone() if isinstance(v, torch.Tensor) else int(v)) for k, v in st.items()} for layer, st in state.items()}
         trainer = self._trainer() if self._trainer is not None else None
         if trainer is not None:
-            trainer._head_masters = {layer: [st["weight"], st.get("bias")] for layer, st in self.state.items()}
-            for layer, (w, b) in trainer._head_masters.items():
-                if b is None:
+            trainer._head_masters = {layer: [st["weight"], st.get("bias")] + ([st["bn_weight"], st["bn_bias"]] if "bn_weight" in st else [])
+                                     for layer, st in self.state.items()}
+            for layer, (w, b, *bn) in trainer._head_masters.items():
+                if bn:
+                    trainer.darknet.update_conv_bn(layer, w, bn[0], bn[1])
+                elif b is None:
                     trainer.darknet.update_conv_weight(layer, w)
                 else:
                     trainer.darknet.update_conv(layer, w, b)
@@ -511,6 +589,24 @@ class DarknetTrainer:
         self._net_input = None             # the prepared input of the last _forward_train (what layer 0 read)
         self._graph_cache = None           # gradients: (scope, plan and weight version, the graph of that scope with its scales)
         self.optimizer = HeadOptimizer()
+        self._require_bn_option("DarknetTrainer", trainable)
+
+    # ------------------------------------------------------------------ BatchNorm on batch statistics: the one place that decides the mode
+    def _batch_stats(self):
+        """The model normalises with the statistics of the batch (``.train()``, ``bn_running_stats_in_train`` off)."""
+        m = self.darknet
+        return bool(getattr(m, "training", False) and not getattr(m, "bn_running_stats_in_train", False))
+
+    def _batch_mode(self):
+        """Batch mode: batch statistics, and the plan keeps the BatchNorm inputs (option ``keep_bn_inputs``): the walk goes through
+        ``bn_grad_async`` and gamma and beta are trained.  Otherwise BatchNorm is frozen (an eval model)."""
+        return self._batch_stats() and bool(int(getattr(self.darknet, "options", {}).get("keep_bn_inputs", 0)))
+
+    def _require_bn_option(self, who, scope):
+        if scope in self.SCOPES and self._batch_stats() and not self._batch_mode():
+            raise RuntimeError("%s: the model is in .train() (BatchNorm on batch statistics) and scope %r trains BatchNorm convs: set "
+                               "model.options['keep_bn_inputs'] = 1 before the first forward (the BatchNorm backward reads the raw conv outputs), "
+                               "or call .eval() to train with BatchNorm frozen" % (who, scope))
 
     @property
     def optimizer(self):
@@ -673,16 +769,20 @@ class DarknetTrainer:
 
     def _masters(self, layers, dev):
         """The float32 device masters ``[weight, bias]`` of the trained convs (bias None for a block conv: it has BatchNorm), taken
-        from the model's parameters the first time each is needed."""
+        from the model's parameters the first time each is needed.  In batch mode a BatchNorm conv's entry is ``[weight, None, gamma,
+        beta]``."""
         if self._head_masters is None:
             self._head_masters = {}
-        missing = [layer for layer in layers if layer not in self._head_masters]
+        batch = self._batch_mode()
+        missing = [layer for layer in layers if layer not in self._head_masters or (batch and self.darknet._conv_bn(layer)[1] is not None and len(self._head_masters[layer]) < 4)]
         if missing:
             self.darknet.sync_stepped_parameters()
+            own = lambda p: p.detach().to(dev, torch.float32).clone()
             for layer in missing:
-                conv = self.darknet._conv_bn(layer)[0]
-                bias = None if conv.bias is None else conv.bias.detach().to(dev, torch.float32).clone()
-                self._head_masters[layer] = [conv.weight.detach().to(dev, torch.float32).clone(), bias]
+                conv, bn = self.darknet._conv_bn(layer)
+                kept = self._head_masters.get(layer)
+                entry = kept[:2] if kept else [own(conv.weight), None if conv.bias is None else own(conv.bias)]
+                self._head_masters[layer] = entry + ([own(bn.weight), own(bn.bias)] if batch and bn is not None else [])
         return self._head_masters
 
     # ------------------------------------------------------------------ gradients behind the heads: one entry, three scopes
@@ -698,16 +798,26 @@ class DarknetTrainer:
         """``(loss, {head_conv_layer: (dW, db)}, {conv_layer: dW [Cout,Cin,k,k]})`` over the BatchNorm convs of ``scope`` ("blocks",
         "neck", "backbone" or "full"; default ``self.trainable``): ``head_gradients``, then ``_walk`` through ``_graph(scope)``.  All on the
         current stream, nothing synchronises.  The model's ``options`` must hold ``keep_head_inputs`` and the option of the scope."""
+        return self.batchnorm_gradients(frames_or_x, bndbox, scope)[:3]
+
+    def batchnorm_gradients(self, frames_or_x, bndbox, scope=None):
+        """``gradients`` with a fourth element: ``(loss, head grads, {conv_layer: dW}, {conv_layer: (dgamma [Cout], dbeta [Cout])})``.
+        In batch mode (the model in ``.train()``, ``options['keep_bn_inputs']``) these are what ``loss.backward()`` of the reference's
+        trainer leaves on ``conv.weight``, ``bn.weight`` and ``bn.bias`` of every BatchNorm conv of ``scope``: the walk turns the
+        gradient of each BatchNorm output into that of the raw conv output by ``bn_grad_async`` over ``Darknet.read_bn_input`` and the
+        plan's own statistics, and the conv gradients take no frozen scale.  On an eval model the fourth element is empty."""
         scope = self.trainable if scope is None else scope
         if scope not in self.SCOPES:
             raise ValueError("DarknetTrainer.gradients: scope must be 'blocks', 'neck', 'backbone' or 'full', got %r" % (scope,))
+        self._require_bn_option("DarknetTrainer.gradients", scope)
         entry, kept, lost = self.SCOPES[scope]
         opts = getattr(self.darknet, "options", {})
         if not (int(opts.get("keep_head_inputs", 0)) and any(int(opts.get(name, 0)) for name in kept)):
             raise RuntimeError("DarknetTrainer.%s: set model.options['keep_head_inputs'] = 1 and model.options['%s'] = 1 before the first forward; "
                                "without them %s" % (entry, kept[0], lost))
         loss, head_grads, operands = self._head_pass(frames_or_x, bndbox)
-        return loss, head_grads, self._walk(loss, head_grads, operands, self._graph(scope), self._net_input)
+        bn_grads = {} if self._batch_mode() else None
+        return loss, head_grads, self._walk(loss, head_grads, operands, self._graph(scope), self._net_input, bn_grads), bn_grads or {}
 
     def block_gradients(self, frames_or_x, bndbox):
         """``(loss, {head_conv_layer: (dW, db)}, {block_conv_layer: dW [Cout,Cin,k,k]})``: what ``loss.backward()`` of the reference
@@ -758,11 +868,13 @@ class DarknetTrainer:
         The model's ``options`` must hold ``keep_head_inputs`` and ``keep_full_activations``."""
         return self.gradients(frames_or_x, bndbox, "full")
 
-    def _walk(self, loss, head_grads, operands, graph, net_input=None):
+    def _walk(self, loss, head_grads, operands, graph, net_input=None, bn_grads=None):
         """The one walk under ``gradients``: ``{conv_layer: dW}`` of the BatchNorm convs of ``graph = (layers, readers, member,
         scales)``, in descending layer order, from the heads' ``operands`` (``_head_pass``).  No layer is copied twice in one call:
         ``stored`` starts out with the head-conv inputs ``_head_pass`` read.  A layer's dense ``read_layer`` copy is dropped once the
-        walk has passed the layer (every use of it lies at or behind it), and its entry of ``parts`` when its gradient is taken."""
+        walk has passed the layer (every use of it lies at or behind it), and its entry of ``parts`` when its gradient is taken.
+        ``bn_grads`` (a dict, batch mode): the gradient of a BatchNorm conv's output goes through ``bn_grad_async`` first — the raw conv
+        output of the forward, the plan's statistics, the gamma master —, which leaves ``(dgamma, dbeta)`` there; the scales are None."""
         model = self.darknet
         layers, readers, member, scales = graph
         masters = self._masters(list(head_grads) + sorted(scales), loss.device)
@@ -810,6 +922,9 @@ class DarknetTrainer:
                 head = i in operands
                 dz = operands[i][0] if head else gradient(i)
                 scale = None if head else scales[i]
+                if bn_grads is not None and not head:                 # du -> dz through the BatchNorm of the batch
+                    dz, dgamma, dbeta = bn_grad_async(dz, model.read_bn_input(i, B), *model.bn_stats_dev(i), masters[i][2])
+                    bn_grads[i] = (dgamma, dbeta)
                 if not head:
                     grads[i] = conv_wgrad_async(dz, read(i - 1), L.size, row_scale=scale, stride=L.stride)[0]
                 if i > 0:
@@ -841,7 +956,7 @@ class DarknetTrainer:
         "backbone" and "full": routes, upsamples, in the trainable graph shortcuts and in the full graph size-2 max-pools follow by
         the plan's closure rule: every reader is a member or a [yolo] layer."""
         model = self.darknet
-        key = (scope, model._plan.value, model._plan_weights_version)
+        key = (scope, model._plan.value, model._plan_weights_version, self._batch_mode())
         if self._graph_cache is None or self._graph_cache[0] != key:
             h = int(model.net_info["height"])
             w = int(model.input_width) if getattr(model, "input_width", None) is not None else h
@@ -863,7 +978,7 @@ class DarknetTrainer:
                 if L.type == "maxpool":                               # rtod_maxpool_grad's pools (the plan's rule)
                     ok = ok and L.size == 2 and L.stride in (1, 2) and not L.pool_pad
                 member[L.index] = ok and (scope == "blocks" or all(layers[r].type == "yolo" or member[r] for r in readers[L.index]))
-            scales = {c: model.conv_scale(c)[0] for c in trained}
+            scales = {c: None if self._batch_mode() else model.conv_scale(c)[0] for c in trained}     # batch mode: nothing is folded
             self._graph_cache = (key, (layers, readers, member, scales))
         return self._graph_cache[1]
 
@@ -878,9 +993,9 @@ class DarknetTrainer:
         if self.trainable in self.SCOPES:
             # every gradient kernel of the batch is enqueued before the first step, as autograd has it: the steps update the
             # masters in place, and the data gradients through the heads and the neck convs read them
-            loss, grads, block_grads = self.gradients(batch_data, bndbox)
+            loss, grads, block_grads, bn_grads = self.batchnorm_gradients(batch_data, bndbox)
             grads = dict(grads)
-            grads.update({layer: (dw, None) for layer, dw in block_grads.items()})
+            grads.update({layer: (dw, None) + tuple(bn_grads.get(layer, ())) for layer, dw in block_grads.items()})
         else:
             loss, grads = self.head_gradients(batch_data, bndbox)
         self.optimizer.step(self.darknet, self._masters(grads, loss.device), grads)
