@@ -211,7 +211,8 @@ int rtod_plan_set_precision(rtod_plan* plan, int mode);
  *                       convs (any Cin, layer 0 on a generic layout) and size-2 max-pools too.  Holds the same fusions
  *   "keep_bn_inputs"    (default 0) training under batch statistics: on a "bn_batch_stats" plan (inert without it) every BatchNorm conv
  *                       the plan trains — a detection block, and every BatchNorm conv of the graph the keep option above names — writes
- *                       its raw sums z into an arena buffer of its own (dense rows of Cout floats, never reused during the forward); the
+ *                       its raw sums z into an arena buffer of its own (never reused during the forward; rows of Cout floats on an
+ *                       exact-fp32 plan, of the raw-sum scratch's stride — Cout rounded up to 128 — on an f16s3 plan); the
  *                       normalise step reads it and writes the layer's view, so the forward's values are those of the in-place path bit
  *                       for bit.  rtod_plan_head_blocks, _neck_layers, _trainable_layers and _full_layers then list what the eval plan
  *                       with the same keep option lists (without it a batch-statistics plan lists nothing), rtod_plan_read_bn_input
@@ -725,7 +726,12 @@ int rtod_plan_step_conv(rtod_plan* plan, int layer, const rtod_opt_step* opt,
  * "keep_block_inputs" (its scales are not on the device). */
 int rtod_plan_step_conv_folded(rtod_plan* plan, int layer, const rtod_opt_step* opt, float* weight_dev, const float* dw_dev,
                                float* m_w_dev, float* v_w_dev, void* stream);
-/* ---- training under batch statistics (plan options "bn_batch_stats" + "keep_bn_inputs", exact fp32) ----------------------------
+/* ---- training under batch statistics (plan options "bn_batch_stats" + "keep_bn_inputs": exact fp32, or f16s3 with "bn_batch_split") ----
+ * On an f16s3 plan the option is accepted exactly when "bn_batch_stats" and "bn_batch_split" are both set (every other plan of
+ * precision 1 or 2 refuses it, RTOD_E_CFG), and not together with "bn_split_narrow", "stem_pool" or "k_slices_split".  The raw-sum
+ * instance of every trained conv then writes its own buffer instead of the shared scratch — the forward's bits do not change —,
+ * rtod_plan_read_bn_input returns those fp32 rows, and rtod_plan_step_conv_bn re-packs what that instance reads: the unfolded hi / lo
+ * planes, the per-channel pre-scale (inv_scale) and the [beta, gamma] block.  rtod_plan_describe marks the plan "bn_batch_trained":"split".
  * replaces .train() + optim.Adam(self.darknet.parameters()) + loss.backward() through nn.BatchNorm2d     train.py:57, 77, 412-425
  * (new) rtod_plan_read_bn_input: beside rtod_plan_read_layer, a dense NCHW copy [batch, Cout, H, W] of the raw conv output z that the
  * last forward's normalise step read for `layer` — the z of rtod_bn_grad.  RTOD_E_ARG: a null pointer, a batch outside 1..max_batch, a

@@ -17,7 +17,9 @@
 // A head conv is the case taps = 1, s = 1: (double)w' * 1.0 is w' itself, and the exponent of a double equals that of the float.
 // A conv whose BatchNorm runs on batch statistics (rtod_plan_step_conv_bn) is the case s = 1 with any taps — pack_conv leaves such a
 // conv unfolded — and the extra workgroup steps beta and gamma where a head conv's steps the bias: one mode of this kernel, not a
-// second launch for 2 Cout floats.
+// second launch for 2 Cout floats.  On a split plan (option bn_batch_split) that case takes the split arm below: the hi / lo planes, the
+// pre-scale and inv[o] of the unfolded weight, which is what the raw-sum conv instances read.  Every split tile family (generic, bandd,
+// 1x1 slabs) reads this one image layout, so there is one placement rule here as there is one in pack_conv.
 // f32 -> f16 and back are the host's integer routines (f16_round.h: round to nearest even, subnormal halves kept, values at or
 // below 2^-25 to (signed) zero) — independent of the denormal mode the library is built with.  Nothing outside channel rows
 // [0, Cout) and columns [0, Cin) of this conv's block is written: padding channels, padding K and other convs keep their bits.

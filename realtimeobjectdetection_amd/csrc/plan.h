@@ -33,7 +33,7 @@ struct Layer {
     int buf = -1, coff = 0;   // materialised output: arena buffer id + channel offset (-1: none/alias)
     int alias_of = -1;        // single-source route / yolo: same view as that layer
     int z_buf = -1;           // BatchNorm conv of a batch-statistics plan with option keep_bn_inputs that the plan trains (Plan::trains_bn): the arena buffer of its
-                              // raw sums z, dense rows of cout floats, live from the conv to the end of the forward (-1: normalised in place)
+                              // raw sums z, rows of Plan::z_stride floats, live from the conv to the end of the forward (-1: normalised in place, or from the shared scratch)
     int bn_pool = -1;         // BatchNorm conv of a batch-statistics split plan (options bn_split_narrow + fuse_bn_pool): index of the 2x2 / stride-2
                               // max-pool that alone reads it and that its normalise kernel can run (candidate; Plan::form decides at run time)
 };
@@ -161,7 +161,7 @@ struct Plan {
                                       // liveness only: the plan then forms no fusion that hides a trainable conv (fusions_held, next to form)
     bool opt_keep_full_activations = false; // a superset of keep_backbone_activations over the FULL graph (scope_graph(SCOPE_FULL): convs of any Cin, layer 0 on a generic
                                       // layout, size-2 max-pools).  Holds the same fusions
-    bool opt_keep_bn_inputs = false;  // batch-statistics fp32 plans (inert without bn_batch_stats, refused on another precision): the raw output z of every BatchNorm
+    bool opt_keep_bn_inputs = false;  // batch-statistics plans, exact fp32 or f16s3 with bn_batch_split (inert without bn_batch_stats on fp32, refused on any other plan): the raw output z of every BatchNorm
                                       // conv the plan trains survives the forward in a buffer of its own (Layer::z_buf) — the operand of rtod_bn_grad —, and the
                                       // *_shape_ok predicates stop excluding the plan: the listings are those of the eval plan with the same keep option
     bool opt_fuse_stem_pool = true;   // ... with the 2x2 / stride-2 max-pool that follows it in the same kernel where the plan allows it (off: A/B and tests)
@@ -219,6 +219,7 @@ struct Plan {
     bool trains_bn(int layer) const { return batch_trained() && trained_member(layer, scope_graph(kept_scope())); }
     int bn_conv(const char* who, int layer, size_t& slot) const;                    // the slot of a conv that trains_bn, or why `layer` is none
     View bn_input_view(int layer) const;                                            // the kept raw sums z of that conv (base null: none)
+    int z_stride(const Layer& L) const;                                             // floats per row of that buffer: Cout (fp32 plan) or raw_stride (split plan)
     int read_bn_input(int layer, int batch, float* out_nchw, hipStream_t s) const;  // rtod_plan_read_bn_input
     int bn_stats_dev(int layer, const double** mean_dev, const double** var_dev) const;   // rtod_plan_bn_stats_dev
     int step_conv_bn(int layer, const rtod_opt_step* opt, float* weight, const float* dw, float* gamma, float* beta, const float* dgamma, const float* dbeta,
@@ -268,7 +269,7 @@ struct Plan {
     bool raw_launch(const Launch& l) const { return bn_split_active() && l.kind == LK_CONV && layers[l.layer].bn; }   // a BatchNorm conv of such a plan: raw sums, then normalise
     bool bn_narrow_active() const { return bn_split_active() && opt_bn_split_narrow; }   // ... narrow tiles, 16-filter stem and fused pools included
     int raw_stride(const PackedConv& pc) const;           // floats per row of the raw-sum scratch: Npad; narrow tiles and the 16-filter stem: Cout rounded up to 8
-    View bn_raw_view(const Launch& l, int batch) const;   // fp32 view over d_bn_raw for this launch's conv
+    View bn_raw_view(const Launch& l, int batch) const;   // fp32 view of this launch's raw sums: the conv's kept buffer (Layer::z_buf) if it has one, else over d_bn_raw
     bool stem2_pattern = false;                 // launches 0 / 1 are a stem and the stride-2 conv conv_stem2_f16s3 fuses (candidate, set by plan_buffers)
     bool stem_pool_pattern = false;             // launch 0 is the 16-filter stem and launch 1 the 2x2 / stride-2 max-pool that alone reads it (candidate, set by plan_buffers)
     bool fusions_held() const;                  // option keep_backbone_activations: plan_buffers forms no shortcut fusion, no pointwise pair, no stem2 pattern

@@ -284,12 +284,12 @@ int Plan::plan_buffers() {
                 L.bn_pool = i + 1;
         }
     // option keep_bn_inputs on a batch-statistics plan: every BatchNorm conv the plan trains writes its raw sums into a buffer of its own
-    // (dense rows of cout floats), which nothing reuses before the end of the forward; the normalise step reads it and writes the layer's view
+    // (rows of z_stride floats), which nothing reuses before the end of the forward; the normalise step reads it and writes the layer's view
     if (batch_trained()) {
         const std::vector<char> kept = scope_graph(kept_scope());
         for (auto& L : layers) {
             if (L.type != LT_CONV || !trained_member(L.index, kept)) continue;
-            Buffer b; b.C = L.cout; b.H = L.hout; b.W = L.wout; b.bn_input = true;
+            Buffer b; b.C = z_stride(L); b.H = L.hout; b.W = L.wout; b.bn_input = true;
             L.z_buf = (int)bufs.size();
             bufs.push_back(b);
         }
@@ -447,7 +447,20 @@ bool Plan::uses_split(const Layer& L) const {
 
 int Plan::check_split_supported(int mode) const {
     const char* pn = mode == 2 ? "f16" : "f16s3";
-    if (opt_keep_bn_inputs) { set_error("precision %s unsupported with keep_bn_inputs (the BatchNorm backward reads fp32 raw sums: exact-fp32 plans only)", pn); return RTOD_E_CFG; }
+    // the BatchNorm backward reads fp32 raw sums: the exact-fp32 kernels write them, and so do the raw-sum instances of the split kernels
+    // (bn_split_active); no other plan of these precisions has any
+    const bool split_bn = mode == 1 && opt_bn_batch_stats && opt_bn_batch_split;
+    if (opt_keep_bn_inputs && !split_bn) {
+        set_error("precision %s unsupported with keep_bn_inputs (the BatchNorm backward reads fp32 raw sums: exact-fp32 plans, or f16s3 with bn_batch_stats + bn_batch_split)", pn);
+        return RTOD_E_CFG;
+    }
+    // ... and of those instances the generic, bandd and 1x1 slab tiles alone feed a conv that head_step_kernel can re-pack: the narrow
+    // tiles and the 16-filter stem have packers of their own
+    if (opt_keep_bn_inputs && (opt_bn_split_narrow || opt_stem_pool)) {
+        set_error("precision %s with keep_bn_inputs: option %s is not supported in that mode (narrow tiles and the 16-filter stem are not trained under batch statistics)",
+                  pn, opt_bn_split_narrow ? "bn_split_narrow" : "stem_pool");
+        return RTOD_E_CFG;
+    }
     if (opt_bn_batch_stats && !(opt_bn_batch_split && mode == 1)) {
         set_error("precision %s unsupported with bn_batch_stats (batch-statistics BatchNorm runs on the exact-fp32 kernels%s)", pn,
                   mode == 1 ? "; option bn_batch_split runs it on the split-f16 kernels" : "");
@@ -564,6 +577,16 @@ int Plan::raw_stride(const PackedConv& pc) const {
     return (pc.split && (pc.narrow || pc.stem16)) ? (layers[pc.layer].cout + 7) / 8 * 8 : pc.Npad;
 }
 
+// Floats per row of a kept BatchNorm input (Layer::z_buf), the one rule: dense, Cout, where an exact-fp32 conv writes it as its own
+// output; on a batch-statistics split plan the buffer stands in for the raw-sum scratch of that conv, so its rows are the scratch's
+// (raw_stride: Npad, which the bandd and slab tiles require of raw_ld and the generic tiles, the exact-fp32 layer 0 and
+// launch_bn_batch_split accept).  bn_input_view, and through it read_bn_input, take the stride from the buffer.
+int Plan::z_stride(const Layer& L) const {
+    if (bn_split_active())
+        for (const auto& pc : convs) if (pc.layer == L.index) return raw_stride(pc);
+    return L.cout;
+}
+
 void Plan::assign_arena() {
     const int NB = (int)bufs.size();
     // greedy arena assignment (first fit by offset among lifetime-overlapping buffers)
@@ -656,6 +679,11 @@ std::string Plan::describe() const {
     }
     os << "]";
     if (bn_split_active()) os << ",\"bn_batch_split\":true,\"bn_raw_bytes\":" << bn_raw_floats * 4;     // batch-statistics BatchNorm on the split kernels: its raw-sum scratch
+    if (bn_split_active() && batch_trained()) {                        // ... trained there (option keep_bn_inputs): the kept raw sums behind the arena
+        int64_t kept = 0;
+        for (const auto& b : bufs) if (b.bn_input) kept += (b.floats_per_frame * max_batch + 63) / 64 * 64;
+        os << ",\"bn_batch_trained\":\"split\",\"bn_input_bytes\":" << kept * 4;
+    }
     os << "}";
     return os.str();
 }

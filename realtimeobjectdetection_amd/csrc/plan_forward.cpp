@@ -98,9 +98,11 @@ int Plan::build_conv_args(const Launch& l, const LaunchForm& f, int batch, float
     return RTOD_OK;
 }
 
-// fp32 view over the raw-sum scratch for the conv of launch `l` at this batch: rows of raw_stride floats (base null: no scratch / too small)
+// fp32 view of the raw sums of launch `l`'s conv at this batch, rows of raw_stride floats: the conv's own kept buffer where the plan trains
+// it (option keep_bn_inputs: the same rows, which then survive the forward), else the shared scratch (base null: no scratch / too small)
 View Plan::bn_raw_view(const Launch& l, int batch) const {
-    View v;
+    View v = bn_input_view(l.layer);
+    if (v.base) return v;
     const Layer& L = layers[l.layer];
     const PackedConv& pc = convs[l.conv_slot];
     if (!d_bn_raw || (int64_t)batch * L.hout * L.wout * raw_stride(pc) > bn_raw_floats) return v;

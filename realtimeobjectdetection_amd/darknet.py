@@ -378,7 +378,8 @@ class Darknet(nn.Module):
     def read_bn_input(self, layer: int, batch: int) -> torch.Tensor:
         """Dense NCHW copy of the raw conv output ``z`` that the last forward's BatchNorm step read for ``layer``
         (rtod_plan_read_bn_input): the ``z`` of ``train.bn_grad_async``.  Needs a model in ``.train()`` (batch statistics) with
-        options ``keep_bn_inputs`` and a conv the plan trains under the keep option of the scope."""
+        options ``keep_bn_inputs`` and a conv the plan trains under the keep option of the scope.  On a split-f16 plan (options
+        ``bn_batch_split``) these are the fp32 sums the raw-sum conv instance wrote, the operand of that plan's normalise step."""
         if self._plan is None:
             raise RuntimeError("Darknet.read_bn_input: no plan yet; run a forward first")
         self._trained_conv("read_bn_input", layer, with_bn=True)

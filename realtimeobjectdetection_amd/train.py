@@ -9,8 +9,9 @@ BatchNorm in front of the [yolo] blocks), with a plain SGD step on them — fine
 the plan can train (``Darknet.trainable_layers``: on YOLOv3 all but layer 0), through 3x3 / stride-2 convs and residual shortcuts,
 and with ``trainable="full"`` through size-2 max-pools, convs of any Cin and a generic-layout layer 0 too (``Darknet.full_layers``: all
 11 BatchNorm convs of YOLOv3-tiny).
-On a model left in ``.train()`` with ``options['keep_bn_inputs']`` (batch mode, exact fp32) every scope trains under the statistics of
-the batch, as the reference's trainer does: the walk goes through the BatchNorm backward (``bn_grad_async``) and ``bn.weight`` and
+On a model left in ``.train()`` with ``options['keep_bn_inputs']`` (batch mode: exact fp32, or precision "f16s3" with
+``options['bn_batch_split']``, where the forward runs the split-f16 raw-sum kernels and the backward stays exact fp32 over the values that
+forward stored) every scope trains under the statistics of the batch, as the reference's trainer does: the walk goes through the BatchNorm backward (``bn_grad_async``) and ``bn.weight`` and
 ``bn.bias`` are stepped beside the conv weights (``batchnorm_gradients``).  Symmetric-pool and SiLU backward, weight decay, epochs and
 data loaders are out of scope.  The reference's
 optimiser — ``optim.Adam(lr=1e-2)``, train.py:57 — runs on the trained convs as one kernel per conv that also re-packs the conv's weights in
