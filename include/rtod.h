@@ -672,6 +672,38 @@ int rtod_bn_grad_workspace(int batch, int channels, int pixels, size_t* bytes);
 int rtod_bn_grad(const float* du_dev, const float* z_dev, const double* mean_dev, const double* var_dev, const float* gamma_dev,
                  int batch, int channels, int pixels, float* dz_dev, float* dgamma_dev, float* dbeta_dev,
                  void* workspace_dev, size_t workspace_bytes, void* stream);
+/* (new) rtod_conv_dgrad on the forward's split-f16 MFMA tiles (opt-in; dgrad_split.hip).  Operands and result are those of
+ * rtod_conv_dgrad: dx = m(y) * conv_T(dz, v), v = (float)((double)w * row_scale[o]) or w, dense fp32 NCHW, size 1 or 3, stride 1,
+ * cin a positive multiple of 32, any cout >= 1 (K is padded with zero channels to a multiple of 32).  The arithmetic:
+ *   dz       per image b, a_b = max |dz[b]|, e_b puts a_b 2^e_b in [2^12, 2^13) (a_b == 0: e_b = 0; e_b held to -126 .. 126);
+ *            dz 2^e_b stored as f16 hi = RNE(v), lo = RNE(v - hi), NHWC split layout (no 8 x).  Per image: an image's dx does not
+ *            depend on the batch it rides in.
+ *   weights  row c of the gradient conv (the forward's input channel) is pre-scaled like an output channel of the forward's packed
+ *            weights: max over o and taps of |(double)w * row_scale| placed in [2^12, 2^13), e_c in -24 .. 40, an all-zero row e_c = 0;
+ *            hi / lo planes [chunk][Npad][32], K index ((o / 32) * taps + tap') * 32 + o % 32, tap' = taps - 1 - tap.  Packed on the
+ *            device from the masters at every call.
+ *   sum      hi*hi + hi*lo + lo*hi in the MFMA's fp32 accumulators, by the raw-sum instance of an existing forward tile.
+ *   finish   dx[b][c] = m(y) * (sum * 2^-e_c * 2^-e_b): exact scales, one rounding multiplication (the mask).
+ * rtod_conv_dgrad_split_tiles (no device): the number of legal tile ids of the shape, the default first, by the rules that pick the
+ * forward's tiles (band layers W <= 94: the bandd modes of their K-group count; 94 < W <= 160 with Npad % 128 == 0: the wide tile too;
+ * 1x1 with K a multiple of 64: the slab tiles too; the generic tiles for the rest); at most `capacity` ids are written.  tile = -1
+ * runs the default; an id outside the list: RTOD_E_ARG.  Workspace: rtod_conv_dgrad_split_workspace bytes, 16-byte aligned; every
+ * byte a kernel reads is written earlier in the same call.  Seven launches on `stream`, nothing synchronises, no host read of device
+ * memory, no atomics: bit-identical from call to call and from tile to tile; legal under stream capture.  RTOD_E_ARG, each text
+ * starting with the entry's name: a null w / dz / dx / workspace, batch, cout, height or width < 1, batch > 65535, cin not a
+ * positive multiple of 32, size not 1 or 3, slope NaN, batch * pixels >= 2^31 - 256, a split dz buffer (4 * batch * pixels * K bytes)
+ * or a weight plane (2 * K * taps * Npad bytes) of 2 GiB or more, a workspace that is too small or misaligned. */
+int rtod_conv_dgrad_split_tiles(int batch, int cout, int cin, int height, int width, int size, int* ids, int capacity);
+int rtod_conv_dgrad_split_workspace(int batch, int cout, int cin, int height, int width, int size, size_t* bytes);
+int rtod_conv_dgrad_split(const float* w_oihw_dev, const double* row_scale_dev, const float* dz_dev, const float* y_dev, float slope,
+                          int batch, int cout, int cin, int height, int width, int size, int tile,
+                          float* dx_dev, void* workspace, size_t workspace_bytes, void* stream);
+/* ... for measurement (tools/exp_grad_split.py): the same call enqueues only the kernel groups named in `phases`, a sum of 1 (the
+ * images' maxima and exponents), 2 (dz to split planes), 4 (row maxima and weight pack), 8 (the conv) and 16 (the finish), on a
+ * workspace that a full call of the same shape has filled.  31 is rtod_conv_dgrad_split; outside 1 .. 31: RTOD_E_ARG. */
+int rtod_conv_dgrad_split_phases(const float* w_oihw_dev, const double* row_scale_dev, const float* dz_dev, const float* y_dev, float slope,
+                                 int batch, int cout, int cin, int height, int width, int size, int tile,
+                                 float* dx_dev, void* workspace, size_t workspace_bytes, void* stream, int phases);
 
 /* ---- optimiser step of a detection-head conv, on the stream ------------------------------------------
  * replaces optim.Adam(self.darknet.parameters(), lr=1e-2) + optimizer.step()     train.py:57, 412-425

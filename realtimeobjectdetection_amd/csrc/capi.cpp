@@ -540,6 +540,36 @@ int rtod_conv_dgrad_thin(const float* w_oihw_dev, const double* row_scale_dev, c
     RTOD_GUARD_END
 }
 
+int rtod_conv_dgrad_split_tiles(int batch, int cout, int cin, int height, int width, int size, int* ids, int capacity) {
+    RTOD_GUARD_BEGIN
+    return conv_dgrad_split_tiles(batch, cout, cin, height, width, size, ids, capacity);
+    RTOD_GUARD_END
+}
+
+int rtod_conv_dgrad_split_workspace(int batch, int cout, int cin, int height, int width, int size, size_t* bytes) {
+    RTOD_GUARD_BEGIN
+    return conv_dgrad_split_workspace(batch, cout, cin, height, width, size, bytes);
+    RTOD_GUARD_END
+}
+
+int rtod_conv_dgrad_split(const float* w_oihw_dev, const double* row_scale_dev, const float* dz_dev, const float* y_dev, float slope,
+                          int batch, int cout, int cin, int height, int width, int size, int tile,
+                          float* dx_dev, void* workspace, size_t workspace_bytes, void* stream) {
+    RTOD_GUARD_BEGIN
+    return launch_conv_dgrad_split(w_oihw_dev, row_scale_dev, dz_dev, y_dev, slope, batch, cout, cin, height, width, size, tile, dx_dev, workspace,
+                                   workspace_bytes, (hipStream_t)stream);
+    RTOD_GUARD_END
+}
+
+int rtod_conv_dgrad_split_phases(const float* w_oihw_dev, const double* row_scale_dev, const float* dz_dev, const float* y_dev, float slope,
+                                 int batch, int cout, int cin, int height, int width, int size, int tile,
+                                 float* dx_dev, void* workspace, size_t workspace_bytes, void* stream, int phases) {
+    RTOD_GUARD_BEGIN
+    return launch_conv_dgrad_split(w_oihw_dev, row_scale_dev, dz_dev, y_dev, slope, batch, cout, cin, height, width, size, tile, dx_dev, workspace,
+                                   workspace_bytes, (hipStream_t)stream, phases);
+    RTOD_GUARD_END
+}
+
 int rtod_bn_grad_parts(int batch, int channels, int pixels, int* parts, int* part_len) { return bn_grad_parts(batch, channels, pixels, parts, part_len); }
 
 int rtod_bn_grad_workspace(int batch, int channels, int pixels, size_t* bytes) { return bn_grad_workspace(batch, channels, pixels, bytes); }

@@ -403,6 +403,14 @@ int launch_wgrad(const char* who, WgradRule rule, const float* dz, const float* 
 // alone), h x w the conv's INPUT map, the same chains over parity-class tiles.  `who` names the entry in the error texts.
 int launch_conv_dgrad(const char* who, const float* w, const double* row_scale, const float* dz, const float* y, float slope, int batch, int cout,
                       int cin, int h, int w_, int size, int stride, float* dx, hipStream_t s, bool any_cin = false);   // any_cin (rtod_conv_dgrad_thin): cin % 32 is not refused, stride 2 is
+// the same gradient (size 1 or 3, stride 1, cin % 32 == 0) on the forward's split-f16 tiles (dgrad_split.hip): per-image scaled split
+// dz, weights packed transposed and flipped at every call, a raw-sum launch of an existing tile, a finishing transpose with the mask
+int conv_dgrad_split_tiles(int batch, int cout, int cin, int h, int w, int size, int* ids, int capacity);
+int conv_dgrad_split_workspace(int batch, int cout, int cin, int h, int w, int size, size_t* bytes);
+int launch_conv_dgrad_split(const float* w, const double* row_scale, const float* dz, const float* y, float slope, int batch, int cout, int cin,
+                            int h, int w_, int size, int tile, float* dx, void* workspace, size_t workspace_bytes, hipStream_t s, int phases = 31);
+// ... `phases` (rtod_conv_dgrad_split_phases: measurement): which kernel groups of the call are enqueued, on a workspace a full call has filled
+enum { DGS_AMAX = 1, DGS_SPLIT = 2, DGS_PACK = 4, DGS_CONV = 8, DGS_FINISH = 16, DGS_ALL = 31 };
 // out = m(y) * (((c0 + c1) + c2) + c3): the fan-out sum of the gradient walk, 1 to 4 contributions, in one launch (grad_join.hip)
 int launch_grad_join(const float* const* contributions, int count, const float* y, float slope, int64_t n, float* out, hipStream_t s);
 // backward of the 2x upsample (bilinear align_corners=False, or nearest) in gather form, the producing conv's mask fused (upsample_grad.hip)

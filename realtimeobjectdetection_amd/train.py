@@ -330,6 +330,71 @@ def conv_dgrad_thin_async(w, dz, size, row_scale=None, y=None, slope=1.0, stride
     return _dgrad("conv_dgrad_thin", w, dz, int(size), row_scale, y, slope, stride, None, thin=True)
 
 
+_dgrad_split_ws = {}
+GRAD_PRECISIONS = ("fp32", "f16s3")      # DarknetTrainer(grad_precision=...): the exact data gradients, or the split-f16 ones where the walk sends the conv there
+# ... which is the 3x3 convs the entry takes.  The 1x1 convs stay on the exact entry: measured (tools/exp_grad_split.py, profiles/experiments/grad_split_cost.log;
+# 416x416 batch 8) YOLOv3's 37 take 2033.6 us exact and 1786.5 us through the split entry, YOLOv3-tiny's 4 take 95.3 us exact and 129.6 us split (four helper
+# launches per call around a small GEMM), and YOLOv3's whole step is the same within the rounds' spread either way (34151.8 us with them, 34207.7 us without)
+GRAD_SPLIT_SIZES = (3,)
+
+
+def conv_dgrad_split_tiles(batch, cout, cin, height, width, size):
+    """The legal tile ids of rtod_conv_dgrad_split for that shape, the default first (rtod_conv_dgrad_split_tiles; no device)."""
+    lib = _ffi.lib()
+    shape = (int(batch), int(cout), int(cin), int(height), int(width), int(size))
+    n = lib.rtod_conv_dgrad_split_tiles(*shape, None, 0)
+    if n < 0:
+        _ffi.check(n)
+    ids = (C.c_int * max(n, 1))()
+    n = lib.rtod_conv_dgrad_split_tiles(*shape, ids, n)
+    if n < 0:
+        _ffi.check(n)
+    return [ids[i] for i in range(n)]
+
+
+def conv_dgrad_split_takes(cin, size, stride=1):
+    """Does rtod_conv_dgrad_split take a conv of that shape?  Stride 1, size 1 or 3, ``Cin`` a positive multiple of 32."""
+    return stride == 1 and size in (1, 3) and cin >= 32 and cin % 32 == 0
+
+
+def conv_dgrad_split_async(w, dz, size, row_scale=None, y=None, slope=1.0, tile=None, phases=None):
+    """Enqueue rtod_conv_dgrad_split: the operands and the result of ``conv_dgrad_async`` (stride 1, ``Cin`` a multiple of 32), summed
+    on the forward's split-f16 MFMA tiles: ``dz`` scaled per image by a power of two and split into f16 hi / lo planes, the weights
+    packed transposed, flipped and pre-scaled per row from the masters at every call, hi*hi + hi*lo + lo*hi in fp32 accumulators, then
+    exact inverse scales and one multiplication by the mask.  ``tile``: one of ``conv_dgrad_split_tiles`` (None: the default; every
+    legal tile gives the same bits).  The workspace is cached per shape; nothing synchronises.  ``phases`` (measurement only,
+    rtod_conv_dgrad_split_phases): a sum of 1, 2, 4, 8, 16 naming the kernel groups to enqueue on the workspace a full call has filled."""
+    who = "conv_dgrad_split"
+    for t in (w, dz) + ((y,) if y is not None else ()):
+        _need_cuda(t, who)
+    k = int(size)
+    ok = dz.dim() == 4 and w.dim() in (2, 4) and w.size(0) == dz.size(1) and w.numel() == w.size(0) * w.size(1) * k * k and w.dtype == dz.dtype == torch.float32
+    if ok and y is not None:
+        ok = y.dtype == torch.float32 and tuple(y.shape) == (dz.size(0), w.size(1), dz.size(2), dz.size(3))
+    if not ok:
+        raise ValueError("%s: expected float32 w [Cout,Cin,%d,%d], dz [B,Cout,H,W] and y [B,Cin,H,W], got %s, %s and %s"
+                         % (who, k, k, tuple(w.shape), tuple(dz.shape), None if y is None else tuple(y.shape)))
+    w, dz = w.contiguous(), dz.contiguous()
+    y = None if y is None else y.contiguous()
+    B, cout, cin, H, W = dz.size(0), dz.size(1), w.size(1), dz.size(2), dz.size(3)
+    shape = (B, cout, cin, H, W, k)
+    lib, dev = _ffi.lib(), dz.device
+    key = (dev.index,) + shape
+    ws = _dgrad_split_ws.get(key)
+    if ws is None:
+        nbytes = C.c_size_t()
+        _ffi.check(lib.rtod_conv_dgrad_split_workspace(*shape, C.byref(nbytes)))
+        if len(_dgrad_split_ws) > 48:
+            _dgrad_split_ws.clear()
+        ws = _dgrad_split_ws[key] = (torch.empty(nbytes.value, dtype=torch.uint8, device=dev), nbytes.value)
+    dx = torch.empty((B, cin, H, W), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        args = (C.c_void_p(w.data_ptr()), _scale_ptr(row_scale, cout, dev), C.c_void_p(dz.data_ptr()), C.c_void_p(y.data_ptr()) if y is not None else None,
+                float(slope)) + shape + (-1 if tile is None else int(tile), C.c_void_p(dx.data_ptr()), C.c_void_p(ws[0].data_ptr()), ws[1], _stream(dev))
+        _ffi.check(lib.rtod_conv_dgrad_split(*args) if phases is None else lib.rtod_conv_dgrad_split_phases(*args, int(phases)))
+    return dx
+
+
 def maxpool_grad_async(dz, x, slope=1.0, size=2, stride=2):
     """Enqueue rtod_maxpool_grad: ``dz`` on the pool's output map ([B,C,H//2,W//2] for ``stride`` 2, [B,C,H,W] for the clamped
     ``stride`` 1 pool) and ``x`` [B,C,H,W], the pool's stored input -> ``dx`` [B,C,H,W]: every window's gradient goes to its first
@@ -564,9 +629,13 @@ class DarknetTrainer:
     was skipped; OR-ed by every call, read it when you synchronise anyway), ``last_components`` (device float64 [6] of the
     last loss: total, xy, wh, obj, noobj, cls)."""
 
-    def __init__(self, model, resolution=None, num_classes=None, trainable="heads"):
+    def __init__(self, model, resolution=None, num_classes=None, trainable="heads", grad_precision="fp32"):
         if trainable not in ("heads", "blocks", "neck", "backbone", "full"):
             raise ValueError("DarknetTrainer: trainable must be 'heads', 'blocks', 'neck', 'backbone' or 'full', got %r" % (trainable,))
+        if grad_precision not in GRAD_PRECISIONS:
+            raise ValueError("DarknetTrainer: grad_precision must be 'fp32' or 'f16s3', got %r" % (grad_precision,))
+        self.grad_precision = grad_precision   # "f16s3": _walk sends the data gradient of every stride-1 3x3 conv with Cin % 32 == 0 through
+                                           # conv_dgrad_split_async; 1x1 convs (GRAD_SPLIT_SIZES), stride 2, thin convs, weight gradients, BatchNorm and joins stay exact
         self.trainable = trainable         # "blocks": feed_forward_through_model also trains the BatchNorm conv in front of each head conv;
                                            # "neck": every BatchNorm conv behind the backbone (Darknet.neck_layers);
                                            # "backbone": every conv the plan can train (Darknet.trainable_layers: all but layer 0 on YOLOv3)
@@ -930,7 +999,10 @@ class DarknetTrainer:
                     grads[i] = conv_wgrad_async(dz, read(i - 1), L.size, row_scale=scale, stride=L.stride)[0]
                 if i > 0:
                     hw = (layers[i - 1].hout, layers[i - 1].wout)
-                    send(i - 1, i, lambda y, slope, dz=dz, scale=scale, L=L, hw=hw: conv_dgrad_async(masters[i][0], dz, L.size, scale, y, slope, L.stride, hw), True)
+                    if self.grad_precision == "f16s3" and L.size in GRAD_SPLIT_SIZES and conv_dgrad_split_takes(L.cin, L.size, L.stride):
+                        send(i - 1, i, lambda y, slope, dz=dz, scale=scale, L=L: conv_dgrad_split_async(masters[i][0], dz, L.size, scale, y, slope), True)
+                    else:
+                        send(i - 1, i, lambda y, slope, dz=dz, scale=scale, L=L, hw=hw: conv_dgrad_async(masters[i][0], dz, L.size, scale, y, slope, L.stride, hw), True)
             elif L.type == "upsample":
                 g = gradient(i)
                 send(i - 1, i, lambda y, slope, g=g, L=L: upsample2x_grad_async(g, y, slope, "nearest" if L.nearest else "bilinear"), True)
