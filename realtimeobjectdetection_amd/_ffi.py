@@ -2,9 +2,17 @@
 
 The product path has no CPU fallback: if the shared library is missing or a call fails this
 module raises — it never routes to PyTorch ops or to the oracle.
+
+The one way from Python into the library (DESIGN.md "One way from Python into the library"): ``Ptr`` is the type of every data
+pointer in ``SIGNATURES``, so a call site hands over the tensor itself; ``enqueue`` is the call of every entry that takes a
+stream; ``workspace`` / ``cache`` hold every device buffer that is kept from call to call.
 """
 import ctypes as C
 import os
+from collections import OrderedDict
+
+import numpy as np
+import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, os.environ.get("RTOD_LIB", "librtod.so"))   # RTOD_LIB: A/B an alternative build (dev only)
@@ -40,6 +48,26 @@ class OptStep(C.Structure):
     _fields_ = [("kind", C.c_int), ("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("step", C.c_int)]
 
 
+class Ptr(C.c_void_p):
+    """The type of a ``void*`` / ``float*`` / ``double*`` DATA parameter (not a plan handle, not a stream): a call passes None
+    (NULL), a ``torch.Tensor`` (its ``data_ptr()``; it must be contiguous), a numpy array (``ctypes.data``; C-contiguous), a Python
+    int (that address: what ``Darknet.conv_scale`` and ``bn_stats_dev`` hand out) or anything ``c_void_p`` takes (a ``c_void_p``,
+    ``byref(...)``, a ctypes array).  The caller keeps the tensor alive, as it does for every kernel argument.  A refusal raised
+    here reaches the caller of a foreign function as ``ctypes.ArgumentError`` carrying this text."""
+
+    @classmethod
+    def from_param(cls, obj):
+        if isinstance(obj, torch.Tensor):
+            if not obj.is_contiguous():
+                raise ValueError("Ptr: a non-contiguous tensor %s (strides %s) cannot be passed as a pointer" % (tuple(obj.shape), obj.stride()))
+            return C.c_void_p(obj.data_ptr())
+        if isinstance(obj, np.ndarray):
+            if not obj.flags.c_contiguous:
+                raise ValueError("Ptr: a non-contiguous array %s cannot be passed as a pointer" % (obj.shape,))
+            return C.c_void_p(obj.ctypes.data)
+        return C.c_void_p.from_param(obj)
+
+
 # name -> (restype, argtypes): every symbol include/rtod.h declares
 SIGNATURES = {
     "rtod_version": (C.c_int, []),
@@ -51,95 +79,86 @@ SIGNATURES = {
     "rtod_plan_get_info": (C.c_int, [C.c_void_p, C.POINTER(PlanInfo)]),
     "rtod_plan_get_launch": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(LaunchInfo)]),
     "rtod_plan_describe": (C.c_int, [C.c_void_p, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
-    "rtod_plan_pack_weights": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "rtod_plan_pack_weights": (C.c_int, [C.c_void_p, Ptr, C.c_size_t, Ptr, C.c_size_t, C.POINTER(C.c_size_t)]),
     "rtod_conv_variant_name": (C.c_char_p, [C.c_int]),
     "rtod_conv_kernel_name": (C.c_int, [C.c_int, C.c_int, C.c_char_p, C.c_size_t]),
     "rtod_plan_launch_kernel_name": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.c_size_t]),
     "rtod_plan_set_precision": (C.c_int, [C.c_void_p, C.c_int]),
     "rtod_plan_set_option": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int]),
-    "rtod_plan_set_overflow_flag": (C.c_int, [C.c_void_p, C.c_void_p]),
-    "rtod_plan_autotune": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "rtod_plan_set_overflow_flag": (C.c_int, [C.c_void_p, Ptr]),
+    "rtod_plan_autotune": (C.c_int, [C.c_void_p, Ptr, C.c_int, Ptr, C.c_void_p]),
     "rtod_plan_get_tiles": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_int]),
     "rtod_plan_set_tiles": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_int]),
-    "rtod_plan_load_weights": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
-    "rtod_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
-    "rtod_forward_timed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]),
+    "rtod_plan_load_weights": (C.c_int, [C.c_void_p, Ptr, C.c_size_t]),
+    "rtod_forward": (C.c_int, [C.c_void_p, Ptr, C.c_int, Ptr, C.c_void_p]),
+    "rtod_forward_timed": (C.c_int, [C.c_void_p, Ptr, C.c_int, Ptr, C.c_void_p, C.POINTER(C.c_float)]),
     "rtod_plan_set_train_decode": (C.c_int, [C.c_void_p, C.c_int]),
-    "rtod_plan_finish_decode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "rtod_plan_finish_decode": (C.c_int, [C.c_void_p, Ptr, C.c_int, C.c_void_p]),
     "rtod_plan_set_keep_all_layers": (C.c_int, [C.c_void_p, C.c_int]),
     "rtod_plan_layer_shape": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
-    "rtod_plan_read_layer": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
-    "rtod_plan_bn_batch_stats": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "rtod_plan_read_layer": (C.c_int, [C.c_void_p, C.c_int, C.c_int, Ptr, C.c_void_p]),
+    "rtod_plan_bn_batch_stats": (C.c_int, [C.c_void_p, C.c_int, Ptr, Ptr, C.c_int, C.c_void_p]),
+    # (the two tables of running-statistics addresses are pointer arrays, not data)
     "rtod_plan_bn_update_running": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_void_p]),
-    "rtod_predict_transform": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
-    "rtod_confidence_mask": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_float, C.c_void_p, C.c_void_p]),
-    "rtod_bbox_iou": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
-    "rtod_prep_image": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
-    "rtod_prep_frames": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "rtod_predict_transform": (C.c_int, [Ptr, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_int, Ptr, C.c_void_p]),
+    "rtod_confidence_mask": (C.c_int, [Ptr, C.c_int64, C.c_int, C.c_float, Ptr, C.c_void_p]),
+    "rtod_bbox_iou": (C.c_int, [Ptr, Ptr, C.c_int, C.c_int, Ptr, C.c_void_p]),
+    "rtod_prep_image": (C.c_int, [Ptr, C.c_int, C.c_int, C.c_int, C.c_int, Ptr, C.c_void_p]),
+    "rtod_prep_frames": (C.c_int, [Ptr, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, Ptr, C.c_void_p]),
     "rtod_write_results_workspace": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
-    "rtod_nms_class_offset": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "rtod_write_results": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "rtod_nms_class_offset": (C.c_int, [Ptr, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_int, Ptr, C.c_int, Ptr, Ptr, C.c_size_t, C.c_void_p]),
+    "rtod_write_results": (C.c_int, [Ptr, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, Ptr, C.c_int, Ptr, Ptr, C.c_size_t, C.c_void_p]),
     "rtod_score_detections_limits": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "rtod_score_detections_workspace": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
-    "rtod_score_detections": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_uint32), C.c_float,
-                                        C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "rtod_score_detections": (C.c_int, [Ptr, Ptr, C.c_int, C.c_int, Ptr, Ptr, C.c_int, C.POINTER(C.c_uint32), C.c_float,
+                                        C.c_double, C.c_int, C.c_int, Ptr, Ptr, Ptr, Ptr, Ptr, Ptr, C.c_size_t, C.c_void_p]),
     "rtod_yolo_loss_workspace": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
-    "rtod_yolo_loss": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(YoloHead), C.c_int, C.c_void_p, C.c_void_p, C.c_float,
-                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "rtod_darknet_loss_dense": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "rtod_yolo_loss_grad": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(YoloHead), C.c_int, C.c_void_p, C.c_void_p, C.c_float,
-                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "rtod_yolo_loss": (C.c_int, [Ptr, C.c_int, C.c_int, C.c_int, C.POINTER(YoloHead), C.c_int, Ptr, Ptr, C.c_float,
+                                 Ptr, Ptr, Ptr, Ptr, Ptr, Ptr, Ptr, C.c_size_t, C.c_void_p]),
+    "rtod_darknet_loss_dense": (C.c_int, [Ptr, Ptr, Ptr, C.c_int64, C.c_int, Ptr, Ptr, C.c_size_t, C.c_void_p]),
+    "rtod_yolo_loss_grad": (C.c_int, [Ptr, C.c_int, C.c_int, C.c_int, C.POINTER(YoloHead), C.c_int, Ptr, Ptr, C.c_float,
+                                      Ptr, Ptr, Ptr, Ptr, Ptr, Ptr, C.c_size_t, C.c_void_p]),
     "rtod_plan_head_layers": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int]),
-    "rtod_plan_update_conv": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
-    "rtod_plan_step_conv": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(OptStep), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "rtod_plan_read_packed_weights": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "rtod_plan_update_conv": (C.c_int, [C.c_void_p, C.c_int, Ptr, Ptr]),
+    "rtod_plan_step_conv": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(OptStep)] + [Ptr] * 8 + [C.c_void_p]),
+    "rtod_plan_read_packed_weights": (C.c_int, [C.c_void_p, Ptr, C.c_size_t, C.POINTER(C.c_size_t)]),
     "rtod_plan_head_blocks": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int]),
-    "rtod_plan_conv_scale": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_void_p, C.c_int]),
-    "rtod_plan_update_conv_weight": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
-    "rtod_plan_step_conv_folded": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(OptStep), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rtod_plan_conv_scale": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), Ptr, C.c_int]),
+    "rtod_plan_update_conv_weight": (C.c_int, [C.c_void_p, C.c_int, Ptr]),
+    "rtod_plan_step_conv_folded": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(OptStep)] + [Ptr] * 4 + [C.c_void_p]),
     "rtod_conv_wgrad_workspace": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
-    "rtod_conv_wgrad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
-                                  C.c_void_p, C.c_size_t, C.c_void_p]),
+    "rtod_conv_wgrad": (C.c_int, [Ptr, Ptr, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, Ptr, Ptr, Ptr, Ptr, C.c_size_t, C.c_void_p]),
     "rtod_plan_neck_layers": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int]),
-    "rtod_conv_dgrad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                  C.c_void_p, C.c_void_p]),
+    "rtod_conv_dgrad": (C.c_int, [Ptr, Ptr, Ptr, Ptr, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, Ptr, C.c_void_p]),
     "rtod_plan_trainable_layers": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int]),
-    "rtod_grad_join": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_float, C.c_longlong, C.c_void_p, C.c_void_p]),
+    # (the contributions are a pointer array, not data)
+    "rtod_grad_join": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, Ptr, C.c_float, C.c_longlong, Ptr, C.c_void_p]),
     "rtod_plan_full_layers": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int]),
-    "rtod_maxpool_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "rtod_maxpool_grad": (C.c_int, [Ptr, Ptr, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, Ptr, C.c_void_p]),
     "rtod_conv_wgrad_thin_slices": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "rtod_conv_wgrad_thin_workspace": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
-    "rtod_conv_wgrad_thin": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
-                                       C.c_void_p, C.c_size_t, C.c_void_p]),
-    "rtod_conv_dgrad_thin": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                       C.c_void_p, C.c_void_p]),
-    "rtod_plan_read_bn_input": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "rtod_conv_wgrad_thin": (C.c_int, [Ptr, Ptr, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, Ptr, Ptr, Ptr, C.c_size_t, C.c_void_p]),
+    "rtod_conv_dgrad_thin": (C.c_int, [Ptr, Ptr, Ptr, Ptr, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, Ptr, C.c_void_p]),
+    "rtod_plan_read_bn_input": (C.c_int, [C.c_void_p, C.c_int, C.c_int, Ptr, C.c_void_p]),
     "rtod_plan_bn_stats_dev": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
-    "rtod_plan_step_conv_bn": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(OptStep)] + [C.c_void_p] * 13),
-    "rtod_plan_update_conv_bn": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rtod_plan_step_conv_bn": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(OptStep)] + [Ptr] * 12 + [C.c_void_p]),
+    "rtod_plan_update_conv_bn": (C.c_int, [C.c_void_p, C.c_int, Ptr, Ptr, Ptr]),
     "rtod_bn_grad_parts": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "rtod_bn_grad_workspace": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
-    "rtod_bn_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
-                               C.c_void_p, C.c_size_t, C.c_void_p]),
+    "rtod_bn_grad": (C.c_int, [Ptr, Ptr, Ptr, Ptr, Ptr, C.c_int, C.c_int, C.c_int, Ptr, Ptr, Ptr, Ptr, C.c_size_t, C.c_void_p]),
     "rtod_conv_dgrad_split_tiles": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int]),
     "rtod_conv_dgrad_split_workspace": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
-    "rtod_conv_dgrad_split": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                        C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "rtod_conv_dgrad_split_phases": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                               C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int]),
-}
-# ... and the entry points whose names hold a digit (the scan of the header for declared names reads lower-case letters and '_')
-SIGNATURES_DIGIT_NAMES = {
+    "rtod_conv_dgrad_split": (C.c_int, [Ptr, Ptr, Ptr, Ptr, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                        C.c_int, Ptr, Ptr, C.c_size_t, C.c_void_p]),
+    "rtod_conv_dgrad_split_phases": (C.c_int, [Ptr, Ptr, Ptr, Ptr, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                               C.c_int, Ptr, Ptr, C.c_size_t, C.c_void_p, C.c_int]),
     "rtod_conv1x1_wgrad_workspace": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
-    "rtod_conv1x1_wgrad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "rtod_conv1x1_dgrad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
-    "rtod_upsample2x_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
-    "rtod_conv_dgrad_s2": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                     C.c_void_p, C.c_void_p]),
+    "rtod_conv1x1_wgrad": (C.c_int, [Ptr, Ptr, C.c_int, C.c_int, C.c_int, C.c_int, Ptr, Ptr, Ptr, C.c_size_t, C.c_void_p]),
+    "rtod_conv1x1_dgrad": (C.c_int, [Ptr, Ptr, Ptr, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, Ptr, C.c_void_p]),
+    "rtod_upsample2x_grad": (C.c_int, [Ptr, Ptr, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, Ptr, C.c_void_p]),
+    "rtod_conv_dgrad_s2": (C.c_int, [Ptr, Ptr, Ptr, Ptr, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, Ptr, C.c_void_p]),
     "rtod_conv_wgrad_s2_workspace": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
-    "rtod_conv_wgrad_s2": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
-                                     C.c_void_p, C.c_size_t, C.c_void_p]),
+    "rtod_conv_wgrad_s2": (C.c_int, [Ptr, Ptr, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, Ptr, Ptr, Ptr, Ptr, C.c_size_t, C.c_void_p]),
 }
 
 _lib = None
@@ -155,12 +174,11 @@ def lib():
         # One HIP runtime per process: PyTorch-ROCm bundles its own libamdhip64.so.7 (torch/lib) and
         # librtod.so must bind to that same instance (same SONAME -> the loader reuses it), otherwise
         # /opt/rocm's copy is pulled in and the two runtimes do not share devices/streams/allocations.
-        import torch
         bundled = os.path.join(os.path.dirname(torch.__file__), "lib", "libamdhip64.so")
         if os.path.exists(bundled):
             C.CDLL(bundled, mode=C.RTLD_GLOBAL)
         l = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_DIGIT_NAMES.items()):
+        for name, (res, args) in SIGNATURES.items():
             fn = getattr(l, name)
             fn.restype = res
             fn.argtypes = args
@@ -177,3 +195,66 @@ def last_error() -> str:
 def check(rc: int):
     if rc != 0:
         raise RtodError(rc, last_error())
+
+
+def enqueue(entry, dev, *args, after=()):
+    """The call of every entry that takes a stream: on device ``dev``, ``lib().<entry>(*args, current stream of dev, *after)``;
+    a non-zero return raises ``RtodError``.  Nothing synchronises."""
+    with torch.cuda.device(dev):
+        rc = getattr(lib(), entry)(*args, torch.cuda.current_stream(dev).cuda_stream, *after)
+    if rc != 0:
+        raise RtodError(rc, last_error())
+
+
+CACHE_CAPACITY = 96     # entries.  One YOLOv3 backbone step at one batch size holds 23 weight-gradient, 16 BatchNorm-gradient and 5
+                        # split data-gradient keys beside the loss, score and NMS buffers: two batch sizes fit
+
+
+class LruCache:
+    """``get(key, build)``: the value ``build()`` made for ``key``, kept until ``capacity`` more recently used keys have pushed it
+    out.  A miss beyond the capacity drops the least recently used entry alone; nothing empties the cache as a whole."""
+
+    def __init__(self, capacity):
+        self.capacity = int(capacity)
+        self._items = OrderedDict()                                   # least recently used first
+
+    def get(self, key, build):
+        item = self._items.get(key)
+        if item is None:
+            item = self._items[key] = build()
+            if len(self._items) > self.capacity:
+                self._items.popitem(last=False)
+        else:
+            self._items.move_to_end(key)
+        return item
+
+    def keys(self):
+        """The keys, most recently used first."""
+        return list(reversed(self._items))
+
+    def __len__(self):
+        return len(self._items)
+
+    def __contains__(self, key):
+        return key in self._items
+
+
+cache = LruCache(CACHE_CAPACITY)    # the one cache of device buffers that outlive a call
+
+
+def stream_key(dev):
+    """``(device index, handle of the current stream of dev)``, the head of every key of ``cache``: a cached buffer is used only on
+    the stream it was allocated on.  That keeps two streams from sharing scratch memory, and it is what makes dropping an entry
+    whose kernel is still in flight safe: torch's allocator hands the memory out again in the order of that stream."""
+    return dev.index, torch.cuda.current_stream(dev).cuda_stream
+
+
+def workspace(entry, dev, *shape):
+    """``(byte tensor, nbytes)``: the scratch memory of ``entry`` (a name of ``SIGNATURES``) for ``shape`` on the current stream of
+    ``dev``, out of ``cache``; a miss asks ``<entry>_workspace(*shape, &nbytes)`` for the size.  The allocator aligns the tensor to
+    256 bytes; its length is ``nbytes`` rounded up to 16."""
+    def build():
+        n = C.c_size_t()
+        check(getattr(lib(), entry + "_workspace")(*shape, C.byref(n)))
+        return torch.empty((n.value + 15) // 16 * 16, dtype=torch.uint8, device=dev), n.value
+    return cache.get(stream_key(dev) + (entry, shape), build)

@@ -23,6 +23,7 @@ import json
 import os
 import warnings
 import weakref
+from collections import namedtuple
 from contextlib import contextmanager
 
 import numpy as np
@@ -35,6 +36,28 @@ from .cfg import parse_cfg, build_ir
 
 _OVERFLOW_MSG = ("Darknet (precision f16s3 / f16): an activation reached the split-f16 range limit (|x| >= 8188) and was saturated; "
                  "the results of that forward are not valid. Use precision='fp32' (exact MFMA kernels) for these weights.")
+
+
+# The three kinds of trained conv, stated once: what ``Darknet._step`` / ``_update`` / ``sync_stepped_parameters`` and train.py read.
+#   bn      the layer has BatchNorm (what ``_trained_conv`` holds it to)
+#   params  its trained parameters, by the names the trainer uses; ``attrs``: the (module, attribute) each lives in
+#   step, update   the two doors of the kind; their C entries are "rtod_plan_" + the door's name.  The update entry takes the new
+#           values in the order of ``params``
+#   order   the order in which the step door and its C entry take masters ("name") and gradients ("d.name"); the moments follow,
+#           (exp_avg, exp_avg_sq) per parameter in the order of ``params``, NULL for SGD
+#   moments, takes, update_got   the kind's own words in the error texts
+ConvKind = namedtuple("ConvKind", "bn params attrs step update order moments takes update_got")
+CONV_KINDS = {
+    "head": ConvKind(False, ("weight", "bias"), (("conv", "weight"), ("conv", "bias")), "step_conv", "update_conv",
+                     ("weight", "bias", "d.weight", "d.bias"), "(exp_avg_w, exp_avg_sq_w, exp_avg_b, exp_avg_sq_b)",
+                     "weight %(weight)s and bias %(channels)s", True),
+    "folded": ConvKind(True, ("weight",), (("conv", "weight"),), "step_conv_folded", "update_conv_weight",
+                       ("weight", "d.weight"), "(exp_avg, exp_avg_sq)", "weight %(weight)s", True),
+    "bn": ConvKind(True, ("weight", "gamma", "beta"), (("conv", "weight"), ("bn", "weight"), ("bn", "bias")), "step_conv_bn", "update_conv_bn",
+                   ("weight", "d.weight", "gamma", "beta", "d.gamma", "d.beta"),
+                   "(exp_avg_w, exp_avg_sq_w, exp_avg_gamma, exp_avg_sq_gamma, exp_avg_beta, exp_avg_sq_beta)",
+                   "weight %(weight)s, gamma and beta [%(cout)d]", False),
+}
 
 
 def take_pending_overflow(prediction):
@@ -130,7 +153,7 @@ class Darknet(nn.Module):
         self._stats_version = 0             # running_mean / running_var updates of training-mode forwards (eval plans fold them)
         self._plan_weights_version = -1
         self._info = None
-        self._stepped = {}                  # step_conv: {conv layer: (weight master, bias master)} the module's parameters lag behind
+        self._stepped = {}                  # _step: {conv layer: (kind, its masters in the order of the kind's params)} the module's parameters lag behind
 
     # ------------------------------------------------------------------ reference getters
     def get_blocks(self) -> list:
@@ -263,10 +286,9 @@ class Darknet(nn.Module):
         """Replace the weights of one conv without BatchNorm: ``weight`` [Cout,Cin,k,k] and ``bias`` [Cout] go into the module's
         parameters and, when a plan with current weights is loaded, into that plan through rtod_plan_update_conv, which re-packs
         this conv alone (the bits a full re-pack gives) — the next forward does not re-pack the network.  Synchronises."""
-        self._update("update_conv", layer, weight, bias, folded=False)
+        self._update("head", layer, (weight, bias))
 
-    # ---- what the head entries (a conv without BatchNorm: weight and bias) and the block entries (a conv with frozen BatchNorm:
-    # weight alone, ``folded``) share
+    # ---- what the six doors of the three kinds of trained conv (CONV_KINDS) share
     def _conv_bn(self, layer):
         """``(conv, batch_norm)`` modules of a layer, None for what it does not have (or for a layer out of range)."""
         conv = bn = None
@@ -296,50 +318,54 @@ class Darknet(nn.Module):
             if not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != torch.float32 or not t.is_contiguous():
                 raise ValueError("Darknet.%s: every tensor must be a contiguous float32 tensor on %s" % (who, dev))
 
-    def _update(self, who, layer, weight, bias, folded):
+    def _params(self, kind, layer):
+        """The module parameters of a conv of ``kind``, in the order of the kind's ``params``."""
+        mods = dict(zip(("conv", "bn"), self._conv_bn(layer)))
+        return [getattr(mods[m], a) for m, a in CONV_KINDS[kind].attrs]
+
+    @staticmethod
+    def _takes(K, conv):
+        return K.takes % {"weight": tuple(conv.weight.shape), "channels": (conv.out_channels,), "cout": conv.out_channels}
+
+    def _update(self, kind, layer, values):
         """The parameters of one conv replaced in the module and, when a plan with current weights is loaded, re-packed there alone."""
+        K = CONV_KINDS[kind]
         layer = int(layer)
-        conv = self._trained_conv(who, layer, with_bn=folded)
-        new = [("weight", conv.weight, weight)] + ([("bias", conv.bias, bias)] if not folded else [])
-        new = [(name, p, torch.as_tensor(t).detach().to(torch.float32)) for name, p, t in new]
-        if any(tuple(t.shape) != tuple(p.shape) for _, p, t in new):
-            raise ValueError("Darknet.%s: layer %d takes %s, got %s" % (who, layer, " and ".join("%s %s" % (name, tuple(p.shape)) for name, p, _ in new),
-                                                                      " and ".join(str(tuple(t.shape)) for _, _, t in new)))
+        conv = self._trained_conv(K.update, layer, K.bn)
+        new = [(p, torch.as_tensor(t).detach().to(torch.float32)) for p, t in zip(self._params(kind, layer), values)]
+        if any(tuple(t.shape) != tuple(p.shape) for p, t in new):
+            got = ", got %s" % " and ".join(str(tuple(t.shape)) for _, t in new) if K.update_got else ""
+            raise ValueError("Darknet.%s: layer %d takes %s%s" % (K.update, layer, self._takes(K, conv), got))
         with torch.no_grad():
-            for _, p, t in new:
+            for p, t in new:
                 p.copy_(t)
         self._stepped.pop(layer, None)                            # the parameters are current again
         if self._plan_is_current():
-            host = [np.ascontiguousarray(t.cpu().numpy()) for _, _, t in new]
-            fn = _ffi.lib().rtod_plan_update_conv_weight if folded else _ffi.lib().rtod_plan_update_conv
+            host = [np.ascontiguousarray(t.cpu().numpy()) for _, t in new]
             with torch.cuda.device(self._plan_key[2]):
-                _ffi.check(fn(self._plan, layer, *[h.ctypes.data_as(C.c_void_p) for h in host]))
+                _ffi.check(getattr(_ffi.lib(), "rtod_plan_" + K.update)(self._plan, layer, *host))
         # the plan's weight version stays current: parameters and plan agree again (a plan that was stale before still re-packs)
 
-    def _step(self, who, layer, opt, weight, bias, dw, db, moments, folded):
-        """One optimiser step of one conv on the current stream: masters and moments in place, the conv's block of the image re-packed."""
-        layer = int(layer)
+    def _step(self, kind, layer, opt, operands, moments):
+        """One optimiser step of one conv on the current stream: masters and moments in place, the conv's block of the image
+        re-packed.  ``operands``: masters and gradients in the kind's ``order``."""
+        K = CONV_KINDS[kind]
+        who, layer = K.step, int(layer)
         if not self._plan_is_current():
             raise RuntimeError("Darknet.%s: no loaded plan holds the current parameters; run a forward first" % who)
         dev = torch.device("cuda", self._plan_key[2])
-        n_mom = 2 if folded else 4
+        n_mom = 2 * len(K.params)
         if moments is not None and len(moments) != n_mom:
-            raise ValueError("Darknet.%s: moments = %s" % (who, "(exp_avg, exp_avg_sq)" if folded else "(exp_avg_w, exp_avg_sq_w, exp_avg_b, exp_avg_sq_b)"))
+            raise ValueError("Darknet.%s: moments = %s" % (who, K.moments))
         mom = list(moments) if moments is not None else []
-        like_w, like_b = [weight, dw] + mom[:2], ([] if folded else [bias, db] + mom[2:])
-        tensors = like_w if folded else [weight, bias, dw, db] + mom                    # in the order the entry takes them
-        self._need_f32_on(who, dev, tensors)
-        conv = self._trained_conv(who, layer, folded)
-        if (tuple(weight.shape) != tuple(conv.weight.shape) or any(t.numel() != weight.numel() for t in like_w)
-                or (not folded and (tuple(bias.shape) != tuple(conv.bias.shape) or any(t.numel() != bias.numel() for t in like_b)))):
-            raise ValueError("Darknet.%s: layer %d takes weight %s%s, and gradients and moments of their sizes"
-                             % (who, layer, tuple(conv.weight.shape), "" if folded else " and bias %s" % (tuple(conv.bias.shape),)))
-        opt = self._opt_step(opt)
-        args = [C.c_void_p(t.data_ptr()) for t in tensors] + [None] * (n_mom - len(mom))
-        fn = _ffi.lib().rtod_plan_step_conv_folded if folded else _ffi.lib().rtod_plan_step_conv
-        with torch.cuda.device(dev):
-            _ffi.check(fn(self._plan, layer, C.byref(opt), *args, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
-        self._stepped[layer] = (weight, bias)
+        self._need_f32_on(who, dev, list(operands) + mom)
+        conv = self._trained_conv(who, layer, K.bn)
+        named = dict(zip(K.order, operands))
+        for j, (name, p) in enumerate(zip(K.params, self._params(kind, layer))):
+            if tuple(named[name].shape) != tuple(p.shape) or any(t.numel() != p.numel() for t in [named["d." + name]] + mom[2 * j:2 * j + 2]):
+                raise ValueError("Darknet.%s: layer %d takes %s, and gradients and moments of their sizes" % (who, layer, self._takes(K, conv)))
+        _ffi.enqueue("rtod_plan_" + who, dev, self._plan, layer, C.byref(self._opt_step(opt)), *operands, *mom, *[None] * (n_mom - len(mom)))
+        self._stepped[layer] = (kind, [named[name] for name in K.params])
 
     def _plan_is_current(self) -> bool:
         """A plan exists and holds the packed image of the parameters as they are (no re-pack is due at the next forward)."""
@@ -356,22 +382,18 @@ class Darknet(nn.Module):
         NOT touched and lag behind from here on; ``weight_stream()``, ``state_dict()``, ``invalidate_weights()`` and every
         re-pack bring them up to date from these masters first (``sync_stepped_parameters``), reading ``conv.weight`` directly
         does not."""
-        self._step("step_conv", layer, opt, weight, bias, dw, db, moments, folded=False)
+        self._step("head", layer, opt, (weight, bias, dw, db), moments)
 
     def sync_stepped_parameters(self) -> None:
-        """Copy the masters of every conv ``step_conv`` has stepped into the module's ``conv.weight`` / ``conv.bias`` (waits for the
-        steps in flight).  The plan's image already holds them, so it stays valid: no re-pack follows."""
+        """Copy the masters of every conv a step door has stepped into the module's parameters (``conv.weight`` / ``conv.bias``, for
+        ``step_conv_bn`` ``bn.weight`` / ``bn.bias``; waits for the steps in flight).  The plan's image already holds them, so it
+        stays valid: no re-pack follows."""
         if not self._stepped:
             return
         with torch.no_grad():
-            for layer, (w, b, *gamma_beta) in self._stepped.items():
-                conv, bn = self._conv_bn(layer)
-                conv.weight.copy_(w)
-                if b is not None:                                 # (a block conv has BatchNorm and no bias: weight-only entry)
-                    conv.bias.copy_(b)
-                if gamma_beta:                                    # (step_conv_bn: BatchNorm on batch statistics trains gamma and beta too)
-                    bn.weight.copy_(gamma_beta[0])
-                    bn.bias.copy_(gamma_beta[1])
+            for layer, (kind, masters) in self._stepped.items():
+                for p, t in zip(self._params(kind, layer), masters):
+                    p.copy_(t)
         self._stepped.clear()
 
     # ------------------------------------------------------------------ training under batch statistics (options keep_bn_inputs)
@@ -387,9 +409,7 @@ class Darknet(nn.Module):
         _ffi.check(_ffi.lib().rtod_plan_layer_shape(self._plan, int(layer), C.byref(c), C.byref(h), C.byref(w)))
         dev = torch.device("cuda", self._plan_key[2])
         out = torch.empty((int(batch), c.value, h.value, w.value), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            _ffi.check(_ffi.lib().rtod_plan_read_bn_input(self._plan, int(layer), int(batch), C.c_void_p(out.data_ptr()),
-                                                          C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        _ffi.enqueue("rtod_plan_read_bn_input", dev, self._plan, int(layer), int(batch), out)
         return out
 
     def bn_stats_dev(self, layer: int):
@@ -409,43 +429,13 @@ class Darknet(nn.Module):
         ``dbeta`` and, for Adam, ``moments = (exp_avg, exp_avg_sq)`` of the weight, of gamma, of beta: six tensors.  One kernel
         re-packs the unfolded conv and the [beta, gamma] block of the plan's image in place.  Nothing synchronises, nothing is
         allocated.  The module's parameters lag behind as after ``step_conv``."""
-        layer = int(layer)
-        if not self._plan_is_current():
-            raise RuntimeError("Darknet.step_conv_bn: no loaded plan holds the current parameters; run a forward first")
-        dev = torch.device("cuda", self._plan_key[2])
-        if moments is not None and len(moments) != 6:
-            raise ValueError("Darknet.step_conv_bn: moments = (exp_avg_w, exp_avg_sq_w, exp_avg_gamma, exp_avg_sq_gamma, exp_avg_beta, exp_avg_sq_beta)")
-        mom = list(moments) if moments is not None else []
-        tensors = [weight, dw, gamma, beta, dgamma, dbeta] + mom
-        self._need_f32_on("step_conv_bn", dev, tensors)
-        conv = self._trained_conv("step_conv_bn", layer, with_bn=True)
-        like_w, like_c = [weight, dw] + mom[:2], [gamma, beta, dgamma, dbeta] + mom[2:]
-        if tuple(weight.shape) != tuple(conv.weight.shape) or any(t.numel() != weight.numel() for t in like_w) or any(t.numel() != conv.out_channels for t in like_c):
-            raise ValueError("Darknet.step_conv_bn: layer %d takes weight %s, gamma and beta [%d], and gradients and moments of their sizes"
-                             % (layer, tuple(conv.weight.shape), conv.out_channels))
-        args = [C.c_void_p(t.data_ptr()) for t in tensors] + [None] * (6 - len(mom))
-        with torch.cuda.device(dev):
-            _ffi.check(_ffi.lib().rtod_plan_step_conv_bn(self._plan, layer, C.byref(self._opt_step(opt)), *args, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
-        self._stepped[layer] = (weight, None, gamma, beta)
+        self._step("bn", layer, opt, (weight, dw, gamma, beta, dgamma, dbeta), moments)
 
     def update_conv_bn(self, layer: int, weight, gamma, beta) -> None:
         """``update_conv_weight`` for a conv whose BatchNorm runs on batch statistics: ``weight`` [Cout,Cin,k,k], ``gamma`` and
         ``beta`` [Cout] go into ``conv.weight``, ``bn.weight`` and ``bn.bias`` and, when a plan with current weights is loaded,
         into that plan through rtod_plan_update_conv_bn, which re-packs this conv alone.  Synchronises."""
-        layer = int(layer)
-        conv = self._trained_conv("update_conv_bn", layer, with_bn=True)
-        bn = self._conv_bn(layer)[1]
-        new = [(p, torch.as_tensor(t).detach().to(torch.float32)) for p, t in ((conv.weight, weight), (bn.weight, gamma), (bn.bias, beta))]
-        if any(tuple(t.shape) != tuple(p.shape) for p, t in new):
-            raise ValueError("Darknet.update_conv_bn: layer %d takes weight %s, gamma and beta [%d]" % (layer, tuple(conv.weight.shape), conv.out_channels))
-        with torch.no_grad():
-            for p, t in new:
-                p.copy_(t)
-        self._stepped.pop(layer, None)
-        if self._plan_is_current():
-            host = [np.ascontiguousarray(t.cpu().numpy()) for _, t in new]
-            with torch.cuda.device(self._plan_key[2]):
-                _ffi.check(_ffi.lib().rtod_plan_update_conv_bn(self._plan, layer, *[h.ctypes.data_as(C.c_void_p) for h in host]))
+        self._update("bn", layer, (weight, gamma, beta))
 
     # ------------------------------------------------------------------ detection blocks (the BatchNorm conv a head conv reads)
     def _plan_list(self, who, entry, columns) -> list:
@@ -502,14 +492,14 @@ class Darknet(nn.Module):
         conv = self._trained_conv("conv_scale", layer, with_bn=True)
         host = np.zeros(conv.out_channels, np.float64)
         dev = C.c_void_p()
-        _ffi.check(_ffi.lib().rtod_plan_conv_scale(self._plan, int(layer), C.byref(dev), host.ctypes.data_as(C.c_void_p), host.size))
+        _ffi.check(_ffi.lib().rtod_plan_conv_scale(self._plan, int(layer), C.byref(dev), host, host.size))
         return dev.value, host
 
     def update_conv_weight(self, layer: int, weight) -> None:
         """``update_conv`` for a detection block conv, BatchNorm untouched: ``weight`` [Cout,Cin,k,k] goes into the module's
         ``conv.weight`` and, when a plan with current weights is loaded, into that plan through rtod_plan_update_conv_weight,
         which re-packs this conv alone (the bits a full re-pack gives).  Synchronises."""
-        self._update("update_conv_weight", layer, weight, None, folded=True)
+        self._update("folded", layer, (weight,))
 
     def step_conv_folded(self, layer: int, opt, weight, dw, moments=None) -> None:
         """``step_conv`` for a detection block conv (rtod_plan_step_conv_folded): ``weight`` [Cout,Cin,k,k] is the caller's RAW
@@ -518,7 +508,7 @@ class Darknet(nn.Module):
         frozen BatchNorm scale and re-packs the conv's block of the plan's weight image in place.  Nothing synchronises, nothing
         is allocated.  Needs a current plan with options ``keep_block_inputs``, ``keep_neck_activations`` or ``keep_backbone_activations``
         (the widest of them decides which convs are accepted).  ``conv.weight`` lags behind as after ``step_conv``."""
-        self._step("step_conv_folded", layer, opt, weight, None, dw, None, moments, folded=True)
+        self._step("folded", layer, opt, (weight, dw), moments)
 
     def packed_weights(self) -> np.ndarray:
         """The plan's packed weight image as it is on the device now, as uint32 words (rtod_plan_read_packed_weights; tests and
@@ -529,7 +519,7 @@ class Darknet(nn.Module):
         _ffi.check(_ffi.lib().rtod_plan_read_packed_weights(self._plan, None, 0, C.byref(need)))
         out = np.zeros(need.value, np.float32)
         with torch.cuda.device(self._plan_key[2]):
-            _ffi.check(_ffi.lib().rtod_plan_read_packed_weights(self._plan, out.ctypes.data_as(C.c_void_p), out.size, None))
+            _ffi.check(_ffi.lib().rtod_plan_read_packed_weights(self._plan, out, out.size, None))
         return out.view(np.uint32)
 
     # ------------------------------------------------------------------ plan
@@ -597,7 +587,7 @@ class Darknet(nn.Module):
                 _ffi.check(lib.rtod_plan_set_option(self._plan, name.encode(), int(value)))
             if self._ovf is None or self._ovf.device != device:
                 self._ovf = torch.zeros(1, dtype=torch.int32, device=device)
-            _ffi.check(lib.rtod_plan_set_overflow_flag(self._plan, C.c_void_p(self._ovf.data_ptr())))
+            _ffi.check(lib.rtod_plan_set_overflow_flag(self._plan, self._ovf))
             # "auto": the split-f16 kernels when the cfg supports them (yolov3 does; a cfg with a conv after layer 0 whose
             # Cin % 32 != 0 does not — yolov3-tiny's 16-channel layer 2 does with options = {"narrow_cin": 1}, already set
             # above), else the exact-fp32 MFMA kernels.  Both are HIP paths.
@@ -624,7 +614,7 @@ class Darknet(nn.Module):
         if self._plan_weights_version != version:
             w = np.ascontiguousarray(self.weight_stream())
             with torch.cuda.device(device):
-                _ffi.check(lib.rtod_plan_load_weights(self._plan, w.ctypes.data_as(C.c_void_p), w.size))
+                _ffi.check(lib.rtod_plan_load_weights(self._plan, w, w.size))
             self._plan_weights_version = version
         return self._info
 
@@ -690,20 +680,17 @@ class Darknet(nn.Module):
         info = self.prepare(max_batch, x.device)
         x = x.contiguous()
         out = torch.empty((B, info.total_rows, info.attrs), dtype=torch.float32, device=x.device)
-        stream = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
-        with torch.cuda.device(x.device):
-            _ffi.check(lib.rtod_plan_set_train_decode(self._plan, 1 if self.TRAIN else 0))
-            if _launch_ms is None:
-                if self.autotune and self.active_precision in ("f16s3", "f16") and B not in self._tuned:
-                    # first forward of a batch size: measures the tile variants (synchronises); rtod_forward itself never does
-                    _ffi.check(lib.rtod_plan_autotune(self._plan, C.c_void_p(x.data_ptr()), B, C.c_void_p(out.data_ptr()), stream))
-                    self._tuned.add(B)
-                else:
-                    _ffi.check(lib.rtod_forward(self._plan, C.c_void_p(x.data_ptr()), B, C.c_void_p(out.data_ptr()), stream))
-            else:
-                _ffi.check(lib.rtod_forward_timed(self._plan, C.c_void_p(x.data_ptr()), B, C.c_void_p(out.data_ptr()), stream, _launch_ms))
+        _ffi.check(lib.rtod_plan_set_train_decode(self._plan, 1 if self.TRAIN else 0))      # (host state of the plan)
+        if _launch_ms is not None:
+            _ffi.enqueue("rtod_forward_timed", x.device, self._plan, x, B, out, after=(_launch_ms,))
+        elif self.autotune and self.active_precision in ("f16s3", "f16") and B not in self._tuned:
+            # first forward of a batch size: measures the tile variants (synchronises); rtod_forward itself never does
+            _ffi.enqueue("rtod_plan_autotune", x.device, self._plan, x, B, out)
+            self._tuned.add(B)
+        else:
+            _ffi.enqueue("rtod_forward", x.device, self._plan, x, B, out)
         if self.training and not self.bn_running_stats_in_train and self.update_running_stats and _launch_ms is None:
-            self._update_running_stats(B, stream)
+            self._update_running_stats(B)
         # attributes the reference sets as a side effect of forward (src/darknet.py:239-243, 260)
         anchors = []
         for m, blk in zip(self.module_list, self.blocks[1:]):
@@ -725,12 +712,11 @@ class Darknet(nn.Module):
                 out._rtod_forward = (weakref.ref(self), self._forward_seq)
         return out
 
-    def _update_running_stats(self, batch, stream):
+    def _update_running_stats(self, batch):
         """Training-mode side effect of nn.BatchNorm2d (momentum 0.1): running_mean / running_var move towards the batch's mean
         and UNBIASED variance, num_batches_tracked counts up — the reference mutates them on every forward.
         One kernel launch for all BatchNorm layers (rtod_plan_bn_update_running), no host round trip: the module buffers are
         updated in place on the device, behind the forward on the same stream."""
-        lib = _ffi.lib()
         bns = [sub for m in self.module_list for sub in m.children() if isinstance(sub, nn.BatchNorm2d)]
         if not bns:
             return
@@ -748,8 +734,8 @@ class Darknet(nn.Module):
         n = len(bns)
         rm = (C.c_void_p * n)(*[bn.running_mean.data_ptr() for bn in bns])
         rv = (C.c_void_p * n)(*[bn.running_var.data_ptr() for bn in bns])
+        _ffi.enqueue("rtod_plan_bn_update_running", dev, self._plan, int(batch), rm, rv, n, float(mom.pop()))
         with torch.cuda.device(dev):
-            _ffi.check(lib.rtod_plan_bn_update_running(self._plan, int(batch), rm, rv, n, float(mom.pop()), stream))
             torch._foreach_add_([bn.num_batches_tracked for bn in bns], 1)
         self._stats_version += 1                # an eval-mode plan built later folds the updated statistics
 
@@ -812,14 +798,11 @@ class Darknet(nn.Module):
 
     def read_layer(self, layer: int, batch: int) -> torch.Tensor:
         """Dense NCHW copy of a materialised layer output of the last forward (tests/debug)."""
-        lib = _ffi.lib()
         c, h, w = C.c_int(), C.c_int(), C.c_int()
-        _ffi.check(lib.rtod_plan_layer_shape(self._plan, layer, C.byref(c), C.byref(h), C.byref(w)))
+        _ffi.check(_ffi.lib().rtod_plan_layer_shape(self._plan, layer, C.byref(c), C.byref(h), C.byref(w)))
         dev = torch.device("cuda", self._plan_key[2])
         out = torch.empty((batch, c.value, h.value, w.value), dtype=torch.float32, device=dev)
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        with torch.cuda.device(dev):
-            _ffi.check(lib.rtod_plan_read_layer(self._plan, layer, batch, C.c_void_p(out.data_ptr()), stream))
+        _ffi.enqueue("rtod_plan_read_layer", dev, self._plan, layer, batch, out)
         return out
 
     @contextmanager
@@ -843,7 +826,5 @@ class Darknet(nn.Module):
         if p.dtype != torch.float32 or p.dim() != 3 or not p.is_contiguous() or tuple(p.shape[1:]) != (self._info.total_rows, self._info.attrs):
             raise ValueError("Darknet.finish_decode: expected the contiguous float32 [B,%d,%d] output of forward, got %s %s"
                              % (self._info.total_rows, self._info.attrs, p.dtype, tuple(p.shape)))
-        with torch.cuda.device(p.device):
-            stream = C.c_void_p(torch.cuda.current_stream(p.device).cuda_stream)
-            _ffi.check(_ffi.lib().rtod_plan_finish_decode(self._plan, C.c_void_p(p.data_ptr()), p.size(0), stream))
+        _ffi.enqueue("rtod_plan_finish_decode", p.device, self._plan, p, p.size(0))
         return p

@@ -63,21 +63,12 @@ import torch
 
 from . import _ffi
 from .cfg import build_ir
-from .util import _need_cuda, _stream, prep_frames
-
-_ws_cache = {}
+from .darknet import CONV_KINDS
+from .util import _need_cuda, prep_frames
 
 
 def _workspace(dev, batch, n_rows):
-    key = (dev.index, batch, n_rows)
-    ws = _ws_cache.get(key)
-    if ws is None:
-        nbytes = C.c_size_t()
-        _ffi.check(_ffi.lib().rtod_yolo_loss_workspace(batch, n_rows, C.byref(nbytes)))
-        if len(_ws_cache) > 16:
-            _ws_cache.clear()
-        ws = _ws_cache[key] = (torch.empty((nbytes.value + 7) // 8, dtype=torch.float64, device=dev), nbytes.value)
-    return ws
+    return _ffi.workspace("rtod_yolo_loss", dev, batch, n_rows)
 
 
 def make_heads(heads):
@@ -139,12 +130,8 @@ def yolo_loss_async(pred, bndbox, heads, num_class, min_box_size=24, dense=False
     if dense:
         out["target"] = torch.empty((B, N, attrs), dtype=torch.float32, device=dev)
         out["mask"] = torch.empty((B, N), dtype=torch.uint8, device=dev)
-    ptr = lambda k: C.c_void_p(out[k].data_ptr()) if k in out else None
-    with torch.cuda.device(dev):
-        _ffi.check(_ffi.lib().rtod_yolo_loss(
-            C.c_void_p(pred.data_ptr()), B, N, int(num_class), make_heads(heads), len(heads), C.c_void_p(boxes.data_ptr()), C.c_void_p(offs.data_ptr()),
-            float(min_box_size), ptr("components"), ptr("per_image"), ptr("target"), ptr("mask"), ptr("n_obj"), ptr("status"),
-            C.c_void_p(ws.data_ptr()), nbytes, _stream(dev)))
+    _ffi.enqueue("rtod_yolo_loss", dev, pred, B, N, int(num_class), make_heads(heads), len(heads), boxes, offs, float(min_box_size),
+                 out["components"], out.get("per_image"), out.get("target"), out.get("mask"), out["n_obj"], out["status"], ws, nbytes)
     return out
 
 
@@ -157,12 +144,8 @@ def yolo_loss_grad_async(pred, bndbox, heads, num_class, min_box_size=24, grad_p
     out["grad_raw_flat"] = torch.empty(B * N * attrs, dtype=torch.float32, device=dev)
     if grad_pred:
         out["grad_pred"] = torch.empty((B, N, attrs), dtype=torch.float32, device=dev)
-    ptr = lambda k: C.c_void_p(out[k].data_ptr()) if k in out else None
-    with torch.cuda.device(dev):
-        _ffi.check(_ffi.lib().rtod_yolo_loss_grad(
-            C.c_void_p(pred.data_ptr()), B, N, int(num_class), make_heads(heads), len(heads), C.c_void_p(boxes.data_ptr()), C.c_void_p(offs.data_ptr()),
-            float(min_box_size), ptr("grad_raw_flat"), ptr("grad_pred"), ptr("components"), ptr("n_obj"), ptr("status"),
-            C.c_void_p(ws.data_ptr()), nbytes, _stream(dev)))
+    _ffi.enqueue("rtod_yolo_loss_grad", dev, pred, B, N, int(num_class), make_heads(heads), len(heads), boxes, offs, float(min_box_size),
+                 out["grad_raw_flat"], out.get("grad_pred"), out["components"], out["n_obj"], out["status"], ws, nbytes)
     views, off = [], 0
     for gh, gw, _, anchors in heads:                                  # head h at float offset B * sum of the earlier heads' A * attrs * GH * GW
         n = B * len(anchors) * attrs * gh * gw
@@ -172,7 +155,6 @@ def yolo_loss_grad_async(pred, bndbox, heads, num_class, min_box_size=24, grad_p
     return out
 
 
-_wgrad_ws = {}
 # (no size, stride, thin) -> the C entry of _wgrad (its workspace entry: the name + "_workspace"), whether it takes a row scale, a db
 _WGRAD_ENTRIES = {(True, 1, False): ("rtod_conv1x1_wgrad", False, True), (False, 1, False): ("rtod_conv_wgrad", True, True),
                   (False, 2, False): ("rtod_conv_wgrad_s2", True, True), (False, 1, True): ("rtod_conv_wgrad_thin", True, False)}
@@ -197,25 +179,15 @@ def _wgrad(who, dz, x, size, row_scale, bias, stride=1, thin=False):
     dz, x = dz.contiguous(), x.contiguous()
     B, cout, cin, H, W = dz.size(0), dz.size(1), x.size(1), x.size(2), x.size(3)
     shape = (B, cout, cin, H * W) if size is None else (B, cout, cin, H, W, int(size))
-    lib, dev = _ffi.lib(), dz.device
+    dev = dz.device
     name, takes_scale, takes_db = _WGRAD_ENTRIES.get((size is None, stride, bool(thin)), (None, False, False))
     if thin and (name is None or bias):
         raise ValueError("%s: the thin entry takes a size, stride 1 and no bias gradient" % who)
-    key = (dev.index, stride, thin) + shape
-    ws = _wgrad_ws.get(key)
-    if ws is None:
-        nbytes = C.c_size_t()
-        _ffi.check(getattr(lib, name + "_workspace")(*shape, C.byref(nbytes)))
-        if len(_wgrad_ws) > 16:
-            _wgrad_ws.clear()
-        ws = _wgrad_ws[key] = (torch.empty((nbytes.value + 7) // 8, dtype=torch.float64, device=dev), nbytes.value)
+    scale = (_scale_ptr(row_scale, cout, dev),) if takes_scale else ()
     k = 1 if size is None else int(size)
     dw = torch.empty((cout, cin, k, k), dtype=torch.float32, device=dev)
     db = torch.empty(cout, dtype=torch.float32, device=dev) if bias else None
-    args = (C.c_void_p(dz.data_ptr()), C.c_void_p(x.data_ptr())) + shape + ((_scale_ptr(row_scale, cout, dev),) if takes_scale else ()) + (C.c_void_p(dw.data_ptr()),)
-    args += ((C.c_void_p(db.data_ptr()) if bias else None,) if takes_db else ()) + (C.c_void_p(ws[0].data_ptr()), ws[1], _stream(dev))
-    with torch.cuda.device(dev):
-        _ffi.check(getattr(lib, name)(*args))
+    _ffi.enqueue(name, dev, dz, x, *shape, *scale, dw, *((db,) if takes_db else ()), *_ffi.workspace(name, dev, *shape))
     return dw, db
 
 
@@ -226,15 +198,13 @@ def conv1x1_wgrad_async(dz, x, bias=True):
 
 
 def _scale_ptr(row_scale, cout, dev):
-    """``row_scale`` of ``conv_wgrad_async`` as a pointer: None, a float64 device tensor [Cout], or an integer device address
-    (what ``Darknet.conv_scale`` hands out)."""
-    if row_scale is None:
-        return None
+    """``row_scale`` of ``conv_wgrad_async`` as a pointer argument: None, a float64 device tensor [Cout] (checked), or an integer
+    device address (what ``Darknet.conv_scale`` hands out)."""
     if isinstance(row_scale, torch.Tensor):
         if row_scale.device != dev or row_scale.dtype != torch.float64 or row_scale.numel() != cout or not row_scale.is_contiguous():
             raise ValueError("conv_wgrad: row_scale must be a contiguous float64 tensor [%d] on %s" % (cout, dev))
-        return C.c_void_p(row_scale.data_ptr())
-    return C.c_void_p(int(row_scale))
+        return row_scale
+    return None if row_scale is None else int(row_scale)
 
 
 def conv_wgrad_async(dz, x, size, row_scale=None, bias=False, stride=1):
@@ -263,10 +233,9 @@ def conv_wgrad_thin_slices(batch, cout, cin, height, width, size):
     return s.value, n.value
 
 
-def _dgrad(who, w, dz, size, row_scale, y, slope, stride=1, in_hw=None, thin=False):
-    """The body of ``conv1x1_dgrad_async`` (``size`` None: rtod_conv1x1_dgrad, shape (B, Cout, Cin, pixels), no scale) and
-    ``conv_dgrad_async`` (rtod_conv_dgrad, shape (B, Cout, Cin, H, W, size); ``stride`` 2: rtod_conv_dgrad_s2, H x W the conv's INPUT
-    map): the tensor checks, the output, the launch.  ``thin``: rtod_conv_dgrad_thin (any Cin, stride 1)."""
+def _dgrad_operands(who, w, dz, size, y, stride=1, in_hw=None):
+    """The operand check ``_dgrad`` and ``conv_dgrad_split_async`` share.  Returns ``(w, dz, y)`` contiguous and ``(H, W)``, the map
+    ``dx`` lives on (for ``stride`` 2 the conv's INPUT map, from ``y`` or ``in_hw``)."""
     for t in (w, dz) + ((y,) if y is not None else ()):
         _need_cuda(t, who)
     k = 1 if size is None else int(size)
@@ -288,19 +257,23 @@ def _dgrad(who, w, dz, size, row_scale, y, slope, stride=1, in_hw=None, thin=Fal
         raise ValueError("%s: expected float32 w [Cout,Cin%s], dz [B,Cout,%s] and y [B,Cin,H,W], got %s, %s and %s"
                          % (who, "" if size is None else ",%d,%d" % (k, k), "(H-1)//2+1,(W-1)//2+1" if stride == 2 else "H,W", tuple(w.shape), tuple(dz.shape),
                             None if y is None else tuple(y.shape)))
-    w, dz = w.contiguous(), dz.contiguous()
-    y = None if y is None else y.contiguous()
+    return w.contiguous(), dz.contiguous(), None if y is None else y.contiguous(), H, W
+
+
+def _dgrad(who, w, dz, size, row_scale, y, slope, stride=1, in_hw=None, thin=False):
+    """The body of ``conv1x1_dgrad_async`` (``size`` None: rtod_conv1x1_dgrad, shape (B, Cout, Cin, pixels), no scale) and
+    ``conv_dgrad_async`` (rtod_conv_dgrad, shape (B, Cout, Cin, H, W, size); ``stride`` 2: rtod_conv_dgrad_s2, H x W the conv's INPUT
+    map): the tensor checks, the output, the launch.  ``thin``: rtod_conv_dgrad_thin (any Cin, stride 1)."""
+    w, dz, y, H, W = _dgrad_operands(who, w, dz, size, y, stride, in_hw)
     B, cout, cin = dz.size(0), dz.size(1), w.size(1)
-    shape = (B, cout, cin, H * W) if size is None else (B, cout, cin, H, W, k)
-    lib, dev = _ffi.lib(), dz.device
+    shape = (B, cout, cin, H * W) if size is None else (B, cout, cin, H, W, int(size))
+    dev = dz.device
     name = _DGRAD_ENTRIES.get((size is None, stride, bool(thin)))
     if name is None:
         raise ValueError("%s: the thin entry takes a size and stride 1" % who)
     dx = torch.empty((B, cin, H, W), dtype=torch.float32, device=dev)
     scale = () if size is None else (_scale_ptr(row_scale, cout, dev),)
-    args = (C.c_void_p(w.data_ptr()),) + scale + (C.c_void_p(dz.data_ptr()), C.c_void_p(y.data_ptr()) if y is not None else None, float(slope)) + shape
-    with torch.cuda.device(dev):
-        _ffi.check(getattr(lib, name)(*args, C.c_void_p(dx.data_ptr()), _stream(dev)))
+    _ffi.enqueue(name, dev, w, *scale, dz, y, float(slope), *shape, dx)
     return dx
 
 
@@ -330,7 +303,6 @@ def conv_dgrad_thin_async(w, dz, size, row_scale=None, y=None, slope=1.0, stride
     return _dgrad("conv_dgrad_thin", w, dz, int(size), row_scale, y, slope, stride, None, thin=True)
 
 
-_dgrad_split_ws = {}
 GRAD_PRECISIONS = ("fp32", "f16s3")      # DarknetTrainer(grad_precision=...): the exact data gradients, or the split-f16 ones where the walk sends the conv there
 # ... which is the 3x3 convs the entry takes.  The 1x1 convs stay on the exact entry: measured (tools/exp_grad_split.py, profiles/experiments/grad_split_cost.log;
 # 416x416 batch 8) YOLOv3's 37 take 2033.6 us exact and 1786.5 us through the split entry, YOLOv3-tiny's 4 take 95.3 us exact and 129.6 us split (four helper
@@ -364,34 +336,13 @@ def conv_dgrad_split_async(w, dz, size, row_scale=None, y=None, slope=1.0, tile=
     exact inverse scales and one multiplication by the mask.  ``tile``: one of ``conv_dgrad_split_tiles`` (None: the default; every
     legal tile gives the same bits).  The workspace is cached per shape; nothing synchronises.  ``phases`` (measurement only,
     rtod_conv_dgrad_split_phases): a sum of 1, 2, 4, 8, 16 naming the kernel groups to enqueue on the workspace a full call has filled."""
-    who = "conv_dgrad_split"
-    for t in (w, dz) + ((y,) if y is not None else ()):
-        _need_cuda(t, who)
-    k = int(size)
-    ok = dz.dim() == 4 and w.dim() in (2, 4) and w.size(0) == dz.size(1) and w.numel() == w.size(0) * w.size(1) * k * k and w.dtype == dz.dtype == torch.float32
-    if ok and y is not None:
-        ok = y.dtype == torch.float32 and tuple(y.shape) == (dz.size(0), w.size(1), dz.size(2), dz.size(3))
-    if not ok:
-        raise ValueError("%s: expected float32 w [Cout,Cin,%d,%d], dz [B,Cout,H,W] and y [B,Cin,H,W], got %s, %s and %s"
-                         % (who, k, k, tuple(w.shape), tuple(dz.shape), None if y is None else tuple(y.shape)))
-    w, dz = w.contiguous(), dz.contiguous()
-    y = None if y is None else y.contiguous()
-    B, cout, cin, H, W = dz.size(0), dz.size(1), w.size(1), dz.size(2), dz.size(3)
-    shape = (B, cout, cin, H, W, k)
-    lib, dev = _ffi.lib(), dz.device
-    key = (dev.index,) + shape
-    ws = _dgrad_split_ws.get(key)
-    if ws is None:
-        nbytes = C.c_size_t()
-        _ffi.check(lib.rtod_conv_dgrad_split_workspace(*shape, C.byref(nbytes)))
-        if len(_dgrad_split_ws) > 48:
-            _dgrad_split_ws.clear()
-        ws = _dgrad_split_ws[key] = (torch.empty(nbytes.value, dtype=torch.uint8, device=dev), nbytes.value)
+    w, dz, y, H, W = _dgrad_operands("conv_dgrad_split", w, dz, int(size), y)
+    B, cout, cin = dz.size(0), dz.size(1), w.size(1)
+    shape = (B, cout, cin, H, W, int(size))
+    dev = dz.device
     dx = torch.empty((B, cin, H, W), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        args = (C.c_void_p(w.data_ptr()), _scale_ptr(row_scale, cout, dev), C.c_void_p(dz.data_ptr()), C.c_void_p(y.data_ptr()) if y is not None else None,
-                float(slope)) + shape + (-1 if tile is None else int(tile), C.c_void_p(dx.data_ptr()), C.c_void_p(ws[0].data_ptr()), ws[1], _stream(dev))
-        _ffi.check(lib.rtod_conv_dgrad_split(*args) if phases is None else lib.rtod_conv_dgrad_split_phases(*args, int(phases)))
+    _ffi.enqueue("rtod_conv_dgrad_split" if phases is None else "rtod_conv_dgrad_split_phases", dev, w, _scale_ptr(row_scale, cout, dev), dz, y, float(slope),
+                 *shape, -1 if tile is None else int(tile), dx, *_ffi.workspace("rtod_conv_dgrad_split", dev, *shape), after=() if phases is None else (int(phases),))
     return dx
 
 
@@ -412,13 +363,8 @@ def maxpool_grad_async(dz, x, slope=1.0, size=2, stride=2):
     B, ch, H, W = x.shape
     dev = x.device
     dx = torch.empty((B, ch, H, W), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        _ffi.check(_ffi.lib().rtod_maxpool_grad(C.c_void_p(dz.data_ptr()) if dz.numel() else None, C.c_void_p(x.data_ptr()), float(slope), B, ch, H, W,
-                                                int(size), int(stride), C.c_void_p(dx.data_ptr()), _stream(dev)))
+    _ffi.enqueue("rtod_maxpool_grad", dev, dz if dz.numel() else None, x, float(slope), B, ch, H, W, int(size), int(stride), dx)
     return dx
-
-
-_bn_grad_ws = {}
 
 
 def bn_grad_parts(batch, channels, pixels):
@@ -430,12 +376,13 @@ def bn_grad_parts(batch, channels, pixels):
 
 
 def _stat_ptr(who, t, channels, dev):
-    """``mean`` / ``var`` of ``bn_grad_async`` as a pointer: a contiguous float64 device tensor [C], or an integer device address."""
+    """``mean`` / ``var`` of ``bn_grad_async`` as a pointer argument: a contiguous float64 device tensor [C] (checked), or an integer
+    device address."""
     if isinstance(t, torch.Tensor):
         if t.device != dev or t.dtype != torch.float64 or t.numel() != channels or not t.is_contiguous():
             raise ValueError("%s: mean and var must be contiguous float64 tensors [%d] on %s" % (who, channels, dev))
-        return C.c_void_p(t.data_ptr())
-    return C.c_void_p(int(t))
+        return t
+    return int(t)
 
 
 def bn_grad_async(du, z, mean, var, gamma):
@@ -453,22 +400,12 @@ def bn_grad_async(du, z, mean, var, gamma):
     aligned = lambda t: t.contiguous() if t.contiguous().data_ptr() % 16 == 0 else t.contiguous().clone()
     du, z, gamma = aligned(du), aligned(z), gamma.contiguous()
     B, ch, pixels = du.size(0), du.size(1), du.size(2) * du.size(3)
-    lib, dev = _ffi.lib(), du.device
-    key = (dev.index, B, ch, pixels)
-    ws = _bn_grad_ws.get(key)
-    if ws is None:
-        nbytes = C.c_size_t()
-        _ffi.check(lib.rtod_bn_grad_workspace(B, ch, pixels, C.byref(nbytes)))
-        if len(_bn_grad_ws) > 16:
-            _bn_grad_ws.clear()
-        ws = _bn_grad_ws[key] = (torch.empty((nbytes.value + 7) // 8, dtype=torch.float64, device=dev), nbytes.value)
+    dev = du.device
     dz = torch.empty_like(du)
     dgamma = torch.empty(ch, dtype=torch.float32, device=dev)
     dbeta = torch.empty(ch, dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        _ffi.check(lib.rtod_bn_grad(C.c_void_p(du.data_ptr()), C.c_void_p(z.data_ptr()), _stat_ptr("bn_grad", mean, ch, dev), _stat_ptr("bn_grad", var, ch, dev),
-                                    C.c_void_p(gamma.data_ptr()), B, ch, pixels, C.c_void_p(dz.data_ptr()), C.c_void_p(dgamma.data_ptr()),
-                                    C.c_void_p(dbeta.data_ptr()), C.c_void_p(ws[0].data_ptr()), ws[1], _stream(dev)))
+    _ffi.enqueue("rtod_bn_grad", dev, du, z, _stat_ptr("bn_grad", mean, ch, dev), _stat_ptr("bn_grad", var, ch, dev), gamma, B, ch, pixels,
+                 dz, dgamma, dbeta, *_ffi.workspace("rtod_bn_grad", dev, B, ch, pixels))
     return dz, dgamma, dbeta
 
 
@@ -486,15 +423,13 @@ def grad_join_async(contributions, y=None, slope=1.0):
             raise ValueError("grad_join: expected equally shaped float32 tensors, got %s and %s" % (tuple(cs[0].shape), tuple(t.shape)))
     cs = [c.contiguous() for c in cs]
     y = None if y is None else y.contiguous()
-    dev, lib = cs[0].device, _ffi.lib()
+    dev = cs[0].device
     while True:
         now, cs = cs[:4], cs[4:]
         last = not cs
         out = torch.empty_like(now[0])
         ptrs = (C.c_void_p * 4)(*[c.data_ptr() for c in now])
-        with torch.cuda.device(dev):
-            _ffi.check(lib.rtod_grad_join(ptrs, len(now), C.c_void_p(y.data_ptr()) if last and y is not None else None, float(slope) if last else 1.0,
-                                          out.numel(), C.c_void_p(out.data_ptr()), _stream(dev)))
+        _ffi.enqueue("rtod_grad_join", dev, ptrs, len(now), y if last else None, float(slope) if last else 1.0, out.numel(), out)
         if last:
             return out
         cs = [out] + cs
@@ -518,9 +453,7 @@ def upsample2x_grad_async(dz, y=None, slope=1.0, mode="bilinear"):
     B, ch, H, W = dz.size(0), dz.size(1), dz.size(2) // 2, dz.size(3) // 2
     dev = dz.device
     dx = torch.empty((B, ch, H, W), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        _ffi.check(_ffi.lib().rtod_upsample2x_grad(C.c_void_p(dz.data_ptr()), C.c_void_p(y.data_ptr()) if y is not None else None, float(slope),
-                                                   1 if mode == "nearest" else 0, B, ch, H, W, C.c_void_p(dx.data_ptr()), _stream(dev)))
+    _ffi.enqueue("rtod_upsample2x_grad", dev, dz, y, float(slope), 1 if mode == "nearest" else 0, B, ch, H, W, dx)
     return dx
 
 
@@ -539,6 +472,39 @@ def model_heads(model, height=None, width=None):
     if not heads:
         raise ValueError("DarknetTrainer: the cfg has no [yolo] layer")
     return heads, classes
+
+
+def batch_mode(model):
+    """Batch mode: the model normalises with the statistics of the batch (``.train()``, ``bn_running_stats_in_train`` off) and its
+    plan keeps the BatchNorm inputs (option ``keep_bn_inputs``), so the walk goes through ``bn_grad_async`` and gamma and beta are
+    trained.  Otherwise BatchNorm is frozen (an eval model)."""
+    return bool(getattr(model, "training", False) and not getattr(model, "bn_running_stats_in_train", False)
+                and int(getattr(model, "options", {}).get("keep_bn_inputs", 0)))
+
+
+def conv_kind(model, layer):
+    """The kind of a trained conv, a key of ``darknet.CONV_KINDS``, decided here and nowhere else: "head" (no BatchNorm: weight and
+    bias), "bn" (BatchNorm on batch statistics in batch mode: weight, gamma, beta) or "folded" (BatchNorm frozen: weight alone)."""
+    return "head" if model._conv_bn(layer)[1] is None else "bn" if batch_mode(model) else "folded"
+
+
+# A conv's masters (``DarknetTrainer._head_masters[layer]``) and its gradients (``HeadOptimizer.step``) are lists with one slot per
+# parameter name, cut after the last one the kind has: [weight, bias or None(, gamma, beta)].  ``HeadOptimizer.state`` names them in
+# torch's words; the moments of "weight" carry no suffix.
+_SLOT = {"weight": 0, "bias": 1, "gamma": 2, "beta": 3}
+_STATE_KEY = {"weight": "weight", "bias": "bias", "gamma": "bn_weight", "beta": "bn_bias"}
+
+
+def _slots(kind, named):
+    """``{parameter name: tensor}`` of a conv of ``kind`` as its list of slots."""
+    out = [None] * (1 + max(_SLOT[name] for name in CONV_KINDS[kind].params + ("bias",)))
+    for name in CONV_KINDS[kind].params:
+        out[_SLOT[name]] = named[name]
+    return out
+
+
+def _moment_keys(name):
+    return tuple(m + ("" if name == "weight" else "_" + _STATE_KEY[name]) for m in ("exp_avg", "exp_avg_sq"))
 
 
 class HeadOptimizer:
@@ -562,21 +528,20 @@ class HeadOptimizer:
         self.state = {}
         self._trainer = None               # weak reference to the DarknetTrainer this optimiser is the ``optimizer`` of
 
-    def _entry(self, layer, masters):
+    def _entry(self, kind, layer, masters):
+        """The state of a conv of ``kind``: its masters adopted (new weight or bias masters start the moments afresh, the step count
+        stays), for Adam the moments of every parameter the kind has."""
         st = self.state.get(layer)
         if st is None or st["weight"] is not masters[0] or st.get("bias") is not masters[1]:
-            st = self.state[layer] = {"step": 0 if st is None else st["step"], "weight": masters[0]}
-            if masters[1] is not None:                             # (a block conv has no bias: no bias keys)
-                st["bias"] = masters[1]
-        if self.kind == "adam" and "exp_avg" not in st:
-            st.update(exp_avg=torch.zeros_like(masters[0]), exp_avg_sq=torch.zeros_like(masters[0]))
-            if masters[1] is not None:
-                st.update(exp_avg_bias=torch.zeros_like(masters[1]), exp_avg_sq_bias=torch.zeros_like(masters[1]))
-        if len(masters) == 4 and (st.get("bn_weight") is not masters[2] or st.get("bn_bias") is not masters[3]):
-            st.update(bn_weight=masters[2], bn_bias=masters[3])      # BatchNorm on batch statistics: gamma and beta train too
-        if self.kind == "adam" and "bn_weight" in st and "exp_avg_bn_weight" not in st:
-            st.update(exp_avg_bn_weight=torch.zeros_like(st["bn_weight"]), exp_avg_sq_bn_weight=torch.zeros_like(st["bn_weight"]),
-                      exp_avg_bn_bias=torch.zeros_like(st["bn_bias"]), exp_avg_sq_bn_bias=torch.zeros_like(st["bn_bias"]))
+            st = self.state[layer] = {"step": 0 if st is None else st["step"]}
+        names = CONV_KINDS[kind].params
+        for name in names:
+            st[_STATE_KEY[name]] = masters[_SLOT[name]]
+        if self.kind == "adam":
+            for name in names:
+                for key in _moment_keys(name):
+                    if key not in st:
+                        st[key] = torch.zeros_like(st[_STATE_KEY[name]])
         return st
 
     def step(self, model, masters, grads):
@@ -584,19 +549,15 @@ class HeadOptimizer:
         head conv (``Darknet.step_conv``), ``(dW, None)`` and ``[weight, None]`` for a block conv (``Darknet.step_conv_folded``),
         ``(dW, None, dgamma, dbeta)`` and ``[weight, None, gamma, beta]`` for a conv whose BatchNorm runs on batch statistics
         (``Darknet.step_conv_bn``)."""
-        for layer, (dw, db, *bn) in grads.items():
-            st = self._entry(layer, masters[layer])
+        for layer, grad in grads.items():
+            kind = conv_kind(model, layer)
+            K = CONV_KINDS[kind]
+            st = self._entry(kind, layer, masters[layer])
             st["step"] += 1
             opt = _ffi.OptStep(self.KINDS[self.kind], self.lr, self.betas[0], self.betas[1], self.eps, st["step"])
-            adam = self.kind == "adam"
-            if bn:
-                moments = tuple(st[k] for k in ("exp_avg", "exp_avg_sq", "exp_avg_bn_weight", "exp_avg_sq_bn_weight", "exp_avg_bn_bias", "exp_avg_sq_bn_bias")) if adam else None
-                model.step_conv_bn(layer, opt, st["weight"], dw, st["bn_weight"], st["bn_bias"], bn[0], bn[1], moments)
-            elif db is None:
-                model.step_conv_folded(layer, opt, st["weight"], dw, (st["exp_avg"], st["exp_avg_sq"]) if adam else None)
-            else:
-                moments = (st["exp_avg"], st["exp_avg_sq"], st["exp_avg_bias"], st["exp_avg_sq_bias"]) if adam else None
-                model.step_conv(layer, opt, st["weight"], st["bias"], dw, db, moments)
+            operands = [grad[_SLOT[name[2:]]] if name.startswith("d.") else st[_STATE_KEY[name]] for name in K.order]
+            moments = tuple(st[key] for name in K.params for key in _moment_keys(name)) if self.kind == "adam" else None
+            getattr(model, K.step)(layer, opt, *operands, moments)
 
     def state_dict(self):
         """``{conv_layer: {"step": int, name: tensor}}`` of the masters and moments (the tensors themselves, as torch's does)."""
@@ -609,15 +570,12 @@ class HeadOptimizer:
         self.state = {int(layer): {k: (v.detach().clone() if isinstance(v, torch.Tensor) else int(v)) for k, v in st.items()} for layer, st in state.items()}
         trainer = self._trainer() if self._trainer is not None else None
         if trainer is not None:
-            trainer._head_masters = {layer: [st["weight"], st.get("bias")] + ([st["bn_weight"], st["bn_bias"]] if "bn_weight" in st else [])
-                                     for layer, st in self.state.items()}
-            for layer, (w, b, *bn) in trainer._head_masters.items():
-                if bn:
-                    trainer.darknet.update_conv_bn(layer, w, bn[0], bn[1])
-                elif b is None:
-                    trainer.darknet.update_conv_weight(layer, w)
-                else:
-                    trainer.darknet.update_conv(layer, w, b)
+            trainer._head_masters = {}
+            for layer, st in self.state.items():
+                kind = conv_kind(trainer.darknet, layer)
+                named = {name: st[_STATE_KEY[name]] for name in CONV_KINDS[kind].params}
+                trainer._head_masters[layer] = _slots(kind, named)
+                getattr(trainer.darknet, CONV_KINDS[kind].update)(layer, *named.values())
 
 
 class DarknetTrainer:
@@ -668,9 +626,7 @@ class DarknetTrainer:
         return bool(getattr(m, "training", False) and not getattr(m, "bn_running_stats_in_train", False))
 
     def _batch_mode(self):
-        """Batch mode: batch statistics, and the plan keeps the BatchNorm inputs (option ``keep_bn_inputs``): the walk goes through
-        ``bn_grad_async`` and gamma and beta are trained.  Otherwise BatchNorm is frozen (an eval model)."""
-        return self._batch_stats() and bool(int(getattr(self.darknet, "options", {}).get("keep_bn_inputs", 0)))
+        return batch_mode(self.darknet)
 
     def _require_bn_option(self, who, scope):
         if scope in self.SCOPES and self._batch_stats() and not self._batch_mode():
@@ -759,11 +715,8 @@ class DarknetTrainer:
         attrs = pred.size(-1)
         rows = pred.numel() // attrs
         dev = pred.device
-        ws, nbytes = _workspace(dev, 1, rows)
         comp = torch.empty(6, dtype=torch.float64, device=dev)
-        with torch.cuda.device(dev):
-            _ffi.check(_ffi.lib().rtod_darknet_loss_dense(C.c_void_p(pred.data_ptr()), C.c_void_p(target.data_ptr()), C.c_void_p(mask.data_ptr()),
-                                                          rows, attrs, C.c_void_p(comp.data_ptr()), C.c_void_p(ws.data_ptr()), nbytes, _stream(dev)))
+        _ffi.enqueue("rtod_darknet_loss_dense", dev, pred, target, mask, rows, attrs, comp, *_workspace(dev, 1, rows))
         self.last_components = comp
         return comp[0].float()
 
@@ -843,16 +796,16 @@ class DarknetTrainer:
         beta]``."""
         if self._head_masters is None:
             self._head_masters = {}
-        batch = self._batch_mode()
-        missing = [layer for layer in layers if layer not in self._head_masters or (batch and self.darknet._conv_bn(layer)[1] is not None and len(self._head_masters[layer]) < 4)]
+        kinds = {layer: conv_kind(self.darknet, layer) for layer in layers}
+        missing = [layer for layer, kind in kinds.items() if layer not in self._head_masters or (kind == "bn" and len(self._head_masters[layer]) < 4)]
         if missing:
             self.darknet.sync_stepped_parameters()
-            own = lambda p: p.detach().to(dev, torch.float32).clone()
             for layer in missing:
-                conv, bn = self.darknet._conv_bn(layer)
-                kept = self._head_masters.get(layer)
-                entry = kept[:2] if kept else [own(conv.weight), None if conv.bias is None else own(conv.bias)]
-                self._head_masters[layer] = entry + ([own(bn.weight), own(bn.bias)] if batch and bn is not None else [])
+                K = CONV_KINDS[kinds[layer]]
+                kept = self._head_masters.get(layer, ())                  # (a conv that was trained with BatchNorm frozen keeps its weight master)
+                named = {name: kept[_SLOT[name]] if _SLOT[name] < len(kept) else p.detach().to(dev, torch.float32).clone()
+                         for name, p in zip(K.params, self.darknet._params(kinds[layer], layer))}
+                self._head_masters[layer] = _slots(kinds[layer], named)
         return self._head_masters
 
     # ------------------------------------------------------------------ gradients behind the heads: one entry, three scopes
@@ -1068,7 +1021,8 @@ class DarknetTrainer:
             # masters in place, and the data gradients through the heads and the neck convs read them
             loss, grads, block_grads, bn_grads = self.batchnorm_gradients(batch_data, bndbox)
             grads = dict(grads)
-            grads.update({layer: (dw, None) + tuple(bn_grads.get(layer, ())) for layer, dw in block_grads.items()})
+            for layer, dw in block_grads.items():
+                grads[layer] = _slots(conv_kind(self.darknet, layer), dict(zip(("gamma", "beta"), bn_grads.get(layer, ())), weight=dw))
         else:
             loss, grads = self.head_gradients(batch_data, bndbox)
         self.optimizer.step(self.darknet, self._masters(grads, loss.device), grads)

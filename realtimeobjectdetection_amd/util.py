@@ -17,8 +17,6 @@ import torch
 
 from . import _ffi
 
-_ws_cache = {}
-
 COCO_NAMES = ("person bicycle car motorbike aeroplane bus train truck boat|traffic light|fire hydrant|stop sign|parking meter|bench "
               "bird cat dog horse sheep cow elephant bear zebra giraffe backpack umbrella handbag tie suitcase frisbee skis snowboard|"
               "sports ball|kite|baseball bat|baseball glove|skateboard surfboard|tennis racket|bottle|wine glass|cup fork knife spoon bowl "
@@ -80,9 +78,7 @@ def prep_image(img, inp_dim, mode="BGR", device=None) -> torch.Tensor:
         device = t.device if t.is_cuda else torch.device("cuda", torch.cuda.current_device())
     t = t.to(device).contiguous()
     out = torch.empty((1, 3, int(inp_dim), int(inp_dim)), dtype=torch.float32, device=t.device)
-    with torch.cuda.device(t.device):
-        _ffi.check(_ffi.lib().rtod_prep_image(C.c_void_p(t.data_ptr()), t.size(0), t.size(1), 1 if mode == "BGR" else 0,
-                                              int(inp_dim), C.c_void_p(out.data_ptr()), _stream(t.device)))
+    _ffi.enqueue("rtod_prep_image", t.device, t, t.size(0), t.size(1), 1 if mode == "BGR" else 0, int(inp_dim), out)
     return out
 
 
@@ -99,9 +95,7 @@ def prep_frames(frames, size, mode="BGR", device=None) -> torch.Tensor:
         device = t.device if t.is_cuda else torch.device("cuda", torch.cuda.current_device())
     t = t.to(device).contiguous()
     out = torch.empty((t.size(0), 3, h, w), dtype=torch.float32, device=t.device)
-    with torch.cuda.device(t.device):
-        _ffi.check(_ffi.lib().rtod_prep_frames(C.c_void_p(t.data_ptr()), t.size(0), t.size(1), t.size(2), 1 if mode == "BGR" else 0,
-                                               h, w, C.c_void_p(out.data_ptr()), _stream(t.device)))
+    _ffi.enqueue("rtod_prep_frames", t.device, t, t.size(0), t.size(1), t.size(2), 1 if mode == "BGR" else 0, h, w, out)
     return out
 
 
@@ -143,7 +137,6 @@ def predict_transform(prediction, inp_dim, anchors, num_class, CUDA=True, TRAIN=
     _need_cuda(prediction, "predict_transform")
     if prediction.dim() != 4 or prediction.size(2) != prediction.size(3):
         raise ValueError("predict_transform: expected [B, A*(5+C), G, G], got %s" % (tuple(prediction.shape),))
-    lib = _ffi.lib()
     B, ch, G = prediction.size(0), prediction.size(1), prediction.size(2)
     attrs = 5 + int(num_class)
     A = len(anchors)
@@ -152,9 +145,7 @@ def predict_transform(prediction, inp_dim, anchors, num_class, CUDA=True, TRAIN=
     x = prediction.contiguous()
     out = torch.empty((B, G * G * A, attrs), dtype=torch.float32, device=x.device)
     anc = (C.c_float * (2 * A))(*[float(v) for a in anchors for v in a])
-    with torch.cuda.device(x.device):
-        _ffi.check(lib.rtod_predict_transform(C.c_void_p(x.data_ptr()), B, attrs, G, A, anc, int(inp_dim),
-                                              1 if TRAIN else 0, C.c_void_p(out.data_ptr()), _stream(x.device)))
+    _ffi.enqueue("rtod_predict_transform", x.device, x, B, attrs, G, A, anc, int(inp_dim), 1 if TRAIN else 0, out)
     return out
 
 
@@ -164,9 +155,7 @@ def confidence_mask(tensor: torch.Tensor, confidence: float) -> torch.Tensor:
         raise ValueError("confidence_mask: expected [B,N,>=5]")
     x = tensor.contiguous()
     out = torch.empty_like(x)
-    with torch.cuda.device(x.device):
-        _ffi.check(_ffi.lib().rtod_confidence_mask(C.c_void_p(x.data_ptr()), x.size(0) * x.size(1), x.size(2),
-                                                   float(confidence), C.c_void_p(out.data_ptr()), _stream(x.device)))
+    _ffi.enqueue("rtod_confidence_mask", x.device, x, x.size(0) * x.size(1), x.size(2), float(confidence), out)
     return out
 
 
@@ -182,9 +171,7 @@ def bbox_iou(box1: torch.Tensor, box2: torch.Tensor) -> torch.Tensor:
     b2 = b2.contiguous()
     k = b2.size(0)
     out = torch.empty((k,), dtype=torch.float32, device=b2.device)
-    with torch.cuda.device(b2.device):
-        _ffi.check(_ffi.lib().rtod_bbox_iou(C.c_void_p(b1.data_ptr()), C.c_void_p(b2.data_ptr()), k, b2.size(1),
-                                            C.c_void_p(out.data_ptr()), _stream(b2.device)))
+    _ffi.enqueue("rtod_bbox_iou", b2.device, b1, b2, k, b2.size(1), out)
     return out
 
 
@@ -200,19 +187,16 @@ def _host_ints(dev):
 
 
 def _nms_buffers(dev, B, n, cap):
-    key = (dev.index, B, n, cap)
-    buf = _ws_cache.get(key)
-    if buf is None:
+    """``(workspace, rows [cap,8], counts, workspace bytes)`` of write_results / nms_class_offset, kept together per shape (and
+    stream) in ``_ffi.cache``."""
+    def build():
         nbytes = C.c_size_t()
         _ffi.check(_ffi.lib().rtod_write_results_workspace(B, n, C.byref(nbytes)))
-        ws = torch.empty((nbytes.value + 15) // 16 * 4, dtype=torch.int32, device=dev)
+        ws = torch.empty((nbytes.value + 15) // 16 * 16, dtype=torch.uint8, device=dev)
         out = torch.empty((max(cap, 1), 8), dtype=torch.float32, device=dev)
         counts = torch.zeros((2 + B + 2,), dtype=torch.int32, device=dev)
-        buf = (ws, out, counts, nbytes.value)
-        if len(_ws_cache) > 16:
-            _ws_cache.clear()
-        _ws_cache[key] = buf
-    return buf
+        return ws, out, counts, nbytes.value
+    return _ffi.cache.get(_ffi.stream_key(dev) + ("nms_buffers", (B, n, cap)), build)
 
 
 def write_results_async(prediction, num_class, confidence=0.6, nms_conf=0.4, cap=None):
@@ -230,11 +214,7 @@ def write_results_async(prediction, num_class, confidence=0.6, nms_conf=0.4, cap
     if cap is None:
         cap = min(B * n, 16384)
     ws, out, counts, nbytes = _nms_buffers(x.device, B, n, int(cap))
-    with torch.cuda.device(x.device):
-        _ffi.check(_ffi.lib().rtod_write_results(C.c_void_p(x.data_ptr()), B, n, int(num_class), float(confidence),
-                                                 float(nms_conf), C.c_void_p(out.data_ptr()), int(cap),
-                                                 C.c_void_p(counts.data_ptr()), C.c_void_p(ws.data_ptr()), nbytes,
-                                                 _stream(x.device)))
+    _ffi.enqueue("rtod_write_results", x.device, x, B, n, int(num_class), float(confidence), float(nms_conf), out, int(cap), counts, ws, nbytes)
     return out, counts
 
 
@@ -243,17 +223,7 @@ def nms_class_offset(prediction, num_class, conf_thres=0.25, iou_thres=0.45, max
     detect.py:255-285; this follows the published class-offset batched NMS — parity unpinned).  ``prediction``
     ``[B,N,5+C]`` rows ``(cx,cy,w,h,obj,cls...)`` -> ``[D,8]`` rows ``[img,x1,y1,x2,y2,conf,obj,cls]``, per image by
     descending ``conf = obj * max cls`` (ties: lower row first), at most ``max_det`` per image; one host sync."""
-    _need_cuda(prediction, "nms_class_offset")
-    if prediction.dim() != 3 or prediction.size(2) != 5 + int(num_class):
-        raise ValueError("nms_class_offset: expected [B,N,5+num_class], got %s" % (tuple(prediction.shape),))
-    x = prediction.contiguous()
-    B, n = x.size(0), x.size(1)
-    cap = B * min(n, int(max_det))
-    ws, out, counts, nbytes = _nms_buffers(x.device, B, n, int(cap))
-    with torch.cuda.device(x.device):
-        _ffi.check(_ffi.lib().rtod_nms_class_offset(C.c_void_p(x.data_ptr()), B, n, int(num_class), float(conf_thres), float(iou_thres),
-                                                    float(max_wh), int(max_det), C.c_void_p(out.data_ptr()), int(cap),
-                                                    C.c_void_p(counts.data_ptr()), C.c_void_p(ws.data_ptr()), nbytes, _stream(x.device)))
+    out, counts = nms_class_offset_async(prediction, num_class, conf_thres, iou_thres, max_wh, max_det)
     return out[:int(counts[0].item())].clone()
 
 
@@ -268,10 +238,8 @@ def nms_class_offset_async(prediction, num_class, conf_thres=0.25, iou_thres=0.4
     if cap is None:
         cap = B * min(n, int(max_det))
     ws, out, counts, nbytes = _nms_buffers(x.device, B, n, int(cap))
-    with torch.cuda.device(x.device):
-        _ffi.check(_ffi.lib().rtod_nms_class_offset(C.c_void_p(x.data_ptr()), B, n, int(num_class), float(conf_thres), float(iou_thres),
-                                                    float(max_wh), int(max_det), C.c_void_p(out.data_ptr()), int(cap),
-                                                    C.c_void_p(counts.data_ptr()), C.c_void_p(ws.data_ptr()), nbytes, _stream(x.device)))
+    _ffi.enqueue("rtod_nms_class_offset", x.device, x, B, n, int(num_class), float(conf_thres), float(iou_thres), float(max_wh), int(max_det),
+                 out, int(cap), counts, ws, nbytes)
     return out, counts
 
 

@@ -19,9 +19,7 @@ import os
 import torch
 
 from . import _ffi
-from .util import _need_cuda, _stream, prep_frames, write_results_async
-
-_ws_cache = {}
+from .util import _need_cuda, prep_frames, write_results_async
 
 
 def score_limits():
@@ -41,15 +39,7 @@ def _class_mask(permitted_classes, num_classes):
 
 
 def _score_workspace(dev, batch, cap, max_targets):
-    key = (dev.index, batch, cap, max_targets)
-    ws = _ws_cache.get(key)
-    if ws is None:
-        nbytes = C.c_size_t()
-        _ffi.check(_ffi.lib().rtod_score_detections_workspace(batch, cap, max_targets, C.byref(nbytes)))
-        if len(_ws_cache) > 16:
-            _ws_cache.clear()
-        ws = _ws_cache[key] = (torch.empty((nbytes.value + 15) // 16 * 4, dtype=torch.int32, device=dev), nbytes.value)
-    return ws
+    return _ffi.workspace("rtod_score_detections", dev, batch, cap, max_targets)
 
 
 def score_detections_async(rows, counts, targets, num_class, permitted_classes=(0,), min_box_size=24, iou_threshold=0.5,
@@ -87,12 +77,8 @@ def score_detections_async(rows, counts, targets, num_class, permitted_classes=(
     miou = torch.empty((cap,), dtype=torch.float32, device=dev)
     if status is None:
         status = torch.zeros(1, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        _ffi.check(_ffi.lib().rtod_score_detections(
-            C.c_void_p(rows.data_ptr()), C.c_void_p(counts.data_ptr()), cap, B, C.c_void_p(tgt.data_ptr()), C.c_void_p(toff.data_ptr()),
-            int(num_class), _class_mask(permitted_classes, num_class), float(min_box_size), float(iou_threshold), max_tgt, 1 if corners else 0,
-            C.c_void_p(scores.data_ptr()), C.c_void_p(totals.data_ptr()) if totals is not None else None, C.c_void_p(match.data_ptr()),
-            C.c_void_p(miou.data_ptr()), C.c_void_p(status.data_ptr()), C.c_void_p(ws.data_ptr()), nbytes, _stream(dev)))
+    _ffi.enqueue("rtod_score_detections", dev, rows, counts, cap, B, tgt, toff, int(num_class), _class_mask(permitted_classes, num_class),
+                 float(min_box_size), float(iou_threshold), max_tgt, 1 if corners else 0, scores, totals, match, miou, status, ws, nbytes)
     return scores, match, miou, status
 
 

@@ -96,8 +96,9 @@ def test_ragged_k_padding_of_the_workspace_never_reaches_dx(scaled):
     half or a double — before the call; the result is finite and holds the bits of the first call."""
     s = _setup("F", scaled)
     case = s["case"]
-    ws = [v[0] for k, v in T._dgrad_split_ws.items() if k[1:] == case]
-    assert ws, "the workspace of case F is cached per shape"
+    key = T._ffi.stream_key(s["dx"].device) + ("rtod_conv_dgrad_split", case)
+    assert key in T._ffi.cache, "the workspace of case F is cached per shape"
+    ws = [T._ffi.workspace("rtod_conv_dgrad_split", s["dx"].device, *case)[0]]
     for tile in T.conv_dgrad_split_tiles(*case)[:3]:
         for t in ws:
             t.fill_(0xFF)

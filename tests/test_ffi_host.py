@@ -33,7 +33,7 @@ def _describe(h):
 
 def test_header_symbols_all_exported():
     hdr = open(os.path.join(ROOT, "include", "rtod.h")).read()
-    declared = set(re.findall(r"\b(rtod_[a-z_]+)\s*\(", hdr))
+    declared = set(re.findall(r"\b(rtod_[a-z0-9_]+)\s*\(", hdr))
     assert declared, "no declarations parsed"
     lib = C.CDLL(_ffi.LIB_PATH)
     for name in declared:
