@@ -704,6 +704,44 @@ int rtod_conv_dgrad_split(const float* w_oihw_dev, const double* row_scale_dev, 
 int rtod_conv_dgrad_split_phases(const float* w_oihw_dev, const double* row_scale_dev, const float* dz_dev, const float* y_dev, float slope,
                                  int batch, int cout, int cin, int height, int width, int size, int tile,
                                  float* dx_dev, void* workspace, size_t workspace_bytes, void* stream, int phases);
+/* (new) rtod_conv_wgrad as three f16 MFMA products (opt-in; wgrad_split.hip): a size x size (1 or 3), stride 1, pad size / 2 BatchNorm
+ * conv, cin a positive multiple of 32, any cout >= 1, dense fp32 NCHW dz [batch, cout, height, width] and x [batch, cin, height, width]:
+ *   dW[o][c][ky][kx] = row_scale[o] * sum_{b,y,x} dz[b,o,y,x] * x[b,c,y+ky-p,x+kx-p]          (x an exact zero outside the map; no db)
+ * The arithmetic, defined free of any summation order:
+ *   exponents  ONE per tensor (dW is a sum over the batch): a = max |t|, e = 13 - frexp(a).exp, so that a 2^e lies in [2^12, 2^13);
+ *              a == 0 or not finite: e = 0; e held to -126 .. 126.  e_z for dz, e_x for x.
+ *   split      v = t 2^e (exact), hi = RNE_f16(v), lo = RNE_f16(v - hi); subnormal halves are kept.
+ *   sum        zh*xh + zh*xl + zl*xh over all (b, y, x), products of halves summed in fp32 by v_mfma_f32_32x32x16_f16; zl*xl is absent
+ *              by definition.
+ *   finish     dW = (float)((double)sum * 2^-(e_z + e_x) * row_scale[o]) (row_scale_dev NULL: the factor 1): one rounding, in double;
+ *              2^-(e_z + e_x) need not be a normal float.
+ * dz and x are re-laid as channel-major f16 planes on a common padded k grid (size 3: [batch][height + 2][Wp], Wp = 8 * ceil((width +
+ * 2) / 8), halo written as zeros in both; size 1: the flat batch * height * width), rounded up with zeros to k_padded, a multiple of
+ * 16; a workgroup owns a tile of dW (3x3: 64 filters x 64 channels x all nine taps; 1x1: 128 x 128) over one K slice.
+ * rtod_conv_wgrad_split_schedule (no device): tiles, slices, slice_len and k_padded of the shape; with u = k_padded / 16 and
+ * want = max(1, min(64, ceil(1024 / tiles), u / 4)): slice_len = 16 * ceil(u / want), slices = ceil(k_padded / slice_len) <= want (the
+ * workspace holds `want` slice sums): a pure function of the shape.  The slice sums are
+ * added in ascending order; no atomics: bit-identical from call to call.  rtod_conv_wgrad_split_bounds (no device): the lowest and
+ * the highest half index, from the start of a plane of plane_halves halves (guards included), that the GEMM forms for the shape; the
+ * split kernel writes every half of every plane, so 0 <= lowest and highest < plane_halves is the bounds proof of the call.
+ * Workspace: rtod_conv_wgrad_split_workspace bytes, 16-byte aligned; every byte a kernel reads is written earlier in the same call.
+ * Five launches on `stream`, nothing synchronises, no host read of device memory; legal under stream capture.  RTOD_E_ARG, each text
+ * starting with the entry's name: a null dz / x / dw / workspace, batch, cout, height or width < 1, cin not a positive multiple of 32,
+ * size not 1 or 3, the padded k grid or cout * cin * size * size beyond int32, a plane of 2 GiB or more, cout + cin > 65535, a workspace
+ * that is too small or misaligned. */
+int rtod_conv_wgrad_split_schedule(int batch, int cout, int cin, int height, int width, int size,
+                                   int* tiles, int* slices, int* slice_len, int64_t* k_padded);
+int rtod_conv_wgrad_split_bounds(int batch, int cout, int cin, int height, int width, int size,
+                                 int64_t* lowest, int64_t* highest, int64_t* plane_halves);
+int rtod_conv_wgrad_split_workspace(int batch, int cout, int cin, int height, int width, int size, size_t* bytes);
+int rtod_conv_wgrad_split(const float* dz_dev, const float* x_dev, int batch, int cout, int cin, int height, int width, int size,
+                          const double* row_scale_dev, float* dw_dev, void* workspace, size_t workspace_bytes, void* stream);
+/* ... for measurement (tools/exp_wgrad_split.py): the same call enqueues only the kernel groups named in `phases`, a sum of 1 (maxima and
+ * exponents), 2 (the split), 4 (the GEMM) and 8 (the reduce), on a workspace that a full call of the same shape has filled.  15 is
+ * rtod_conv_wgrad_split; outside 1 .. 15: RTOD_E_ARG. */
+int rtod_conv_wgrad_split_phases(const float* dz_dev, const float* x_dev, int batch, int cout, int cin, int height, int width, int size,
+                                 const double* row_scale_dev, float* dw_dev, void* workspace, size_t workspace_bytes, void* stream,
+                                 int phases);
 
 /* ---- optimiser step of a detection-head conv, on the stream ------------------------------------------
  * replaces optim.Adam(self.darknet.parameters(), lr=1e-2) + optimizer.step()     train.py:57, 412-425

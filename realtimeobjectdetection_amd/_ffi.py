@@ -152,6 +152,14 @@ SIGNATURES = {
                                         C.c_int, Ptr, Ptr, C.c_size_t, C.c_void_p]),
     "rtod_conv_dgrad_split_phases": (C.c_int, [Ptr, Ptr, Ptr, Ptr, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                                C.c_int, Ptr, Ptr, C.c_size_t, C.c_void_p, C.c_int]),
+    "rtod_conv_wgrad_split_schedule": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                                 C.POINTER(C.c_int), C.POINTER(C.c_int64)]),
+    "rtod_conv_wgrad_split_bounds": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                               C.POINTER(C.c_int64)]),
+    "rtod_conv_wgrad_split_workspace": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    "rtod_conv_wgrad_split": (C.c_int, [Ptr, Ptr, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, Ptr, Ptr, Ptr, C.c_size_t, C.c_void_p]),
+    "rtod_conv_wgrad_split_phases": (C.c_int, [Ptr, Ptr, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, Ptr, Ptr, Ptr, C.c_size_t, C.c_void_p,
+                                               C.c_int]),
     "rtod_conv1x1_wgrad_workspace": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
     "rtod_conv1x1_wgrad": (C.c_int, [Ptr, Ptr, C.c_int, C.c_int, C.c_int, C.c_int, Ptr, Ptr, Ptr, C.c_size_t, C.c_void_p]),
     "rtod_conv1x1_dgrad": (C.c_int, [Ptr, Ptr, Ptr, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, Ptr, C.c_void_p]),
@@ -206,8 +214,8 @@ def enqueue(entry, dev, *args, after=()):
         raise RtodError(rc, last_error())
 
 
-CACHE_CAPACITY = 96     # entries.  One YOLOv3 backbone step at one batch size holds 23 weight-gradient, 16 BatchNorm-gradient and 5
-                        # split data-gradient keys beside the loss, score and NMS buffers: two batch sizes fit
+CACHE_CAPACITY = 96     # entries.  One YOLOv3 backbone step at one batch size holds 23 weight-gradient, 16 BatchNorm-gradient, 5
+                        # split data-gradient and 5 split weight-gradient keys beside the loss, score and NMS buffers: two batch sizes fit
 
 
 class LruCache:

@@ -570,6 +570,38 @@ int rtod_conv_dgrad_split_phases(const float* w_oihw_dev, const double* row_scal
     RTOD_GUARD_END
 }
 
+int rtod_conv_wgrad_split_schedule(int batch, int cout, int cin, int height, int width, int size, int* tiles, int* slices, int* slice_len, int64_t* k_padded) {
+    RTOD_GUARD_BEGIN
+    return conv_wgrad_split_schedule(batch, cout, cin, height, width, size, tiles, slices, slice_len, k_padded);
+    RTOD_GUARD_END
+}
+
+int rtod_conv_wgrad_split_bounds(int batch, int cout, int cin, int height, int width, int size, int64_t* lowest, int64_t* highest, int64_t* plane_halves) {
+    RTOD_GUARD_BEGIN
+    return conv_wgrad_split_bounds(batch, cout, cin, height, width, size, lowest, highest, plane_halves);
+    RTOD_GUARD_END
+}
+
+int rtod_conv_wgrad_split_workspace(int batch, int cout, int cin, int height, int width, int size, size_t* bytes) {
+    RTOD_GUARD_BEGIN
+    return conv_wgrad_split_workspace(batch, cout, cin, height, width, size, bytes);
+    RTOD_GUARD_END
+}
+
+int rtod_conv_wgrad_split(const float* dz_dev, const float* x_dev, int batch, int cout, int cin, int height, int width, int size,
+                          const double* row_scale_dev, float* dw_dev, void* workspace, size_t workspace_bytes, void* stream) {
+    RTOD_GUARD_BEGIN
+    return launch_conv_wgrad_split(dz_dev, x_dev, batch, cout, cin, height, width, size, row_scale_dev, dw_dev, workspace, workspace_bytes, (hipStream_t)stream);
+    RTOD_GUARD_END
+}
+
+int rtod_conv_wgrad_split_phases(const float* dz_dev, const float* x_dev, int batch, int cout, int cin, int height, int width, int size,
+                                 const double* row_scale_dev, float* dw_dev, void* workspace, size_t workspace_bytes, void* stream, int phases) {
+    RTOD_GUARD_BEGIN
+    return launch_conv_wgrad_split(dz_dev, x_dev, batch, cout, cin, height, width, size, row_scale_dev, dw_dev, workspace, workspace_bytes, (hipStream_t)stream, phases);
+    RTOD_GUARD_END
+}
+
 int rtod_bn_grad_parts(int batch, int channels, int pixels, int* parts, int* part_len) { return bn_grad_parts(batch, channels, pixels, parts, part_len); }
 
 int rtod_bn_grad_workspace(int batch, int channels, int pixels, size_t* bytes) { return bn_grad_workspace(batch, channels, pixels, bytes); }

@@ -411,6 +411,15 @@ int launch_conv_dgrad_split(const float* w, const double* row_scale, const float
                             int h, int w_, int size, int tile, float* dx, void* workspace, size_t workspace_bytes, hipStream_t s, int phases = 31);
 // ... `phases` (rtod_conv_dgrad_split_phases: measurement): which kernel groups of the call are enqueued, on a workspace a full call has filled
 enum { DGS_AMAX = 1, DGS_SPLIT = 2, DGS_PACK = 4, DGS_CONV = 8, DGS_FINISH = 16, DGS_ALL = 31 };
+// weight gradient of a stride-1 1x1 / 3x3 BatchNorm conv (cin % 32 == 0, no db) as three f16 MFMA products (wgrad_split.hip): one exponent per
+// tensor, dz and x split into f16 hi / lo planes on a common padded k grid, a tile of dW x all taps per workgroup, K slices added in order
+int conv_wgrad_split_schedule(int batch, int cout, int cin, int h, int w, int size, int* tiles, int* slices, int* slice_len, int64_t* k_padded);
+int conv_wgrad_split_bounds(int batch, int cout, int cin, int h, int w, int size, int64_t* lowest, int64_t* highest, int64_t* plane_halves);
+int conv_wgrad_split_workspace(int batch, int cout, int cin, int h, int w, int size, size_t* bytes);
+int launch_conv_wgrad_split(const float* dz, const float* x, int batch, int cout, int cin, int h, int w, int size, const double* row_scale,
+                            float* dw, void* workspace, size_t workspace_bytes, hipStream_t s, int phases = 15);
+// ... `phases` (rtod_conv_wgrad_split_phases: measurement): which kernel groups of the call are enqueued, on a workspace a full call has filled
+enum { WGS_EXPONENTS = 1, WGS_SPLIT = 2, WGS_GEMM = 4, WGS_REDUCE = 8, WGS_ALL = 15 };
 // out = m(y) * (((c0 + c1) + c2) + c3): the fan-out sum of the gradient walk, 1 to 4 contributions, in one launch (grad_join.hip)
 int launch_grad_join(const float* const* contributions, int count, const float* y, float slope, int64_t n, float* out, hipStream_t s);
 // backward of the 2x upsample (bilinear align_corners=False, or nearest) in gather form, the producing conv's mask fused (upsample_grad.hip)

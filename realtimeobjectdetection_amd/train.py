@@ -346,6 +346,51 @@ def conv_dgrad_split_async(w, dz, size, row_scale=None, y=None, slope=1.0, tile=
     return dx
 
 
+WGRAD_PRECISIONS = ("fp32", "f16s3")     # DarknetTrainer(wgrad_precision=...): the exact weight gradients, or the split-f16 ones where the walk sends the conv there
+# ... which is the stride-1 3x3 BatchNorm convs the entry takes.  Settled by tools/exp_wgrad_split.py (profiles/experiments/wgrad_split_cost.log): a size stays only
+# if its summed split time is below its summed exact time on YOLOv3 416x416 batch 8.  Its 32 3x3 layers take 9136.2 us exact and 5087.6 us through the split entry;
+# its 34 1x1 layers take 2739.7 us exact and 2790.5 us split (on YOLOv3-tiny 47.3 against 71.8 us): two planes written and read back around one tap's worth of
+# MFMAs, so the 1x1 convs stay on the exact entry.  The ENTRY takes them and the tests cover them
+WGRAD_SPLIT_SIZES = (3,)
+
+
+def conv_wgrad_split_takes(cin, size, stride=1):
+    """Does rtod_conv_wgrad_split take a conv of that shape?  Stride 1, size 1 or 3, ``Cin`` a positive multiple of 32."""
+    return stride == 1 and size in (1, 3) and cin >= 32 and cin % 32 == 0
+
+
+def conv_wgrad_split_schedule(batch, cout, cin, height, width, size):
+    """``(tiles, slices, slice_len, k_padded)`` of rtod_conv_wgrad_split for that shape (rtod_conv_wgrad_split_schedule; no device)."""
+    t, s, n, k = C.c_int(), C.c_int(), C.c_int(), C.c_int64()
+    _ffi.check(_ffi.lib().rtod_conv_wgrad_split_schedule(int(batch), int(cout), int(cin), int(height), int(width), int(size), C.byref(t), C.byref(s), C.byref(n), C.byref(k)))
+    return t.value, s.value, n.value, k.value
+
+
+def conv_wgrad_split_async(dz, x, size, row_scale=None, phases=None):
+    """Enqueue rtod_conv_wgrad_split: the operands of ``conv_wgrad_async`` (stride 1, no bias gradient, ``Cin`` a multiple of 32) ->
+    ``dW [Cout,Cin,size,size]`` summed as three f16 MFMA products: ``dz`` and ``x`` scaled by ONE power of two per tensor and split
+    into f16 hi / lo planes on a common padded k grid, hi*hi + hi*lo + lo*hi in fp32 accumulators, K slices added in ascending
+    order, then ``2^-(e_z + e_x) * row_scale[o]`` once in double.  The workspace is cached per shape; nothing synchronises.
+    ``phases`` (measurement only, rtod_conv_wgrad_split_phases): a sum of 1, 2, 4, 8 naming the kernel groups to enqueue on the
+    workspace a full call has filled."""
+    who = "conv_wgrad_split"
+    _need_cuda(dz, who)
+    _need_cuda(x, who)
+    ok = dz.dim() == 4 and x.dim() == 4 and dz.size(0) == x.size(0) and dz.dtype == torch.float32 and x.dtype == torch.float32 and tuple(dz.shape[2:]) == tuple(x.shape[2:])
+    if not ok:
+        raise ValueError("%s: expected float32 dz [B,Cout,H,W] and x [B,Cin,H,W], got %s and %s" % (who, tuple(dz.shape), tuple(x.shape)))
+    dz, x = dz.contiguous(), x.contiguous()
+    B, cout, cin, H, W = dz.size(0), dz.size(1), x.size(1), x.size(2), x.size(3)
+    shape = (B, cout, cin, H, W, int(size))
+    dev = dz.device
+    scale = _scale_ptr(row_scale, cout, dev)
+    ws = _ffi.workspace("rtod_conv_wgrad_split", dev, *shape)         # a refused shape raises here: nothing is launched
+    dw = torch.empty((cout, cin, int(size), int(size)), dtype=torch.float32, device=dev)
+    _ffi.enqueue("rtod_conv_wgrad_split" if phases is None else "rtod_conv_wgrad_split_phases", dev, dz, x, *shape, scale, dw, *ws,
+                 after=() if phases is None else (int(phases),))
+    return dw
+
+
 def maxpool_grad_async(dz, x, slope=1.0, size=2, stride=2):
     """Enqueue rtod_maxpool_grad: ``dz`` on the pool's output map ([B,C,H//2,W//2] for ``stride`` 2, [B,C,H,W] for the clamped
     ``stride`` 1 pool) and ``x`` [B,C,H,W], the pool's stored input -> ``dx`` [B,C,H,W]: every window's gradient goes to its first
@@ -587,11 +632,15 @@ class DarknetTrainer:
     was skipped; OR-ed by every call, read it when you synchronise anyway), ``last_components`` (device float64 [6] of the
     last loss: total, xy, wh, obj, noobj, cls)."""
 
-    def __init__(self, model, resolution=None, num_classes=None, trainable="heads", grad_precision="fp32"):
+    def __init__(self, model, resolution=None, num_classes=None, trainable="heads", grad_precision="fp32", wgrad_precision="fp32"):
         if trainable not in ("heads", "blocks", "neck", "backbone", "full"):
             raise ValueError("DarknetTrainer: trainable must be 'heads', 'blocks', 'neck', 'backbone' or 'full', got %r" % (trainable,))
         if grad_precision not in GRAD_PRECISIONS:
             raise ValueError("DarknetTrainer: grad_precision must be 'fp32' or 'f16s3', got %r" % (grad_precision,))
+        if wgrad_precision not in WGRAD_PRECISIONS:
+            raise ValueError("DarknetTrainer: wgrad_precision must be 'fp32' or 'f16s3', got %r" % (wgrad_precision,))
+        self.wgrad_precision = wgrad_precision  # "f16s3": _walk sends dW of every stride-1 BatchNorm conv with a size in WGRAD_SPLIT_SIZES and Cin % 32 == 0 through
+                                           # conv_wgrad_split_async; head convs, stride 2 and thin convs stay exact.  Independent of grad_precision
         self.grad_precision = grad_precision   # "f16s3": _walk sends the data gradient of every stride-1 3x3 conv with Cin % 32 == 0 through
                                            # conv_dgrad_split_async; 1x1 convs (GRAD_SPLIT_SIZES), stride 2, thin convs, weight gradients, BatchNorm and joins stay exact
         self.trainable = trainable         # "blocks": feed_forward_through_model also trains the BatchNorm conv in front of each head conv;
@@ -948,7 +997,9 @@ class DarknetTrainer:
                 if bn_grads is not None and not head:                 # du -> dz through the BatchNorm of the batch
                     dz, dgamma, dbeta = bn_grad_async(dz, model.read_bn_input(i, B), *model.bn_stats_dev(i), masters[i][2])
                     bn_grads[i] = (dgamma, dbeta)
-                if not head:
+                if not head and self.wgrad_precision == "f16s3" and L.stride == 1 and L.size in WGRAD_SPLIT_SIZES and conv_wgrad_split_takes(L.cin, L.size):
+                    grads[i] = conv_wgrad_split_async(dz, read(i - 1), L.size, row_scale=scale)
+                elif not head:
                     grads[i] = conv_wgrad_async(dz, read(i - 1), L.size, row_scale=scale, stride=L.stride)[0]
                 if i > 0:
                     hw = (layers[i - 1].hout, layers[i - 1].wout)
